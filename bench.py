@@ -15,8 +15,13 @@ halo), so that its match tables are those of the single-GPU run (src/track.cpp:1
 and the maps are merged inside the step by ssm_voxel_allgather: ONE RCCL all-gather behind the C ABI, no torch on the data path
 (torch.distributed only ships the ncclUniqueId and provides the barrier / max of the timing contract).
 
-Prints ONE JSON line on rank 0.  cpu_baseline = the CPU oracle (oracle/, kind "port") timed on a bounded sample of
-the same stream on the host cores of this box (rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`, `ms_per_step`); everything
+else -- the serialised per-stage pass behind `roofline`, the PCIe-inclusive rate, the CPU baselines, the merge self-validation and, with no mode flag,
+the configs[2] / configs[3] / closed-pose-loop / exp_mapping legs (`other_configs`) -- runs only with --full.  cpu_baseline (--full) = the CPU oracle
+(oracle/, kind "port") timed on a bounded sample of the same stream on the host cores of this box (rank 0, N=1 only).
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64, a fixed seeded sample of the frames
+where the whole output would be too large (DUMP_LIMIT_BYTES in all); the inputs are seeded, so two builds can be compared array for array.
 """
 import argparse
 import json
@@ -195,27 +200,44 @@ def stereo_main(args):
     dt = time.perf_counter() - t0
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=torch.device("cuda", local_rank)); dist.all_reduce(t, op=dist.ReduceOp.MAX); dt = float(t.item())
-    # undisturbed stage durations: the same steps with SGBM on the chain's stream (profiling mode 2)
+    res = ctx.stereo_seq_fetch(out, F, Wd, Hd, (1 | 2 | 4) if args.dump_outputs else (1 | 4))     # the last timed step's outputs
+    # undisturbed stage durations (--full): the same steps with SGBM on the chain's stream (profiling mode 2)
     stage_acc = {k: list(v) for k, v in stage_ovl.items()} if args.serial_only else {}
     ctx.set_profiling(2)
-    for _ in range(0 if args.serial_only else max(1, min(args.steps, 3))):
+    for _ in range(0 if args.serial_only or not args.full else max(1, min(args.steps, 3))):
         step()
         for k, (ms, ln) in ctx.stage_times().items():
             a = stage_acc.setdefault(k, [0.0, 0]); a[0] += ms; a[1] += ln
     ctx.set_profiling(0)
-    res = ctx.stereo_seq_fetch(out, F, Wd, Hd, 1 | 4)
     if rank != 0:
         ctx.close()
         return None
-    nser = args.steps if args.serial_only else max(1, min(args.steps, 3))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, stereo_outputs(res))
     frames = world * F * args.steps
-    sg_ms_launch = stage_acc["sgbm"][0] / max(stage_acc["sgbm"][1], 1)
-    fpl = F * nser / max(stage_acc["sgbm"][1], 1)            # frame pairs per SGBM launch group
-    vol = (Wd - D) * Hd * D
-    alg = 6 * vol * 2 * fpl                                 # u16 cost volume: written once, read once by each of the 5 scan directions
-    ach = alg / (sg_ms_launch * 1e-3) / 1e9
+    roofline = None
+    if args.full:
+        nser = args.steps if args.serial_only else max(1, min(args.steps, 3))
+        sg_ms_launch = stage_acc["sgbm"][0] / max(stage_acc["sgbm"][1], 1)
+        fpl = F * nser / max(stage_acc["sgbm"][1], 1)            # frame pairs per SGBM launch group
+        vol = (Wd - D) * Hd * D
+        alg = 6 * vol * 2 * fpl                                 # u16 cost volume: written once, read once by each of the 5 scan directions
+        ach = alg / (sg_ms_launch * 1e-3) / 1e9
+        traffic = None
+        try:        # HBM bytes of the SGBM kernels per launch from the committed PMC passes (profiles/rNN_stereo_traffic.json: FETCH_SIZE x 2 + WRITE_SIZE)
+            tpath, twhy = traffic_profile("stereo_traffic.json", "kernels_sgbm.hip")
+            kk = json.load(open(tpath))["kernels"]
+            traffic = round(sum(v["total_bytes_per_frame"] for name, v in kk.items() if name.startswith("sgbm_")) * fpl)
+        except Exception:
+            pass
+        roofline = {"bound": "hbm", "kernel": "sgbm (prefilter .. wta, median, speckle, depth: all kernels of the SGBM stage)", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic,
+                    "traffic_source": traffic_profile("stereo_traffic.json", "kernels_sgbm.hip")[1] if traffic is None else os.path.relpath(latest_profile("stereo_traffic.json"), ROOT) + " (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not measured in this run)",
+                    "algorithmic_bytes_per_launch": round(alg),
+                    "stages_ms_per_frame": {k: round(v[0] / (F * nser), 4) for k, v in stage_acc.items()},
+                    "stages_ms_per_frame_overlapped": {k: round(v[0] / (F * args.steps), 4) for k, v in stage_ovl.items()}}
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if world == 1 and args.full and not args.no_cpu:
         from oracle.binding import Oracle                   # the checker, here only as the timed CPU baseline
         orc = Oracle()
         t1 = time.perf_counter(); ref = orc.sgbm(L[1], R[1], orc.sgbm_params()); orc.disparity_to_depth(ref, **KITTI); tc = time.perf_counter() - t1
@@ -224,13 +246,6 @@ def stereo_main(args):
                "sample": "one frame pair of the same sequence: oracle/ quad matcher + SGBM + depth conversion (C, 1 thread); the VO is below a millisecond",
                "ms_per_frame": {"sgbm": round(tc * 1e3, 2), "quad_track": round(tq * 1e3, 2)},
                "quad_matches_equal_gpu": bool(int(res["nquad"][1]) == len(qm) and res["quad"][1, :len(qm)].tobytes() == qm.tobytes())}
-    traffic = None
-    try:        # HBM bytes of the SGBM kernels per launch from the committed PMC passes (profiles/rNN_stereo_traffic.json: FETCH_SIZE x 2 + WRITE_SIZE)
-        tpath, twhy = traffic_profile("stereo_traffic.json", "kernels_sgbm.hip")
-        kk = json.load(open(tpath))["kernels"]
-        traffic = round(sum(v["total_bytes_per_frame"] for name, v in kk.items() if name.startswith("sgbm_")) * fpl)
-    except Exception:
-        pass
     nq = res["nquad"][1:]
     line = {"metric": "frame pairs/sec stereo front end (quad matcher + SGBM depth + stereo VO), 1241x376 rectified stereo", "value": round(frames / dt, 2), "unit": "frame pairs/s",
             "n_gpus": world, "steps": args.steps,
@@ -241,13 +256,7 @@ def stereo_main(args):
                                    "hypotheses); %d frame pairs resident in HBM per step, ssm_stereo_seq_process" % F,
                        "frame_pairs_per_gpu": F, "frame_pairs_per_launch": B, "parallelism": "replicas" if world > 1 else "single GPU"},
             "per_frame": {"quad_matches": round(float(nq.mean()), 1), "vo_success_rate": round(float(res["vo_result"][1:, 1].mean()), 3)},
-            "roofline": {"bound": "hbm", "kernel": "sgbm (prefilter .. wta, median, speckle, depth: all kernels of the SGBM stage)", "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_profile("stereo_traffic.json", "kernels_sgbm.hip")[1] if traffic is None else os.path.relpath(latest_profile("stereo_traffic.json"), ROOT) + " (committed rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command, not measured in this run)",
-                         "algorithmic_bytes_per_launch": round(alg),
-                         "stages_ms_per_frame": {k: round(v[0] / (F * nser), 4) for k, v in stage_acc.items()},
-                         "stages_ms_per_frame_overlapped": {k: round(v[0] / (F * args.steps), 4) for k, v in stage_ovl.items()}},
-            "cpu_baseline": cpu}
+            "roofline": roofline, "cpu_baseline": cpu}
     for p in (dl, dr, ds):
         ctx.dev_free(p)
     ctx.close()
@@ -338,6 +347,88 @@ def cpu_all_cores(orc, frames_per_thread, leaf):
             "sample": f"{cores} threads x {frames_per_thread} consecutive frames each (blocks of the same stream, synth included: {dt:.1f} s wall)"}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SEED = 0x5EED0D
+
+
+def dump_sample(n, k):
+    """the frames a dump keeps: k of n, drawn with a fixed seed (the same n gives the same frames in every run), in stream order"""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, k), replace=False))
+
+
+def valid_rows(a, counts):
+    """a[i, :counts[i]] kept, the rest of row i zeroed (slots past a frame's count hold whatever the device buffer held), as float32"""
+    import numpy as np
+    a = np.asarray(a, dtype=np.float32)
+    keep = np.arange(a.shape[1])[None, :] < np.maximum(np.asarray(counts), 0).reshape(-1, 1)
+    return np.where(keep.reshape(keep.shape + (1,) * (a.ndim - 2)), a, np.float32(0))
+
+
+def record_columns(a):
+    """a structured array as float32 columns, field by field (its integer fields are small: exact in float32)"""
+    import numpy as np
+    return np.stack([a[f].astype(np.float32) for f in a.dtype.names], axis=-1)
+
+
+def split_int64(a):
+    """64-bit integers as (high 32 bits, low 32 bits) float64 columns: exact, unlike one float64"""
+    import numpy as np
+    u = np.ascontiguousarray(a).view(np.uint64)
+    return np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def write_outputs(path, arrays):
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def rgbd_outputs(res, table, R):
+    """what ssm_seq_process + the map export of a step return: per-frame counts of every frame; keypoints, descriptors, 3-D positions and match
+    lists of 32 seeded frames; the sorted voxel table (a seeded sample of 65536 rows when the map is larger)"""
+    import numpy as np
+    from semantic_slam_mapping_amd.api import VOXEL_DTYPE
+    F = len(res["nkp"])
+    idx = dump_sample(F, 32)
+    nkp = res["nkp"][idx]
+    nm = res["nmatch"][idx]
+    vox = np.frombuffer(table, dtype=VOXEL_DTYPE)
+    if len(vox) > 65536:
+        vox = vox[dump_sample(len(vox), 65536)]
+    ints = [split_int64(vox[f]) for f in ("key", "sx", "sy", "sz", "sr", "sg", "sb", "n")]
+    voxels = np.concatenate(ints + [vox["hist"].astype(np.float64)], axis=1)
+    return {
+        "nkp": res["nkp"].astype(np.float64), "npoints": res["npoints"].astype(np.float64), "nmatch": res["nmatch"].astype(np.float64),
+        "sample_frames": idx.astype(np.float64),
+        "keypoints": valid_rows(record_columns(res["kps"][idx]), nkp),
+        "descriptors": valid_rows(res["desc"][idx], nkp),
+        "pos3d": valid_rows(res["pos3d"][idx], nkp),
+        "matches": np.stack([valid_rows(record_columns(res["matches"][idx, r]), nm[:, r]) for r in range(R)], axis=1),
+        "voxels": voxels,
+    }
+
+
+def stereo_outputs(res):
+    """what ssm_stereo_seq_process returns: counts, motions and VO results of every frame pair; quad matches, corners, VO inliers, disparity and
+    depth of 4 seeded frame pairs"""
+    import numpy as np
+    idx = dump_sample(len(res["nquad"]), 4)
+    return {
+        "nquad": res["nquad"].astype(np.float64), "ncorners": res["ncorners"].astype(np.float64), "tr": res["tr"].astype(np.float64),
+        "vo_result": res["vo_result"].astype(np.float64), "sample_frames": idx.astype(np.float64),
+        "quad": valid_rows(record_columns(res["quad"][idx]), res["nquad"][idx]),
+        "corners": valid_rows(res["corners"][idx], res["ncorners"][idx]),
+        "inliers": valid_rows(res["inliers"][idx], res["vo_result"][idx, 0]),
+        "disparity": res["disp"][idx].astype(np.float32), "depth": res["depth"][idx].astype(np.float32),
+    }
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -372,7 +463,15 @@ def parse_args(argv=None):
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false", help="default run (N = 1, no mode flag): skip the short configs[2] / configs[3] / "
                     "closed-pose-loop legs that are reported as `other_configs` beside the configs[1] headline")
     ap.add_argument("--other-scale", type=float, default=1.0, help="size factor of the `other_configs` legs (tests: 0.1 with a short headline; 1.0 = 256 SegNet frames, 256 stereo pairs, 400 pose frames)")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the serialised pass of `roofline`, the PCIe-inclusive rate, the CPU "
+                    "baselines, the merge self-validation and, with no mode flag, the `other_configs` legs (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (float32 / float64; "
+                    "a fixed seeded sample of the frames where the whole output is larger)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     args.pose_cpu_sample = 0
     return args
 
@@ -481,13 +580,15 @@ def rgbd_main(args):
     dt = time.perf_counter() - t0
     for k, (ms, ln) in ctx.stage_times().items():      # the last step's brackets, scaled to the K steps (the steps are identical)
         stage_ovl[k] = [ms * args.steps, ln * args.steps]
-    # ---- kernel durations for the roofline: the same K steps with every stage serialised on one stream (profiling mode 2),
+    res = ctx.seq_fetch(out, F)                        # the last timed step's outputs (the passes below overwrite the device buffers)
+    table = tab_buf[: n_vox * sharding.VOXEL_BYTES].cpu().numpy().tobytes() if args.dump_outputs and rank == 0 else None
+    # ---- kernel durations for the roofline (--full): the same K steps with every stage serialised on one stream (profiling mode 2),
     # so that a stage's hipEvent bracket is that kernel alone (this is also what profiles/*_kernel_stats.md lists)
     ctx.set_profiling(2)
     stage_acc = {}
     if args.serial_only:                               # the timed region already ran serialised: every launch of the process is of that kind
         stage_acc = {k: list(v) for k, v in stage_ovl.items()}
-    for _ in range(0 if args.serial_only else args.steps):
+    for _ in range(0 if args.serial_only or not args.full else args.steps):
         step()
         for k, (ms, ln) in ctx.stage_times().items():
             a = stage_acc.setdefault(k, [0.0, 0])
@@ -497,7 +598,7 @@ def rgbd_main(args):
     # ---- PCIe-inclusive rate (reported beside `value`, never as `value`): the same steps with the frames copied from pinned
     # host memory to the device inside the timed region (bgr + depth + labels + pose = 2.46 MB per frame), copy and compute overlapped
     h2d_fps = None
-    if world == 1 and not args.segnet and not args.serial_only and os.environ.get("SSM_BENCH_H2D", "1") == "1":
+    if world == 1 and args.full and not args.segnet and not args.serial_only and os.environ.get("SSM_BENCH_H2D", "1") == "1":
         try:
             hbuf = [t.cpu().pin_memory() for t in (bgr, dep, sem, pose)]
             torch.cuda.synchronize()
@@ -529,13 +630,12 @@ def rgbd_main(args):
             del hbuf
         except Exception:
             h2d_fps = None
-    # ---- self-validation of the merge (N > 1, or the 1-rank communicator of SSM_FORCE_MERGE): one more, untimed step in which every rank reads its
+    # ---- self-validation of the merge (--full; N > 1, or the 1-rank communicator of SSM_FORCE_MERGE): one more, untimed step in which every rank reads its
     # local voxel count before the all-gather, then hashes the merged table it exports; the hashes must agree on every rank.  With --verify-whole
     # (default for strong scaling, where the stream is one) rank 0 also rebuilds the map of the WHOLE stream by itself (map stage only, block by
     # block through its own buffers) and compares the tables byte for byte: merged == single-GPU.
-    res = ctx.seq_fetch(out, F)                  # the last timed / serialised step's outputs (the validation below overwrites the device buffers)
     merge_info = None
-    if world > 1 or force_merge:
+    if (world > 1 or force_merge) and args.full:
         ctx.map_clear()
         if HN:
             ctx.seq_process(hb[0].data_ptr(), None, None, None, HN, stages=ssm.api.STAGE_ORB)
@@ -679,62 +779,64 @@ def rgbd_main(args):
         frames_total = frames_all * args.steps        # frames of all ranks (rank 0's stage breakdown below is per ITS frames)
         value = frames_total / dt
         P = P_total / F; nkp = kp_total / F
-        # dominant kernel and its roofline
-        per_stage = {k: (v[0] / max(v[1], 1), v[0] / args.steps / F * 1e3) for k, v in stage_acc.items()}   # ms/launch-group, us/frame
-        nb = -(-F // args.batch)
-        dom = max(stage_acc, key=lambda k: stage_acc[k][0])
-        launches_per_step = stage_acc[dom][1] / args.steps
-        ms_per_launch = stage_acc[dom][0] / max(stage_acc[dom][1], 1)
-        frames_per_launch = F / launches_per_step
-        if dom == "segnet":
-            from semantic_slam_mapping_amd import segnet_model
-            tf = segnet_model.flops() * frames_per_launch / (ms_per_launch * 1e-3) / 1e12
-            roof = {"bound": "mfma", "kernel": "conv3x3_dma2_kernel + conv3x3_first_kernel (26 conv layers with fused pool / un-pool / ArgMax, prep, colouring: whole SegNet stage)", "achieved": round(tf, 1), "peak": 2500.0,
-                    "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4), "traffic": measured_traffic("segnet", frames_per_launch, "segnet_traffic.json")}
-            if roof["traffic"] is None:
-                roof["traffic_source"] = traffic_profile("segnet_traffic.json", "kernels_segnet.hip")[1]
+        roof = None
+        if args.full:
+            # dominant kernel and its roofline
+            per_stage = {k: (v[0] / max(v[1], 1), v[0] / args.steps / F * 1e3) for k, v in stage_acc.items()}   # ms/launch-group, us/frame
+            nb = -(-F // args.batch)
+            dom = max(stage_acc, key=lambda k: stage_acc[k][0])
+            launches_per_step = stage_acc[dom][1] / args.steps
+            ms_per_launch = stage_acc[dom][0] / max(stage_acc[dom][1], 1)
+            frames_per_launch = F / launches_per_step
+            if dom == "segnet":
+                from semantic_slam_mapping_amd import segnet_model
+                tf = segnet_model.flops() * frames_per_launch / (ms_per_launch * 1e-3) / 1e12
+                roof = {"bound": "mfma", "kernel": "conv3x3_dma2_kernel + conv3x3_first_kernel (26 conv layers with fused pool / un-pool / ArgMax, prep, colouring: whole SegNet stage)", "achieved": round(tf, 1), "peak": 2500.0,
+                        "unit": "TFLOP/s", "frac": round(tf / 2500.0, 4), "traffic": measured_traffic("segnet", frames_per_launch, "segnet_traffic.json")}
+                if roof["traffic"] is None:
+                    roof["traffic_source"] = traffic_profile("segnet_traffic.json", "kernels_segnet.hip")[1]
+                else:
+                    roof["traffic_source"] = os.path.relpath(latest_profile("segnet_traffic.json"), ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --segnet`, scripts/collect_profiles.sh pmc_segnet; per frame x frames per launch group, not measured in this run)"
+            elif dom == "match":
+                # K6 runs on the matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4 on descriptors expanded to +-1 FP4 elements): 2 x 256 operations per
+                # descriptor pair, against the dense FP4 peak (4 x the bf16 rate: MI355X_MICROARCH.md, Matrix cores)
+                pairs = sum(int(res["nkp"][max(f - R + r, 0)]) * int(res["nkp"][f]) for f in range(F) for r in range(R) if m[f, r] >= 0) / F
+                tops = pairs * 512 * frames_per_launch / (ms_per_launch * 1e-3) / 1e12
+                roof = {"bound": "mfma", "kernel": "match_mfma_kernel (+ match_expand_kernel, match_compact_kernel)", "achieved": round(tops, 1), "peak": 10000.0, "unit": "TOP/s (fp4)",
+                        "frac": round(tops / 10000.0, 4), "traffic": measured_traffic(dom, frames_per_launch),
+                        "note": "Hamming distance matrix as an exact FP4 matrix product; algorithmic operations only (the padding of 1000 descriptors to 1024 is not counted); "
+                                "the kernel's longer side is the VALU top-2 tracking of the distance tiles: DESIGN.md s.4.1",
+                        "descriptor_pairs_per_frame": round(pairs)}
             else:
-                roof["traffic_source"] = os.path.relpath(latest_profile("segnet_traffic.json"), ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of `bench.py --segnet`, scripts/collect_profiles.sh pmc_segnet; per frame x frames per launch group, not measured in this run)"
-        elif dom == "match":
-            # K6 runs on the matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4 on descriptors expanded to +-1 FP4 elements): 2 x 256 operations per
-            # descriptor pair, against the dense FP4 peak (4 x the bf16 rate: MI355X_MICROARCH.md, Matrix cores)
-            pairs = sum(int(res["nkp"][max(f - R + r, 0)]) * int(res["nkp"][f]) for f in range(F) for r in range(R) if m[f, r] >= 0) / F
-            tops = pairs * 512 * frames_per_launch / (ms_per_launch * 1e-3) / 1e12
-            roof = {"bound": "mfma", "kernel": "match_mfma_kernel (+ match_expand_kernel, match_compact_kernel)", "achieved": round(tops, 1), "peak": 10000.0, "unit": "TOP/s (fp4)",
-                    "frac": round(tops / 10000.0, 4), "traffic": measured_traffic(dom, frames_per_launch),
-                    "note": "Hamming distance matrix as an exact FP4 matrix product; algorithmic operations only (the padding of 1000 descriptors to 1024 is not counted); "
-                            "the kernel's longer side is the VALU top-2 tracking of the distance tiles: DESIGN.md s.4.1",
-                    "descriptor_pairs_per_frame": round(pairs)}
-        else:
-            gb = algorithmic_bytes(dom, P, nkp) * frames_per_launch / 1e9
-            ach = gb / (ms_per_launch * 1e-3)
-            roof = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": measured_traffic(dom, frames_per_launch),
-                    "algorithmic_bytes_per_launch": round(gb * 1e9),
-                    "note": "integer/byte kernel limited by VALU issue (4 cycles per instruction, profiles/r02_valu_rate.md) and LDS, not HBM: see `valu` and DESIGN.md s.4"}
-        if roof.get("bound") == "hbm":
-            roof["valu"] = measured_valu(dom, per_stage[dom][1])      # what actually bounds the integer stages
-        try:    # the whole pipeline against the VALU issue ceiling: every kernel's wave-instructions per frame (committed SQ pass) x 64 x frames/s
-            kk = json.load(open(latest_profile("sq_counters.json")))["kernels"]
-            wi = sum(v["valu_wave_insts_per_frame"] for name, v in kk.items() if "synth" not in name)
-            if not args.segnet:
-                roof["pipeline_valu"] = {"achieved": round(wi * 64 * value / 1e12, 2), "peak": VALU_LANEOPS_PEAK / 1e12, "unit": "Tlaneop/s",
-                                         "frac": round(wi * 64 * value / VALU_LANEOPS_PEAK, 3), "frac_of_simple_op_peak": round(wi * 64 * value / VALU_SIMPLE_OP_PEAK, 3),
-                                         "wave_insts_per_frame": round(wi),
-                                         "note": "all kernels of a frame (ORB, match, map) at the timed rate `value`, two chains overlapped"}
-        except Exception:
-            pass
-        if roof.get("traffic") is None and "traffic_source" not in roof and dom in ("map_fuse", "voxel_insert"):
-            roof["traffic_source"] = traffic_profile("traffic.json", "kernels_map.hip")[1]      # why there is no figure (a stale or missing counter pass)
-        if roof.get("traffic") is not None and "traffic_source" not in roof:     # `traffic` is NOT measured in this run: it is this kernel's figure from the committed counter passes of the same command
-            roof["traffic_source"] = os.path.relpath(latest_profile("traffic.json"), ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, scripts/collect_profiles.sh pmc; per frame x frames per launch)"
-        roof["stages_us_per_frame"] = {k: round(v[1], 3) for k, v in sorted(per_stage.items(), key=lambda kv: -kv[1][1])}
-        roof["stages_us_per_frame_overlapped"] = {k: round(v[0] / args.steps / F * 1e3, 3) for k, v in sorted(stage_ovl.items(), key=lambda kv: -kv[1][0])}
-        roof["timing"] = ("achieved / stages_us_per_frame: hipEvents around each stage in a second pass of the same K steps with all stages "
-                          "serialised on one stream; value / ms_per_step: the timed region, where the map (and SegNet) stage runs on a second "
-                          "stream beside ORB + match (stages_us_per_frame_overlapped)")
+                gb = algorithmic_bytes(dom, P, nkp) * frames_per_launch / 1e9
+                ach = gb / (ms_per_launch * 1e-3)
+                roof = {"bound": "hbm", "kernel": dom, "achieved": round(ach, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBS, 4), "traffic": measured_traffic(dom, frames_per_launch),
+                        "algorithmic_bytes_per_launch": round(gb * 1e9),
+                        "note": "integer/byte kernel limited by VALU issue (4 cycles per instruction, profiles/r02_valu_rate.md) and LDS, not HBM: see `valu` and DESIGN.md s.4"}
+            if roof.get("bound") == "hbm":
+                roof["valu"] = measured_valu(dom, per_stage[dom][1])      # what actually bounds the integer stages
+            try:    # the whole pipeline against the VALU issue ceiling: every kernel's wave-instructions per frame (committed SQ pass) x 64 x frames/s
+                kk = json.load(open(latest_profile("sq_counters.json")))["kernels"]
+                wi = sum(v["valu_wave_insts_per_frame"] for name, v in kk.items() if "synth" not in name)
+                if not args.segnet:
+                    roof["pipeline_valu"] = {"achieved": round(wi * 64 * value / 1e12, 2), "peak": VALU_LANEOPS_PEAK / 1e12, "unit": "Tlaneop/s",
+                                             "frac": round(wi * 64 * value / VALU_LANEOPS_PEAK, 3), "frac_of_simple_op_peak": round(wi * 64 * value / VALU_SIMPLE_OP_PEAK, 3),
+                                             "wave_insts_per_frame": round(wi),
+                                             "note": "all kernels of a frame (ORB, match, map) at the timed rate `value`, two chains overlapped"}
+            except Exception:
+                pass
+            if roof.get("traffic") is None and "traffic_source" not in roof and dom in ("map_fuse", "voxel_insert"):
+                roof["traffic_source"] = traffic_profile("traffic.json", "kernels_map.hip")[1]      # why there is no figure (a stale or missing counter pass)
+            if roof.get("traffic") is not None and "traffic_source" not in roof:     # `traffic` is NOT measured in this run: it is this kernel's figure from the committed counter passes of the same command
+                roof["traffic_source"] = os.path.relpath(latest_profile("traffic.json"), ROOT) + " (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes, scripts/collect_profiles.sh pmc; per frame x frames per launch)"
+            roof["stages_us_per_frame"] = {k: round(v[1], 3) for k, v in sorted(per_stage.items(), key=lambda kv: -kv[1][1])}
+            roof["stages_us_per_frame_overlapped"] = {k: round(v[0] / args.steps / F * 1e3, 3) for k, v in sorted(stage_ovl.items(), key=lambda kv: -kv[1][0])}
+            roof["timing"] = ("achieved / stages_us_per_frame: hipEvents around each stage in a second pass of the same K steps with all stages "
+                              "serialised on one stream; value / ms_per_step: the timed region, where the map (and SegNet) stage runs on a second "
+                              "stream beside ORB + match (stages_us_per_frame_overlapped)")
         cpu = None
-        if world == 1 and not args.no_cpu and args.cpu_frames > 0:
+        if world == 1 and args.full and not args.no_cpu and args.cpu_frames > 0:
             from oracle.binding import Oracle, build
             try:
                 build(native=True); orc = Oracle(native=True)
@@ -775,6 +877,8 @@ def rgbd_main(args):
         if merge_info is not None:
             line["merge_verified"] = merge_info["verified"]
             line["merge"] = merge_info
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, rgbd_outputs(res, table, R))
     else:
         line = None
     if world > 1 or force_merge:
@@ -927,6 +1031,7 @@ def other_configs(args, head):
         # ---- configs[2]: the SegNet stage in front of the map stage (labels from the network instead of the precomputed masks)
         a = copy.copy(args)
         a.segnet, a.solve_poses, a.frames, a.batch, a.steps, a.warmup = True, False, max(16, int(256 * sc)), max(8, int(128 * sc)), 3, 1
+        a.dump_outputs = None                                  # the dump is the headline's
         a.no_cpu = True                                        # its CPU leg is segnet_cpu_baseline below (the pipeline part is the headline's sample)
         t0 = time.perf_counter()
         try:
@@ -940,6 +1045,7 @@ def other_configs(args, head):
         # ---- configs[3]: the stereo front end on resident 1241 x 376 pairs
         a = copy.copy(args)
         a.stereo, a.frames, a.steps, a.warmup, a.stereo_batch = True, max(8, int(256 * sc)), 3, 1, max(4, min(args.stereo_batch, int(128 * sc)))
+        a.dump_outputs = None
         t0 = time.perf_counter()
         try:
             out["configs[3]"] = sub_line(stereo_main(a), wall_s=round(time.perf_counter() - t0, 1))
@@ -973,8 +1079,8 @@ def main():
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))              # nothing below has run: no torch import, no HIP call in this process
     world = int(os.environ.get("WORLD_SIZE", "1"))
-    # the default run (the command the driver times: N = 1, no mode flag) also carries configs[2], configs[3] and the closed pose loop as `other_configs`
-    default_run = (world == 1 and args.other_configs and (args.frames == 1000 or args.other_scale != 1.0)
+    # the default run with --full (N = 1, no mode flag) also carries configs[2], configs[3], the closed pose loop and exp_mapping as `other_configs`
+    default_run = (args.full and world == 1 and args.other_configs and (args.frames == 1000 or args.other_scale != 1.0)
                    and not (args.stereo or args.segnet or args.solve_poses or args.serial_only or args.total_frames > 0 or os.environ.get("SSM_FORCE_MERGE") == "1"))
     expmap = None
     if default_run and os.environ.get("SSM_BENCH_EXP_MAPPING", "1") != "0":

@@ -11,7 +11,7 @@ using namespace rgbd_tutor;
 int main(int argc, char** argv)
 {
     ParameterReader para(argc > 1 ? argv[1] : "./parameters_test.txt");
-    para.set("keyframe_min_translation", "0.005"); para.set("map_output", "/tmp/ssm_san_threads.pcd");
+    para.set("keyframe_min_translation", "0.005"); para.set("map_output", argc > 2 ? argv[2] : "/tmp/ssm_san_threads.pcd");
     shared_ptr<Tracker> none;
     PoseGraph pg(para, none);
     Mapper mapper(para, pg);

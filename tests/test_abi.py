@@ -53,7 +53,7 @@ def test_product_never_imports_the_oracle():
     assert "oracle" not in out
 
 
-def test_struct_layouts_match_reference_types():
+def test_struct_layouts_match_reference_types(tmp_path):
     import semantic_slam_mapping_amd as ssm
     k, m, p, v = ssm.KEYPOINT_DTYPE, ssm.DMATCH_DTYPE, ssm.POINT_DTYPE, ssm.VOXEL_DTYPE
     assert k.itemsize == 28 and [k.fields[n][1] for n in ("x", "y", "size", "angle", "response", "octave", "class_id")] == [0, 4, 8, 12, 16, 20, 24]   # cv::KeyPoint
@@ -62,7 +62,7 @@ def test_struct_layouts_match_reference_types():
     assert v.itemsize == 112
     # the C compiler agrees
     code = '#include "ssm_hip.h"\n#include <stdio.h>\nint main(){printf("%zu %zu %zu %zu %zu %zu", sizeof(ssm_keypoint), sizeof(ssm_dmatch), sizeof(ssm_point), sizeof(ssm_voxel), sizeof(ssm_camera), sizeof(ssm_config));return 0;}'
-    exe = "/tmp/ssm_layout_check"
+    exe = str(tmp_path / "ssm_layout_check")
     subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), "-x", "c", "-", "-o", exe], input=code, text=True, check=True)
     sizes = subprocess.run([exe], capture_output=True, text=True).stdout.split()
     assert sizes[:5] == ["28", "16", "32", "112", "40"]

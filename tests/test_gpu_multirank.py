@@ -44,7 +44,7 @@ def test_bench_two_ranks_merge_verified():
     """`bench.py --gpus 2`: two ranks of 60 frames each; every rank must export the same merged map (CRC all-gather) and rank 0's own rebuild of the
     whole 120-frame stream must equal it byte for byte"""
     need_two_gpus()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "60", "--batch", "30", "--steps", "1", "--warmup", "0", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "60", "--batch", "30", "--steps", "1", "--warmup", "0", "--no-cpu", "--full"],
                        capture_output=True, text=True, timeout=900, env=dict(os.environ, SSM_RANKS_TIMEOUT="600", SSM_BENCH_H2D="0"))
     print(r.stdout[-3000:], r.stderr[-3000:])
     assert r.returncode == 0
@@ -60,7 +60,7 @@ def test_bench_two_ranks_merge_verified():
 def test_bench_two_ranks_strong_scaling_split():
     """--total-frames: ONE 90-frame stream cut into two contiguous blocks with the matcher halo (configs[4]'s partitioning)"""
     need_two_gpus()
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--total-frames", "90", "--batch", "30", "--steps", "1", "--warmup", "0", "--no-cpu"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--total-frames", "90", "--batch", "30", "--steps", "1", "--warmup", "0", "--no-cpu", "--full"],
                        capture_output=True, text=True, timeout=900, env=dict(os.environ, SSM_RANKS_TIMEOUT="600", SSM_BENCH_H2D="0"))
     print(r.stdout[-3000:], r.stderr[-3000:])
     assert r.returncode == 0

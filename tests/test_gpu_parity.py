@@ -470,7 +470,7 @@ def test_bench_line_and_allgather_path():
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SSM_FORCE_MERGE="1", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29577")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "40", "--batch", "20", "--steps", "2", "--warmup", "1", "--cpu-frames", "3"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "40", "--batch", "20", "--steps", "2", "--warmup", "1", "--cpu-frames", "3", "--full"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -484,11 +484,11 @@ def test_bench_line_and_allgather_path():
 
 
 def test_bench_default_line_carries_the_other_configs():
-    """the command the driver times (`python bench.py`, N = 1, no mode flag) also reports configs[2] (SegNet), configs[3] (stereo) and the closed pose loop as
+    """`python bench.py --full` (N = 1, no mode flag) also reports configs[2] (SegNet), configs[3] (stereo) and the closed pose loop as
     `other_configs`, each with value / ms_per_step / steps / roofline (frac recomputable from achieved / peak) / cpu_baseline.  Run here at a tenth of the size."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "60", "--batch", "30", "--steps", "1", "--warmup", "1", "--cpu-frames", "3", "--other-scale", "0.1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "60", "--batch", "30", "--steps", "1", "--warmup", "1", "--cpu-frames", "3", "--other-scale", "0.1", "--full"],
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -516,6 +516,34 @@ def test_bench_default_line_carries_the_other_configs():
     assert em["map_fnv_equal"] is True and em["pose_fnv_equal"] is True
     assert em["cpu_baseline"]["value"] > 0 and em["cpu_baseline"]["kind"] == "port"
     assert set(("detect_ms", "match_ms", "pnp_ms")) <= set(em["per_call_ms"]) and all(int(v["lost"]) == 0 for v in em["runs"].values())
+
+
+def test_bench_plain_line_and_output_dump(tmp_path):
+    """a plain run (no --full) times --steps steps and prints the headline without the extra passes; --dump-outputs writes the last timed step's
+    outputs as float32 / float64 .npy files, and two runs with the same arguments write the same arrays"""
+    import json, os, subprocess, sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--frames", "40", "--batch", "20", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]))
+    line = lines[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert abs(line["value"] - 40 * 1e3 / line["ms_per_step"]) <= 1e-3 * line["value"] + 0.1
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "other_configs" not in line and line["frames_per_s_including_h2d"] is None
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and {"nkp.npy", "keypoints.npy", "descriptors.npy", "matches.npy", "voxels.npy"} <= set(names)
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype in (np.float32, np.float64) and a.shape == b.shape and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    nkp = np.load(tmp_path / "a" / "nkp.npy")
+    assert len(nkp) == 40 and nkp.min() > 0 and len(np.load(tmp_path / "a" / "voxels.npy")) == line["per_frame"]["voxels_in_map"]
 
 
 def test_full_size_properties_of_configs1(oracle):

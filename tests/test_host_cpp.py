@@ -98,9 +98,9 @@ def test_frame_reader_tum_and_kitti_layouts(tmp_path):
 
 
 @pytest.mark.gpu
-def test_host_classes_on_gpu():
+def test_host_classes_on_gpu(tmp_path):
     subprocess.run(["make", "-C", HOST], check=True, stdout=subprocess.DEVNULL)
-    wfile = "/tmp/ssm_test_segnet.ssmw"
+    wfile = str(tmp_path / "ssm_test_segnet.ssmw")
     subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "export_ssmw.py"), wfile], check=True)
     # the same weights as a .caffemodel: convolution (weight, bias) + caffe-segnet BN (scale, shift) blobs whose folding gives back (scale, shift)
     import numpy as np
@@ -111,7 +111,7 @@ def test_host_classes_on_gpu():
         if name == "conv1_1_D":                     # no BN behind the classifier layer: scale must be 1 there, so fold it into the weights
             layers.append((name, "Convolution", [(w * sc[:, None, None, None]).astype(np.float32), sh])); continue
         layers.append((name, "Convolution", [w, np.zeros(len(sc), np.float32)])); layers.append((name + "_bn", "BN", [sc.reshape(1, -1, 1, 1), sh.reshape(1, -1, 1, 1)]))
-    cfile = "/tmp/ssm_test_segnet.caffemodel"
+    cfile = str(tmp_path / "ssm_test_segnet.caffemodel")
     open(cfile, "wb").write(cm.encode_caffemodel(layers))
     # conv1_1_D of the .ssmw twin gets the same folded weights, so that both files describe the same network bit for bit
     ws = make_weights(1234); w, sc, sh = ws[-1]; ws[-1] = ((w * sc[:, None, None, None]).astype(np.float32), np.ones_like(sc), sh)
@@ -325,5 +325,5 @@ def test_sanitizer_builds_of_oracle_and_host_layer(tmp_path):
         r = subprocess.run(["make", "-s", "-C", ORACLE, f"SAN={san}", "san"], capture_output=True, text=True, timeout=600)
         assert r.returncode == 0 and "san_check OK" in r.stdout and "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stdout[-800:] + r.stderr[-2000:]
     subprocess.run(["make", "-s", "-C", HOST, "SAN=tsan", "test_threads_tsan"], check=True, capture_output=True, timeout=600)
-    r = subprocess.run([os.path.join(HOST, "test_threads_tsan"), os.path.join(HOST, "parameters_test.txt")], capture_output=True, text=True, timeout=300)
+    r = subprocess.run([os.path.join(HOST, "test_threads_tsan"), os.path.join(HOST, "parameters_test.txt"), str(tmp_path / "threads.pcd")], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ALL PASSED" in r.stdout and "ThreadSanitizer" not in r.stderr, r.stdout[-500:] + r.stderr[-3000:]
