@@ -420,6 +420,15 @@ class Context:
         self._chk(self.lib.ssm_segnet_debug_op(self.h, 4, layer, _ptr(xin), h, w, _ptr(out), _ptr(cin_code)))
         return out[:, :, :cout]
 
+    def segnet_debug_conv_argmax(self, layer, x_hwc_f16):
+        """conv + scale / shift of the last layer with the class ArgMax in its epilogue (the kernel ssm_segnet_forward_dev's labels come from): labels [h][w]"""
+        cin, cout, _, _ = self.segnet_layers()[layer]
+        x = np.ascontiguousarray(x_hwc_f16, np.float16); h, w, c = x.shape
+        xin = np.zeros((h, w, (cin + 15) & ~15), np.float16); xin[:, :, :c] = x
+        labels = np.full((h, w), 255, np.uint8); dummy = np.zeros(1, np.float16)
+        self._chk(self.lib.ssm_segnet_debug_op(self.h, 5, layer, _ptr(xin), h, w, _ptr(dummy), _ptr(labels)))
+        return labels
+
     def segnet_debug_pool(self, x_hwc_f16):
         x = np.ascontiguousarray(x_hwc_f16, np.float16); h, w, c = x.shape
         out = np.zeros(((h + 1) // 2, (w + 1) // 2, c), np.float16); code = np.zeros(out.shape, np.uint8)

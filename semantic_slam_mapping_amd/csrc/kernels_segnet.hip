@@ -460,12 +460,20 @@ conv3x3_dma2_kernel(const _Float16* __restrict__ in, const _Float16* __restrict_
                         const float4 sc = *reinterpret_cast<const float4*>(&s_ss[0][c0]), sf = *reinterpret_cast<const float4*>(&s_ss[1][c0]);
                         const float scv[4] = {sc.x, sc.y, sc.z, sc.w}, sfv[4] = {sf.x, sf.y, sf.z, sf.w};
                         bv[g] = (_Float16)-65504.f; bi[g] = 255;
+                        // the logits as conv_epilogue stores them: one fp32 FMA per value, then the packed RNE conversion (v_cvt_pk_f16_f32).  A scalar
+                        // (_Float16)fmaf(..) is folded into v_fma_mixlo_f16, which rounds once, straight to fp16: where the fp32 result sits on an fp16
+                        // midpoint that is one ulp off the stored logit, and the labels left the logits + argmax_kernel path on near ties
+                        typedef float float2v __attribute__((ext_vector_type(2)));
+                        typedef _Float16 half2v __attribute__((ext_vector_type(2)));
 #pragma unroll
-                        for (int q = 0; q < 4; q++) {
-                            float val = __builtin_fmaf(acc[2 * half + tm][0][4 * g + q], scv[q], sfv[q]);
-                            if (RELU) val = fmaxf(val, 0.f);
-                            const _Float16 hvq = (_Float16)val;
-                            if (c0 + q < Cout && (bi[g] == 255 || hvq > bv[g])) { bv[g] = hvq; bi[g] = c0 + q; }
+                        for (int q = 0; q < 4; q += 2) {
+                            float2v val = {__builtin_fmaf(acc[2 * half + tm][0][4 * g + q], scv[q], sfv[q]), __builtin_fmaf(acc[2 * half + tm][0][4 * g + q + 1], scv[q + 1], sfv[q + 1])};
+                            asm volatile("" : "+v"(val));                                 // the fp32 values exist: no fma + fptrunc fold
+                            half2v h2 = __builtin_convertvector(val, half2v);
+                            if (RELU) h2 = __builtin_elementwise_max(h2, (half2v){(_Float16)0, (_Float16)0});
+#pragma unroll
+                            for (int u = 0; u < 2; u++)
+                                if (c0 + q + u < Cout && (bi[g] == 255 || h2[u] > bv[g])) { bv[g] = h2[u]; bi[g] = c0 + q + u; }
                         }
                     }
                     unsigned short vb; memcpy(&vb, &bv[0], 2);

@@ -286,6 +286,19 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
         HIPCHK(c, hipMemcpyAsync(hout.data(), g->actB, hout.size() * 2, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < co16; ch++) out[p * co16 + ch] = hout[((size_t)(ch / 32) * H * W + p) * 32 + ch % 32];
+    } else if (op == 5) {                 // conv + scale/shift of layer `arg` + class ArgMax in the epilogue (the labels path of ssm_segnet_forward_dev), one kernel
+        if (arg < 0 || arg >= SEG_LAYERS || !g->set[arg] || !code || g->cinp[arg] == 8 || k_seg_layers[arg].cout > SEG_NCLS)
+            FAIL(c, SSM_E_INVAL, "layer not set, or not one the fused conv + ArgMax kernel takes");
+        const int ci16 = (k_seg_layers[arg].cin + 15) & ~15;
+        std::vector<uint16_t> hin((size_t)H * W * g->cinp[arg], 0);
+        for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < ci16; ch++) hin[((size_t)(ch / 32) * H * W + p) * 32 + ch % 32] = in[p * ci16 + ch];
+        r = ensure_scratch(c, (size_t)H * W); if (r) return r;
+        uint8_t* dlab = (uint8_t*)c->d_scratch;
+        HIPCHK(c, k_segnet_begin(s));
+        HIPCHK(c, hipMemcpyAsync(g->actA, hin.data(), hin.size() * 2, hipMemcpyHostToDevice, s));
+        HIPCHK(c, k_segnet_conv_argmax(g->actA, g->w[arg], g->scale[arg], g->shift[arg], dlab, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, s));
+        HIPCHK(c, hipMemcpyAsync(code, dlab, (size_t)H * W, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipStreamSynchronize(s));
     } else FAIL(c, SSM_E_INVAL, "unknown op");
     HIPCHK(c, hipStreamSynchronize(s));
     return SSM_OK;

@@ -29,3 +29,109 @@ def forward(x_u8_chw, weights, emulate_fp16=False, threads=None):
             else:
                 x = F.max_unpool2d(x, idx[op[1]], 2, 2, output_size=(op[2], op[3]))
     return x[0].numpy()
+
+
+# ---------------------------------------------------------------- float64 reference of ONE layer and the per-element bound
+# (tests/test_gpu_segnet_precision.py, tests/test_gpu_fuzz.py).  The contract of a conv3x3 + scale / shift (+ ReLU) layer on real-valued data: fp16 operands
+# (inputs as given, weights rounded to fp16 with RNE as ssm_segnet_set_layer does), fp32 accumulation in any order, one fp32 FMA for scale / shift, one
+# IEEE fp16 round-to-nearest-even of the result (subnormals kept, overflow to +-inf), ReLU on every layer but the last.  For the exact value y64 that gives
+#   |got - y64| <= half_ulp16(y64) + d,   d = |scale| K 2^-24 sum|w16||x16| + 2^-24 |y64|,   K = 9 Cin
+# (K 2^-24 sum|w||x|: fp32 accumulation of K terms in any order; 2^-24 |y|: the epilogue FMA).  The bound is loose by design -- it must hold for every
+# summation order -- so the fraction of outputs that equal float16(y64) exactly is checked as well: fp32 accumulation misrounds a small fraction of them,
+# round-toward-zero or a narrower accumulator about half.
+U32 = 2.0 ** -24                  # fp32 unit roundoff
+U16 = 2.0 ** -11                  # fp16 unit roundoff
+F16_INF_AT = 65520.0              # smallest magnitude that RNE takes to inf (65504 + half an ulp)
+
+
+def half_ulp16(a):
+    """half an fp16 ulp at |a|: 2^(e - 11) for |a| in [2^e, 2^(e+1)), 2^-25 in the subnormal range (|a| < 2^-14)"""
+    a = np.abs(np.asarray(a, np.float64))
+    return np.exp2(np.floor(np.log2(np.maximum(a, 2.0 ** -14))) - 11)
+
+
+def conv64(x_hwc, w):
+    """3x3 pad-1 convolution in float64 (torch CPU): x [H][W][Cin], w [Cout][Cin][3][3] -> [H][W][Cout]"""
+    import torch
+    import torch.nn.functional as F
+    xt = torch.from_numpy(np.ascontiguousarray(np.asarray(x_hwc, np.float64).transpose(2, 0, 1)))[None]
+    return F.conv2d(xt, torch.from_numpy(np.ascontiguousarray(w, np.float64)), padding=1)[0].numpy().transpose(1, 2, 0)
+
+
+def wino_allowance(x, w32, w16):
+    """Extra error of the Winograd F(2, 3) kernel (SSM_CONV_WINOGRAD=1) over the direct one, before the scale: it multiplies U = G g (rounded to fp16 from
+    the fp32 weights: |U~ - U| <= 2^-11 (|g0| + |g1| + |g2|) + 2^-25 against U of the fp16 weights) with V = B^T d (fp16 sums of two inputs: |V~ - V| <=
+    2^-11 |V|), and accumulates 3 Cin terms per M_k plus the two sums of the inverse transform in fp32.  With |U| <= G1 = |g0| + |g1| + |g2| and the three
+    |V_k| an output uses summing to at most 2 D4 (D4 = the four inputs d0 .. d3 of its pixel pair's row):
+        |y~ - y| <= (4 2^-11 + 2 (3 Cin + 2) 2^-24) 1.01 sum over (dy, Cin) of (G1 + 2^-13) D4"""
+    import torch
+    import torch.nn.functional as F
+    cin = x.shape[2]
+    g1 = np.maximum(np.abs(w32).astype(np.float64), np.abs(w16)).sum(axis=3, keepdims=True) + 2.0 ** -13     # [Cout][Cin][3][1]
+    xt = torch.from_numpy(np.ascontiguousarray(np.abs(x).transpose(2, 0, 1)))[None]
+    t = F.conv2d(xt, torch.from_numpy(g1), padding=(1, 0))[0].numpy()                     # [Cout][H][W]: sum over (dy, Cin) at each column
+    H, W = t.shape[1:]
+    tp = np.zeros((t.shape[0], H, W + 4)); tp[:, :, 2:W + 2] = t                          # column c of t at c + 2
+    s4 = sum(tp[:, :, 1 + k:1 + k + W:2] for k in range(4))                               # pair j: d0 .. d3 = columns 2j - 1 .. 2j + 2
+    s = np.empty_like(t)
+    s[:, :, 0::2] = s4; s[:, :, 1::2] = s4[:, :, :W // 2]                                   # both pixels of a pair use the same four columns
+    return ((4 * U16 + 2 * (3 * cin + 2) * U32) * 1.01 * s).transpose(1, 2, 0)
+
+
+def wino_active(cin, cout):
+    """the layer runs through the Winograd kernel in this process: SSM_CONV_WINOGRAD set (read as the library reads it) and a plain conv layer with whole
+    32-channel chunks on both sides (ssm_segnet_set_layer packs Winograd weights for those only: layers 1 .. 24)"""
+    import os
+    try:
+        on = int(os.environ.get("SSM_CONV_WINOGRAD", "0") or "0") != 0
+    except ValueError:
+        on = False
+    return on and cin > 8 and cout % 32 == 0
+
+
+def layer_ref(x16, w32, scale, shift, relu, wino=False):
+    """x16: the layer's input [H][W][Cin] (fp16 values), w32 / scale / shift as given to ssm_segnet_set_layer.
+    Returns (y64 [H][W][Cout] after the ReLU, d [H][W][Cout]: the allowance of the bound above)."""
+    x = np.asarray(x16, np.float16).astype(np.float64)
+    w32 = np.asarray(w32, np.float32)
+    w16 = w32.astype(np.float16).astype(np.float64)
+    sc = np.asarray(scale, np.float32).astype(np.float64); sh = np.asarray(shift, np.float32).astype(np.float64)
+    cout, cin = w16.shape[:2]
+    if (x >= 0).all():                                     # |x| = x: the value and the magnitude sum in one convolution
+        both = conv64(x, np.concatenate([w16, np.abs(w16)]))
+        acc, mag = both[:, :, :cout], both[:, :, cout:]
+    else:
+        acc, mag = conv64(x, w16), conv64(np.abs(x), np.abs(w16))
+    y = sc * acc + sh
+    d = np.abs(sc) * (9 * cin) * U32 * mag + U32 * np.abs(y)
+    if wino:
+        d = d + np.abs(sc) * wino_allowance(x, w32, w16)
+    return (np.maximum(y, 0.0) if relu else y), d
+
+
+def check_layer(got, y64, d):
+    """got: the kernel's fp16 output, y64 / d from layer_ref.  Returns a dict:
+       bad      -- mask of the elements outside the bound (|got - y64| <= half_ulp16(|y64| + d) + d; |y64| - d >= 65520 must be exactly +-inf, and
+                   inf is also accepted where |y64| + d reaches 65520; NaN is never accepted),
+       exact    -- fraction of the outputs with y64 != 0 that equal float16(y64) (correctly rounded),
+       margin   -- max |got - y64| / (half_ulp16 + d) over the finite references (<= 1 inside the bound),
+       bias     -- mean of (got - y64) sign(y64) in half-ulps over the finite non-zero ones: about 0 for round-to-nearest, about -1 toward zero,
+       n_inf    -- outputs that had to be +-inf."""
+    g = np.asarray(got, np.float16).astype(np.float64)
+    ay = np.abs(y64)
+    must_inf, may_inf = ay - d >= F16_INF_AT, ay + d >= F16_INF_AT
+    tol = half_ulp16(ay + d) + d
+    with np.errstate(invalid="ignore"):
+        err = np.abs(g - y64)
+        inside = err <= tol
+        is_inf = g == np.sign(y64) * np.inf
+    bad = np.where(must_inf, ~is_inf, np.where(may_inf, ~(is_inf | inside), ~inside))
+    nz = y64 != 0
+    with np.errstate(over="ignore"):
+        exact = float((g[nz] == y64[nz].astype(np.float16).astype(np.float64)).mean()) if nz.any() else 1.0
+    fin = ~may_inf
+    with np.errstate(invalid="ignore"):
+        margin = float(np.nanmax(np.where(fin, err / tol, 0.0))) if fin.any() else 0.0
+        sel = nz & fin & np.isfinite(g)
+        bias = float(((g - y64) * np.sign(y64) / half_ulp16(y64))[sel].mean()) if sel.any() else 0.0
+    return dict(bad=bad, exact=exact, margin=margin, bias=bias, n_inf=int(must_inf.sum()))

@@ -453,3 +453,34 @@ def test_fuzz_segnet_ops(ctx, seed, layer, h, w, amp):
         ref = ctx.segnet_debug_conv(layer, ctx.segnet_debug_unpool(pooled, code, h, w))
         out = ctx.segnet_debug_unpool_conv(layer, pooled, code, h, w)
         assert np.array_equal(out, ref), msg + " unpool+conv"
+
+
+# ---------------------------------------------------------------- SegNet conv layers on drawn REAL-VALUED data against float64 (tests/segnet_ref.py: check_layer)
+@settings(max_examples=int(20 * SCALE), **COMMON)
+@given(seed=st.integers(0, 2**31 - 1), layer=st.integers(0, 25), h=st.integers(1, 35), w=st.integers(1, 35), mag=st.integers(-17, 6),
+       scale_exp=st.integers(-22, 14), signed=st.booleans())
+def test_fuzz_segnet_real(ctx, seed, layer, h, w, mag, scale_exp, signed):
+    """a conv3x3 + scale / shift (+ ReLU) layer of the net on an odd drawn image size (2 h + 1, 2 w + 1) with fp16 inputs of magnitude 2^mag (signed or
+    post-ReLU-like), He-normal weights and scale / shift times 2^scale_exp -- from fp16-subnormal to overflowing outputs -- against float64 within the bound
+    of segnet_ref.check_layer; the correctly-rounded fraction and the rounding bias where enough outputs are non-zero (test_gpu_segnet_precision)"""
+    import segnet_ref as S
+    from test_gpu_segnet_precision import BIAS_MAX, EXACT_MIN, EXACT_MIN_WINO, conv_padded
+    msg = log_case("segnet_real", seed=seed, layer=layer, h=h, w=w, mag=mag, scale_exp=scale_exp, signed=signed)
+    rng = np.random.default_rng(seed)
+    cin, cout, _, _ = ctx.segnet_layers()[layer]
+    H, W = 2 * h + 1, 2 * w + 1
+    wt = (rng.standard_normal((cout, cin, 3, 3)) * np.sqrt(2.0 / (9 * cin))).astype(np.float32)
+    sc = ((1.0 + 0.05 * rng.standard_normal(cout)) * 2.0 ** scale_exp).astype(np.float32)
+    sh = (0.05 * rng.standard_normal(cout) * 2.0 ** scale_exp).astype(np.float32)
+    x = rng.standard_normal((H, W, cin)) * 2.0 ** mag
+    x = (x if signed else np.maximum(x, 0)).astype(np.float16)
+    wino = S.wino_active(cin, cout)
+    ctx.segnet_set_layer(layer, wt, sc, sh)
+    out = conv_padded(ctx, layer, x)
+    y64, d = S.layer_ref(x, wt, sc, sh, relu=layer != 25, wino=wino)
+    r = S.check_layer(out[:, :, :cout], y64, d)
+    assert not r["bad"].any(), msg + f" {int(r['bad'].sum())} outside the bound, first at {np.argwhere(r['bad'])[0]}"
+    assert (out[:, :, cout:] == 0).all(), msg + " padding channels"
+    if (y64 != 0).sum() >= 2000:
+        assert r["exact"] >= (EXACT_MIN_WINO if wino else EXACT_MIN), msg + f" exact {r['exact']:.4f}"
+        assert wino or abs(r["bias"]) <= BIAS_MAX, msg + f" bias {r['bias']:+.3f}"

@@ -11,6 +11,11 @@ from conftest import SEED
 
 pytestmark = pytest.mark.gpu
 
+# label agreement with the pure fp32 reference in test_segnet_forward_tolerance: the lowest measured on the MI355X over its three frames (direct kernel 0.9207,
+# Winograd 0.9165; DESIGN.md s.2 "SegNet numerics") less a margin of one point, rounded down
+AGREE32_MIN = 0.91
+AGREE32_MIN_WINO = 0.90
+
 
 @pytest.fixture(scope="module")
 def seg(ctx):
@@ -28,37 +33,43 @@ def test_segnet_flops_match_survey():
 
 
 def test_segnet_forward_tolerance(ctx, oracle, frames, seg):
+    import json, os
     import segnet_ref
     for l, (wt, sc, sh) in enumerate(seg):                      # (re)load the seeded weights
         ctx.segnet_set_layer(l, wt, sc, sh)
-    bgr = frames[0][0]
-    labels, sem = ctx.classify(bgr)
-    logits = ctx.segnet_logits()                                 # [360][480][12]
-    x = np.stack([oracle.resize(np.ascontiguousarray(bgr[:, :, c]), 480, 360) for c in range(3)])      # Preprocess: cv::resize per channel
-    ref16 = segnet_ref.forward(x, seg, emulate_fp16=True).transpose(1, 2, 0)
-    ref32 = segnet_ref.forward(x, seg, emulate_fp16=False).transpose(1, 2, 0)
-    assert np.isfinite(logits).all() and np.abs(ref32).max() > 0.1
-    err = np.abs(logits - ref16).max() / np.abs(ref16).max()
-    agree16 = (labels == ref16.argmax(2)).mean()
-    agree32 = (labels == ref32.argmax(2)).mean()
-    print(f"segnet: rel logit err vs fp16-emulated ref {err:.4f}, label agreement {agree16:.4f} (fp16-emulated) {agree32:.4f} (fp32)")
-    assert np.array_equal(labels, logits.argmax(2))              # ArgMax: first maximum
-    noise = np.abs(ref16 - ref32).mean(); mine = np.abs(logits - ref16).mean(); base = (ref16.argmax(2) == ref32.argmax(2)).mean()
-    print(f"        fp16 noise floor: mean|ref16-ref32| {noise:.5f}, mean|kernel-ref16| {mine:.5f}, ref16/ref32 label agreement {base:.4f}")
-    import os
-    if os.environ.get("SSM_CONV_WINOGRAD") == "1":
-        # the Winograd variant rounds V = B^T d and U = G g to fp16 once more than the direct kernel: its distance to the fp16-emulated reference is allowed up to the
-        # fp16 noise floor itself (measured 0.77 of it; the direct kernel: 0.55), the labels within half a point of the fp16-emulated reference's own agreement
-        assert mine <= 1.0 * noise and agree16 >= base - 0.005 and agree32 >= 0.90
-    else:
-        assert mine <= 0.75 * noise and agree16 >= base and agree32 >= 0.90
-    # colour-label image: Pavement(5)->Road(4) remap, resize of the ids with the reference's bilinear-on-ids, palette LUT
-    ids = labels.copy(); ids[ids == 5] = 4
-    up = oracle.resize(ids, 640, 480)
+    wino = os.environ.get("SSM_CONV_WINOGRAD") == "1"
     pal = np.zeros((256, 3), np.uint8)
-    import json, os
     pal[:12] = np.array(json.load(open(os.path.join(os.path.dirname(__file__), "golden", "palette.json")))["palette_bgr"], np.uint8)
-    assert np.array_equal(sem, pal[up])
+    agree32s = []
+    for fi in (0, 3, 6):                                        # three distinct frames of the synthetic stream
+        bgr = frames[fi][0]
+        labels, sem = ctx.classify(bgr)
+        logits = ctx.segnet_logits()                             # [360][480][12]
+        x = np.stack([oracle.resize(np.ascontiguousarray(bgr[:, :, c]), 480, 360) for c in range(3)])      # Preprocess: cv::resize per channel
+        ref16 = segnet_ref.forward(x, seg, emulate_fp16=True).transpose(1, 2, 0)
+        ref32 = segnet_ref.forward(x, seg, emulate_fp16=False).transpose(1, 2, 0)
+        assert np.isfinite(logits).all() and np.abs(ref32).max() > 0.1
+        err = np.abs(logits - ref16).max() / np.abs(ref16).max()
+        agree16 = (labels == ref16.argmax(2)).mean()
+        agree32 = (labels == ref32.argmax(2)).mean()
+        agree32s.append(agree32)
+        noise = np.abs(ref16 - ref32).mean(); mine = np.abs(logits - ref16).mean(); base = (ref16.argmax(2) == ref32.argmax(2)).mean()
+        print(f"segnet frame {fi}{' wino' if wino else ''}: rel logit err vs fp16-emulated ref {err:.4f}, label agreement {agree16:.4f} (fp16-emulated) "
+              f"{agree32:.4f} (fp32); fp16 noise floor mean|ref16-ref32| {noise:.5f}, mean|kernel-ref16| {mine:.5f} = {mine / noise:.3f} of it, "
+              f"ref16/ref32 label agreement {base:.4f}")
+        assert np.array_equal(labels, logits.argmax(2))          # ArgMax: first maximum
+        # agreement with the pure fp32 reference: the measured minimum over these frames (DESIGN.md s.2 "SegNet numerics") less a stated margin
+        if wino:
+            # the Winograd variant rounds V = B^T d and U = G g to fp16 once more than the direct kernel: its distance to the fp16-emulated reference is allowed up to the
+            # fp16 noise floor itself (measured 0.77 of it; the direct kernel: 0.55), the labels within half a point of the fp16-emulated reference's own agreement
+            assert mine <= 1.0 * noise and agree16 >= base - 0.005 and agree32 >= AGREE32_MIN_WINO
+        else:
+            assert mine <= 0.75 * noise and agree16 >= base and agree32 >= AGREE32_MIN
+        # colour-label image: Pavement(5)->Road(4) remap, resize of the ids with the reference's bilinear-on-ids, palette LUT
+        ids = labels.copy(); ids[ids == 5] = 4
+        up = oracle.resize(ids, 640, 480)
+        assert np.array_equal(sem, pal[up])
+    print(f"segnet: lowest agreement with the fp32 reference over the frames {min(agree32s):.4f}")
 
 
 @pytest.mark.parametrize("layer,h,w", [(0, 20, 33), (1, 23, 30), (3, 12, 15), (9, 45, 60), (18, 23, 30), (25, 31, 17)])
@@ -220,17 +231,118 @@ def test_seq_process_with_segnet_stage(ctx, oracle, seg):
             ctx.dev_free(p)
 
 
+# ---------------------------------------------------------------- the production batch: SegNetState::batch = 64 (bench.py --segnet runs max_batch 250) plus a tail sub-batch
+N_BIG = 70                       # 64 frames in the first SegNet launch, 6 in the tail
+
+
+@pytest.fixture(scope="module")
+def big_ctx(seg):
+    """a context of its own whose SegNet sub-batch is the production one (seg_init: min(max_batch, 64) frames per launch)"""
+    import semantic_slam_mapping_amd as ssm
+    from conftest import CAM
+    c = ssm.Context(0, orb_features=1000, max_batch=N_BIG, voxel_capacity_log2=18, camera=CAM)
+    try:
+        for l, (wt, sc, sh) in enumerate(seg):
+            c.segnet_set_layer(l, wt, sc, sh)
+        yield c
+    finally:
+        c.close()
+
+
+def test_forward_dev_full_batch_every_frame(big_ctx, oracle):
+    """ssm_segnet_forward_dev on 70 distinct frames (one 64-frame launch + a 6-frame tail), fused ArgMax (flags 0) and logits + ArgMax kernel (flags 4): every
+    frame's labels equal classify() of that frame alone, and its colour labels the oracle resize + palette of them -- a frame-stride, tail or tile-queue
+    mistake anywhere in the batch shows up in some frame"""
+    import json, os
+    c, n, W, H = big_ctx, N_BIG, 640, 480
+    pal = np.zeros((256, 3), np.uint8)
+    pal[:12] = np.array(json.load(open(os.path.join(os.path.dirname(__file__), "golden", "palette.json")))["palette_bgr"], np.uint8)
+    bufs = [c.dev_alloc(n * W * H * 3), c.dev_alloc(n * W * H * 2), c.dev_alloc(n * W * H * 3), c.dev_alloc(n * 128)]
+    lab = [c.dev_alloc(n * 360 * 480) for _ in range(2)]
+    sem = [c.dev_alloc(n * W * H * 3) for _ in range(2)]
+    try:
+        c.synth_frames_dev(SEED, 300, n, *bufs)
+        c.segnet_forward_dev(bufs[0], n, lab[0], sem[0], 0)
+        c.segnet_forward_dev(bufs[0], n, lab[1], sem[1], 4)
+        c.sync()
+        frames = c.d2h(bufs[0], (n, H, W, 3), np.uint8)
+        assert np.array_equal(frames[n - 1], oracle.synth_frame(SEED, 300 + n - 1)[0])
+        a = c.d2h(lab[0], (n, 360, 480), np.uint8); b = c.d2h(lab[1], (n, 360, 480), np.uint8)
+        sa = c.d2h(sem[0], (n, H, W, 3), np.uint8); sb = c.d2h(sem[1], (n, H, W, 3), np.uint8)
+        assert np.array_equal(a, b) and np.array_equal(sa, sb)
+        assert len({x.tobytes() for x in a}) == n, "label maps repeat between frames: a frame-offset bug could pass"
+        for i in range(n):
+            one, _ = c.classify(frames[i], want_sem=False)
+            assert np.array_equal(a[i], one), f"frame {i}"
+            ids = a[i].copy(); ids[ids == 5] = 4
+            assert np.array_equal(sa[i], pal[oracle.resize(ids, W, H)]), f"frame {i} colour labels"
+    finally:
+        for p in bufs + lab + sem:
+            c.dev_free(p)
+
+
+def test_seq_process_with_segnet_stage_full_batch(big_ctx, oracle):
+    """BASELINE configs[2] at the bench's sub-batching: ORB | SEGNET | MAP on 70 frames in one seq_process call (SegNet 64 + 6, d_sem_gen per sub-batch);
+    the map must equal the oracle map built from per-frame classify() labels"""
+    from conftest import CAM
+    c, n, W, H = big_ctx, N_BIG, 640, 480
+    bufs = [c.dev_alloc(n * W * H * 3), c.dev_alloc(n * W * H * 2), c.dev_alloc(n * W * H * 3), c.dev_alloc(n * 128)]
+    try:
+        c.synth_frames_dev(SEED, 300, n, *bufs)
+        c.map_clear()
+        out = c.seq_process(bufs[0], bufs[1], None, bufs[3], n, stages=1 | 4 | 8)
+        c.sync()
+        res = c.seq_fetch(out, n)
+        clouds = []
+        for i in range(n):
+            bgr, dep, _, _, T = oracle.synth_frame(SEED, 300 + i)
+            _, sem = c.classify(bgr)
+            cl = oracle.backproject(dep, bgr, sem, oracle.moving_mask(sem), CAM, T, 40.0)
+            assert res["npoints"][i] == len(cl), f"frame {i}"
+            clouds.append(cl)
+        ref_map = oracle.voxel_filter(np.concatenate(clouds), np.float32(c.cfg.mapper_resolution))
+        assert c.map_export().tobytes() == ref_map.tobytes()
+        c.map_clear()
+    finally:
+        for p in bufs:
+            c.dev_free(p)
+
+
+def test_argmax_paths_agree_on_a_near_tie(ctx, oracle, seg):
+    """regression: frame 326 of the stream (inside the full-batch tests' frames 300 .. 369) has a pixel, (318, 5), whose two best logits are one fp16 ulp
+    apart (0.092712, class 3, and 0.092773, class 10).  The fused conv + ArgMax epilogue (flags 0) once rounded fma(acc, scale, shift) straight to fp16
+    (v_fma_mixlo_f16) where the stored logits are rounded to fp32 first, and the two paths disagreed on that pixel"""
+    for l, (wt, sc, sh) in enumerate(seg):
+        ctx.segnet_set_layer(l, wt, sc, sh)
+    frame = oracle.synth_frame(SEED, 326)[0][None]
+    d_bgr = ctx.dev_alloc(frame.nbytes); d_a = ctx.dev_alloc(360 * 480); d_b = ctx.dev_alloc(360 * 480)
+    try:
+        ctx.h2d(d_bgr, frame)
+        ctx.segnet_forward_dev(d_bgr, 1, d_a, None, 0)
+        ctx.segnet_forward_dev(d_bgr, 1, d_b, None, 4)
+        ctx.sync()
+        a = ctx.d2h(d_a, (360, 480), np.uint8); b = ctx.d2h(d_b, (360, 480), np.uint8)
+        assert b[318, 5] == 10                                   # the near tie is still there (the case keeps its power)
+        assert np.array_equal(a, b), f"labels differ at {np.argwhere(a != b).tolist()}: fused {a[a != b].tolist()}, logits path {b[a != b].tolist()}"
+    finally:
+        for p in (d_bgr, d_a, d_b):
+            ctx.dev_free(p)
+
+
 @pytest.mark.gpu
 def test_winograd_conv_kernel_passes_the_same_tests():
     """conv3x3_wino_kernel (Winograd F(2, 3) along x, SSM_CONV_WINOGRAD=1; not the default: profiles/r06_segnet_winograd.md) on the plain conv + BN + ReLU layers: the
     per-op tests on integer data stay BIT-EXACT under it (the transform constants are 1, -1 and 1/2), the committed fixture and the fused-layer tests run through it,
+    the real-valued tests of test_gpu_segnet_precision.py and test_gpu_fuzz.py hold with the Winograd bound (segnet_ref.wino_allowance),
     and the end-to-end labels stay within the stated tolerance (test_segnet_forward_tolerance reads the variable); the variant is read once per process, hence the
     subprocess"""
     import os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SSM_CONV_WINOGRAD="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_segnet.py"), "-x", "-q", "-m", "gpu",
-                        "-k", "conv_layer_exact or conv_pool_fused_exact or committed_fixture or fused_argmax or forward_tolerance"],
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_segnet.py"), os.path.join(root, "tests", "test_gpu_segnet_precision.py"),
+                        os.path.join(root, "tests", "test_gpu_fuzz.py"), "-x", "-q", "-m", "gpu",
+                        "-k", "conv_layer_exact or conv_pool_fused_exact or committed_fixture or fused_argmax or forward_tolerance or against_float64 or subnormal or "
+                              "overflow_to_inf or fuzz_segnet_real"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
     assert " passed" in r.stdout and "deselected" in r.stdout
