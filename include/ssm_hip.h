@@ -387,6 +387,11 @@ int ssm_segnet_forward_dev(ssm_ctx* ctx, const uint8_t* bgr_dev, int n, uint8_t*
  * op 5 = conv layer `arg` (Cout <= 12: the last one) + class ArgMax through the fused epilogue the network runs: in[H][W][CinPad16] ->
  * code[H][W] (the labels; `out` is not written) */
 int ssm_segnet_debug_op(ssm_ctx* ctx, int op, int arg, const uint16_t* in, int H, int W, uint16_t* out, uint8_t* code);
+/* the image pyramid of n frames (host, w x h x channels each, rows packed; n <= max_batch) -> out (n x the pyramid buffer of one frame: every level,
+ * rows padded to 16 bytes), for exact tests of the fused pyramid kernel: bands < 0 = gray_kernel + one resize launch per level, 0 = what the ORB
+ * calls run, > 0 = the fused kernel with that many bands (SSM_E_INVAL where the geometry has no fused form at that band count).  *bytes: one frame's
+ * buffer (img and out both NULL: only that) */
+int ssm_debug_pyramid(ssm_ctx* ctx, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes);
 /* class logits (12 floats per net pixel, 360*480 pixels) of frame 0 of the most recent forward: for tolerance tests */
 int ssm_segnet_logits(ssm_ctx* ctx, float* out);
 

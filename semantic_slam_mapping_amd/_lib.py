@@ -131,6 +131,7 @@ SYMBOLS = {
     "ssm_segnet_forward_dev": (_I, [_P, _P, _I, _P, _P, _I]),
     "ssm_segnet_logits": (_I, [_P, _P]),
     "ssm_segnet_debug_op": (_I, [_P, _I, _I, _P, _I, _I, _P, _P]),
+    "ssm_debug_pyramid": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_I)]),
     "ssm_set_profiling": (_I, [_P, _I]),
     "ssm_get_stage_times": (_I, [_P, _P, _P, _P, _I, C.POINTER(_I)]),
     "ssm_dev_alloc": (_I, [_P, _SZ, C.POINTER(_P)]),

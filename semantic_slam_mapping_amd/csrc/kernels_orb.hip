@@ -5,6 +5,11 @@
 #include "ssm_internal.h"
 #include <cstdlib>
 #include <type_traits>
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <set>
+#include <vector>
 
 #define WAVE 64
 
@@ -187,6 +192,210 @@ hipError_t k_pyramid(int n, const OrbGeom& g, uint8_t* pyr, const int32_t* const
                                                                      xofs[l], xa[l], yofs[l], ya[l]);
     }
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ K1 + K2 fused: the whole pyramid in one launch
+// gray_kernel + one resize4_kernel per level made 8 launches, each a grid-wide dependency on the previous one, and each level re-read its source level
+// from memory.  Here one block = one horizontal band of one frame: it converts the input rows its band needs (its own rows + the halo rows that the
+// coarser levels' own rows reach down to) to gray in LDS, then makes every level from the previous one in LDS, ping-ponging between two buffers, and
+// writes only its own rows of each level to the pyramid buffer as 16-byte stores.  The arithmetic is gray_kernel's and resize4_kernel's, so the
+// buffer is byte-identical to theirs.  Band rows (pyramid_band_plan, host): own(l, b) = [b h_l / B, (b + 1) h_l / B); comp(L-1, b) = own(L-1, b),
+// comp(l, b) = own(l, b) u src_rows(comp(l + 1, b)) -- contiguous.  The per-band halo is recomputed, not exchanged: 15 % more level-0 rows at B = 8, 33 % at B = 16,
+// and the kernel's time grows with them (it is bound by instruction issue, not by latency: more, smaller bands were slower).
+// The kernel's name starts with resize4_kernel so that the profiles attribute it to the pyramid stage.
+#ifndef PB_T
+#define PB_T 1024             // (512 threads: 4 % slower at B = 8)
+#endif
+#ifndef PB_U
+#define PB_U 4                 // level-0 quads a thread has in flight at once
+#endif
+#ifndef PB_BANDS
+#define PB_BANDS 8             // bands per frame in batches (640 x 480: 79 KB of LDS, two blocks per CU); measured per 250 frames: 8 bands 176 us, 12: 197, 16: 208, 32: 280
+#endif
+template <int MODE>            // 0: BGR, byte loads; 1: BGR, 12-byte loads (W % 4 == 0, input 4-aligned); 2: one channel
+__global__ void __launch_bounds__(PB_T)
+resize4_kernel_bands(const uint8_t* __restrict__ img, uint8_t* __restrict__ pyr, OrbGeom g, const int4* __restrict__ band_tab, PyrBandArgs t)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // [level buffer 0 (even levels)][level buffer 1 (odd levels), at t.buf1]
+    const int frame = blockIdx.y;
+    const int4* bt = band_tab + blockIdx.x * g.nlevels;                 // (comp_lo, comp_hi, own_lo, own_hi) per level
+    uint8_t* fpyr = pyr + (size_t)frame * g.pyr_bytes;
+    {   // level 0: comp rows of the input to gray, one dword (4 pixels) per item, PB_U items' loads in flight before the first is used
+        const int4 r = bt[0];
+        const int W = g.W, quads = g.L[0].stride >> 2, items = quads * (r.y - r.x + 1);
+        const uint8_t* src = img + (size_t)frame * W * g.H * (MODE == 2 ? 1 : 3);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(smem);
+        for (int q0 = threadIdx.x; q0 < items; q0 += PB_T * PB_U) {
+            uint32_t v[PB_U][3];
+#pragma unroll
+            for (int k = 0; k < PB_U; k++) {
+                const int q = q0 + k * PB_T;
+                const int ry = (int)__umulhi((uint32_t)q, t.mulq0), x = (q - ry * quads) << 2;
+                v[k][0] = v[k][1] = v[k][2] = 0;
+                if (q >= items || x >= W) continue;                                                   // row padding: zeros
+                const size_t p = (size_t)(r.x + ry) * W + x;
+                if (MODE == 1) __builtin_memcpy(v[k], src + 3 * p, 12);
+                else if (MODE == 2) { for (int i = 0; i < 4; i++) if (x + i < W) v[k][0] |= (uint32_t)src[p + i] << (8 * i); }
+                else {
+                    for (int i = 0; i < 4; i++)
+                        if (x + i < W) v[k][0] |= ((src[3 * (p + i)] * 1868u + src[3 * (p + i) + 1] * 9617u + src[3 * (p + i) + 2] * 4899u + 8192u) >> 14) << (8 * i);
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < PB_U; k++) {
+                const int q = q0 + k * PB_T;
+                if (q >= items) break;
+                uint32_t out = v[k][0];
+                if (MODE == 1) {
+                    const uint32_t a = v[k][0], b = v[k][1], c = v[k][2];
+                    const uint32_t p0 = ((a & 255) * 1868 + ((a >> 8) & 255) * 9617 + ((a >> 16) & 255) * 4899 + 8192) >> 14;
+                    const uint32_t p1 = ((a >> 24) * 1868 + (b & 255) * 9617 + ((b >> 8) & 255) * 4899 + 8192) >> 14;
+                    const uint32_t p2 = (((b >> 16) & 255) * 1868 + (b >> 24) * 9617 + (c & 255) * 4899 + 8192) >> 14;
+                    const uint32_t p3 = (((c >> 8) & 255) * 1868 + ((c >> 16) & 255) * 9617 + (c >> 24) * 4899 + 8192) >> 14;
+                    const int ry = (int)__umulhi((uint32_t)q, t.mulq0), x = (q - ry * quads) << 2;
+                    out = x < W ? p0 | (p1 << 8) | (p2 << 16) | (p3 << 24) : 0u;
+                }
+                dst[q] = out;
+            }
+        }
+    }
+    // the tables of a thread's first item of the next level do not depend on LDS: their loads are issued before the barrier that ends a level
+    uint4 pA = {}, pQ = {}, pYO = {}, pYA = {};
+    auto tables = [&](int l, int i, uint4& A, uint4& Q, uint4& YO, uint4& YA) {
+        const int4 r = bt[l];
+        const int groups = g.L[l].stride >> 2, ch = (int)__umulhi((uint32_t)i, t.mulg[l]), gi = i - ch * groups, y0 = (r.x & ~3) + 4 * ch;
+        const uint4* xg = reinterpret_cast<const uint4*>(t.xg[l]);
+        A = xg[2 * gi]; Q = xg[2 * gi + 1];
+        YO = *reinterpret_cast<const uint4*>(t.yofs[l] + y0); YA = *reinterpret_cast<const uint4*>(t.ya[l] + 2 * y0);
+    };
+    auto first_items = [&](int l) { const int4 r = bt[l]; return (g.L[l].stride >> 2) * (((r.y - (r.x & ~3)) >> 2) + 1); };
+    if (g.nlevels > 1 && (int)threadIdx.x < first_items(1)) tables(1, threadIdx.x, pA, pQ, pYO, pYA);
+    __syncthreads();
+    for (int l = 1; l <= g.nlevels; l++) {
+        const int4 rs = bt[l - 1];
+        const LevelGeom& a = g.L[l - 1];
+        const uint8_t* sbuf = smem + ((l - 1) & 1 ? t.buf1 : 0);
+        {   // level l-1 is complete in sbuf, which nothing writes in this phase: its own rows leave for the pyramid buffer
+            const int n16 = ((rs.w - rs.z + 1) * a.stride) >> 4;
+            const uint4* s = reinterpret_cast<const uint4*>(sbuf + (rs.z - rs.x) * a.stride);
+            uint4* d = reinterpret_cast<uint4*>(fpyr + a.img_off + (size_t)rs.z * a.stride);
+            for (int i = threadIdx.x; i < n16; i += PB_T) d[i] = s[i];
+        }
+        if (l == g.nlevels) break;
+        // level l, comp rows, from level l-1 in LDS: resize4_kernel's item (one 4-pixel group x four rows of the y tables' 4-row blocks)
+        const int4 r = bt[l];
+        const LevelGeom& b = g.L[l];
+        uint8_t* dbuf = smem + (l & 1 ? t.buf1 : 0);
+        const int groups = b.stride >> 2, c0 = r.x & ~3, items = groups * (((r.y - c0) >> 2) + 1);
+        typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
+        for (int i = threadIdx.x; i < items; i += PB_T) {
+            const int ch = (int)__umulhi((uint32_t)i, t.mulg[l]), gi = i - ch * groups, y0 = c0 + 4 * ch;
+            uint4 A = pA, Q = pQ, YO = pYO, YA = pYA;
+            if (i != (int)threadIdx.x) tables(l, i, A, Q, YO, YA);
+            const uint32_t yo[4] = {YO.x, YO.y, YO.z, YO.w}, yc[4] = {YA.x, YA.y, YA.z, YA.w};
+            const uint32_t av[4] = {A.x, A.y, A.z, A.w};
+            uint32_t sel[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) sel[k] = ((Q.y >> (4 * k)) & 15u) * 0x00010001u + 0x0C010C00u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const int y = y0 + j;
+                if (y < r.x || y > r.y) continue;
+                const int syA = (int)yo[j], syB = min(syA + 1, a.h - 1);
+                // the 8-byte window of each source row from three aligned dwords (LDS has no unaligned 8-byte read): the same bytes as resize4_kernel's load
+                const int e0 = (syA - rs.x) * a.stride + (int)Q.x, e1 = (syB - rs.x) * a.stride + (int)Q.x;
+                const uint32_t* w0 = reinterpret_cast<const uint32_t*>(sbuf + (e0 & ~3));
+                const uint32_t* w1 = reinterpret_cast<const uint32_t*>(sbuf + (e1 & ~3));
+                const uint32_t u0 = w0[0], u1 = w0[1], u2 = w0[2], t0 = w1[0], t1 = w1[1], t2 = w1[2];
+                const uint32_t r0x = __builtin_amdgcn_alignbyte(u1, u0, e0 & 3), r0y = __builtin_amdgcn_alignbyte(u2, u1, e0 & 3);
+                const uint32_t r1x = __builtin_amdgcn_alignbyte(t1, t0, e1 & 3), r1y = __builtin_amdgcn_alignbyte(t2, t1, e1 & 3);
+                const uint32_t b0 = yc[j] << 16, b1 = yc[j] & 0xFFFF0000u;
+                uint32_t o = 0;
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t p0 = __builtin_amdgcn_perm(r0y, r0x, sel[k]), p1 = __builtin_amdgcn_perm(r1y, r1x, sel[k]);
+                    ushort2v c2, x0, x1; memcpy(&c2, &av[k], 4); memcpy(&x0, &p0, 4); memcpy(&x1, &p1, 4);
+                    const uint32_t h0 = __builtin_amdgcn_udot2(x0, c2, 0u, false), h1 = __builtin_amdgcn_udot2(x1, c2, 0u, false);
+                    const uint32_t v = (__umulhi(b0, h0 >> 4) + __umulhi(b1, h1 >> 4) + 2u) >> 2;
+                    o |= (v & 255u) << (8 * k);
+                }
+                *reinterpret_cast<uint32_t*>(dbuf + (y - r.x) * b.stride + 4 * gi) = o;
+            }
+        }
+        if (l + 1 < g.nlevels && (int)threadIdx.x < first_items(l + 1)) tables(l + 1, threadIdx.x, pA, pQ, pYO, pYA);
+        __syncthreads();
+    }
+}
+static hipError_t pb_allow_lds(const void* fn, size_t bytes)
+{
+    if (bytes <= 48 * 1024) return hipSuccess;
+    static std::mutex mu; static std::set<std::pair<int, const void*>> done;
+    int dev = 0; (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.count({dev, fn})) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PB_MAX_LDS);
+    if (e == hipSuccess) done.insert({dev, fn});
+    return e;
+}
+hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeom& g, uint8_t* pyr, const PyrBandPlan& p,
+                           const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, hipStream_t s)
+{
+    PyrBandArgs t = p.args;
+    for (int l = 1; l < g.nlevels; l++) { t.xg[l] = xgroups[l]; t.yofs[l] = yofs[l]; t.ya[l] = ya[l]; }
+    const dim3 grid(p.bands, n);
+    const int4* tab = reinterpret_cast<const int4*>(p.d_tab);
+    const void* fn;
+    if (channels == 1) fn = reinterpret_cast<const void*>(resize4_kernel_bands<2>);
+    else if ((g.W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0) fn = reinterpret_cast<const void*>(resize4_kernel_bands<1>);
+    else fn = reinterpret_cast<const void*>(resize4_kernel_bands<0>);
+    const hipError_t e = pb_allow_lds(fn, p.lds); if (e != hipSuccess) return e;
+    if (channels == 1) resize4_kernel_bands<2><<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
+    else if (fn == reinterpret_cast<const void*>(resize4_kernel_bands<1>)) resize4_kernel_bands<1><<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
+    else resize4_kernel_bands<0><<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
+    return hipGetLastError();
+}
+// the band count of a geometry: PB_BANDS per frame for batches, 32 for the one-frame call (one frame on more CUs); more bands where the level
+// buffers would not fit; none where a level needs the general resize kernel (p.bands stays 0)
+bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p)
+{
+    static const int cand[2][8] = {{PB_BANDS, 12, 16, 24, 32, 48, 64, 0}, {32, 48, 64, 0}};
+    for (int i = 0; i < 8 && cand[batch ? 0 : 1][i]; i++)
+        if (cand[batch ? 0 : 1][i] >= (batch ? PB_BANDS : 0) && pyramid_band_plan(g, yofs, streaming, cand[batch ? 0 : 1][i], tab, p)) return true;
+    return false;
+}
+// The band rows of every (band, level) for `bands` bands, from the host's y tables (yofs[l]: level l's source rows in level l-1).  false: the geometry
+// has no fused form at this band count (a level without the streaming x tables, fewer rows than bands, or level buffers beyond PB_MAX_LDS).
+bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, int bands, std::vector<int32_t>& tab, PyrBandPlan& p)
+{
+    const int L = g.nlevels;
+    if (bands < 1) return false;
+    for (int l = 0; l < L; l++) if (g.L[l].h < bands || (l > 0 && !streaming[l])) return false;
+    tab.assign((size_t)bands * L * 4, 0);
+    size_t need[2] = {0, 0};
+    for (int b = 0; b < bands; b++) {
+        int lo = 0, hi = -1;
+        for (int l = L - 1; l >= 0; l--) {
+            const int h = g.L[l].h, olo = (int)((int64_t)b * h / bands), ohi = (int)((int64_t)(b + 1) * h / bands) - 1;
+            int clo = olo, chi = ohi;
+            if (l < L - 1) {                                               // the source rows of comp(l + 1): [yofs[lo], min(yofs[hi] + 1, h - 1)]
+                clo = std::min(clo, yofs[l + 1][lo]); chi = std::max(chi, std::min(yofs[l + 1][hi] + 1, h - 1));
+            }
+            int32_t* e = &tab[((size_t)b * L + l) * 4];
+            e[0] = clo; e[1] = chi; e[2] = olo; e[3] = ohi;
+            need[l & 1] = std::max(need[l & 1], (size_t)(chi - clo + 1) * g.L[l].stride);
+            lo = clo; hi = chi;
+        }
+    }
+    // 16 bytes of slack behind each buffer: the 8-byte windows (read as three dwords) may end past the last row, as resize4_kernel's do past the pyramid
+    const size_t buf1 = (need[0] + 16 + 15) & ~(size_t)15, lds = buf1 + need[1] + 16;
+    if (lds > PB_MAX_LDS) return false;
+    memset(&p.args, 0, sizeof(p.args));
+    p.args.buf1 = (int)buf1;
+    const int q0 = g.L[0].stride >> 2;
+    p.args.mulq0 = (uint32_t)(((1ull << 32) + q0 - 1) / q0);
+    for (int l = 1; l < L; l++) { const int gr = g.L[l].stride >> 2; p.args.mulg[l] = (uint32_t)(((1ull << 32) + gr - 1) / gr); }
+    p.bands = bands; p.lds = lds;
+    return true;
 }
 
 // ------------------------------------------------------------------ K5a: 7x7 sigma-2 Gaussian, fixed point

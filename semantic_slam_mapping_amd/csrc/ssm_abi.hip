@@ -182,9 +182,11 @@ static int ctx_init(ssm_ctx* c)
           HIPCHK(c, hipMemcpy(c->d_blur_tab, bt.data(), bt.size(), hipMemcpyHostToDevice)); }
         DALLOC(c, c->d_pattern_f, 1024);
         HIPCHK(c, hipMemcpy(c->d_pattern_f, pf, sizeof(pf), hipMemcpyHostToDevice)); }
+    std::vector<int32_t> yall[SSM_MAX_LEVELS]; bool streaming[SSM_MAX_LEVELS] = {};
     for (int l = 1; l < g.nlevels; l++) {
         std::vector<int32_t> xo, yo; std::vector<int16_t> xa, ya;
         resize_tables(g.L[l-1].w, g.L[l].w, xo, xa); resize_tables(g.L[l-1].h, g.L[l].h, yo, ya);
+        yall[l] = yo;
         while (yo.size() & 3) { yo.push_back(yo.back()); ya.push_back(ya[ya.size() - 2]); ya.push_back(ya[ya.size() - 2]); }   // resize4_kernel reads the y tables four rows at a time
         DALLOC(c, c->d_xofs[l], xo.size()); DALLOC(c, c->d_xa[l], xa.size()); DALLOC(c, c->d_yofs[l], yo.size()); DALLOC(c, c->d_ya[l], ya.size());
         HIPCHK(c, hipMemcpy(c->d_xofs[l], xo.data(), xo.size() * 4, hipMemcpyHostToDevice));
@@ -211,8 +213,16 @@ static int ctx_init(ssm_ctx* c)
         if (fits) {
             uint32_t* d = nullptr; DALLOC(c, d, xg.size());
             HIPCHK(c, hipMemcpy(d, xg.data(), xg.size() * 4, hipMemcpyHostToDevice));
-            c->d_xgrp[l] = d;
+            c->d_xgrp[l] = d; streaming[l] = true;
         }
+    }
+    // the fused pyramid's band tables (none where a level needs the general resize kernel)
+    for (int k = 0; k < 2; k++) {
+        PyrBandPlan& p = k ? c->pyr_bands1 : c->pyr_bands; std::vector<int32_t> tab;
+        if (!pyramid_band_choose(g, yall, streaming, k == 0, tab, p)) continue;
+        int32_t* d = nullptr; DALLOC(c, d, tab.size());
+        HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        p.d_tab = d;
     }
     // d_pyr + 16: resize4_kernel's 8-byte windows may end past the last row
     DALLOC(c, c->d_pyr, (size_t)B * g.pyr_bytes + 16); DALLOC(c, c->d_blur, (size_t)B * g.blur_bytes);
@@ -286,6 +296,7 @@ extern "C" void ssm_destroy(ssm_ctx* c)
     if (c->stream4) hipStreamDestroy(c->stream4);
     if (c->ev_join4) hipEventDestroy(c->ev_join4);
     for (int l = 0; l < SSM_MAX_LEVELS; l++) { if (c->d_xofs[l]) hipFree(c->d_xofs[l]); if (c->d_xa[l]) hipFree(c->d_xa[l]); if (c->d_yofs[l]) hipFree(c->d_yofs[l]); if (c->d_ya[l]) hipFree(c->d_ya[l]); if (c->d_xgrp[l]) hipFree(c->d_xgrp[l]); }
+    if (c->pyr_bands.d_tab) hipFree(c->pyr_bands.d_tab); if (c->pyr_bands1.d_tab) hipFree(c->pyr_bands1.d_tab);
     if (c->seg) {
         SegNetState* g = c->seg;
         void* sp[] = { g->actA, g->actB, g->labels, g->d_sem_gen, g->pre_xofs, g->pre_yofs, g->post_xofs, g->post_yofs, g->pre_xa, g->pre_ya, g->post_xa, g->post_ya,
@@ -397,16 +408,58 @@ struct ChainSwap {                    // chains 1, 2 of ssm_seq_process: the hel
     ~ChainSwap() { if (chain) swap_all(); }
 };
 // ---------------------------------------------------------------- the ORB front end for nb frames already on the device
+// level 0 + every level of nb frames into c->d_pyr: one launch where the geometry has the fused form (plan), gray_kernel + one launch per level otherwise
+static int make_pyramid(ssm_ctx* c, const uint8_t* d_img, int channels, int nb, const PyrBandPlan& plan)
+{
+    const OrbGeom& g = c->g; hipStream_t s = c->stream;
+    if (plan.bands) {
+        prof_begin(c, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, c->d_pyr, plan, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c);
+        return SSM_OK;
+    }
+    prof_begin(c, "gray");      HIPCHK(c, k_gray(d_img, channels, nb, g, c->d_pyr, s)); prof_end(c);
+    prof_begin(c, "pyramid");   HIPCHK(c, k_pyramid(nb, g, c->d_pyr, c->d_xofs, c->d_xa, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c);
+    return SSM_OK;
+}
 static int run_orb(ssm_ctx* c, const uint8_t* d_img, int channels, const uint16_t* d_depth, int nb,
                    ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp)
 {
     const OrbGeom& g = c->g; hipStream_t s = c->stream;
-    prof_begin(c, "gray");      HIPCHK(c, k_gray(d_img, channels, nb, g, c->d_pyr, s)); prof_end(c);
-    prof_begin(c, "pyramid");   HIPCHK(c, k_pyramid(nb, g, c->d_pyr, c->d_xofs, c->d_xa, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c);
+    { const int r = make_pyramid(c, d_img, channels, nb, nb > 1 ? c->pyr_bands : c->pyr_bands1); if (r) return r; }
     prof_begin(c, "fast");      HIPCHK(c, k_fast(nb, g, c->d_pyr, c->d_cand, c->d_ncand, c->d_cellmax, s)); prof_end(c);
     prof_begin(c, "octree");    HIPCHK(c, k_octree(nb, g, c->d_cand, c->d_ncand, c->d_cellmax, c->d_nodeof, c->d_sel, c->d_nsel, c->d_status, s)); prof_end(c);
     prof_begin(c, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(nb, g, c->d_pyr, c->d_blur, c->d_blur_tab, s) : k_blur(nb, g, c->d_pyr, c->d_blur, s)); prof_end(c);
     prof_begin(c, "describe");  HIPCHK(c, k_describe(nb, g, c->d_pyr, c->d_blur, c->d_sel, c->d_nsel, c->d_pattern_f, d_depth, c->cfg.camera, c->d_kpaux, kps, desc, pos3d, nkp, s)); prof_end(c);
+    return SSM_OK;
+}
+
+extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    const OrbGeom& g = c->g;
+    if (bytes) *bytes = g.pyr_bytes;
+    if (!img && !out) return SSM_OK;                                     // the size query
+    if (!img || !out || (channels != 1 && channels != 3) || n < 1 || n > c->B) FAIL(c, SSM_E_INVAL, "bad arguments");
+    { const int r = wait_pending(c); if (r) return r; }
+    const size_t ib = (size_t)g.W * g.H * channels;
+    { const int r = ensure_scratch(c, ib * n); if (r) return r; }
+    HIPCHK(c, hipMemcpyAsync(c->d_scratch, img, ib * n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_pyr, 0xA5, (size_t)n * g.pyr_bytes, c->stream));      // every byte the pyramid owns must be written
+    PyrBandPlan p;
+    if (bands < 0) p.bands = 0;
+    else if (bands == 0) p = n > 1 ? c->pyr_bands : c->pyr_bands1;
+    else {
+        std::vector<int32_t> yall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {};
+        for (int l = 1; l < g.nlevels; l++) { std::vector<int16_t> ya; resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya); streaming[l] = c->d_xgrp[l] != nullptr; }
+        if (!pyramid_band_plan(g, yall, streaming, bands, tab, p)) FAIL(c, SSM_E_INVAL, "no fused pyramid at this band count");
+        int32_t* d = nullptr; DALLOC(c, d, tab.size()); p.d_tab = d;
+        HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+    }
+    int r = make_pyramid(c, static_cast<const uint8_t*>(c->d_scratch), channels, n, p);
+    if (bands > 0) { hipStreamSynchronize(c->stream); hipFree(p.d_tab); }
+    if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(out, c->d_pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
 }
 
@@ -484,8 +537,7 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
     float* dps = reinterpret_cast<float*>(dd + (size_t)ocap * 32);
     {
         const OrbGeom& g = c->g; hipStream_t s = c->stream;
-        prof_begin(c, "gray");      HIPCHK(c, k_gray(c->d_in_img, channels, 1, g, c->d_pyr, s)); prof_end(c);
-        prof_begin(c, "pyramid");   HIPCHK(c, k_pyramid(1, g, c->d_pyr, c->d_xofs, c->d_xa, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c);
+        { const int r = make_pyramid(c, c->d_in_img, channels, 1, c->pyr_bands1); if (r) return r; }
         prof_begin(c, "fast");      HIPCHK(c, k_fast(1, g, c->d_pyr, c->d_cand, c->d_ncand, c->d_cellmax, s)); prof_end(c);
         prof_begin(c, "octree");    HIPCHK(c, k_octree(1, g, c->d_cand, c->d_ncand, c->d_cellmax, c->d_nodeof, c->d_sel, c->d_nsel, c->d_status, s)); prof_end(c);
         prof_begin(c, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(1, g, c->d_pyr, c->d_blur, c->d_blur_tab, s) : k_blur(1, g, c->d_pyr, c->d_blur, s)); prof_end(c);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <vector>
 #include "../../include/ssm_hip.h"
 
 #define SSM_MAX_LEVELS 12
@@ -53,6 +54,15 @@ hipError_t k_gray(const uint8_t* img, int channels, int n, const OrbGeom& g, uin
 hipError_t k_copy_gray_strided(const uint8_t* img, int stride, const OrbGeom& g, uint8_t* pyr, hipStream_t s);
 hipError_t k_pyramid(int n, const OrbGeom& g, uint8_t* pyr, const int32_t* const* xofs, const int16_t* const* xa,
                      const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, hipStream_t s);
+// the pyramid in one launch (resize4_kernel_bands: gray + every level, one block per (band, frame)); the plan is built once per geometry and band count
+#define PB_MAX_LDS (80 * 1024)     // two blocks per CU at least
+struct PyrBandArgs { const void* xg[SSM_MAX_LEVELS]; const int32_t* yofs[SSM_MAX_LEVELS]; const int16_t* ya[SSM_MAX_LEVELS]; uint32_t mulq0, mulg[SSM_MAX_LEVELS]; int buf1; };
+struct PyrBandPlan { int bands = 0; size_t lds = 0; void* d_tab = nullptr; PyrBandArgs args = {}; };     // bands == 0: no fused form (k_gray + k_pyramid)
+// tab: bands x levels x (comp_lo, comp_hi, own_lo, own_hi); false: no fused form at this band count
+bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p);
+bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, int bands, std::vector<int32_t>& tab, PyrBandPlan& p);
+hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeom& g, uint8_t* pyr, const PyrBandPlan& p,
+                           const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, hipStream_t s);
 hipError_t k_blur(int n, const OrbGeom& g, const uint8_t* pyr, uint8_t* blur, hipStream_t s);
 // the same blur on the matrix cores; tab = blur_mfma_tables() on the device
 #define BLUR_ROWS 58           // output rows of one blur_mfma block (64 input rows)
