@@ -392,6 +392,10 @@ int ssm_segnet_debug_op(ssm_ctx* ctx, int op, int arg, const uint16_t* in, int H
  * calls run, > 0 = the fused kernel with that many bands (SSM_E_INVAL where the geometry has no fused form at that band count).  *bytes: one frame's
  * buffer (img and out both NULL: only that) */
 int ssm_debug_pyramid(ssm_ctx* ctx, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes);
+/* the SGBM post stages alone, as the last steps of ssm_sgbm launch them, on n stacked int16 maps (host, w x h each, rows packed) -> out (same shape):
+ * op bit 0 = medianBlur 3x3 (replicate border), bit 1 = filterSpeckles (4-neighbours, both != new_val, |a - b| <= max_diff; components of at most
+ * max_size pixels become new_val) on the median's output, or on the input without bit 0.  For exact tests of the kernels on constructed maps */
+int ssm_debug_sgbm_post(ssm_ctx* ctx, const int16_t* disp, int w, int h, int n, int op, int new_val, int max_size, int max_diff, int16_t* out);
 /* class logits (12 floats per net pixel, 360*480 pixels) of frame 0 of the most recent forward: for tolerance tests */
 int ssm_segnet_logits(ssm_ctx* ctx, float* out);
 

@@ -429,6 +429,13 @@ class Context:
         self._chk(self.lib.ssm_segnet_debug_op(self.h, 5, layer, _ptr(xin), h, w, _ptr(dummy), _ptr(labels)))
         return labels
 
+    def debug_sgbm_post(self, disp, op, new_val=-16, max_size=100, max_diff=32):
+        """int16 maps (h x w, or n x h x w: one launch over all n) through SGBM's last steps: op bit 0 = medianBlur 3x3, bit 1 = filterSpeckles"""
+        d = np.ascontiguousarray(disp, np.int16); d3 = d.reshape((-1,) + d.shape[-2:]); n, h, w = d3.shape
+        out = np.empty_like(d3)
+        self._chk(self.lib.ssm_debug_sgbm_post(self.h, _ptr(d3), w, h, n, op, new_val, max_size, max_diff, _ptr(out)))
+        return out.reshape(d.shape)
+
     def segnet_debug_pool(self, x_hwc_f16):
         x = np.ascontiguousarray(x_hwc_f16, np.float16); h, w, c = x.shape
         out = np.zeros(((h + 1) // 2, (w + 1) // 2, c), np.float16); code = np.zeros(out.shape, np.uint8)

@@ -123,6 +123,11 @@ mineig_kernel(QuadBatch q, float* __restrict__ eig_all, int* __restrict__ maxord
 // Round 4: a block takes 1024 consecutive pixels (a wave 256: lane l looks at pixels l, l + 64, l + 128, l + 192 of them, so each of its four ballots is
 // 64 consecutive pixels = two whole words of the bit image), row / column of a pixel by a reciprocal multiplication: the thread-per-pixel version spent its
 // time on three barriers, one division sequence and two atomics per 256 pixels of almost no work (0.017 VALU instructions per clock, 19 us per 1241 x 376 frame)
+__device__ __forceinline__ float gftt_threshold(int maxord, double quality)        // threshold(eig, maxVal * qualityLevel, THRESH_TOZERO) keeps v > this
+{
+    const float mx = __int_as_float(maxord >= 0 ? maxord : maxord ^ 0x7FFFFFFF);
+    return (float)((double)fmaxf(mx, 0.f) * quality);
+}
 #define GC_PX 16      // (round 4, later: 16 pixels per thread = 4096 per block -- the block's one atomic on the frame's counter is a ~0.4 us step of a serial chain, 456 of them per 1241 x 376 frame with 1024-pixel blocks)
 __global__ void __launch_bounds__(256)
 gftt_collect_kernel(const float* __restrict__ eig_all, int w, int h, const int* __restrict__ maxord_all, double quality, unsigned long long* __restrict__ keys_all,
@@ -134,8 +139,7 @@ gftt_collect_kernel(const float* __restrict__ eig_all, int w, int h, const int* 
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int i0 = (blockIdx.x * 4 + wv) * (64 * GC_PX) + lane;         // the lane's first pixel; + 64 j
     const int np = w * h;
-    const int mo = maxord_all[f]; const float mx = __int_as_float(mo >= 0 ? mo : mo ^ 0x7FFFFFFF);
-    const float thr = (float)((double)fmaxf(mx, 0.f) * quality);
+    const float thr = gftt_threshold(maxord_all[f], quality);
     bool keep[GC_PX]; float v[GC_PX];
 #pragma unroll
     for (int j = 0; j < GC_PX; j++) {
@@ -281,19 +285,106 @@ gftt_round_kernel(const int* __restrict__ count_all, int cap, const uint32_t* __
     if (rejected) __atomic_store_n(&state[i], (uint8_t)3, __ATOMIC_RELAXED);
     else if (!blocked) __atomic_store_n(&state[i], (uint8_t)2, __ATOMIC_RELAXED);
 }
+// A frame with more candidates than the list holds.  The 3x3 maxima keep ties, so every pixel of a plateau of equal eigenvalues is a candidate (2 x 2-pixel
+// checkerboard cells: ~ one per pixel, far beyond w*h/4 + 1024).  The frame's finish block then redoes the whole selection on the PIXEL grid, without the list
+// or the dependency lists: cand_at holds each pixel's state (0 no candidate, 1 undecided, 2 kept, 3 rejected), keys are made from the eigenvalue map, and an
+// undecided candidate scans its window every round.  The scan stops at the first undecided stronger neighbour (a later round decides the candidate).  The kept
+// corners go to the list, the `cap` strongest of them when more are kept (cap >= maxc >= max_corners: the rank kernel outputs no more than that), found by
+// building the cap-th largest kept key bit by bit.  The map is zero again at the end.  Slow (one block, a pass over the frame per round), but only such
+// frames take it.
+__device__ void gftt_select_pixels(const float* __restrict__ eig, int w, int h, float thr, float min_distance, int cap, int* state, unsigned long long* kept,
+                                   int* s_pending, int* s_nkept)
+{
+    const int tid = threadIdx.x, np = w * h;
+    auto key_of = [&](int p) { return ((unsigned long long)__float_as_uint(eig[p]) << 32) | (0xFFFFFFFFu - (unsigned)p); };
+    for (int p = tid; p < np; p += 1024) {                    // the candidates of gftt_collect_kernel
+        const int y = p / w, x = p - y * w;
+        int s = 0;
+        if (y >= 1 && y < h - 1 && x >= 1 && x < w - 1) {
+            const float v = eig[p];
+            if (v > thr) {
+                float m = 0.f;
+                for (int a = -1; a <= 1; a++)
+                    for (int k = -1; k <= 1; k++) { float qv = eig[p + a * w + k]; qv = qv > thr ? qv : 0.f; m = fmaxf(m, qv); }
+                s = v == m ? 1 : 0;
+            }
+        }
+        state[p] = s;
+    }
+    __syncthreads();
+    const float md2 = min_distance * min_distance;
+    const int rad = (int)ceilf(min_distance);
+    for (;;) {
+        for (int p = tid; p < np; p += 1024) {
+            if (__atomic_load_n(&state[p], __ATOMIC_RELAXED) != 1) continue;
+            const unsigned long long key = key_of(p);
+            const int y = p / w, x = p - y * w;
+            bool blocked = false, rejected = false;
+            for (int dy = -rad; dy <= rad && !blocked && !rejected; dy++) {
+                const int yy = y + dy;
+                if (yy < 0 || yy >= h) continue;
+                for (int dx = -rad; dx <= rad; dx++) {
+                    const int xx = x + dx;
+                    if (xx < 0 || xx >= w || (dx == 0 && dy == 0)) continue;
+                    if ((float)dx * (float)dx + (float)dy * (float)dy >= md2) continue;
+                    const int q = yy * w + xx;
+                    const int sq = __atomic_load_n(&state[q], __ATOMIC_RELAXED);
+                    if (sq == 0 || sq == 3 || key_of(q) < key) continue;
+                    if (sq == 2) rejected = true; else blocked = true;
+                    break;
+                }
+            }
+            if (rejected) __atomic_store_n(&state[p], 3, __ATOMIC_RELAXED);
+            else if (!blocked) __atomic_store_n(&state[p], 2, __ATOMIC_RELAXED);
+            else *s_pending = 1;
+        }
+        __syncthreads();
+        const int pending = *s_pending;
+        __syncthreads();
+        if (!pending) break;
+        if (tid == 0) *s_pending = 0;
+        __syncthreads();
+    }
+    // how many are kept; above cap, the cap-th largest kept key t (keys are distinct: the largest t with cap kept keys >= t)
+    auto count_from = [&](unsigned long long t) {
+        int n = 0;
+        for (int p = tid; p < np; p += 1024) n += state[p] == 2 && key_of(p) >= t;
+        if (tid == 0) *s_nkept = 0;
+        __syncthreads();
+        if (n) atomicAdd(s_nkept, n);
+        __syncthreads();
+        const int total = *s_nkept;
+        __syncthreads();
+        return total;
+    };
+    unsigned long long t = 0;
+    if (count_from(0) > cap)
+        for (int b = 63; b >= 0; b--) { const unsigned long long u = t | (1ull << b); if (count_from(u) >= cap) t = u; }
+    if (tid == 0) *s_nkept = 0;
+    __syncthreads();
+    for (int p = tid; p < np; p += 1024) {
+        if (state[p] == 2) { const unsigned long long key = key_of(p); if (key >= t) kept[atomicAdd(s_nkept, 1)] = key; }
+        state[p] = 0;
+    }
+}
 __global__ void __launch_bounds__(1024)
 gftt_finish_kernel(int w, int h, const unsigned long long* __restrict__ keys_all, const int* __restrict__ count_all, int cap, float min_distance,
                    int* __restrict__ cand_at_all, const uint32_t* __restrict__ deps_all, const uint8_t* __restrict__ depn_all, uint8_t* __restrict__ state_all,
-                   unsigned long long* __restrict__ kept_all, int* __restrict__ nkept_all, int* __restrict__ overflow)
+                   unsigned long long* __restrict__ kept_all, int* __restrict__ nkept_all, const float* __restrict__ eig_all, const int* __restrict__ maxord_all, double quality)
 {
     __shared__ int s_pending, s_nkept;
     const int f = blockIdx.x, tid = threadIdx.x;
     int* cand_at = cand_at_all + (size_t)f * w * h; uint8_t* state = state_all + (size_t)f * cap;
     const unsigned long long* keys = keys_all + (size_t)f * cap; unsigned long long* kept = kept_all + (size_t)f * cap;
-    int nc = count_all[f];
-    if (nc > cap) { nc = cap; if (tid == 0) atomicOr(overflow, 1); }       // candidate buffer too small: reported by the host
+    const int nc = count_all[f];
     if (tid == 0) { s_pending = 0; s_nkept = 0; }
     __syncthreads();
+    if (nc > cap) {                                           // (block-uniform) the list is incomplete: the selection on the pixel grid
+        gftt_select_pixels(eig_all + (size_t)f * w * h, w, h, gftt_threshold(maxord_all[f], quality), min_distance, cap, cand_at, kept, &s_pending, &s_nkept);
+        __syncthreads();
+        if (tid == 0) nkept_all[f] = s_nkept;
+        return;
+    }
     const float md2 = min_distance * min_distance;
     const int rad = (int)ceilf(min_distance);
     for (;;) {
@@ -742,8 +833,8 @@ hipError_t k_quad_pyramids(const QuadBatch& q, int nb, hipStream_t s)
     return hipGetLastError();
 }
 // cv::goodFeaturesToTrack on the left image of frames [0, nb): pts[f][stride] (x, y), ncorner[f].  Workspace (GfttWork): eig nb*w*h floats; cand_at
-// nb*w*h ints, ZERO on entry (left zeroed); keys / kept nb*cap u64; deps nb*cap*GFTT_DEPS u32; depn / state nb*cap bytes; maxord / count / nkept nb ints;
-// overflow 1 int (set when a frame has more than cap candidates)
+// nb*w*h ints, ZERO on entry (left zeroed); keys / kept nb*cap u64 (cap >= max_corners); deps nb*cap*GFTT_DEPS u32; depn / state nb*cap bytes; maxord / count /
+// nkept nb ints.  A frame with more than cap candidates is selected on the pixel grid by its finish block (gftt_select_pixels)
 size_t k_quad_gftt_bits_words(int w, int h) { return ((size_t)w * h + 256 * GC_PX - 1) / (256 * GC_PX) * (8 * GC_PX) + 2; }      // whole blocks of gftt_collect_kernel (256 x GC_PX pixels) + the word a window may read past the end
 size_t k_quad_gftt_deps_per_candidate() { return GFTT_DEPS; }
 hipError_t k_quad_gftt(const QuadBatch& q, int nb, int max_corners, double quality, double min_distance, const GfttWork& g, float* pts, int stride, int* ncorner, hipStream_t s)
@@ -760,7 +851,7 @@ hipError_t k_quad_gftt(const QuadBatch& q, int nb, int max_corners, double quali
     const dim3 gc((cap + 255) / 256, nb);
     gftt_deps_kernel<<<gc, 256, 0, s>>>(w, h, g.keys, g.count, cap, (float)min_distance, g.cand_at, g.cand_bits, bw, g.deps, g.depn, g.state);
     for (int r = 0; r < GFTT_ROUNDS; r++) gftt_round_kernel<<<gc, 256, 0, s>>>(g.count, cap, g.deps, g.depn, g.state);
-    gftt_finish_kernel<<<nb, 1024, 0, s>>>(w, h, g.keys, g.count, cap, (float)min_distance, g.cand_at, g.deps, g.depn, g.state, g.kept, g.nkept, g.overflow);
+    gftt_finish_kernel<<<nb, 1024, 0, s>>>(w, h, g.keys, g.count, cap, (float)min_distance, g.cand_at, g.deps, g.depn, g.state, g.kept, g.nkept, g.eig, g.maxord, quality);
     gftt_rank_kernel<<<gc, 256, 0, s>>>(g.kept, g.nkept, cap, w, max_corners, pts, stride, ncorner);
     return hipGetLastError();
 }

@@ -311,7 +311,6 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
     int* parent = (int*)q; q += al(np * 4);
     int* count = (int*)q; q += al(np * 4);
     unsigned* sweep_flags = (unsigned*)q;                     // 256 bytes of flags, then the sweep's mailboxes
-    const dim3 gimg((w + 255) / 256, h, nb);
     {
         int TX = 0; size_t lds = 0;
         if (!sgbm_cost_geometry(D, SW, &TX, &lds)) return hipErrorInvalidValue;
@@ -358,14 +357,20 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
         default: return hipErrorInvalidValue;
     }
     if (e != hipSuccess || raw_only == 1) return e;
-    sgbm_median3<<<gimg, 256, 0, s>>>(d_raw, w, h, disp_out);
-    if (p.speckleWindowSize > 0 && raw_only != 2) {
-        const int n = (int)np1; const dim3 gb((n + 255) / 256, nb);
-        sgbm_speckle_tile<<<dim3((w + SPK_TW - 1) / SPK_TW, (h + SPK_TH - 1) / SPK_TH, nb), 256, 0, s>>>(disp_out, w, h, INVALID, SG_DISP_SCALE * p.speckleRange, parent, count);
+    return k_sgbm_post(d_raw, disp_out, w, h, nb, 1 | (p.speckleWindowSize > 0 && raw_only != 2 ? 2 : 0), INVALID, p.speckleWindowSize, SG_DISP_SCALE * p.speckleRange,
+                       parent, count, s);
+}
+// the last steps of k_sgbm on nb stacked maps: op bit 0 = medianBlur 3 (src -> dst), bit 1 = filterSpeckles in place on dst.  parent / count: nb*w*h ints each
+hipError_t k_sgbm_post(const int16_t* src, int16_t* dst, int w, int h, int nb, int op, int newVal, int maxSpeckleSize, int maxDiff, int* parent, int* count, hipStream_t s)
+{
+    if (op & 1) sgbm_median3<<<dim3((w + 255) / 256, h, nb), 256, 0, s>>>(src, w, h, dst);
+    if (op & 2) {
+        const int n = w * h; const dim3 gb((n + 255) / 256, nb);
+        sgbm_speckle_tile<<<dim3((w + SPK_TW - 1) / SPK_TW, (h + SPK_TH - 1) / SPK_TH, nb), 256, 0, s>>>(dst, w, h, newVal, maxDiff, parent, count);
         const int nedge = ((w - 1) / SPK_TW) * h + ((h - 1) / SPK_TH) * w;
-        if (nedge > 0) sgbm_speckle_edges<<<dim3((nedge + 255) / 256, nb), 256, 0, s>>>(disp_out, w, h, INVALID, SG_DISP_SCALE * p.speckleRange, parent);
+        if (nedge > 0) sgbm_speckle_edges<<<dim3((nedge + 255) / 256, nb), 256, 0, s>>>(dst, w, h, newVal, maxDiff, parent);
         sgbm_speckle_count<<<gb, 256, 0, s>>>(n, parent, count);
-        sgbm_speckle_apply<<<gb, 256, 0, s>>>(disp_out, n, INVALID, p.speckleWindowSize, parent, count);
+        sgbm_speckle_apply<<<gb, 256, 0, s>>>(dst, n, newVal, maxSpeckleSize, parent, count);
     }
     return hipGetLastError();
 }

@@ -130,9 +130,6 @@ int check_device_flags(ssm_ctx* c, bool with_map)
     HIPCHK(c, hipMemcpy(&st, c->d_status, 4, hipMemcpyDeviceToHost));
     if (st) { hipMemset(c->d_status, 0, 4); FAIL(c, SSM_E_CAPACITY, "ORB scratch capacity exceeded (status " + std::to_string(st) + ")"); }
     if (c->stereo) {
-        int32_t ov = 0;
-        HIPCHK(c, hipMemcpy(&ov, c->stereo->overflow, 4, hipMemcpyDeviceToHost));
-        if (ov) { hipMemset(c->stereo->overflow, 0, 4); FAIL(c, SSM_E_CAPACITY, "goodFeaturesToTrack: more corner candidates than the buffer holds (w*h/4 + 1024)"); }
         if (c->stereo->sg_fail) { const int r = sgbm_recover(c); if (r) return r; }
     }
     if (with_map) {

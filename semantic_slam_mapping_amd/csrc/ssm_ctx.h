@@ -47,7 +47,7 @@ struct StereoState {        // workspace of the stereo path (quad matcher, SGBM 
     QuadBatch qb{};                          // image slots: 2 sides x (B + 1) pyramids + Scharr derivatives
     uint8_t* pyr = nullptr; int16_t* der = nullptr;
     GfttWork gw{};                           // goodFeaturesToTrack workspace (kernels_quad.hip)
-    int keycap = 0; int *overflow = nullptr, *ncorner = nullptr, *has_prev = nullptr;
+    int keycap = 0; int *ncorner = nullptr, *has_prev = nullptr;
     int* sg_fail = nullptr;                  // SG_FAIL_WORDS words: word (sub-batch index mod SG_FAIL_WORDS) is set by that sub-batch's sgbm_sweep when a strip hand-off times out (kernels_sgbm.hip)
     // the depth stage of the most recent sequence call, kept so that sub-batches whose sweep timed out can be repeated in form 1 once the call is known to have
     // failed (ssm_sync / check_device_flags: the caller's input buffers must stay untouched until then, as for any asynchronous call)

@@ -146,6 +146,8 @@ bool sgbm_cost_geometry(int D, int SW, int* TX_out, size_t* lds_out);      // fa
 // fail_flag: device int the sweep kernel ORs 1 into when a strip hand-off times out (never on a healthy device; the host turns it into SSM_E_HIP)
 hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int nb, const ssm_sgbm_params& p, void* workspace, size_t ws_bytes, int16_t* disp_out, int raw_only, hipStream_t s, int* fail_flag = nullptr,
                   int form_cfg = 0, int concurrent = 1);
+// medianBlur 3 (op bit 0: src -> dst) and / or filterSpeckles (bit 1: in place on dst) on nb stacked w x h maps, launched as k_sgbm's last steps; parent / count nb*w*h ints
+hipError_t k_sgbm_post(const int16_t* src, int16_t* dst, int w, int h, int nb, int op, int newVal, int maxSpeckleSize, int maxDiff, int* parent, int* count, hipStream_t s);
 hipError_t k_sgbm_depth(const int16_t* disp, int w, int h, int nb, double baseline, double cu, double cv, double f, double roix, double roiy, double roiz, double scale,
                         int* min_scratch /* nb ints */, uint16_t* depth, hipStream_t s);
 hipError_t k_vo_estimate(const ssm_pmatch* m, int n, const ssm_vo_params& P, const int32_t* samples, int iters,
@@ -170,7 +172,7 @@ hipError_t k_segnet_color(const uint8_t* ids, int n, int sw, int sh, int dw, int
 // Slot 0 = the carried previous frame, slot 1 + f = frame f of the sub-batch.
 struct QuadBatch { const uint8_t* pyr; const int16_t* der; size_t slot_elems; int B1; int w[4], h[4], off[4]; };
 hipError_t k_quad_pyramids(const QuadBatch& q, int nb, hipStream_t s);
-struct GfttWork { float* eig; int* cand_at; uint32_t* cand_bits; /* one bit per pixel: cand_at != 0; k_quad_gftt_bits_words(w, h) words per frame */ unsigned long long *keys, *kept; uint32_t* deps; uint8_t *depn, *state; int *maxord, *count, *nkept, *overflow; int cap; };
+struct GfttWork { float* eig; int* cand_at; uint32_t* cand_bits; /* one bit per pixel: cand_at != 0; k_quad_gftt_bits_words(w, h) words per frame */ unsigned long long *keys, *kept; uint32_t* deps; uint8_t *depn, *state; int *maxord, *count, *nkept; int cap; };
 size_t k_quad_gftt_deps_per_candidate();
 size_t k_quad_gftt_bits_words(int w, int h);
 hipError_t k_quad_gftt(const QuadBatch& q, int nb, int max_corners, double quality, double min_distance, const GfttWork& g, float* pts, int stride, int* ncorner, hipStream_t s);

@@ -5,7 +5,7 @@
 // ---------------------------------------------------------------- stereo path: QuadFeatureMatch, StereoSGBM depth, VisualOdometryStereo
 void stereo_free(StereoState* q)
 {
-    void* p[] = { q->pyr, q->der, q->gw.eig, q->gw.cand_at, q->gw.cand_bits, q->gw.keys, q->gw.kept, q->gw.deps, q->gw.depn, q->gw.state, q->gw.maxord, q->gw.count, q->gw.nkept, q->overflow, q->sg_fail, q->ncorner, q->has_prev, q->pts, q->status, q->err,
+    void* p[] = { q->pyr, q->der, q->gw.eig, q->gw.cand_at, q->gw.cand_bits, q->gw.keys, q->gw.kept, q->gw.deps, q->gw.depn, q->gw.state, q->gw.maxord, q->gw.count, q->gw.nkept, q->sg_fail, q->ncorner, q->has_prev, q->pts, q->status, q->err,
                   q->tr_all, q->vcount, q->rand_off, q->consumed, q->sg_wsN[0], q->dminN[0], q->sg_wsN[1], q->dminN[1], q->sg_wsN[2], q->dminN[2], q->quad, q->nquad, q->corners, q->ncorners, q->disp, q->depth, q->tr,
                   q->inliers, q->vo_result, q->in_stage };
     for (void* x : p) if (x) hipFree(x);
@@ -27,15 +27,15 @@ static int stereo_init(ssm_ctx* c, int w, int h, int maxc, bool exact = false)
     DALLOC(c, q->pyr, (size_t)2 * b.B1 * b.slot_elems); DALLOC(c, q->der, (size_t)2 * b.B1 * b.slot_elems * 2);
     b.pyr = q->pyr; b.der = q->der;
     const size_t np = (size_t)w * h;
-    q->keycap = w * h / 4 + 1024;                            // 3x3 local maxima: at most one per 2x2 pixels
+    // candidate list of a frame: 3x3 maxima keep ties, so a plateau of equal eigenvalues makes almost every pixel a candidate; a frame with more than this is
+    // selected on the pixel grid instead (gftt_select_pixels), whose kept corners must fit in the list up to max_corners
+    q->keycap = w * h / 4 + 1024 > maxc ? w * h / 4 + 1024 : maxc;
     GfttWork& g = q->gw; g.cap = q->keycap;
     DALLOC(c, g.eig, (size_t)B * np); DALLOC(c, g.cand_at, (size_t)B * np); DALLOC(c, g.keys, (size_t)B * q->keycap); DALLOC(c, g.kept, (size_t)B * q->keycap);
     DALLOC(c, g.deps, (size_t)B * q->keycap * k_quad_gftt_deps_per_candidate()); DALLOC(c, g.depn, (size_t)B * q->keycap); DALLOC(c, g.state, (size_t)B * q->keycap);
     HIPCHK(c, hipMemset(g.cand_at, 0, (size_t)B * np * 4));      // gftt_finish_kernel keeps the map zeroed between calls
     DALLOC(c, g.cand_bits, (size_t)B * k_quad_gftt_bits_words(w, h));
-    DALLOC(c, g.maxord, B); DALLOC(c, g.count, B); DALLOC(c, g.nkept, B); DALLOC(c, q->overflow, 1); DALLOC(c, q->sg_fail, SG_FAIL_WORDS); DALLOC(c, q->ncorner, B); DALLOC(c, q->has_prev, B);
-    g.overflow = q->overflow;
-    HIPCHK(c, hipMemset(q->overflow, 0, 4));
+    DALLOC(c, g.maxord, B); DALLOC(c, g.count, B); DALLOC(c, g.nkept, B); DALLOC(c, q->sg_fail, SG_FAIL_WORDS); DALLOC(c, q->ncorner, B); DALLOC(c, q->has_prev, B);
     HIPCHK(c, hipMemset(q->sg_fail, 0, 4 * SG_FAIL_WORDS));
     DALLOC(c, q->pts, (size_t)5 * B * maxc * 2); DALLOC(c, q->status, maxc); DALLOC(c, q->err, maxc);
     DALLOC(c, q->rand_off, B); DALLOC(c, q->consumed, 1);
@@ -406,6 +406,25 @@ extern "C" int ssm_stereo_depth(ssm_ctx* c, const uint8_t* left, const uint8_t* 
     memcpy(depth, c->h_pinned + 4 * np, np * 2);
     if (disp) memcpy(disp, c->h_pinned + 2 * np, np * 2);
     if (repeated) c->err = "note: the SGBM sweep of this pair timed out in a strip hand-off and was repeated with form 1 (results complete; " + std::to_string(c->sgbm_fallbacks) + " such repeats on this context so far)";
+    return SSM_OK;
+}
+// the SGBM post stages alone (exact tests of the median and of the speckle union-find on constructed maps): n stacked maps through k_sgbm_post
+extern "C" int ssm_debug_sgbm_post(ssm_ctx* c, const int16_t* disp, int w, int h, int n, int op, int new_val, int max_size, int max_diff, int16_t* out)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    if (!disp || !out || w < 1 || h < 1 || n < 1 || op < 1 || op > 3 || max_diff < 0 || new_val < -32768 || new_val > 32767) FAIL(c, SSM_E_INVAL, "bad arguments");
+    if (h > 65535 || n > 65535 || (long long)w * h >= (1ll << 30)) FAIL(c, SSM_E_INVAL, "map too large");
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t np = (size_t)w * h * n, b16 = al(np * 2), b32 = al(np * 4);
+    int r = ensure_scratch(c, 2 * b16 + 2 * b32); if (r) return r;
+    uint8_t* p = (uint8_t*)c->d_scratch;
+    int16_t* d_in = (int16_t*)p; int16_t* d_out = (int16_t*)(p + b16); int* parent = (int*)(p + 2 * b16); int* count = (int*)(p + 2 * b16 + b32);
+    HIPCHK(c, hipMemcpyAsync(d_in, disp, np * 2, hipMemcpyHostToDevice, c->stream));
+    if (!(op & 1)) HIPCHK(c, hipMemcpyAsync(d_out, d_in, np * 2, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, k_sgbm_post(d_in, d_out, w, h, n, op, new_val, max_size, max_diff, parent, count, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, d_out, np * 2, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
 }
 
