@@ -392,6 +392,12 @@ int ssm_segnet_debug_op(ssm_ctx* ctx, int op, int arg, const uint16_t* in, int H
  * calls run, > 0 = the fused kernel with that many bands (SSM_E_INVAL where the geometry has no fused form at that band count).  *bytes: one frame's
  * buffer (img and out both NULL: only that) */
 int ssm_debug_pyramid(ssm_ctx* ctx, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes);
+/* the FAST tile plan of a configuration, on the host only (no context, no device): for exact tests of the tiling.  Per tile, 16 ints:
+ * level, interior x0, x1, y0, y1 (half-open), scored rectangle xs0, xs1, ys0, ys1 (interior + 1 on each side, clipped to the FAST window
+ * [19, w - 19) x [19, h - 19)), 4-column groups, scored rows, cell columns and cell rows the scored rectangle touches, level w, h, stride.
+ * *ntiles: the tile count (tiles NULL: only that; SSM_E_INVAL when cap is smaller).  limits (6 ints, may be NULL): the static LDS bytes of the FAST
+ * kernel, the most groups and scored rows its arrays hold, the staged pixel row width and row count, the staging area (candidates) */
+int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int cap, int* ntiles, int32_t* limits);
 /* the SGBM post stages alone, as the last steps of ssm_sgbm launch them, on n stacked int16 maps (host, w x h each, rows packed) -> out (same shape):
  * op bit 0 = medianBlur 3x3 (replicate border), bit 1 = filterSpeckles (4-neighbours, both != new_val, |a - b| <= max_diff; components of at most
  * max_size pixels become new_val) on the median's output, or on the input without bit 0.  For exact tests of the kernels on constructed maps */

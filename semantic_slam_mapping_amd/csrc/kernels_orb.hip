@@ -684,8 +684,8 @@ hipError_t k_blur_mfma(int n, const OrbGeom& g, const uint8_t* pyr, uint8_t* blu
 //     pass 2 -- a second launch, because a cell spans tiles -- looks at the cells its tile touches, returns at once unless one of them stayed empty
 //     (cellmax <= ini), and otherwise runs the same steps at minThFAST on the positions of the empty cells only (their same-cell neighbours are in
 //     the same empty cell).  What pass 2 adds to cellmax is <= ini, so the consumer's rule and the emptiness test of other pass-2 tiles are unaffected.
-// One block per 128x32 tile of one level of one frame (all levels in one launch), tile + 4-px apron staged in LDS by
-// dword loads.
+// One block per tile of one level of one frame (all levels in one launch; tiles of at most 126 x 32 fitted to the FAST window, build_geometry),
+// tile + 4-px apron staged in LDS by 16-byte loads.
 // inclusive scan of a u32 across a wave64 (DPP Hillis-Steele inside the 16-lane rows, then row broadcasts)
 __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v)
 {
@@ -756,43 +756,43 @@ __device__ __forceinline__ uint32_t fast_S2(const uint8_t* pa, const uint8_t* pb
     // max(bright, -dark, +0): a positive denormal's bits ARE the integer
     return pk_max3h(bright, dark ^ 0x80008000u, 0u);
 }
-#define FT_W 128
-#define FT_H 32
-#define FT_PW (FT_W + 16)     // staged pixel row [tx0 - 4, tx0 + 140) = nine 16-byte words: 4-px apron each side (3 for the ring + 1 for the NMS neighbours)
-#define FT_PH (FT_H + 8)
-#define FT_SW (FT_W + 2)      // scored positions: tile + 1
-#define FT_SH (FT_H + 2)
-#define FT_SST 132
-#define FT_STAGE ((FT_PH * FT_PW) / 8)   // candidates staged per tile: as many as fit in the pixel tile they replace (680)
 template <int PASS>
 __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, const uint8_t* __restrict__ pyr, const OrbGeom& g, cand_t* __restrict__ cand,
                                           int32_t* __restrict__ ncand, int32_t* __restrict__ cellmax, int stage_cap)
 {
     __shared__ uint32_t emptyrow[8];                             // pass 2: bit j of word i = cell (cy0 + i, cx0 + j) had no corner at iniThFAST
     __shared__ __attribute__((aligned(16))) uint8_t px[FT_PH * FT_PW];
-    __shared__ __attribute__((aligned(16))) uint8_t sc[(FT_SH * FT_SST + 15) / 16 * 16];
-    __shared__ uint16_t list[FT_SW * FT_SH];
-    __shared__ int16_t cellx[FT_SW], celly[FT_SH];
+    __shared__ __attribute__((aligned(16))) uint8_t sc[(FT_SH + 2) * FT_SST];     // scores, with a 1-position border of zeros around the scored rectangle
+    __shared__ __attribute__((aligned(16))) uint16_t list[FT_SW * FT_SH];
+    __shared__ int16_t cellx[FT_SW + 2], celly[FT_SH + 2];
     __shared__ int lmax[64];
+    __shared__ int wsum[4];
     // occupancy is what this kernel lives on (LDS-limited: 27.5 KB gave 5 blocks per CU, 19.4 KB gives 8 = the 32-wave limit; 3.42 -> 2.7 us/frame),
     // so the candidate staging area reuses the pixel tile: px is dead once every position is scored, and the NMS pass that fills
-    // `stage` starts behind the barrier that ends the scoring loop
+    // `stage` starts behind the barrier that ends the scoring loop.  The pass-bit image of the quick test lives in the head of `list`: it is read
+    // into registers before the barrier behind which the position list is written
     cand_t* stage = reinterpret_cast<cand_t*>(px);
-    __shared__ int nlist, nsurv, nstage, gbase;
-    const int tid = threadIdx.x, lane = tid & 63;
+    uint8_t* bits = reinterpret_cast<uint8_t*>(list);
+    __shared__ int nsurv, nstage, gbase;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     int l = 0;
     while (l + 1 < g.nlevels && tile_id >= g.L[l+1].ftile_off) l++;
     const LevelGeom& L = g.L[l];
     const int t = tile_id - L.ftile_off;
     const int trow = L.ftiles_x == 1 ? t : (int)__umulhi((uint32_t)t, L.fmulTX);
-    const int tx0 = SSM_EDGE + (t - trow * L.ftiles_x) * FT_W, ty0 = SSM_EDGE + trow * FT_H;      // the grid starts at the first position FAST may report
+    int X0, X1, Y0, Y1;                                          // the interior: the positions this tile may report
+    ftile_rect(L, t - trow * L.ftiles_x, trow, X0, X1, Y0, Y1);
     const int w = L.w, h = L.h, stride = L.stride;
+    // the scored rectangle: the interior + the NMS neighbours around it, inside the FAST window (nothing outside it passes the quick test);
+    // G groups of 4 columns x R rows.  Coordinates below (rx, ry) are relative to (xs0, ys0)
+    const int xs0 = max(X0 - 1, SSM_EDGE), xs1 = min(X1 + 1, w - SSM_EDGE), ys0 = max(Y0 - 1, SSM_EDGE), ys1 = min(Y1 + 1, h - SSM_EDGE);
+    const int G = (xs1 - xs0 + 3) >> 2, R = ys1 - ys0;
     const uint8_t* im = pyr + (size_t)frame * g.pyr_bytes + L.img_off;
+    // the first cell of the interior in x and y (cells: build_geometry; the scored rectangle touches at most 8 x 8 from cx0 - 1 / cy0 - 1 on)
+    const int cx0 = (int)__umulhi((uint32_t)(X0 - L.minBX - 3), L.mulW), cy0 = (int)__umulhi((uint32_t)(Y0 - L.minBY - 3), L.mulH);
     if (PASS == 2) {
-        // the cells this tile touches: cells of its first and last scored position in x and y (at most 8 x 8: build_geometry)
-        auto cell_of = [](int gpos, int origin, uint32_t mul) { const int v = gpos - origin - 3; return v >= 0 ? (int)__umulhi((uint32_t)v, mul) : 0; };
-        const int cx0 = cell_of(tx0, L.minBX, L.mulW), cy0 = cell_of(ty0, L.minBY, L.mulH);
-        const int cx1 = min(cell_of(min(tx0 + FT_W - 1, w - 1), L.minBX, L.mulW), L.nCols - 1), cy1 = min(cell_of(min(ty0 + FT_H - 1, h - 1), L.minBY, L.mulH), L.nRows - 1);
+        // the cells of the interior's first and last position in x and y
+        const int cx1 = min((int)__umulhi((uint32_t)(X1 - 1 - L.minBX - 3), L.mulW), L.nCols - 1), cy1 = min((int)__umulhi((uint32_t)(Y1 - 1 - L.minBY - 3), L.mulH), L.nRows - 1);
         bool mine = false;
         if (tid < 64) {
             const int ci = cy0 + (tid >> 3), cj = cx0 + (tid & 7);
@@ -802,45 +802,39 @@ __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, co
         if (tid < 8) emptyrow[tid] = (uint32_t)((bal >> (8 * tid)) & 0xFFull);
         if (!__syncthreads_or(mine ? 1 : 0)) return;             // every cell of the tile has its corners from pass 1 (block-uniform)
     }
-    // ---- stage the tile: nine (unaligned) 16-byte loads per row, 360 per tile.  Rows / words outside the image are CLAMPED into it instead of
-    // zero-filled: they then hold shifted pixels, which no valid position ever looks at (valid positions sit >= 19 px from every border, the ring and
-    // the NMS neighbours reach 4), and no address leaves the level image
-    for (int i = tid; i < FT_PH * (FT_PW / 16); i += 256) {
+    // ---- stage the tile: nine (unaligned) 16-byte loads per row.  Rows / words outside the image are CLAMPED into it instead of zero-filled: they
+    // then hold shifted pixels, which no scored position ever looks at (scored positions sit >= 19 px from every border, the ring reaches 3), and no
+    // address leaves the level image
+    for (int i = tid; i < (R + 6) * (FT_PW / 16); i += 256) {
         const int ly = (i * 7282) >> 16, c = i - ly * (FT_PW / 16);                 // i / 9 for i < 360
-        const int gy = min(max(ty0 - 4 + ly, 0), h - 1), gx = min(max(tx0 - 4 + 16 * c, 0), stride - 16);
+        const int gy = min(max(ys0 - 3 + ly, 0), h - 1), gx = min(max(xs0 - 4 + 16 * c, 0), stride - 16);
         uint4 v; __builtin_memcpy(&v, im + (size_t)gy * stride + gx, 16);
         reinterpret_cast<uint4*>(px)[i] = v;
     }
-    for (int i = tid; i < (FT_SH * FT_SST + 15) / 16; i += 256) reinterpret_cast<uint4*>(sc)[i] = make_uint4(0, 0, 0, 0);
+    for (int i = tid; i < (FT_SH + 2) * FT_SST / 16; i += 256) reinterpret_cast<uint4*>(sc)[i] = make_uint4(0, 0, 0, 0);
+    if (tid < R * FT_BW / 16) reinterpret_cast<uint4*>(bits)[tid] = make_uint4(0, 0, 0, 0);
     // (cell index by multiplication with the host's reciprocal: the two integer divisions cost every wave ~70 instructions)
-    if (tid < FT_SW) { const int gx = tx0 + tid - 1 - L.minBX - 3; cellx[tid] = (int16_t)(gx >= 0 ? (int)__umulhi((uint32_t)gx, L.mulW) : -1); }
-    if (tid < FT_SH) { const int gy = ty0 + tid - 1 - L.minBY - 3; celly[tid] = (int16_t)(gy >= 0 ? (int)__umulhi((uint32_t)gy, L.mulH) : -1); }
+    if (tid < FT_SW + 2) { const int gx = xs0 - 1 + tid - L.minBX - 3; cellx[tid] = (int16_t)(gx >= 0 ? (int)__umulhi((uint32_t)gx, L.mulW) : -1); }
+    if (tid < FT_SH + 2) { const int gy = ys0 - 1 + tid - L.minBY - 3; celly[tid] = (int16_t)(gy >= 0 ? (int)__umulhi((uint32_t)gy, L.mulH) : -1); }
     if (tid < 64) lmax[tid] = 0;
-    if (tid == 0) { nlist = 0; nsurv = 0; nstage = 0; gbase = 0; }
+    if (tid < 4) wsum[tid] = 0;
+    if (tid == 0) { nsurv = 0; nstage = 0; gbase = 0; }
     __syncthreads();
-    // ---- quick reject + compaction of the positions worth scoring.  A position passes when two ADJACENT compass points of
-    // the ring (N, E, S, W at distance 3) are both brighter than v + t or both darker than v - t (necessary for a 9-arc).
-    // Four horizontally adjacent positions per thread: five dword LDS reads (the centre dword, its left/right neighbours and
-    // the dwords 3 rows up/down), bytes widened to packed u16 pairs, then packed 16-bit min/max:
+    // ---- quick reject.  A position passes when two ADJACENT compass points of the ring (N, E, S, W at distance 3) are both brighter than v + t or
+    // both darker than v - t (necessary for a 9-arc).  Four horizontally adjacent positions per work item: five dword LDS reads (the centre dword,
+    // its left/right neighbours and the dwords 3 rows up/down), bytes widened to packed u16 pairs, then packed 16-bit min/max:
     //   bright = max over adjacent pairs of min(x - v, y - v),  dark = max over pairs of min(v - x, v - y) = -min over pairs of max
-    // thread = (group of 4 columns g = tid & 31, row tid >> 5 + 8k): no division, conflict-free rows.
+    // Work item p = (row p / G, group p % G): only the groups of the scored rectangle take lanes.  The 4 pass bits of a group go to one byte of the
+    // bit image (row-major, FT_BW bytes per row); no compaction here
     const int min_th = PASS == 1 ? g.ini_th : g.min_th;         // the threshold of this pass
-    const int pcx0 = max((int)cellx[1], 0), pcy0 = max((int)celly[1], 0);
     {
         const uint32_t* pxw = reinterpret_cast<const uint32_t*>(px);
-        const int gq = tid & 31, r0 = tid >> 5;
-        int cjs[4];                                                     // pass 2: the cell columns of this thread's four positions, relative to the tile's first cell
-#pragma unroll
-        for (int j = 0; j < 4; j++) cjs[j] = PASS == 2 ? ((int)cellx[4 * gq + 1 + j] - pcx0) & 7 : 0;
         const uint32_t t1 = (uint32_t)(min_th + 1) * 0x00010001u;
-        const int gx0 = tx0 + 4 * gq;                                   // first of the 4 positions; sx = 4 gq + 1 + j
-        unsigned xvalid = 0;                                            // positions inside the FAST window of the level, in x (the same for every row)
-#pragma unroll
-        for (int j = 0; j < 4; j++) if (gx0 + j >= SSM_EDGE && gx0 + j < w - SSM_EDGE) xvalid |= 1u << j;
+        const float rG = __builtin_amdgcn_rcpf((float)G);      // (p + 0.5) / G is >= 1/64 away from an integer for p < 2048, G <= 32: exact quotient
 #pragma unroll 1
-        for (int sy = r0; sy < FT_SH; sy += 8) {
-            const int gy = ty0 + sy - 1;
-            const int rowc = (sy + 3) * (FT_PW / 4) + gq + 1;
+        for (int p = tid; p < R * G; p += 256) {
+            const int ry = (int)(((float)p + 0.5f) * rG), k = p - ry * G;
+            const int rowc = (ry + 3) * (FT_PW / 4) + k + 1;
             const uint32_t C = pxw[rowc], P = pxw[rowc - 1], Nx = pxw[rowc + 1];
             const uint32_t U = pxw[rowc - 3 * (FT_PW / 4)], D = pxw[rowc + 3 * (FT_PW / 4)];
             const uint32_t Lw = __builtin_amdgcn_alignbyte(C, P, 1);     // pixels x-3 of the four positions
@@ -863,94 +857,97 @@ __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, co
                 passbits |= ((~eb >> 15) & 1u) << (2 * hpair);
                 passbits |= ((~eb >> 31) & 1u) << (2 * hpair + 1);
             }
-            // positions outside the FAST window of the level never pass
-            passbits &= (gy >= SSM_EDGE && gy < h - SSM_EDGE) ? xvalid : 0u;
+            // positions right of the scored rectangle (last group only) never pass
+            passbits &= 15u >> max(4 - (xs1 - xs0 - 4 * k), 0);
             if (PASS == 2) {                                            // only the cells that stayed empty at iniThFAST are retried
-                const uint32_t er = emptyrow[((int)celly[sy] - pcy0) & 7];
+                const uint32_t er = emptyrow[((int)celly[ry + 1] - cy0) & 7];
                 unsigned m = 0;
 #pragma unroll
-                for (int j = 0; j < 4; j++) m |= ((er >> cjs[j]) & 1u) << j;
+                for (int j = 0; j < 4; j++) m |= ((er >> (((int)cellx[4 * k + 1 + j] - cx0) & 7)) & 1u) << j;
                 passbits &= m;
             }
-            // compaction: wave scan of the per-thread counts, one LDS reservation per wave
-            const uint32_t cntp = __popc(passbits);
-            const uint32_t incl = wave_incl_scan_u32(cntp);
-            const uint32_t tot = __shfl(incl, 63, 64);
-            if (tot) {
-                int base = 0;
-                if (lane == 0) base = atomicAdd(&nlist, (int)tot);
-                base = __shfl(base, 0, 64) + (int)(incl - cntp);
-#pragma unroll
-                for (int j = 0; j < 4; j++) if (passbits & (1u << j)) list[base++] = (uint16_t)((sy << 8) | (4 * gq + 1 + j));
-            }
-        }
-        // the two apron columns sx = 0 and sx = FT_W + 1 (scored only as NMS neighbours)
-        if (tid < 2 * FT_SH) {
-            const int sy = tid >> 1, sx = (tid & 1) ? FT_W + 1 : 0;
-            const int gx = tx0 + sx - 1, gy = ty0 + sy - 1;
-            if (gx >= SSM_EDGE && gx < w - SSM_EDGE && gy >= SSM_EDGE && gy < h - SSM_EDGE &&
-                (PASS == 1 || ((emptyrow[((int)celly[sy] - pcy0) & 7] >> (((int)cellx[sx] - pcx0) & 7)) & 1u))) {
-                const uint8_t* p = &px[(sy + 3) * FT_PW + sx + 3];
-                const int v = p[0];
-                const int a = p[3 * FT_PW] - v, b = p[3] - v, c = p[-3 * FT_PW] - v, d = p[-3] - v;
-                const int br = min(max(a, c), max(b, d));
-                const int dk = max(min(a, c), min(b, d));
-                if (max(br, -dk) > min_th) list[atomicAdd(&nlist, 1)] = (uint16_t)((sy << 8) | sx);
-            }
+            bits[ry * FT_BW + k] = (uint8_t)passbits;
         }
     }
     __syncthreads();
-    const int n = nlist;
-    // ---- score the listed positions, two per lane (fast_S2), and compact the ones that can become keypoints (S > minThFAST, inside the tile and the
-    // image) to the front of the same list: a chunk's entries are all read before the barrier, survivors are written behind it into slots below the
-    // chunk's end (there are never more survivors than entries processed), so the NMS pass below walks ~10 % of the positions instead of ~23 %
+    // ---- one compaction of the bit image into the position list (row-major order; nothing downstream depends on the order inside a tile):
+    // thread = (row tid >> 2, groups 8 (tid & 3) .. + 7) = 32 positions, one block-wide scan of the counts, then each thread writes its entries
+    int n;
+    {
+        uint32_t m = 0, cnt = 0, incl = 0;
+        if (wv * 64 < R * 4) {                                          // wave-uniform: the rows of the tile take R * 4 threads
+            if (tid < R * 4) {
+                const uint2 d = reinterpret_cast<const uint2*>(bits)[tid];
+                // the low nibbles of the 8 bytes in order -> bit b = position rx = 32 (tid & 3) + b
+                m = __builtin_amdgcn_perm(d.y | (d.y >> 4), d.x | (d.x >> 4), 0x06040200u);
+            }
+            cnt = __popc(m);
+            incl = wave_incl_scan_u32(cnt);
+            if (lane == 63) wsum[wv] = (int)incl;
+        }
+        __syncthreads();                                                // the bit image has been read: the list may overwrite it
+        const int w0 = wsum[0], w1 = wsum[1], w2 = wsum[2];
+        n = w0 + w1 + w2 + wsum[3];
+        int base = (int)(incl - cnt) + (wv > 0 ? w0 : 0) + (wv > 1 ? w1 : 0) + (wv > 2 ? w2 : 0);
+        const uint32_t ent = ((uint32_t)(tid >> 2) << 8) | (uint32_t)(32 * (tid & 3));
+        while (m) { list[base++] = (uint16_t)(ent + (uint32_t)__builtin_ctz(m)); m &= m - 1u; }
+    }
+    __syncthreads();
+    // ---- score the listed positions, two per lane (fast_S2), and compact the ones that can become keypoints (S > minThFAST, inside the interior)
+    // to the front of the same list: a chunk's entries are all read before the barrier, survivors are written behind it into slots below the
+    // chunk's end (there are never more survivors than entries processed), so the NMS pass below walks ~10 % of the positions instead of ~23 %.
+    // A chunk of m <= 512 entries pairs entry e with e + ceil(m / 2): only ceil(m / 128) waves score
+    const int ix0 = X0 - xs0, iw = X1 - X0, iy0 = Y0 - ys0, ih = Y1 - Y0;
     for (int e0 = 0; e0 < n; e0 += 512) {
-        const int ea = e0 + tid, eb = e0 + 256 + tid;
-        const int ia = list[min(ea, n - 1)], ib = list[min(eb, n - 1)];
-        const int sya = ia >> 8, sxa = ia & 255, syb = ib >> 8, sxb = ib & 255;
-        const uint32_t S2 = fast_S2(&px[(sya + 3) * FT_PW + sxa + 3], &px[(syb + 3) * FT_PW + sxb + 3], FT_PW);
-        const int Sa = (int)(S2 & 0xFFFFu), Sb = (int)(S2 >> 16);
-        if (ea < n) sc[sya * FT_SST + sxa] = (uint8_t)Sa;
-        if (eb < n) sc[syb * FT_SST + sxb] = (uint8_t)Sb;
-        const bool ka = ea < n && Sa > min_th && sxa >= 1 && sxa <= FT_W && sya >= 1 && sya <= FT_H && tx0 + sxa - 1 < w && ty0 + sya - 1 < h;
-        const bool kb = eb < n && Sb > min_th && sxb >= 1 && sxb <= FT_W && syb >= 1 && syb <= FT_H && tx0 + sxb - 1 < w && ty0 + syb - 1 < h;
+        const int m = min(n - e0, 512), H = (m + 1) >> 1;
+        const bool act = wv * 64 < H;                                   // wave-uniform
+        bool ka = false, kb = false; int ia = 0, ib = 0;
+        if (act) {
+            const int ea = tid, eb = H + tid;
+            ia = list[e0 + min(ea, m - 1)]; ib = list[e0 + min(eb, m - 1)];
+            const int sya = ia >> 8, sxa = ia & 255, syb = ib >> 8, sxb = ib & 255;
+            const uint32_t S2 = fast_S2(&px[(sya + 3) * FT_PW + sxa + 4], &px[(syb + 3) * FT_PW + sxb + 4], FT_PW);
+            const int Sa = (int)(S2 & 0xFFFFu), Sb = (int)(S2 >> 16);
+            if (ea < H) sc[(sya + 1) * FT_SST + sxa + 1] = (uint8_t)Sa;
+            if (eb < m) sc[(syb + 1) * FT_SST + sxb + 1] = (uint8_t)Sb;
+            ka = ea < H && Sa > min_th && (unsigned)(sxa - ix0) < (unsigned)iw && (unsigned)(sya - iy0) < (unsigned)ih;
+            kb = eb < m && Sb > min_th && (unsigned)(sxb - ix0) < (unsigned)iw && (unsigned)(syb - iy0) < (unsigned)ih;
+        }
         __syncthreads();                                                // every entry of the chunk has been read
-        const unsigned long long ba = __ballot(ka), bb = __ballot(kb);
-        const int ca = __popcll(ba), cb = __popcll(bb);
-        if (ca + cb) {
-            int base = 0;
-            if (lane == 0) base = atomicAdd(&nsurv, ca + cb);
-            base = __shfl(base, 0, 64);
-            const unsigned long long below = (1ull << lane) - 1ull;
-            if (ka) list[base + __popcll(ba & below)] = (uint16_t)ia;
-            if (kb) list[base + ca + __popcll(bb & below)] = (uint16_t)ib;
+        if (act) {
+            const unsigned long long ba = __ballot(ka), bb = __ballot(kb);
+            const int ca = __popcll(ba), cb = __popcll(bb);
+            if (ca + cb) {
+                int base = 0;
+                if (lane == 0) base = atomicAdd(&nsurv, ca + cb);
+                base = __shfl(base, 0, 64);
+                const unsigned long long below = (1ull << lane) - 1ull;
+                if (ka) list[base + __popcll(ba & below)] = (uint16_t)ia;
+                if (kb) list[base + ca + __popcll(bb & below)] = (uint16_t)ib;
+            }
         }
     }
     __syncthreads();
     const int n2 = nsurv;
     // ---- local maxima among same-cell neighbours; staged in LDS, ONE global reservation per tile
-    const int cx0 = max((int)cellx[1], 0), cy0 = max((int)celly[1], 0);
     cand_t* out = cand + (size_t)frame * g.cand_total + L.cand_off;
     int32_t* nc = ncand + frame * g.nlevels + l;
     for (int e0 = 0; e0 < n2; e0 += 256) {
+        if (e0 + wv * 64 >= n2) continue;                               // wave-uniform: no entry for this wave
         const int e = e0 + tid;
         bool keep = false; int S = 0, sx = 0, sy = 0;
         if (e < n2) {
             const int i = list[e]; sy = i >> 8; sx = i & 255;
-            {
-                const uint8_t* q = &sc[sy * FT_SST + sx];
-                S = q[0];
-                {
-                    const int cx = cellx[sx], cy = celly[sy];
-                    const bool xl = cellx[sx-1] == cx, xr = cellx[sx+1] == cx, yu = celly[sy-1] == cy, yd = celly[sy+1] == cy;
-                    int nb = 0;
-                    if (yu) { nb = max(nb, (int)q[-FT_SST]); if (xl) nb = max(nb, (int)q[-FT_SST-1]); if (xr) nb = max(nb, (int)q[-FT_SST+1]); }
-                    if (yd) { nb = max(nb, (int)q[FT_SST]);  if (xl) nb = max(nb, (int)q[FT_SST-1]);  if (xr) nb = max(nb, (int)q[FT_SST+1]); }
-                    if (xl) nb = max(nb, (int)q[-1]);
-                    if (xr) nb = max(nb, (int)q[1]);
-                    keep = nb < S;
-                }
-            }
+            const uint8_t* q = &sc[(sy + 1) * FT_SST + sx + 1];
+            S = q[0];
+            const int cx = cellx[sx + 1], cy = celly[sy + 1];
+            const bool xl = cellx[sx] == cx, xr = cellx[sx + 2] == cx, yu = celly[sy] == cy, yd = celly[sy + 2] == cy;
+            int nb = 0;
+            if (yu) { nb = max(nb, (int)q[-FT_SST]); if (xl) nb = max(nb, (int)q[-FT_SST-1]); if (xr) nb = max(nb, (int)q[-FT_SST+1]); }
+            if (yd) { nb = max(nb, (int)q[FT_SST]);  if (xl) nb = max(nb, (int)q[FT_SST-1]);  if (xr) nb = max(nb, (int)q[FT_SST+1]); }
+            if (xl) nb = max(nb, (int)q[-1]);
+            if (xr) nb = max(nb, (int)q[1]);
+            keep = nb < S;
         }
         const unsigned long long bal = __ballot(keep);
         if (bal) {
@@ -959,8 +956,8 @@ __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, co
             base = __shfl(base, 0, 64);
             if (keep) {
                 const int k = base + __popcll(bal & ((1ull << lane) - 1ull));
-                const int gx = tx0 + sx - 1, gy = ty0 + sy - 1;
-                const int cj = cellx[sx], ci = celly[sy];
+                const int gx = xs0 + sx, gy = ys0 + sy;
+                const int cj = cellx[sx + 1], ci = celly[sy + 1];
                 atomicMax(&lmax[((ci - cy0) & 7) * 8 + ((cj - cx0) & 7)], S);
                 cand_t c;
                 c.x = (uint32_t)(gx - L.minBX) | ((uint32_t)(gy - L.minBY) << 12) | ((uint32_t)(S - 1) << 24);
@@ -1002,10 +999,10 @@ fast_need_kernel(OrbGeom g, const int32_t* __restrict__ cellmax, int nframes, in
         const LevelGeom& L = g.L[l];
         const int t = tile_id - L.ftile_off;
         const int trow = L.ftiles_x == 1 ? t : (int)__umulhi((uint32_t)t, L.fmulTX);
-        const int tx0 = SSM_EDGE + (t - trow * L.ftiles_x) * FT_W, ty0 = SSM_EDGE + trow * FT_H;      // the grid starts at the first position FAST may report
-        auto cell_of = [](int gpos, int origin, uint32_t mul) { const int v = gpos - origin - 3; return v >= 0 ? (int)__umulhi((uint32_t)v, mul) : 0; };
-        const int cx0 = cell_of(tx0, L.minBX, L.mulW), cy0 = cell_of(ty0, L.minBY, L.mulH);
-        const int cx1 = min(cell_of(min(tx0 + FT_W - 1, L.w - 1), L.minBX, L.mulW), L.nCols - 1), cy1 = min(cell_of(min(ty0 + FT_H - 1, L.h - 1), L.minBY, L.mulH), L.nRows - 1);
+        int X0, X1, Y0, Y1;                                      // the tile's interior, as fast_tile sees it
+        ftile_rect(L, t - trow * L.ftiles_x, trow, X0, X1, Y0, Y1);
+        const int cx0 = (int)__umulhi((uint32_t)(X0 - L.minBX - 3), L.mulW), cy0 = (int)__umulhi((uint32_t)(Y0 - L.minBY - 3), L.mulH);
+        const int cx1 = min((int)__umulhi((uint32_t)(X1 - 1 - L.minBX - 3), L.mulW), L.nCols - 1), cy1 = min((int)__umulhi((uint32_t)(Y1 - 1 - L.minBY - 3), L.mulH), L.nRows - 1);
         const int32_t* cm = cellmax + (size_t)frame * g.cells_total + L.cell_off;
         for (int ci = cy0; ci <= cy1 && !need; ci++) for (int cj = cx0; cj <= cx1; cj++) if (cm[ci * L.nCols + cj] <= g.ini_th) { need = true; break; }
     }

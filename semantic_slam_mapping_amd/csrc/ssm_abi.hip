@@ -10,6 +10,12 @@ static const int8_t k_default_pattern[1024] = {
 thread_local std::string g_create_err;
 
 // ---------------------------------------------------------------- geometry (mirrors ORBextractor ctor / ComputePyramid)
+// cells (of size `cell`, counted from origin + 3) that the scored positions [max(a - 1, EDGE), min(b + 1, n - EDGE)) of a FAST tile interior [a, b) touch
+static int fast_scored_cells(int a, int b, int n, int origin, int cell)
+{
+    const int s0 = a - 1 > SSM_EDGE ? a - 1 : SSM_EDGE, s1 = (b + 1 < n - SSM_EDGE ? b + 1 : n - SSM_EDGE) - 1;
+    return (s1 - origin - 3) / cell - (s0 - origin - 3) / cell + 1;
+}
 static int build_geometry(const ssm_config& c, OrbGeom& g, std::string& err)
 {
     memset(&g, 0, sizeof(g));
@@ -50,12 +56,24 @@ static int build_geometry(const ssm_config& c, OrbGeom& g, std::string& err)
         const float width = (float)(L.maxBX - L.minBX), height = (float)(L.maxBY - L.minBY);
         L.nCols = (int)(width / 30.f); L.nRows = (int)(height / 30.f);
         L.wCell = (int)ceilf(width / L.nCols); L.hCell = (int)ceilf(height / L.nRows);
-        if (L.wCell < 17 || L.hCell < 5) { err = "FAST cell too small"; return SSM_E_INVAL; }   /* <= 8x8 cells per 128x32 tile */
+        if (L.wCell < 17 || L.hCell < 5) { err = "FAST cell too small"; return SSM_E_INVAL; }   /* FAST tiles: at most 8 x 8 cells (checked below) */
         L.mulW = (uint32_t)(((1ull << 32) + L.wCell - 1) / L.wCell); L.mulH = (uint32_t)(((1ull << 32) + L.hCell - 1) / L.hCell);
         L.cell_off = cells; cells += L.nCols * L.nRows;
         L.tiles_x = (L.w + 127) / 128; L.mulTX = (uint32_t)(((1ull << 32) + L.tiles_x - 1) / L.tiles_x); L.tile_off = tiles; tiles += L.tiles_x * ((L.h + 31) / 32);
-        /* FAST reports nothing within SSM_EDGE of the border: its tile grid starts there (640x480, 8 levels: 233 tiles instead of 278) */
-        L.ftiles_x = (L.w - 2 * SSM_EDGE + 127) / 128; L.fmulTX = (uint32_t)(((1ull << 32) + L.ftiles_x - 1) / L.ftiles_x); L.ftile_off = ftiles; ftiles += L.ftiles_x * ((L.h - 2 * SSM_EDGE + 31) / 32);
+        /* FAST reports nothing within SSM_EDGE of the border: its tiles cover that window only, as few as fit and all but the last of each row and
+           column of one size (640x480, 8 levels: 227 tiles; interiors 121 x 32 at level 0), so that little of a tile lies outside the window */
+        {
+            const int fw = L.w - 2 * SSM_EDGE, fh = L.h - 2 * SSM_EDGE;
+            const int kx = (fw + FT_W - 1) / FT_W, ky = (fh + FT_H - 1) / FT_H;
+            L.ftw = (fw + kx - 1) / kx; L.fth = (fh + ky - 1) / ky;
+            L.ftiles_x = (fw + L.ftw - 1) / L.ftw;
+            L.fmulTX = (uint32_t)(((1ull << 32) + L.ftiles_x - 1) / L.ftiles_x); L.ftile_off = ftiles; ftiles += L.ftiles_x * ((fh + L.fth - 1) / L.fth);
+            /* the scored rectangle of a tile (interior + apron) touches at most 8 x 8 cells: pass 2's emptyrow bytes and the 64 lmax slots of fast_tile */
+            for (int x0 = SSM_EDGE; x0 < L.w - SSM_EDGE; x0 += L.ftw)
+                if (fast_scored_cells(x0, x0 + L.ftw, L.w, L.minBX, L.wCell) > 8) { err = "FAST tile spans more than 8 cell columns"; return SSM_E_INVAL; }
+            for (int y0 = SSM_EDGE; y0 < L.h - SSM_EDGE; y0 += L.fth)
+                if (fast_scored_cells(y0, y0 + L.fth, L.h, L.minBY, L.hCell) > 8) { err = "FAST tile spans more than 8 cell rows"; return SSM_E_INVAL; }
+        }
         L.bt_x = (L.stride + 127) / 128; L.bt_off = btiles; btiles += L.bt_x; L.bt_units_off = bunits; bunits += (L.stride + 31) / 32;
         if (L.nCols * L.nRows >= (1 << 17)) { err = "too many FAST cells"; return SSM_E_INVAL; }
         L.nfeat = feat[l];
@@ -426,6 +444,31 @@ static int run_orb(ssm_ctx* c, const uint8_t* d_img, int channels, const uint16_
     prof_begin(c, "octree");    HIPCHK(c, k_octree(nb, g, c->d_cand, c->d_ncand, c->d_cellmax, c->d_nodeof, c->d_sel, c->d_nsel, c->d_status, s)); prof_end(c);
     prof_begin(c, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(nb, g, c->d_pyr, c->d_blur, c->d_blur_tab, s) : k_blur(nb, g, c->d_pyr, c->d_blur, s)); prof_end(c);
     prof_begin(c, "describe");  HIPCHK(c, k_describe(nb, g, c->d_pyr, c->d_blur, c->d_sel, c->d_nsel, c->d_pattern_f, d_depth, c->cfg.camera, c->d_kpaux, kps, desc, pos3d, nkp, s)); prof_end(c);
+    return SSM_OK;
+}
+
+extern "C" int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int cap, int* ntiles, int32_t* limits)
+{
+    if (!cfg || !ntiles) return SSM_E_INVAL;
+    OrbGeom g; std::string err;
+    { const int r = build_geometry(*cfg, g, err); if (r) return r; }
+    if (limits) { const int32_t v[6] = {FT_LDS_BYTES, FT_SW / 4, FT_SH, FT_PW, FT_PH, FT_STAGE}; memcpy(limits, v, sizeof(v)); }
+    *ntiles = g.ftiles_total;
+    if (!tiles) return SSM_OK;
+    if (cap < g.ftiles_total) return SSM_E_INVAL;
+    for (int l = 0; l < g.nlevels; l++) {
+        const LevelGeom& L = g.L[l];
+        const int ntl = (l + 1 < g.nlevels ? g.L[l+1].ftile_off : g.ftiles_total) - L.ftile_off;
+        for (int t = 0; t < ntl; t++) {
+            int x0, x1, y0, y1;
+            ftile_rect(L, t % L.ftiles_x, t / L.ftiles_x, x0, x1, y0, y1);
+            /* the same rectangle and cells as fast_tile */
+            const int xs0 = std::max(x0 - 1, SSM_EDGE), xs1 = std::min(x1 + 1, L.w - SSM_EDGE), ys0 = std::max(y0 - 1, SSM_EDGE), ys1 = std::min(y1 + 1, L.h - SSM_EDGE);
+            const int ncx = (xs1 - 1 - L.minBX - 3) / L.wCell - (xs0 - L.minBX - 3) / L.wCell + 1, ncy = (ys1 - 1 - L.minBY - 3) / L.hCell - (ys0 - L.minBY - 3) / L.hCell + 1;
+            const int32_t v[16] = {l, x0, x1, y0, y1, xs0, xs1, ys0, ys1, (xs1 - xs0 + 3) / 4, ys1 - ys0, ncx, ncy, L.w, L.h, L.stride};
+            memcpy(tiles + 16 * (size_t)(L.ftile_off + t), v, sizeof(v));
+        }
+    }
     return SSM_OK;
 }
 

@@ -18,7 +18,8 @@ struct LevelGeom {
     int nCols, nRows, wCell, hCell;   // FAST cell grid (ComputeKeyPointsOctTree, W = 30)
     int cell_off;              // first flattened cell id of this level
     int tile_off, tiles_x;     // 128x32 tiles of the whole level image in the flattened grid (blur_kernel)
-    int ftile_off, ftiles_x;   // FAST tiles (128x32) of this level: they cover [SSM_EDGE, w - SSM_EDGE) x [SSM_EDGE, h - SSM_EDGE) only, the positions FAST may report
+    int ftile_off, ftiles_x;   // FAST tiles of this level: they cover [SSM_EDGE, w - SSM_EDGE) x [SSM_EDGE, h - SSM_EDGE) only, the positions FAST may report
+    int ftw, fth;              // FAST tile interior (<= FT_W x FT_H), fitted to that window: ftile_rect
     int nfeat;                 // mnFeaturesPerLevel
     int cand_off, cand_cap;    // entries inside one frame's candidate buffer
     int sel_off, sel_cap;      // slots inside one frame's selected-keypoint staging (nfeat + 3)
@@ -35,6 +36,25 @@ struct LevelGeom {
 // and a patch covers ~25 such lines instead of the ~47 it touches in a row-major image (a 37-byte row segment drags in a whole 128-byte line).
 // Offset of the 16-byte word that holds (x, y): rows padded to a multiple of 8.
 __host__ __device__ inline int blur_off(int boff, int stride, int x, int y) { return boff + (((y >> 3) * (stride >> 4) + (x >> 4)) << 7) + ((y & 7) << 4) + (x & 15); }
+// FAST tiles (fast_kernel): the interiors partition the window [SSM_EDGE, w - SSM_EDGE) x [SSM_EDGE, h - SSM_EDGE) of a level; a block quick-tests
+// the interior plus a 1-position apron (the NMS neighbours) clipped to the window, as 4-column groups counted from the apron's first column
+#define FT_W 126              // interior, at most: the scored width (+ 2) is 32 groups of 4
+#define FT_H 32
+#define FT_SW (FT_W + 2)      // scored positions per row / rows, at most
+#define FT_SH (FT_H + 2)
+#define FT_PW 144             // staged pixel row: [xs0 - 4, xs0 + 140) = nine 16-byte words
+#define FT_PH (FT_SH + 6)     // staged rows: [ys0 - 3, ys0 + FT_SH + 3)
+#define FT_SST 132            // score rows: [xs0 - 1, xs0 + 131), FT_SH + 2 of them
+#define FT_BW 32              // pass-bit image: one byte (the 4 positions of a group) per group, 32 bytes per scored row
+#define FT_STAGE ((FT_PH * FT_PW) / 8)   // candidates staged per tile: as many as fit in the pixel tile they replace (720)
+// the LDS arrays fast_tile declares (the compiler may pad; tests/test_fast_tiling.py reads what the built kernels take from the code object)
+#define FT_LDS_BYTES (4 * 8 + FT_PH * FT_PW + (FT_SH + 2) * FT_SST + 2 * FT_SW * FT_SH + 2 * (FT_SW + 2) + 2 * (FT_SH + 2) + 4 * 64 + 4 * 4 + 4 * 3)
+// interior [x0, x1) x [y0, y1) of FAST tile (tx, ty) of a level
+__host__ __device__ inline void ftile_rect(const LevelGeom& L, int tx, int ty, int& x0, int& x1, int& y0, int& y1)
+{
+    x0 = SSM_EDGE + tx * L.ftw; x1 = x0 + L.ftw < L.w - SSM_EDGE ? x0 + L.ftw : L.w - SSM_EDGE;
+    y0 = SSM_EDGE + ty * L.fth; y1 = y0 + L.fth < L.h - SSM_EDGE ? y0 + L.fth : L.h - SSM_EDGE;
+}
 struct OrbGeom {
     int nlevels, W, H;
     int pyr_bytes;             // one frame's pyramid (all levels)
