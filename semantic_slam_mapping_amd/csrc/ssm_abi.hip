@@ -129,15 +129,15 @@ int ensure_scratch2(ssm_ctx* c, size_t bytes)
     uint8_t* p; int r = dalloc(c, &p, bytes); if (r) return r;
     c->d_scratch2 = p; c->scratch2_bytes = bytes; return SSM_OK;
 }
-void prof_begin(ssm_ctx* c, const char* name)
+void prof_begin(ssm_ctx* c, hipStream_t s, const char* name)
 {
     if (!c->profiling) return;
     auto get = [&]() { if (c->pool_used == c->pool.size()) { hipEvent_t e; hipEventCreate(&e); c->pool.push_back(e); } return c->pool[c->pool_used++]; };
     StageRec r; r.name = name; r.a = get(); r.b = get();
-    hipEventRecord(r.a, c->stream);
+    hipEventRecord(r.a, s);
     c->recs.push_back(r);
 }
-void prof_end(ssm_ctx* c) { if (c->profiling) hipEventRecord(c->recs.back().b, c->stream); }
+void prof_end(ssm_ctx* c, hipStream_t s) { if (c->profiling) hipEventRecord(c->recs.back().b, s); }
 
 // ORB scratch overflow (d_status) is checked after every ORB entry point; the voxel-table-full flag (counters[1]) belongs to the MAP entry points
 // (ssm_sync after ssm_seq_process, ssm_map_*): it is reported once, so that one overflowing call does not fail every later call on the
@@ -183,6 +183,24 @@ extern "C" void ssm_config_default(ssm_config* c)
 extern "C" const char* ssm_version(void) { return "ssm_hip 0.1 (gfx950)"; }
 extern "C" const char* ssm_last_error(const ssm_ctx* c) { return c ? c->err.c_str() : g_create_err.c_str(); }
 
+// an ORB workspace for the context's B frames; complete once kpaux is set (ensure_alt)
+static int orb_work_alloc(ssm_ctx* c, OrbWork& w)
+{
+    const OrbGeom& g = c->g; const int B = c->B;
+    // pyr + 16: resize4_kernel's 8-byte windows may end past the last row
+    DALLOC(c, w.pyr, (size_t)B * g.pyr_bytes + 16); DALLOC(c, w.blur, (size_t)B * g.blur_bytes);
+    // the per-level candidate counters and the cell maxima (+ k_fast's retry list) share ONE allocation, counters first: k_fast zeroes both with one fill
+    DALLOC(c, w.ncand, k_fast_ncand_pad(B, g) + k_fast_cellmax_ints(B, g)); w.cellmax = w.ncand + k_fast_ncand_pad(B, g);
+    DALLOC(c, w.cand, (size_t)B * g.cand_total); DALLOC(c, w.nodeof, (size_t)B * g.cand_total);
+    DALLOC(c, w.sel, (size_t)B * g.sel_total); DALLOC(c, w.nsel, (size_t)B * g.nlevels);
+    DALLOC(c, w.kpaux, (size_t)B * g.sel_total * 2);             // KpAux + KpRec per slot
+    return SSM_OK;
+}
+static void orb_work_free(OrbWork& w)
+{
+    void* ptrs[] = { w.pyr, w.blur, w.ncand /* cellmax: inside ncand's allocation */, w.cand, w.nodeof, w.sel, w.nsel, w.kpaux };
+    for (void* p : ptrs) if (p) hipFree(p);
+}
 static int ctx_init(ssm_ctx* c)
 {
     const ssm_config& cfg = c->cfg; const OrbGeom& g = c->g; const int B = c->B, W = g.W, H = g.H;
@@ -239,13 +257,7 @@ static int ctx_init(ssm_ctx* c)
         HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         p.d_tab = d;
     }
-    // d_pyr + 16: resize4_kernel's 8-byte windows may end past the last row
-    DALLOC(c, c->d_pyr, (size_t)B * g.pyr_bytes + 16); DALLOC(c, c->d_blur, (size_t)B * g.blur_bytes);
-    // the per-level candidate counters and the cell maxima (+ k_fast's retry list) share ONE allocation, counters first: k_fast zeroes both with one fill
-    DALLOC(c, c->d_ncand, k_fast_ncand_pad(B, g) + k_fast_cellmax_ints(B, g)); c->d_cellmax = c->d_ncand + k_fast_ncand_pad(B, g);
-    DALLOC(c, c->d_cand, (size_t)B * g.cand_total); DALLOC(c, c->d_nodeof, (size_t)B * g.cand_total);
-    DALLOC(c, c->d_sel, (size_t)B * g.sel_total); DALLOC(c, c->d_nsel, (size_t)B * g.nlevels);
-    DALLOC(c, c->d_kpaux, (size_t)B * g.sel_total * 2);          // KpAux + KpRec per slot
+    { const int r = orb_work_alloc(c, c->work[0]); if (r) return r; }
     DALLOC(c, c->d_status, 1); HIPCHK(c, hipMemset(c->d_status, 0, 4));
     const int chunks = backproject_chunks(W, H);
     DALLOC(c, c->d_mask, (size_t)B * W * H); DALLOC(c, c->d_chunk_cnt, (size_t)B * chunks); DALLOC(c, c->d_chunk_off, (size_t)B * chunks);
@@ -254,7 +266,7 @@ static int ctx_init(ssm_ctx* c)
     DALLOC(c, c->map.ovf, VOX_OVF_RECORDS); c->map.ovf_cap = VOX_OVF_RECORDS;
     { void* hp = nullptr; HIPCHK(c, hipHostMalloc(&hp, 64, hipHostMallocDefault)); c->h_map_snap = (int32_t*)hp; memset(hp, 0, 64); }
     for (int k = 0; k < 2; k++) HIPCHK(c, hipEventCreateWithFlags(&c->map_snap_ev[k], hipEventDisableTiming));
-    int r = table_alloc(c, c->map, cfg.voxel_capacity_log2); if (r) return r;
+    int r = table_alloc(c, c->stream, c->map, cfg.voxel_capacity_log2); if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
 }
@@ -294,20 +306,17 @@ extern "C" void ssm_destroy(ssm_ctx* c)
     if (!c) return;
     hipSetDevice(c->device);
     if (c->stream) hipStreamSynchronize(c->stream);
-    void* ptrs[] = { c->d_pattern, c->d_pyr, c->d_blur, /* d_cellmax: inside d_ncand's allocation */ c->d_cand, c->d_nodeof, c->d_ncand, c->d_sel, c->d_nsel, c->d_status, c->d_mask,
+    for (OrbWork& w : c->work) orb_work_free(w);
+    void* ptrs[] = { c->d_pattern, c->d_status, c->d_mask,
                      c->d_chunk_cnt, c->d_chunk_off, c->d_total, c->d_points, c->d_in_img, c->d_in_sem, c->d_in_depth, c->d_in_pose,
                      c->d_scratch, c->d_scratch2, c->d_kps, c->d_desc_all, c->d_nkp_all, c->d_pos3d, c->d_matches, c->d_nmatch, c->d_match_pend, c->d_npoints,
-                     c->d_hist_tmp, c->map.tab, c->tmp.tab, c->d_kpaux, c->d_pattern_f, c->d_exp_q, c->d_exp_t, c->d_knn, c->d_blur_tab, c->d_vmap, c->d_vcat };
+                     c->d_hist_tmp, c->map.tab, c->tmp.tab, c->d_pattern_f, c->d_exp_q, c->d_exp_t, c->d_knn, c->d_blur_tab, c->d_vmap, c->d_vcat };
     for (void* p : ptrs) if (p) hipFree(p);
     if (c->map.ovf) hipFree(c->map.ovf);
     if (c->d_pnp_xchg) hipFree(c->d_pnp_xchg);
     if (c->h_map_snap) hipHostFree(c->h_map_snap);
     for (int k = 0; k < 2; k++) if (c->map_snap_ev[k]) hipEventDestroy(c->map_snap_ev[k]);
-    { void* ap[] = { c->alt.pyr, c->alt.blur, c->alt.cand, c->alt.nodeof, c->alt.ncand, c->alt.sel, c->alt.nsel, c->alt.mask, c->alt.kpaux };
-      for (void* p : ap) if (p) hipFree(p); }
     for (int i = 0; i < 3; i++) if (c->ev_orb[i]) hipEventDestroy(c->ev_orb[i]);
-    { void* ap2[] = { c->alt2.pyr, c->alt2.blur, c->alt2.cand, c->alt2.nodeof, c->alt2.ncand, c->alt2.sel, c->alt2.nsel, c->alt2.mask, c->alt2.kpaux };
-      for (void* p : ap2) if (p) hipFree(p); }
     if (c->stream4) hipStreamDestroy(c->stream4);
     if (c->ev_join4) hipEventDestroy(c->ev_join4);
     for (int l = 0; l < SSM_MAX_LEVELS; l++) { if (c->d_xofs[l]) hipFree(c->d_xofs[l]); if (c->d_xa[l]) hipFree(c->d_xa[l]); if (c->d_yofs[l]) hipFree(c->d_yofs[l]); if (c->d_ya[l]) hipFree(c->d_ya[l]); if (c->d_xgrp[l]) hipFree(c->d_xgrp[l]); }
@@ -374,7 +383,6 @@ extern "C" int ssm_get_stage_times(ssm_ctx* c, const char** names, float* ms, in
     return SSM_OK;
 }
 
-// second workspace for the two-chain mode of ssm_seq_process (same sizes as ctx_init's)
 // The side streams of ssm_seq_process (stream2: second chain / SegNet + map side; stream3: map stage; stream4: third chain) are created at first use, not
 // with the context: HIP spreads streams over a few hardware queues in creation order, and a context that only serves per-frame calls (the stereo bench
 // runs eight of them) should take ONE slot of that rotation -- with four streams per context every context's main stream landed on the same queue
@@ -395,56 +403,45 @@ int ensure_side_streams(ssm_ctx* c)
     c->side_ready = true;
     return SSM_OK;
 }
-static int ensure_alt_ws(ssm_ctx* c, ssm_ctx::AltWork& a)
+static int ensure_alt(ssm_ctx* c)          // the workspaces of chains 1, 2 of ssm_seq_process
 {
-    if (a.ready) return SSM_OK;
-    const OrbGeom& g = c->g; const int B = c->B;
-    DALLOC(c, a.pyr, (size_t)B * g.pyr_bytes + 16); DALLOC(c, a.blur, (size_t)B * g.blur_bytes);
-    DALLOC(c, a.ncand, k_fast_ncand_pad(B, g) + k_fast_cellmax_ints(B, g)); a.cellmax = a.ncand + k_fast_ncand_pad(B, g);
-    DALLOC(c, a.cand, (size_t)B * g.cand_total); DALLOC(c, a.nodeof, (size_t)B * g.cand_total);
-    DALLOC(c, a.sel, (size_t)B * g.sel_total); DALLOC(c, a.nsel, (size_t)B * g.nlevels);
-    DALLOC(c, a.mask, (size_t)B * g.W * g.H); DALLOC(c, a.kpaux, (size_t)B * g.sel_total * 2);
-    a.ready = true;
+    for (int k = 1; k < 3; k++) if (!c->work[k].kpaux) { const int r = orb_work_alloc(c, c->work[k]); if (r) return r; }
     return SSM_OK;
 }
-static int ensure_alt(ssm_ctx* c)
+// ---------------------------------------------------------------- the ORB front end for nb frames already on the device, on stream s with workspace w
+// level 0 + every level of nb frames into w.pyr: one launch where the geometry has the fused form (plan), gray_kernel + one launch per level otherwise
+static int make_pyramid(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_img, int channels, int nb, const PyrBandPlan& plan)
 {
-    int r = ensure_alt_ws(c, c->alt); if (r) return r;
-    if (c->nchains >= 3) { r = ensure_alt_ws(c, c->alt2); if (r) return r; }
-    return SSM_OK;
-}
-struct ChainSwap {                    // chains 1, 2 of ssm_seq_process: the helpers use c->stream and the c->d_* workspace; point both at that chain's set
-    ssm_ctx* c; int chain;
-    void swap_all() { ssm_ctx::AltWork& a = chain == 1 ? c->alt : c->alt2;
-                      std::swap(c->stream, chain == 1 ? c->stream2 : c->stream4); std::swap(c->d_pyr, a.pyr); std::swap(c->d_blur, a.blur); std::swap(c->d_cellmax, a.cellmax);
-                      std::swap(c->d_cand, a.cand); std::swap(c->d_nodeof, a.nodeof); std::swap(c->d_ncand, a.ncand); std::swap(c->d_sel, a.sel);
-                      std::swap(c->d_nsel, a.nsel); std::swap(c->d_mask, a.mask); std::swap(c->d_kpaux, a.kpaux); }
-    ChainSwap(ssm_ctx* c_, int chain_) : c(c_), chain(chain_) { if (chain) swap_all(); }
-    ~ChainSwap() { if (chain) swap_all(); }
-};
-// ---------------------------------------------------------------- the ORB front end for nb frames already on the device
-// level 0 + every level of nb frames into c->d_pyr: one launch where the geometry has the fused form (plan), gray_kernel + one launch per level otherwise
-static int make_pyramid(ssm_ctx* c, const uint8_t* d_img, int channels, int nb, const PyrBandPlan& plan)
-{
-    const OrbGeom& g = c->g; hipStream_t s = c->stream;
+    const OrbGeom& g = c->g;
     if (plan.bands) {
-        prof_begin(c, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, c->d_pyr, plan, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c);
+        prof_begin(c, s, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, w.pyr, plan, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c, s);
         return SSM_OK;
     }
-    prof_begin(c, "gray");      HIPCHK(c, k_gray(d_img, channels, nb, g, c->d_pyr, s)); prof_end(c);
-    prof_begin(c, "pyramid");   HIPCHK(c, k_pyramid(nb, g, c->d_pyr, c->d_xofs, c->d_xa, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c);
+    prof_begin(c, s, "gray");      HIPCHK(c, k_gray(d_img, channels, nb, g, w.pyr, s)); prof_end(c, s);
+    prof_begin(c, s, "pyramid");   HIPCHK(c, k_pyramid(nb, g, w.pyr, c->d_xofs, c->d_xa, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c, s);
     return SSM_OK;
 }
-static int run_orb(ssm_ctx* c, const uint8_t* d_img, int channels, const uint16_t* d_depth, int nb,
+// run_orb in two halves, because the per-frame call (orb_extract_enqueue) has host work to do between them: everything in front of the one kernel that reads the depth image ...
+static int orb_detect(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_img, int channels, int nb)
+{
+    const OrbGeom& g = c->g;
+    { const int r = make_pyramid(c, s, w, d_img, channels, nb, nb > 1 ? c->pyr_bands : c->pyr_bands1); if (r) return r; }
+    prof_begin(c, s, "fast");      HIPCHK(c, k_fast(nb, g, w.pyr, w.cand, w.ncand, w.cellmax, s)); prof_end(c, s);
+    prof_begin(c, s, "octree");    HIPCHK(c, k_octree(nb, g, w.cand, w.ncand, w.cellmax, w.nodeof, w.sel, w.nsel, c->d_status, s)); prof_end(c, s);
+    prof_begin(c, s, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(nb, g, w.pyr, w.blur, c->d_blur_tab, s) : k_blur(nb, g, w.pyr, w.blur, s)); prof_end(c, s);
+    return SSM_OK;
+}
+// ... and that kernel
+static int orb_describe(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint16_t* d_depth, int nb, ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp)
+{
+    prof_begin(c, s, "describe");  HIPCHK(c, k_describe(nb, c->g, w.pyr, w.blur, w.sel, w.nsel, c->d_pattern_f, d_depth, c->cfg.camera, w.kpaux, kps, desc, pos3d, nkp, s)); prof_end(c, s);
+    return SSM_OK;
+}
+static int run_orb(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_img, int channels, const uint16_t* d_depth, int nb,
                    ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp)
 {
-    const OrbGeom& g = c->g; hipStream_t s = c->stream;
-    { const int r = make_pyramid(c, d_img, channels, nb, nb > 1 ? c->pyr_bands : c->pyr_bands1); if (r) return r; }
-    prof_begin(c, "fast");      HIPCHK(c, k_fast(nb, g, c->d_pyr, c->d_cand, c->d_ncand, c->d_cellmax, s)); prof_end(c);
-    prof_begin(c, "octree");    HIPCHK(c, k_octree(nb, g, c->d_cand, c->d_ncand, c->d_cellmax, c->d_nodeof, c->d_sel, c->d_nsel, c->d_status, s)); prof_end(c);
-    prof_begin(c, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(nb, g, c->d_pyr, c->d_blur, c->d_blur_tab, s) : k_blur(nb, g, c->d_pyr, c->d_blur, s)); prof_end(c);
-    prof_begin(c, "describe");  HIPCHK(c, k_describe(nb, g, c->d_pyr, c->d_blur, c->d_sel, c->d_nsel, c->d_pattern_f, d_depth, c->cfg.camera, c->d_kpaux, kps, desc, pos3d, nkp, s)); prof_end(c);
-    return SSM_OK;
+    const int r = orb_detect(c, s, w, d_img, channels, nb);
+    return r ? r : orb_describe(c, s, w, d_depth, nb, kps, desc, pos3d, nkp);
 }
 
 extern "C" int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int cap, int* ntiles, int32_t* limits)
@@ -484,7 +481,7 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
     const size_t ib = (size_t)g.W * g.H * channels;
     { const int r = ensure_scratch(c, ib * n); if (r) return r; }
     HIPCHK(c, hipMemcpyAsync(c->d_scratch, img, ib * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_pyr, 0xA5, (size_t)n * g.pyr_bytes, c->stream));      // every byte the pyramid owns must be written
+    HIPCHK(c, hipMemsetAsync(c->work[0].pyr, 0xA5, (size_t)n * g.pyr_bytes, c->stream));      // every byte the pyramid owns must be written
     PyrBandPlan p;
     if (bands < 0) p.bands = 0;
     else if (bands == 0) p = n > 1 ? c->pyr_bands : c->pyr_bands1;
@@ -495,10 +492,10 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
         int32_t* d = nullptr; DALLOC(c, d, tab.size()); p.d_tab = d;
         HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     }
-    int r = make_pyramid(c, static_cast<const uint8_t*>(c->d_scratch), channels, n, p);
+    int r = make_pyramid(c, c->stream, c->work[0], static_cast<const uint8_t*>(c->d_scratch), channels, n, p);
     if (bands > 0) { hipStreamSynchronize(c->stream); hipFree(p.d_tab); }
     if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(out, c->d_pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->work[0].pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
 }
@@ -575,21 +572,15 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
     ssm_keypoint* dk = reinterpret_cast<ssm_keypoint*>(dp + 64);
     uint8_t* dd = reinterpret_cast<uint8_t*>(dk + ocap);
     float* dps = reinterpret_cast<float*>(dd + (size_t)ocap * 32);
-    {
-        const OrbGeom& g = c->g; hipStream_t s = c->stream;
-        { const int r = make_pyramid(c, c->d_in_img, channels, 1, c->pyr_bands1); if (r) return r; }
-        prof_begin(c, "fast");      HIPCHK(c, k_fast(1, g, c->d_pyr, c->d_cand, c->d_ncand, c->d_cellmax, s)); prof_end(c);
-        prof_begin(c, "octree");    HIPCHK(c, k_octree(1, g, c->d_cand, c->d_ncand, c->d_cellmax, c->d_nodeof, c->d_sel, c->d_nsel, c->d_status, s)); prof_end(c);
-        prof_begin(c, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(1, g, c->d_pyr, c->d_blur, c->d_blur_tab, s) : k_blur(1, g, c->d_pyr, c->d_blur, s)); prof_end(c);
-        const uint16_t* d_depth = nullptr;
-        if (depth) {
-            if (!depth_direct) memcpy(h_in + ib, depth, db);       // (the device is busy with the launches above meanwhile)
-            void* mapped = nullptr;
-            HIPCHK(c, hipHostGetDevicePointer(&mapped, depth_direct ? const_cast<uint16_t*>(depth) : reinterpret_cast<uint16_t*>(h_in + ib), 0));
-            d_depth = reinterpret_cast<const uint16_t*>(mapped);
-        }
-        prof_begin(c, "describe");  HIPCHK(c, k_describe(1, g, c->d_pyr, c->d_blur, c->d_sel, c->d_nsel, c->d_pattern_f, d_depth, c->cfg.camera, c->d_kpaux, dk, dd, dps, dn, s)); prof_end(c);
+    r = orb_detect(c, c->stream, c->work[0], c->d_in_img, channels, 1); if (r) return r;
+    const uint16_t* d_depth = nullptr;
+    if (depth) {
+        if (!depth_direct) memcpy(h_in + ib, depth, db);       // (the device is busy with the launches above meanwhile)
+        void* mapped = nullptr;
+        HIPCHK(c, hipHostGetDevicePointer(&mapped, depth_direct ? const_cast<uint16_t*>(depth) : reinterpret_cast<uint16_t*>(h_in + ib), 0));
+        d_depth = reinterpret_cast<const uint16_t*>(mapped);
     }
+    r = orb_describe(c, c->stream, c->work[0], d_depth, 1, dk, dd, dps, dn); if (r) return r;
     HIPCHK(c, hipMemcpyAsync(dn + 1, c->d_status, 4, hipMemcpyDeviceToDevice, c->stream));          // the ORB scratch-overflow word travels in the block's header
     HIPCHK(c, hipMemcpyAsync(h_out, dp, blk, hipMemcpyDeviceToHost, c->stream));
     c->pending.push_back([=](ssm_ctx* cc) -> int {
@@ -910,7 +901,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     // map / SegNet work.  stream2 starts behind everything already queued on the context stream and is joined at the end.
     const bool side_work = (stages & (SSM_STAGE_MAP | SSM_STAGE_SEGNET)) != 0;
     // Two chains: without the SegNet stage (one activation workspace) and with two or more sub-batches, alternate sub-batches run
-    // their whole ORB -> match -> map chain on the context stream and on stream2 with a workspace each, so that one chain's
+    // their whole ORB -> match -> map chain on the context stream and on stream2 (and stream4, from three sub-batches on) with an OrbWork each, so that one chain's
     // latency-bound kernels (quad-tree, pyramid launches, block tails) overlap the other chain's VALU-bound ones.  The only
     // dependence between neighbours is the matcher's: the reference descriptors of sub-batch b - 1 (an event per chain).
     const bool two_chains = !c->serialize && !(stages & SSM_STAGE_SEGNET) && n > c->B && (stages & SSM_STAGE_ORB) && (W & 15) == 0;
@@ -918,56 +909,50 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     if (side || two_chains) { r = ensure_side_streams(c); if (r) return r; }
     if (two_chains) { r = ensure_alt(c); if (r) return r; }
     if (side || two_chains) { HIPCHK(c, hipEventRecord(c->ev_fork, c->stream)); HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0)); }
-    const int nch = two_chains ? (c->nchains >= 3 && n > 2 * c->B ? 3 : 2) : 1;
+    const int nch = two_chains ? (n > 2 * c->B ? 3 : 2) : 1;
     if (nch == 3) HIPCHK(c, hipStreamWaitEvent(c->stream4, c->ev_fork, 0));
     const bool map3 = two_chains && c->map_stream == 1;
     if (map3) HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
-    struct StreamSwap {               // the helpers below launch on c->stream; point it at stream2 for the side work
-        ssm_ctx* c; bool on;
-        StreamSwap(ssm_ctx* c_, bool on_) : c(c_), on(on_) { if (on) std::swap(c->stream, c->stream2); }
-        ~StreamSwap() { if (on) std::swap(c->stream, c->stream2); }
-    };
+    const hipStream_t chain_stream[3] = {c->stream, c->stream2, c->stream4};
     int bi = 0;
     for (int f0 = 0; f0 < n; f0 += c->B, bi++) {
         const int nb = (n - f0 < c->B) ? n - f0 : c->B;
         const int chain = bi % nch;
-        ChainSwap cs(c, chain);                                      // from here c->stream / c->d_* are this chain's
+        const hipStream_t cs = chain_stream[chain]; OrbWork& work = c->work[chain];      // this chain's stream and ORB workspace
         auto front = [&]() -> int {                                       // ORB -> match of this sub-batch
             if (stages & SSM_STAGE_ORB) {
-                r = run_orb(c, in->bgr + (size_t)f0 * npix * 3, 3, in->depth ? in->depth + (size_t)f0 * npix : nullptr, nb,
+                r = run_orb(c, cs, work, in->bgr + (size_t)f0 * npix * 3, 3, in->depth ? in->depth + (size_t)f0 * npix : nullptr, nb,
                             c->d_kps + (size_t)f0 * g.cap, desc + (size_t)f0 * row, c->d_pos3d + (size_t)f0 * g.cap * 3, nkp + f0);
                 if (r) return r;
-                if (mfma) { prof_begin(c, "match"); HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, c->stream)); prof_end(c); }
+                if (mfma) { prof_begin(c, cs, "match"); HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs)); prof_end(c, cs); }
                 if (two_chains) {
                     // The matcher of sub-batch bi reads the descriptor rows of the R preceding FRAMES, i.e. (max_batch < tracker_ref_frames) of several
                     // preceding sub-batches.  Every other chain's newest event is the ORB + expand of one of bi-1 .. bi-(nch-1); an older sub-batch sits on
                     // one of those streams (or on this one) in front of that record, so waiting on all of them orders the matcher behind every row it reads.
-                    HIPCHK(c, hipEventRecord(c->ev_orb[chain], c->stream));
-                    for (int k = 1; k < nch && k <= bi; k++) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_orb[(bi - k) % nch], 0));
+                    HIPCHK(c, hipEventRecord(c->ev_orb[chain], cs));
+                    for (int k = 1; k < nch && k <= bi; k++) HIPCHK(c, hipStreamWaitEvent(cs, c->ev_orb[(bi - k) % nch], 0));
                 }
             }
             if (stages & SSM_STAGE_MATCH) {
-                prof_begin(c, "match");
+                prof_begin(c, cs, "match");
                 if (mfma) {
-                    if (!(stages & SSM_STAGE_ORB)) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, c->stream));
-                    HIPCHK(c, k_match_seq_mfma(c->d_exp_q, c->d_exp_t, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->capT, c->d_knn, c->d_matches, c->d_nmatch, c->stream));
+                    if (!(stages & SSM_STAGE_ORB)) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs));
+                    HIPCHK(c, k_match_seq_mfma(c->d_exp_q, c->d_exp_t, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->capT, c->d_knn, c->d_matches, c->d_nmatch, cs));
                 } else
-                    HIPCHK(c, k_match_seq(c->d_desc_all, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->d_matches, c->d_nmatch, c->d_match_pend + (size_t)f0 * R, c->stream));
-                prof_end(c);
+                    HIPCHK(c, k_match_seq(c->d_desc_all, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->d_matches, c->d_nmatch, c->d_match_pend + (size_t)f0 * R, cs));
+                prof_end(c, cs);
             }
             return SSM_OK;
         };
         auto back = [&]() -> int {                                        // (SegNet ->) map of this sub-batch
             if (!side_work) return SSM_OK;
-            StreamSwap sw(c, side);
-            hipStream_t s = map3 ? c->stream3 : c->stream;                // = stream2 inside this scope (unless serialised)
-            struct StreamSet { ssm_ctx* c; hipStream_t keep; StreamSet(ssm_ctx* c_, hipStream_t s_) : c(c_), keep(c_->stream) { c->stream = s_; } ~StreamSet() { c->stream = keep; } } onmap(c, s);   // the stage events follow the kernels
+            const hipStream_t s = map3 ? c->stream3 : side ? c->stream2 : cs;      // the map stream, stream2 beside a single chain, or the chain's own stream
             const uint8_t* sem_src = in->sem_bgr ? in->sem_bgr + (size_t)f0 * npix * 3 : nullptr;
             if (stages & SSM_STAGE_SEGNET) {          // Classifier in the loop (the variant commented out at src/rgbdframe.cpp:119-136)
                 r = seg_init(c); if (r) return r;
-                prof_begin(c, "segnet");
-                r = seg_forward_dev(c, in->bgr + (size_t)f0 * npix * 3, nb, nullptr, c->seg->d_sem_gen, 0); if (r) return r;
-                prof_end(c);
+                prof_begin(c, s, "segnet");
+                r = seg_forward_dev(c, s, in->bgr + (size_t)f0 * npix * 3, nb, nullptr, c->seg->d_sem_gen, 0); if (r) return r;
+                prof_end(c, s);
                 sem_src = c->seg->d_sem_gen;
             }
             // The map of a context grows (map_settle): a launch covers all nb frames when the table is large, fewer while it is small, and the table's counters
@@ -977,21 +962,21 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
                 const int g0 = f0 + q0;
                 const uint8_t* sem_q = sem_src + (size_t)q0 * npix * 3;
                 if ((W & 15) == 0) {         // streaming fused kernels (16 pixels per thread, 16-byte loads)
-                    prof_begin(c, "map_fuse");
+                    prof_begin(c, s, "map_fuse");
                     { MapLaunch L; L.depth = in->depth + (size_t)g0 * npix; L.rgb = in->bgr + (size_t)g0 * npix * 3; L.sem = sem_q; L.pose = in->pose ? in->pose + (size_t)g0 * 16 : nullptr;
                       L.n = nq; L.w = W; L.h = H; L.npoints = c->d_npoints + g0; L.valid = true;
                       r = map_fuse_launch(c, s, L); if (r) return r; }
-                    prof_end(c);
+                    prof_end(c, s);
                 } else {                     // odd widths: mask -> ordered back-projection -> insert
-                    prof_begin(c, "mask");
-                    HIPCHK(c, k_moving_mask(sem_q, nq, W, H, c->d_mask, s)); prof_end(c);
-                    prof_begin(c, "backproject");
+                    prof_begin(c, s, "mask");
+                    HIPCHK(c, k_moving_mask(sem_q, nq, W, H, c->d_mask, s)); prof_end(c, s);
+                    prof_begin(c, s, "backproject");
                     HIPCHK(c, k_backproject(in->depth + (size_t)g0 * npix, in->bgr + (size_t)g0 * npix * 3, sem_q, c->d_mask,
                                             in->pose ? in->pose + (size_t)g0 * 16 : nullptr, nq, W, H, c->cfg.camera, c->cfg.mapper_max_distance,
-                                            c->d_chunk_cnt, c->d_chunk_off, c->d_npoints + g0, c->d_total, c->d_points, s)); prof_end(c);
-                    prof_begin(c, "voxel_insert");
+                                            c->d_chunk_cnt, c->d_chunk_off, c->d_npoints + g0, c->d_total, c->d_points, s)); prof_end(c, s);
+                    prof_begin(c, s, "voxel_insert");
                     HIPCHK(c, k_voxel_insert(c->d_points, c->d_total, (int64_t)nq * (int64_t)npix, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, s));
-                    prof_end(c);
+                    prof_end(c, s);
                 }
                 r = map_after_launch(c, s, nq, (stages & SSM_STAGE_SEGNET) != 0 && (W & 15) == 0); if (r) return r;
             }
@@ -999,9 +984,9 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
         };
         // The map stage shares no data with the ORB -> match chain: in two-chain mode it runs on a third stream (all sub-batches in order, one workspace),
         // so that the chains' latency-bound kernels (pyramid, quad-tree, orientation / BRIEF gathers) always have VALU-bound map work beside them
-        // (+4 % over map-after-match on the chain's own stream).  With SSM_MAP_STREAM=0 chain 1 runs it FIRST instead, which puts the two chains half a
-        // sub-batch out of step (+2.4 %)
-        const bool map_first = two_chains && chain == 1 && c->map_first;
+        // (+4 % over map-after-match on the chain's own stream).  Chain 1 enqueues its map stage FIRST: with SSM_MAP_STREAM=0 (the map stage on the chain's
+        // own stream) that puts the two chains half a sub-batch out of step (+2.4 %)
+        const bool map_first = two_chains && chain == 1;
         if (map_first) { r = back(); if (r) return r; r = front(); if (r) return r; }
         else           { r = front(); if (r) return r; r = back(); if (r) return r; }
     }

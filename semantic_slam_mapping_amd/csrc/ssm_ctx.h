@@ -75,13 +75,18 @@ struct SegNetState {
     uint8_t* d_sem_gen = nullptr;       // generated colour labels for the sequence path (max_batch frames)
 };
 
+// workspace of the ORB front end for B frames (ssm_abi.hip orb_work_alloc): what pyramid .. describe write and read between them
+struct OrbWork {
+    uint8_t *pyr = nullptr, *blur = nullptr; int32_t *ncand = nullptr, *cellmax = nullptr /* inside ncand's allocation */; cand_t* cand = nullptr; uint16_t* nodeof = nullptr;
+    uint32_t* sel = nullptr; int32_t* nsel = nullptr; uint4* kpaux = nullptr;
+};
 
 struct ssm_ctx {
     std::mutex mu;
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;       // the context's main stream: created in ctx_init and never re-pointed; chain 0 of ssm_seq_process
     bool side_ready = false;            // ensure_side_streams completed
-    hipStream_t stream2 = nullptr;      // ssm_seq_process: the SegNet + map stage of a sub-batch runs here, beside the ORB + match chain
+    hipStream_t stream2 = nullptr;      // ssm_seq_process: chain 1; with a single chain, the SegNet + map stage of a sub-batch runs here beside it (stereo: SGBM)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipStream_t stream3 = nullptr; hipEvent_t ev_join3 = nullptr; int map_stream = 1;   // two-chain mode: the map stage on a stream of its own (SSM_MAP_STREAM=0: on the chain's stream)
     ssm_config cfg{};
@@ -95,14 +100,12 @@ struct ssm_ctx {
     void* d_xgrp[SSM_MAX_LEVELS] = {};       // resize4_kernel's per-group constants (null: the level uses the general resize kernel)
     PyrBandPlan pyr_bands, pyr_bands1;       // resize4_kernel_bands for batches / for the per-frame call (bands == 0: gray_kernel + k_pyramid)
     int32_t* d_yofs[SSM_MAX_LEVELS] = {}; int16_t* d_ya[SSM_MAX_LEVELS] = {};
-    // batch workspace (B frames)
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr; int32_t* d_cellmax = nullptr; cand_t* d_cand = nullptr; uint16_t* d_nodeof = nullptr;
-    int32_t* d_ncand = nullptr; uint32_t* d_sel = nullptr; int32_t* d_nsel = nullptr; int32_t* d_status = nullptr; uint4* d_kpaux = nullptr;
-    // second ORB / map workspace: ssm_seq_process runs alternate sub-batches as two chains on two streams (allocated at first use)
-    struct AltWork { uint8_t *pyr = nullptr, *blur = nullptr; int32_t* cellmax = nullptr; cand_t* cand = nullptr; uint16_t* nodeof = nullptr;
-                     int32_t* ncand = nullptr; uint32_t* sel = nullptr; int32_t* nsel = nullptr; uint8_t* mask = nullptr; uint4* kpaux = nullptr; bool ready = false; } alt, alt2;
+    // ORB workspaces (B frames each): work[0] serves every entry point that runs on `stream`; ssm_seq_process runs successive sub-batches as up to three
+    // ORB -> match chains -- chain k on its own stream (stream, stream2, stream4) with work[k]; work[1], work[2] are allocated at first use
+    OrbWork work[3];
+    int32_t* d_status = nullptr;        // the ORB scratch-overflow word: one, shared by all chains
     hipEvent_t ev_orb[3] = {nullptr, nullptr, nullptr};
-    hipStream_t stream4 = nullptr; hipEvent_t ev_join4 = nullptr; int nchains = 3;      // a third ORB -> match chain (workspace alt2, stream4) when a call has more than two sub-batches; SSM_CHAINS=2: two
+    hipStream_t stream4 = nullptr; hipEvent_t ev_join4 = nullptr;      // the third chain, used when a call has more than two sub-batches
     uint8_t* d_mask = nullptr; int32_t* d_chunk_cnt = nullptr; int64_t* d_chunk_off = nullptr; int64_t* d_total = nullptr;
     ssm_point* d_points = nullptr;
     ssm_point* d_vmap = nullptr; int vmap_n = 0; size_t vmap_cap = 0;      // Mapper::viewer's filtered map, device-resident (ssm_viewer_map_update)
@@ -124,7 +127,7 @@ struct ssm_ctx {
     int seq_cap = 0, prev_n = -1;
     ssm_keypoint* d_kps = nullptr; uint8_t* d_desc_all = nullptr; int32_t* d_nkp_all = nullptr; float* d_pos3d = nullptr;
     ssm_dmatch* d_matches = nullptr; int32_t* d_nmatch = nullptr; int32_t* d_match_pend = nullptr; int32_t* d_npoints = nullptr; uint8_t* d_hist_tmp = nullptr;
-    uint8_t* d_exp_q = nullptr; uint8_t* d_exp_t = nullptr; uint8_t* d_knn = nullptr; int capT = 0; bool match_mfma = true; bool map_first = true;   // the matcher's expanded descriptor rows (kernels_match.hip)
+    uint8_t* d_exp_q = nullptr; uint8_t* d_exp_t = nullptr; uint8_t* d_knn = nullptr; int capT = 0; bool match_mfma = true;   // the matcher's expanded descriptor rows (kernels_match.hip)
     // voxel tables
     MapLaunch map_ring[8] = {}; unsigned map_ring_next = 0; int32_t* d_redo = nullptr; std::vector<int32_t> map_skipped;    // launches that may still have skipped blocks; ids to run again (host)
     std::vector<hipStream_t> map_launch_streams; long map_redone = 0;      // streams fused launches were queued on; blocks run again so far
@@ -174,21 +177,21 @@ SSM_HIDDEN void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, s
 SSM_HIDDEN int ensure_scratch(ssm_ctx* c, size_t bytes);
 SSM_HIDDEN int ensure_pinned(ssm_ctx* c, size_t bytes);
 SSM_HIDDEN int ensure_scratch2(ssm_ctx* c, size_t bytes);
-SSM_HIDDEN void prof_begin(ssm_ctx* c, const char* name);
-SSM_HIDDEN void prof_end(ssm_ctx* c);
+SSM_HIDDEN void prof_begin(ssm_ctx* c, hipStream_t s, const char* name);     // s: the stream the stage's kernels run on
+SSM_HIDDEN void prof_end(ssm_ctx* c, hipStream_t s);
 SSM_HIDDEN int check_device_flags(ssm_ctx* c, bool with_map);
 SSM_HIDDEN int wait_pending(ssm_ctx* c);
 SSM_HIDDEN bool host_is_pinned(const void* p);             // page-locked host memory (ssm_host_alloc, hipHostRegister)?
 SSM_HIDDEN int ensure_side_streams(ssm_ctx* c);
 // ssm_map.hip
-SSM_HIDDEN int table_alloc(ssm_ctx* c, VoxTable& t, int cap_log2);
+SSM_HIDDEN int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2);
 SSM_HIDDEN int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out = nullptr);
 SSM_HIDDEN int map_before_launch(ssm_ctx* c, hipStream_t s, int remaining, int* nq);
 SSM_HIDDEN int map_after_launch(ssm_ctx* c, hipStream_t s, int frames, bool inputs_volatile);
 SSM_HIDDEN int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L);      // one launch of the fused map stage on the context map, recorded for a redo
 // ssm_segnet_abi.hip
 SSM_HIDDEN int seg_init(ssm_ctx* c);
-SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
+SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
 // ssm_stereo_abi.hip
 SSM_HIDDEN void stereo_free(StereoState* q);
 SSM_HIDDEN int sgbm_recover(ssm_ctx* c);

@@ -3,20 +3,20 @@
 #include "ssm_ctx.h"
 #include <algorithm>
 
-int table_alloc(ssm_ctx* c, VoxTable& t, int cap_log2)
+int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2)
 {
     t.cap_log2 = cap_log2;
     uint8_t* p; int r = dalloc(c, &p, t.bytes()); if (r) return r;
     const size_t slots = (size_t)1 << cap_log2;
     t.tab = reinterpret_cast<ssm_voxel*>(p); t.occ = reinterpret_cast<uint32_t*>(t.tab + slots); t.counters = reinterpret_cast<int32_t*>(t.occ + slots);
-    HIPCHK(c, k_voxel_clear(t.tab, -cap_log2, t.counters, c->stream));
+    HIPCHK(c, k_voxel_clear(t.tab, -cap_log2, t.counters, s));
     struct { int32_t cap, pad; ssm_voxel* buf; } tail = { t.ovf ? t.ovf_cap : 0, 0, t.ovf };      // counters[3], counters[4..5]
     static_assert(sizeof(tail) == 16, "counter block tail");
     int32_t head[3] = {0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(t.counters, head, 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t.counters + 3, &tail.cap, 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(t.counters + 4, &tail.buf, 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));                   // (the sources are on this stack)
+    HIPCHK(c, hipMemcpyAsync(t.counters, head, 12, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(t.counters + 3, &tail.cap, 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(t.counters + 4, &tail.buf, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));                   // (the sources are on this stack)
     return SSM_OK;
 }
 // every stream of the context that may hold work on the context map (ssm_seq_process with SSM_MAP_STREAM=0 runs the map stage of alternate sub-batches on the
@@ -134,7 +134,7 @@ int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out
             { const int r = map_drain_other_streams(c, s); if (r) return r; }      // nobody may still be inserting into the table that is replaced
             int L = t.cap_log2; while (L < c->vox_max_log2 && 4 * (n + m + reserve) > ((int64_t)1 << L)) L++;
             VoxTable nt; nt.ovf = t.ovf; nt.ovf_cap = t.ovf_cap; nt.skip = t.skip;
-            { hipStream_t keep = c->stream; c->stream = s; const int r = table_alloc(c, nt, L); c->stream = keep; if (r) return r; }
+            { const int r = table_alloc(c, s, nt, L); if (r) return r; }
             // the flags travel with the map; the new counter block goes on counting overflow records where the old one stopped (the records [lo, hi) are still to
             // merge, and the re-hash itself appends behind them should it need the list)
             const int32_t carry[2] = { cnt[1], cnt[2] < t.ovf_cap ? cnt[2] : t.ovf_cap };
@@ -430,7 +430,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
     // count all-gather below carries to every rank
     const int r_settle = map_settle(c, s, 0);
     if (r_settle) { const int32_t one = 1; HIPCHK(c, hipMemcpyAsync(c->map.counters + 1, &one, 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s)); }
-    prof_begin(c, "allgather");
+    prof_begin(c, s, "allgather");
     // Every decision that can end the call is taken COLLECTIVELY: a rank that returned between two collectives would leave its peers blocked in the
     // next one.  (1) all-gather {voxel count, flag word} per rank -- counters[0..1] of the map table, already on the device.
     NCCLCHK(c, ncclAllGather(c->map.counters, c->d_comm_counts, 2, ncclInt32, comm, s));
@@ -440,8 +440,8 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
     std::vector<int32_t> counts(world);
     int mx = 1, bad_rank = -1, neg_rank = -1;
     for (int q = 0; q < world; q++) { counts[q] = cf[2 * q]; if (cf[2 * q + 1] & 1) bad_rank = q; if (counts[q] < 0) neg_rank = q; if (counts[q] > mx) mx = counts[q]; }
-    if (bad_rank >= 0) { prof_end(c); FAIL(c, SSM_E_CAPACITY, "voxel table of rank " + std::to_string(bad_rank) + " is incomplete (contributions were dropped, or it could not be settled); no rank merged"); }
-    if (neg_rank >= 0) { prof_end(c); FAIL(c, SSM_E_COMM, "negative voxel count received from rank " + std::to_string(neg_rank)); }
+    if (bad_rank >= 0) { prof_end(c, s); FAIL(c, SSM_E_CAPACITY, "voxel table of rank " + std::to_string(bad_rank) + " is incomplete (contributions were dropped, or it could not be settled); no rank merged"); }
+    if (neg_rank >= 0) { prof_end(c, s); FAIL(c, SSM_E_COMM, "negative voxel count received from rank " + std::to_string(neg_rank)); }
     // (2) the receive buffer: slot r = rank r's voxels, mx entries each.  An allocation failure on one rank is agreed on by a second tiny all-gather.
     const size_t slot = (size_t)mx * sizeof(ssm_voxel);
     int r_alloc = ensure_scratch2(c, slot * world + 256);
@@ -453,7 +453,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
         HIPCHK(c, hipMemcpyAsync(cf.data(), c->d_comm_counts, (size_t)world * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (int q = 0; q < world; q++) if (cf[q]) {
-            prof_end(c);
+            prof_end(c, s);
             if (r_alloc) return r_alloc;
             FAIL(c, SSM_E_NOMEM, "rank " + std::to_string(q) + " could not allocate the all-gather buffer; no rank merged");
         }
@@ -467,7 +467,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
         if (q == rank) continue;
         HIPCHK(c, k_voxel_merge(reinterpret_cast<const ssm_voxel*>(recv + slot * q), counts[q], c->map.tab, c->map.cap_log2, c->map.counters, s));
     }
-    prof_end(c);
+    prof_end(c, s);
     return SSM_OK;
 }
 static inline float ord2f(int i) { i = i >= 0 ? i : i ^ 0x7FFFFFFF; float f; memcpy(&f, &i, 4); return f; }
@@ -479,7 +479,7 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
     *n_out = 0;
     if (n == 0) return SSM_OK;
     int r;
-    if (!c->tmp.tab) { r = table_alloc(c, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
+    if (!c->tmp.tab) { r = table_alloc(c, c->stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
     else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_point) + 64); if (r) return r;
     ssm_point* dp = reinterpret_cast<ssm_point*>(c->d_scratch);
@@ -505,7 +505,7 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
         const int bigger = c->tmp.cap_log2 + 2;
         if (bigger > 28) FAIL(c, SSM_E_CAPACITY, "voxel_filter: more than 2^28 voxels");
         hipFree(c->tmp.tab); c->tmp.tab = nullptr;
-        r = table_alloc(c, c->tmp, bigger); if (r) return r;
+        r = table_alloc(c, c->stream, c->tmp, bigger); if (r) return r;
     }
     return table_export_points(c, c->tmp, out, cap, n_out);
 }
@@ -614,7 +614,7 @@ extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* 
     if (!rebuild && c->vmap_n) { HIPCHK(c, hipMemcpyAsync(c->d_vcat, c->d_vmap, (size_t)c->vmap_n * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->stream)); off = (size_t)c->vmap_n; }
     for (int i = 0; i < n; i++) { HIPCHK(c, k_cloud_transform(clouds[i]->d, clouds[i]->n, poses + (size_t)16 * i, c->d_vcat + off, c->stream)); off += (size_t)clouds[i]->n; }
     const int N = (int)total;
-    if (!c->tmp.tab) { r = table_alloc(c, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
+    if (!c->tmp.tab) { r = table_alloc(c, c->stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
     else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
     float* mm = reinterpret_cast<float*>(c->d_vcat + total);
     HIPCHK(c, k_voxel_bounds(c->d_vcat, N, mm, c->stream));
@@ -642,7 +642,7 @@ extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* 
         const int bigger = c->tmp.cap_log2 + 2;
         if (bigger > 28) FAIL(c, SSM_E_CAPACITY, "viewer map: more than 2^28 voxels");
         hipFree(c->tmp.tab); c->tmp.tab = nullptr;
-        r = table_alloc(c, c->tmp, bigger); if (r) return r;
+        r = table_alloc(c, c->stream, c->tmp, bigger); if (r) return r;
     }
     int nv; ssm_voxel* comp; uint32_t* order;
     r = table_sorted(c, c->tmp, &nv, &comp, &order); if (r) return r;

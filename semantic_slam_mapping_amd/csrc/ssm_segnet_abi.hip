@@ -109,9 +109,9 @@ extern "C" int ssm_segnet_set_layer(ssm_ctx* c, int l, const float* weight, cons
 // forward for nb <= seg->batch device frames already pre-processed into actA; leaves logits in the returned buffer
 // logits_out != nullptr: the class logits are materialised (returned buffer) and the caller runs the ArgMax kernel;
 // logits_out == nullptr: the last layer writes the labels (g->labels) straight from its epilogue.
-static int seg_forward_core(ssm_ctx* c, int nb, void** logits_out)
+static int seg_forward_core(ssm_ctx* c, hipStream_t s, int nb, void** logits_out)
 {
-    SegNetState* g = c->seg; hipStream_t s = c->stream;
+    SegNetState* g = c->seg;
     void* cur = g->actA; void* nxt = g->actB;
     HIPCHK(c, k_segnet_begin(s));
     auto conv = [&](int l) -> int {
@@ -156,22 +156,22 @@ static int seg_forward_core(ssm_ctx* c, int nb, void** logits_out)
     }
     return SSM_OK;
 }
-int seg_forward_dev(ssm_ctx* c, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags)
+int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags)
 {
     int r = seg_init(c); if (r) return r;
     SegNetState* g = c->seg;
     for (int l = 0; l < SEG_LAYERS; l++) if (!g->set[l]) FAIL(c, SSM_E_INVAL, "SegNet layer " + std::to_string(l) + " has no weights (ssm_segnet_set_layer)");
-    const int W = c->g.W, H = c->g.H; hipStream_t s = c->stream;
+    const int W = c->g.W, H = c->g.H;
     for (int f0 = 0; f0 < n; f0 += g->batch) {
         const int nb = n - f0 < g->batch ? n - f0 : g->batch;
         HIPCHK(c, k_segnet_prep(bgr + (size_t)f0 * W * H * 3, nb, W, H, SEG_NW, SEG_NH, g->pre_xofs, g->pre_xa, g->pre_yofs, g->pre_ya, g->actA, s));
         if (flags & 4) {                           // keep the class logits (ssm_segnet_forward / ssm_segnet_logits): separate ArgMax kernel
             void* logits = nullptr;
-            r = seg_forward_core(c, nb, &logits); if (r) return r;
+            r = seg_forward_core(c, s, nb, &logits); if (r) return r;
             g->last_logits = logits;               // frame f0 of the last sub-batch starts the buffer
             HIPCHK(c, k_segnet_argmax(logits, nb, SEG_NW * SEG_NH, g->coutstore[SEG_LAYERS - 1], SEG_NCLS, g->labels, s));
         } else {
-            r = seg_forward_core(c, nb, nullptr); if (r) return r;
+            r = seg_forward_core(c, s, nb, nullptr); if (r) return r;
             g->last_logits = nullptr;
         }
         if (labels_net) HIPCHK(c, hipMemcpyAsync(labels_net + (size_t)f0 * SEG_NW * SEG_NH, g->labels, (size_t)nb * SEG_NW * SEG_NH, hipMemcpyDeviceToDevice, s));
@@ -185,7 +185,7 @@ extern "C" int ssm_segnet_forward_dev(ssm_ctx* c, const uint8_t* bgr, int n, uin
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!bgr || n < 0) FAIL(c, SSM_E_INVAL, "bad arguments");
-    return seg_forward_dev(c, bgr, n, labels_net, sem_bgr, flags);
+    return seg_forward_dev(c, c->stream, bgr, n, labels_net, sem_bgr, flags);
 }
 extern "C" int ssm_segnet_forward(ssm_ctx* c, const uint8_t* bgr, int w, int h, int stride, uint8_t* labels_net, uint8_t* sem_bgr)
 {
@@ -196,7 +196,7 @@ extern "C" int ssm_segnet_forward(ssm_ctx* c, const uint8_t* bgr, int w, int h, 
     if (stride < w * 3) FAIL(c, SSM_E_INVAL, "stride smaller than a row");
     HIPCHK(c, hipMemcpy2DAsync(c->d_in_img, (size_t)w * 3, bgr, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream));
     int r = ensure_scratch(c, (size_t)SEG_NW * SEG_NH); if (r) return r;
-    r = seg_forward_dev(c, c->d_in_img, 1, labels_net ? (uint8_t*)c->d_scratch : nullptr, sem_bgr ? c->d_in_sem : nullptr, 4); if (r) return r;
+    r = seg_forward_dev(c, c->stream, c->d_in_img, 1, labels_net ? (uint8_t*)c->d_scratch : nullptr, sem_bgr ? c->d_in_sem : nullptr, 4); if (r) return r;
     if (labels_net) HIPCHK(c, hipMemcpyAsync(labels_net, c->d_scratch, (size_t)SEG_NW * SEG_NH, hipMemcpyDeviceToHost, c->stream));
     if (sem_bgr) HIPCHK(c, hipMemcpyAsync(sem_bgr, c->d_in_sem, (size_t)w * h * 3, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));

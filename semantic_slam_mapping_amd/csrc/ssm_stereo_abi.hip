@@ -130,7 +130,7 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     for (int f0 = 0; f0 < n; f0 += B) {
         const int nb = n - f0 < B ? n - f0 : B;
         if (stages & SSM_STEREO_QUAD) {
-            prof_begin(c, "quad_track");
+            prof_begin(c, sq, "quad_track");
             // level 0 of the nb frames into slots 1 .. nb of both sides, then the pyramids and derivatives
             HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(0 * qb.B1 + 1) * qb.slot_elems, qb.slot_elems, in->left + (size_t)f0 * np, np, np, nb, hipMemcpyDeviceToDevice, sq));
             HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(1 * qb.B1 + 1) * qb.slot_elems, qb.slot_elems, in->right + (size_t)f0 * np, np, np, nb, hipMemcpyDeviceToDevice, sq));
@@ -148,23 +148,22 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
                 HIPCHK(c, hipMemcpyAsync(q->pyr + (size_t)(side * qb.B1) * qb.slot_elems, q->pyr + (size_t)(side * qb.B1 + nb) * qb.slot_elems, qb.slot_elems, hipMemcpyDeviceToDevice, sq));
                 HIPCHK(c, hipMemcpyAsync(q->der + (size_t)(side * qb.B1) * qb.slot_elems * 2, q->der + (size_t)(side * qb.B1 + nb) * qb.slot_elems * 2, qb.slot_elems * 4, hipMemcpyDeviceToDevice, sq));
             }
-            prof_end(c);
+            prof_end(c, sq);
         }
         if (stages & SSM_STEREO_VO) {
-            prof_begin(c, "vo");
+            prof_begin(c, sq, "vo");
             HIPCHK(c, k_vo_estimate_batch(q->quad + (size_t)f0 * maxc, maxc, q->nquad + f0, nb, in->vo, in->rand_stream, in->ransac_iters, q->consumed, q->rand_off,
                                           q->tr_all, q->vcount, q->tr + (size_t)f0 * 6, q->inliers + (size_t)f0 * maxc, q->vo_result + (size_t)f0 * 2, sq));
-            prof_end(c);
+            prof_end(c, sq);
         }
         if (stages & SSM_STEREO_DEPTH) {
             const int alt = (f0 / B) % nsg;
             hipStream_t sg = sgs[alt];
-            struct StreamSet { ssm_ctx* c; hipStream_t keep; StreamSet(ssm_ctx* c_, hipStream_t s_) : c(c_), keep(c_->stream) { c->stream = s_; } ~StreamSet() { c->stream = keep; } } on(c, sg);   // stage events on SGBM's stream
-            prof_begin(c, "sgbm");
+            prof_begin(c, sg, "sgbm");                                  // (the stage events on SGBM's stream)
             HIPCHK(c, k_sgbm(in->left + (size_t)f0 * np, in->right + (size_t)f0 * np, w, h, nb, in->sgbm, q->sg_wsN[alt], q->sg_ws_bytesN[alt], q->disp + (size_t)f0 * np, 0, sg, q->sg_fail + (f0 / B) % SG_FAIL_WORDS,
                              c->sgbm_form_cfg, nsg));
             HIPCHK(c, k_sgbm_depth(q->disp + (size_t)f0 * np, w, h, nb, in->baseline, in->cu, in->cv, in->f, in->roix, in->roiy, in->roiz, in->scale, q->dminN[alt], q->depth + (size_t)f0 * np, sg));
-            prof_end(c);
+            prof_end(c, sg);
         }
     }
     if (two) { HIPCHK(c, hipEventRecord(c->ev_join, sd)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); }
@@ -318,9 +317,9 @@ static int sgbm_run(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w
     uint8_t* dev = nullptr;
     r = stereo_stage_images(c, imgs, 2, w, h, stride, &dev); if (r) return r;
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }      // ssm_get_stage_times then reports this call ("sgbm": all kernels of k_sgbm)
-    prof_begin(c, "sgbm");
+    prof_begin(c, c->stream, "sgbm");
     HIPCHK(c, k_sgbm(dev, dev + (size_t)w * h, w, h, 1, *params, q->sg_wsN[0], q->sg_ws_bytesN[0], q->disp, stage, c->stream, q->sg_fail, form, 1));
-    prof_end(c);
+    prof_end(c, c->stream);
     q->sg_pending.valid = false;                                  // (the staged pair is this call's: the host-pointer entry points repeat a timed-out sweep themselves)
     *d_disp_out = q->disp; *d_depth_out = q->depth;
     return SSM_OK;
@@ -447,10 +446,10 @@ extern "C" int ssm_vo_estimate(ssm_ctx* c, const ssm_pmatch* matches, int n, con
     HIPCHK(c, hipMemcpyAsync(p + o_m, matches, (size_t)n * sizeof(ssm_pmatch), hipMemcpyHostToDevice, s));
     if (iters) HIPCHK(c, hipMemcpyAsync(p + o_s, samples, (size_t)iters * 12, hipMemcpyHostToDevice, s));
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
-    prof_begin(c, "vo");
+    prof_begin(c, s, "vo");
     HIPCHK(c, k_vo_estimate((const ssm_pmatch*)(p + o_m), n, *params, (const int32_t*)(p + o_s), iters, (double*)(p + o_tr), (int32_t*)(p + o_cnt),
                             (double*)(p + o_out), (int32_t*)(p + o_inl), (int32_t*)(p + o_res), s));
-    prof_end(c);
+    prof_end(c, s);
     int32_t res[2] = {0, 0};
     HIPCHK(c, hipMemcpyAsync(tr, p + o_out, 48, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipMemcpyAsync(res, p + o_res, 8, hipMemcpyDeviceToHost, s));
@@ -496,9 +495,9 @@ static int pnp_solve_impl(ssm_ctx* c, const float* img, const float* obj, int n,
     a.seq_base = (unsigned)c->pnp_epoch << 20;                  // a solve makes a few thousand passes at most; the ring is zeroed again when the epoch wraps
     if (G > 1) c->pnp_epoch = (c->pnp_epoch + 1) & 4095;
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
-    prof_begin(c, "pnp");
+    prof_begin(c, s, "pnp");
     HIPCHK(c, k_pnp_solve(a, s));
-    prof_end(c);
+    prof_end(c, s);
     HIPCHK(c, hipMemcpyAsync(hd, p + o_hdr + 128, down, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     unsigned failed = 0; int32_t m = 0;
