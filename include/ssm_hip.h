@@ -398,6 +398,16 @@ int ssm_debug_pyramid(ssm_ctx* ctx, const uint8_t* img, int channels, int n, int
  * *ntiles: the tile count (tiles NULL: only that; SSM_E_INVAL when cap is smaller).  limits (6 ints, may be NULL): the static LDS bytes of the FAST
  * kernel, the most groups and scored rows its arrays hold, the staged pixel row width and row count, the staging area (candidates) */
 int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int cap, int* ntiles, int32_t* limits);
+/* the fused pyramid's plan of a configuration, on the host only (no context, no device): the work items of every (band, level >= 1), listed by the
+ * decomposition the kernel uses.  bands > 0: that band count; 0: what batches run; -1: what the one-frame call runs (4-pixel items on every level).  Per item, 12 ints: level, band,
+ * pixels per item (8, or 4 where the level's groups do not fit the 8-pixel layout), column group, first and last output row it writes, first and last
+ * source row it reads, the byte range [lo, hi) its windows read in the source level's LDS buffer and the byte range [lo, hi) it writes in its own.
+ * *nitems: the item count (items NULL: only that; SSM_E_INVAL when cap is smaller).  band_tab (may be NULL): bands x levels x (comp_lo, comp_hi,
+ * own_lo, own_hi), rows inclusive.  limits (52 ints, may be NULL): band count (0: the geometry has no fused plan at this count; nothing else is
+ * listed), LDS bytes, offset of the odd levels' buffer, slack bytes behind each buffer, threads per block, LDS limit, levels, bit masks per level
+ * (has the 4-pixel table; fits the 8-pixel layout; the plan uses the 8-pixel item), six
+ * reserved, then (w, h, stride) of each level */
+int ssm_debug_pyramid_plan(const ssm_config* cfg, int bands, int32_t* items, int cap, int* nitems, int32_t* band_tab, int32_t* limits);
 /* the SGBM post stages alone, as the last steps of ssm_sgbm launch them, on n stacked int16 maps (host, w x h each, rows packed) -> out (same shape):
  * op bit 0 = medianBlur 3x3 (replicate border), bit 1 = filterSpeckles (4-neighbours, both != new_val, |a - b| <= max_diff; components of at most
  * max_size pixels become new_val) on the median's output, or on the input without bit 0.  For exact tests of the kernels on constructed maps */

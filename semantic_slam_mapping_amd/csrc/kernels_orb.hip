@@ -126,6 +126,7 @@ resize_kernel(uint8_t* __restrict__ pyr, int pyr_bytes, int src_off, int sw, int
 // resident) -- no LDS staging, no barrier, no byte-granular LDS reads.  Per pixel: pick the dword pair, v_alignbyte to bring
 // the two neighbours to the low bytes, v_perm to spread them into 16-bit lanes, v_dot2_u32_u16 with the (a0, a1) pair, then
 // the vertical blend with umulhi on coefficients pre-shifted by 16.  The per-group constants (XGroup) come from the host.
+struct XGroup8 { uint32_t a[8]; uint32_t base, offs, pad0, pad1; };  // the same for 8 pixels; offs of pixels 4 - 7 counted from base + 4 (resize4_kernel_bands)
 struct XGroup { uint32_t a[4]; uint32_t base, offs, pad0, pad1; };   // a[k] = a0 | a1 << 16; base = byte offset of pixel 0's left neighbour (any alignment); offs = 4 bits per pixel: its left neighbour's offset from base (<= 6)
 __global__ void __launch_bounds__(256)
 resize4_kernel(uint8_t* __restrict__ pyr, int pyr_bytes, int src_off, int sh, int sstride, int dst_off, int dh, int dstride,
@@ -201,128 +202,211 @@ hipError_t k_pyramid(int n, const OrbGeom& g, uint8_t* pyr, const int32_t* const
 // writes only its own rows of each level to the pyramid buffer as 16-byte stores.  The arithmetic is gray_kernel's and resize4_kernel's, so the
 // buffer is byte-identical to theirs.  Band rows (pyramid_band_plan, host): own(l, b) = [b h_l / B, (b + 1) h_l / B); comp(L-1, b) = own(L-1, b),
 // comp(l, b) = own(l, b) u src_rows(comp(l + 1, b)) -- contiguous.  The per-band halo is recomputed, not exchanged: 15 % more level-0 rows at B = 8, 33 % at B = 16,
-// and the kernel's time grows with them (it is bound by instruction issue, not by latency: more, smaller bands were slower).
+// and the kernel's time grows with them: more, smaller bands were slower.
+// A level's work items (pyr_items, ssm_internal.h; tests/test_pyramid_items.py checks them on the host): 8 pixels x the four rows of one block of the y
+// tables where every 8-pixel group of the level fits four dwords (scale factors below ~1.4; pyramid_xgroups), else resize4_kernel's 4 pixels x 4 rows.
 // The kernel's name starts with resize4_kernel so that the profiles attribute it to the pyramid stage.
 #ifndef PB_T
-#define PB_T 1024             // (512 threads: 4 % slower at B = 8)
-#endif
-#ifndef PB_U
-#define PB_U 4                 // level-0 quads a thread has in flight at once
+#define PB_T 1024             // (512 threads: 154 us against 150 at B = 8)
 #endif
 #ifndef PB_BANDS
-#define PB_BANDS 8             // bands per frame in batches (640 x 480: 79 KB of LDS, two blocks per CU); measured per 250 frames: 8 bands 176 us, 12: 197, 16: 208, 32: 280
+#define PB_BANDS 8             // bands per frame in batches (640 x 480: 79 KB of LDS, two blocks per CU); measured per 250 frames with the 8-pixel items: 8 bands 150 us, 12: 173, 16: 208 (4-pixel items: 176, 197, 208)
 #endif
-template <int MODE>            // 0: BGR, byte loads; 1: BGR, 12-byte loads (W % 4 == 0, input 4-aligned); 2: one channel
-__global__ void __launch_bounds__(PB_T)
+// MODE 0: BGR, byte loads; 1: BGR, 12-byte loads (W % 4 == 0, input 4-aligned); 2: one channel.  WIDE: the plan has levels with 8-pixel items (batches);
+// false (the one-frame call: 32 blocks on the whole device, bound by each block's chain of latencies, not by issue): every level runs the shorter 4-pixel
+// items, and a thread's first tables of the next level are loaded ahead of the barrier -- registers that the 8-pixel loop cannot spare
+template <int MODE, bool WIDE>
+__global__ void __launch_bounds__(PB_T, PB_T / 128)      // two blocks per CU (their LDS): PB_T / 128 waves per SIMD, 64 VGPRs at 1024 threads
 resize4_kernel_bands(const uint8_t* __restrict__ img, uint8_t* __restrict__ pyr, OrbGeom g, const int4* __restrict__ band_tab, PyrBandArgs t)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // [level buffer 0 (even levels)][level buffer 1 (odd levels), at t.buf1]
     const int frame = blockIdx.y;
     const int4* bt = band_tab + blockIdx.x * g.nlevels;                 // (comp_lo, comp_hi, own_lo, own_hi) per level
     uint8_t* fpyr = pyr + (size_t)frame * g.pyr_bytes;
-    {   // level 0: comp rows of the input to gray, one dword (4 pixels) per item, PB_U items' loads in flight before the first is used
+    {   // level 0: comp rows of the input to gray.  One item = 16 pixels of one row = one 16-byte LDS store: the (row, column) split and the addresses are
+        // paid once per 16 pixels, and an item's four loads are in flight before the first is used.  Offsets are 32-bit from a uniform base (a frame
+        // whose bands fit the level buffers is far below 2^31 bytes)
         const int4 r = bt[0];
-        const int W = g.W, quads = g.L[0].stride >> 2, items = quads * (r.y - r.x + 1);
-        const uint8_t* src = img + (size_t)frame * W * g.H * (MODE == 2 ? 1 : 3);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(smem);
-        for (int q0 = threadIdx.x; q0 < items; q0 += PB_T * PB_U) {
-            uint32_t v[PB_U][3];
+        const int W = g.W, g16 = g.L[0].stride >> 4, items = g16 * (r.y - r.x + 1);
+        constexpr int CH = MODE == 2 ? 1 : 3;
+        const uint8_t* src = img + ((size_t)frame * g.H + r.x) * W * CH;
+        uint4* dst = reinterpret_cast<uint4*>(smem);
+        for (int i = threadIdx.x; i < items; i += PB_T) {
+            const int ry = (int)__umulhi((uint32_t)i, t.mulq0), x0 = (i - ry * g16) << 4;
+            const uint32_t p = (uint32_t)ry * (uint32_t)W + (uint32_t)x0;
+            uint32_t v[4][3];
 #pragma unroll
-            for (int k = 0; k < PB_U; k++) {
-                const int q = q0 + k * PB_T;
-                const int ry = (int)__umulhi((uint32_t)q, t.mulq0), x = (q - ry * quads) << 2;
+            for (int k = 0; k < 4; k++) {
+                const int x = x0 + 4 * k;
+                if (MODE == 1) { __builtin_memcpy(v[k], src + 3 * (p - x0 + min(x, W - 4)), 12); continue; }   // (a padding quad loads the row's last one and is zeroed below)
                 v[k][0] = v[k][1] = v[k][2] = 0;
-                if (q >= items || x >= W) continue;                                                   // row padding: zeros
-                const size_t p = (size_t)(r.x + ry) * W + x;
-                if (MODE == 1) __builtin_memcpy(v[k], src + 3 * p, 12);
-                else if (MODE == 2) { for (int i = 0; i < 4; i++) if (x + i < W) v[k][0] |= (uint32_t)src[p + i] << (8 * i); }
+                if (x >= W) continue;                                                                 // row padding: zeros
+                const uint32_t pk = p + 4 * k;
+                if (MODE == 2) { for (int j = 0; j < 4; j++) if (x + j < W) v[k][0] |= (uint32_t)src[pk + j] << (8 * j); }
                 else {
-                    for (int i = 0; i < 4; i++)
-                        if (x + i < W) v[k][0] |= ((src[3 * (p + i)] * 1868u + src[3 * (p + i) + 1] * 9617u + src[3 * (p + i) + 2] * 4899u + 8192u) >> 14) << (8 * i);
+                    for (int j = 0; j < 4; j++)
+                        if (x + j < W) v[k][0] |= ((src[3 * (pk + j)] * 1868u + src[3 * (pk + j) + 1] * 9617u + src[3 * (pk + j) + 2] * 4899u + 8192u) >> 14) << (8 * j);
                 }
             }
+            uint32_t o[4];
 #pragma unroll
-            for (int k = 0; k < PB_U; k++) {
-                const int q = q0 + k * PB_T;
-                if (q >= items) break;
-                uint32_t out = v[k][0];
+            for (int k = 0; k < 4; k++) {
+                o[k] = v[k][0];
                 if (MODE == 1) {
+                    // gray_kernel's sums, times four, by v_dot4_u32_u8: the weights x 4 split as 256 hi + lo (7472 = 29, 48; 38468 = 150, 68; 19596 = 76, 140),
+                    // rounding constant 4 x 8192; (4 s) >> 16 == s >> 14 exactly, every partial sum is below 2^24, and the result (<= 255: the weights sum
+                    // to 2^16) is byte 2 of the sum, which v_perm gathers.  A pixel's three bytes are brought into one dword (pixel 3 lies in bytes 1 - 3
+                    // of c: shifted weights); the fourth byte meets a zero weight.  The builtin, not inline asm: see udot4 below
+                    const uint32_t LO = 0x008C4430u, HI = 0x004C961Du;
                     const uint32_t a = v[k][0], b = v[k][1], c = v[k][2];
-                    const uint32_t p0 = ((a & 255) * 1868 + ((a >> 8) & 255) * 9617 + ((a >> 16) & 255) * 4899 + 8192) >> 14;
-                    const uint32_t p1 = ((a >> 24) * 1868 + (b & 255) * 9617 + ((b >> 8) & 255) * 4899 + 8192) >> 14;
-                    const uint32_t p2 = (((b >> 16) & 255) * 1868 + (b >> 24) * 9617 + (c & 255) * 4899 + 8192) >> 14;
-                    const uint32_t p3 = (((c >> 8) & 255) * 1868 + ((c >> 16) & 255) * 9617 + (c >> 24) * 4899 + 8192) >> 14;
-                    const int ry = (int)__umulhi((uint32_t)q, t.mulq0), x = (q - ry * quads) << 2;
-                    out = x < W ? p0 | (p1 << 8) | (p2 << 16) | (p3 << 24) : 0u;
+                    const uint32_t x1 = __builtin_amdgcn_alignbyte(b, a, 3), x2 = __builtin_amdgcn_alignbyte(c, b, 2);
+                    const uint32_t s0 = (__builtin_amdgcn_udot4(a, HI, 0u, false) << 8) + __builtin_amdgcn_udot4(a, LO, 32768u, false);
+                    const uint32_t s1 = (__builtin_amdgcn_udot4(x1, HI, 0u, false) << 8) + __builtin_amdgcn_udot4(x1, LO, 32768u, false);
+                    const uint32_t s2 = (__builtin_amdgcn_udot4(x2, HI, 0u, false) << 8) + __builtin_amdgcn_udot4(x2, LO, 32768u, false);
+                    const uint32_t s3 = (__builtin_amdgcn_udot4(c, HI << 8, 0u, false) << 8) + __builtin_amdgcn_udot4(c, LO << 8, 32768u, false);
+                    o[k] = __builtin_amdgcn_perm(s1, s0, 0x0C0C0602u) | __builtin_amdgcn_perm(s3, s2, 0x06020C0Cu);
+                    if (x0 + 4 * k >= W) o[k] = 0;                                                    // row padding
                 }
-                dst[q] = out;
             }
+            dst[i] = make_uint4(o[0], o[1], o[2], o[3]);
         }
     }
-    // the tables of a thread's first item of the next level do not depend on LDS: their loads are issued before the barrier that ends a level
+    // (!WIDE) the tables of a thread's first item of the next level do not depend on LDS: their loads are issued before the barrier that ends a level
     uint4 pA = {}, pQ = {}, pYO = {}, pYA = {};
-    auto tables = [&](int l, int i, uint4& A, uint4& Q, uint4& YO, uint4& YA) {
+    auto tables4 = [&](int l, int i, uint4& A, uint4& Q, uint4& YO, uint4& YA) {
         const int4 r = bt[l];
-        const int groups = g.L[l].stride >> 2, ch = (int)__umulhi((uint32_t)i, t.mulg[l]), gi = i - ch * groups, y0 = (r.x & ~3) + 4 * ch;
+        const PyrItems it = pyr_items(g.L[l].stride, 0, r.x, r.y);
+        if (i >= it.items) return;
+        const int ch = pyr_item_run(i, t.mulg[l]), gi = i - ch * it.groups, y0 = it.c0 + 4 * ch;
         const uint4* xg = reinterpret_cast<const uint4*>(t.xg[l]);
         A = xg[2 * gi]; Q = xg[2 * gi + 1];
         YO = *reinterpret_cast<const uint4*>(t.yofs[l] + y0); YA = *reinterpret_cast<const uint4*>(t.ya[l] + 2 * y0);
     };
-    auto first_items = [&](int l) { const int4 r = bt[l]; return (g.L[l].stride >> 2) * (((r.y - (r.x & ~3)) >> 2) + 1); };
-    if (g.nlevels > 1 && (int)threadIdx.x < first_items(1)) tables(1, threadIdx.x, pA, pQ, pYO, pYA);
+    if (!WIDE && g.nlevels > 1) tables4(1, threadIdx.x, pA, pQ, pYO, pYA);
     __syncthreads();
     for (int l = 1; l <= g.nlevels; l++) {
         const int4 rs = bt[l - 1];
         const LevelGeom& a = g.L[l - 1];
-        const uint8_t* sbuf = smem + ((l - 1) & 1 ? t.buf1 : 0);
+        const int soff = (l - 1) & 1 ? t.buf1 : 0;
+        const uint8_t* sbuf = smem + soff;
         {   // level l-1 is complete in sbuf, which nothing writes in this phase: its own rows leave for the pyramid buffer
             const int n16 = ((rs.w - rs.z + 1) * a.stride) >> 4;
             const uint4* s = reinterpret_cast<const uint4*>(sbuf + (rs.z - rs.x) * a.stride);
             uint4* d = reinterpret_cast<uint4*>(fpyr + a.img_off + (size_t)rs.z * a.stride);
-            for (int i = threadIdx.x; i < n16; i += PB_T) d[i] = s[i];
+            for (uint32_t i = threadIdx.x; i < (uint32_t)n16; i += PB_T) d[i] = s[i];        // (unsigned: a uniform base + a 32-bit lane offset, no 64-bit pointer kept per thread)
         }
         if (l == g.nlevels) break;
-        // level l, comp rows, from level l-1 in LDS: resize4_kernel's item (one 4-pixel group x four rows of the y tables' 4-row blocks)
         const int4 r = bt[l];
         const LevelGeom& b = g.L[l];
-        uint8_t* dbuf = smem + (l & 1 ? t.buf1 : 0);
-        const int groups = b.stride >> 2, c0 = r.x & ~3, items = groups * (((r.y - c0) >> 2) + 1);
+        const int doff = l & 1 ? t.buf1 : 0;
+        uint8_t* dbuf = smem + doff;
+        const int wide = WIDE ? pyr_wide(t, l) : 0;
+        const PyrItems it = pyr_items(b.stride, wide, r.x, r.y);
+        const int32_t* yofs = t.yofs[l]; const int16_t* ya = t.ya[l];
         typedef unsigned short ushort2v __attribute__((ext_vector_type(2)));
-        for (int i = threadIdx.x; i < items; i += PB_T) {
-            const int ch = (int)__umulhi((uint32_t)i, t.mulg[l]), gi = i - ch * groups, y0 = c0 + 4 * ch;
-            uint4 A = pA, Q = pQ, YO = pYO, YA = pYA;
-            if (i != (int)threadIdx.x) tables(l, i, A, Q, YO, YA);
-            const uint32_t yo[4] = {YO.x, YO.y, YO.z, YO.w}, yc[4] = {YA.x, YA.y, YA.z, YA.w};
-            const uint32_t av[4] = {A.x, A.y, A.z, A.w};
-            uint32_t sel[4];
+        if (wide) {
+            // level l, comp rows, from level l-1 in LDS.  One item = 8 pixels x the rows of one of the y tables' 4-row blocks.  The thread keeps the
+            // horizontal pass (>> 4) of two source rows, hX and hY, which take turns as the upper and the lower row of the vertical blend: an output row
+            // whose upper source row is the previous output row's lower one (four times out of five at scale 1.2) computes one horizontal pass, not two.
+            // prevB = the source row in the array that is the upper one next (-1: none).  Same integers in the same order as resize4_kernel.
+            // (Two blocks per item would share more rows -- 1.3 horizontal passes per output row against 1.4 -- but the rolling state across the second
+            // block's table loads, and likewise loading a thread's first tables of the next level ahead of the barrier as the 4-pixel form does,
+            // took the kernel past the 64 VGPRs that two 1024-thread blocks per CU leave it: both spilled.)
+            const uint4* xg = reinterpret_cast<const uint4*>(t.xg[l]);
+            const int sstride = a.stride, dstride = b.stride, nrows = r.y - r.x, shm1 = a.h - 1;
+            for (int i = threadIdx.x; i < it.items; i += PB_T) {
+                const int blk = pyr_item_run(i, t.mulg[l]), gi = i - blk * it.groups, y0 = it.c0 + 4 * blk;
+                const uint4 A = xg[3 * gi], A2 = xg[3 * gi + 1], Q = xg[3 * gi + 2];
+                const uint4 YO = *reinterpret_cast<const uint4*>(yofs + y0), YA = *reinterpret_cast<const uint4*>(ya + 2 * y0);
+                const uint32_t av[8] = {A.x, A.y, A.z, A.w, A2.x, A2.y, A2.z, A2.w};
+                uint32_t sel[8];
 #pragma unroll
-            for (int k = 0; k < 4; k++) sel[k] = ((Q.y >> (4 * k)) & 15u) * 0x00010001u + 0x0C010C00u;
+                for (int k = 0; k < 8; k++) sel[k] = ((Q.y >> (4 * k)) & 15u) * 0x00010001u + 0x0C010C00u;      // bytes (off, zero, off + 1, zero) of the pixel's dword pair
+                // row strides are multiples of 16, so a window's misalignment is the group's (Q.x & 3) in every row, and its aligned start advances by the stride
+                const uint32_t shift = Q.x & 3u;
+                const int ebase = soff + (int)(Q.x & ~3u) - rs.x * sstride, dbase = doff + 8 * gi - r.x * dstride;
+                auto hrow = [&](int sy, uint32_t (&h)[8]) {
+                    const uint32_t* w = reinterpret_cast<const uint32_t*>(smem + (ebase + (int)__umul24(sy, sstride)));
+                    const uint32_t u0 = w[0], u1 = w[1], u2 = w[2], u3 = w[3];
+                    const uint32_t n0 = __builtin_amdgcn_alignbyte(u1, u0, shift), n1 = __builtin_amdgcn_alignbyte(u2, u1, shift), n2 = __builtin_amdgcn_alignbyte(u3, u2, shift);
 #pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int y = y0 + j;
-                if (y < r.x || y > r.y) continue;
-                const int syA = (int)yo[j], syB = min(syA + 1, a.h - 1);
-                // the 8-byte window of each source row from three aligned dwords (LDS has no unaligned 8-byte read): the same bytes as resize4_kernel's load
-                const int e0 = (syA - rs.x) * a.stride + (int)Q.x, e1 = (syB - rs.x) * a.stride + (int)Q.x;
-                const uint32_t* w0 = reinterpret_cast<const uint32_t*>(sbuf + (e0 & ~3));
-                const uint32_t* w1 = reinterpret_cast<const uint32_t*>(sbuf + (e1 & ~3));
-                const uint32_t u0 = w0[0], u1 = w0[1], u2 = w0[2], t0 = w1[0], t1 = w1[1], t2 = w1[2];
-                const uint32_t r0x = __builtin_amdgcn_alignbyte(u1, u0, e0 & 3), r0y = __builtin_amdgcn_alignbyte(u2, u1, e0 & 3);
-                const uint32_t r1x = __builtin_amdgcn_alignbyte(t1, t0, e1 & 3), r1y = __builtin_amdgcn_alignbyte(t2, t1, e1 & 3);
-                const uint32_t b0 = yc[j] << 16, b1 = yc[j] & 0xFFFF0000u;
-                uint32_t o = 0;
+                    for (int k = 0; k < 8; k++) {
+                        const uint32_t p = k < 4 ? __builtin_amdgcn_perm(n1, n0, sel[k]) : __builtin_amdgcn_perm(n2, n1, sel[k]);
+                        ushort2v c2, x; memcpy(&c2, &av[k], 4); memcpy(&x, &p, 4);
+                        h[k] = __builtin_amdgcn_udot2(x, c2, 0u, false) >> 4;
+                    }
+                };
+                uint32_t hX[8], hY[8];
 #pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t p0 = __builtin_amdgcn_perm(r0y, r0x, sel[k]), p1 = __builtin_amdgcn_perm(r1y, r1x, sel[k]);
-                    ushort2v c2, x0, x1; memcpy(&c2, &av[k], 4); memcpy(&x0, &p0, 4); memcpy(&x1, &p1, 4);
-                    const uint32_t h0 = __builtin_amdgcn_udot2(x0, c2, 0u, false), h1 = __builtin_amdgcn_udot2(x1, c2, 0u, false);
-                    const uint32_t v = (__umulhi(b0, h0 >> 4) + __umulhi(b1, h1 >> 4) + 2u) >> 2;
-                    o |= (v & 255u) << (8 * k);
+                for (int k = 0; k < 8; k++) { hX[k] = __builtin_nondeterministic_value(hX[k]); hY[k] = __builtin_nondeterministic_value(hY[k]); }   // any value, for no instruction: the first row writes both (prevB = -1), and without this the arrays stay live around the loop as if carried from the previous item
+                int prevB = -1;
+                {
+                    const uint32_t yo[4] = {YO.x, YO.y, YO.z, YO.w}, yc[4] = {YA.x, YA.y, YA.z, YA.w};
+#pragma unroll
+                    for (int j = 0; j < 4; j++) {
+                        const int y = y0 + j;
+                        if ((uint32_t)(y - r.x) > (uint32_t)nrows) continue;
+                        const int syA = (int)yo[j], syB = min(syA + 1, shm1);
+                        uint32_t (&up)[8] = j & 1 ? hY : hX;
+                        uint32_t (&lo)[8] = j & 1 ? hX : hY;
+                        if (syA != prevB) hrow(syA, up);
+                        hrow(syB, lo);
+                        prevB = syB;
+                        const uint32_t b0 = yc[j] << 16, b1 = yc[j] & 0xFFFF0000u;
+                        uint32_t o[2] = {0, 0};
+#pragma unroll
+                        for (int k = 0; k < 8; k++) {
+                            const uint32_t v = (__umulhi(b0, up[k]) + __umulhi(b1, lo[k]) + 2u) >> 2;       // <= 255: the host checked a0 + a1 <= 2048 and b0 + b1 <= 2048
+                            o[k >> 2] |= v << (8 * (k & 3));
+                        }
+                        *reinterpret_cast<uint2*>(smem + (dbase + (int)__umul24(y, dstride))) = make_uint2(o[0], o[1]);
+                    }
                 }
-                *reinterpret_cast<uint32_t*>(dbuf + (y - r.x) * b.stride + 4 * gi) = o;
+            }
+        } else {
+            // the levels whose 8-pixel groups do not fit four dwords (scale factors above ~1.4): resize4_kernel's item (one 4-pixel group x four rows of the y tables' 4-row blocks)
+            for (int i = threadIdx.x; i < it.items; i += PB_T) {
+                const int ch = pyr_item_run(i, t.mulg[l]), gi = i - ch * it.groups, y0 = it.c0 + 4 * ch;
+                uint4 A, Q, YO, YA;
+                if (WIDE) {
+                    const uint4* xg = reinterpret_cast<const uint4*>(t.xg[l]);
+                    A = xg[2 * gi]; Q = xg[2 * gi + 1]; YO = *reinterpret_cast<const uint4*>(yofs + y0); YA = *reinterpret_cast<const uint4*>(ya + 2 * y0);
+                } else {
+                    A = pA; Q = pQ; YO = pYO; YA = pYA;
+                    if (i != (int)threadIdx.x) tables4(l, i, A, Q, YO, YA);
+                }
+                const uint32_t yo[4] = {YO.x, YO.y, YO.z, YO.w}, yc[4] = {YA.x, YA.y, YA.z, YA.w};
+                const uint32_t av[4] = {A.x, A.y, A.z, A.w};
+                uint32_t sel[4];
+#pragma unroll
+                for (int k = 0; k < 4; k++) sel[k] = ((Q.y >> (4 * k)) & 15u) * 0x00010001u + 0x0C010C00u;
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const int y = y0 + j;
+                    if (y < r.x || y > r.y) continue;
+                    const int syA = (int)yo[j], syB = min(syA + 1, a.h - 1);
+                    // the 8-byte window of each source row from three aligned dwords (LDS has no unaligned 8-byte read): the same bytes as resize4_kernel's load
+                    const int e0 = (syA - rs.x) * a.stride + (int)Q.x, e1 = (syB - rs.x) * a.stride + (int)Q.x;
+                    const uint32_t* w0 = reinterpret_cast<const uint32_t*>(sbuf + (e0 & ~3));
+                    const uint32_t* w1 = reinterpret_cast<const uint32_t*>(sbuf + (e1 & ~3));
+                    const uint32_t u0 = w0[0], u1 = w0[1], u2 = w0[2], t0 = w1[0], t1 = w1[1], t2 = w1[2];
+                    const uint32_t r0x = __builtin_amdgcn_alignbyte(u1, u0, e0 & 3), r0y = __builtin_amdgcn_alignbyte(u2, u1, e0 & 3);
+                    const uint32_t r1x = __builtin_amdgcn_alignbyte(t1, t0, e1 & 3), r1y = __builtin_amdgcn_alignbyte(t2, t1, e1 & 3);
+                    const uint32_t b0 = yc[j] << 16, b1 = yc[j] & 0xFFFF0000u;
+                    uint32_t o = 0;
+#pragma unroll
+                    for (int k = 0; k < 4; k++) {
+                        const uint32_t p0 = __builtin_amdgcn_perm(r0y, r0x, sel[k]), p1 = __builtin_amdgcn_perm(r1y, r1x, sel[k]);
+                        ushort2v c2, x0, x1; memcpy(&c2, &av[k], 4); memcpy(&x0, &p0, 4); memcpy(&x1, &p1, 4);
+                        const uint32_t h0 = __builtin_amdgcn_udot2(x0, c2, 0u, false), h1 = __builtin_amdgcn_udot2(x1, c2, 0u, false);
+                        const uint32_t v = (__umulhi(b0, h0 >> 4) + __umulhi(b1, h1 >> 4) + 2u) >> 2;
+                        o |= (v & 255u) << (8 * k);
+                    }
+                    *reinterpret_cast<uint32_t*>(dbuf + (y - r.x) * b.stride + 4 * gi) = o;
+                }
             }
         }
-        if (l + 1 < g.nlevels && (int)threadIdx.x < first_items(l + 1)) tables(l + 1, threadIdx.x, pA, pQ, pYO, pYA);
+        if (!WIDE && l + 1 < g.nlevels) tables4(l + 1, threadIdx.x, pA, pQ, pYO, pYA);
         __syncthreads();
     }
 }
@@ -338,34 +422,36 @@ static hipError_t pb_allow_lds(const void* fn, size_t bytes)
     return e;
 }
 hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeom& g, uint8_t* pyr, const PyrBandPlan& p,
-                           const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, hipStream_t s)
+                           const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, const void* const* xgroups8, hipStream_t s)
 {
     PyrBandArgs t = p.args;
-    for (int l = 1; l < g.nlevels; l++) { t.xg[l] = xgroups[l]; t.yofs[l] = yofs[l]; t.ya[l] = ya[l]; }
+    for (int l = 1; l < g.nlevels; l++) { t.xg[l] = pyr_wide(t, l) ? xgroups8[l] : xgroups[l]; t.yofs[l] = yofs[l]; t.ya[l] = ya[l]; }
     const dim3 grid(p.bands, n);
     const int4* tab = reinterpret_cast<const int4*>(p.d_tab);
-    const void* fn;
-    if (channels == 1) fn = reinterpret_cast<const void*>(resize4_kernel_bands<2>);
-    else if ((g.W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0) fn = reinterpret_cast<const void*>(resize4_kernel_bands<1>);
-    else fn = reinterpret_cast<const void*>(resize4_kernel_bands<0>);
-    const hipError_t e = pb_allow_lds(fn, p.lds); if (e != hipSuccess) return e;
-    if (channels == 1) resize4_kernel_bands<2><<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
-    else if (fn == reinterpret_cast<const void*>(resize4_kernel_bands<1>)) resize4_kernel_bands<1><<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
-    else resize4_kernel_bands<0><<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
-    return hipGetLastError();
+    const int mode = channels == 1 ? 2 : ((g.W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0) ? 1 : 0;
+    auto launch = [&](auto kernel) {
+        const hipError_t e = pb_allow_lds(reinterpret_cast<const void*>(kernel), p.lds); if (e != hipSuccess) return e;
+        kernel<<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
+        return hipGetLastError();
+    };
+    if (t.wide) return mode == 2 ? launch(resize4_kernel_bands<2, true>) : mode == 1 ? launch(resize4_kernel_bands<1, true>) : launch(resize4_kernel_bands<0, true>);
+    return mode == 2 ? launch(resize4_kernel_bands<2, false>) : mode == 1 ? launch(resize4_kernel_bands<1, false>) : launch(resize4_kernel_bands<0, false>);
 }
+int pyramid_block_threads() { return PB_T; }
 // the band count of a geometry: PB_BANDS per frame for batches, 32 for the one-frame call (one frame on more CUs); more bands where the level
-// buffers would not fit; none where a level needs the general resize kernel (p.bands stays 0)
-bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p)
+// buffers would not fit; none where a level needs the general resize kernel (p.bands stays 0).  The 8-pixel items are for batches, where the kernel is
+// bound by instruction issue; the one-frame call keeps the 4-pixel items on every level (shorter dependent chains per thread: measured 17.0 us against
+// 18.9 with the 8-pixel items, profiles/r10_pyramid_rows.md)
+bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, const bool* wide_ok, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p)
 {
     static const int cand[2][8] = {{PB_BANDS, 12, 16, 24, 32, 48, 64, 0}, {32, 48, 64, 0}};
     for (int i = 0; i < 8 && cand[batch ? 0 : 1][i]; i++)
-        if (cand[batch ? 0 : 1][i] >= (batch ? PB_BANDS : 0) && pyramid_band_plan(g, yofs, streaming, cand[batch ? 0 : 1][i], tab, p)) return true;
+        if (cand[batch ? 0 : 1][i] >= (batch ? PB_BANDS : 0) && pyramid_band_plan(g, yofs, streaming, batch ? wide_ok : nullptr, cand[batch ? 0 : 1][i], tab, p)) return true;
     return false;
 }
 // The band rows of every (band, level) for `bands` bands, from the host's y tables (yofs[l]: level l's source rows in level l-1).  false: the geometry
 // has no fused form at this band count (a level without the streaming x tables, fewer rows than bands, or level buffers beyond PB_MAX_LDS).
-bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, int bands, std::vector<int32_t>& tab, PyrBandPlan& p)
+bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, const bool* wide_ok, int bands, std::vector<int32_t>& tab, PyrBandPlan& p)
 {
     const int L = g.nlevels;
     if (bands < 1) return false;
@@ -386,16 +472,59 @@ bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const
             lo = clo; hi = chi;
         }
     }
-    // 16 bytes of slack behind each buffer: the 8-byte windows (read as three dwords) may end past the last row, as resize4_kernel's do past the pyramid
-    const size_t buf1 = (need[0] + 16 + 15) & ~(size_t)15, lds = buf1 + need[1] + 16;
+    // PYR_SLACK bytes behind each buffer: a window starts at the 4-aligned address at or below a source byte of its row (<= stride - 4 from the row's
+    // start) and is 12 (4-pixel item, three dwords) or 16 bytes long (8-pixel item, four), so in a buffer's last row it ends up to 8 / 12 bytes past it
+    const size_t buf1 = (need[0] + PYR_SLACK + 15) & ~(size_t)15, lds = buf1 + need[1] + PYR_SLACK;
     if (lds > PB_MAX_LDS) return false;
     memset(&p.args, 0, sizeof(p.args));
     p.args.buf1 = (int)buf1;
-    const int q0 = g.L[0].stride >> 2;
+    const int q0 = g.L[0].stride >> 4;                                     // level 0's items: 16 pixels
     p.args.mulq0 = (uint32_t)(((1ull << 32) + q0 - 1) / q0);
-    for (int l = 1; l < L; l++) { const int gr = g.L[l].stride >> 2; p.args.mulg[l] = (uint32_t)(((1ull << 32) + gr - 1) / gr); }
+    for (int l = 1; l < L; l++) {
+        const int wide = wide_ok && wide_ok[l] ? 1 : 0;
+        const int gr = g.L[l].stride >> (wide ? 3 : 2);
+        p.args.wide |= (uint32_t)wide << l;
+        p.args.mulg[l] = (uint32_t)(((1ull << 32) + gr - 1) / gr);
+    }
     p.bands = bands; p.lds = lds;
     return true;
+}
+void pyramid_xgroups(const std::vector<int32_t>& xo, const std::vector<int16_t>& xa, const std::vector<int16_t>& ya, int dw, int dstride, int sstride,
+                     std::vector<uint32_t>& xg4, std::vector<uint32_t>& xg8, bool& fits4, bool& fits8)
+{
+    const int g4 = dstride / 4, g8 = dstride / 8;
+    xg4.assign((size_t)g4 * 8, 0u); xg8.assign((size_t)g8 * 12, 0u); fits4 = fits8 = true;
+    auto pair = [&](int x) { return (uint32_t)(uint16_t)xa[2 * x] | ((uint32_t)(uint16_t)xa[2 * x + 1] << 16); };
+    for (int x = 0; x < dw; x++) if (xa[2 * x] < 0 || xa[2 * x + 1] < 0 || xa[2 * x] + xa[2 * x + 1] > 2048) fits8 = false;
+    for (size_t y = 0; 2 * y + 1 < ya.size(); y++) if (ya[2 * y] < 0 || ya[2 * y + 1] < 0 || ya[2 * y] + ya[2 * y + 1] > 2048) fits8 = false;
+    for (int q = 0; q < g4; q++) {
+        uint32_t* e = &xg4[(size_t)q * 8];
+        const int x0 = 4 * q;
+        if (x0 >= dw) continue;                                               // padding group: coefficients 0 -> zeros, window at 0
+        const int base = xo[x0];
+        e[4] = (uint32_t)base;
+        for (int k = 0; k < 4 && x0 + k < dw; k++) {
+            const int off = xo[x0 + k] - base;
+            if (off < 0 || off > 6) fits4 = false;
+            e[k] = pair(x0 + k);
+            e[5] |= (uint32_t)(off & 15) << (4 * k);
+        }
+        if ((base & ~3) + 12 > sstride + PYR_SLACK) fits4 = false;            // (cannot happen: base < sstride)
+    }
+    for (int q = 0; q < g8; q++) {
+        uint32_t* e = &xg8[(size_t)q * 12];
+        const int x0 = 8 * q;
+        if (x0 >= dw) continue;
+        const int base = xo[x0];
+        e[8] = (uint32_t)base;
+        for (int k = 0; k < 8 && x0 + k < dw; k++) {
+            const int off = xo[x0 + k] - base - (k < 4 ? 0 : 4);              // from the pixel's dword pair: (0, 1) of the normalised window or (1, 2)
+            if (off < 0 || off > 6) fits8 = false;
+            e[k] = pair(x0 + k);
+            e[9] |= (uint32_t)(off & 15) << (4 * k);
+        }
+        if ((base & ~3) + 16 > sstride + PYR_SLACK) fits8 = false;
+    }
 }
 
 // ------------------------------------------------------------------ K5a: 7x7 sigma-2 Gaussian, fixed point

@@ -215,44 +215,36 @@ static int ctx_init(ssm_ctx* c)
           HIPCHK(c, hipMemcpy(c->d_blur_tab, bt.data(), bt.size(), hipMemcpyHostToDevice)); }
         DALLOC(c, c->d_pattern_f, 1024);
         HIPCHK(c, hipMemcpy(c->d_pattern_f, pf, sizeof(pf), hipMemcpyHostToDevice)); }
-    std::vector<int32_t> yall[SSM_MAX_LEVELS]; bool streaming[SSM_MAX_LEVELS] = {};
+    std::vector<int32_t> yall[SSM_MAX_LEVELS]; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
     for (int l = 1; l < g.nlevels; l++) {
         std::vector<int32_t> xo, yo; std::vector<int16_t> xa, ya;
         resize_tables(g.L[l-1].w, g.L[l].w, xo, xa); resize_tables(g.L[l-1].h, g.L[l].h, yo, ya);
         yall[l] = yo;
+        // per 4-pixel group (the streaming kernel takes a group's source bytes with one 8-byte load per row) and per 8-pixel group (the fused kernel:
+        // four LDS dwords per row): the (a0, a1) pairs, the byte offset of the first pixel's left neighbour and each pixel's offset from it
+        std::vector<uint32_t> xg, xg8; bool fits = false, fits8 = false;
+        pyramid_xgroups(xo, xa, ya, g.L[l].w, g.L[l].stride, g.L[l-1].stride, xg, xg8, fits, fits8);
         while (yo.size() & 3) { yo.push_back(yo.back()); ya.push_back(ya[ya.size() - 2]); ya.push_back(ya[ya.size() - 2]); }   // resize4_kernel reads the y tables four rows at a time
         DALLOC(c, c->d_xofs[l], xo.size()); DALLOC(c, c->d_xa[l], xa.size()); DALLOC(c, c->d_yofs[l], yo.size()); DALLOC(c, c->d_ya[l], ya.size());
         HIPCHK(c, hipMemcpy(c->d_xofs[l], xo.data(), xo.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_xa[l], xa.data(), xa.size() * 2, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_yofs[l], yo.data(), yo.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_ya[l], ya.data(), ya.size() * 2, hipMemcpyHostToDevice));
-        // per 4-pixel group: the (a0, a1) pairs, the byte offset of the first pixel's left neighbour and each pixel's offset from it; the streaming
-        // kernel takes the group's source bytes with one 8-byte load per row, so every offset + 1 must lie inside those 8 bytes
-        const int groups = g.L[l].stride / 4, dw = g.L[l].w;
-        std::vector<uint32_t> xg((size_t)groups * 8, 0u); bool fits = true;
-        for (int q = 0; q < groups; q++) {
-            uint32_t* e = &xg[(size_t)q * 8];
-            const int x0 = 4 * q;
-            if (x0 >= dw) continue;                                               // padding group: coefficients 0 -> zeros, window at 0
-            const int base = xo[x0];
-            e[4] = (uint32_t)base;
-            for (int k = 0; k < 4 && x0 + k < dw; k++) {
-                const int off = xo[x0 + k] - base;
-                if (off < 0 || off > 6) fits = false;
-                e[k] = (uint32_t)(uint16_t)xa[2 * (x0 + k)] | ((uint32_t)(uint16_t)xa[2 * (x0 + k) + 1] << 16);
-                e[5] |= (uint32_t)(off & 15) << (4 * k);
-            }
-        }
         if (fits) {
             uint32_t* d = nullptr; DALLOC(c, d, xg.size());
             HIPCHK(c, hipMemcpy(d, xg.data(), xg.size() * 4, hipMemcpyHostToDevice));
             c->d_xgrp[l] = d; streaming[l] = true;
         }
+        if (fits && fits8) {
+            uint32_t* d = nullptr; DALLOC(c, d, xg8.size());
+            HIPCHK(c, hipMemcpy(d, xg8.data(), xg8.size() * 4, hipMemcpyHostToDevice));
+            c->d_xgrp8[l] = d; wide_ok[l] = true;
+        }
     }
     // the fused pyramid's band tables (none where a level needs the general resize kernel)
     for (int k = 0; k < 2; k++) {
         PyrBandPlan& p = k ? c->pyr_bands1 : c->pyr_bands; std::vector<int32_t> tab;
-        if (!pyramid_band_choose(g, yall, streaming, k == 0, tab, p)) continue;
+        if (!pyramid_band_choose(g, yall, streaming, wide_ok, k == 0, tab, p)) continue;
         int32_t* d = nullptr; DALLOC(c, d, tab.size());
         HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         p.d_tab = d;
@@ -319,7 +311,7 @@ extern "C" void ssm_destroy(ssm_ctx* c)
     for (int i = 0; i < 3; i++) if (c->ev_orb[i]) hipEventDestroy(c->ev_orb[i]);
     if (c->stream4) hipStreamDestroy(c->stream4);
     if (c->ev_join4) hipEventDestroy(c->ev_join4);
-    for (int l = 0; l < SSM_MAX_LEVELS; l++) { if (c->d_xofs[l]) hipFree(c->d_xofs[l]); if (c->d_xa[l]) hipFree(c->d_xa[l]); if (c->d_yofs[l]) hipFree(c->d_yofs[l]); if (c->d_ya[l]) hipFree(c->d_ya[l]); if (c->d_xgrp[l]) hipFree(c->d_xgrp[l]); }
+    for (int l = 0; l < SSM_MAX_LEVELS; l++) { if (c->d_xofs[l]) hipFree(c->d_xofs[l]); if (c->d_xa[l]) hipFree(c->d_xa[l]); if (c->d_yofs[l]) hipFree(c->d_yofs[l]); if (c->d_ya[l]) hipFree(c->d_ya[l]); if (c->d_xgrp[l]) hipFree(c->d_xgrp[l]); if (c->d_xgrp8[l]) hipFree(c->d_xgrp8[l]); }
     if (c->pyr_bands.d_tab) hipFree(c->pyr_bands.d_tab); if (c->pyr_bands1.d_tab) hipFree(c->pyr_bands1.d_tab);
     if (c->seg) {
         SegNetState* g = c->seg;
@@ -414,7 +406,7 @@ static int make_pyramid(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_
 {
     const OrbGeom& g = c->g;
     if (plan.bands) {
-        prof_begin(c, s, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, w.pyr, plan, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c, s);
+        prof_begin(c, s, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, w.pyr, plan, c->d_yofs, c->d_ya, c->d_xgrp, c->d_xgrp8, s)); prof_end(c, s);
         return SSM_OK;
     }
     prof_begin(c, s, "gray");      HIPCHK(c, k_gray(d_img, channels, nb, g, w.pyr, s)); prof_end(c, s);
@@ -469,6 +461,64 @@ extern "C" int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int ca
     return SSM_OK;
 }
 
+extern "C" int ssm_debug_pyramid_plan(const ssm_config* cfg, int bands, int32_t* items, int cap, int* nitems, int32_t* band_tab, int32_t* limits)
+{
+    if (!cfg || !nitems) return SSM_E_INVAL;
+    OrbGeom g; std::string err;
+    { const int r = build_geometry(*cfg, g, err); if (r) return r; }
+    const int L = g.nlevels;
+    std::vector<int32_t> yall[SSM_MAX_LEVELS], xall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
+    for (int l = 1; l < L; l++) {
+        std::vector<int16_t> xa, ya; std::vector<uint32_t> xg, xg8; bool f4, f8;
+        resize_tables(g.L[l-1].w, g.L[l].w, xall[l], xa); resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya);
+        pyramid_xgroups(xall[l], xa, ya, g.L[l].w, g.L[l].stride, g.L[l-1].stride, xg, xg8, f4, f8);
+        streaming[l] = f4; wide_ok[l] = f4 && f8;
+    }
+    PyrBandPlan p;
+    const bool ok = bands > 0 ? pyramid_band_plan(g, yall, streaming, wide_ok, bands, tab, p) : pyramid_band_choose(g, yall, streaming, wide_ok, bands == 0, tab, p);
+    if (limits) {
+        int32_t v[16 + 3 * SSM_MAX_LEVELS] = {ok ? p.bands : 0, (int32_t)p.lds, p.args.buf1, PYR_SLACK, pyramid_block_threads(), PB_MAX_LDS, L};
+        for (int l = 1; l < L; l++) { v[7] |= (streaming[l] ? 1 : 0) << l; v[8] |= (wide_ok[l] ? 1 : 0) << l; }
+        if (ok) v[9] = (int32_t)p.args.wide;
+        for (int l = 0; l < L; l++) { v[16 + 3 * l] = g.L[l].w; v[17 + 3 * l] = g.L[l].h; v[18 + 3 * l] = g.L[l].stride; }
+        memcpy(limits, v, sizeof(v));
+    }
+    *nitems = 0;
+    if (!ok) return SSM_OK;                                              // no fused form: limits[0] == 0
+    if (band_tab) memcpy(band_tab, tab.data(), tab.size() * 4);
+    int n = 0;
+    for (int b = 0; b < p.bands; b++)
+        for (int l = 1; l < L; l++) {
+            const int32_t* rs = &tab[((size_t)b * L + l - 1) * 4]; const int32_t* r = &tab[((size_t)b * L + l) * 4];
+            const LevelGeom& A = g.L[l-1]; const LevelGeom& B = g.L[l];
+            const int wide = pyr_wide(p.args, l), px = wide ? 8 : 4;
+            const PyrItems it = pyr_items(B.stride, wide, r[0], r[1]);
+            for (int i = 0; i < it.items; i++, n++) {
+                if (!items) continue;
+                if (n >= cap) return SSM_E_INVAL;
+                /* the rows and windows of item i, as resize4_kernel_bands walks them */
+                const int blk = pyr_item_run(i, p.args.mulg[l]), gi = i - blk * it.groups;
+                const int x0 = px * gi, base = x0 < B.w ? xall[l][x0] : 0;
+                int ylo = 1 << 30, yhi = -1, slo = 1 << 30, shi = -1, rlo = 1 << 30, rhi = -(1 << 30);
+                    for (int j = 0; j < 4; j++) {
+                        const int y = it.c0 + 4 * blk + j;
+                        if (y < r[0] || y > r[1]) continue;
+                        ylo = std::min(ylo, y); yhi = std::max(yhi, y);
+                        const int sy[2] = {yall[l][y], std::min(yall[l][y] + 1, A.h - 1)};
+                        for (int k = 0; k < 2; k++) {
+                            const int e = (sy[k] - rs[0]) * A.stride + base;
+                            slo = std::min(slo, sy[k]); shi = std::max(shi, sy[k]);
+                            rlo = std::min(rlo, e & ~3); rhi = std::max(rhi, (e & ~3) + (wide ? 16 : 12));
+                        }
+                    }
+                const int32_t v[12] = {l, b, px, gi, ylo, yhi, slo, shi, rlo, rhi, (ylo - r[0]) * B.stride + px * gi, (yhi - r[0]) * B.stride + px * gi + px};
+                memcpy(items + 12 * (size_t)n, v, sizeof(v));
+            }
+        }
+    *nitems = n;
+    return SSM_OK;
+}
+
 extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes)
 {
     if (!c) return SSM_E_INVAL;
@@ -486,9 +536,9 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
     if (bands < 0) p.bands = 0;
     else if (bands == 0) p = n > 1 ? c->pyr_bands : c->pyr_bands1;
     else {
-        std::vector<int32_t> yall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {};
-        for (int l = 1; l < g.nlevels; l++) { std::vector<int16_t> ya; resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya); streaming[l] = c->d_xgrp[l] != nullptr; }
-        if (!pyramid_band_plan(g, yall, streaming, bands, tab, p)) FAIL(c, SSM_E_INVAL, "no fused pyramid at this band count");
+        std::vector<int32_t> yall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
+        for (int l = 1; l < g.nlevels; l++) { std::vector<int16_t> ya; resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya); streaming[l] = c->d_xgrp[l] != nullptr; wide_ok[l] = c->d_xgrp8[l] != nullptr; }
+        if (!pyramid_band_plan(g, yall, streaming, wide_ok, bands, tab, p)) FAIL(c, SSM_E_INVAL, "no fused pyramid at this band count");
         int32_t* d = nullptr; DALLOC(c, d, tab.size()); p.d_tab = d;
         HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     }

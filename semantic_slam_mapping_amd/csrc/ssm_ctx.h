@@ -98,6 +98,7 @@ struct ssm_ctx {
     int8_t* d_pattern = nullptr; float* d_pattern_f = nullptr;      // the BRIEF table as given, and as floats for brief_kernel
     int32_t* d_xofs[SSM_MAX_LEVELS] = {}; int16_t* d_xa[SSM_MAX_LEVELS] = {};
     void* d_xgrp[SSM_MAX_LEVELS] = {};       // resize4_kernel's per-group constants (null: the level uses the general resize kernel)
+    void* d_xgrp8[SSM_MAX_LEVELS] = {};      // the fused pyramid's 8-pixel groups (null: the level's groups do not fit that layout; it keeps the 4-pixel item)
     PyrBandPlan pyr_bands, pyr_bands1;       // resize4_kernel_bands for batches / for the per-frame call (bands == 0: gray_kernel + k_pyramid)
     int32_t* d_yofs[SSM_MAX_LEVELS] = {}; int16_t* d_ya[SSM_MAX_LEVELS] = {};
     // ORB workspaces (B frames each): work[0] serves every entry point that runs on `stream`; ssm_seq_process runs successive sub-batches as up to three

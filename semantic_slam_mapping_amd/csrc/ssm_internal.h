@@ -76,13 +76,36 @@ hipError_t k_pyramid(int n, const OrbGeom& g, uint8_t* pyr, const int32_t* const
                      const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, hipStream_t s);
 // the pyramid in one launch (resize4_kernel_bands: gray + every level, one block per (band, frame)); the plan is built once per geometry and band count
 #define PB_MAX_LDS (80 * 1024)     // two blocks per CU at least
-struct PyrBandArgs { const void* xg[SSM_MAX_LEVELS]; const int32_t* yofs[SSM_MAX_LEVELS]; const int16_t* ya[SSM_MAX_LEVELS]; uint32_t mulq0, mulg[SSM_MAX_LEVELS]; int buf1; };
+struct PyrBandArgs {
+    const void* xg[SSM_MAX_LEVELS]; const int32_t* yofs[SSM_MAX_LEVELS]; const int16_t* ya[SSM_MAX_LEVELS]; uint32_t mulq0, mulg[SSM_MAX_LEVELS]; int buf1;
+    uint32_t wide;                 // bit l: level l's items are 8 pixels wide (xg[l] = its XGroup8 table); clear: 4 pixels (XGroup)
+};
+__host__ __device__ inline int pyr_wide(const PyrBandArgs& t, int l) { return (int)(t.wide >> l) & 1; }
 struct PyrBandPlan { int bands = 0; size_t lds = 0; void* d_tab = nullptr; PyrBandArgs args = {}; };     // bands == 0: no fused form (k_gray + k_pyramid)
-// tab: bands x levels x (comp_lo, comp_hi, own_lo, own_hi); false: no fused form at this band count
-bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p);
-bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, int bands, std::vector<int32_t>& tab, PyrBandPlan& p);
+// The work items of one (band, level) of the fused kernel: column groups of 4 or 8 pixels x the y tables' 4-row blocks, counted from
+// the block that holds the band's first comp row.  Item i = (block, group) = (i / groups, i % groups), the division by the plan's reciprocal mulg.
+// The kernel and ssm_debug_pyramid_plan (which lists the items for the tests) both take the decomposition from here.
+struct PyrItems { int groups, c0, nblk, items; };
+__host__ __device__ inline PyrItems pyr_items(int stride, int wide, int comp_lo, int comp_hi)
+{
+    PyrItems it; it.groups = stride >> (wide ? 3 : 2); it.c0 = comp_lo & ~3; it.nblk = ((comp_hi - it.c0) >> 2) + 1;
+    it.items = it.groups * it.nblk;
+    return it;
+}
+__host__ __device__ inline int pyr_item_run(int i, uint32_t mulg) { return (int)(((uint64_t)(uint32_t)i * mulg) >> 32); }      // exact: i * groups < 2^32
+#define PYR_SLACK 16               // bytes behind each level buffer: a window of the last source row may end past it (pyramid_xgroups bounds it)
+// the per-group x constants of one level: XGroup (4 pixels, 8 dwords) and XGroup8 (8 pixels, 12 dwords), and whether every group of the level fits the
+// layout the kernels assume (fits4: each pixel's pair inside 8 bytes from the first pixel's left neighbour; fits8: pixels 0 - 3 inside those 8 bytes,
+// pixels 4 - 7 inside the 8 bytes from 4 on, and no coefficient pair -- ya: the level's y pairs -- above 2048 in sum, which bounds a result by 255)
+void pyramid_xgroups(const std::vector<int32_t>& xo, const std::vector<int16_t>& xa, const std::vector<int16_t>& ya, int dw, int dstride, int sstride,
+                     std::vector<uint32_t>& xg4, std::vector<uint32_t>& xg8, bool& fits4, bool& fits8);
+// tab: bands x levels x (comp_lo, comp_hi, own_lo, own_hi); false: no fused form at this band count.  streaming[l]: level l has the 4-pixel table,
+// wide_ok[l]: it also fits the 8-pixel layout
+bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, const bool* wide_ok, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p);
+bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, const bool* wide_ok, int bands, std::vector<int32_t>& tab, PyrBandPlan& p);
 hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeom& g, uint8_t* pyr, const PyrBandPlan& p,
-                           const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, hipStream_t s);
+                           const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, const void* const* xgroups8, hipStream_t s);
+int pyramid_block_threads();       // PB_T
 hipError_t k_blur(int n, const OrbGeom& g, const uint8_t* pyr, uint8_t* blur, hipStream_t s);
 // the same blur on the matrix cores; tab = blur_mfma_tables() on the device
 #define BLUR_ROWS 58           // output rows of one blur_mfma block (64 input rows)
