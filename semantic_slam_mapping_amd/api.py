@@ -89,6 +89,13 @@ def default_config(**kw):
     return cfg
 
 
+def live_allocations():
+    """(buffers, device bytes, pinned host bytes) the library itself holds right now, process-wide: ssm_debug_live_allocations"""
+    n, d, p = C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+    _lib.load().ssm_debug_live_allocations(C.byref(n), C.byref(d), C.byref(p))
+    return n.value, d.value, p.value
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None else None
 

@@ -10,7 +10,7 @@
 //   (DESIGN.md s.4.1).
 // Also here: Classifier::Preprocess (segnet.cpp:130-167; cv::resize to 480x360, planar float, mean 0) and the label
 // colouring of experiment/segnet.cpp:80-83,131-146 (Pavement->Road remap, cv::resize back to the frame size, cv::LUT).
-#include "ssm_internal.h"
+#include "ssm_ctx.h"              // DevBuf: the per-stream tile-counter buffers
 #include <map>
 #include <mutex>
 #include <utility>
@@ -1012,13 +1012,12 @@ hipError_t k_segnet_prep(const uint8_t* bgr, int n, int sw, int sh, int dw, int 
 }
 // tile counters of conv3x3_dma2_kernel (self-resetting, see there): one small zeroed buffer per (device, stream); launches on a
 // stream are ordered, so they can share it
-static std::mutex g_tq_mu; static std::map<std::pair<int, hipStream_t>, int*> g_tq_bufs;
+static std::mutex g_tq_mu; static std::map<std::pair<int, hipStream_t>, DevBuf<int>> g_tq_bufs;
 void k_segnet_release_stream(hipStream_t s)                       // ssm_destroy: the stream's tile-counter buffer goes with the context
 {
     int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return;
     std::lock_guard<std::mutex> lk(g_tq_mu);
-    auto it = g_tq_bufs.find({dev, s});
-    if (it != g_tq_bufs.end()) { (void)hipFree(it->second); g_tq_bufs.erase(it); }
+    g_tq_bufs.erase({dev, s});
 }
 #define CONV_QUEUE_INTS 1024          // a counter pair per (XCD group, cout tile): 8 x 32 x 2 at most
 static int* conv_tile_queue(hipStream_t s)
@@ -1028,10 +1027,9 @@ static int* conv_tile_queue(hipStream_t s)
     std::lock_guard<std::mutex> lk(mu);
     auto it = bufs.find({dev, s});
     if (it != bufs.end()) return it->second;
-    int* p = nullptr;
-    if (hipMalloc(&p, CONV_QUEUE_INTS * sizeof(int)) != hipSuccess || hipMemset(p, 0, CONV_QUEUE_INTS * sizeof(int)) != hipSuccess) return nullptr;
-    bufs[{dev, s}] = p;
-    return p;
+    DevBuf<int> p;
+    if (p.alloc(nullptr, CONV_QUEUE_INTS) || hipMemset(p, 0, CONV_QUEUE_INTS * sizeof(int)) != hipSuccess) return nullptr;
+    return bufs[{dev, s}] = std::move(p);
 }
 // start of a forward pass: zero the stream's tile counters (they reset themselves at the end of every launch; this only
 // keeps an aborted launch from poisoning the passes after it)

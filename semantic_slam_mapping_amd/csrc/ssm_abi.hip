@@ -109,25 +109,22 @@ void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, std::vector<
 // ---------------------------------------------------------------- helpers
 int ensure_scratch(ssm_ctx* c, size_t bytes)
 {
-    if (bytes <= c->scratch_bytes) return SSM_OK;
-    if (c->d_scratch) { hipStreamSynchronize(c->stream); hipFree(c->d_scratch); c->d_scratch = nullptr; c->scratch_bytes = 0; }
-    uint8_t* p; int r = dalloc(c, &p, bytes); if (r) return r;
-    c->d_scratch = p; c->scratch_bytes = bytes; return SSM_OK;
+    if (bytes <= c->d_scratch.bytes()) return SSM_OK;
+    if (c->d_scratch) hipStreamSynchronize(c->stream);
+    return c->d_scratch.alloc(c, bytes);
 }
 int ensure_pinned(ssm_ctx* c, size_t bytes)
 {
-    if (bytes <= c->pinned_bytes) return SSM_OK;
-    if (c->h_pinned) { hipStreamSynchronize(c->stream); hipHostFree(c->h_pinned); c->h_pinned = nullptr; c->pinned_bytes = 0; }
-    void* p = nullptr;
-    if (hipHostMalloc(&p, bytes, hipHostMallocDefault) != hipSuccess) { c->err = "hipHostMalloc failed"; return SSM_E_HIP; }
-    c->h_pinned = (uint8_t*)p; c->pinned_bytes = bytes; return SSM_OK;
+    if (bytes <= c->h_pinned.bytes()) return SSM_OK;
+    if (c->h_pinned) hipStreamSynchronize(c->stream);
+    if (c->h_pinned.alloc(c, bytes)) FAIL(c, SSM_E_HIP, "hipHostMalloc failed");
+    return SSM_OK;
 }
 int ensure_scratch2(ssm_ctx* c, size_t bytes)
 {
-    if (bytes <= c->scratch2_bytes) return SSM_OK;
-    if (c->d_scratch2) { hipStreamSynchronize(c->stream); hipFree(c->d_scratch2); c->d_scratch2 = nullptr; c->scratch2_bytes = 0; }
-    uint8_t* p; int r = dalloc(c, &p, bytes); if (r) return r;
-    c->d_scratch2 = p; c->scratch2_bytes = bytes; return SSM_OK;
+    if (bytes <= c->d_scratch2.bytes()) return SSM_OK;
+    if (c->d_scratch2) hipStreamSynchronize(c->stream);
+    return c->d_scratch2.alloc(c, bytes);
 }
 void prof_begin(ssm_ctx* c, hipStream_t s, const char* name)
 {
@@ -196,11 +193,6 @@ static int orb_work_alloc(ssm_ctx* c, OrbWork& w)
     DALLOC(c, w.kpaux, (size_t)B * g.sel_total * 2);             // KpAux + KpRec per slot
     return SSM_OK;
 }
-static void orb_work_free(OrbWork& w)
-{
-    void* ptrs[] = { w.pyr, w.blur, w.ncand /* cellmax: inside ncand's allocation */, w.cand, w.nodeof, w.sel, w.nsel, w.kpaux };
-    for (void* p : ptrs) if (p) hipFree(p);
-}
 static int ctx_init(ssm_ctx* c)
 {
     const ssm_config& cfg = c->cfg; const OrbGeom& g = c->g; const int B = c->B, W = g.W, H = g.H;
@@ -211,7 +203,7 @@ static int ctx_init(ssm_ctx* c)
         for (int i = 0; i < 1024; i++) pf[i] = (float)src[i];
         { const char* e = getenv("SSM_BLUR_VARIANT"); c->blur_mfma = !(e && atoi(e) == 0); }
         { std::vector<uint8_t> bt(blur_mfma_table_bytes(c->g)); blur_mfma_tables(c->g, bt.data());
-          uint8_t* dbt; DALLOC(c, dbt, bt.size()); c->d_blur_tab = dbt;
+          DALLOC(c, c->d_blur_tab, bt.size());
           HIPCHK(c, hipMemcpy(c->d_blur_tab, bt.data(), bt.size(), hipMemcpyHostToDevice)); }
         DALLOC(c, c->d_pattern_f, 1024);
         HIPCHK(c, hipMemcpy(c->d_pattern_f, pf, sizeof(pf), hipMemcpyHostToDevice)); }
@@ -231,21 +223,23 @@ static int ctx_init(ssm_ctx* c)
         HIPCHK(c, hipMemcpy(c->d_yofs[l], yo.data(), yo.size() * 4, hipMemcpyHostToDevice));
         HIPCHK(c, hipMemcpy(c->d_ya[l], ya.data(), ya.size() * 2, hipMemcpyHostToDevice));
         if (fits) {
-            uint32_t* d = nullptr; DALLOC(c, d, xg.size());
-            HIPCHK(c, hipMemcpy(d, xg.data(), xg.size() * 4, hipMemcpyHostToDevice));
-            c->d_xgrp[l] = d; streaming[l] = true;
+            DALLOC(c, c->d_xgrp[l], xg.size());
+            HIPCHK(c, hipMemcpy(c->d_xgrp[l], xg.data(), xg.size() * 4, hipMemcpyHostToDevice));
+            streaming[l] = true;
         }
         if (fits && fits8) {
-            uint32_t* d = nullptr; DALLOC(c, d, xg8.size());
-            HIPCHK(c, hipMemcpy(d, xg8.data(), xg8.size() * 4, hipMemcpyHostToDevice));
-            c->d_xgrp8[l] = d; wide_ok[l] = true;
+            DALLOC(c, c->d_xgrp8[l], xg8.size());
+            HIPCHK(c, hipMemcpy(c->d_xgrp8[l], xg8.data(), xg8.size() * 4, hipMemcpyHostToDevice));
+            wide_ok[l] = true;
         }
+        auto& T = c->pyr_tabs;
+        T.xofs[l] = c->d_xofs[l]; T.xa[l] = c->d_xa[l]; T.yofs[l] = c->d_yofs[l]; T.ya[l] = c->d_ya[l]; T.xgrp[l] = c->d_xgrp[l]; T.xgrp8[l] = c->d_xgrp8[l];
     }
     // the fused pyramid's band tables (none where a level needs the general resize kernel)
     for (int k = 0; k < 2; k++) {
-        PyrBandPlan& p = k ? c->pyr_bands1 : c->pyr_bands; std::vector<int32_t> tab;
+        PyrBandPlan& p = k ? c->pyr_bands1 : c->pyr_bands; DevBuf<int32_t>& d = k ? c->d_band_tab1 : c->d_band_tab; std::vector<int32_t> tab;
         if (!pyramid_band_choose(g, yall, streaming, wide_ok, k == 0, tab, p)) continue;
-        int32_t* d = nullptr; DALLOC(c, d, tab.size());
+        DALLOC(c, d, tab.size());
         HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         p.d_tab = d;
     }
@@ -256,7 +250,8 @@ static int ctx_init(ssm_ctx* c)
     DALLOC(c, c->d_total, 2); DALLOC(c, c->d_points, (size_t)B * W * H);
     DALLOC(c, c->d_in_img, (size_t)W * H * 3); DALLOC(c, c->d_in_sem, (size_t)W * H * 3); DALLOC(c, c->d_in_depth, (size_t)W * H); DALLOC(c, c->d_in_pose, 16);
     DALLOC(c, c->map.ovf, VOX_OVF_RECORDS); c->map.ovf_cap = VOX_OVF_RECORDS;
-    { void* hp = nullptr; HIPCHK(c, hipHostMalloc(&hp, 64, hipHostMallocDefault)); c->h_map_snap = (int32_t*)hp; memset(hp, 0, 64); }
+    if (c->h_map_snap.alloc(c, 16)) FAIL(c, SSM_E_HIP, "hipHostMalloc of the map counter ring failed");
+    memset(c->h_map_snap, 0, 64);
     for (int k = 0; k < 2; k++) HIPCHK(c, hipEventCreateWithFlags(&c->map_snap_ev[k], hipEventDisableTiming));
     int r = table_alloc(c, c->stream, c->map, cfg.voxel_capacity_log2); if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -293,50 +288,19 @@ extern "C" int ssm_create(int device, const ssm_config* cfg, ssm_ctx** out)
     *out = c;
     return SSM_OK;
 }
+// What a destructor cannot order: the device is drained before anything goes (no buffer is released while a stream of the context can still touch it), the
+// per-stream SGBM / SegNet caches go before their streams, events and streams are destroyed; `delete c` then releases every buffer the context, its
+// StereoState and its SegNetState own.  The context's device stays current until it returns.
 extern "C" void ssm_destroy(ssm_ctx* c)
 {
     if (!c) return;
     hipSetDevice(c->device);
-    if (c->stream) hipStreamSynchronize(c->stream);
-    for (OrbWork& w : c->work) orb_work_free(w);
-    void* ptrs[] = { c->d_pattern, c->d_status, c->d_mask,
-                     c->d_chunk_cnt, c->d_chunk_off, c->d_total, c->d_points, c->d_in_img, c->d_in_sem, c->d_in_depth, c->d_in_pose,
-                     c->d_scratch, c->d_scratch2, c->d_kps, c->d_desc_all, c->d_nkp_all, c->d_pos3d, c->d_matches, c->d_nmatch, c->d_match_pend, c->d_npoints,
-                     c->d_hist_tmp, c->map.tab, c->tmp.tab, c->d_pattern_f, c->d_exp_q, c->d_exp_t, c->d_knn, c->d_blur_tab, c->d_vmap, c->d_vcat };
-    for (void* p : ptrs) if (p) hipFree(p);
-    if (c->map.ovf) hipFree(c->map.ovf);
-    if (c->d_pnp_xchg) hipFree(c->d_pnp_xchg);
-    if (c->h_map_snap) hipHostFree(c->h_map_snap);
-    for (int k = 0; k < 2; k++) if (c->map_snap_ev[k]) hipEventDestroy(c->map_snap_ev[k]);
-    for (int i = 0; i < 3; i++) if (c->ev_orb[i]) hipEventDestroy(c->ev_orb[i]);
-    if (c->stream4) hipStreamDestroy(c->stream4);
-    if (c->ev_join4) hipEventDestroy(c->ev_join4);
-    for (int l = 0; l < SSM_MAX_LEVELS; l++) { if (c->d_xofs[l]) hipFree(c->d_xofs[l]); if (c->d_xa[l]) hipFree(c->d_xa[l]); if (c->d_yofs[l]) hipFree(c->d_yofs[l]); if (c->d_ya[l]) hipFree(c->d_ya[l]); if (c->d_xgrp[l]) hipFree(c->d_xgrp[l]); if (c->d_xgrp8[l]) hipFree(c->d_xgrp8[l]); }
-    if (c->pyr_bands.d_tab) hipFree(c->pyr_bands.d_tab); if (c->pyr_bands1.d_tab) hipFree(c->pyr_bands1.d_tab);
-    if (c->seg) {
-        SegNetState* g = c->seg;
-        void* sp[] = { g->actA, g->actB, g->labels, g->d_sem_gen, g->pre_xofs, g->pre_yofs, g->post_xofs, g->post_yofs, g->pre_xa, g->pre_ya, g->post_xa, g->post_ya,
-                       g->code[0], g->code[1], g->code[2], g->code[3], g->code[4] };
-        for (void* p : sp) if (p) hipFree(p);
-        for (int l = 0; l < SEG_LAYERS; l++) { if (g->ww[l]) hipFree(g->ww[l]); if (g->w[l]) hipFree(g->w[l]); if (g->scale[l]) hipFree(g->scale[l]); if (g->shift[l]) hipFree(g->shift[l]); }
-        delete g;
-    }
-    if (c->stereo) { stereo_free(c->stereo); delete c->stereo; }
+    hipDeviceSynchronize();
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    if (c->d_comm_counts) hipFree(c->d_comm_counts);
-    for (hipEvent_t e : c->pool) hipEventDestroy(e);
     for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream4}) if (st) { k_sgbm_release_stream(st); k_segnet_release_stream(st); }
-    if (c->stream) hipStreamDestroy(c->stream);
-    if (c->h_pinned) hipHostFree(c->h_pinned);
-    for (auto& sl : c->cloud_slabs) if (sl.d) hipFree(sl.d);
-    if (c->h_ring) hipHostFree(c->h_ring);
-    if (c->d_ring) hipFree(c->d_ring);
-    if (c->stream2) hipStreamDestroy(c->stream2);
-    if (c->stream3) hipStreamDestroy(c->stream3);
-    if (c->ev_join3) hipEventDestroy(c->ev_join3);
-    if (c->map.skip) hipFree(c->map.skip); if (c->d_redo) hipFree(c->d_redo);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
+    for (hipEvent_t e : {c->map_snap_ev[0], c->map_snap_ev[1], c->ev_orb[0], c->ev_orb[1], c->ev_orb[2], c->ev_fork, c->ev_join, c->ev_join3, c->ev_join4}) if (e) hipEventDestroy(e);
+    for (hipEvent_t e : c->pool) hipEventDestroy(e);
+    for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream4}) if (st) hipStreamDestroy(st);
     delete c;
 }
 void ssm_internal_get_config(const ssm_ctx* c, ssm_config* out) { *out = c->cfg; }
@@ -406,11 +370,11 @@ static int make_pyramid(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_
 {
     const OrbGeom& g = c->g;
     if (plan.bands) {
-        prof_begin(c, s, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, w.pyr, plan, c->d_yofs, c->d_ya, c->d_xgrp, c->d_xgrp8, s)); prof_end(c, s);
+        prof_begin(c, s, "pyramid"); HIPCHK(c, k_pyramid_bands(d_img, channels, nb, g, w.pyr, plan, c->pyr_tabs.yofs, c->pyr_tabs.ya, c->pyr_tabs.xgrp, c->pyr_tabs.xgrp8, s)); prof_end(c, s);
         return SSM_OK;
     }
     prof_begin(c, s, "gray");      HIPCHK(c, k_gray(d_img, channels, nb, g, w.pyr, s)); prof_end(c, s);
-    prof_begin(c, s, "pyramid");   HIPCHK(c, k_pyramid(nb, g, w.pyr, c->d_xofs, c->d_xa, c->d_yofs, c->d_ya, c->d_xgrp, s)); prof_end(c, s);
+    prof_begin(c, s, "pyramid");   HIPCHK(c, k_pyramid(nb, g, w.pyr, c->pyr_tabs.xofs, c->pyr_tabs.xa, c->pyr_tabs.yofs, c->pyr_tabs.ya, c->pyr_tabs.xgrp, s)); prof_end(c, s);
     return SSM_OK;
 }
 // run_orb in two halves, because the per-frame call (orb_extract_enqueue) has host work to do between them: everything in front of the one kernel that reads the depth image ...
@@ -519,6 +483,13 @@ extern "C" int ssm_debug_pyramid_plan(const ssm_config* cfg, int bands, int32_t*
     return SSM_OK;
 }
 
+extern "C" void ssm_debug_live_allocations(int* buffers, size_t* device_bytes, size_t* pinned_bytes)
+{
+    if (buffers) *buffers = DevBufLive::buffers.load();
+    if (device_bytes) *device_bytes = DevBufLive::device_bytes.load();
+    if (pinned_bytes) *pinned_bytes = DevBufLive::pinned_bytes.load();
+}
+
 extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes)
 {
     if (!c) return SSM_E_INVAL;
@@ -532,18 +503,18 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
     { const int r = ensure_scratch(c, ib * n); if (r) return r; }
     HIPCHK(c, hipMemcpyAsync(c->d_scratch, img, ib * n, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemsetAsync(c->work[0].pyr, 0xA5, (size_t)n * g.pyr_bytes, c->stream));      // every byte the pyramid owns must be written
-    PyrBandPlan p;
+    PyrBandPlan p; DevBuf<int32_t> own_tab;                             // a plan of this call alone and its band table
     if (bands < 0) p.bands = 0;
     else if (bands == 0) p = n > 1 ? c->pyr_bands : c->pyr_bands1;
     else {
         std::vector<int32_t> yall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
         for (int l = 1; l < g.nlevels; l++) { std::vector<int16_t> ya; resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya); streaming[l] = c->d_xgrp[l] != nullptr; wide_ok[l] = c->d_xgrp8[l] != nullptr; }
         if (!pyramid_band_plan(g, yall, streaming, wide_ok, bands, tab, p)) FAIL(c, SSM_E_INVAL, "no fused pyramid at this band count");
-        int32_t* d = nullptr; DALLOC(c, d, tab.size()); p.d_tab = d;
-        HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        DALLOC(c, own_tab, tab.size()); p.d_tab = own_tab;
+        HIPCHK(c, hipMemcpy(own_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     }
-    int r = make_pyramid(c, c->stream, c->work[0], static_cast<const uint8_t*>(c->d_scratch), channels, n, p);
-    if (bands > 0) { hipStreamSynchronize(c->stream); hipFree(p.d_tab); }
+    int r = make_pyramid(c, c->stream, c->work[0], c->d_scratch, channels, n, p);
+    if (bands > 0) { hipStreamSynchronize(c->stream); own_tab.reset(); }
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(out, c->work[0].pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -572,21 +543,17 @@ int wait_pending(ssm_ctx* c)
 static int ring_take(ssm_ctx* c, size_t hbytes, size_t dbytes, uint8_t** hp, uint8_t** dp)
 {
     hbytes = (hbytes + 255) & ~(size_t)255; dbytes = (dbytes + 255) & ~(size_t)255;
-    if (c->h_ring_off + hbytes > c->ring_bytes || c->d_ring_off + dbytes > c->ring_bytes) {
+    if (c->h_ring_off + hbytes > c->d_ring.bytes() || c->d_ring_off + dbytes > c->d_ring.bytes()) {
         int r = wait_pending(c); if (r) return r;                                // out of room: finish what is in flight (its results are delivered now)
         const size_t need = hbytes > dbytes ? hbytes : dbytes;
-        if (need > c->ring_bytes) {
+        if (need > c->d_ring.bytes()) {
             HIPCHK(c, hipStreamSynchronize(c->stream));
-            if (c->h_ring) hipHostFree(c->h_ring); if (c->d_ring) hipFree(c->d_ring);
-            c->h_ring = nullptr; c->d_ring = nullptr; c->ring_bytes = 0;
+            c->h_ring.reset(); c->d_ring.reset();
             const size_t nb = need * 4 > ((size_t)8 << 20) ? need * 4 : ((size_t)8 << 20);
-            void* hp_ = nullptr;
-            if (hipHostMalloc(&hp_, nb, hipHostMallocDefault) != hipSuccess) FAIL(c, SSM_E_HIP, "hipHostMalloc of the staging ring failed");
-            c->h_ring = (uint8_t*)hp_;
-            if (hipMalloc((void**)&c->d_ring, nb) != hipSuccess) { hipHostFree(c->h_ring); c->h_ring = nullptr; FAIL(c, SSM_E_HIP, "hipMalloc of the result ring failed"); }
-            c->ring_bytes = nb;
+            if (c->h_ring.alloc(c, nb)) FAIL(c, SSM_E_HIP, "hipHostMalloc of the staging ring failed");
+            if (c->d_ring.alloc(c, nb)) { c->h_ring.reset(); FAIL(c, SSM_E_HIP, "hipMalloc of the result ring failed"); }
         }
-        if (c->h_ring_off + hbytes > c->ring_bytes || c->d_ring_off + dbytes > c->ring_bytes) FAIL(c, SSM_E_HIP, "staging ring: the request does not fit after the wait");
+        if (c->h_ring_off + hbytes > c->d_ring.bytes() || c->d_ring_off + dbytes > c->d_ring.bytes()) FAIL(c, SSM_E_HIP, "staging ring: the request does not fit after the wait");
     }
     *hp = c->h_ring + c->h_ring_off; *dp = c->d_ring + c->d_ring_off;
     c->h_ring_off += hbytes; c->d_ring_off += dbytes;
@@ -711,7 +678,7 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
         const size_t rowb = (size_t)capm * 32, expb = (size_t)2 * capT * SSM_MATCH_DESC_BYTES;
         const size_t need = 2 * rowb + 16 + 2 * expb + (size_t)capT * 8 + (size_t)nq * sizeof(ssm_dmatch) + 64;
         int r = ensure_scratch(c, need); if (r) return r;
-        uint8_t* dd = reinterpret_cast<uint8_t*>(c->d_scratch);
+        uint8_t* dd = c->d_scratch;
         int32_t* dnk = reinterpret_cast<int32_t*>(dd + 2 * rowb);
         uint8_t* eq = reinterpret_cast<uint8_t*>(dnk) + 16; uint8_t* et = eq + expb;
         uint2* knn = reinterpret_cast<uint2*>(et + expb);
@@ -738,7 +705,7 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
     }
     const size_t need = (size_t)(nq + nt) * 32 + sizeof(MatchPair) + (size_t)nq * (16 + 16) + 64;
     int r = ensure_scratch(c, need); if (r) return r;
-    uint8_t* dd = reinterpret_cast<uint8_t*>(c->d_scratch);
+    uint8_t* dd = c->d_scratch;
     ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(dd + (size_t)(nq + nt) * 32);
     int32_t* di = reinterpret_cast<int32_t*>(dm + nq); int32_t* ds = di + 2 * (size_t)nq;
     MatchPair* dp = reinterpret_cast<MatchPair*>(ds + 2 * (size_t)nq); int32_t* dn = reinterpret_cast<int32_t*>(dp + 1);
@@ -893,28 +860,22 @@ static int ensure_seq(ssm_ctx* c, int n)
     if (n <= c->seq_cap) return SSM_OK;
     const OrbGeom& g = c->g; const int R = c->R;
     // keep the history rows across the re-allocation
-    uint8_t* old_desc = c->d_desc_all; int32_t* old_nkp = c->d_nkp_all; const int old_prev = c->prev_n;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    void* olds[] = { c->d_kps, c->d_pos3d, c->d_matches, c->d_nmatch, c->d_npoints, c->d_match_pend, c->d_exp_q, c->d_exp_t, c->d_knn };
-    for (void* p : olds) if (p) hipFree(p);
-    c->d_kps = nullptr; c->d_pos3d = nullptr; c->d_matches = nullptr; c->d_nmatch = nullptr; c->d_npoints = nullptr; c->d_match_pend = nullptr;
-    c->d_exp_q = nullptr; c->d_exp_t = nullptr; c->d_knn = nullptr;
+    c->seq_cap = 0;                                                 // (a failure below leaves some of the outputs empty: the next call allocates again)
     c->capT = (g.cap + 31) & ~31;
     if (c->match_mfma) {       // expanded rows are rebuilt from the bit descriptors at the start of every call (history) and after every ORB sub-batch
         DALLOC(c, c->d_exp_q, (size_t)(n + R) * c->capT * SSM_MATCH_DESC_BYTES); DALLOC(c, c->d_exp_t, (size_t)(n + R) * c->capT * SSM_MATCH_DESC_BYTES); DALLOC(c, c->d_knn, (size_t)n * R * c->capT * 8);
     }
     DALLOC(c, c->d_kps, (size_t)n * g.cap); DALLOC(c, c->d_pos3d, (size_t)n * g.cap * 3);
     DALLOC(c, c->d_matches, (size_t)n * R * g.cap); DALLOC(c, c->d_nmatch, (size_t)n * R); DALLOC(c, c->d_match_pend, (size_t)n * R); DALLOC(c, c->d_npoints, (size_t)n);
-    uint8_t* nd; int32_t* nn;
+    DevBuf<uint8_t> nd; DevBuf<int32_t> nn;                         // the context takes them once the history is across
     DALLOC(c, nd, (size_t)(n + R) * g.cap * 32); DALLOC(c, nn, (size_t)(n + R));
     if (!c->d_hist_tmp) DALLOC(c, c->d_hist_tmp, (size_t)R * g.cap * 32 + (size_t)R * 4);
-    if (old_desc && old_prev >= 0) {
-        HIPCHK(c, hipMemcpy(nd, old_desc, (size_t)(old_prev + R) * g.cap * 32, hipMemcpyDeviceToDevice));
-        HIPCHK(c, hipMemcpy(nn, old_nkp, (size_t)(old_prev + R) * 4, hipMemcpyDeviceToDevice));
+    if (c->d_desc_all && c->prev_n >= 0) {
+        HIPCHK(c, hipMemcpy(nd, c->d_desc_all, (size_t)(c->prev_n + R) * g.cap * 32, hipMemcpyDeviceToDevice));
+        HIPCHK(c, hipMemcpy(nn, c->d_nkp_all, (size_t)(c->prev_n + R) * 4, hipMemcpyDeviceToDevice));
     }
-    if (old_desc) hipFree(old_desc);
-    if (old_nkp) hipFree(old_nkp);
-    c->d_desc_all = nd; c->d_nkp_all = nn; c->seq_cap = n;
+    c->d_desc_all = std::move(nd); c->d_nkp_all = std::move(nn); c->seq_cap = n;
     return SSM_OK;
 }
 extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out_dev* out)
@@ -1059,7 +1020,9 @@ extern "C" int ssm_dev_alloc(ssm_ctx* c, size_t bytes, void** out)
 {
     if (!c || !out) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    uint8_t* p; int r = dalloc(c, &p, bytes); if (r) return r;
+    void* p = nullptr; if (bytes == 0) bytes = 1;
+    const hipError_t e = hipMalloc(&p, bytes);
+    if (e != hipSuccess) FAIL(c, SSM_E_NOMEM, std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
     *out = p; return SSM_OK;
 }
 extern "C" int ssm_dev_free(ssm_ctx* c, void* p)

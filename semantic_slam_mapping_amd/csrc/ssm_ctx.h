@@ -8,17 +8,48 @@
 #include <cfloat>
 #include <cstring>
 #include <cstdlib>
+#include <atomic>
+#include <memory>
 #include <mutex>
+#include <type_traits>
+#include <utility>
 #include <functional>
 #include <string>
 #include <vector>
 #define SSM_HIDDEN __attribute__((visibility("hidden")))
 
+// Owner of ONE device allocation (Pinned: page-locked host memory) of a context, a StereoState, a SegNetState, an OrbWork or an ssm_tracker.  Move-only;
+// alloc releases what the buffer held first, reset() and the destructor release it.  It converts to T*, so launches, copies and pointer arithmetic read
+// as with a raw pointer.  Nothing here waits for the device: whoever releases a buffer that queued work may still touch synchronises first.
+struct DevBufLive { static inline std::atomic<int> buffers{0}; static inline std::atomic<size_t> device_bytes{0}, pinned_bytes{0}; };      // process-wide: ssm_debug_live_allocations
+template <class T, bool Pinned = false> class DevBuf {
+    T* p = nullptr; size_t nbytes = 0;
+public:
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), nbytes(std::exchange(o.nbytes, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept { if (this != &o) { reset(); p = std::exchange(o.p, nullptr); nbytes = std::exchange(o.nbytes, 0); } return *this; }
+    ~DevBuf() { reset(); }
+    operator T*() const { return p; }
+    template <class U> U* as() const { return reinterpret_cast<U*>(p); }
+    size_t bytes() const { return nbytes; }                     // what alloc asked for; 0: empty
+    void reset()
+    {
+        if (!p) return;
+        if (Pinned) (void)hipHostFree(p); else (void)hipFree(p);
+        DevBufLive::buffers--; (Pinned ? DevBufLive::pinned_bytes : DevBufLive::device_bytes) -= nbytes;
+        p = nullptr; nbytes = 0;
+    }
+    // SSM_E_NOMEM + the message in c->err (c may be null: no message) when the allocation fails; the buffer is empty then
+    int alloc_bytes(ssm_ctx* c, size_t bytes);
+    int alloc(ssm_ctx* c, size_t count) { return alloc_bytes(c, (count ? count : 1) * sizeof(std::conditional_t<std::is_void<T>::value, char, T>)); }
+};
+template <class T> using PinBuf = DevBuf<T, true>;
 
 struct VoxTable {           // tab[slots] | occ[slots] | counter block (32 bytes: count, flags, overflow records, overflow capacity, overflow list address)
-    ssm_voxel* tab = nullptr; uint32_t* occ = nullptr; int32_t* counters = nullptr; int cap_log2 = 0;
-    ssm_voxel* ovf = nullptr; int ovf_cap = 0;       // the overflow list of the context map (kernels_map.hip vox_overflow_slot); the temporary tables have none
-    int32_t* skip = nullptr;                         // the context map's skip list (kernels_map.hip map_stream2_kernel): blocks of the fused map stage that found the overflow list beyond its high-water mark
+    DevBuf<ssm_voxel> tab; uint32_t* occ = nullptr; int32_t* counters = nullptr; int cap_log2 = 0;        // occ, counters: inside tab's allocation
+    DevBuf<ssm_voxel> ovf; int ovf_cap = 0;       // the overflow list of the context map (kernels_map.hip vox_overflow_slot); the temporary tables have none
+    DevBuf<int32_t> skip;                            // the context map's skip list (kernels_map.hip map_stream2_kernel): blocks of the fused map stage that found the overflow list beyond its high-water mark
     size_t bytes() const { const size_t s = (size_t)1 << cap_log2; return s * sizeof(ssm_voxel) + s * 4 + 32; }
 };
 static const int VOX_OVF_RECORDS = 1 << 18;          // 29 MB per context; a context that runs the fused map stage (ssm_seq_process) trades it for the large list of map_ensure_stream_list
@@ -44,41 +75,42 @@ static const SegLayerDef k_seg_layers[SEG_LAYERS] = {
 #define SG_FAIL_WORDS 256
 struct StereoState {        // workspace of the stereo path (quad matcher, SGBM depth, stereo VO) for one image geometry, B frames per launch
     int w = 0, h = 0, maxc = 0, B = 0;
-    QuadBatch qb{};                          // image slots: 2 sides x (B + 1) pyramids + Scharr derivatives
-    uint8_t* pyr = nullptr; int16_t* der = nullptr;
-    GfttWork gw{};                           // goodFeaturesToTrack workspace (kernels_quad.hip)
-    int keycap = 0; int *ncorner = nullptr, *has_prev = nullptr;
-    int* sg_fail = nullptr;                  // SG_FAIL_WORDS words: word (sub-batch index mod SG_FAIL_WORDS) is set by that sub-batch's sgbm_sweep when a strip hand-off times out (kernels_sgbm.hip)
+    QuadBatch qb{};                          // image slots: 2 sides x (B + 1) pyramids + Scharr derivatives (the kernels' view of pyr, der: stereo_init)
+    DevBuf<uint8_t> pyr; DevBuf<int16_t> der;
+    GfttWork gw{};                           // goodFeaturesToTrack workspace (kernels_quad.hip): the kernels' view of the buffers below (stereo_init)
+    DevBuf<float> g_eig; DevBuf<int> g_cand_at, g_maxord, g_count, g_nkept; DevBuf<uint32_t> g_cand_bits, g_deps; DevBuf<unsigned long long> g_keys, g_kept; DevBuf<uint8_t> g_depn, g_state;
+    int keycap = 0; DevBuf<int> ncorner, has_prev;
+    DevBuf<int> sg_fail;                     // SG_FAIL_WORDS words: word (sub-batch index mod SG_FAIL_WORDS) is set by that sub-batch's sgbm_sweep when a strip hand-off times out (kernels_sgbm.hip)
     // the depth stage of the most recent sequence call, kept so that sub-batches whose sweep timed out can be repeated in form 1 once the call is known to have
     // failed (ssm_sync / check_device_flags: the caller's input buffers must stay untouched until then, as for any asynchronous call)
     struct { bool valid = false; ssm_stereo_frames_dev in{}; int B = 0; } sg_pending;
-    float* pts = nullptr;                    // [5][B][maxc] (x, y): lc (GFTT corners), rc, rp, lp, lp_direct
-    uint8_t* status = nullptr; float* err = nullptr;        // ssm_lk_track outputs
-    double* tr_all = nullptr; int32_t *vcount = nullptr, *rand_off = nullptr, *consumed = nullptr; int vo_iters = 0;   // stereo VO scratch (B x iters hypotheses)
-    void* sg_wsN[3] = {nullptr, nullptr, nullptr}; size_t sg_ws_bytesN[3] = {0, 0, 0}; int* dminN[3] = {nullptr, nullptr, nullptr};   // SGBM workspaces (sized for the frames per launch actually used): successive sub-batches of a sequence run SGBM on up to three streams, one workspace each
+    DevBuf<float> pts;                       // [5][B][maxc] (x, y): lc (GFTT corners), rc, rp, lp, lp_direct
+    DevBuf<uint8_t> status; DevBuf<float> err;              // ssm_lk_track outputs
+    DevBuf<double> tr_all; DevBuf<int32_t> vcount, rand_off, consumed; int vo_iters = 0;   // stereo VO scratch (B x iters hypotheses)
+    DevBuf<void> sg_wsN[3]; DevBuf<int> dminN[3];   // SGBM workspaces (sized for the frames per launch actually used): successive sub-batches of a sequence run SGBM on up to three streams, one workspace each
     // sequence outputs (seq_cap frames)
     int seq_cap = 0;
-    ssm_pmatch* quad = nullptr; int32_t* nquad = nullptr; float* corners = nullptr; int32_t* ncorners = nullptr; int16_t* disp = nullptr; uint16_t* depth = nullptr;
-    double* tr = nullptr; int32_t *inliers = nullptr, *vo_result = nullptr;
+    DevBuf<ssm_pmatch> quad; DevBuf<int32_t> nquad; DevBuf<float> corners; DevBuf<int32_t> ncorners; DevBuf<int16_t> disp; DevBuf<uint16_t> depth;
+    DevBuf<double> tr; DevBuf<int32_t> inliers, vo_result;
     bool have_prev = false;                  // slot 0 holds the last frame of the previous sequence call
-    uint8_t* in_stage = nullptr; size_t in_stage_bytes = 0;     // device staging of the per-pair host-pointer entry points
+    DevBuf<uint8_t> in_stage;                // device staging of the per-pair host-pointer entry points
 };
 struct SegNetState {
     bool set[SEG_LAYERS] = {};
-    void* w[SEG_LAYERS] = {}; float* scale[SEG_LAYERS] = {}; float* shift[SEG_LAYERS] = {};
-    void* ww[SEG_LAYERS] = {};           // the layer's weights in Winograd F(2, 3) form (kernels_segnet.hip conv3x3_wino_kernel), or null: the direct kernel only
+    DevBuf<void> w[SEG_LAYERS]; DevBuf<float> scale[SEG_LAYERS], shift[SEG_LAYERS];
+    DevBuf<void> ww[SEG_LAYERS];         // the layer's weights in Winograd F(2, 3) form (kernels_segnet.hip conv3x3_wino_kernel), or null: the direct kernel only
     int cinp[SEG_LAYERS], coutp[SEG_LAYERS], coutstore[SEG_LAYERS];
     int batch = 0;
-    void *actA = nullptr, *actB = nullptr, *last_logits = nullptr; uint8_t* code[5] = {}; uint8_t* labels = nullptr;
-    int32_t *pre_xofs = nullptr, *pre_yofs = nullptr, *post_xofs = nullptr, *post_yofs = nullptr;
-    int16_t *pre_xa = nullptr, *pre_ya = nullptr, *post_xa = nullptr, *post_ya = nullptr;
-    uint8_t* d_sem_gen = nullptr;       // generated colour labels for the sequence path (max_batch frames)
+    DevBuf<void> actA, actB; void* last_logits = nullptr /* actA or actB */; DevBuf<uint8_t> code[5], labels;
+    DevBuf<int32_t> pre_xofs, pre_yofs, post_xofs, post_yofs;
+    DevBuf<int16_t> pre_xa, pre_ya, post_xa, post_ya;
+    DevBuf<uint8_t> d_sem_gen;          // generated colour labels for the sequence path (max_batch frames)
 };
 
 // workspace of the ORB front end for B frames (ssm_abi.hip orb_work_alloc): what pyramid .. describe write and read between them
 struct OrbWork {
-    uint8_t *pyr = nullptr, *blur = nullptr; int32_t *ncand = nullptr, *cellmax = nullptr /* inside ncand's allocation */; cand_t* cand = nullptr; uint16_t* nodeof = nullptr;
-    uint32_t* sel = nullptr; int32_t* nsel = nullptr; uint4* kpaux = nullptr;
+    DevBuf<uint8_t> pyr, blur; DevBuf<int32_t> ncand; int32_t* cellmax = nullptr /* inside ncand's allocation */; DevBuf<cand_t> cand; DevBuf<uint16_t> nodeof;
+    DevBuf<uint32_t> sel; DevBuf<int32_t> nsel; DevBuf<uint4> kpaux;
 };
 
 struct ssm_ctx {
@@ -94,63 +126,65 @@ struct ssm_ctx {
     std::string err;
     int B = 1, R = 5;
     // constant tables
-    void* d_blur_tab = nullptr; bool blur_mfma = true;                 // blur_mfma_kernel's coefficient fragments (kernels_orb.hip); SSM_BLUR_VARIANT=0: the VALU kernel
-    int8_t* d_pattern = nullptr; float* d_pattern_f = nullptr;      // the BRIEF table as given, and as floats for brief_kernel
-    int32_t* d_xofs[SSM_MAX_LEVELS] = {}; int16_t* d_xa[SSM_MAX_LEVELS] = {};
-    void* d_xgrp[SSM_MAX_LEVELS] = {};       // resize4_kernel's per-group constants (null: the level uses the general resize kernel)
-    void* d_xgrp8[SSM_MAX_LEVELS] = {};      // the fused pyramid's 8-pixel groups (null: the level's groups do not fit that layout; it keeps the 4-pixel item)
+    DevBuf<uint8_t> d_blur_tab; bool blur_mfma = true;                // blur_mfma_kernel's coefficient fragments (kernels_orb.hip); SSM_BLUR_VARIANT=0: the VALU kernel
+    DevBuf<int8_t> d_pattern; DevBuf<float> d_pattern_f;            // the BRIEF table as given, and as floats for brief_kernel
+    DevBuf<int32_t> d_xofs[SSM_MAX_LEVELS], d_yofs[SSM_MAX_LEVELS]; DevBuf<int16_t> d_xa[SSM_MAX_LEVELS], d_ya[SSM_MAX_LEVELS];
+    DevBuf<uint32_t> d_xgrp[SSM_MAX_LEVELS];     // resize4_kernel's per-group constants (null: the level uses the general resize kernel)
+    DevBuf<uint32_t> d_xgrp8[SSM_MAX_LEVELS];    // the fused pyramid's 8-pixel groups (null: the level's groups do not fit that layout; it keeps the 4-pixel item)
+    // the per-level tables above as the plain pointer arrays the pyramid launchers take (filled where the tables are made: ctx_init)
+    struct { const int32_t *xofs[SSM_MAX_LEVELS], *yofs[SSM_MAX_LEVELS]; const int16_t *xa[SSM_MAX_LEVELS], *ya[SSM_MAX_LEVELS]; const void *xgrp[SSM_MAX_LEVELS], *xgrp8[SSM_MAX_LEVELS]; } pyr_tabs = {};
     PyrBandPlan pyr_bands, pyr_bands1;       // resize4_kernel_bands for batches / for the per-frame call (bands == 0: gray_kernel + k_pyramid)
-    int32_t* d_yofs[SSM_MAX_LEVELS] = {}; int16_t* d_ya[SSM_MAX_LEVELS] = {};
+    DevBuf<int32_t> d_band_tab, d_band_tab1; // their band tables (PyrBandPlan::d_tab points here)
     // ORB workspaces (B frames each): work[0] serves every entry point that runs on `stream`; ssm_seq_process runs successive sub-batches as up to three
     // ORB -> match chains -- chain k on its own stream (stream, stream2, stream4) with work[k]; work[1], work[2] are allocated at first use
     OrbWork work[3];
-    int32_t* d_status = nullptr;        // the ORB scratch-overflow word: one, shared by all chains
+    DevBuf<int32_t> d_status;           // the ORB scratch-overflow word: one, shared by all chains
     hipEvent_t ev_orb[3] = {nullptr, nullptr, nullptr};
     hipStream_t stream4 = nullptr; hipEvent_t ev_join4 = nullptr;      // the third chain, used when a call has more than two sub-batches
-    uint8_t* d_mask = nullptr; int32_t* d_chunk_cnt = nullptr; int64_t* d_chunk_off = nullptr; int64_t* d_total = nullptr;
-    ssm_point* d_points = nullptr;
-    ssm_point* d_vmap = nullptr; int vmap_n = 0; size_t vmap_cap = 0;      // Mapper::viewer's filtered map, device-resident (ssm_viewer_map_update)
-    ssm_point* d_vcat = nullptr; size_t vcat_cap = 0;                        // its concatenation buffer
-    struct CloudSlab { ssm_point* d = nullptr; size_t cap = 0, used = 0; int live = 0; };
+    DevBuf<uint8_t> d_mask; DevBuf<int32_t> d_chunk_cnt; DevBuf<int64_t> d_chunk_off, d_total;
+    DevBuf<ssm_point> d_points;
+    DevBuf<ssm_point> d_vmap; int vmap_n = 0;    // Mapper::viewer's filtered map, device-resident (ssm_viewer_map_update)
+    DevBuf<ssm_point> d_vcat;                    // its concatenation buffer
+    struct CloudSlab { DevBuf<ssm_point> d; size_t cap = 0, used = 0; int live = 0; };
     bool viewer_fail_next = false;                                           // tests: the next ssm_viewer_map_update fails (ssm_viewer_map_release)
     std::vector<CloudSlab> cloud_slabs;                                      // key-frame clouds (ssm_backproject_dev) are carved from slabs: no hipMalloc per cloud
     // staging for the host-pointer entry points (one frame) + generic scratch
-    uint8_t *d_in_img = nullptr, *d_in_sem = nullptr; uint16_t* d_in_depth = nullptr; double* d_in_pose = nullptr;
-    void* d_scratch = nullptr; size_t scratch_bytes = 0;
-    unsigned long long* d_pnp_xchg = nullptr; unsigned pnp_epoch = 0;    // ssm_pnp_solve's cluster: the exchange ring (persistent) and the launch number its pass tags start from
+    DevBuf<uint8_t> d_in_img, d_in_sem; DevBuf<uint16_t> d_in_depth; DevBuf<double> d_in_pose;
+    DevBuf<uint8_t> d_scratch;
+    DevBuf<unsigned long long> d_pnp_xchg; unsigned pnp_epoch = 0;   // ssm_pnp_solve's cluster: the exchange ring (persistent) and the launch number its pass tags start from
     bool pnp_solve_one_block = false;                        // ssm_pnp_solve: a cluster of eight blocks timed out once -> one block per solve from then on
-    void* d_scratch2 = nullptr; size_t scratch2_bytes = 0;
+    DevBuf<uint8_t> d_scratch2;
     // the stream that holds the newest work on the context map when that is a side stream of ssm_seq_process (joined into `stream` by an event, so everything queued
     // on `stream` afterwards is ordered behind it): ssm_map_size / ssm_map_export_table_dev read the map there and wait for THAT stream only -- the ORB -> match chain of
     // the call's last sub-batch keeps running.  nullptr: the map's newest work is on `stream`.
     hipStream_t map_tail = nullptr;
     // sequence outputs
     int seq_cap = 0, prev_n = -1;
-    ssm_keypoint* d_kps = nullptr; uint8_t* d_desc_all = nullptr; int32_t* d_nkp_all = nullptr; float* d_pos3d = nullptr;
-    ssm_dmatch* d_matches = nullptr; int32_t* d_nmatch = nullptr; int32_t* d_match_pend = nullptr; int32_t* d_npoints = nullptr; uint8_t* d_hist_tmp = nullptr;
-    uint8_t* d_exp_q = nullptr; uint8_t* d_exp_t = nullptr; uint8_t* d_knn = nullptr; int capT = 0; bool match_mfma = true;   // the matcher's expanded descriptor rows (kernels_match.hip)
+    DevBuf<ssm_keypoint> d_kps; DevBuf<uint8_t> d_desc_all; DevBuf<int32_t> d_nkp_all; DevBuf<float> d_pos3d;
+    DevBuf<ssm_dmatch> d_matches; DevBuf<int32_t> d_nmatch, d_match_pend, d_npoints; DevBuf<uint8_t> d_hist_tmp;
+    DevBuf<uint8_t> d_exp_q, d_exp_t, d_knn; int capT = 0; bool match_mfma = true;   // the matcher's expanded descriptor rows (kernels_match.hip)
     // voxel tables
-    MapLaunch map_ring[8] = {}; unsigned map_ring_next = 0; int32_t* d_redo = nullptr; std::vector<int32_t> map_skipped;    // launches that may still have skipped blocks; ids to run again (host)
+    MapLaunch map_ring[8] = {}; unsigned map_ring_next = 0; DevBuf<int32_t> d_redo; std::vector<int32_t> map_skipped;    // launches that may still have skipped blocks; ids to run again (host)
     std::vector<hipStream_t> map_launch_streams; long map_redone = 0;      // streams fused launches were queued on; blocks run again so far
     bool map_unexamined = false;                            // a fused map launch was queued since the counters were last read on a drained stream
     VoxTable map, tmp; bool map_full_reported = false;   // table-full already reported by check_device_flags (reset by ssm_map_clear)
     // the context map grows (map_settle); between the map launches of ssm_seq_process its counters come back through a two-slot ring of asynchronous copies
-    int vox_max_log2 = 28; int32_t* h_map_snap = nullptr; hipEvent_t map_snap_ev[2] = {nullptr, nullptr}; uint64_t map_launches = 0; int map_grown = 0;
+    int vox_max_log2 = 28; PinBuf<int32_t> h_map_snap; hipEvent_t map_snap_ev[2] = {nullptr, nullptr}; uint64_t map_launches = 0; int map_grown = 0;
     double map_vpf = -1.0;                                  // voxels (+ overflow records) per fused frame, the largest rate seen on this context; < 0: none yet
     int64_t map_frames = 0, map_snap_frames[2] = {0, 0}, map_known_total = 0, map_known_frames = 0;     // frames fused since the last clear; at the ring's snapshots; the last count the host has seen and when
     // multi-GPU: the communicator of ssm_comm_init_rank (one rank per context / GPU) and the gathered counts
-    ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1; int32_t* d_comm_counts = nullptr; int comm_counts_cap = 0;
+    ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1; DevBuf<int32_t> d_comm_counts; int comm_counts_cap = 0;
     // SegNet
-    struct SegNetState* seg = nullptr;
+    std::unique_ptr<SegNetState> seg;
     // quad matcher
-    struct StereoState* stereo = nullptr; int stereo_B = 16; int stereo_sgbm_streams = 2;      // ssm_config.sgbm_streams 
+    std::unique_ptr<StereoState> stereo; int stereo_B = 16; int stereo_sgbm_streams = 2;      // ssm_config.sgbm_streams 
     int sgbm_form_cfg = 0; long sgbm_fallbacks = 0;                                              // ssm_config.sgbm_form; sub-batches repeated in form 1 after a sweep time-out
     // profiling
     bool profiling = false;
-    uint8_t* h_pinned = nullptr; size_t pinned_bytes = 0;   // host staging for the image-sized host-pointer calls (pageable hipMemcpy is ~1 GB/s)
+    PinBuf<uint8_t> h_pinned;          // host staging for the image-sized host-pointer calls (pageable hipMemcpy is ~1 GB/s)
     // the per-frame entry points (ssm_orb_extract[_async], ssm_match[_async]): a ring of pinned host memory (inputs staged, results landed) and a ring of
     // device memory (result blocks), bump-allocated per call and released by ssm_wait; `pending` = what ssm_wait still has to hand to the callers
-    uint8_t* h_ring = nullptr; uint8_t* d_ring = nullptr; size_t ring_bytes = 0, h_ring_off = 0, d_ring_off = 0;
+    PinBuf<uint8_t> h_ring; DevBuf<uint8_t> d_ring /* both of d_ring.bytes() */; size_t h_ring_off = 0, d_ring_off = 0;
     std::vector<std::function<int(ssm_ctx*)>> pending;
     bool serialize = false;             // profiling mode 2: keep the side work of ssm_seq_process on the context stream (clean per-stage times)
     std::vector<StageRec> recs; std::vector<hipEvent_t> pool; size_t pool_used = 0;
@@ -162,14 +196,16 @@ struct ssm_ctx {
 
 inline int cv_round_f(float v) { return (int)lrint((double)v); }
 
-#define DALLOC(ctx, p, n) do { int r__ = dalloc(ctx, &(p), (size_t)(n)); if (r__) return r__; } while (0)
+#define DALLOC(ctx, buf, n) do { int r__ = (buf).alloc(ctx, (size_t)(n)); if (r__) return r__; } while (0)
 #define NCCLCHK(ctx, expr) do { ncclResult_t e__ = (expr); if (e__ != ncclSuccess) { (ctx)->err = std::string(#expr) + ": " + ncclGetErrorString(e__); return SSM_E_COMM; } } while (0)
-template <class T> inline int dalloc(ssm_ctx* c, T** p, size_t count)
+template <class T, bool Pinned> int DevBuf<T, Pinned>::alloc_bytes(ssm_ctx* c, size_t bytes)
 {
-    *p = nullptr;
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-    if (e != hipSuccess) { c->err = std::string("hipMalloc(") + std::to_string(count * sizeof(T)) + "): " + hipGetErrorString(e); return SSM_E_NOMEM; }
+    reset();
+    void* q = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
+    if (e != hipSuccess) { if (c) c->err = std::string(Pinned ? "hipHostMalloc(" : "hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e); return SSM_E_NOMEM; }
+    p = static_cast<T*>(q); nbytes = bytes;
+    DevBufLive::buffers++; (Pinned ? DevBufLive::pinned_bytes : DevBufLive::device_bytes) += bytes;
     return SSM_OK;
 }
 // ssm_abi.hip
@@ -185,7 +221,7 @@ SSM_HIDDEN int wait_pending(ssm_ctx* c);
 SSM_HIDDEN bool host_is_pinned(const void* p);             // page-locked host memory (ssm_host_alloc, hipHostRegister)?
 SSM_HIDDEN int ensure_side_streams(ssm_ctx* c);
 // ssm_map.hip
-SSM_HIDDEN int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2);
+SSM_HIDDEN int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2, const VoxTable* lists = nullptr);      // lists: the table whose overflow list the counter block names (default: t's own)
 SSM_HIDDEN int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out = nullptr);
 SSM_HIDDEN int map_before_launch(ssm_ctx* c, hipStream_t s, int remaining, int* nq);
 SSM_HIDDEN int map_after_launch(ssm_ctx* c, hipStream_t s, int frames, bool inputs_volatile);
@@ -194,5 +230,4 @@ SSM_HIDDEN int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L);  
 SSM_HIDDEN int seg_init(ssm_ctx* c);
 SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
 // ssm_stereo_abi.hip
-SSM_HIDDEN void stereo_free(StereoState* q);
 SSM_HIDDEN int sgbm_recover(ssm_ctx* c);

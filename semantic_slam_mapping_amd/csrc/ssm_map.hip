@@ -3,14 +3,15 @@
 #include "ssm_ctx.h"
 #include <algorithm>
 
-int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2)
+int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2, const VoxTable* lists)
 {
+    if (!lists) lists = &t;
     t.cap_log2 = cap_log2;
-    uint8_t* p; int r = dalloc(c, &p, t.bytes()); if (r) return r;
+    { const int r = t.tab.alloc_bytes(c, t.bytes()); if (r) return r; }
     const size_t slots = (size_t)1 << cap_log2;
-    t.tab = reinterpret_cast<ssm_voxel*>(p); t.occ = reinterpret_cast<uint32_t*>(t.tab + slots); t.counters = reinterpret_cast<int32_t*>(t.occ + slots);
+    t.occ = reinterpret_cast<uint32_t*>(t.tab + slots); t.counters = reinterpret_cast<int32_t*>(t.occ + slots);
     HIPCHK(c, k_voxel_clear(t.tab, -cap_log2, t.counters, s));
-    struct { int32_t cap, pad; ssm_voxel* buf; } tail = { t.ovf ? t.ovf_cap : 0, 0, t.ovf };      // counters[3], counters[4..5]
+    struct { int32_t cap, pad; ssm_voxel* buf; } tail = { lists->ovf ? lists->ovf_cap : 0, 0, lists->ovf };      // counters[3], counters[4..5]
     static_assert(sizeof(tail) == 16, "counter block tail");
     int32_t head[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(t.counters, head, 12, hipMemcpyHostToDevice, s));
@@ -42,10 +43,9 @@ static int map_ensure_stream_list(ssm_ctx* c, hipStream_t s)
     int r = map_settle(c, s, 0); if (r) return r;
     if (!t.skip) { DALLOC(c, t.skip, (size_t)k_map_fuse_skip_cap()); DALLOC(c, c->d_redo, (size_t)k_map_fuse_skip_cap()); }
     if (t.ovf_cap < map_stream_list_records()) {
-        ssm_voxel* big = nullptr;
+        DevBuf<ssm_voxel> big;
         DALLOC(c, big, (size_t)map_stream_list_records());
-        if (t.ovf) hipFree(t.ovf);
-        t.ovf = big; t.ovf_cap = (int)map_stream_list_records();
+        t.ovf = std::move(big); t.ovf_cap = (int)map_stream_list_records();
         struct { int32_t cap, pad; ssm_voxel* buf; } tail = { t.ovf_cap, 0, t.ovf };
         HIPCHK(c, hipMemcpyAsync(t.counters + 3, &tail.cap, 4, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(t.counters + 4, &tail.buf, 8, hipMemcpyHostToDevice, s));
@@ -133,16 +133,16 @@ int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out
         if (grow) {
             { const int r = map_drain_other_streams(c, s); if (r) return r; }      // nobody may still be inserting into the table that is replaced
             int L = t.cap_log2; while (L < c->vox_max_log2 && 4 * (n + m + reserve) > ((int64_t)1 << L)) L++;
-            VoxTable nt; nt.ovf = t.ovf; nt.ovf_cap = t.ovf_cap; nt.skip = t.skip;
-            { const int r = table_alloc(c, s, nt, L); if (r) return r; }
+            VoxTable nt;                                          // the larger table only: the lists stay with t
+            { const int r = table_alloc(c, s, nt, L, &t); if (r) return r; }
             // the flags travel with the map; the new counter block goes on counting overflow records where the old one stopped (the records [lo, hi) are still to
             // merge, and the re-hash itself appends behind them should it need the list)
             const int32_t carry[2] = { cnt[1], cnt[2] < t.ovf_cap ? cnt[2] : t.ovf_cap };
             HIPCHK(c, hipMemcpyAsync(nt.counters + 1, carry, 8, hipMemcpyHostToDevice, s));
             HIPCHK(c, k_voxel_rehash(t.tab, t.cap_log2, nt.tab, nt.cap_log2, nt.counters, s));
             HIPCHK(c, hipStreamSynchronize(s));
-            hipFree(t.tab);
-            t = nt; c->map_grown++;
+            t.tab = std::move(nt.tab); t.occ = nt.occ; t.counters = nt.counters; t.cap_log2 = nt.cap_log2;      // (releases the old table)
+            c->map_grown++;
             continue;                                             // (count again: the re-hash itself may have used the list)
         }
         HIPCHK(c, k_voxel_merge(t.ovf + lo, (int)m, t.tab, t.cap_log2, t.counters, s));
@@ -249,7 +249,7 @@ static int table_sorted(ssm_ctx* c, VoxTable& t, int* n_out, ssm_voxel** compact
     HIPCHK(c, voxel_sort_pairs(nullptr, &tmp_bytes, nullptr, n, nullptr, nullptr, nullptr, nullptr, st));
     const size_t a = ((size_t)n * sizeof(ssm_voxel) + 255) & ~(size_t)255, kb = ((size_t)n * 8 + 255) & ~(size_t)255, ib = ((size_t)n * 4 + 255) & ~(size_t)255;
     r = ensure_scratch2(c, a + 2 * kb + 2 * ib + tmp_bytes + 512); if (r) return r;
-    uint8_t* p = reinterpret_cast<uint8_t*>(c->d_scratch2);
+    uint8_t* p = c->d_scratch2;
     ssm_voxel* comp = reinterpret_cast<ssm_voxel*>(p); p += a;
     uint64_t* ka = reinterpret_cast<uint64_t*>(p); p += kb; uint64_t* kbuf = reinterpret_cast<uint64_t*>(p); p += kb;
     uint32_t* ia = reinterpret_cast<uint32_t*>(p); p += ib; uint32_t* ibuf = reinterpret_cast<uint32_t*>(p); p += ib;
@@ -267,7 +267,7 @@ static int table_export_points(ssm_ctx* c, VoxTable& t, ssm_point* out, int cap,
     if (n > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small (need " + std::to_string(n) + ")");
     if (n == 0) return SSM_OK;
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_point)); if (r) return r;
-    HIPCHK(c, k_voxel_gather_points(comp, order, n, reinterpret_cast<ssm_point*>(c->d_scratch), c->stream));
+    HIPCHK(c, k_voxel_gather_points(comp, order, n, c->d_scratch.as<ssm_point>(), c->stream));
     HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
@@ -295,7 +295,7 @@ extern "C" int ssm_map_insert(ssm_ctx* c, const ssm_point* pts, int n)
     for (int a = 0; a < n; ) {
         int64_t chunk = ((int64_t)1 << c->map.cap_log2) / 8; if (chunk < 4096) chunk = 4096; if (chunk > n - a) chunk = n - a;
         r = map_settle(c, c->stream, chunk); if (r) return r;
-        HIPCHK(c, k_voxel_insert(reinterpret_cast<ssm_point*>(c->d_scratch) + a, nullptr, chunk, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
+        HIPCHK(c, k_voxel_insert(c->d_scratch.as<ssm_point>() + a, nullptr, chunk, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
         a += (int)chunk;
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -332,7 +332,7 @@ extern "C" int ssm_map_export_table(ssm_ctx* c, ssm_voxel* out, int cap, int* n_
     if (n > cap) FAIL(c, SSM_E_CAPACITY, "table buffer too small (need " + std::to_string(n) + ")");
     if (n == 0) return SSM_OK;
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_voxel)); if (r) return r;
-    HIPCHK(c, k_voxel_gather_table(comp, order, n, reinterpret_cast<ssm_voxel*>(c->d_scratch), c->stream));
+    HIPCHK(c, k_voxel_gather_table(comp, order, n, c->d_scratch.as<ssm_voxel>(), c->stream));
     HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)n * sizeof(ssm_voxel), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
@@ -347,7 +347,7 @@ extern "C" int ssm_map_merge_table(ssm_ctx* c, const ssm_voxel* tab, int n)
     int r = ensure_scratch(c, (size_t)n * sizeof(ssm_voxel)); if (r) return r;
     HIPCHK(c, hipMemcpyAsync(c->d_scratch, tab, (size_t)n * sizeof(ssm_voxel), hipMemcpyHostToDevice, c->stream));
     r = map_settle(c, c->stream, n); if (r) return r;               // room for n new voxels first
-    HIPCHK(c, k_voxel_merge(reinterpret_cast<ssm_voxel*>(c->d_scratch), n, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
+    HIPCHK(c, k_voxel_merge(c->d_scratch.as<ssm_voxel>(), n, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
 }
@@ -422,7 +422,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
     int world = 0, rank = 0;
     NCCLCHK(c, ncclCommCount(comm, &world)); NCCLCHK(c, ncclCommUserRank(comm, &rank));
     if (world > c->comm_counts_cap) {     // 2 ints per rank + one word of this rank's own flag
-        if (c->d_comm_counts) { HIPCHK(c, hipStreamSynchronize(c->stream)); hipFree(c->d_comm_counts); c->d_comm_counts = nullptr; c->comm_counts_cap = 0; }
+        if (c->d_comm_counts) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->comm_counts_cap = 0; }
         DALLOC(c, c->d_comm_counts, (size_t)2 * world + 4); c->comm_counts_cap = world;
     }
     hipStream_t s = c->stream;
@@ -458,7 +458,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
             FAIL(c, SSM_E_NOMEM, "rank " + std::to_string(q) + " could not allocate the all-gather buffer; no rank merged");
         }
     }
-    uint8_t* recv = reinterpret_cast<uint8_t*>(c->d_scratch2);
+    uint8_t* recv = c->d_scratch2;
     int32_t* dn = reinterpret_cast<int32_t*>(recv + slot * world);
     HIPCHK(c, k_voxel_compact(c->map.tab, c->map.cap_log2, reinterpret_cast<ssm_voxel*>(recv + slot * rank), dn, s));
     NCCLCHK(c, ncclAllGather(recv + slot * rank, recv, slot, ncclUint8, comm, s));
@@ -482,7 +482,7 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
     if (!c->tmp.tab) { r = table_alloc(c, c->stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
     else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_point) + 64); if (r) return r;
-    ssm_point* dp = reinterpret_cast<ssm_point*>(c->d_scratch);
+    ssm_point* dp = c->d_scratch.as<ssm_point>();
     float* mm = reinterpret_cast<float*>(dp + n);
     HIPCHK(c, hipMemcpyAsync(dp, pts, (size_t)n * sizeof(ssm_point), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, k_voxel_bounds(dp, n, mm, c->stream));
@@ -504,7 +504,6 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
         if (!(cnt[1] & 1)) break;
         const int bigger = c->tmp.cap_log2 + 2;
         if (bigger > 28) FAIL(c, SSM_E_CAPACITY, "voxel_filter: more than 2^28 voxels");
-        hipFree(c->tmp.tab); c->tmp.tab = nullptr;
         r = table_alloc(c, c->stream, c->tmp, bigger); if (r) return r;
     }
     return table_export_points(c, c->tmp, out, cap, n_out);
@@ -525,7 +524,7 @@ extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint
     int r = ensure_pinned(c, np * 8); if (r) return r;
     memcpy(c->h_pinned, depth, np * 2); memcpy(c->h_pinned + np * 2, rgb, np * 3); memcpy(c->h_pinned + np * 5, sem, np * 3);
     r = ensure_scratch(c, np * 8); if (r) return r;
-    uint8_t* din = reinterpret_cast<uint8_t*>(c->d_scratch);
+    uint8_t* din = c->d_scratch;
     HIPCHK(c, hipMemcpyAsync(din, c->h_pinned, np * 8, hipMemcpyHostToDevice, c->stream));
     const uint16_t* dd = reinterpret_cast<const uint16_t*>(din); const uint8_t* drgb = din + np * 2; const uint8_t* dsem = din + np * 5;
     // the cloud is written straight into a slab of device memory (room for the worst case, w h points; only the n points made are kept): no allocation, no
@@ -534,15 +533,15 @@ extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint
     for (size_t i = 0; i < c->cloud_slabs.size(); i++) if (c->cloud_slabs[i].cap - c->cloud_slabs[i].used >= np) { si = (int)i; break; }
     if (si < 0) {
         ssm_ctx::CloudSlab sl; sl.cap = np * 8 > ((size_t)2 << 20) ? np * 8 : ((size_t)2 << 20);          // >= 64 MB of points
-        if (hipMalloc((void**)&sl.d, sl.cap * sizeof(ssm_point)) != hipSuccess) FAIL(c, SSM_E_HIP, "hipMalloc of a key-frame cloud slab failed");
-        c->cloud_slabs.push_back(sl); si = (int)c->cloud_slabs.size() - 1;
+        if (sl.d.alloc(c, sl.cap)) FAIL(c, SSM_E_HIP, "hipMalloc of a key-frame cloud slab failed");
+        c->cloud_slabs.push_back(std::move(sl)); si = (int)c->cloud_slabs.size() - 1;
     }
     ssm_ctx::CloudSlab& sl = c->cloud_slabs[si];
     ssm_point* dst = sl.d + sl.used;
     HIPCHK(c, k_moving_mask(dsem, 1, w, h, c->d_mask, c->stream));
     HIPCHK(c, k_backproject(dd, drgb, dsem, c->d_mask, nullptr, 1, w, h, *cam, max_distance,
                             c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, dst, c->stream));
-    int64_t* h_total = reinterpret_cast<int64_t*>(c->h_pinned);                  // (the staged images at the front of the pinned area are consumed by then: stream order)
+    int64_t* h_total = c->h_pinned.as<int64_t>();                  // (the staged images at the front of the pinned area are consumed by then: stream order)
     HIPCHK(c, hipMemcpyAsync(h_total, c->d_total, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t total = *h_total;
@@ -570,21 +569,18 @@ extern "C" int ssm_cloud_fetch(ssm_ctx* c, const ssm_cloud* cl, const double* T,
     if (cl->n == 0) return SSM_OK;
     if (!out) FAIL(c, SSM_E_INVAL, "null argument");
     int r = ensure_scratch(c, (size_t)cl->n * sizeof(ssm_point)); if (r) return r;
-    HIPCHK(c, k_cloud_transform(cl->d, cl->n, T, reinterpret_cast<ssm_point*>(c->d_scratch), c->stream));
+    HIPCHK(c, k_cloud_transform(cl->d, cl->n, T, c->d_scratch.as<ssm_point>(), c->stream));
     HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)cl->n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SSM_OK;
 }
-static int grow_points(ssm_ctx* c, ssm_point*& p, size_t& cap, size_t need, size_t keep)
+static int grow_points(ssm_ctx* c, DevBuf<ssm_point>& p, size_t need)          // room for `need` points; what p held is not kept
 {
-    if (need <= cap) return SSM_OK;
-    const size_t ncap = need + need / 2 + 1024;
-    ssm_point* q = nullptr;
+    if (need * sizeof(ssm_point) <= p.bytes()) return SSM_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (hipMalloc(&q, ncap * sizeof(ssm_point)) != hipSuccess) FAIL(c, SSM_E_HIP, "hipMalloc of the viewer map failed");
-    if (p && keep) HIPCHK(c, hipMemcpy(q, p, keep * sizeof(ssm_point), hipMemcpyDeviceToDevice));
-    if (p) hipFree(p);
-    p = q; cap = ncap;
+    DevBuf<ssm_point> q;                                        // (a failure leaves p as it is: the published map stays fetchable)
+    if (q.alloc(c, need + need / 2 + 1024)) FAIL(c, SSM_E_HIP, "hipMalloc of the viewer map failed");
+    p = std::move(q);
     return SSM_OK;
 }
 extern "C" int ssm_viewer_map_release(ssm_ctx* c, int test_fail_next)
@@ -593,9 +589,9 @@ extern "C" int ssm_viewer_map_release(ssm_ctx* c, int test_fail_next)
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (test_fail_next) { c->viewer_fail_next = true; return SSM_OK; }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (ssm_ctx::CloudSlab& sl : c->cloud_slabs) if (sl.live == 0 && sl.d) { hipFree(sl.d); sl.d = nullptr; sl.cap = 0; sl.used = 0; }      // (an emptied slab is skipped by the allocator: cap 0)
-    if (c->d_vcat) { hipFree(c->d_vcat); c->d_vcat = nullptr; c->vcat_cap = 0; }
-    if (c->d_vmap) { hipFree(c->d_vmap); c->d_vmap = nullptr; c->vmap_cap = 0; c->vmap_n = 0; }
+    for (ssm_ctx::CloudSlab& sl : c->cloud_slabs) if (sl.live == 0 && sl.d) { sl.d.reset(); sl.cap = 0; sl.used = 0; }      // (an emptied slab is skipped by the allocator: cap 0)
+    c->d_vcat.reset();
+    c->d_vmap.reset(); c->vmap_n = 0;
     return SSM_OK;
 }
 extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* clouds, const double* poses, int n, float leaf, int* n_map_out)
@@ -608,7 +604,7 @@ extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* 
     for (int i = 0; i < n; i++) { if (!clouds[i]) FAIL(c, SSM_E_INVAL, "null cloud"); if (clouds[i]->device != c->device) FAIL(c, SSM_E_INVAL, "cloud of another device"); total += (size_t)clouds[i]->n; }
     if (total > (size_t)0x7FFFFFFF) FAIL(c, SSM_E_CAPACITY, "more than 2^31 points in one map update");
     if (total == 0) { c->vmap_n = 0; if (n_map_out) *n_map_out = 0; return SSM_OK; }
-    int r = grow_points(c, c->d_vcat, c->vcat_cap, total + 8, 0); if (r) return r;       // (+ 8 points: the bounds words behind the data)
+    int r = grow_points(c, c->d_vcat, total + 8); if (r) return r;       // (+ 8 points: the bounds words behind the data)
     // previous centroids, then every cloud transformed by its pose: the viewer's `*map += *generatePointCloud(kf)`
     size_t off = 0;
     if (!rebuild && c->vmap_n) { HIPCHK(c, hipMemcpyAsync(c->d_vcat, c->d_vmap, (size_t)c->vmap_n * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->stream)); off = (size_t)c->vmap_n; }
@@ -626,7 +622,7 @@ extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* 
         const int64_t dx = (int64_t)((ord2f(ord[3]) - ord2f(ord[0])) * inv) + 1, dy = (int64_t)((ord2f(ord[4]) - ord2f(ord[1])) * inv) + 1,
                       dz = (int64_t)((ord2f(ord[5]) - ord2f(ord[2])) * inv) + 1;
         if (dx * dy * dz > (int64_t)2147483647) {
-            r = grow_points(c, c->d_vmap, c->vmap_cap, total, 0); if (r) return r;
+            r = grow_points(c, c->d_vmap, total); if (r) return r;
             HIPCHK(c, hipMemcpyAsync(c->d_vmap, c->d_vcat, total * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
             c->vmap_n = N; if (n_map_out) *n_map_out = N;
@@ -641,12 +637,11 @@ extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* 
         if (!(cnt[1] & 1)) break;
         const int bigger = c->tmp.cap_log2 + 2;
         if (bigger > 28) FAIL(c, SSM_E_CAPACITY, "viewer map: more than 2^28 voxels");
-        hipFree(c->tmp.tab); c->tmp.tab = nullptr;
         r = table_alloc(c, c->stream, c->tmp, bigger); if (r) return r;
     }
     int nv; ssm_voxel* comp; uint32_t* order;
     r = table_sorted(c, c->tmp, &nv, &comp, &order); if (r) return r;
-    r = grow_points(c, c->d_vmap, c->vmap_cap, (size_t)nv, 0); if (r) return r;
+    r = grow_points(c, c->d_vmap, (size_t)nv); if (r) return r;
     if (nv) HIPCHK(c, k_voxel_gather_points(comp, order, nv, c->d_vmap, c->stream));
     c->vmap_n = nv;
     if (n_map_out) *n_map_out = nv;

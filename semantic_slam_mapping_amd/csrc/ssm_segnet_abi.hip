@@ -17,8 +17,8 @@ extern "C" int ssm_segnet_layer_shape(int l, int* cin, int* cout, int* h, int* w
 int seg_init(ssm_ctx* c)
 {
     if (c->seg) return SSM_OK;
-    SegNetState* g = new SegNetState();
-    c->seg = g;
+    // built aside and handed to the context complete: a failure below leaves c->seg null and the next call builds again
+    std::unique_ptr<SegNetState> g(new SegNetState());
     for (int l = 0; l < SEG_LAYERS; l++) {
         g->cinp[l] = k_seg_layers[l].cin <= 8 ? 8 : (k_seg_layers[l].cin + 63) & ~63;   // <= 8 channels: the first-layer kernel ([H][W][8] input)
         g->coutp[l] = (k_seg_layers[l].cout + 63) & ~63;
@@ -29,21 +29,21 @@ int seg_init(ssm_ctx* c)
         g->batch = c->B < sb ? c->B : sb;
     }
     const size_t act = (size_t)g->batch * SEG_NW * SEG_NH * 64 * 2;
-    uint8_t* p;
-    int r = dalloc(c, &p, act); if (r) return r; g->actA = p;
-    r = dalloc(c, &p, act); if (r) return r; g->actB = p;
+    int r;
+    DALLOC(c, g->actA, act); DALLOC(c, g->actB, act);
     const int ph[5] = {180, 90, 45, 23, 12}, pw[5] = {240, 120, 60, 30, 15}, pc[5] = {64, 128, 256, 512, 512};
     for (int i = 0; i < 5; i++) DALLOC(c, g->code[i], (size_t)g->batch * ph[i] * pw[i] * pc[i]);
     DALLOC(c, g->labels, (size_t)g->batch * SEG_NW * SEG_NH);
     DALLOC(c, g->d_sem_gen, (size_t)c->B * c->g.W * c->g.H * 3);
-    auto up = [&](int ssize, int dsize, int32_t** o, int16_t** a) -> int {
+    auto up = [&](int ssize, int dsize, DevBuf<int32_t>& o, DevBuf<int16_t>& a) -> int {
         std::vector<int32_t> ofs; std::vector<int16_t> co; resize_tables(ssize, dsize, ofs, co);
-        int rr = dalloc(c, o, ofs.size()); if (rr) return rr; rr = dalloc(c, a, co.size()); if (rr) return rr;
-        if (hipMemcpy(*o, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(*a, co.data(), co.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { c->err = "segnet table upload"; return SSM_E_HIP; }
+        DALLOC(c, o, ofs.size()); DALLOC(c, a, co.size());
+        if (hipMemcpy(o, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(a, co.data(), co.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { c->err = "segnet table upload"; return SSM_E_HIP; }
         return SSM_OK;
     };
-    if ((r = up(c->g.W, SEG_NW, &g->pre_xofs, &g->pre_xa)) || (r = up(c->g.H, SEG_NH, &g->pre_yofs, &g->pre_ya)) ||
-        (r = up(SEG_NW, c->g.W, &g->post_xofs, &g->post_xa)) || (r = up(SEG_NH, c->g.H, &g->post_yofs, &g->post_ya))) return r;
+    if ((r = up(c->g.W, SEG_NW, g->pre_xofs, g->pre_xa)) || (r = up(c->g.H, SEG_NH, g->pre_yofs, g->pre_ya)) ||
+        (r = up(SEG_NW, c->g.W, g->post_xofs, g->post_xa)) || (r = up(SEG_NH, c->g.H, g->post_yofs, g->post_ya))) return r;
+    c->seg = std::move(g);
     return SSM_OK;
 }
 // the layer's Winograd weights when that kernel is to run it: SSM_CONV_WINOGRAD=1 (A/B runs and tests).  The default is the direct kernel on every layer: the
@@ -61,7 +61,7 @@ extern "C" int ssm_segnet_set_layer(ssm_ctx* c, int l, const float* weight, cons
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (l < 0 || l >= SEG_LAYERS || !weight || !scale || !shift) FAIL(c, SSM_E_INVAL, "bad arguments");
     int r = seg_init(c); if (r) return r;
-    SegNetState* g = c->seg;
+    SegNetState* g = c->seg.get();
     const int cin = k_seg_layers[l].cin, cout = k_seg_layers[l].cout, cinp = g->cinp[l], coutp = g->coutp[l];
     std::vector<uint16_t> w;
     if (cinp == 8) {
@@ -94,10 +94,10 @@ extern "C" int ssm_segnet_set_layer(ssm_ctx* c, int l, const float* weight, cons
         }
     }
     if (!wwv.empty()) {
-        if (!g->ww[l]) { uint16_t* p; r = dalloc(c, &p, wwv.size()); if (r) return r; g->ww[l] = p; }
+        if (!g->ww[l]) DALLOC(c, g->ww[l], wwv.size() * 2);
         HIPCHK(c, hipMemcpy(g->ww[l], wwv.data(), wwv.size() * 2, hipMemcpyHostToDevice));
     }
-    if (!g->w[l]) { uint16_t* p; r = dalloc(c, &p, w.size()); if (r) return r; g->w[l] = p; DALLOC(c, g->scale[l], coutp); DALLOC(c, g->shift[l], coutp); }
+    if (!g->w[l]) { DALLOC(c, g->w[l], w.size() * 2); DALLOC(c, g->scale[l], coutp); DALLOC(c, g->shift[l], coutp); }
     std::vector<float> sc(coutp, 0.f), sh(coutp, 0.f);
     for (int o = 0; o < cout; o++) { sc[o] = scale[o]; sh[o] = shift[o]; }
     HIPCHK(c, hipMemcpy(g->w[l], w.data(), w.size() * 2, hipMemcpyHostToDevice));
@@ -111,7 +111,7 @@ extern "C" int ssm_segnet_set_layer(ssm_ctx* c, int l, const float* weight, cons
 // logits_out == nullptr: the last layer writes the labels (g->labels) straight from its epilogue.
 static int seg_forward_core(ssm_ctx* c, hipStream_t s, int nb, void** logits_out)
 {
-    SegNetState* g = c->seg;
+    SegNetState* g = c->seg.get();
     void* cur = g->actA; void* nxt = g->actB;
     HIPCHK(c, k_segnet_begin(s));
     auto conv = [&](int l) -> int {
@@ -159,7 +159,7 @@ static int seg_forward_core(ssm_ctx* c, hipStream_t s, int nb, void** logits_out
 int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags)
 {
     int r = seg_init(c); if (r) return r;
-    SegNetState* g = c->seg;
+    SegNetState* g = c->seg.get();
     for (int l = 0; l < SEG_LAYERS; l++) if (!g->set[l]) FAIL(c, SSM_E_INVAL, "SegNet layer " + std::to_string(l) + " has no weights (ssm_segnet_set_layer)");
     const int W = c->g.W, H = c->g.H;
     for (int f0 = 0; f0 < n; f0 += g->batch) {
@@ -208,7 +208,7 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!in || !out || H < 1 || W < 1 || (size_t)H * W > (size_t)SEG_NW * SEG_NH) FAIL(c, SSM_E_INVAL, "bad arguments");
     int r = seg_init(c); if (r) return r;
-    SegNetState* g = c->seg; hipStream_t s = c->stream;
+    SegNetState* g = c->seg.get(); hipStream_t s = c->stream;
     const int PH = (H + 1) / 2, PW = (W + 1) / 2;
     if (op == 0) {
         if (arg < 0 || arg >= SEG_LAYERS || !g->set[arg]) FAIL(c, SSM_E_INVAL, "layer not set");

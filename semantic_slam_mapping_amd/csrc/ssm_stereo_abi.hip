@@ -3,21 +3,15 @@
 #include "ssm_ctx.h"
 
 // ---------------------------------------------------------------- stereo path: QuadFeatureMatch, StereoSGBM depth, VisualOdometryStereo
-void stereo_free(StereoState* q)
-{
-    void* p[] = { q->pyr, q->der, q->gw.eig, q->gw.cand_at, q->gw.cand_bits, q->gw.keys, q->gw.kept, q->gw.deps, q->gw.depn, q->gw.state, q->gw.maxord, q->gw.count, q->gw.nkept, q->sg_fail, q->ncorner, q->has_prev, q->pts, q->status, q->err,
-                  q->tr_all, q->vcount, q->rand_off, q->consumed, q->sg_wsN[0], q->dminN[0], q->sg_wsN[1], q->dminN[1], q->sg_wsN[2], q->dminN[2], q->quad, q->nquad, q->corners, q->ncorners, q->disp, q->depth, q->tr,
-                  q->inliers, q->vo_result, q->in_stage };
-    for (void* x : p) if (x) hipFree(x);
-}
 // exact: the row stride of the sequence outputs is max_corners, so the sequence path wants exactly that many; the per-call entry points take any workspace that is large enough
 static int stereo_init(ssm_ctx* c, int w, int h, int maxc, bool exact = false)
 {
     if (c->stereo && c->stereo->w == w && c->stereo->h == h && (exact ? c->stereo->maxc == maxc : c->stereo->maxc >= maxc)) return SSM_OK;
     if (w < 4 || h < 2 || w > 4096 || h > 4096) FAIL(c, SSM_E_INVAL, "stereo path: image size must be at most 4096 x 4096");
     if (maxc < 1 || maxc > 32767) FAIL(c, SSM_E_INVAL, "max_corners must be 1..32767");
-    if (c->stereo) { hipDeviceSynchronize(); stereo_free(c->stereo); delete c->stereo; c->stereo = nullptr; }
-    StereoState* q = new StereoState(); c->stereo = q;
+    if (c->stereo) { hipDeviceSynchronize(); c->stereo.reset(); }
+    // built aside and handed to the context complete: a failure below leaves c->stereo null and the next call builds again
+    std::unique_ptr<StereoState> q(new StereoState());
     q->w = w; q->h = h; q->maxc = maxc; q->B = c->stereo_B;
     const int B = q->B;
     QuadBatch& b = q->qb;
@@ -31,24 +25,24 @@ static int stereo_init(ssm_ctx* c, int w, int h, int maxc, bool exact = false)
     // selected on the pixel grid instead (gftt_select_pixels), whose kept corners must fit in the list up to max_corners
     q->keycap = w * h / 4 + 1024 > maxc ? w * h / 4 + 1024 : maxc;
     GfttWork& g = q->gw; g.cap = q->keycap;
-    DALLOC(c, g.eig, (size_t)B * np); DALLOC(c, g.cand_at, (size_t)B * np); DALLOC(c, g.keys, (size_t)B * q->keycap); DALLOC(c, g.kept, (size_t)B * q->keycap);
-    DALLOC(c, g.deps, (size_t)B * q->keycap * k_quad_gftt_deps_per_candidate()); DALLOC(c, g.depn, (size_t)B * q->keycap); DALLOC(c, g.state, (size_t)B * q->keycap);
-    HIPCHK(c, hipMemset(g.cand_at, 0, (size_t)B * np * 4));      // gftt_finish_kernel keeps the map zeroed between calls
-    DALLOC(c, g.cand_bits, (size_t)B * k_quad_gftt_bits_words(w, h));
-    DALLOC(c, g.maxord, B); DALLOC(c, g.count, B); DALLOC(c, g.nkept, B); DALLOC(c, q->sg_fail, SG_FAIL_WORDS); DALLOC(c, q->ncorner, B); DALLOC(c, q->has_prev, B);
+    DALLOC(c, q->g_eig, (size_t)B * np); DALLOC(c, q->g_cand_at, (size_t)B * np); DALLOC(c, q->g_keys, (size_t)B * q->keycap); DALLOC(c, q->g_kept, (size_t)B * q->keycap);
+    DALLOC(c, q->g_deps, (size_t)B * q->keycap * k_quad_gftt_deps_per_candidate()); DALLOC(c, q->g_depn, (size_t)B * q->keycap); DALLOC(c, q->g_state, (size_t)B * q->keycap);
+    HIPCHK(c, hipMemset(q->g_cand_at, 0, (size_t)B * np * 4));      // gftt_finish_kernel keeps the map zeroed between calls
+    DALLOC(c, q->g_cand_bits, (size_t)B * k_quad_gftt_bits_words(w, h));
+    DALLOC(c, q->g_maxord, B); DALLOC(c, q->g_count, B); DALLOC(c, q->g_nkept, B); DALLOC(c, q->sg_fail, SG_FAIL_WORDS); DALLOC(c, q->ncorner, B); DALLOC(c, q->has_prev, B);
+    g.eig = q->g_eig; g.cand_at = q->g_cand_at; g.cand_bits = q->g_cand_bits; g.keys = q->g_keys; g.kept = q->g_kept; g.deps = q->g_deps; g.depn = q->g_depn; g.state = q->g_state;
+    g.maxord = q->g_maxord; g.count = q->g_count; g.nkept = q->g_nkept;
     HIPCHK(c, hipMemset(q->sg_fail, 0, 4 * SG_FAIL_WORDS));
     DALLOC(c, q->pts, (size_t)5 * B * maxc * 2); DALLOC(c, q->status, maxc); DALLOC(c, q->err, maxc);
     DALLOC(c, q->rand_off, B); DALLOC(c, q->consumed, 1);
+    c->stereo = std::move(q);
     return SSM_OK;
 }
 static int stereo_ensure_seq(ssm_ctx* c, int n)
 {
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     if (n <= q->seq_cap) return SSM_OK;
     HIPCHK(c, hipDeviceSynchronize());
-    void* olds[] = { q->quad, q->nquad, q->corners, q->ncorners, q->disp, q->depth, q->tr, q->inliers, q->vo_result };
-    for (void* p : olds) if (p) hipFree(p);
-    q->quad = nullptr; q->nquad = nullptr; q->corners = nullptr; q->ncorners = nullptr; q->disp = nullptr; q->depth = nullptr; q->tr = nullptr; q->inliers = nullptr; q->vo_result = nullptr;
     q->seq_cap = 0;
     const size_t np = (size_t)q->w * q->h;
     DALLOC(c, q->quad, (size_t)n * q->maxc); DALLOC(c, q->nquad, n); DALLOC(c, q->corners, (size_t)n * q->maxc * 2); DALLOC(c, q->ncorners, n);
@@ -59,28 +53,22 @@ static int stereo_ensure_seq(ssm_ctx* c, int n)
 }
 static int stereo_ensure_vo(ssm_ctx* c, int iters)
 {
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     if (iters <= q->vo_iters) return SSM_OK;
     HIPCHK(c, hipDeviceSynchronize());
-    if (q->tr_all) hipFree(q->tr_all); if (q->vcount) hipFree(q->vcount);
-    q->tr_all = nullptr; q->vcount = nullptr; q->vo_iters = 0;
+    q->vo_iters = 0;
     DALLOC(c, q->tr_all, (size_t)q->B * iters * 6); DALLOC(c, q->vcount, (size_t)q->B * iters);
     q->vo_iters = iters;
     return SSM_OK;
 }
 static int stereo_ensure_sgbm(ssm_ctx* c, const ssm_sgbm_params& p, int nb, int which = 0)
 {
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     const size_t need = k_sgbm_workspace_bytes(q->w, q->h, p, nb, c->sgbm_form_cfg);
-    void*& ws = q->sg_wsN[which]; size_t& have = q->sg_ws_bytesN[which];
     if (!q->dminN[which]) DALLOC(c, q->dminN[which], 128);
-    if (need <= have) return SSM_OK;
+    if (need <= q->sg_wsN[which].bytes()) return SSM_OK;
     HIPCHK(c, hipDeviceSynchronize());
-    if (ws) hipFree(ws);
-    ws = nullptr; have = 0;
-    uint8_t* p8; int r = dalloc(c, &p8, need); if (r) return r;
-    ws = p8; have = need;
-    return SSM_OK;
+    return q->sg_wsN[which].alloc(c, need);
 }
 static int sgbm_check_params(ssm_ctx* c, const ssm_sgbm_params* params, int w, int h)
 {
@@ -105,7 +93,7 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     const int maxc = in->max_corners > 0 ? in->max_corners : 1000;
     if ((stages & SSM_STEREO_QUAD) && (w < 32 || h < 32)) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
     int r = stereo_init(c, w, h, maxc, true); if (r) return r;
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     if (stages & SSM_STEREO_DEPTH) { r = sgbm_check_params(c, &in->sgbm, w, h); if (r) return r; }
     r = stereo_ensure_seq(c, n > 0 ? n : 1); if (r) return r;
     if (stages & SSM_STEREO_VO) { r = stereo_ensure_vo(c, in->ransac_iters > 0 ? in->ransac_iters : 1); if (r) return r; }
@@ -160,7 +148,7 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
             const int alt = (f0 / B) % nsg;
             hipStream_t sg = sgs[alt];
             prof_begin(c, sg, "sgbm");                                  // (the stage events on SGBM's stream)
-            HIPCHK(c, k_sgbm(in->left + (size_t)f0 * np, in->right + (size_t)f0 * np, w, h, nb, in->sgbm, q->sg_wsN[alt], q->sg_ws_bytesN[alt], q->disp + (size_t)f0 * np, 0, sg, q->sg_fail + (f0 / B) % SG_FAIL_WORDS,
+            HIPCHK(c, k_sgbm(in->left + (size_t)f0 * np, in->right + (size_t)f0 * np, w, h, nb, in->sgbm, q->sg_wsN[alt], q->sg_wsN[alt].bytes(), q->disp + (size_t)f0 * np, 0, sg, q->sg_fail + (f0 / B) % SG_FAIL_WORDS,
                              c->sgbm_form_cfg, nsg));
             HIPCHK(c, k_sgbm_depth(q->disp + (size_t)f0 * np, w, h, nb, in->baseline, in->cu, in->cv, in->f, in->roix, in->roiy, in->roiz, in->scale, q->dminN[alt], q->depth + (size_t)f0 * np, sg));
             prof_end(c, sg);
@@ -190,14 +178,12 @@ extern "C" int ssm_stereo_seq_process(ssm_ctx* c, const ssm_stereo_frames_dev* i
 // 1241x376 image costs ~1 ms)
 static int stereo_stage_images(ssm_ctx* c, const uint8_t* const* imgs, int nimg, int w, int h, int stride, uint8_t** dev_out)
 {
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     const size_t np = (size_t)w * h;
     int r = ensure_pinned(c, np * 6 > (size_t)nimg * np ? np * 6 : (size_t)nimg * np); if (r) return r;
-    if ((size_t)nimg * np > q->in_stage_bytes) {
+    if ((size_t)nimg * np > q->in_stage.bytes()) {
         HIPCHK(c, hipDeviceSynchronize());
-        if (q->in_stage) hipFree(q->in_stage);
-        q->in_stage = nullptr; q->in_stage_bytes = 0;
-        DALLOC(c, q->in_stage, (size_t)4 * np); q->in_stage_bytes = (size_t)4 * np;
+        DALLOC(c, q->in_stage, (size_t)4 * np);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));               // the previous call's copies out of the staging buffer are done
     for (int k = 0; k < nimg; k++)
@@ -241,7 +227,7 @@ extern "C" int ssm_gftt(ssm_ctx* c, const uint8_t* img, int w, int h, int stride
     if (w < 32 || h < 32) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
     if (max_corners > 32767) FAIL(c, SSM_E_INVAL, "max_corners must be <= 32767");
     int r = stereo_init(c, w, h, max_corners); if (r) return r;
-    StereoState* q = c->stereo; const QuadBatch& qb = q->qb;
+    StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
     HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, img, stride, w, h, hipMemcpyHostToDevice, c->stream));        // side 0, slot 1, level 0
     HIPCHK(c, k_quad_gftt(qb, 1, max_corners, quality, min_distance, q->gw, q->pts, q->maxc, q->ncorner, c->stream));
     int n = 0;
@@ -262,7 +248,7 @@ extern "C" int ssm_lk_track(ssm_ctx* c, const uint8_t* prev, const uint8_t* next
     if (n == 0) return SSM_OK;
     if (w < 32 || h < 32) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
     int r = stereo_init(c, w, h, n > 1000 ? n : 1000); if (r) return r;
-    StereoState* q = c->stereo; const QuadBatch& qb = q->qb;
+    StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
     // previous image = (side 0, slot 1), next image = (side 1, slot 1)
     HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, prev, stride, w, h, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(qb.B1 + 1) * qb.slot_elems, w, next, stride, w, h, hipMemcpyHostToDevice, c->stream));
@@ -312,13 +298,13 @@ static int sgbm_run(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w
     r = stereo_init(c, w, h, c->stereo && c->stereo->w == w && c->stereo->h == h ? c->stereo->maxc : 1000); if (r) return r;
     r = stereo_ensure_seq(c, 1); if (r) return r;
     r = stereo_ensure_sgbm(c, *params, 1); if (r) return r;
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     const uint8_t* imgs[2] = { left, right };
     uint8_t* dev = nullptr;
     r = stereo_stage_images(c, imgs, 2, w, h, stride, &dev); if (r) return r;
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }      // ssm_get_stage_times then reports this call ("sgbm": all kernels of k_sgbm)
     prof_begin(c, c->stream, "sgbm");
-    HIPCHK(c, k_sgbm(dev, dev + (size_t)w * h, w, h, 1, *params, q->sg_wsN[0], q->sg_ws_bytesN[0], q->disp, stage, c->stream, q->sg_fail, form, 1));
+    HIPCHK(c, k_sgbm(dev, dev + (size_t)w * h, w, h, 1, *params, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp, stage, c->stream, q->sg_fail, form, 1));
     prof_end(c, c->stream);
     q->sg_pending.valid = false;                                  // (the staged pair is this call's: the host-pointer entry points repeat a timed-out sweep themselves)
     *d_disp_out = q->disp; *d_depth_out = q->depth;
@@ -330,7 +316,7 @@ static int sgbm_run(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w
 // are the oracle's after all.  Reported through ssm_last_error (a note, the call succeeds) and counted in sgbm_fallbacks.
 int sgbm_recover(ssm_ctx* c)
 {
-    StereoState* q = c->stereo;
+    StereoState* q = c->stereo.get();
     int32_t sf[SG_FAIL_WORDS];
     HIPCHK(c, hipMemcpy(sf, q->sg_fail, sizeof(sf), hipMemcpyDeviceToHost));
     bool any = false; for (int k = 0; k < SG_FAIL_WORDS; k++) any = any || sf[k] != 0;
@@ -342,7 +328,7 @@ int sgbm_recover(ssm_ctx* c)
     for (int f0 = 0, bi = 0; f0 < in.n; f0 += B, bi++) {
         if (!sf[bi % SG_FAIL_WORDS]) continue;
         const int nb = in.n - f0 < B ? in.n - f0 : B;
-        HIPCHK(c, k_sgbm(in.left + (size_t)f0 * np, in.right + (size_t)f0 * np, w, h, nb, in.sgbm, q->sg_wsN[0], q->sg_ws_bytesN[0], q->disp + (size_t)f0 * np, 0, c->stream, q->sg_fail + bi % SG_FAIL_WORDS, 1, 1));
+        HIPCHK(c, k_sgbm(in.left + (size_t)f0 * np, in.right + (size_t)f0 * np, w, h, nb, in.sgbm, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp + (size_t)f0 * np, 0, c->stream, q->sg_fail + bi % SG_FAIL_WORDS, 1, 1));
         HIPCHK(c, k_sgbm_depth(q->disp + (size_t)f0 * np, w, h, nb, in.baseline, in.cu, in.cv, in.f, in.roix, in.roiy, in.roiz, in.scale, q->dminN[0], q->depth + (size_t)f0 * np, c->stream));
         redone++;
     }
@@ -479,7 +465,7 @@ static int pnp_solve_impl(ssm_ctx* c, const float* img, const float* obj, int n,
     int r = ensure_scratch(c, total); if (r) return r;
     r = ensure_pinned(c, al(up) + al(down)); if (r) return r;
     if (G > 1) {
-        if (!c->d_pnp_xchg) { HIPCHK(c, hipMalloc((void**)&c->d_pnp_xchg, k_pnp_xchg_bytes())); c->pnp_epoch = 0; }
+        if (!c->d_pnp_xchg) { if (c->d_pnp_xchg.alloc_bytes(c, k_pnp_xchg_bytes())) return SSM_E_HIP; c->pnp_epoch = 0; }
         if (c->pnp_epoch == 0) HIPCHK(c, hipMemsetAsync(c->d_pnp_xchg, 0, k_pnp_xchg_bytes(), c->stream));
     }
     uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->stream;

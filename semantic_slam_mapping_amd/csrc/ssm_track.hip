@@ -1,8 +1,8 @@
 // ssm_track.hip -- ssm_tracker_*: rgbd_tutor::Tracker::updateFrame (reference src/track.cpp:8-36, 140-212) for all frames of an ssm_seq_process call.
 // Host orchestration of the pose chain (the chain is serial by nature: frame f's initial value and its reference poses are frame f-1's results); the PnP
 // arithmetic is include/ssm/pnp_core.h, the code the per-frame host class (include/ssm/pnp.h) runs, so both give the same bits.  Written against the
-// public C ABI (ssm_match for the on-demand pairs, ssm_memcpy_d2h) -- no access to the context's internals.
-#include "pnp_chain.h"
+// public C ABI (ssm_match for the on-demand pairs, ssm_memcpy_d2h) -- no access to the context's internals (ssm_ctx.h is here for DevBuf alone).
+#include "ssm_ctx.h"
 #include <deque>
 #include <string>
 #include <vector>
@@ -26,9 +26,9 @@ struct ssm_tracker {
     std::vector<float> img, obj; std::vector<unsigned char> inl; std::vector<ssm_pnp::Edge> edges; std::vector<ssm_dmatch> tmp_matches;
     std::vector<uint8_t> have;            // per frame of the current call: bit 0 = features on the host, bit 1 = match tables on the host
     // device chain (use_device): scratch + the state block, allocated at first use
-    PnpState* d_state = nullptr; double* d_pose = nullptr; ssm_track_info* d_info = nullptr; float *d_img = nullptr, *d_obj = nullptr, *d_hist = nullptr;
-    uint8_t *d_inl = nullptr, *d_dec = nullptr; void* d_edges = nullptr; double2* d_err = nullptr; int d_cap = 0, d_R = 0, d_n = 0;
-    unsigned long long* d_xchg = nullptr; int blocks = 1;      // the cluster form of the device chain (SSM_PNP_BLOCKS, kernels_pnp.hip): blocks per chain, their exchange ring
+    DevBuf<PnpState> d_state; DevBuf<double> d_pose; DevBuf<ssm_track_info> d_info; DevBuf<float> d_img, d_obj, d_hist;
+    DevBuf<uint8_t> d_inl, d_dec; DevBuf<void> d_edges; DevBuf<double2> d_err; int d_cap = 0, d_R = 0, d_n = 0;
+    DevBuf<unsigned long long> d_xchg; int blocks = 1;     // the cluster form of the device chain (SSM_PNP_BLOCKS, kernels_pnp.hip): blocks per chain, their exchange ring
     long device_frames = 0, host_frames = 0;
     bool downgraded = false;              // the cluster form timed out once: one block per chain since (reported by ssm_tracker_last_error)
     int64_t work[4] = {0, 0, 0, 0};       // the device chain's passes over the edges (ssm_tracker_work)
@@ -66,21 +66,13 @@ extern "C" int ssm_tracker_create(ssm_ctx* ctx, const ssm_tracker_params* p, ssm
     *out = t;
     return SSM_OK;
 }
-static void tracker_free_device(ssm_tracker* t)
-{
-    void* p[] = { t->d_state, t->d_pose, t->d_info, t->d_img, t->d_obj, t->d_hist, t->d_inl, t->d_dec, t->d_edges, t->d_err, t->d_xchg };
-    t->d_xchg = nullptr;
-    for (void* x : p) if (x) hipFree(x);
-    t->d_state = nullptr; t->d_pose = nullptr; t->d_info = nullptr; t->d_img = t->d_obj = t->d_hist = nullptr; t->d_inl = t->d_dec = nullptr; t->d_edges = nullptr; t->d_err = nullptr;
-    t->d_cap = t->d_R = t->d_n = 0;
-}
 extern "C" void ssm_tracker_destroy(ssm_tracker* t)
 {
     if (!t) return;
     (void)hipSetDevice(ssm_internal_get_device(t->ctx));
     if (t->own) { hipStreamSynchronize(t->own); hipStreamDestroy(t->own); }
     if (t->ev) hipEventDestroy(t->ev);
-    tracker_free_device(t); delete t;
+    delete t;                                                      // (its device buffers with it)
 }
 extern "C" const char* ssm_tracker_last_error(const ssm_tracker* t) { return t ? t->err.c_str() : "null tracker"; }
 extern "C" int ssm_tracker_reset(ssm_tracker* t)
@@ -97,15 +89,14 @@ static int tracker_ensure_device(ssm_tracker* t, int cap, int R, int n)
 {
     if (t->d_state && t->d_cap == cap && t->d_R == R && t->d_n >= n) return SSM_OK;
     ssm_sync(t->ctx);
-    tracker_free_device(t);
+    t->d_state.reset(); t->d_cap = t->d_R = t->d_n = 0;               // (d_state marks a complete set: a failure below is tried again by the next call)
     const size_t mc = (size_t)R * cap, G = (size_t)t->blocks;          // G private slices of the state and of every scratch array (the cluster form)
-    bool ok = hipMalloc((void**)&t->d_state, G * sizeof(PnpState)) == hipSuccess && hipMalloc((void**)&t->d_pose, (size_t)n * 128) == hipSuccess &&
-              hipMalloc((void**)&t->d_info, (size_t)n * sizeof(ssm_track_info)) == hipSuccess && hipMalloc((void**)&t->d_img, G * mc * 8) == hipSuccess &&
-              hipMalloc((void**)&t->d_obj, G * mc * 12) == hipSuccess && hipMalloc((void**)&t->d_hist, mc * 12) == hipSuccess && hipMalloc((void**)&t->d_inl, G * mc) == hipSuccess &&
-              hipMalloc((void**)&t->d_dec, G * mc) == hipSuccess && hipMalloc(&t->d_edges, G * mc * k_pnp_edge_bytes()) == hipSuccess && hipMalloc((void**)&t->d_err, G * mc * sizeof(double2)) == hipSuccess &&
-              hipMalloc((void**)&t->d_xchg, k_pnp_xchg_bytes()) == hipSuccess;
-    if (!ok) { tracker_free_device(t); t->err = "device allocation for the pose chain failed"; return SSM_E_NOMEM; }
-    t->d_cap = cap; t->d_R = R; t->d_n = n;
+    DevBuf<PnpState> st;
+    const bool ok = !st.alloc(nullptr, G) && !t->d_pose.alloc(nullptr, (size_t)n * 16) && !t->d_info.alloc(nullptr, (size_t)n) && !t->d_img.alloc(nullptr, G * mc * 2) &&
+                    !t->d_obj.alloc(nullptr, G * mc * 3) && !t->d_hist.alloc(nullptr, mc * 3) && !t->d_inl.alloc(nullptr, G * mc) && !t->d_dec.alloc(nullptr, G * mc) &&
+                    !t->d_edges.alloc(nullptr, G * mc * k_pnp_edge_bytes()) && !t->d_err.alloc(nullptr, G * mc) && !t->d_xchg.alloc_bytes(nullptr, k_pnp_xchg_bytes());
+    if (!ok) { t->err = "device allocation for the pose chain failed"; return SSM_E_NOMEM; }
+    t->d_state = std::move(st); t->d_cap = cap; t->d_R = R; t->d_n = n;
     return SSM_OK;
 }
 extern "C" int ssm_tracker_run(ssm_tracker* t, const ssm_seq_out_dev* seq, int n, double* pose_out, ssm_track_info* info_out)
@@ -190,8 +181,8 @@ extern "C" int ssm_tracker_run(ssm_tracker* t, const ssm_seq_out_dev* seq, int n
                 if (hipMemcpyAsync(t->d_state + b, &hs, sizeof(hs), hipMemcpyHostToDevice, st) != hipSuccess) TFAIL(t, SSM_E_HIP, "upload of the tracker state failed");
             PnpChainArgs a; a.kps = seq->kps; a.pos3d = seq->pos3d; a.matches = seq->matches; a.nmatch = seq->nmatch; a.hist_pos3d = t->d_hist;
             a.cap = cap; a.R = R; a.f_begin = f; a.f_end = n; a.max_lost = t->prm.max_lost_frame; a.cam = cam;
-            a.state = t->d_state; a.pose_out = t->d_pose; a.info_out = t->d_info; a.img = t->d_img; a.obj = t->d_obj; a.inl = t->d_inl; a.dec = t->d_dec; a.ledges = (LEdge*)t->d_edges; a.err = t->d_err; a.edges_in_lds = 0;
-            a.blocks = t->blocks; a.xchg = t->d_xchg; a.xfail = reinterpret_cast<unsigned*>(reinterpret_cast<unsigned char*>(t->d_xchg) + k_pnp_xchg_bytes() - 64);
+            a.state = t->d_state; a.pose_out = t->d_pose; a.info_out = t->d_info; a.img = t->d_img; a.obj = t->d_obj; a.inl = t->d_inl; a.dec = t->d_dec; a.ledges = t->d_edges.as<LEdge>(); a.err = t->d_err; a.edges_in_lds = 0;
+            a.blocks = t->blocks; a.xchg = t->d_xchg; a.xfail = reinterpret_cast<unsigned*>(t->d_xchg.as<unsigned char>() + k_pnp_xchg_bytes() - 64);
             if (k_pnp_chain(a, st) != hipSuccess) TFAIL(t, SSM_E_HIP, "pose chain launch failed");
             if (hipMemcpyAsync(&hs, t->d_state, sizeof(hs), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) TFAIL(t, SSM_E_HIP, "pose chain failed");
             if (hs.stopped_at == -1 && t->blocks > 1) {

@@ -1,0 +1,141 @@
+"""Who owns the library's device memory: every buffer of a context, its stereo and SegNet state, its ORB workspaces and of a tracker is a DevBuf
+(csrc/ssm_ctx.h), and the library counts the live ones (ssm_debug_live_allocations: buffers, device bytes, pinned host bytes -- as asked for, process-wide,
+without what ssm_dev_alloc / ssm_host_alloc hand to the caller).  The test walks every growth and replacement path once and checks the count with exact
+equalities; the device's free memory cannot serve (the GPU is shared).  The walk runs in a fresh child process (this file as a script), so that the
+contexts of other tests do not count; the child prints its readings as one JSON line and the test asserts on them.
+
+Not covered: an allocation that fails half-way through a set-up (ensure_seq, stereo_init, seg_init, tracker_ensure_device) -- there is no failure-injection
+hook; those paths are checked by reading."""
+import json
+import os
+import subprocess
+import sys
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CAM = (318.6, 255.3, 517.3, 516.5, 1000.0)
+W, H = 640, 480
+GEOM1 = (640, 480, 1000)          # stereo: width, height, max_corners
+GEOM2 = (480, 320, 600)
+
+
+def _stereo(ssm, c, geom, n=3, iters=50):
+    """stereo_seq_process (quad matcher + SGBM depth + VO) on n frame pairs of `geom`; the inputs are the caller's memory and are given back"""
+    w, h, maxc = geom
+    rng = np.random.default_rng(7)
+    L = np.kron(rng.integers(0, 256, (n, h // 8, w // 8), dtype=np.uint8), np.ones((1, 8, 8), np.uint8)); R = np.roll(L, -4, axis=2)      # blocks of 8 x 8: corners to find
+    draws = ssm.GlibcRand(1).draws(n * iters * 3)
+    bufs = [c.dev_alloc(L.nbytes), c.dev_alloc(R.nbytes), c.dev_alloc(draws.nbytes)]
+    try:
+        c.h2d(bufs[0], L); c.h2d(bufs[1], R); c.h2d(bufs[2], draws)
+        c.stereo_seq_process(bufs[0], bufs[1], n, w, h, max_corners=maxc, vo=(700.0, w / 2.0, h / 2.0, 0.5, 2.0, True), ransac_iters=iters, rand_stream_dev=bufs[2],
+                             baseline=0.5, cu=w / 2.0, cv=h / 2.0, f=700.0, roix=100.0, roiy=100.0, roiz=100.0, scale=1000.0)
+        c.sync()
+    finally:
+        for p in bufs:
+            c.dev_free(p)
+
+
+def child():
+    sys.path.insert(0, ROOT)
+    import semantic_slam_mapping_amd as ssm
+    from semantic_slam_mapping_amd.segnet_model import make_weights
+    def live():          # + the device bytes without the context map's table: the map grows as frames are fused (map_settle), whatever else a call does
+        n, d, p = ssm.live_allocations()
+        slots = 1 << c.map_stats()[0] if c is not None else 0
+        return [n, d, p, d - (slots * (ssm.VOXEL_DTYPE.itemsize + 4) + 32 if slots else 0)]
+    c = None
+    r = {"start": live()}                                                        # (a) before any context exists
+    c = ssm.Context(0, orb_features=500, max_batch=2, voxel_capacity_log2=16, camera=CAM)
+    r["context"] = live()
+    # 1. the sequence path with the map stage: 3 frames (sets seq_cap), 2 frames (below it: nothing may be allocated), 6 frames (above it: ensure_seq grows and
+    #    carries the history rows over); the first fused map launch trades the overflow list for the large one
+    n = 6
+    bufs = [c.dev_alloc(n * W * H * 3), c.dev_alloc(n * W * H * 2), c.dev_alloc(n * W * H * 3), c.dev_alloc(n * 128)]
+    c.synth_frames_dev(0x5EED0000, 0, n, *bufs)
+    r["ovf_cap_before"] = c.map_stats()[3]
+    c.seq_process(*bufs, 3); c.sync()
+    r["seq3"] = live()
+    r["ovf_cap_after"] = c.map_stats()[3]
+    c.seq_process(*bufs, 2, continue_sequence=True); c.sync()
+    r["seq2"] = live()
+    out = c.seq_process(*bufs, n, continue_sequence=True); c.sync()
+    r["seq6"] = live()
+    r["map_size"] = c.map_size()
+    # 4. (while the call's outputs are there) a device-chain tracker, run and closed
+    trk = ssm.Tracker(c, use_device=True)
+    trk.run(out, n)
+    r["tracker_device_frames"] = trk.stats()[0]
+    r["tracker_open"] = live()
+    trk.close()
+    r["tracker_closed"] = live()
+    bgr = c.d2h(bufs[0], (n, H, W, 3), np.uint8); depth = c.d2h(bufs[1], (n, H, W), np.uint16); sem = c.d2h(bufs[2], (n, H, W, 3), np.uint8)
+    for p in bufs:
+        c.dev_free(p)
+    # 2. SegNet: weights set, one forward pass
+    for l, (wt, sc, sh) in enumerate(make_weights(1234)):
+        c.segnet_set_layer(l, wt, sc, sh)
+    c.classify(bgr[0])
+    r["segnet"] = live()
+    # 3. the viewer map: two key-frame clouds, an update, then everything given back
+    before = live()
+    clouds = [c.backproject_dev(depth[k], bgr[k], sem[k]) for k in range(2)]
+    r["viewer_points"] = c.viewer_map_update(clouds, [np.eye(4)] * 2, rebuild=True, leaf=0.1)
+    r["viewer_open"] = live()
+    for cl in clouds:
+        c.cloud_free(cl)
+    assert c.lib.ssm_viewer_map_release(c.h, 0) == 0
+    r["viewer_before"], r["viewer_released"] = before, live()
+    # 5. stereo on a context of its own (the first one stays open: its share is constant): one geometry, then a second one with another max_corners --
+    #    stereo_init replaces the state -- against a fresh context taken straight to the second geometry
+    base = live()
+    s1 = ssm.Context(0, orb_features=500, max_batch=2, voxel_capacity_log2=16, camera=CAM)
+    _stereo(ssm, s1, GEOM1)
+    r["stereo_geom1"] = [a - b for a, b in zip(live(), base)]
+    _stereo(ssm, s1, GEOM2)
+    r["stereo_geom1_then_2"] = [a - b for a, b in zip(live(), base)]
+    s1.close()
+    r["stereo_closed"], r["stereo_base"] = live(), base
+    s2 = ssm.Context(0, orb_features=500, max_batch=2, voxel_capacity_log2=16, camera=CAM)
+    _stereo(ssm, s2, GEOM2)
+    r["stereo_geom2_fresh"] = [a - b for a, b in zip(live(), base)]
+    s2.close()
+    c.close(); c = None
+    r["end"] = live()                                                            # (d) every tracker and context closed
+    print("OWNERSHIP " + json.dumps(r))
+
+
+@pytest.mark.gpu
+def test_live_allocations_follow_every_owner():
+    p = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    print(p.stdout[-4000:]); print(p.stderr[-4000:])
+    assert p.returncode == 0
+    r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("OWNERSHIP ")][-1][len("OWNERSHIP "):])
+    for k, v in r.items():
+        print(k, v)
+    assert r["start"] == [0, 0, 0, 0]                                               # (a)
+    assert r["context"][0] > 0 and r["context"][1] > 0 and r["context"][2] == 64       # (the map counter ring: the one pinned buffer of a fresh context)
+    # (b) 1: the walk reached the paths it is meant to reach
+    assert r["ovf_cap_after"] > r["ovf_cap_before"] == 1 << 18                   # the fused map launch swapped the overflow list
+    assert r["seq2"][0] == r["seq3"][0] and r["seq2"][2:] == r["seq3"][2:]       # below seq_cap: nothing allocated, nothing released (but the map's table may have grown)
+    assert r["seq6"][0] == r["seq3"][0] and r["seq6"][3] > r["seq3"][3]          # above it: the same buffers, larger -- the old ones are gone
+    assert r["map_size"] > 0
+    # (b) 4: the device chain ran; its eleven buffers came and went
+    assert r["tracker_device_frames"] > 0
+    assert r["tracker_open"][0] == r["tracker_closed"][0] + 11 and r["tracker_open"][3] > r["tracker_closed"][3]
+    assert r["tracker_closed"][0] >= r["seq6"][0] and r["tracker_closed"][3] >= r["seq6"][3]      # (the host steps of the run may have made the context's staging rings)
+    # (b) 2, 3
+    assert r["segnet"][0] > r["tracker_closed"][0] and r["segnet"][1] > r["tracker_closed"][1]
+    assert r["viewer_points"] > 0 and r["viewer_open"][1] > r["viewer_before"][1]
+    # the release gives back the slabs, the map and its concatenation buffer; the temporary voxel table and the scratch the update made stay with the context
+    assert r["viewer_released"][1] < r["viewer_open"][1] and r["viewer_released"][0] == r["viewer_open"][0] - 3
+    # (c) nothing of the first stereo geometry survives the second
+    assert r["stereo_geom1_then_2"] == r["stereo_geom2_fresh"]
+    assert r["stereo_geom1"][1] > r["stereo_geom1_then_2"][1]
+    assert r["stereo_closed"] == r["stereo_base"]
+    assert r["end"] == [0, 0, 0, 0]                                                 # (d)
+
+
+if __name__ == "__main__":
+    child()
