@@ -1,6 +1,6 @@
 // ssm/rgbdframe.h -- rgbd_tutor::RGBDFrame and FrameReader (reference include/rgbdframe.h:26-186, src/rgbdframe.cpp).
 // RGBDFrame keeps the reference's public field and method names.  Not reproduced: the per-frame imread of an
-// absolute-path color.png in the constructor (rgbdframe.h:29-32) and the DBoW2 bag-of-words vector (loop closure, out of scope).
+// absolute-path color.png in the constructor (rgbdframe.h:29-32).  bowVec is DBoW2::BowVector as a plain std::map (filled by Looper::add, include/ssm/looper.h).
 #pragma once
 #include "common_headers.h"
 #include "device.h"
@@ -10,6 +10,7 @@
 #include "png_io.h"
 #include "stereo.h"
 namespace rgbd_tutor {
+typedef std::map<unsigned, double> BowVector;            // DBoW2::BowVector: word id -> normalised weight
 class RGBDFrame {
 public:
     typedef shared_ptr<RGBDFrame> Ptr;
@@ -26,6 +27,7 @@ public:
     vector<Feature> features;
     CAMERA_INTRINSIC_PARAMETERS camera;
     PointCloud::Ptr pointcloud = nullptr;
+    BowVector bowVec;
 
     // pin-hole unprojection, reference include/rgbdframe.h:63-75 (host copy of the arithmetic the kernels use)
     cv::Point3f project2dTo3d(int u, int v) const {

@@ -318,6 +318,49 @@ int ssm_vo_estimate(ssm_ctx* ctx, const ssm_pmatch* matches, int n, const ssm_vo
 int ssm_pnp_solve(ssm_ctx* ctx, const float* img, const float* obj, int n, const double cam[4], int min_inliers, double T[16],
                   uint8_t* inliers, int* n_inliers, int* success);
 
+/* ---- Looper (reference include/looper.h, src/looper.cpp): the DBoW2 bag-of-words loop detector ------------------------------------------------------
+ * Looper::add is vocab.transform(descriptors, frame->bowVec, ..), Looper::getPossibleLoops is vocab.score(frame, pf) against every stored key-frame with
+ * `score > min_sim_score && abs(pf->id - frame->id) > min_interval`.  DBoW2 is not in the reference tree; DESIGN.md s.10 restates the contract of
+ * TemplatedVocabulary<FORB> as ORB-SLAM2 ships it, and include/ssm/looper_core.h holds the arithmetic (host and device give the same bits).
+ * A VOCABULARY is a host object and needs no GPU.  The text format is DBoW2's saveToTextFile (looper_vocab_file, parameters.txt:91): line 1 `k L scoring
+ * weighting`, then one node per non-blank line `parent isLeaf b0 .. b31 weight`; node ids count from 1 in line order, id 0 is the root; word ids count from
+ * 0 in order of the isLeaf > 0 lines.  0 <= k <= 20, 1 <= L <= 10.  ONLY scoring == 0 (L1_NORM) with weighting == 0 (TF_IDF) -- what ORBvoc.txt uses -- is
+ * supported: anything else, a parent that is not an earlier node, a leaf with children, a non-leaf or a root without children and a malformed line are
+ * SSM_E_INVAL, with the reason in ssm_last_error(NULL).  The FeatureVector (levelsup = 4) that Looper::add computes and drops is not built. */
+typedef struct ssm_vocab ssm_vocab;
+int  ssm_vocab_load_text(const char* path, ssm_vocab** out);
+/* the same from arrays: node i (id i + 1) has parent[i] (an id), is_leaf[i], desc + 32 i, weight[i] */
+int  ssm_vocab_create(int k, int L, int scoring, int weighting, const int32_t* parent, const uint8_t* is_leaf,
+                      const uint8_t* desc, const double* weight, int n_nodes, ssm_vocab** out);
+void ssm_vocab_destroy(ssm_vocab* v);
+int  ssm_vocab_info(const ssm_vocab* v, int32_t info[6]);             /* k, L, nodes incl. the root, words, scoring, weighting */
+/* vocab.transform on the host: word_of_feature (n entries, may be NULL) = the word id of every descriptor; (ids, vals) = the normalised vector in ascending
+ * word id, *n_out entries (more than cap: SSM_E_CAPACITY, *n_out = the count needed) */
+int  ssm_vocab_transform_host(const ssm_vocab* v, const uint8_t* desc, int n, int32_t* word_of_feature,
+                              int32_t* ids, double* vals, int cap, int* n_out);
+/* vocab.score(v1, v2): v1 = the query frame, v2 = the stored frame (the sum runs over v2's entries: looper_core.h) */
+int  ssm_bow_score_host(const int32_t* ids1, const double* v1, int n1, const int32_t* ids2, const double* v2, int n2, double* score);
+/* A LOOPER belongs to a context: the vocabulary tree (re-numbered breadth-first, 32-byte descriptor rows) and the database of the added frames' vectors
+ * (CSR: offsets, word ids, f64 values, frame ids; grows by doubling) live in the context's device memory.  ssm_looper_create uploads and waits: v may be
+ * destroyed afterwards.  Entries are numbered in the order they were added.  A frame holds at most ssm_orb_capacity descriptors (at most 4096). */
+typedef struct ssm_looper ssm_looper;
+int  ssm_looper_create(ssm_ctx* ctx, const ssm_vocab* v, ssm_looper** out);
+void ssm_looper_destroy(ssm_looper* l);
+int  ssm_looper_clear(ssm_looper* l);                                 /* forget every entry (the memory stays) */
+int  ssm_looper_size(const ssm_looper* l);                            /* entries */
+int  ssm_looper_add(ssm_looper* l, const uint8_t* desc, int n, int frame_id);          /* Looper::add of one frame, host descriptors; synchronous */
+/* Looper::add of n_frames frames whose descriptors are on the device: desc_dev (n_frames x cap x 32) / nkp_dev (n_frames) = ssm_seq_out_dev.desc / .nkp as
+ * they are (cap = ssm_orb_capacity); frame_ids: HOST, copied before the call returns.  Enqueued on the context stream, not waited for */
+int  ssm_looper_add_dev(ssm_looper* l, const uint8_t* desc_dev, const int32_t* nkp_dev, int n_frames, int cap, const int32_t* frame_ids);
+int  ssm_looper_bow(ssm_looper* l, int entry, int32_t* ids, double* vals, int cap, int* n_out);     /* an entry's vector */
+/* scores[e] = score(entry, e) for e in [0, against), or for e in [0, entry] when against = -1 */
+int  ssm_looper_scores(ssm_looper* l, int entry, int against, double* scores);
+/* Looper::getPossibleLoops for the query entries [first, first + n): entry q is compared with the entries [0, against), or with 0 .. q when against = -1
+ * (the reference's order: add(frame) directly before getPossibleLoops(frame)).  pairs: cap x 2 (query entry, candidate entry), sorted by (query, candidate);
+ * scores: cap.  More than cap candidates: SSM_E_CAPACITY, *n_out = the count needed.  Waits once, for the download */
+int  ssm_looper_query(ssm_looper* l, int first, int n, int against, double min_sim_score, int min_interval,
+                      int32_t* pairs, double* scores, int cap, int* n_out);
+
 /* ---- device-resident batched stereo path (BASELINE.json configs[3]): n frames of a rectified stereo sequence, all DEVICE pointers.
  * The reference walks the KITTI sequence one frame at a time: FrameReader::next() computes the depth of the current pair with SGBM
  * (src/rgbdframe.cpp:64-116, src/stereo.cpp:11-30), Tracker::estimateVO builds a QuadFeatureMatch on (current left, current right, previous left,

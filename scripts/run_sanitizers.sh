@@ -1,7 +1,8 @@
 #!/bin/bash
 # CPU sanitizer runs of the oracle and of the host layer (SURVEY.md s.5 "race detection"; no GPU involved).  Usage: bash scripts/run_sanitizers.sh [logfile]
 # oracle: san_check.c over every stage + the pipeline entry point on four threads.  host: test_png (PNG decoder), test_pnp (PnPSolver / pnp_core.h on the
-# committed golden case files), test_threads (PoseGraph + Mapper::viewer + a polling thread; device calls -> san_stub_device.cpp).
+# committed golden case files), test_threads (PoseGraph + Mapper::viewer + a polling thread; device calls -> san_stub_device.cpp), test_looper (rgbd_tutor::Looper on
+# its host path + the library's vocabulary code, csrc/ssm_vocab.inc, compiled into the stub).
 # Every step's OWN exit status decides (no status of a `tail` / `grep` behind a pipe): a failed build, a missing binary, a non-zero exit or a sanitizer
 # report anywhere in the full, un-tailed output makes the run fail; the log keeps the complete output of failing steps and the tail of passing ones.
 set -u
@@ -26,6 +27,8 @@ sys.path.insert(0, os.path.join(root, "tests"))
 from test_host_cpp import _write_png_set
 os.makedirs(os.path.join(d, "png"), exist_ok=True)
 _write_png_set(os.path.join(d, "png"))
+import looper_ref
+looper_ref.write_vocab_text(os.path.join(d, "looper_vocab.txt"), *looper_ref.make_vocab(10, 3, 11))
 PY
 fail=0
 MARK="ThreadSanitizer|ERROR: AddressSanitizer|runtime error:|LeakSanitizer|AddressSanitizer:|UndefinedBehaviorSanitizer"
@@ -47,11 +50,12 @@ step() {
     step "oracle build + run ($s)" make -s -C "$ROOT/oracle" SAN=$s san
     echo "## host SAN=$s"
     step "host build ($s)" make -s -C "$HOST" SAN=$s san
-    for b in test_png_$s test_pnp_$s test_threads_$s; do [ -x "$HOST/$b" ] || { echo "### $b: MISSING BINARY"; fail=1; }; done
+    for b in test_png_$s test_pnp_$s test_threads_$s test_looper_$s; do [ -x "$HOST/$b" ] || { echo "### $b: MISSING BINARY"; fail=1; }; done
     [ -x "$HOST/test_png_$s" ] && step "test_png_$s" "$HOST/test_png_$s" "$TMP/png"
     for c in outliers nodepth lanes; do
       [ -x "$HOST/test_pnp_$s" ] && step "test_pnp_$s $c" "$HOST/test_pnp_$s" "$HOST/parameters_test.txt" "$TMP/$c.bin" "$TMP/$c.out"
     done
+    [ -x "$HOST/test_looper_$s" ] && step "test_looper_$s" "$HOST/test_looper_$s" "$TMP" "$TMP/looper_vocab.txt"
     [ -x "$HOST/test_threads_$s" ] && step "test_threads_$s" "$HOST/test_threads_$s" "$HOST/parameters_test.txt"
   done
   echo "## result: $([ $fail = 0 ] && echo CLEAN || echo FINDINGS)"

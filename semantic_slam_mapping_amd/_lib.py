@@ -124,6 +124,21 @@ SYMBOLS = {
     "ssm_stereo_depth": (_I, [_P, _P, _P, _I, _I, _I, _P] + [_D] * 8 + [_P, _P]),
     "ssm_vo_estimate": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
     "ssm_pnp_solve": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "ssm_vocab_load_text": (_I, [C.c_char_p, C.POINTER(_P)]),
+    "ssm_vocab_create": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, C.POINTER(_P)]),
+    "ssm_vocab_destroy": (None, [_P]),
+    "ssm_vocab_info": (_I, [_P, C.POINTER(C.c_int32 * 6)]),
+    "ssm_vocab_transform_host": (_I, [_P, _P, _I, _P, _P, _P, _I, C.POINTER(_I)]),
+    "ssm_bow_score_host": (_I, [_P, _P, _I, _P, _P, _I, C.POINTER(_D)]),
+    "ssm_looper_create": (_I, [_P, _P, C.POINTER(_P)]),
+    "ssm_looper_destroy": (None, [_P]),
+    "ssm_looper_clear": (_I, [_P]),
+    "ssm_looper_size": (_I, [_P]),
+    "ssm_looper_add": (_I, [_P, _P, _I, _I]),
+    "ssm_looper_add_dev": (_I, [_P, _P, _P, _I, _I, _P]),
+    "ssm_looper_bow": (_I, [_P, _I, _P, _P, _I, C.POINTER(_I)]),
+    "ssm_looper_scores": (_I, [_P, _I, _I, _P]),
+    "ssm_looper_query": (_I, [_P, _I, _I, _I, _D, _I, _P, _P, _I, C.POINTER(_I)]),
     "ssm_segnet_num_layers": (_I, []),
     "ssm_segnet_layer_shape": (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ssm_segnet_set_layer": (_I, [_P, _I, _P, _P, _P]),

@@ -159,6 +159,132 @@ class Tracker:
             pass
 
 
+class Vocabulary:
+    """ssm_vocab: a DBoW2 TemplatedVocabulary<FORB> (L1_NORM / TF_IDF), a host object that needs no GPU.  Vocabulary(path) loads DBoW2's text format;
+    Vocabulary.from_arrays(k, L, parent, is_leaf, desc, weight) builds one from the per-node arrays (node i has id i + 1, id 0 is the root)."""
+
+    def __init__(self, path=None, _handle=None):
+        self.lib = _lib.load()
+        if _handle is None:
+            h = C.c_void_p()
+            rc = self.lib.ssm_vocab_load_text(str(path).encode(), C.byref(h))
+            if rc != 0:
+                raise SsmError(rc, (self.lib.ssm_last_error(None) or b"").decode())
+            _handle = h
+        self.h = _handle
+        info = (C.c_int32 * 6)()
+        self.lib.ssm_vocab_info(self.h, C.byref(info))
+        self.k, self.L, self.nodes, self.words, self.scoring, self.weighting = (int(x) for x in info)
+
+    @classmethod
+    def from_arrays(cls, k, L, parent, is_leaf, desc, weight, scoring=0, weighting=0):
+        lib = _lib.load()
+        parent = np.ascontiguousarray(parent, np.int32); is_leaf = np.ascontiguousarray(is_leaf, np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32); weight = np.ascontiguousarray(weight, np.float64)
+        assert len(parent) == len(is_leaf) == len(desc) == len(weight)
+        h = C.c_void_p()
+        rc = lib.ssm_vocab_create(k, L, scoring, weighting, _ptr(parent), _ptr(is_leaf), _ptr(desc), _ptr(weight), len(parent), C.byref(h))
+        if rc != 0:
+            raise SsmError(rc, (lib.ssm_last_error(None) or b"").decode())
+        return cls(_handle=h)
+
+    def transform(self, desc, cap=None):
+        """vocab.transform on the host -> (word id of every feature, vector ids, vector values)"""
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        n = len(desc); cap = n if cap is None else cap
+        wof = np.zeros(max(n, 1), np.int32); ids = np.zeros(max(cap, 1), np.int32); vals = np.zeros(max(cap, 1), np.float64); m = C.c_int(0)
+        rc = self.lib.ssm_vocab_transform_host(self.h, _ptr(desc), n, _ptr(wof), _ptr(ids), _ptr(vals), cap, C.byref(m))
+        if rc != 0:
+            e = SsmError(rc, "ssm_vocab_transform_host"); e.needed = m.value
+            raise e
+        return wof[:n], ids[:m.value].copy(), vals[:m.value].copy()
+
+    def score(self, ids1, v1, ids2, v2):
+        """vocab.score(v1, v2) on the host: v1 the query frame, v2 the stored frame"""
+        ids1 = np.ascontiguousarray(ids1, np.int32); v1 = np.ascontiguousarray(v1, np.float64); ids2 = np.ascontiguousarray(ids2, np.int32); v2 = np.ascontiguousarray(v2, np.float64)
+        s = C.c_double(0)
+        rc = self.lib.ssm_bow_score_host(_ptr(ids1), _ptr(v1), len(ids1), _ptr(ids2), _ptr(v2), len(ids2), C.byref(s))
+        if rc != 0:
+            raise SsmError(rc, "ssm_bow_score_host")
+        return s.value
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.ssm_vocab_destroy(self.h); self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Looper:
+    """ssm_looper: rgbd_tutor::Looper on the device -- the vocabulary tree and the database of the added frames' bag-of-words vectors live in the context's
+    device memory.  add = Looper::add of one frame, add_dev the same for the frames of a seq_process call, query = Looper::getPossibleLoops in bulk."""
+
+    def __init__(self, ctx, vocab):
+        self.ctx = ctx; self.lib = ctx.lib
+        h = C.c_void_p()
+        ctx._chk(self.lib.ssm_looper_create(ctx.h, vocab.h, C.byref(h)))
+        self.h = h
+
+    def __len__(self):
+        return self.lib.ssm_looper_size(self.h)
+
+    def clear(self):
+        self.ctx._chk(self.lib.ssm_looper_clear(self.h))
+
+    def add(self, desc, frame_id):
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        self.ctx._chk(self.lib.ssm_looper_add(self.h, _ptr(desc), len(desc), int(frame_id)))
+
+    def add_dev(self, seq_out, n, frame_ids):
+        """the n frames of a seq_process output (device descriptors and counts as they are); enqueued, not waited for"""
+        ids = np.ascontiguousarray(frame_ids, np.int32)
+        assert len(ids) == n
+        self.ctx._chk(self.lib.ssm_looper_add_dev(self.h, seq_out.desc, seq_out.nkp, n, seq_out.cap, _ptr(ids)))
+
+    def bow(self, entry, cap=None):
+        cap = self.ctx.cap if cap is None else cap
+        ids = np.zeros(max(cap, 1), np.int32); vals = np.zeros(max(cap, 1), np.float64); m = C.c_int(0)
+        self.ctx._chk(self.lib.ssm_looper_bow(self.h, entry, _ptr(ids), _ptr(vals), cap, C.byref(m)))
+        return ids[:m.value].copy(), vals[:m.value].copy()
+
+    def scores(self, entry, against=-1):
+        out = np.zeros(max(entry + 1 if against < 0 else against, 1), np.float64)
+        self.ctx._chk(self.lib.ssm_looper_scores(self.h, entry, against, _ptr(out)))
+        return out[:entry + 1 if against < 0 else against]
+
+    def query(self, first, n, min_sim_score, min_interval, against=-1, cap=None):
+        """-> (pairs m x 2 [query entry, candidate entry], scores m), sorted by (query, candidate).  cap=None: retried once with the count the library reports"""
+        auto = cap is None
+        cap = 4096 if auto else cap
+        while True:
+            pairs = np.zeros((max(cap, 1), 2), np.int32); sc = np.zeros(max(cap, 1), np.float64); m = C.c_int(0)
+            rc = self.lib.ssm_looper_query(self.h, first, n, against, float(min_sim_score), int(min_interval), _ptr(pairs), _ptr(sc), cap, C.byref(m))
+            if rc == -4 and auto and m.value > cap:
+                cap = m.value
+                continue
+            if rc != 0:
+                e = SsmError(rc, (self.lib.ssm_last_error(self.ctx.h) or b"").decode()); e.needed = m.value
+                raise e
+            return pairs[:m.value].copy(), sc[:m.value].copy()
+
+    def close(self):
+        """before the context's close(): a looper that outlives its context is dropped without a call into it"""
+        if getattr(self, "h", None):
+            if self.ctx.h:
+                self.lib.ssm_looper_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Context:
     """One ssm_ctx: device workspace + stream on one GPU."""
 

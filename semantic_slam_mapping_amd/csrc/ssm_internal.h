@@ -224,6 +224,19 @@ hipError_t k_quad_track(const QuadBatch& q, int nb, float* pts, int stride, cons
 hipError_t k_quad_window_match(const float* kp1, const uint8_t* d1, int n1, const float* kp2, const uint8_t* d2, int n2, int sw, int sh, float thr,
                                ssm_dmatch* out, hipStream_t s);
 
+// looper (kernels_bow.hip): words of nframes x cap descriptors (frame f has nkp[f] of them, or n_fixed when nkp is null), the vector of each frame into a staging
+// area (cap entries per frame), the append to the CSR database, the score rows of nq query entries and their candidates in (query, entry) order
+namespace ssm_bow { struct Tree; }
+hipError_t k_bow_words(const ssm_bow::Tree& t, const uint8_t* desc, const int32_t* nkp, int n_fixed, int nframes, int cap, int32_t* words, int variant /* 0: 16 lanes per descriptor, 1: one */, hipStream_t s);
+size_t k_bow_frame_lds(int P);
+hipError_t k_bow_frame(const int32_t* words, const double* weight, const int32_t* nkp, int n_fixed, int nframes, int cap, int P /* power of two >= cap, <= 4096 */, int32_t* st_ids, double* st_vals, int32_t* st_m, hipStream_t s);
+hipError_t k_bow_append(const int32_t* st_ids, const double* st_vals, const int32_t* st_m, int nframes, int cap, int32_t* offsets, int e0, int32_t* db_ids, double* db_vals, long long db_cap, int32_t* hdr, hipStream_t s);
+size_t k_bow_score_lds(int qcap);
+hipError_t k_bow_score(const int32_t* offsets, const int32_t* db_ids, const double* db_vals, const int32_t* frame_ids, int first, int nq, int against, int row, int qcap,
+                       double min_score, int min_interval, double* scores, int32_t* counts, hipStream_t s);
+hipError_t k_bow_emit(const int32_t* frame_ids, const double* scores, const int32_t* counts, int first, int nq, int against, int row, double min_score, int min_interval,
+                      int32_t* pairs, double* out_scores, int cap, int32_t* hdr /* [1] = the candidate count */, hipStream_t s);
+
 // for the translation units that only use the public ABI (ssm_track.hip): the configuration a context was created with
 void ssm_internal_get_config(const ssm_ctx* c, ssm_config* out);
 int ssm_internal_get_device(const ssm_ctx* c);      // the HIP device the context lives on: raw HIP calls of another translation unit select it first

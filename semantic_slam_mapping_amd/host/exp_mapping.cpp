@@ -8,6 +8,11 @@
 // BatchTracker runs ORB + the match tables for a whole chunk in batched launches and then the Tracker state machine + PnP over it (ssm_tracker_run:
 // the poses of the per-frame Tracker, bit for bit), after which the chunk's frames go through tryInsertKeyFrame like in the per-frame loop.
 //
+// `exp_mapping <parameters> --loops` (or looper=1): every key-frame goes through Looper::add and Looper::getPossibleLoops (include/ssm/looper.h; the vocabulary is
+// looper_vocab_file) right after tryInsertKeyFrame accepted it; with --batched the key-frames of a chunk are added in bulk from the chunk's device descriptors and
+// queried in one call (BatchLooper).  The summary line then ends with `loop_candidates N loop_fnv H` (FNV-1a over frame id, candidate id and the score's bytes, in
+// order: the same in both modes); loops_output=<file> gets one line per candidate.  Without the flag nothing of this runs and no output changes.
+//
 // `exp_mapping <parameters> --ranks N`: the multi-GPU form (BASELINE.json configs[4]; the reference is one process).  The parent starts
 // N FRESH processes of itself (`--rank r`, fork + exec of /proc/self/exe) before anything touches HIP -- a forked copy of a process whose HIP / RCCL
 // static constructors have already run is not a state either library is tested in; rank r drives GPU r, owns the contiguous frame block [lo, hi) of
@@ -24,6 +29,7 @@
 #include "ssm/vo_stereo.hpp"
 #include "ssm/batch_stereo_tracker.h"
 #include "ssm/batch_tracker.h"
+#include "ssm/looper.h"
 #include <signal.h>
 #include <sys/stat.h>
 #include <sys/wait.h>
@@ -51,12 +57,26 @@ struct Trajectory {
     }
 };
 
+// the loop candidates in the order they were found: count, FNV-1a over (frame id, candidate id, score), and with loops_output=<file> one text line each
+struct LoopLog {
+    uint64_t h = 0xCBF29CE484222325ull; long n = 0; ofstream out;
+    explicit LoopLog(const string& path) { if (!path.empty()) out.open(path); }
+    void add(int32_t frame_id, int32_t cand_id, double score) {
+        unsigned char b[16]; memcpy(b, &frame_id, 4); memcpy(b + 4, &cand_id, 4); memcpy(b + 8, &score, 8);
+        for (int k = 0; k < 16; k++) { h ^= b[k]; h *= 0x100000001B3ull; }
+        n++;
+        if (out.is_open()) { char buf[64]; snprintf(buf, sizeof(buf), " %a", score); out << frame_id << " " << cand_id << buf << "\n"; }
+    }
+};
+
 int main(int argc, char** argv)
 {
     ParameterReader parameterReader(argc > 1 ? argv[1] : "./parameters.txt");
     int nranks = 1, my_rank = -1; string id_dir;
     bool batched = parameterReader.getData<int>("tracker_batched", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--batched") batched = true;
+    bool loops = parameterReader.getData<int>("looper", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--loops") loops = true;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
         if (string(argv[i]) == "--rank") my_rank = atoi(argv[i + 1]);
@@ -131,6 +151,8 @@ int main(int argc, char** argv)
         int nframes = 0;
         const int frame_period_ms = parameterReader.getData<int>("frame_period_ms", 0);
         Trajectory traj(parameterReader.getData<string>("trajectory_output", string("")));
+        LoopLog loop_log(loops ? parameterReader.getData<string>("loops_output", string("")) : string(""));
+        if (loops && batched_stereo) cerr << "exp_mapping: --loops needs ORB descriptors; the bulk stereo tracker computes none (ignored)" << endl;
         // `sequence_length` = L > 0: the stream is a concatenation of independent sequences of L frames (synthetic_rigid streams): the tracker starts over at every
         // multiple of L.  `timing_skip_frames`: the rates printed at the end leave out the first frames (context creation, code-object load, first-use allocations).
         const int seq_len = parameterReader.getData<int>("sequence_length", 0), skip = parameterReader.getData<int>("timing_skip_frames", 0);
@@ -154,19 +176,25 @@ int main(int argc, char** argv)
             return f; };
         if (batched && parameterReader.getData<string>("tracker_mode", string("rgbd")) == "rgbd") {
             unique_ptr<BatchTracker> bt; map<int, Eigen::Isometry3d> gt; int lost = 0; int pushed = 0;
+            unique_ptr<BatchLooper> bl;                        // (after bt: it lives in the tracker's context and goes first)
             const bool chain = parameterReader.getData<int>("tracker_batched_chain", 1) != 0;
             if (!chain && !use_gt_pose) throw invalid_argument("tracker_batched_chain=0 needs use_stream_pose=1: without the chain nothing computes the poses");
             // (rates: a chunk counts as a whole -- the frames of a flush that started at or after timing_skip_frames, against the time of that flush)
             auto handle = [&](const vector<RGBDFrame::Ptr>& done, bool counted) {
+                vector<int> picked;                            // the chunk's key-frames
                 for (size_t i = 0; i < done.size(); i++) {
                     const RGBDFrame::Ptr& f = done[i];
                     if (use_gt_pose) f->setTransform(gt[f->id]);
                     gt.erase(f->id);
                     traj.add(f);
-                    poseGraph.tryInsertKeyFrame(const_cast<RGBDFrame::Ptr&>(f));
+                    if (poseGraph.tryInsertKeyFrame(const_cast<RGBDFrame::Ptr&>(f))) picked.push_back((int)i);
                     if (bt->infos[i].state == Tracker::LOST) { cout << "tracker is lost" << endl; lost++; }
                     if (counted) timed++;
                     nframes++;
+                }
+                if (loops && !picked.empty()) {
+                    if (!bl) bl.reset(new BatchLooper(parameterReader, bt->device()));
+                    for (const BatchLooper::Candidate& c : bl->addChunk(bt->last_out, done, picked)) loop_log.add(c.frame->id, c.loop->id, c.score);
                 }
             };
             while (RGBDFrame::Ptr frame = read_next()) {
@@ -210,6 +238,7 @@ int main(int argc, char** argv)
             t1 = now();
             cout << "batched stereo tracker: chunk " << (bs ? bs->chunk() : 0) << " lost " << lost << endl;
         } else {
+        unique_ptr<Looper> looper; if (loops) looper.reset(new Looper(parameterReader));
         while (RGBDFrame::Ptr frame = read_next()) {
             if (nframes == skip) { t_timed0 = now(); tracker->timing = Tracker::Timing(); }
             if (seq_len > 0 && nframes > 0 && nframes % seq_len == 0) tracker->reset();
@@ -219,7 +248,11 @@ int main(int argc, char** argv)
             const tp b = now();
             if (use_gt_pose) frame->setTransform(gt);           // synthetic stream: poses are given, the tracker only produces features/matches
             traj.add(frame);
-            poseGraph.tryInsertKeyFrame(frame);
+            if (poseGraph.tryInsertKeyFrame(frame) && looper) {
+                looper->add(frame);
+                looper->getPossibleLoops(frame);
+                for (int i : looper->last_indices) loop_log.add(frame->id, looper->frameAt(i)->id, looper->last_scores[i]);
+            }
             if (nframes >= skip) { track_s += sec(a, b); kf_s += sec(b, now()); timed++; }
             if (tracker->getState() == Tracker::LOST) cout << "tracker is lost" << endl;
             nframes++;
@@ -258,6 +291,7 @@ int main(int argc, char** argv)
             for (int i = 0; i < nvox; i++) { const unsigned char* b = (const unsigned char*)&m[i]; for (int k = 0; k < 24; k++) { h ^= b[k]; h *= 0x100000001B3ull; } }
             cout << " map_voxels " << nvox << " map_fnv " << hex << h << dec;
         }
+        if (loops) cout << " loop_candidates " << loop_log.n << " loop_fnv " << hex << loop_log.h << dec;
         cout << endl;
     } catch (const exception& e) { cerr << RED << "exp_mapping: " << e.what() << RESET << endl; return 2; }
     return 0;

@@ -5,17 +5,29 @@
 // returns are placeholders.  It is linked into test_threads / test_pnp / test_png of a SAN build ONLY -- never into exp_mapping or the library.
 #include "ssm_hip.h"
 #include "ssm/pnp_core.h"
+#include "ssm/looper_core.h"
 #include <cstring>
 #include <string>
 #include <vector>
 struct ssm_ctx { ssm_config cfg; std::string err; };
+// the looper's vocabulary is host code: the library's own implementation runs under the sanitizers (test_looper).  The device looper is never reached there
+// (Looper takes the host path on a thread without a context); its entry points only have to link
+static thread_local std::string g_vocab_err;
+static int vocab_fail(const std::string& msg) { g_vocab_err = msg; return SSM_E_INVAL; }
+#include "../csrc/ssm_vocab.inc"
 extern "C" {
+int ssm_looper_create(ssm_ctx*, const ssm_vocab*, ssm_looper**) { return SSM_E_NODEVICE; }
+void ssm_looper_destroy(ssm_looper*) {}
+int ssm_looper_size(const ssm_looper*) { return 0; }
+int ssm_looper_add(ssm_looper*, const uint8_t*, int, int) { return SSM_E_NODEVICE; }
+int ssm_looper_bow(ssm_looper*, int, int32_t*, double*, int, int*) { return SSM_E_NODEVICE; }
+int ssm_looper_scores(ssm_looper*, int, int, double*) { return SSM_E_NODEVICE; }
 void ssm_config_default(ssm_config* c) { memset(c, 0, sizeof(*c)); c->width = 640; c->height = 480; c->orb_features = 1000; c->orb_scale = 1.2f; c->orb_levels = 8;
     c->orb_iniThFAST = 20; c->orb_minThFAST = 7; c->knn_match_ratio = 0.8; c->tracker_ref_frames = 5; c->mapper_resolution = 0.1; c->mapper_max_distance = 40;
     c->camera.cx = 318.6; c->camera.cy = 255.3; c->camera.fx = 517.3; c->camera.fy = 516.5; c->camera.scale = 1000.0; c->max_batch = 1; c->voxel_capacity_log2 = 16; }
 int ssm_create(int, const ssm_config* cfg, ssm_ctx** out) { *out = new ssm_ctx(); (*out)->cfg = *cfg; return SSM_OK; }
 void ssm_destroy(ssm_ctx* c) { delete c; }
-const char* ssm_last_error(const ssm_ctx* c) { return c ? c->err.c_str() : "stub"; }
+const char* ssm_last_error(const ssm_ctx* c) { return c ? c->err.c_str() : (g_vocab_err.empty() ? "stub" : g_vocab_err.c_str()); }
 int ssm_orb_capacity(const ssm_ctx*) { return 1024; }
 int ssm_backproject(ssm_ctx*, const uint16_t* depth, const uint8_t* rgb, const uint8_t*, int w, int h, const ssm_camera*, const double*, double, ssm_point* out, int cap, int* n_out)
 {
