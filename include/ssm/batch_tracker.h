@@ -46,7 +46,8 @@ public:
     vector<RGBDFrame::Ptr> flush() {
         const int n = (int)pending.size();
         if (n == 0) return vector<RGBDFrame::Ptr>();
-        ssm_frames_dev in;                                 // (the images were uploaded by push(), on the context's stream: the launches below run behind the copies) memset(&in, 0, sizeof(in));
+        // (the images were uploaded by push(), on the context's stream: the launches below run behind the copies)
+        ssm_frames_dev in = {};
         in.bgr = (const uint8_t*)d_bgr; in.depth = (const uint16_t*)d_depth; in.n = n; in.continue_sequence = fed > 0 ? 1 : 0; in.stages = SSM_STAGE_ORB | SSM_STAGE_MATCH;
         ssm_seq_out_dev out;
         dev->check(ssm_seq_process(dev->ctx(), &in, &out), "ssm_seq_process");

@@ -455,10 +455,13 @@ int ssm_debug_pyramid_plan(const ssm_config* cfg, int bands, int32_t* items, int
  * op bit 0 = medianBlur 3x3 (replicate border), bit 1 = filterSpeckles (4-neighbours, both != new_val, |a - b| <= max_diff; components of at most
  * max_size pixels become new_val) on the median's output, or on the input without bit 0.  For exact tests of the kernels on constructed maps */
 int ssm_debug_sgbm_post(ssm_ctx* ctx, const int16_t* disp, int w, int h, int n, int op, int new_val, int max_size, int max_diff, int16_t* out);
-/* what the library itself holds at this moment, process-wide (every context, tracker and per-stream cache): live buffers, their device bytes and their
+/* what the library itself holds at this moment, process-wide (every context with its lanes, every tracker): live buffers, their device bytes and their
  * page-locked host bytes, each as asked for.  Memory handed to the caller (ssm_dev_alloc, ssm_host_alloc) is not counted.  Any pointer may be NULL.  For
  * tests of ownership: exact, unlike the device's free memory, which moves with other processes */
 void ssm_debug_live_allocations(int* buffers, size_t* device_bytes, size_t* pinned_bytes);
+/* likewise the streams and events the library itself holds (contexts with their side lanes and SGBM fans, the profiling pool, trackers with a stream of
+ * their own): every one is a Stream / Event of csrc/ssm_ctx.h.  Either pointer may be NULL */
+void ssm_debug_live_handles(int* streams, int* events);
 /* class logits (12 floats per net pixel, 360*480 pixels) of frame 0 of the most recent forward: for tolerance tests */
 int ssm_segnet_logits(ssm_ctx* ctx, float* out);
 

@@ -18,6 +18,9 @@ int main(int argc, char** argv)
     std::mt19937 rng(1);
     std::uniform_real_distribution<float> ud(-1.f, 1.f);
     double tot_us = 0, tot_fl = 0;
+    DeviceInfo dev; int* tiles;                                   // what a context hands the conv launchers: the CU count and a stream's zeroed tile counters
+    { int cus = 0; if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, 0) == hipSuccess && cus > 0) dev.cus = cus; }
+    CK(hipMalloc(&tiles, CONV_QUEUE_INTS * sizeof(int))); CK(hipMemset(tiles, 0, CONV_QUEUE_INTS * sizeof(int)));
     for (const Shape& sh : shapes) {
         const size_t na = (size_t)n * sh.H * sh.W * sh.Cin, nw = (size_t)sh.Cout * sh.Cin * 9, no = (size_t)n * sh.H * sh.W * sh.Cout;
         std::vector<_Float16> ha(na), hw(nw);
@@ -30,9 +33,9 @@ int main(int argc, char** argv)
         CK(hipMemcpy(dsc, sc.data(), sh.Cout * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(dsf, sf.data(), sh.Cout * 4, hipMemcpyHostToDevice));
         hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
         CK(hipMemset(dout, 0xFF, no * 2));
-        for (int i = 0; i < 2; i++) CK(k_segnet_conv(da, dw, dsc, dsf, dout, n, sh.H, sh.W, sh.Cin, sh.Cout, 1, 0));
+        for (int i = 0; i < 2; i++) CK(k_segnet_conv(da, dw, dsc, dsf, dout, n, sh.H, sh.W, sh.Cin, sh.Cout, 1, dev, tiles, 0));
         CK(hipEventRecord(e0, 0));
-        for (int i = 0; i < reps; i++) CK(k_segnet_conv(da, dw, dsc, dsf, dout, n, sh.H, sh.W, sh.Cin, sh.Cout, 1, 0));
+        for (int i = 0; i < reps; i++) CK(k_segnet_conv(da, dw, dsc, dsf, dout, n, sh.H, sh.W, sh.Cin, sh.Cout, 1, dev, tiles, 0));
         CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
         float ms; CK(hipEventElapsedTime(&ms, e0, e1));
         const double us = ms * 1e3 / reps, fl = 2.0 * n * sh.H * sh.W * (double)sh.Cin * sh.Cout * 9;
@@ -41,7 +44,7 @@ int main(int argc, char** argv)
         {   // one more launch with the block-lifetime counter: MFMA utilisation in shader clocks, independent of the clock the chip holds
             unsigned long long zero = 0, cyc = 0;
             CK(hipMemcpyToSymbol(HIP_SYMBOL(g_conv_cycles), &zero, 8));
-            CK(k_segnet_conv(da, dw, dsc, dsf, dout, n, sh.H, sh.W, sh.Cin, sh.Cout, 1, 0));
+            CK(k_segnet_conv(da, dw, dsc, dsf, dout, n, sh.H, sh.W, sh.Cin, sh.Cout, 1, dev, tiles, 0));
             CK(hipDeviceSynchronize());
             CK(hipMemcpyFromSymbol(&cyc, HIP_SYMBOL(g_conv_cycles), 8));
             if (cyc) { util = fl / (double)cyc / 1048576.0; ghz = (double)cyc / us * 1e-3; }

@@ -96,6 +96,13 @@ def live_allocations():
     return n.value, d.value, p.value
 
 
+def live_handles():
+    """(streams, events) the library itself holds right now, process-wide: ssm_debug_live_handles"""
+    s, e = C.c_int(0), C.c_int(0)
+    _lib.load().ssm_debug_live_handles(C.byref(s), C.byref(e))
+    return s.value, e.value
+
+
 def _ptr(a):
     return a.ctypes.data if a is not None else None
 

@@ -4,7 +4,6 @@
 //   K12 pcl::VoxelGrid in Mapper::viewer /root/reference/src/mapper.cpp:106-107,154-155
 // Contracts = oracle/mapper.c.  Batched over frames.
 #include "ssm_internal.h"
-#include <mutex>
 #include <cstring>
 #include <cmath>
 
@@ -487,7 +486,6 @@ __device__ __forceinline__ void wave_flush(LdsVox* lt, long long key, uint32_t l
 // 5 f64 instructions instead of ~11 per division; f64 runs at half rate, and these were a quarter of the kernel's f64 work.
 // Checked exhaustively on the CPU for the cameras of the tests and benches (all 16-bit depths x 1300 columns x 500 rows: 7e8
 // divisions, no mismatch) and by tests/test_gpu_parity.py against the division-based ordered path (bp_emit_kernel).
-struct MapDiv { double rscale, rfx, rfy; };
 __device__ __forceinline__ double markstein_div(double n, double f, double r)
 {
     double q = n * r;
@@ -756,26 +754,22 @@ map_stream2_kernel(const uint16_t* __restrict__ depth, const uint8_t* __restrict
     }
     if (tid == 0 && s_npts) atomicAdd(&npoints[by], s_npts);
 }
-// MapDiv for a camera (see the struct): the reciprocal form when the divisors allow it; the check is cached per camera
-static bool map_div_for(const ssm_camera& cam, MapDiv& md)
+// MapDiv for a camera (see markstein_div): true when the divisors allow the reciprocal form.  Every depth value goes through the same arithmetic on the host, so
+// the caller asks once per camera (ssm_abi.hip ctx_init) and hands the answer to k_map_fuse.
+bool k_map_div(const ssm_camera& cam, MapDiv& md)
 {
-    static std::mutex mu; static ssm_camera seen = {0, 0, 0, 0, 0}; static bool seen_ok = false;
     md.rscale = 1.0 / cam.scale; md.rfx = 1.0 / cam.fx; md.rfy = 1.0 / cam.fy;
-    std::lock_guard<std::mutex> lk(mu);
-    if (seen.scale != cam.scale || seen.fx != cam.fx || seen.fy != cam.fy) {
-        auto plain = [](double f) {                       // normal, positive, significand not all ones
-            uint64_t b; memcpy(&b, &f, 8);
-            const uint64_t man = b & 0xFFFFFFFFFFFFFull; const int ex = (int)((b >> 52) & 0x7FF);
-            return f > 0 && ex > 0 && ex < 0x7FF && man != 0xFFFFFFFFFFFFFull;
-        };
-        bool ok = plain(cam.scale) && plain(cam.fx) && plain(cam.fy);
-        for (int d = 0; d < 65536 && ok; d++) {           // every depth value through the same arithmetic on the host
-            double q = (double)d * md.rscale; q = std::fma(std::fma(-q, cam.scale, (double)d), md.rscale, q); q = std::fma(std::fma(-q, cam.scale, (double)d), md.rscale, q);
-            if (q != (double)d / cam.scale) ok = false;
-        }
-        seen = cam; seen_ok = ok;
+    auto plain = [](double f) {                       // normal, positive, significand not all ones
+        uint64_t b; memcpy(&b, &f, 8);
+        const uint64_t man = b & 0xFFFFFFFFFFFFFull; const int ex = (int)((b >> 52) & 0x7FF);
+        return f > 0 && ex > 0 && ex < 0x7FF && man != 0xFFFFFFFFFFFFFull;
+    };
+    bool ok = plain(cam.scale) && plain(cam.fx) && plain(cam.fy);
+    for (int d = 0; d < 65536 && ok; d++) {
+        double q = (double)d * md.rscale; q = std::fma(std::fma(-q, cam.scale, (double)d), md.rscale, q); q = std::fma(std::fma(-q, cam.scale, (double)d), md.rscale, q);
+        if (q != (double)d / cam.scale) ok = false;
     }
-    return seen_ok;
+    return ok;
 }
 int k_map_fuse_blocks_per_frame(int w, int h) { const int words = (w >> 4) * h; return (words + 256 * MS_CH - 1) / (256 * MS_CH); }
 int k_map_fuse_block_records(void) { return MS_CH * 4096; }            // overflow records one block can append at most: one per pixel
@@ -784,13 +778,12 @@ int k_map_fuse_skip_cap(void) { return MS2_SKIP_CAP; }
 // n frames of w x h (w % 16 == 0, w <= 4096).  skip / hw / tag: see map_stream2_kernel (skip = the context's skip list, MS2_SKIP_CAP entries; counters[6] counts them).
 // nredo > 0: run exactly the blocks redo_ids[0 .. nredo) (device) of an earlier launch with these arguments again (its per-frame point counts go on counting).
 hipError_t k_map_fuse(const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const double* pose, int n, int w, int h,
-                      ssm_camera cam, double max_distance, float leaf,
+                      ssm_camera cam, const MapDiv& md, bool fast, double max_distance, float leaf,
                       ssm_voxel* tab, int cap_log2, int32_t* counters, int32_t* npoints, hipStream_t s, int32_t* skip, int hw, int tag, const int32_t* redo_ids, int nredo)
 {
     const int wpr = w >> 4, words = wpr * h;
     if (!((long long)words * wpr < (1ll << 32) && wpr <= 256)) return hipErrorInvalidValue;      // frames wider than 4096 pixels: not supported by the fused map stage
     if (nredo <= 0) { const hipError_t e = hipMemsetAsync(npoints, 0, sizeof(int32_t) * n, s); if (e != hipSuccess) return e; }
-    MapDiv md; const bool fast = map_div_for(cam, md);
     const int gx = (words + 256 * MS_CH - 1) / (256 * MS_CH);
     const dim3 grid(gx, n);
     const uint32_t mul_wpr = (uint32_t)(((1ull << 32) + wpr - 1) / wpr);           // floor(i / wpr) = umulhi(i, mul) for i < words (i * wpr < 2^32)

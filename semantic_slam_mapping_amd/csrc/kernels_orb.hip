@@ -7,8 +7,6 @@
 #include <type_traits>
 #include <algorithm>
 #include <cstring>
-#include <mutex>
-#include <set>
 #include <vector>
 
 #define WAVE 64
@@ -410,17 +408,6 @@ resize4_kernel_bands(const uint8_t* __restrict__ img, uint8_t* __restrict__ pyr,
         __syncthreads();
     }
 }
-static hipError_t pb_allow_lds(const void* fn, size_t bytes)
-{
-    if (bytes <= 48 * 1024) return hipSuccess;
-    static std::mutex mu; static std::set<std::pair<int, const void*>> done;
-    int dev = 0; (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.count({dev, fn})) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, PB_MAX_LDS);
-    if (e == hipSuccess) done.insert({dev, fn});
-    return e;
-}
 hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeom& g, uint8_t* pyr, const PyrBandPlan& p,
                            const int32_t* const* yofs, const int16_t* const* ya, const void* const* xgroups, const void* const* xgroups8, hipStream_t s)
 {
@@ -430,7 +417,7 @@ hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeo
     const int4* tab = reinterpret_cast<const int4*>(p.d_tab);
     const int mode = channels == 1 ? 2 : ((g.W & 3) == 0 && (reinterpret_cast<uintptr_t>(img) & 3) == 0) ? 1 : 0;
     auto launch = [&](auto kernel) {
-        const hipError_t e = pb_allow_lds(reinterpret_cast<const void*>(kernel), p.lds); if (e != hipSuccess) return e;
+        const hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), p.lds, PB_MAX_LDS); if (e != hipSuccess) return e;
         kernel<<<grid, PB_T, p.lds, s>>>(img, pyr, g, tab, t);
         return hipGetLastError();
     };

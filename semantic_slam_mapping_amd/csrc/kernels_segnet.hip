@@ -10,10 +10,7 @@
 //   (DESIGN.md s.4.1).
 // Also here: Classifier::Preprocess (segnet.cpp:130-167; cv::resize to 480x360, planar float, mean 0) and the label
 // colouring of experiment/segnet.cpp:80-83,131-146 (Pavement->Road remap, cv::resize back to the frame size, cv::LUT).
-#include "ssm_ctx.h"              // DevBuf: the per-stream tile-counter buffers
-#include <map>
-#include <mutex>
-#include <utility>
+#include "ssm_internal.h"
 #include <cstdlib>
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -1010,44 +1007,13 @@ hipError_t k_segnet_prep(const uint8_t* bgr, int n, int sw, int sh, int dw, int 
     segnet_prep_kernel<<<dim3((dw * dh + 255) / 256, n), 256, 0, s>>>(bgr, sw, sh, dw, dh, xofs, xa, yofs, ya, (_Float16*)out_f16);
     return hipGetLastError();
 }
-// tile counters of conv3x3_dma2_kernel (self-resetting, see there): one small zeroed buffer per (device, stream); launches on a
-// stream are ordered, so they can share it
-static std::mutex g_tq_mu; static std::map<std::pair<int, hipStream_t>, DevBuf<int>> g_tq_bufs;
-void k_segnet_release_stream(hipStream_t s)                       // ssm_destroy: the stream's tile-counter buffer goes with the context
-{
-    int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return;
-    std::lock_guard<std::mutex> lk(g_tq_mu);
-    g_tq_bufs.erase({dev, s});
-}
-#define CONV_QUEUE_INTS 1024          // a counter pair per (XCD group, cout tile): 8 x 32 x 2 at most
-static int* conv_tile_queue(hipStream_t s)
-{
-    std::mutex& mu = g_tq_mu; auto& bufs = g_tq_bufs;
-    int dev = 0; if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = bufs.find({dev, s});
-    if (it != bufs.end()) return it->second;
-    DevBuf<int> p;
-    if (p.alloc(nullptr, CONV_QUEUE_INTS) || hipMemset(p, 0, CONV_QUEUE_INTS * sizeof(int)) != hipSuccess) return nullptr;
-    return bufs[{dev, s}] = std::move(p);
-}
 // start of a forward pass: zero the stream's tile counters (they reset themselves at the end of every launch; this only
 // keeps an aborted launch from poisoning the passes after it)
-hipError_t k_segnet_begin(hipStream_t s)
-{
-    int* q = conv_tile_queue(s);
-    return q ? hipMemsetAsync(q, 0, CONV_QUEUE_INTS * sizeof(int), s) : hipErrorOutOfMemory;
-}
-static int conv_grid_limit()
-{
-    static int cus = 0;
-    if (!cus) { int dev = 0; hipGetDevice(&dev); if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256; }
-    return cus;
-}
+hipError_t k_segnet_begin(int* tiles, hipStream_t s) { return tiles ? hipMemsetAsync(tiles, 0, CONV_QUEUE_INTS * sizeof(int), s) : hipErrorInvalidValue; }
 // epi 0: conv; 1: conv + max-pool (out pooled, code); 2: conv + class ArgMax (out = uint8 labels [n][H][W]; Cout <= 12)
 // ucode != nullptr: `in` is the max-pooled tensor of an H x W image and ucode its arg-max codes (un-pool on load)
 static hipError_t conv_dma_launch(const void* in, const void* wt, const float* scale, const float* shift, void* out, uint8_t* code, int n, int H, int W,
-                                  int CinPad, int Cout, int relu, int epi, hipStream_t s, const uint8_t* ucode = nullptr)
+                                  int CinPad, int Cout, int relu, int epi, int cus, int* queue, hipStream_t s, const uint8_t* ucode = nullptr)
 {
     const int nct = (Cout + CT_N - 1) / CT_N, VH = (H + 2) & ~1, cs = (Cout + 31) & ~31;
     const unsigned long long in_bytes = ucode ? (unsigned long long)n * ((H + 1) / 2) * ((W + 1) / 2) * CinPad * 2 : (unsigned long long)n * H * W * CinPad * 2, wt_bytes = (unsigned long long)nct * CT_N * CinPad * 9 * 2;
@@ -1069,7 +1035,6 @@ static hipError_t conv_dma_launch(const void* in, const void* wt, const float* s
         // its weight slab.  Tiles are 64 output channels wide, or 32 when that balances the CUs better: blocks b and b + grid/2
         // share a CU and its matrix cores, so a CU's time is the work of both; a 32-wide tile costs a bit more than half
         // (the input tile is staged once per 32 channels instead of once per 64).
-        const int cus = conv_grid_limit();
         auto makespan = [&](int units, int tiles_n, double cost) {
             int grid = 2 * cus; grid -= grid % tiles_n; if (grid > units) grid = units;
             const int half = cus;                                                  // blocks b and b + cus share a CU
@@ -1088,7 +1053,6 @@ static hipError_t conv_dma_launch(const void* in, const void* wt, const float* s
         int grid = 2 * cus; grid -= grid % nct_k; if (grid > total_k) grid = total_k;
 #define D2_LAUNCH(R, E, N) conv3x3_dma2_kernel<R, E, N><<<grid, 256, 0, s>>>((const _Float16*)in, (const _Float16*)wt, scale, shift, (_Float16*)out, code, n, H, W, CinPad, Cout, tx, nct_k, total_k, (unsigned)in_bytes, (unsigned)wt_bytes, (unsigned)out_bytes, queue, ucode, xcd_map)
 #define D2_LAUNCH_UP(N) conv3x3_dma2_kernel<true, 0, N, true><<<grid, 256, 0, s>>>((const _Float16*)in, (const _Float16*)wt, scale, shift, (_Float16*)out, code, n, H, W, CinPad, Cout, tx, nct_k, total_k, (unsigned)in_bytes, (unsigned)wt_bytes, (unsigned)out_bytes, queue, ucode, xcd_map)
-        int* queue = conv_tile_queue(s);
         if (!queue || nct_k > 32) return hipErrorOutOfMemory;
         // the XCD-aware tile order needs whole groups of 8 x nct_k blocks (a full grid has them; a launch smaller than the grid keeps the plain order)
         // (A/B on the stage, same box: 5.04-5.12k frames/s plain, 5.14-5.16k with the XCD order; measured bytes 607 -> 386 MB per frame)
@@ -1109,63 +1073,61 @@ static hipError_t conv_dma_launch(const void* in, const void* wt, const float* s
         return hipGetLastError();
     }
 }
-static hipError_t conv_first_launch(const void* in, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W, int Cout, int relu, hipStream_t s)
+static hipError_t conv_first_launch(const void* in, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W, int Cout, int relu, int cus, hipStream_t s)
 {
     const int nct = (Cout + CT_N - 1) / CT_N, VH = (H + 2) & ~1, cs = (Cout + 31) & ~31;
     const unsigned long long in_bytes = (unsigned long long)n * H * W * 16, wt_bytes = (unsigned long long)nct * FT_BCH * 16, out_bytes = (unsigned long long)n * H * W * cs * 2;
     if (in_bytes >= 0x80000000ull || out_bytes >= 0x80000000ull || (long long)n * VH >= 65536) return hipErrorInvalidValue;
     const int tx = (W + DT_W - 1) / DT_W, ty = (n * VH + DT_H - 1) / DT_H, total = tx * ty * nct;
-    int grid = 2 * conv_grid_limit(); grid -= grid % nct; if (grid > total) grid = total;        // 31 KB of LDS: two blocks per CU
+    int grid = 2 * cus; grid -= grid % nct; if (grid > total) grid = total;        // 31 KB of LDS: two blocks per CU
     if (relu) conv3x3_first_kernel<true><<<grid, 512, 0, s>>>((const _Float16*)in, (const _Float16*)wt, scale, shift, (_Float16*)out, n, H, W, Cout, tx, nct, total, (unsigned)in_bytes, (unsigned)wt_bytes, (unsigned)out_bytes);
     else      conv3x3_first_kernel<false><<<grid, 512, 0, s>>>((const _Float16*)in, (const _Float16*)wt, scale, shift, (_Float16*)out, n, H, W, Cout, tx, nct, total, (unsigned)in_bytes, (unsigned)wt_bytes, (unsigned)out_bytes);
     return hipGetLastError();
 }
 // CinPad == 8: the <= 8-channel first layer ([n][H][W][8] input, its own weight packing); otherwise CinPad is a multiple of 64
-static hipError_t conv_wino_launch(const void* in, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W, int CinPad, int Cout, int relu, hipStream_t s)
+static hipError_t conv_wino_launch(const void* in, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W, int CinPad, int Cout, int relu, int cus, int* queue, hipStream_t s)
 {
     const int nct64 = (Cout + CT_N - 1) / CT_N, VH = (H + 2) & ~1;
     const unsigned long long in_bytes = (unsigned long long)n * H * W * CinPad * 2, wt_bytes = (unsigned long long)nct64 * CT_N * CinPad * WG_TAPS * 2, out_bytes = (unsigned long long)n * H * W * Cout * 2;
     if (Cout % 32 || CinPad % (2 * CT_KC)) return hipErrorInvalidValue;
     if (in_bytes >= 0x80000000ull || wt_bytes >= 0x80000000ull || out_bytes >= 0x80000000ull || (long long)n * VH >= 65536) return hipErrorInvalidValue;
     const int tx = (W + DT_W - 1) / DT_W, ty = (n * VH + DT_H - 1) / DT_H, nct = Cout / 32, total = tx * ty * nct;
-    const int cus = conv_grid_limit();
     int grid = 2 * cus; grid -= grid % nct; if (grid > total) grid = total;
-    int* queue = conv_tile_queue(s);
     if (!queue || nct > 32) return hipErrorOutOfMemory;
     if (relu) conv3x3_wino_kernel<true><<<grid, 256, 0, s>>>((const _Float16*)in, (const _Float16*)wt, scale, shift, (_Float16*)out, n, H, W, CinPad, Cout, tx, nct, total, (unsigned)in_bytes, (unsigned)wt_bytes, (unsigned)out_bytes, queue);
     else conv3x3_wino_kernel<false><<<grid, 256, 0, s>>>((const _Float16*)in, (const _Float16*)wt, scale, shift, (_Float16*)out, n, H, W, CinPad, Cout, tx, nct, total, (unsigned)in_bytes, (unsigned)wt_bytes, (unsigned)out_bytes, queue);
     return hipGetLastError();
 }
 hipError_t k_segnet_conv(const void* in, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W,
-                         int CinPad, int Cout, int relu, hipStream_t s, const void* wt_wino)
+                         int CinPad, int Cout, int relu, const DeviceInfo& dev, int* tiles, hipStream_t s, const void* wt_wino)
 {
-    if (CinPad == 8) return conv_first_launch(in, wt, scale, shift, out, n, H, W, Cout, relu, s);
+    if (CinPad == 8) return conv_first_launch(in, wt, scale, shift, out, n, H, W, Cout, relu, dev.cus, s);
     if (CinPad % (2 * CT_KC)) return hipErrorInvalidValue;
-    if (wt_wino) return conv_wino_launch(in, wt_wino, scale, shift, out, n, H, W, CinPad, Cout, relu, s);
-    return conv_dma_launch(in, wt, scale, shift, out, nullptr, n, H, W, CinPad, Cout, relu, 0, s);
+    if (wt_wino) return conv_wino_launch(in, wt_wino, scale, shift, out, n, H, W, CinPad, Cout, relu, dev.cus, tiles, s);
+    return conv_dma_launch(in, wt, scale, shift, out, nullptr, n, H, W, CinPad, Cout, relu, 0, dev.cus, tiles, s);
 }
 // conv + BN + ReLU + max-pool 2x2 (CEIL) in one pass: out is [n][Cout/32][PH][PW][32], code the arg-max codes in the same index space
 hipError_t k_segnet_conv_pool(const void* in, const void* wt, const float* scale, const float* shift, void* out, uint8_t* code, int n, int H, int W,
-                              int CinPad, int Cout, hipStream_t s)
+                              int CinPad, int Cout, const DeviceInfo& dev, int* tiles, hipStream_t s)
 {
     if ((CinPad / CT_KC) & 1) return hipErrorInvalidValue;
-    return conv_dma_launch(in, wt, scale, shift, out, code, n, H, W, CinPad, Cout, 1, 1, s);
+    return conv_dma_launch(in, wt, scale, shift, out, code, n, H, W, CinPad, Cout, 1, 1, dev.cus, tiles, s);
 }
 // last layer + ArgMax in one pass: labels [n][H][W] uint8 (the class logits are not materialised)
 hipError_t k_segnet_conv_argmax(const void* in, const void* wt, const float* scale, const float* shift, uint8_t* labels, int n, int H, int W,
-                                int CinPad, int Cout, hipStream_t s)
+                                int CinPad, int Cout, const DeviceInfo& dev, int* tiles, hipStream_t s)
 {
     if (CinPad % (2 * CT_KC)) return hipErrorInvalidValue;
-    return conv_dma_launch(in, wt, scale, shift, labels, nullptr, n, H, W, CinPad, Cout, 0, 2, s);
+    return conv_dma_launch(in, wt, scale, shift, labels, nullptr, n, H, W, CinPad, Cout, 0, 2, dev.cus, tiles, s);
 }
 // un-pool + conv + BN + ReLU in one pass: `pooled` is [n][CinPad/32][(H+1)/2][(W+1)/2][32] with its codes, out the H x W convolution
 // of the un-pooled image (which is never written).  Only the default kernel has this form: k_segnet_conv_unpool_available().
 int k_segnet_conv_unpool_available() { return 1; }
 hipError_t k_segnet_conv_unpool(const void* pooled, const uint8_t* ucode, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W,
-                                int CinPad, int Cout, hipStream_t s)
+                                int CinPad, int Cout, const DeviceInfo& dev, int* tiles, hipStream_t s)
 {
     if (CinPad % (2 * CT_KC) || !ucode) return hipErrorInvalidValue;
-    return conv_dma_launch(pooled, wt, scale, shift, out, nullptr, n, H, W, CinPad, Cout, 1, 0, s, ucode);
+    return conv_dma_launch(pooled, wt, scale, shift, out, nullptr, n, H, W, CinPad, Cout, 1, 0, dev.cus, tiles, s, ucode);
 }
 hipError_t k_segnet_pool(const void* in, int n, int H, int W, int C, void* out, uint8_t* code, hipStream_t s)
 {

@@ -21,12 +21,10 @@
 //   sgbm_lrcheck     the left-right consistency check on both roundings of the disparity
 //   sgbm_median3, sgbm_speckle_* (connected components by union-find), sgbm_depth
 // HBM-bound by design (about a GB of volume traffic per 1241x376x80 frame); no MFMA.
-#include "ssm_internal.h"
+#include "ssm_ctx.h"              // SgFan: the lane's side streams of forms 0 / 1
 #include <climits>
-#include <mutex>
 #include <tuple>
 #include <map>
-#include <set>
 #include <utility>
 #include <type_traits>
 
@@ -41,55 +39,6 @@
 #include "sgbm_sweep.inc"
 #include "sgbm_post.inc"
 // ------------------------------------------------------------------ launcher
-// side streams for the five concurrent scan directions: one set per caller stream (a context), created at its first call;
-// every call forks them from and joins them into the caller's stream by events, so calls on one context stay ordered and
-// contexts used from different host threads never share an event
-struct SgStreams { hipStream_t s[4] = {}; hipEvent_t fork = nullptr, done[4] = {}; bool ok = false; };
-static std::mutex g_sg_mu;
-static std::map<std::pair<int, hipStream_t>, SgStreams*> g_sg_sets;
-// ssm_destroy: the side streams / events of a context's stream go with it (and a recycled stream handle can never find a stale set)
-void k_sgbm_release_stream(hipStream_t caller)
-{
-    int dev = 0; (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(g_sg_mu);
-    auto it = g_sg_sets.find({dev, caller});
-    if (it == g_sg_sets.end()) return;
-    SgStreams* st = it->second;
-    for (int i = 0; i < 4; i++) { if (st->s[i]) { (void)hipStreamSynchronize(st->s[i]); (void)hipStreamDestroy(st->s[i]); } if (st->done[i]) (void)hipEventDestroy(st->done[i]); }
-    if (st->fork) (void)hipEventDestroy(st->fork);
-    delete st;
-    g_sg_sets.erase(it);
-}
-static SgStreams& sg_streams(hipStream_t caller)
-{
-    std::mutex& mu = g_sg_mu;
-    auto& sets = g_sg_sets;
-    int dev = 0; (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    SgStreams*& st = sets[{dev, caller}];
-    if (!st) {
-        st = new SgStreams;
-        bool ok = hipEventCreateWithFlags(&st->fork, hipEventDisableTiming) == hipSuccess;
-        for (int i = 0; i < 4 && ok; i++)
-            ok = hipStreamCreateWithFlags(&st->s[i], hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&st->done[i], hipEventDisableTiming) == hipSuccess;
-        st->ok = ok;
-    }
-    return *st;
-}
-// dynamic LDS above the 64 KB default needs the attribute on the current device's copy of the function: once per (device, kernel)
-static hipError_t sg_allow_lds(const void* fn, size_t bytes)
-{
-    if (bytes <= 48 * 1024) return hipSuccess;
-    static std::mutex mu; static std::set<std::pair<int, const void*>> done;
-    int dev = 0; (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    if (done.count({dev, fn})) return hipSuccess;
-    int lim = 0;
-    if (hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess || lim <= 0) lim = 160 * 1024;
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lim - 1024);
-    if (e == hipSuccess) done.insert({dev, fn});
-    return e;
-}
 // SSM_SGBM_FORM (read once per process): 2 = sgbm_rows + sgbm_sweep (default), 1 = four L volumes + sgbm_col_wta (round 3), 0 = five L volumes + sgbm_wta
 // SSM_SGBM_STRIP: columns per sweep strip (tests: many seams on small images).
 static int sgbm_form()
@@ -107,18 +56,9 @@ static size_t sgbm_mbox_bytes_per_frame(int w1, int D)
     const int K = D / 16, NG = (K + 1) / 2 + 1, maxNS = (w1 + 2 * SGS_CPG - 1) / (2 * SGS_CPG);
     return (size_t)(maxNS > 1 ? maxNS - 1 : 0) * 2 * SGS_SLOTS * NG * 16 * 8;
 }
-static int sg_num_cus()
-{
-    static std::mutex mu; static std::map<int, int> cus;
-    int dev = 0; (void)hipGetDevice(&dev);
-    std::lock_guard<std::mutex> lk(mu);
-    int& n = cus[dev];
-    if (n <= 0 && (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)) n = 256;
-    return n;
-}
 template <int K>
 static hipError_t sgbm_aggregate2(const uint16_t* C, uint16_t* S04, uint16_t* ck, unsigned* flags, int w, int w1, int h, int nb, const ssm_sgbm_params& p, int minX1, int P1, int P2,
-                                  bool costs_below_2_15, int16_t* disp_tmp, unsigned* disp2key, int16_t* disp1, int* fail_out, int concurrent, hipStream_t s)
+                                  bool costs_below_2_15, int16_t* disp_tmp, unsigned* disp2key, int16_t* disp1, int* fail_out, int concurrent, const DeviceInfo& dev, hipStream_t s)
 {
     constexpr int NG = (K + 1) / 2 + 1, D = 16 * K;
     const size_t np = (size_t)w * h, npb = np * nb;
@@ -130,7 +70,7 @@ static hipError_t sgbm_aggregate2(const uint16_t* C, uint16_t* S04, uint16_t* ck
     // start, and the blocks they displace make a fourth round.  A launch that would leave most CUs empty (few frames) takes narrower strips, down to 32 columns.
     int cap = 64 * SGS_CPG;
     if (strip_env >= 2 * SGS_CPG && strip_env < cap) cap = strip_env / SGS_CPG * SGS_CPG;
-    else { const int cus = sg_num_cus(); while (cap > 32 && (long)nb * ((w1 + cap - 1) / cap) * 2 <= cus) cap /= 2; }
+    else { const int cus = dev.cus; while (cap > 32 && (long)nb * ((w1 + cap - 1) / cap) * 2 <= cus) cap /= 2; }
     int NS = (w1 + cap - 1) / cap;
     const int TX = ((w1 + NS - 1) / NS + SGS_CPG - 1) / SGS_CPG * SGS_CPG;
     NS = (w1 + TX - 1) / TX;
@@ -141,7 +81,7 @@ static hipError_t sgbm_aggregate2(const uint16_t* C, uint16_t* S04, uint16_t* ck
     const int threads = use8 ? threads8 : (TX / SGS_CPG * 16 + 63) / 64 * 64, ng = threads / 16;
     const size_t lds = use8 ? lds8 : (size_t)4 * ng * NG * 16 * 4 + (size_t)ng * D * 2;
     auto sweep = use8 ? (costs_below_2_15 ? sgbm_sweep8<K, true> : sgbm_sweep8<K, false>) : (costs_below_2_15 ? sgbm_sweep<K, SGS_CPG, true> : sgbm_sweep<K, SGS_CPG, false>);
-    hipError_t e = sg_allow_lds(reinterpret_cast<const void*>(sweep), lds);
+    hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(sweep), lds, dev.max_lds - 1024);
     if (e != hipSuccess) return e;
     // Forward progress of the strips' hand-offs (an ordinary launch: nothing guarantees co-residency): the blocks that run hold the lowest tickets, so a frame
     // advances as soon as all NS strips of the lowest unfinished frame are resident -- which needs NS block slots for this launch even when `concurrent` sweeps
@@ -149,11 +89,10 @@ static hipError_t sgbm_aggregate2(const uint16_t* C, uint16_t* S04, uint16_t* ck
     // does not hold the caller takes form 1 (no cross-block waits).  SSM_SGBM_TEST_TIMEOUT=2 (tests) pretends it does not.
     {
         static std::mutex mu; static std::map<std::tuple<int, const void*, int, size_t>, int> occ;
-        int dev = 0; (void)hipGetDevice(&dev);
         int per_cu = 0;
         {
             std::lock_guard<std::mutex> lk(mu);
-            auto key = std::make_tuple(dev, reinterpret_cast<const void*>(sweep), threads, lds);
+            auto key = std::make_tuple(dev.id, reinterpret_cast<const void*>(sweep), threads, lds);
             auto it = occ.find(key);
             if (it == occ.end()) {
                 if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(sweep), threads, lds) != hipSuccess) per_cu = 0;
@@ -161,7 +100,7 @@ static hipError_t sgbm_aggregate2(const uint16_t* C, uint16_t* S04, uint16_t* ck
             } else per_cu = it->second;
         }
         static const int test_hook = [] { const char* v = getenv("SSM_SGBM_TEST_TIMEOUT"); return v ? atoi(v) : 0; }();
-        if (test_hook == 2 || (long)per_cu * sg_num_cus() < (long)NS * (concurrent > 0 ? concurrent : 1)) return hipErrorCooperativeLaunchTooLarge;
+        if (test_hook == 2 || (long)per_cu * dev.cus < (long)NS * (concurrent > 0 ? concurrent : 1)) return hipErrorCooperativeLaunchTooLarge;
     }
     // checkpoints every 12 columns (measured at 8 / 12 / 16: 0.1966 / 0.1933 / 0.1918 ms per pair for the SGBM stage, but 4.32 / 4.38 / 4.33 k pairs/s for the whole
     // path -- 16 columns of costs in registers leave the kernels of the other streams less room beside it)
@@ -201,12 +140,11 @@ static hipError_t sgbm_aggregate2(const uint16_t* C, uint16_t* S04, uint16_t* ck
 }
 template <int K>
 static hipError_t sgbm_aggregate(const uint16_t* C, uint16_t* const* Lv, int w, int w1, int h, int nb, const ssm_sgbm_params& p, int minX1, int P1, int P2,
-                                 int16_t* disp_tmp, unsigned* disp2key, int16_t* disp1, int form, hipStream_t s)
+                                 int16_t* disp_tmp, unsigned* disp2key, int16_t* disp1, int form, SgFan& st, hipStream_t s)
 {
     auto blocks = [](int paths) { return (paths * 16 + 255) / 256; };
-    SgStreams& st = sg_streams(s);
-    if (!st.ok) return hipErrorUnknown;
-    hipError_t e = hipEventRecord(st.fork, s);
+    hipError_t e = st.ensure();                               // the fan is forked from and joined into `s` by events on every call
+    if (e == hipSuccess) e = hipEventRecord(st.fork, s);
     for (int i = 0; i < 4 && e == hipSuccess; i++) e = hipStreamWaitEvent(st.s[i], st.fork, 0);
     if (e != hipSuccess) return e;
     const size_t np = (size_t)w * h, npb = np * nb;
@@ -273,17 +211,17 @@ size_t k_sgbm_workspace_bytes(int w, int h, const ssm_sgbm_params& p, int nb, in
 // of this function that may be in flight on other streams at the same time (the occupancy check of form 2)
 // ws_bytes: what `workspace` holds.  A formulation whose volumes for nb frames do not fit (form 1 as the repeat of a timed-out form-2 sub-batch in a workspace
 // sized for form 2) runs in pieces of frames that do, one after the other on the same stream.
-hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int nb, const ssm_sgbm_params& p, void* workspace, size_t ws_bytes, int16_t* disp_out, int raw_only, hipStream_t s, int* fail_flag,
-                  int form_cfg, int concurrent)
+hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int nb, const ssm_sgbm_params& p, void* workspace, size_t ws_bytes, int16_t* disp_out, int raw_only,
+                  const DeviceInfo& dev, SgFan& fan, hipStream_t s, int* fail_flag, int form_cfg, int concurrent)
 {
     int form = sgbm_resolve_form(form_cfg);
     if (nb <= 0) return hipSuccess;
     if (sgbm_ws_bytes(w, h, p, nb, sgbm_form_volumes(form)) > ws_bytes) {
         if (nb == 1) return hipErrorOutOfMemory;
         const int half = (nb + 1) / 2; const size_t np1_ = (size_t)w * h;
-        hipError_t e1 = k_sgbm(left, right, w, h, half, p, workspace, ws_bytes, disp_out, raw_only, s, fail_flag, form_cfg, concurrent);
+        hipError_t e1 = k_sgbm(left, right, w, h, half, p, workspace, ws_bytes, disp_out, raw_only, dev, fan, s, fail_flag, form_cfg, concurrent);
         if (e1 != hipSuccess) return e1;
-        return k_sgbm(left + (size_t)half * np1_, right + (size_t)half * np1_, w, h, nb - half, p, workspace, ws_bytes, disp_out + (size_t)half * np1_, raw_only, s, fail_flag, form_cfg, concurrent);
+        return k_sgbm(left + (size_t)half * np1_, right + (size_t)half * np1_, w, h, nb - half, p, workspace, ws_bytes, disp_out + (size_t)half * np1_, raw_only, dev, fan, s, fail_flag, form_cfg, concurrent);
     }
     const int minD = p.minDisparity, D = p.numberOfDisparities, maxD = minD + D;
     const int SW = p.SADWindowSize > 0 ? p.SADWindowSize : 5, SW2 = SW / 2;
@@ -317,7 +255,7 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
         const int nstrips = (w1 + TX - 1) / TX;
         const int tail = nstrips > 1 ? ((w1 - (nstrips - 1) * TX < SW2 && nstrips > 2) ? 2 : 1) : 0;     // a last strip narrower than the half window: the one before it reaches the border too
         auto launch = [&](auto kern) {
-            (void)sg_allow_lds(reinterpret_cast<const void*>(kern), lds);       // the ring of a wide window needs more than the 64 KB default of dynamic LDS
+            (void)allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, dev.max_lds - 1024);       // the ring of a wide window needs more than the 64 KB default of dynamic LDS
             kern<<<dim3(nstrips, nb), SGC_THREADS, lds, s>>>(planes, w, h, minD, D, minX1, w1, SW2, P2, TX, tail, C);
         };
         const long cmax_c = (long)P2 + (long)SW * SW * (2 * ftzero + 63);
@@ -326,7 +264,7 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
             constexpr int AWc = 32 + 10, RWc = AWc + 79;
             lds = 2 * ((((size_t)(AWc + 6) * 80) + 15) & ~(size_t)15) + 2 * (size_t)(AWc + RWc) * 16;
             auto kern = sgbm_cost_reg_kernel<80, 5, 32, 6>;
-            (void)sg_allow_lds(reinterpret_cast<const void*>(kern), lds);
+            (void)allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds, dev.max_lds - 1024);
             kern<<<dim3(nstrips, nb), SGC_THREADS, lds, s>>>(left, right, ftzero, w, h, minD, minX1, w1, P2, tail, C);
         } else {
             sgbm_prefilter<<<dim3((w + 255) / 256, h, nb * 2), 256, 0, s>>>(left, right, w, h, ftzero, planes);
@@ -341,17 +279,17 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
     e = hipSuccess;
     if (form == 2) {
         switch (D / 16) {
-#define SG_AGG2(KK) case KK: e = sgbm_aggregate2<KK>(C, Lv[0], Lv[1], sweep_flags, w, w1, h, nb, p, minX1, P1, P2, cmax < 32768, d_tmp, d2key, wta_out, fail_flag, concurrent, s); break;
+#define SG_AGG2(KK) case KK: e = sgbm_aggregate2<KK>(C, Lv[0], Lv[1], sweep_flags, w, w1, h, nb, p, minX1, P1, P2, cmax < 32768, d_tmp, d2key, wta_out, fail_flag, concurrent, dev, s); break;
             SG_AGG2(1) SG_AGG2(2) SG_AGG2(3) SG_AGG2(4) SG_AGG2(5) SG_AGG2(6) SG_AGG2(8)
 #undef SG_AGG2
             default: return hipErrorInvalidValue;
         }
         if (e == hipErrorCooperativeLaunchTooLarge) {       // the sweep's strips cannot all be resident: the form without cross-block waits (nothing was launched; the cost volume is recomputed)
-            return k_sgbm(left, right, w, h, nb, p, workspace, ws_bytes, disp_out, raw_only, s, fail_flag, 1, concurrent);
+            return k_sgbm(left, right, w, h, nb, p, workspace, ws_bytes, disp_out, raw_only, dev, fan, s, fail_flag, 1, concurrent);
         }
     }
     if (form != 2) switch (D / 16) {
-#define SG_AGG1(KK) case KK: e = sgbm_aggregate<KK>(C, Lv, w, w1, h, nb, p, minX1, P1, P2, d_tmp, d2key, wta_out, form, s); break;
+#define SG_AGG1(KK) case KK: e = sgbm_aggregate<KK>(C, Lv, w, w1, h, nb, p, minX1, P1, P2, d_tmp, d2key, wta_out, form, fan, s); break;
         SG_AGG1(1) SG_AGG1(2) SG_AGG1(3) SG_AGG1(4) SG_AGG1(5) SG_AGG1(6) SG_AGG1(8)
 #undef SG_AGG1
         default: return hipErrorInvalidValue;

@@ -3,6 +3,7 @@
 // moves caller data and enqueues the kernels of kernels_*.hip on the context stream.  There is NO CPU fallback: if
 // HIP is unusable ssm_create fails with SSM_E_NODEVICE / SSM_E_HIP.
 #include "ssm_ctx.h"
+#include <set>
 
 static const int8_t k_default_pattern[1024] = {
 #include "orb_pattern.inc"
@@ -110,31 +111,42 @@ void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, std::vector<
 int ensure_scratch(ssm_ctx* c, size_t bytes)
 {
     if (bytes <= c->d_scratch.bytes()) return SSM_OK;
-    if (c->d_scratch) hipStreamSynchronize(c->stream);
+    if (c->d_scratch) hipStreamSynchronize(c->main.stream);
     return c->d_scratch.alloc(c, bytes);
 }
 int ensure_pinned(ssm_ctx* c, size_t bytes)
 {
     if (bytes <= c->h_pinned.bytes()) return SSM_OK;
-    if (c->h_pinned) hipStreamSynchronize(c->stream);
+    if (c->h_pinned) hipStreamSynchronize(c->main.stream);
     if (c->h_pinned.alloc(c, bytes)) FAIL(c, SSM_E_HIP, "hipHostMalloc failed");
     return SSM_OK;
 }
 int ensure_scratch2(ssm_ctx* c, size_t bytes)
 {
     if (bytes <= c->d_scratch2.bytes()) return SSM_OK;
-    if (c->d_scratch2) hipStreamSynchronize(c->stream);
+    if (c->d_scratch2) hipStreamSynchronize(c->main.stream);
     return c->d_scratch2.alloc(c, bytes);
 }
 void prof_begin(ssm_ctx* c, hipStream_t s, const char* name)
 {
     if (!c->profiling) return;
-    auto get = [&]() { if (c->pool_used == c->pool.size()) { hipEvent_t e; hipEventCreate(&e); c->pool.push_back(e); } return c->pool[c->pool_used++]; };
+    auto get = [&]() -> hipEvent_t { if (c->pool_used == c->pool.size()) { c->pool.emplace_back(); (void)c->pool.back().ensure(true); } return c->pool[c->pool_used++]; };
     StageRec r; r.name = name; r.a = get(); r.b = get();
     hipEventRecord(r.a, s);
     c->recs.push_back(r);
 }
 void prof_end(ssm_ctx* c, hipStream_t s) { if (c->profiling) hipEventRecord(c->recs.back().b, s); }
+hipError_t allow_dynamic_lds(const void* fn, size_t bytes, int limit)
+{
+    if (bytes <= 48 * 1024) return hipSuccess;
+    static std::mutex mu; static std::set<std::pair<int, const void*>> done;
+    int dev = 0; (void)hipGetDevice(&dev);
+    std::lock_guard<std::mutex> lk(mu);
+    if (done.count({dev, fn})) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, limit);
+    if (e == hipSuccess) done.insert({dev, fn});
+    return e;
+}
 
 // ORB scratch overflow (d_status) is checked after every ORB entry point; the voxel-table-full flag (counters[1]) belongs to the MAP entry points
 // (ssm_sync after ssm_seq_process, ssm_map_*): it is reported once, so that one overflowing call does not fail every later call on the
@@ -148,7 +160,7 @@ int check_device_flags(ssm_ctx* c, bool with_map)
         if (c->stereo->sg_fail) { const int r = sgbm_recover(c); if (r) return r; }
     }
     if (with_map) {
-        { const int r = map_settle(c, c->stream, 0); if (r) return r; }
+        { const int r = map_settle(c, c->main.stream, 0); if (r) return r; }
         HIPCHK(c, hipMemcpy(cnt, c->map.counters, 8, hipMemcpyDeviceToHost));
         if (cnt[1]) {
             // bit 1 (skipped points: a defined contract, DESIGN.md "voxel key range") is reported once and cleared.  Bit 0 (table full: points were DROPPED,
@@ -196,7 +208,11 @@ static int orb_work_alloc(ssm_ctx* c, OrbWork& w)
 static int ctx_init(ssm_ctx* c)
 {
     const ssm_config& cfg = c->cfg; const OrbGeom& g = c->g; const int B = c->B, W = g.W, H = g.H;
-    HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    HIPCHK(c, c->main.stream.ensure());
+    c->dev.id = c->device;             // (a failed query keeps DeviceInfo's fall-back)
+    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) c->dev.cus = v; }
+    { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) == hipSuccess && v > 0) c->dev.max_lds = v; }
+    c->map_div_exact = k_map_div(cfg.camera, c->map_div);
     DALLOC(c, c->d_pattern, 1024);
     HIPCHK(c, hipMemcpy(c->d_pattern, cfg.brief_pattern ? cfg.brief_pattern : k_default_pattern, 1024, hipMemcpyHostToDevice));
     {   float pf[1024]; const int8_t* src = cfg.brief_pattern ? cfg.brief_pattern : k_default_pattern;
@@ -243,7 +259,7 @@ static int ctx_init(ssm_ctx* c)
         HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
         p.d_tab = d;
     }
-    { const int r = orb_work_alloc(c, c->work[0]); if (r) return r; }
+    { const int r = orb_work_alloc(c, c->chain[0].work); if (r) return r; }
     DALLOC(c, c->d_status, 1); HIPCHK(c, hipMemset(c->d_status, 0, 4));
     const int chunks = backproject_chunks(W, H);
     DALLOC(c, c->d_mask, (size_t)B * W * H); DALLOC(c, c->d_chunk_cnt, (size_t)B * chunks); DALLOC(c, c->d_chunk_off, (size_t)B * chunks);
@@ -252,9 +268,9 @@ static int ctx_init(ssm_ctx* c)
     DALLOC(c, c->map.ovf, VOX_OVF_RECORDS); c->map.ovf_cap = VOX_OVF_RECORDS;
     if (c->h_map_snap.alloc(c, 16)) FAIL(c, SSM_E_HIP, "hipHostMalloc of the map counter ring failed");
     memset(c->h_map_snap, 0, 64);
-    for (int k = 0; k < 2; k++) HIPCHK(c, hipEventCreateWithFlags(&c->map_snap_ev[k], hipEventDisableTiming));
-    int r = table_alloc(c, c->stream, c->map, cfg.voxel_capacity_log2); if (r) return r;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 2; k++) HIPCHK(c, c->map_snap_ev[k].ensure());
+    int r = table_alloc(c, c->main.stream, c->map, cfg.voxel_capacity_log2); if (r) return r;
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_create(int device, const ssm_config* cfg, ssm_ctx** out)
@@ -288,25 +304,21 @@ extern "C" int ssm_create(int device, const ssm_config* cfg, ssm_ctx** out)
     *out = c;
     return SSM_OK;
 }
-// What a destructor cannot order: the device is drained before anything goes (no buffer is released while a stream of the context can still touch it), the
-// per-stream SGBM / SegNet caches go before their streams, events and streams are destroyed; `delete c` then releases every buffer the context, its
-// StereoState and its SegNetState own.  The context's device stays current until it returns.
+// What a destructor cannot order: the device is drained before anything goes (no buffer, stream or event is released while a stream of the context can still
+// touch it) and the communicator is torn down; `delete c` then releases every stream, event and buffer the context, its lanes, its StereoState and its
+// SegNetState own.  The context's device stays current until it returns.
 extern "C" void ssm_destroy(ssm_ctx* c)
 {
     if (!c) return;
     hipSetDevice(c->device);
     hipDeviceSynchronize();
     if (c->comm) { ncclCommDestroy(c->comm); c->comm = nullptr; }
-    for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream4}) if (st) { k_sgbm_release_stream(st); k_segnet_release_stream(st); }
-    for (hipEvent_t e : {c->map_snap_ev[0], c->map_snap_ev[1], c->ev_orb[0], c->ev_orb[1], c->ev_orb[2], c->ev_fork, c->ev_join, c->ev_join3, c->ev_join4}) if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->pool) hipEventDestroy(e);
-    for (hipStream_t st : {c->stream, c->stream2, c->stream3, c->stream4}) if (st) hipStreamDestroy(st);
     delete c;
 }
 void ssm_internal_get_config(const ssm_ctx* c, ssm_config* out) { *out = c->cfg; }
 int ssm_internal_get_device(const ssm_ctx* c) { return c->device; }
 extern "C" int ssm_orb_capacity(const ssm_ctx* c) { return c ? c->g.cap : 0; }
-extern "C" void* ssm_stream(ssm_ctx* c) { return c ? (void*)c->stream : nullptr; }
+extern "C" void* ssm_stream(ssm_ctx* c) { return c ? (void*)c->main.stream : nullptr; }
 extern "C" int ssm_sync(ssm_ctx* c)
 {
     if (!c) return SSM_E_INVAL;
@@ -314,7 +326,7 @@ extern "C" int ssm_sync(ssm_ctx* c)
     hipSetDevice(c->device);
     c->err.clear();                                               // (after a successful ssm_sync ssm_last_error is empty, or the note of a repeated SGBM sweep)
     { int r = wait_pending(c); if (r) return r; }                 // asynchronous per-frame calls still in flight are completed (their results delivered) too
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->map_tail = nullptr;                                        // (every stream of the context is idle: the context stream joined them)
     return check_device_flags(c, true);
 }
@@ -324,7 +336,7 @@ extern "C" int ssm_get_stage_times(ssm_ctx* c, const char** names, float* ms, in
     if (!c || !n_out) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
     hipSetDevice(c->device);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->stage_names.clear(); c->stage_ms.clear(); c->stage_launches.clear();
     for (const StageRec& r : c->recs) {
         float t = 0.f; hipEventElapsedTime(&t, r.a, r.b);
@@ -339,29 +351,37 @@ extern "C" int ssm_get_stage_times(ssm_ctx* c, const char** names, float* ms, in
     return SSM_OK;
 }
 
-// The side streams of ssm_seq_process (stream2: second chain / SegNet + map side; stream3: map stage; stream4: third chain) are created at first use, not
-// with the context: HIP spreads streams over a few hardware queues in creation order, and a context that only serves per-frame calls (the stereo bench
-// runs eight of them) should take ONE slot of that rotation -- with four streams per context every context's main stream landed on the same queue
-// (configs[3]: 233 instead of 346-386 frame pairs/s).
+// The side lanes (ssm_ctx::side) are created at first use, not with the context: HIP spreads streams over a few hardware queues in creation order, and a
+// context that only serves per-frame calls (the stereo bench runs eight of them) should take ONE slot of that rotation -- with four streams per context
+// every context's main stream landed on the same queue (configs[3]: 233 instead of 346-386 frame pairs/s).
 int ensure_side_streams(ssm_ctx* c)
 {
     if (c->side_ready) return SSM_OK;
-    // each handle is created only if it is still missing: a call that failed half-way leaves side_ready false and the next call resumes
+    // ensure() creates only what is still missing: a call that failed half-way leaves side_ready false and the next call resumes
     // (Round 5 measured a static split of the machine -- the map stage's stream confined to N compute units, the chains' streams to the rest, hipExtStreamCreateWithCUMask --
     // against the hardware's block-by-block arbitration: -9 %, profiles/r05_cu_split.md.  The switches are gone.)
-    auto mk_stream = [&](hipStream_t* st, int = 0) -> hipError_t { return *st ? hipSuccess : hipStreamCreateWithFlags(st, hipStreamNonBlocking); };
-    auto mk_event = [&](hipEvent_t* ev) -> hipError_t { return *ev ? hipSuccess : hipEventCreateWithFlags(ev, hipEventDisableTiming); };
-    HIPCHK(c, mk_stream(&c->stream2, 2));
-    HIPCHK(c, mk_stream(&c->stream3, 1)); HIPCHK(c, mk_event(&c->ev_join3));
-    HIPCHK(c, mk_event(&c->ev_fork)); HIPCHK(c, mk_event(&c->ev_join));
-    for (int i = 0; i < 3; i++) HIPCHK(c, mk_event(&c->ev_orb[i]));
-    HIPCHK(c, mk_stream(&c->stream4, 2)); HIPCHK(c, mk_event(&c->ev_join4));
+    HIPCHK(c, c->side[0].stream.ensure());
+    HIPCHK(c, c->side[1].stream.ensure()); HIPCHK(c, c->side[1].joined.ensure());
+    HIPCHK(c, c->forked.ensure()); HIPCHK(c, c->side[0].joined.ensure());
+    for (OrbChain& ch : c->chain) HIPCHK(c, ch.orb_done.ensure());
+    HIPCHK(c, c->side[2].stream.ensure()); HIPCHK(c, c->side[2].joined.ensure());
     c->side_ready = true;
+    return SSM_OK;
+}
+int lanes_fork(ssm_ctx* c, std::initializer_list<Lane*> lanes)
+{
+    HIPCHK(c, hipEventRecord(c->forked, c->main.stream));
+    for (Lane* l : lanes) if (l) HIPCHK(c, hipStreamWaitEvent(l->stream, c->forked, 0));
+    return SSM_OK;
+}
+int lanes_join(ssm_ctx* c, std::initializer_list<Lane*> lanes)
+{
+    for (Lane* l : lanes) if (l) { HIPCHK(c, hipEventRecord(l->joined, l->stream)); HIPCHK(c, hipStreamWaitEvent(c->main.stream, l->joined, 0)); }
     return SSM_OK;
 }
 static int ensure_alt(ssm_ctx* c)          // the workspaces of chains 1, 2 of ssm_seq_process
 {
-    for (int k = 1; k < 3; k++) if (!c->work[k].kpaux) { const int r = orb_work_alloc(c, c->work[k]); if (r) return r; }
+    for (int k = 1; k < 3; k++) if (!c->chain[k].work.kpaux) { const int r = orb_work_alloc(c, c->chain[k].work); if (r) return r; }
     return SSM_OK;
 }
 // ---------------------------------------------------------------- the ORB front end for nb frames already on the device, on stream s with workspace w
@@ -490,6 +510,12 @@ extern "C" void ssm_debug_live_allocations(int* buffers, size_t* device_bytes, s
     if (pinned_bytes) *pinned_bytes = DevBufLive::pinned_bytes.load();
 }
 
+extern "C" void ssm_debug_live_handles(int* streams, int* events)
+{
+    if (streams) *streams = HandleLive::streams.load();
+    if (events) *events = HandleLive::events.load();
+}
+
 extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes)
 {
     if (!c) return SSM_E_INVAL;
@@ -501,8 +527,8 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
     { const int r = wait_pending(c); if (r) return r; }
     const size_t ib = (size_t)g.W * g.H * channels;
     { const int r = ensure_scratch(c, ib * n); if (r) return r; }
-    HIPCHK(c, hipMemcpyAsync(c->d_scratch, img, ib * n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->work[0].pyr, 0xA5, (size_t)n * g.pyr_bytes, c->stream));      // every byte the pyramid owns must be written
+    HIPCHK(c, hipMemcpyAsync(c->d_scratch, img, ib * n, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemsetAsync(c->chain[0].work.pyr, 0xA5, (size_t)n * g.pyr_bytes, c->main.stream));      // every byte the pyramid owns must be written
     PyrBandPlan p; DevBuf<int32_t> own_tab;                             // a plan of this call alone and its band table
     if (bands < 0) p.bands = 0;
     else if (bands == 0) p = n > 1 ? c->pyr_bands : c->pyr_bands1;
@@ -513,11 +539,11 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
         DALLOC(c, own_tab, tab.size()); p.d_tab = own_tab;
         HIPCHK(c, hipMemcpy(own_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
     }
-    int r = make_pyramid(c, c->stream, c->work[0], c->d_scratch, channels, n, p);
-    if (bands > 0) { hipStreamSynchronize(c->stream); own_tab.reset(); }
+    int r = make_pyramid(c, c->main.stream, c->chain[0].work, c->d_scratch, channels, n, p);
+    if (bands > 0) { hipStreamSynchronize(c->main.stream); own_tab.reset(); }
     if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(out, c->work[0].pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->chain[0].work.pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 
@@ -529,11 +555,11 @@ int wait_pending(ssm_ctx* c)
 {
     if (c->pending.empty()) {
         // (an enqueue that failed behind its ring_take has advanced the offsets without registering a finisher: drain what may still read the ring, then rewind)
-        if (c->h_ring_off || c->d_ring_off) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->h_ring_off = 0; c->d_ring_off = 0; }
+        if (c->h_ring_off || c->d_ring_off) { HIPCHK(c, hipStreamSynchronize(c->main.stream)); c->h_ring_off = 0; c->d_ring_off = 0; }
         return SSM_OK;
     }
     int rc = SSM_OK;
-    const hipError_t e = hipStreamSynchronize(c->stream);
+    const hipError_t e = hipStreamSynchronize(c->main.stream);
     if (e != hipSuccess) { c->err = std::string("hipStreamSynchronize: ") + hipGetErrorString(e); rc = SSM_E_HIP; }
     std::vector<std::function<int(ssm_ctx*)>> fins; fins.swap(c->pending);
     for (auto& f : fins) { if (rc == SSM_OK) { const int r = f(c); if (r != SSM_OK) rc = r; } }      // after a failure the later calls' outputs stay untouched
@@ -547,7 +573,7 @@ static int ring_take(ssm_ctx* c, size_t hbytes, size_t dbytes, uint8_t** hp, uin
         int r = wait_pending(c); if (r) return r;                                // out of room: finish what is in flight (its results are delivered now)
         const size_t need = hbytes > dbytes ? hbytes : dbytes;
         if (need > c->d_ring.bytes()) {
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->main.stream));
             c->h_ring.reset(); c->d_ring.reset();
             const size_t nb = need * 4 > ((size_t)8 << 20) ? need * 4 : ((size_t)8 << 20);
             if (c->h_ring.alloc(c, nb)) FAIL(c, SSM_E_HIP, "hipHostMalloc of the staging ring failed");
@@ -579,17 +605,17 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
     // there, through the ring's device mapping -- no 0.6 MB upload, no staging time in front of the first kernel.  (Measured and dropped: the blur on a side stream
     // beside FAST + the quad-tree -- two cross-stream events cost more than the 17 us they hide: 177 -> 223 us from first to last kernel.)
     const bool img_direct = in_place && (size_t)stride == row && host_is_pinned(img), depth_direct = in_place && depth && host_is_pinned(depth);
-    if (img_direct) HIPCHK(c, hipMemcpyAsync(c->d_in_img, img, ib, hipMemcpyHostToDevice, c->stream));       // page-locked input (ssm_host_alloc): no staging pass
+    if (img_direct) HIPCHK(c, hipMemcpyAsync(c->d_in_img, img, ib, hipMemcpyHostToDevice, c->main.stream));       // page-locked input (ssm_host_alloc): no staging pass
     else {
         if ((size_t)stride == row) memcpy(h_in, img, ib);
         else for (int y = 0; y < h; y++) memcpy(h_in + (size_t)y * row, img + (size_t)y * stride, row);
-        HIPCHK(c, hipMemcpyAsync(c->d_in_img, h_in, ib, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_in_img, h_in, ib, hipMemcpyHostToDevice, c->main.stream));
     }
     int32_t* dn = reinterpret_cast<int32_t*>(dp);
     ssm_keypoint* dk = reinterpret_cast<ssm_keypoint*>(dp + 64);
     uint8_t* dd = reinterpret_cast<uint8_t*>(dk + ocap);
     float* dps = reinterpret_cast<float*>(dd + (size_t)ocap * 32);
-    r = orb_detect(c, c->stream, c->work[0], c->d_in_img, channels, 1); if (r) return r;
+    r = orb_detect(c, c->main.stream, c->chain[0].work, c->d_in_img, channels, 1); if (r) return r;
     const uint16_t* d_depth = nullptr;
     if (depth) {
         if (!depth_direct) memcpy(h_in + ib, depth, db);       // (the device is busy with the launches above meanwhile)
@@ -597,9 +623,9 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
         HIPCHK(c, hipHostGetDevicePointer(&mapped, depth_direct ? const_cast<uint16_t*>(depth) : reinterpret_cast<uint16_t*>(h_in + ib), 0));
         d_depth = reinterpret_cast<const uint16_t*>(mapped);
     }
-    r = orb_describe(c, c->stream, c->work[0], d_depth, 1, dk, dd, dps, dn); if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(dn + 1, c->d_status, 4, hipMemcpyDeviceToDevice, c->stream));          // the ORB scratch-overflow word travels in the block's header
-    HIPCHK(c, hipMemcpyAsync(h_out, dp, blk, hipMemcpyDeviceToHost, c->stream));
+    r = orb_describe(c, c->main.stream, c->chain[0].work, d_depth, 1, dk, dd, dps, dn); if (r) return r;
+    HIPCHK(c, hipMemcpyAsync(dn + 1, c->d_status, 4, hipMemcpyDeviceToDevice, c->main.stream));          // the ORB scratch-overflow word travels in the block's header
+    HIPCHK(c, hipMemcpyAsync(h_out, dp, blk, hipMemcpyDeviceToHost, c->main.stream));
     c->pending.push_back([=](ssm_ctx* cc) -> int {
         int32_t hdr[2]; memcpy(hdr, h_out, 8);
         if (hdr[1]) { hipMemset(cc->d_status, 0, 4); FAIL(cc, SSM_E_CAPACITY, "ORB scratch capacity exceeded (status " + std::to_string(hdr[1]) + ")"); }
@@ -659,10 +685,10 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
         uint2* knn = reinterpret_cast<uint2*>(et + expb);
         uint8_t* dout = reinterpret_cast<uint8_t*>(knn) + (((size_t)capT * 8 + 255) & ~(size_t)255);
         int32_t* dn = reinterpret_cast<int32_t*>(dout); ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(dout + 64);
-        HIPCHK(c, hipMemcpyAsync(dd, hp, inb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, k_match_expand(dd, dnk, 0, 2, capm, capT, eq, et, c->stream));
-        HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, 1, 1, ratio, capm, capT, knn, dm, dn, c->stream));
-        HIPCHK(c, hipMemcpyAsync(h_out, dout, outb, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dd, hp, inb, hipMemcpyHostToDevice, c->main.stream));
+        HIPCHK(c, k_match_expand(dd, dnk, 0, 2, capm, capT, eq, et, c->main.stream));
+        HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, 1, 1, ratio, capm, capT, knn, dm, dn, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(h_out, dout, outb, hipMemcpyDeviceToHost, c->main.stream));
         c->pending.push_back([=](ssm_ctx* cc) -> int {
             int32_t n; memcpy(&n, h_out, 4);
             *n_out = n;
@@ -684,14 +710,14 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
         uint2* knn = reinterpret_cast<uint2*>(et + expb);
         ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(knn + capT); int32_t* dn = reinterpret_cast<int32_t*>(dm + nq);
         const int32_t hn[2] = {nq, nt};
-        HIPCHK(c, hipMemcpyAsync(dd, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dd + rowb, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dnk, hn, 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, k_match_expand(dd, dnk, 0, 2, capm, capT, eq, et, c->stream));
-        HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, 1, 1, ratio, capm, capT, knn, dm, dn, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dd, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(dd + rowb, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(dnk, hn, 8, hipMemcpyHostToDevice, c->main.stream));
+        HIPCHK(c, k_match_expand(dd, dnk, 0, 2, capm, capT, eq, et, c->main.stream));
+        HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, 1, 1, ratio, capm, capT, knn, dm, dn, c->main.stream));
         int n = 0;
-        HIPCHK(c, hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         if (want_knn) {
             std::vector<uint2> hk((size_t)nq);
             HIPCHK(c, hipMemcpy(hk.data(), knn, (size_t)nq * 8, hipMemcpyDeviceToHost));
@@ -710,13 +736,13 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
     int32_t* di = reinterpret_cast<int32_t*>(dm + nq); int32_t* ds = di + 2 * (size_t)nq;
     MatchPair* dp = reinterpret_cast<MatchPair*>(ds + 2 * (size_t)nq); int32_t* dn = reinterpret_cast<int32_t*>(dp + 1);
     MatchPair p; p.qoff = 0; p.nq = nq; p.toff = nq; p.nt = nt; p.out_slot = 0;
-    HIPCHK(c, hipMemcpyAsync(dd, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dd + (size_t)nq * 32, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dp, &p, sizeof(p), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_match_pairs(dd, dp, 1, ratio, nq, dm, dn, want_knn ? di : nullptr, want_knn ? ds : nullptr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dd, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(dd + (size_t)nq * 32, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(dp, &p, sizeof(p), hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_match_pairs(dd, dp, 1, ratio, nq, dm, dn, want_knn ? di : nullptr, want_knn ? ds : nullptr, c->main.stream));
     int n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     if (want_knn) {
         HIPCHK(c, hipMemcpy(idx, di, (size_t)nq * 8, hipMemcpyDeviceToHost));
         HIPCHK(c, hipMemcpy(dist, ds, (size_t)nq * 8, hipMemcpyDeviceToHost));
@@ -776,10 +802,10 @@ static int match_refs_enqueue(ssm_ctx* c, const uint8_t* const* refs, const int*
     uint8_t* eq = dp + ((inb + 255) & ~(size_t)255); uint8_t* et = eq + expb;
     uint8_t* knn = et + expb; uint8_t* dout = knn + knnb;
     int32_t* dn = reinterpret_cast<int32_t*>(dout); ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(dout + 256);
-    HIPCHK(c, hipMemcpyAsync(dd, hp, inb, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_match_expand(dd, dnk, 0, rows, capm, capT, eq, et, c->stream));
-    HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, nref, nref, ratio, capm, capT, knn, dm, dn, c->stream));
-    HIPCHK(c, hipMemcpyAsync(h_out, dout, outb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dd, hp, inb, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_match_expand(dd, dnk, 0, rows, capm, capT, eq, et, c->main.stream));
+    HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, nref, nref, ratio, capm, capT, knn, dm, dn, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(h_out, dout, outb, hipMemcpyDeviceToHost, c->main.stream));
     std::vector<ssm_dmatch*> vo(outs, outs + nref); std::vector<int> vc(caps, caps + nref);
     c->pending.push_back([=](ssm_ctx* cc) -> int {
         for (int i = 0; i < nref; i++) {
@@ -824,10 +850,10 @@ extern "C" int ssm_moving_mask(ssm_ctx* c, const uint8_t* sem, int w, int h, int
     if (!sem || !mask) FAIL(c, SSM_E_INVAL, "null argument");
     if (w != c->g.W || h != c->g.H) FAIL(c, SSM_E_INVAL, "frame size differs from the context configuration");
     if (stride < w * 3) FAIL(c, SSM_E_INVAL, "stride smaller than a row");
-    HIPCHK(c, hipMemcpy2DAsync(c->d_in_sem, (size_t)w * 3, sem, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_moving_mask(c->d_in_sem, 1, w, h, c->d_mask, c->stream));
-    HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, (size_t)w * h, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(c->d_in_sem, (size_t)w * 3, sem, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_moving_mask(c->d_in_sem, 1, w, h, c->d_mask, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(mask, c->d_mask, (size_t)w * h, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_backproject(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, int w, int h,
@@ -838,16 +864,16 @@ extern "C" int ssm_backproject(ssm_ctx* c, const uint16_t* depth, const uint8_t*
     if (!depth || !rgb || !sem || !cam || !n_out || (cap > 0 && !out)) FAIL(c, SSM_E_INVAL, "null argument");
     if (w != c->g.W || h != c->g.H) FAIL(c, SSM_E_INVAL, "frame size differs from the context configuration");
     const size_t np = (size_t)w * h;
-    HIPCHK(c, hipMemcpyAsync(c->d_in_depth, depth, np * 2, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_in_img, rgb, np * 3, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_in_sem, sem, np * 3, hipMemcpyHostToDevice, c->stream));
-    if (T) HIPCHK(c, hipMemcpyAsync(c->d_in_pose, T, 128, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_moving_mask(c->d_in_sem, 1, w, h, c->d_mask, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_in_depth, depth, np * 2, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_in_img, rgb, np * 3, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_in_sem, sem, np * 3, hipMemcpyHostToDevice, c->main.stream));
+    if (T) HIPCHK(c, hipMemcpyAsync(c->d_in_pose, T, 128, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_moving_mask(c->d_in_sem, 1, w, h, c->d_mask, c->main.stream));
     HIPCHK(c, k_backproject(c->d_in_depth, c->d_in_img, c->d_in_sem, c->d_mask, T ? c->d_in_pose : nullptr, 1, w, h, *cam, max_distance,
-                            c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, c->d_points, c->stream));
+                            c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, c->d_points, c->main.stream));
     int64_t total = 0;
-    HIPCHK(c, hipMemcpyAsync(&total, c->d_total, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&total, c->d_total, 8, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     *n_out = (int)total;
     if (total > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small (need " + std::to_string(total) + ")");
     HIPCHK(c, hipMemcpy(out, c->d_points, sizeof(ssm_point) * (size_t)total, hipMemcpyDeviceToHost));
@@ -860,7 +886,7 @@ static int ensure_seq(ssm_ctx* c, int n)
     if (n <= c->seq_cap) return SSM_OK;
     const OrbGeom& g = c->g; const int R = c->R;
     // keep the history rows across the re-allocation
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->seq_cap = 0;                                                 // (a failure below leaves some of the outputs empty: the next call allocates again)
     c->capT = (g.cap + 31) & ~31;
     if (c->match_mfma) {       // expanded rows are rebuilt from the bit descriptors at the start of every call (history) and after every ORB sub-batch
@@ -886,11 +912,11 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     const int stages = in->stages ? in->stages : (SSM_STAGE_ORB | SSM_STAGE_MATCH | SSM_STAGE_MAP);
     if ((stages & (SSM_STAGE_ORB | SSM_STAGE_MATCH)) && !in->bgr) FAIL(c, SSM_E_INVAL, "bgr is required");
     if ((stages & SSM_STAGE_MAP) && (!in->depth || !in->bgr || (!in->sem_bgr && !(stages & SSM_STAGE_SEGNET)))) FAIL(c, SSM_E_INVAL, "bgr, depth and sem_bgr (or SSM_STAGE_SEGNET) are required for the map stage");
-    const OrbGeom& g = c->g; const int R = c->R, n = in->n, W = g.W, H = g.H; hipStream_t s = c->stream;
+    const OrbGeom& g = c->g; const int R = c->R, n = in->n, W = g.W, H = g.H; const hipStream_t s = c->main.stream;
     const size_t npix = (size_t)W * H;
     // fused map launches of an earlier call that nobody has looked at since (no ssm_sync / map read in between): their skipped blocks -- if any -- are run again NOW,
     // while the launch descriptors still point at that call's outputs (ensure_seq below may re-allocate the per-frame point counts)
-    if (c->map_unexamined) { const int r0 = map_settle(c, c->map_tail ? c->map_tail : c->stream, 0); if (r0) return r0; }
+    if (c->map_unexamined) { const int r0 = map_settle(c, c->map_tail ? c->map_tail : c->main.stream, 0); if (r0) return r0; }
     int r = ensure_seq(c, n > 0 ? n : 1); if (r) return r;
     c->recs.clear(); c->pool_used = 0;
     // history rows
@@ -908,28 +934,26 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     const bool mfma = c->match_mfma && (stages & SSM_STAGE_MATCH);
     if (mfma) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, 0, R, g.cap, c->capT, c->d_exp_q, c->d_exp_t, s));      // the history rows
     // Two streams: the ORB -> match chain of a sub-batch and its (SegNet ->) map stage share no data, only the inputs, so the
-    // map side runs on stream2.  The chain's latency-bound kernels (pyramid, octree, describe) then overlap VALU/MFMA-bound
-    // map / SegNet work.  stream2 starts behind everything already queued on the context stream and is joined at the end.
+    // map side runs on side[0].  The chain's latency-bound kernels (pyramid, octree, describe) then overlap VALU/MFMA-bound
+    // map / SegNet work.  side[0] starts behind everything already queued on the context stream and is joined at the end.
     const bool side_work = (stages & (SSM_STAGE_MAP | SSM_STAGE_SEGNET)) != 0;
     // Two chains: without the SegNet stage (one activation workspace) and with two or more sub-batches, alternate sub-batches run
-    // their whole ORB -> match -> map chain on the context stream and on stream2 (and stream4, from three sub-batches on) with an OrbWork each, so that one chain's
+    // their whole ORB -> match -> map chain on the context stream and on side[0] (and side[2], from three sub-batches on) with an OrbWork each, so that one chain's
     // latency-bound kernels (quad-tree, pyramid launches, block tails) overlap the other chain's VALU-bound ones.  The only
     // dependence between neighbours is the matcher's: the reference descriptors of sub-batch b - 1 (an event per chain).
     const bool two_chains = !c->serialize && !(stages & SSM_STAGE_SEGNET) && n > c->B && (stages & SSM_STAGE_ORB) && (W & 15) == 0;
     const bool side = side_work && !c->serialize && !two_chains;
     if (side || two_chains) { r = ensure_side_streams(c); if (r) return r; }
     if (two_chains) { r = ensure_alt(c); if (r) return r; }
-    if (side || two_chains) { HIPCHK(c, hipEventRecord(c->ev_fork, c->stream)); HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0)); }
     const int nch = two_chains ? (n > 2 * c->B ? 3 : 2) : 1;
-    if (nch == 3) HIPCHK(c, hipStreamWaitEvent(c->stream4, c->ev_fork, 0));
     const bool map3 = two_chains && c->map_stream == 1;
-    if (map3) HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_fork, 0));
-    const hipStream_t chain_stream[3] = {c->stream, c->stream2, c->stream4};
+    Lane* const used[3] = {&c->side[0], nch == 3 ? &c->side[2] : nullptr, map3 ? &c->side[1] : nullptr};      // the side lanes of this call, in fork / join order
+    if (side || two_chains) { r = lanes_fork(c, {used[0], used[1], used[2]}); if (r) return r; }
     int bi = 0;
     for (int f0 = 0; f0 < n; f0 += c->B, bi++) {
         const int nb = (n - f0 < c->B) ? n - f0 : c->B;
         const int chain = bi % nch;
-        const hipStream_t cs = chain_stream[chain]; OrbWork& work = c->work[chain];      // this chain's stream and ORB workspace
+        OrbChain& ch = c->chain[chain]; const hipStream_t cs = ch.lane->stream; OrbWork& work = ch.work;      // this chain's stream and ORB workspace
         auto front = [&]() -> int {                                       // ORB -> match of this sub-batch
             if (stages & SSM_STAGE_ORB) {
                 r = run_orb(c, cs, work, in->bgr + (size_t)f0 * npix * 3, 3, in->depth ? in->depth + (size_t)f0 * npix : nullptr, nb,
@@ -940,8 +964,8 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
                     // The matcher of sub-batch bi reads the descriptor rows of the R preceding FRAMES, i.e. (max_batch < tracker_ref_frames) of several
                     // preceding sub-batches.  Every other chain's newest event is the ORB + expand of one of bi-1 .. bi-(nch-1); an older sub-batch sits on
                     // one of those streams (or on this one) in front of that record, so waiting on all of them orders the matcher behind every row it reads.
-                    HIPCHK(c, hipEventRecord(c->ev_orb[chain], cs));
-                    for (int k = 1; k < nch && k <= bi; k++) HIPCHK(c, hipStreamWaitEvent(cs, c->ev_orb[(bi - k) % nch], 0));
+                    HIPCHK(c, hipEventRecord(ch.orb_done, cs));
+                    for (int k = 1; k < nch && k <= bi; k++) HIPCHK(c, hipStreamWaitEvent(cs, c->chain[(bi - k) % nch].orb_done, 0));
                 }
             }
             if (stages & SSM_STAGE_MATCH) {
@@ -957,12 +981,13 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
         };
         auto back = [&]() -> int {                                        // (SegNet ->) map of this sub-batch
             if (!side_work) return SSM_OK;
-            const hipStream_t s = map3 ? c->stream3 : side ? c->stream2 : cs;      // the map stream, stream2 beside a single chain, or the chain's own stream
+            Lane& ml = map3 ? c->side[1] : side ? c->side[0] : *ch.lane;      // the map lane, side[0] beside a single chain, or the chain's own lane
+            const hipStream_t s = ml.stream;
             const uint8_t* sem_src = in->sem_bgr ? in->sem_bgr + (size_t)f0 * npix * 3 : nullptr;
             if (stages & SSM_STAGE_SEGNET) {          // Classifier in the loop (the variant commented out at src/rgbdframe.cpp:119-136)
                 r = seg_init(c); if (r) return r;
                 prof_begin(c, s, "segnet");
-                r = seg_forward_dev(c, s, in->bgr + (size_t)f0 * npix * 3, nb, nullptr, c->seg->d_sem_gen, 0); if (r) return r;
+                r = seg_forward_dev(c, ml, in->bgr + (size_t)f0 * npix * 3, nb, nullptr, c->seg->d_sem_gen, 0); if (r) return r;
                 prof_end(c, s);
                 sem_src = c->seg->d_sem_gen;
             }
@@ -1001,11 +1026,9 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
         if (map_first) { r = back(); if (r) return r; r = front(); if (r) return r; }
         else           { r = front(); if (r) return r; r = back(); if (r) return r; }
     }
-    if (side || two_chains) { HIPCHK(c, hipEventRecord(c->ev_join, c->stream2)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); }
-    if (nch == 3) { HIPCHK(c, hipEventRecord(c->ev_join4, c->stream4)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join4, 0)); }
-    if (map3) { HIPCHK(c, hipEventRecord(c->ev_join3, c->stream3)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join3, 0)); }
+    if (side || two_chains) { r = lanes_join(c, {used[0], used[1], used[2]}); if (r) return r; }
     // where the map's newest work sits (ssm_ctx::map_tail): one side stream, or the context stream (serialised, no map stage, or the chains' own streams in turn)
-    if (stages & SSM_STAGE_MAP) c->map_tail = map3 ? c->stream3 : (side ? c->stream2 : nullptr);
+    if (stages & SSM_STAGE_MAP) c->map_tail = map3 ? (hipStream_t)c->side[1].stream : side ? (hipStream_t)c->side[0].stream : nullptr;
     c->prev_n = n;
     if (out) {
         out->kps = c->d_kps; out->desc = desc; out->pos3d = c->d_pos3d; out->nkp = nkp; out->matches = c->d_matches; out->nmatch = c->d_nmatch;
@@ -1029,7 +1052,7 @@ extern "C" int ssm_dev_free(ssm_ctx* c, void* p)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     if (p) HIPCHK(c, hipFree(p));
     return SSM_OK;
 }
@@ -1037,8 +1060,8 @@ extern "C" int ssm_memcpy_h2d(ssm_ctx* c, void* dst, const void* src, size_t byt
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_dev_mem_info(ssm_ctx* c, size_t* free_bytes, size_t* total_bytes)
@@ -1052,14 +1075,14 @@ extern "C" int ssm_memcpy_h2d_async(ssm_ctx* c, void* dst, const void* src, size
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_memcpy_d2h_async(ssm_ctx* c, void* dst, const void* src, size_t bytes)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_host_alloc(size_t bytes, void** out)
@@ -1082,8 +1105,8 @@ extern "C" int ssm_memcpy_d2h(ssm_ctx* c, void* dst, const void* src, size_t byt
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_synth_frames_dev(ssm_ctx* c, uint64_t seed, int first, int n, int w, int h,
@@ -1092,6 +1115,6 @@ extern "C" int ssm_synth_frames_dev(ssm_ctx* c, uint64_t seed, int first, int n,
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (n <= 0 || !bgr || !depth || !sem) FAIL(c, SSM_E_INVAL, "bad arguments");
-    HIPCHK(c, k_synth(seed, first, n, w, h, bgr, depth, sem, lab, pose, c->stream));
+    HIPCHK(c, k_synth(seed, first, n, w, h, bgr, depth, sem, lab, pose, c->main.stream));
     return SSM_OK;
 }

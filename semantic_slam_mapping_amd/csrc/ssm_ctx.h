@@ -46,6 +46,60 @@ public:
 };
 template <class T> using PinBuf = DevBuf<T, true>;
 
+// Owners of ONE stream / ONE event the library created: move-only, empty by default, converting to the raw handle.  ensure() creates the handle if it is
+// missing (streams: hipStreamNonBlocking; events: without timing, for ordering -- the profiling pool asks for timing); reset() and the destructor destroy
+// it.  As with DevBuf nothing here waits for the device.  Counted process-wide: ssm_debug_live_handles.
+struct HandleLive { static inline std::atomic<int> streams{0}, events{0}; };
+class Stream {
+    hipStream_t h = nullptr;
+public:
+    Stream() = default;
+    Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+    Stream(Stream&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Stream& operator=(Stream&& o) noexcept { if (this != &o) { reset(); h = std::exchange(o.h, nullptr); } return *this; }
+    ~Stream() { reset(); }
+    operator hipStream_t() const { return h; }
+    hipError_t ensure() { if (h) return hipSuccess; const hipError_t e = hipStreamCreateWithFlags(&h, hipStreamNonBlocking); if (e == hipSuccess) HandleLive::streams++; else h = nullptr; return e; }
+    void reset() { if (!h) return; (void)hipStreamDestroy(h); HandleLive::streams--; h = nullptr; }
+};
+class Event {
+    hipEvent_t h = nullptr;
+public:
+    Event() = default;
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+    Event(Event&& o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    Event& operator=(Event&& o) noexcept { if (this != &o) { reset(); h = std::exchange(o.h, nullptr); } return *this; }
+    ~Event() { reset(); }
+    operator hipEvent_t() const { return h; }
+    hipError_t ensure(bool timing = false)
+    {
+        if (h) return hipSuccess;
+        const hipError_t e = timing ? hipEventCreate(&h) : hipEventCreateWithFlags(&h, hipEventDisableTiming);
+        if (e == hipSuccess) HandleLive::events++; else h = nullptr;
+        return e;
+    }
+    void reset() { if (!h) return; (void)hipEventDestroy(h); HandleLive::events--; h = nullptr; }
+};
+// The fan of k_sgbm's forms 0 / 1 (kernels_sgbm.hip sgbm_aggregate): four streams for the scan directions that run beside the caller's stream, forked from and
+// joined into it by events on every call, so calls on one lane stay ordered and two lanes never share an event.  Owned by the lane and created at its first
+// form-0/1 launch (form 2, the default, needs none); a creation that failed half-way resumes at the next.
+struct SgFan {
+    Stream s[4]; Event fork, done[4];
+    hipError_t ensure()
+    {
+        hipError_t e = fork.ensure();
+        for (int i = 0; i < 4 && e == hipSuccess; i++) { e = s[i].ensure(); if (e == hipSuccess) e = done[i].ensure(); }
+        return e;
+    }
+};
+// What belongs to ONE stream of a context: the stream, the event that joins it back into the main stream (lanes_join; unused on the main lane) and the state
+// the launchers keep per stream -- passed to them as arguments, created where the lane first needs it.
+struct Lane {
+    Stream stream; Event joined;
+    SgFan sg;                           // k_sgbm, forms 0 / 1
+    DevBuf<int> conv_tiles;             // CONV_QUEUE_INTS tile counters of the SegNet conv kernels (ssm_segnet_abi.hip seg_lane_tiles); launches on a stream are ordered, so they share it
+};
+
 struct VoxTable {           // tab[slots] | occ[slots] | counter block (32 bytes: count, flags, overflow records, overflow capacity, overflow list address)
     DevBuf<ssm_voxel> tab; uint32_t* occ = nullptr; int32_t* counters = nullptr; int cap_log2 = 0;        // occ, counters: inside tab's allocation
     DevBuf<ssm_voxel> ovf; int ovf_cap = 0;       // the overflow list of the context map (kernels_map.hip vox_overflow_slot); the temporary tables have none
@@ -55,7 +109,7 @@ struct VoxTable {           // tab[slots] | occ[slots] | counter block (32 bytes
 static const int VOX_OVF_RECORDS = 1 << 18;          // 29 MB per context; a context that runs the fused map stage (ssm_seq_process) trades it for the large list of map_ensure_stream_list
 // one launch of the fused map stage, kept so that blocks it skipped can be run again (ssm_map.hip map_redo)
 struct MapLaunch { const uint16_t* depth; const uint8_t* rgb; const uint8_t* sem; const double* pose; int n, w, h; int32_t* npoints; bool valid; };
-struct StageRec { const char* name; hipEvent_t a, b; };
+struct StageRec { const char* name; hipEvent_t a, b; };      // a, b: events of the context's profiling pool
 // SegNet driving_webdemo: 26 conv layers; op list interleaves pools / unpools
 struct SegLayerDef { int cin, cout, h, w; };
 static const int SEG_NW = 480, SEG_NH = 360, SEG_NCLS = 12, SEG_LAYERS = 26;
@@ -112,15 +166,19 @@ struct OrbWork {
     DevBuf<uint8_t> pyr, blur; DevBuf<int32_t> ncand; int32_t* cellmax = nullptr /* inside ncand's allocation */; DevBuf<cand_t> cand; DevBuf<uint16_t> nodeof;
     DevBuf<uint32_t> sel; DevBuf<int32_t> nsel; DevBuf<uint4> kpaux;
 };
+// one ORB -> match chain of ssm_seq_process: the lane it runs on, its workspace, and the event behind its newest ORB + expand (what the next sub-batch's matcher waits for)
+struct OrbChain { Lane* lane; OrbWork work; Event orb_done; };
 
 struct ssm_ctx {
     std::mutex mu;
     int device = 0;
-    hipStream_t stream = nullptr;       // the context's main stream: created in ctx_init and never re-pointed; chain 0 of ssm_seq_process
-    bool side_ready = false;            // ensure_side_streams completed
-    hipStream_t stream2 = nullptr;      // ssm_seq_process: chain 1; with a single chain, the SegNet + map stage of a sub-batch runs here beside it (stereo: SGBM)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    hipStream_t stream3 = nullptr; hipEvent_t ev_join3 = nullptr; int map_stream = 1;   // two-chain mode: the map stage on a stream of its own (SSM_MAP_STREAM=0: on the chain's stream)
+    DeviceInfo dev;                     // CU count and LDS limit of `device`, asked once (ctx_init): what the launchers size grids and dynamic LDS from
+    // main: the context's stream, created in ctx_init and never re-pointed; every per-call entry point runs here, and chain 0 of ssm_seq_process.
+    // side[]: created at first use (ensure_side_streams), forked from and joined into main by every call that uses them (lanes_fork / lanes_join):
+    //   side[0]  ssm_seq_process: chain 1; with a single chain, the SegNet + map stage of a sub-batch runs here beside it.  Stereo: SGBM (first workspace)
+    //   side[1]  two-chain mode: the map stage on a stream of its own (SSM_MAP_STREAM=0: on the chain's stream).  Stereo: SGBM, second workspace
+    //   side[2]  the third chain, used when a call has more than two sub-batches.  Stereo: SGBM, third workspace
+    Lane main, side[3]; Event forked; bool side_ready = false /* ensure_side_streams completed */; int map_stream = 1;
     ssm_config cfg{};
     OrbGeom g{};
     std::string err;
@@ -135,12 +193,10 @@ struct ssm_ctx {
     struct { const int32_t *xofs[SSM_MAX_LEVELS], *yofs[SSM_MAX_LEVELS]; const int16_t *xa[SSM_MAX_LEVELS], *ya[SSM_MAX_LEVELS]; const void *xgrp[SSM_MAX_LEVELS], *xgrp8[SSM_MAX_LEVELS]; } pyr_tabs = {};
     PyrBandPlan pyr_bands, pyr_bands1;       // resize4_kernel_bands for batches / for the per-frame call (bands == 0: gray_kernel + k_pyramid)
     DevBuf<int32_t> d_band_tab, d_band_tab1; // their band tables (PyrBandPlan::d_tab points here)
-    // ORB workspaces (B frames each): work[0] serves every entry point that runs on `stream`; ssm_seq_process runs successive sub-batches as up to three
-    // ORB -> match chains -- chain k on its own stream (stream, stream2, stream4) with work[k]; work[1], work[2] are allocated at first use
-    OrbWork work[3];
+    // the ORB -> match chains (a workspace of B frames each): chain[0] serves every entry point that runs on the main lane; ssm_seq_process runs successive
+    // sub-batches on up to three chains, each on its own lane; the workspaces of chains 1, 2 are allocated at first use
+    OrbChain chain[3] = {{&main}, {&side[0]}, {&side[2]}};
     DevBuf<int32_t> d_status;           // the ORB scratch-overflow word: one, shared by all chains
-    hipEvent_t ev_orb[3] = {nullptr, nullptr, nullptr};
-    hipStream_t stream4 = nullptr; hipEvent_t ev_join4 = nullptr;      // the third chain, used when a call has more than two sub-batches
     DevBuf<uint8_t> d_mask; DevBuf<int32_t> d_chunk_cnt; DevBuf<int64_t> d_chunk_off, d_total;
     DevBuf<ssm_point> d_points;
     DevBuf<ssm_point> d_vmap; int vmap_n = 0;    // Mapper::viewer's filtered map, device-resident (ssm_viewer_map_update)
@@ -154,9 +210,9 @@ struct ssm_ctx {
     DevBuf<unsigned long long> d_pnp_xchg; unsigned pnp_epoch = 0;   // ssm_pnp_solve's cluster: the exchange ring (persistent) and the launch number its pass tags start from
     bool pnp_solve_one_block = false;                        // ssm_pnp_solve: a cluster of eight blocks timed out once -> one block per solve from then on
     DevBuf<uint8_t> d_scratch2;
-    // the stream that holds the newest work on the context map when that is a side stream of ssm_seq_process (joined into `stream` by an event, so everything queued
-    // on `stream` afterwards is ordered behind it): ssm_map_size / ssm_map_export_table_dev read the map there and wait for THAT stream only -- the ORB -> match chain of
-    // the call's last sub-batch keeps running.  nullptr: the map's newest work is on `stream`.
+    // the stream that holds the newest work on the context map when that is a side lane of ssm_seq_process (joined into the main stream by an event, so everything queued
+    // on the main stream afterwards is ordered behind it): ssm_map_size / ssm_map_export_table_dev read the map there and wait for THAT stream only -- the ORB -> match chain of
+    // the call's last sub-batch keeps running.  nullptr: the map's newest work is on the main stream.
     hipStream_t map_tail = nullptr;
     // sequence outputs
     int seq_cap = 0, prev_n = -1;
@@ -167,9 +223,10 @@ struct ssm_ctx {
     MapLaunch map_ring[8] = {}; unsigned map_ring_next = 0; DevBuf<int32_t> d_redo; std::vector<int32_t> map_skipped;    // launches that may still have skipped blocks; ids to run again (host)
     std::vector<hipStream_t> map_launch_streams; long map_redone = 0;      // streams fused launches were queued on; blocks run again so far
     bool map_unexamined = false;                            // a fused map launch was queued since the counters were last read on a drained stream
+    MapDiv map_div{}; bool map_div_exact = false;          // cfg.camera's reciprocals and whether the fused map stage may divide by them (k_map_div, once: ctx_init)
     VoxTable map, tmp; bool map_full_reported = false;   // table-full already reported by check_device_flags (reset by ssm_map_clear)
     // the context map grows (map_settle); between the map launches of ssm_seq_process its counters come back through a two-slot ring of asynchronous copies
-    int vox_max_log2 = 28; PinBuf<int32_t> h_map_snap; hipEvent_t map_snap_ev[2] = {nullptr, nullptr}; uint64_t map_launches = 0; int map_grown = 0;
+    int vox_max_log2 = 28; PinBuf<int32_t> h_map_snap; Event map_snap_ev[2]; uint64_t map_launches = 0; int map_grown = 0;
     double map_vpf = -1.0;                                  // voxels (+ overflow records) per fused frame, the largest rate seen on this context; < 0: none yet
     int64_t map_frames = 0, map_snap_frames[2] = {0, 0}, map_known_total = 0, map_known_frames = 0;     // frames fused since the last clear; at the ring's snapshots; the last count the host has seen and when
     // multi-GPU: the communicator of ssm_comm_init_rank (one rank per context / GPU) and the gathered counts
@@ -187,7 +244,7 @@ struct ssm_ctx {
     PinBuf<uint8_t> h_ring; DevBuf<uint8_t> d_ring /* both of d_ring.bytes() */; size_t h_ring_off = 0, d_ring_off = 0;
     std::vector<std::function<int(ssm_ctx*)>> pending;
     bool serialize = false;             // profiling mode 2: keep the side work of ssm_seq_process on the context stream (clean per-stage times)
-    std::vector<StageRec> recs; std::vector<hipEvent_t> pool; size_t pool_used = 0;
+    std::vector<StageRec> recs; std::vector<Event> pool; size_t pool_used = 0;
     std::vector<std::string> stage_names; std::vector<float> stage_ms; std::vector<int> stage_launches;
 };
 
@@ -220,6 +277,9 @@ SSM_HIDDEN int check_device_flags(ssm_ctx* c, bool with_map);
 SSM_HIDDEN int wait_pending(ssm_ctx* c);
 SSM_HIDDEN bool host_is_pinned(const void* p);             // page-locked host memory (ssm_host_alloc, hipHostRegister)?
 SSM_HIDDEN int ensure_side_streams(ssm_ctx* c);
+// fork: the listed side lanes wait for everything queued on the main stream so far; join: the main stream waits for everything queued on them.  Null entries are skipped.
+SSM_HIDDEN int lanes_fork(ssm_ctx* c, std::initializer_list<Lane*> lanes);
+SSM_HIDDEN int lanes_join(ssm_ctx* c, std::initializer_list<Lane*> lanes);
 // ssm_map.hip
 SSM_HIDDEN int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2, const VoxTable* lists = nullptr);      // lists: the table whose overflow list the counter block names (default: t's own)
 SSM_HIDDEN int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out = nullptr);
@@ -228,6 +288,6 @@ SSM_HIDDEN int map_after_launch(ssm_ctx* c, hipStream_t s, int frames, bool inpu
 SSM_HIDDEN int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L);      // one launch of the fused map stage on the context map, recorded for a redo
 // ssm_segnet_abi.hip
 SSM_HIDDEN int seg_init(ssm_ctx* c);
-SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
+SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, Lane& lane, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
 // ssm_stereo_abi.hip
 SSM_HIDDEN int sgbm_recover(ssm_ctx* c);

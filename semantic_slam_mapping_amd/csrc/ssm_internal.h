@@ -69,6 +69,13 @@ struct OrbGeom {
 // candidate: lo = x | y<<12 | score<<24 (x,y relative to minBorder), hi = rank (cell-major raster order)
 typedef uint2 cand_t;
 
+// What the launchers size grids and dynamic LDS from, asked once per context (ssm_abi.hip ctx_init); the defaults are the fall-backs when a query fails.
+struct DeviceInfo { int id = 0, cus = 256, max_lds = 160 * 1024; };
+// Dynamic LDS above the 64 KB default needs the attribute on the current device's copy of the function: set once per (device, function) to `limit`, the largest
+// size any launch of it will ask for -- not per launch: the call can serialise against kernels in flight.  The set of pairs already done is process-global on
+// purpose: the attribute belongs to the device and the function, not to a context.  bytes <= 48 KB: nothing to do.
+hipError_t allow_dynamic_lds(const void* fn, size_t bytes, int limit);
+
 // ---- launchers (each enqueues on `s`; returns hipGetLastError()) ----
 hipError_t k_gray(const uint8_t* img, int channels, int n, const OrbGeom& g, uint8_t* pyr, hipStream_t s);
 hipError_t k_copy_gray_strided(const uint8_t* img, int stride, const OrbGeom& g, uint8_t* pyr, hipStream_t s);
@@ -151,8 +158,11 @@ hipError_t k_voxel_insert(const ssm_point* pts, const int64_t* n_dev, int64_t n_
 // the fused map stage (kernels_map.hip map_stream2_kernel): n frames of w x h (w % 16 == 0, w <= 4096).  skip: the context's skip list (k_map_fuse_skip_cap() ints,
 // counted in counters[6]); hw: a block that starts with more than hw records in the overflow list logs itself there and adds nothing; tag: the launch's slot in the
 // host's ring of launch descriptors.  nredo > 0: run the blocks redo_ids[0 .. nredo) (device; entries as logged) of the launch with these arguments again.
+// md, exact: k_map_div of cam, which the caller computes once per camera
+struct MapDiv { double rscale, rfx, rfy; };      // the reciprocals of cam.scale, fx, fy (kernels_map.hip markstein_div)
+bool k_map_div(const ssm_camera& cam, MapDiv& md);      // false: these divisors need the division itself (a 65,536-step host check)
 hipError_t k_map_fuse(const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const double* pose, int n, int w, int h,
-                      ssm_camera cam, double max_distance, float leaf,
+                      ssm_camera cam, const MapDiv& md, bool exact, double max_distance, float leaf,
                       ssm_voxel* tab, int cap_log2, int32_t* counters, int32_t* npoints, hipStream_t s, int32_t* skip, int hw, int tag, const int32_t* redo_ids, int nredo);
 int k_map_fuse_blocks_per_frame(int w, int h);
 int k_map_fuse_block_records(void);        // overflow records one block can append at most
@@ -177,18 +187,20 @@ hipError_t k_synth(uint64_t seed, int first, int n, int w, int h, uint8_t* bgr, 
 // SegNet (kernels_segnet.hip)
 hipError_t k_segnet_prep(const uint8_t* bgr, int n, int sw, int sh, int dw, int dh, const int32_t* xofs, const int16_t* xa,
                          const int32_t* yofs, const int16_t* ya, void* out_f16, hipStream_t s);
-hipError_t k_segnet_begin(hipStream_t s);
-void k_segnet_release_stream(hipStream_t s);     // per-stream helper state of the SegNet / SGBM launchers, freed by ssm_destroy
-void k_sgbm_release_stream(hipStream_t s);
+// the tile counters of the conv kernels (self-resetting, see conv3x3_dma2_kernel): CONV_QUEUE_INTS zeroed ints per stream, owned by the caller (Lane::conv_tiles)
+#define CONV_QUEUE_INTS 1024          // a counter pair per (XCD group, cout tile): 8 x 32 x 2 at most
+hipError_t k_segnet_begin(int* tiles, hipStream_t s);
 // wt_wino != nullptr: the layer's weights transformed for the Winograd F(2, 3) kernel ([cout tile 64][cin chunk 32][tap = 4 dy + k][c8 4][cout 64][8] fp16): that kernel runs
 hipError_t k_segnet_conv(const void* in, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W,
-                         int CinPad, int Cout, int relu, hipStream_t s, const void* wt_wino = nullptr);
+                         int CinPad, int Cout, int relu, const DeviceInfo& dev, int* tiles, hipStream_t s, const void* wt_wino = nullptr);
 // nb frames per launch: left / right [nb][h][w], disp_out [nb][h][w]
 size_t k_sgbm_workspace_bytes(int w, int h, const ssm_sgbm_params& p, int nb, int form_cfg);      // sized for the configured formulation (0 = the default), never less than one frame in the largest
 bool sgbm_cost_geometry(int D, int SW, int* TX_out, size_t* lds_out);      // false: SADWindowSize too wide for the streaming cost kernel
 // fail_flag: device int the sweep kernel ORs 1 into when a strip hand-off times out (never on a healthy device; the host turns it into SSM_E_HIP)
-hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int nb, const ssm_sgbm_params& p, void* workspace, size_t ws_bytes, int16_t* disp_out, int raw_only, hipStream_t s, int* fail_flag = nullptr,
-                  int form_cfg = 0, int concurrent = 1);
+// fan: the lane's side streams for forms 0 / 1 (ssm_ctx.h SgFan), created here when such a form first runs
+struct SgFan;
+hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int nb, const ssm_sgbm_params& p, void* workspace, size_t ws_bytes, int16_t* disp_out, int raw_only,
+                  const DeviceInfo& dev, SgFan& fan, hipStream_t s, int* fail_flag = nullptr, int form_cfg = 0, int concurrent = 1);
 // medianBlur 3 (op bit 0: src -> dst) and / or filterSpeckles (bit 1: in place on dst) on nb stacked w x h maps, launched as k_sgbm's last steps; parent / count nb*w*h ints
 hipError_t k_sgbm_post(const int16_t* src, int16_t* dst, int w, int h, int nb, int op, int newVal, int maxSpeckleSize, int maxDiff, int* parent, int* count, hipStream_t s);
 hipError_t k_sgbm_depth(const int16_t* disp, int w, int h, int nb, double baseline, double cu, double cv, double f, double roix, double roiy, double roiz, double scale,
@@ -198,12 +210,12 @@ hipError_t k_vo_estimate(const ssm_pmatch* m, int n, const ssm_vo_params& P, con
 hipError_t k_vo_estimate_batch(const ssm_pmatch* m_all, int stride, const int32_t* n_all, int nb, const ssm_vo_params& P, const uint32_t* rand_stream, int iters,
                                int32_t* consumed, int32_t* rand_off, double* tr_all, int32_t* count, double* tr_out, int32_t* inliers, int32_t* result, hipStream_t s);
 hipError_t k_segnet_conv_argmax(const void* in, const void* wt, const float* scale, const float* shift, uint8_t* labels, int n, int H, int W,
-                                int CinPad, int Cout, hipStream_t s);
+                                int CinPad, int Cout, const DeviceInfo& dev, int* tiles, hipStream_t s);
 hipError_t k_segnet_conv_pool(const void* in, const void* wt, const float* scale, const float* shift, void* out, uint8_t* code, int n, int H, int W,
-                              int CinPad, int Cout, hipStream_t s);
+                              int CinPad, int Cout, const DeviceInfo& dev, int* tiles, hipStream_t s);
 int k_segnet_conv_unpool_available();
 hipError_t k_segnet_conv_unpool(const void* pooled, const uint8_t* ucode, const void* wt, const float* scale, const float* shift, void* out, int n, int H, int W,
-                                int CinPad, int Cout, hipStream_t s);
+                                int CinPad, int Cout, const DeviceInfo& dev, int* tiles, hipStream_t s);
 hipError_t k_segnet_pool(const void* in, int n, int H, int W, int C, void* out, uint8_t* code, hipStream_t s);
 hipError_t k_segnet_unpool(const void* in, const uint8_t* code, int n, int PH, int PW, int C, void* out, int H, int W, hipStream_t s);
 hipError_t k_segnet_argmax(const void* logits, int n, int npix, int Cstore, int ncls, uint8_t* labels, hipStream_t s);

@@ -29,8 +29,8 @@ template <class T> static int grow_keep(ssm_looper* l, DevBuf<T>& b, size_t keep
 {
     ssm_ctx* c = l->c;
     DevBuf<T> nb; { const int r = nb.alloc(c, count); if (r) return r; }
-    if (keep) HIPCHK(c, hipMemcpyAsync(nb, b, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // the old buffer goes: nothing queued may still read it
+    if (keep) HIPCHK(c, hipMemcpyAsync(nb, b, keep * sizeof(T), hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));             // the old buffer goes: nothing queued may still read it
     b = std::move(nb);
     return SSM_OK;
 }
@@ -46,12 +46,12 @@ static int looper_reserve(ssm_looper* l, int add_entries, long long add_nnz)
         { PinBuf<int32_t> nh; const int r = nh.alloc(c, (size_t)nc); if (r) return r;            // (grow_keep has drained the stream: no copy still reads the old block)
           if (l->entries) memcpy(nh, l->h_frame_ids, (size_t)l->entries * 4);
           l->h_frame_ids = std::move(nh); }
-        if (!l->entry_cap) HIPCHK(c, hipMemsetAsync(l->d_offsets, 0, 4, c->stream));
+        if (!l->entry_cap) HIPCHK(c, hipMemsetAsync(l->d_offsets, 0, 4, c->main.stream));
         l->entry_cap = nc;
     }
     if (l->nnz_ub + add_nnz > l->nnz_cap) {
         int32_t exact = 0;
-        if (l->entries) { HIPCHK(c, hipMemcpyAsync(&exact, l->d_offsets + l->entries, 4, hipMemcpyDeviceToHost, c->stream)); HIPCHK(c, hipStreamSynchronize(c->stream)); }
+        if (l->entries) { HIPCHK(c, hipMemcpyAsync(&exact, l->d_offsets + l->entries, 4, hipMemcpyDeviceToHost, c->main.stream)); HIPCHK(c, hipStreamSynchronize(c->main.stream)); }
         l->nnz_ub = exact;
         if (l->nnz_ub + add_nnz > 0x7FFFFFFFll) LFAIL(l, SSM_E_CAPACITY, "looper: the database would exceed 2^31 values");
         if (l->nnz_ub + add_nnz > l->nnz_cap) {
@@ -67,7 +67,7 @@ static int looper_stage(ssm_looper* l, int frames)
 {
     ssm_ctx* c = l->c;
     if (frames <= l->stage_frames) return SSM_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     int nf = l->stage_frames ? l->stage_frames : 1; while (nf < frames) nf *= 2;
     const size_t n = (size_t)nf * l->cap;
     DALLOC(c, l->d_words, n); DALLOC(c, l->d_st_ids, n); DALLOC(c, l->d_st_vals, n); DALLOC(c, l->d_st_m, nf);
@@ -81,10 +81,10 @@ static int looper_add_enqueue(ssm_looper* l, const uint8_t* desc_dev, const int3
     { const int r = looper_reserve(l, frames, nnz_bound); if (r) return r; }
     { const int r = looper_stage(l, frames); if (r) return r; }
     memcpy(l->h_frame_ids + l->entries, frame_ids, (size_t)frames * 4);
-    HIPCHK(c, hipMemcpyAsync(l->d_frame_ids + l->entries, l->h_frame_ids + l->entries, (size_t)frames * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_bow_words(l->tree, desc_dev, nkp_dev, n_fixed, frames, l->cap, l->d_words, l->variant, c->stream));
-    HIPCHK(c, k_bow_frame(l->d_words, l->d_weight, nkp_dev, n_fixed, frames, l->cap, l->P, l->d_st_ids, l->d_st_vals, l->d_st_m, c->stream));
-    HIPCHK(c, k_bow_append(l->d_st_ids, l->d_st_vals, l->d_st_m, frames, l->cap, l->d_offsets, l->entries, l->d_ids, l->d_vals, l->nnz_cap, l->d_hdr, c->stream));
+    HIPCHK(c, hipMemcpyAsync(l->d_frame_ids + l->entries, l->h_frame_ids + l->entries, (size_t)frames * 4, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_bow_words(l->tree, desc_dev, nkp_dev, n_fixed, frames, l->cap, l->d_words, l->variant, c->main.stream));
+    HIPCHK(c, k_bow_frame(l->d_words, l->d_weight, nkp_dev, n_fixed, frames, l->cap, l->P, l->d_st_ids, l->d_st_vals, l->d_st_m, c->main.stream));
+    HIPCHK(c, k_bow_append(l->d_st_ids, l->d_st_vals, l->d_st_m, frames, l->cap, l->d_offsets, l->entries, l->d_ids, l->d_vals, l->nnz_cap, l->d_hdr, c->main.stream));
     l->entries += frames; l->nnz_ub += nnz_bound;
     return SSM_OK;
 }
@@ -102,13 +102,13 @@ extern "C" int ssm_looper_create(ssm_ctx* c, const ssm_vocab* v, ssm_looper** ou
     { const char* e = getenv("SSM_BOW_VARIANT"); l->variant = (e && atoi(e) == 1) ? 1 : 0; }        // 1: one lane per descriptor (ablation runs); default: 16 lanes per descriptor
     const size_t nn = v->n_child.size(), nw = v->weight.size();
     DALLOC(c, l->d_first, nn); DALLOC(c, l->d_nchild, nn); DALLOC(c, l->d_word, nn); DALLOC(c, l->d_desc, nn * 8); DALLOC(c, l->d_weight, nw); DALLOC(c, l->d_hdr, 4);
-    HIPCHK(c, hipMemcpyAsync(l->d_first, v->first_child.data(), nn * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(l->d_nchild, v->n_child.data(), nn * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(l->d_word, v->word.data(), nn * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(l->d_desc, v->desc.data(), nn * 32, hipMemcpyHostToDevice, c->stream));
-    if (nw) HIPCHK(c, hipMemcpyAsync(l->d_weight, v->weight.data(), nw * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(l->d_hdr, 0, 16, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));             // v may be destroyed once this returns
+    HIPCHK(c, hipMemcpyAsync(l->d_first, v->first_child.data(), nn * 4, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(l->d_nchild, v->n_child.data(), nn * 4, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(l->d_word, v->word.data(), nn * 4, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(l->d_desc, v->desc.data(), nn * 32, hipMemcpyHostToDevice, c->main.stream));
+    if (nw) HIPCHK(c, hipMemcpyAsync(l->d_weight, v->weight.data(), nw * 8, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemsetAsync(l->d_hdr, 0, 16, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));             // v may be destroyed once this returns
     l->tree.first_child = l->d_first; l->tree.n_child = l->d_nchild; l->tree.desc = l->d_desc; l->tree.word = l->d_word; l->tree.weight = l->d_weight;
     l->tree.n_nodes = (int)nn; l->tree.n_words = (int)nw; l->tree.max_depth = v->max_depth;
     *out = l.release();
@@ -117,7 +117,7 @@ extern "C" int ssm_looper_create(ssm_ctx* c, const ssm_vocab* v, ssm_looper** ou
 extern "C" void ssm_looper_destroy(ssm_looper* l)
 {
     if (!l) return;
-    { std::lock_guard<std::mutex> lk(l->c->mu); hipSetDevice(l->c->device); (void)hipStreamSynchronize(l->c->stream); }
+    { std::lock_guard<std::mutex> lk(l->c->mu); hipSetDevice(l->c->device); (void)hipStreamSynchronize(l->c->main.stream); }
     delete l;
 }
 extern "C" int ssm_looper_clear(ssm_looper* l)
@@ -125,7 +125,7 @@ extern "C" int ssm_looper_clear(ssm_looper* l)
     if (!l) return SSM_E_INVAL;
     ssm_ctx* c = l->c; std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     l->entries = 0; l->nnz_ub = 0;
-    if (l->entry_cap) HIPCHK(c, hipMemsetAsync(l->d_offsets, 0, 4, c->stream));
+    if (l->entry_cap) HIPCHK(c, hipMemsetAsync(l->d_offsets, 0, 4, c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_looper_size(const ssm_looper* l) { return l ? l->entries : 0; }
@@ -139,12 +139,12 @@ extern "C" int ssm_looper_add(ssm_looper* l, const uint8_t* desc, int n, int fra
     if (n < 0 || (n > 0 && !desc)) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n > l->cap) FAIL(c, SSM_E_CAPACITY, "looper: more descriptors than ssm_orb_capacity");
     if (l->d_in.bytes() < (size_t)l->cap * 32) DALLOC(c, l->d_in, (size_t)l->cap * 32);
-    if (n) HIPCHK(c, hipMemcpyAsync(l->d_in, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+    if (n) HIPCHK(c, hipMemcpyAsync(l->d_in, desc, (size_t)n * 32, hipMemcpyHostToDevice, c->main.stream));
     const int32_t fid = frame_id;
     { const int r = looper_add_enqueue(l, l->d_in, nullptr, n, 1, &fid, n); if (r) return r; }
     int32_t hdr[4];
-    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return looper_check(l, hdr);
 }
 extern "C" int ssm_looper_add_dev(ssm_looper* l, const uint8_t* desc_dev, const int32_t* nkp_dev, int n_frames, int cap, const int32_t* frame_ids)
@@ -162,17 +162,17 @@ extern "C" int ssm_looper_bow(ssm_looper* l, int entry, int32_t* ids, double* va
     ssm_ctx* c = l->c; std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (entry < 0 || entry >= l->entries || !n_out || cap < 0 || (cap > 0 && (!ids || !vals))) FAIL(c, SSM_E_INVAL, "bad arguments");
     int32_t o[2], hdr[4];
-    HIPCHK(c, hipMemcpyAsync(o, l->d_offsets + entry, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(o, l->d_offsets + entry, 8, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     { const int r = looper_check(l, hdr); if (r) return r; }
     const int m = o[1] - o[0];
     *n_out = m;
     if (m > cap) FAIL(c, SSM_E_CAPACITY, "looper: the vector has more entries than the caller's buffers");
     if (m) {
-        HIPCHK(c, hipMemcpyAsync(ids, l->d_ids + o[0], (size_t)m * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(vals, l->d_vals + o[0], (size_t)m * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(ids, l->d_ids + o[0], (size_t)m * 4, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(vals, l->d_vals + o[0], (size_t)m * 8, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
     }
     return SSM_OK;
 }
@@ -183,11 +183,11 @@ static int looper_scores_enqueue(ssm_looper* l, int first, int n, int against, d
     const int row = against < 0 ? first + n : against;
     const size_t need = (size_t)n * (row ? row : 1);
     if (need > l->scores_n || n > l->counts_n) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         if (need > l->scores_n) { DALLOC(c, l->d_scores, need); l->scores_n = need; }
         if (n > l->counts_n) { DALLOC(c, l->d_counts, n); l->counts_n = n; }
     }
-    HIPCHK(c, k_bow_score(l->d_offsets, l->d_ids, l->d_vals, l->d_frame_ids, first, n, against, row, l->cap, min_score, min_interval, l->d_scores, l->d_counts, c->stream));
+    HIPCHK(c, k_bow_score(l->d_offsets, l->d_ids, l->d_vals, l->d_frame_ids, first, n, against, row, l->cap, min_score, min_interval, l->d_scores, l->d_counts, c->main.stream));
     *row_out = row;
     return SSM_OK;
 }
@@ -199,9 +199,9 @@ extern "C" int ssm_looper_scores(ssm_looper* l, int entry, int against, double* 
     int row = 0;
     { const int r = looper_scores_enqueue(l, entry, 1, against, 0.0, 0, &row); if (r) return r; }
     int32_t hdr[4];
-    if (row) HIPCHK(c, hipMemcpyAsync(scores, l->d_scores, (size_t)row * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (row) HIPCHK(c, hipMemcpyAsync(scores, l->d_scores, (size_t)row * 8, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return looper_check(l, hdr);
 }
 extern "C" int ssm_looper_query(ssm_looper* l, int first, int n, int against, double min_sim_score, int min_interval, int32_t* pairs, double* scores, int cap, int* n_out)
@@ -217,17 +217,17 @@ extern "C" int ssm_looper_query(ssm_looper* l, int first, int n, int against, do
     long long all = against < 0 ? (long long)n * first + (long long)n * (n + 1) / 2 : (long long)n * against;
     const int stage = (int)std::min<long long>(cap, all);
     if (stage > l->out_n) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         DALLOC(c, l->d_pairs, (size_t)stage * 2); DALLOC(c, l->d_out_scores, stage); l->out_n = stage;
     }
-    HIPCHK(c, k_bow_emit(l->d_frame_ids, l->d_scores, l->d_counts, first, n, against, row, min_sim_score, min_interval, l->d_pairs, l->d_out_scores, stage, l->d_hdr, c->stream));
+    HIPCHK(c, k_bow_emit(l->d_frame_ids, l->d_scores, l->d_counts, first, n, against, row, min_sim_score, min_interval, l->d_pairs, l->d_out_scores, stage, l->d_hdr, c->main.stream));
     int32_t hdr[4];
-    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hdr, l->d_hdr, 16, hipMemcpyDeviceToHost, c->main.stream));
     if (stage) {
-        HIPCHK(c, hipMemcpyAsync(pairs, l->d_pairs, (size_t)stage * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(scores, l->d_out_scores, (size_t)stage * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(pairs, l->d_pairs, (size_t)stage * 8, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(scores, l->d_out_scores, (size_t)stage * 8, hipMemcpyDeviceToHost, c->main.stream));
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     { const int r = looper_check(l, hdr); if (r) return r; }
     *n_out = hdr[1];
     if (hdr[1] > cap) FAIL(c, SSM_E_CAPACITY, "looper: more candidates than the caller's buffers hold");

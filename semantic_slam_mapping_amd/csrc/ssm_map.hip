@@ -67,7 +67,7 @@ int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L)
     c->map_ring[tag] = L; c->map_ring[tag].valid = true;
     c->map_unexamined = true;
     if (std::find(c->map_launch_streams.begin(), c->map_launch_streams.end(), s) == c->map_launch_streams.end()) c->map_launch_streams.push_back(s);
-    HIPCHK(c, k_map_fuse(L.depth, L.rgb, L.sem, L.pose, L.n, L.w, L.h, c->cfg.camera, c->cfg.mapper_max_distance, (float)c->cfg.mapper_resolution,
+    HIPCHK(c, k_map_fuse(L.depth, L.rgb, L.sem, L.pose, L.n, L.w, L.h, c->cfg.camera, c->map_div, c->map_div_exact, c->cfg.mapper_max_distance, (float)c->cfg.mapper_resolution,
                          t.tab, t.cap_log2, t.counters, L.npoints, s, t.skip, (int)hw, tag, nullptr, 0));
     return SSM_OK;
 }
@@ -122,7 +122,7 @@ int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out
                 std::vector<int32_t> batch;
                 for (size_t i = c->map_skipped.size(); i-- > 0 && batch.size() < room; ) if (((c->map_skipped[i] >> 24) & 7) == tag) { batch.push_back(c->map_skipped[i]); c->map_skipped.erase(c->map_skipped.begin() + (long)i); }
                 HIPCHK(c, hipMemcpyAsync(c->d_redo, batch.data(), batch.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s));
-                HIPCHK(c, k_map_fuse(L.depth, L.rgb, L.sem, L.pose, L.n, L.w, L.h, c->cfg.camera, c->cfg.mapper_max_distance, (float)c->cfg.mapper_resolution,
+                HIPCHK(c, k_map_fuse(L.depth, L.rgb, L.sem, L.pose, L.n, L.w, L.h, c->cfg.camera, c->map_div, c->map_div_exact, c->cfg.mapper_max_distance, (float)c->cfg.mapper_resolution,
                                      t.tab, t.cap_log2, t.counters, L.npoints, s, t.skip, 0, tag, c->d_redo, (int)batch.size()));
                 c->map_redone += (long)batch.size();
                 continue;
@@ -227,7 +227,7 @@ int map_after_launch(ssm_ctx* c, hipStream_t s, int frames, bool inputs_volatile
 
 // ---------------------------------------------------------------- voxel map
 // the stream the context map is read on (ssm_ctx::map_tail) -- the scratch table lives on the context stream
-static hipStream_t table_stream(ssm_ctx* c, VoxTable& t) { return (&t == &c->map && c->map_tail) ? c->map_tail : c->stream; }
+static hipStream_t table_stream(ssm_ctx* c, VoxTable& t) { return (&t == &c->map && c->map_tail) ? c->map_tail : c->main.stream; }
 static int table_count(ssm_ctx* c, VoxTable& t, int* n)
 {
     int32_t cnt[4];
@@ -267,9 +267,9 @@ static int table_export_points(ssm_ctx* c, VoxTable& t, ssm_point* out, int cap,
     if (n > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small (need " + std::to_string(n) + ")");
     if (n == 0) return SSM_OK;
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_point)); if (r) return r;
-    HIPCHK(c, k_voxel_gather_points(comp, order, n, c->d_scratch.as<ssm_point>(), c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, k_voxel_gather_points(comp, order, n, c->d_scratch.as<ssm_point>(), c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_map_clear(ssm_ctx* c)
@@ -277,7 +277,7 @@ extern "C" int ssm_map_clear(ssm_ctx* c)
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
-    HIPCHK(c, k_voxel_clear(c->map.tab, c->map.cap_log2, c->map.counters, c->stream));       // (the capacity it has grown to stays)
+    HIPCHK(c, k_voxel_clear(c->map.tab, c->map.cap_log2, c->map.counters, c->main.stream));       // (the capacity it has grown to stays)
     c->map_full_reported = false; c->map_launches = 0; c->map_frames = 0; c->map_known_total = 0; c->map_known_frames = 0;      // (the rate map_vpf is the stream's: kept)
     c->map_skipped.clear(); for (MapLaunch& L : c->map_ring) L.valid = false;            // (blocks that skipped themselves belong to the map that is cleared)
     return SSM_OK;
@@ -290,15 +290,15 @@ extern "C" int ssm_map_insert(ssm_ctx* c, const ssm_point* pts, int n)
     if (n < 0 || (n && !pts)) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n == 0) return SSM_OK;
     int r = ensure_scratch(c, (size_t)n * sizeof(ssm_point)); if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_scratch, pts, (size_t)n * sizeof(ssm_point), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_scratch, pts, (size_t)n * sizeof(ssm_point), hipMemcpyHostToDevice, c->main.stream));
     // in chunks the table is grown for beforehand (every point of a chunk may open a voxel): nothing can overflow
     for (int a = 0; a < n; ) {
         int64_t chunk = ((int64_t)1 << c->map.cap_log2) / 8; if (chunk < 4096) chunk = 4096; if (chunk > n - a) chunk = n - a;
-        r = map_settle(c, c->stream, chunk); if (r) return r;
-        HIPCHK(c, k_voxel_insert(c->d_scratch.as<ssm_point>() + a, nullptr, chunk, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
+        r = map_settle(c, c->main.stream, chunk); if (r) return r;
+        HIPCHK(c, k_voxel_insert(c->d_scratch.as<ssm_point>() + a, nullptr, chunk, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, c->main.stream));
         a += (int)chunk;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return check_device_flags(c, true);
 }
 extern "C" int ssm_map_size(ssm_ctx* c, int* n)
@@ -332,9 +332,9 @@ extern "C" int ssm_map_export_table(ssm_ctx* c, ssm_voxel* out, int cap, int* n_
     if (n > cap) FAIL(c, SSM_E_CAPACITY, "table buffer too small (need " + std::to_string(n) + ")");
     if (n == 0) return SSM_OK;
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_voxel)); if (r) return r;
-    HIPCHK(c, k_voxel_gather_table(comp, order, n, c->d_scratch.as<ssm_voxel>(), c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)n * sizeof(ssm_voxel), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, k_voxel_gather_table(comp, order, n, c->d_scratch.as<ssm_voxel>(), c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)n * sizeof(ssm_voxel), hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_map_merge_table(ssm_ctx* c, const ssm_voxel* tab, int n)
@@ -345,10 +345,10 @@ extern "C" int ssm_map_merge_table(ssm_ctx* c, const ssm_voxel* tab, int n)
     if (n < 0 || (n && !tab)) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n == 0) return SSM_OK;
     int r = ensure_scratch(c, (size_t)n * sizeof(ssm_voxel)); if (r) return r;
-    HIPCHK(c, hipMemcpyAsync(c->d_scratch, tab, (size_t)n * sizeof(ssm_voxel), hipMemcpyHostToDevice, c->stream));
-    r = map_settle(c, c->stream, n); if (r) return r;               // room for n new voxels first
-    HIPCHK(c, k_voxel_merge(c->d_scratch.as<ssm_voxel>(), n, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_scratch, tab, (size_t)n * sizeof(ssm_voxel), hipMemcpyHostToDevice, c->main.stream));
+    r = map_settle(c, c->main.stream, n); if (r) return r;               // room for n new voxels first
+    HIPCHK(c, k_voxel_merge(c->d_scratch.as<ssm_voxel>(), n, c->map.tab, c->map.cap_log2, c->map.counters, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_map_export_table_dev(ssm_ctx* c, ssm_voxel* out, int cap, int* n_out)
@@ -372,8 +372,8 @@ extern "C" int ssm_map_merge_table_dev(ssm_ctx* c, const ssm_voxel* tab, int n)
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
     if (n < 0 || (n && !tab)) FAIL(c, SSM_E_INVAL, "bad arguments");
-    { const int r = map_settle(c, c->stream, n); if (r) return r; }
-    HIPCHK(c, k_voxel_merge(tab, n, c->map.tab, c->map.cap_log2, c->map.counters, c->stream));
+    { const int r = map_settle(c, c->main.stream, n); if (r) return r; }
+    HIPCHK(c, k_voxel_merge(tab, n, c->map.tab, c->map.cap_log2, c->map.counters, c->main.stream));
     return SSM_OK;
 }
 // ---------------------------------------------------------------- multi-GPU: one process per GPU, the voxel-map merge is the only collective
@@ -402,7 +402,7 @@ extern "C" int ssm_comm_finalize(ssm_ctx* c)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    if (c->comm) { HIPCHK(c, hipStreamSynchronize(c->stream)); NCCLCHK(c, ncclCommDestroy(c->comm)); c->comm = nullptr; }
+    if (c->comm) { HIPCHK(c, hipStreamSynchronize(c->main.stream)); NCCLCHK(c, ncclCommDestroy(c->comm)); c->comm = nullptr; }
     c->comm_rank = 0; c->comm_size = 1;
     return SSM_OK;
 }
@@ -422,10 +422,10 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
     int world = 0, rank = 0;
     NCCLCHK(c, ncclCommCount(comm, &world)); NCCLCHK(c, ncclCommUserRank(comm, &rank));
     if (world > c->comm_counts_cap) {     // 2 ints per rank + one word of this rank's own flag
-        if (c->d_comm_counts) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->comm_counts_cap = 0; }
+        if (c->d_comm_counts) { HIPCHK(c, hipStreamSynchronize(c->main.stream)); c->comm_counts_cap = 0; }
         DALLOC(c, c->d_comm_counts, (size_t)2 * world + 4); c->comm_counts_cap = world;
     }
-    hipStream_t s = c->stream;
+    hipStream_t s = c->main.stream;
     // the local map at rest first (overflow list merged).  A rank that cannot settle must not leave before the collectives: it raises its map's LOST flag, which the
     // count all-gather below carries to every rank
     const int r_settle = map_settle(c, s, 0);
@@ -479,16 +479,16 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
     *n_out = 0;
     if (n == 0) return SSM_OK;
     int r;
-    if (!c->tmp.tab) { r = table_alloc(c, c->stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
-    else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
+    if (!c->tmp.tab) { r = table_alloc(c, c->main.stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
+    else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->main.stream));
     r = ensure_scratch(c, (size_t)n * sizeof(ssm_point) + 64); if (r) return r;
     ssm_point* dp = c->d_scratch.as<ssm_point>();
     float* mm = reinterpret_cast<float*>(dp + n);
-    HIPCHK(c, hipMemcpyAsync(dp, pts, (size_t)n * sizeof(ssm_point), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_voxel_bounds(dp, n, mm, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dp, pts, (size_t)n * sizeof(ssm_point), hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_voxel_bounds(dp, n, mm, c->main.stream));
     int ord[6];
-    HIPCHK(c, hipMemcpyAsync(ord, mm, 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(ord, mm, 24, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     {   // pcl::VoxelGrid::applyFilter overflow guard: (dx*dy*dz) > INT_MAX -> warning, output = input
         const float inv = 1.0f / leaf;
         const int64_t dx = (int64_t)((ord2f(ord[3]) - ord2f(ord[0])) * inv) + 1, dy = (int64_t)((ord2f(ord[4]) - ord2f(ord[1])) * inv) + 1,
@@ -497,14 +497,14 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
     }
     // pcl::VoxelGrid has no table to overflow: when the temporary table fills up, re-allocate it four times as large and insert again
     for (;;) {
-        HIPCHK(c, k_voxel_insert(dp, nullptr, n, leaf, c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
+        HIPCHK(c, k_voxel_insert(dp, nullptr, n, leaf, c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->main.stream));
         int32_t cnt[2];
-        HIPCHK(c, hipMemcpyAsync(cnt, c->tmp.counters, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(cnt, c->tmp.counters, 8, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         if (!(cnt[1] & 1)) break;
         const int bigger = c->tmp.cap_log2 + 2;
         if (bigger > 28) FAIL(c, SSM_E_CAPACITY, "voxel_filter: more than 2^28 voxels");
-        r = table_alloc(c, c->stream, c->tmp, bigger); if (r) return r;
+        r = table_alloc(c, c->main.stream, c->tmp, bigger); if (r) return r;
     }
     return table_export_points(c, c->tmp, out, cap, n_out);
 }
@@ -525,7 +525,7 @@ extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint
     memcpy(c->h_pinned, depth, np * 2); memcpy(c->h_pinned + np * 2, rgb, np * 3); memcpy(c->h_pinned + np * 5, sem, np * 3);
     r = ensure_scratch(c, np * 8); if (r) return r;
     uint8_t* din = c->d_scratch;
-    HIPCHK(c, hipMemcpyAsync(din, c->h_pinned, np * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(din, c->h_pinned, np * 8, hipMemcpyHostToDevice, c->main.stream));
     const uint16_t* dd = reinterpret_cast<const uint16_t*>(din); const uint8_t* drgb = din + np * 2; const uint8_t* dsem = din + np * 5;
     // the cloud is written straight into a slab of device memory (room for the worst case, w h points; only the n points made are kept): no allocation, no
     // device-to-device copy and ONE wait per key-frame
@@ -538,12 +538,12 @@ extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint
     }
     ssm_ctx::CloudSlab& sl = c->cloud_slabs[si];
     ssm_point* dst = sl.d + sl.used;
-    HIPCHK(c, k_moving_mask(dsem, 1, w, h, c->d_mask, c->stream));
+    HIPCHK(c, k_moving_mask(dsem, 1, w, h, c->d_mask, c->main.stream));
     HIPCHK(c, k_backproject(dd, drgb, dsem, c->d_mask, nullptr, 1, w, h, *cam, max_distance,
-                            c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, dst, c->stream));
+                            c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, dst, c->main.stream));
     int64_t* h_total = c->h_pinned.as<int64_t>();                  // (the staged images at the front of the pinned area are consumed by then: stream order)
-    HIPCHK(c, hipMemcpyAsync(h_total, c->d_total, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(h_total, c->d_total, 8, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     const int64_t total = *h_total;
     ssm_cloud* cl = new ssm_cloud(); cl->n = (int)total; cl->device = c->device; cl->slab = si; cl->d = dst;
     sl.used += ((size_t)total + 7) & ~(size_t)7; sl.live++;
@@ -556,7 +556,7 @@ extern "C" void ssm_cloud_free(ssm_ctx* c, ssm_cloud* cl)
     if (!cl) return;
     if (c) {                                                                   // a slab whose clouds are all freed is reused from its start
         std::lock_guard<std::mutex> lk(c->mu);
-        if (cl->slab >= 0 && cl->slab < (int)c->cloud_slabs.size()) { ssm_ctx::CloudSlab& sl = c->cloud_slabs[cl->slab]; if (--sl.live == 0) { hipSetDevice(c->device); hipStreamSynchronize(c->stream); sl.used = 0; } }
+        if (cl->slab >= 0 && cl->slab < (int)c->cloud_slabs.size()) { ssm_ctx::CloudSlab& sl = c->cloud_slabs[cl->slab]; if (--sl.live == 0) { hipSetDevice(c->device); hipStreamSynchronize(c->main.stream); sl.used = 0; } }
     }
     delete cl;                                                                  // (without a context the slab goes with ssm_destroy)
 }
@@ -569,15 +569,15 @@ extern "C" int ssm_cloud_fetch(ssm_ctx* c, const ssm_cloud* cl, const double* T,
     if (cl->n == 0) return SSM_OK;
     if (!out) FAIL(c, SSM_E_INVAL, "null argument");
     int r = ensure_scratch(c, (size_t)cl->n * sizeof(ssm_point)); if (r) return r;
-    HIPCHK(c, k_cloud_transform(cl->d, cl->n, T, c->d_scratch.as<ssm_point>(), c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)cl->n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, k_cloud_transform(cl->d, cl->n, T, c->d_scratch.as<ssm_point>(), c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_scratch, (size_t)cl->n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 static int grow_points(ssm_ctx* c, DevBuf<ssm_point>& p, size_t need)          // room for `need` points; what p held is not kept
 {
     if (need * sizeof(ssm_point) <= p.bytes()) return SSM_OK;
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     DevBuf<ssm_point> q;                                        // (a failure leaves p as it is: the published map stays fetchable)
     if (q.alloc(c, need + need / 2 + 1024)) FAIL(c, SSM_E_HIP, "hipMalloc of the viewer map failed");
     p = std::move(q);
@@ -588,7 +588,7 @@ extern "C" int ssm_viewer_map_release(ssm_ctx* c, int test_fail_next)
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (test_fail_next) { c->viewer_fail_next = true; return SSM_OK; }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     for (ssm_ctx::CloudSlab& sl : c->cloud_slabs) if (sl.live == 0 && sl.d) { sl.d.reset(); sl.cap = 0; sl.used = 0; }      // (an emptied slab is skipped by the allocator: cap 0)
     c->d_vcat.reset();
     c->d_vmap.reset(); c->vmap_n = 0;
@@ -607,42 +607,42 @@ extern "C" int ssm_viewer_map_update(ssm_ctx* c, int rebuild, ssm_cloud* const* 
     int r = grow_points(c, c->d_vcat, total + 8); if (r) return r;       // (+ 8 points: the bounds words behind the data)
     // previous centroids, then every cloud transformed by its pose: the viewer's `*map += *generatePointCloud(kf)`
     size_t off = 0;
-    if (!rebuild && c->vmap_n) { HIPCHK(c, hipMemcpyAsync(c->d_vcat, c->d_vmap, (size_t)c->vmap_n * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->stream)); off = (size_t)c->vmap_n; }
-    for (int i = 0; i < n; i++) { HIPCHK(c, k_cloud_transform(clouds[i]->d, clouds[i]->n, poses + (size_t)16 * i, c->d_vcat + off, c->stream)); off += (size_t)clouds[i]->n; }
+    if (!rebuild && c->vmap_n) { HIPCHK(c, hipMemcpyAsync(c->d_vcat, c->d_vmap, (size_t)c->vmap_n * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->main.stream)); off = (size_t)c->vmap_n; }
+    for (int i = 0; i < n; i++) { HIPCHK(c, k_cloud_transform(clouds[i]->d, clouds[i]->n, poses + (size_t)16 * i, c->d_vcat + off, c->main.stream)); off += (size_t)clouds[i]->n; }
     const int N = (int)total;
-    if (!c->tmp.tab) { r = table_alloc(c, c->stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
-    else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
+    if (!c->tmp.tab) { r = table_alloc(c, c->main.stream, c->tmp, c->cfg.voxel_capacity_log2); if (r) return r; }
+    else HIPCHK(c, k_voxel_clear(c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->main.stream));
     float* mm = reinterpret_cast<float*>(c->d_vcat + total);
-    HIPCHK(c, k_voxel_bounds(c->d_vcat, N, mm, c->stream));
+    HIPCHK(c, k_voxel_bounds(c->d_vcat, N, mm, c->main.stream));
     int ord[6];
-    HIPCHK(c, hipMemcpyAsync(ord, mm, 24, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(ord, mm, 24, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     {   // pcl::VoxelGrid::applyFilter overflow guard (as in ssm_voxel_filter): the map is then the unfiltered concatenation
         const float inv = 1.0f / leaf;
         const int64_t dx = (int64_t)((ord2f(ord[3]) - ord2f(ord[0])) * inv) + 1, dy = (int64_t)((ord2f(ord[4]) - ord2f(ord[1])) * inv) + 1,
                       dz = (int64_t)((ord2f(ord[5]) - ord2f(ord[2])) * inv) + 1;
         if (dx * dy * dz > (int64_t)2147483647) {
             r = grow_points(c, c->d_vmap, total); if (r) return r;
-            HIPCHK(c, hipMemcpyAsync(c->d_vmap, c->d_vcat, total * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+            HIPCHK(c, hipMemcpyAsync(c->d_vmap, c->d_vcat, total * sizeof(ssm_point), hipMemcpyDeviceToDevice, c->main.stream));
+            HIPCHK(c, hipStreamSynchronize(c->main.stream));
             c->vmap_n = N; if (n_map_out) *n_map_out = N;
             return SSM_OK;
         }
     }
     for (;;) {
-        HIPCHK(c, k_voxel_insert(c->d_vcat, nullptr, N, leaf, c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->stream));
+        HIPCHK(c, k_voxel_insert(c->d_vcat, nullptr, N, leaf, c->tmp.tab, c->tmp.cap_log2, c->tmp.counters, c->main.stream));
         int32_t cnt[2];
-        HIPCHK(c, hipMemcpyAsync(cnt, c->tmp.counters, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(cnt, c->tmp.counters, 8, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         if (!(cnt[1] & 1)) break;
         const int bigger = c->tmp.cap_log2 + 2;
         if (bigger > 28) FAIL(c, SSM_E_CAPACITY, "viewer map: more than 2^28 voxels");
-        r = table_alloc(c, c->stream, c->tmp, bigger); if (r) return r;
+        r = table_alloc(c, c->main.stream, c->tmp, bigger); if (r) return r;
     }
     int nv; ssm_voxel* comp; uint32_t* order;
     r = table_sorted(c, c->tmp, &nv, &comp, &order); if (r) return r;
     r = grow_points(c, c->d_vmap, (size_t)nv); if (r) return r;
-    if (nv) HIPCHK(c, k_voxel_gather_points(comp, order, nv, c->d_vmap, c->stream));
+    if (nv) HIPCHK(c, k_voxel_gather_points(comp, order, nv, c->d_vmap, c->main.stream));
     c->vmap_n = nv;
     if (n_map_out) *n_map_out = nv;
     return SSM_OK;
@@ -655,8 +655,8 @@ extern "C" int ssm_viewer_map_fetch(ssm_ctx* c, ssm_point* out, int cap, int* n_
     if (c->vmap_n > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small (need " + std::to_string(c->vmap_n) + ")");
     if (c->vmap_n == 0) return SSM_OK;
     if (!out) FAIL(c, SSM_E_INVAL, "null argument");
-    HIPCHK(c, hipMemcpyAsync(out, c->d_vmap, (size_t)c->vmap_n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_vmap, (size_t)c->vmap_n * sizeof(ssm_point), hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 

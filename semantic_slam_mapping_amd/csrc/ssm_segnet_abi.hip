@@ -109,14 +109,14 @@ extern "C" int ssm_segnet_set_layer(ssm_ctx* c, int l, const float* weight, cons
 // forward for nb <= seg->batch device frames already pre-processed into actA; leaves logits in the returned buffer
 // logits_out != nullptr: the class logits are materialised (returned buffer) and the caller runs the ArgMax kernel;
 // logits_out == nullptr: the last layer writes the labels (g->labels) straight from its epilogue.
-static int seg_forward_core(ssm_ctx* c, hipStream_t s, int nb, void** logits_out)
+static int seg_forward_core(ssm_ctx* c, Lane& lane, int nb, void** logits_out)
 {
-    SegNetState* g = c->seg.get();
+    SegNetState* g = c->seg.get(); const hipStream_t s = lane.stream; const DeviceInfo& dev = c->dev; int* const tiles = lane.conv_tiles;
     void* cur = g->actA; void* nxt = g->actB;
-    HIPCHK(c, k_segnet_begin(s));
+    HIPCHK(c, k_segnet_begin(tiles, s));
     auto conv = [&](int l) -> int {
         const SegLayerDef& d = k_seg_layers[l];
-        HIPCHK(c, k_segnet_conv(cur, g->w[l], g->scale[l], g->shift[l], nxt, nb, d.h, d.w, g->cinp[l], d.cout, l != SEG_LAYERS - 1, s, seg_wino(g, l)));
+        HIPCHK(c, k_segnet_conv(cur, g->w[l], g->scale[l], g->shift[l], nxt, nb, d.h, d.w, g->cinp[l], d.cout, l != SEG_LAYERS - 1, dev, tiles, s, seg_wino(g, l)));
         std::swap(cur, nxt); return SSM_OK;
     };
     auto unpool = [&](int i, int PH, int PW, int C, int H, int W) -> int { HIPCHK(c, k_segnet_unpool(cur, g->code[i], nb, PH, PW, C, nxt, H, W, s)); std::swap(cur, nxt); return SSM_OK; };
@@ -129,13 +129,13 @@ static int seg_forward_core(ssm_ctx* c, hipStream_t s, int nb, void** logits_out
         // pass on the stage's critical path costs more than the separate un-pool (362 vs 327, 121 vs 103 us)
         if (!fused_up || C > 256) { int r_ = unpool(i, PH, PW, C, H, W); return r_ ? r_ : conv(l); }
         const SegLayerDef& d = k_seg_layers[l];
-        HIPCHK(c, k_segnet_conv_unpool(cur, g->code[i], g->w[l], g->scale[l], g->shift[l], nxt, nb, d.h, d.w, g->cinp[l], d.cout, s));
+        HIPCHK(c, k_segnet_conv_unpool(cur, g->code[i], g->w[l], g->scale[l], g->shift[l], nxt, nb, d.h, d.w, g->cinp[l], d.cout, dev, tiles, s));
         std::swap(cur, nxt); return SSM_OK;
     };
     // conv + pool pairs run as one kernel (the full-resolution activation of the pooled layer is never written)
     auto conv_pool = [&](int l, int i) -> int {
         const SegLayerDef& d = k_seg_layers[l];
-        HIPCHK(c, k_segnet_conv_pool(cur, g->w[l], g->scale[l], g->shift[l], nxt, g->code[i], nb, d.h, d.w, g->cinp[l], d.cout, s));
+        HIPCHK(c, k_segnet_conv_pool(cur, g->w[l], g->scale[l], g->shift[l], nxt, g->code[i], nb, d.h, d.w, g->cinp[l], d.cout, dev, tiles, s));
         std::swap(cur, nxt); return SSM_OK;
     };
     int r;
@@ -152,13 +152,24 @@ static int seg_forward_core(ssm_ctx* c, hipStream_t s, int nb, void** logits_out
     if (logits_out) { if ((r = conv(25))) return r; *logits_out = cur; }
     else {
         const SegLayerDef& d = k_seg_layers[25];
-        HIPCHK(c, k_segnet_conv_argmax(cur, g->w[25], g->scale[25], g->shift[25], g->labels, nb, d.h, d.w, g->cinp[25], d.cout, s));
+        HIPCHK(c, k_segnet_conv_argmax(cur, g->w[25], g->scale[25], g->shift[25], g->labels, nb, d.h, d.w, g->cinp[25], d.cout, dev, tiles, s));
     }
     return SSM_OK;
 }
-int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags)
+// the lane's tile counters: allocated and zeroed where the lane first runs SegNet (the conv kernels leave them zeroed)
+static int seg_lane_tiles(ssm_ctx* c, Lane& lane)
+{
+    if (lane.conv_tiles) return SSM_OK;
+    DevBuf<int> q; DALLOC(c, q, CONV_QUEUE_INTS);
+    HIPCHK(c, hipMemset(q, 0, CONV_QUEUE_INTS * sizeof(int)));
+    lane.conv_tiles = std::move(q);
+    return SSM_OK;
+}
+int seg_forward_dev(ssm_ctx* c, Lane& lane, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags)
 {
     int r = seg_init(c); if (r) return r;
+    r = seg_lane_tiles(c, lane); if (r) return r;
+    const hipStream_t s = lane.stream;
     SegNetState* g = c->seg.get();
     for (int l = 0; l < SEG_LAYERS; l++) if (!g->set[l]) FAIL(c, SSM_E_INVAL, "SegNet layer " + std::to_string(l) + " has no weights (ssm_segnet_set_layer)");
     const int W = c->g.W, H = c->g.H;
@@ -167,11 +178,11 @@ int seg_forward_dev(ssm_ctx* c, hipStream_t s, const uint8_t* bgr, int n, uint8_
         HIPCHK(c, k_segnet_prep(bgr + (size_t)f0 * W * H * 3, nb, W, H, SEG_NW, SEG_NH, g->pre_xofs, g->pre_xa, g->pre_yofs, g->pre_ya, g->actA, s));
         if (flags & 4) {                           // keep the class logits (ssm_segnet_forward / ssm_segnet_logits): separate ArgMax kernel
             void* logits = nullptr;
-            r = seg_forward_core(c, s, nb, &logits); if (r) return r;
+            r = seg_forward_core(c, lane, nb, &logits); if (r) return r;
             g->last_logits = logits;               // frame f0 of the last sub-batch starts the buffer
             HIPCHK(c, k_segnet_argmax(logits, nb, SEG_NW * SEG_NH, g->coutstore[SEG_LAYERS - 1], SEG_NCLS, g->labels, s));
         } else {
-            r = seg_forward_core(c, s, nb, nullptr); if (r) return r;
+            r = seg_forward_core(c, lane, nb, nullptr); if (r) return r;
             g->last_logits = nullptr;
         }
         if (labels_net) HIPCHK(c, hipMemcpyAsync(labels_net + (size_t)f0 * SEG_NW * SEG_NH, g->labels, (size_t)nb * SEG_NW * SEG_NH, hipMemcpyDeviceToDevice, s));
@@ -185,7 +196,7 @@ extern "C" int ssm_segnet_forward_dev(ssm_ctx* c, const uint8_t* bgr, int n, uin
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!bgr || n < 0) FAIL(c, SSM_E_INVAL, "bad arguments");
-    return seg_forward_dev(c, c->stream, bgr, n, labels_net, sem_bgr, flags);
+    return seg_forward_dev(c, c->main, bgr, n, labels_net, sem_bgr, flags);
 }
 extern "C" int ssm_segnet_forward(ssm_ctx* c, const uint8_t* bgr, int w, int h, int stride, uint8_t* labels_net, uint8_t* sem_bgr)
 {
@@ -194,12 +205,12 @@ extern "C" int ssm_segnet_forward(ssm_ctx* c, const uint8_t* bgr, int w, int h, 
     if (!bgr) FAIL(c, SSM_E_INVAL, "null argument");
     if (w != c->g.W || h != c->g.H) FAIL(c, SSM_E_INVAL, "frame size differs from the context configuration");
     if (stride < w * 3) FAIL(c, SSM_E_INVAL, "stride smaller than a row");
-    HIPCHK(c, hipMemcpy2DAsync(c->d_in_img, (size_t)w * 3, bgr, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(c->d_in_img, (size_t)w * 3, bgr, stride, (size_t)w * 3, h, hipMemcpyHostToDevice, c->main.stream));
     int r = ensure_scratch(c, (size_t)SEG_NW * SEG_NH); if (r) return r;
-    r = seg_forward_dev(c, c->stream, c->d_in_img, 1, labels_net ? (uint8_t*)c->d_scratch : nullptr, sem_bgr ? c->d_in_sem : nullptr, 4); if (r) return r;
-    if (labels_net) HIPCHK(c, hipMemcpyAsync(labels_net, c->d_scratch, (size_t)SEG_NW * SEG_NH, hipMemcpyDeviceToHost, c->stream));
-    if (sem_bgr) HIPCHK(c, hipMemcpyAsync(sem_bgr, c->d_in_sem, (size_t)w * h * 3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    r = seg_forward_dev(c, c->main, c->d_in_img, 1, labels_net ? (uint8_t*)c->d_scratch : nullptr, sem_bgr ? c->d_in_sem : nullptr, 4); if (r) return r;
+    if (labels_net) HIPCHK(c, hipMemcpyAsync(labels_net, c->d_scratch, (size_t)SEG_NW * SEG_NH, hipMemcpyDeviceToHost, c->main.stream));
+    if (sem_bgr) HIPCHK(c, hipMemcpyAsync(sem_bgr, c->d_in_sem, (size_t)w * h * 3, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* in, int H, int W, uint16_t* out, uint8_t* code)
@@ -208,7 +219,8 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!in || !out || H < 1 || W < 1 || (size_t)H * W > (size_t)SEG_NW * SEG_NH) FAIL(c, SSM_E_INVAL, "bad arguments");
     int r = seg_init(c); if (r) return r;
-    SegNetState* g = c->seg.get(); hipStream_t s = c->stream;
+    r = seg_lane_tiles(c, c->main); if (r) return r;
+    SegNetState* g = c->seg.get(); hipStream_t s = c->main.stream; const DeviceInfo& dev = c->dev; int* const tiles = c->main.conv_tiles;
     const int PH = (H + 1) / 2, PW = (W + 1) / 2;
     if (op == 0) {
         if (arg < 0 || arg >= SEG_LAYERS || !g->set[arg]) FAIL(c, SSM_E_INVAL, "layer not set");
@@ -218,7 +230,7 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
         if (g->cinp[arg] == 8) { for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < k_seg_layers[arg].cin; ch++) hin[p * 8 + ch] = in[p * ci16 + ch]; }
         else for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < ci16; ch++) hin[((size_t)(ch / 32) * H * W + p) * 32 + ch % 32] = in[p * ci16 + ch];
         HIPCHK(c, hipMemcpyAsync(g->actA, hin.data(), hin.size() * 2, hipMemcpyHostToDevice, s));
-        HIPCHK(c, k_segnet_conv(g->actA, g->w[arg], g->scale[arg], g->shift[arg], g->actB, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, arg != SEG_LAYERS - 1, s, seg_wino(g, arg)));
+        HIPCHK(c, k_segnet_conv(g->actA, g->w[arg], g->scale[arg], g->shift[arg], g->actB, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, arg != SEG_LAYERS - 1, dev, tiles, s, seg_wino(g, arg)));
         HIPCHK(c, hipMemcpyAsync(hout.data(), g->actB, hout.size() * 2, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < co16; ch++) out[p * co16 + ch] = hout[((size_t)(ch / 32) * H * W + p) * 32 + ch % 32];
@@ -259,7 +271,7 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
         r = ensure_scratch(c, hcode.size()); if (r) return r;
         uint8_t* dcode = (uint8_t*)c->d_scratch;
         HIPCHK(c, hipMemcpyAsync(g->actA, hin.data(), hin.size() * 2, hipMemcpyHostToDevice, s));
-        HIPCHK(c, k_segnet_conv_pool(g->actA, g->w[arg], g->scale[arg], g->shift[arg], g->actB, dcode, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, s));
+        HIPCHK(c, k_segnet_conv_pool(g->actA, g->w[arg], g->scale[arg], g->shift[arg], g->actB, dcode, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, dev, tiles, s));
         HIPCHK(c, hipMemcpyAsync(hout.data(), g->actB, hout.size() * 2, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipMemcpyAsync(hcode.data(), dcode, hcode.size(), hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
@@ -279,10 +291,10 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
         }
         r = ensure_scratch(c, hcode.size()); if (r) return r;
         uint8_t* dcode = (uint8_t*)c->d_scratch;
-        HIPCHK(c, k_segnet_begin(s));
+        HIPCHK(c, k_segnet_begin(tiles, s));
         HIPCHK(c, hipMemcpyAsync(g->actA, hin.data(), hin.size() * 2, hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(dcode, hcode.data(), hcode.size(), hipMemcpyHostToDevice, s));
-        HIPCHK(c, k_segnet_conv_unpool(g->actA, dcode, g->w[arg], g->scale[arg], g->shift[arg], g->actB, 1, H, W, cip, k_seg_layers[arg].cout, s));
+        HIPCHK(c, k_segnet_conv_unpool(g->actA, dcode, g->w[arg], g->scale[arg], g->shift[arg], g->actB, 1, H, W, cip, k_seg_layers[arg].cout, dev, tiles, s));
         HIPCHK(c, hipMemcpyAsync(hout.data(), g->actB, hout.size() * 2, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < co16; ch++) out[p * co16 + ch] = hout[((size_t)(ch / 32) * H * W + p) * 32 + ch % 32];
@@ -294,9 +306,9 @@ extern "C" int ssm_segnet_debug_op(ssm_ctx* c, int op, int arg, const uint16_t* 
         for (size_t p = 0; p < (size_t)H * W; p++) for (int ch = 0; ch < ci16; ch++) hin[((size_t)(ch / 32) * H * W + p) * 32 + ch % 32] = in[p * ci16 + ch];
         r = ensure_scratch(c, (size_t)H * W); if (r) return r;
         uint8_t* dlab = (uint8_t*)c->d_scratch;
-        HIPCHK(c, k_segnet_begin(s));
+        HIPCHK(c, k_segnet_begin(tiles, s));
         HIPCHK(c, hipMemcpyAsync(g->actA, hin.data(), hin.size() * 2, hipMemcpyHostToDevice, s));
-        HIPCHK(c, k_segnet_conv_argmax(g->actA, g->w[arg], g->scale[arg], g->shift[arg], dlab, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, s));
+        HIPCHK(c, k_segnet_conv_argmax(g->actA, g->w[arg], g->scale[arg], g->shift[arg], dlab, 1, H, W, g->cinp[arg], k_seg_layers[arg].cout, dev, tiles, s));
         HIPCHK(c, hipMemcpyAsync(code, dlab, (size_t)H * W, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
     } else FAIL(c, SSM_E_INVAL, "unknown op");
@@ -311,7 +323,7 @@ extern "C" int ssm_segnet_logits(ssm_ctx* c, float* out)
     if (!c->seg->last_logits) FAIL(c, SSM_E_INVAL, "no forward has run");
     const int cs = c->seg->coutstore[SEG_LAYERS - 1];
     std::vector<uint16_t> h((size_t)SEG_NW * SEG_NH * cs);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     HIPCHK(c, hipMemcpy(h.data(), c->seg->last_logits, h.size() * 2, hipMemcpyDeviceToHost));
     for (size_t p = 0; p < (size_t)SEG_NW * SEG_NH; p++)
         for (int k = 0; k < SEG_NCLS; k++) { _Float16 v; memcpy(&v, &h[p * cs + k], 2); out[p * SEG_NCLS + k] = (float)v; }

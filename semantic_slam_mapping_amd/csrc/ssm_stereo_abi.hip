@@ -101,17 +101,18 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     if (stages & SSM_STEREO_DEPTH) { r = stereo_ensure_sgbm(c, in->sgbm, n < B ? (n > 0 ? n : 1) : B); if (r) return r; }
     const size_t np = (size_t)w * h;
     const QuadBatch& qb = q->qb;
-    hipStream_t sq = c->stream, sd = c->stream;
+    const hipStream_t sq = c->main.stream;
     // the quad matcher + VO chain (many small latency-bound kernels) and SGBM (volume kernels) of a sub-batch share nothing but the input images:
-    // SGBM runs on the second context stream beside the chain; sub-batches follow each other on both streams without a join in between
+    // SGBM runs on the first side lane beside the chain; sub-batches follow each other on both streams without a join in between
     const bool two = (stages & SSM_STEREO_DEPTH) && (stages & SSM_STEREO_QUAD) && !c->serialize;
-    if (two) { r = ensure_side_streams(c); if (r) return r; sd = c->stream2; HIPCHK(c, hipEventRecord(c->ev_fork, c->stream)); HIPCHK(c, hipStreamWaitEvent(sd, c->ev_fork, 0)); }
-    // ... and with more than one sub-batch SGBM alternates between TWO streams with a workspace each: the cost kernel and the small kernels of one
-    // sub-batch (LDS / latency-bound) run beside the scan-direction and winner-takes-all kernels of the other (HBM-bound)
+    if (two) { r = ensure_side_streams(c); if (r) return r; }
+    // ... and with more than one sub-batch SGBM alternates between TWO (sgbm_streams: up to three) lanes with a workspace each: the cost kernel and the small
+    // kernels of one sub-batch (LDS / latency-bound) run beside the scan-direction and winner-takes-all kernels of the other (HBM-bound)
     const int nsub = (n + B - 1) / B;
     const int nsg = two ? (c->stereo_sgbm_streams < nsub ? c->stereo_sgbm_streams : nsub) : 1;
-    hipStream_t sgs[3] = {sd, two ? c->stream3 : sd, two ? c->stream4 : sd};
-    for (int k = 1; k < nsg; k++) { r = stereo_ensure_sgbm(c, in->sgbm, B, k); if (r) return r; HIPCHK(c, hipStreamWaitEvent(sgs[k], c->ev_fork, 0)); }
+    Lane* const sgl[3] = {two ? &c->side[0] : &c->main, nsg > 1 ? &c->side[1] : nullptr, nsg > 2 ? &c->side[2] : nullptr};      // SGBM's lanes
+    for (int k = 1; k < nsg; k++) { r = stereo_ensure_sgbm(c, in->sgbm, B, k); if (r) return r; }
+    if (two) { r = lanes_fork(c, {sgl[0], sgl[1], sgl[2]}); if (r) return r; }
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
     const bool prev0 = in->continue_sequence && q->have_prev;
     if (stages & SSM_STEREO_VO) HIPCHK(c, hipMemsetAsync(q->consumed, 0, 4, sq));
@@ -146,17 +147,15 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
         }
         if (stages & SSM_STEREO_DEPTH) {
             const int alt = (f0 / B) % nsg;
-            hipStream_t sg = sgs[alt];
+            Lane& sl = *sgl[alt]; const hipStream_t sg = sl.stream;
             prof_begin(c, sg, "sgbm");                                  // (the stage events on SGBM's stream)
-            HIPCHK(c, k_sgbm(in->left + (size_t)f0 * np, in->right + (size_t)f0 * np, w, h, nb, in->sgbm, q->sg_wsN[alt], q->sg_wsN[alt].bytes(), q->disp + (size_t)f0 * np, 0, sg, q->sg_fail + (f0 / B) % SG_FAIL_WORDS,
-                             c->sgbm_form_cfg, nsg));
+            HIPCHK(c, k_sgbm(in->left + (size_t)f0 * np, in->right + (size_t)f0 * np, w, h, nb, in->sgbm, q->sg_wsN[alt], q->sg_wsN[alt].bytes(), q->disp + (size_t)f0 * np, 0, c->dev, sl.sg, sg,
+                             q->sg_fail + (f0 / B) % SG_FAIL_WORDS, c->sgbm_form_cfg, nsg));
             HIPCHK(c, k_sgbm_depth(q->disp + (size_t)f0 * np, w, h, nb, in->baseline, in->cu, in->cv, in->f, in->roix, in->roiy, in->roiz, in->scale, q->dminN[alt], q->depth + (size_t)f0 * np, sg));
             prof_end(c, sg);
         }
     }
-    if (two) { HIPCHK(c, hipEventRecord(c->ev_join, sd)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0)); }
-    if (nsg > 1) { HIPCHK(c, hipEventRecord(c->ev_join3, c->stream3)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join3, 0)); }
-    if (nsg > 2) { HIPCHK(c, hipEventRecord(c->ev_join4, c->stream4)); HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join4, 0)); }
+    if (two) { r = lanes_join(c, {sgl[0], sgl[1], sgl[2]}); if (r) return r; }
     if (n > 0) q->have_prev = (stages & SSM_STEREO_QUAD) != 0;
     q->sg_pending.valid = (stages & SSM_STEREO_DEPTH) && n > 0;
     if (q->sg_pending.valid) { q->sg_pending.in = *in; q->sg_pending.B = B; }
@@ -185,10 +184,10 @@ static int stereo_stage_images(ssm_ctx* c, const uint8_t* const* imgs, int nimg,
         HIPCHK(c, hipDeviceSynchronize());
         DALLOC(c, q->in_stage, (size_t)4 * np);
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));               // the previous call's copies out of the staging buffer are done
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));               // the previous call's copies out of the staging buffer are done
     for (int k = 0; k < nimg; k++)
         for (int y = 0; y < h; y++) memcpy(c->h_pinned + (size_t)k * np + (size_t)y * w, imgs[k] + (size_t)y * stride, w);
-    HIPCHK(c, hipMemcpyAsync(q->in_stage, c->h_pinned, (size_t)nimg * np, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(q->in_stage, c->h_pinned, (size_t)nimg * np, hipMemcpyHostToDevice, c->main.stream));
     *dev_out = q->in_stage;
     return SSM_OK;
 }
@@ -209,8 +208,8 @@ extern "C" int ssm_quad_track(ssm_ctx* c, const uint8_t* lc, const uint8_t* rc, 
     r = stereo_seq_run(c, &in, &o, true); if (r) return r;
     c->stereo->have_prev = false;                                // a per-pair call is not part of a sequence
     int m = 0;
-    HIPCHK(c, hipMemcpyAsync(&m, o.nquad + 1, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&m, o.nquad + 1, 4, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     r = check_device_flags(c, false); if (r) return r;
     *n_out = m;
     if (m > cap) FAIL(c, SSM_E_CAPACITY, "pmatch buffer too small (need " + std::to_string(m) + ")");
@@ -228,11 +227,11 @@ extern "C" int ssm_gftt(ssm_ctx* c, const uint8_t* img, int w, int h, int stride
     if (max_corners > 32767) FAIL(c, SSM_E_INVAL, "max_corners must be <= 32767");
     int r = stereo_init(c, w, h, max_corners); if (r) return r;
     StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
-    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, img, stride, w, h, hipMemcpyHostToDevice, c->stream));        // side 0, slot 1, level 0
-    HIPCHK(c, k_quad_gftt(qb, 1, max_corners, quality, min_distance, q->gw, q->pts, q->maxc, q->ncorner, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, img, stride, w, h, hipMemcpyHostToDevice, c->main.stream));        // side 0, slot 1, level 0
+    HIPCHK(c, k_quad_gftt(qb, 1, max_corners, quality, min_distance, q->gw, q->pts, q->maxc, q->ncorner, c->main.stream));
     int n = 0;
-    HIPCHK(c, hipMemcpyAsync(&n, q->ncorner, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(&n, q->ncorner, 4, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     r = check_device_flags(c, false); if (r) return r;
     *n_out = n;
     if (n > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small");
@@ -250,16 +249,16 @@ extern "C" int ssm_lk_track(ssm_ctx* c, const uint8_t* prev, const uint8_t* next
     int r = stereo_init(c, w, h, n > 1000 ? n : 1000); if (r) return r;
     StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
     // previous image = (side 0, slot 1), next image = (side 1, slot 1)
-    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, prev, stride, w, h, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(qb.B1 + 1) * qb.slot_elems, w, next, stride, w, h, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_quad_pyramids(qb, 1, c->stream));
+    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, prev, stride, w, h, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(qb.B1 + 1) * qb.slot_elems, w, next, stride, w, h, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_quad_pyramids(qb, 1, c->main.stream));
     float* d_in = q->pts; float* d_out = q->pts + (size_t)2 * q->maxc;
-    HIPCHK(c, hipMemcpyAsync(d_in, prev_pts, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, k_quad_lk(qb, d_in, n, d_out, q->status, q->err, max_count, (float)(epsilon * epsilon), (float)min_eig_threshold, c->stream));
-    HIPCHK(c, hipMemcpyAsync(next_pts, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->stream));
-    if (status) HIPCHK(c, hipMemcpyAsync(status, q->status, n, hipMemcpyDeviceToHost, c->stream));
-    if (err) HIPCHK(c, hipMemcpyAsync(err, q->err, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, prev_pts, (size_t)n * 8, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_quad_lk(qb, d_in, n, d_out, q->status, q->err, max_count, (float)(epsilon * epsilon), (float)min_eig_threshold, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(next_pts, d_out, (size_t)n * 8, hipMemcpyDeviceToHost, c->main.stream));
+    if (status) HIPCHK(c, hipMemcpyAsync(status, q->status, n, hipMemcpyDeviceToHost, c->main.stream));
+    if (err) HIPCHK(c, hipMemcpyAsync(err, q->err, (size_t)n * 4, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->stereo->have_prev = false;
     return SSM_OK;
 }
@@ -274,11 +273,11 @@ extern "C" int ssm_window_match(ssm_ctx* c, const float* kp1, const uint8_t* d1,
     int r = ensure_scratch(c, a1 + a2 + b1 + b2 + (size_t)n1 * 16 + 256); if (r) return r;
     uint8_t* p = (uint8_t*)c->d_scratch;
     float* dk1 = (float*)p; p += a1; float* dk2 = (float*)p; p += a2; uint8_t* dd1 = p; p += b1; uint8_t* dd2 = p; p += b2; ssm_dmatch* dm = (ssm_dmatch*)p;
-    HIPCHK(c, hipMemcpyAsync(dk1, kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, c->stream));
-    if (n2) { HIPCHK(c, hipMemcpyAsync(dk2, kp2, (size_t)n2 * 8, hipMemcpyHostToDevice, c->stream)); HIPCHK(c, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, c->stream)); }
-    HIPCHK(c, k_quad_window_match(dk1, dd1, n1, dk2, dd2, n2, search_width, search_height, distance_threshold, dm, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, dm, (size_t)n1 * 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(dk1, kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->main.stream)); HIPCHK(c, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, c->main.stream));
+    if (n2) { HIPCHK(c, hipMemcpyAsync(dk2, kp2, (size_t)n2 * 8, hipMemcpyHostToDevice, c->main.stream)); HIPCHK(c, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, c->main.stream)); }
+    HIPCHK(c, k_quad_window_match(dk1, dd1, n1, dk2, dd2, n2, search_width, search_height, distance_threshold, dm, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(out, dm, (size_t)n1 * 16, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 
@@ -303,9 +302,9 @@ static int sgbm_run(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w
     uint8_t* dev = nullptr;
     r = stereo_stage_images(c, imgs, 2, w, h, stride, &dev); if (r) return r;
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }      // ssm_get_stage_times then reports this call ("sgbm": all kernels of k_sgbm)
-    prof_begin(c, c->stream, "sgbm");
-    HIPCHK(c, k_sgbm(dev, dev + (size_t)w * h, w, h, 1, *params, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp, stage, c->stream, q->sg_fail, form, 1));
-    prof_end(c, c->stream);
+    prof_begin(c, c->main.stream, "sgbm");
+    HIPCHK(c, k_sgbm(dev, dev + (size_t)w * h, w, h, 1, *params, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp, stage, c->dev, c->main.sg, c->main.stream, q->sg_fail, form, 1));
+    prof_end(c, c->main.stream);
     q->sg_pending.valid = false;                                  // (the staged pair is this call's: the host-pointer entry points repeat a timed-out sweep themselves)
     *d_disp_out = q->disp; *d_depth_out = q->depth;
     return SSM_OK;
@@ -328,11 +327,11 @@ int sgbm_recover(ssm_ctx* c)
     for (int f0 = 0, bi = 0; f0 < in.n; f0 += B, bi++) {
         if (!sf[bi % SG_FAIL_WORDS]) continue;
         const int nb = in.n - f0 < B ? in.n - f0 : B;
-        HIPCHK(c, k_sgbm(in.left + (size_t)f0 * np, in.right + (size_t)f0 * np, w, h, nb, in.sgbm, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp + (size_t)f0 * np, 0, c->stream, q->sg_fail + bi % SG_FAIL_WORDS, 1, 1));
-        HIPCHK(c, k_sgbm_depth(q->disp + (size_t)f0 * np, w, h, nb, in.baseline, in.cu, in.cv, in.f, in.roix, in.roiy, in.roiz, in.scale, q->dminN[0], q->depth + (size_t)f0 * np, c->stream));
+        HIPCHK(c, k_sgbm(in.left + (size_t)f0 * np, in.right + (size_t)f0 * np, w, h, nb, in.sgbm, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp + (size_t)f0 * np, 0, c->dev, c->main.sg, c->main.stream, q->sg_fail + bi % SG_FAIL_WORDS, 1, 1));
+        HIPCHK(c, k_sgbm_depth(q->disp + (size_t)f0 * np, w, h, nb, in.baseline, in.cu, in.cv, in.f, in.roix, in.roiy, in.roiz, in.scale, q->dminN[0], q->depth + (size_t)f0 * np, c->main.stream));
         redone++;
     }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->sgbm_fallbacks += redone;
     c->err = "note: the SGBM sweep of " + std::to_string(redone) + " sub-batch(es) timed out in a strip hand-off; they were repeated with form 1 (results complete)";
     return SSM_OK;
@@ -355,9 +354,9 @@ extern "C" int ssm_sgbm(ssm_ctx* c, const uint8_t* left, const uint8_t* right, i
     bool repeated = false;
     for (int attempt = 0; ; attempt++) {                      // a sweep whose hand-off timed out is repeated once, in form 1 (no cross-block waits)
         int r = sgbm_run(c, left, right, w, h, stride, params, stage, &dd, &ddepth, attempt ? 1 : c->sgbm_form_cfg); if (r) return r;
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2 * np, dd, np * 2, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->stereo->sg_fail, 4, hipMemcpyDeviceToHost, c->stream));      // (the staged input images at the front of the pinned area are consumed)
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2 * np, dd, np * 2, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->stereo->sg_fail, 4, hipMemcpyDeviceToHost, c->main.stream));      // (the staged input images at the front of the pinned area are consumed)
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         if (!sgbm_failed(c)) break;
         if (attempt) FAIL(c, SSM_E_HIP, "SGBM: the time-out word is set after a form-1 run");
         c->sgbm_fallbacks++; repeated = true;
@@ -379,11 +378,11 @@ extern "C" int ssm_stereo_depth(ssm_ctx* c, const uint8_t* left, const uint8_t* 
     bool repeated = false;
     for (int attempt = 0; ; attempt++) {
         int r = sgbm_run(c, left, right, w, h, stride, params, 0, &dd, &ddepth, attempt ? 1 : c->sgbm_form_cfg); if (r) return r;
-        HIPCHK(c, k_sgbm_depth(dd, w, h, 1, baseline, cu, cv, f, roix, roiy, roiz, scale, c->stereo->dminN[0], ddepth, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned + 4 * np, ddepth, np * 2, hipMemcpyDeviceToHost, c->stream));
-        if (disp) HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2 * np, dd, np * 2, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->stereo->sg_fail, 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, k_sgbm_depth(dd, w, h, 1, baseline, cu, cv, f, roix, roiy, roiz, scale, c->stereo->dminN[0], ddepth, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_pinned + 4 * np, ddepth, np * 2, hipMemcpyDeviceToHost, c->main.stream));
+        if (disp) HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2 * np, dd, np * 2, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->stereo->sg_fail, 4, hipMemcpyDeviceToHost, c->main.stream));
+        HIPCHK(c, hipStreamSynchronize(c->main.stream));
         if (!sgbm_failed(c)) break;
         if (attempt) FAIL(c, SSM_E_HIP, "SGBM: the time-out word is set after a form-1 run");
         c->sgbm_fallbacks++; repeated = true;
@@ -405,11 +404,11 @@ extern "C" int ssm_debug_sgbm_post(ssm_ctx* c, const int16_t* disp, int w, int h
     int r = ensure_scratch(c, 2 * b16 + 2 * b32); if (r) return r;
     uint8_t* p = (uint8_t*)c->d_scratch;
     int16_t* d_in = (int16_t*)p; int16_t* d_out = (int16_t*)(p + b16); int* parent = (int*)(p + 2 * b16); int* count = (int*)(p + 2 * b16 + b32);
-    HIPCHK(c, hipMemcpyAsync(d_in, disp, np * 2, hipMemcpyHostToDevice, c->stream));
-    if (!(op & 1)) HIPCHK(c, hipMemcpyAsync(d_out, d_in, np * 2, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, k_sgbm_post(d_in, d_out, w, h, n, op, new_val, max_size, max_diff, parent, count, c->stream));
-    HIPCHK(c, hipMemcpyAsync(out, d_out, np * 2, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_in, disp, np * 2, hipMemcpyHostToDevice, c->main.stream));
+    if (!(op & 1)) HIPCHK(c, hipMemcpyAsync(d_out, d_in, np * 2, hipMemcpyDeviceToDevice, c->main.stream));
+    HIPCHK(c, k_sgbm_post(d_in, d_out, w, h, n, op, new_val, max_size, max_diff, parent, count, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(out, d_out, np * 2, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 
@@ -428,7 +427,7 @@ extern "C" int ssm_vo_estimate(ssm_ctx* c, const ssm_pmatch* matches, int n, con
     const size_t o_m = 0, o_s = o_m + al((size_t)n * sizeof(ssm_pmatch)), o_tr = o_s + al((size_t)iters * 12 + 16), o_cnt = o_tr + al((size_t)iters * 48 + 48),
                  o_out = o_cnt + al((size_t)iters * 4 + 16), o_inl = o_out + 256, o_res = o_inl + al((size_t)n * 4), total = o_res + 256;
     int r = ensure_scratch(c, total); if (r) return r;
-    uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->stream;
+    uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->main.stream;
     HIPCHK(c, hipMemcpyAsync(p + o_m, matches, (size_t)n * sizeof(ssm_pmatch), hipMemcpyHostToDevice, s));
     if (iters) HIPCHK(c, hipMemcpyAsync(p + o_s, samples, (size_t)iters * 12, hipMemcpyHostToDevice, s));
     if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
@@ -466,9 +465,9 @@ static int pnp_solve_impl(ssm_ctx* c, const float* img, const float* obj, int n,
     r = ensure_pinned(c, al(up) + al(down)); if (r) return r;
     if (G > 1) {
         if (!c->d_pnp_xchg) { if (c->d_pnp_xchg.alloc_bytes(c, k_pnp_xchg_bytes())) return SSM_E_HIP; c->pnp_epoch = 0; }
-        if (c->pnp_epoch == 0) HIPCHK(c, hipMemsetAsync(c->d_pnp_xchg, 0, k_pnp_xchg_bytes(), c->stream));
+        if (c->pnp_epoch == 0) HIPCHK(c, hipMemsetAsync(c->d_pnp_xchg, 0, k_pnp_xchg_bytes(), c->main.stream));
     }
-    uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->stream;
+    uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->main.stream;
     uint8_t* hu = c->h_pinned; uint8_t* hd = c->h_pinned + al(up);
     if (n) { memcpy(hu + o_img, img, (size_t)n * 8); memcpy(hu + o_obj, obj, (size_t)n * 12); }
     memset(hu + o_hdr, 0, HDR); memcpy(hu + o_hdr, T, 128);

@@ -1,7 +1,7 @@
 // ssm_track.hip -- ssm_tracker_*: rgbd_tutor::Tracker::updateFrame (reference src/track.cpp:8-36, 140-212) for all frames of an ssm_seq_process call.
 // Host orchestration of the pose chain (the chain is serial by nature: frame f's initial value and its reference poses are frame f-1's results); the PnP
 // arithmetic is include/ssm/pnp_core.h, the code the per-frame host class (include/ssm/pnp.h) runs, so both give the same bits.  Written against the
-// public C ABI (ssm_match for the on-demand pairs, ssm_memcpy_d2h) -- no access to the context's internals (ssm_ctx.h is here for DevBuf alone).
+// public C ABI (ssm_match for the on-demand pairs, ssm_memcpy_d2h) -- no access to the context's internals (ssm_ctx.h is here for DevBuf, Stream and Event alone).
 #include "ssm_ctx.h"
 #include <deque>
 #include <string>
@@ -32,7 +32,7 @@ struct ssm_tracker {
     long device_frames = 0, host_frames = 0;
     bool downgraded = false;              // the cluster form timed out once: one block per chain since (reported by ssm_tracker_last_error)
     int64_t work[4] = {0, 0, 0, 0};       // the device chain's passes over the edges (ssm_tracker_work)
-    hipStream_t own = nullptr; hipEvent_t ev = nullptr;      // own_stream: the chain's stream and the event that orders it behind the context's stream
+    Stream own; Event ev;                 // own_stream: the chain's stream and the event that orders it behind the context's stream
 };
 static void iso_identity(double* T) { for (int k = 0; k < 16; k++) T[k] = (k % 5 == 0) ? 1.0 : 0.0; }
 
@@ -58,10 +58,7 @@ extern "C" int ssm_tracker_create(ssm_ctx* ctx, const ssm_tracker_params* p, ssm
     // have to be resident together.  SSM_PNP_BLOCKS = 1 | 2 | 4 | 8 overrides (same bits in every form).
     { const char* e = getenv("SSM_PNP_BLOCKS"); const int d = p->own_stream ? 1 : 8, g = e ? atoi(e) : (p->blocks > 0 ? p->blocks : d); t->blocks = (g == 1 || g == 2 || g == 4 || g == 8) ? g : d; }
     (void)hipSetDevice(ssm_internal_get_device(ctx));              // the raw HIP calls of this file act on the context's device, whatever the calling thread used last
-    if (p->own_stream && (hipStreamCreateWithFlags(&t->own, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&t->ev, hipEventDisableTiming) != hipSuccess)) {
-        if (t->own) hipStreamDestroy(t->own);
-        delete t; return SSM_E_HIP;
-    }
+    if (p->own_stream && (t->own.ensure() != hipSuccess || t->ev.ensure() != hipSuccess)) { delete t; return SSM_E_HIP; }
     ssm_tracker_reset(t);
     *out = t;
     return SSM_OK;
@@ -70,9 +67,8 @@ extern "C" void ssm_tracker_destroy(ssm_tracker* t)
 {
     if (!t) return;
     (void)hipSetDevice(ssm_internal_get_device(t->ctx));
-    if (t->own) { hipStreamSynchronize(t->own); hipStreamDestroy(t->own); }
-    if (t->ev) hipEventDestroy(t->ev);
-    delete t;                                                      // (its device buffers with it)
+    if (t->own) hipStreamSynchronize(t->own);
+    delete t;                                                      // (its stream, event and device buffers with it)
 }
 extern "C" const char* ssm_tracker_last_error(const ssm_tracker* t) { return t ? t->err.c_str() : "null tracker"; }
 extern "C" int ssm_tracker_reset(ssm_tracker* t)

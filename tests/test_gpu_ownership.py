@@ -4,6 +4,10 @@ without what ssm_dev_alloc / ssm_host_alloc hand to the caller).  The test walks
 equalities; the device's free memory cannot serve (the GPU is shared).  The walk runs in a fresh child process (this file as a script), so that the
 contexts of other tests do not count; the child prints its readings as one JSON line and the test asserts on them.
 
+Streams and events have owners of the same kind (Stream, Event: the context's main lane and its three side lanes, the events that fork, join and order
+them, the profiling pool, a tracker's own stream, the SGBM fan of a lane) and the library counts them too (ssm_debug_live_handles); the walk reads both counts
+at the same places, and a second child forces a form-1 SGBM run to see a lane's fan -- four streams, five events -- come and go.
+
 Not covered: an allocation that fails half-way through a set-up (ensure_seq, stereo_init, seg_init, tracker_ensure_device) -- there is no failure-injection
 hook; those paths are checked by reading."""
 import json
@@ -45,10 +49,12 @@ def child():
         n, d, p = ssm.live_allocations()
         slots = 1 << c.map_stats()[0] if c is not None else 0
         return [n, d, p, d - (slots * (ssm.VOXEL_DTYPE.itemsize + 4) + 32 if slots else 0)]
+    def handles():
+        return list(ssm.live_handles())
     c = None
-    r = {"start": live()}                                                        # (a) before any context exists
+    r = {"start": live(), "h_start": handles()}                                                        # (a) before any context exists
     c = ssm.Context(0, orb_features=500, max_batch=2, voxel_capacity_log2=16, camera=CAM)
-    r["context"] = live()
+    r["context"] = live(); r["h_context"] = handles()
     # 1. the sequence path with the map stage: 3 frames (sets seq_cap), 2 frames (below it: nothing may be allocated), 6 frames (above it: ensure_seq grows and
     #    carries the history rows over); the first fused map launch trades the overflow list for the large one
     n = 6
@@ -61,15 +67,19 @@ def child():
     c.seq_process(*bufs, 2, continue_sequence=True); c.sync()
     r["seq2"] = live()
     out = c.seq_process(*bufs, n, continue_sequence=True); c.sync()
-    r["seq6"] = live()
+    r["seq6"] = live(); r["h_seq6"] = handles()
     r["map_size"] = c.map_size()
     # 4. (while the call's outputs are there) a device-chain tracker, run and closed
     trk = ssm.Tracker(c, use_device=True)
     trk.run(out, n)
     r["tracker_device_frames"] = trk.stats()[0]
-    r["tracker_open"] = live()
+    r["tracker_open"] = live(); r["h_tracker_open"] = handles()
     trk.close()
-    r["tracker_closed"] = live()
+    r["tracker_closed"] = live(); r["h_tracker_closed"] = handles()
+    trk = ssm.Tracker(c, use_device=True, own_stream=True)                       # a tracker with a stream of its own: one stream, one event
+    r["h_tracker_own_open"] = handles()
+    trk.close()
+    r["h_tracker_own_closed"] = handles()
     bgr = c.d2h(bufs[0], (n, H, W, 3), np.uint8); depth = c.d2h(bufs[1], (n, H, W), np.uint16); sem = c.d2h(bufs[2], (n, H, W, 3), np.uint8)
     for p in bufs:
         c.dev_free(p)
@@ -89,7 +99,7 @@ def child():
     r["viewer_before"], r["viewer_released"] = before, live()
     # 5. stereo on a context of its own (the first one stays open: its share is constant): one geometry, then a second one with another max_corners --
     #    stereo_init replaces the state -- against a fresh context taken straight to the second geometry
-    base = live()
+    base = live(); h_base = handles()
     s1 = ssm.Context(0, orb_features=500, max_batch=2, voxel_capacity_log2=16, camera=CAM)
     _stereo(ssm, s1, GEOM1)
     r["stereo_geom1"] = [a - b for a, b in zip(live(), base)]
@@ -97,23 +107,47 @@ def child():
     r["stereo_geom1_then_2"] = [a - b for a, b in zip(live(), base)]
     s1.close()
     r["stereo_closed"], r["stereo_base"] = live(), base
+    r["h_stereo_closed"], r["h_stereo_base"] = handles(), h_base
     s2 = ssm.Context(0, orb_features=500, max_batch=2, voxel_capacity_log2=16, camera=CAM)
     _stereo(ssm, s2, GEOM2)
     r["stereo_geom2_fresh"] = [a - b for a, b in zip(live(), base)]
     s2.close()
     c.close(); c = None
-    r["end"] = live()                                                            # (d) every tracker and context closed
+    r["end"] = live(); r["h_end"] = handles()                                    # (d) every tracker and context closed
     print("OWNERSHIP " + json.dumps(r))
 
 
-@pytest.mark.gpu
-def test_live_allocations_follow_every_owner():
-    p = subprocess.run([sys.executable, os.path.abspath(__file__)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+def child_fan():
+    """SSM_SGBM_TEST_TIMEOUT=2 (set by the parent): the occupancy check in front of form 2's sweep refuses, so the pair runs in form 1 -- on the fan of the main lane"""
+    sys.path.insert(0, ROOT)
+    import semantic_slam_mapping_amd as ssm
+    rng = np.random.default_rng(11)
+    L = np.kron(rng.integers(0, 256, (8, 40), dtype=np.uint8), np.ones((8, 8), np.uint8)); R = np.roll(L, -4, axis=1)
+    r = {"start": list(ssm.live_handles())}
+    c = ssm.Context(0, width=640, height=480, max_batch=1)
+    r["context"] = list(ssm.live_handles())
+    c.sgbm(L, R)
+    r["sgbm"] = list(ssm.live_handles())
+    c.sgbm(L, R)
+    r["sgbm_again"] = list(ssm.live_handles())
+    c.close()
+    r["end"] = list(ssm.live_handles())
+    print("OWNERSHIP " + json.dumps(r))
+
+
+def _run_child(*args, **env):
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), *args], capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, **env))
     print(p.stdout[-4000:]); print(p.stderr[-4000:])
     assert p.returncode == 0
     r = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("OWNERSHIP ")][-1][len("OWNERSHIP "):])
     for k, v in r.items():
         print(k, v)
+    return r
+
+
+@pytest.mark.gpu
+def test_live_allocations_follow_every_owner():
+    r = _run_child()
     assert r["start"] == [0, 0, 0, 0]                                               # (a)
     assert r["context"][0] > 0 and r["context"][1] > 0 and r["context"][2] == 64       # (the map counter ring: the one pinned buffer of a fresh context)
     # (b) 1: the walk reached the paths it is meant to reach
@@ -135,7 +169,24 @@ def test_live_allocations_follow_every_owner():
     assert r["stereo_geom1"][1] > r["stereo_geom1_then_2"][1]
     assert r["stereo_closed"] == r["stereo_base"]
     assert r["end"] == [0, 0, 0, 0]                                                 # (d)
+    # streams and events, at the same places
+    assert r["h_start"] == [0, 0]                                                # before any context
+    assert r["h_context"][0] == 1                                                # a fresh context owns its main stream alone: the side lanes come at first use
+    assert r["h_seq6"][0] == 4                                                   # three sub-batches per call: main + the three side lanes
+    assert r["h_tracker_open"] == r["h_tracker_closed"] == r["h_seq6"]           # a tracker on the context's stream owns no handle
+    assert r["h_tracker_own_open"] == [r["h_seq6"][0] + 1, r["h_seq6"][1] + 1] and r["h_tracker_own_closed"] == r["h_seq6"]
+    assert r["h_stereo_closed"] == r["h_stereo_base"]
+    assert r["h_end"] == [0, 0]
+
+
+@pytest.mark.gpu
+def test_sgbm_fan_belongs_to_its_lane():
+    r = _run_child("fan", SSM_SGBM_TEST_TIMEOUT="2")
+    assert r["start"] == [0, 0] and r["context"][0] == 1
+    assert r["sgbm"] == [r["context"][0] + 4, r["context"][1] + 5]               # the fan: four streams, a fork event and four done events
+    assert r["sgbm_again"] == r["sgbm"]                                           # made once per lane
+    assert r["end"] == [0, 0]
 
 
 if __name__ == "__main__":
-    child()
+    child_fan() if sys.argv[1:] == ["fan"] else child()
