@@ -17,6 +17,9 @@ HOST = os.path.join(ROOT, "semantic_slam_mapping_amd", "host")
 SIZES = (0, 1, 63, 64, 65, 1000, 2024)
 SCORE_TOL = 8 * 2024 * 2.0 ** -53
 VOCABS = {"k10L3": lambda: R.make_vocab(10, 3, 11), "k4L5": lambda: R.make_vocab(4, 5, 12), "irregular": lambda: R.make_irregular_vocab(13)}
+# transform only: a 300-child root over 17- to 20-child groups with planted duplicate descriptors, and three words of which some or all weigh nothing
+TRANSFORM_VOCABS = dict(VOCABS, wide=lambda: R.make_wide_vocab(14)[0], tiny=lambda: R.make_tiny_vocab(15), tiny_zero1=lambda: R.make_tiny_vocab(15, zero=(1,)),
+                        tiny_zero02=lambda: R.make_tiny_vocab(15, zero=(0, 2)), tiny_zero_all=lambda: R.make_tiny_vocab(15, zero=(0, 1, 2)))
 
 
 def _ssm():
@@ -113,9 +116,9 @@ def test_loader_accepts_the_valid_form_of_the_rejection_cases(tmp_path):
         assert _ssm().Vocabulary(str(p)).k == k
 
 
-@pytest.mark.parametrize("name", sorted(VOCABS))
+@pytest.mark.parametrize("name", sorted(TRANSFORM_VOCABS))
 def test_transform_against_restatement(name):
-    arrays = VOCABS[name]()
+    arrays = TRANSFORM_VOCABS[name]()
     rv = R.RefVocab(*arrays)
     v = _ssm().Vocabulary.from_arrays(*arrays)
     rng = np.random.default_rng(21)
@@ -139,6 +142,50 @@ def test_transform_against_restatement(name):
         assert set(ids.tolist()) == set(int(w) for w in wof if int(w) not in zero_words)
     if name == "irregular":
         assert len(zero_words) > 0
+    if name == "tiny_zero_all":
+        assert len(ids) == 0 and len(wof) == SIZES[-1]                    # a non-empty frame, an empty vector
+    if name.startswith("tiny"):
+        assert set(wof.tolist()) == {0, 1, 2}                             # runs of about n / 3
+
+
+def test_wide_vocab_earlier_copy_wins():
+    """the 300-child root and the 17- to 20-child groups: a query equal to a duplicated descriptor is at distance 0 from both copies and gets the earlier one,
+    on the host path and in the restatement; random queries meet natural ties for the minimum at the root as well"""
+    arrays, queries, want = R.make_wide_vocab(14)
+    rv = R.RefVocab(*arrays)
+    v = _ssm().Vocabulary.from_arrays(*arrays)
+    assert (v.k, v.L, v.nodes, rv.cnt[0]) == (20, 2, rv.nodes, 300) and sorted(set(rv.cnt[1:21].tolist())) == [17, 18, 19, 20] and not rv.cnt[21:].any()
+    assert len(queries) == len(R.WIDE_ROOT_PAIRS) + len(R.WIDE_GROUPS) * len(R.WIDE_GROUP_PAIRS)
+    assert np.array_equal(rv.words_of(queries), want) and np.array_equal(v.transform(queries)[0], want)
+    inner = want[len(R.WIDE_ROOT_PAIRS):]                                # the group queries did go down into their groups: words of the groups' leaves
+    assert inner.min() >= 280 and len(set(inner.tolist())) == len(inner)
+    desc = arrays[4]                                                     # every root child's own descriptor: itself, or the earlier copy
+    first = np.arange(300); first[[b for _, b in R.WIDE_ROOT_PAIRS]] = [a for a, _ in R.WIDE_ROOT_PAIRS]
+    leaves = np.arange(20, 300)
+    assert np.array_equal(v.transform(desc[leaves])[0], first[leaves] - 20) and np.array_equal(rv.words_of(desc[leaves]), first[leaves] - 20)
+    q = R.rand_desc(np.random.default_rng(22), 200)
+    dist = R._POP[desc[None, :300] ^ q[:, None]].sum(2)
+    ties = int(((dist == dist.min(1)[:, None]).sum(1) > 1).sum())
+    print(f"{ties} of 200 random queries tie for the minimum at the root")
+    assert ties >= 20                                                    # (about one in five: 300 distances of spread 8 around 128, the minimum near 100)
+    assert np.array_equal(v.transform(q)[0], rv.words_of(q))
+
+
+def test_score_matrix_and_candidates_range_restate_score():
+    """the vectorised sum of looper_ref is score() bit for bit, and candidates_range with the default arguments is candidates()"""
+    arrays = R.make_vocab(10, 2, 21)
+    rv = R.RefVocab(*arrays)
+    rng = np.random.default_rng(78)
+    vecs = [rv.transform(R.rand_desc(rng, n))[1:] for n in (0, 1, 30, 80, 55, 0, 300, 2)]
+    S = R.score_matrix(vecs, rv.words)
+    for q, a in enumerate(vecs):
+        for e, b in enumerate(vecs):
+            assert S[q, e] == R.score(*a, *b) and not np.signbit(S[q, e])
+    ids = [5, 3, 40, -7, 12, 13, 100, 0]
+    assert R.candidates_range(vecs, ids, 0, len(vecs), -1, 0.2, 4) == R.candidates(vecs, ids, 0.2, 4) == R.candidates_range(vecs, ids, 0, len(vecs), -1, 0.2, 4, scores=S)
+    got = R.candidates_range(vecs, ids, 2, 3, 7, -1.0, -1)
+    assert [(q, e) for q, e, _ in got] == [(q, e) for q in (2, 3, 4) for e in range(7)]      # 0 > -1 and |d| > -1: every pair in range, later entries and self too
+    assert R.candidates_range(vecs, ids, 2, 3, 0, -1.0, -1) == [] and R.candidates_range(vecs, ids, 2, 0, -1, -1.0, -1) == []
 
 
 def test_transform_capacity_reports_needed():
@@ -160,14 +207,16 @@ def test_score_against_restatement():
     for n, share in ((2024, 0), (2024, 1500), (1000, 900), (65, 65), (64, 10), (1, 1)):
         q = R.rand_desc(rng, n); q[:share] = base[:share]
         vecs.append(v.transform(q)[1:])
-    worst = 0.0
+    worst = worst_exact = 0.0
     for a in vecs:
         for b in vecs:
-            s, r = v.score(*a, *b), R.score(*a, *b)
-            worst = max(worst, abs(s - r))
+            s, r, x = v.score(*a, *b), R.score(*a, *b), R.score_exact(*a, *b)
+            worst = max(worst, abs(s - r)); worst_exact = max(worst_exact, abs(s - x), abs(r - x))
             assert abs(s - r) <= SCORE_TOL, (s, r)
+            assert abs(s - x) <= SCORE_TOL and abs(r - x) <= SCORE_TOL, (s, r, x)      # both summation orders against the sum without one
         assert abs(v.score(*a, *a) - 1.0) <= SCORE_TOL
-    print(f"worst |score - restatement| {worst:.3g} (tol {SCORE_TOL:.3g})")
+    print(f"worst |score - restatement| {worst:.3g}, worst |host or restatement - exact| {worst_exact:.3g} (tol {SCORE_TOL:.3g})")
+    assert R.score_exact(*vecs[0], np.zeros(0, np.int32), np.zeros(0)) == 0.0
     empty = (np.zeros(0, np.int32), np.zeros(0))
     assert v.score(*empty, *vecs[0]) == 0.0 and v.score(*vecs[0], *empty) == 0.0 and v.score(*empty, *empty) == 0.0
     ids, vals = vecs[0]
