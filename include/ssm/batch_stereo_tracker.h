@@ -9,6 +9,10 @@
 // raw draws and reports how many it used.  One case breaks the bulk call's assumption that every frame with a previous frame runs the VO: a frame that arrives
 // while the tracker is LOST goes through lostRecover and draws nothing -- from that frame to the end of the chunk the VO is redone per frame on the chunk's
 // quad matches (VisualOdometryStereo::ProcessMatches), with the stream where the per-frame walk would have it.
+// With uv_disparity=1 in parameters.txt (default 0: nothing changes) the chunk also gets what the triangulate10D / UVDisparity block of estimateVO
+// (track.cpp:66-79) gives every frame whose VO succeeded: after the walk one ssm_uvd_process_dev runs on the chunk's device left images and disparities,
+// with the quad matches and inlier lists downloaded (frames on the redo path take their inlier lists from ProcessMatches) and nmatch = -1 for the frames
+// that were not tracked; those frames' moving_mask / roi_mask / ground_mask stay empty, as in the per-frame class.  The pitches land in `infos`.
 // Not done here: estimateVO's orb->detectFeatures(currentFrame) (track.cpp:42) -- the ORB features of a stereo frame feed only the pose graph's loop closure
 // (out of scope); a caller that wants them runs OrbFeature::detectFeatures on the frames this class returns (their depth is set).
 #pragma once
@@ -20,7 +24,7 @@
 namespace rgbd_tutor {
 class BatchStereoTracker {
 public:
-    struct Info { int state = Tracker::NOT_READY; bool tracked = false; int n_matches = -1, n_inliers = 0; };
+    struct Info { int state = Tracker::NOT_READY; bool tracked = false; int n_matches = -1, n_inliers = 0; bool uv = false, uv_redo = false /* its inlier list came from ProcessMatches */; double pitch1 = 0, pitch2 = 0; ssm_uvd_info uvd{}; };
     BatchStereoTracker(const ParameterReader& para, VisualOdometryStereo::parameters vp, int width, int height, int chunk = 0)
         : W(width), H(height), viso(vp), voparam(vp) {
         ssm_config cfg = para.deviceConfig(width, height);
@@ -34,8 +38,15 @@ public:
         const size_t np = (size_t)W * H;
         dev->check(ssm_dev_alloc(dev->ctx(), (size_t)N * np, &d_left), "ssm_dev_alloc"); dev->check(ssm_dev_alloc(dev->ctx(), (size_t)N * np, &d_right), "ssm_dev_alloc");
         dev->check(ssm_dev_alloc(dev->ctx(), (size_t)N * vp.ransac_iters * 3 * 4 + 16, &d_rand), "ssm_dev_alloc");
+        uv_on = para.getData<int>("uv_disparity", 0) != 0;
+        if (uv_on) {                                        // the parameters Tracker's constructor sets (track.h:76-101)
+            ssm_uvd_params p; ssm_uvd_params_default(&p);
+            p.f = camera.fx; p.cu = camera.cx; p.cv = camera.cy; p.base = baseline; p.roi_x = (int)roix; p.roi_y = (int)roiy; p.roi_z = (int)roiz; p.inlier_tolerance = 3;
+            dev->check(ssm_uvd_create(dev->ctx(), &p, &uvd), "ssm_uvd_create");
+            for (void** q : {&d_moving, &d_roi, &d_ground}) dev->check(ssm_dev_alloc(dev->ctx(), (size_t)N * np, q), "ssm_dev_alloc");
+        }
     }
-    ~BatchStereoTracker() { if (dev) for (void* p : {d_left, d_right, d_rand}) if (p) ssm_dev_free(dev->ctx(), p); }
+    ~BatchStereoTracker() { if (uvd) ssm_uvd_destroy(uvd); if (dev) for (void* p : {d_left, d_right, d_rand, d_moving, d_roi, d_ground}) if (p) ssm_dev_free(dev->ctx(), p); }
     BatchStereoTracker(const BatchStereoTracker&) = delete; BatchStereoTracker& operator=(const BatchStereoTracker&) = delete;
     int chunk() const { return N; }
     Tracker::trackerState getState() const { return (Tracker::trackerState)state; }
@@ -82,6 +93,7 @@ public:
         dev->check(ssm_memcpy_d2h(dev->ctx(), vres.data(), out.vo_result, (size_t)n * 8), "ssm_memcpy_d2h");
         dev->check(ssm_memcpy_d2h(dev->ctx(), tr.data(), out.tr, (size_t)n * 48), "ssm_memcpy_d2h");
         infos.assign(n, Info());
+        vector<int32_t> uv_nm(n, -1); vector<vector<int>> uv_inl(n); vector<char> uv_redo(n, 0);      // frames whose VO succeeded: their match count; redo path: their inlier lists
         bool redo = false;                                  // from here on the VO is redone per frame (a frame went through lostRecover)
         long used = 0;                                      // draws of the frames walked so far, while the bulk results are in use
         for (int i = 0; i < n; i++) {
@@ -119,6 +131,7 @@ public:
                 }
             }
             if (!success) { cntLost++; if (cntLost > max_lost_frame) state = Tracker::LOST; info.state = state; continue; }
+            uv_nm[i] = nquad[i]; if (redo) { uv_redo[i] = 1; uv_inl[i] = viso.getInlierIndices(); }
             pose = pose * M.inverse();
             f->setTransform(pose);
             cntLost = 0;
@@ -128,15 +141,44 @@ public:
             info.state = state; info.tracked = true;
         }
         if (!redo) { viso.restoreRand(rs0); for (long k = 0; k < used; k++) (void)viso.rawRand(); }
+        if (uv_on) movingMasks(n, out, vres, uv_nm, uv_inl, uv_redo);
         fed += n;
         vector<RGBDFrame::Ptr> done; done.swap(pending);
         return done;
     }
     vector<Info> infos;                           // of the most recent flush
+private:
+    // the UVDisparity block of estimateVO (track.cpp:66-79) for the chunk: one bulk call on the chunk's device images
+    void movingMasks(int n, const ssm_stereo_out_dev& out, const vector<int32_t>& vres, vector<int32_t>& uv_nm, const vector<vector<int>>& uv_inl, const vector<char>& uv_redo) {
+        const size_t np = (size_t)W * H; const int cap = out.max_corners;
+        vector<ssm_pmatch> qm((size_t)n * cap); vector<int32_t> inl((size_t)n * cap); vector<uint8_t> fl((size_t)n * cap, 0);
+        dev->check(ssm_memcpy_d2h(dev->ctx(), qm.data(), out.quad, qm.size() * sizeof(ssm_pmatch)), "ssm_memcpy_d2h");
+        dev->check(ssm_memcpy_d2h(dev->ctx(), inl.data(), out.inliers, inl.size() * 4), "ssm_memcpy_d2h");
+        for (int i = 0; i < n; i++) {
+            if (uv_nm[i] < 0) continue;
+            if (uv_redo[i]) for (int k : uv_inl[i]) fl[(size_t)i * cap + k] = 1;
+            else for (int k = 0; k < vres[(size_t)i * 2]; k++) fl[(size_t)i * cap + inl[(size_t)i * cap + k]] = 1;
+        }
+        vector<ssm_uvd_info> ui(n);
+        dev->check(ssm_uvd_process_dev(uvd, (const uint8_t*)d_left, out.disp, n, W, H, qm.data(), uv_nm.data(), fl.data(), cap,
+                                       (uint8_t*)d_moving, (uint8_t*)d_roi, (uint8_t*)d_ground, ui.data()), "ssm_uvd_process_dev");
+        for (int i = 0; i < n; i++) {
+            if (uv_nm[i] < 0) continue;
+            const RGBDFrame::Ptr& f = pending[i];
+            f->moving_mask.create(H, W, CV_8UC1); f->roi_mask.create(H, W, CV_8UC1); f->ground_mask.create(H, W, CV_8UC1);
+            dev->check(ssm_memcpy_d2h_async(dev->ctx(), f->moving_mask.data, (uint8_t*)d_moving + (size_t)i * np, np), "ssm_memcpy_d2h_async");
+            dev->check(ssm_memcpy_d2h_async(dev->ctx(), f->roi_mask.data, (uint8_t*)d_roi + (size_t)i * np, np), "ssm_memcpy_d2h_async");
+            dev->check(ssm_memcpy_d2h_async(dev->ctx(), f->ground_mask.data, (uint8_t*)d_ground + (size_t)i * np, np), "ssm_memcpy_d2h_async");
+            infos[i].uv = true; infos[i].uv_redo = uv_redo[i] != 0; infos[i].pitch1 = infos[i].pitch2 = ui[i].pitch_measured; infos[i].uvd = ui[i];
+        }
+        dev->check(ssm_sync(dev->ctx()), "ssm_sync");
+    }
+public:
     ssm::Device& device() { return *dev; }
 private:
     int W, H, N = 64; long fed = 0;
     unique_ptr<ssm::Device> dev; void *d_left = nullptr, *d_right = nullptr, *d_rand = nullptr;
+    bool uv_on = false; ssm_uvd* uvd = nullptr; void *d_moving = nullptr, *d_roi = nullptr, *d_ground = nullptr;
     VisualOdometryStereo viso; VisualOdometryStereo::parameters voparam;
     CAMERA_INTRINSIC_PARAMETERS camera; double baseline = 0, roix = 20, roiy = 5, roiz = 40;
     int state = Tracker::NOT_READY, cntLost = 0, max_lost_frame = 10;

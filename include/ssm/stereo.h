@@ -1,7 +1,8 @@
 // ssm/stereo.h -- the depth-from-stereo step of the KITTI path: calDisparity_SGBM (reference include/stereo.h:15,
 // src/stereo.cpp:11-30) and the disparity -> depth conversion FrameReader::next() applies right after it
 // (src/rgbdframe.cpp:81-116), both on the GPU (ssm_sgbm, ssm_stereo_depth).  triangulate10D / correct3DPoints /
-// setImageROI (the UV-disparity moving-object pipeline) are not rebuilt: Mapper discards their result.
+// setImageROI (src/stereo.cpp:41-192) have no functions of their own here: their 10-channel xyz image is never built, its channels are
+// computed per pixel where UVDisparity::Process consumes them (include/ssm/uvd_core.h, include/ssm/uvdisparity.hpp).
 #pragma once
 #include "common_headers.h"
 #include "device.h"

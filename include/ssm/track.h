@@ -3,14 +3,16 @@
 // OrbFeature (tracker_mode = rgbd, the default here).  The checked-in reference instead calls the stereo estimateVO()
 // (track.cpp:19, 38-138): tracker_mode = stereo runs that branch -- ORB features for the back end, QuadFeatureMatch in
 // tracking mode on the frame's four stereo images, VisualOdometryStereo::Process, pose chained as pose * inv(motion).  The
-// triangulate10D / UVDisparity block between them (track.cpp:68-80) only fills moving_mask, which Mapper overwrites
-// (SURVEY.md s.2), and is not rebuilt; inv() of the rigid motion is the closed form [R^T | -R^T t] instead of Matrix_'s LU
-// inverse.  PoseGraph is out of scope: setPoseGraph is kept as a no-op hook.
+// triangulate10D / UVDisparity block between them (track.cpp:66-79) runs when parameters.txt has uv_disparity=1 (the default 0 leaves the frame's
+// moving_mask, roi_mask and ground_mask empty, as before: Mapper overwrites the moving mask anyway): UVDisparity::Process of
+// include/ssm/uvdisparity.hpp after a successful viso->Process, on the frame's left image and SGBM disparity.  inv() of the rigid
+// motion is the closed form [R^T | -R^T t] instead of Matrix_'s LU inverse.  PoseGraph is out of scope: setPoseGraph is kept as a no-op hook.
 #pragma once
 #include "common_headers.h"
 #include "orb.h"
 #include "pnp.h"
 #include "vo_stereo.hpp"
+#include "uvdisparity.hpp"
 namespace rgbd_tutor {
 class PoseGraph;
 class Tracker {
@@ -26,6 +28,14 @@ public:
         if (mode != "rgbd" && mode != "stereo") throw invalid_argument("tracker_mode: 'rgbd' (Tracker::trackRefFrame) or 'stereo' (Tracker::estimateVO)");
         stereo = mode == "stereo";
         if (stereo) viso.reset(new VisualOdometryStereo(param));
+        uv_on = para.getData<int>("uv_disparity", 0) != 0;              // (not a reference parameter: the reference always runs the block)
+        if (uv_on) {                                                    // track.h:76-101
+            roi_3d.x_max = (int)para.getData<double>("camera.roix", 20.0); roi_3d.y_max = (int)para.getData<double>("camera.roiy", 5.0); roi_3d.z_max = (int)para.getData<double>("camera.roiz", 40.0);
+            const CAMERA_INTRINSIC_PARAMETERS cam = para.getCamera();
+            calib_.f = cam.fx; calib_.c_x = cam.cx; calib_.c_y = cam.cy; calib_.b = para.getData<double>("camera.baseline");
+            uv_disparity.SetCalibPars(calib_); uv_disparity.SetROI3D(roi_3d);
+            uv_disparity.SetOutThreshold(6.0f); uv_disparity.SetInlierTolerance(3); uv_disparity.SetMinAdjustIntense(20);
+        }
     }
     void setPoseGraph(shared_ptr<PoseGraph> pg) { poseGraph = pg; }
     // put in a new frame, returns its pose (src/track.cpp:8-28)
@@ -81,6 +91,9 @@ protected:
             lastMatches = (int)quadmatcher.quadmatches.size();
             if (viso->Process(quadmatcher)) {
                 cv::Mat motion = viso->getMotion();
+                if (uv_on && !currentFrame->disparity.empty())         // track.cpp:66-79 (triangulate10D's xyz image is computed per pixel inside Process)
+                    currentFrame->moving_mask = uv_disparity.Process(currentFrame->img_lc, currentFrame->disparity, *viso, currentFrame->xyz,
+                                                                     currentFrame->roi_mask, currentFrame->ground_mask, pitch1, pitch2);
                 Eigen::Isometry3d M;
                 for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) M(i, j) = motion.at<double>(i, j);
                 pose = pose * M.inverse();
@@ -142,10 +155,15 @@ protected:
     }
 public:
     int lastMatches = 0, lastInliers = 0;
+    // motion (track.h:135-138)
+    ROI3D roi_3d = ROI3D(30, 10, 30);
+    CalibPars calib_;
+    UVDisparity uv_disparity;
+    double pitch1 = 0, pitch2 = 0;
 protected:
     const ParameterReader& parameterReader;
     VisualOdometryStereo::parameters voparam;
-    bool stereo = false; unique_ptr<VisualOdometryStereo> viso; Eigen::Isometry3d pose = Eigen::Isometry3d::Identity();      // estimateVO state (track.h:181)
+    bool stereo = false, uv_on = false; unique_ptr<VisualOdometryStereo> viso; Eigen::Isometry3d pose = Eigen::Isometry3d::Identity();      // estimateVO state (track.h:181)
     RGBDFrame::Ptr currentFrame = nullptr;
     deque<RGBDFrame::Ptr> refFrames;
     int refFramesSize = 5;

@@ -361,6 +361,64 @@ int  ssm_looper_scores(ssm_looper* l, int entry, int against, double* scores);
 int  ssm_looper_query(ssm_looper* l, int first, int n, int against, double min_sim_score, int min_interval,
                       int32_t* pairs, double* scores, int cap, int* n_out);
 
+/* ---- UVDisparity::Process (include/uvdisparity.hpp, src/uvdisparity.cpp:842-903) with triangulate10D, correct3DPoints and setImageROI
+ * (src/stereo.cpp:41-192): the moving-object mask, the ROI mask, the ground (obstacle) mask and the pitch of a stereo frame from its left image, its
+ * SGBM disparity (x16 fixed point) and the quad matches with their VO inlier flags.  DESIGN.md s.11 is the contract; include/ssm/uvd_core.h the per-pixel
+ * arithmetic, shared by the kernels and the host function, so device == host bit for bit.  Disparities 0 < d / 16 <= 255 are supported. */
+typedef struct {
+    double f, cu, cv, base;                  /* CalibPars */
+    double roi_x, roi_y, roi_z;              /* ROI3D (parameters.txt camera.roix / roiy / roiz: include/track.h:80-86) */
+    int32_t min_intense, min_disparity_raw, min_area;       /* USegmentPars() = 32, 64, 40 */
+    int32_t inlier_tolerance;                /* SetInlierTolerance(3), include/track.h:100 */
+} ssm_uvd_params;
+enum { SSM_UVD_TOO_LARGE = 1 /* a disparity above 255 x 16 */, SSM_UVD_NO_LINE = 2 /* v_cols <= 26 or fewer than 2 line points */, SSM_UVD_SKIPPED = 4 /* nmatch < 0 */ };
+typedef struct {
+    int32_t status;                          /* SSM_UVD_* bits; any bit: the three masks are zero and the Kalman filters did not move */
+    int32_t v_cols, u_rows;                  /* ceil(max / 16), and that + 1 */
+    int32_t otsu_threshold, n_line_points;
+    float   slope;                           /* b / a of the ground line in the V-disparity image */
+    double  v_c;                             /* its intercept */
+    float   pitch_measured, pitch_filtered;  /* (float)atan((cv - v_c) / f) = Process' pitch1 = pitch2; Kalman filter 1's state after this frame */
+    int32_t n_seeds, n_masks_found, n_masks_merged, n_masks_kept;     /* flood fills started; of area > min_area; after mergeMasks; after verifyByInliers */
+    int32_t n_moving;                        /* pixels of the moving mask that are 255 */
+    float   line[4];                         /* fitLine's (cos t, sin t, mean x, mean y) */
+    int32_t pad;
+} ssm_uvd_info;
+typedef struct ssm_uvd ssm_uvd;
+void ssm_uvd_params_default(ssm_uvd_params* p);          /* include/track.h:84-101 + USegmentPars(); the calibration is KITTI 00's (parameters.txt) */
+/* the object owns the workspaces and the two Kalman filters.  ctx may be NULL: an object for ssm_uvd_process_host only, which needs no GPU */
+int  ssm_uvd_create(ssm_ctx* ctx, const ssm_uvd_params* params, ssm_uvd** out);
+void ssm_uvd_destroy(ssm_uvd* u);
+int  ssm_uvd_reset(ssm_uvd* u);                           /* the Kalman filters start again from x = 0, P = 1 */
+/* one pair, HOST pointers; left (bytes) and disp (int16) have rows of `stride` elements, the masks (w x h bytes, packed; each may be NULL) are written.
+ * matches / inlier_flags (n_matches; 1 = VO inlier, 0 = outlier) are in/out the way filterInOut edits vo.quadmatches_inlier / _outlier: a match that
+ * is erased gets bit 1 (value 2) of its flag set, one that stays gets its dis_c recorded.  n_matches < 0 skips the frame like nmatch[i] < 0 below.  Synchronous */
+int  ssm_uvd_process(ssm_uvd* u, const uint8_t* left, const int16_t* disp, int w, int h, int stride, ssm_pmatch* matches, uint8_t* inlier_flags,
+                     int n_matches, uint8_t* moving, uint8_t* roi, uint8_t* ground, ssm_uvd_info* info);
+/* n frames in frame order; left_dev / disp_dev (n x h x w, packed) and the masks (n x h x w bytes; each may be NULL) are DEVICE pointers, e.g.
+ * ssm_stereo_out_dev.disp of a chunk.  matches (n x cap), nmatch (n) and inlier_flags (n x cap) are HOST arrays, edited as above; nmatch[i] < 0 skips
+ * frame i (viso.Process failed: the reference does not run the block, src/track.cpp:62-79): zero masks, SSM_UVD_SKIPPED, the Kalman state does not move.
+ * info: n entries.  Three device phases around two host steps, one wait each; returns when the masks are complete.  The context's lock is released during
+ * the host steps (other threads of the context run meanwhile); one ssm_uvd object serves one thread at a time */
+int  ssm_uvd_process_dev(ssm_uvd* u, const uint8_t* left_dev, const int16_t* disp_dev, int n, int w, int h, ssm_pmatch* matches, const int32_t* nmatch,
+                         uint8_t* inlier_flags, int cap, uint8_t* moving_dev, uint8_t* roi_dev, uint8_t* ground_dev, ssm_uvd_info* info);
+/* ssm_uvd_process on the CPU: the same functions of uvd_core.h, the same bits.  Needs no GPU */
+int  ssm_uvd_process_host(ssm_uvd* u, const uint8_t* left, const int16_t* disp, int w, int h, int stride, ssm_pmatch* matches, uint8_t* inlier_flags,
+                          int n_matches, uint8_t* moving, uint8_t* roi, uint8_t* ground, ssm_uvd_info* info);
+/* intermediate images of frame `frame` of the last call, for the tests (each may be NULL): v_dis h x 256 (columns from v_cols on are zero), u_dis
+ * u_rows x w after adjustUdisIntense, bin h x 256 (the Otsu image, v_cols columns used), union_mask u_rows x w */
+int  ssm_debug_uvd_images(ssm_uvd* u, int frame, uint8_t* v_dis, uint8_t* u_dis, uint8_t* bin, uint8_t* union_mask);
+/* one recorded stage of that frame, packed: 1 blurred, 2 eroded, 3 binary (h x v_cols bytes), 4 the point list (int32 x, y pairs), 5 the U-disparity
+ * image before the adjustment (u_rows x w), 7 the area of every flood fill (int32), 8 / 9 / 10 the masks found / merged / kept (each u_rows x w bytes).
+ * *bytes: the stage's size (out NULL: only that; more than cap: SSM_E_CAPACITY) */
+/* on != 0: later calls keep a copy of every mask found / merged / kept per frame (stages 8 - 10; SSM_E_INVAL without it).  Off by default: the masks then move
+ * through findAllMasks, mergeMasks and verifyByInliers without being copied */
+int  ssm_debug_uvd_record(ssm_uvd* u, int on);
+int  ssm_debug_uvd_stage(ssm_uvd* u, int frame, int stage, void* out, size_t cap, size_t* bytes);
+/* host wall time of the last ssm_uvd_process / ssm_uvd_process_dev in milliseconds: host step 1 (lines, Kalman), host step 2 (filter, fills, merge, verify),
+ * the whole call with its three waits.  For scripts/uvd_bench.py */
+int  ssm_debug_uvd_times(ssm_uvd* u, double ms[3]);
+
 /* ---- device-resident batched stereo path (BASELINE.json configs[3]): n frames of a rectified stereo sequence, all DEVICE pointers.
  * The reference walks the KITTI sequence one frame at a time: FrameReader::next() computes the depth of the current pair with SGBM
  * (src/rgbdframe.cpp:64-116, src/stereo.cpp:11-30), Tracker::estimateVO builds a QuadFeatureMatch on (current left, current right, previous left,

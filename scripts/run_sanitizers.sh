@@ -50,12 +50,13 @@ step() {
     step "oracle build + run ($s)" make -s -C "$ROOT/oracle" SAN=$s san
     echo "## host SAN=$s"
     step "host build ($s)" make -s -C "$HOST" SAN=$s san
-    for b in test_png_$s test_pnp_$s test_threads_$s test_looper_$s; do [ -x "$HOST/$b" ] || { echo "### $b: MISSING BINARY"; fail=1; }; done
+    for b in test_png_$s test_pnp_$s test_threads_$s test_looper_$s test_uvd_$s; do [ -x "$HOST/$b" ] || { echo "### $b: MISSING BINARY"; fail=1; }; done
     [ -x "$HOST/test_png_$s" ] && step "test_png_$s" "$HOST/test_png_$s" "$TMP/png"
     for c in outliers nodepth lanes; do
       [ -x "$HOST/test_pnp_$s" ] && step "test_pnp_$s $c" "$HOST/test_pnp_$s" "$HOST/parameters_test.txt" "$TMP/$c.bin" "$TMP/$c.out"
     done
     [ -x "$HOST/test_looper_$s" ] && step "test_looper_$s" "$HOST/test_looper_$s" "$TMP" "$TMP/looper_vocab.txt"
+    [ -x "$HOST/test_uvd_$s" ] && step "test_uvd_$s" "$HOST/test_uvd_$s"
     [ -x "$HOST/test_threads_$s" ] && step "test_threads_$s" "$HOST/test_threads_$s" "$HOST/parameters_test.txt"
   done
   echo "## result: $([ $fail = 0 ] && echo CLEAN || echo FINDINGS)"

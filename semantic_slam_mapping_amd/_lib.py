@@ -60,6 +60,17 @@ class TrackerParams(C.Structure):
     _fields_ = [("max_lost_frame", C.c_int32), ("ref_frames", C.c_int32), ("pnp_min_inliers", C.c_int32), ("use_device", C.c_int32), ("first_pose", C.c_double * 16), ("own_stream", C.c_int32), ("blocks", C.c_int32)]
 
 
+class UvdParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("f", "cu", "cv", "base", "roi_x", "roi_y", "roi_z")] + \
+               [(n, C.c_int32) for n in ("min_intense", "min_disparity_raw", "min_area", "inlier_tolerance")]
+
+
+class UvdInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("status", "v_cols", "u_rows", "otsu_threshold", "n_line_points")] + \
+               [("slope", C.c_float), ("v_c", C.c_double), ("pitch_measured", C.c_float), ("pitch_filtered", C.c_float)] + \
+               [(n, C.c_int32) for n in ("n_seeds", "n_masks_found", "n_masks_merged", "n_masks_kept", "n_moving")] + [("line", C.c_float * 4), ("pad", C.c_int32)]
+
+
 # every symbol include/ssm_hip.h declares: name -> (restype, argtypes)
 _P, _I, _D, _F, _U64, _SZ = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_uint64, C.c_size_t
 SYMBOLS = {
@@ -139,6 +150,17 @@ SYMBOLS = {
     "ssm_looper_bow": (_I, [_P, _I, _P, _P, _I, C.POINTER(_I)]),
     "ssm_looper_scores": (_I, [_P, _I, _I, _P]),
     "ssm_looper_query": (_I, [_P, _I, _I, _I, _D, _I, _P, _P, _I, C.POINTER(_I)]),
+    "ssm_uvd_params_default": (None, [C.POINTER(UvdParams)]),
+    "ssm_uvd_create": (_I, [_P, C.POINTER(UvdParams), C.POINTER(_P)]),
+    "ssm_uvd_destroy": (None, [_P]),
+    "ssm_uvd_reset": (_I, [_P]),
+    "ssm_uvd_process": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "ssm_uvd_process_dev": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "ssm_uvd_process_host": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _P]),
+    "ssm_debug_uvd_images": (_I, [_P, _I, _P, _P, _P, _P]),
+    "ssm_debug_uvd_stage": (_I, [_P, _I, _I, _P, _SZ, C.POINTER(_SZ)]),
+    "ssm_debug_uvd_record": (_I, [_P, _I]),
+    "ssm_debug_uvd_times": (_I, [_P, C.POINTER(C.c_double * 3)]),
     "ssm_segnet_num_layers": (_I, []),
     "ssm_segnet_layer_shape": (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ssm_segnet_set_layer": (_I, [_P, _I, _P, _P, _P]),

@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -283,6 +283,114 @@ class Looper:
         if getattr(self, "h", None):
             if self.ctx.h:
                 self.lib.ssm_looper_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+UVD_INFO_DTYPE = np.dtype([("status", "i4"), ("v_cols", "i4"), ("u_rows", "i4"), ("otsu_threshold", "i4"), ("n_line_points", "i4"), ("slope", "f4"), ("v_c", "f8"),
+                           ("pitch_measured", "f4"), ("pitch_filtered", "f4"), ("n_seeds", "i4"), ("n_masks_found", "i4"), ("n_masks_merged", "i4"),
+                           ("n_masks_kept", "i4"), ("n_moving", "i4"), ("line", "f4", (4,)), ("pad", "i4")])
+assert UVD_INFO_DTYPE.itemsize == C.sizeof(UvdInfo) == 80
+UVD_TOO_LARGE, UVD_NO_LINE, UVD_SKIPPED = 1, 2, 4
+UVD_STAGE_BLUR, UVD_STAGE_ERODE, UVD_STAGE_BIN, UVD_STAGE_POINTS, UVD_STAGE_U_RAW, UVD_STAGE_AREAS, UVD_STAGE_FOUND, UVD_STAGE_MERGED, UVD_STAGE_KEPT = 1, 2, 3, 4, 5, 7, 8, 9, 10
+
+
+class UVDisparity:
+    """ssm_uvd: UVDisparity::Process (src/uvdisparity.cpp:842-903) -- the moving-object, ROI and ground masks and the pitch of stereo frames from the left
+    image, the SGBM disparity (x16) and the quad matches with their VO inlier flags.  UVDisparity(ctx) runs the per-pixel stages on the device;
+    UVDisparity(None) is a host-only object whose process_host needs no GPU.  Keyword arguments are fields of ssm_uvd_params (SetCalibPars, SetROI3D,
+    SetUSegmentPars, SetInlierTolerance).  matches / inlier_flags come back edited the way filterInOut edits the VO's lists: flag bit 1 (value 2) = erased."""
+
+    def __init__(self, ctx=None, record=False, **kw):
+        """record: keep every flood-fill mask of a frame for stage() (ssm_debug_uvd_record; the tests)"""
+        self.ctx = ctx; self.lib = ctx.lib if ctx is not None else _lib.load()
+        p = UvdParams()
+        self.lib.ssm_uvd_params_default(C.byref(p))
+        for k, v in kw.items():
+            if not hasattr(p, k):
+                raise KeyError(k)
+            setattr(p, k, v)
+        self.params = p
+        h = C.c_void_p()
+        rc = self.lib.ssm_uvd_create(ctx.h if ctx is not None else None, C.byref(p), C.byref(h))
+        if rc != 0:
+            raise SsmError(rc, (self.lib.ssm_last_error(ctx.h if ctx is not None else None) or b"").decode())
+        self.h = h
+        if record:
+            self.lib.ssm_debug_uvd_record(self.h, 1)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SsmError(rc, (self.lib.ssm_last_error(self.ctx.h) or b"").decode() if self.ctx is not None else "ssm_uvd")
+
+    def reset(self):
+        self._chk(self.lib.ssm_uvd_reset(self.h))
+
+    def _one(self, fn, left, disp, matches, inlier_flags, skip):
+        left = np.asarray(left, np.uint8); disp = np.asarray(disp, np.int16)
+        if left.strides[1] != 1 or disp.strides[1] != 2 or disp.strides[0] != 2 * left.strides[0]:
+            left = np.ascontiguousarray(left); disp = np.ascontiguousarray(disp)
+        h, w = left.shape
+        assert disp.shape == (h, w)
+        m = np.ascontiguousarray(matches if matches is not None else np.zeros(0, PMATCH_DTYPE), PMATCH_DTYPE).copy()
+        fl = np.ascontiguousarray(inlier_flags if inlier_flags is not None else np.zeros(0, np.uint8), np.uint8).copy()
+        assert len(m) == len(fl)
+        out = {k: np.zeros((h, w), np.uint8) for k in ("moving", "roi", "ground")}
+        info = np.zeros(1, UVD_INFO_DTYPE)
+        self._chk(fn(self.h, _ptr(left), _ptr(disp), w, h, left.strides[0], _ptr(m) if len(m) else None, _ptr(fl) if len(fl) else None, -1 if skip else len(m),
+                     _ptr(out["moving"]), _ptr(out["roi"]), _ptr(out["ground"]), _ptr(info)))
+        out.update(info=info[0], matches=m, inlier_flags=fl)
+        return out
+
+    def process(self, left, disp, matches=None, inlier_flags=None, skip=False):
+        """one pair through the device path -> dict(moving, roi, ground, info, matches, inlier_flags).  left / disp may be views with a common row stride"""
+        return self._one(self.lib.ssm_uvd_process, left, disp, matches, inlier_flags, skip)
+
+    def process_host(self, left, disp, matches=None, inlier_flags=None, skip=False):
+        """the same on the CPU (no GPU needed): the same bits"""
+        return self._one(self.lib.ssm_uvd_process_host, left, disp, matches, inlier_flags, skip)
+
+    def process_dev(self, left_dev, disp_dev, n, w, h, matches, nmatch, inlier_flags, moving_dev=None, roi_dev=None, ground_dev=None):
+        """n device frames (packed); matches (n x cap), nmatch (n; < 0 skips the frame) and inlier_flags (n x cap) are host arrays -> (info, matches, inlier_flags)"""
+        m = np.ascontiguousarray(matches, PMATCH_DTYPE).reshape(n, -1).copy(); fl = np.ascontiguousarray(inlier_flags, np.uint8).reshape(n, -1).copy()
+        nm = np.ascontiguousarray(nmatch, np.int32)
+        cap = m.shape[1]
+        assert fl.shape == m.shape and len(nm) == n
+        info = np.zeros(max(n, 1), UVD_INFO_DTYPE)
+        self._chk(self.lib.ssm_uvd_process_dev(self.h, left_dev, disp_dev, n, w, h, _ptr(m) if cap else None, _ptr(nm), _ptr(fl) if cap else None, cap, moving_dev, roi_dev, ground_dev, _ptr(info)))
+        return info[:n], m, fl
+
+    def images(self, frame, w, h):
+        """the intermediate images of a frame of the last call: v_dis and bin (h x 256), u_dis and union (256 x w; u_rows rows used)"""
+        out = dict(v_dis=np.zeros((h, 256), np.uint8), u_dis=np.zeros((256, w), np.uint8), bin=np.zeros((h, 256), np.uint8), union=np.zeros((256, w), np.uint8))
+        self._chk(self.lib.ssm_debug_uvd_images(self.h, frame, _ptr(out["v_dis"]), _ptr(out["u_dis"]), _ptr(out["bin"]), _ptr(out["union"])))
+        return out
+
+    def stage(self, frame, stage):
+        """one recorded stage of a frame of the last call as bytes (UVD_STAGE_*; the point list and the areas are int32)"""
+        n = C.c_size_t(0)
+        self._chk(self.lib.ssm_debug_uvd_stage(self.h, frame, stage, None, 0, C.byref(n)))
+        buf = np.zeros(max(n.value, 1), np.uint8)
+        self._chk(self.lib.ssm_debug_uvd_stage(self.h, frame, stage, _ptr(buf), n.value, C.byref(n)))
+        buf = buf[:n.value]
+        return buf.view(np.int32) if stage in (UVD_STAGE_POINTS, UVD_STAGE_AREAS) else buf
+
+    def times(self):
+        """host wall time of the last device call in ms: (host step 1, host step 2, the whole call)"""
+        t = (C.c_double * 3)()
+        self._chk(self.lib.ssm_debug_uvd_times(self.h, C.byref(t)))
+        return tuple(float(x) for x in t)
+
+    def close(self):
+        """before the context's close(), like a Looper"""
+        if getattr(self, "h", None):
+            if self.ctx is None or self.ctx.h:
+                self.lib.ssm_uvd_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -249,6 +249,16 @@ hipError_t k_bow_score(const int32_t* offsets, const int32_t* db_ids, const doub
 hipError_t k_bow_emit(const int32_t* frame_ids, const double* scores, const int32_t* counts, int first, int nq, int against, int row, double min_score, int min_interval,
                       int32_t* pairs, double* out_scores, int cap, int32_t* hdr /* [1] = the candidate count */, hipStream_t s);
 
+// UVDisparity (kernels_uvd.hip; the arithmetic is include/ssm/uvd_core.h): n packed frames of w x h.  v_dis: n x h x 256 u8 rows of the V-disparity image,
+// maxmin: n x (max, min) of the raw disparities, preset to (INT_MIN, INT_MAX).  K: n FrameK.  u_raw / u_adj / uni: n x 256 x w (u_rows rows of each frame used).
+// coords: n x cap (u, v) of the matches, probes: n x cap (roi << 16 | the disparity's 16 bits).  counts: n, preset to 0
+namespace ssm_uvdc { struct FrameK; struct Calib; struct Roi; }
+hipError_t k_uvd_vdisp(const int16_t* disp, int n, int w, int h, uint8_t* v_dis, int32_t* maxmin, hipStream_t s);
+hipError_t k_uvd_classify(const uint8_t* left, const int16_t* disp, int n, int w, int h, const ssm_uvdc::FrameK* K, const ssm_uvdc::Calib& c, const ssm_uvdc::Roi& r,
+                          const double* rate, uint8_t* ground, uint8_t* roi, uint8_t* u_raw, uint8_t* u_adj, hipStream_t s);
+hipError_t k_uvd_probe(const uint8_t* roi, const int16_t* disp, int n, int w, int h, const int32_t* coords, const int32_t* nmatch, int cap, int32_t* probes, hipStream_t s);
+hipError_t k_uvd_segment(const int16_t* disp, const uint8_t* roi, const uint8_t* uni, int n, int w, int h, const ssm_uvdc::FrameK* K, uint8_t* moving, int32_t* counts, hipStream_t s);
+
 // for the translation units that only use the public ABI (ssm_track.hip): the configuration a context was created with
 void ssm_internal_get_config(const ssm_ctx* c, ssm_config* out);
 int ssm_internal_get_device(const ssm_ctx* c);      // the HIP device the context lives on: raw HIP calls of another translation unit select it first

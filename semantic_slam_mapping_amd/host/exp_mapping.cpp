@@ -13,6 +13,11 @@
 // queried in one call (BatchLooper).  The summary line then ends with `loop_candidates N loop_fnv H` (FNV-1a over frame id, candidate id and the score's bytes, in
 // order: the same in both modes); loops_output=<file> gets one line per candidate.  Without the flag nothing of this runs and no output changes.
 //
+// `exp_mapping <parameters> --moving` (or uv_disparity=1; needs tracker_mode=stereo): the triangulate10D / UVDisparity block of Tracker::estimateVO (reference
+// src/track.cpp:66-79; include/ssm/uvdisparity.hpp) runs after every successful stereo VO and fills the frame's moving_mask, roi_mask and ground_mask;
+// with --batched one bulk call per chunk does it.  The summary line then carries `moving_pixels N moving_fnv H pitch_fnv P` (the 255-pixels, FNV-1a over the mask
+// bytes and over the measured pitches of those frames, in order: the same in both modes).  Without the flag nothing of this runs and no output changes.
+//
 // `exp_mapping <parameters> --ranks N`: the multi-GPU form (BASELINE.json configs[4]; the reference is one process).  The parent starts
 // N FRESH processes of itself (`--rank r`, fork + exec of /proc/self/exe) before anything touches HIP -- a forked copy of a process whose HIP / RCCL
 // static constructors have already run is not a state either library is tested in; rank r drives GPU r, owns the contiguous frame block [lo, hi) of
@@ -69,6 +74,17 @@ struct LoopLog {
     }
 };
 
+// --moving: the moving masks of the frames UVDisparity::Process ran on, in frame order: the count of moving pixels, FNV-1a over the mask bytes, FNV-1a over the
+// measured pitches (the 8 bytes of pitch1)
+struct MovingLog {
+    uint64_t hm = 0xCBF29CE484222325ull, hp = 0xCBF29CE484222325ull; long long pixels = 0;
+    void add(const cv::Mat& mask, double pitch) {
+        for (int r = 0; r < mask.rows; r++) { const unsigned char* b = mask.ptr<unsigned char>(r); for (int c = 0; c < mask.cols; c++) { hm ^= b[c]; hm *= 0x100000001B3ull; pixels += b[c] == 255; } }
+        unsigned char pb[8]; memcpy(pb, &pitch, 8);
+        for (int k = 0; k < 8; k++) { hp ^= pb[k]; hp *= 0x100000001B3ull; }
+    }
+};
+
 int main(int argc, char** argv)
 {
     ParameterReader parameterReader(argc > 1 ? argv[1] : "./parameters.txt");
@@ -77,6 +93,13 @@ int main(int argc, char** argv)
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--batched") batched = true;
     bool loops = parameterReader.getData<int>("looper", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--loops") loops = true;
+    bool moving = parameterReader.getData<int>("uv_disparity", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--moving") moving = true;
+    if (moving) {
+        if (parameterReader.getData<string>("tracker_mode", string("rgbd")) != "stereo") { cerr << "exp_mapping: --moving needs tracker_mode=stereo (the U/V-disparity stage works on the SGBM disparity)" << endl; return 2; }
+        parameterReader.set("uv_disparity", "1");
+    }
+    MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
         if (string(argv[i]) == "--rank") my_rank = atoi(argv[i + 1]);
@@ -219,6 +242,7 @@ int main(int argc, char** argv)
                 for (size_t i = 0; i < done.size(); i++) {
                     const RGBDFrame::Ptr& f = done[i];
                     traj.add(f);
+                    if (moving && bs->infos[i].uv) moving_log.add(f->moving_mask, bs->infos[i].pitch1);       // (before the key-frame gate: Mapper overwrites a key-frame's mask)
                     poseGraph.tryInsertKeyFrame(const_cast<RGBDFrame::Ptr&>(f));
                     if (bs->infos[i].state == Tracker::LOST) { cout << "tracker is lost" << endl; lost++; }
                     if (counted) timed++;
@@ -248,6 +272,7 @@ int main(int argc, char** argv)
             const tp b = now();
             if (use_gt_pose) frame->setTransform(gt);           // synthetic stream: poses are given, the tracker only produces features/matches
             traj.add(frame);
+            if (moving && !frame->moving_mask.empty()) moving_log.add(frame->moving_mask, tracker->pitch1);
             if (poseGraph.tryInsertKeyFrame(frame) && looper) {
                 looper->add(frame);
                 looper->getPossibleLoops(frame);
@@ -268,6 +293,7 @@ int main(int argc, char** argv)
              << " map_points " << (mapper.getGlobalMap() ? mapper.getGlobalMap()->points.size() : 0) << " pose_fnv " << hex << traj.h << dec << " host_loop_fps " << nframes / s;
         // the rates of the frames after timing_skip_frames: loop_fps = the whole loop (reader included); tracker_fps = frames / time inside updateFrame (or BatchTracker::push /
         // flush) -- what experiment/run_tracker.cpp:35-48 times; the *_ms are per frame
+        if (moving) cout << " moving_pixels " << moving_log.pixels << " moving_fnv " << hex << moving_log.hm << " pitch_fnv " << moving_log.hp << dec;
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;
             cout << " timed_frames " << timed << " loop_fps " << timed / s_timed << " tracker_fps " << (track_s > 0 ? timed / track_s : 0.0) << " reader_ms " << reader_s * 1e3 / timed

@@ -15,7 +15,36 @@ struct ssm_ctx { ssm_config cfg; std::string err; };
 static thread_local std::string g_vocab_err;
 static int vocab_fail(const std::string& msg) { g_vocab_err = msg; return SSM_E_INVAL; }
 #include "../csrc/ssm_vocab.inc"
+// likewise the U/V-disparity stage: UVDisparity::Process takes ssm_uvd_process_host on a thread without a context, and that is the library's own host pipeline
+// (csrc/ssm_uvd_host.inc over include/ssm/uvd_core.h), which so runs under the sanitizers (test_uvd); the device entry points only have to link
+#include "ssm/uvd_core.h"
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include "../csrc/ssm_uvd_host.inc"
+struct ssm_uvd { ssm_uvd_params p; UvdKalman kf1, kf2; double rate[ssm_uvdc::MAX_BINS]; UvdFrame frame; };
 extern "C" {
+void ssm_uvd_params_default(ssm_uvd_params* p) { if (p) uvd_set_defaults(p); }
+int ssm_uvd_create(ssm_ctx* c, const ssm_uvd_params* params, ssm_uvd** out)
+{
+    if (!out || !params) return SSM_E_INVAL;
+    if (c) { *out = nullptr; return SSM_E_NODEVICE; }
+    ssm_uvd* u = new ssm_uvd(); u->p = *params; uvd_rate_table(u->rate); *out = u;
+    return SSM_OK;
+}
+void ssm_uvd_destroy(ssm_uvd* u) { delete u; }
+int ssm_uvd_reset(ssm_uvd* u) { if (!u) return SSM_E_INVAL; u->kf1 = UvdKalman(); u->kf2 = UvdKalman(); return SSM_OK; }
+int ssm_uvd_process_host(ssm_uvd* u, const uint8_t* left, const int16_t* disp, int w, int h, int stride, ssm_pmatch* matches, uint8_t* inlier_flags, int n_matches,
+                         uint8_t* moving, uint8_t* roi, uint8_t* ground, ssm_uvd_info* info)
+{
+    if (!u) return SSM_E_INVAL;
+    return uvd_process_host(u->p, u->rate, u->kf1, u->kf2, u->frame, left, disp, w, h, stride, matches, inlier_flags, n_matches, moving, roi, ground, info, false);
+}
+int ssm_debug_uvd_record(ssm_uvd*, int) { return SSM_OK; }
+int ssm_debug_uvd_times(ssm_uvd*, double*) { return SSM_E_NODEVICE; }
+int ssm_vo_estimate(ssm_ctx*, const ssm_pmatch*, int, const ssm_vo_params*, const int32_t*, int, double*, int32_t*, int, int*, int*) { return SSM_E_NODEVICE; }      // (VisualOdometryStereo has to link: test_uvd fills its lists by hand)
+int ssm_uvd_process(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
+int ssm_uvd_process_dev(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, const int32_t*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
 int ssm_looper_create(ssm_ctx*, const ssm_vocab*, ssm_looper**) { return SSM_E_NODEVICE; }
 void ssm_looper_destroy(ssm_looper*) {}
 int ssm_looper_size(const ssm_looper*) { return 0; }
