@@ -48,6 +48,7 @@ public:
         return currentFrame->getTransform();
     }
     trackerState getState() const { return state; }
+    bool hasCurrentFrame() { unique_lock<mutex> lck(adjustMutex); return currentFrame != nullptr; }      // (not in the reference: PoseGraph::step asks before adjust)
     // re-anchor the current frame on `ref` (called by the pose graph after optimisation), track.h:114-131
     bool adjust(const RGBDFrame::Ptr& ref) {
         unique_lock<mutex> lck(adjustMutex);

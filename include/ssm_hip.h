@@ -419,6 +419,68 @@ int  ssm_debug_uvd_stage(ssm_uvd* u, int frame, int stage, void* out, size_t cap
  * the whole call with its three waits.  For scripts/uvd_bench.py */
 int  ssm_debug_uvd_times(ssm_uvd* u, double ms[3]);
 
+/* ---- PoseGraph's optimiser (reference src/pose_graph.cpp:82-305, include/pose_graph.h:53-62): a graph of SE3 vertices and SE3 edges with Huber kernels,
+ * Levenberg (g2o's OptimizationAlgorithmLevenberg) over a direct block-envelope L D L^T.  DESIGN.md s.12 is the contract; include/ssm/pgo_core.h holds the
+ * arithmetic, ONE function template that the host function runs with one thread and the device path with one 1024-thread block per graph, so device ==
+ * host bit for bit.  Poses and measurements are 4 x 4 column-major isometries; an information matrix is its 21 upper-triangle entries row by row (the
+ * order of a g2o file), NULL = 100 I (pose_graph.cpp's edges).  Vertices are named by caller ids; edges are numbered in the order they were added. */
+enum { SSM_PGO_MAX_ITERS = 32, SSM_PGO_MAX_TRIALS = 10, SSM_PGO_PHASES = 5 };
+typedef struct {
+    int32_t iterations;                      /* iterations run */
+    int32_t active_vertices, active_edges;   /* free vertices with an active edge; edges with a free vertex */
+    int32_t solve_failures;                  /* trials whose factorisation met a pivot that is not > 0 */
+    int64_t envelope_scalars;                /* doubles of the block envelope */
+    double  lambda;                          /* after the last iteration */
+    int32_t trials[SSM_PGO_MAX_ITERS];       /* per iteration */
+    uint32_t accepted[SSM_PGO_MAX_ITERS];    /* bit t: trial t of the iteration was accepted */
+    double  chi2_before[SSM_PGO_MAX_ITERS], chi2_after[SSM_PGO_MAX_ITERS];     /* the robustified active chi2 */
+    double  gain[SSM_PGO_MAX_ITERS][SSM_PGO_MAX_TRIALS];
+    int64_t clocks[SSM_PGO_PHASES];          /* device path: 100 MHz ticks per phase (ssm_pgo_times converts) */
+} ssm_pgo_report;
+typedef struct ssm_pgo ssm_pgo;
+/* ctx may be NULL: an object for ssm_pgo_optimize_host and the host inspection calls only, which needs no GPU; its errors are in ssm_last_error(NULL) */
+int  ssm_pgo_create(ssm_ctx* ctx, ssm_pgo** out);
+void ssm_pgo_destroy(ssm_pgo* g);
+int  ssm_pgo_clear(ssm_pgo* g);                                          /* no vertices, no edges; the memory stays */
+int  ssm_pgo_add_vertex(ssm_pgo* g, int id, const double T[16], int fixed);     /* a duplicate id: SSM_E_INVAL */
+/* an unknown id, from == to: SSM_E_INVAL.  Multi-edges are allowed */
+int  ssm_pgo_add_edge(ssm_pgo* g, int id_from, int id_to, const double Z[16], const double* info21, int robust);
+int  ssm_pgo_set_fixed(ssm_pgo* g, int id, int fixed);
+/* mode 0 (pose_graph.cpp:242-246): every vertex free but the first added; mode 1 (:268-276): only the last five added free -- with fewer than six vertices
+ * none, the reference's unsigned `i > size() - 6` */
+int  ssm_pgo_set_mode(ssm_pgo* g, int local);
+int  ssm_pgo_set_pose(ssm_pgo* g, int id, const double T[16]);
+int  ssm_pgo_get_poses(const ssm_pgo* g, int32_t* ids, double* T, int cap, int* n_out);      /* insertion order; ids / T may be NULL */
+int  ssm_pgo_size(const ssm_pgo* g, int* vertices, int* edges);
+int  ssm_pgo_edge_chi2(const ssm_pgo* g, int edge, double* chi2);         /* the plain e^T Om e at the current estimate: what mainLoop accumulates */
+/* the envelope (H and the factor, 16 bytes per scalar) may take at most this many bytes: beyond it ssm_pgo_optimize* return SSM_E_CAPACITY and leave the graph
+ * as it was.  Default: a quarter of the device memory free at ssm_pgo_create, 1 GiB for a host-only object */
+int  ssm_pgo_set_envelope_cap(ssm_pgo* g, size_t bytes);
+/* optimize(iterations), 0 <= iterations <= SSM_PGO_MAX_ITERS: one launch, one wait (poses and report).  report may be NULL */
+int  ssm_pgo_optimize(ssm_pgo* g, int iterations, ssm_pgo_report* report);
+int  ssm_pgo_optimize_host(ssm_pgo* g, int iterations, ssm_pgo_report* report);           /* the same bits on the CPU; needs no GPU */
+/* n graphs of ONE context as n blocks of one launch; reports: n entries or NULL */
+int  ssm_pgo_optimize_many(ssm_pgo** graphs, int n, int iterations, ssm_pgo_report* reports);
+/* the active set of the current graph: free vertices with an active edge, edges with a free vertex.  Plans only: the last report and times stay */
+int  ssm_pgo_active(ssm_pgo* g, int* vertices, int* edges);
+/* inspection, for the tests; device != 0: the device path.  Linearises the active edges at the current estimate: e / Ji / Jj: active edges x 6 / 36 / 36
+ * (row-major; ascending edge number), w: their Huber weights, H: the assembled envelope (ssm_pgo_envelope's layout), b: 6 x active vertices.  Any may be NULL */
+int  ssm_pgo_linearize(ssm_pgo* g, int device, double* e, double* Ji, double* Jj, double* w, double* H, double* b);
+/* the envelope of the current active set: first[r] = the first block column of block row r (nr_out rows; row r holds the 6 x 6 (r - first[r] + 1) scalars of
+ * its block columns first[r] .. r, scalar row by scalar row, rows in order; entries right of the diagonal are not read) */
+int  ssm_pgo_envelope(ssm_pgo* g, int32_t* first, int cap, int* nr_out, int64_t* scalars_out);
+/* solves (H + lambda I) x = b for a caller-given envelope: nr block rows with first[] (first[r] <= r).  *ok = 0: a pivot was not > 0 (x = 0) */
+int  ssm_pgo_factor_solve(ssm_pgo* g, int device, int nr, const int32_t* first, const double* H, const double* b, double lambda, double* x, int* ok);
+/* milliseconds of the last device call per phase: linearise, assemble, factor + solves, update + chi2, decide */
+int  ssm_pgo_times(const ssm_pgo* g, double ms[SSM_PGO_PHASES]);
+/* for the tests: one Levenberg decision by pnp_core.h's lm_update (scaled == 0) or by pgo_core.h's lm_update_scaled fed the same six-term sum (scaled != 0).
+ * state: (lambda, nu) in / out; out: (gain, accepted) */
+int  ssm_debug_pgo_lm_update(int scaled, double state[2], double chi, double chi_new, int solved, const double x[6], const double b[6], double out[2]);
+/* VERTEX_SE3:QUAT id x y z qx qy qz qw / FIX id / EDGE_SE3:QUAT from to x y z qx qy qz qw + the 21 information entries, %.17g: what PoseGraph::save writes.
+ * Any other tag: SSM_E_INVAL with the line number in ssm_last_error.  Loaded edges carry the robust flag `robust` */
+int  ssm_pgo_save_g2o(const ssm_pgo* g, const char* path);
+int  ssm_pgo_load_g2o(ssm_pgo* g, const char* path, int robust);
+
 /* ---- device-resident batched stereo path (BASELINE.json configs[3]): n frames of a rectified stereo sequence, all DEVICE pointers.
  * The reference walks the KITTI sequence one frame at a time: FrameReader::next() computes the depth of the current pair with SGBM
  * (src/rgbdframe.cpp:64-116, src/stereo.cpp:11-30), Tracker::estimateVO builds a QuadFeatureMatch on (current left, current right, previous left,

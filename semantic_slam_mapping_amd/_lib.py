@@ -161,6 +161,29 @@ SYMBOLS = {
     "ssm_debug_uvd_stage": (_I, [_P, _I, _I, _P, _SZ, C.POINTER(_SZ)]),
     "ssm_debug_uvd_record": (_I, [_P, _I]),
     "ssm_debug_uvd_times": (_I, [_P, C.POINTER(C.c_double * 3)]),
+    "ssm_pgo_create": (_I, [_P, C.POINTER(_P)]),
+    "ssm_pgo_destroy": (None, [_P]),
+    "ssm_pgo_clear": (_I, [_P]),
+    "ssm_pgo_add_vertex": (_I, [_P, _I, _P, _I]),
+    "ssm_pgo_add_edge": (_I, [_P, _I, _I, _P, _P, _I]),
+    "ssm_pgo_set_fixed": (_I, [_P, _I, _I]),
+    "ssm_pgo_set_mode": (_I, [_P, _I]),
+    "ssm_pgo_set_pose": (_I, [_P, _I, _P]),
+    "ssm_pgo_get_poses": (_I, [_P, _P, _P, _I, C.POINTER(_I)]),
+    "ssm_pgo_size": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "ssm_pgo_edge_chi2": (_I, [_P, _I, C.POINTER(_D)]),
+    "ssm_pgo_set_envelope_cap": (_I, [_P, _SZ]),
+    "ssm_pgo_optimize": (_I, [_P, _I, _P]),
+    "ssm_pgo_optimize_host": (_I, [_P, _I, _P]),
+    "ssm_pgo_optimize_many": (_I, [C.POINTER(_P), _I, _I, _P]),
+    "ssm_pgo_active": (_I, [_P, C.POINTER(_I), C.POINTER(_I)]),
+    "ssm_debug_pgo_lm_update": (_I, [_I, _P, _D, _D, _I, _P, _P, _P]),
+    "ssm_pgo_linearize": (_I, [_P, _I, _P, _P, _P, _P, _P, _P]),
+    "ssm_pgo_envelope": (_I, [_P, _P, _I, C.POINTER(_I), C.POINTER(C.c_int64)]),
+    "ssm_pgo_factor_solve": (_I, [_P, _I, _I, _P, _P, _P, _D, _P, C.POINTER(_I)]),
+    "ssm_pgo_times": (_I, [_P, C.POINTER(C.c_double * 5)]),
+    "ssm_pgo_save_g2o": (_I, [_P, C.c_char_p]),
+    "ssm_pgo_load_g2o": (_I, [_P, C.c_char_p, _I]),
     "ssm_segnet_num_layers": (_I, []),
     "ssm_segnet_layer_shape": (_I, [_I, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "ssm_segnet_set_layer": (_I, [_P, _I, _P, _P, _P]),

@@ -910,3 +910,161 @@ class Context:
             "npoints": self.d2h(out.npoints, n, np.int32),
         }
         return res
+
+
+PGO_MAX_ITERS, PGO_MAX_TRIALS, PGO_PHASES = 32, 10, 5
+PGO_REPORT_DTYPE = np.dtype([("iterations", "i4"), ("active_vertices", "i4"), ("active_edges", "i4"), ("solve_failures", "i4"), ("envelope_scalars", "i8"), ("lambda", "f8"),
+                             ("trials", "i4", (PGO_MAX_ITERS,)), ("accepted", "u4", (PGO_MAX_ITERS,)), ("chi2_before", "f8", (PGO_MAX_ITERS,)), ("chi2_after", "f8", (PGO_MAX_ITERS,)),
+                             ("gain", "f8", (PGO_MAX_ITERS, PGO_MAX_TRIALS)), ("clocks", "i8", (PGO_PHASES,))])
+assert PGO_REPORT_DTYPE.itemsize == 32 + 4 * 32 * 2 + 8 * 32 * 2 + 8 * 320 + 40
+
+
+class PoseGraphOptimizer:
+    """ssm_pgo: PoseGraph's optimiser (src/pose_graph.cpp:82-305) -- SE3 vertices, SE3 edges with Huber kernels, Levenberg over a block-envelope L D L^T
+    (DESIGN.md s.12).  PoseGraphOptimizer(ctx) has the device path (optimize, one 1024-thread block per graph); PoseGraphOptimizer(None) is a host-only
+    object whose optimize_host needs no GPU.  Both give the same bits.  Poses are 4 x 4 matrices in the usual row-major numpy form."""
+
+    def __init__(self, ctx=None, envelope_cap=None):
+        self.ctx = ctx; self.lib = ctx.lib if ctx is not None else _lib.load()
+        h = C.c_void_p()
+        rc = self.lib.ssm_pgo_create(ctx.h if ctx is not None else None, C.byref(h))
+        if rc != 0:
+            raise SsmError(rc, (self.lib.ssm_last_error(ctx.h if ctx is not None else None) or b"").decode())
+        self.h = h
+        if envelope_cap is not None:
+            self.set_envelope_cap(envelope_cap)
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SsmError(rc, (self.lib.ssm_last_error(self.ctx.h if self.ctx is not None else None) or b"").decode())
+
+    @staticmethod
+    def _cm(T):
+        """a 4 x 4 matrix as the ABI's 16 column-major doubles"""
+        T = np.asarray(T, np.float64)
+        assert T.shape == (4, 4)
+        return np.ascontiguousarray(T.T).reshape(16)
+
+    def clear(self):
+        self._chk(self.lib.ssm_pgo_clear(self.h))
+
+    def add_vertex(self, vid, T, fixed=False):
+        self._chk(self.lib.ssm_pgo_add_vertex(self.h, int(vid), _ptr(self._cm(T)), int(bool(fixed))))
+
+    def add_edge(self, id_from, id_to, Z, info=None, robust=True):
+        """info: None (100 I), a 6 x 6 symmetric matrix, or the 21 upper-triangle entries row by row"""
+        i21 = None
+        if info is not None:
+            info = np.asarray(info, np.float64)
+            i21 = np.ascontiguousarray(info[np.triu_indices(6)] if info.shape == (6, 6) else info.reshape(21))
+        self._chk(self.lib.ssm_pgo_add_edge(self.h, int(id_from), int(id_to), _ptr(self._cm(Z)), _ptr(i21) if i21 is not None else None, int(bool(robust))))
+
+    def set_fixed(self, vid, fixed=True):
+        self._chk(self.lib.ssm_pgo_set_fixed(self.h, int(vid), int(bool(fixed))))
+
+    def set_mode(self, local):
+        """False: every vertex free but the first; True: only the last five free (fewer than six vertices: none)"""
+        self._chk(self.lib.ssm_pgo_set_mode(self.h, int(bool(local))))
+
+    def set_pose(self, vid, T):
+        self._chk(self.lib.ssm_pgo_set_pose(self.h, int(vid), _ptr(self._cm(T))))
+
+    def set_envelope_cap(self, nbytes):
+        self._chk(self.lib.ssm_pgo_set_envelope_cap(self.h, int(nbytes)))
+
+    def size(self):
+        v, e = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.ssm_pgo_size(self.h, C.byref(v), C.byref(e)))
+        return v.value, e.value
+
+    def poses(self):
+        """(ids, n x 4 x 4 poses) in insertion order"""
+        n = self.size()[0]
+        ids = np.zeros(max(n, 1), np.int32); T = np.zeros((max(n, 1), 16))
+        k = C.c_int(0)
+        self._chk(self.lib.ssm_pgo_get_poses(self.h, _ptr(ids), _ptr(T), n, C.byref(k)))
+        return ids[:n], np.ascontiguousarray(T[:n].reshape(n, 4, 4).transpose(0, 2, 1))
+
+    def edge_chi2(self, edge):
+        v = C.c_double(0)
+        self._chk(self.lib.ssm_pgo_edge_chi2(self.h, int(edge), C.byref(v)))
+        return v.value
+
+    def _opt(self, fn, iterations):
+        rep = np.zeros(1, PGO_REPORT_DTYPE)
+        self._chk(fn(self.h, int(iterations), _ptr(rep)))
+        return rep[0]
+
+    def optimize(self, iterations=10):
+        """on the device -> the report (PGO_REPORT_DTYPE)"""
+        return self._opt(self.lib.ssm_pgo_optimize, iterations)
+
+    def optimize_host(self, iterations=10):
+        """the same on the CPU (no GPU needed): the same bits"""
+        return self._opt(self.lib.ssm_pgo_optimize_host, iterations)
+
+    @staticmethod
+    def optimize_many(graphs, iterations=10):
+        """the graphs (of one context) as the blocks of one launch -> their reports"""
+        g0 = graphs[0]
+        hs = (C.c_void_p * len(graphs))(*[g.h for g in graphs])
+        rep = np.zeros(len(graphs), PGO_REPORT_DTYPE)
+        g0._chk(g0.lib.ssm_pgo_optimize_many(hs, len(graphs), int(iterations), _ptr(rep)))
+        return rep
+
+    def envelope(self):
+        """(first block column of every block row, scalars) of the current active set"""
+        n, tot = C.c_int(0), C.c_int64(0)
+        self._chk(self.lib.ssm_pgo_envelope(self.h, None, 0, C.byref(n), C.byref(tot)))
+        first = np.zeros(max(n.value, 1), np.int32)
+        self._chk(self.lib.ssm_pgo_envelope(self.h, _ptr(first), n.value, C.byref(n), C.byref(tot)))
+        return first[:n.value], tot.value
+
+    def linearize(self, device=False):
+        """dict(e, Ji, Jj, w of the active edges; H: the assembled envelope; b; first) at the current estimate"""
+        first, tot = self.envelope()
+        rep_v, rep_e = len(first), self.active()[1]
+        out = dict(e=np.zeros((rep_e, 6)), Ji=np.zeros((rep_e, 6, 6)), Jj=np.zeros((rep_e, 6, 6)), w=np.zeros(rep_e), H=np.zeros(max(tot, 1)), b=np.zeros(6 * rep_v + 1))
+        self._chk(self.lib.ssm_pgo_linearize(self.h, int(bool(device)), *[_ptr(out[k]) for k in ("e", "Ji", "Jj", "w", "H", "b")]))
+        out["H"] = out["H"][:tot]; out["b"] = out["b"][:6 * rep_v]; out["first"] = first
+        return out
+
+    def active(self):
+        """(active free vertices, active edges) of the current graph; the last report and times stay"""
+        v, e = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.ssm_pgo_active(self.h, C.byref(v), C.byref(e)))
+        return v.value, e.value
+
+    def factor_solve(self, first, H, b, lam, device=False):
+        """(H + lam I) x = b on a caller-given envelope -> (x, ok)"""
+        first = np.ascontiguousarray(first, np.int32); H = np.ascontiguousarray(H, np.float64); b = np.ascontiguousarray(b, np.float64)
+        nr = len(first)
+        assert len(b) == 6 * nr and len(H) == 36 * int(np.sum(np.arange(nr) - first + 1))
+        x = np.zeros(6 * nr); ok = C.c_int(0)
+        self._chk(self.lib.ssm_pgo_factor_solve(self.h, int(bool(device)), nr, _ptr(first), _ptr(H), _ptr(b), float(lam), _ptr(x), C.byref(ok)))
+        return x, bool(ok.value)
+
+    def times(self):
+        """ms of the last device call per phase: linearise, assemble, factor + solves, update + chi2, decide"""
+        t = (C.c_double * 5)()
+        self._chk(self.lib.ssm_pgo_times(self.h, C.byref(t)))
+        return tuple(float(x) for x in t)
+
+    def save_g2o(self, path):
+        self._chk(self.lib.ssm_pgo_save_g2o(self.h, str(path).encode()))
+
+    def load_g2o(self, path, robust=True):
+        self._chk(self.lib.ssm_pgo_load_g2o(self.h, str(path).encode(), int(bool(robust))))
+
+    def close(self):
+        """before the context's close(), like a Looper"""
+        if getattr(self, "h", None):
+            if self.ctx is None or self.ctx.h:
+                self.lib.ssm_pgo_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

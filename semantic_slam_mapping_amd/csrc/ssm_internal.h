@@ -259,6 +259,11 @@ hipError_t k_uvd_classify(const uint8_t* left, const int16_t* disp, int n, int w
 hipError_t k_uvd_probe(const uint8_t* roi, const int16_t* disp, int n, int w, int h, const int32_t* coords, const int32_t* nmatch, int cap, int32_t* probes, hipStream_t s);
 hipError_t k_uvd_segment(const int16_t* disp, const uint8_t* roi, const uint8_t* uni, int n, int w, int h, const ssm_uvdc::FrameK* K, uint8_t* moving, int32_t* counts, hipStream_t s);
 
+// pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);
+// op 1: linearise + assemble; op 2: factor and solve the view's envelope with `lambda`
+namespace ssm_pgc { struct View; }
+hipError_t k_pgo(const ssm_pgc::View* views, int n, int iterations, int op, double lambda, hipStream_t s);
+
 // for the translation units that only use the public ABI (ssm_track.hip): the configuration a context was created with
 void ssm_internal_get_config(const ssm_ctx* c, ssm_config* out);
 int ssm_internal_get_device(const ssm_ctx* c);      // the HIP device the context lives on: raw HIP calls of another translation unit select it first

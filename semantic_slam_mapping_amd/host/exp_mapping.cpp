@@ -93,6 +93,14 @@ int main(int argc, char** argv)
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--batched") batched = true;
     bool loops = parameterReader.getData<int>("looper", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--loops") loops = true;
+    // --optimize (or pose_graph_optimize=1): PoseGraph keeps the graph and PoseGraph::step() runs SYNCHRONOUSLY -- after every accepted key-frame, or, with
+    // pose_graph_step_frames=K > 0, after every K-th frame and at the end (the boundaries of a --batched run with tracker_chunk=K, which steps once per chunk).
+    // It implies --loops when a vocabulary is configured; the candidates then come from PoseGraph's own Looper.  The summary line gets
+    // `graph_vertices V graph_edges E graph_opts K kf_pose_fnv H` and traj.g2o is written next to map_output.  Off by default: nothing of this runs.
+    bool optimize = parameterReader.getData<int>("pose_graph_optimize", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--optimize") optimize = true;
+    if (optimize) { parameterReader.set("pose_graph_optimize", "1"); if (!parameterReader.getData<string>("looper_vocab_file", string("")).empty()) loops = true; }
+    const int step_frames = parameterReader.getData<int>("pose_graph_step_frames", 0);
     bool moving = parameterReader.getData<int>("uv_disparity", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--moving") moving = true;
     if (moving) {
@@ -166,6 +174,10 @@ int main(int argc, char** argv)
         Tracker::Ptr tracker(new Tracker(parameterReader, voparam));
         const FrameReader::DATASET type = dataset_type(parameterReader);
         const bool batched_stereo = batched && parameterReader.getData<string>("tracker_mode", string("rgbd")) == "stereo";
+        if (optimize && batched_stereo) {                  // solvePnPLazy needs ORB features and RGB-D key-frames; the bulk stereo tracker has neither
+            cerr << "exp_mapping: --optimize is not available with the bulk stereo tracker (ignored)" << endl;
+            optimize = false; parameterReader.set("pose_graph_optimize", "0");
+        }
         if (batched_stereo) parameterReader.set("kitti_reader_depth", "0");     // the bulk stereo tracker computes the depth images, a chunk of frames per launch
         FrameReader frameReader(parameterReader, type);
         PoseGraph poseGraph(parameterReader, tracker);
@@ -215,7 +227,8 @@ int main(int argc, char** argv)
                     if (counted) timed++;
                     nframes++;
                 }
-                if (loops && !picked.empty()) {
+                if (optimize) { if (!done.empty()) poseGraph.step(); }          // once per chunk; its Looper supplies the candidates
+                else if (loops && !picked.empty()) {
                     if (!bl) bl.reset(new BatchLooper(parameterReader, bt->device()));
                     for (const BatchLooper::Candidate& c : bl->addChunk(bt->last_out, done, picked)) loop_log.add(c.frame->id, c.loop->id, c.score);
                 }
@@ -262,7 +275,7 @@ int main(int argc, char** argv)
             t1 = now();
             cout << "batched stereo tracker: chunk " << (bs ? bs->chunk() : 0) << " lost " << lost << endl;
         } else {
-        unique_ptr<Looper> looper; if (loops) looper.reset(new Looper(parameterReader));
+        unique_ptr<Looper> looper; if (loops && !optimize) looper.reset(new Looper(parameterReader));
         while (RGBDFrame::Ptr frame = read_next()) {
             if (nframes == skip) { t_timed0 = now(); tracker->timing = Tracker::Timing(); }
             if (seq_len > 0 && nframes > 0 && nframes % seq_len == 0) tracker->reset();
@@ -273,17 +286,21 @@ int main(int argc, char** argv)
             if (use_gt_pose) frame->setTransform(gt);           // synthetic stream: poses are given, the tracker only produces features/matches
             traj.add(frame);
             if (moving && !frame->moving_mask.empty()) moving_log.add(frame->moving_mask, tracker->pitch1);
-            if (poseGraph.tryInsertKeyFrame(frame) && looper) {
+            const bool inserted = poseGraph.tryInsertKeyFrame(frame);
+            if (inserted && looper) {
                 looper->add(frame);
                 looper->getPossibleLoops(frame);
                 for (int i : looper->last_indices) loop_log.add(frame->id, looper->frameAt(i)->id, looper->last_scores[i]);
             }
+            if (optimize && (step_frames > 0 ? (nframes + 1) % step_frames == 0 : inserted)) poseGraph.step();
             if (nframes >= skip) { track_s += sec(a, b); kf_s += sec(b, now()); timed++; }
             if (tracker->getState() == Tracker::LOST) cout << "tracker is lost" << endl;
             nframes++;
             if (frame_period_ms > 0) this_thread::sleep_for(chrono::milliseconds(frame_period_ms));      // a camera's frame period (measurements of the viewer thread under a paced stream)
         }
+        if (optimize && step_frames > 0) poseGraph.step();                 // the frames after the last boundary (a --batched run's final flush)
         t1 = now(); }
+        if (optimize) for (const PoseGraph::LoopCandidate& c : poseGraph.loopCandidates) loop_log.add(c.frame, c.loop, c.score);
         const double s = sec(t0, t1), s_timed = sec(t_timed0, t1);
         mapper.SaveMap();
         poseGraph.shutdown();
@@ -318,6 +335,15 @@ int main(int argc, char** argv)
             cout << " map_voxels " << nvox << " map_fnv " << hex << h << dec;
         }
         if (loops) cout << " loop_candidates " << loop_log.n << " loop_fnv " << hex << loop_log.h << dec;
+        if (optimize) {
+            uint64_t h = 0xCBF29CE484222325ull;                           // FNV-1a over the key-frames' final poses, in key-frame order
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) { const Eigen::Isometry3d T = kf->getTransform(); const unsigned char* b = (const unsigned char*)T.data(); for (int k = 0; k < 128; k++) { h ^= b[k]; h *= 0x100000001B3ull; } }
+            cout << " graph_vertices " << poseGraph.graphVertices() << " graph_edges " << poseGraph.graphEdges() << " graph_opts " << poseGraph.globalOpts + poseGraph.localOpts
+                 << " kf_pose_fnv " << hex << h << dec;
+            const string mo = parameterReader.getData<string>("map_output", string(""));
+            const size_t slash = mo.find_last_of('/');
+            poseGraph.save((slash == string::npos ? string("") : mo.substr(0, slash + 1)) + "traj.g2o");
+        }
         cout << endl;
     } catch (const exception& e) { cerr << RED << "exp_mapping: " << e.what() << RESET << endl; return 2; }
     return 0;

@@ -22,6 +22,11 @@ static int vocab_fail(const std::string& msg) { g_vocab_err = msg; return SSM_E_
 #include <climits>
 #include <cmath>
 #include "../csrc/ssm_uvd_host.inc"
+// and the pose-graph optimiser: PoseGraph without a context uses ssm_pgo_optimize_host, the library's own host function (csrc/ssm_pgo.hip over
+// include/ssm/pgo_core.h), built here without its device half
+#define SSM_PGO_HOST_ONLY
+static thread_local std::string g_create_err;
+#include "../csrc/ssm_pgo.hip"
 struct ssm_uvd { ssm_uvd_params p; UvdKalman kf1, kf2; double rate[ssm_uvdc::MAX_BINS]; UvdFrame frame; };
 extern "C" {
 void ssm_uvd_params_default(ssm_uvd_params* p) { if (p) uvd_set_defaults(p); }
@@ -45,6 +50,9 @@ int ssm_debug_uvd_times(ssm_uvd*, double*) { return SSM_E_NODEVICE; }
 int ssm_vo_estimate(ssm_ctx*, const ssm_pmatch*, int, const ssm_vo_params*, const int32_t*, int, double*, int32_t*, int, int*, int*) { return SSM_E_NODEVICE; }      // (VisualOdometryStereo has to link: test_uvd fills its lists by hand)
 int ssm_uvd_process(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
 int ssm_uvd_process_dev(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, const int32_t*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
+// PoseGraph::step reaches the extractor and the matcher through solvePnPLazy; test_posegraph --graph-only never gets there (no neighbours, no looper): they only have to link
+int ssm_orb_extract(ssm_ctx*, const uint8_t*, int, int, int, int, const uint16_t*, ssm_keypoint*, uint8_t*, float*, int, int*) { return SSM_E_NODEVICE; }
+int ssm_match(ssm_ctx*, const uint8_t*, int, const uint8_t*, int, double, ssm_dmatch*, int, int*) { return SSM_E_NODEVICE; }
 int ssm_looper_create(ssm_ctx*, const ssm_vocab*, ssm_looper**) { return SSM_E_NODEVICE; }
 void ssm_looper_destroy(ssm_looper*) {}
 int ssm_looper_size(const ssm_looper*) { return 0; }
