@@ -575,6 +575,10 @@ int ssm_debug_pyramid_plan(const ssm_config* cfg, int bands, int32_t* items, int
  * op bit 0 = medianBlur 3x3 (replicate border), bit 1 = filterSpeckles (4-neighbours, both != new_val, |a - b| <= max_diff; components of at most
  * max_size pixels become new_val) on the median's output, or on the input without bit 0.  For exact tests of the kernels on constructed maps */
 int ssm_debug_sgbm_post(ssm_ctx* ctx, const int16_t* disp, int w, int h, int n, int op, int new_val, int max_size, int max_diff, int16_t* out);
+/* one level (0 .. 3) of the LK pyramid that the last ssm_lk_track built and its Scharr derivatives, for exact tests of the pyramid and derivative kernels on
+ * every pixel: side 0 = the previous image, 1 = the next; img receives *w x *h bytes, der *w x *h (dx, dy) int16 pairs, rows packed (either may be NULL: only
+ * the size).  SSM_E_INVAL when the last stereo call on the context was not an ssm_lk_track with n > 0 */
+int ssm_debug_quad_pyramid(ssm_ctx* ctx, int side, int level, uint8_t* img, int16_t* der, int* w, int* h);
 /* what the library itself holds at this moment, process-wide (every context with its lanes, every tracker): live buffers, their device bytes and their
  * page-locked host bytes, each as asked for.  Memory handed to the caller (ssm_dev_alloc, ssm_host_alloc) is not counted.  Any pointer may be NULL.  For
  * tests of ownership: exact, unlike the device's free memory, which moves with other processes */

@@ -195,6 +195,7 @@ SYMBOLS = {
     "ssm_debug_fast_plan": (_I, [C.POINTER(Config), _P, _I, C.POINTER(_I), _P]),
     "ssm_debug_pyramid_plan": (_I, [C.POINTER(Config), _I, _P, _I, C.POINTER(_I), _P, _P]),
     "ssm_debug_sgbm_post": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "ssm_debug_quad_pyramid": (_I, [_P, _I, _I, _P, _P, C.POINTER(_I), C.POINTER(_I)]),
     "ssm_debug_live_allocations": (None, [C.POINTER(_I), C.POINTER(_SZ), C.POINTER(_SZ)]),
     "ssm_debug_live_handles": (None, [C.POINTER(_I), C.POINTER(_I)]),
     "ssm_set_profiling": (_I, [_P, _I]),

@@ -107,6 +107,14 @@ def _ptr(a):
     return a.ctypes.data if a is not None else None
 
 
+def _rows(a):
+    """an 8-bit image whose pixels are adjacent inside a row: a row-strided 2-D view passes as it is (the ABI takes the row stride), anything else is packed"""
+    a = np.asarray(a)
+    if a.dtype != np.uint8 or a.ndim != 2 or a.shape[1] == 0 or a.strides[1] != 1 or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a, np.uint8)
+    return a
+
+
 TRACK_INFO_DTYPE = np.dtype([("state", "i4"), ("tracked", "i4"), ("n_matches", "i4"), ("n_inliers", "i4")])
 
 
@@ -599,11 +607,23 @@ class Context:
         return pts[:n.value]
 
     def lk_track(self, prev, nxt, pts, max_count=200, epsilon=0.01, min_eig=1e-6):
-        prev = np.ascontiguousarray(prev, np.uint8); nxt = np.ascontiguousarray(nxt, np.uint8); h, w = prev.shape
+        prev, nxt = _rows(prev), _rows(nxt); h, w = prev.shape
+        if nxt.shape != prev.shape:
+            raise ValueError("lk_track: the two images differ in size")
+        if nxt.strides[0] != prev.strides[0]:                       # (the ABI takes one row stride for both images)
+            prev = np.ascontiguousarray(prev); nxt = np.ascontiguousarray(nxt)
         pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
         out = np.zeros_like(pts); st = np.zeros(len(pts), np.uint8); err = np.zeros(len(pts), np.float32)
-        self._chk(self.lib.ssm_lk_track(self.h, _ptr(prev), _ptr(nxt), w, h, w, _ptr(pts), len(pts), _ptr(out), _ptr(st), _ptr(err), max_count, epsilon, min_eig))
+        self._chk(self.lib.ssm_lk_track(self.h, _ptr(prev), _ptr(nxt), w, h, prev.strides[0], _ptr(pts), len(pts), _ptr(out), _ptr(st), _ptr(err), max_count, epsilon, min_eig))
         return out, st, err
+
+    def debug_quad_pyramid(self, side, level):
+        """level 0 .. 3 of the LK pyramid of the last lk_track (side 0 = previous image, 1 = next) and its Scharr (dx, dy) pairs: (uint8 h x w, int16 h x w x 2)"""
+        w = C.c_int(0); h = C.c_int(0)
+        self._chk(self.lib.ssm_debug_quad_pyramid(self.h, side, level, None, None, C.byref(w), C.byref(h)))
+        img = np.zeros((h.value, w.value), np.uint8); der = np.zeros((h.value, w.value, 2), np.int16)
+        self._chk(self.lib.ssm_debug_quad_pyramid(self.h, side, level, _ptr(img), _ptr(der), C.byref(w), C.byref(h)))
+        return img, der
 
     def window_match(self, kp1, d1, kp2, d2, sw, sh, thr):
         kp1 = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2); kp2 = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)

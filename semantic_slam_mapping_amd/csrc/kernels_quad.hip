@@ -547,9 +547,11 @@ scharr_kernel(QuadBatch q, short2* __restrict__ der)
         uint4 out; __builtin_memcpy(&out, o, 16);
         *reinterpret_cast<uint4*>(der + sl + e) = out;      // (sl and e are multiples of 4 elements: 16-byte aligned)
     } else {
-        // (elements in the padding behind a level are computed like the one-element kernel did: rows past the level, values nobody reads)
+        // (elements in the padding behind a level belong to no row: they are written as zeros WITHOUT a load -- their centre row r1 would start at or behind the
+        // level's end, and for the last padding element of level 3 the tap r1[xk + 1] is the first element behind the slot, behind the allocation for the last slot)
         for (int k = 0; k < 4; k++) {
             const int ik = i + k, yk = ik / w, xk = ik - yk * w;
+            if (yk >= h) { der[sl + e + k] = make_short2(0, 0); continue; }
             const uint8_t *r0 = src + (size_t)refl101d(yk - 1, h) * w, *r1 = src + (size_t)yk * w, *r2 = src + (size_t)refl101d(yk + 1, h) * w;
             const int xm = refl101d(xk - 1, w), xp = refl101d(xk + 1, w);
             der[sl + e + k] = make_short2((short)(3 * (r0[xp] - r0[xm]) + 10 * (r1[xp] - r1[xm]) + 3 * (r2[xp] - r2[xm])),

@@ -147,6 +147,7 @@ struct StereoState {        // workspace of the stereo path (quad matcher, SGBM 
     DevBuf<ssm_pmatch> quad; DevBuf<int32_t> nquad; DevBuf<float> corners; DevBuf<int32_t> ncorners; DevBuf<int16_t> disp; DevBuf<uint16_t> depth;
     DevBuf<double> tr; DevBuf<int32_t> inliers, vo_result;
     bool have_prev = false;                  // slot 0 holds the last frame of the previous sequence call
+    bool lk_built = false;                   // slot 1 of both sides holds the pyramids and derivatives of the last ssm_lk_track (ssm_debug_quad_pyramid)
     DevBuf<uint8_t> in_stage;                // device staging of the per-pair host-pointer entry points
 };
 struct SegNetState {

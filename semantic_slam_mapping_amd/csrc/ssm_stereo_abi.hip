@@ -94,6 +94,7 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     if ((stages & SSM_STEREO_QUAD) && (w < 32 || h < 32)) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
     int r = stereo_init(c, w, h, maxc, true); if (r) return r;
     StereoState* q = c->stereo.get();
+    q->lk_built = false;                                          // (the sub-batch overwrites slot 1)
     if (stages & SSM_STEREO_DEPTH) { r = sgbm_check_params(c, &in->sgbm, w, h); if (r) return r; }
     r = stereo_ensure_seq(c, n > 0 ? n : 1); if (r) return r;
     if (stages & SSM_STEREO_VO) { r = stereo_ensure_vo(c, in->ransac_iters > 0 ? in->ransac_iters : 1); if (r) return r; }
@@ -227,6 +228,7 @@ extern "C" int ssm_gftt(ssm_ctx* c, const uint8_t* img, int w, int h, int stride
     if (max_corners > 32767) FAIL(c, SSM_E_INVAL, "max_corners must be <= 32767");
     int r = stereo_init(c, w, h, max_corners); if (r) return r;
     StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
+    q->lk_built = false;
     HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, img, stride, w, h, hipMemcpyHostToDevice, c->main.stream));        // side 0, slot 1, level 0
     HIPCHK(c, k_quad_gftt(qb, 1, max_corners, quality, min_distance, q->gw, q->pts, q->maxc, q->ncorner, c->main.stream));
     int n = 0;
@@ -249,6 +251,7 @@ extern "C" int ssm_lk_track(ssm_ctx* c, const uint8_t* prev, const uint8_t* next
     int r = stereo_init(c, w, h, n > 1000 ? n : 1000); if (r) return r;
     StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
     // previous image = (side 0, slot 1), next image = (side 1, slot 1)
+    q->lk_built = false;
     HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, prev, stride, w, h, hipMemcpyHostToDevice, c->main.stream));
     HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(qb.B1 + 1) * qb.slot_elems, w, next, stride, w, h, hipMemcpyHostToDevice, c->main.stream));
     HIPCHK(c, k_quad_pyramids(qb, 1, c->main.stream));
@@ -260,6 +263,24 @@ extern "C" int ssm_lk_track(ssm_ctx* c, const uint8_t* prev, const uint8_t* next
     if (err) HIPCHK(c, hipMemcpyAsync(err, q->err, (size_t)n * 4, hipMemcpyDeviceToHost, c->main.stream));
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->stereo->have_prev = false;
+    c->stereo->lk_built = true;
+    return SSM_OK;
+}
+// what the LK kernels of the last ssm_lk_track read (exact tests of pyrdown_kernel and scharr_kernel on every pixel): one level of slot 1 of `side`
+extern "C" int ssm_debug_quad_pyramid(ssm_ctx* c, int side, int level, uint8_t* img, int16_t* der, int* w, int* h)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    if (side < 0 || side > 1 || level < 0 || level > 3) FAIL(c, SSM_E_INVAL, "bad arguments (side 0..1, level 0..3)");
+    StereoState* q = c->stereo.get();
+    if (!q || !q->lk_built) FAIL(c, SSM_E_INVAL, "no LK state: ssm_lk_track (n > 0) must be the last stereo call on this context");
+    const QuadBatch& qb = q->qb;
+    const size_t at = (size_t)(side * qb.B1 + 1) * qb.slot_elems + qb.off[level], np = (size_t)qb.w[level] * qb.h[level];
+    if (w) *w = qb.w[level];
+    if (h) *h = qb.h[level];
+    if (img) HIPCHK(c, hipMemcpyAsync(img, q->pyr + at, np, hipMemcpyDeviceToHost, c->main.stream));
+    if (der) HIPCHK(c, hipMemcpyAsync(der, q->der + 2 * at, np * 4, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_window_match(ssm_ctx* c, const float* kp1, const uint8_t* d1, int n1, const float* kp2, const uint8_t* d2, int n2,

@@ -47,11 +47,11 @@ def test_lk_track_matches_oracle(ctx, oracle):
     edge = np.array([[0.5, 0.5], [1240.0, 375.0], [-30.0, 10.0], [600.0, 400.0], [3.0, 200.0]], np.float32)
     g, gs, ge = ctx.lk_track(lc, rc, edge)
     o, os_, oe = oracle.lk_track(lc, rc, edge)
-    assert np.array_equal(gs, os_) and g.tobytes() == o.tobytes()
+    assert np.array_equal(gs, os_) and g.tobytes() == o.tobytes() and ge.tobytes() == oe.tobytes()
     flat = np.full((376, 1241), 77, np.uint8)
-    g, gs, _ = ctx.lk_track(flat, flat, pts[:50])
-    o, os_, _ = oracle.lk_track(flat, flat, pts[:50])
-    assert (gs == 0).all() and np.array_equal(gs, os_) and g.tobytes() == o.tobytes()
+    g, gs, ge = ctx.lk_track(flat, flat, pts[:50])
+    o, os_, oe = oracle.lk_track(flat, flat, pts[:50])
+    assert (gs == 0).all() and np.array_equal(gs, os_) and g.tobytes() == o.tobytes() and ge.tobytes() == oe.tobytes()
 
 
 @pytest.mark.parametrize("w,h,disp,flow", [(1241, 376, 12, (3, 1)), (640, 480, 7, (-2, 0)), (1241, 376, 2, (1, 1))])
