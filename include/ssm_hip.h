@@ -92,7 +92,8 @@ void*       ssm_stream(ssm_ctx* ctx);                    /* hipStream_t of the c
 int ssm_orb_extract(ssm_ctx* ctx, const uint8_t* img, int w, int h, int stride, int channels, const uint16_t* depth,
                     ssm_keypoint* kps, uint8_t* desc, float* pos3d, int cap, int* n_out);
 
-/* ---- cv::BFMatcher(NORM_HAMMING)::knnMatch(q,t,knn,2) as called at src/orb.cpp:21.  idx/dist: nq x 2 */
+/* ---- cv::BFMatcher(NORM_HAMMING)::knnMatch(q,t,knn,2) as called at src/orb.cpp:21.  idx/dist: nq x 2.  Like ssm_match it completes the context's pending
+ * asynchronous calls (below) before it returns. */
 int ssm_hamming_knn2(ssm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx, int32_t* dist);
 /* ---- OrbFeature::match (src/orb.cpp:16-29): knn + ratio test, ascending queryIdx */
 int ssm_match(ssm_ctx* ctx, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio,

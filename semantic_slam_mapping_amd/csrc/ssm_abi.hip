@@ -108,11 +108,12 @@ void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, std::vector<
 }
 
 // ---------------------------------------------------------------- helpers
-int ensure_scratch(ssm_ctx* c, size_t bytes)
+int ensure_scratch(ssm_ctx* c, size_t bytes, DevBuf<uint8_t>* buf)
 {
-    if (bytes <= c->d_scratch.bytes()) return SSM_OK;
-    if (c->d_scratch) hipStreamSynchronize(c->main.stream);
-    return c->d_scratch.alloc(c, bytes);
+    DevBuf<uint8_t>& b = buf ? *buf : c->d_scratch;
+    if (bytes <= b.bytes()) return SSM_OK;
+    if (b) hipStreamSynchronize(c->main.stream);
+    return b.alloc(c, bytes);
 }
 int ensure_pinned(ssm_ctx* c, size_t bytes)
 {
@@ -120,12 +121,6 @@ int ensure_pinned(ssm_ctx* c, size_t bytes)
     if (c->h_pinned) hipStreamSynchronize(c->main.stream);
     if (c->h_pinned.alloc(c, bytes)) FAIL(c, SSM_E_HIP, "hipHostMalloc failed");
     return SSM_OK;
-}
-int ensure_scratch2(ssm_ctx* c, size_t bytes)
-{
-    if (bytes <= c->d_scratch2.bytes()) return SSM_OK;
-    if (c->d_scratch2) hipStreamSynchronize(c->main.stream);
-    return c->d_scratch2.alloc(c, bytes);
 }
 void prof_begin(ssm_ctx* c, hipStream_t s, const char* name)
 {
@@ -548,9 +543,11 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
 }
 
 // ---- the per-frame calls of the reference's unchanged loop (Tracker::trackRefFrame: detectFeatures, then match against every reference frame,
-// /root/reference/src/track.cpp:140-163).  Each call: inputs into the pinned ring (one memcpy per image), ONE host-to-device copy per image, the kernels, ONE
-// device-to-host copy of a result block that carries the count with the payload (capacity-sized: no round trip to learn the count first), and a finisher that
-// ssm_wait runs after the stream has drained.  The synchronous forms are the asynchronous ones + ssm_wait.
+// src/track.cpp:140-163 there).  Each call takes ONE block of the pinned ring (inputs staged, results landed) and ONE block of the device ring.  A small struct
+// (OrbBlock, MatchBlock) lays the blocks out once per call; the enqueue and the finisher both read its offsets.  Inputs go into the pinned block (one memcpy per
+// image / descriptor set), then ONE host-to-device copy per image / per matcher call, the kernels, ONE device-to-host copy of a result block that carries the
+// counts with the payload (capacity-sized: no round trip to learn a count first), and a finisher that ssm_wait runs after the stream has drained.  The
+// synchronous forms are the asynchronous ones + ssm_wait.
 int wait_pending(ssm_ctx* c)
 {
     if (c->pending.empty()) {
@@ -585,6 +582,34 @@ static int ring_take(ssm_ctx* c, size_t hbytes, size_t dbytes, uint8_t** hp, uin
     c->h_ring_off += hbytes; c->d_ring_off += dbytes;
     return SSM_OK;
 }
+// result block of one ORB extraction with room for ocap keypoints: [n, status, pad to 64 bytes][keypoints][descriptors][positions]
+struct OrbBlock {
+    size_t kps, desc, pos, bytes;                                       // offsets (n, status at 0) and the size of the block
+    explicit OrbBlock(int ocap) : kps(64), desc(kps + (size_t)ocap * sizeof(ssm_keypoint)), pos(desc + (size_t)ocap * 32), bytes(pos + (size_t)ocap * 12) {}
+};
+// the matrix-core matcher's rows (kernels_match.hip): capT = descriptors per row rounded up to the 32-row tile; expanded rows (each of eq, et); key rows, one per pair
+static int match_capT(int cap) { return (cap + 31) & ~31; }
+static size_t match_exp_bytes(size_t rows, int capT) { return rows * capT * SSM_MATCH_DESC_BYTES; }
+static size_t match_knn_bytes(size_t pairs, int capT) { return pairs * capT * 8; }
+// One matrix-core matcher call on rows <= 17 descriptor sets of up to capm descriptors: the query sets first, the train set last, nref = rows - 1 pairs.
+//   pinned block: [rows x capm descriptors][counts] .. [what comes back: the result block, or key rows]
+//   device block: [the same inputs + counts][eq][et][knn: nref key rows][result block: counts header + nref lists of capm matches], regions 256-aligned
+struct MatchBlock {
+    static constexpr size_t counts_bytes = 128, res_hdr = 256;         // 32 row counts; nref list lengths
+    int rows, nref, capm, capT;
+    size_t rowb, inb, expb, knnb, resb;                                 // sizes: one input row, inputs + counts, each of eq / et, knn, result block
+    size_t counts, h_res, hbytes;                                       // pinned block (inputs at 0; counts: the same offset in both blocks)
+    size_t d_eq, d_et, d_knn, d_res, dbytes;                            // device block (inputs at 0)
+    MatchBlock(int rows_, int capm_) : rows(rows_), nref(rows_ - 1), capm(capm_), capT(match_capT(capm_))
+    {
+        const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        rowb = (size_t)capm * 32; counts = rows * rowb; inb = counts + counts_bytes;
+        expb = match_exp_bytes(rows, capT); knnb = up(match_knn_bytes(nref, capT)); resb = list(nref);
+        h_res = (inb + 63) & ~(size_t)63; hbytes = h_res + (resb > knnb ? resb : knnb);
+        d_eq = up(inb); d_et = d_eq + expb; d_knn = d_et + expb; d_res = d_knn + knnb; dbytes = d_res + resb;
+    }
+    size_t list(int i) const { return res_hdr + (size_t)i * capm * sizeof(ssm_dmatch); }      // list i inside the result block
+};
 // in_place: the caller's buffers outlive the device work (the synchronous form) -- page-locked inputs are then used where they are
 static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int stride, int channels, const uint16_t* depth,
                                ssm_keypoint* kps, uint8_t* desc, float* pos3d, int cap, int* n_out, bool in_place = false)
@@ -595,10 +620,9 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
     if (stride < w * channels) FAIL(c, SSM_E_INVAL, "stride smaller than a row");
     const int ocap = c->g.cap;
     const size_t row = (size_t)w * channels, ib = row * h, db = depth ? (size_t)w * h * 2 : 0;
-    // result block: [n, status, pad][keypoints][descriptors][positions]
-    const size_t blk = 64 + (size_t)ocap * (sizeof(ssm_keypoint) + 32 + 12);
+    const OrbBlock B(ocap);
     uint8_t *hp, *dp;
-    int r = ring_take(c, ib + db + 64 + blk, blk, &hp, &dp); if (r) return r;
+    int r = ring_take(c, ib + db + 64 + B.bytes, B.bytes, &hp, &dp); if (r) return r;
     uint8_t* h_in = hp; uint8_t* h_out = hp + ((ib + db + 63) & ~(size_t)63);
     // round 6: the call is a latency chain (20 launches of 4 - 40 us for one frame + the staging copies).  The depth image is read by the LAST kernel only, and only at
     // the <= cap keypoints: it is staged into the pinned ring while gray .. quad-tree run (after their launches, before the describe launches) and the kernel reads it
@@ -612,9 +636,9 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
         HIPCHK(c, hipMemcpyAsync(c->d_in_img, h_in, ib, hipMemcpyHostToDevice, c->main.stream));
     }
     int32_t* dn = reinterpret_cast<int32_t*>(dp);
-    ssm_keypoint* dk = reinterpret_cast<ssm_keypoint*>(dp + 64);
-    uint8_t* dd = reinterpret_cast<uint8_t*>(dk + ocap);
-    float* dps = reinterpret_cast<float*>(dd + (size_t)ocap * 32);
+    ssm_keypoint* dk = reinterpret_cast<ssm_keypoint*>(dp + B.kps);
+    uint8_t* dd = dp + B.desc;
+    float* dps = reinterpret_cast<float*>(dp + B.pos);
     r = orb_detect(c, c->main.stream, c->chain[0].work, c->d_in_img, channels, 1); if (r) return r;
     const uint16_t* d_depth = nullptr;
     if (depth) {
@@ -625,16 +649,16 @@ static int orb_extract_enqueue(ssm_ctx* c, const uint8_t* img, int w, int h, int
     }
     r = orb_describe(c, c->main.stream, c->chain[0].work, d_depth, 1, dk, dd, dps, dn); if (r) return r;
     HIPCHK(c, hipMemcpyAsync(dn + 1, c->d_status, 4, hipMemcpyDeviceToDevice, c->main.stream));          // the ORB scratch-overflow word travels in the block's header
-    HIPCHK(c, hipMemcpyAsync(h_out, dp, blk, hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipMemcpyAsync(h_out, dp, B.bytes, hipMemcpyDeviceToHost, c->main.stream));
     c->pending.push_back([=](ssm_ctx* cc) -> int {
         int32_t hdr[2]; memcpy(hdr, h_out, 8);
         if (hdr[1]) { hipMemset(cc->d_status, 0, 4); FAIL(cc, SSM_E_CAPACITY, "ORB scratch capacity exceeded (status " + std::to_string(hdr[1]) + ")"); }
         const int n = hdr[0];
         *n_out = n;
         if (n > cap) FAIL(cc, SSM_E_CAPACITY, "keypoint buffer too small (need " + std::to_string(n) + ")");
-        memcpy(kps, h_out + 64, sizeof(ssm_keypoint) * (size_t)n);
-        memcpy(desc, h_out + 64 + (size_t)ocap * sizeof(ssm_keypoint), (size_t)n * 32);
-        if (pos3d) memcpy(pos3d, h_out + 64 + (size_t)ocap * (sizeof(ssm_keypoint) + 32), (size_t)n * 12);
+        memcpy(kps, h_out + B.kps, sizeof(ssm_keypoint) * (size_t)n);
+        memcpy(desc, h_out + B.desc, (size_t)n * 32);
+        if (pos3d) memcpy(pos3d, h_out + B.pos, (size_t)n * 12);
         return SSM_OK;
     });
     return SSM_OK;
@@ -662,73 +686,56 @@ extern "C" int ssm_wait(ssm_ctx* c)
 }
 
 // ---------------------------------------------------------------- matcher, host pointers
-static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, bool want_knn,
-                      int32_t* idx, int32_t* dist, ssm_dmatch* out, int cap, int* n_out)
+// The matrix-core matcher of the sequence path on a short "sequence" through the rings: rows 0 .. nref - 1 are the query sets (Tracker::trackRefFrame's reference
+// frames, oldest first), row nref is the train set of every pair (the current frame) -- one upload, one expansion, ONE matrix-core launch for all pairs, one
+// download.  The finisher delivers list i = OrbFeature::match(qs[i], t) into outs[i] / n_outs[i]; with idx / dist given (nref == 1) it delivers the two nearest of
+// every query instead, decoded from the pair's key row.  The arguments have been checked by the caller; capm = the largest row.
+static int match_mfma_enqueue(ssm_ctx* c, const uint8_t* const* qs, const int* nqs, int nref, const uint8_t* t, int nt, int capm, double ratio,
+                              ssm_dmatch* const* outs, const int* caps, int* n_outs, int32_t* idx = nullptr, int32_t* dist = nullptr)
 {
-    if (nq < 0 || nt < 0 || (nq && !q) || (nt && !t)) FAIL(c, SSM_E_INVAL, "bad descriptor arguments");
-    if (nt < 2) FAIL(c, SSM_E_TOO_FEW_TRAIN, "knnMatch(k=2) needs at least 2 train descriptors");
-    if (nt > 65535) FAIL(c, SSM_E_INVAL, "at most 65535 train descriptors per call");
-    if (nq == 0) { if (n_out) *n_out = 0; return SSM_OK; }
-    if (c->match_mfma && !want_knn) {
-        // the matrix-core matcher on a two-row "sequence" (row 0 = query set, row 1 = train set) through the rings: one upload, one result block
-        const int capm = nq > nt ? nq : nt, capT = (capm + 31) & ~31;
-        const size_t rowb = (size_t)capm * 32, expb = (size_t)2 * capT * SSM_MATCH_DESC_BYTES;
-        const size_t inb = 2 * rowb + 16, outb = 64 + (size_t)nq * sizeof(ssm_dmatch);
-        const size_t devb = ((inb + 255) & ~(size_t)255) + 2 * expb + (((size_t)capT * 8 + 255) & ~(size_t)255) + outb;
-        uint8_t *hp, *dp;
-        int r = ring_take(c, inb + 64 + outb, devb, &hp, &dp); if (r) return r;
-        uint8_t* h_out = hp + ((inb + 63) & ~(size_t)63);
-        memcpy(hp, q, (size_t)nq * 32); memcpy(hp + rowb, t, (size_t)nt * 32);
-        const int32_t hn[2] = {nq, nt}; memcpy(hp + 2 * rowb, hn, 8);
-        uint8_t* dd = dp; int32_t* dnk = reinterpret_cast<int32_t*>(dd + 2 * rowb);
-        uint8_t* eq = dp + ((inb + 255) & ~(size_t)255); uint8_t* et = eq + expb;
-        uint2* knn = reinterpret_cast<uint2*>(et + expb);
-        uint8_t* dout = reinterpret_cast<uint8_t*>(knn) + (((size_t)capT * 8 + 255) & ~(size_t)255);
-        int32_t* dn = reinterpret_cast<int32_t*>(dout); ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(dout + 64);
-        HIPCHK(c, hipMemcpyAsync(dd, hp, inb, hipMemcpyHostToDevice, c->main.stream));
-        HIPCHK(c, k_match_expand(dd, dnk, 0, 2, capm, capT, eq, et, c->main.stream));
-        HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, 1, 1, ratio, capm, capT, knn, dm, dn, c->main.stream));
-        HIPCHK(c, hipMemcpyAsync(h_out, dout, outb, hipMemcpyDeviceToHost, c->main.stream));
-        c->pending.push_back([=](ssm_ctx* cc) -> int {
-            int32_t n; memcpy(&n, h_out, 4);
-            *n_out = n;
-            if (n > cap) FAIL(cc, SSM_E_CAPACITY, "match buffer too small (need " + std::to_string(n) + ")");
-            memcpy(out, h_out + 64, sizeof(ssm_dmatch) * (size_t)n);
+    const MatchBlock L(nref + 1, capm);
+    uint8_t *hp, *dp;
+    int r = ring_take(c, L.hbytes, L.dbytes, &hp, &dp); if (r) return r;
+    int32_t hn[MatchBlock::counts_bytes / 4] = {0};
+    for (int i = 0; i < nref; i++) { if (nqs[i]) memcpy(hp + i * L.rowb, qs[i], (size_t)nqs[i] * 32); hn[i] = nqs[i]; }
+    memcpy(hp + nref * L.rowb, t, (size_t)nt * 32); hn[nref] = nt;
+    memcpy(hp + L.counts, hn, sizeof(hn));
+    const int32_t* dnk = reinterpret_cast<const int32_t*>(dp + L.counts);
+    uint8_t* h_res = hp + L.h_res;
+    HIPCHK(c, hipMemcpyAsync(dp, hp, L.inb, hipMemcpyHostToDevice, c->main.stream));
+    HIPCHK(c, k_match_expand(dp, dnk, 0, L.rows, capm, L.capT, dp + L.d_eq, dp + L.d_et, c->main.stream));
+    HIPCHK(c, k_match_seq_mfma(dp + L.d_eq, dp + L.d_et, dnk, 0, 1, nref, nref, ratio, capm, L.capT, dp + L.d_knn,
+                               reinterpret_cast<ssm_dmatch*>(dp + L.d_res + L.list(0)), reinterpret_cast<int32_t*>(dp + L.d_res), c->main.stream));
+    if (idx) {
+        const int nq = nqs[0];
+        HIPCHK(c, hipMemcpyAsync(h_res, dp + L.d_knn, (size_t)nq * 8, hipMemcpyDeviceToHost, c->main.stream));
+        c->pending.push_back([=](ssm_ctx*) -> int {
+            const uint2* hk = reinterpret_cast<const uint2*>(h_res);
+            for (int i = 0; i < nq; i++) { idx[2*i] = hk[i].x & 0xFFFF; idx[2*i+1] = hk[i].y & 0xFFFF; dist[2*i] = hk[i].x >> 16; dist[2*i+1] = hk[i].y >> 16; }
             return SSM_OK;
         });
         return SSM_OK;
     }
-    if (c->match_mfma) {
-        // the matrix-core matcher of the sequence path on a two-row "sequence": row 0 = the query set (reference frame), row 1 = the train set
-        const int capm = nq > nt ? nq : nt, capT = (capm + 31) & ~31;
-        const size_t rowb = (size_t)capm * 32, expb = (size_t)2 * capT * SSM_MATCH_DESC_BYTES;
-        const size_t need = 2 * rowb + 16 + 2 * expb + (size_t)capT * 8 + (size_t)nq * sizeof(ssm_dmatch) + 64;
-        int r = ensure_scratch(c, need); if (r) return r;
-        uint8_t* dd = c->d_scratch;
-        int32_t* dnk = reinterpret_cast<int32_t*>(dd + 2 * rowb);
-        uint8_t* eq = reinterpret_cast<uint8_t*>(dnk) + 16; uint8_t* et = eq + expb;
-        uint2* knn = reinterpret_cast<uint2*>(et + expb);
-        ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(knn + capT); int32_t* dn = reinterpret_cast<int32_t*>(dm + nq);
-        const int32_t hn[2] = {nq, nt};
-        HIPCHK(c, hipMemcpyAsync(dd, q, (size_t)nq * 32, hipMemcpyHostToDevice, c->main.stream));
-        HIPCHK(c, hipMemcpyAsync(dd + rowb, t, (size_t)nt * 32, hipMemcpyHostToDevice, c->main.stream));
-        HIPCHK(c, hipMemcpyAsync(dnk, hn, 8, hipMemcpyHostToDevice, c->main.stream));
-        HIPCHK(c, k_match_expand(dd, dnk, 0, 2, capm, capT, eq, et, c->main.stream));
-        HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, 1, 1, ratio, capm, capT, knn, dm, dn, c->main.stream));
-        int n = 0;
-        HIPCHK(c, hipMemcpyAsync(&n, dn, 4, hipMemcpyDeviceToHost, c->main.stream));
-        HIPCHK(c, hipStreamSynchronize(c->main.stream));
-        if (want_knn) {
-            std::vector<uint2> hk((size_t)nq);
-            HIPCHK(c, hipMemcpy(hk.data(), knn, (size_t)nq * 8, hipMemcpyDeviceToHost));
-            for (int i = 0; i < nq; i++) { idx[2*i] = hk[i].x & 0xFFFF; idx[2*i+1] = hk[i].y & 0xFFFF; dist[2*i] = hk[i].x >> 16; dist[2*i+1] = hk[i].y >> 16; }
-        } else {
-            *n_out = n;
-            if (n > cap) FAIL(c, SSM_E_CAPACITY, "match buffer too small (need " + std::to_string(n) + ")");
-            HIPCHK(c, hipMemcpy(out, dm, sizeof(ssm_dmatch) * n, hipMemcpyDeviceToHost));
+    // (the last list is copied up to its own capacity: with one pair, the query count)
+    HIPCHK(c, hipMemcpyAsync(h_res, dp + L.d_res, L.list(nref - 1) + (size_t)nqs[nref - 1] * sizeof(ssm_dmatch), hipMemcpyDeviceToHost, c->main.stream));
+    struct { ssm_dmatch* out[16]; int cap[16]; } to;
+    for (int i = 0; i < nref; i++) { to.out[i] = outs[i]; to.cap[i] = caps[i]; }
+    c->pending.push_back([=](ssm_ctx* cc) -> int {
+        for (int i = 0; i < nref; i++) {
+            int32_t n; memcpy(&n, h_res + 4 * (size_t)i, 4);
+            if (n < 0) n = 0;
+            n_outs[i] = n;
+            if (n > to.cap[i]) FAIL(cc, SSM_E_CAPACITY, "match buffer too small (need " + std::to_string(n) + ")");
+            memcpy(to.out[i], h_res + L.list(i), sizeof(ssm_dmatch) * (size_t)n);
         }
         return SSM_OK;
-    }
+    });
+    return SSM_OK;
+}
+// the VALU variant (SSM_MATCH_VARIANT=0): one pair through d_scratch, complete when the call returns
+static int match_valu(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, int32_t* idx, int32_t* dist, ssm_dmatch* out, int cap, int* n_out)
+{
+    const bool want_knn = idx != nullptr;
     const size_t need = (size_t)(nq + nt) * 32 + sizeof(MatchPair) + (size_t)nq * (16 + 16) + 64;
     int r = ensure_scratch(c, need); if (r) return r;
     uint8_t* dd = c->d_scratch;
@@ -753,24 +760,40 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
     }
     return SSM_OK;
 }
+// one pair: idx / dist (the two nearest of every query) or out / cap / n_out (the ratio-tested list)
+static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, int32_t* idx, int32_t* dist, ssm_dmatch* out, int cap, int* n_out)
+{
+    if (nq < 0 || nt < 0 || (nq && !q) || (nt && !t)) FAIL(c, SSM_E_INVAL, "bad descriptor arguments");
+    if (nt < 2) FAIL(c, SSM_E_TOO_FEW_TRAIN, "knnMatch(k=2) needs at least 2 train descriptors");
+    if (nt > 65535) FAIL(c, SSM_E_INVAL, "at most 65535 train descriptors per call");
+    if (nq == 0) { if (n_out) *n_out = 0; return SSM_OK; }
+    if (!c->match_mfma) return match_valu(c, q, nq, t, nt, ratio, idx, dist, out, cap, n_out);
+    return match_mfma_enqueue(c, &q, &nq, 1, t, nt, nq > nt ? nq : nt, ratio, &out, &cap, n_out, idx, dist);
+}
 extern "C" int ssm_hamming_knn2(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx, int32_t* dist)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (nq > 0 && (!idx || !dist)) FAIL(c, SSM_E_INVAL, "null output");
-    return match_host(c, q, nq, t, nt, c->cfg.knn_match_ratio, true, idx, dist, nullptr, 0, nullptr);
+    int r = match_host(c, q, nq, t, nt, c->cfg.knn_match_ratio, idx, dist, nullptr, 0, nullptr); if (r) return r;
+    return wait_pending(c);
 }
 extern "C" int ssm_match(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, ssm_dmatch* out, int cap, int* n_out)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!n_out || (cap > 0 && !out)) FAIL(c, SSM_E_INVAL, "null output");
-    int r = match_host(c, q, nq, t, nt, ratio, false, nullptr, nullptr, out, cap, n_out); if (r) return r;
+    int r = match_host(c, q, nq, t, nt, ratio, nullptr, nullptr, out, cap, n_out); if (r) return r;
     return wait_pending(c);
 }
-// Tracker::trackRefFrame's loop `for (pFrame : refFrames) matches = orb.match(pFrame, currentFrame)` (/root/reference/src/track.cpp:150-152) as ONE call: the
-// reference frames' descriptor sets and the current frame's are the rows of a short "sequence" (refs oldest first, the current frame last) for the sequence
-// matcher -- one upload, one expansion, ONE matrix-core launch for all pairs, one result block; list i is exactly ssm_match(refs[i], cur).
+extern "C" int ssm_match_async(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, ssm_dmatch* out, int cap, int* n_out)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    if (!n_out || (cap > 0 && !out)) FAIL(c, SSM_E_INVAL, "null output");
+    return match_host(c, q, nq, t, nt, ratio, nullptr, nullptr, out, cap, n_out);       // the VALU variant (SSM_MATCH_VARIANT=0) completes inside the call
+}
+// Tracker::trackRefFrame's loop `for (pFrame : refFrames) matches = orb.match(pFrame, currentFrame)` (src/track.cpp:150-152 of the reference) as ONE call
 static int match_refs_enqueue(ssm_ctx* c, const uint8_t* const* refs, const int* nrefs, int nref, const uint8_t* cur, int ncur, double ratio,
                               ssm_dmatch* const* outs, const int* caps, int* n_outs)
 {
@@ -780,43 +803,11 @@ static int match_refs_enqueue(ssm_ctx* c, const uint8_t* const* refs, const int*
     if (ncur > 65535) FAIL(c, SSM_E_INVAL, "at most 65535 train descriptors per call");
     int capm = ncur;
     for (int i = 0; i < nref; i++) { if (nrefs[i] < 0 || (nrefs[i] && !refs[i]) || (caps[i] > 0 && !outs[i])) FAIL(c, SSM_E_INVAL, "bad reference set"); if (nrefs[i] > capm) capm = nrefs[i]; }
-    if (!c->match_mfma || nref > 16) {                                         // the VALU variant (SSM_MATCH_VARIANT=0): pair by pair through the same entry
-        for (int i = 0; i < nref; i++) {
-            if (nrefs[i] == 0) { n_outs[i] = 0; continue; }
-            int r = match_host(c, refs[i], nrefs[i], cur, ncur, ratio, false, nullptr, nullptr, outs[i], caps[i], &n_outs[i]); if (r) return r;
-        }
-        return SSM_OK;
+    if (c->match_mfma && nref <= 16) return match_mfma_enqueue(c, refs, nrefs, nref, cur, ncur, capm, ratio, outs, caps, n_outs);
+    for (int i = 0; i < nref; i++) {                                           // the VALU variant, or more pairs than one block holds: pair by pair
+        if (nrefs[i] == 0) { n_outs[i] = 0; continue; }
+        int r = match_host(c, refs[i], nrefs[i], cur, ncur, ratio, nullptr, nullptr, outs[i], caps[i], &n_outs[i]); if (r) return r;
     }
-    const int rows = nref + 1, capT = (capm + 31) & ~31;
-    const size_t rowb = (size_t)capm * 32, inb = (size_t)rows * rowb + 128;
-    const size_t expb = (size_t)rows * capT * SSM_MATCH_DESC_BYTES, knnb = ((size_t)nref * capT * 8 + 255) & ~(size_t)255;
-    const size_t outb = 256 + (size_t)nref * capm * sizeof(ssm_dmatch);
-    uint8_t *hp, *dp;
-    int r = ring_take(c, inb + 64 + outb, ((inb + 255) & ~(size_t)255) + 2 * expb + knnb + outb, &hp, &dp); if (r) return r;
-    uint8_t* h_out = hp + ((inb + 63) & ~(size_t)63);
-    int32_t hn[32] = {0};
-    for (int i = 0; i < nref; i++) { if (nrefs[i]) memcpy(hp + (size_t)i * rowb, refs[i], (size_t)nrefs[i] * 32); hn[i] = nrefs[i]; }
-    memcpy(hp + (size_t)nref * rowb, cur, (size_t)ncur * 32); hn[nref] = ncur;
-    memcpy(hp + (size_t)rows * rowb, hn, 128);
-    uint8_t* dd = dp; int32_t* dnk = reinterpret_cast<int32_t*>(dd + (size_t)rows * rowb);
-    uint8_t* eq = dp + ((inb + 255) & ~(size_t)255); uint8_t* et = eq + expb;
-    uint8_t* knn = et + expb; uint8_t* dout = knn + knnb;
-    int32_t* dn = reinterpret_cast<int32_t*>(dout); ssm_dmatch* dm = reinterpret_cast<ssm_dmatch*>(dout + 256);
-    HIPCHK(c, hipMemcpyAsync(dd, hp, inb, hipMemcpyHostToDevice, c->main.stream));
-    HIPCHK(c, k_match_expand(dd, dnk, 0, rows, capm, capT, eq, et, c->main.stream));
-    HIPCHK(c, k_match_seq_mfma(eq, et, dnk, 0, 1, nref, nref, ratio, capm, capT, knn, dm, dn, c->main.stream));
-    HIPCHK(c, hipMemcpyAsync(h_out, dout, outb, hipMemcpyDeviceToHost, c->main.stream));
-    std::vector<ssm_dmatch*> vo(outs, outs + nref); std::vector<int> vc(caps, caps + nref);
-    c->pending.push_back([=](ssm_ctx* cc) -> int {
-        for (int i = 0; i < nref; i++) {
-            int32_t n; memcpy(&n, h_out + 4 * (size_t)i, 4);
-            if (n < 0) n = 0;
-            n_outs[i] = n;
-            if (n > vc[i]) FAIL(cc, SSM_E_CAPACITY, "match buffer too small (need " + std::to_string(n) + ")");
-            memcpy(vo[i], h_out + 256 + (size_t)i * capm * sizeof(ssm_dmatch), sizeof(ssm_dmatch) * (size_t)n);
-        }
-        return SSM_OK;
-    });
     return SSM_OK;
 }
 extern "C" int ssm_match_refs_async(ssm_ctx* c, const uint8_t* const* refs, const int* nrefs, int nref, const uint8_t* cur, int ncur, double ratio,
@@ -833,13 +824,6 @@ extern "C" int ssm_match_refs(ssm_ctx* c, const uint8_t* const* refs, const int*
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     int r = match_refs_enqueue(c, refs, nrefs, nref, cur, ncur, ratio, outs, caps, n_outs); if (r) return r;
     return wait_pending(c);
-}
-extern "C" int ssm_match_async(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, ssm_dmatch* out, int cap, int* n_out)
-{
-    if (!c) return SSM_E_INVAL;
-    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    if (!n_out || (cap > 0 && !out)) FAIL(c, SSM_E_INVAL, "null output");
-    return match_host(c, q, nq, t, nt, ratio, false, nullptr, nullptr, out, cap, n_out);       // the VALU variant (SSM_MATCH_VARIANT=0) completes inside the call
 }
 
 // ---------------------------------------------------------------- mapper front half, host pointers
@@ -888,9 +872,9 @@ static int ensure_seq(ssm_ctx* c, int n)
     // keep the history rows across the re-allocation
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     c->seq_cap = 0;                                                 // (a failure below leaves some of the outputs empty: the next call allocates again)
-    c->capT = (g.cap + 31) & ~31;
+    c->capT = match_capT(g.cap);
     if (c->match_mfma) {       // expanded rows are rebuilt from the bit descriptors at the start of every call (history) and after every ORB sub-batch
-        DALLOC(c, c->d_exp_q, (size_t)(n + R) * c->capT * SSM_MATCH_DESC_BYTES); DALLOC(c, c->d_exp_t, (size_t)(n + R) * c->capT * SSM_MATCH_DESC_BYTES); DALLOC(c, c->d_knn, (size_t)n * R * c->capT * 8);
+        DALLOC(c, c->d_exp_q, match_exp_bytes(n + R, c->capT)); DALLOC(c, c->d_exp_t, match_exp_bytes(n + R, c->capT)); DALLOC(c, c->d_knn, match_knn_bytes((size_t)n * R, c->capT));
     }
     DALLOC(c, c->d_kps, (size_t)n * g.cap); DALLOC(c, c->d_pos3d, (size_t)n * g.cap * 3);
     DALLOC(c, c->d_matches, (size_t)n * R * g.cap); DALLOC(c, c->d_nmatch, (size_t)n * R); DALLOC(c, c->d_match_pend, (size_t)n * R); DALLOC(c, c->d_npoints, (size_t)n);

@@ -269,9 +269,8 @@ template <class T, bool Pinned> int DevBuf<T, Pinned>::alloc_bytes(ssm_ctx* c, s
 // ssm_abi.hip
 extern SSM_HIDDEN thread_local std::string g_create_err;
 SSM_HIDDEN void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, std::vector<int16_t>& coef);
-SSM_HIDDEN int ensure_scratch(ssm_ctx* c, size_t bytes);
+SSM_HIDDEN int ensure_scratch(ssm_ctx* c, size_t bytes, DevBuf<uint8_t>* buf = nullptr);     // buf: c->d_scratch (the default) or c->d_scratch2
 SSM_HIDDEN int ensure_pinned(ssm_ctx* c, size_t bytes);
-SSM_HIDDEN int ensure_scratch2(ssm_ctx* c, size_t bytes);
 SSM_HIDDEN void prof_begin(ssm_ctx* c, hipStream_t s, const char* name);     // s: the stream the stage's kernels run on
 SSM_HIDDEN void prof_end(ssm_ctx* c, hipStream_t s);
 SSM_HIDDEN int check_device_flags(ssm_ctx* c, bool with_map);

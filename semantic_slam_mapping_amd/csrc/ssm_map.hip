@@ -248,7 +248,7 @@ static int table_sorted(ssm_ctx* c, VoxTable& t, int* n_out, ssm_voxel** compact
     size_t tmp_bytes = 0;
     HIPCHK(c, voxel_sort_pairs(nullptr, &tmp_bytes, nullptr, n, nullptr, nullptr, nullptr, nullptr, st));
     const size_t a = ((size_t)n * sizeof(ssm_voxel) + 255) & ~(size_t)255, kb = ((size_t)n * 8 + 255) & ~(size_t)255, ib = ((size_t)n * 4 + 255) & ~(size_t)255;
-    r = ensure_scratch2(c, a + 2 * kb + 2 * ib + tmp_bytes + 512); if (r) return r;
+    r = ensure_scratch(c, a + 2 * kb + 2 * ib + tmp_bytes + 512, &c->d_scratch2); if (r) return r;
     uint8_t* p = c->d_scratch2;
     ssm_voxel* comp = reinterpret_cast<ssm_voxel*>(p); p += a;
     uint64_t* ka = reinterpret_cast<uint64_t*>(p); p += kb; uint64_t* kbuf = reinterpret_cast<uint64_t*>(p); p += kb;
@@ -444,7 +444,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
     if (neg_rank >= 0) { prof_end(c, s); FAIL(c, SSM_E_COMM, "negative voxel count received from rank " + std::to_string(neg_rank)); }
     // (2) the receive buffer: slot r = rank r's voxels, mx entries each.  An allocation failure on one rank is agreed on by a second tiny all-gather.
     const size_t slot = (size_t)mx * sizeof(ssm_voxel);
-    int r_alloc = ensure_scratch2(c, slot * world + 256);
+    int r_alloc = ensure_scratch(c, slot * world + 256, &c->d_scratch2);
     if (r_alloc == SSM_OK) { int64_t remote = 0; for (int q = 0; q < world; q++) if (q != rank) remote += counts[q]; r_alloc = map_settle(c, s, remote); }   // room for every remote voxel: the merges below cannot overflow
     {
         const int32_t ok = r_alloc == SSM_OK ? 0 : 1;

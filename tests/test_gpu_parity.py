@@ -1042,3 +1042,63 @@ def test_match_refs_equals_pairwise_match(ctx, oracle, frames):
         got = ctx.match_refs(descs[:3], cur, ratio)
         assert all(same_struct(g, oracle.match(r, cur, ratio)) for r, g in zip(descs[:3], got))
 
+
+
+# ---------------------------------------------------------------- ssm_hamming_knn2 in the staging rings, beside pending calls
+def test_knn2_between_pending_calls(ctx, oracle):
+    """ssm_hamming_knn2 takes its blocks from the same rings as the pending asynchronous calls and completes them: the call made before it is delivered when it
+    returns, its own result and the calls around it equal the oracle's"""
+    rng = np.random.default_rng(41)
+    a, b, c, d, e, f = (rand_desc(rng, int(n)) for n in rng.integers(50, 701, 6))
+    h0 = ctx.match_async(a, b)
+    gi, gd = ctx.knn2(c, d)
+    assert same_struct(h0(), oracle.match(a, b, 0.8))                            # already delivered: knn2 completed it
+    h1 = ctx.match_async(e, f)
+    ctx.wait()
+    oi, od = oracle.knn2(c, d)
+    assert np.array_equal(gi, oi) and np.array_equal(gd, od)
+    assert same_struct(h0(), oracle.match(a, b, 0.8)) and same_struct(h1(), oracle.match(e, f, 0.8))
+
+
+def test_failing_knn2_between_pending_calls_leaves_them_intact(ctx, oracle):
+    """a refused ssm_hamming_knn2 (one train descriptor) between pending calls does not disturb them: the next ssm_wait delivers both"""
+    from semantic_slam_mapping_amd.api import SsmError
+    rng = np.random.default_rng(42)
+    a, b, c, d = (rand_desc(rng, int(n)) for n in rng.integers(50, 701, 4))
+    h0 = ctx.match_async(a, b)
+    with pytest.raises(SsmError) as err:
+        ctx.knn2(c, d[:1])
+    assert err.value.code == -5
+    h1 = ctx.match_async(c, d)
+    ctx.wait()
+    assert same_struct(h0(), oracle.match(a, b, 0.8)) and same_struct(h1(), oracle.match(c, d, 0.8))
+
+
+def test_knn2_grows_the_rings(oracle):
+    """16400 descriptors on either side: capT = 16416, and the two expanded rows of both sides (2 x 2 x 16416 x 128 bytes = 8.4 MB) exceed the 8 MB a fresh context's
+    rings start with, so the first call re-allocates them; the second has the large set on the query side.  A plain match afterwards shows the rings rewound."""
+    import semantic_slam_mapping_amd as ssm
+    rng = np.random.default_rng(43)
+    big, small, three = rand_desc(rng, 16400), rand_desc(rng, 40), rand_desc(rng, 3)
+    c = ssm.Context(0, orb_features=1000, max_batch=1, voxel_capacity_log2=16, camera=CAM)
+    try:
+        for q, t in ((small, big), (big, three)):
+            gi, gd = c.knn2(q, t)
+            oi, od = oracle.knn2(q, t)
+            assert np.array_equal(gi, oi) and np.array_equal(gd, od)
+        q, t = rand_desc(rng, 300), rand_desc(rng, 500)
+        assert same_struct(c.match(q, t), oracle.match(q, t, 0.8))
+    finally:
+        c.close()
+
+
+@pytest.mark.parametrize("nq,nt", [(1, 2), (31, 33), (1025, 64), (64, 1025)])
+def test_match_refs_with_one_reference_is_match(ctx, oracle, nq, nt):
+    """one reference frame: ssm_match_refs and ssm_match are the same call; sizes around the 32-row tile, the row capacity set by the query or by the train side"""
+    rng = np.random.default_rng(nq * 131 + nt)
+    t = rand_desc(rng, nt)
+    q = np.concatenate([t[rng.integers(0, nt, size=nq // 2)], rand_desc(rng, nq - nq // 2)])      # half of the queries are train rows: they pass the ratio test
+    one, = ctx.match_refs([q], t)
+    two = ctx.match(q, t)
+    ref = oracle.match(q, t, 0.8)
+    assert same_struct(one, two) and same_struct(one, ref)
