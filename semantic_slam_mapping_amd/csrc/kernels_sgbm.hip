@@ -193,17 +193,24 @@ bool sgbm_cost_geometry(int D, int SW, int* TX_out, size_t* lds_out)
 // round-3 form C + five = 6 (round 6: sized by the CONFIGURED form -- it was always six, 0.45 GB per pair and 115 GB for the bench's two workspaces of 128 pairs;
 // a sub-batch that has to be repeated in form 1 runs in pieces that fit, see k_sgbm).  Never less than one frame in the largest form.
 static int sgbm_form_volumes(int form) { return form == 2 ? 3 : form == 1 ? 5 : 6; }
-static size_t sgbm_ws_bytes(int w, int h, const ssm_sgbm_params& p, int nb, int nvol)
-{
-    const int maxD = p.minDisparity + p.numberOfDisparities, minX1 = maxD > 0 ? maxD : 0, maxX1 = w + (p.minDisparity < 0 ? p.minDisparity : 0);
-    const size_t w1 = maxX1 > minX1 ? (size_t)(maxX1 - minX1) : 0, vol = w1 * h * p.numberOfDisparities * nb, np = (size_t)w * h * nb;
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    return al(32 * np) + (size_t)nvol * al(vol * 2) + 2 * al(np * 2) + 3 * al(np * 4) + 256 + al(256 + (size_t)nb * sgbm_mbox_bytes_per_frame((int)w1, p.numberOfDisparities));
-}
+// The layout, regions 256-aligned: [pre-filter planes: 32 B per pixel, 12 per pixel and image used][nvol volumes, C first][d_raw][d_tmp][d2key][parent][count]
+// [256 bytes of sweep flags, then the sweep's mailboxes][256 spare]
+struct SgbmWs {
+    size_t planes, V[6], d_raw, d_tmp, d2key, parent, count, flags, bytes;
+    SgbmWs(int w, int h, const ssm_sgbm_params& p, int nb, int nvol)
+    {
+        const int maxD = p.minDisparity + p.numberOfDisparities, minX1 = maxD > 0 ? maxD : 0, maxX1 = w + (p.minDisparity < 0 ? p.minDisparity : 0);
+        const size_t w1 = maxX1 > minX1 ? (size_t)(maxX1 - minX1) : 0, vol = w1 * h * p.numberOfDisparities * nb, np = (size_t)w * h * nb;
+        Carve k; planes = k.take<uint8_t>(32 * np);
+        for (int i = 0; i < nvol; i++) V[i] = k.take<uint16_t>(vol);
+        d_raw = k.take<int16_t>(np); d_tmp = k.take<int16_t>(np); d2key = k.take<unsigned>(np); parent = k.take<int>(np); count = k.take<int>(np);
+        flags = k.take<uint8_t>(256 + (size_t)nb * sgbm_mbox_bytes_per_frame((int)w1, p.numberOfDisparities)); k.take<uint8_t>(256); bytes = k.off;
+    }
+};
 static int sgbm_resolve_form(int form_cfg) { return form_cfg == 0 ? sgbm_form() : form_cfg == 3 ? 0 : form_cfg == 1 ? 1 : 2; }
 size_t k_sgbm_workspace_bytes(int w, int h, const ssm_sgbm_params& p, int nb, int form_cfg)
 {
-    const size_t a = sgbm_ws_bytes(w, h, p, nb, sgbm_form_volumes(sgbm_resolve_form(form_cfg))), b = sgbm_ws_bytes(w, h, p, 1, 6);
+    const size_t a = SgbmWs(w, h, p, nb, sgbm_form_volumes(sgbm_resolve_form(form_cfg))).bytes, b = SgbmWs(w, h, p, 1, 6).bytes;
     return a > b ? a : b;
 }
 // left / right: device u8 images [nb][h][w]; disp_out: device int16 [nb][h][w] (x16 fixed point, (minD-1)*16 = invalid)
@@ -216,7 +223,8 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
 {
     int form = sgbm_resolve_form(form_cfg);
     if (nb <= 0) return hipSuccess;
-    if (sgbm_ws_bytes(w, h, p, nb, sgbm_form_volumes(form)) > ws_bytes) {
+    const SgbmWs ws(w, h, p, nb, sgbm_form_volumes(form));
+    if (ws.bytes > ws_bytes) {
         if (nb == 1) return hipErrorOutOfMemory;
         const int half = (nb + 1) / 2; const size_t np1_ = (size_t)w * h;
         hipError_t e1 = k_sgbm(left, right, w, h, half, p, workspace, ws_bytes, disp_out, raw_only, dev, fan, s, fail_flag, form_cfg, concurrent);
@@ -234,21 +242,14 @@ hipError_t k_sgbm(const uint8_t* left, const uint8_t* right, int w, int h, int n
         sgbm_fill<<<(unsigned)((np + 255) / 256), 256, 0, s>>>(disp_out, (int)np, (int16_t)INVALID);
         return hipGetLastError();
     }
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
     uint8_t* q = (uint8_t*)workspace;
-    uint3* planes = (uint3*)q; q += al(32 * np);                 // (12 bytes per pixel and image are used)
-    const size_t vol = (size_t)w1 * h * D * nb;
-    uint16_t* C = (uint16_t*)q; q += al(vol * 2);
+    uint3* planes = (uint3*)(q + ws.planes); uint16_t* C = (uint16_t*)(q + ws.V[0]);
     uint16_t* Lv[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    // (the layout sgbm_ws_bytes sizes: C + the form's volumes.  Form 2: S04 and the checkpoints in Lv[0], Lv[1]; form 1: the four path volumes 0, 1, 3, 4 -- the column
-    // direction lives inside sgbm_col_wta --; the round-3 form: all five)
-    for (int i = 0; i < 5; i++) { if (form == 2 ? i < 2 : form == 1 ? i != 2 : true) { Lv[i] = (uint16_t*)q; q += al(vol * 2); } }
-    int16_t* d_raw = (int16_t*)q; q += al(np * 2);
-    int16_t* d_tmp = (int16_t*)q; q += al(np * 2);
-    unsigned* d2key = (unsigned*)q; q += al(np * 4);
-    int* parent = (int*)q; q += al(np * 4);
-    int* count = (int*)q; q += al(np * 4);
-    unsigned* sweep_flags = (unsigned*)q;                     // 256 bytes of flags, then the sweep's mailboxes
+    // (form 2: S04 and the checkpoints in Lv[0], Lv[1]; form 1: the four path volumes 0, 1, 3, 4 -- the column direction lives inside sgbm_col_wta --; the round-3 form: all five)
+    for (int i = 0, j = 1; i < 5; i++) { if (form == 2 ? i < 2 : form == 1 ? i != 2 : true) Lv[i] = (uint16_t*)(q + ws.V[j++]); }
+    int16_t* d_raw = (int16_t*)(q + ws.d_raw); int16_t* d_tmp = (int16_t*)(q + ws.d_tmp); unsigned* d2key = (unsigned*)(q + ws.d2key);
+    int* parent = (int*)(q + ws.parent); int* count = (int*)(q + ws.count);
+    unsigned* sweep_flags = (unsigned*)(q + ws.flags);        // 256 bytes of flags, then the sweep's mailboxes
     {
         int TX = 0; size_t lds = 0;
         if (!sgbm_cost_geometry(D, SW, &TX, &lds)) return hipErrorInvalidValue;

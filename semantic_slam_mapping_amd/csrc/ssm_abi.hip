@@ -131,6 +131,7 @@ void prof_begin(ssm_ctx* c, hipStream_t s, const char* name)
     c->recs.push_back(r);
 }
 void prof_end(ssm_ctx* c, hipStream_t s) { if (c->profiling) hipEventRecord(c->recs.back().b, s); }
+void prof_reset(ssm_ctx* c) { if (c->profiling) { c->recs.clear(); c->pool_used = 0; } }
 hipError_t allow_dynamic_lds(const void* fn, size_t bytes, int limit)
 {
     if (bytes <= 48 * 1024) return hipSuccess;
@@ -565,7 +566,7 @@ int wait_pending(ssm_ctx* c)
 }
 static int ring_take(ssm_ctx* c, size_t hbytes, size_t dbytes, uint8_t** hp, uint8_t** dp)
 {
-    hbytes = (hbytes + 255) & ~(size_t)255; dbytes = (dbytes + 255) & ~(size_t)255;
+    hbytes = up256(hbytes); dbytes = up256(dbytes);
     if (c->h_ring_off + hbytes > c->d_ring.bytes() || c->d_ring_off + dbytes > c->d_ring.bytes()) {
         int r = wait_pending(c); if (r) return r;                                // out of room: finish what is in flight (its results are delivered now)
         const size_t need = hbytes > dbytes ? hbytes : dbytes;
@@ -602,11 +603,10 @@ struct MatchBlock {
     size_t d_eq, d_et, d_knn, d_res, dbytes;                            // device block (inputs at 0)
     MatchBlock(int rows_, int capm_) : rows(rows_), nref(rows_ - 1), capm(capm_), capT(match_capT(capm_))
     {
-        const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
         rowb = (size_t)capm * 32; counts = rows * rowb; inb = counts + counts_bytes;
-        expb = match_exp_bytes(rows, capT); knnb = up(match_knn_bytes(nref, capT)); resb = list(nref);
+        expb = match_exp_bytes(rows, capT); knnb = up256(match_knn_bytes(nref, capT)); resb = list(nref);
         h_res = (inb + 63) & ~(size_t)63; hbytes = h_res + (resb > knnb ? resb : knnb);
-        d_eq = up(inb); d_et = d_eq + expb; d_knn = d_et + expb; d_res = d_knn + knnb; dbytes = d_res + resb;
+        d_eq = up256(inb); d_et = d_eq + expb; d_knn = d_et + expb; d_res = d_knn + knnb; dbytes = d_res + resb;
     }
     size_t list(int i) const { return res_hdr + (size_t)i * capm * sizeof(ssm_dmatch); }      // list i inside the result block
 };

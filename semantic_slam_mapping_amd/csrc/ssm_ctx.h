@@ -148,7 +148,7 @@ struct StereoState {        // workspace of the stereo path (quad matcher, SGBM 
     DevBuf<double> tr; DevBuf<int32_t> inliers, vo_result;
     bool have_prev = false;                  // slot 0 holds the last frame of the previous sequence call
     bool lk_built = false;                   // slot 1 of both sides holds the pyramids and derivatives of the last ssm_lk_track (ssm_debug_quad_pyramid)
-    DevBuf<uint8_t> in_stage;                // device staging of the per-pair host-pointer entry points
+    DevBuf<uint8_t> in_stage;                // device staging of the per-pair host-pointer entry points: PairBlock::stage_bytes (ssm_stereo_abi.hip), up to four packed images
 };
 struct SegNetState {
     bool set[SEG_LAYERS] = {};
@@ -273,6 +273,7 @@ SSM_HIDDEN int ensure_scratch(ssm_ctx* c, size_t bytes, DevBuf<uint8_t>* buf = n
 SSM_HIDDEN int ensure_pinned(ssm_ctx* c, size_t bytes);
 SSM_HIDDEN void prof_begin(ssm_ctx* c, hipStream_t s, const char* name);     // s: the stream the stage's kernels run on
 SSM_HIDDEN void prof_end(ssm_ctx* c, hipStream_t s);
+SSM_HIDDEN void prof_reset(ssm_ctx* c);                     // a profiling context forgets the stages of the previous call: ssm_get_stage_times then reports this one
 SSM_HIDDEN int check_device_flags(ssm_ctx* c, bool with_map);
 SSM_HIDDEN int wait_pending(ssm_ctx* c);
 SSM_HIDDEN bool host_is_pinned(const void* p);             // page-locked host memory (ssm_host_alloc, hipHostRegister)?

@@ -11,6 +11,14 @@
 #define SSM_PATCH 31
 #define SSM_MAX_NODES 1024     // quad-tree nodes held in LDS per (frame, level)
 #define SSM_VOX_EMPTY ((int64_t)-1)
+// Layout of one buffer that several regions share.  take<T>(count) starts a region of count T at the next multiple of `align` and returns its byte offset;
+// off is then the bytes used so far (end(): rounded up).  The offsets are computed first, the total goes to whoever provides the buffer, and base + offset
+// gives the pointers: the size asked for and the pointers used come from the same statements.
+inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+struct Carve {
+    size_t off = 0; template <class T> size_t take(size_t count, size_t align = 256) { const size_t at = (off + align - 1) & ~(align - 1); off = at + count * sizeof(T); return at; }
+    size_t end() { return take<uint8_t>(0); }
+};
 
 struct LevelGeom {
     int w, h, stride;          // level image; rows padded to a multiple of 16 bytes

@@ -247,15 +247,15 @@ static int table_sorted(ssm_ctx* c, VoxTable& t, int* n_out, ssm_voxel** compact
     if (n == 0) return SSM_OK;
     size_t tmp_bytes = 0;
     HIPCHK(c, voxel_sort_pairs(nullptr, &tmp_bytes, nullptr, n, nullptr, nullptr, nullptr, nullptr, st));
-    const size_t a = ((size_t)n * sizeof(ssm_voxel) + 255) & ~(size_t)255, kb = ((size_t)n * 8 + 255) & ~(size_t)255, ib = ((size_t)n * 4 + 255) & ~(size_t)255;
-    r = ensure_scratch(c, a + 2 * kb + 2 * ib + tmp_bytes + 512, &c->d_scratch2); if (r) return r;
+    Carve k;
+    const size_t o_comp = k.take<ssm_voxel>(n), o_ka = k.take<uint64_t>(n), o_kb = k.take<uint64_t>(n), o_ia = k.take<uint32_t>(n), o_ib = k.take<uint32_t>(n),
+                 o_n = k.take<int32_t>(64), o_tmp = k.take<uint8_t>(tmp_bytes);
+    k.take<uint8_t>(256, 1); r = ensure_scratch(c, k.off, &c->d_scratch2); if (r) return r;      // (256 spare)
     uint8_t* p = c->d_scratch2;
-    ssm_voxel* comp = reinterpret_cast<ssm_voxel*>(p); p += a;
-    uint64_t* ka = reinterpret_cast<uint64_t*>(p); p += kb; uint64_t* kbuf = reinterpret_cast<uint64_t*>(p); p += kb;
-    uint32_t* ia = reinterpret_cast<uint32_t*>(p); p += ib; uint32_t* ibuf = reinterpret_cast<uint32_t*>(p); p += ib;
-    int32_t* dn = reinterpret_cast<int32_t*>(p); p += 256;
-    HIPCHK(c, k_voxel_compact(t.tab, t.cap_log2, comp, dn, st));
-    HIPCHK(c, voxel_sort_pairs(p, &tmp_bytes, comp, n, ka, kbuf, ia, ibuf, st));
+    ssm_voxel* comp = reinterpret_cast<ssm_voxel*>(p + o_comp);
+    uint32_t* ibuf = reinterpret_cast<uint32_t*>(p + o_ib);
+    HIPCHK(c, k_voxel_compact(t.tab, t.cap_log2, comp, reinterpret_cast<int32_t*>(p + o_n), st));
+    HIPCHK(c, voxel_sort_pairs(p + o_tmp, &tmp_bytes, comp, n, reinterpret_cast<uint64_t*>(p + o_ka), reinterpret_cast<uint64_t*>(p + o_kb), reinterpret_cast<uint32_t*>(p + o_ia), ibuf, st));
     *compact = comp; *order = ibuf;
     return SSM_OK;
 }

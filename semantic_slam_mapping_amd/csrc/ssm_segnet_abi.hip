@@ -35,14 +35,14 @@ int seg_init(ssm_ctx* c)
     for (int i = 0; i < 5; i++) DALLOC(c, g->code[i], (size_t)g->batch * ph[i] * pw[i] * pc[i]);
     DALLOC(c, g->labels, (size_t)g->batch * SEG_NW * SEG_NH);
     DALLOC(c, g->d_sem_gen, (size_t)c->B * c->g.W * c->g.H * 3);
-    auto up = [&](int ssize, int dsize, DevBuf<int32_t>& o, DevBuf<int16_t>& a) -> int {
+    auto upload = [&](int ssize, int dsize, DevBuf<int32_t>& o, DevBuf<int16_t>& a) -> int {
         std::vector<int32_t> ofs; std::vector<int16_t> co; resize_tables(ssize, dsize, ofs, co);
         DALLOC(c, o, ofs.size()); DALLOC(c, a, co.size());
         if (hipMemcpy(o, ofs.data(), ofs.size() * 4, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(a, co.data(), co.size() * 2, hipMemcpyHostToDevice) != hipSuccess) { c->err = "segnet table upload"; return SSM_E_HIP; }
         return SSM_OK;
     };
-    if ((r = up(c->g.W, SEG_NW, g->pre_xofs, g->pre_xa)) || (r = up(c->g.H, SEG_NH, g->pre_yofs, g->pre_ya)) ||
-        (r = up(SEG_NW, c->g.W, g->post_xofs, g->post_xa)) || (r = up(SEG_NH, c->g.H, g->post_yofs, g->post_ya))) return r;
+    if ((r = upload(c->g.W, SEG_NW, g->pre_xofs, g->pre_xa)) || (r = upload(c->g.H, SEG_NH, g->pre_yofs, g->pre_ya)) ||
+        (r = upload(SEG_NW, c->g.W, g->post_xofs, g->post_xa)) || (r = upload(SEG_NH, c->g.H, g->post_yofs, g->post_ya))) return r;
     c->seg = std::move(g);
     return SSM_OK;
 }

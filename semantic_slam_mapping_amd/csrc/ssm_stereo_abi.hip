@@ -80,6 +80,7 @@ static int sgbm_check_params(ssm_ctx* c, const ssm_sgbm_params* params, int w, i
     { int tx; size_t lds; if (!sgbm_cost_geometry(D, SW, &tx, &lds)) FAIL(c, SSM_E_INVAL, "SADWindowSize too large for this numberOfDisparities (the cost kernel keeps SADWindowSize rows of 4 columns x D sums in LDS)"); }
     return SSM_OK;
 }
+static int quad_size_check(ssm_ctx* c, int w, int h) { if (w < 32 || h < 32) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096"); return SSM_OK; }
 // the sequence path on device images; the caller holds the context lock
 // pair_call: the caller is ssm_quad_track (frame 0 = the previous pair of ONE matcher call: only its pyramids and derivatives are needed -- its corners and tracks
 // are nobody's output, and skipping them takes a third off the call: 1.06 -> 0.8 ms at 1241 x 376)
@@ -91,8 +92,8 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     if ((stages & SSM_STEREO_VO) && !(stages & SSM_STEREO_QUAD)) FAIL(c, SSM_E_INVAL, "SSM_STEREO_VO needs SSM_STEREO_QUAD");
     if ((stages & SSM_STEREO_VO) && (in->ransac_iters < 0 || (in->ransac_iters > 0 && !in->rand_stream))) FAIL(c, SSM_E_INVAL, "the VO stage needs rand_stream (n * ransac_iters * 3 draws)");
     const int maxc = in->max_corners > 0 ? in->max_corners : 1000;
-    if ((stages & SSM_STEREO_QUAD) && (w < 32 || h < 32)) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
-    int r = stereo_init(c, w, h, maxc, true); if (r) return r;
+    int r = (stages & SSM_STEREO_QUAD) ? quad_size_check(c, w, h) : SSM_OK; if (r) return r;
+    r = stereo_init(c, w, h, maxc, true); if (r) return r;
     StereoState* q = c->stereo.get();
     q->lk_built = false;                                          // (the sub-batch overwrites slot 1)
     if (stages & SSM_STEREO_DEPTH) { r = sgbm_check_params(c, &in->sgbm, w, h); if (r) return r; }
@@ -114,7 +115,7 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     Lane* const sgl[3] = {two ? &c->side[0] : &c->main, nsg > 1 ? &c->side[1] : nullptr, nsg > 2 ? &c->side[2] : nullptr};      // SGBM's lanes
     for (int k = 1; k < nsg; k++) { r = stereo_ensure_sgbm(c, in->sgbm, B, k); if (r) return r; }
     if (two) { r = lanes_fork(c, {sgl[0], sgl[1], sgl[2]}); if (r) return r; }
-    if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
+    prof_reset(c);
     const bool prev0 = in->continue_sequence && q->have_prev;
     if (stages & SSM_STEREO_VO) HIPCHK(c, hipMemsetAsync(q->consumed, 0, 4, sq));
     for (int f0 = 0; f0 < n; f0 += B) {
@@ -174,22 +175,28 @@ extern "C" int ssm_stereo_seq_process(ssm_ctx* c, const ssm_stereo_frames_dev* i
     if (!in) FAIL(c, SSM_E_INVAL, "null argument");
     return stereo_seq_run(c, in, out);
 }
-// host images -> packed device staging: slot k of the staging area holds image k ([h][w] bytes each); through pinned memory (a pageable copy of a
-// 1241x376 image costs ~1 ms)
-static int stereo_stage_images(ssm_ctx* c, const uint8_t* const* imgs, int nimg, int w, int h, int stride, uint8_t** dev_out)
+// The pinned area of a per-pair call on images of np pixels.  Going up: [image 0] .. [image 3], packed, which StereoState::in_stage mirrors on the device.  Coming
+// back, once the upload has consumed the images: [the sweep's time-out word] .. [disparity, behind two images][depth].
+struct PairBlock {
+    size_t np, plane, fail = 0, disp, depth, bytes, stage_bytes;  // plane: bytes of the disparity (int16) or depth (uint16) image; stage_bytes: four images (ssm_quad_track)
+    explicit PairBlock(size_t np_) : np(np_), plane(np * sizeof(int16_t)), disp(image(2)), depth(disp + plane), bytes(depth + plane), stage_bytes(image(4)) {}
+    size_t image(int k) const { return k * np; }
+};
+// host images -> packed device staging (StereoState::in_stage): slot k of the staging area holds image k ([h][w] bytes each); through pinned memory (a pageable
+// copy of a 1241x376 image costs ~1 ms)
+static int stereo_stage_images(ssm_ctx* c, const uint8_t* const* imgs, int nimg, int w, int h, int stride)
 {
     StereoState* q = c->stereo.get();
-    const size_t np = (size_t)w * h;
-    int r = ensure_pinned(c, np * 6 > (size_t)nimg * np ? np * 6 : (size_t)nimg * np); if (r) return r;
-    if ((size_t)nimg * np > q->in_stage.bytes()) {
+    const PairBlock P((size_t)w * h);
+    int r = ensure_pinned(c, P.bytes > P.image(nimg) ? P.bytes : P.image(nimg)); if (r) return r;
+    if (P.image(nimg) > q->in_stage.bytes()) {
         HIPCHK(c, hipDeviceSynchronize());
-        DALLOC(c, q->in_stage, (size_t)4 * np);
+        DALLOC(c, q->in_stage, P.stage_bytes);
     }
     HIPCHK(c, hipStreamSynchronize(c->main.stream));               // the previous call's copies out of the staging buffer are done
     for (int k = 0; k < nimg; k++)
-        for (int y = 0; y < h; y++) memcpy(c->h_pinned + (size_t)k * np + (size_t)y * w, imgs[k] + (size_t)y * stride, w);
-    HIPCHK(c, hipMemcpyAsync(q->in_stage, c->h_pinned, (size_t)nimg * np, hipMemcpyHostToDevice, c->main.stream));
-    *dev_out = q->in_stage;
+        for (int y = 0; y < h; y++) memcpy(c->h_pinned + P.image(k) + (size_t)y * w, imgs[k] + (size_t)y * stride, w);
+    HIPCHK(c, hipMemcpyAsync(q->in_stage, c->h_pinned, P.image(nimg), hipMemcpyHostToDevice, c->main.stream));
     return SSM_OK;
 }
 extern "C" int ssm_quad_track(ssm_ctx* c, const uint8_t* lc, const uint8_t* rc, const uint8_t* lp, const uint8_t* rp, int w, int h, int stride,
@@ -201,10 +208,10 @@ extern "C" int ssm_quad_track(ssm_ctx* c, const uint8_t* lc, const uint8_t* rc, 
     int r = stereo_init(c, w, h, max_corners, true); if (r) return r;
     // a two-frame sequence: frame 0 = the previous pair, frame 1 = the current pair (left images first, then the right ones)
     const uint8_t* imgs[4] = { lp, lc, rp, rc };
-    uint8_t* dev = nullptr;
-    r = stereo_stage_images(c, imgs, 4, w, h, stride, &dev); if (r) return r;
+    r = stereo_stage_images(c, imgs, 4, w, h, stride); if (r) return r;
+    uint8_t* dev = c->stereo->in_stage;
     ssm_stereo_frames_dev in; memset(&in, 0, sizeof(in));
-    in.left = dev; in.right = dev + (size_t)2 * w * h; in.n = 2; in.w = w; in.h = h; in.stages = SSM_STEREO_QUAD; in.max_corners = max_corners;
+    in.left = dev; in.right = dev + PairBlock((size_t)w * h).image(2); in.n = 2; in.w = w; in.h = h; in.stages = SSM_STEREO_QUAD; in.max_corners = max_corners;
     ssm_stereo_out_dev o;
     r = stereo_seq_run(c, &in, &o, true); if (r) return r;
     c->stereo->have_prev = false;                                // a per-pair call is not part of a sequence
@@ -217,6 +224,13 @@ extern "C" int ssm_quad_track(ssm_ctx* c, const uint8_t* lc, const uint8_t* rc, 
     if (m > 0) HIPCHK(c, hipMemcpy(out, o.quad + o.max_corners, (size_t)m * sizeof(ssm_pmatch), hipMemcpyDeviceToHost));
     return SSM_OK;
 }
+// level 0 of a host image into slot 1 of `side` (what the per-call GFTT and LK read)
+static int quad_upload_slot1(ssm_ctx* c, int side, const uint8_t* img, int stride)
+{
+    StereoState* q = c->stereo.get(); q->lk_built = false;
+    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(side * q->qb.B1 + 1) * q->qb.slot_elems, q->w, img, stride, q->w, q->h, hipMemcpyHostToDevice, c->main.stream));
+    return SSM_OK;
+}
 extern "C" int ssm_gftt(ssm_ctx* c, const uint8_t* img, int w, int h, int stride, int max_corners, double quality, double min_distance,
                         float* pts, int cap, int* n_out)
 {
@@ -224,12 +238,11 @@ extern "C" int ssm_gftt(ssm_ctx* c, const uint8_t* img, int w, int h, int stride
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!img || !pts || !n_out || stride < w || max_corners < 1 || !(min_distance >= 1.0)) FAIL(c, SSM_E_INVAL, "bad arguments (max_corners >= 1, min_distance >= 1)");
     if (min_distance > 64.0) FAIL(c, SSM_E_INVAL, "min_distance must be <= 64");
-    if (w < 32 || h < 32) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
+    int r = quad_size_check(c, w, h); if (r) return r;
     if (max_corners > 32767) FAIL(c, SSM_E_INVAL, "max_corners must be <= 32767");
-    int r = stereo_init(c, w, h, max_corners); if (r) return r;
+    r = stereo_init(c, w, h, max_corners); if (r) return r;
     StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
-    q->lk_built = false;
-    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, img, stride, w, h, hipMemcpyHostToDevice, c->main.stream));        // side 0, slot 1, level 0
+    r = quad_upload_slot1(c, 0, img, stride); if (r) return r;
     HIPCHK(c, k_quad_gftt(qb, 1, max_corners, quality, min_distance, q->gw, q->pts, q->maxc, q->ncorner, c->main.stream));
     int n = 0;
     HIPCHK(c, hipMemcpyAsync(&n, q->ncorner, 4, hipMemcpyDeviceToHost, c->main.stream));
@@ -247,13 +260,11 @@ extern "C" int ssm_lk_track(ssm_ctx* c, const uint8_t* prev, const uint8_t* next
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!prev || !next || n < 0 || (n && (!prev_pts || !next_pts)) || stride < w || max_count < 1) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n == 0) return SSM_OK;
-    if (w < 32 || h < 32) FAIL(c, SSM_E_INVAL, "quad matcher: image size must be 32..4096");
-    int r = stereo_init(c, w, h, n > 1000 ? n : 1000); if (r) return r;
+    int r = quad_size_check(c, w, h); if (r) return r;
+    r = stereo_init(c, w, h, n > 1000 ? n : 1000); if (r) return r;
     StereoState* q = c->stereo.get(); const QuadBatch& qb = q->qb;
     // previous image = (side 0, slot 1), next image = (side 1, slot 1)
-    q->lk_built = false;
-    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)1 * qb.slot_elems, w, prev, stride, w, h, hipMemcpyHostToDevice, c->main.stream));
-    HIPCHK(c, hipMemcpy2DAsync(q->pyr + (size_t)(qb.B1 + 1) * qb.slot_elems, w, next, stride, w, h, hipMemcpyHostToDevice, c->main.stream));
+    if ((r = quad_upload_slot1(c, 0, prev, stride)) || (r = quad_upload_slot1(c, 1, next, stride))) return r;
     HIPCHK(c, k_quad_pyramids(qb, 1, c->main.stream));
     float* d_in = q->pts; float* d_out = q->pts + (size_t)2 * q->maxc;
     HIPCHK(c, hipMemcpyAsync(d_in, prev_pts, (size_t)n * 8, hipMemcpyHostToDevice, c->main.stream));
@@ -290,10 +301,10 @@ extern "C" int ssm_window_match(ssm_ctx* c, const float* kp1, const uint8_t* d1,
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (n1 < 0 || n2 < 0 || (n1 && (!kp1 || !d1 || !out)) || (n2 && (!kp2 || !d2))) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n1 == 0) return SSM_OK;
-    const size_t a1 = ((size_t)n1 * 8 + 255) & ~(size_t)255, a2 = ((size_t)n2 * 8 + 255) & ~(size_t)255, b1 = ((size_t)n1 * 32 + 255) & ~(size_t)255, b2 = ((size_t)n2 * 32 + 255) & ~(size_t)255;
-    int r = ensure_scratch(c, a1 + a2 + b1 + b2 + (size_t)n1 * 16 + 256); if (r) return r;
+    Carve k; const size_t o_k1 = k.take<float>(2 * (size_t)n1), o_k2 = k.take<float>(2 * (size_t)n2), o_d1 = k.take<uint8_t>(32 * (size_t)n1), o_d2 = k.take<uint8_t>(32 * (size_t)n2), o_m = k.take<ssm_dmatch>(n1);
+    k.take<uint8_t>(256, 1); int r = ensure_scratch(c, k.off); if (r) return r;      // (256 spare)
     uint8_t* p = (uint8_t*)c->d_scratch;
-    float* dk1 = (float*)p; p += a1; float* dk2 = (float*)p; p += a2; uint8_t* dd1 = p; p += b1; uint8_t* dd2 = p; p += b2; ssm_dmatch* dm = (ssm_dmatch*)p;
+    float* dk1 = (float*)(p + o_k1); float* dk2 = (float*)(p + o_k2); uint8_t* dd1 = p + o_d1; uint8_t* dd2 = p + o_d2; ssm_dmatch* dm = (ssm_dmatch*)(p + o_m);
     HIPCHK(c, hipMemcpyAsync(dk1, kp1, (size_t)n1 * 8, hipMemcpyHostToDevice, c->main.stream)); HIPCHK(c, hipMemcpyAsync(dd1, d1, (size_t)n1 * 32, hipMemcpyHostToDevice, c->main.stream));
     if (n2) { HIPCHK(c, hipMemcpyAsync(dk2, kp2, (size_t)n2 * 8, hipMemcpyHostToDevice, c->main.stream)); HIPCHK(c, hipMemcpyAsync(dd2, d2, (size_t)n2 * 32, hipMemcpyHostToDevice, c->main.stream)); }
     HIPCHK(c, k_quad_window_match(dk1, dd1, n1, dk2, dd2, n2, search_width, search_height, distance_threshold, dm, c->main.stream));
@@ -308,27 +319,6 @@ extern "C" void ssm_sgbm_params_default(ssm_sgbm_params* p)
     if (!p) return;
     p->minDisparity = 0; p->numberOfDisparities = 80; p->SADWindowSize = 11; p->P1 = 4 * 11 * 11; p->P2 = 32 * 11 * 11;       // src/stereo.cpp:16-27
     p->disp12MaxDiff = 1; p->preFilterCap = 63; p->uniquenessRatio = 10; p->speckleWindowSize = 100; p->speckleRange = 32;
-}
-// one host pair through the batched kernels (nb = 1): images staged on the device, disparity (and depth) left in the sequence output buffers
-static int sgbm_run(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, const ssm_sgbm_params* params, int stage,
-                    int16_t** d_disp_out, uint16_t** d_depth_out, int form)
-{
-    if (!left || !right || !params || w < 3 || h < 1 || stride < w) FAIL(c, SSM_E_INVAL, "bad arguments");
-    int r = sgbm_check_params(c, params, w, h); if (r) return r;
-    r = stereo_init(c, w, h, c->stereo && c->stereo->w == w && c->stereo->h == h ? c->stereo->maxc : 1000); if (r) return r;
-    r = stereo_ensure_seq(c, 1); if (r) return r;
-    r = stereo_ensure_sgbm(c, *params, 1); if (r) return r;
-    StereoState* q = c->stereo.get();
-    const uint8_t* imgs[2] = { left, right };
-    uint8_t* dev = nullptr;
-    r = stereo_stage_images(c, imgs, 2, w, h, stride, &dev); if (r) return r;
-    if (c->profiling) { c->recs.clear(); c->pool_used = 0; }      // ssm_get_stage_times then reports this call ("sgbm": all kernels of k_sgbm)
-    prof_begin(c, c->main.stream, "sgbm");
-    HIPCHK(c, k_sgbm(dev, dev + (size_t)w * h, w, h, 1, *params, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp, stage, c->dev, c->main.sg, c->main.stream, q->sg_fail, form, 1));
-    prof_end(c, c->main.stream);
-    q->sg_pending.valid = false;                                  // (the staged pair is this call's: the host-pointer entry points repeat a timed-out sweep themselves)
-    *d_disp_out = q->disp; *d_depth_out = q->depth;
-    return SSM_OK;
 }
 // cv::StereoSGBM cannot fail (src/stereo.cpp:11-30); form 2's sweep can: its strips wait for each other, and when a hand-off exceeds its spin bound every block
 // leaves mid-image with the sub-batch's fail word set.  Called with the streams drained: every sub-batch of the last sequence call whose word is set is computed again
@@ -357,12 +347,42 @@ int sgbm_recover(ssm_ctx* c)
     c->err = "note: the SGBM sweep of " + std::to_string(redone) + " sub-batch(es) timed out in a strip hand-off; they were repeated with form 1 (results complete)";
     return SSM_OK;
 }
-// the sweep kernel's time-out word, copied to the front of the pinned area with the results of a host-pointer call
-static bool sgbm_failed(ssm_ctx* c)
+// One host pair through the batched kernels (nb = 1): images staged on the device, disparity (and depth, with `da`) left in the sequence output buffers and brought
+// back through the pinned area (PairBlock) together with the sweep kernel's time-out word.  A sweep whose hand-off timed out is repeated once, in form 1 (no
+// cross-block waits): the host-pointer entry points repeat it themselves, with a note.  disp may be null with depth.
+struct DepthArgs { double baseline, cu, cv, f, roix, roiy, roiz, scale; };
+static int sgbm_pair(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, const ssm_sgbm_params* params, int stage,
+                     const DepthArgs* da /* null: no conversion */, int16_t* disp, uint16_t* depth)
 {
-    int32_t sf; memcpy(&sf, c->h_pinned, 4);
-    if (sf) hipMemset(c->stereo->sg_fail, 0, 4);
-    return sf != 0;
+    if (!left || !right || !params || w < 3 || h < 1 || stride < w) FAIL(c, SSM_E_INVAL, "bad arguments");
+    int r = sgbm_check_params(c, params, w, h); if (r) return r;
+    r = stereo_init(c, w, h, c->stereo && c->stereo->w == w && c->stereo->h == h ? c->stereo->maxc : 1000); if (r) return r;
+    if ((r = stereo_ensure_seq(c, 1)) || (r = stereo_ensure_sgbm(c, *params, 1))) return r;
+    StereoState* q = c->stereo.get();
+    const PairBlock P((size_t)w * h); const hipStream_t s = c->main.stream;
+    const uint8_t* imgs[2] = { left, right }; bool repeated = false;
+    for (int attempt = 0; ; attempt++) {
+        r = stereo_stage_images(c, imgs, 2, w, h, stride); if (r) return r;
+        prof_reset(c);                                            // ssm_get_stage_times then reports this call ("sgbm": all kernels of k_sgbm)
+        prof_begin(c, s, "sgbm");
+        HIPCHK(c, k_sgbm(q->in_stage, q->in_stage + P.image(1), w, h, 1, *params, q->sg_wsN[0], q->sg_wsN[0].bytes(), q->disp, stage, c->dev, c->main.sg, s, q->sg_fail, attempt ? 1 : c->sgbm_form_cfg, 1));
+        prof_end(c, s);
+        q->sg_pending.valid = false;                              // (the staged pair is this call's, not a sequence call's that sgbm_recover could repeat)
+        if (da) HIPCHK(c, k_sgbm_depth(q->disp, w, h, 1, da->baseline, da->cu, da->cv, da->f, da->roix, da->roiy, da->roiz, da->scale, q->dminN[0], q->depth, s));
+        if (da) HIPCHK(c, hipMemcpyAsync(c->h_pinned + P.depth, q->depth, P.plane, hipMemcpyDeviceToHost, s));
+        if (disp) HIPCHK(c, hipMemcpyAsync(c->h_pinned + P.disp, q->disp, P.plane, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(c->h_pinned + P.fail, q->sg_fail, 4, hipMemcpyDeviceToHost, s));      // (the staged input images at the front of the pinned area are consumed)
+        HIPCHK(c, hipStreamSynchronize(s));
+        int32_t sf; memcpy(&sf, c->h_pinned + P.fail, 4);
+        if (!sf) break;
+        HIPCHK(c, hipMemset(q->sg_fail, 0, 4));
+        if (attempt) FAIL(c, SSM_E_HIP, "SGBM: the time-out word is set after a form-1 run");
+        c->sgbm_fallbacks++; repeated = true;
+    }
+    if (repeated) c->err = "note: the SGBM sweep of this pair timed out in a strip hand-off and was repeated with form 1 (results complete; " + std::to_string(c->sgbm_fallbacks) + " such repeats on this context so far)";
+    if (da) memcpy(depth, c->h_pinned + P.depth, P.plane);
+    if (disp) memcpy(disp, c->h_pinned + P.disp, P.plane);
+    return SSM_OK;
 }
 extern "C" int ssm_sgbm(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, const ssm_sgbm_params* params, int stage, int16_t* disp)
 {
@@ -370,21 +390,7 @@ extern "C" int ssm_sgbm(ssm_ctx* c, const uint8_t* left, const uint8_t* right, i
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!disp) FAIL(c, SSM_E_INVAL, "null argument");
     c->err.clear();
-    int16_t* dd; uint16_t* ddepth;
-    const size_t np = (size_t)w * h;
-    bool repeated = false;
-    for (int attempt = 0; ; attempt++) {                      // a sweep whose hand-off timed out is repeated once, in form 1 (no cross-block waits)
-        int r = sgbm_run(c, left, right, w, h, stride, params, stage, &dd, &ddepth, attempt ? 1 : c->sgbm_form_cfg); if (r) return r;
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2 * np, dd, np * 2, hipMemcpyDeviceToHost, c->main.stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->stereo->sg_fail, 4, hipMemcpyDeviceToHost, c->main.stream));      // (the staged input images at the front of the pinned area are consumed)
-        HIPCHK(c, hipStreamSynchronize(c->main.stream));
-        if (!sgbm_failed(c)) break;
-        if (attempt) FAIL(c, SSM_E_HIP, "SGBM: the time-out word is set after a form-1 run");
-        c->sgbm_fallbacks++; repeated = true;
-    }
-    memcpy(disp, c->h_pinned + 2 * np, np * 2);
-    if (repeated) c->err = "note: the SGBM sweep of this pair timed out in a strip hand-off and was repeated with form 1 (results complete; " + std::to_string(c->sgbm_fallbacks) + " such repeats on this context so far)";
-    return SSM_OK;
+    return sgbm_pair(c, left, right, w, h, stride, params, stage, nullptr, disp, nullptr);
 }
 extern "C" int ssm_stereo_depth(ssm_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride, const ssm_sgbm_params* params,
                                 double baseline, double cu, double cv, double f, double roix, double roiy, double roiz, double scale,
@@ -394,24 +400,8 @@ extern "C" int ssm_stereo_depth(ssm_ctx* c, const uint8_t* left, const uint8_t* 
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!depth) FAIL(c, SSM_E_INVAL, "null argument");
     c->err.clear();
-    int16_t* dd; uint16_t* ddepth;
-    const size_t np = (size_t)w * h;
-    bool repeated = false;
-    for (int attempt = 0; ; attempt++) {
-        int r = sgbm_run(c, left, right, w, h, stride, params, 0, &dd, &ddepth, attempt ? 1 : c->sgbm_form_cfg); if (r) return r;
-        HIPCHK(c, k_sgbm_depth(dd, w, h, 1, baseline, cu, cv, f, roix, roiy, roiz, scale, c->stereo->dminN[0], ddepth, c->main.stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned + 4 * np, ddepth, np * 2, hipMemcpyDeviceToHost, c->main.stream));
-        if (disp) HIPCHK(c, hipMemcpyAsync(c->h_pinned + 2 * np, dd, np * 2, hipMemcpyDeviceToHost, c->main.stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_pinned, c->stereo->sg_fail, 4, hipMemcpyDeviceToHost, c->main.stream));
-        HIPCHK(c, hipStreamSynchronize(c->main.stream));
-        if (!sgbm_failed(c)) break;
-        if (attempt) FAIL(c, SSM_E_HIP, "SGBM: the time-out word is set after a form-1 run");
-        c->sgbm_fallbacks++; repeated = true;
-    }
-    memcpy(depth, c->h_pinned + 4 * np, np * 2);
-    if (disp) memcpy(disp, c->h_pinned + 2 * np, np * 2);
-    if (repeated) c->err = "note: the SGBM sweep of this pair timed out in a strip hand-off and was repeated with form 1 (results complete; " + std::to_string(c->sgbm_fallbacks) + " such repeats on this context so far)";
-    return SSM_OK;
+    const DepthArgs da = { baseline, cu, cv, f, roix, roiy, roiz, scale };
+    return sgbm_pair(c, left, right, w, h, stride, params, 0, &da, disp, depth);
 }
 // the SGBM post stages alone (exact tests of the median and of the speckle union-find on constructed maps): n stacked maps through k_sgbm_post
 extern "C" int ssm_debug_sgbm_post(ssm_ctx* c, const int16_t* disp, int w, int h, int n, int op, int new_val, int max_size, int max_diff, int16_t* out)
@@ -420,11 +410,11 @@ extern "C" int ssm_debug_sgbm_post(ssm_ctx* c, const int16_t* disp, int w, int h
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (!disp || !out || w < 1 || h < 1 || n < 1 || op < 1 || op > 3 || max_diff < 0 || new_val < -32768 || new_val > 32767) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (h > 65535 || n > 65535 || (long long)w * h >= (1ll << 30)) FAIL(c, SSM_E_INVAL, "map too large");
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t np = (size_t)w * h * n, b16 = al(np * 2), b32 = al(np * 4);
-    int r = ensure_scratch(c, 2 * b16 + 2 * b32); if (r) return r;
+    const size_t np = (size_t)w * h * n;
+    Carve k; const size_t o_in = k.take<int16_t>(np), o_out = k.take<int16_t>(np), o_parent = k.take<int>(np), o_count = k.take<int>(np);
+    int r = ensure_scratch(c, k.end()); if (r) return r;
     uint8_t* p = (uint8_t*)c->d_scratch;
-    int16_t* d_in = (int16_t*)p; int16_t* d_out = (int16_t*)(p + b16); int* parent = (int*)(p + 2 * b16); int* count = (int*)(p + 2 * b16 + b32);
+    int16_t* d_in = (int16_t*)(p + o_in); int16_t* d_out = (int16_t*)(p + o_out); int* parent = (int*)(p + o_parent); int* count = (int*)(p + o_count);
     HIPCHK(c, hipMemcpyAsync(d_in, disp, np * 2, hipMemcpyHostToDevice, c->main.stream));
     if (!(op & 1)) HIPCHK(c, hipMemcpyAsync(d_out, d_in, np * 2, hipMemcpyDeviceToDevice, c->main.stream));
     HIPCHK(c, k_sgbm_post(d_in, d_out, w, h, n, op, new_val, max_size, max_diff, parent, count, c->main.stream));
@@ -444,14 +434,13 @@ extern "C" int ssm_vo_estimate(ssm_ctx* c, const ssm_pmatch* matches, int n, con
     *n_inliers = 0; *success = 0;
     if (n < 6) return SSM_OK;                                 // estimateMotion returns an empty vector (vo_stereo.cpp:61-63)
     for (int k = 0; k < 3 * iters; k++) if (samples[k] < 0 || samples[k] >= n) FAIL(c, SSM_E_INVAL, "sample index out of range");
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t o_m = 0, o_s = o_m + al((size_t)n * sizeof(ssm_pmatch)), o_tr = o_s + al((size_t)iters * 12 + 16), o_cnt = o_tr + al((size_t)iters * 48 + 48),
-                 o_out = o_cnt + al((size_t)iters * 4 + 16), o_inl = o_out + 256, o_res = o_inl + al((size_t)n * 4), total = o_res + 256;
-    int r = ensure_scratch(c, total); if (r) return r;
+    Carve k; const size_t o_m = k.take<ssm_pmatch>(n), o_s = k.take<uint8_t>((size_t)iters * 12 + 16), o_tr = k.take<uint8_t>((size_t)iters * 48 + 48), o_cnt = k.take<uint8_t>((size_t)iters * 4 + 16),
+                 o_out = k.take<uint8_t>(256), o_inl = k.take<int32_t>(n), o_res = k.take<uint8_t>(256);
+    int r = ensure_scratch(c, k.off); if (r) return r;         // (the last region is the 256 bytes of o_res)
     uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->main.stream;
     HIPCHK(c, hipMemcpyAsync(p + o_m, matches, (size_t)n * sizeof(ssm_pmatch), hipMemcpyHostToDevice, s));
     if (iters) HIPCHK(c, hipMemcpyAsync(p + o_s, samples, (size_t)iters * 12, hipMemcpyHostToDevice, s));
-    if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
+    prof_reset(c);
     prof_begin(c, s, "vo");
     HIPCHK(c, k_vo_estimate((const ssm_pmatch*)(p + o_m), n, *params, (const int32_t*)(p + o_s), iters, (double*)(p + o_tr), (int32_t*)(p + o_cnt),
                             (double*)(p + o_out), (int32_t*)(p + o_inl), (int32_t*)(p + o_res), s));
@@ -477,40 +466,41 @@ static int pnp_solve_impl(ssm_ctx* c, const float* img, const float* obj, int n,
     // ONE upload ([img | obj | header: T in, T out, time-out word, inlier count] staged in pinned memory) and ONE download ([T out .. count | the inlier flags]): the
     // call was three uploads, a fill of the exchange ring and four downloads (0.09 ms of its 0.42).  The cluster's ring lives in the context and is zeroed when its
     // pass numbers wrap, not per call.
-    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t ne = (size_t)(n > 0 ? n : 1), slice = al(ne);
-    const size_t o_img = 0, o_obj = o_img + ne * 8, o_hdr = (o_obj + ne * 12 + 15) & ~(size_t)15, HDR = 288 /* T in 128 | T out 128 | xfail 4, pad 4 | count 4, pad 4 | pad 16 */,
-                 o_inl = o_hdr + HDR, o_dec = o_inl + G * slice, o_le = al(o_dec + G * slice), o_err = o_le + al(G * slice * k_pnp_edge_bytes()), total = o_err + al(G * slice * 16);
-    const size_t up = o_hdr + HDR, down = HDR - 128 + (size_t)n;               // download: [T out | xfail | count | pad][inl slice 0: n bytes]
-    int r = ensure_scratch(c, total); if (r) return r;
-    r = ensure_pinned(c, al(up) + al(down)); if (r) return r;
+    enum : size_t { H_TOUT = 128, H_XFAIL = 256, H_COUNT = 264, HDR = 288 };      // the header: T in 128 | T out 128 | xfail 4, pad 4 | count 4, pad 4 | pad 16
+    const size_t ne = (size_t)(n > 0 ? n : 1), slice = up256(ne);
+    Carve k; const size_t o_img = k.take<float>(2 * ne, 8), o_obj = k.take<float>(3 * ne, 8), o_hdr = k.take<uint8_t>(HDR, 16), o_inl = k.take<uint8_t>(G * slice, 1), o_dec = k.take<uint8_t>(G * slice, 1),
+                 o_le = k.take<uint8_t>(G * slice * k_pnp_edge_bytes()), o_err = k.take<double2>(G * slice);
+    const size_t up = o_hdr + HDR, down = HDR - H_TOUT + (size_t)n;            // download: [T out | xfail | count | pad][inl slice 0: n bytes]
+    Carve hk; const size_t h_up = hk.take<uint8_t>(up), h_down = hk.take<uint8_t>(down);
+    int r = ensure_scratch(c, k.off); if (r) return r;         // (slice is a multiple of 256, so the last region, G * slice * 16 bytes, ends on one)
+    r = ensure_pinned(c, hk.end()); if (r) return r;
     if (G > 1) {
         if (!c->d_pnp_xchg) { if (c->d_pnp_xchg.alloc_bytes(c, k_pnp_xchg_bytes())) return SSM_E_HIP; c->pnp_epoch = 0; }
         if (c->pnp_epoch == 0) HIPCHK(c, hipMemsetAsync(c->d_pnp_xchg, 0, k_pnp_xchg_bytes(), c->main.stream));
     }
     uint8_t* p = (uint8_t*)c->d_scratch; hipStream_t s = c->main.stream;
-    uint8_t* hu = c->h_pinned; uint8_t* hd = c->h_pinned + al(up);
+    uint8_t* hu = c->h_pinned + h_up; uint8_t* hd = c->h_pinned + h_down;
     if (n) { memcpy(hu + o_img, img, (size_t)n * 8); memcpy(hu + o_obj, obj, (size_t)n * 12); }
     memset(hu + o_hdr, 0, HDR); memcpy(hu + o_hdr, T, 128);
-    { const char* tv = getenv("SSM_PNP_TEST_TIMEOUT"); if (G > 1 && tv && atoi(tv) != 0) { const unsigned one = 1; memcpy(hu + o_hdr + 256, &one, 4); } }      // tests: the time-out word set from the start -> the one-block retry
+    { const char* tv = getenv("SSM_PNP_TEST_TIMEOUT"); if (G > 1 && tv && atoi(tv) != 0) { const unsigned one = 1; memcpy(hu + o_hdr + H_XFAIL, &one, 4); } }      // tests: the time-out word set from the start -> the one-block retry
     HIPCHK(c, hipMemcpyAsync(p, hu, up, hipMemcpyHostToDevice, s));
     PnpSolveArgs a; a.img = (const float*)(p + o_img); a.obj = (const float*)(p + o_obj); a.n = n;
     a.cam.fx = cam[0]; a.cam.fy = cam[1]; a.cam.cx = cam[2]; a.cam.cy = cam[3];
-    a.T = (double*)(p + o_hdr); a.inl = p + o_inl; a.dec = p + o_dec; a.ledges = (LEdge*)(p + o_le); a.err = (double2*)(p + o_err); a.n_inliers = (int32_t*)(p + o_hdr + 264); a.edges_in_lds = 0;
-    a.blocks = G; a.slice = slice; a.xchg = c->d_pnp_xchg; a.xfail = reinterpret_cast<unsigned*>(p + o_hdr + 256);
+    a.T = (double*)(p + o_hdr); a.inl = p + o_inl; a.dec = p + o_dec; a.ledges = (LEdge*)(p + o_le); a.err = (double2*)(p + o_err); a.n_inliers = (int32_t*)(p + o_hdr + H_COUNT); a.edges_in_lds = 0;
+    a.blocks = G; a.slice = slice; a.xchg = c->d_pnp_xchg; a.xfail = reinterpret_cast<unsigned*>(p + o_hdr + H_XFAIL);
     a.seq_base = (unsigned)c->pnp_epoch << 20;                  // a solve makes a few thousand passes at most; the ring is zeroed again when the epoch wraps
     if (G > 1) c->pnp_epoch = (c->pnp_epoch + 1) & 4095;
-    if (c->profiling) { c->recs.clear(); c->pool_used = 0; }
+    prof_reset(c);
     prof_begin(c, s, "pnp");
     HIPCHK(c, k_pnp_solve(a, s));
     prof_end(c, s);
-    HIPCHK(c, hipMemcpyAsync(hd, p + o_hdr + 128, down, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(hd, p + o_hdr + H_TOUT, down, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     unsigned failed = 0; int32_t m = 0;
-    memcpy(&failed, hd + 128, 4); memcpy(&m, hd + 136, 4);
+    memcpy(&failed, hd + H_XFAIL - H_TOUT, 4); memcpy(&m, hd + H_COUNT - H_TOUT, 4);
     if (G > 1 && failed) { c->pnp_epoch = 0; return 1; }        // an exchange of the cluster timed out: nothing of this attempt is used (and the ring starts clean next time)
     memcpy(T, hd, 128);
-    if (inliers && n) memcpy(inliers, hd + HDR - 128, (size_t)n);
+    if (inliers && n) memcpy(inliers, hd + HDR - H_TOUT, (size_t)n);
     *n_inliers = m;
     if (success) *success = n > min_inliers;                   // pnp.cpp:115 tests the flag vector's LENGTH (quirk 14)
     return SSM_OK;

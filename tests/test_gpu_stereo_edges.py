@@ -7,11 +7,19 @@
   ssm_quad_track and a batch of ssm_stereo_seq_process;
 * the SGBM post stages (sgbm_post.inc) through ssm_debug_sgbm_post: the int16 3x3 median and the two-level union-find of filterSpeckles on combs,
   spirals, serpentines, components of exactly maxSize, maxDiff boundaries, int16 extremes and dense random maps, every map as several frames of one
-  launch (all frames must agree), and stacked frames that would join if their forests leaked into each other."""
+  launch (all frames must agree), and stacked frames that would join if their forests leaked into each other;
+* the per-call functions that carve one scratch / pinned buffer into regions, interleaved on one context so that every layout is built small, large and
+  small again and each buffer grows under one function and is carved again by the next."""
 import numpy as np
 import pytest
 import stereo_ref as R
 from test_gpu_stereo_seq import stereo_sequence, reference_walk, check_against_walk, run_seq
+from conftest import rand_desc
+from test_gpu_quad import stereo_pair as quad_images
+from test_gpu_pnp import KCAM, _check as check_pnp
+from test_pnp import _case as pnp_case
+from test_sgbm import stereo_pair as sgbm_pair
+from test_vo import scene as vo_scene, F, CU, CV, BASE
 
 pytestmark = pytest.mark.gpu
 
@@ -114,3 +122,53 @@ def test_sgbm_post_sizes(ctx, oracle, w, h):
         out = ctx.debug_sgbm_post(maps, 3, R.NV, ms, md)
         for i, m in enumerate(maps):
             assert np.array_equal(out[i], _post_expected(oracle, m, 3, R.NV, ms, md)), (ms, md, i)
+
+
+def test_per_call_layouts_small_large_small(oracle):
+    """window_match, vo_estimate, pnp_solve, debug_sgbm_post, sgbm and quad_track take their regions from the context's one scratch buffer and one pinned area
+    (and the pair calls from one device staging buffer).  Three rounds on a fresh context -- small, large, small again -- so that each buffer is allocated by one
+    function, grown by another and carved again by every one of them at a size below what it holds; every result is the oracle's, bit for bit."""
+    import semantic_slam_mapping_amd as ssm
+    rng = np.random.default_rng(77)
+    vals = np.array([R.NV, 100, 101, 103, 110, -32768, 32767], np.int16)
+
+    def window(c, n1, n2):
+        k1 = rng.uniform(0, 100, (n1, 2)).astype(np.float32); k2 = rng.uniform(0, 100, (n2, 2)).astype(np.float32)
+        d1 = rand_desc(rng, n1); d2 = (d1[rng.integers(0, n1, n2)] ^ (rng.random((n2, 32)) < 0.02).astype(np.uint8)) if n2 else np.zeros((0, 32), np.uint8)
+        g = c.window_match(k1, d1, k2, d2, 20, 20, 80.0)
+        assert len(g) == n1 and g.tobytes() == oracle.window_match(k1, d1, k2, d2, 20, 20, 80.0).tobytes(), (n1, n2)
+
+    def vo(c, n, iters):
+        m = vo_scene(n, n // 5, 300 + n, noise=0.2 if n > 6 else 0.0)
+        smp = oracle.vo_samples(oracle.rand_state(0), n, iters)
+        ok, tr, inl = oracle.vo_estimate(m, oracle.vo_params(F, CU, CV, BASE, 2.0, True), smp)
+        gok, gtr, ginl = c.vo_estimate(m, F, CU, CV, BASE, smp, 2.0, True)
+        assert gok == ok and np.array_equal(ginl, inl) and gtr.tobytes() == tr.tobytes(), (n, iters)
+
+    def pnp(c, n):
+        img, obj, _ = pnp_case(40 + n % 7, n, 6, 7, 0.5)
+        check_pnp(c, oracle, img, obj, np.eye(4))
+
+    def post(c, n, h, w):
+        maps = rng.choice(vals, size=(n, h, w), p=[0.1, 0.3, 0.25, 0.15, 0.1, 0.05, 0.05])
+        out = c.debug_sgbm_post(maps, 3, R.NV, 5, 1)
+        for i, m in enumerate(maps):
+            assert np.array_equal(out[i], _post_expected(oracle, m, 3, R.NV, 5, 1)), (n, h, w, i)
+
+    def sgbm(c, h, w, nd, sad, seed):
+        l, r, _ = sgbm_pair(h, w, seed, planes=((nd // 4, None), (nd // 2 + 3, (0.3, 0.75, 0.3, 0.7))), noise=3)
+        assert np.array_equal(c.sgbm(l, r, c.sgbm_params(numberOfDisparities=nd, SADWindowSize=sad)), oracle.sgbm(l, r, oracle.sgbm_params(num_disp=nd, sad=sad))), (h, w)
+
+    def quad(c):
+        ims = quad_images(oracle, 64, 48, 5, (2, 1))
+        g = c.quad_track(*ims); o = oracle.quad_track(*ims)
+        assert len(o) > 0 and len(g) == len(o) and g.tobytes() == o.tobytes()
+
+    c = ssm.Context(0, width=640, height=480, max_batch=1)
+    try:
+        for wm, von, pn, pm, sg in (((1, 0), (6, 1), 0, (1, 7, 5), (40, 120, 16, 5, 6)),
+                                    ((700, 650), (900, 50), 3000, (3, 40, 120), (61, 333, 80, 11, 9)),
+                                    ((3, 5), (6, 1), 1, (1, 7, 5), (40, 120, 16, 5, 6))):
+            window(c, *wm); vo(c, *von); pnp(c, pn); post(c, *pm); sgbm(c, *sg); quad(c)
+    finally:
+        c.close()

@@ -179,7 +179,8 @@ def test_gpu_sgbm_form_is_a_context_setting(oracle):
 def test_gpu_sgbm_sweep_timeout_falls_back_to_form_1(oracle, tmp_path, hook):
     """cv::StereoSGBM cannot fail (src/stereo.cpp:11-30).  The sweep of form 2 can time out in a strip hand-off: SSM_SGBM_TEST_TIMEOUT=1 makes every sweep report one, =2
     makes the occupancy check in front of the sweep say that its strips cannot all be resident.  Either way the call must return the oracle's disparities (repeated / run
-    in form 1) -- per-pair entry points and the batched path (whose failure is only known at ssm_sync), there with a note in ssm_last_error"""
+    in form 1) -- both per-pair entry points (ssm_sgbm and ssm_stereo_depth share one repeat loop, sgbm_pair) and the batched path (whose failure is only known
+    at ssm_sync), there with a note in ssm_last_error"""
     import os, subprocess, sys
     h, w, n = 61, 333, 5
     pairs = [stereo_pair(h, w, 20 + k, planes=((20, None), (43, (0.3, 0.75, 0.3, 0.7))), noise=3) for k in range(n)]
@@ -189,6 +190,8 @@ def test_gpu_sgbm_sweep_timeout_falls_back_to_form_1(oracle, tmp_path, hook):
             f"g = np.load(r'{tmp_path / 'in.npz'}'); L, R = g['L'], g['R']; n, h, w = L.shape\n"
             "c = ssm.Context(0, width=640, height=480, max_batch=2)\n"
             "out = {'pair': c.sgbm(L[0], R[0]), 'note_pair': np.array(c.last_error())}\n"
+            "out['pd_depth'], out['pd_disp'] = c.stereo_depth(L[0], R[0], baseline=0.5, cu=160.0, cv=30.0, f=700.0, roix=20.0, roiy=5.0, roiz=40.0, scale=1000.0)\n"
+            "out['note_depth'] = np.array(c.last_error())\n"
             "dl = c.dev_alloc(L.nbytes); dr = c.dev_alloc(R.nbytes); c.h2d(dl, L); c.h2d(dr, R)\n"
             "o = c.stereo_seq_process(dl, dr, n, w, h, stages=2, baseline=0.5, cu=160.0, cv=30.0, f=700.0, roix=20.0, roiy=5.0, roiz=40.0, scale=1000.0)\n"
             "c.sync(); out['note_seq'] = np.array(c.last_error())\n"
@@ -200,11 +203,14 @@ def test_gpu_sgbm_sweep_timeout_falls_back_to_form_1(oracle, tmp_path, hook):
     got = np.load(tmp_path / "out.npz")
     po = oracle.sgbm_params()
     assert np.array_equal(got["pair"], oracle.sgbm(L[0], R[0], po))
+    assert np.array_equal(got["pd_disp"], oracle.sgbm(L[0], R[0], po))
+    assert np.array_equal(got["pd_depth"], oracle.disparity_to_depth(oracle.sgbm(L[0], R[0], po), 0.5, 160.0, 30.0, 700.0, 20.0, 5.0, 40.0, 1000.0))
     for k in range(n):
         d = oracle.sgbm(L[k], R[k], po)
         assert np.array_equal(got["disp"][k], d), k
         assert np.array_equal(got["depth"][k], oracle.disparity_to_depth(d, 0.5, 160.0, 30.0, 700.0, 20.0, 5.0, 40.0, 1000.0)), k
     if hook == "1":       # a reported time-out leaves a note (the call itself succeeds); the occupancy check chooses form 1 silently
         assert "form 1" in str(got["note_pair"]) and "form 1" in str(got["note_seq"]) and "3 sub-batch" in str(got["note_seq"])
+        assert "form 1" in str(got["note_depth"])
     else:
         assert str(got["note_seq"]) == ""
