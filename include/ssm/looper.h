@@ -20,6 +20,34 @@ inline ssm_vocab* load_vocab(const ParameterReader& para) {
     return v;
 }
 }  // namespace looper_detail
+// Vocabulary training (not in the reference, which loads ORBvoc.txt): a hierarchical k-majority tree from the descriptors of a sequence's
+// key-frames (desc_sets[f]: 32 bytes per descriptor of key-frame f), with looper_train_k / looper_train_L / looper_train_iters (10 / 5 / 32), written to
+// `file` in the text format looper_vocab_file names.  dev: the device trainer of that context; null: the host function -- the same bytes either way.
+struct TrainedVocabulary { int nodes = 0, words = 0; uint64_t fnv = 0; ssm_vocab_train_report report{}; };      // fnv: FNV-1a over the exported parent, is_leaf, descriptor and weight arrays
+inline TrainedVocabulary trainVocabulary(const ParameterReader& para, const vector<vector<uint8_t>>& desc_sets, ssm::Device* dev, const string& file) {
+    ssm_vocab_train_params p; ssm_vocab_train_params_default(&p);
+    p.k = para.getData<int>("looper_train_k", p.k); p.L = para.getData<int>("looper_train_L", p.L); p.max_iters = para.getData<int>("looper_train_iters", p.max_iters);
+    vector<uint8_t> all; vector<int32_t> npf;
+    for (const vector<uint8_t>& d : desc_sets) { npf.push_back((int32_t)(d.size() / 32)); all.insert(all.end(), d.begin(), d.begin() + (d.size() / 32) * 32); }
+    TrainedVocabulary tv; ssm_vocab* v = nullptr;
+    if (all.empty()) throw ssm::DeviceError(SSM_E_INVAL, "trainVocabulary: no descriptors (no key-frame was accepted)");
+    const int rc = dev ? ssm_vocab_train(dev->ctx(), all.data(), npf.data(), (int)npf.size(), &p, nullptr, &tv.report, &v)
+                       : ssm_vocab_train_host(all.data(), npf.data(), (int)npf.size(), &p, nullptr, &tv.report, &v);
+    if (rc != SSM_OK) throw ssm::DeviceError(rc, string("trainVocabulary: ") + ssm_last_error(dev ? dev->ctx() : nullptr));
+    int32_t info[6]; ssm_vocab_info(v, info);
+    tv.nodes = info[2]; tv.words = info[3];
+    const int n = tv.nodes - 1;
+    vector<int32_t> parent((size_t)n); vector<uint8_t> leaf((size_t)n), desc((size_t)n * 32); vector<double> weight((size_t)n);
+    int rc2 = ssm_vocab_export(v, parent.data(), leaf.data(), desc.data(), weight.data(), n);
+    uint64_t h = 0xCBF29CE484222325ull;
+    auto eat = [&h](const void* q, size_t bytes) { const unsigned char* b = (const unsigned char*)q; for (size_t i = 0; i < bytes; i++) { h ^= b[i]; h *= 0x100000001B3ull; } };
+    eat(parent.data(), (size_t)n * 4); eat(leaf.data(), (size_t)n); eat(desc.data(), (size_t)n * 32); eat(weight.data(), (size_t)n * 8);
+    tv.fnv = h;
+    if (rc2 == SSM_OK) rc2 = ssm_vocab_save_text(v, file.c_str());
+    ssm_vocab_destroy(v);
+    if (rc2 != SSM_OK) throw ssm::DeviceError(rc2, string("trainVocabulary: ") + ssm_last_error(nullptr));
+    return tv;
+}
 class Looper {
 public:
     Looper(const ParameterReader& para) : parameterReader(para) {

@@ -341,6 +341,35 @@ int  ssm_vocab_transform_host(const ssm_vocab* v, const uint8_t* desc, int n, in
                               int32_t* ids, double* vals, int cap, int* n_out);
 /* vocab.score(v1, v2): v1 = the query frame, v2 = the stored frame (the sum runs over v2's entries: looper_core.h) */
 int  ssm_bow_score_host(const int32_t* ids1, const double* v1, int n1, const int32_t* ids2, const double* v2, int n2, double* score);
+/* the arrays ssm_vocab_create / the text file take, in the order the vocabulary was given (node i has id i + 1): parent, is_leaf: cap entries, desc: cap x
+ * 32, weight: cap (0.0 for inner nodes); any of them may be NULL.  cap < nodes - 1: SSM_E_CAPACITY.  ssm_vocab_create on them gives an equal vocabulary */
+int  ssm_vocab_export(const ssm_vocab* v, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight, int cap);
+/* DBoW2's text format, as ssm_vocab_load_text reads it; weights with 17 significant digits: load(save(v)) exports the same bits */
+int  ssm_vocab_save_text(const ssm_vocab* v, const char* path);
+/* VOCABULARY TRAINING (include/ssm/vocab_train_core.h): a hierarchical k-majority tree over the descriptors of F frames -- desc: N x 32, frame
+ * 0's first; n_per_frame[F]: counts (zeros allowed) that sum to N, 1 <= N <= 2^26.  Farthest-point seeding, nearest-centre assignment (lowest centre on ties),
+ * bitwise-majority centres (a tie gives 1), at most max_iters passes per node, breadth-first ids, weight = log(F / frames that hold the word).  Integers only,
+ * so the host function and the device path give the same vocabulary, word_of_feature (N entries, may be NULL: the word every training descriptor was trained
+ * into, which is also where ssm_vocab_transform_host puts it) and report, byte for byte.  Bad parameters: SSM_E_INVAL. */
+typedef struct { int32_t k, L, max_iters; } ssm_vocab_train_params;                    /* 2 .. 20, 1 .. 10, >= 1 */
+typedef struct {
+    int32_t nodes, words;            /* nodes incl. the root */
+    int32_t levels;                  /* the deepest level that holds a node */
+    int32_t capped_nodes;            /* nodes whose max_iters-th pass still changed an assignment */
+    int32_t passes[10];              /* per level l (the nodes of level l being split): the assignment passes after seeding, the maximum over its nodes */
+} ssm_vocab_train_report;
+void ssm_vocab_train_params_default(ssm_vocab_train_params* p);                        /* 10, 5, 32 */
+int  ssm_vocab_train_host(const uint8_t* desc, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* params,
+                          int32_t* word_of_feature, ssm_vocab_train_report* report, ssm_vocab** out);
+int  ssm_vocab_train(ssm_ctx* ctx, const uint8_t* desc, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* params,
+                     int32_t* word_of_feature, ssm_vocab_train_report* report, ssm_vocab** out);
+/* ONE pass of step 4 (centre update, then assignment) on a state the caller makes up: descriptor i belongs to node node_of[i] (non-decreasing, < n_nodes)
+ * and cluster cluster_of[i] (< k); centres: n_nodes x k x 32, in and out (an empty cluster keeps its row); assign_out[i]: the new cluster.  ctx NULL: the
+ * host function.  Tests reach emptied clusters and constructed ties this way */
+int  ssm_debug_vocab_kmajority(ssm_ctx* ctx, const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k,
+                               uint8_t* centres, int32_t* assign_out);
+/* wall time of the last ssm_vocab_train on this context per level (upload / the final word pass are in total_ms only): scripts/vocab_train_bench.py */
+int  ssm_debug_vocab_train_times(ssm_ctx* ctx, double level_ms[10], double* total_ms);
 /* A LOOPER belongs to a context: the vocabulary tree (re-numbered breadth-first, 32-byte descriptor rows) and the database of the added frames' vectors
  * (CSR: offsets, word ids, f64 values, frame ids; grows by doubling) live in the context's device memory.  ssm_looper_create uploads and waits: v may be
  * destroyed afterwards.  Entries are numbered in the order they were added.  A frame holds at most ssm_orb_capacity descriptors (at most 4096). */

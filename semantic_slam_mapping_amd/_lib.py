@@ -71,6 +71,14 @@ class UvdInfo(C.Structure):
                [(n, C.c_int32) for n in ("n_seeds", "n_masks_found", "n_masks_merged", "n_masks_kept", "n_moving")] + [("line", C.c_float * 4), ("pad", C.c_int32)]
 
 
+class VocabTrainParams(C.Structure):
+    _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iters", C.c_int32)]
+
+
+class VocabTrainReport(C.Structure):
+    _fields_ = [("nodes", C.c_int32), ("words", C.c_int32), ("levels", C.c_int32), ("capped_nodes", C.c_int32), ("passes", C.c_int32 * 10)]
+
+
 # every symbol include/ssm_hip.h declares: name -> (restype, argtypes)
 _P, _I, _D, _F, _U64, _SZ = C.c_void_p, C.c_int, C.c_double, C.c_float, C.c_uint64, C.c_size_t
 SYMBOLS = {
@@ -141,6 +149,13 @@ SYMBOLS = {
     "ssm_vocab_info": (_I, [_P, C.POINTER(C.c_int32 * 6)]),
     "ssm_vocab_transform_host": (_I, [_P, _P, _I, _P, _P, _P, _I, C.POINTER(_I)]),
     "ssm_bow_score_host": (_I, [_P, _P, _I, _P, _P, _I, C.POINTER(_D)]),
+    "ssm_vocab_export": (_I, [_P, _P, _P, _P, _P, _I]),
+    "ssm_vocab_save_text": (_I, [_P, C.c_char_p]),
+    "ssm_vocab_train_params_default": (None, [C.POINTER(VocabTrainParams)]),
+    "ssm_vocab_train_host": (_I, [_P, _P, _I, C.POINTER(VocabTrainParams), _P, C.POINTER(VocabTrainReport), C.POINTER(_P)]),
+    "ssm_vocab_train": (_I, [_P, _P, _P, _I, C.POINTER(VocabTrainParams), _P, C.POINTER(VocabTrainReport), C.POINTER(_P)]),
+    "ssm_debug_vocab_kmajority": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P]),
+    "ssm_debug_vocab_train_times": (_I, [_P, C.POINTER(C.c_double * 10), C.POINTER(_D)]),
     "ssm_looper_create": (_I, [_P, _P, C.POINTER(_P)]),
     "ssm_looper_destroy": (None, [_P]),
     "ssm_looper_clear": (_I, [_P]),

@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -203,6 +203,43 @@ class Vocabulary:
             raise SsmError(rc, (lib.ssm_last_error(None) or b"").decode())
         return cls(_handle=h)
 
+    @classmethod
+    def train(cls, desc_sets, k=10, L=5, max_iters=32, ctx=None):
+        """A vocabulary from the descriptor sets of a sequence (one n_f x 32 array per frame; empty ones allowed): the hierarchical k-majority tree of
+        DESIGN.md s.13.  ctx None: the host function; else the device trainer of that context -- the same bytes either way.  The result carries
+        `report` (nodes, words, levels, capped_nodes, passes per level) and `word_of_feature` (the word each training descriptor was trained into)."""
+        lib = _lib.load()
+        sets = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in desc_sets]
+        npf = np.array([len(d) for d in sets], np.int32)
+        desc = np.ascontiguousarray(np.concatenate(sets)) if sets else np.zeros((0, 32), np.uint8)
+        p = VocabTrainParams(int(k), int(L), int(max_iters)); rep = VocabTrainReport(); h = C.c_void_p()
+        wof = np.zeros(max(len(desc), 1), np.int32)
+        if ctx is None:
+            rc = lib.ssm_vocab_train_host(_ptr(desc), _ptr(npf), len(npf), C.byref(p), _ptr(wof), C.byref(rep), C.byref(h))
+        else:
+            rc = lib.ssm_vocab_train(ctx.h, _ptr(desc), _ptr(npf), len(npf), C.byref(p), _ptr(wof), C.byref(rep), C.byref(h))
+        if rc != 0:
+            raise SsmError(rc, (lib.ssm_last_error(ctx.h if ctx is not None else None) or b"").decode())
+        v = cls(_handle=h)
+        v.report = {"nodes": rep.nodes, "words": rep.words, "levels": rep.levels, "capped_nodes": rep.capped_nodes, "passes": [int(x) for x in rep.passes]}
+        v.word_of_feature = wof[:len(desc)]
+        return v
+
+    def arrays(self):
+        """-> (parent, is_leaf, desc, weight) as from_arrays takes them: ssm_vocab_export"""
+        n = self.nodes - 1
+        parent = np.zeros(n, np.int32); leaf = np.zeros(n, np.uint8); desc = np.zeros((n, 32), np.uint8); weight = np.zeros(n, np.float64)
+        rc = self.lib.ssm_vocab_export(self.h, _ptr(parent), _ptr(leaf), _ptr(desc), _ptr(weight), n)
+        if rc != 0:
+            raise SsmError(rc, "ssm_vocab_export")
+        return parent, leaf, desc, weight
+
+    def save(self, path):
+        """DBoW2's text format, as Vocabulary(path) reads it; the weights come back bit for bit"""
+        rc = self.lib.ssm_vocab_save_text(self.h, str(path).encode())
+        if rc != 0:
+            raise SsmError(rc, (self.lib.ssm_last_error(None) or b"").decode())
+
     def transform(self, desc, cap=None):
         """vocab.transform on the host -> (word id of every feature, vector ids, vector values)"""
         desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
@@ -232,6 +269,19 @@ class Vocabulary:
             self.close()
         except Exception:
             pass
+
+
+def vocab_kmajority(desc, node_of, cluster_of, centres, ctx=None):
+    """ssm_debug_vocab_kmajority: one k-majority pass (centre update, then assignment) on a made-up state.  centres: n_nodes x k x 32 -> (new centres, new clusters)"""
+    lib = _lib.load()
+    desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32); node_of = np.ascontiguousarray(node_of, np.int32); cluster_of = np.ascontiguousarray(cluster_of, np.int32)
+    centres = np.array(centres, np.uint8, order="C"); n_nodes, k = centres.shape[0], centres.shape[1]
+    assert centres.shape == (n_nodes, k, 32) and len(node_of) == len(cluster_of) == len(desc)
+    out = np.zeros(max(len(desc), 1), np.int32)
+    rc = lib.ssm_debug_vocab_kmajority(ctx.h if ctx is not None else None, _ptr(desc), len(desc), _ptr(node_of), _ptr(cluster_of), n_nodes, k, _ptr(centres), _ptr(out))
+    if rc != 0:
+        raise SsmError(rc, "ssm_debug_vocab_kmajority")
+    return centres, out[:len(desc)]
 
 
 class Looper:

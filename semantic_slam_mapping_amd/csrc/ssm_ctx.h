@@ -237,6 +237,7 @@ struct ssm_ctx {
     // quad matcher
     std::unique_ptr<StereoState> stereo; int stereo_B = 16; int stereo_sgbm_streams = 2;      // ssm_config.sgbm_streams 
     int sgbm_form_cfg = 0; long sgbm_fallbacks = 0;                                              // ssm_config.sgbm_form; sub-batches repeated in form 1 after a sweep time-out
+    double vt_level_ms[10] = {0}, vt_total_ms = -1.0;      // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;
     PinBuf<uint8_t> h_pinned;          // host staging for the image-sized host-pointer calls (pageable hipMemcpy is ~1 GB/s)

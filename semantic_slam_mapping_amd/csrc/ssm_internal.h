@@ -257,6 +257,37 @@ hipError_t k_bow_score(const int32_t* offsets, const int32_t* db_ids, const doub
 hipError_t k_bow_emit(const int32_t* frame_ids, const double* scores, const int32_t* counts, int first, int nq, int against, int row, double min_score, int min_interval,
                       int32_t* pairs, double* out_scores, int cap, int32_t* hdr /* [1] = the candidate count */, hipStream_t s);
 
+// vocabulary training (kernels_vocab_train.hip; the arithmetic is include/ssm/vocab_train_core.h): ONE LEVEL of the tree under construction.  A POSITION p holds
+// the input index perm[p] and the level's node nodeof[p]; a node's members are the positions start[v] .. start[v + 1], in ascending input index.  A CHUNK is
+// VT_CHUNK consecutive positions = one block.  Every kernel is one thread per position (or per bit of a chunk); no loop runs longer than k or VT_CHUNK.
+#define VT_CHUNK 256
+struct VtLevel {
+    const uint32_t* desc;          // N x 8, input order
+    int N, k, nn;                  // positions, centres per node at most, nodes of this level
+    int32_t* perm; int32_t* nodeof; const int32_t* start /* nn + 1 */;
+    int32_t* m; int32_t* a;        // per position: distance to the nearest seed so far; cluster
+    uint32_t* centres;             // nn x k x 8
+    int32_t* ncent;                // nn: centres seeded
+    uint32_t* gcnt;                // per straddling node (one that crosses a chunk boundary; slot = the chunk it starts in): k x 257 (ones per bit, then the count); all 0 between passes
+    int32_t* changed_at;           // nn: the last pass that changed an assignment of the node
+    int32_t* flag;                 // [0]: an assignment changed in this pass
+};
+// seeding round r (0 .. k - 1): centre r of every node that has not stopped (keys_in: the argmax of round r - 1; null for r = 0) -> m, a, centres, ncent, and the
+// argmax for centre r + 1 into keys_out (preset to 0; null for the last round)
+hipError_t k_vt_seed(const VtLevel& L, int r, const unsigned long long* keys_in, unsigned long long* keys_out, hipStream_t s);
+// centre update: per chunk the ones of every (node, cluster, bit); nodes inside the chunk get their new centres at once, straddling nodes add into gcnt and
+// k_vt_finish (strad: their ids, ns of them) makes their centres and zeroes gcnt again
+hipError_t k_vt_count(const VtLevel& L, hipStream_t s);
+hipError_t k_vt_finish(const VtLevel& L, const int32_t* strad, int ns, hipStream_t s);
+hipError_t k_vt_assign(const VtLevel& L, int pass, hipStream_t s);
+// stable partition of every node by cluster: hist (chunks x k) = members of cluster j in the chunk; with its exclusive prefix over the chunks (prefix), rank[p] =
+// the positions before p that hold cluster a[p] and noderank (nn x k) the same for every cluster at each node's first position; then the move to
+// dest[v k + a] + (rank - noderank[v k + a]) with the child node child[v k + a]
+hipError_t k_vt_hist(const VtLevel& L, int32_t* hist, hipStream_t s);
+hipError_t k_vt_rank(const VtLevel& L, const int32_t* prefix, int32_t* rank, int32_t* noderank, hipStream_t s);
+hipError_t k_vt_scatter(const VtLevel& L, const int32_t* rank, const int32_t* noderank, const int32_t* dest, const int32_t* child, int32_t* perm_out, int32_t* nodeof_out, hipStream_t s);
+hipError_t k_vt_leaves(const VtLevel& L, const int32_t* leaf_id /* nn */, int32_t* leaf_of_feature /* N, input order */, hipStream_t s);
+
 // UVDisparity (kernels_uvd.hip; the arithmetic is include/ssm/uvd_core.h): n packed frames of w x h.  v_dis: n x h x 256 u8 rows of the V-disparity image,
 // maxmin: n x (max, min) of the raw disparities, preset to (INT_MIN, INT_MAX).  K: n FrameK.  u_raw / u_adj / uni: n x 256 x w (u_rows rows of each frame used).
 // coords: n x cap (u, v) of the matches, probes: n x cap (roi << 16 | the disparity's 16 bits).  counts: n, preset to 0

@@ -13,6 +13,7 @@ struct ssm_vocab {
     std::vector<int32_t> first_child, n_child, word;      // per node, breadth-first numbering (node 0 = the root)
     std::vector<uint32_t> desc;                           // per node, 8 words
     std::vector<double> weight;                           // per word id
+    std::vector<int32_t> file_id;                         // per node: the id it was given under (ssm_vocab_export writes that order back)
     int max_depth = 0;
     ssm_bow::Tree tree() const
     {
@@ -58,7 +59,41 @@ extern "C" int ssm_vocab_create(int k, int L, int scoring, int weighting, const 
             if (word_of_id[id] >= 0) v->weight[word_of_id[id]] = weight[id - 1];
         }
     }
+    v->file_id = order;
     *out = v;
+    return SSM_OK;
+}
+extern "C" int ssm_vocab_export(const ssm_vocab* v, int32_t* parent, uint8_t* is_leaf, uint8_t* desc, double* weight, int cap)
+{
+    if (!v || cap < 0) return SSM_E_INVAL;
+    const int nn = (int)v->n_child.size();
+    if (cap < nn - 1) return SSM_E_CAPACITY;
+    for (int at = 0; at < nn; at++) {
+        for (int c = 0; c < v->n_child[at]; c++) if (parent) parent[v->file_id[v->first_child[at] + c] - 1] = v->file_id[at];
+        if (at == 0) continue;
+        const int i = v->file_id[at] - 1;
+        if (is_leaf) is_leaf[i] = v->n_child[at] == 0;
+        if (desc) memcpy(desc + (size_t)i * 32, &v->desc[(size_t)at * 8], 32);
+        if (weight) weight[i] = v->word[at] >= 0 ? v->weight[v->word[at]] : 0.0;
+    }
+    return SSM_OK;
+}
+extern "C" int ssm_vocab_save_text(const ssm_vocab* v, const char* path)
+{
+    if (!v || !path) return vocab_fail("null argument");
+    const int n = (int)v->n_child.size() - 1;
+    std::vector<int32_t> parent((size_t)n); std::vector<uint8_t> leaf((size_t)n), desc((size_t)n * 32); std::vector<double> weight((size_t)n);
+    { const int rc = ssm_vocab_export(v, parent.data(), leaf.data(), desc.data(), weight.data(), n); if (rc) return rc; }
+    FILE* f = fopen(path, "wb");
+    if (!f) return vocab_fail(std::string("vocabulary: cannot write ") + path);
+    fprintf(f, "%d %d %d %d\n", v->k, v->L, v->scoring, v->weighting);
+    for (int i = 0; i < n; i++) {
+        fprintf(f, "%d %d", parent[i], (int)leaf[i]);
+        for (int b = 0; b < 32; b++) fprintf(f, " %d", (int)desc[(size_t)i * 32 + b]);
+        fprintf(f, " %.17g\n", weight[i]);                       // 17 significant digits give every double back
+    }
+    const bool bad = ferror(f) != 0;
+    if (fclose(f) != 0 || bad) return vocab_fail(std::string("vocabulary: write error on ") + path);
     return SSM_OK;
 }
 extern "C" int ssm_vocab_load_text(const char* path, ssm_vocab** out)

@@ -12,6 +12,10 @@
 // looper_vocab_file) right after tryInsertKeyFrame accepted it; with --batched the key-frames of a chunk are added in bulk from the chunk's device descriptors and
 // queried in one call (BatchLooper).  The summary line then ends with `loop_candidates N loop_fnv H` (FNV-1a over frame id, candidate id and the score's bytes, in
 // order: the same in both modes); loops_output=<file> gets one line per candidate.  Without the flag nothing of this runs and no output changes.
+// `exp_mapping <parameters> --train-vocab FILE` (or looper_train_vocab=FILE): the ORB descriptors of every accepted key-frame are collected (with --batched they
+// come down from the chunk's device tables) and after the sequence a vocabulary is trained from them (trainVocabulary in include/ssm/looper.h: looper_train_k /
+// looper_train_L / looper_train_iters) and written to FILE, which a later run names as looper_vocab_file.  The summary line then ends with `vocab_nodes N
+// vocab_words W vocab_fnv H` (FNV-1a over the exported arrays: the same in both modes).  The bulk stereo tracker has no descriptors: ignored there.
 //
 // `exp_mapping <parameters> --moving` (or uv_disparity=1; needs tracker_mode=stereo): the triangulate10D / UVDisparity block of Tracker::estimateVO (reference
 // src/track.cpp:66-79; include/ssm/uvdisparity.hpp) runs after every successful stereo VO and fills the frame's moving_mask, roi_mask and ground_mask;
@@ -101,6 +105,8 @@ int main(int argc, char** argv)
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--optimize") optimize = true;
     if (optimize) { parameterReader.set("pose_graph_optimize", "1"); if (!parameterReader.getData<string>("looper_vocab_file", string("")).empty()) loops = true; }
     const int step_frames = parameterReader.getData<int>("pose_graph_step_frames", 0);
+    string train_vocab = parameterReader.getData<string>("looper_train_vocab", string(""));
+    for (int i = 2; i + 1 < argc; i++) if (string(argv[i]) == "--train-vocab") train_vocab = argv[i + 1];
     bool moving = parameterReader.getData<int>("uv_disparity", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--moving") moving = true;
     if (moving) {
@@ -188,6 +194,9 @@ int main(int argc, char** argv)
         Trajectory traj(parameterReader.getData<string>("trajectory_output", string("")));
         LoopLog loop_log(loops ? parameterReader.getData<string>("loops_output", string("")) : string(""));
         if (loops && batched_stereo) cerr << "exp_mapping: --loops needs ORB descriptors; the bulk stereo tracker computes none (ignored)" << endl;
+        if (!train_vocab.empty() && batched_stereo) { cerr << "exp_mapping: --train-vocab needs ORB descriptors; the bulk stereo tracker computes none (ignored)" << endl; train_vocab.clear(); }
+        vector<vector<uint8_t>> train_sets;                    // --train-vocab: the descriptors of every accepted key-frame, in key-frame order
+        TrainedVocabulary trained;
         // `sequence_length` = L > 0: the stream is a concatenation of independent sequences of L frames (synthetic_rigid streams): the tracker starts over at every
         // multiple of L.  `timing_skip_frames`: the rates printed at the end leave out the first frames (context creation, code-object load, first-use allocations).
         const int seq_len = parameterReader.getData<int>("sequence_length", 0), skip = parameterReader.getData<int>("timing_skip_frames", 0);
@@ -232,6 +241,15 @@ int main(int argc, char** argv)
                     if (!bl) bl.reset(new BatchLooper(parameterReader, bt->device()));
                     for (const BatchLooper::Candidate& c : bl->addChunk(bt->last_out, done, picked)) loop_log.add(c.frame->id, c.loop->id, c.score);
                 }
+                if (!train_vocab.empty() && !picked.empty()) {      // the bulk loop keeps no host copy of the descriptors: the key-frames' rows come down per chunk
+                    const ssm_seq_out_dev& o = bt->last_out;
+                    vector<int32_t> nkp(done.size());
+                    bt->device().check(ssm_memcpy_d2h(bt->device().ctx(), nkp.data(), o.nkp, nkp.size() * 4), "ssm_memcpy_d2h");
+                    for (int i : picked) {
+                        train_sets.emplace_back((size_t)max(0, min(nkp[i], o.cap)) * 32);
+                        if (!train_sets.back().empty()) bt->device().check(ssm_memcpy_d2h(bt->device().ctx(), train_sets.back().data(), o.desc + (size_t)i * o.cap * 32, train_sets.back().size()), "ssm_memcpy_d2h");
+                    }
+                }
             };
             while (RGBDFrame::Ptr frame = read_next()) {
                 if (!bt) bt.reset(new BatchTracker(parameterReader, frame->rgb.cols, frame->rgb.rows, frame->T_f_w));
@@ -247,6 +265,7 @@ int main(int argc, char** argv)
             if (bt) handle(bt->flush(), count);
             if (count) track_s += sec(a, now());
             t1 = now();
+            if (!train_vocab.empty()) trained = trainVocabulary(parameterReader, train_sets, bt ? &bt->device() : nullptr, train_vocab);      // (while the tracker's context lives)
             cout << "batched tracker: chunk " << (bt ? bt->chunk() : 0) << " lost " << lost << endl;
         } else if (batched_stereo) {
             // Tracker::estimateVO + FrameReader's SGBM depth in bulk (include/ssm/batch_stereo_tracker.h): quad matcher, depth and ego-motion of a chunk per launch
@@ -287,6 +306,7 @@ int main(int argc, char** argv)
             traj.add(frame);
             if (moving && !frame->moving_mask.empty()) moving_log.add(frame->moving_mask, tracker->pitch1);
             const bool inserted = poseGraph.tryInsertKeyFrame(frame);
+            if (inserted && !train_vocab.empty()) { const cv::Mat d = frame->getAllDescriptors(); train_sets.emplace_back(d.data, d.data + (size_t)d.rows * 32); }
             if (inserted && looper) {
                 looper->add(frame);
                 looper->getPossibleLoops(frame);
@@ -299,7 +319,8 @@ int main(int argc, char** argv)
             if (frame_period_ms > 0) this_thread::sleep_for(chrono::milliseconds(frame_period_ms));      // a camera's frame period (measurements of the viewer thread under a paced stream)
         }
         if (optimize && step_frames > 0) poseGraph.step();                 // the frames after the last boundary (a --batched run's final flush)
-        t1 = now(); }
+        t1 = now();
+        if (!train_vocab.empty()) trained = trainVocabulary(parameterReader, train_sets, OrbFeature::lastDevice(), train_vocab); }
         if (optimize) for (const PoseGraph::LoopCandidate& c : poseGraph.loopCandidates) loop_log.add(c.frame, c.loop, c.score);
         const double s = sec(t0, t1), s_timed = sec(t_timed0, t1);
         mapper.SaveMap();
@@ -335,6 +356,7 @@ int main(int argc, char** argv)
             cout << " map_voxels " << nvox << " map_fnv " << hex << h << dec;
         }
         if (loops) cout << " loop_candidates " << loop_log.n << " loop_fnv " << hex << loop_log.h << dec;
+        if (!train_vocab.empty()) cout << " vocab_nodes " << trained.nodes << " vocab_words " << trained.words << " vocab_fnv " << hex << trained.fnv << dec;
         if (optimize) {
             uint64_t h = 0xCBF29CE484222325ull;                           // FNV-1a over the key-frames' final poses, in key-frame order
             for (RGBDFrame::Ptr& kf : poseGraph.keyframes) { const Eigen::Isometry3d T = kf->getTransform(); const unsigned char* b = (const unsigned char*)T.data(); for (int k = 0; k < 128; k++) { h ^= b[k]; h *= 0x100000001B3ull; } }
