@@ -1,6 +1,6 @@
 // uvd_core.h -- the per-pixel arithmetic of UVDisparity::Process (reference src/uvdisparity.cpp:842-903) and of the three functions of src/stereo.cpp it
 // depends on (triangulate10D :41-118, correct3DPoints :127-181, setImageROI :183-192), compiled for host and device like looper_core.h and pnp_core.h:
-// csrc/kernels_uvd.hip and the host pipeline of csrc/ssm_uvd.hip call the same functions, so device == host bit for bit.  Operand types are
+// csrc/kernels_uvd.hip and the host pipeline of csrc/ssm_uvd_host.cpp call the same functions, so device == host bit for bit.  Operand types are
 // restated as the reference writes them; the functions use IEEE + - * /, conversions and round-to-nearest-even only, and every translation unit that includes
 // this is built with -ffp-contract=off.  cos, sin, atan, atan2 and exp never appear here: the host evaluates them and hands the numbers over (FrameK, the rate
 // table).  The 10-channel xyz image is never materialised: channels 0-2, 5, 6 and 9 are computed where they are consumed.

@@ -1,7 +1,7 @@
 // ssm/vocab_train_core.h -- the arithmetic of vocabulary training: a hierarchical k-majority tree over 256-bit ORB descriptors, of the shape
 // of DBoW2's TemplatedVocabulary<FORB>::create (k-means with bitwise-majority means, TF-IDF weights) but with a deterministic, integer-only contract of our
 // own (DBoW2 seeds from its own random stream, so bit parity with it is no goal).  Shared by
-//   * the host function of libssm_hip.so (ssm_vocab_train_host, csrc/ssm_vocab_train.inc),
+//   * the host function of libssm_hip.so (ssm_vocab_train_host, csrc/ssm_vocab_train_host.cpp),
 //   * the device trainer (csrc/kernels_vocab_train.hip),
 // so that both build the same tree, byte for byte.
 // THE CONTRACT (per node with members S, always taken in ascending input index)

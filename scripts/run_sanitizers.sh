@@ -2,8 +2,9 @@
 # CPU sanitizer runs of the oracle and of the host layer (SURVEY.md s.5 "race detection"; no GPU involved).  Usage: bash scripts/run_sanitizers.sh [logfile]
 # oracle: san_check.c over every stage + the pipeline entry point on four threads.  host: test_png (PNG decoder), test_pnp (PnPSolver / pnp_core.h on the
 # committed golden case files), test_threads (PoseGraph + Mapper::viewer + a polling thread; device calls -> san_stub_device.cpp), test_looper (rgbd_tutor::Looper on
-# its host path + the library's vocabulary code, csrc/ssm_vocab.inc, compiled into the stub), test_posegraph --graph-only (PoseGraph's graph bookkeeping + the
-# pose-graph optimiser's host function, csrc/ssm_pgo.hip built without its device half).
+# its host path), test_uvd (UVDisparity on its host path), test_posegraph --graph-only (PoseGraph's graph bookkeeping + the pose-graph optimiser's host function).
+# The stages' host code is the library's own: csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp and ssm_pgo_host.cpp are compiled with the
+# sanitizer and linked beside the stub.
 # Every step's OWN exit status decides (no status of a `tail` / `grep` behind a pipe): a failed build, a missing binary, a non-zero exit or a sanitizer
 # report anywhere in the full, un-tailed output makes the run fail; the log keeps the complete output of failing steps and the tail of passing ones.
 set -u

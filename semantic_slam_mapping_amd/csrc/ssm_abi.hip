@@ -3,12 +3,16 @@
 // moves caller data and enqueues the kernels of kernels_*.hip on the context stream.  There is NO CPU fallback: if
 // HIP is unusable ssm_create fails with SSM_E_NODEVICE / SSM_E_HIP.
 #include "ssm_ctx.h"
+#include "ssm_host.h"
 #include <set>
 
 static const int8_t k_default_pattern[1024] = {
 #include "orb_pattern.inc"
 };
 thread_local std::string g_create_err;
+// the error path and the lock of the host-only sources (ssm_host.h), which do not know the context
+int host_fail(ssm_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; else g_create_err = msg; return code; }
+std::unique_lock<std::mutex> host_lock(ssm_ctx* c) { return c ? std::unique_lock<std::mutex>(c->mu) : std::unique_lock<std::mutex>(); }
 
 // ---------------------------------------------------------------- geometry (mirrors ORBextractor ctor / ComputePyramid)
 // cells (of size `cell`, counted from origin + 3) that the scored positions [max(a - 1, EDGE), min(b + 1, n - EDGE)) of a FAST tile interior [a, b) touch

@@ -1,0 +1,107 @@
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp: plain C++ without a HIP
+// header and without ssm_ctx.h) share with the device translation units.  Those sources are compiled once and LINKED into libssm_hip.so, into the CPU sanitizer
+// binaries of the host layer and into host/test_vocab_train.  What they need from the side that owns the context and the device are the hooks: defined in
+// ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
+#pragma once
+#include "../../include/ssm_hip.h"
+#include "../../include/ssm/vocab_train_core.h"
+#include "../../include/ssm/uvd_core.h"
+#include "../../include/ssm/pgo_core.h"
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+#define SSM_HIDDEN __attribute__((visibility("hidden")))
+// hooks (ssm_abi.hip).  The one error path: the message goes to the context, or without one to what ssm_last_error(NULL) reads on this thread; returns `code`
+SSM_HIDDEN int host_fail(ssm_ctx* c, int code, const std::string& msg);
+SSM_HIDDEN std::unique_lock<std::mutex> host_lock(ssm_ctx* c);          // the context's lock, held; nothing without a context
+
+// ---------------------------------------------------------------- vocabulary (ssm_vocab.cpp, ssm_vocab_train_host.cpp)
+struct ssm_vocab {
+    int k = 0, L = 0, scoring = 0, weighting = 0;
+    std::vector<int32_t> first_child, n_child, word;      // per node, breadth-first numbering (node 0 = the root)
+    std::vector<uint32_t> desc;                           // per node, 8 words
+    std::vector<double> weight;                           // per word id
+    std::vector<int32_t> file_id;                         // per node: the id it was given under (ssm_vocab_export writes that order back)
+    int max_depth = 0;
+    ssm_bow::Tree tree() const
+    {
+        ssm_bow::Tree t; t.first_child = first_child.data(); t.n_child = n_child.data(); t.desc = desc.data(); t.word = word.data(); t.weight = weight.data();
+        t.n_nodes = (int)n_child.size(); t.n_words = (int)weight.size(); t.max_depth = max_depth;
+        return t;
+    }
+};
+// the tree as ssm_vocab_create takes it: node i has id i + 1, ids are breadth-first (level by level; inside a level by parent id, then by cluster)
+struct VtTree {
+    std::vector<int32_t> parent; std::vector<uint8_t> leaf; std::vector<uint32_t> desc;
+    int add(int parent_id, const uint32_t* d) { parent.push_back(parent_id); leaf.push_back(0); desc.insert(desc.end(), d, d + ssm_vt::DESC_WORDS); return (int)parent.size(); }      // -> the new id
+};
+SSM_HIDDEN int vt_check(ssm_ctx* c, const uint8_t* desc, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* p, ssm_vocab** out, int* n_out);
+SSM_HIDDEN int vt_finish(const VtTree& t, const std::vector<int32_t>& leaf_of_feature, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* p,
+                         int32_t* word_of_feature, ssm_vocab_train_report* report, ssm_vocab** out);          // (its ssm_vocab_create cannot fail on a tree built here)
+SSM_HIDDEN int vt_kmajority_check(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, const uint8_t* centres, const int32_t* assign_out);
+SSM_HIDDEN int vt_kmajority_host(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, uint8_t* centres, int32_t* assign_out);
+
+// ---------------------------------------------------------------- U/V-disparity (ssm_uvd_host.cpp)
+struct UvdKalman {          // KalmanFilter(2, 1, 0) of uvdisparity.cpp:35-47 whose second state is never observed: a scalar float32 filter
+    float x = 0.0f, P = 1.0f;
+    void update(float z) { P += 5e-6f; const float K = P / (P + 0.001f); x += K * (z - x); P = (1.0f - K) * P; }
+};
+typedef std::vector<uint8_t> UvdImg;
+struct UvdFrame {           // one frame of the last call: what the host steps produce and ssm_debug_uvd_* hand out
+    ssm_uvd_info info{}; ssm_uvdc::FrameK k{};
+    int w = 0, h = 0, max_disp = 0;
+    UvdImg v_dis, blur, erode, bin;           // v_dis: h x 256; the others h x v_cols
+    std::vector<int32_t> pts, areas;
+    UvdImg u_raw, u_adj, uni;                 // u_rows x w
+    std::vector<UvdImg> found, merged, kept;
+};
+struct UvdDev;              // the device workspaces of an object with a context: ssm_uvd.hip
+struct ssm_uvd {
+    ssm_ctx* c = nullptr;                       // null: a host-only object (ssm_uvd_process_host)
+    ssm_uvd_params p{};
+    UvdKalman kf1, kf2;
+    double rate[ssm_uvdc::MAX_BINS];             // adjustUdisIntense's sigmoid(row, 0.02, 32) per U-disparity row
+    std::vector<UvdFrame> frames;               // the last call
+    bool record = false;                        // ssm_debug_uvd_record: keep the masks found / merged / kept of every frame for ssm_debug_uvd_stage
+    double call_ms[3] = {0, 0, 0};              // the last device call: host step 1, host step 2, the whole call (ssm_debug_uvd_times)
+    UvdDev* dev = nullptr;
+};
+SSM_HIDDEN void uvd_host_step1(const ssm_uvd_params& p, UvdKalman& kf1, UvdKalman& kf2, UvdFrame& F, int min_disp, bool skip);
+SSM_HIDDEN void uvd_host_step2(const ssm_uvd_params& p, UvdFrame& F, ssm_pmatch* m, uint8_t* flags, int nm, const uint8_t* probe_roi, const int16_t* probe_disp, bool record);
+inline ssm_uvdc::Calib uvd_calib(const ssm_uvd_params& p) { return ssm_uvdc::Calib{p.f, p.cu, p.cv, p.base}; }
+inline ssm_uvdc::Roi uvd_roi(const ssm_uvd_params& p) { return ssm_uvdc::Roi{p.roi_x, p.roi_y, p.roi_z}; }
+SSM_HIDDEN int uvd_dev_attach(ssm_uvd* u);          // hooks (ssm_uvd.hip): ssm_uvd_create with a context -> u->dev; ssm_uvd_destroy of such an object
+SSM_HIDDEN void uvd_dev_release(ssm_uvd* u);
+
+// ---------------------------------------------------------------- pose graph (ssm_pgo_host.cpp)
+struct PgoPlan {
+    int nf = 0, na = 0; int64_t total = 0;
+    std::vector<int32_t> aedge, vslot, svert, csr_off, csr_edge, first, reach; std::vector<int64_t> rowoff;
+};
+struct PgoDev;              // the device buffer and staging of an object with a context: ssm_pgo.hip
+struct ssm_pgo {
+    ssm_ctx* c = nullptr;                       // null: a host-only object
+    std::vector<int32_t> ids; std::unordered_map<int, int> index;
+    std::vector<double> pose; std::vector<uint8_t> fixed;
+    std::vector<int32_t> efrom, eto, robust; std::vector<double> Z, zinv, omega;
+    size_t cap_bytes = (size_t)1 << 30;
+    PgoPlan plan;
+    std::vector<double> lin, H, L, b, x, y, d, saved; ssm_pgc::Control ctl{}; ssm_pgc::Report rep{};     // host workspace / the last report
+    PgoDev* dev = nullptr;
+    double ms[ssm_pgc::NPHASE] = {0, 0, 0, 0, 0};
+    int nv() const { return (int)ids.size(); }
+    int ne() const { return (int)efrom.size(); }
+};
+// hooks (ssm_pgo.hip): ssm_pgo_create with a context (sets cap_bytes from the free device memory), ssm_pgo_destroy of such an object, and the device legs of
+// ssm_pgo_optimize[_many], ssm_pgo_linearize and ssm_pgo_factor_solve: arguments checked, the graphs planned, hv / v = their host views
+SSM_HIDDEN int pgo_dev_attach(ssm_pgo* g);
+SSM_HIDDEN void pgo_dev_release(ssm_pgo* g);
+SSM_HIDDEN int pgo_dev_optimize(ssm_pgo** graphs, int n, const ssm_pgc::View* hv, int iterations);                  // -> every pose, rep
+SSM_HIDDEN int pgo_dev_linearize(ssm_pgo* g, const ssm_pgc::View& v);                                      // -> g->lin, g->H, g->b
+SSM_HIDDEN int pgo_dev_factor_solve(ssm_pgo* g, ssm_pgo& t, const ssm_pgc::View& v, double lambda);       // g owns the device memory; -> t.x, t.ctl

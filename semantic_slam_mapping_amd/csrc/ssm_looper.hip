@@ -1,14 +1,8 @@
-// ssm_looper.hip -- rgbd_tutor::Looper (reference include/looper.h, src/looper.cpp) behind the C ABI: the vocabulary (a host object: text loader, tree,
-// the host transform / score of include/ssm/looper_core.h) and the device looper of a context (kernels_bow.hip): a CSR database of bag-of-words vectors
-// that grows by doubling, bulk add from device descriptors, score rows and ordered loop candidates.
+// ssm_looper.hip -- rgbd_tutor::Looper (reference include/looper.h, src/looper.cpp) behind the C ABI: the device looper of a context (kernels_bow.hip) over a
+// vocabulary (a host object: ssm_vocab.cpp): a CSR database of bag-of-words vectors that grows by doubling, bulk add from device descriptors, score rows
+// and ordered loop candidates.
 #include "ssm_ctx.h"
-#include "../../include/ssm/looper_core.h"
-#include <algorithm>
-#include <cerrno>
-#include <cstdio>
-
-static int vocab_fail(const std::string& msg) { g_create_err = msg; return SSM_E_INVAL; }
-#include "ssm_vocab.inc"
+#include "ssm_host.h"
 
 // ---------------------------------------------------------------- the device looper
 struct ssm_looper {

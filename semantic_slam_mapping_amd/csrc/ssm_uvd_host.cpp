@@ -1,20 +1,9 @@
-// ssm_uvd_host.inc -- the host-only steps of UVDisparity::Process: the ground line of the V-disparity image, the two Kalman filters, and the
-// seeds, flood fills, merge and verification on the U-disparity image.  Small and sequential; the device path and ssm_uvd_process_host run exactly this code
-// between their per-pixel stages.  Included by ssm_uvd.hip only (as ssm_vocab.inc is by ssm_looper.hip).
-
-struct UvdKalman {          // KalmanFilter(2, 1, 0) of uvdisparity.cpp:35-47 whose second state is never observed: a scalar float32 filter
-    float x = 0.0f, P = 1.0f;
-    void update(float z) { P += 5e-6f; const float K = P / (P + 0.001f); x += K * (z - x); P = (1.0f - K) * P; }
-};
-typedef std::vector<uint8_t> UvdImg;
-struct UvdFrame {           // one frame of the last call: what the host steps produce and ssm_debug_uvd_* hand out
-    ssm_uvd_info info{}; ssm_uvdc::FrameK k{};
-    int w = 0, h = 0, max_disp = 0;
-    UvdImg v_dis, blur, erode, bin;           // v_dis: h x 256; the others h x v_cols
-    std::vector<int32_t> pts, areas;
-    UvdImg u_raw, u_adj, uni;                 // u_rows x w
-    std::vector<UvdImg> found, merged, kept;
-};
+// ssm_uvd_host.cpp -- the host half of UVDisparity::Process: the object, and the host-only steps -- the ground line of the V-disparity image, the
+// two Kalman filters, and the seeds, flood fills, merge and verification on the U-disparity image.  Small and sequential; the device path (ssm_uvd.hip) runs
+// the two steps between its per-pixel phases, ssm_uvd_process_host runs them around the per-pixel stages of include/ssm/uvd_core.h on the CPU.  Plain C++
+// without any device call: linked into the library and, as it is, into the CPU sanitizer builds of the host layer (ssm_host.h).
+#include "ssm_host.h"
+#include <climits>
 
 // GaussianBlur(3 x 3, sigma 0) on u8: the 1-2-1 x 1-2-1 kernel in fixed point, reflect-101 border (a single row / column reflects onto itself)
 static void uvd_blur3(const UvdImg& src, int rows, int cols, int stride, UvdImg& dst)
@@ -58,7 +47,7 @@ static int uvd_otsu(const UvdImg& img)
 
 // host step 1 (calVDisparity's sizes, Pitch_Classify's line, Process' Kalman update): F.v_dis holds the h x 256 u8 rows, F.max_disp / min_disp the extremes.
 // skip: the frame is not to be run at all
-static void uvd_host_step1(const ssm_uvd_params& p, UvdKalman& kf1, UvdKalman& kf2, UvdFrame& F, int min_disp, bool skip)
+void uvd_host_step1(const ssm_uvd_params& p, UvdKalman& kf1, UvdKalman& kf2, UvdFrame& F, int min_disp, bool skip)
 {
     using namespace ssm_uvdc;
     const int h = F.h;
@@ -135,7 +124,7 @@ static bool uvd_overlap(const UvdImg& a, const UvdImg& b) { for (size_t i = 0; i
 // host step 2 (filterInOut, findAllMasks, mergeMasks, verifyByInliers): F.u_adj is the adjusted U-disparity image, probe_roi / probe_disp what the ROI mask and
 // the disparity hold at each match's (v1c, u1c) (a match outside the image: roi 0).  Edits matches / flags as the C ABI describes; F.uni = the union of the kept masks
 // record: keep copies of the masks found / merged / kept in F for ssm_debug_uvd_stage (the tests); off, the masks move through the three steps without a copy
-static void uvd_host_step2(const ssm_uvd_params& p, UvdFrame& F, ssm_pmatch* m, uint8_t* flags, int nm, const uint8_t* probe_roi, const int16_t* probe_disp, bool record)
+void uvd_host_step2(const ssm_uvd_params& p, UvdFrame& F, ssm_pmatch* m, uint8_t* flags, int nm, const uint8_t* probe_roi, const int16_t* probe_disp, bool record)
 {
     using namespace ssm_uvdc;
     ssm_uvd_info& I = F.info;
@@ -197,23 +186,54 @@ static void uvd_host_step2(const ssm_uvd_params& p, UvdFrame& F, ssm_pmatch* m, 
     if (I.n_masks_kept == 0) F.k.run = 0;
 }
 
-static ssm_uvdc::Calib uvd_calib(const ssm_uvd_params& p) { return ssm_uvdc::Calib{p.f, p.cu, p.cv, p.base}; }
-static ssm_uvdc::Roi uvd_roi(const ssm_uvd_params& p) { return ssm_uvdc::Roi{p.roi_x, p.roi_y, p.roi_z}; }
 // adjustUdisIntense's sigmoid(row, 0.02, 32, 1) per U-disparity row (uvdisparity.cpp:815, :991-996)
 static void uvd_rate_table(double* rate) { for (int j = 0; j < ssm_uvdc::MAX_BINS; j++) { const double t = j, scale = 0.02, range = 32; rate[j] = range * 1.0f / (1 + exp(t * scale)); } }
-static void uvd_set_defaults(ssm_uvd_params* p)
+
+
+// ---------------------------------------------------------------- the object
+extern "C" void ssm_uvd_params_default(ssm_uvd_params* p)
 {
+    if (!p) return;
     *p = ssm_uvd_params{};
     p->f = 718.8560; p->cu = 607.1928; p->cv = 185.2157; p->base = 0.532331858;         // parameters.txt:37-41
     p->roi_x = 20; p->roi_y = 5; p->roi_z = 40;                                          // :50-54
     p->min_intense = 32; p->min_disparity_raw = 64; p->min_area = 40;                    // USegmentPars()
     p->inlier_tolerance = 3;                                                             // include/track.h:100
 }
-
-// ssm_uvd_process_host: the whole of Process on the CPU -- the per-pixel stages from uvd_core.h around the two host steps.  n_matches < 0 skips the frame
-static int uvd_process_host(const ssm_uvd_params& p, const double* rate, UvdKalman& kf1, UvdKalman& kf2, UvdFrame& F, const uint8_t* left, const int16_t* disp, int w, int h, int stride,
-                            ssm_pmatch* matches, uint8_t* inlier_flags, int n_matches, uint8_t* moving, uint8_t* roi, uint8_t* ground, ssm_uvd_info* info, bool record)
+extern "C" int ssm_uvd_create(ssm_ctx* c, const ssm_uvd_params* params, ssm_uvd** out)
 {
+    if (!out) return SSM_E_INVAL;
+    *out = nullptr;
+    if (!params) return host_fail(c, SSM_E_INVAL, "uvd: null parameters");
+    if (!(params->f > 0)) return host_fail(c, SSM_E_INVAL, "uvd: the focal length must be positive");
+    std::unique_ptr<ssm_uvd> u(new ssm_uvd());
+    u->c = c; u->p = *params;
+    uvd_rate_table(u->rate);
+    if (c) { const int r = uvd_dev_attach(u.get()); if (r) return r; }
+    *out = u.release();
+    return SSM_OK;
+}
+extern "C" void ssm_uvd_destroy(ssm_uvd* u)
+{
+    if (!u) return;
+    if (u->c) uvd_dev_release(u);
+    delete u;
+}
+extern "C" int ssm_uvd_reset(ssm_uvd* u)
+{
+    if (!u) return SSM_E_INVAL;
+    const std::unique_lock<std::mutex> lk = host_lock(u->c);
+    u->kf1 = UvdKalman(); u->kf2 = UvdKalman();
+    return SSM_OK;
+}
+extern "C" int ssm_debug_uvd_record(ssm_uvd* u, int on) { if (!u) return SSM_E_INVAL; u->record = on != 0; return SSM_OK; }
+// the whole of Process on the CPU -- the per-pixel stages from uvd_core.h around the two host steps.  n_matches < 0 skips the frame
+extern "C" int ssm_uvd_process_host(ssm_uvd* u, const uint8_t* left, const int16_t* disp, int w, int h, int stride, ssm_pmatch* matches, uint8_t* inlier_flags,
+                                    int n_matches, uint8_t* moving, uint8_t* roi, uint8_t* ground, ssm_uvd_info* info)
+{
+    if (!u) return SSM_E_INVAL;
+    u->frames.resize(1);
+    const ssm_uvd_params& p = u->p; const double* rate = u->rate; UvdKalman &kf1 = u->kf1, &kf2 = u->kf2; UvdFrame& F = u->frames[0]; const bool record = u->record;
     using namespace ssm_uvdc;
     if (!left || !disp || w < 1 || h < 1 || h > 32767 || stride < w || (n_matches > 0 && (!matches || !inlier_flags)) || !info) return SSM_E_INVAL;
     const bool skip = n_matches < 0;                 // as nmatch[i] < 0 of ssm_uvd_process_dev
@@ -263,5 +283,54 @@ static int uvd_process_host(const ssm_uvd_params& p, const double* rate, UvdKalm
     if (ground) memcpy(ground, ground_v.data(), px);
     if (moving) memcpy(moving, moving_v.data(), px);
     *info = F.info;
+    return SSM_OK;
+}
+
+// ---------------------------------------------------------------- what the tests look at
+extern "C" int ssm_debug_uvd_images(ssm_uvd* u, int frame, uint8_t* v_dis, uint8_t* u_dis, uint8_t* bin, uint8_t* union_mask)
+{
+    using namespace ssm_uvdc;
+    if (!u || frame < 0 || frame >= (int)u->frames.size()) return SSM_E_INVAL;
+    const UvdFrame& F = u->frames[frame];
+    if (v_dis) memcpy(v_dis, F.v_dis.data(), F.v_dis.size());
+    if (u_dis && !F.u_adj.empty()) memcpy(u_dis, F.u_adj.data(), F.u_adj.size());
+    if (bin) {
+        memset(bin, 0, (size_t)F.h * MAX_BINS);
+        if (!F.bin.empty()) for (int r = 0; r < F.h; r++) memcpy(bin + (size_t)r * MAX_BINS, F.bin.data() + (size_t)r * F.info.v_cols, F.info.v_cols);
+    }
+    if (union_mask && !F.uni.empty()) memcpy(union_mask, F.uni.data(), F.uni.size());
+    return SSM_OK;
+}
+extern "C" int ssm_debug_uvd_times(ssm_uvd* u, double ms[3])
+{
+    if (!u || !ms) return SSM_E_INVAL;
+    for (int i = 0; i < 3; i++) ms[i] = u->call_ms[i];
+    return SSM_OK;
+}
+extern "C" int ssm_debug_uvd_stage(ssm_uvd* u, int frame, int stage, void* out, size_t cap, size_t* bytes)
+{
+    if (!u || frame < 0 || frame >= (int)u->frames.size() || !bytes) return SSM_E_INVAL;
+    const UvdFrame& F = u->frames[frame];
+    std::vector<uint8_t> cat;
+    const void* src = nullptr; size_t n = 0;
+    auto img = [&](const UvdImg& v) { src = v.data(); n = v.size(); };
+    auto list = [&](const std::vector<UvdImg>& l) { for (const UvdImg& v : l) cat.insert(cat.end(), v.begin(), v.end()); src = cat.data(); n = cat.size(); };
+    if (stage >= 8 && stage <= 10 && !u->record) return SSM_E_INVAL;          // not recorded: ssm_debug_uvd_record
+    switch (stage) {
+    case 1: img(F.blur); break;
+    case 2: img(F.erode); break;
+    case 3: img(F.bin); break;
+    case 4: src = F.pts.data(); n = F.pts.size() * 4; break;
+    case 5: img(F.u_raw); break;
+    case 7: src = F.areas.data(); n = F.areas.size() * 4; break;
+    case 8: list(F.found); break;
+    case 9: list(F.merged); break;
+    case 10: list(F.kept); break;
+    default: return SSM_E_INVAL;
+    }
+    *bytes = n;
+    if (!out) return SSM_OK;
+    if (n > cap) return SSM_E_CAPACITY;
+    if (n) memcpy(out, src, n);
     return SSM_OK;
 }

@@ -1,45 +1,25 @@
-// ssm_vocab.inc -- the vocabulary of the looper (ssm_vocab_*, ssm_bow_score_host): a host object, plain C++ without any device call.  Included by ssm_looper.hip
-// (the library) and by host/san_stub_device.cpp (the CPU sanitizer builds of the host layer, which do not link the library).  The includer defines
-// `static int vocab_fail(const std::string& msg)` first: it records the message for ssm_last_error(NULL) and returns SSM_E_INVAL.
-#include <algorithm>
+// ssm_vocab.cpp -- the vocabulary of the looper (ssm_vocab_*, ssm_bow_score_host): a host object, plain C++ without any device call, over
+// include/ssm/looper_core.h.  Linked into the library and, as it is, into the CPU sanitizer builds of the host layer and host/test_vocab_train (ssm_host.h).
+#include "ssm_host.h"
 #include <cerrno>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-struct ssm_vocab {
-    int k = 0, L = 0, scoring = 0, weighting = 0;
-    std::vector<int32_t> first_child, n_child, word;      // per node, breadth-first numbering (node 0 = the root)
-    std::vector<uint32_t> desc;                           // per node, 8 words
-    std::vector<double> weight;                           // per word id
-    std::vector<int32_t> file_id;                         // per node: the id it was given under (ssm_vocab_export writes that order back)
-    int max_depth = 0;
-    ssm_bow::Tree tree() const
-    {
-        ssm_bow::Tree t; t.first_child = first_child.data(); t.n_child = n_child.data(); t.desc = desc.data(); t.word = word.data(); t.weight = weight.data();
-        t.n_nodes = (int)n_child.size(); t.n_words = (int)weight.size(); t.max_depth = max_depth;
-        return t;
-    }
-};
-
 extern "C" int ssm_vocab_create(int k, int L, int scoring, int weighting, const int32_t* parent, const uint8_t* is_leaf, const uint8_t* desc, const double* weight, int n, ssm_vocab** out)
 {
-    if (!out) return vocab_fail("null argument");
+    if (!out) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     *out = nullptr;
-    if (n < 0 || (n > 0 && (!parent || !is_leaf || !desc || !weight))) return vocab_fail("null argument");
-    if (k < 0 || k > 20 || L < 1 || L > 10) return vocab_fail("vocabulary: k must be in [0, 20] and L in [1, 10]");
-    if (scoring != 0 || weighting != 0) return vocab_fail("vocabulary: only scoring 0 (L1_NORM) with weighting 0 (TF_IDF) is supported");
-    if (n == 0) return vocab_fail("vocabulary: the root has no children");
+    if (n < 0 || (n > 0 && (!parent || !is_leaf || !desc || !weight))) return host_fail(nullptr, SSM_E_INVAL, "null argument");
+    if (k < 0 || k > 20 || L < 1 || L > 10) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: k must be in [0, 20] and L in [1, 10]");
+    if (scoring != 0 || weighting != 0) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: only scoring 0 (L1_NORM) with weighting 0 (TF_IDF) is supported");
+    if (n == 0) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: the root has no children");
     // file ids: 0 = the root, node i of the arrays = id i + 1
     std::vector<int32_t> cnt((size_t)n + 1, 0), start((size_t)n + 2, 0);
     for (int i = 0; i < n; i++) {
-        if (parent[i] < 0 || parent[i] > i) return vocab_fail("vocabulary: node " + std::to_string(i + 1) + " names parent " + std::to_string(parent[i]) + ", which is not an earlier node");
-        if (parent[i] > 0 && is_leaf[parent[i] - 1]) return vocab_fail("vocabulary: leaf node " + std::to_string(parent[i]) + " has children");
+        if (parent[i] < 0 || parent[i] > i) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: node " + std::to_string(i + 1) + " names parent " + std::to_string(parent[i]) + ", which is not an earlier node");
+        if (parent[i] > 0 && is_leaf[parent[i] - 1]) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: leaf node " + std::to_string(parent[i]) + " has children");
         cnt[parent[i]]++;
     }
-    for (int i = 0; i < n; i++) if (!is_leaf[i] && cnt[i + 1] == 0) return vocab_fail("vocabulary: node " + std::to_string(i + 1) + " is neither a leaf nor has children");
-    for (int i = 0; i <= n; i++) { if (cnt[i] > 65535) return vocab_fail("vocabulary: more than 65535 children under one node"); start[i + 1] = start[i] + cnt[i]; }
+    for (int i = 0; i < n; i++) if (!is_leaf[i] && cnt[i + 1] == 0) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: node " + std::to_string(i + 1) + " is neither a leaf nor has children");
+    for (int i = 0; i <= n; i++) { if (cnt[i] > 65535) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: more than 65535 children under one node"); start[i + 1] = start[i] + cnt[i]; }
     std::vector<int32_t> kids((size_t)n), fill(start.begin(), start.end() - 1);
     for (int i = 0; i < n; i++) kids[fill[parent[i]]++] = i + 1;                    // the children of every id, in file order
     std::vector<int32_t> word_of_id((size_t)n + 1, -1); int nwords = 0;
@@ -80,12 +60,12 @@ extern "C" int ssm_vocab_export(const ssm_vocab* v, int32_t* parent, uint8_t* is
 }
 extern "C" int ssm_vocab_save_text(const ssm_vocab* v, const char* path)
 {
-    if (!v || !path) return vocab_fail("null argument");
+    if (!v || !path) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     const int n = (int)v->n_child.size() - 1;
     std::vector<int32_t> parent((size_t)n); std::vector<uint8_t> leaf((size_t)n), desc((size_t)n * 32); std::vector<double> weight((size_t)n);
     { const int rc = ssm_vocab_export(v, parent.data(), leaf.data(), desc.data(), weight.data(), n); if (rc) return rc; }
     FILE* f = fopen(path, "wb");
-    if (!f) return vocab_fail(std::string("vocabulary: cannot write ") + path);
+    if (!f) return host_fail(nullptr, SSM_E_INVAL, std::string("vocabulary: cannot write ") + path);
     fprintf(f, "%d %d %d %d\n", v->k, v->L, v->scoring, v->weighting);
     for (int i = 0; i < n; i++) {
         fprintf(f, "%d %d", parent[i], (int)leaf[i]);
@@ -93,16 +73,16 @@ extern "C" int ssm_vocab_save_text(const ssm_vocab* v, const char* path)
         fprintf(f, " %.17g\n", weight[i]);                       // 17 significant digits give every double back
     }
     const bool bad = ferror(f) != 0;
-    if (fclose(f) != 0 || bad) return vocab_fail(std::string("vocabulary: write error on ") + path);
+    if (fclose(f) != 0 || bad) return host_fail(nullptr, SSM_E_INVAL, std::string("vocabulary: write error on ") + path);
     return SSM_OK;
 }
 extern "C" int ssm_vocab_load_text(const char* path, ssm_vocab** out)
 {
-    if (!out) return vocab_fail("null argument");
+    if (!out) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     *out = nullptr;
-    if (!path) return vocab_fail("null argument");
+    if (!path) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     FILE* f = fopen(path, "rb");
-    if (!f) return vocab_fail(std::string("vocabulary: cannot open ") + path);
+    if (!f) return host_fail(nullptr, SSM_E_INVAL, std::string("vocabulary: cannot open ") + path);
     std::string text; { char buf[1 << 16]; size_t got; while ((got = fread(buf, 1, sizeof(buf), f)) > 0) text.append(buf, got); }
     fclose(f);
     std::vector<int32_t> parent; std::vector<uint8_t> leaf, desc; std::vector<double> weight;
@@ -117,25 +97,25 @@ extern "C" int ssm_vocab_load_text(const char* path, ssm_vocab** out)
             // (a number ends at white space or at the end of the line: `1.5` is not the integer 1; strtol / strtod never run into the next line, the newline stops them)
             auto next_long = [&](long& v) { while (q < eol && (*q == ' ' || *q == '\t')) q++; if (q >= eol) return false; char* e; errno = 0; v = strtol(q, &e, 10); if (e == q || e > eol || errno || (e < eol && *e != ' ' && *e != '\t' && *e != '\r')) return false; q = e; return true; };
             if (!have_hdr) {
-                for (int i = 0; i < 4; i++) if (!next_long(hdr[i])) return vocab_fail(where);
+                for (int i = 0; i < 4; i++) if (!next_long(hdr[i])) return host_fail(nullptr, SSM_E_INVAL, where);
                 have_hdr = true;
             } else {
                 long pa, lf, b;
-                if (!next_long(pa) || !next_long(lf) || pa < 0 || pa > 0x7FFFFFFE) return vocab_fail(where);
+                if (!next_long(pa) || !next_long(lf) || pa < 0 || pa > 0x7FFFFFFE) return host_fail(nullptr, SSM_E_INVAL, where);
                 parent.push_back((int32_t)pa); leaf.push_back(lf > 0 ? 1 : 0);
-                for (int i = 0; i < 32; i++) { if (!next_long(b) || b < 0 || b > 255) return vocab_fail(where); desc.push_back((uint8_t)b); }
+                for (int i = 0; i < 32; i++) { if (!next_long(b) || b < 0 || b > 255) return host_fail(nullptr, SSM_E_INVAL, where); desc.push_back((uint8_t)b); }
                 while (q < eol && (*q == ' ' || *q == '\t')) q++;
-                if (q >= eol) return vocab_fail(where);
-                char* e; errno = 0; const double w = strtod(q, &e); if (e == q || e > eol) return vocab_fail(where);
+                if (q >= eol) return host_fail(nullptr, SSM_E_INVAL, where);
+                char* e; errno = 0; const double w = strtod(q, &e); if (e == q || e > eol) return host_fail(nullptr, SSM_E_INVAL, where);
                 q = e; weight.push_back(w);
             }
             while (q < eol && (*q == ' ' || *q == '\t' || *q == '\r')) q++;
-            if (q != eol) return vocab_fail(where);
+            if (q != eol) return host_fail(nullptr, SSM_E_INVAL, where);
         }
         p = eol + 1;
     }
-    if (!have_hdr) return vocab_fail("vocabulary: empty file");
-    if (hdr[0] < 0 || hdr[0] > 20 || hdr[1] < 1 || hdr[1] > 10 || hdr[2] < 0 || hdr[2] > 5 || hdr[3] < 0 || hdr[3] > 3) return vocab_fail("vocabulary: bad header (k L scoring weighting)");
+    if (!have_hdr) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: empty file");
+    if (hdr[0] < 0 || hdr[0] > 20 || hdr[1] < 1 || hdr[1] > 10 || hdr[2] < 0 || hdr[2] > 5 || hdr[3] < 0 || hdr[3] > 3) return host_fail(nullptr, SSM_E_INVAL, "vocabulary: bad header (k L scoring weighting)");
     return ssm_vocab_create((int)hdr[0], (int)hdr[1], (int)hdr[2], (int)hdr[3], parent.data(), leaf.data(), desc.data(), weight.data(), (int)parent.size(), out);
 }
 extern "C" void ssm_vocab_destroy(ssm_vocab* v) { delete v; }

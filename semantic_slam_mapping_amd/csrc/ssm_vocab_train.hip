@@ -1,12 +1,9 @@
-// ssm_vocab_train.hip -- vocabulary training behind the C ABI: the host function (ssm_vocab_train.inc) and the device trainer, which grows the
-// tree level by level with the kernels of kernels_vocab_train.hip.  Per level the host reads back what it needs to build the tree (centres seeded, members per
+// ssm_vocab_train.hip -- vocabulary training behind the C ABI: the device trainer (the host function is ssm_vocab_train_host.cpp), which grows
+// the tree level by level with the kernels of kernels_vocab_train.hip.  Per level the host reads back what it needs to build the tree (centres seeded, members per
 // cluster, the centres) and the "an assignment changed" flag after every pass; the descriptors, the permutation and the assignments never leave the device.
 #include "ssm_ctx.h"
-#include "../../include/ssm/vocab_train_core.h"
+#include "ssm_host.h"
 #include <chrono>
-
-static int vocab_fail(const std::string& msg) { g_create_err = msg; return SSM_E_INVAL; }
-#include "ssm_vocab_train.inc"
 
 namespace {
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -56,7 +53,7 @@ extern "C" int ssm_vocab_train(ssm_ctx* c, const uint8_t* desc, const int32_t* n
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     int N = 0;
-    { const int rc = vt_check(desc, n_per_frame, n_frames, p, out, &N); if (rc) { c->err = g_create_err; return rc; } }
+    { const int rc = vt_check(c, desc, n_per_frame, n_frames, p, out, &N); if (rc) return rc; }
     if (report) memset(report, 0, sizeof(*report));
     hipStream_t s = c->main.stream;
     const double t_begin = now_ms();
@@ -156,7 +153,6 @@ extern "C" int ssm_vocab_train(ssm_ctx* c, const uint8_t* desc, const int32_t* n
     { const int rc = down(c, leaf_of, (const int32_t*)R.leaf_of, (size_t)N); if (rc) return rc; }
     if (report) { report->levels = levels; report->capped_nodes = capped; }
     const int rc = vt_finish(t, leaf_of, n_per_frame, n_frames, p, word_of_feature, report, out);
-    if (rc) c->err = g_create_err;
     c->vt_total_ms = now_ms() - t_begin;
     return rc;
 }

@@ -1,30 +1,22 @@
-// ssm_vocab_train.inc -- vocabulary training on the host (ssm_vocab_train_host, the host half of ssm_debug_vocab_kmajority) and what the device trainer shares
-// with it: the argument checks, the tree under construction and its last step (word ids, TF-IDF weights, ssm_vocab_create).  Plain C++ without any device
-// call, over include/ssm/vocab_train_core.h.  Included by ssm_vocab_train.hip (the library) and by host/test_vocab_train.cpp (a stand-alone program that
-// runs under the CPU sanitizers).  The includer defines `static int vocab_fail(const std::string& msg)` first, as for ssm_vocab.inc.
-#include <cstring>
-#include <string>
-#include <vector>
-// the tree as ssm_vocab_create takes it: node i has id i + 1, ids are breadth-first (level by level; inside a level by parent id, then by cluster)
-struct VtTree {
-    std::vector<int32_t> parent; std::vector<uint8_t> leaf; std::vector<uint32_t> desc;
-    int add(int parent_id, const uint32_t* d) { parent.push_back(parent_id); leaf.push_back(0); desc.insert(desc.end(), d, d + ssm_vt::DESC_WORDS); return (int)parent.size(); }      // -> the new id
-};
-static int vt_check(const uint8_t* desc, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* p, ssm_vocab** out, int* n_out)
+// ssm_vocab_train_host.cpp -- vocabulary training on the host (ssm_vocab_train_host, the host half of ssm_debug_vocab_kmajority) and what the device trainer
+// (ssm_vocab_train.hip) shares with it: the argument checks, the tree under construction and its last step (word ids, TF-IDF weights, the vocabulary).  Plain
+// C++ without any device call, over include/ssm/vocab_train_core.h; linked into the library and, as it is, into host/test_vocab_train (ssm_host.h).
+#include "ssm_host.h"
+int vt_check(ssm_ctx* c, const uint8_t* desc, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* p, ssm_vocab** out, int* n_out)
 {
     if (out) *out = nullptr;
-    if (!desc || !n_per_frame || !p || !out) return vocab_fail("vocabulary training: null argument");
-    if (n_frames < 1) return vocab_fail("vocabulary training: no frames");
-    if (p->k < 2 || p->k > ssm_vt::MAX_K || p->L < 1 || p->L > ssm_vt::MAX_L || p->max_iters < 1) return vocab_fail("vocabulary training: k must be in [2, 20], L in [1, 10] and max_iters >= 1");
+    if (!desc || !n_per_frame || !p || !out) return host_fail(c, SSM_E_INVAL, "vocabulary training: null argument");
+    if (n_frames < 1) return host_fail(c, SSM_E_INVAL, "vocabulary training: no frames");
+    if (p->k < 2 || p->k > ssm_vt::MAX_K || p->L < 1 || p->L > ssm_vt::MAX_L || p->max_iters < 1) return host_fail(c, SSM_E_INVAL, "vocabulary training: k must be in [2, 20], L in [1, 10] and max_iters >= 1");
     long long n = 0;
-    for (int f = 0; f < n_frames; f++) { if (n_per_frame[f] < 0) return vocab_fail("vocabulary training: a negative descriptor count"); n += n_per_frame[f]; if (n > ssm_vt::MAX_N) break; }
-    if (n < 1 || n > ssm_vt::MAX_N) return vocab_fail("vocabulary training: the descriptor count must be in [1, 2^26]");
+    for (int f = 0; f < n_frames; f++) { if (n_per_frame[f] < 0) return host_fail(c, SSM_E_INVAL, "vocabulary training: a negative descriptor count"); n += n_per_frame[f]; if (n > ssm_vt::MAX_N) break; }
+    if (n < 1 || n > ssm_vt::MAX_N) return host_fail(c, SSM_E_INVAL, "vocabulary training: the descriptor count must be in [1, 2^26]");
     *n_out = (int)n;
     return SSM_OK;
 }
 // the finished tree + the leaf (node id) every training descriptor ended in -> word ids in leaf order, Ni per word, weights, the vocabulary
-static int vt_finish(const VtTree& t, const std::vector<int32_t>& leaf_of_feature, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* p,
-                     int32_t* word_of_feature, ssm_vocab_train_report* report, ssm_vocab** out)
+int vt_finish(const VtTree& t, const std::vector<int32_t>& leaf_of_feature, const int32_t* n_per_frame, int n_frames, const ssm_vocab_train_params* p,
+              int32_t* word_of_feature, ssm_vocab_train_report* report, ssm_vocab** out)
 {
     const int n = (int)t.parent.size();
     std::vector<int32_t> word_of_id((size_t)n + 1, -1); int words = 0;
@@ -66,7 +58,7 @@ extern "C" int ssm_vocab_train_host(const uint8_t* desc, const int32_t* n_per_fr
 {
     using namespace ssm_vt;
     int N = 0;
-    { const int rc = vt_check(desc, n_per_frame, n_frames, p, out, &N); if (rc) return rc; }
+    { const int rc = vt_check(nullptr, desc, n_per_frame, n_frames, p, out, &N); if (rc) return rc; }
     if (report) memset(report, 0, sizeof(*report));
     std::vector<uint32_t> D((size_t)N * DESC_WORDS); memcpy(D.data(), desc, (size_t)N * 32);
     struct Node { int id; std::vector<int32_t> mem; };
@@ -112,13 +104,13 @@ extern "C" int ssm_vocab_train_host(const uint8_t* desc, const int32_t* n_per_fr
     if (report) { report->levels = levels; report->capped_nodes = capped; }
     return vt_finish(t, leaf_of, n_per_frame, n_frames, p, word_of_feature, report, out);
 }
-static int vt_kmajority_check(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, const uint8_t* centres, const int32_t* assign_out)
+int vt_kmajority_check(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, const uint8_t* centres, const int32_t* assign_out)
 {
     if (n < 1 || n > ssm_vt::MAX_N || n_nodes < 1 || k < 1 || k > ssm_vt::MAX_K || !desc || !node_of || !cluster_of || !centres || !assign_out) return SSM_E_INVAL;
     for (int i = 0; i < n; i++) if (node_of[i] < 0 || node_of[i] >= n_nodes || cluster_of[i] < 0 || cluster_of[i] >= k || (i && node_of[i] < node_of[i - 1])) return SSM_E_INVAL;
     return SSM_OK;
 }
-static int vt_kmajority_host(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, uint8_t* centres, int32_t* assign_out)
+int vt_kmajority_host(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, uint8_t* centres, int32_t* assign_out)
 {
     using namespace ssm_vt;
     { const int rc = vt_kmajority_check(desc, n, node_of, cluster_of, n_nodes, k, centres, assign_out); if (rc) return rc; }

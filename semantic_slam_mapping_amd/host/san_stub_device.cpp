@@ -1,52 +1,29 @@
-// san_stub_device.cpp -- TEST INFRASTRUCTURE for the CPU sanitizer builds of the host layer (make SAN=asan|ubsan|tsan): a stand-in for the handful of
-// libssm_hip.so entry points that Mapper / PoseGraph reach, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main
-// thread's tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the
-// build container, which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  It computes nothing of the product: the numbers it
-// returns are placeholders.  It is linked into test_threads / test_pnp / test_png of a SAN build ONLY -- never into exp_mapping or the library.
+// san_stub_device.cpp -- TEST INFRASTRUCTURE for the CPU sanitizer builds of the host layer (make SAN=asan|ubsan|tsan): a stand-in for the side of libssm_hip.so
+// that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
+// tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
+// which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the "no device" form of
+// csrc/ssm_host.h's hooks here.  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
 #include "ssm_hip.h"
 #include "ssm/pnp_core.h"
-#include "ssm/looper_core.h"
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 struct ssm_ctx { ssm_config cfg; std::string err; };
-// the looper's vocabulary is host code: the library's own implementation runs under the sanitizers (test_looper).  The device looper is never reached there
-// (Looper takes the host path on a thread without a context); its entry points only have to link
-static thread_local std::string g_vocab_err;
-static int vocab_fail(const std::string& msg) { g_vocab_err = msg; return SSM_E_INVAL; }
-#include "../csrc/ssm_vocab.inc"
-// likewise the U/V-disparity stage: UVDisparity::Process takes ssm_uvd_process_host on a thread without a context, and that is the library's own host pipeline
-// (csrc/ssm_uvd_host.inc over include/ssm/uvd_core.h), which so runs under the sanitizers (test_uvd); the device entry points only have to link
-#include "ssm/uvd_core.h"
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include "../csrc/ssm_uvd_host.inc"
-// and the pose-graph optimiser: PoseGraph without a context uses ssm_pgo_optimize_host, the library's own host function (csrc/ssm_pgo.hip over
-// include/ssm/pgo_core.h), built here without its device half
-#define SSM_PGO_HOST_ONLY
 static thread_local std::string g_create_err;
-#include "../csrc/ssm_pgo.hip"
-struct ssm_uvd { ssm_uvd_params p; UvdKalman kf1, kf2; double rate[ssm_uvdc::MAX_BINS]; UvdFrame frame; };
+int host_fail(ssm_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; else g_create_err = msg; return code; }
+std::unique_lock<std::mutex> host_lock(ssm_ctx*) { return {}; }
+namespace ssm_pgc { struct View; }
+int uvd_dev_attach(ssm_uvd*) { return SSM_E_NODEVICE; }
+void uvd_dev_release(ssm_uvd*) {}
+int pgo_dev_attach(ssm_pgo*) { return SSM_E_NODEVICE; }
+void pgo_dev_release(ssm_pgo*) {}
+int pgo_dev_optimize(ssm_pgo**, int, const ssm_pgc::View*, int) { return SSM_E_NODEVICE; }
+int pgo_dev_linearize(ssm_pgo*, const ssm_pgc::View&) { return SSM_E_NODEVICE; }
+int pgo_dev_factor_solve(ssm_pgo*, ssm_pgo&, const ssm_pgc::View&, double) { return SSM_E_NODEVICE; }
 extern "C" {
-void ssm_uvd_params_default(ssm_uvd_params* p) { if (p) uvd_set_defaults(p); }
-int ssm_uvd_create(ssm_ctx* c, const ssm_uvd_params* params, ssm_uvd** out)
-{
-    if (!out || !params) return SSM_E_INVAL;
-    if (c) { *out = nullptr; return SSM_E_NODEVICE; }
-    ssm_uvd* u = new ssm_uvd(); u->p = *params; uvd_rate_table(u->rate); *out = u;
-    return SSM_OK;
-}
-void ssm_uvd_destroy(ssm_uvd* u) { delete u; }
-int ssm_uvd_reset(ssm_uvd* u) { if (!u) return SSM_E_INVAL; u->kf1 = UvdKalman(); u->kf2 = UvdKalman(); return SSM_OK; }
-int ssm_uvd_process_host(ssm_uvd* u, const uint8_t* left, const int16_t* disp, int w, int h, int stride, ssm_pmatch* matches, uint8_t* inlier_flags, int n_matches,
-                         uint8_t* moving, uint8_t* roi, uint8_t* ground, ssm_uvd_info* info)
-{
-    if (!u) return SSM_E_INVAL;
-    return uvd_process_host(u->p, u->rate, u->kf1, u->kf2, u->frame, left, disp, w, h, stride, matches, inlier_flags, n_matches, moving, roi, ground, info, false);
-}
-int ssm_debug_uvd_record(ssm_uvd*, int) { return SSM_OK; }
-int ssm_debug_uvd_times(ssm_uvd*, double*) { return SSM_E_NODEVICE; }
+// the device entry points of the stages whose host halves are linked in: never reached (the host classes take the host path on a thread without a context)
 int ssm_vo_estimate(ssm_ctx*, const ssm_pmatch*, int, const ssm_vo_params*, const int32_t*, int, double*, int32_t*, int, int*, int*) { return SSM_E_NODEVICE; }      // (VisualOdometryStereo has to link: test_uvd fills its lists by hand)
 int ssm_uvd_process(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
 int ssm_uvd_process_dev(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, const int32_t*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
@@ -64,7 +41,7 @@ void ssm_config_default(ssm_config* c) { memset(c, 0, sizeof(*c)); c->width = 64
     c->camera.cx = 318.6; c->camera.cy = 255.3; c->camera.fx = 517.3; c->camera.fy = 516.5; c->camera.scale = 1000.0; c->max_batch = 1; c->voxel_capacity_log2 = 16; }
 int ssm_create(int, const ssm_config* cfg, ssm_ctx** out) { *out = new ssm_ctx(); (*out)->cfg = *cfg; return SSM_OK; }
 void ssm_destroy(ssm_ctx* c) { delete c; }
-const char* ssm_last_error(const ssm_ctx* c) { return c ? c->err.c_str() : (g_vocab_err.empty() ? "stub" : g_vocab_err.c_str()); }
+const char* ssm_last_error(const ssm_ctx* c) { return c ? c->err.c_str() : (g_create_err.empty() ? "stub" : g_create_err.c_str()); }
 int ssm_orb_capacity(const ssm_ctx*) { return 1024; }
 int ssm_backproject(ssm_ctx*, const uint16_t* depth, const uint8_t* rgb, const uint8_t*, int w, int h, const ssm_camera*, const double*, double, ssm_point* out, int cap, int* n_out)
 {

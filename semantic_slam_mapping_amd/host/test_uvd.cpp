@@ -4,8 +4,8 @@
 // Prints one "PASS name" / "FAIL name" line per check; exit code = number of failures.
 //
 // Without a sequence directory (`test_uvd` or `test_uvd <parameters>`) it runs the host-only checks: class UVDisparity on a thread without a device context takes
-// ssm_uvd_process_host -- no device call, so this half runs in the CPU suite and, built with -DSSM_UVD_HOST_ONLY against host/san_stub_device.cpp (which
-// compiles the library's own host pipeline), under the sanitizers.
+// ssm_uvd_process_host -- no device call, so this half runs in the CPU suite and, built with -DSSM_UVD_HOST_ONLY against host/san_stub_device.cpp and the
+// library's own host sources, under the sanitizers.
 #include "ssm/uvdisparity.hpp"
 #ifndef SSM_UVD_HOST_ONLY
 #include "ssm/rgbdframe.h"
@@ -73,6 +73,9 @@ static int host_checks()
     direct = direct && fl[2] == 3 && fl[5] == 2 && fl[0] == 1 && fl[3] == 0;
     ssm_uvd_destroy(u);
     CHECK("uvd_host_class_equals_the_c_function", direct);
+    // the same ssm_uvd_create with and without a device: it refuses a focal length that is not positive
+    P.f = 0; u = nullptr;
+    CHECK("uvd_create_refuses_a_focal_length_of_zero", ssm_uvd_create(nullptr, &P, &u) == SSM_E_INVAL && u == nullptr && string(ssm_last_error(nullptr)) == "uvd: the focal length must be positive");
     uv.Process(left, disp, vo, xyz, roi, ground, p1, p2);
     CHECK("uvd_host_class_keeps_its_kalman_state", uv.last_info.pitch_measured == i1.pitch_measured && uv.last_info.pitch_filtered != i1.pitch_filtered);
     cout << (fails ? "FAILED" : "ALL PASSED") << endl;

@@ -1,5 +1,5 @@
-// test_vocab_train.cpp -- vocabulary training on the host (csrc/ssm_vocab_train.inc over include/ssm/vocab_train_core.h, with the vocabulary object of
-// csrc/ssm_vocab.inc) as a stand-alone program: it compiles the library's own host sources into itself, so it needs neither libssm_hip.so nor a GPU and runs
+// test_vocab_train.cpp -- vocabulary training on the host (csrc/ssm_vocab_train_host.cpp over include/ssm/vocab_train_core.h, with the vocabulary object of
+// csrc/ssm_vocab.cpp) as a stand-alone program: it is linked with the library's own host sources, so it needs neither libssm_hip.so nor a GPU and runs
 // as it is under the CPU sanitizers (make SAN=asan san, or -fsanitize=address,undefined).  Checked here, from C++: every training descriptor comes back to the
 // word it was trained into (ssm_vocab_transform_host), the report and the weights are what the exported tree says, export -> create and save -> load give the
 // same bits, degenerate and invalid inputs, and the one-pass function with an empty cluster and an exact half split.
@@ -8,13 +8,14 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <string>
 #include <vector>
 #include <unistd.h>
+// what the host sources ask of their surroundings (csrc/ssm_host.h): the error path; and the one function checked here that the C ABI reaches only with a context argument
 static std::string g_err;
-static int vocab_fail(const std::string& msg) { g_err = msg; return SSM_E_INVAL; }
-#include "../csrc/ssm_vocab.inc"
-#include "../csrc/ssm_vocab_train.inc"
+int host_fail(ssm_ctx*, int code, const std::string& msg) { g_err = msg; return code; }
+int vt_kmajority_host(const uint8_t* desc, int n, const int32_t* node_of, const int32_t* cluster_of, int n_nodes, int k, uint8_t* centres, int32_t* assign_out);
 using namespace std;
 
 static int failures = 0;

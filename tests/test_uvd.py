@@ -224,5 +224,5 @@ def test_host_class_on_its_host_path_and_under_sanitizers():
         runs.append(os.path.join(HOST, f"test_uvd_{san}"))
     for exe in runs:
         r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
-        assert r.returncode == 0 and "ALL PASSED" in r.stdout and r.stdout.count("PASS ") == 6, r.stdout[-1500:] + r.stderr[-3000:]
+        assert r.returncode == 0 and "ALL PASSED" in r.stdout and r.stdout.count("PASS ") == 7, r.stdout[-1500:] + r.stderr[-3000:]
         assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-3000:]
