@@ -69,7 +69,7 @@ hipError_t k_copy_gray_strided(const uint8_t* img, int stride, const OrbGeom& g,
 }
 
 // ------------------------------------------------------------------ K2: pyramid level from the previous level
-// cv::resize INTER_LINEAR 8u fixed point (coefficient tables built on the host, oracle/orb.c sso_resize_tables).
+// cv::resize INTER_LINEAR 8u fixed point (coefficient tables built on the host: resize_tables in ssm_orb_plan.cpp, oracle/orb.c sso_resize_tables).
 // The per-CU texture-address unit spends >= 16 cycles on every vector-memory instruction whatever its width, so the
 // source rows a block needs are staged in LDS with 16-byte loads and the results leave as 16-byte stores:
 // one block = PY_ROWS output rows x the full output width; 16 output pixels per thread-iteration.
@@ -198,18 +198,12 @@ hipError_t k_pyramid(int n, const OrbGeom& g, uint8_t* pyr, const int32_t* const
 // from memory.  Here one block = one horizontal band of one frame: it converts the input rows its band needs (its own rows + the halo rows that the
 // coarser levels' own rows reach down to) to gray in LDS, then makes every level from the previous one in LDS, ping-ponging between two buffers, and
 // writes only its own rows of each level to the pyramid buffer as 16-byte stores.  The arithmetic is gray_kernel's and resize4_kernel's, so the
-// buffer is byte-identical to theirs.  Band rows (pyramid_band_plan, host): own(l, b) = [b h_l / B, (b + 1) h_l / B); comp(L-1, b) = own(L-1, b),
+// buffer is byte-identical to theirs.  Band rows (pyramid_band_plan, ssm_orb_plan.cpp): own(l, b) = [b h_l / B, (b + 1) h_l / B); comp(L-1, b) = own(L-1, b),
 // comp(l, b) = own(l, b) u src_rows(comp(l + 1, b)) -- contiguous.  The per-band halo is recomputed, not exchanged: 15 % more level-0 rows at B = 8, 33 % at B = 16,
 // and the kernel's time grows with them: more, smaller bands were slower.
-// A level's work items (pyr_items, ssm_internal.h; tests/test_pyramid_items.py checks them on the host): 8 pixels x the four rows of one block of the y
-// tables where every 8-pixel group of the level fits four dwords (scale factors below ~1.4; pyramid_xgroups), else resize4_kernel's 4 pixels x 4 rows.
-// The kernel's name starts with resize4_kernel so that the profiles attribute it to the pyramid stage.
-#ifndef PB_T
-#define PB_T 1024             // (512 threads: 154 us against 150 at B = 8)
-#endif
-#ifndef PB_BANDS
-#define PB_BANDS 8             // bands per frame in batches (640 x 480: 79 KB of LDS, two blocks per CU); measured per 250 frames with the 8-pixel items: 8 bands 150 us, 12: 173, 16: 208 (4-pixel items: 176, 197, 208)
-#endif
+// A level's work items (pyr_items, ssm_orb_plan.h; tests/test_pyramid_items.py checks them on the host): 8 pixels x the four rows of one block of the y
+// tables where every 8-pixel group of the level fits four dwords (scale factors below ~1.4; pyramid_xgroups, ssm_orb_plan.cpp), else resize4_kernel's 4 pixels x 4 rows.
+// The kernel's name starts with resize4_kernel so that the profiles attribute it to the pyramid stage.  PB_T threads per block, PB_BANDS bands per frame: ssm_orb_plan.h.
 // MODE 0: BGR, byte loads; 1: BGR, 12-byte loads (W % 4 == 0, input 4-aligned); 2: one channel.  WIDE: the plan has levels with 8-pixel items (batches);
 // false (the one-frame call: 32 blocks on the whole device, bound by each block's chain of latencies, not by issue): every level runs the shorter 4-pixel
 // items, and a thread's first tables of the next level are loaded ahead of the barrier -- registers that the 8-pixel loop cannot spare
@@ -424,95 +418,6 @@ hipError_t k_pyramid_bands(const uint8_t* img, int channels, int n, const OrbGeo
     if (t.wide) return mode == 2 ? launch(resize4_kernel_bands<2, true>) : mode == 1 ? launch(resize4_kernel_bands<1, true>) : launch(resize4_kernel_bands<0, true>);
     return mode == 2 ? launch(resize4_kernel_bands<2, false>) : mode == 1 ? launch(resize4_kernel_bands<1, false>) : launch(resize4_kernel_bands<0, false>);
 }
-int pyramid_block_threads() { return PB_T; }
-// the band count of a geometry: PB_BANDS per frame for batches, 32 for the one-frame call (one frame on more CUs); more bands where the level
-// buffers would not fit; none where a level needs the general resize kernel (p.bands stays 0).  The 8-pixel items are for batches, where the kernel is
-// bound by instruction issue; the one-frame call keeps the 4-pixel items on every level (shorter dependent chains per thread: measured 17.0 us against
-// 18.9 with the 8-pixel items, profiles/r10_pyramid_rows.md)
-bool pyramid_band_choose(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, const bool* wide_ok, bool batch, std::vector<int32_t>& tab, PyrBandPlan& p)
-{
-    static const int cand[2][8] = {{PB_BANDS, 12, 16, 24, 32, 48, 64, 0}, {32, 48, 64, 0}};
-    for (int i = 0; i < 8 && cand[batch ? 0 : 1][i]; i++)
-        if (cand[batch ? 0 : 1][i] >= (batch ? PB_BANDS : 0) && pyramid_band_plan(g, yofs, streaming, batch ? wide_ok : nullptr, cand[batch ? 0 : 1][i], tab, p)) return true;
-    return false;
-}
-// The band rows of every (band, level) for `bands` bands, from the host's y tables (yofs[l]: level l's source rows in level l-1).  false: the geometry
-// has no fused form at this band count (a level without the streaming x tables, fewer rows than bands, or level buffers beyond PB_MAX_LDS).
-bool pyramid_band_plan(const OrbGeom& g, const std::vector<int32_t>* yofs, const bool* streaming, const bool* wide_ok, int bands, std::vector<int32_t>& tab, PyrBandPlan& p)
-{
-    const int L = g.nlevels;
-    if (bands < 1) return false;
-    for (int l = 0; l < L; l++) if (g.L[l].h < bands || (l > 0 && !streaming[l])) return false;
-    tab.assign((size_t)bands * L * 4, 0);
-    size_t need[2] = {0, 0};
-    for (int b = 0; b < bands; b++) {
-        int lo = 0, hi = -1;
-        for (int l = L - 1; l >= 0; l--) {
-            const int h = g.L[l].h, olo = (int)((int64_t)b * h / bands), ohi = (int)((int64_t)(b + 1) * h / bands) - 1;
-            int clo = olo, chi = ohi;
-            if (l < L - 1) {                                               // the source rows of comp(l + 1): [yofs[lo], min(yofs[hi] + 1, h - 1)]
-                clo = std::min(clo, yofs[l + 1][lo]); chi = std::max(chi, std::min(yofs[l + 1][hi] + 1, h - 1));
-            }
-            int32_t* e = &tab[((size_t)b * L + l) * 4];
-            e[0] = clo; e[1] = chi; e[2] = olo; e[3] = ohi;
-            need[l & 1] = std::max(need[l & 1], (size_t)(chi - clo + 1) * g.L[l].stride);
-            lo = clo; hi = chi;
-        }
-    }
-    // PYR_SLACK bytes behind each buffer: a window starts at the 4-aligned address at or below a source byte of its row (<= stride - 4 from the row's
-    // start) and is 12 (4-pixel item, three dwords) or 16 bytes long (8-pixel item, four), so in a buffer's last row it ends up to 8 / 12 bytes past it
-    const size_t buf1 = (need[0] + PYR_SLACK + 15) & ~(size_t)15, lds = buf1 + need[1] + PYR_SLACK;
-    if (lds > PB_MAX_LDS) return false;
-    memset(&p.args, 0, sizeof(p.args));
-    p.args.buf1 = (int)buf1;
-    const int q0 = g.L[0].stride >> 4;                                     // level 0's items: 16 pixels
-    p.args.mulq0 = (uint32_t)(((1ull << 32) + q0 - 1) / q0);
-    for (int l = 1; l < L; l++) {
-        const int wide = wide_ok && wide_ok[l] ? 1 : 0;
-        const int gr = g.L[l].stride >> (wide ? 3 : 2);
-        p.args.wide |= (uint32_t)wide << l;
-        p.args.mulg[l] = (uint32_t)(((1ull << 32) + gr - 1) / gr);
-    }
-    p.bands = bands; p.lds = lds;
-    return true;
-}
-void pyramid_xgroups(const std::vector<int32_t>& xo, const std::vector<int16_t>& xa, const std::vector<int16_t>& ya, int dw, int dstride, int sstride,
-                     std::vector<uint32_t>& xg4, std::vector<uint32_t>& xg8, bool& fits4, bool& fits8)
-{
-    const int g4 = dstride / 4, g8 = dstride / 8;
-    xg4.assign((size_t)g4 * 8, 0u); xg8.assign((size_t)g8 * 12, 0u); fits4 = fits8 = true;
-    auto pair = [&](int x) { return (uint32_t)(uint16_t)xa[2 * x] | ((uint32_t)(uint16_t)xa[2 * x + 1] << 16); };
-    for (int x = 0; x < dw; x++) if (xa[2 * x] < 0 || xa[2 * x + 1] < 0 || xa[2 * x] + xa[2 * x + 1] > 2048) fits8 = false;
-    for (size_t y = 0; 2 * y + 1 < ya.size(); y++) if (ya[2 * y] < 0 || ya[2 * y + 1] < 0 || ya[2 * y] + ya[2 * y + 1] > 2048) fits8 = false;
-    for (int q = 0; q < g4; q++) {
-        uint32_t* e = &xg4[(size_t)q * 8];
-        const int x0 = 4 * q;
-        if (x0 >= dw) continue;                                               // padding group: coefficients 0 -> zeros, window at 0
-        const int base = xo[x0];
-        e[4] = (uint32_t)base;
-        for (int k = 0; k < 4 && x0 + k < dw; k++) {
-            const int off = xo[x0 + k] - base;
-            if (off < 0 || off > 6) fits4 = false;
-            e[k] = pair(x0 + k);
-            e[5] |= (uint32_t)(off & 15) << (4 * k);
-        }
-        if ((base & ~3) + 12 > sstride + PYR_SLACK) fits4 = false;            // (cannot happen: base < sstride)
-    }
-    for (int q = 0; q < g8; q++) {
-        uint32_t* e = &xg8[(size_t)q * 12];
-        const int x0 = 8 * q;
-        if (x0 >= dw) continue;
-        const int base = xo[x0];
-        e[8] = (uint32_t)base;
-        for (int k = 0; k < 8 && x0 + k < dw; k++) {
-            const int off = xo[x0 + k] - base - (k < 4 ? 0 : 4);              // from the pixel's dword pair: (0, 1) of the normalised window or (1, 2)
-            if (off < 0 || off > 6) fits8 = false;
-            e[k] = pair(x0 + k);
-            e[9] |= (uint32_t)(off & 15) << (4 * k);
-        }
-        if ((base & ~3) + 16 > sstride + PYR_SLACK) fits8 = false;
-    }
-}
 
 // ------------------------------------------------------------------ K5a: 7x7 sigma-2 Gaussian, fixed point
 // taps {18,34,49,55,49,34,18}; row pass fits u16 (<= 257*255); (v + 2^15) >> 16, saturate; BORDER_REFLECT_101.
@@ -631,37 +536,11 @@ hipError_t k_blur(int n, const OrbGeom& g, const uint8_t* pyr, uint8_t* blur, hi
 // Rows reflect as whole rows when the block stages its 64 input rows (58 output rows + 6) in LDS (coalesced 16-byte loads, p - 128 applied there); the
 // output leaves through an LDS tile as whole 128-byte rows.  Per pixel the VALU only repacks bytes (v_perm) and shifts / saturates the result: about a
 // quarter of the instructions of blur_kernel, which is VALU-issue bound.  Bit-exact with it (all sums are exact integers).
-// Coefficient table (built on the host by blur_mfma_tables): [F_same: 64 x 16 B][F_next: 64 x 16 B] then per level and 32-column unit [K half s: 2][lane: 64] x 16 B.
+// Coefficient table (built on the host by blur_mfma_tables, ssm_orb_plan.cpp): [F_same: 64 x 16 B][F_next: 64 x 16 B] then per level and 32-column unit [K half s: 2][lane: 64] x 16 B.
 #define BM_IN_RS 176      // bytes between staged input rows (160 used: columns [X0 - 16, X0 + 144))
 #define BM_OUT_RS 144     // bytes between rows of the output tile (128 used)
 typedef int bm_v4i __attribute__((ext_vector_type(4)));
 typedef int bm_v16i __attribute__((ext_vector_type(16)));
-size_t blur_mfma_table_bytes(const OrbGeom& g) { return (size_t)(128 + 128 * g.bt_units_total) * 16; }
-void blur_mfma_tables(const OrbGeom& g, void* host_out)
-{
-    static const int tc[7] = {18, 34, 49, 55, 49, 34, 18};
-    int8_t* o = reinterpret_cast<int8_t*>(host_out);
-    auto refl = [](int i, int n) { i = i < 0 ? -i : i; i = i >= n ? 2 * n - 2 - i : i; return i < 0 ? 0 : (i >= n ? n - 1 : i); };
-    for (int which = 0; which < 2; which++)                       // column pass: B[k][n], k in the accumulator's row order: element j of lane half h = row 8 (j >> 2) + 4 h + (j & 3)
-        for (int lane = 0; lane < 64; lane++)
-            for (int j = 0; j < 16; j++) {
-                const int n = lane & 31, h = lane >> 5, k = 8 * (j >> 2) + 4 * h + (j & 3) + 32 * which, d = k - n;
-                o[(which * 64 + lane) * 16 + j] = (int8_t)((d >= 0 && d <= 6) ? tc[d] : 0);
-            }
-    for (int l = 0; l < g.nlevels; l++) {
-        const LevelGeom& L = g.L[l];
-        for (int u = 0; u < (L.stride + 31) / 32; u++)
-            for (int s = 0; s < 2; s++)
-                for (int lane = 0; lane < 64; lane++)
-                    for (int j = 0; j < 16; j++) {
-                        const int n = lane & 31, h = lane >> 5, k = 32 * s + 16 * h + j;
-                        const int x_in = 32 * u - 16 + k, x_out = 32 * u + n;
-                        int coef = 0;
-                        if (x_out < L.w) for (int t = 0; t < 7; t++) if (refl(x_out + t - 3, L.w) == x_in) coef += tc[t];
-                        o[((size_t)(128 + (L.bt_units_off + u) * 128 + s * 64 + lane)) * 16 + j] = (int8_t)coef;
-                    }
-    }
-}
 __global__ void __launch_bounds__(256, 4)                    // 128 registers: four blocks per CU
 blur_mfma_kernel(const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur, OrbGeom g, const uint4* __restrict__ tab, int nframes)
 {

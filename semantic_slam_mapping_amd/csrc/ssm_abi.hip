@@ -1,4 +1,4 @@
-// ssm_abi.hip -- host side of libssm_hip.so: context, geometry, device workspace and the extern "C" entry points
+// ssm_abi.hip -- host side of libssm_hip.so: context, device workspace and the extern "C" entry points (the ORB geometry and plan: ssm_orb_plan.cpp)
 // declared in include/ssm_hip.h.  No computation of the path happens on the host: this file only sizes buffers,
 // moves caller data and enqueues the kernels of kernels_*.hip on the context stream.  There is NO CPU fallback: if
 // HIP is unusable ssm_create fails with SSM_E_NODEVICE / SSM_E_HIP.
@@ -13,103 +13,6 @@ thread_local std::string g_create_err;
 // the error path and the lock of the host-only sources (ssm_host.h), which do not know the context
 int host_fail(ssm_ctx* c, int code, const std::string& msg) { if (c) c->err = msg; else g_create_err = msg; return code; }
 std::unique_lock<std::mutex> host_lock(ssm_ctx* c) { return c ? std::unique_lock<std::mutex>(c->mu) : std::unique_lock<std::mutex>(); }
-
-// ---------------------------------------------------------------- geometry (mirrors ORBextractor ctor / ComputePyramid)
-// cells (of size `cell`, counted from origin + 3) that the scored positions [max(a - 1, EDGE), min(b + 1, n - EDGE)) of a FAST tile interior [a, b) touch
-static int fast_scored_cells(int a, int b, int n, int origin, int cell)
-{
-    const int s0 = a - 1 > SSM_EDGE ? a - 1 : SSM_EDGE, s1 = (b + 1 < n - SSM_EDGE ? b + 1 : n - SSM_EDGE) - 1;
-    return (s1 - origin - 3) / cell - (s0 - origin - 3) / cell + 1;
-}
-static int build_geometry(const ssm_config& c, OrbGeom& g, std::string& err)
-{
-    memset(&g, 0, sizeof(g));
-    if (c.orb_levels < 1 || c.orb_levels > SSM_MAX_LEVELS) { err = "orb_levels must be 1..12"; return SSM_E_INVAL; }
-    if (c.orb_features < 1) { err = "orb_features must be >= 1"; return SSM_E_INVAL; }
-    if (c.orb_iniThFAST < 1 || c.orb_minThFAST < 1 || c.orb_minThFAST > 254 || c.orb_iniThFAST > 254) { err = "FAST thresholds must be 1..254"; return SSM_E_INVAL; }
-    if (c.width < 64 || c.height < 64 || c.width > 4000 || c.height > 4000) { err = "frame size must be 64..4000"; return SSM_E_INVAL; }
-    if (!(c.orb_scale > 1.0f)) { err = "orb_scale must be > 1"; return SSM_E_INVAL; }
-    g.nlevels = c.orb_levels; g.W = c.width; g.H = c.height; g.ini_th = c.orb_iniThFAST; g.min_th = c.orb_minThFAST;
-    const double scaleFactor = (double)c.orb_scale;
-    float sf[SSM_MAX_LEVELS], inv[SSM_MAX_LEVELS];
-    sf[0] = 1.0f;
-    for (int i = 1; i < g.nlevels; i++) sf[i] = (float)(sf[i-1] * scaleFactor);
-    for (int i = 0; i < g.nlevels; i++) inv[i] = 1.0f / sf[i];
-    int feat[SSM_MAX_LEVELS];
-    {
-        const float factor = (float)(1.0f / scaleFactor);
-        float nd = c.orb_features * (1 - factor) / (1 - (float)pow((double)factor, (double)g.nlevels));
-        int sum = 0;
-        for (int l = 0; l < g.nlevels - 1; l++) { feat[l] = cv_round_f(nd); sum += feat[l]; nd *= factor; }
-        feat[g.nlevels-1] = c.orb_features - sum > 0 ? c.orb_features - sum : 0;
-    }
-    {
-        const int vmax = (int)floor(SSM_HALF_PATCH * sqrt(2.0) / 2 + 1), vmin = (int)ceil(SSM_HALF_PATCH * sqrt(2.0) / 2);
-        const double hp2 = SSM_HALF_PATCH * SSM_HALF_PATCH;
-        int um[SSM_HALF_PATCH + 2] = {0};
-        for (int v = 0; v <= vmax; ++v) um[v] = (int)lrint(sqrt(hp2 - v * v));
-        for (int v = SSM_HALF_PATCH, v0 = 0; v >= vmin; --v) { while (um[v0] == um[v0 + 1]) ++v0; um[v] = v0; ++v0; }
-        for (int v = 0; v <= SSM_HALF_PATCH; v++) g.umax[v] = um[v];
-    }
-    int off = 0, cells = 0, cands = 0, sels = 0, tiles = 0, ftiles = 0, btiles = 0, bunits = 0, boff = 0;
-    for (int l = 0; l < g.nlevels; l++) {
-        LevelGeom& L = g.L[l];
-        L.w = cv_round_f((float)c.width * inv[l]); L.h = cv_round_f((float)c.height * inv[l]);
-        if (L.w < 2 * SSM_EDGE + 8 + 30 || L.h < 2 * SSM_EDGE + 8 + 30) { err = "pyramid level too small for the ORB border; lower orb_levels"; return SSM_E_INVAL; }
-        L.stride = (L.w + 15) & ~15; L.img_off = off; off += L.stride * L.h; L.boff = boff; boff += L.stride * ((L.h + 7) & ~7);      /* rows 16-B aligned: wide loads/stores everywhere */
-        L.minBX = SSM_EDGE - 3; L.minBY = SSM_EDGE - 3; L.maxBX = L.w - SSM_EDGE + 3; L.maxBY = L.h - SSM_EDGE + 3;
-        const float width = (float)(L.maxBX - L.minBX), height = (float)(L.maxBY - L.minBY);
-        L.nCols = (int)(width / 30.f); L.nRows = (int)(height / 30.f);
-        L.wCell = (int)ceilf(width / L.nCols); L.hCell = (int)ceilf(height / L.nRows);
-        if (L.wCell < 17 || L.hCell < 5) { err = "FAST cell too small"; return SSM_E_INVAL; }   /* FAST tiles: at most 8 x 8 cells (checked below) */
-        L.mulW = (uint32_t)(((1ull << 32) + L.wCell - 1) / L.wCell); L.mulH = (uint32_t)(((1ull << 32) + L.hCell - 1) / L.hCell);
-        L.cell_off = cells; cells += L.nCols * L.nRows;
-        L.tiles_x = (L.w + 127) / 128; L.mulTX = (uint32_t)(((1ull << 32) + L.tiles_x - 1) / L.tiles_x); L.tile_off = tiles; tiles += L.tiles_x * ((L.h + 31) / 32);
-        /* FAST reports nothing within SSM_EDGE of the border: its tiles cover that window only, as few as fit and all but the last of each row and
-           column of one size (640x480, 8 levels: 227 tiles; interiors 121 x 32 at level 0), so that little of a tile lies outside the window */
-        {
-            const int fw = L.w - 2 * SSM_EDGE, fh = L.h - 2 * SSM_EDGE;
-            const int kx = (fw + FT_W - 1) / FT_W, ky = (fh + FT_H - 1) / FT_H;
-            L.ftw = (fw + kx - 1) / kx; L.fth = (fh + ky - 1) / ky;
-            L.ftiles_x = (fw + L.ftw - 1) / L.ftw;
-            L.fmulTX = (uint32_t)(((1ull << 32) + L.ftiles_x - 1) / L.ftiles_x); L.ftile_off = ftiles; ftiles += L.ftiles_x * ((fh + L.fth - 1) / L.fth);
-            /* the scored rectangle of a tile (interior + apron) touches at most 8 x 8 cells: pass 2's emptyrow bytes and the 64 lmax slots of fast_tile */
-            for (int x0 = SSM_EDGE; x0 < L.w - SSM_EDGE; x0 += L.ftw)
-                if (fast_scored_cells(x0, x0 + L.ftw, L.w, L.minBX, L.wCell) > 8) { err = "FAST tile spans more than 8 cell columns"; return SSM_E_INVAL; }
-            for (int y0 = SSM_EDGE; y0 < L.h - SSM_EDGE; y0 += L.fth)
-                if (fast_scored_cells(y0, y0 + L.fth, L.h, L.minBY, L.hCell) > 8) { err = "FAST tile spans more than 8 cell rows"; return SSM_E_INVAL; }
-        }
-        L.bt_x = (L.stride + 127) / 128; L.bt_off = btiles; btiles += L.bt_x; L.bt_units_off = bunits; bunits += (L.stride + 31) / 32;
-        if (L.nCols * L.nRows >= (1 << 17)) { err = "too many FAST cells"; return SSM_E_INVAL; }
-        L.nfeat = feat[l];
-        if (L.nfeat + 3 > SSM_MAX_NODES - 8) { err = "too many features per level for the LDS quad-tree (max 1013 per level)"; return SSM_E_INVAL; }
-        L.cand_off = cands; L.cand_cap = ((L.w + 1) / 2 + L.nCols + 1) * ((L.h + 1) / 2 + L.nRows + 1); cands += L.cand_cap;
-        if (L.cand_cap > 65535 * 16) { err = "level too large"; return SSM_E_INVAL; }
-        L.sel_off = sels; L.sel_cap = L.nfeat + 3; sels += L.sel_cap;
-        int nIni = (int)roundf((float)(L.maxBX - L.minBX) / (float)(L.maxBY - L.minBY)); if (nIni < 1) nIni = 1;
-        L.nIni = nIni; L.hX = (float)(L.maxBX - L.minBX) / nIni;
-        if (4 * nIni + 8 > SSM_MAX_NODES) { err = "aspect ratio too extreme"; return SSM_E_INVAL; }
-        L.sf = sf[l];
-    }
-    g.bt_total = btiles; g.bt_units_total = bunits; g.blur_bytes = boff;
-    g.pyr_bytes = off; g.tiles_total = tiles; g.ftiles_total = ftiles; g.cells_total = cells; g.cand_total = cands; g.sel_total = sels;
-    g.cap = c.orb_features + 3 * g.nlevels;
-    return SSM_OK;
-}
-void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, std::vector<int16_t>& coef)
-{
-    ofs.resize(dsize); coef.resize(2 * dsize);
-    const double inv_scale = (double)dsize / ssize, scale = 1.0 / inv_scale;
-    for (int d = 0; d < dsize; d++) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= (float)s;
-        if (s < 0) { f = 0.f; s = 0; }
-        if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
-        ofs[d] = s;
-        coef[2*d] = (int16_t)cv_round_f((1.f - f) * 2048.f); coef[2*d+1] = (int16_t)cv_round_f(f * 2048.f);
-    }
-}
 
 // ---------------------------------------------------------------- helpers
 int ensure_scratch(ssm_ctx* c, size_t bytes, DevBuf<uint8_t>* buf)
@@ -205,58 +108,41 @@ static int orb_work_alloc(ssm_ctx* c, OrbWork& w)
     DALLOC(c, w.kpaux, (size_t)B * g.sel_total * 2);             // KpAux + KpRec per slot
     return SSM_OK;
 }
+// a device buffer of the vector's size, holding its elements
+template <class T> static int upload(ssm_ctx* c, DevBuf<T>& d, const std::vector<T>& v)
+{
+    DALLOC(c, d, v.size());
+    HIPCHK(c, hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return SSM_OK;
+}
+#define UPLOAD(ctx, buf, vec) do { int r__ = upload(ctx, buf, vec); if (r__) return r__; } while (0)
+// the streams, the plan's tables on the device (ssm_orb_plan.h OrbPlan, built by ssm_create) and the workspaces
 static int ctx_init(ssm_ctx* c)
 {
-    const ssm_config& cfg = c->cfg; const OrbGeom& g = c->g; const int B = c->B, W = g.W, H = g.H;
+    const ssm_config& cfg = c->cfg; const OrbPlan& P = c->plan; const OrbGeom& g = c->g; const int B = c->B, W = g.W, H = g.H;
     HIPCHK(c, c->main.stream.ensure());
     c->dev.id = c->device;             // (a failed query keeps DeviceInfo's fall-back)
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && v > 0) c->dev.cus = v; }
     { int v = 0; if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, c->device) == hipSuccess && v > 0) c->dev.max_lds = v; }
     c->map_div_exact = k_map_div(cfg.camera, c->map_div);
-    DALLOC(c, c->d_pattern, 1024);
-    HIPCHK(c, hipMemcpy(c->d_pattern, cfg.brief_pattern ? cfg.brief_pattern : k_default_pattern, 1024, hipMemcpyHostToDevice));
-    {   float pf[1024]; const int8_t* src = cfg.brief_pattern ? cfg.brief_pattern : k_default_pattern;
-        for (int i = 0; i < 1024; i++) pf[i] = (float)src[i];
-        { const char* e = getenv("SSM_BLUR_VARIANT"); c->blur_mfma = !(e && atoi(e) == 0); }
-        { std::vector<uint8_t> bt(blur_mfma_table_bytes(c->g)); blur_mfma_tables(c->g, bt.data());
-          DALLOC(c, c->d_blur_tab, bt.size());
-          HIPCHK(c, hipMemcpy(c->d_blur_tab, bt.data(), bt.size(), hipMemcpyHostToDevice)); }
-        DALLOC(c, c->d_pattern_f, 1024);
-        HIPCHK(c, hipMemcpy(c->d_pattern_f, pf, sizeof(pf), hipMemcpyHostToDevice)); }
-    std::vector<int32_t> yall[SSM_MAX_LEVELS]; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
+    const int8_t* pat = cfg.brief_pattern ? cfg.brief_pattern : k_default_pattern;
+    { const char* e = getenv("SSM_BLUR_VARIANT"); c->blur_mfma = !(e && atoi(e) == 0); }
+    UPLOAD(c, c->d_pattern, std::vector<int8_t>(pat, pat + 1024));
+    UPLOAD(c, c->d_blur_tab, P.blur_tab);
+    UPLOAD(c, c->d_pattern_f, std::vector<float>(pat, pat + 1024));
     for (int l = 1; l < g.nlevels; l++) {
-        std::vector<int32_t> xo, yo; std::vector<int16_t> xa, ya;
-        resize_tables(g.L[l-1].w, g.L[l].w, xo, xa); resize_tables(g.L[l-1].h, g.L[l].h, yo, ya);
-        yall[l] = yo;
-        // per 4-pixel group (the streaming kernel takes a group's source bytes with one 8-byte load per row) and per 8-pixel group (the fused kernel:
-        // four LDS dwords per row): the (a0, a1) pairs, the byte offset of the first pixel's left neighbour and each pixel's offset from it
-        std::vector<uint32_t> xg, xg8; bool fits = false, fits8 = false;
-        pyramid_xgroups(xo, xa, ya, g.L[l].w, g.L[l].stride, g.L[l-1].stride, xg, xg8, fits, fits8);
-        while (yo.size() & 3) { yo.push_back(yo.back()); ya.push_back(ya[ya.size() - 2]); ya.push_back(ya[ya.size() - 2]); }   // resize4_kernel reads the y tables four rows at a time
-        DALLOC(c, c->d_xofs[l], xo.size()); DALLOC(c, c->d_xa[l], xa.size()); DALLOC(c, c->d_yofs[l], yo.size()); DALLOC(c, c->d_ya[l], ya.size());
-        HIPCHK(c, hipMemcpy(c->d_xofs[l], xo.data(), xo.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_xa[l], xa.data(), xa.size() * 2, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_yofs[l], yo.data(), yo.size() * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(c->d_ya[l], ya.data(), ya.size() * 2, hipMemcpyHostToDevice));
-        if (fits) {
-            DALLOC(c, c->d_xgrp[l], xg.size());
-            HIPCHK(c, hipMemcpy(c->d_xgrp[l], xg.data(), xg.size() * 4, hipMemcpyHostToDevice));
-            streaming[l] = true;
-        }
-        if (fits && fits8) {
-            DALLOC(c, c->d_xgrp8[l], xg8.size());
-            HIPCHK(c, hipMemcpy(c->d_xgrp8[l], xg8.data(), xg8.size() * 4, hipMemcpyHostToDevice));
-            wide_ok[l] = true;
-        }
+        UPLOAD(c, c->d_xofs[l], P.xofs[l]); UPLOAD(c, c->d_xa[l], P.xa[l]); UPLOAD(c, c->d_yofs[l], P.yofs[l]); UPLOAD(c, c->d_ya[l], P.ya[l]);
+        if (P.streaming[l]) UPLOAD(c, c->d_xgrp[l], P.xgrp[l]);
+        if (P.wide_ok[l]) UPLOAD(c, c->d_xgrp8[l], P.xgrp8[l]);
         auto& T = c->pyr_tabs;
         T.xofs[l] = c->d_xofs[l]; T.xa[l] = c->d_xa[l]; T.yofs[l] = c->d_yofs[l]; T.ya[l] = c->d_ya[l]; T.xgrp[l] = c->d_xgrp[l]; T.xgrp8[l] = c->d_xgrp8[l];
     }
     // the fused pyramid's band tables (none where a level needs the general resize kernel)
     for (int k = 0; k < 2; k++) {
-        PyrBandPlan& p = k ? c->pyr_bands1 : c->pyr_bands; DevBuf<int32_t>& d = k ? c->d_band_tab1 : c->d_band_tab; std::vector<int32_t> tab;
-        if (!pyramid_band_choose(g, yall, streaming, wide_ok, k == 0, tab, p)) continue;
-        DALLOC(c, d, tab.size());
-        HIPCHK(c, hipMemcpy(d, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        PyrBandPlan& p = k ? c->pyr_bands1 : c->pyr_bands; DevBuf<int32_t>& d = k ? c->d_band_tab1 : c->d_band_tab;
+        p = P.bands[k];
+        if (!p.bands) continue;
+        UPLOAD(c, d, P.band_tab[k]);
         p.d_tab = d;
     }
     { const int r = orb_work_alloc(c, c->chain[0].work); if (r) return r; }
@@ -291,7 +177,7 @@ extern "C" int ssm_create(int device, const ssm_config* cfg, ssm_ctx** out)
     { const char* e = getenv("SSM_MAP_STREAM"); c->map_stream = e ? atoi(e) : 1; }
     { const char* e = getenv("SSM_MATCH_VARIANT"); c->match_mfma = !(e && atoi(e) == 0); }      // 0: the VALU matcher in the sequence path (A/B runs)
     c->B = cfg->max_batch > 0 ? cfg->max_batch : 1; c->R = cfg->tracker_ref_frames > 0 ? cfg->tracker_ref_frames : 1;
-    int r = build_geometry(*cfg, c->g, c->err);
+    int r = orb_plan_build(*cfg, c->plan, c->err);
     if (!r && (cfg->voxel_capacity_log2 < 8 || cfg->voxel_capacity_log2 > 28)) { c->err = "voxel_capacity_log2 must be 8..28"; r = SSM_E_INVAL; }
     if (!r && cfg->voxel_max_capacity_log2 != 0 && (cfg->voxel_max_capacity_log2 < cfg->voxel_capacity_log2 || cfg->voxel_max_capacity_log2 > 28)) { c->err = "voxel_max_capacity_log2 must be voxel_capacity_log2..28 (0: 28)"; r = SSM_E_INVAL; }
     if (!r) c->vox_max_log2 = cfg->voxel_max_capacity_log2 ? cfg->voxel_max_capacity_log2 : 28;
@@ -420,89 +306,6 @@ static int run_orb(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_img, 
     return r ? r : orb_describe(c, s, w, d_depth, nb, kps, desc, pos3d, nkp);
 }
 
-extern "C" int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int cap, int* ntiles, int32_t* limits)
-{
-    if (!cfg || !ntiles) return SSM_E_INVAL;
-    OrbGeom g; std::string err;
-    { const int r = build_geometry(*cfg, g, err); if (r) return r; }
-    if (limits) { const int32_t v[6] = {FT_LDS_BYTES, FT_SW / 4, FT_SH, FT_PW, FT_PH, FT_STAGE}; memcpy(limits, v, sizeof(v)); }
-    *ntiles = g.ftiles_total;
-    if (!tiles) return SSM_OK;
-    if (cap < g.ftiles_total) return SSM_E_INVAL;
-    for (int l = 0; l < g.nlevels; l++) {
-        const LevelGeom& L = g.L[l];
-        const int ntl = (l + 1 < g.nlevels ? g.L[l+1].ftile_off : g.ftiles_total) - L.ftile_off;
-        for (int t = 0; t < ntl; t++) {
-            int x0, x1, y0, y1;
-            ftile_rect(L, t % L.ftiles_x, t / L.ftiles_x, x0, x1, y0, y1);
-            /* the same rectangle and cells as fast_tile */
-            const int xs0 = std::max(x0 - 1, SSM_EDGE), xs1 = std::min(x1 + 1, L.w - SSM_EDGE), ys0 = std::max(y0 - 1, SSM_EDGE), ys1 = std::min(y1 + 1, L.h - SSM_EDGE);
-            const int ncx = (xs1 - 1 - L.minBX - 3) / L.wCell - (xs0 - L.minBX - 3) / L.wCell + 1, ncy = (ys1 - 1 - L.minBY - 3) / L.hCell - (ys0 - L.minBY - 3) / L.hCell + 1;
-            const int32_t v[16] = {l, x0, x1, y0, y1, xs0, xs1, ys0, ys1, (xs1 - xs0 + 3) / 4, ys1 - ys0, ncx, ncy, L.w, L.h, L.stride};
-            memcpy(tiles + 16 * (size_t)(L.ftile_off + t), v, sizeof(v));
-        }
-    }
-    return SSM_OK;
-}
-
-extern "C" int ssm_debug_pyramid_plan(const ssm_config* cfg, int bands, int32_t* items, int cap, int* nitems, int32_t* band_tab, int32_t* limits)
-{
-    if (!cfg || !nitems) return SSM_E_INVAL;
-    OrbGeom g; std::string err;
-    { const int r = build_geometry(*cfg, g, err); if (r) return r; }
-    const int L = g.nlevels;
-    std::vector<int32_t> yall[SSM_MAX_LEVELS], xall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
-    for (int l = 1; l < L; l++) {
-        std::vector<int16_t> xa, ya; std::vector<uint32_t> xg, xg8; bool f4, f8;
-        resize_tables(g.L[l-1].w, g.L[l].w, xall[l], xa); resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya);
-        pyramid_xgroups(xall[l], xa, ya, g.L[l].w, g.L[l].stride, g.L[l-1].stride, xg, xg8, f4, f8);
-        streaming[l] = f4; wide_ok[l] = f4 && f8;
-    }
-    PyrBandPlan p;
-    const bool ok = bands > 0 ? pyramid_band_plan(g, yall, streaming, wide_ok, bands, tab, p) : pyramid_band_choose(g, yall, streaming, wide_ok, bands == 0, tab, p);
-    if (limits) {
-        int32_t v[16 + 3 * SSM_MAX_LEVELS] = {ok ? p.bands : 0, (int32_t)p.lds, p.args.buf1, PYR_SLACK, pyramid_block_threads(), PB_MAX_LDS, L};
-        for (int l = 1; l < L; l++) { v[7] |= (streaming[l] ? 1 : 0) << l; v[8] |= (wide_ok[l] ? 1 : 0) << l; }
-        if (ok) v[9] = (int32_t)p.args.wide;
-        for (int l = 0; l < L; l++) { v[16 + 3 * l] = g.L[l].w; v[17 + 3 * l] = g.L[l].h; v[18 + 3 * l] = g.L[l].stride; }
-        memcpy(limits, v, sizeof(v));
-    }
-    *nitems = 0;
-    if (!ok) return SSM_OK;                                              // no fused form: limits[0] == 0
-    if (band_tab) memcpy(band_tab, tab.data(), tab.size() * 4);
-    int n = 0;
-    for (int b = 0; b < p.bands; b++)
-        for (int l = 1; l < L; l++) {
-            const int32_t* rs = &tab[((size_t)b * L + l - 1) * 4]; const int32_t* r = &tab[((size_t)b * L + l) * 4];
-            const LevelGeom& A = g.L[l-1]; const LevelGeom& B = g.L[l];
-            const int wide = pyr_wide(p.args, l), px = wide ? 8 : 4;
-            const PyrItems it = pyr_items(B.stride, wide, r[0], r[1]);
-            for (int i = 0; i < it.items; i++, n++) {
-                if (!items) continue;
-                if (n >= cap) return SSM_E_INVAL;
-                /* the rows and windows of item i, as resize4_kernel_bands walks them */
-                const int blk = pyr_item_run(i, p.args.mulg[l]), gi = i - blk * it.groups;
-                const int x0 = px * gi, base = x0 < B.w ? xall[l][x0] : 0;
-                int ylo = 1 << 30, yhi = -1, slo = 1 << 30, shi = -1, rlo = 1 << 30, rhi = -(1 << 30);
-                    for (int j = 0; j < 4; j++) {
-                        const int y = it.c0 + 4 * blk + j;
-                        if (y < r[0] || y > r[1]) continue;
-                        ylo = std::min(ylo, y); yhi = std::max(yhi, y);
-                        const int sy[2] = {yall[l][y], std::min(yall[l][y] + 1, A.h - 1)};
-                        for (int k = 0; k < 2; k++) {
-                            const int e = (sy[k] - rs[0]) * A.stride + base;
-                            slo = std::min(slo, sy[k]); shi = std::max(shi, sy[k]);
-                            rlo = std::min(rlo, e & ~3); rhi = std::max(rhi, (e & ~3) + (wide ? 16 : 12));
-                        }
-                    }
-                const int32_t v[12] = {l, b, px, gi, ylo, yhi, slo, shi, rlo, rhi, (ylo - r[0]) * B.stride + px * gi, (yhi - r[0]) * B.stride + px * gi + px};
-                memcpy(items + 12 * (size_t)n, v, sizeof(v));
-            }
-        }
-    *nitems = n;
-    return SSM_OK;
-}
-
 extern "C" void ssm_debug_live_allocations(int* buffers, size_t* device_bytes, size_t* pinned_bytes)
 {
     if (buffers) *buffers = DevBufLive::buffers.load();
@@ -533,11 +336,9 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
     if (bands < 0) p.bands = 0;
     else if (bands == 0) p = n > 1 ? c->pyr_bands : c->pyr_bands1;
     else {
-        std::vector<int32_t> yall[SSM_MAX_LEVELS], tab; bool streaming[SSM_MAX_LEVELS] = {}, wide_ok[SSM_MAX_LEVELS] = {};
-        for (int l = 1; l < g.nlevels; l++) { std::vector<int16_t> ya; resize_tables(g.L[l-1].h, g.L[l].h, yall[l], ya); streaming[l] = c->d_xgrp[l] != nullptr; wide_ok[l] = c->d_xgrp8[l] != nullptr; }
-        if (!pyramid_band_plan(g, yall, streaming, wide_ok, bands, tab, p)) FAIL(c, SSM_E_INVAL, "no fused pyramid at this band count");
-        DALLOC(c, own_tab, tab.size()); p.d_tab = own_tab;
-        HIPCHK(c, hipMemcpy(own_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+        std::vector<int32_t> tab;
+        if (!orb_plan_bands(c->plan, bands, tab, p)) FAIL(c, SSM_E_INVAL, "no fused pyramid at this band count");
+        UPLOAD(c, own_tab, tab); p.d_tab = own_tab;
     }
     int r = make_pyramid(c, c->main.stream, c->chain[0].work, c->d_scratch, channels, n, p);
     if (bands > 0) { hipStreamSynchronize(c->main.stream); own_tab.reset(); }

@@ -181,7 +181,8 @@ struct ssm_ctx {
     //   side[2]  the third chain, used when a call has more than two sub-batches.  Stereo: SGBM, third workspace
     Lane main, side[3]; Event forked; bool side_ready = false /* ensure_side_streams completed */; int map_stream = 1;
     ssm_config cfg{};
-    OrbGeom g{};
+    OrbPlan plan;                       // what cfg fixes of the ORB front end (ssm_orb_plan.h), built by ssm_create; ctx_init uploads its tables
+    const OrbGeom& g = plan.g;          // its geometry, under the name every launcher reads
     std::string err;
     int B = 1, R = 5;
     // constant tables
@@ -190,7 +191,7 @@ struct ssm_ctx {
     DevBuf<int32_t> d_xofs[SSM_MAX_LEVELS], d_yofs[SSM_MAX_LEVELS]; DevBuf<int16_t> d_xa[SSM_MAX_LEVELS], d_ya[SSM_MAX_LEVELS];
     DevBuf<uint32_t> d_xgrp[SSM_MAX_LEVELS];     // resize4_kernel's per-group constants (null: the level uses the general resize kernel)
     DevBuf<uint32_t> d_xgrp8[SSM_MAX_LEVELS];    // the fused pyramid's 8-pixel groups (null: the level's groups do not fit that layout; it keeps the 4-pixel item)
-    // the per-level tables above as the plain pointer arrays the pyramid launchers take (filled where the tables are made: ctx_init)
+    // the per-level tables above as the plain pointer arrays the pyramid launchers take (filled where the tables are uploaded: ctx_init)
     struct { const int32_t *xofs[SSM_MAX_LEVELS], *yofs[SSM_MAX_LEVELS]; const int16_t *xa[SSM_MAX_LEVELS], *ya[SSM_MAX_LEVELS]; const void *xgrp[SSM_MAX_LEVELS], *xgrp8[SSM_MAX_LEVELS]; } pyr_tabs = {};
     PyrBandPlan pyr_bands, pyr_bands1;       // resize4_kernel_bands for batches / for the per-frame call (bands == 0: gray_kernel + k_pyramid)
     DevBuf<int32_t> d_band_tab, d_band_tab1; // their band tables (PyrBandPlan::d_tab points here)
@@ -253,8 +254,6 @@ struct ssm_ctx {
 #define FAIL(ctx, code, msg) do { (ctx)->err = (msg); return (code); } while (0)
 #define HIPCHK(ctx, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__); return SSM_E_HIP; } } while (0)
 
-inline int cv_round_f(float v) { return (int)lrint((double)v); }
-
 #define DALLOC(ctx, buf, n) do { int r__ = (buf).alloc(ctx, (size_t)(n)); if (r__) return r__; } while (0)
 #define NCCLCHK(ctx, expr) do { ncclResult_t e__ = (expr); if (e__ != ncclSuccess) { (ctx)->err = std::string(#expr) + ": " + ncclGetErrorString(e__); return SSM_E_COMM; } } while (0)
 template <class T, bool Pinned> int DevBuf<T, Pinned>::alloc_bytes(ssm_ctx* c, size_t bytes)
@@ -269,7 +268,6 @@ template <class T, bool Pinned> int DevBuf<T, Pinned>::alloc_bytes(ssm_ctx* c, s
 }
 // ssm_abi.hip
 extern SSM_HIDDEN thread_local std::string g_create_err;
-SSM_HIDDEN void resize_tables(int ssize, int dsize, std::vector<int32_t>& ofs, std::vector<int16_t>& coef);
 SSM_HIDDEN int ensure_scratch(ssm_ctx* c, size_t bytes, DevBuf<uint8_t>* buf = nullptr);     // buf: c->d_scratch (the default) or c->d_scratch2
 SSM_HIDDEN int ensure_pinned(ssm_ctx* c, size_t bytes);
 SSM_HIDDEN void prof_begin(ssm_ctx* c, hipStream_t s, const char* name);     // s: the stream the stage's kernels run on

@@ -1,4 +1,4 @@
-"""The FAST tile plan (build_geometry: tiles fitted to each level's FAST window), read on the host through ssm_debug_fast_plan: no GPU.
+"""The FAST tile plan (build_geometry in csrc/ssm_orb_plan.cpp: tiles fitted to each level's FAST window), read on the host through ssm_debug_fast_plan: no GPU.
 For each geometry: every position of every level's window [19, w - 19) x [19, h - 19) lies in exactly one tile interior and is quick-tested
 by it; the scored rectangles are the interiors plus their NMS neighbours inside the window; no scored rectangle touches more than 8 x 8 cells;
 each tile fits the kernel's LDS arrays; no scored position reads a staged word that was clamped.  The LDS the built FAST kernels take is read

@@ -1,5 +1,5 @@
 """The fused pyramid's work items (resize4_kernel_bands), read on the host through ssm_debug_pyramid_plan: no GPU.  The entry lists the items of
-every (band, level) with the decomposition the kernel itself uses (pyr_items / pyr_item_run in ssm_internal.h).  For each geometry, level count,
+every (band, level) with the decomposition the kernel itself uses (pyr_items / pyr_item_run in csrc/ssm_orb_plan.h; the plan itself is csrc/ssm_orb_plan.cpp).  For each geometry, level count,
 band count and scale factor: the items of a (band, level) cover each (comp row, column group) exactly once; every source row an item reads lies
 inside the band's comp rows of the level below; every LDS byte its windows read, and every byte it writes, lies inside the level buffer the plan
 allocates, and the windows do hold the pixels the x tables point at; a level is given the 8-pixel item exactly where every 8-pixel group fits
