@@ -591,6 +591,11 @@ int ssm_debug_pyramid(ssm_ctx* ctx, const uint8_t* img, int channels, int n, int
  * *ntiles: the tile count (tiles NULL: only that; SSM_E_INVAL when cap is smaller).  limits (6 ints, may be NULL): the static LDS bytes of the FAST
  * kernel, the most groups and scored rows its arrays hold, the staged pixel row width and row count, the staging area (candidates) */
 int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int cap, int* ntiles, int32_t* limits);
+/* the FAST kernel's compass quick test (include/ssm/fast_quick_core.h, the code the kernel runs), on the host only: n groups of four horizontally
+ * adjacent positions.  words: per group the five pixel dwords the kernel reads -- the centres (byte j = position j), the dwords left and right of
+ * them in the row, the dwords 3 rows up and 3 rows down.  threshold: 0 .. 255; valid: 1 .. 4, the positions of the group inside the scored
+ * rectangle (the others never pass).  out: per group one byte, bit j = position j passes */
+int ssm_debug_fast_quick(const uint32_t* words, int n, int threshold, int valid, uint8_t* out);
 /* the fused pyramid's plan of a configuration, on the host only (no context, no device): the work items of every (band, level >= 1), listed by the
  * decomposition the kernel uses.  bands > 0: that band count; 0: what batches run; -1: what the one-frame call runs (4-pixel items on every level).  Per item, 12 ints: level, band,
  * pixels per item (8, or 4 where the level's groups do not fit the 8-pixel layout), column group, first and last output row it writes, first and last

@@ -3,6 +3,7 @@
 // batched over frames (grid.y = frame).  Integer / byte work, HBM- and LDS-bound: no MFMA here by design.
 // Contracts (rounding rules, tie-breaks) are those of oracle/orb.c; compile with -ffp-contract=off.
 #include "ssm_internal.h"
+#include "../../include/ssm/fast_quick_core.h"
 #include <cstdlib>
 #include <type_traits>
 #include <algorithm>
@@ -671,7 +672,9 @@ hipError_t k_blur_mfma(int n, const OrbGeom& g, const uint8_t* pyr, uint8_t* blu
 //   * keep(p, t)  <=>  S(p) > t  and no same-cell neighbour n with S(n) >= S(p)      (for t in {ini, min}: a neighbour
 //     with S(n) >= S(p) > t is itself a corner at t), so ONE local-maximum flag serves both thresholds;
 //   * a 9-arc always contains two adjacent compass points, so pixels failing that test at minThFAST are dropped before
-//     scoring (about 3/4 of a textured image); survivors are compacted in LDS and scored densely;
+//     scoring (about 3/4 of a textured image); survivors are compacted in LDS and scored densely.  The test is ssm_fq::quick4
+//     (include/ssm/fast_quick_core.h: four positions at a time, raw ring values against c + t and c - t), host and device code, so that
+//     ssm_debug_fast_quick checks it exhaustively without a GPU;
 //   * the consumer (quad-tree kernel) keeps a maximum iff S > (cellmax > iniThFAST ? iniThFAST : minThFAST)  ==  "retry the cell at minThFAST";
 //   * TWO PASSES (round 3).  In a cell that has a corner at iniThFAST only maxima with S > ini survive, and a neighbour with S <= ini can neither be
 //     one nor suppress one (suppression needs S(n) >= S(p) > ini), so such a cell only needs the positions that pass the quick test AT ini: pass 1
@@ -718,11 +721,14 @@ __device__ __forceinline__ int fast_S(const uint8_t* p, int st)
     bright = max(bright, mn9[15]); dark = min(dark, mx9[15]);
     return max(bright, -dark);
 }
-// The same score for TWO positions per lane.  The ring differences of position A live in the low half of a dword and those of B in the high half,
+// The same score for TWO positions per lane.  The ring pixels of position A live in the low half of a dword and those of B in the high half,
 // as f16 DENORMALS: the bit pattern n (0..255) is the half-precision number n * 2^-24, sums and differences of such numbers are exact (|n| < 1024) and
 // kernels run with f16 denormals enabled, so v_pk_add_f16 is an exact packed 16-bit subtract whose results order like the integers -- and gfx950 has the
 // three-input packed v_pk_minimum3_f16 / v_pk_maximum3_f16 (there is no three-input packed INTEGER min / max): one instruction does what two v_min3_i32
-// did.  Result: S_A | S_B << 16 (each clamped at 0 like fast_S's callers do).
+// did.  Min and max commute with subtracting the centre, so the arcs are taken over the RAW ring values and the centre is subtracted from the two
+// results only (16 subtractions fewer than differencing every ring value).  Result: S_A | S_B << 16 (each clamped at 0 like fast_S's callers do).
+// (The pack of B's byte into the high half stays one instruction per ring value: gfx950 runs with SRAM ECC, where a d16_hi load does not preserve the
+// low half, so the compiler never selects ds_read_u8_d16_hi.)
 __device__ __forceinline__ uint32_t pk_min3h(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_pk_minimum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ uint32_t pk_max3h(uint32_t a, uint32_t b, uint32_t c) { uint32_t r; asm("v_pk_maximum3_f16 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ uint32_t pk_addh(uint32_t a, uint32_t b) { uint32_t r; asm("v_pk_add_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
@@ -731,12 +737,12 @@ __device__ __forceinline__ uint32_t pk_minh(uint32_t a, uint32_t b) { uint32_t r
 __device__ __forceinline__ uint32_t fast_S2(const uint8_t* pa, const uint8_t* pb, int st)
 {
 #define RING2(o) ((uint32_t)pa[o] | ((uint32_t)pb[o] << 16))
-    const uint32_t negc = RING2(0) ^ 0x80008000u;                      // -(centre) in both halves
+    const uint32_t c = RING2(0);
     uint32_t d[16];
-    d[0] = pk_addh(RING2(3*st), negc);      d[1] = pk_addh(RING2(3*st+1), negc);   d[2] = pk_addh(RING2(2*st+2), negc);   d[3] = pk_addh(RING2(st+3), negc);
-    d[4] = pk_addh(RING2(3), negc);         d[5] = pk_addh(RING2(-st+3), negc);    d[6] = pk_addh(RING2(-2*st+2), negc);  d[7] = pk_addh(RING2(-3*st+1), negc);
-    d[8] = pk_addh(RING2(-3*st), negc);     d[9] = pk_addh(RING2(-3*st-1), negc);  d[10] = pk_addh(RING2(-2*st-2), negc); d[11] = pk_addh(RING2(-st-3), negc);
-    d[12] = pk_addh(RING2(-3), negc);       d[13] = pk_addh(RING2(st-3), negc);    d[14] = pk_addh(RING2(2*st-2), negc);  d[15] = pk_addh(RING2(3*st-1), negc);
+    d[0] = RING2(3*st);      d[1] = RING2(3*st+1);   d[2] = RING2(2*st+2);   d[3] = RING2(st+3);
+    d[4] = RING2(3);         d[5] = RING2(-st+3);    d[6] = RING2(-2*st+2);  d[7] = RING2(-3*st+1);
+    d[8] = RING2(-3*st);     d[9] = RING2(-3*st-1);  d[10] = RING2(-2*st-2); d[11] = RING2(-st-3);
+    d[12] = RING2(-3);       d[13] = RING2(st-3);    d[14] = RING2(2*st-2);  d[15] = RING2(3*st-1);
 #undef RING2
     uint32_t mn3[16], mx3[16];
 #pragma unroll
@@ -748,8 +754,8 @@ __device__ __forceinline__ uint32_t fast_S2(const uint8_t* pa, const uint8_t* pb
 #pragma unroll
     for (int k = 3; k < 15; k += 2) { bright = pk_max3h(bright, mn9[k], mn9[k+1]); dark = pk_min3h(dark, mx9[k], mx9[k+1]); }
     bright = pk_maxh(bright, mn9[15]); dark = pk_minh(dark, mx9[15]);
-    // max(bright, -dark, +0): a positive denormal's bits ARE the integer
-    return pk_max3h(bright, dark ^ 0x80008000u, 0u);
+    // bright and dark are the best arc minimum / the least arc maximum of the raw ring: max(bright - c, c - dark, +0); a positive denormal's bits ARE the integer
+    return pk_max3h(pk_addh(bright, c ^ 0x80008000u), pk_addh(c, dark ^ 0x80008000u), 0u);
 }
 template <int PASS>
 __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, const uint8_t* __restrict__ pyr, const OrbGeom& g, cand_t* __restrict__ cand,
@@ -815,53 +821,41 @@ __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, co
     if (tid < 4) wsum[tid] = 0;
     if (tid == 0) { nsurv = 0; nstage = 0; gbase = 0; }
     __syncthreads();
-    // ---- quick reject.  A position passes when two ADJACENT compass points of the ring (N, E, S, W at distance 3) are both brighter than v + t or
-    // both darker than v - t (necessary for a 9-arc).  Four horizontally adjacent positions per work item: five dword LDS reads (the centre dword,
-    // its left/right neighbours and the dwords 3 rows up/down), bytes widened to packed u16 pairs, then packed 16-bit min/max:
-    //   bright = max over adjacent pairs of min(x - v, y - v),  dark = max over pairs of min(v - x, v - y) = -min over pairs of max
-    // Work item p = (row p / G, group p % G): only the groups of the scored rectangle take lanes.  The 4 pass bits of a group go to one byte of the
-    // bit image (row-major, FT_BW bytes per row); no compaction here
+    // ---- quick reject (ssm_fq::quick4, include/ssm/fast_quick_core.h).  A position passes when two ADJACENT compass points of the ring (N, E, S, W at
+    // distance 3) are both brighter than v + t or both darker than v - t (necessary for a 9-arc).  Four horizontally adjacent positions per work item:
+    // five dword LDS reads (the centre dword, its left/right neighbours and the dwords 3 rows up/down), bytes widened to packed u16 pairs and compared
+    // RAW against c + t and c - t by packed 16-bit min/max; the four sign bits become the pass nibble by one perm, one mask and one multiplication.
+    // A thread keeps ONE column group k = tid % G and walks the rows tid / G, + 256 / G, ... (the first (256 / G) * G threads work): the right-edge
+    // mask (only the last group reaches past the scored rectangle) and pass 2's cell columns are per-thread constants, and a trip advances two LDS
+    // addresses instead of dividing the item index.  The 4 pass bits of a group go to one byte of the bit image (row-major, FT_BW bytes per row);
+    // no compaction here
     const int min_th = PASS == 1 ? g.ini_th : g.min_th;         // the threshold of this pass
     {
-        const uint32_t* pxw = reinterpret_cast<const uint32_t*>(px);
-        const uint32_t t1 = (uint32_t)(min_th + 1) * 0x00010001u;
-        const float rG = __builtin_amdgcn_rcpf((float)G);      // (p + 0.5) / G is >= 1/64 away from an integer for p < 2048, G <= 32: exact quotient
-#pragma unroll 1
-        for (int p = tid; p < R * G; p += 256) {
-            const int ry = (int)(((float)p + 0.5f) * rG), k = p - ry * G;
-            const int rowc = (ry + 3) * (FT_PW / 4) + k + 1;
-            const uint32_t C = pxw[rowc], P = pxw[rowc - 1], Nx = pxw[rowc + 1];
-            const uint32_t U = pxw[rowc - 3 * (FT_PW / 4)], D = pxw[rowc + 3 * (FT_PW / 4)];
-            const uint32_t Lw = __builtin_amdgcn_alignbyte(C, P, 1);     // pixels x-3 of the four positions
-            const uint32_t Rw = __builtin_amdgcn_alignbyte(Nx, C, 3);    // pixels x+3
-            unsigned passbits = 0;
+        const uint32_t th2 = ssm_fq::pack_threshold(min_th);
+        const float rG = __builtin_amdgcn_rcpf((float)G);      // (p + 0.5) / G is >= 1/64 away from an integer for p <= 256, G <= 32: exact quotients
+        const int rpt = (int)(256.5f * rG);                     // rows per trip
+        const int r0 = (int)(((float)tid + 0.5f) * rG), k = tid - r0 * G;
+        const uint32_t keep = ssm_fq::keep_mask(xs1 - xs0 - 4 * k);
+        uint32_t colsh = 0;                                      // pass 2: the four positions' cell columns relative to cx0, a byte each
+        if (PASS == 2) {
 #pragma unroll
-            for (int hpair = 0; hpair < 2; hpair++) {
-                const uint32_t sel = hpair ? 0x0C030C02u : 0x0C010C00u;  // bytes (2h, 2h+1) zero-extended to u16 pairs
-                typedef short short2v __attribute__((ext_vector_type(2)));
-                auto widen = [&](uint32_t w) { uint32_t r = __builtin_amdgcn_perm(0u, w, sel); short2v o; __builtin_memcpy(&o, &r, 4); return o; };
-                const short2v c = widen(C);
-                const short2v a = widen(D) - c, bq = widen(Rw) - c, cq = widen(U) - c, d = widen(Lw) - c;
-                // max over the four adjacent pairs of the cycle a-b-c-d of min(x, y) = min(max(a, c), max(b, d)): "some adjacent pair is
-                // above the threshold" is (A or C) and (B or D); likewise the min over pairs of max = max(min(a, c), min(b, d))
-                const short2v br = __builtin_elementwise_min(__builtin_elementwise_max(a, cq), __builtin_elementwise_max(bq, d));
-                const short2v dk = __builtin_elementwise_max(__builtin_elementwise_min(a, cq), __builtin_elementwise_min(bq, d));
-                short2v t1v; __builtin_memcpy(&t1v, &t1, 4);
-                const short2v e = __builtin_elementwise_max(br, (short2v)(0 - dk)) - t1v;      // >= 0  <=>  pass
-                uint32_t eb; __builtin_memcpy(&eb, &e, 4);
-                passbits |= ((~eb >> 15) & 1u) << (2 * hpair);
-                passbits |= ((~eb >> 31) & 1u) << (2 * hpair + 1);
-            }
-            // positions right of the scored rectangle (last group only) never pass
-            passbits &= 15u >> max(4 - (xs1 - xs0 - 4 * k), 0);
+            for (int j = 0; j < 4; j++) colsh |= (uint32_t)(((int)cellx[4 * k + 1 + j] - cx0) & 7) << (8 * j);
+        }
+        const uint32_t* pc = reinterpret_cast<const uint32_t*>(px) + (r0 + 3) * (FT_PW / 4) + k + 1;
+        const uint32_t* const pend = reinterpret_cast<const uint32_t*>(px) + (R + 3) * (FT_PW / 4);      // the centre row behind the last scored one
+        uint8_t* pb = bits + r0 * FT_BW + k;
+        if (r0 >= rpt) pc = pend;                                // the threads behind the last whole row of a trip
+#pragma unroll 1
+        for (int ry = r0; pc < pend; ry += rpt, pc += rpt * (FT_PW / 4), pb += rpt * FT_BW) {
+            unsigned passbits = ssm_fq::quick4(pc[0], pc[-1], pc[1], pc[-3 * (FT_PW / 4)], pc[3 * (FT_PW / 4)], th2, keep);
             if (PASS == 2) {                                            // only the cells that stayed empty at iniThFAST are retried
                 const uint32_t er = emptyrow[((int)celly[ry + 1] - cy0) & 7];
                 unsigned m = 0;
 #pragma unroll
-                for (int j = 0; j < 4; j++) m |= ((er >> (((int)cellx[4 * k + 1 + j] - cx0) & 7)) & 1u) << j;
+                for (int j = 0; j < 4; j++) m |= ((er >> ((colsh >> (8 * j)) & 7u)) & 1u) << j;
                 passbits &= m;
             }
-            bits[ry * FT_BW + k] = (uint8_t)passbits;
+            *pb = (uint8_t)passbits;
         }
     }
     __syncthreads();
@@ -972,8 +966,8 @@ __device__ __forceinline__ void fast_tile(const int frame, const int tile_id, co
         atomicMax(&cellmax[(size_t)frame * g.cells_total + L.cell_off + ci * L.nCols + cj], lmax[tid]);
     }
 }
-// pass 1: one block per (frame, tile)
-__global__ void __launch_bounds__(256)
+// pass 1: one block per (frame, tile).  Eight waves per SIMD (64 registers): the eight blocks per CU that the LDS allows
+__global__ void __launch_bounds__(256, 8)
 fast_kernel(const uint8_t* __restrict__ pyr, OrbGeom g, cand_t* __restrict__ cand, int32_t* __restrict__ ncand, int32_t* __restrict__ cellmax, int stage_cap, int nframes)
 {
     const int frame = blockIdx.x, tile_id = blockIdx.y;          // frame-fastest launch order: see blur_kernel

@@ -1,6 +1,7 @@
 // ssm_orb_plan.cpp -- the plan of the ORB front end (ssm_orb_plan.h): geometry, resize and group tables, the fused pyramid's bands, the blur coefficients, and the
 // two debug entries that list a plan for the tests.  Host arithmetic only, plain C++: built once into libssm_hip.so; host/test_orb_plan.cpp links this file alone.
 #include "ssm_orb_plan.h"
+#include "../../include/ssm/fast_quick_core.h"
 #include <algorithm>
 #include <cstring>
 
@@ -266,6 +267,15 @@ extern "C" int ssm_debug_fast_plan(const ssm_config* cfg, int32_t* tiles, int ca
             memcpy(tiles + 16 * (size_t)(L.ftile_off + t), v, sizeof(v));
         }
     }
+    return SSM_OK;
+}
+
+// fast_tile's quick test (ssm_fq::quick4) on n groups of four positions: words = n x (C, P, Nx, U, D), out = n pass nibbles
+extern "C" int ssm_debug_fast_quick(const uint32_t* words, int n, int threshold, int valid, uint8_t* out)
+{
+    if (!words || !out || n < 0 || threshold < 0 || threshold > 255 || valid < 1 || valid > 4) return SSM_E_INVAL;
+    const uint32_t th2 = ssm_fq::pack_threshold(threshold), keep = ssm_fq::keep_mask(valid);
+    for (int i = 0; i < n; i++) { const uint32_t* w = words + 5 * (size_t)i; out[i] = (uint8_t)ssm_fq::quick4(w[0], w[1], w[2], w[3], w[4], th2, keep); }
     return SSM_OK;
 }
 

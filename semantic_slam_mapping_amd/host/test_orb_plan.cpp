@@ -108,6 +108,32 @@ int main()
     run(config(63, 480, 1, 1.2f));
     run(config(640, 4001, 1, 1.2f));
     { const ssm_config c = config(640, 480, 8, 1.2f); g_cfg = &c; check(refused == before + 6, "the six bad thresholds / sizes are refused"); }
+    // the FAST quick test (ssm_debug_fast_quick) on seeded random groups against the definition: two adjacent compass points above c + t or below c - t
+    {
+        const ssm_config c = config(640, 480, 8, 1.2f); g_cfg = &c;
+        const int N = 20000; vector<uint32_t> words((size_t)5 * N); vector<uint8_t> out(N);
+        uint32_t seed = 12345u;
+        for (uint32_t& w : words) { seed = seed * 1664525u + 1013904223u; w = seed ^ (seed >> 13); }
+        for (size_t i = 0; i < words.size(); i += 3) words[i] = (words[i] & 0x1F1F1F1Fu) + 0x70707070u;      // some near-flat words: values within a threshold or two
+        bool ok = true;
+        for (int t : {c.orb_minThFAST, c.orb_iniThFAST}) for (int valid = 1; valid <= 4; valid++) {
+            check(ssm_debug_fast_quick(words.data(), N, t, valid, out.data()) == SSM_OK, "ssm_debug_fast_quick");
+            for (int i = 0; i < N; i++) {
+                const uint32_t* w = &words[5 * (size_t)i];
+                uint8_t row[12]; memcpy(row, &w[1], 4); memcpy(row + 4, &w[0], 4); memcpy(row + 8, &w[2], 4);      // pixels x - 4 .. x + 7
+                int want = 0;
+                for (int j = 0; j < valid; j++) {
+                    const int ce = row[4 + j], p[4] = {(int)((w[3] >> (8 * j)) & 255), row[4 + j + 3], (int)((w[4] >> (8 * j)) & 255), row[4 + j - 3]};
+                    bool pass = false;
+                    for (int k = 0; k < 4; k++) pass = pass || (p[k] > ce + t && p[(k + 1) & 3] > ce + t) || (p[k] < ce - t && p[(k + 1) & 3] < ce - t);
+                    want |= (pass ? 1 : 0) << j;
+                }
+                ok = ok && out[i] == want;
+            }
+        }
+        check(ok, "ssm_debug_fast_quick equals the definition");
+        check(ssm_debug_fast_quick(words.data(), 1, 7, 5, out.data()) == SSM_E_INVAL && ssm_debug_fast_quick(nullptr, 1, 7, 4, out.data()) == SSM_E_INVAL, "ssm_debug_fast_quick refuses bad arguments");
+    }
     printf("orb plan: %d configurations accepted, %d refused; %d fused pyramid plans, %d band arguments without one\n", accepted, refused, fused, unfused);
     if (!accepted || !refused || !fused || !unfused) { printf("FAIL the sweep must see accepted and refused configurations, fused plans and geometries without one\n"); failures++; }
     printf(failures ? "%d FAILED\n" : "ALL PASSED\n", failures);
