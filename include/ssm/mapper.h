@@ -12,6 +12,10 @@
 // camera-frame cloud is made once and stays in HBM (ssm_backproject_dev: the device form of frame->pointcloud, mapper.cpp:17-20), an update transforms
 // the chosen clouds by their current poses, adds the previous centroids and filters, all on the device (ssm_viewer_map_update), and only the map that is
 // published (globalMap / the PCD) is downloaded.  Same bytes: the filter's sums are exact integers, independent of the order of the points.
+// motion_semantic_fuse=1 (default 0: the class exactly as before): the mask that gates a key-frame's cloud is the semantic-motion fusion's (DESIGN.md s.14;
+// reference src/mapper.cpp:217-271, commented out there for want of a motion mask): Car joins the maybe-moving classes, and a blob of them leaves the map only
+// when it is large (motion_area_thres) and enough of it (motion_overlay_portion_thres) lies under frame->moving_mask, which UVDisparity fills (uv_disparity=1).
+// A frame whose moving_mask is empty is gated as before.  Both routes to a cloud take the fused form of their call.
 #pragma once
 #include "common_headers.h"
 #include <atomic>
@@ -29,6 +33,7 @@ public:
         max_distance = para.getData<double>("mapper_max_distance", 40.0);
         area_thres = para.getData<int>("motion_area_thres", 1000);
         overlay_portion_thres = para.getData<double>("motion_overlay_portion_thres", 0.143);
+        fuse_motion = para.getData<int>("motion_semantic_fuse", 0) != 0;
         fix_incremental = para.getData<int>("mapper_fix_incremental", 0) != 0;
         invert_pose = para.getData<int>("mapper_invert_pose", 0) != 0;          // the commented alternative at mapper.cpp:89
         map_output = para.getData<string>("map_output", string(""));
@@ -117,6 +122,10 @@ public:
         const int w = frame->depth.cols, h = frame->depth.rows;
         ssm_camera cam; cam.cx = frame->camera.cx; cam.cy = frame->camera.cy; cam.fx = frame->camera.fx; cam.fy = frame->camera.fy; cam.scale = frame->camera.scale;
         ssm_cloud* cl = nullptr;
+        if (fuse_motion) {
+            const ssm_motion_fuse_params P = fuseParams();
+            d.check(ssm_backproject_fused_dev(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, motionOf(frame), w, h, &cam, max_distance, &P, &cl), "ssm_backproject_fused_dev");
+        } else
         d.check(ssm_backproject_dev(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, w, h, &cam, max_distance, &cl), "ssm_backproject_dev");
         devClouds[frame.get()] = cl;
         cloudsComputed++;
@@ -143,6 +152,11 @@ public:
             PointCloud::Ptr pc(new PointCloud());
             pc->points.resize((size_t)w * h);
             int n = 0;
+            if (fuse_motion) {
+                const ssm_motion_fuse_params P = fuseParams();
+                d.check(ssm_backproject_fused(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, motionOf(frame), w, h, &cam, nullptr, max_distance, &P,
+                                              reinterpret_cast<ssm_point*>(pc->points.data()), w * h, &n), "ssm_backproject_fused");
+            } else
             d.check(ssm_backproject(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, w, h, &cam, nullptr, max_distance,
                                     reinterpret_cast<ssm_point*>(pc->points.data()), w * h, &n), "ssm_backproject");
             pc->points.resize(n); pc->points.shrink_to_fit(); pc->width = n; pc->is_dense = false;
@@ -161,6 +175,17 @@ public:
         tmp->is_dense = false;
         return tmp;
     }
+    // src/mapper.cpp:189-271 under its own name: the mask that gates the frame's cloud.  motion_semantic_fuse=0: the always-moving classes, dilated (what
+    // ssm_moving_mask gives); 1: fused with frame->moving_mask.  info: the fusion's counters.  Uses the Mapper's device: not while the viewer thread runs
+    cv::Mat semantic_motion_fuse(const RGBDFrame::Ptr& frame, ssm_motion_fuse_info* info = nullptr) {
+        const int w = frame->semantic.cols, h = frame->semantic.rows;
+        ssm::Device& d = device(w, h);
+        cv::Mat mask; mask.create(h, w, CV_8UC1);
+        const ssm_motion_fuse_params P = fuseParams();
+        d.check(ssm_motion_fuse(d.ctx(), frame->semantic.data, fuse_motion ? motionOf(frame) : nullptr, w, h, w * 3, &P, mask.data, info), "ssm_motion_fuse");
+        return mask;
+    }
+    bool fusesMotion() const { return fuse_motion; }
     std::atomic<bool> viewerFailed{false};
     std::atomic<bool> deviceMapFellBack{false};                              // the device-resident map update failed once: host path since (same bits)
     int cloudsComputed = 0;                                                    // device back-projections so far (each frame costs one)
@@ -178,6 +203,12 @@ public:
         return out;
     }
 protected:
+    ssm_motion_fuse_params fuseParams() const { ssm_motion_fuse_params P; ssm_motion_fuse_params_default(&P); P.area_thres = area_thres; P.overlay_thres = overlay_portion_thres; return P; }
+    // the frame's motion mask when UVDisparity left one of the semantic image's size (packed rows), else none
+    static const uint8_t* motionOf(const RGBDFrame::Ptr& f) {
+        const cv::Mat& m = f->moving_mask;
+        return (!m.empty() && m.cols == f->semantic.cols && m.rows == f->semantic.rows && m.isContinuous()) ? m.data : nullptr;
+    }
     ssm::Device& device(int w, int h) {
         if (!dev) { if (w == 0) { w = 640; h = 480; } dev.reset(new ssm::Device(parameterReader.deviceConfig(w, h))); }
         return *dev;
@@ -190,7 +221,7 @@ protected:
     int keyframe_size = 0; std::atomic<int> cntGlobalUpdate{0};       // read by other threads (updates()): atomic -- the reference's plain int is a data race
     double resolution = 0.8, max_distance = 8.0;
     std::atomic<bool> shutdownFlag{false};                           // set by shutdown() on another thread (ThreadSanitizer finding, profiles/r03_sanitizers.log)
-    bool fix_incremental = false, invert_pose = false, device_map = true; int test_fail_update = -1;
+    bool fix_incremental = false, invert_pose = false, device_map = true, fuse_motion = false; int test_fail_update = -1;
     std::unordered_map<const RGBDFrame*, ssm_cloud*> devClouds;       // key-frame -> its camera-frame cloud in device memory (held until the viewer ends)
     int area_thres = 1000; double overlay_portion_thres = 0.143;
     string map_output;

@@ -449,6 +449,33 @@ int  ssm_debug_uvd_stage(ssm_uvd* u, int frame, int stage, void* out, size_t cap
  * the whole call with its three waits.  For scripts/uvd_bench.py */
 int  ssm_debug_uvd_times(ssm_uvd* u, double ms[3]);
 
+/* ---- the semantic-motion fusion (reference src/mapper.cpp:217-271 with the Car class of src/mapper.cpp~:146-229): the maybe-moving classes of the semantic
+ * image, dilated, taken as outer blobs with their holes filled; a blob joins the moving mask when it is large and enough of it lies under the motion mask
+ * (UVDisparity's).  DESIGN.md s.14 is the contract; include/ssm/motion_fuse_core.h the arithmetic shared by the device path and the host function.
+ * sem: BGR class colours; motion: w x h bytes, packed, only 255 counts; NULL = no motion, and the mask is then ssm_moving_mask's byte for byte. */
+typedef struct { int32_t area_thres; int32_t pad; double overlay_thres; } ssm_motion_fuse_params;
+typedef struct { int32_t blobs, large, confirmed, added; } ssm_motion_fuse_info;       /* blobs; those with area > area_thres; those confirmed; mask pixels the always-moving classes did not set */
+void ssm_motion_fuse_params_default(ssm_motion_fuse_params* p);          /* parameters.txt: motion_area_thres 1000, motion_overlay_portion_thres 0.143 */
+void ssm_motion_fuse_tile(int32_t wh[2]);                                /* the device labelling's tile (width, height): the tests build their sizes around it */
+/* host images of any size (stride: bytes per row of sem); info may be NULL */
+int  ssm_motion_fuse(ssm_ctx* ctx, const uint8_t* sem, const uint8_t* motion, int w, int h, int stride, const ssm_motion_fuse_params* params, uint8_t* mask,
+                     ssm_motion_fuse_info* info);
+/* n packed frames in device memory, one launch sequence and one wait; mask_dev: n x w x h; info: n entries on the host (may be NULL) */
+int  ssm_motion_fuse_dev(ssm_ctx* ctx, const uint8_t* sem_dev, const uint8_t* motion_dev, int n, int w, int h, const ssm_motion_fuse_params* params,
+                         uint8_t* mask_dev, ssm_motion_fuse_info* info);
+/* the same on the CPU, the same bits; needs no GPU.  labels (w x h int32: the smallest row-major index of the pixel's blob, -1 outside every blob), area and
+ * overlap (w x h int32: the blob's figures at its root pixel, 0 elsewhere) and cand (w x h bytes) may each be NULL */
+int  ssm_motion_fuse_host(const uint8_t* sem, const uint8_t* motion, int w, int h, int stride, const ssm_motion_fuse_params* params, uint8_t* mask,
+                          ssm_motion_fuse_info* info, int32_t* labels, int32_t* area, int32_t* overlap, uint8_t* cand);
+/* what ssm_motion_fuse_host hands out, of frame `frame` of the context's last device call (each may be NULL) */
+int  ssm_debug_motion_fuse(ssm_ctx* ctx, int frame, int32_t* labels, int32_t* area, int32_t* overlap, uint8_t* cand);
+/* ssm_backproject / ssm_backproject_dev with the fusion in the place of the class mask: points under the fused mask are dropped.  motion NULL: the bytes of
+ * the plain calls.  params NULL: the defaults */
+int  ssm_backproject_fused(ssm_ctx* ctx, const uint16_t* depth, const uint8_t* rgb_bgr, const uint8_t* sem_bgr, const uint8_t* motion, int w, int h,
+                           const ssm_camera* cam, const double* T, double max_distance, const ssm_motion_fuse_params* params, ssm_point* out, int cap, int* n_out);
+int  ssm_backproject_fused_dev(ssm_ctx* ctx, const uint16_t* depth, const uint8_t* rgb_bgr, const uint8_t* sem_bgr, const uint8_t* motion, int w, int h,
+                               const ssm_camera* cam, double max_distance, const ssm_motion_fuse_params* params, ssm_cloud** cloud_out);
+
 /* ---- PoseGraph's optimiser (reference src/pose_graph.cpp:82-305, include/pose_graph.h:53-62): a graph of SE3 vertices and SE3 edges with Huber kernels,
  * Levenberg (g2o's OptimizationAlgorithmLevenberg) over a direct block-envelope L D L^T.  DESIGN.md s.12 is the contract; include/ssm/pgo_core.h holds the
  * arithmetic, ONE function template that the host function runs with one thread and the device path with one 1024-thread block per graph, so device ==

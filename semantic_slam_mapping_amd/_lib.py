@@ -71,6 +71,14 @@ class UvdInfo(C.Structure):
                [(n, C.c_int32) for n in ("n_seeds", "n_masks_found", "n_masks_merged", "n_masks_kept", "n_moving")] + [("line", C.c_float * 4), ("pad", C.c_int32)]
 
 
+class MotionFuseParams(C.Structure):
+    _fields_ = [("area_thres", C.c_int32), ("pad", C.c_int32), ("overlay_thres", C.c_double)]
+
+
+class MotionFuseInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("blobs", "large", "confirmed", "added")]
+
+
 class VocabTrainParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iters", C.c_int32)]
 
@@ -176,6 +184,14 @@ SYMBOLS = {
     "ssm_debug_uvd_stage": (_I, [_P, _I, _I, _P, _SZ, C.POINTER(_SZ)]),
     "ssm_debug_uvd_record": (_I, [_P, _I]),
     "ssm_debug_uvd_times": (_I, [_P, C.POINTER(C.c_double * 3)]),
+    "ssm_motion_fuse_params_default": (None, [C.POINTER(MotionFuseParams)]),
+    "ssm_motion_fuse_tile": (None, [C.POINTER(C.c_int32 * 2)]),
+    "ssm_motion_fuse": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(MotionFuseParams), _P, C.POINTER(MotionFuseInfo)]),
+    "ssm_motion_fuse_dev": (_I, [_P, _P, _P, _I, _I, _I, C.POINTER(MotionFuseParams), _P, _P]),
+    "ssm_motion_fuse_host": (_I, [_P, _P, _I, _I, _I, C.POINTER(MotionFuseParams), _P, C.POINTER(MotionFuseInfo), _P, _P, _P, _P]),
+    "ssm_debug_motion_fuse": (_I, [_P, _I, _P, _P, _P, _P]),
+    "ssm_backproject_fused": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Camera), _P, _D, C.POINTER(MotionFuseParams), _P, _I, C.POINTER(_I)]),
+    "ssm_backproject_fused_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Camera), _D, C.POINTER(MotionFuseParams), C.POINTER(_P)]),
     "ssm_pgo_create": (_I, [_P, C.POINTER(_P)]),
     "ssm_pgo_destroy": (None, [_P]),
     "ssm_pgo_clear": (_I, [_P]),

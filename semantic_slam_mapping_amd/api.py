@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -105,6 +105,45 @@ def live_handles():
 
 def _ptr(a):
     return a.ctypes.data if a is not None else None
+
+
+MOTION_FUSE_INFO_DTYPE = np.dtype([("blobs", "i4"), ("large", "i4"), ("confirmed", "i4"), ("added", "i4")])
+
+
+def motion_fuse_tile():
+    """(width, height) of the device labelling's tile: ssm_motion_fuse_tile"""
+    wh = (C.c_int32 * 2)()
+    _lib.load().ssm_motion_fuse_tile(C.byref(wh))
+    return wh[0], wh[1]
+
+
+def _mf_images(sem, motion):
+    sem = np.ascontiguousarray(sem, np.uint8)
+    if sem.ndim < 3 or sem.shape[-1] != 3:
+        raise ValueError("sem: H x W x 3 (or n x H x W x 3)")
+    if motion is not None:
+        motion = np.ascontiguousarray(motion, np.uint8)
+        if motion.shape != sem.shape[:-1]:
+            raise ValueError("motion: the shape of sem without its channels")
+    return sem, motion
+
+
+def motion_fuse_host(sem, motion=None, area_thres=1000, overlay_thres=0.143, record=False):
+    """the semantic-motion fusion on the CPU (ssm_motion_fuse_host, no GPU): -> (mask, info), or with record (mask, info, {labels, area, overlap, cand})"""
+    sem, motion = _mf_images(sem, motion)
+    h, w = sem.shape[:2]
+    P = MotionFuseParams(int(area_thres), 0, float(overlay_thres)); I = MotionFuseInfo()
+    mask = np.zeros((h, w), np.uint8)
+    rec = {k: np.zeros((h, w), np.int32) for k in ("labels", "area", "overlap")} if record else {}
+    if record:
+        rec["cand"] = np.zeros((h, w), np.uint8)
+    lib = _lib.load()
+    rc = lib.ssm_motion_fuse_host(_ptr(sem), _ptr(motion), w, h, w * 3, C.byref(P), _ptr(mask), C.byref(I), _ptr(rec.get("labels")), _ptr(rec.get("area")),
+                                  _ptr(rec.get("overlap")), _ptr(rec.get("cand")))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    info = {k: getattr(I, k) for k in MOTION_FUSE_INFO_DTYPE.names}
+    return (mask, info, rec) if record else (mask, info)
 
 
 def _rows(a):
@@ -776,6 +815,58 @@ class Context:
         mask = np.zeros((h, w), np.uint8)
         self._chk(self.lib.ssm_moving_mask(self.h, _ptr(sem), w, h, sem.strides[0], _ptr(mask)))
         return mask
+
+    def motion_fuse(self, sem, motion=None, area_thres=1000, overlay_thres=0.143, record=False):
+        """the semantic-motion fusion on the device.  sem H x W x 3 (host-image call) or n x H x W x 3 (the batched device-resident call, through temporary device
+        buffers): -> (mask, info), info a dict or a MOTION_FUSE_INFO_DTYPE array of n; record adds {labels, area, overlap, cand} (a list of n for a batch)"""
+        sem, motion = _mf_images(sem, motion)
+        P = MotionFuseParams(int(area_thres), 0, float(overlay_thres))
+        h, w = sem.shape[-3:-1]
+
+        def recorded(f):
+            rec = {k: np.zeros((h, w), np.int32) for k in ("labels", "area", "overlap")}
+            rec["cand"] = np.zeros((h, w), np.uint8)
+            self._chk(self.lib.ssm_debug_motion_fuse(self.h, f, _ptr(rec["labels"]), _ptr(rec["area"]), _ptr(rec["overlap"]), _ptr(rec["cand"])))
+            return rec
+        if sem.ndim == 3:
+            mask = np.zeros((h, w), np.uint8); I = MotionFuseInfo()
+            self._chk(self.lib.ssm_motion_fuse(self.h, _ptr(sem), _ptr(motion), w, h, w * 3, C.byref(P), _ptr(mask), C.byref(I)))
+            info = {k: getattr(I, k) for k in MOTION_FUSE_INFO_DTYPE.names}
+            return (mask, info, recorded(0)) if record else (mask, info)
+        n = sem.shape[0]
+        info = np.zeros(n, MOTION_FUSE_INFO_DTYPE)
+        bufs = [self.dev_alloc(sem.nbytes), self.dev_alloc(n * w * h), self.dev_alloc(n * w * h) if motion is not None else None]
+        try:
+            self.h2d(bufs[0], sem)
+            if motion is not None:
+                self.h2d(bufs[2], motion)
+            self._chk(self.lib.ssm_motion_fuse_dev(self.h, bufs[0], bufs[2], n, w, h, C.byref(P), bufs[1], _ptr(info)))
+            mask = self.d2h(bufs[1], (n, h, w), np.uint8)
+            rec = [recorded(f) for f in range(n)] if record else None
+        finally:
+            for b in bufs:
+                if b is not None:
+                    self.dev_free(b)
+        return (mask, info, rec) if record else (mask, info)
+
+    def backproject_fused(self, depth, rgb, sem, motion=None, T=None, camera=None, max_distance=None, area_thres=1000, overlay_thres=0.143, device=False):
+        """generate_point_cloud with the fused mask (ssm_backproject_fused); device=True: backproject_dev's form, -> an opaque cloud handle (cloud_free it)"""
+        depth = np.ascontiguousarray(depth, np.uint16); rgb = np.ascontiguousarray(rgb, np.uint8)
+        sem, motion = _mf_images(sem, motion)
+        h, w = depth.shape
+        cam = Camera(*camera) if camera is not None else self.cfg.camera
+        md = self.cfg.mapper_max_distance if max_distance is None else max_distance
+        P = MotionFuseParams(int(area_thres), 0, float(overlay_thres))
+        if device:
+            cl = C.c_void_p()
+            self._chk(self.lib.ssm_backproject_fused_dev(self.h, _ptr(depth), _ptr(rgb), _ptr(sem), _ptr(motion), w, h, C.byref(cam), md, C.byref(P), C.byref(cl)))
+            return cl.value
+        Tc = None if T is None else np.ascontiguousarray(np.asarray(T, np.float64).reshape(4, 4).T)
+        out = np.zeros(w * h, POINT_DTYPE)
+        n = C.c_int(0)
+        self._chk(self.lib.ssm_backproject_fused(self.h, _ptr(depth), _ptr(rgb), _ptr(sem), _ptr(motion), w, h, C.byref(cam), _ptr(Tc), md, C.byref(P),
+                                                 _ptr(out), len(out), C.byref(n)))
+        return out[:n.value]
 
     def generate_point_cloud(self, depth, rgb, sem, T=None, camera=None, max_distance=None):
         depth = np.ascontiguousarray(depth, np.uint16)

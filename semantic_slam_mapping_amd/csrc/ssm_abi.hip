@@ -645,8 +645,9 @@ extern "C" int ssm_moving_mask(ssm_ctx* c, const uint8_t* sem, int w, int h, int
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
 }
-extern "C" int ssm_backproject(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, int w, int h,
-                               const ssm_camera* cam, const double* T, double max_distance, ssm_point* out, int cap, int* n_out)
+// fused: the mask is the semantic-motion fusion's (ssm_motion_fuse.hip) instead of the class mask
+static int backproject_host(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, bool fused, const uint8_t* motion, const ssm_motion_fuse_params* params,
+                            int w, int h, const ssm_camera* cam, const double* T, double max_distance, ssm_point* out, int cap, int* n_out)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
@@ -657,7 +658,8 @@ extern "C" int ssm_backproject(ssm_ctx* c, const uint16_t* depth, const uint8_t*
     HIPCHK(c, hipMemcpyAsync(c->d_in_img, rgb, np * 3, hipMemcpyHostToDevice, c->main.stream));
     HIPCHK(c, hipMemcpyAsync(c->d_in_sem, sem, np * 3, hipMemcpyHostToDevice, c->main.stream));
     if (T) HIPCHK(c, hipMemcpyAsync(c->d_in_pose, T, 128, hipMemcpyHostToDevice, c->main.stream));
-    HIPCHK(c, k_moving_mask(c->d_in_sem, 1, w, h, c->d_mask, c->main.stream));
+    if (fused) { const int r = mf_enqueue(c, c->d_in_sem, nullptr, motion, 1, w, h, params, c->d_mask); if (r) return r; }
+    else HIPCHK(c, k_moving_mask(c->d_in_sem, 1, w, h, c->d_mask, c->main.stream));
     HIPCHK(c, k_backproject(c->d_in_depth, c->d_in_img, c->d_in_sem, c->d_mask, T ? c->d_in_pose : nullptr, 1, w, h, *cam, max_distance,
                             c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, c->d_points, c->main.stream));
     int64_t total = 0;
@@ -667,6 +669,16 @@ extern "C" int ssm_backproject(ssm_ctx* c, const uint16_t* depth, const uint8_t*
     if (total > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small (need " + std::to_string(total) + ")");
     HIPCHK(c, hipMemcpy(out, c->d_points, sizeof(ssm_point) * (size_t)total, hipMemcpyDeviceToHost));
     return SSM_OK;
+}
+extern "C" int ssm_backproject(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, int w, int h,
+                               const ssm_camera* cam, const double* T, double max_distance, ssm_point* out, int cap, int* n_out)
+{
+    return backproject_host(c, depth, rgb, sem, false, nullptr, nullptr, w, h, cam, T, max_distance, out, cap, n_out);
+}
+extern "C" int ssm_backproject_fused(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const uint8_t* motion, int w, int h,
+                                     const ssm_camera* cam, const double* T, double max_distance, const ssm_motion_fuse_params* params, ssm_point* out, int cap, int* n_out)
+{
+    return backproject_host(c, depth, rgb, sem, true, motion, params, w, h, cam, T, max_distance, out, cap, n_out);
 }
 
 // ---------------------------------------------------------------- device-resident sequence path

@@ -167,6 +167,12 @@ struct OrbWork {
     DevBuf<uint8_t> pyr, blur; DevBuf<int32_t> ncand; int32_t* cellmax = nullptr /* inside ncand's allocation */; DevBuf<cand_t> cand; DevBuf<uint16_t> nodeof;
     DevBuf<uint32_t> sel; DevBuf<int32_t> nsel; DevBuf<uint4> kpaux;
 };
+// workspace of the semantic-motion fusion (ssm_motion_fuse.hip) for cap_n frames of cap_px pixels; n, w, h: the last call, for ssm_debug_motion_fuse
+struct MfWork {
+    int cap_n = 0, n = 0, w = 0, h = 0; size_t cap_px = 0;
+    DevBuf<uint8_t> always, cand, filled; DevBuf<int32_t> labels, area, overlap, info; PinBuf<int32_t> h_info;
+    DevBuf<uint8_t> in_sem, in_motion, out_mask;      // staging of the host-image entry points (one frame)
+};
 // one ORB -> match chain of ssm_seq_process: the lane it runs on, its workspace, and the event behind its newest ORB + expand (what the next sub-batch's matcher waits for)
 struct OrbChain { Lane* lane; OrbWork work; Event orb_done; };
 
@@ -238,7 +244,8 @@ struct ssm_ctx {
     // quad matcher
     std::unique_ptr<StereoState> stereo; int stereo_B = 16; int stereo_sgbm_streams = 2;      // ssm_config.sgbm_streams 
     int sgbm_form_cfg = 0; long sgbm_fallbacks = 0;                                              // ssm_config.sgbm_form; sub-batches repeated in form 1 after a sweep time-out
-    double vt_level_ms[10] = {0}, vt_total_ms = -1.0;      // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
+    MfWork mf;                                               // semantic-motion fusion: allocated by its first call
+    double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;
     PinBuf<uint8_t> h_pinned;          // host staging for the image-sized host-pointer calls (pageable hipMemcpy is ~1 GB/s)
@@ -291,3 +298,7 @@ SSM_HIDDEN int seg_init(ssm_ctx* c);
 SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, Lane& lane, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
 // ssm_stereo_abi.hip
 SSM_HIDDEN int sgbm_recover(ssm_ctx* c);
+// ssm_motion_fuse.hip: the fusion of n device frames queued on the main stream (no wait); motion_host: one frame's motion mask on the host, staged first (n == 1);
+// both null: no motion.  The counters stay in c->mf.info
+SSM_HIDDEN int mf_enqueue(ssm_ctx* c, const uint8_t* sem_dev, const uint8_t* motion_dev, const uint8_t* motion_host, int n, int w, int h,
+                          const ssm_motion_fuse_params* params, uint8_t* mask_dev);

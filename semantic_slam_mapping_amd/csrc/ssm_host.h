@@ -1,4 +1,4 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp: plain C++ without a HIP
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp: plain C++ without a HIP
 // header and without ssm_ctx.h) share with the device translation units.  Those sources are compiled once and LINKED into libssm_hip.so, into the CPU sanitizer
 // binaries of the host layer and into host/test_vocab_train.  What they need from the side that owns the context and the device are the hooks: defined in
 // ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
@@ -7,6 +7,7 @@
 #include "../../include/ssm/vocab_train_core.h"
 #include "../../include/ssm/uvd_core.h"
 #include "../../include/ssm/pgo_core.h"
+#include "../../include/ssm/motion_fuse_core.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -78,6 +79,9 @@ inline ssm_uvdc::Calib uvd_calib(const ssm_uvd_params& p) { return ssm_uvdc::Cal
 inline ssm_uvdc::Roi uvd_roi(const ssm_uvd_params& p) { return ssm_uvdc::Roi{p.roi_x, p.roi_y, p.roi_z}; }
 SSM_HIDDEN int uvd_dev_attach(ssm_uvd* u);          // hooks (ssm_uvd.hip): ssm_uvd_create with a context -> u->dev; ssm_uvd_destroy of such an object
 SSM_HIDDEN void uvd_dev_release(ssm_uvd* u);
+
+// ---------------------------------------------------------------- semantic-motion fusion (ssm_motion_fuse_host.cpp)
+SSM_HIDDEN int mf_check(ssm_ctx* c, int n, int w, int h, size_t stride);          // the sizes a call may have (host function and device entry points alike)
 
 // ---------------------------------------------------------------- pose graph (ssm_pgo_host.cpp)
 struct PgoPlan {

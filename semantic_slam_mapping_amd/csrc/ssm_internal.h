@@ -207,6 +207,15 @@ hipError_t k_uvd_classify(const uint8_t* left, const int16_t* disp, int n, int w
 hipError_t k_uvd_probe(const uint8_t* roi, const int16_t* disp, int n, int w, int h, const int32_t* coords, const int32_t* nmatch, int cap, int32_t* probes, hipStream_t s);
 hipError_t k_uvd_segment(const int16_t* disp, const uint8_t* roi, const uint8_t* uni, int n, int w, int h, const ssm_uvdc::FrameK* K, uint8_t* moving, int32_t* counts, hipStream_t s);
 
+// semantic-motion fusion (kernels_motion_fuse.hip; the arithmetic is include/ssm/motion_fuse_core.h): n packed frames of w x h, motion null = all zero.  One launch
+// sequence, no wait.  always / cand / filled / mask: n x w x h; labels: n x k_mf_label_stride(w, h) ints (a frame's labels are its first w h); area / overlap:
+// n x w x h ints, the figures at each blob's root pixel and 0 elsewhere; info: n x (blobs, large, confirmed, added)
+size_t k_mf_label_stride(int w, int h);
+int k_mf_tile_w();
+int k_mf_tile_h();
+hipError_t k_motion_fuse(const uint8_t* sem, const uint8_t* motion, int n, int w, int h, int32_t area_thres, double overlay_thres, uint8_t* always, uint8_t* cand,
+                         uint8_t* filled, int32_t* labels, int32_t* area, int32_t* overlap, uint8_t* mask, int32_t* info, hipStream_t s);
+
 // pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);
 // op 1: linearise + assemble; op 2: factor and solve the view's envelope with `lambda`
 namespace ssm_pgc { struct View; }

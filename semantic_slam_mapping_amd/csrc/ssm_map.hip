@@ -511,8 +511,9 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
 
 // ---------------------------------------------------------------- device-resident Mapper (ssm_backproject_dev, ssm_viewer_map_*)
 struct ssm_cloud { ssm_point* d = nullptr; int n = 0; int device = 0; int slab = -1; };
-extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, int w, int h,
-                                   const ssm_camera* cam, double max_distance, ssm_cloud** cloud_out)
+// fused: the mask is the semantic-motion fusion's (ssm_motion_fuse.hip) instead of the class mask
+static int backproject_cloud(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, bool fused, const uint8_t* motion, const ssm_motion_fuse_params* params,
+                             int w, int h, const ssm_camera* cam, double max_distance, ssm_cloud** cloud_out)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
@@ -538,7 +539,8 @@ extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint
     }
     ssm_ctx::CloudSlab& sl = c->cloud_slabs[si];
     ssm_point* dst = sl.d + sl.used;
-    HIPCHK(c, k_moving_mask(dsem, 1, w, h, c->d_mask, c->main.stream));
+    if (fused) { r = mf_enqueue(c, dsem, nullptr, motion, 1, w, h, params, c->d_mask); if (r) return r; }
+    else HIPCHK(c, k_moving_mask(dsem, 1, w, h, c->d_mask, c->main.stream));
     HIPCHK(c, k_backproject(dd, drgb, dsem, c->d_mask, nullptr, 1, w, h, *cam, max_distance,
                             c->d_chunk_cnt, c->d_chunk_off, reinterpret_cast<int32_t*>(c->d_total + 1), c->d_total, dst, c->main.stream));
     int64_t* h_total = c->h_pinned.as<int64_t>();                  // (the staged images at the front of the pinned area are consumed by then: stream order)
@@ -549,6 +551,16 @@ extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint
     sl.used += ((size_t)total + 7) & ~(size_t)7; sl.live++;
     *cloud_out = cl;
     return SSM_OK;
+}
+extern "C" int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, int w, int h,
+                                   const ssm_camera* cam, double max_distance, ssm_cloud** cloud_out)
+{
+    return backproject_cloud(c, depth, rgb, sem, false, nullptr, nullptr, w, h, cam, max_distance, cloud_out);
+}
+extern "C" int ssm_backproject_fused_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const uint8_t* motion, int w, int h,
+                                         const ssm_camera* cam, double max_distance, const ssm_motion_fuse_params* params, ssm_cloud** cloud_out)
+{
+    return backproject_cloud(c, depth, rgb, sem, true, motion, params, w, h, cam, max_distance, cloud_out);
 }
 extern "C" int ssm_cloud_size(const ssm_cloud* cl) { return cl ? cl->n : 0; }
 extern "C" void ssm_cloud_free(ssm_ctx* c, ssm_cloud* cl)

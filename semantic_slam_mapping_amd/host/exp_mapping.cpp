@@ -22,6 +22,11 @@
 // with --batched one bulk call per chunk does it.  The summary line then carries `moving_pixels N moving_fnv H pitch_fnv P` (the 255-pixels, FNV-1a over the mask
 // bytes and over the measured pitches of those frames, in order: the same in both modes).  Without the flag nothing of this runs and no output changes.
 //
+// `exp_mapping <parameters> --fuse-motion` (or motion_semantic_fuse=1; implies --moving, so it needs tracker_mode=stereo too): Mapper gates every key-frame's cloud with
+// the semantic-motion fusion of the frame's semantic image and its moving_mask (include/ssm/mapper.h) instead of the class mask alone.  The summary line
+// then carries `fused_keyframes K fused_confirmed C fused_added N fused_fnv H`: over the key-frames in order, the blobs confirmed as moving, the mask pixels they add to
+// the always-moving classes, and FNV-1a over every fused mask (the same in both modes).  Without the flag nothing of this runs and no output changes.
+//
 // `exp_mapping <parameters> --ranks N`: the multi-GPU form (BASELINE.json configs[4]; the reference is one process).  The parent starts
 // N FRESH processes of itself (`--rank r`, fork + exec of /proc/self/exe) before anything touches HIP -- a forked copy of a process whose HIP / RCCL
 // static constructors have already run is not a state either library is tested in; rank r drives GPU r, owns the contiguous frame block [lo, hi) of
@@ -109,10 +114,14 @@ int main(int argc, char** argv)
     for (int i = 2; i + 1 < argc; i++) if (string(argv[i]) == "--train-vocab") train_vocab = argv[i + 1];
     bool moving = parameterReader.getData<int>("uv_disparity", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--moving") moving = true;
+    bool fuse_motion = parameterReader.getData<int>("motion_semantic_fuse", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--fuse-motion") fuse_motion = true;
+    if (fuse_motion) moving = true;
     if (moving) {
-        if (parameterReader.getData<string>("tracker_mode", string("rgbd")) != "stereo") { cerr << "exp_mapping: --moving needs tracker_mode=stereo (the U/V-disparity stage works on the SGBM disparity)" << endl; return 2; }
+        if (parameterReader.getData<string>("tracker_mode", string("rgbd")) != "stereo") { cerr << "exp_mapping: " << (fuse_motion ? "--fuse-motion" : "--moving") << " needs tracker_mode=stereo (the U/V-disparity stage works on the SGBM disparity)" << endl; return 2; }
         parameterReader.set("uv_disparity", "1");
     }
+    if (fuse_motion) parameterReader.set("motion_semantic_fuse", "1");
     MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
@@ -332,6 +341,16 @@ int main(int argc, char** argv)
         // the rates of the frames after timing_skip_frames: loop_fps = the whole loop (reader included); tracker_fps = frames / time inside updateFrame (or BatchTracker::push /
         // flush) -- what experiment/run_tracker.cpp:35-48 times; the *_ms are per frame
         if (moving) cout << " moving_pixels " << moving_log.pixels << " moving_fnv " << hex << moving_log.hm << " pitch_fnv " << moving_log.hp << dec;
+        if (fuse_motion) {      // (the viewer thread has ended: the Mapper's device is this thread's now)
+            uint64_t h = 0xCBF29CE484222325ull; long long confirmed = 0, added = 0;
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) {
+                ssm_motion_fuse_info I{};
+                const cv::Mat m = mapper.semantic_motion_fuse(kf, &I);
+                confirmed += I.confirmed; added += I.added;
+                for (int r = 0; r < m.rows; r++) { const unsigned char* b = m.ptr<unsigned char>(r); for (int c = 0; c < m.cols; c++) { h ^= b[c]; h *= 0x100000001B3ull; } }
+            }
+            cout << " fused_keyframes " << poseGraph.keyframes.size() << " fused_confirmed " << confirmed << " fused_added " << added << " fused_fnv " << hex << h << dec;
+        }
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;
             cout << " timed_frames " << timed << " loop_fps " << timed / s_timed << " tracker_fps " << (track_s > 0 ? timed / track_s : 0.0) << " reader_ms " << reader_s * 1e3 / timed

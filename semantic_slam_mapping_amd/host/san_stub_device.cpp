@@ -2,7 +2,7 @@
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
 // which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the "no device" form of
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the "no device" form of
 // csrc/ssm_host.h's hooks here.  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
 #include "ssm_hip.h"
 #include "ssm/pnp_core.h"
@@ -78,6 +78,13 @@ int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, c
     ssm_backproject(c, depth, rgb, sem, w, h, cam, nullptr, md, cl->p.data(), (int)cl->p.size(), &n);
     cl->p.resize(n); *out = cl; return SSM_OK;
 }
+// the fused forms (Mapper with motion_semantic_fuse=1): the same placeholders; the fusion itself is the linked host function
+int ssm_backproject_fused(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const uint8_t*, int w, int h, const ssm_camera* cam, const double* T, double md,
+                          const ssm_motion_fuse_params*, ssm_point* out, int cap, int* n_out) { return ssm_backproject(c, depth, rgb, sem, w, h, cam, T, md, out, cap, n_out); }
+int ssm_backproject_fused_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const uint8_t*, int w, int h, const ssm_camera* cam, double md,
+                              const ssm_motion_fuse_params*, ssm_cloud** out) { return ssm_backproject_dev(c, depth, rgb, sem, w, h, cam, md, out); }
+int ssm_motion_fuse(ssm_ctx*, const uint8_t* sem, const uint8_t* motion, int w, int h, int stride, const ssm_motion_fuse_params* params, uint8_t* mask, ssm_motion_fuse_info* info)
+{ return ssm_motion_fuse_host(sem, motion, w, h, stride, params, mask, info, nullptr, nullptr, nullptr, nullptr); }
 int ssm_cloud_size(const ssm_cloud* cl) { return cl ? (int)cl->p.size() : 0; }
 void ssm_cloud_free(ssm_ctx*, ssm_cloud* cl) { delete cl; }
 int ssm_cloud_fetch(ssm_ctx*, const ssm_cloud* cl, const double*, ssm_point* out, int cap, int* n_out)
