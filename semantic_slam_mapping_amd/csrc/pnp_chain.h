@@ -1,19 +1,9 @@
-// pnp_chain.h -- interface between the tracker's host orchestration (ssm_track.hip) and the device pose chain (kernels_pnp.hip).  Not installed.
+// pnp_chain.h -- interface between the tracker's device leg (ssm_track.hip: the hooks the host state machine in ssm_track_host.cpp calls) and the device pose chain
+// (kernels_pnp.hip).  The chain's state block, which the host source shares, is pnp_state.h.  Not installed.
 #pragma once
 #include "ssm_internal.h"
+#include "pnp_state.h"
 #include "../../include/ssm/pnp_core.h"
-#define SSM_TRACK_MAXREF 64
-// the Tracker's state while the chain runs on the device (device memory; the host uploads it before a run and reads it back after)
-struct PnpState {
-    double speed[16], last_pose[16];                 // column-major 4 x 4
-    double ref_pose[SSM_TRACK_MAXREF][16];           // refFrames deque, oldest first
-    int32_t ref_idx[SSM_TRACK_MAXREF];               // their frame indices relative to the current ssm_seq_process call (negative: frames of the previous call)
-    int32_t nref, cnt_lost, stopped_at, pad;
-    long long work[4];                               // out: fused passes, chi2 passes, active edges evaluated by the fused / by the chi2 passes of this launch
-#ifdef SSM_PNP_PROF
-    long long prof[32];                              // shader clocks per section (thread 0), ablation builds only
-#endif
-};
 struct PnpChainArgs {
     const ssm_keypoint* kps; const float* pos3d; const ssm_dmatch* matches; const int32_t* nmatch;     // the call's outputs (device)
     const float* hist_pos3d;                         // R x cap x 3: positions of the deque members that precede the call, row idx + R

@@ -1,17 +1,20 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp: plain C++ without a HIP
-// header and without ssm_ctx.h) share with the device translation units.  Those sources are compiled once and LINKED into libssm_hip.so, into the CPU sanitizer
-// binaries of the host layer and into host/test_vocab_train.  What they need from the side that owns the context and the device are the hooks: defined in
-// ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_track_host.cpp:
+// plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units.  Those sources are compiled once and LINKED into libssm_hip.so, into the
+// CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
+// defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
 #pragma once
 #include "../../include/ssm_hip.h"
 #include "../../include/ssm/vocab_train_core.h"
 #include "../../include/ssm/uvd_core.h"
 #include "../../include/ssm/pgo_core.h"
 #include "../../include/ssm/motion_fuse_core.h"
+#include "../../include/ssm/pnp_core.h"
+#include "pnp_state.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -82,6 +85,42 @@ SSM_HIDDEN void uvd_dev_release(ssm_uvd* u);
 
 // ---------------------------------------------------------------- semantic-motion fusion (ssm_motion_fuse_host.cpp)
 SSM_HIDDEN int mf_check(ssm_ctx* c, int n, int w, int h, size_t stride);          // the sizes a call may have (host function and device entry points alike)
+
+// ---------------------------------------------------------------- bulk tracker (ssm_track_host.cpp)
+struct TrackRef {                         // a member of Tracker::refFrames: what trackRefFrame reads of it
+    int64_t gidx = 0; int nkp = 0; double pose[16];
+    std::vector<float> pos3d; std::vector<uint8_t> desc;
+};
+struct TrackDev;            // the chain's stream, event, scratch and state block on the device: ssm_track.hip
+struct ssm_tracker {
+    ssm_ctx* ctx = nullptr; ssm_tracker_params prm{}; ssm_camera cam{}; double ratio = 0.8;          // cam, ratio: the context's configuration (the attach hook)
+    std::string err;
+    int state = 0, cnt_lost = 0;          // Tracker::trackerState: 0 NOT_READY, 1 OK, 2 LOST
+    double speed[16], last_pose[16];
+    std::deque<TrackRef> refs;
+    int64_t next_gidx = 0;                // global index of the current call's frame 0: a member with gidx < next_gidx is a frame of an earlier call
+    // host copies of one call's outputs
+    std::vector<int32_t> nkp, nmatch; std::vector<ssm_keypoint> kps; std::vector<float> pos3d; std::vector<uint8_t> desc; std::vector<ssm_dmatch> matches;
+    std::vector<float> img, obj; std::vector<unsigned char> inl; std::vector<ssm_pnp::Edge> edges; std::vector<ssm_dmatch> tmp_matches;
+    std::vector<uint8_t> have;            // per frame of the current call: bit 0 = features on the host, bit 1 = match tables on the host
+    int blocks = 1;                       // the cluster form of the device chain (kernels_pnp.hip): blocks per chain, chosen by the attach hook
+    long device_frames = 0, host_frames = 0;
+    bool downgraded = false;              // the cluster form timed out once: one block per chain since (reported by ssm_tracker_last_error)
+    int64_t work[4] = {0, 0, 0, 0};       // the device chain's passes over the edges (ssm_tracker_work)
+    TrackDev* dev = nullptr;
+};
+// the state machine's steps that host/test_track.cpp also drives one by one.  track_regular: the deque is the run of frames directly in front of frame f of the
+// call, so the device chain may take over there.  track_frame_host: Tracker::updateFrame for frame f on the host -> T_frame (16 doubles), *info
+SSM_HIDDEN bool track_regular(const ssm_tracker* t, int f);
+SSM_HIDDEN int track_frame_host(ssm_tracker* t, const ssm_seq_out_dev* seq, int f, double* T_frame, ssm_track_info* info);
+// hooks (ssm_track.hip); the call's outputs themselves come to the host through the public ABI (ssm_sync, ssm_memcpy_d2h; ssm_match for an on-demand pair).
+// attach: ssm_tracker_create -> cam, ratio, blocks, t->dev (SSM_E_INVAL: the context was configured with another tracker_ref_frames).  release: ssm_tracker_destroy.
+// run: the chain on frames [f, n) of the call from the block *hs, which comes back as the device left it; the positions of the members with a negative ref_idx are
+// read from t->refs (same order as the block).  A cluster (t->blocks > 1) that timed out gives SSM_OK with hs->stopped_at == -1 and nothing else: the caller goes
+// on with one block.  Otherwise f < hs->stopped_at <= n, and pose_out[f .. stopped_at) and info (resized to stopped_at - f rows) hold the frames the chain walked
+SSM_HIDDEN int track_dev_attach(ssm_tracker* t);
+SSM_HIDDEN void track_dev_release(ssm_tracker* t);
+SSM_HIDDEN int track_dev_run(ssm_tracker* t, const ssm_seq_out_dev* seq, int f, int n, PnpState* hs, double* pose_out, std::vector<ssm_track_info>& info);
 
 // ---------------------------------------------------------------- pose graph (ssm_pgo_host.cpp)
 struct PgoPlan {

@@ -2,8 +2,9 @@
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
 // which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the "no device" form of
-// csrc/ssm_host.h's hooks here.  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_track_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
+// "no device" form of csrc/ssm_host.h's hooks here (the bulk tracker's among them: no tracker is ever created on the stub; its state machine runs under the sanitizers
+// in host/test_track.cpp, over hooks of that program's own).  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
 #include "ssm_hip.h"
 #include "ssm/pnp_core.h"
 #include <cstring>
@@ -22,7 +23,13 @@ void pgo_dev_release(ssm_pgo*) {}
 int pgo_dev_optimize(ssm_pgo**, int, const ssm_pgc::View*, int) { return SSM_E_NODEVICE; }
 int pgo_dev_linearize(ssm_pgo*, const ssm_pgc::View&) { return SSM_E_NODEVICE; }
 int pgo_dev_factor_solve(ssm_pgo*, ssm_pgo&, const ssm_pgc::View&, double) { return SSM_E_NODEVICE; }
+struct PnpState;
+int track_dev_attach(ssm_tracker*) { return SSM_E_NODEVICE; }
+void track_dev_release(ssm_tracker*) {}
+int track_dev_run(ssm_tracker*, const ssm_seq_out_dev*, int, int, PnpState*, double*, std::vector<ssm_track_info>&) { return SSM_E_NODEVICE; }
 extern "C" {
+int ssm_sync(ssm_ctx*) { return SSM_E_NODEVICE; }                    // (the bulk tracker's downloads: never reached, see above)
+int ssm_memcpy_d2h(ssm_ctx*, void*, const void*, size_t) { return SSM_E_NODEVICE; }
 // the device entry points of the stages whose host halves are linked in: never reached (the host classes take the host path on a thread without a context)
 int ssm_vo_estimate(ssm_ctx*, const ssm_pmatch*, int, const ssm_vo_params*, const int32_t*, int, double*, int32_t*, int, int*, int*) { return SSM_E_NODEVICE; }      // (VisualOdometryStereo has to link: test_uvd fills its lists by hand)
 int ssm_uvd_process(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int, ssm_pmatch*, uint8_t*, int, uint8_t*, uint8_t*, uint8_t*, ssm_uvd_info*) { return SSM_E_NODEVICE; }
