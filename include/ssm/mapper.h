@@ -16,6 +16,12 @@
 // reference src/mapper.cpp:217-271, commented out there for want of a motion mask): Car joins the maybe-moving classes, and a blob of them leaves the map only
 // when it is large (motion_area_thres) and enough of it (motion_overlay_portion_thres) lies under frame->moving_mask, which UVDisparity fills (uv_disparity=1).
 // A frame whose moving_mask is empty is gated as before.  Both routes to a cloud take the fused form of their call.
+// mapper_outlier_removal=1 (default 0: the clouds exactly as before): a key-frame's camera-frame cloud goes through the statistical outlier removal (DESIGN.md s.15;
+// pcl::StatisticalOutlierRemoval with mapper_sor_mean_k 30 and mapper_sor_stddev 1.0 as reference src/mapper.cpp:137-146 sets it up, commented out there for its cost
+// on a CPU) ONCE, when the cloud is made, on both routes: deviceCloud through ssm_cloud_sor, generatePointCloud through ssm_sor_filter -- the same bytes.  The
+// reference's block filters the world-frame copy, in the incremental branch only, and again at every update.  Here the rebuild branch sees the same filtered clouds as
+// the incremental one and no cloud is filtered twice; a rigid transform changes the distances between points only by its rounding, so what the filter removes is the
+// same up to points whose value sits within that rounding of the threshold.
 #pragma once
 #include "common_headers.h"
 #include <atomic>
@@ -38,6 +44,9 @@ public:
         invert_pose = para.getData<int>("mapper_invert_pose", 0) != 0;          // the commented alternative at mapper.cpp:89
         map_output = para.getData<string>("map_output", string(""));
         device_map = para.getData<int>("mapper_device_map", 1) != 0;
+        outlier_removal = para.getData<int>("mapper_outlier_removal", 0) != 0;
+        sor_mean_k = para.getData<int>("mapper_sor_mean_k", 30);
+        sor_stddev = para.getData<double>("mapper_sor_stddev", 1.0);
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
     }
@@ -127,6 +136,13 @@ public:
             d.check(ssm_backproject_fused_dev(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, motionOf(frame), w, h, &cam, max_distance, &P, &cl), "ssm_backproject_fused_dev");
         } else
         d.check(ssm_backproject_dev(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, w, h, &cam, max_distance, &cl), "ssm_backproject_dev");
+        if (outlier_removal) {
+            const ssm_sor_params P = sorParams(); ssm_sor_info I{};
+            const int rc = ssm_cloud_sor(d.ctx(), cl, &P, &I);
+            if (rc != SSM_OK) ssm_cloud_free(d.ctx(), cl);
+            d.check(rc, "ssm_cloud_sor");
+            sorInfo[frame.get()] = I;
+        }
         devClouds[frame.get()] = cl;
         cloudsComputed++;
         return cl;
@@ -159,6 +175,14 @@ public:
             } else
             d.check(ssm_backproject(d.ctx(), frame->depth.ptr<uint16_t>(), frame->rgb.data, frame->semantic.data, w, h, &cam, nullptr, max_distance,
                                     reinterpret_cast<ssm_point*>(pc->points.data()), w * h, &n), "ssm_backproject");
+            if (outlier_removal) {
+                const ssm_sor_params P = sorParams(); ssm_sor_info I{};
+                vector<ssm_point> kept((size_t)max(n, 1)); int nk = 0;
+                d.check(ssm_sor_filter(d.ctx(), reinterpret_cast<const ssm_point*>(pc->points.data()), n, &P, kept.data(), (int)kept.size(), &nk, &I), "ssm_sor_filter");
+                if (nk > 0) memcpy((void*)pc->points.data(), kept.data(), (size_t)nk * sizeof(ssm_point));
+                n = nk;
+                sorInfo[frame.get()] = I;
+            }
             pc->points.resize(n); pc->points.shrink_to_fit(); pc->width = n; pc->is_dense = false;
             frame->pointcloud = pc;
             cloudsComputed++;
@@ -186,6 +210,14 @@ public:
         return mask;
     }
     bool fusesMotion() const { return fuse_motion; }
+    bool removesOutliers() const { return outlier_removal; }
+    // the filter's figures for a key-frame whose cloud has been made (either route; not while the viewer thread runs); false: no cloud yet, or the switch is off
+    bool sorInfoOf(const RGBDFrame::Ptr& frame, ssm_sor_info* info) const {
+        auto it = sorInfo.find(frame.get());
+        if (it == sorInfo.end()) return false;
+        if (info) *info = it->second;
+        return true;
+    }
     std::atomic<bool> viewerFailed{false};
     std::atomic<bool> deviceMapFellBack{false};                              // the device-resident map update failed once: host path since (same bits)
     int cloudsComputed = 0;                                                    // device back-projections so far (each frame costs one)
@@ -203,6 +235,7 @@ public:
         return out;
     }
 protected:
+    ssm_sor_params sorParams() const { ssm_sor_params P; ssm_sor_params_default(&P); P.mean_k = sor_mean_k; P.stddev_mul = sor_stddev; return P; }
     ssm_motion_fuse_params fuseParams() const { ssm_motion_fuse_params P; ssm_motion_fuse_params_default(&P); P.area_thres = area_thres; P.overlay_thres = overlay_portion_thres; return P; }
     // the frame's motion mask when UVDisparity left one of the semantic image's size (packed rows), else none
     static const uint8_t* motionOf(const RGBDFrame::Ptr& f) {
@@ -224,6 +257,8 @@ protected:
     bool fix_incremental = false, invert_pose = false, device_map = true, fuse_motion = false; int test_fail_update = -1;
     std::unordered_map<const RGBDFrame*, ssm_cloud*> devClouds;       // key-frame -> its camera-frame cloud in device memory (held until the viewer ends)
     int area_thres = 1000; double overlay_portion_thres = 0.143;
+    bool outlier_removal = false; int sor_mean_k = 30; double sor_stddev = 1.0;
+    std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)
     string map_output;
 };
 }  // namespace rgbd_tutor

@@ -476,6 +476,31 @@ int  ssm_backproject_fused(ssm_ctx* ctx, const uint16_t* depth, const uint8_t* r
 int  ssm_backproject_fused_dev(ssm_ctx* ctx, const uint16_t* depth, const uint8_t* rgb_bgr, const uint8_t* sem_bgr, const uint8_t* motion, int w, int h,
                                const ssm_camera* cam, double max_distance, const ssm_motion_fuse_params* params, ssm_cloud** cloud_out);
 
+/* ---- statistical outlier removal of a key-frame cloud (pcl::StatisticalOutlierRemoval as reference src/mapper.cpp:137-146 sets it up: meanK 30, stddev
+ * multiplier 1.0; commented out there): a point's value is the mean distance to its mean_k nearest neighbours, and a point stays when that is at most
+ * mean + stddev_mul * stddev over the cloud.  DESIGN.md s.15 is the contract; include/ssm/sor_core.h the arithmetic shared by the device path and the host
+ * function.  The neighbours are exact (a ladder of uniform grids, cell = its first cell size, 0: automatic -- a tuning parameter that changes no output);
+ * mean and stddev come from exact integer sums on a 2^-20 m grid.  Non-finite points are dropped; with fewer than mean_k + 1 finite points nothing else is
+ * (too_few).  The output keeps the input order and a kept point's 32 bytes.  1 <= mean_k <= 64. */
+typedef struct { int32_t mean_k; float cell; double stddev_mul; } ssm_sor_params;
+typedef struct { int32_t n_in, n_finite, n_kept, too_few, levels, pad; uint64_t sum_q, sum_q2_lo, sum_q2_hi; double mean, stddev, threshold; } ssm_sor_info;
+void ssm_sor_params_default(ssm_sor_params* p);                          /* 30, 0 (automatic), 1.0 */
+int  ssm_sor_chunk(void);                                                /* candidates per LDS chunk of the device search: the tests build a case around it */
+/* host arrays in and out; *n_out is the number kept (SSM_E_CAPACITY when cap is smaller: nothing written); info may be NULL.  SSM_E_INVAL: mean_k outside
+ * 1..64, a negative or non-finite cell, a non-finite stddev_mul, or a mean distance of 4096 m or more (off the statistics grid) */
+int  ssm_sor_filter(ssm_ctx* ctx, const ssm_point* pts, int n, const ssm_sor_params* params, ssm_point* out, int cap, int* n_out, ssm_sor_info* info);
+/* the same on the CPU, the same bits; needs no GPU.  mean_dist (n floats: the point's value, 0 where it has none) and keep (n bytes) may each be NULL */
+int  ssm_sor_filter_host(const ssm_point* pts, int n, const ssm_sor_params* params, ssm_point* out, int cap, int* n_out, ssm_sor_info* info,
+                         float* mean_dist, uint8_t* keep);
+/* the two arrays of the context's last device call (ssm_sor_filter or ssm_cloud_sor) over n points; each may be NULL */
+int  ssm_debug_sor_record(ssm_ctx* ctx, float* mean_dist, uint8_t* keep, int n);
+/* the ladder of the context's last device call: queries[l] = the points still unsettled when level l began (at most cap entries are written), *n_levels = info.levels.
+ * For scripts/sor_bench.py */
+int  ssm_debug_sor_levels(ssm_ctx* ctx, int32_t* queries, int cap, int* n_levels);
+/* the device-resident form: the cloud is filtered where it lives and shrinks in place (its memory is a piece of a slab that later clouds follow, so there
+ * is nothing to hand back); ssm_cloud_size is n_kept afterwards */
+int  ssm_cloud_sor(ssm_ctx* ctx, ssm_cloud* cloud, const ssm_sor_params* params, ssm_sor_info* info);
+
 /* ---- PoseGraph's optimiser (reference src/pose_graph.cpp:82-305, include/pose_graph.h:53-62): a graph of SE3 vertices and SE3 edges with Huber kernels,
  * Levenberg (g2o's OptimizationAlgorithmLevenberg) over a direct block-envelope L D L^T.  DESIGN.md s.12 is the contract; include/ssm/pgo_core.h holds the
  * arithmetic, ONE function template that the host function runs with one thread and the device path with one 1024-thread block per graph, so device ==

@@ -79,6 +79,15 @@ class MotionFuseInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("blobs", "large", "confirmed", "added")]
 
 
+class SorParams(C.Structure):
+    _fields_ = [("mean_k", C.c_int32), ("cell", C.c_float), ("stddev_mul", C.c_double)]
+
+
+class SorInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_in", "n_finite", "n_kept", "too_few", "levels", "pad")] + \
+               [(n, C.c_uint64) for n in ("sum_q", "sum_q2_lo", "sum_q2_hi")] + [(n, C.c_double) for n in ("mean", "stddev", "threshold")]
+
+
 class VocabTrainParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iters", C.c_int32)]
 
@@ -192,6 +201,13 @@ SYMBOLS = {
     "ssm_debug_motion_fuse": (_I, [_P, _I, _P, _P, _P, _P]),
     "ssm_backproject_fused": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Camera), _P, _D, C.POINTER(MotionFuseParams), _P, _I, C.POINTER(_I)]),
     "ssm_backproject_fused_dev": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(Camera), _D, C.POINTER(MotionFuseParams), C.POINTER(_P)]),
+    "ssm_sor_params_default": (None, [C.POINTER(SorParams)]),
+    "ssm_sor_chunk": (_I, []),
+    "ssm_sor_filter": (_I, [_P, _P, _I, C.POINTER(SorParams), _P, _I, C.POINTER(_I), C.POINTER(SorInfo)]),
+    "ssm_sor_filter_host": (_I, [_P, _I, C.POINTER(SorParams), _P, _I, C.POINTER(_I), C.POINTER(SorInfo), _P, _P]),
+    "ssm_debug_sor_record": (_I, [_P, _P, _P, _I]),
+    "ssm_debug_sor_levels": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "ssm_cloud_sor": (_I, [_P, _P, C.POINTER(SorParams), C.POINTER(SorInfo)]),
     "ssm_pgo_create": (_I, [_P, C.POINTER(_P)]),
     "ssm_pgo_destroy": (None, [_P]),
     "ssm_pgo_clear": (_I, [_P]),

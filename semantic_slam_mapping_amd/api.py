@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -144,6 +144,36 @@ def motion_fuse_host(sem, motion=None, area_thres=1000, overlay_thres=0.143, rec
         raise SsmError(rc, lib.ssm_last_error(None).decode())
     info = {k: getattr(I, k) for k in MOTION_FUSE_INFO_DTYPE.names}
     return (mask, info, rec) if record else (mask, info)
+
+
+SOR_INFO_FIELDS = ("n_in", "n_finite", "n_kept", "too_few", "levels", "sum_q", "sum_q2_lo", "sum_q2_hi", "mean", "stddev", "threshold")
+
+
+def sor_chunk():
+    """candidates per LDS chunk of the device search: ssm_sor_chunk"""
+    return _lib.load().ssm_sor_chunk()
+
+
+def _sor_points(points):
+    points = np.ascontiguousarray(points)
+    if points.dtype != POINT_DTYPE or points.ndim != 1:
+        raise ValueError("points: a 1-D array of POINT_DTYPE")
+    return points
+
+
+def sor_filter_host(points, mean_k=30, stddev_mul=1.0, cell=0.0, record=False):
+    """the statistical outlier removal on the CPU (ssm_sor_filter_host, no GPU): -> (points, info), or with record (points, info, {mean_dist, keep})"""
+    points = _sor_points(points)
+    n = len(points)
+    P = SorParams(int(mean_k), float(cell), float(stddev_mul)); I = SorInfo()
+    out = np.zeros(n, POINT_DTYPE); got = C.c_int(0)
+    rec = {"mean_dist": np.zeros(n, np.float32), "keep": np.zeros(n, np.uint8)} if record else {}
+    lib = _lib.load()
+    rc = lib.ssm_sor_filter_host(_ptr(points), n, C.byref(P), _ptr(out), n, C.byref(got), C.byref(I), _ptr(rec.get("mean_dist")), _ptr(rec.get("keep")))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    info = {k: getattr(I, k) for k in SOR_INFO_FIELDS}
+    return (out[:got.value], info, rec) if record else (out[:got.value], info)
 
 
 def _rows(a):
@@ -848,6 +878,35 @@ class Context:
                 if b is not None:
                     self.dev_free(b)
         return (mask, info, rec) if record else (mask, info)
+
+    def _sor_record(self, n):
+        rec = {"mean_dist": np.zeros(n, np.float32), "keep": np.zeros(n, np.uint8)}
+        self._chk(self.lib.ssm_debug_sor_record(self.h, _ptr(rec["mean_dist"]), _ptr(rec["keep"]), n))
+        return rec
+
+    def sor_filter(self, points, mean_k=30, stddev_mul=1.0, cell=0.0, record=False):
+        """the statistical outlier removal on the device (ssm_sor_filter): -> (points, info), or with record (points, info, {mean_dist, keep})"""
+        points = _sor_points(points)
+        n = len(points)
+        P = SorParams(int(mean_k), float(cell), float(stddev_mul)); I = SorInfo()
+        out = np.zeros(n, POINT_DTYPE); got = C.c_int(0)
+        self._chk(self.lib.ssm_sor_filter(self.h, _ptr(points), n, C.byref(P), _ptr(out), n, C.byref(got), C.byref(I)))
+        info = {k: getattr(I, k) for k in SOR_INFO_FIELDS}
+        return (out[:got.value], info, self._sor_record(n)) if record else (out[:got.value], info)
+
+    def sor_levels(self):
+        """the ladder of the last device call: the points still unsettled when each level began (ssm_debug_sor_levels)"""
+        q = np.zeros(24, np.int32); n = C.c_int(0)
+        self._chk(self.lib.ssm_debug_sor_levels(self.h, _ptr(q), len(q), C.byref(n)))
+        return q[:n.value].tolist()
+
+    def cloud_sor(self, cloud, mean_k=30, stddev_mul=1.0, cell=0.0, record=False):
+        """the same on a device-resident cloud (backproject_dev's handle), which shrinks in place: -> info, or with record (info, {mean_dist, keep})"""
+        n = self.lib.ssm_cloud_size(cloud)
+        P = SorParams(int(mean_k), float(cell), float(stddev_mul)); I = SorInfo()
+        self._chk(self.lib.ssm_cloud_sor(self.h, cloud, C.byref(P), C.byref(I)))
+        info = {k: getattr(I, k) for k in SOR_INFO_FIELDS}
+        return (info, self._sor_record(n)) if record else info
 
     def backproject_fused(self, depth, rgb, sem, motion=None, T=None, camera=None, max_distance=None, area_thres=1000, overlay_thres=0.143, device=False):
         """generate_point_cloud with the fused mask (ssm_backproject_fused); device=True: backproject_dev's form, -> an opaque cloud handle (cloud_free it)"""

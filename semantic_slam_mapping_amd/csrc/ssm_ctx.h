@@ -173,6 +173,16 @@ struct MfWork {
     DevBuf<uint8_t> always, cand, filled; DevBuf<int32_t> labels, area, overlap, info; PinBuf<int32_t> h_info;
     DevBuf<uint8_t> in_sem, in_motion, out_mask;      // staging of the host-image entry points (one frame)
 };
+// a key-frame's camera-frame cloud in device memory (ssm_map.hip ssm_backproject_dev; ssm_sor.hip filters it in place): n points at d, carved from cloud_slabs[slab]
+struct ssm_cloud { ssm_point* d = nullptr; int n = 0; int device = 0; int slab = -1; };
+// workspace of the statistical outlier removal (ssm_sor.hip) for cap points; n: the last call, for ssm_debug_sor_record
+struct SorWork {
+    int cap = 0, n = 0;
+    int levels = 0, level_q[24] = {};      // the last call's ladder: points unsettled when each level began (ssm_debug_sor_levels)
+    DevBuf<SorHead> head; PinBuf<SorHead> h_head; DevBuf<float> mean_dist; DevBuf<uint8_t> settled, keep, flags; DevBuf<uint64_t> keys_a, keys_b;
+    DevBuf<uint32_t> idx_a, idx_b, query, block_cnt, block_off; DevBuf<float4> sorted; DevBuf<uint8_t> tmp; size_t tmp_bytes = 0;
+    DevBuf<ssm_point> in, out;      // the host-array call's staging; out also holds ssm_cloud_sor's kept points before they go back into the cloud
+};
 // one ORB -> match chain of ssm_seq_process: the lane it runs on, its workspace, and the event behind its newest ORB + expand (what the next sub-batch's matcher waits for)
 struct OrbChain { Lane* lane; OrbWork work; Event orb_done; };
 
@@ -245,6 +255,7 @@ struct ssm_ctx {
     std::unique_ptr<StereoState> stereo; int stereo_B = 16; int stereo_sgbm_streams = 2;      // ssm_config.sgbm_streams 
     int sgbm_form_cfg = 0; long sgbm_fallbacks = 0;                                              // ssm_config.sgbm_form; sub-batches repeated in form 1 after a sweep time-out
     MfWork mf;                                               // semantic-motion fusion: allocated by its first call
+    SorWork sor;                                             // statistical outlier removal: allocated by its first call, grown by the largest
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;
@@ -298,6 +309,8 @@ SSM_HIDDEN int seg_init(ssm_ctx* c);
 SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, Lane& lane, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);
 // ssm_stereo_abi.hip
 SSM_HIDDEN int sgbm_recover(ssm_ctx* c);
+// ssm_sor.hip: the filter on n points in device memory, from the first launch to the call's last wait; the kept points are in c->sor.out, their number in info->n_kept
+SSM_HIDDEN int sor_run(ssm_ctx* c, const ssm_point* d_pts, int n, const ssm_sor_params* params, ssm_sor_info* info);
 // ssm_motion_fuse.hip: the fusion of n device frames queued on the main stream (no wait); motion_host: one frame's motion mask on the host, staged first (n == 1);
 // both null: no motion.  The counters stay in c->mf.info
 SSM_HIDDEN int mf_enqueue(ssm_ctx* c, const uint8_t* sem_dev, const uint8_t* motion_dev, const uint8_t* motion_host, int n, int w, int h,

@@ -216,6 +216,24 @@ int k_mf_tile_h();
 hipError_t k_motion_fuse(const uint8_t* sem, const uint8_t* motion, int n, int w, int h, int32_t area_thres, double overlay_thres, uint8_t* always, uint8_t* cand,
                          uint8_t* filled, int32_t* labels, int32_t* area, int32_t* overlap, uint8_t* mask, int32_t* info, hipStream_t s);
 
+// statistical outlier removal (kernels_sor.hip; the arithmetic is include/ssm/sor_core.h).  SorHead: the call's counters in device memory -- the finite points' box as
+// ordered ints, their number, the queries a level left unsettled, `bad` (a mean distance off the statistics grid), the queries of the current level, the three sums.
+// SorBufs: the workspaces, n entries each (block_cnt / block_off: one per k_sor_block() points, plus one); tmp: k_sor_tmp_bytes(n) for rocPRIM.
+// k_sor_begin: head, mean_dist = 0, settled = non-finite.  k_sor_level: one level of the ladder over the n_query points still unsettled (the host knows that number
+// from the previous level's read of head->remaining; level 0: nf).  k_sor_stats: the sums.  k_sor_compact: keep[] and the kept points, in input order, to `out`
+// (not pts); head->... is not touched: block_off[blocks] is the number kept.  Everything is queued on s, nothing waits.
+struct SorHead { int32_t mn[3], mx[3], n_finite, remaining, bad; uint32_t nq; unsigned long long s1, s2_lo, s2_hi; };
+struct SorBufs {
+    SorHead* head; float* mean_dist; uint8_t *settled, *keep, *flags; uint64_t *keys_a, *keys_b; uint32_t *idx_a, *idx_b, *query, *block_cnt, *block_off; float4* sorted;
+    void* tmp; size_t tmp_bytes;
+};
+int k_sor_block();
+size_t k_sor_tmp_bytes(int n);
+hipError_t k_sor_begin(const ssm_point* pts, int n, const SorBufs& B, hipStream_t s);
+hipError_t k_sor_level(const ssm_point* pts, int n, int nf, const float lo[3], double c, int top, int k, float r2, int n_query, const SorBufs& B, hipStream_t s);
+hipError_t k_sor_stats(const ssm_point* pts, int n, const SorBufs& B, hipStream_t s);
+hipError_t k_sor_compact(const ssm_point* pts, int n, double threshold, int too_few, const SorBufs& B, ssm_point* out, hipStream_t s);
+
 // pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);
 // op 1: linearise + assemble; op 2: factor and solve the view's envelope with `lambda`
 namespace ssm_pgc { struct View; }

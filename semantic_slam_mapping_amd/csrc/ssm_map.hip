@@ -510,7 +510,6 @@ extern "C" int ssm_voxel_filter(ssm_ctx* c, const ssm_point* pts, int n, float l
 }
 
 // ---------------------------------------------------------------- device-resident Mapper (ssm_backproject_dev, ssm_viewer_map_*)
-struct ssm_cloud { ssm_point* d = nullptr; int n = 0; int device = 0; int slab = -1; };
 // fused: the mask is the semantic-motion fusion's (ssm_motion_fuse.hip) instead of the class mask
 static int backproject_cloud(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, bool fused, const uint8_t* motion, const ssm_motion_fuse_params* params,
                              int w, int h, const ssm_camera* cam, double max_distance, ssm_cloud** cloud_out)

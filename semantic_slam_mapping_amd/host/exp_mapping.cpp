@@ -22,6 +22,9 @@
 // with --batched one bulk call per chunk does it.  The summary line then carries `moving_pixels N moving_fnv H pitch_fnv P` (the 255-pixels, FNV-1a over the mask
 // bytes and over the measured pitches of those frames, in order: the same in both modes).  Without the flag nothing of this runs and no output changes.
 //
+// `exp_mapping <parameters> --sor` (or mapper_outlier_removal=1): Mapper passes every key-frame's camera-frame cloud through the statistical outlier removal
+// (include/ssm/mapper.h) when it makes it.  The summary line then carries `sor_keyframes N sor_in P sor_kept K sor_fnv H`: over the key-frames in order,
+// the points before and after the filter and FNV-1a over the kept points (position and colour; the same in both modes).  Without the flag nothing of this runs.
 // `exp_mapping <parameters> --fuse-motion` (or motion_semantic_fuse=1; implies --moving, so it needs tracker_mode=stereo too): Mapper gates every key-frame's cloud with
 // the semantic-motion fusion of the frame's semantic image and its moving_mask (include/ssm/mapper.h) instead of the class mask alone.  The summary line
 // then carries `fused_keyframes K fused_confirmed C fused_added N fused_fnv H`: over the key-frames in order, the blobs confirmed as moving, the mask pixels they add to
@@ -122,6 +125,9 @@ int main(int argc, char** argv)
         parameterReader.set("uv_disparity", "1");
     }
     if (fuse_motion) parameterReader.set("motion_semantic_fuse", "1");
+    bool sor = parameterReader.getData<int>("mapper_outlier_removal", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--sor") sor = true;
+    if (sor) parameterReader.set("mapper_outlier_removal", "1");
     MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
@@ -350,6 +356,17 @@ int main(int argc, char** argv)
                 for (int r = 0; r < m.rows; r++) { const unsigned char* b = m.ptr<unsigned char>(r); for (int c = 0; c < m.cols; c++) { h ^= b[c]; h *= 0x100000001B3ull; } }
             }
             cout << " fused_keyframes " << poseGraph.keyframes.size() << " fused_confirmed " << confirmed << " fused_added " << added << " fused_fnv " << hex << h << dec;
+        }
+        if (sor) {              // (the viewer thread has ended; a key-frame it never reached gets its cloud here, by the host route -- the same bytes)
+            uint64_t h = 0xCBF29CE484222325ull; long long n_in = 0, n_kept = 0;
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) {
+                mapper.generatePointCloud(kf);
+                ssm_sor_info I{};
+                if (!mapper.sorInfoOf(kf, &I)) { cerr << "exp_mapping: a key-frame's cloud was not filtered" << endl; return 3; }
+                n_in += I.n_in; n_kept += I.n_kept;
+                for (const Mapper::PointT& p : kf->pointcloud->points) { const unsigned char* b = (const unsigned char*)&p; for (int k = 0; k < 20; k++) { if (k == 12) k = 16; h ^= b[k]; h *= 0x100000001B3ull; } }
+            }
+            cout << " sor_keyframes " << poseGraph.keyframes.size() << " sor_in " << n_in << " sor_kept " << n_kept << " sor_fnv " << hex << h << dec;
         }
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;

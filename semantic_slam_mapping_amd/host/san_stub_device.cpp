@@ -2,7 +2,7 @@
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
 // which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_track_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_track_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
 // "no device" form of csrc/ssm_host.h's hooks here (the bulk tracker's among them: no tracker is ever created on the stub; its state machine runs under the sanitizers
 // in host/test_track.cpp, over hooks of that program's own).  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
 #include "ssm_hip.h"
@@ -92,6 +92,16 @@ int ssm_backproject_fused_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* 
                               const ssm_motion_fuse_params*, ssm_cloud** out) { return ssm_backproject_dev(c, depth, rgb, sem, w, h, cam, md, out); }
 int ssm_motion_fuse(ssm_ctx*, const uint8_t* sem, const uint8_t* motion, int w, int h, int stride, const ssm_motion_fuse_params* params, uint8_t* mask, ssm_motion_fuse_info* info)
 { return ssm_motion_fuse_host(sem, motion, w, h, stride, params, mask, info, nullptr, nullptr, nullptr, nullptr); }
+// the outlier removal (Mapper with mapper_outlier_removal=1): the linked host function in the device entry points' place
+int ssm_sor_filter(ssm_ctx*, const ssm_point* pts, int n, const ssm_sor_params* params, ssm_point* out, int cap, int* n_out, ssm_sor_info* info)
+{ return ssm_sor_filter_host(pts, n, params, out, cap, n_out, info, nullptr, nullptr); }
+int ssm_cloud_sor(ssm_ctx*, ssm_cloud* cl, const ssm_sor_params* params, ssm_sor_info* info)
+{
+    std::vector<ssm_point> out(cl->p.size() + 1); int n = 0;
+    const int rc = ssm_sor_filter_host(cl->p.data(), (int)cl->p.size(), params, out.data(), (int)out.size(), &n, info, nullptr, nullptr);
+    if (rc == SSM_OK) { out.resize((size_t)n); cl->p.swap(out); }
+    return rc;
+}
 int ssm_cloud_size(const ssm_cloud* cl) { return cl ? (int)cl->p.size() : 0; }
 void ssm_cloud_free(ssm_ctx*, ssm_cloud* cl) { delete cl; }
 int ssm_cloud_fetch(ssm_ctx*, const ssm_cloud* cl, const double*, ssm_point* out, int cap, int* n_out)
