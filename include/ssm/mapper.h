@@ -22,6 +22,14 @@
 // reference's block filters the world-frame copy, in the incremental branch only, and again at every update.  Here the rebuild branch sees the same filtered clouds as
 // the incremental one and no cloud is filtered twice; a rigid transform changes the distances between points only by its rounding, so what the filter removes is the
 // same up to points whose value sits within that rounding of the threshold.
+// mapper_carve=1 (default 0: nothing of this runs, every cloud and every map exactly as before): free-space carving (the reference has no such
+// step).  Every key-frame j is a VIEW exactly once, in ascending j, before the viewer selects the clouds of an update and once more when the viewer ends (so every
+// key-frame has been applied however the thread was scheduled): its depth image judges the clouds of key-frames j - mapper_carve_window .. j - 1, which are made on
+// demand; the poses are read at that moment.  A point seen through mapper_carve_votes views in a row leaves its cloud for good.  Both routes give the same bytes:
+// deviceCloud / ssm_carve (one call per view: the view's depth image is uploaded, applied to all its clouds and freed -- it is never needed again, so no view lives
+// for `window` key-frames) and frame->pointcloud / ssm_carve_points with the counters kept beside the cloud (carveRun).  The two do not mix: when the device-resident
+// update fails with the switch on, the counters of the freed device clouds are gone, so the viewer stops (viewerFailed) instead of falling back to the host path.
+// Carved points leave the PUBLISHED map at the next rebuild (every 15th update): an incremental update carries the previous centroids.  The schedule is unchanged.
 #pragma once
 #include "common_headers.h"
 #include <atomic>
@@ -47,6 +55,13 @@ public:
         outlier_removal = para.getData<int>("mapper_outlier_removal", 0) != 0;
         sor_mean_k = para.getData<int>("mapper_sor_mean_k", 30);
         sor_stddev = para.getData<double>("mapper_sor_stddev", 1.0);
+        carve = para.getData<int>("mapper_carve", 0) != 0;
+        carve_window = para.getData<int>("mapper_carve_window", 5);                 // the reach of the reference's "last five" loop (mapper.cpp:134)
+        ssm_carve_params_default(&carve_params);
+        carve_params.min_votes = para.getData<int>("mapper_carve_votes", carve_params.min_votes);
+        carve_params.radius = para.getData<int>("mapper_carve_radius", carve_params.radius);
+        carve_params.tol_abs = para.getData<double>("mapper_carve_tol_abs", carve_params.tol_abs);
+        carve_params.tol_rel_ppm = para.getData<int>("mapper_carve_tol_rel_ppm", carve_params.tol_rel_ppm);
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
     }
@@ -64,6 +79,7 @@ public:
             if (nkf <= (size_t)keyframe_size) { this_thread::sleep_for(chrono::milliseconds(1)); continue; }
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
             auto t0 = chrono::steady_clock::now();
+            if (carve) carveUpTo(kfs);
             // the key-frames this update adds (mapper.cpp:121-141)
             vector<RGBDFrame::Ptr> sel; const bool rebuild = cntGlobalUpdate % 15 == 0;
             if (rebuild) { for (size_t i = 0; i < kfs.size(); i += 2) sel.push_back(kfs[i]); }
@@ -96,6 +112,7 @@ public:
                     keyframe_size = (int)kfs.size();
                     on_device = true;
                 } catch (const std::exception& e) {
+                    if (carve) { cerr << "Mapper: the device-resident map update failed with mapper_carve=1; the clouds' run counters cannot follow to the host path" << endl; throw; }
                     cerr << "Mapper: the device-resident map update failed (" << e.what() << "); this and the following updates run on the host path" << endl;
                     for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second);
                     devClouds.clear(); device_map = false; deviceMapFellBack = true;
@@ -115,6 +132,10 @@ public:
             const double ms = chrono::duration<double, milli>(chrono::steady_clock::now() - t0).count();
             cout << "points in global map: " << map->points.size() << endl;
             cout << "Mapping cost time: " << ms << "ms" << endl;
+        }
+        if (carve) {                                    // the key-frames that came after the last update are views too: the clouds' final state does not depend on this thread's timing
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            carveUpTo(kfs);
         }
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
@@ -161,6 +182,21 @@ public:
     // frame's current pose (pcl::transformPointCloud, mapper.cpp:91: x' = float(t00 x + t01 y + t02 z + t03) in double, left to right -- the same
     // arithmetic ssm_backproject applies on the device when it is given T, so both routes give identical bits; -ffp-contract=off in host/Makefile)
     PointCloud::Ptr generatePointCloud(const RGBDFrame::Ptr& frame) {
+        hostCloud(frame);
+        const Eigen::Isometry3d T = invert_pose ? frame->getTransform().inverse() : frame->getTransform();
+        const double* t = T.data();                                            // column-major
+        PointCloud::Ptr tmp(new PointCloud(*frame->pointcloud));
+        for (PointT& p : tmp->points) {
+            const double x = p.x, y = p.y, z = p.z;
+            p.x = (float)(t[0] * x + t[4] * y + t[8] * z + t[12]);
+            p.y = (float)(t[1] * x + t[5] * y + t[9] * z + t[13]);
+            p.z = (float)(t[2] * x + t[6] * y + t[10] * z + t[14]);
+        }
+        tmp->is_dense = false;
+        return tmp;
+    }
+    // the first half of generatePointCloud: frame->pointcloud, made once
+    void hostCloud(const RGBDFrame::Ptr& frame) {
         if (frame->pointcloud == nullptr) {
             ssm::Device& d = device(frame->depth.cols, frame->depth.rows);
             const int w = frame->depth.cols, h = frame->depth.rows;
@@ -187,17 +223,65 @@ public:
             frame->pointcloud = pc;
             cloudsComputed++;
         }
-        const Eigen::Isometry3d T = invert_pose ? frame->getTransform().inverse() : frame->getTransform();
-        const double* t = T.data();                                            // column-major
-        PointCloud::Ptr tmp(new PointCloud(*frame->pointcloud));
-        for (PointT& p : tmp->points) {
-            const double x = p.x, y = p.y, z = p.z;
-            p.x = (float)(t[0] * x + t[4] * y + t[8] * z + t[12]);
-            p.y = (float)(t[1] * x + t[5] * y + t[9] * z + t[13]);
-            p.z = (float)(t[2] * x + t[6] * y + t[10] * z + t[14]);
+    }
+    // free-space carving: the key-frames kfs[carved ..] become views, one after the other, each of the clouds of the `carve_window` key-frames before it.  The
+    // viewer thread calls this; once that has ended its owner may (the host route then: the device clouds went with the thread)
+    void carveUpTo(const vector<RGBDFrame::Ptr>& kfs) {
+        for (; carved < kfs.size(); carved++) {
+            const size_t j = carved, first = j > (size_t)max(carve_window, 0) ? j - (size_t)max(carve_window, 0) : 0;
+            if (first == j) continue;
+            const RGBDFrame::Ptr& vf = kfs[j];
+            const int w = vf->depth.cols, h = vf->depth.rows;
+            ssm::Device& d = device(w, h);
+            ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
+            const Eigen::Isometry3d Tv = invert_pose ? vf->getTransform().inverse() : vf->getTransform();
+            const int m = (int)(j - first);
+            vector<double> poses; vector<ssm_carve_info> infos((size_t)m);
+            for (size_t i = first; i < j; i++) {
+                const Eigen::Isometry3d T = invert_pose ? kfs[i]->getTransform().inverse() : kfs[i]->getTransform();
+                poses.insert(poses.end(), T.data(), T.data() + 16);
+            }
+            if (device_map) {
+                vector<ssm_cloud*> cl;
+                for (size_t i = first; i < j; i++) cl.push_back(deviceCloud(kfs[i]));
+                ssm_carve_view* view = nullptr;
+                d.check(ssm_carve_view_create(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, &view), "ssm_carve_view_create");
+                const int rc = ssm_carve(d.ctx(), view, Tv.data(), cl.data(), poses.data(), m, &carve_params, infos.data());
+                ssm_carve_view_free(d.ctx(), view);
+                d.check(rc, "ssm_carve");
+            } else {
+                for (size_t i = first; i < j; i++) {
+                    hostCloud(kfs[i]);
+                    PointCloud& pc = *kfs[i]->pointcloud;
+                    const int n = (int)pc.points.size();
+                    vector<uint8_t>& run = carveRun[kfs[i].get()];
+                    run.resize((size_t)n, 0);
+                    vector<ssm_point> kept((size_t)max(n, 1)); int nk = 0;
+                    d.check(ssm_carve_points(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, Tv.data(), reinterpret_cast<const ssm_point*>(pc.points.data()), n, &poses[(i - first) * 16],
+                                             run.data(), &carve_params, kept.data(), (int)kept.size(), &nk, &infos[i - first]), "ssm_carve_points");
+                    if (nk > 0) memcpy((void*)pc.points.data(), kept.data(), (size_t)nk * sizeof(ssm_point));
+                    pc.points.resize((size_t)nk); pc.width = nk; run.resize((size_t)nk);
+                }
+            }
+            for (size_t i = first; i < j; i++) {
+                const ssm_carve_info& I = infos[i - first];
+                auto it = carveInfo.find(kfs[i].get());
+                if (it == carveInfo.end()) it = carveInfo.emplace(kfs[i].get(), ssm_carve_info{I.n_in, I.n_in, 0, 0, 0, 0, 0, 0}).first;
+                ssm_carve_info& A = it->second;
+                A.n_kept = I.n_kept; A.unknown += I.unknown; A.occluded += I.occluded; A.supported += I.supported; A.seen_through += I.seen_through; A.removed += I.removed;
+            }
+            carveViews++;
         }
-        tmp->is_dense = false;
-        return tmp;
+    }
+    bool carves() const { return carve; }
+    int carvedViews() const { return carveViews; }                            // views applied so far (a first key-frame has no earlier cloud and is none)
+    // what carving did to a key-frame's cloud over all the views applied to it: n_in its size before the first, n_kept its size now, the verdicts and `removed` summed
+    // (not while the viewer thread runs); false: no view has been applied to it, or the switch is off
+    bool carveInfoOf(const RGBDFrame::Ptr& frame, ssm_carve_info* info) const {
+        auto it = carveInfo.find(frame.get());
+        if (it == carveInfo.end()) return false;
+        if (info) *info = it->second;
+        return true;
     }
     // src/mapper.cpp:189-271 under its own name: the mask that gates the frame's cloud.  motion_semantic_fuse=0: the always-moving classes, dilated (what
     // ssm_moving_mask gives); 1: fused with frame->moving_mask.  info: the fusion's counters.  Uses the Mapper's device: not while the viewer thread runs
@@ -258,6 +342,9 @@ protected:
     std::unordered_map<const RGBDFrame*, ssm_cloud*> devClouds;       // key-frame -> its camera-frame cloud in device memory (held until the viewer ends)
     int area_thres = 1000; double overlay_portion_thres = 0.143;
     bool outlier_removal = false; int sor_mean_k = 30; double sor_stddev = 1.0;
+    bool carve = false; int carve_window = 5; ssm_carve_params carve_params{}; size_t carved = 0; int carveViews = 0;
+    std::unordered_map<const RGBDFrame*, vector<uint8_t>> carveRun;      // host route: the run counters beside frame->pointcloud
+    std::unordered_map<const RGBDFrame*, ssm_carve_info> carveInfo;      // key-frame -> what the views did to its cloud (viewer thread, or its owner once that has ended)
     std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)
     string map_output;
 };

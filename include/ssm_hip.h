@@ -501,6 +501,40 @@ int  ssm_debug_sor_levels(ssm_ctx* ctx, int32_t* queries, int cap, int* n_levels
  * is nothing to hand back); ssm_cloud_size is n_kept afterwards */
 int  ssm_cloud_sor(ssm_ctx* ctx, ssm_cloud* cloud, const ssm_sor_params* params, ssm_sor_info* info);
 
+/* ---- free-space carving: a LATER key-frame's depth image (the view) judges the points of earlier key-frames' camera-frame clouds, and a point the view has
+ * seen through `min_votes` times in a row leaves its cloud.  The reference has no such step; DESIGN.md s.16 is the contract, include/ssm/carve_core.h the
+ * arithmetic shared by the device path and the host function.  A point is carried into the view's frame by T_rel = inverse(T_view) . T_cloud (4x4, column-major
+ * doubles as elsewhere in this header), projected to the nearest pixel and compared, in integer depth units, with the (2 radius + 1)^2 window around it:
+ * verdict 0 UNKNOWN (non-finite, nearer than z_min, window not inside the image or holding a zero depth), 1 OCCLUDED, 2 SUPPORTED (within tol of the centre
+ * depth), 3 SEEN_THROUGH (nearer than the window's minimum by more than tol); tol = tol_abs + depth * tol_rel_ppm / 10^6.  Every point has a run counter
+ * (uint8, zero when the cloud is made): SEEN_THROUGH adds one (up to 255), SUPPORTED clears it, the others leave it; afterwards a point whose counter is at
+ * least min_votes is removed.  The rest keep their order, their 32 bytes and their counters.
+ * SSM_E_INVAL: min_votes outside 1..255, radius outside 0..3, tol_abs outside 0..10^6 or non-finite, tol_rel_ppm outside 0..10^6, z_min negative or
+ * non-finite, a camera whose fx, fy, cx, cy are not finite or whose scale is outside (0, 10^6], a non-finite pose. */
+typedef struct { int32_t min_votes, radius; double tol_abs; int32_t tol_rel_ppm, pad; double z_min; } ssm_carve_params;
+typedef struct { int32_t n_in, n_kept, unknown, occluded, supported, seen_through, removed, pad; } ssm_carve_info;
+typedef struct ssm_carve_view ssm_carve_view;
+void ssm_carve_params_default(ssm_carve_params* p);                      /* 2, 1, 0.05 m, 20000 ppm, 0.1 m */
+/* a view: the depth image goes to device memory and stays there until ssm_carve_view_free */
+int  ssm_carve_view_create(ssm_ctx* ctx, const uint16_t* depth_host, int w, int h, const ssm_camera* cam, ssm_carve_view** view_out);
+void ssm_carve_view_free(ssm_ctx* ctx, ssm_carve_view* view);
+/* the pipeline's form: one view against m device-resident clouds (T_clouds: m poses of 16 doubles) in one launch sequence and one wait.  The clouds shrink in
+ * place (ssm_cloud_size is the kept count afterwards) and their counters live with them; a cloud of size 0 is legal, the same cloud twice is not.  infos: m
+ * entries, may be NULL.  A cloud that has counters is refused by ssm_cloud_sor (SSM_E_INVAL): filter first, carve afterwards. */
+int  ssm_carve(ssm_ctx* ctx, const ssm_carve_view* view, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
+               const ssm_carve_params* params, ssm_carve_info* infos);
+/* host arrays through the device: run_inout holds the n counters before and the *n_out kept counters after (NULL: all zero, none returned); *n_out is the number
+ * kept (SSM_E_CAPACITY when cap is smaller: nothing written, run_inout untouched); info may be NULL */
+int  ssm_carve_points(ssm_ctx* ctx, const uint16_t* depth, int w, int h, const ssm_camera* cam, const double* T_view, const ssm_point* pts, int n,
+                      const double* T_cloud, uint8_t* run_inout, const ssm_carve_params* params, ssm_point* out, int cap, int* n_out, ssm_carve_info* info);
+/* the same on the CPU, the same bits; needs no GPU.  verdict and run (n bytes each: every point's verdict and its counter BEFORE the compaction) may be NULL */
+int  ssm_carve_host(const uint16_t* depth, int w, int h, const ssm_camera* cam, const double* T_view, const ssm_point* pts, int n, const double* T_cloud,
+                    uint8_t* run_inout, const ssm_carve_params* params, ssm_point* out, int cap, int* n_out, ssm_carve_info* info, uint8_t* verdict, uint8_t* run);
+/* the same two arrays for cloud k of the context's last device call (ssm_carve: k < m; ssm_carve_points: k = 0) over its n points; each may be NULL */
+int  ssm_debug_carve_record(ssm_ctx* ctx, int k, uint8_t* verdict, uint8_t* run, int n);
+/* the counters of a device-resident cloud (all zero before its first ssm_carve): cap >= ssm_cloud_size entries */
+int  ssm_cloud_run_fetch(ssm_ctx* ctx, const ssm_cloud* cloud, uint8_t* run, int cap);
+
 /* ---- PoseGraph's optimiser (reference src/pose_graph.cpp:82-305, include/pose_graph.h:53-62): a graph of SE3 vertices and SE3 edges with Huber kernels,
  * Levenberg (g2o's OptimizationAlgorithmLevenberg) over a direct block-envelope L D L^T.  DESIGN.md s.12 is the contract; include/ssm/pgo_core.h holds the
  * arithmetic, ONE function template that the host function runs with one thread and the device path with one 1024-thread block per graph, so device ==

@@ -88,6 +88,14 @@ class SorInfo(C.Structure):
                [(n, C.c_uint64) for n in ("sum_q", "sum_q2_lo", "sum_q2_hi")] + [(n, C.c_double) for n in ("mean", "stddev", "threshold")]
 
 
+class CarveParams(C.Structure):
+    _fields_ = [("min_votes", C.c_int32), ("radius", C.c_int32), ("tol_abs", C.c_double), ("tol_rel_ppm", C.c_int32), ("pad", C.c_int32), ("z_min", C.c_double)]
+
+
+class CarveInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_in", "n_kept", "unknown", "occluded", "supported", "seen_through", "removed", "pad")]
+
+
 class VocabTrainParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iters", C.c_int32)]
 
@@ -208,6 +216,14 @@ SYMBOLS = {
     "ssm_debug_sor_record": (_I, [_P, _P, _P, _I]),
     "ssm_debug_sor_levels": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "ssm_cloud_sor": (_I, [_P, _P, C.POINTER(SorParams), C.POINTER(SorInfo)]),
+    "ssm_carve_params_default": (None, [C.POINTER(CarveParams)]),
+    "ssm_carve_view_create": (_I, [_P, _P, _I, _I, C.POINTER(Camera), C.POINTER(_P)]),
+    "ssm_carve_view_free": (None, [_P, _P]),
+    "ssm_carve": (_I, [_P, _P, _P, _P, _P, _I, C.POINTER(CarveParams), _P]),
+    "ssm_carve_points": (_I, [_P, _P, _I, _I, C.POINTER(Camera), _P, _P, _I, _P, _P, C.POINTER(CarveParams), _P, _I, C.POINTER(_I), C.POINTER(CarveInfo)]),
+    "ssm_carve_host": (_I, [_P, _I, _I, C.POINTER(Camera), _P, _P, _I, _P, _P, C.POINTER(CarveParams), _P, _I, C.POINTER(_I), C.POINTER(CarveInfo), _P, _P]),
+    "ssm_debug_carve_record": (_I, [_P, _I, _P, _P, _I]),
+    "ssm_cloud_run_fetch": (_I, [_P, _P, _P, _I]),
     "ssm_pgo_create": (_I, [_P, C.POINTER(_P)]),
     "ssm_pgo_destroy": (None, [_P]),
     "ssm_pgo_clear": (_I, [_P]),

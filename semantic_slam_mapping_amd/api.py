@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -174,6 +174,57 @@ def sor_filter_host(points, mean_k=30, stddev_mul=1.0, cell=0.0, record=False):
         raise SsmError(rc, lib.ssm_last_error(None).decode())
     info = {k: getattr(I, k) for k in SOR_INFO_FIELDS}
     return (out[:got.value], info, rec) if record else (out[:got.value], info)
+
+
+CARVE_INFO_FIELDS = ("n_in", "n_kept", "unknown", "occluded", "supported", "seen_through", "removed")
+CARVE_DEFAULTS = dict(min_votes=2, radius=1, tol_abs=0.05, tol_rel_ppm=20000, z_min=0.1)
+
+
+def _carve_params(kw):
+    bad = set(kw) - set(CARVE_DEFAULTS)
+    if bad:
+        raise TypeError("unknown carving parameters: " + ", ".join(sorted(bad)))
+    p = dict(CARVE_DEFAULTS, **kw)
+    return CarveParams(int(p["min_votes"]), int(p["radius"]), float(p["tol_abs"]), int(p["tol_rel_ppm"]), 0, float(p["z_min"]))
+
+
+def _cm16(T):
+    """a 4 x 4 pose as the ABI's 16 column-major doubles"""
+    T = np.asarray(T, np.float64)
+    if T.shape != (4, 4):
+        raise ValueError("a pose is a 4 x 4 matrix")
+    return np.ascontiguousarray(T.T).reshape(16)
+
+
+def _carve_run(run, n):
+    run = np.zeros(n, np.uint8) if run is None else np.array(run, np.uint8)          # (a copy: the call compacts it in place)
+    if run.shape != (n,):
+        raise ValueError("run: one uint8 per point")
+    return run
+
+
+def _carve_info(I):
+    return {k: getattr(I, k) for k in CARVE_INFO_FIELDS}
+
+
+def carve_host(depth, camera, T_view, points, T_cloud, run=None, record=False, **params):
+    """free-space carving on the CPU (ssm_carve_host, no GPU): the view (depth, camera = (cx, cy, fx, fy, scale), T_view) judges `points` of a cloud at T_cloud whose run
+    counters are `run` (None: zero) -> (points, run, info), or with record (points, run, info, {verdict, run}: every point's, before the compaction)"""
+    depth = np.ascontiguousarray(depth, np.uint16); points = _sor_points(points)
+    h, w = depth.shape
+    n = len(points)
+    P = _carve_params(params); I = CarveInfo(); cam = Camera(*camera)
+    Tv, Tc = _cm16(T_view), _cm16(T_cloud)
+    run = _carve_run(run, n)
+    out = np.zeros(n, POINT_DTYPE); got = C.c_int(0)
+    rec = {"verdict": np.zeros(n, np.uint8), "run": np.zeros(n, np.uint8)} if record else {}
+    lib = _lib.load()
+    rc = lib.ssm_carve_host(_ptr(depth), w, h, C.byref(cam), _ptr(Tv), _ptr(points), n, _ptr(Tc), _ptr(run), C.byref(P), _ptr(out), n, C.byref(got), C.byref(I),
+                            _ptr(rec.get("verdict")), _ptr(rec.get("run")))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    res = (out[:got.value], run[:got.value], _carve_info(I))
+    return res + (rec,) if record else res
 
 
 def _rows(a):
@@ -907,6 +958,54 @@ class Context:
         self._chk(self.lib.ssm_cloud_sor(self.h, cloud, C.byref(P), C.byref(I)))
         info = {k: getattr(I, k) for k in SOR_INFO_FIELDS}
         return (info, self._sor_record(n)) if record else info
+
+    def carve_view(self, depth, camera=None):
+        """a view of free-space carving: the depth image goes to the device and stays (ssm_carve_view_create) -> an opaque handle (carve_view_free it)"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        h, w = depth.shape
+        cam = Camera(*camera) if camera is not None else self.cfg.camera
+        v = C.c_void_p()
+        self._chk(self.lib.ssm_carve_view_create(self.h, _ptr(depth), w, h, C.byref(cam), C.byref(v)))
+        return v.value
+
+    def carve_view_free(self, view):
+        self.lib.ssm_carve_view_free(self.h, view)
+
+    def _carve_record(self, k, n):
+        rec = {"verdict": np.zeros(n, np.uint8), "run": np.zeros(n, np.uint8)}
+        self._chk(self.lib.ssm_debug_carve_record(self.h, k, _ptr(rec["verdict"]), _ptr(rec["run"]), n))
+        return rec
+
+    def carve(self, view, T_view, clouds, T_clouds, record=False, **params):
+        """one view against device-resident clouds (backproject_dev's handles), which shrink in place (ssm_carve) -> the infos, or with record (infos, [{verdict, run}])"""
+        m = len(clouds)
+        sizes = [self.cloud_size(cl) for cl in clouds]
+        arr = (C.c_void_p * max(m, 1))(*clouds)
+        Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+        P = _carve_params(params); infos = (CarveInfo * max(m, 1))()
+        self._chk(self.lib.ssm_carve(self.h, view, _ptr(_cm16(T_view)), arr, _ptr(Tc), m, C.byref(P), infos))
+        out = [_carve_info(infos[k]) for k in range(m)]
+        return (out, [self._carve_record(k, sizes[k]) for k in range(m)]) if record else out
+
+    def cloud_run(self, cloud):
+        """the run counters of a device-resident cloud (ssm_cloud_run_fetch)"""
+        n = self.cloud_size(cloud)
+        run = np.zeros(max(n, 1), np.uint8)
+        self._chk(self.lib.ssm_cloud_run_fetch(self.h, cloud, _ptr(run), len(run)))
+        return run[:n]
+
+    def carve_points(self, depth, camera, T_view, points, T_cloud, run=None, record=False, **params):
+        """carve_host's call through the device (ssm_carve_points): -> (points, run, info), or with record (points, run, info, {verdict, run})"""
+        depth = np.ascontiguousarray(depth, np.uint16); points = _sor_points(points)
+        h, w = depth.shape
+        n = len(points)
+        P = _carve_params(params); I = CarveInfo(); cam = Camera(*camera)
+        Tv, Tc = _cm16(T_view), _cm16(T_cloud)
+        run = _carve_run(run, n)
+        out = np.zeros(n, POINT_DTYPE); got = C.c_int(0)
+        self._chk(self.lib.ssm_carve_points(self.h, _ptr(depth), w, h, C.byref(cam), _ptr(Tv), _ptr(points), n, _ptr(Tc), _ptr(run), C.byref(P), _ptr(out), n, C.byref(got), C.byref(I)))
+        res = (out[:got.value], run[:got.value], _carve_info(I))
+        return res + (self._carve_record(0, n),) if record else res
 
     def backproject_fused(self, depth, rgb, sem, motion=None, T=None, camera=None, max_distance=None, area_thres=1000, overlay_thres=0.143, device=False):
         """generate_point_cloud with the fused mask (ssm_backproject_fused); device=True: backproject_dev's form, -> an opaque cloud handle (cloud_free it)"""

@@ -174,7 +174,19 @@ struct MfWork {
     DevBuf<uint8_t> in_sem, in_motion, out_mask;      // staging of the host-image entry points (one frame)
 };
 // a key-frame's camera-frame cloud in device memory (ssm_map.hip ssm_backproject_dev; ssm_sor.hip filters it in place): n points at d, carved from cloud_slabs[slab]
-struct ssm_cloud { ssm_point* d = nullptr; int n = 0; int device = 0; int slab = -1; };
+// run: the points' run counters of free-space carving (ssm_carve.hip), n bytes made by the cloud's first ssm_carve; empty before
+struct ssm_cloud { ssm_point* d = nullptr; int n = 0; int device = 0; int slab = -1; DevBuf<uint8_t> run; };
+// a view of free-space carving: a key-frame's depth image in device memory and its camera
+struct ssm_carve_view { DevBuf<uint16_t> depth; int w = 0, h = 0, device = 0; ssm_camera cam{}; };
+// workspace of free-space carving (ssm_carve.hip) for cap points in cap_m clouds; off: the last call's clouds as numbers of their first points (m + 1 entries), for
+// ssm_debug_carve_record
+struct CarveWork {
+    int cap = 0, cap_m = 0; std::vector<int> off;
+    DevBuf<uint8_t> table; PinBuf<uint8_t> h_table; size_t table_bytes = 0;      // CarveSeg[m], then the blocks' first clouds
+    DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<uint32_t> base, block_cnt, block_off; DevBuf<uint8_t> verdict, run_new, keep, tmp_run, tmp; size_t tmp_bytes = 0;
+    DevBuf<ssm_point> tmp_pts;
+    DevBuf<ssm_point> in; DevBuf<uint8_t> run_in; DevBuf<uint16_t> depth; size_t in_cap = 0, depth_cap = 0;      // the host-array call's staging
+};
 // workspace of the statistical outlier removal (ssm_sor.hip) for cap points; n: the last call, for ssm_debug_sor_record
 struct SorWork {
     int cap = 0, n = 0;
@@ -256,6 +268,7 @@ struct ssm_ctx {
     int sgbm_form_cfg = 0; long sgbm_fallbacks = 0;                                              // ssm_config.sgbm_form; sub-batches repeated in form 1 after a sweep time-out
     MfWork mf;                                               // semantic-motion fusion: allocated by its first call
     SorWork sor;                                             // statistical outlier removal: allocated by its first call, grown by the largest
+    CarveWork carve;                                         // free-space carving: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;

@@ -1,4 +1,4 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_track_host.cpp:
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_track_host.cpp:
 // plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units.  Those sources are compiled once and LINKED into libssm_hip.so, into the
 // CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
 // defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
@@ -9,6 +9,7 @@
 #include "../../include/ssm/pgo_core.h"
 #include "../../include/ssm/motion_fuse_core.h"
 #include "../../include/ssm/sor_core.h"
+#include "../../include/ssm/carve_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
 #include <algorithm>
@@ -90,6 +91,11 @@ SSM_HIDDEN int mf_check(ssm_ctx* c, int n, int w, int h, size_t stride);        
 // ---------------------------------------------------------------- statistical outlier removal (ssm_sor_host.cpp)
 SSM_HIDDEN int sor_check(ssm_ctx* c, int n, const ssm_sor_params& P);          // the arguments a call may have (host function and device entry points alike)
 SSM_HIDDEN int sor_off_grid(ssm_ctx* c);                                       // SSM_E_INVAL with the message of a mean distance off the statistics grid
+
+// ---------------------------------------------------------------- free-space carving (ssm_carve_host.cpp)
+// the arguments a call may have (host function and device entry points alike); S: what the view's size and camera and the parameters become for carve_core.h
+SSM_HIDDEN int carve_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_carve_params& P, ssm_carvec::Setup* S);
+SSM_HIDDEN int carve_pose_check(ssm_ctx* c, const double* T);                  // SSM_E_INVAL for a null or non-finite pose
 
 // ---------------------------------------------------------------- bulk tracker (ssm_track_host.cpp)
 struct TrackRef {                         // a member of Tracker::refFrames: what trackRefFrame reads of it

@@ -234,6 +234,22 @@ hipError_t k_sor_level(const ssm_point* pts, int n, int nf, const float lo[3], d
 hipError_t k_sor_stats(const ssm_point* pts, int n, const SorBufs& B, hipStream_t s);
 hipError_t k_sor_compact(const ssm_point* pts, int n, double threshold, int too_few, const SorBufs& B, ssm_point* out, hipStream_t s);
 
+// free-space carving (kernels_carve.hip; the arithmetic is include/ssm/carve_core.h): one view against m clouds whose points are numbered through, `total` in all.
+// CarveSeg: one per cloud -- its points and run counters in device memory, the number of its first point, its size and the 12 doubles of its relative pose.
+// CarveBufs: seg (m), blk (the cloud of each block's first point: one per k_carve_block() points), info (m ssm_carve_info, as 8 ints), base (m + 1: where a
+// cloud's kept points start in the scratch copy), verdict / run_new / keep / tmp_run (total bytes each), block_cnt / block_off (blocks + 1), tmp_pts (total),
+// tmp: k_carve_tmp_bytes(total) for rocPRIM.  k_carve queues everything on s and waits for nothing; afterwards the clouds hold their kept points and counters
+// at the front, info[k] is complete, and verdict / run_new are every point's verdict and counter before the compaction.
+namespace ssm_carvec { struct Setup; }
+struct CarveSeg { ssm_point* pts; uint8_t* run; int32_t off, n; double M[12]; };
+struct CarveBufs {
+    const CarveSeg* seg; const int32_t* blk; int32_t* info; uint32_t* base; uint8_t *verdict, *run_new, *keep, *tmp_run; uint32_t *block_cnt, *block_off; ssm_point* tmp_pts;
+    void* tmp; size_t tmp_bytes;
+};
+int k_carve_block();
+size_t k_carve_tmp_bytes(int total);
+hipError_t k_carve(const uint16_t* depth, const ssm_carvec::Setup& S, int min_votes, int m, int total, const CarveBufs& B, hipStream_t s);
+
 // pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);
 // op 1: linearise + assemble; op 2: factor and solve the view's envelope with `lambda`
 namespace ssm_pgc { struct View; }

@@ -113,6 +113,7 @@ extern "C" int ssm_cloud_sor(ssm_ctx* c, ssm_cloud* cl, const ssm_sor_params* pa
     if (!c || !cl) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (cl->device != c->device) FAIL(c, SSM_E_INVAL, "cloud of another device");
+    if (cl->run) FAIL(c, SSM_E_INVAL, "sor: the cloud has run counters of free-space carving (filter first, carve afterwards)");
     ssm_sor_info I{};
     { const int r = sor_run(c, cl->d, cl->n, params, &I); if (r) return r; }
     if (I.n_kept < cl->n) {          // (stable: the kept points only move towards the front, but blocks run in any order, so they go through c->sor.out)

@@ -25,6 +25,10 @@
 // `exp_mapping <parameters> --sor` (or mapper_outlier_removal=1): Mapper passes every key-frame's camera-frame cloud through the statistical outlier removal
 // (include/ssm/mapper.h) when it makes it.  The summary line then carries `sor_keyframes N sor_in P sor_kept K sor_fnv H`: over the key-frames in order,
 // the points before and after the filter and FNV-1a over the kept points (position and colour; the same in both modes).  Without the flag nothing of this runs.
+// `exp_mapping <parameters> --carve` (or mapper_carve=1): Mapper applies every key-frame's depth image, as a view, to the clouds of the mapper_carve_window key-frames
+// before it (free-space carving: include/ssm/mapper.h).  The summary line then carries `carve_keyframes V carve_tested T carve_removed R carve_fnv H`:
+// the views applied, the verdicts given and the points removed over all of them, and FNV-1a over every key-frame's kept count and four verdict counts, in key-frame
+// order (the same in both modes: every key-frame is a view exactly once, whatever the viewer thread's timing).  Without the flag nothing of this runs.
 // `exp_mapping <parameters> --fuse-motion` (or motion_semantic_fuse=1; implies --moving, so it needs tracker_mode=stereo too): Mapper gates every key-frame's cloud with
 // the semantic-motion fusion of the frame's semantic image and its moving_mask (include/ssm/mapper.h) instead of the class mask alone.  The summary line
 // then carries `fused_keyframes K fused_confirmed C fused_added N fused_fnv H`: over the key-frames in order, the blobs confirmed as moving, the mask pixels they add to
@@ -128,6 +132,9 @@ int main(int argc, char** argv)
     bool sor = parameterReader.getData<int>("mapper_outlier_removal", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--sor") sor = true;
     if (sor) parameterReader.set("mapper_outlier_removal", "1");
+    bool carve = parameterReader.getData<int>("mapper_carve", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--carve") carve = true;
+    if (carve) parameterReader.set("mapper_carve", "1");
     MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
@@ -367,6 +374,19 @@ int main(int argc, char** argv)
                 for (const Mapper::PointT& p : kf->pointcloud->points) { const unsigned char* b = (const unsigned char*)&p; for (int k = 0; k < 20; k++) { if (k == 12) k = 16; h ^= b[k]; h *= 0x100000001B3ull; } }
             }
             cout << " sor_keyframes " << poseGraph.keyframes.size() << " sor_in " << n_in << " sor_kept " << n_kept << " sor_fnv " << hex << h << dec;
+        }
+        if (carve) {            // (the viewer thread made every key-frame a view before it ended)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before every key-frame was applied" << endl; return 3; }
+            uint64_t h = 0xCBF29CE484222325ull; long long tested = 0, removed = 0;
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) {
+                ssm_carve_info I{};
+                mapper.carveInfoOf(kf, &I);               // (the last key-frame's cloud has seen no view: zeros)
+                tested += (long long)I.unknown + I.occluded + I.supported + I.seen_through; removed += I.removed;
+                const int32_t v[5] = {I.n_kept, I.unknown, I.occluded, I.supported, I.seen_through};
+                const unsigned char* b = (const unsigned char*)v;
+                for (size_t k = 0; k < sizeof v; k++) { h ^= b[k]; h *= 0x100000001B3ull; }
+            }
+            cout << " carve_keyframes " << mapper.carvedViews() << " carve_tested " << tested << " carve_removed " << removed << " carve_fnv " << hex << h << dec;
         }
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;

@@ -2,7 +2,7 @@
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
 // which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_track_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_track_host.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
 // "no device" form of csrc/ssm_host.h's hooks here (the bulk tracker's among them: no tracker is ever created on the stub; its state machine runs under the sanitizers
 // in host/test_track.cpp, over hooks of that program's own).  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
 #include "ssm_hip.h"
@@ -77,7 +77,7 @@ int ssm_pnp_solve(ssm_ctx*, const float* img, const float* obj, int n, const dou
     return SSM_OK;
 }
 // device-resident Mapper entry points: a "cloud" is a host vector here, the map update the same placeholder thinning as ssm_voxel_filter below
-struct ssm_cloud { std::vector<ssm_point> p; };
+struct ssm_cloud { std::vector<ssm_point> p; std::vector<uint8_t> run; };
 static std::vector<ssm_point> g_vmap;
 int ssm_backproject_dev(ssm_ctx* c, const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, int w, int h, const ssm_camera* cam, double md, ssm_cloud** out)
 {
@@ -101,6 +101,27 @@ int ssm_cloud_sor(ssm_ctx*, ssm_cloud* cl, const ssm_sor_params* params, ssm_sor
     const int rc = ssm_sor_filter_host(cl->p.data(), (int)cl->p.size(), params, out.data(), (int)out.size(), &n, info, nullptr, nullptr);
     if (rc == SSM_OK) { out.resize((size_t)n); cl->p.swap(out); }
     return rc;
+}
+// free-space carving (Mapper with mapper_carve=1): a "view" is a host copy of the depth image, the linked host function in the device entry points' place
+struct ssm_carve_view { std::vector<uint16_t> depth; int w, h; ssm_camera cam; };
+int ssm_carve_view_create(ssm_ctx*, const uint16_t* depth, int w, int h, const ssm_camera* cam, ssm_carve_view** out)
+{ ssm_carve_view* v = new ssm_carve_view(); v->depth.assign(depth, depth + (size_t)w * h); v->w = w; v->h = h; v->cam = *cam; *out = v; return SSM_OK; }
+void ssm_carve_view_free(ssm_ctx*, ssm_carve_view* v) { delete v; }
+int ssm_carve_points(ssm_ctx*, const uint16_t* depth, int w, int h, const ssm_camera* cam, const double* Tv, const ssm_point* pts, int n, const double* Tc, uint8_t* run,
+                     const ssm_carve_params* params, ssm_point* out, int cap, int* n_out, ssm_carve_info* info)
+{ return ssm_carve_host(depth, w, h, cam, Tv, pts, n, Tc, run, params, out, cap, n_out, info, nullptr, nullptr); }
+int ssm_carve(ssm_ctx*, const ssm_carve_view* v, const double* Tv, ssm_cloud* const* clouds, const double* Tc, int m, const ssm_carve_params* params, ssm_carve_info* infos)
+{
+    for (int k = 0; k < m; k++) {
+        ssm_cloud* cl = clouds[k];
+        cl->run.resize(cl->p.size(), 0);
+        std::vector<ssm_point> out(cl->p.size() + 1); int n = 0; ssm_carve_info I;
+        const int rc = ssm_carve_host(v->depth.data(), v->w, v->h, &v->cam, Tv, cl->p.data(), (int)cl->p.size(), Tc + 16 * k, cl->run.data(), params, out.data(), (int)out.size(), &n, &I, nullptr, nullptr);
+        if (rc != SSM_OK) return rc;
+        out.resize((size_t)n); cl->p.swap(out); cl->run.resize((size_t)n);
+        if (infos) infos[k] = I;
+    }
+    return SSM_OK;
 }
 int ssm_cloud_size(const ssm_cloud* cl) { return cl ? (int)cl->p.size() : 0; }
 void ssm_cloud_free(ssm_ctx*, ssm_cloud* cl) { delete cl; }
