@@ -70,8 +70,8 @@ int check_device_flags(ssm_ctx* c, bool with_map)
             // the map is incomplete) stays set on the device until ssm_map_clear, so that ssm_map_size / ssm_map_export* / ssm_voxel_allgather keep
             // refusing the incomplete map (and every rank of an all-gather sees it); this function reports it once per fill.
             if (cnt[1] & 2) { const int32_t keep = cnt[1] & 1; hipMemcpy(c->map.counters + 1, &keep, 4, hipMemcpyHostToDevice); }
-            if ((cnt[1] & 1) && !c->map_full_reported) {
-                c->map_full_reported = true;
+            if ((cnt[1] & 1) && !c->gov.full_reported) {
+                c->gov.full_reported = true;
                 FAIL(c, SSM_E_CAPACITY, "voxel map: contributions were dropped (table and overflow list full between two growth checks): ssm_map_clear and start from a larger voxel_capacity_log2");
             }
             if (cnt[1] & 2) FAIL(c, SSM_E_VOXEL_RANGE, "points with a non-finite coordinate or a voxel index outside (-2^20, 2^20) were skipped (leaf too small for the extent, or a bad pose)");
@@ -152,9 +152,10 @@ static int ctx_init(ssm_ctx* c)
     DALLOC(c, c->d_total, 2); DALLOC(c, c->d_points, (size_t)B * W * H);
     DALLOC(c, c->d_in_img, (size_t)W * H * 3); DALLOC(c, c->d_in_sem, (size_t)W * H * 3); DALLOC(c, c->d_in_depth, (size_t)W * H); DALLOC(c, c->d_in_pose, 16);
     DALLOC(c, c->map.ovf, VOX_OVF_RECORDS); c->map.ovf_cap = VOX_OVF_RECORDS;
-    if (c->h_map_snap.alloc(c, 16)) FAIL(c, SSM_E_HIP, "hipHostMalloc of the map counter ring failed");
-    memset(c->h_map_snap, 0, 64);
-    for (int k = 0; k < 2; k++) HIPCHK(c, c->map_snap_ev[k].ensure());
+    if (c->mapdev.snap.alloc(c, 16)) FAIL(c, SSM_E_HIP, "hipHostMalloc of the map counter ring failed");
+    memset(c->mapdev.snap, 0, 64);
+    for (int k = 0; k < 2; k++) HIPCHK(c, c->mapdev.snap_ev[k].ensure());
+    c->gov.dims.skip_cap = k_map_fuse_skip_cap(); c->gov.dims.block_records = k_map_fuse_block_records(); c->gov.dims.resident_blocks = k_map_fuse_resident_blocks();
     int r = table_alloc(c, c->main.stream, c->map, cfg.voxel_capacity_log2); if (r) return r;
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     return SSM_OK;
@@ -174,13 +175,13 @@ extern "C" int ssm_create(int device, const ssm_config* cfg, ssm_ctx** out)
     { int b = cfg->stereo_batch > 0 ? cfg->stereo_batch : (cfg->max_batch > 0 ? cfg->max_batch : 1); c->stereo_B = b < 1 ? 1 : b > 128 ? 128 : b; }
     { const int v = cfg->sgbm_streams; if (v > 0) c->stereo_sgbm_streams = v > 3 ? 3 : v; }
     c->sgbm_form_cfg = cfg->sgbm_form;
-    { const char* e = getenv("SSM_MAP_STREAM"); c->map_stream = e ? atoi(e) : 1; }
+    { const char* e = getenv("SSM_MAP_STREAM"); c->mapdev.own_stream = e ? atoi(e) : 1; }
     { const char* e = getenv("SSM_MATCH_VARIANT"); c->match_mfma = !(e && atoi(e) == 0); }      // 0: the VALU matcher in the sequence path (A/B runs)
     c->B = cfg->max_batch > 0 ? cfg->max_batch : 1; c->R = cfg->tracker_ref_frames > 0 ? cfg->tracker_ref_frames : 1;
     int r = orb_plan_build(*cfg, c->plan, c->err);
     if (!r && (cfg->voxel_capacity_log2 < 8 || cfg->voxel_capacity_log2 > 28)) { c->err = "voxel_capacity_log2 must be 8..28"; r = SSM_E_INVAL; }
     if (!r && cfg->voxel_max_capacity_log2 != 0 && (cfg->voxel_max_capacity_log2 < cfg->voxel_capacity_log2 || cfg->voxel_max_capacity_log2 > 28)) { c->err = "voxel_max_capacity_log2 must be voxel_capacity_log2..28 (0: 28)"; r = SSM_E_INVAL; }
-    if (!r) c->vox_max_log2 = cfg->voxel_max_capacity_log2 ? cfg->voxel_max_capacity_log2 : 28;
+    if (!r) c->gov.vox_max_log2 = cfg->voxel_max_capacity_log2 ? cfg->voxel_max_capacity_log2 : 28;
     if (!r && !(cfg->mapper_resolution > 0)) { c->err = "mapper_resolution must be > 0"; r = SSM_E_INVAL; }
     if (!r && (cfg->sgbm_form < 0 || cfg->sgbm_form > 3 || cfg->sgbm_streams < 0 || cfg->sgbm_streams > 3 || cfg->stereo_batch < 0)) { c->err = "sgbm_form must be 0..3, sgbm_streams 0..3, stereo_batch >= 0"; r = SSM_E_INVAL; }
     if (!r && c->B > 16384) { c->err = "max_batch must be <= 16384"; r = SSM_E_INVAL; }
@@ -213,7 +214,7 @@ extern "C" int ssm_sync(ssm_ctx* c)
     c->err.clear();                                               // (after a successful ssm_sync ssm_last_error is empty, or the note of a repeated SGBM sweep)
     { int r = wait_pending(c); if (r) return r; }                 // asynchronous per-frame calls still in flight are completed (their results delivered) too
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    c->map_tail = nullptr;                                        // (every stream of the context is idle: the context stream joined them)
+    map_on_main(c);                                               // (every stream of the context is idle)
     return check_device_flags(c, true);
 }
 extern "C" int ssm_set_profiling(ssm_ctx* c, int on) { if (!c) return SSM_E_INVAL; std::lock_guard<std::mutex> lk(c->mu); c->profiling = on != 0; c->serialize = on == 2; return SSM_OK; }
@@ -717,7 +718,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     const size_t npix = (size_t)W * H;
     // fused map launches of an earlier call that nobody has looked at since (no ssm_sync / map read in between): their skipped blocks -- if any -- are run again NOW,
     // while the launch descriptors still point at that call's outputs (ensure_seq below may re-allocate the per-frame point counts)
-    if (c->map_unexamined) { const int r0 = map_settle(c, c->map_tail ? c->map_tail : c->main.stream, 0); if (r0) return r0; }
+    if (c->gov.unexamined) { const int r0 = map_settle(c, c->mapdev.tail ? c->mapdev.tail : c->main.stream, 0); if (r0) return r0; }
     int r = ensure_seq(c, n > 0 ? n : 1); if (r) return r;
     c->recs.clear(); c->pool_used = 0;
     // history rows
@@ -747,7 +748,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     if (side || two_chains) { r = ensure_side_streams(c); if (r) return r; }
     if (two_chains) { r = ensure_alt(c); if (r) return r; }
     const int nch = two_chains ? (n > 2 * c->B ? 3 : 2) : 1;
-    const bool map3 = two_chains && c->map_stream == 1;
+    const bool map3 = two_chains && c->mapdev.own_stream == 1;
     Lane* const used[3] = {&c->side[0], nch == 3 ? &c->side[2] : nullptr, map3 ? &c->side[1] : nullptr};      // the side lanes of this call, in fork / join order
     if (side || two_chains) { r = lanes_fork(c, {used[0], used[1], used[2]}); if (r) return r; }
     int bi = 0;
@@ -801,7 +802,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
                 if ((W & 15) == 0) {         // streaming fused kernels (16 pixels per thread, 16-byte loads)
                     prof_begin(c, s, "map_fuse");
                     { MapLaunch L; L.depth = in->depth + (size_t)g0 * npix; L.rgb = in->bgr + (size_t)g0 * npix * 3; L.sem = sem_q; L.pose = in->pose ? in->pose + (size_t)g0 * 16 : nullptr;
-                      L.n = nq; L.w = W; L.h = H; L.npoints = c->d_npoints + g0; L.valid = true;
+                      L.n = nq; L.w = W; L.h = H; L.npoints = c->d_npoints + g0;
                       r = map_fuse_launch(c, s, L); if (r) return r; }
                     prof_end(c, s);
                 } else {                     // odd widths: mask -> ordered back-projection -> insert
@@ -828,8 +829,8 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
         else           { r = front(); if (r) return r; r = back(); if (r) return r; }
     }
     if (side || two_chains) { r = lanes_join(c, {used[0], used[1], used[2]}); if (r) return r; }
-    // where the map's newest work sits (ssm_ctx::map_tail): one side stream, or the context stream (serialised, no map stage, or the chains' own streams in turn)
-    if (stages & SSM_STAGE_MAP) c->map_tail = map3 ? (hipStream_t)c->side[1].stream : side ? (hipStream_t)c->side[0].stream : nullptr;
+    // where the map's newest work sits (MapDev::tail): one side stream, or the context stream (serialised, no map stage, or the chains' own streams in turn)
+    if (stages & SSM_STAGE_MAP) c->mapdev.tail = map3 ? (hipStream_t)c->side[1].stream : side ? (hipStream_t)c->side[0].stream : nullptr;
     c->prev_n = n;
     if (out) {
         out->kps = c->d_kps; out->desc = desc; out->pos3d = c->d_pos3d; out->nkp = nkp; out->matches = c->d_matches; out->nmatch = c->d_nmatch;

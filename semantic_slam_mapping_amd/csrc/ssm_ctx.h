@@ -3,6 +3,7 @@
 #pragma once
 #include "ssm_internal.h"
 #include "pnp_chain.h"
+#include "ssm_map_plan.h"
 #include <rccl/rccl.h>
 #include <cmath>
 #include <cfloat>
@@ -106,9 +107,17 @@ struct VoxTable {           // tab[slots] | occ[slots] | counter block (32 bytes
     DevBuf<int32_t> skip;                            // the context map's skip list (kernels_map.hip map_stream2_kernel): blocks of the fused map stage that found the overflow list beyond its high-water mark
     size_t bytes() const { const size_t s = (size_t)1 << cap_log2; return s * sizeof(ssm_voxel) + s * 4 + 32; }
 };
-static const int VOX_OVF_RECORDS = 1 << 18;          // 29 MB per context; a context that runs the fused map stage (ssm_seq_process) trades it for the large list of map_ensure_stream_list
-// one launch of the fused map stage, kept so that blocks it skipped can be run again (ssm_map.hip map_redo)
-struct MapLaunch { const uint16_t* depth; const uint8_t* rgb; const uint8_t* sem; const double* pose; int n, w, h; int32_t* npoints; bool valid; };
+// what the context map's protocol (ssm_map_plan.h MapGov) needs on the device and of HIP
+struct SSM_HIDDEN MapDev {
+    DevBuf<int32_t> redo;                        // the block ids of a redo launch
+    PinBuf<int32_t> snap; Event snap_ev[2];      // between the map launches of ssm_seq_process the counters come back through a two-slot ring of asynchronous copies
+    std::vector<hipStream_t> launch_streams;     // streams fused launches were queued on
+    // the stream that holds the newest work on the context map when that is a side lane of ssm_seq_process (joined into the main stream by an event, so everything queued
+    // on the main stream afterwards is ordered behind it): ssm_map_size / ssm_map_export_table_dev read the map there and wait for THAT stream only -- the ORB -> match chain of
+    // the call's last sub-batch keeps running.  nullptr: the map's newest work is on the main stream.
+    hipStream_t tail = nullptr;
+    int own_stream = 1;                          // SSM_MAP_STREAM: two-chain mode runs the map stage on side[1] (0: on the chains' streams in turn)
+};
 struct StageRec { const char* name; hipEvent_t a, b; };      // a, b: events of the context's profiling pool
 // SegNet driving_webdemo: 26 conv layers; op list interleaves pools / unpools
 struct SegLayerDef { int cin, cout, h, w; };
@@ -207,7 +216,7 @@ struct ssm_ctx {
     //   side[0]  ssm_seq_process: chain 1; with a single chain, the SegNet + map stage of a sub-batch runs here beside it.  Stereo: SGBM (first workspace)
     //   side[1]  two-chain mode: the map stage on a stream of its own (SSM_MAP_STREAM=0: on the chain's stream).  Stereo: SGBM, second workspace
     //   side[2]  the third chain, used when a call has more than two sub-batches.  Stereo: SGBM, third workspace
-    Lane main, side[3]; Event forked; bool side_ready = false /* ensure_side_streams completed */; int map_stream = 1;
+    Lane main, side[3]; Event forked; bool side_ready = false /* ensure_side_streams completed */;
     ssm_config cfg{};
     OrbPlan plan;                       // what cfg fixes of the ORB front end (ssm_orb_plan.h), built by ssm_create; ctx_init uploads its tables
     const OrbGeom& g = plan.g;          // its geometry, under the name every launcher reads
@@ -240,25 +249,15 @@ struct ssm_ctx {
     DevBuf<unsigned long long> d_pnp_xchg; unsigned pnp_epoch = 0;   // ssm_pnp_solve's cluster: the exchange ring (persistent) and the launch number its pass tags start from
     bool pnp_solve_one_block = false;                        // ssm_pnp_solve: a cluster of eight blocks timed out once -> one block per solve from then on
     DevBuf<uint8_t> d_scratch2;
-    // the stream that holds the newest work on the context map when that is a side lane of ssm_seq_process (joined into the main stream by an event, so everything queued
-    // on the main stream afterwards is ordered behind it): ssm_map_size / ssm_map_export_table_dev read the map there and wait for THAT stream only -- the ORB -> match chain of
-    // the call's last sub-batch keeps running.  nullptr: the map's newest work is on the main stream.
-    hipStream_t map_tail = nullptr;
     // sequence outputs
     int seq_cap = 0, prev_n = -1;
     DevBuf<ssm_keypoint> d_kps; DevBuf<uint8_t> d_desc_all; DevBuf<int32_t> d_nkp_all; DevBuf<float> d_pos3d;
     DevBuf<ssm_dmatch> d_matches; DevBuf<int32_t> d_nmatch, d_match_pend, d_npoints; DevBuf<uint8_t> d_hist_tmp;
     DevBuf<uint8_t> d_exp_q, d_exp_t, d_knn; int capT = 0; bool match_mfma = true;   // the matcher's expanded descriptor rows (kernels_match.hip)
     // voxel tables
-    MapLaunch map_ring[8] = {}; unsigned map_ring_next = 0; DevBuf<int32_t> d_redo; std::vector<int32_t> map_skipped;    // launches that may still have skipped blocks; ids to run again (host)
-    std::vector<hipStream_t> map_launch_streams; long map_redone = 0;      // streams fused launches were queued on; blocks run again so far
-    bool map_unexamined = false;                            // a fused map launch was queued since the counters were last read on a drained stream
     MapDiv map_div{}; bool map_div_exact = false;          // cfg.camera's reciprocals and whether the fused map stage may divide by them (k_map_div, once: ctx_init)
-    VoxTable map, tmp; bool map_full_reported = false;   // table-full already reported by check_device_flags (reset by ssm_map_clear)
-    // the context map grows (map_settle); between the map launches of ssm_seq_process its counters come back through a two-slot ring of asynchronous copies
-    int vox_max_log2 = 28; PinBuf<int32_t> h_map_snap; Event map_snap_ev[2]; uint64_t map_launches = 0; int map_grown = 0;
-    double map_vpf = -1.0;                                  // voxels (+ overflow records) per fused frame, the largest rate seen on this context; < 0: none yet
-    int64_t map_frames = 0, map_snap_frames[2] = {0, 0}, map_known_total = 0, map_known_frames = 0;     // frames fused since the last clear; at the ring's snapshots; the last count the host has seen and when
+    VoxTable map, tmp;
+    MapGov gov; MapDev mapdev;                              // the context map grows (map_settle): its protocol's host state, and what that needs of the device
     // multi-GPU: the communicator of ssm_comm_init_rank (one rank per context / GPU) and the gathered counts
     ncclComm_t comm = nullptr; int comm_rank = 0, comm_size = 1; DevBuf<int32_t> d_comm_counts; int comm_counts_cap = 0;
     // SegNet
@@ -317,6 +316,7 @@ SSM_HIDDEN int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* c
 SSM_HIDDEN int map_before_launch(ssm_ctx* c, hipStream_t s, int remaining, int* nq);
 SSM_HIDDEN int map_after_launch(ssm_ctx* c, hipStream_t s, int frames, bool inputs_volatile);
 SSM_HIDDEN int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L);      // one launch of the fused map stage on the context map, recorded for a redo
+inline void map_on_main(ssm_ctx* c) { c->mapdev.tail = nullptr; }      // the context stream has joined the map's side stream: from here the map's newest work is on it
 // ssm_segnet_abi.hip
 SSM_HIDDEN int seg_init(ssm_ctx* c);
 SSM_HIDDEN int seg_forward_dev(ssm_ctx* c, Lane& lane, const uint8_t* bgr, int n, uint8_t* labels_net, uint8_t* sem_bgr, int flags);

@@ -1,5 +1,5 @@
 // ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_track_host.cpp:
-// plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units.  Those sources are compiled once and LINKED into libssm_hip.so, into the
+// plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units; ssm_orb_plan.cpp and ssm_map_plan.cpp are host-only sources with headers of their own.  Those sources are compiled once and LINKED into libssm_hip.so, into the
 // CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
 // defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
 #pragma once

@@ -3,6 +3,16 @@
 #include "ssm_ctx.h"
 #include <algorithm>
 
+// counters[3], counters[4..5] of a counter block: capacity and address of the overflow list it names (blocking: the sources are on this stack)
+static int write_list_tail(ssm_ctx* c, hipStream_t s, int32_t* counters, const VoxTable& lists)
+{
+    struct { int32_t cap, pad; ssm_voxel* buf; } tail = { lists.ovf ? lists.ovf_cap : 0, 0, lists.ovf };
+    static_assert(sizeof(tail) == 16, "counter block tail");
+    HIPCHK(c, hipMemcpyAsync(counters + 3, &tail.cap, 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(counters + 4, &tail.buf, 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    return SSM_OK;
+}
 int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2, const VoxTable* lists)
 {
     if (!lists) lists = &t;
@@ -11,130 +21,105 @@ int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2, const VoxT
     const size_t slots = (size_t)1 << cap_log2;
     t.occ = reinterpret_cast<uint32_t*>(t.tab + slots); t.counters = reinterpret_cast<int32_t*>(t.occ + slots);
     HIPCHK(c, k_voxel_clear(t.tab, -cap_log2, t.counters, s));
-    struct { int32_t cap, pad; ssm_voxel* buf; } tail = { lists->ovf ? lists->ovf_cap : 0, 0, lists->ovf };      // counters[3], counters[4..5]
-    static_assert(sizeof(tail) == 16, "counter block tail");
     int32_t head[3] = {0, 0, 0};
     HIPCHK(c, hipMemcpyAsync(t.counters, head, 12, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(t.counters + 3, &tail.cap, 4, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(t.counters + 4, &tail.buf, 8, hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipStreamSynchronize(s));                   // (the sources are on this stack)
-    return SSM_OK;
+    return write_list_tail(c, s, t.counters, *lists);
 }
 // every stream of the context that may hold work on the context map (ssm_seq_process with SSM_MAP_STREAM=0 runs the map stage of alternate sub-batches on the
 // chains' own streams): waited for before the table is replaced or skipped blocks are run again (a launch on another stream could still be
 // inserting into the old table while it is re-hashed)
 static int map_drain_other_streams(ssm_ctx* c, hipStream_t s)
 {
-    for (hipStream_t st : c->map_launch_streams) if (st && st != s) HIPCHK(c, hipStreamSynchronize(st));      // (the streams fused launches were queued on: one, normally)
+    for (hipStream_t st : c->mapdev.launch_streams) if (st && st != s) HIPCHK(c, hipStreamSynchronize(st));      // (the streams fused launches were queued on: one, normally)
     return SSM_OK;
 }
-// The fused map stage needs an overflow list that can take what every resident block may still append after the last block passed its high-water check
-// (kernels_map.hip map_stream2_kernel): 2^18 records of head room + resident blocks x records per block (1024 x 12288 records of 112 B: 1.4 GB of the device's 288).
-// The context trades its small list for it at the first fused launch; the map is at rest (list empty) when this runs.
-static int64_t map_stream_list_records()
+static int64_t map_stream_list_records(ssm_ctx* c)
 {
-    const char* e = getenv("SSM_MAP_TEST_SMALL_LIST"); const bool small = e && atoi(e) != 0;      // tests (read per launch): keep the 2^18-record list -- every block then skips itself and is run again, 21 at a time
-    return small ? (int64_t)VOX_OVF_RECORDS : (int64_t)VOX_OVF_RECORDS + (int64_t)k_map_fuse_resident_blocks() * k_map_fuse_block_records();
+    const char* e = getenv("SSM_MAP_TEST_SMALL_LIST");           // tests (read per launch)
+    return map_list_records(c->gov.dims, e && atoi(e) != 0);
 }
+// The context trades its small overflow list for the fused map stage's (ssm_map_plan.h map_list_records) at the first fused launch; the map is at rest (list
+// empty) when this runs.
 static int map_ensure_stream_list(ssm_ctx* c, hipStream_t s)
 {
     VoxTable& t = c->map;
-    if (t.skip && t.ovf_cap >= map_stream_list_records()) return SSM_OK;
+    if (t.skip && t.ovf_cap >= map_stream_list_records(c)) return SSM_OK;
     int r = map_settle(c, s, 0); if (r) return r;
-    if (!t.skip) { DALLOC(c, t.skip, (size_t)k_map_fuse_skip_cap()); DALLOC(c, c->d_redo, (size_t)k_map_fuse_skip_cap()); }
-    if (t.ovf_cap < map_stream_list_records()) {
+    if (!t.skip) { DALLOC(c, t.skip, (size_t)c->gov.dims.skip_cap); DALLOC(c, c->mapdev.redo, (size_t)c->gov.dims.skip_cap); }
+    if (t.ovf_cap < map_stream_list_records(c)) {
         DevBuf<ssm_voxel> big;
-        DALLOC(c, big, (size_t)map_stream_list_records());
-        t.ovf = std::move(big); t.ovf_cap = (int)map_stream_list_records();
-        struct { int32_t cap, pad; ssm_voxel* buf; } tail = { t.ovf_cap, 0, t.ovf };
-        HIPCHK(c, hipMemcpyAsync(t.counters + 3, &tail.cap, 4, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipMemcpyAsync(t.counters + 4, &tail.buf, 8, hipMemcpyHostToDevice, s));
-        HIPCHK(c, hipStreamSynchronize(s));
+        DALLOC(c, big, (size_t)map_stream_list_records(c));
+        t.ovf = std::move(big); t.ovf_cap = (int)map_stream_list_records(c);
+        return write_list_tail(c, s, t.counters, t);
     }
     return SSM_OK;
 }
-// One launch of the fused map stage on the context map.  Its arguments go into a ring of eight (the host looks at the counters at most a few launches late:
-// map_before_launch's snapshots, the start of the next call); the ring slot is the tag the launch's skipped blocks carry.
-int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L)
+static int map_fuse(ssm_ctx* c, hipStream_t s, const MapLaunch& L, int hw, int tag, const int32_t* redo, int nredo)
 {
     VoxTable& t = c->map;
-    int r = map_ensure_stream_list(c, s); if (r) return r;
-    const int gx = k_map_fuse_blocks_per_frame(L.w, L.h);
-    if ((int64_t)gx * L.n > k_map_fuse_skip_cap() / 4) FAIL(c, SSM_E_INVAL, "map stage: more than " + std::to_string(k_map_fuse_skip_cap() / 4) + " blocks in one launch (frames per launch x frame size)");
-    const int64_t resident = std::min<int64_t>(k_map_fuse_resident_blocks(), (int64_t)gx * L.n);
-    const int64_t hw = (int64_t)t.ovf_cap - resident * k_map_fuse_block_records();
-    const int tag = (int)(c->map_ring_next++ & 7u);
-    c->map_ring[tag] = L; c->map_ring[tag].valid = true;
-    c->map_unexamined = true;
-    if (std::find(c->map_launch_streams.begin(), c->map_launch_streams.end(), s) == c->map_launch_streams.end()) c->map_launch_streams.push_back(s);
     HIPCHK(c, k_map_fuse(L.depth, L.rgb, L.sem, L.pose, L.n, L.w, L.h, c->cfg.camera, c->map_div, c->map_div_exact, c->cfg.mapper_max_distance, (float)c->cfg.mapper_resolution,
-                         t.tab, t.cap_log2, t.counters, L.npoints, s, t.skip, (int)hw, tag, nullptr, 0));
+                         t.tab, t.cap_log2, t.counters, L.npoints, s, t.skip, hw, tag, redo, nredo));
     return SSM_OK;
 }
+// One launch of the fused map stage on the context map, its arguments kept in the protocol's ring (MapGov) for its skipped blocks.
+int map_fuse_launch(ssm_ctx* c, hipStream_t s, const MapLaunch& L)
+{
+    MapGov& g = c->gov; MapDev& d = c->mapdev;
+    int r = map_ensure_stream_list(c, s); if (r) return r;
+    const int64_t blocks = (int64_t)k_map_fuse_blocks_per_frame(L.w, L.h) * L.n;
+    if (g.launch_needs_settle()) { r = map_settle(c, s, 0); if (r) return r; }      // (the ring's invariant: not with ssm_seq_process' launches)
+    const int tag = g.begin_launch(L, blocks);
+    if (tag < 0) FAIL(c, SSM_E_INVAL, "map stage: more than " + std::to_string(g.dims.skip_cap / 4) + " blocks in one launch (frames per launch x frame size)");
+    if (std::find(d.launch_streams.begin(), d.launch_streams.end(), s) == d.launch_streams.end()) d.launch_streams.push_back(s);
+    return map_fuse(c, s, L, (int)map_high_water(g.dims, c->map.ovf_cap, blocks), tag, nullptr, 0);
+}
 // The context map has no capacity of its own (the reference's globalMap grows without limit, src/mapper.cpp:121-158): voxel_capacity_log2 is where it STARTS.
-// map_settle brings the map to rest on stream s (blocking): blocks of the fused map stage that skipped themselves are run again (in batches the overflow list can
-// take whole), the overflow list is merged into the table, and the table is re-hashed into a larger one whenever 4 x (voxels + overflow records + reserve) exceeds
-// its slots -- `reserve` = new voxels the caller is about to add at most, so that an insert / merge of a known size can never overflow.  SSM_E_CAPACITY only when
-// something cannot be placed beyond 2^vox_max_log2 slots (28: the key's range), SSM_E_NOMEM when the larger table cannot be allocated; in both cases nothing is
-// lost: table and list stay as they are.
+// map_settle brings the map to rest on stream s (blocking), one MapGov::settle_step per look at the counters: blocks of the fused map stage that skipped
+// themselves are run again (in batches the overflow list can take whole), the overflow list is merged into the table, and the table is re-hashed into a larger
+// one when the step says so.  SSM_E_CAPACITY only when something cannot be placed beyond 2^vox_max_log2 slots (28: the key's range), SSM_E_NOMEM when the larger
+// table cannot be allocated; in both cases nothing is lost: table and list stay as they are.
 int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out)       // counters_out: the table's counter block as it is when the map is at rest
 {
-    VoxTable& t = c->map;
+    VoxTable& t = c->map; MapGov& g = c->gov;
+    const int32_t z = 0;
     int lo = 0;                                                   // overflow records [0, lo) are merged already
-    for (int round = 0; round < 4096; round++) {
+    for (int round = 0; round < MapGov::SETTLE_ROUNDS; round++) {
         int32_t cnt[8];
         HIPCHK(c, hipMemcpyAsync(cnt, t.counters, 32, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
-        if (c->map_unexamined || cnt[6] > 0) {
+        if (g.needs_drained_read(cnt)) {
             // fused launches may sit on the context's other streams: their skip entries (and their table traffic) are complete only when those have drained
             { const int r = map_drain_other_streams(c, s); if (r) return r; }
             HIPCHK(c, hipMemcpyAsync(cnt, t.counters, 32, hipMemcpyDeviceToHost, s)); HIPCHK(c, hipStreamSynchronize(s));
-            c->map_unexamined = false;
+            g.read_drained();
         }
-        if (cnt[6] > 0) {                                          // blocks that skipped themselves: take their ids over, the device list starts again
-            const int ns = cnt[6] < k_map_fuse_skip_cap() ? cnt[6] : k_map_fuse_skip_cap();
-            const size_t at = c->map_skipped.size(); c->map_skipped.resize(at + (size_t)ns);
-            const int32_t z = 0;
-            HIPCHK(c, hipMemcpyAsync(c->map_skipped.data() + at, t.skip, (size_t)ns * 4, hipMemcpyDeviceToHost, s));
+        MapStep a = g.settle_step(cnt, lo, reserve, t.cap_log2, t.ovf_cap);
+        if (a.kind == MapStep::TAKE_SKIPS) {                       // the host takes the ids over, the device list starts again
+            std::vector<int32_t> ids((size_t)a.ids);
+            HIPCHK(c, hipMemcpyAsync(ids.data(), t.skip, (size_t)a.ids * 4, hipMemcpyDeviceToHost, s));
             HIPCHK(c, hipMemcpyAsync(t.counters + 6, &z, 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s));
+            g.take_skips(ids.data(), a.ids);
             cnt[6] = 0;
+            a = g.settle_step(cnt, lo, reserve, t.cap_log2, t.ovf_cap);
         }
-        const int64_t n = cnt[0], hi = cnt[2] < t.ovf_cap ? cnt[2] : t.ovf_cap, m = hi - lo;
-        const int64_t slots = (int64_t)1 << t.cap_log2;
-        const bool grow = 4 * (n + m + reserve) > slots && t.cap_log2 < c->vox_max_log2;
-        if (!grow && 2 * (n + m + reserve) > slots && (m > 0 || reserve > 0)) {
-            // at voxel_max_capacity_log2 and more than half full with something still to place.  A caller that announced its insert (reserve) is refused before
-            // anything is added; records waiting in the overflow list have no table to go to: the map is incomplete from here on (flag bit 0, reported until
-            // ssm_map_clear).  (A complete map that is merely more than half full at the cap stays readable: nothing to place, nothing refused -- ADVICE r05.)
-            if (m > 0) { const int32_t lost[2] = { cnt[1] | 1, 0 }; HIPCHK(c, hipMemcpyAsync(t.counters + 1, lost, 8, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s)); }
-            FAIL(c, SSM_E_CAPACITY, "the voxel map needs more than 2^" + std::to_string(c->vox_max_log2) + " slots (voxel_max_capacity_log2)");
-        }
-        if (m <= 0 && !grow) {
-            if (cnt[2] != 0) { const int32_t z = 0; HIPCHK(c, hipMemcpyAsync(t.counters + 2, &z, 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s)); cnt[2] = 0; }
+        switch (a.kind) {
+        case MapStep::REFUSE:
+            if (a.write_lost) { const int32_t lost[2] = { cnt[1] | 1, 0 }; HIPCHK(c, hipMemcpyAsync(t.counters + 1, lost, 8, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s)); }
+            FAIL(c, SSM_E_CAPACITY, "the voxel map needs more than 2^" + std::to_string(g.vox_max_log2) + " slots (voxel_max_capacity_log2)");
+        case MapStep::REST: case MapStep::REDO: {
+            if (a.reset_list) { HIPCHK(c, hipMemcpyAsync(t.counters + 2, &z, 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s)); cnt[2] = 0; }
             lo = 0;
-            if (!c->map_skipped.empty()) {
-                // the map is at rest and its list is empty: run the next batch of skipped blocks again -- as many as the list can take whole, all of one launch
-                // (the ids of a launch carry its ring slot).  They add to the table what they can and the rest to the list; the loop then merges, grows, goes on.
-                const int tag = (c->map_skipped.back() >> 24) & 7;
-                const MapLaunch L = c->map_ring[tag];
-                if (!L.valid) FAIL(c, SSM_E_HIP, "voxel map: skipped blocks of a launch whose arguments are no longer known");
-                const size_t room = (size_t)(t.ovf_cap / k_map_fuse_block_records());
-                std::vector<int32_t> batch;
-                for (size_t i = c->map_skipped.size(); i-- > 0 && batch.size() < room; ) if (((c->map_skipped[i] >> 24) & 7) == tag) { batch.push_back(c->map_skipped[i]); c->map_skipped.erase(c->map_skipped.begin() + (long)i); }
-                HIPCHK(c, hipMemcpyAsync(c->d_redo, batch.data(), batch.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s));
-                HIPCHK(c, k_map_fuse(L.depth, L.rgb, L.sem, L.pose, L.n, L.w, L.h, c->cfg.camera, c->map_div, c->map_div_exact, c->cfg.mapper_max_distance, (float)c->cfg.mapper_resolution,
-                                     t.tab, t.cap_log2, t.counters, L.npoints, s, t.skip, 0, tag, c->d_redo, (int)batch.size()));
-                c->map_redone += (long)batch.size();
-                continue;
-            }
-            if (counters_out) memcpy(counters_out, cnt, 16);
-            return SSM_OK;
+            if (a.kind == MapStep::REST) { if (counters_out) memcpy(counters_out, cnt, 16); return SSM_OK; }
+            std::vector<int32_t> batch; MapLaunch L; int tag;
+            if (!g.redo_batch(t.ovf_cap, batch, L, tag)) FAIL(c, SSM_E_HIP, "voxel map: skipped blocks of a launch whose arguments are no longer known");
+            HIPCHK(c, hipMemcpyAsync(c->mapdev.redo, batch.data(), batch.size() * 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s));
+            { const int r = map_fuse(c, s, L, 0, tag, c->mapdev.redo, (int)batch.size()); if (r) return r; }
+            break;
         }
-        if (grow) {
+        case MapStep::GROW: {
             { const int r = map_drain_other_streams(c, s); if (r) return r; }      // nobody may still be inserting into the table that is replaced
-            int L = t.cap_log2; while (L < c->vox_max_log2 && 4 * (n + m + reserve) > ((int64_t)1 << L)) L++;
             VoxTable nt;                                          // the larger table only: the lists stay with t
-            { const int r = table_alloc(c, s, nt, L, &t); if (r) return r; }
+            { const int r = table_alloc(c, s, nt, a.new_log2, &t); if (r) return r; }
             // the flags travel with the map; the new counter block goes on counting overflow records where the old one stopped (the records [lo, hi) are still to
             // merge, and the re-hash itself appends behind them should it need the list)
             const int32_t carry[2] = { cnt[1], cnt[2] < t.ovf_cap ? cnt[2] : t.ovf_cap };
@@ -142,92 +127,63 @@ int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out
             HIPCHK(c, k_voxel_rehash(t.tab, t.cap_log2, nt.tab, nt.cap_log2, nt.counters, s));
             HIPCHK(c, hipStreamSynchronize(s));
             t.tab = std::move(nt.tab); t.occ = nt.occ; t.counters = nt.counters; t.cap_log2 = nt.cap_log2;      // (releases the old table)
-            c->map_grown++;
-            continue;                                             // (count again: the re-hash itself may have used the list)
+            g.grown++;
+            break;                                                // (count again: the re-hash itself may have used the list)
         }
-        HIPCHK(c, k_voxel_merge(t.ovf + lo, (int)m, t.tab, t.cap_log2, t.counters, s));
-        lo = (int)hi;
-        if (lo >= t.ovf_cap) {                                    // the list was full to the brim: empty it before anything can be appended again
-            HIPCHK(c, hipStreamSynchronize(s));
-            HIPCHK(c, hipMemcpyAsync(cnt, t.counters, 16, hipMemcpyDeviceToHost, s)); HIPCHK(c, hipStreamSynchronize(s));
-            if (cnt[2] > t.ovf_cap && !(cnt[1] & 1)) FAIL(c, SSM_E_CAPACITY, "voxel map: the overflow list overflowed while it was merged");
-            const int32_t z = 0; HIPCHK(c, hipMemcpyAsync(t.counters + 2, &z, 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s));
-            lo = 0;
+        default:                                                  // MapStep::MERGE
+            HIPCHK(c, k_voxel_merge(t.ovf + a.lo, a.hi - a.lo, t.tab, t.cap_log2, t.counters, s));
+            lo = a.hi;
+            if (a.brim) {                                         // the list was full to the brim: empty it before anything can be appended again
+                HIPCHK(c, hipStreamSynchronize(s));
+                HIPCHK(c, hipMemcpyAsync(cnt, t.counters, 16, hipMemcpyDeviceToHost, s)); HIPCHK(c, hipStreamSynchronize(s));
+                if (cnt[2] > t.ovf_cap && !(cnt[1] & 1)) FAIL(c, SSM_E_CAPACITY, "voxel map: the overflow list overflowed while it was merged");
+                HIPCHK(c, hipMemcpyAsync(t.counters + 2, &z, 4, hipMemcpyHostToDevice, s)); HIPCHK(c, hipStreamSynchronize(s));
+                lo = 0;
+            }
         }
     }
     FAIL(c, SSM_E_CAPACITY, "voxel map: the overflow list did not drain");
 }
-// ssm_seq_process, in front of every launch of the map stage on stream s: decides how many of the `remaining` frames of the sub-batch the launch takes (*nq) and
-// makes room for what they are expected to add.  The expectation is the stream's own rate: voxels (+ overflow records) per frame fused since the last clear, the
-// largest value seen (map_vpf); x 1.5 is what a launch is granted.
-//   * a context that has no rate yet takes ONE frame and is settled behind it (the one wait of its lifetime): a first launch of a whole sub-batch at a leaf far below
-//     the pixel footprint would add more than table + overflow list hold, and what is dropped cannot be recovered;
-//   * a small table (< 2^20 slots) is settled exactly in front of every launch, grown for the launch's expectation, and takes at most slots / 4096 frames;
-//   * a large one is looked at through the counters of the launch BEFORE the previous one (a two-slot ring of asynchronous copies: the host never waits for the
-//     launch it has just queued) and settled -- grown for the expectation -- when it is a quarter full, when its overflow list is in use, or when the frames queued
-//     since that snapshot plus this launch are expected to fill it beyond a half.
-static void map_learn_rate(ssm_ctx* c, int64_t total, int64_t frames) { if (frames > 0 && total > 0) { const double v = (double)total / (double)frames; if (v > c->map_vpf) c->map_vpf = v; } }
 static int map_settle_exact(ssm_ctx* c, hipStream_t s, int64_t reserve)
 {
     int r = map_settle(c, s, reserve); if (r) return r;
     int32_t cnt[4];
     HIPCHK(c, hipMemcpyAsync(cnt, c->map.counters, 16, hipMemcpyDeviceToHost, s)); HIPCHK(c, hipStreamSynchronize(s));
-    map_learn_rate(c, cnt[0], c->map_frames);
-    c->map_launches = 0; c->map_known_total = cnt[0]; c->map_known_frames = c->map_frames;      // (the count just read is the newest the host knows: the estimates start from it)
+    c->gov.settled_exact(cnt[0]);
     return SSM_OK;
 }
+// ssm_seq_process, in front of every launch of the map stage on stream s: how many of the `remaining` frames of the sub-batch the launch takes (*nq), and room
+// for what they are expected to add (MapGov::before_launch: the four regimes)
 int map_before_launch(ssm_ctx* c, hipStream_t s, int remaining, int* nq)
 {
-    VoxTable& t = c->map;
-    if (c->map_vpf < 0) { *nq = 1; return map_settle(c, s, 0); }             // no rate yet (map_after_launch learns it behind this frame)
-    const double grant = c->map_vpf * 1.5;
-    if (t.cap_log2 < 20) {
-        int f = (1 << t.cap_log2) >> 12; f = f < 1 ? 1 : (f > remaining ? remaining : f);
-        *nq = f;
-        return map_settle_exact(c, s, (int64_t)(f * grant));
-    }
-    *nq = remaining;
-    if (c->map_launches < 2) {
-        // no snapshot of this run of launches yet: the table was settled when the run began (map_frames counts what has been queued since)
-        if (2.0 * ((double)c->map_known_total + (double)(c->map_frames - c->map_known_frames + remaining) * grant) > (double)((int64_t)1 << t.cap_log2))
-            return map_settle_exact(c, s, (int64_t)(remaining * grant));
-        return SSM_OK;
-    }
-    const int slot = (int)(c->map_launches & 1);
-    HIPCHK(c, hipEventSynchronize(c->map_snap_ev[slot]));
-    const int32_t* cnt = c->h_map_snap + 8 * slot;
-    const int64_t total = (int64_t)cnt[0] + cnt[2], at = c->map_snap_frames[slot];
-    map_learn_rate(c, total, at);
-    c->map_known_total = total; c->map_known_frames = at;
-    const double expect = (double)total + (double)(c->map_frames - at + remaining) * grant;
-    if (cnt[2] > 0 || cnt[6] > 0 || 4 * (int64_t)cnt[0] > ((int64_t)1 << t.cap_log2) || 2.0 * expect > (double)((int64_t)1 << t.cap_log2))      // (cnt[6]: blocks skipped themselves)
-        return map_settle_exact(c, s, (int64_t)(remaining * grant));
-    return SSM_OK;
+    const int slot = c->gov.snapshot_to_read(c->map.cap_log2);
+    if (slot >= 0) HIPCHK(c, hipEventSynchronize(c->mapdev.snap_ev[slot]));
+    const MapBefore b = c->gov.before_launch(c->map.cap_log2, remaining, slot >= 0 ? c->mapdev.snap + 8 * slot : nullptr);
+    *nq = b.nq;
+    return b.act == MapBefore::SETTLE ? map_settle(c, s, b.reserve) : b.act == MapBefore::SETTLE_EXACT ? map_settle_exact(c, s, b.reserve) : SSM_OK;
 }
 int map_after_launch(ssm_ctx* c, hipStream_t s, int frames, bool inputs_volatile)
 {
-    c->map_frames += frames;
+    MapGov& g = c->gov;
+    g.frames += frames;
     // inputs_volatile: the launch read a buffer that the next work on this stream overwrites (the labels SegNet has just generated): blocks that skipped themselves
     // must run again before that, so the map is brought to rest behind the launch (one wait per SegNet sub-batch, next to ~25 ms of SegNet)
-    if (inputs_volatile && c->map_vpf >= 0) { const int r = map_settle(c, s, 0); if (r) return r; }
-    if (c->map_vpf < 0) {                                         // the context's first frames: wait for them once and take the rate
+    if (inputs_volatile && g.vpf >= 0) { const int r = map_settle(c, s, 0); if (r) return r; }
+    if (g.vpf < 0) {                                              // the context's first frames: wait for them once and take the rate
         int r = map_settle_exact(c, s, 0); if (r) return r;
-        if (c->map_vpf < 0) c->map_vpf = 1.0;                     // (nothing was fused: every pixel gated; the next launches are granted little and watched)
         int32_t cnt[4]; HIPCHK(c, hipMemcpy(cnt, c->map.counters, 16, hipMemcpyDeviceToHost));
-        c->map_known_total = cnt[0]; c->map_known_frames = c->map_frames;
+        g.first_frames(cnt[0]);
         return SSM_OK;
     }
-    const int slot = (int)(c->map_launches & 1);
-    HIPCHK(c, hipMemcpyAsync(c->h_map_snap + 8 * slot, c->map.counters, 32, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipEventRecord(c->map_snap_ev[slot], s));
-    c->map_snap_frames[slot] = c->map_frames;
-    c->map_launches++;
+    const int slot = g.begin_snapshot();
+    HIPCHK(c, hipMemcpyAsync(c->mapdev.snap + 8 * slot, c->map.counters, 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipEventRecord(c->mapdev.snap_ev[slot], s));
     return SSM_OK;
 }
 
 // ---------------------------------------------------------------- voxel map
-// the stream the context map is read on (ssm_ctx::map_tail) -- the scratch table lives on the context stream
-static hipStream_t table_stream(ssm_ctx* c, VoxTable& t) { return (&t == &c->map && c->map_tail) ? c->map_tail : c->main.stream; }
+// the stream the context map is read on (MapDev::tail) -- the scratch table lives on the context stream
+static hipStream_t table_stream(ssm_ctx* c, VoxTable& t) { return (&t == &c->map && c->mapdev.tail) ? c->mapdev.tail : c->main.stream; }
 static int table_count(ssm_ctx* c, VoxTable& t, int* n)
 {
     int32_t cnt[4];
@@ -276,17 +232,16 @@ extern "C" int ssm_map_clear(ssm_ctx* c)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     HIPCHK(c, k_voxel_clear(c->map.tab, c->map.cap_log2, c->map.counters, c->main.stream));       // (the capacity it has grown to stays)
-    c->map_full_reported = false; c->map_launches = 0; c->map_frames = 0; c->map_known_total = 0; c->map_known_frames = 0;      // (the rate map_vpf is the stream's: kept)
-    c->map_skipped.clear(); for (MapLaunch& L : c->map_ring) L.valid = false;            // (blocks that skipped themselves belong to the map that is cleared)
+    c->gov.clear();
     return SSM_OK;
 }
 extern "C" int ssm_map_insert(ssm_ctx* c, const ssm_point* pts, int n)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     if (n < 0 || (n && !pts)) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n == 0) return SSM_OK;
     int r = ensure_scratch(c, (size_t)n * sizeof(ssm_point)); if (r) return r;
@@ -311,21 +266,21 @@ extern "C" int ssm_map_stats(ssm_ctx* c, int64_t stats[4])
 {
     if (!c || !stats) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu);
-    stats[0] = c->map.cap_log2; stats[1] = c->map_grown; stats[2] = c->map_redone; stats[3] = c->map.ovf_cap;
+    stats[0] = c->map.cap_log2; stats[1] = c->gov.grown; stats[2] = c->gov.redone; stats[3] = c->map.ovf_cap;
     return SSM_OK;
 }
 extern "C" int ssm_map_export(ssm_ctx* c, ssm_point* out, int cap, int* n_out)
 {
     if (!c || !n_out) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     return table_export_points(c, c->map, out, cap, n_out);
 }
 extern "C" int ssm_map_export_table(ssm_ctx* c, ssm_voxel* out, int cap, int* n_out)
 {
     if (!c || !n_out) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     int n; ssm_voxel* comp; uint32_t* order;
     int r = table_sorted(c, c->map, &n, &comp, &order); if (r) return r;
     *n_out = n;
@@ -341,7 +296,7 @@ extern "C" int ssm_map_merge_table(ssm_ctx* c, const ssm_voxel* tab, int n)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     if (n < 0 || (n && !tab)) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n == 0) return SSM_OK;
     int r = ensure_scratch(c, (size_t)n * sizeof(ssm_voxel)); if (r) return r;
@@ -361,7 +316,7 @@ extern "C" int ssm_map_export_table_dev(ssm_ctx* c, ssm_voxel* out, int cap, int
     if (n > cap) FAIL(c, SSM_E_CAPACITY, "table buffer too small (need " + std::to_string(n) + ")");
     if (n == 0) return SSM_OK;
     if (!out) FAIL(c, SSM_E_INVAL, "null output");
-    hipStream_t st = table_stream(c, c->map);                            // (waits for the map's stream only: ssm_ctx::map_tail)
+    hipStream_t st = table_stream(c, c->map);                            // (waits for the map's stream only: MapDev::tail)
     HIPCHK(c, k_voxel_gather_table(comp, order, n, out, st));
     HIPCHK(c, hipStreamSynchronize(st));
     return SSM_OK;
@@ -370,7 +325,7 @@ extern "C" int ssm_map_merge_table_dev(ssm_ctx* c, const ssm_voxel* tab, int n)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     if (n < 0 || (n && !tab)) FAIL(c, SSM_E_INVAL, "bad arguments");
     { const int r = map_settle(c, c->main.stream, n); if (r) return r; }
     HIPCHK(c, k_voxel_merge(tab, n, c->map.tab, c->map.cap_log2, c->map.counters, c->main.stream));
@@ -416,7 +371,7 @@ extern "C" int ssm_voxel_allgather(ssm_ctx* c, void* rccl_comm)
 {
     if (!c) return SSM_E_INVAL;
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
-    c->map_tail = nullptr;                                        // (the context stream has joined the map's side stream: from here the map's newest work is on it)
+    map_on_main(c);
     ncclComm_t comm = rccl_comm ? reinterpret_cast<ncclComm_t>(rccl_comm) : c->comm;
     if (!comm) FAIL(c, SSM_E_INVAL, "no communicator: pass a ncclComm_t or call ssm_comm_init_rank");
     int world = 0, rank = 0;

@@ -291,6 +291,58 @@ def test_context_map_grows_from_a_tiny_table(oracle):
         c.close()
 
 
+def test_context_map_growth_schedule_of_announced_inserts(oracle):
+    """the growth schedule of the deterministic path, restated from ssm_map_insert / map_settle: an insert goes in chunks of max(4096, slots / 8) points, and in front
+    of each the table is re-hashed -- once -- into the smallest 2^L with 4 x (voxels so far + chunk) <= 2^L; a merged table announces its length the same way.
+    map_stats() gives (log2 slots, growths) after every call; the voxel counts are the oracle's on the prefixes"""
+    import semantic_slam_mapping_amd as ssm
+    rng = np.random.default_rng(11)
+    pts = np.zeros(30000, ssm.POINT_DTYPE)
+    pts["x"] = rng.uniform(-4, 4, len(pts)); pts["y"] = rng.uniform(-3, 3, len(pts)); pts["z"] = rng.uniform(0, 5, len(pts))
+    pts["r"] = rng.integers(0, 256, len(pts)); pts["g"] = rng.integers(0, 256, len(pts)); pts["label"] = rng.integers(0, 12, len(pts)); pts["w"] = 1.0
+    leaf = np.float32(0.1)
+    voxels = {0: 0}
+
+    def voxels_of_prefix(k):
+        if k not in voxels:
+            voxels[k] = len(oracle.voxel_filter(pts[:k], leaf))
+        return voxels[k]
+
+    def settle(cap, grown, need):          # -> the smallest table from 2^cap on with 4 x need <= slots, and the growths counted
+        L = cap
+        while 4 * need > (1 << L):
+            L += 1
+        return L, grown + (L != cap)
+
+    def insert(cap, grown, first, n):
+        a = 0
+        while a < n:
+            chunk = min(max(4096, (1 << cap) // 8), n - a)
+            cap, grown = settle(cap, grown, voxels_of_prefix(first + a) + chunk)
+            a += chunk
+        return cap, grown
+
+    expect = [insert(8, 0, 0, 17000)]
+    expect.append(insert(*expect[0], 17000, 13000))
+    nref = voxels_of_prefix(len(pts))
+    expect.append(settle(*expect[1], 2 * nref))          # the map's own table merged into it: nref voxels + nref announced
+    assert (1 << expect[1][0]) >= 4 * nref and expect[1][1] >= 3 and expect[2][0] > expect[1][0], expect          # the restatement reaches a table that holds the map
+
+    c = ssm.Context(0, orb_features=500, max_batch=4, voxel_capacity_log2=8, camera=CAM)
+    try:
+        assert np.float32(c.cfg.mapper_resolution) == leaf and c.map_stats()[:2] == (8, 0)
+        got = []
+        c.map_insert(pts[:17000]); got.append(c.map_stats()[:2])
+        c.map_insert(pts[17000:]); got.append(c.map_stats()[:2])
+        tab = c.map_export_table()
+        assert len(tab) == nref and c.map_stats()[:2] == got[1]          # (reading the map grows nothing)
+        c.map_merge_table(tab); got.append(c.map_stats()[:2])
+        assert got == expect, (got, expect)
+        assert c.map_size() == nref
+    finally:
+        c.close()
+
+
 def test_configs1_at_leaf_002_from_a_tiny_table_equals_the_large_table_run():
     """SURVEY.md s.8(d)'s second leaf: the 1000-frame configs[1] stream at mapper_resolution 0.02 from voxel_capacity_log2 = 10 (growth by re-hashing between the map
     launches of ssm_seq_process) gives byte for byte the table of a context that starts with 2^24 slots"""
