@@ -2,7 +2,7 @@
 // key-frames into the global voxel map.  generatePointCloud (+ semantic_motion_fuse) and the pcl::VoxelGrid filter run
 // on the GPU through ssm_backproject / ssm_voxel_filter; the schedule of Mapper::viewer (src/mapper.cpp:109-162) is
 // kept: every 15th update rebuilds from every 2nd key-frame, otherwise the last <= 5 key-frames are added, then one
-// VoxelGrid pass over the whole map.  Differences, all deliberate: no PCL visualiser window; key-frames are read under
+// VoxelGrid pass over the whole map.  Differences, all deliberate: no PCL visualiser window (mapper_render=1 writes rendered views as PNG instead, see below); key-frames are read under
 // keyframes_mutex (the reference polls them unlocked, mapper.cpp:114-136); the PCD path comes from `map_output`
 // instead of a hard-coded absolute path (mapper.cpp:167).  The unsigned wrap of `i > keyframes.size()-6`
 // (mapper.cpp:134: with fewer than 6 key-frames the incremental branch adds nothing) IS reproduced unless
@@ -30,6 +30,14 @@
 // for `window` key-frames) and frame->pointcloud / ssm_carve_points with the counters kept beside the cloud (carveRun).  The two do not mix: when the device-resident
 // update fails with the switch on, the counters of the freed device clouds are gone, so the viewer stops (viewerFailed) instead of falling back to the host path.
 // Carved points leave the PUBLISHED map at the next rebuild (every 15th update): an incremental update carries the previous centroids.  The schedule is unchanged.
+// mapper_render=1 (default 0: nothing of this runs, every cloud, map and figure exactly as before): map rendering (the project's stand-in for the
+// reference's visualiser window, and the yardstick of the three switches above).  When the viewer ends -- after the last carveUpTo, before the device clouds are
+// freed -- every key-frame j is a VIEW once, in ascending j: the clouds of the key-frames i != j with |i - j| <= mapper_render_window, in their final state
+// (filtered and carved as the other switches left them; made on demand) and at the poses read at that moment, are splatted z-buffered into j's camera, and the
+// rendering is compared per pixel with j's own depth and semantic image: a leave-one-out reprojection figure (renderInfoOf).  It runs once, at the end, so it does
+// not depend on the viewer's update schedule.  Both routes give the same bytes: deviceCloud / ssm_render_clouds and frame->pointcloud / ssm_render_points (the host
+// route when mapper_device_map=0 or after the device-resident update fell back).  With mapper_render_dir set every view writes render_%06d_depth.png (16 bit),
+// _bgr.png, _label.png (palette colours) and _class.png (0 unrendered, 1 no depth, 2 in front, 3 behind, 4 agree) there, %06d the key-frame's number.
 #pragma once
 #include "common_headers.h"
 #include <atomic>
@@ -37,6 +45,7 @@
 #include "device.h"
 #include "pose_graph.h"
 #include "rgbdframe.h"
+#include "png_io.h"
 namespace rgbd_tutor {
 class Mapper {
 public:
@@ -62,6 +71,12 @@ public:
         carve_params.radius = para.getData<int>("mapper_carve_radius", carve_params.radius);
         carve_params.tol_abs = para.getData<double>("mapper_carve_tol_abs", carve_params.tol_abs);
         carve_params.tol_rel_ppm = para.getData<int>("mapper_carve_tol_rel_ppm", carve_params.tol_rel_ppm);
+        render = para.getData<int>("mapper_render", 0) != 0;
+        render_window = para.getData<int>("mapper_render_window", 5);
+        render_dir = para.getData<string>("mapper_render_dir", string(""));
+        ssm_render_params_default(&render_params);
+        render_params.point_size = para.getData<double>("mapper_render_point_size", render_params.point_size);
+        render_params.max_radius = para.getData<int>("mapper_render_max_radius", render_params.max_radius);
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
     }
@@ -136,6 +151,10 @@ public:
         if (carve) {                                    // the key-frames that came after the last update are views too: the clouds' final state does not depend on this thread's timing
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
             carveUpTo(kfs);
+        }
+        if (render) {                                   // every key-frame is a view of the clouds around it, in their final state
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            renderAll(kfs);
         }
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
@@ -273,6 +292,85 @@ public:
             carveViews++;
         }
     }
+    // map rendering: every key-frame of kfs is a view once, of the clouds of the key-frames within `render_window` of it (itself left out), compared with its own
+    // depth and semantic image.  The viewer thread calls this as it ends; once that has ended its owner may (the host route then: the device clouds went with the thread)
+    struct RenderTarget {        // the device images, of the size of the current view; freed on every way out
+        ssm_ctx* ctx = nullptr; ssm_render_target* t = nullptr; int w = 0, h = 0;
+        RenderTarget() = default; RenderTarget(const RenderTarget&) = delete; RenderTarget& operator=(const RenderTarget&) = delete;
+        ~RenderTarget() { if (t) ssm_render_target_free(ctx, t); }
+    };
+    // the rendering of view j alone: the clouds around key-frame j into the target, which is made or remade when the view has another size
+    void renderView(const vector<RGBDFrame::Ptr>& kfs, size_t j, RenderTarget& target, ssm_render_info* info = nullptr) {
+        const size_t win = (size_t)max(render_window, 0);
+        {
+            const RGBDFrame::Ptr& vf = kfs[j];
+            const int w = vf->depth.cols, h = vf->depth.rows;
+            ssm::Device& d = device(w, h);
+            ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
+            const Eigen::Isometry3d Tv = invert_pose ? vf->getTransform().inverse() : vf->getTransform();
+            if (!target.t || target.w != w || target.h != h) {
+                if (target.t) { ssm_render_target_free(target.ctx, target.t); target.t = nullptr; }
+                target.ctx = d.ctx(); target.w = w; target.h = h;
+                d.check(ssm_render_target_create(d.ctx(), w, h, &target.t), "ssm_render_target_create");
+            }
+            vector<size_t> around;
+            for (size_t i = j > win ? j - win : 0; i < kfs.size() && i <= j + win; i++) if (i != j) around.push_back(i);
+            vector<double> poses;
+            for (size_t i : around) {
+                const Eigen::Isometry3d T = invert_pose ? kfs[i]->getTransform().inverse() : kfs[i]->getTransform();
+                poses.insert(poses.end(), T.data(), T.data() + 16);
+            }
+            ssm_render_info R{};
+            if (device_map) {
+                vector<ssm_cloud*> cl;
+                for (size_t i : around) cl.push_back(deviceCloud(kfs[i]));
+                d.check(ssm_render_clouds(d.ctx(), target.t, &cam, Tv.data(), cl.data(), poses.data(), (int)cl.size(), &render_params, &R), "ssm_render_clouds");
+            } else {
+                vector<const ssm_point*> pts; vector<int32_t> n;
+                for (size_t i : around) {
+                    hostCloud(kfs[i]);
+                    pts.push_back(reinterpret_cast<const ssm_point*>(kfs[i]->pointcloud->points.data())); n.push_back((int32_t)kfs[i]->pointcloud->points.size());
+                }
+                d.check(ssm_render_points(d.ctx(), target.t, &cam, Tv.data(), pts.data(), n.data(), poses.data(), (int)pts.size(), &render_params, &R), "ssm_render_points");
+            }
+            if (info) *info = R;
+        }
+    }
+    void renderAll(const vector<RGBDFrame::Ptr>& kfs) {
+        RenderTarget target;
+        renderInfo.clear(); renderViews = 0;
+        for (size_t j = 0; j < kfs.size(); j++) {
+            renderView(kfs, j, target);
+            const RGBDFrame::Ptr& vf = kfs[j];
+            const int w = vf->depth.cols, h = vf->depth.rows;
+            ssm::Device& d = device(w, h);
+            const double scale = vf->camera.scale;
+            ssm_render_compare_info I{};
+            cv::Mat cls; if (!render_dir.empty()) cls.create(h, w, CV_8UC1);
+            d.check(ssm_render_compare(d.ctx(), target.t, vf->depth.ptr<uint16_t>(), vf->semantic.data, scale, &render_params, &I, cls.empty() ? nullptr : cls.data), "ssm_render_compare");
+            renderInfo[vf.get()] = I;
+            renderViews++;
+            if (!render_dir.empty()) {
+                cv::Mat dep, bgr, lab, col;
+                dep.create(h, w, CV_16UC1); bgr.create(h, w, CV_8UC3); lab.create(h, w, CV_8UC1); col.create(h, w, CV_8UC3);
+                d.check(ssm_render_fetch(d.ctx(), target.t, dep.ptr<uint16_t>(), bgr.data, lab.data, nullptr), "ssm_render_fetch");
+                ssm_render_label_colours(lab.data, (int64_t)w * h, col.data);
+                char stem[32]; snprintf(stem, sizeof stem, "/render_%06d", (int)j);
+                const string base = render_dir + stem;
+                if (!(ssm::imwritePNG(base + "_depth.png", dep) && ssm::imwritePNG(base + "_bgr.png", bgr) && ssm::imwritePNG(base + "_label.png", col) && ssm::imwritePNG(base + "_class.png", cls)))
+                    throw std::runtime_error("Mapper: cannot write the rendered images to " + render_dir);
+            }
+        }
+    }
+    bool rendersViews() const { return render; }
+    int renderedViews() const { return renderViews; }                        // views rendered by the last renderAll
+    // the comparison of the rendering into a key-frame's view with the frame's own images (not while the viewer thread runs); false: not rendered, or the switch is off
+    bool renderInfoOf(const RGBDFrame::Ptr& frame, ssm_render_compare_info* info) const {
+        auto it = renderInfo.find(frame.get());
+        if (it == renderInfo.end()) return false;
+        if (info) *info = it->second;
+        return true;
+    }
     bool carves() const { return carve; }
     int carvedViews() const { return carveViews; }                            // views applied so far (a first key-frame has no earlier cloud and is none)
     // what carving did to a key-frame's cloud over all the views applied to it: n_in its size before the first, n_kept its size now, the verdicts and `removed` summed
@@ -345,6 +443,8 @@ protected:
     bool carve = false; int carve_window = 5; ssm_carve_params carve_params{}; size_t carved = 0; int carveViews = 0;
     std::unordered_map<const RGBDFrame*, vector<uint8_t>> carveRun;      // host route: the run counters beside frame->pointcloud
     std::unordered_map<const RGBDFrame*, ssm_carve_info> carveInfo;      // key-frame -> what the views did to its cloud (viewer thread, or its owner once that has ended)
+    bool render = false; int render_window = 5, renderViews = 0; string render_dir; ssm_render_params render_params{};
+    std::unordered_map<const RGBDFrame*, ssm_render_compare_info> renderInfo;      // key-frame -> its view's comparison (viewer thread, or its owner once that has ended)
     std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)
     string map_output;
 };

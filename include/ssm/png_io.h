@@ -3,7 +3,7 @@
 // gray+alpha, RGB, RGBA, palette (8 bit).  `flags` follows cv::imread: 1 (default) -> 8-bit BGR, 0 -> 8-bit gray
 // (cv::cvtColor's fixed-point weights, the contract of oracle/orb.c), -1 (CV_LOAD_IMAGE_UNCHANGED) -> the file's depth and
 // channel count (16-bit samples in host byte order, colour as BGR / BGRA).  Returns an empty Mat when the file is missing or
-// not decodable, like cv::imread.  SURVEY.md s.8(f) rank 4.
+// not decodable, like cv::imread.  SURVEY.md s.8(f) rank 4.  imwritePNG (below) is the writer map rendering needs: what it writes, imreadPNG reads back exactly.
 #pragma once
 #include <zlib.h>
 #include <cstdint>
@@ -88,5 +88,45 @@ inline cv::Mat imreadPNG(const std::string& path, int flags = 1) {
         m.ptr<uint8_t>((int)y)[x] = (nch >= 3 || ctype == 3) ? (uint8_t)((c[2] * 1868 + c[1] * 9617 + c[0] * 4899 + 8192) >> 14) : (uint8_t)c[0];
     }
     return m;
+}
+// the slice of cv::imwrite map rendering needs: 8-bit gray, 8-bit BGR (written as RGB) and 16-bit gray (big-endian samples) as a non-interlaced
+// PNG -- filter 0 on every row, one IDAT chunk from zlib's compress2, CRCs from zlib's crc32.  imreadPNG(path, -1) gives the same Mat back.  false: another
+// type, an empty Mat, an image beyond the decoder's 32768 x 32768, or a file that cannot be written.
+inline bool imwritePNG(const std::string& path, const cv::Mat& m) {
+    if (m.empty() || m.cols > 32768 || m.rows > 32768) return false;
+    const int type = m.type();
+    if (type != CV_8UC1 && type != CV_8UC3 && type != CV_16UC1) return false;
+    const int depth = type == CV_16UC1 ? 16 : 8, nch = type == CV_8UC3 ? 3 : 1;
+    const size_t W = (size_t)m.cols, H = (size_t)m.rows, stride = W * nch * depth / 8;
+    std::vector<uint8_t> raw((stride + 1) * H);
+    for (size_t y = 0; y < H; y++) {
+        uint8_t* dst = &raw[(stride + 1) * y];
+        *dst++ = 0;                                                      // filter type 0: none
+        if (type == CV_8UC1) memcpy(dst, m.ptr<uint8_t>((int)y), W);
+        else if (type == CV_8UC3) { const uint8_t* s = m.ptr<uint8_t>((int)y); for (size_t x = 0; x < W; x++) { dst[3 * x] = s[3 * x + 2]; dst[3 * x + 1] = s[3 * x + 1]; dst[3 * x + 2] = s[3 * x]; } }
+        else { const uint16_t* s = m.ptr<uint16_t>((int)y); for (size_t x = 0; x < W; x++) { dst[2 * x] = (uint8_t)(s[x] >> 8); dst[2 * x + 1] = (uint8_t)(s[x] & 255); } }
+    }
+    uLongf zlen = compressBound((uLong)raw.size());
+    std::vector<uint8_t> z(zlen);
+    if (compress2(z.data(), &zlen, raw.data(), (uLong)raw.size(), 6) != Z_OK) return false;
+    std::vector<uint8_t> file = {0x89, 'P', 'N', 'G', 0x0D, 0x0A, 0x1A, 0x0A};
+    auto put32 = [&](uint32_t v) { for (int s = 24; s >= 0; s -= 8) file.push_back((uint8_t)(v >> s)); };
+    auto chunk = [&](const char* name, const uint8_t* d, size_t len) {
+        put32((uint32_t)len);
+        const size_t at = file.size();
+        file.insert(file.end(), name, name + 4);
+        if (len) file.insert(file.end(), d, d + len);
+        put32((uint32_t)crc32(crc32(0L, Z_NULL, 0), &file[at], (uInt)(len + 4)));
+    };
+    uint8_t ihdr[13] = {0};
+    for (int k = 0; k < 4; k++) { ihdr[k] = (uint8_t)((uint32_t)W >> (24 - 8 * k)); ihdr[4 + k] = (uint8_t)((uint32_t)H >> (24 - 8 * k)); }
+    ihdr[8] = (uint8_t)depth; ihdr[9] = nch == 3 ? 2 : 0;                  // colour type: RGB or gray; compression, filter method and interlace stay 0
+    chunk("IHDR", ihdr, 13);
+    chunk("IDAT", z.data(), (size_t)zlen);
+    chunk("IEND", nullptr, 0);
+    FILE* fp = fopen(path.c_str(), "wb");
+    if (!fp) return false;
+    const bool ok = fwrite(file.data(), 1, file.size(), fp) == file.size();
+    return fclose(fp) == 0 && ok;
 }
 }  // namespace ssm

@@ -535,6 +535,49 @@ int  ssm_debug_carve_record(ssm_ctx* ctx, int k, uint8_t* verdict, uint8_t* run,
 /* the counters of a device-resident cloud (all zero before its first ssm_carve): cap >= ssm_cloud_size entries */
 int  ssm_cloud_run_fetch(ssm_ctx* ctx, const ssm_cloud* cloud, uint8_t* run, int cap);
 
+/* ---- map rendering: the points of m posed clouds are splatted, z-buffered, into a pinhole view (w x h, a camera, T_view), and the rendering is compared per
+ * pixel with a key-frame's own depth and semantic image.  The reference has no such step; DESIGN.md s.17 is the contract, include/ssm/render_core.h the
+ * arithmetic shared by the device path and the host functions.  A point is carried into the view's frame by T_rel = inverse(T_view) . T_cloud, projected to the
+ * nearest pixel, its depth quantised to depth units (1..65535, else invisible); it covers the (2 s + 1)^2 pixels around its centre that lie inside the image,
+ * s = min(max_radius, floor(0.5 fx point_size / z)) (point_size 0: one pixel).  Every pixel keeps the smallest key (depth << 32 | index of the point in the
+ * concatenation of the clouds): the nearest point, at equal depth the lowest index, whatever the order of processing.  Per pixel: depth (0 = empty), the winner's
+ * b g r (0), the low byte of its label (255) and its index (-1).
+ * The comparison classifies each pixel: 0 unrendered, 1 the frame has no depth, 2 the map in front of the measured surface, 3 behind it, 4 agree (within
+ * tol = llrint(tol_abs scale) + d tol_rel_ppm / 10^6, carving's tolerance); the agreeing pixels by label: equal and known, both known and different, else unknown.
+ * SSM_E_INVAL: max_radius outside 0..8; point_size, z_min, z_max or tol_abs negative or non-finite (z_max: 1e9 is "no limit"); tolerance and camera limits as
+ * carving's; a non-finite pose; w or h < 1 or w h > 2^26; m < 0; 2^32 points or more in all. */
+typedef struct { double point_size; int32_t max_radius; int32_t pad; double z_min, z_max; double tol_abs; int32_t tol_rel_ppm; int32_t pad2; } ssm_render_params;
+typedef struct { int32_t n_in, n_visible, n_covered, pad; } ssm_render_info;      /* points given, points with a non-empty footprint, non-empty pixels */
+typedef struct { int64_t unrendered, no_depth, in_front, behind, agree, label_agree, label_disagree, label_unknown, n_pixels; } ssm_render_compare_info;
+typedef struct ssm_render_target ssm_render_target;
+void ssm_render_params_default(ssm_render_params* p);                    /* 0 m, 3 px, 0.1 m, 1e9 m, 0.05 m, 20000 ppm */
+/* the device z-buffer and the four output images of a w x h view, reused across calls */
+int  ssm_render_target_create(ssm_ctx* ctx, int w, int h, ssm_render_target** target_out);
+void ssm_render_target_free(ssm_ctx* ctx, ssm_render_target* target);
+/* host arrays through the device: pts[k] holds n[k] points of cloud k, T_clouds m poses of 16 doubles.  info may be NULL */
+int  ssm_render_points(ssm_ctx* ctx, ssm_render_target* target, const ssm_camera* cam, const double* T_view, const ssm_point* const* pts, const int32_t* n,
+                       const double* T_clouds, int m, const ssm_render_params* params, ssm_render_info* info);
+/* device-resident clouds: nothing is uploaded but the poses.  A cloud of size 0 is legal */
+int  ssm_render_clouds(ssm_ctx* ctx, ssm_render_target* target, const ssm_camera* cam, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
+                       const ssm_render_params* params, ssm_render_info* info);
+/* the map the last ssm_viewer_map_update left on the device, at the identity pose; SSM_E_INVAL when there is none (no update yet, an empty map, or released) */
+int  ssm_render_viewer_map(ssm_ctx* ctx, ssm_render_target* target, const ssm_camera* cam, const double* T_view, const ssm_render_params* params, ssm_render_info* info);
+/* the images of the target's last rendering: depth w h uint16, bgr w h 3 bytes, label w h bytes, index w h int32; each may be NULL */
+int  ssm_render_fetch(ssm_ctx* ctx, const ssm_render_target* target, uint16_t* depth, uint8_t* bgr, uint8_t* label, int32_t* index);
+/* the target's last rendering against a frame (host images of the target's size; cam_scale: depth units per metre of both): uploads the frame and compares on the
+ * device.  class_img (w h bytes) may be NULL */
+int  ssm_render_compare(ssm_ctx* ctx, ssm_render_target* target, const uint16_t* depth_host, const uint8_t* sem_bgr_host, double cam_scale,
+                        const ssm_render_params* params, ssm_render_compare_info* info, uint8_t* class_img);
+/* the same on the CPU, the same bits; need no GPU.  Every output pointer may be NULL; keys: the raw z-buffer, w h entries (all ones = empty) */
+int  ssm_render_host(int w, int h, const ssm_camera* cam, const double* T_view, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m,
+                     const ssm_render_params* params, uint16_t* depth, uint8_t* bgr, uint8_t* label, int32_t* index, uint64_t* keys, ssm_render_info* info);
+int  ssm_render_compare_host(const uint16_t* rendered_depth, const uint8_t* rendered_label, int w, int h, const uint16_t* depth, const uint8_t* sem_bgr, double cam_scale,
+                             const ssm_render_params* params, ssm_render_compare_info* info, uint8_t* class_img);
+/* label image -> BGR through the 12-class palette (255 and any other value: black); n pixels, out 3 n bytes */
+void ssm_render_label_colours(const uint8_t* label, int64_t n, uint8_t* bgr_out);
+/* the raw z-buffer after the target's last rendering (w h entries), for the tests */
+int  ssm_debug_render_keys(ssm_ctx* ctx, const ssm_render_target* target, uint64_t* keys);
+
 /* ---- PoseGraph's optimiser (reference src/pose_graph.cpp:82-305, include/pose_graph.h:53-62): a graph of SE3 vertices and SE3 edges with Huber kernels,
  * Levenberg (g2o's OptimizationAlgorithmLevenberg) over a direct block-envelope L D L^T.  DESIGN.md s.12 is the contract; include/ssm/pgo_core.h holds the
  * arithmetic, ONE function template that the host function runs with one thread and the device path with one 1024-thread block per graph, so device ==

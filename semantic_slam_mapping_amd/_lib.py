@@ -96,6 +96,19 @@ class CarveInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_in", "n_kept", "unknown", "occluded", "supported", "seen_through", "removed", "pad")]
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("point_size", C.c_double), ("max_radius", C.c_int32), ("pad", C.c_int32), ("z_min", C.c_double), ("z_max", C.c_double), ("tol_abs", C.c_double),
+                ("tol_rel_ppm", C.c_int32), ("pad2", C.c_int32)]
+
+
+class RenderInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_in", "n_visible", "n_covered", "pad")]
+
+
+class RenderCompareInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("unrendered", "no_depth", "in_front", "behind", "agree", "label_agree", "label_disagree", "label_unknown", "n_pixels")]
+
+
 class VocabTrainParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iters", C.c_int32)]
 
@@ -224,6 +237,18 @@ SYMBOLS = {
     "ssm_carve_host": (_I, [_P, _I, _I, C.POINTER(Camera), _P, _P, _I, _P, _P, C.POINTER(CarveParams), _P, _I, C.POINTER(_I), C.POINTER(CarveInfo), _P, _P]),
     "ssm_debug_carve_record": (_I, [_P, _I, _P, _P, _I]),
     "ssm_cloud_run_fetch": (_I, [_P, _P, _P, _I]),
+    "ssm_render_params_default": (None, [C.POINTER(RenderParams)]),
+    "ssm_render_target_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "ssm_render_target_free": (None, [_P, _P]),
+    "ssm_render_points": (_I, [_P, _P, C.POINTER(Camera), _P, _P, _P, _P, _I, C.POINTER(RenderParams), C.POINTER(RenderInfo)]),
+    "ssm_render_clouds": (_I, [_P, _P, C.POINTER(Camera), _P, _P, _P, _I, C.POINTER(RenderParams), C.POINTER(RenderInfo)]),
+    "ssm_render_viewer_map": (_I, [_P, _P, C.POINTER(Camera), _P, C.POINTER(RenderParams), C.POINTER(RenderInfo)]),
+    "ssm_render_fetch": (_I, [_P, _P, _P, _P, _P, _P]),
+    "ssm_render_compare": (_I, [_P, _P, _P, _P, C.c_double, C.POINTER(RenderParams), C.POINTER(RenderCompareInfo), _P]),
+    "ssm_render_host": (_I, [_I, _I, C.POINTER(Camera), _P, _P, _P, _P, _I, C.POINTER(RenderParams), _P, _P, _P, _P, _P, C.POINTER(RenderInfo)]),
+    "ssm_render_compare_host": (_I, [_P, _P, _I, _I, _P, _P, C.c_double, C.POINTER(RenderParams), C.POINTER(RenderCompareInfo), _P]),
+    "ssm_render_label_colours": (None, [_P, C.c_int64, _P]),
+    "ssm_debug_render_keys": (_I, [_P, _P, _P]),
     "ssm_pgo_create": (_I, [_P, C.POINTER(_P)]),
     "ssm_pgo_destroy": (None, [_P]),
     "ssm_pgo_clear": (_I, [_P]),

@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -194,6 +194,86 @@ def _cm16(T):
     if T.shape != (4, 4):
         raise ValueError("a pose is a 4 x 4 matrix")
     return np.ascontiguousarray(T.T).reshape(16)
+
+
+RENDER_INFO_FIELDS = ("n_in", "n_visible", "n_covered")
+RENDER_COMPARE_FIELDS = ("unrendered", "no_depth", "in_front", "behind", "agree", "label_agree", "label_disagree", "label_unknown", "n_pixels")
+RENDER_DEFAULTS = dict(point_size=0.0, max_radius=3, z_min=0.1, z_max=1.0e9, tol_abs=0.05, tol_rel_ppm=20000)
+
+
+def _render_params(kw):
+    bad = set(kw) - set(RENDER_DEFAULTS)
+    if bad:
+        raise TypeError("unknown rendering parameters: " + ", ".join(sorted(bad)))
+    p = dict(RENDER_DEFAULTS, **kw)
+    return RenderParams(float(p["point_size"]), int(p["max_radius"]), 0, float(p["z_min"]), float(p["z_max"]), float(p["tol_abs"]), int(p["tol_rel_ppm"]), 0)
+
+
+def _render_clouds_args(clouds, T_clouds):
+    """host clouds -> (the arrays kept alive, pointer array, sizes, poses, m)"""
+    clouds = [_sor_points(c) for c in clouds]
+    m = len(clouds)
+    if len(T_clouds) != m:
+        raise ValueError("one pose per cloud")
+    ptrs = (C.c_void_p * max(m, 1))(*[c.ctypes.data for c in clouds])
+    n = np.ascontiguousarray([len(c) for c in clouds] + ([] if m else [0]), np.int32)
+    Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+    return clouds, ptrs, n, Tc, m
+
+
+def _render_images(w, h, keys):
+    out = {"depth": np.zeros((h, w), np.uint16), "bgr": np.zeros((h, w, 3), np.uint8), "label": np.zeros((h, w), np.uint8), "index": np.zeros((h, w), np.int32)}
+    if keys:
+        out["keys"] = np.zeros((h, w), np.uint64)
+    return out
+
+
+def render_host(w, h, camera, T_view, clouds, T_clouds, keys=False, **params):
+    """map rendering on the CPU (ssm_render_host, no GPU): the points of `clouds` (host arrays of POINT_DTYPE at the poses T_clouds) into the w x h view (camera =
+    (cx, cy, fx, fy, scale), T_view) -> {depth, bgr, label, index, info}, with keys=True also the raw z-buffer"""
+    keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+    P = _render_params(params); I = RenderInfo(); cam = Camera(*camera)
+    out = _render_images(int(w), int(h), keys) if w >= 1 and h >= 1 and w * h <= 1 << 26 else _render_images(1, 1, keys)
+    lib = _lib.load()
+    rc = lib.ssm_render_host(int(w), int(h), C.byref(cam), _ptr(_cm16(T_view)), ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), _ptr(out["depth"]), _ptr(out["bgr"]), _ptr(out["label"]),
+                             _ptr(out["index"]), _ptr(out.get("keys")), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    out["info"] = {k: getattr(I, k) for k in RENDER_INFO_FIELDS}
+    return out
+
+
+def _compare_frame(shape, depth, sem):
+    depth = np.ascontiguousarray(depth, np.uint16); sem = np.ascontiguousarray(sem, np.uint8)
+    if depth.shape != shape or sem.shape != shape + (3,):
+        raise ValueError("the frame's images must have the rendering's size")
+    return depth, sem
+
+
+def render_compare_host(rendered_depth, rendered_label, depth, sem, scale, class_image=False, **params):
+    """the rendering (its depth and label images) against a frame's depth and semantic BGR image on the CPU (ssm_render_compare_host) -> the nine counts, or with
+    class_image (counts, the class image)"""
+    rd = np.ascontiguousarray(rendered_depth, np.uint16); rl = np.ascontiguousarray(rendered_label, np.uint8)
+    h, w = rd.shape
+    if rl.shape != (h, w):
+        raise ValueError("depth and label of one rendering")
+    depth, sem = _compare_frame((h, w), depth, sem)
+    P = _render_params(params); I = RenderCompareInfo()
+    cls = np.zeros((h, w), np.uint8) if class_image else None
+    lib = _lib.load()
+    rc = lib.ssm_render_compare_host(_ptr(rd), _ptr(rl), w, h, _ptr(depth), _ptr(sem), float(scale), C.byref(P), C.byref(I), _ptr(cls))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    info = {k: getattr(I, k) for k in RENDER_COMPARE_FIELDS}
+    return (info, cls) if class_image else info
+
+
+def label_colours(label):
+    """a label image -> its BGR image through the project's 12-class palette (255 and anything else: black)"""
+    label = np.ascontiguousarray(label, np.uint8)
+    out = np.zeros(label.shape + (3,), np.uint8)
+    _lib.load().ssm_render_label_colours(_ptr(label), label.size, _ptr(out))
+    return out
 
 
 def _carve_run(run, n):
@@ -1006,6 +1086,62 @@ class Context:
         self._chk(self.lib.ssm_carve_points(self.h, _ptr(depth), w, h, C.byref(cam), _ptr(Tv), _ptr(points), n, _ptr(Tc), _ptr(run), C.byref(P), _ptr(out), n, C.byref(got), C.byref(I)))
         res = (out[:got.value], run[:got.value], _carve_info(I))
         return res + (self._carve_record(0, n),) if record else res
+
+    def render_target(self, w, h):
+        """the device z-buffer and images of a w x h view, reused across renderings (ssm_render_target_create) -> an opaque handle (render_target_free it)"""
+        t = C.c_void_p()
+        self._chk(self.lib.ssm_render_target_create(self.h, int(w), int(h), C.byref(t)))
+        self._render_sizes = getattr(self, "_render_sizes", {})
+        self._render_sizes[t.value] = (int(w), int(h))
+        return t.value
+
+    def render_target_free(self, target):
+        self._render_sizes.pop(target, None)
+        self.lib.ssm_render_target_free(self.h, target)
+
+    def _render_result(self, target, I, keys):
+        w, h = self._render_sizes[target]
+        out = _render_images(w, h, keys)
+        self._chk(self.lib.ssm_render_fetch(self.h, target, _ptr(out["depth"]), _ptr(out["bgr"]), _ptr(out["label"]), _ptr(out["index"])))
+        if keys:
+            self._chk(self.lib.ssm_debug_render_keys(self.h, target, _ptr(out["keys"])))
+        out["info"] = {k: getattr(I, k) for k in RENDER_INFO_FIELDS}
+        return out
+
+    def render_points(self, target, camera, T_view, clouds, T_clouds, keys=False, **params):
+        """render_host's call through the device (ssm_render_points) -> {depth, bgr, label, index, info}, with keys=True also the raw z-buffer"""
+        keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+        P = _render_params(params); I = RenderInfo(); cam = Camera(*camera) if camera is not None else self.cfg.camera
+        self._chk(self.lib.ssm_render_points(self.h, target, C.byref(cam), _ptr(_cm16(T_view)), ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), C.byref(I)))
+        return self._render_result(target, I, keys)
+
+    def render_clouds(self, target, camera, T_view, clouds, T_clouds, keys=False, **params):
+        """device-resident clouds (backproject_dev's handles) at the poses T_clouds into the view (ssm_render_clouds); nothing is uploaded but the poses"""
+        m = len(clouds)
+        if len(T_clouds) != m:
+            raise ValueError("one pose per cloud")
+        arr = (C.c_void_p * max(m, 1))(*clouds)
+        Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+        P = _render_params(params); I = RenderInfo(); cam = Camera(*camera) if camera is not None else self.cfg.camera
+        self._chk(self.lib.ssm_render_clouds(self.h, target, C.byref(cam), _ptr(_cm16(T_view)), arr, _ptr(Tc), m, C.byref(P), C.byref(I)))
+        return self._render_result(target, I, keys)
+
+    def render_viewer_map(self, target, camera, T_view, keys=False, **params):
+        """the map the last viewer_map_update left on the device, at the identity pose (ssm_render_viewer_map)"""
+        P = _render_params(params); I = RenderInfo(); cam = Camera(*camera) if camera is not None else self.cfg.camera
+        self._chk(self.lib.ssm_render_viewer_map(self.h, target, C.byref(cam), _ptr(_cm16(T_view)), C.byref(P), C.byref(I)))
+        return self._render_result(target, I, keys)
+
+    def render_compare(self, target, depth, sem, scale=None, class_image=False, **params):
+        """the target's last rendering against a frame's depth and semantic BGR image, on the device (ssm_render_compare) -> the nine counts, or with class_image
+        (counts, the class image)"""
+        w, h = self._render_sizes[target]
+        depth, sem = _compare_frame((h, w), depth, sem)
+        P = _render_params(params); I = RenderCompareInfo()
+        cls = np.zeros((h, w), np.uint8) if class_image else None
+        self._chk(self.lib.ssm_render_compare(self.h, target, _ptr(depth), _ptr(sem), float(self.cfg.camera.scale if scale is None else scale), C.byref(P), C.byref(I), _ptr(cls)))
+        info = {k: getattr(I, k) for k in RENDER_COMPARE_FIELDS}
+        return (info, cls) if class_image else info
 
     def backproject_fused(self, depth, rgb, sem, motion=None, T=None, camera=None, max_distance=None, area_thres=1000, overlay_thres=0.143, device=False):
         """generate_point_cloud with the fused mask (ssm_backproject_fused); device=True: backproject_dev's form, -> an opaque cloud handle (cloud_free it)"""

@@ -187,6 +187,20 @@ struct MfWork {
 struct ssm_cloud { ssm_point* d = nullptr; int n = 0; int device = 0; int slab = -1; DevBuf<uint8_t> run; };
 // a view of free-space carving: a key-frame's depth image in device memory and its camera
 struct ssm_carve_view { DevBuf<uint16_t> depth; int w = 0, h = 0, device = 0; ssm_camera cam{}; };
+// a render target (ssm_render.hip): the z-buffer and the four images of a w x h view, and the staging of a frame to compare with; rendered: a rendering is in it
+struct ssm_render_target {
+    int w = 0, h = 0, device = 0; bool rendered = false;
+    DevBuf<unsigned long long> keys; DevBuf<uint16_t> depth; DevBuf<uint8_t> bgr, label; DevBuf<int32_t> index;
+    DevBuf<uint16_t> f_depth; DevBuf<uint8_t> f_sem, cls;
+};
+// workspace of map rendering for cap_m clouds and cap_b blocks of points: the table (RenderSeg[m], then the blocks' first clouds), the info, the comparison's
+// counts and the host-array call's staging
+struct RenderWork {
+    size_t cap_m = 0, cap_b = 0, in_cap = 0;
+    DevBuf<uint8_t> table; PinBuf<uint8_t> h_table;
+    DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<unsigned long long> counts; PinBuf<unsigned long long> h_counts;
+    DevBuf<ssm_point> in;
+};
 // workspace of free-space carving (ssm_carve.hip) for cap points in cap_m clouds; off: the last call's clouds as numbers of their first points (m + 1 entries), for
 // ssm_debug_carve_record
 struct CarveWork {
@@ -268,6 +282,7 @@ struct ssm_ctx {
     MfWork mf;                                               // semantic-motion fusion: allocated by its first call
     SorWork sor;                                             // statistical outlier removal: allocated by its first call, grown by the largest
     CarveWork carve;                                         // free-space carving: likewise
+    RenderWork render;                                       // map rendering: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;

@@ -1,4 +1,4 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_track_host.cpp:
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_track_host.cpp:
 // plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units; ssm_orb_plan.cpp and ssm_map_plan.cpp are host-only sources with headers of their own.  Those sources are compiled once and LINKED into libssm_hip.so, into the
 // CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
 // defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
@@ -10,6 +10,7 @@
 #include "../../include/ssm/motion_fuse_core.h"
 #include "../../include/ssm/sor_core.h"
 #include "../../include/ssm/carve_core.h"
+#include "../../include/ssm/render_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
 #include <algorithm>
@@ -96,6 +97,13 @@ SSM_HIDDEN int sor_off_grid(ssm_ctx* c);                                       /
 // the arguments a call may have (host function and device entry points alike); S: what the view's size and camera and the parameters become for carve_core.h
 SSM_HIDDEN int carve_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_carve_params& P, ssm_carvec::Setup* S);
 SSM_HIDDEN int carve_pose_check(ssm_ctx* c, const double* T);                  // SSM_E_INVAL for a null or non-finite pose
+
+// ---------------------------------------------------------------- map rendering (ssm_render_host.cpp)
+// the arguments a call may have (host functions and device entry points alike); S: what the view's size and camera and the parameters become for render_core.h
+SSM_HIDDEN int render_size_check(ssm_ctx* c, int w, int h);
+SSM_HIDDEN int render_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_render_params& P, ssm_renderc::Setup* S);
+SSM_HIDDEN int render_compare_check(ssm_ctx* c, const ssm_render_params& P, double scale, int64_t* tol_abs);      // tol_abs: in depth units
+SSM_HIDDEN int render_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total);                              // SSM_E_INVAL for a negative count or 2^32 points and more
 
 // ---------------------------------------------------------------- bulk tracker (ssm_track_host.cpp)
 struct TrackRef {                         // a member of Tracker::refFrames: what trackRefFrame reads of it

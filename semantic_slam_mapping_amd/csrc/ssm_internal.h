@@ -250,6 +250,18 @@ int k_carve_block();
 size_t k_carve_tmp_bytes(int total);
 hipError_t k_carve(const uint16_t* depth, const ssm_carvec::Setup& S, int min_votes, int m, int total, const CarveBufs& B, hipStream_t s);
 
+// map rendering (kernels_render.hip; the arithmetic is include/ssm/render_core.h): m clouds whose points are numbered through, `total` in all (below 2^32), into a
+// w x h z-buffer of 64-bit keys.  RenderSeg: one per cloud -- its points in device memory, the number of its first point, its size and the 12 doubles of its
+// relative pose.  blk: the cloud of each block's first point (one per k_render_block() points).  info: 4 ints (ssm_render_info).  k_render queues the clear, the
+// splat and the resolve on s and waits for nothing; k_render_compare the comparison (counts: 9 x int64 as ssm_render_compare_info, cleared by the call).
+namespace ssm_renderc { struct Setup; }
+struct RenderSeg { const ssm_point* pts; int64_t off; int32_t n, pad; double M[12]; };
+struct RenderImgs { unsigned long long* keys; uint16_t* depth; uint8_t* bgr; uint8_t* label; int32_t* index; };
+int k_render_block();
+hipError_t k_render(const ssm_renderc::Setup& S, const RenderSeg* seg, const int32_t* blk, int m, int64_t total, const RenderImgs& T, int32_t* info, hipStream_t s);
+hipError_t k_render_compare(const uint16_t* rdepth, const uint8_t* rlabel, const uint16_t* depth, const uint8_t* sem, int64_t np, int64_t tol_abs, int64_t ppm,
+                            uint8_t* cls, unsigned long long* counts, hipStream_t s);
+
 // pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);
 // op 1: linearise + assemble; op 2: factor and solve the view's envelope with `lambda`
 namespace ssm_pgc { struct View; }

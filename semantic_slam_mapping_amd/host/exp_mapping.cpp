@@ -29,6 +29,11 @@
 // before it (free-space carving: include/ssm/mapper.h).  The summary line then carries `carve_keyframes V carve_tested T carve_removed R carve_fnv H`:
 // the views applied, the verdicts given and the points removed over all of them, and FNV-1a over every key-frame's kept count and four verdict counts, in key-frame
 // order (the same in both modes: every key-frame is a view exactly once, whatever the viewer thread's timing).  Without the flag nothing of this runs.
+// `exp_mapping <parameters> --render [DIR]` (or mapper_render=1, mapper_render_dir=DIR): when the viewer ends, Mapper renders into every key-frame's view the clouds of
+// the key-frames around it and compares the rendering with the frame's own depth and semantic image (map rendering: include/ssm/mapper.h); with DIR the
+// rendered images are written there as PNG.  The summary line then carries `render_views V render_agree A render_in_front F render_behind B render_label_agree L
+// render_label_disagree D render_fnv H`: the views, the sums of those counts over them, and FNV-1a over every view's nine counts in key-frame order (the same in both
+// modes: it runs once, at the end).  Without the flag nothing of this runs and the line is as before.
 // `exp_mapping <parameters> --fuse-motion` (or motion_semantic_fuse=1; implies --moving, so it needs tracker_mode=stereo too): Mapper gates every key-frame's cloud with
 // the semantic-motion fusion of the frame's semantic image and its moving_mask (include/ssm/mapper.h) instead of the class mask alone.  The summary line
 // then carries `fused_keyframes K fused_confirmed C fused_added N fused_fnv H`: over the key-frames in order, the blobs confirmed as moving, the mask pixels they add to
@@ -135,6 +140,12 @@ int main(int argc, char** argv)
     bool carve = parameterReader.getData<int>("mapper_carve", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--carve") carve = true;
     if (carve) parameterReader.set("mapper_carve", "1");
+    bool render = parameterReader.getData<int>("mapper_render", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--render") {
+        render = true;
+        if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_render_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
+    }
+    if (render) parameterReader.set("mapper_render", "1");
     MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
@@ -387,6 +398,19 @@ int main(int argc, char** argv)
                 for (size_t k = 0; k < sizeof v; k++) { h ^= b[k]; h *= 0x100000001B3ull; }
             }
             cout << " carve_keyframes " << mapper.carvedViews() << " carve_tested " << tested << " carve_removed " << removed << " carve_fnv " << hex << h << dec;
+        }
+        if (render) {           // (the viewer thread rendered every key-frame's view as it ended)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before every view was rendered" << endl; return 3; }
+            uint64_t h = 0xCBF29CE484222325ull; long long agree = 0, in_front = 0, behind = 0, lab_agree = 0, lab_dis = 0;
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) {
+                ssm_render_compare_info I{};
+                mapper.renderInfoOf(kf, &I);
+                agree += I.agree; in_front += I.in_front; behind += I.behind; lab_agree += I.label_agree; lab_dis += I.label_disagree;
+                const unsigned char* b = (const unsigned char*)&I;
+                for (size_t k = 0; k < sizeof I; k++) { h ^= b[k]; h *= 0x100000001B3ull; }
+            }
+            cout << " render_views " << mapper.renderedViews() << " render_agree " << agree << " render_in_front " << in_front << " render_behind " << behind
+                 << " render_label_agree " << lab_agree << " render_label_disagree " << lab_dis << " render_fnv " << hex << h << dec;
         }
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;

@@ -123,6 +123,35 @@ int ssm_carve(ssm_ctx*, const ssm_carve_view* v, const double* Tv, ssm_cloud* co
     }
     return SSM_OK;
 }
+// map rendering (Mapper with mapper_render=1): a "target" is the host images, the linked host functions in the device entry points' place
+struct ssm_render_target { int w, h; std::vector<uint16_t> depth; std::vector<uint8_t> bgr, label; std::vector<int32_t> index; };
+int ssm_render_target_create(ssm_ctx*, int w, int h, ssm_render_target** out)
+{
+    if (w < 1 || h < 1) return SSM_E_INVAL;
+    ssm_render_target* t = new ssm_render_target(); const size_t np = (size_t)w * h;
+    t->w = w; t->h = h; t->depth.assign(np, 0); t->bgr.assign(np * 3, 0); t->label.assign(np, 255); t->index.assign(np, -1); *out = t; return SSM_OK;
+}
+void ssm_render_target_free(ssm_ctx*, ssm_render_target* t) { delete t; }
+int ssm_render_points(ssm_ctx*, ssm_render_target* t, const ssm_camera* cam, const double* Tv, const ssm_point* const* pts, const int32_t* n, const double* Tc, int m,
+                      const ssm_render_params* params, ssm_render_info* info)
+{ return ssm_render_host(t->w, t->h, cam, Tv, pts, n, Tc, m, params, t->depth.data(), t->bgr.data(), t->label.data(), t->index.data(), nullptr, info); }
+int ssm_render_clouds(ssm_ctx* c, ssm_render_target* t, const ssm_camera* cam, const double* Tv, ssm_cloud* const* clouds, const double* Tc, int m, const ssm_render_params* params,
+                      ssm_render_info* info)
+{
+    std::vector<const ssm_point*> pts; std::vector<int32_t> n;
+    for (int k = 0; k < m; k++) { pts.push_back(clouds[k]->p.data()); n.push_back((int32_t)clouds[k]->p.size()); }
+    return ssm_render_points(c, t, cam, Tv, pts.data(), n.data(), Tc, m, params, info);
+}
+int ssm_render_fetch(ssm_ctx*, const ssm_render_target* t, uint16_t* depth, uint8_t* bgr, uint8_t* label, int32_t* index)
+{
+    if (depth) memcpy(depth, t->depth.data(), t->depth.size() * 2);
+    if (bgr) memcpy(bgr, t->bgr.data(), t->bgr.size());
+    if (label) memcpy(label, t->label.data(), t->label.size());
+    if (index) memcpy(index, t->index.data(), t->index.size() * 4);
+    return SSM_OK;
+}
+int ssm_render_compare(ssm_ctx*, ssm_render_target* t, const uint16_t* depth, const uint8_t* sem, double scale, const ssm_render_params* params, ssm_render_compare_info* info, uint8_t* cls)
+{ return ssm_render_compare_host(t->depth.data(), t->label.data(), t->w, t->h, depth, sem, scale, params, info, cls); }
 int ssm_cloud_size(const ssm_cloud* cl) { return cl ? (int)cl->p.size() : 0; }
 void ssm_cloud_free(ssm_ctx*, ssm_cloud* cl) { delete cl; }
 int ssm_cloud_fetch(ssm_ctx*, const ssm_cloud* cl, const double*, ssm_point* out, int cap, int* n_out)
