@@ -318,6 +318,8 @@ int ssm_vo_estimate(ssm_ctx* ctx, const ssm_pmatch* matches, int n, const ssm_vo
  * include/ssm/pnp_core.h on the host (lane-ordered sums, polynomial sin / cos) and as oracle/pnp.c.  n <= 65535. */
 int ssm_pnp_solve(ssm_ctx* ctx, const float* img, const float* obj, int n, const double cam[4], int min_inliers, double T[16],
                   uint8_t* inliers, int* n_inliers, int* success);
+int ssm_debug_pnp_solve_blocks(ssm_ctx* ctx);                            /* 8 or 1: the blocks the context's next ssm_pnp_solve starts with (1 after a cluster timed out once) */
+int ssm_pnp_lds_edge_capacity(void);                                  /* the largest n whose edge list the device solve keeps in LDS (above it: in global memory, same bits): the tests build their sizes around it */
 
 /* ---- Looper (reference include/looper.h, src/looper.cpp): the DBoW2 bag-of-words loop detector ------------------------------------------------------
  * Looper::add is vocab.transform(descriptors, frame->bowVec, ..), Looper::getPossibleLoops is vocab.score(frame, pf) against every stored key-frame with

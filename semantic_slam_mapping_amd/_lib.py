@@ -181,6 +181,8 @@ SYMBOLS = {
     "ssm_stereo_depth": (_I, [_P, _P, _P, _I, _I, _I, _P] + [_D] * 8 + [_P, _P]),
     "ssm_vo_estimate": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
     "ssm_pnp_solve": (_I, [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "ssm_pnp_lds_edge_capacity": (_I, []),
+    "ssm_debug_pnp_solve_blocks": (_I, [_P]),
     "ssm_vocab_load_text": (_I, [C.c_char_p, C.POINTER(_P)]),
     "ssm_vocab_create": (_I, [_I, _I, _I, _I, _P, _P, _P, _P, _I, C.POINTER(_P)]),
     "ssm_vocab_destroy": (None, [_P]),

@@ -149,6 +149,11 @@ def motion_fuse_host(sem, motion=None, area_thres=1000, overlay_thres=0.143, rec
 SOR_INFO_FIELDS = ("n_in", "n_finite", "n_kept", "too_few", "levels", "sum_q", "sum_q2_lo", "sum_q2_hi", "mean", "stddev", "threshold")
 
 
+def pnp_lds_edge_capacity():
+    """the largest number of correspondences whose edge list Context.pnp_solve keeps in LDS: ssm_pnp_lds_edge_capacity"""
+    return _lib.load().ssm_pnp_lds_edge_capacity()
+
+
 def sor_chunk():
     """candidates per LDS chunk of the device search: ssm_sor_chunk"""
     return _lib.load().ssm_sor_chunk()
@@ -849,6 +854,10 @@ class Context:
         inl = np.zeros(max(len(img), 1), np.uint8); n = C.c_int(0); ok = C.c_int(0)
         self._chk(self.lib.ssm_pnp_solve(self.h, _ptr(img), _ptr(obj), len(img), _ptr(camv), int(min_inliers), _ptr(T), _ptr(inl), C.byref(n), C.byref(ok)))
         return bool(ok.value), T.T.copy(), inl[:len(img)].copy(), n.value
+
+    def pnp_solve_blocks(self):
+        """8 or 1: the blocks the next pnp_solve starts with (ssm_debug_pnp_solve_blocks; 1 once a cluster of eight has timed out on this context)"""
+        return self.lib.ssm_debug_pnp_solve_blocks(self.h)
 
     def gftt(self, img, max_corners=1000, quality=0.04, min_distance=8.0):
         img = np.ascontiguousarray(img, np.uint8); h, w = img.shape

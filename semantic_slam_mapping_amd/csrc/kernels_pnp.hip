@@ -861,11 +861,13 @@ pnp_solve_kernel(PnpSolveArgs a)
         if (threadIdx.x == 0) *a.n_inliers = m;
     }
 }
+// the longest edge list that stays in LDS: what fits beside the static part (160 KB per CU, 1 KB kept free)
+size_t k_pnp_lds_edge_capacity(void) { return (160 * 1024 - sizeof(PcShared) - 1024) / sizeof(LEdge); }
 static hipError_t pc_dyn_size(size_t nedges, int* in_lds, size_t* dyn, const void* fn)
 {
     if (nedges > 65535) return hipErrorInvalidValue;                             // ids are 16-bit in LEdge::meta
     const size_t need = nedges * sizeof(LEdge);
-    *in_lds = need + sizeof(PcShared) + 1024 <= 160 * 1024 ? 1 : 0;              // the edge list in LDS when it fits beside the static part (160 KB per CU)
+    *in_lds = nedges <= k_pnp_lds_edge_capacity() ? 1 : 0;                       // the edge list in LDS when it fits beside the static part
     *dyn = *in_lds ? need : 0;
     // to the largest size any list in LDS can have (allow_dynamic_lds: once per device and kernel; trackers on their own streams launch while other chains run)
     return allow_dynamic_lds(fn, *dyn, 160 * 1024 - (int)sizeof(PcShared) - 1024);

@@ -30,3 +30,4 @@ struct PnpSolveArgs {
 };
 hipError_t k_pnp_solve(const PnpSolveArgs& a, hipStream_t s);
 size_t k_pnp_edge_bytes(void);
+size_t k_pnp_lds_edge_capacity(void);               // the largest n (k_pnp_solve) / R * cap (k_pnp_chain) whose edge list the kernels keep in LDS

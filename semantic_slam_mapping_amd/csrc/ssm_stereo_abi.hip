@@ -505,6 +505,15 @@ static int pnp_solve_impl(ssm_ctx* c, const float* img, const float* obj, int n,
     if (success) *success = n > min_inliers;                   // pnp.cpp:115 tests the flag vector's LENGTH (quirk 14)
     return SSM_OK;
 }
+extern "C" int ssm_pnp_lds_edge_capacity(void) { return (int)k_pnp_lds_edge_capacity(); }
+static int pnp_env_blocks() { static const int b = [] { const char* e = getenv("SSM_PNP_BLOCKS"); return e ? atoi(e) : 8; }(); return b; }
+// the blocks the context's next ssm_pnp_solve starts with (tests: which form a comparison ran in)
+extern "C" int ssm_debug_pnp_solve_blocks(ssm_ctx* c)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu);
+    return pnp_env_blocks() == 8 && !c->pnp_solve_one_block ? 8 : 1;
+}
 extern "C" int ssm_pnp_solve(ssm_ctx* c, const float* img, const float* obj, int n, const double cam[4], int min_inliers, double T[16],
                              uint8_t* inliers, int* n_inliers, int* success)
 {
@@ -512,8 +521,7 @@ extern "C" int ssm_pnp_solve(ssm_ctx* c, const float* img, const float* obj, int
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     if (n < 0 || !cam || !T || !n_inliers || (n && (!img || !obj))) FAIL(c, SSM_E_INVAL, "bad arguments");
     if (n > 65535) FAIL(c, SSM_E_CAPACITY, "at most 65535 correspondences");
-    static const int env_blocks = [] { const char* e = getenv("SSM_PNP_BLOCKS"); return e ? atoi(e) : 8; }();
-    if (env_blocks == 8 && !c->pnp_solve_one_block) {
+    if (pnp_env_blocks() == 8 && !c->pnp_solve_one_block) {
         const int r = pnp_solve_impl(c, img, obj, n, cam, min_inliers, T, inliers, n_inliers, success, 8);
         if (r <= 0) return r;
         c->pnp_solve_one_block = true;                          // (T is untouched: the retry starts from the caller's initial value)

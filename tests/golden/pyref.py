@@ -1022,7 +1022,15 @@ def _pnp_oplus(R, t, d):
     return nR, nt
 
 
-def _pnp_optimize(edges, R, t, cam, delta, iterations):
+def _pnp_count(events, key):
+    if events is not None:
+        events[key] = events.get(key, 0) + 1
+
+
+def _pnp_optimize(edges, R, t, cam, delta, iterations, events=None):
+    """events (optional dict): counts the paths this call takes -- streak_N: an iteration ran N trials (N - 1 rejected ones with gain < 0 in front of the
+    one that ended it; 10 = the trial limit); ten_trials / gain_zero: what terminated the call early; all_10_iterations: nothing did; tenth_trial_accepted: the
+    trial limit stopped a call whose last trial had just moved the estimate (only then does the limit change the result: after ten rejections the estimate stands still); pivot_failed: a trial whose L D L^T met a non-positive pivot"""
     if not any(e.level == 0 for e in edges):
         return R, t
     lam, nu = 0.0, 2.0
@@ -1038,6 +1046,7 @@ def _pnp_optimize(edges, R, t, cam, delta, iterations):
             ok = x is not None
             if not ok:
                 x = [0.0] * 6
+                _pnp_count(events, "pivot_failed")
             R, t = _pnp_oplus(R, t, x)
             chi_new = _pnp_chi(edges, R, t, cam, delta)
             if not ok:
@@ -1061,15 +1070,24 @@ def _pnp_optimize(edges, R, t, cam, delta, iterations):
             trials += 1
             if not (gain < 0 and trials < 10):
                 break
+        if 1 <= trials <= 10:
+            _pnp_count(events, "streak_%d" % trials)
         if trials == 10 or gain == 0:
+            _pnp_count(events, "ten_trials" if trials == 10 else "gain_zero")
+            if trials == 10 and gain > 0:
+                _pnp_count(events, "tenth_trial_accepted")
             break
+    else:
+        _pnp_count(events, "all_10_iterations")
     _pnp_chi(edges, R, t, cam, delta)
     return R, t
 
 
-def pnp_solve(img, obj, cam, T, min_inliers=10):
+def pnp_solve(img, obj, cam, T, min_inliers=10, events=None):
     """img n x 2 float32, obj n x 3 float32 (all-zero row = no depth), cam (cx, cy, fx, fy, ...), T 4 x 4 initial transform.
-    Returns (success, T 4 x 4, inlier indices)."""
+    Returns (success, T 4 x 4, inlier indices).  events (optional dict) counts the paths taken: _pnp_optimize's, rounds_N (the solve ran N rounds),
+    remarked_outlier (a flag cleared in a round and set again in the same round by a later edge's position: quirk 14) and
+    robust_off_round_with_outliers (the fourth round, kernels dropped, ran with edges at level 1); the results do not depend on it."""
     n = len(img)
     delta = float(np.float32(math.sqrt(5.991)))
     inl = [True] * n
@@ -1085,19 +1103,28 @@ def pnp_solve(img, obj, cam, T, min_inliers=10):
     T = np.asarray(T, np.float64)
     R0 = [float(T[r, c]) for r in range(3) for c in range(3)]; t0 = [float(T[r, 3]) for r in range(3)]
     R, t = R0, t0
+    rounds = 0
     for it in range(4):
-        R, t = _pnp_optimize(edges, R0, t0, cam, delta, 10)
+        rounds += 1
+        if it == 3 and any(e.level != 0 for e in edges):
+            _pnp_count(events, "robust_off_round_with_outliers")
+        R, t = _pnp_optimize(edges, R0, t0, cam, delta, 10, events)
+        cleared = set()
         for i, e in enumerate(edges):
             if inl[e.id]:
                 _pnp_error(e, R, t, cam)
             if e.e[0] * e.e[0] + e.e[1] * e.e[1] > 5.991:
                 inl[e.id] = False; e.level = 1; good -= 1
+                cleared.add(e.id)
             else:
+                if i in cleared:
+                    _pnp_count(events, "remarked_outlier")
                 inl[i] = True; e.level = 0
             if it == 2:
                 e.robust = False
         if good < 5:
             break
+    _pnp_count(events, "rounds_%d" % rounds)
     out = np.eye(4)
     for r in range(3):
         for c in range(3):

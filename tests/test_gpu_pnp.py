@@ -38,7 +38,7 @@ def test_device_pnp_equals_oracle(ctx, oracle, seed, n, outlier_every, zero_ever
 
 
 def test_edge_list_in_global_memory_when_it_does_not_fit_in_lds(ctx, oracle):
-    """6250 edges of 24 bytes fit beside the static LDS; 9000 do not: the same passes run on the list in global memory"""
+    """5306 edges of 24 bytes (pnp_lds_edge_capacity()) fit beside the static LDS; 9000 do not: the same passes run on the list in global memory"""
     img, obj, Tgt = _case(21, 9000, 8, 13, 0.5)
     T, inl = _check(ctx, oracle, img, obj, np.eye(4))
     assert np.abs(T - Tgt).max() < 5e-3 and len(inl) > 7000
