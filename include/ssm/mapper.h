@@ -38,6 +38,16 @@
 // not depend on the viewer's update schedule.  Both routes give the same bytes: deviceCloud / ssm_render_clouds and frame->pointcloud / ssm_render_points (the host
 // route when mapper_device_map=0 or after the device-resident update fell back).  With mapper_render_dir set every view writes render_%06d_depth.png (16 bit),
 // _bgr.png, _label.png (palette colours) and _class.png (0 unrendered, 1 no depth, 2 in front, 3 behind, 4 agree) there, %06d the key-frame's number.
+// mapper_align=1 (default 0: nothing of this runs, every cloud, map and figure exactly as before): dense alignment (the reference has no such
+// step).  Every key-frame j is aligned exactly once, in ascending j, before it becomes a carving view (with mapper_carve=1 the two alternate key-frame by key-frame:
+// j is aligned against the clouds as the views before j left them) and before an update reads its pose: its depth image is the
+// VIEW, the clouds of key-frames j - mapper_align_window .. j - 1 (made on demand) at their MAP POSES are aligned to it by point-to-plane ICP, from the start pose
+// D_prev . P_j -- P_j the key-frame's pose as the Mapper hands poses on (mapper_invert_pose applied), D_prev the last accepted world-frame correction, so drift
+// the next key-frame shares is carried forward.  An alignment is accepted when it converged or reached max_iterations with at least min_inliers inliers; it then
+// defines D_j = T_out . inverse(P_j), any other outcome gives D_j = D_prev.  The map pose D_j . P_j is what the Mapper uses wherever it read the key-frame's pose:
+// the map update, carveUpTo and the rendering.  RGBDFrame::T_f_w, the tracker and the pose graph are not written, and the map pose is FIXED when the key-frame is
+// aligned: a pose-graph correction that arrives later does not recompute it (a limit).  Both routes give the same bytes: deviceCloud /
+// ssm_align_clouds and frame->pointcloud / ssm_align_points.
 #pragma once
 #include "common_headers.h"
 #include <atomic>
@@ -77,6 +87,23 @@ public:
         ssm_render_params_default(&render_params);
         render_params.point_size = para.getData<double>("mapper_render_point_size", render_params.point_size);
         render_params.max_radius = para.getData<int>("mapper_render_max_radius", render_params.max_radius);
+        align = para.getData<int>("mapper_align", 0) != 0;
+        align_window = para.getData<int>("mapper_align_window", 5);
+        ssm_align_params_default(&align_params);
+        align_params.max_iterations = para.getData<int>("mapper_align_max_iterations", align_params.max_iterations);
+        align_params.stride = para.getData<int>("mapper_align_stride", align_params.stride);
+        align_params.z_min = para.getData<double>("mapper_align_z_min", align_params.z_min);
+        align_params.z_max = para.getData<double>("mapper_align_z_max", align_params.z_max);
+        align_params.dist_max = para.getData<double>("mapper_align_dist_max", align_params.dist_max);
+        align_params.delta = para.getData<double>("mapper_align_delta", align_params.delta);
+        align_params.damping = para.getData<double>("mapper_align_damping", align_params.damping);
+        align_params.eps_rot = para.getData<double>("mapper_align_eps_rot", align_params.eps_rot);
+        align_params.eps_trans = para.getData<double>("mapper_align_eps_trans", align_params.eps_trans);
+        align_params.min_inliers = para.getData<int>("mapper_align_min_inliers", align_params.min_inliers);
+        align_params.max_shift = para.getData<double>("mapper_align_max_shift", align_params.max_shift);
+        align_params.max_angle = para.getData<double>("mapper_align_max_angle", align_params.max_angle);
+        align_params.tol_abs = para.getData<double>("mapper_align_tol_abs", align_params.tol_abs);
+        align_params.tol_rel_ppm = para.getData<int>("mapper_align_tol_rel_ppm", align_params.tol_rel_ppm);
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
     }
@@ -94,7 +121,7 @@ public:
             if (nkf <= (size_t)keyframe_size) { this_thread::sleep_for(chrono::milliseconds(1)); continue; }
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
             auto t0 = chrono::steady_clock::now();
-            if (carve) carveUpTo(kfs);
+            alignCarveUpTo(kfs);
             // the key-frames this update adds (mapper.cpp:121-141)
             vector<RGBDFrame::Ptr> sel; const bool rebuild = cntGlobalUpdate % 15 == 0;
             if (rebuild) { for (size_t i = 0; i < kfs.size(); i += 2) sel.push_back(kfs[i]); }
@@ -111,7 +138,7 @@ public:
                     vector<ssm_cloud*> cl; vector<double> poses;
                     for (const RGBDFrame::Ptr& f : sel) {
                         cl.push_back(deviceCloud(f));
-                        const Eigen::Isometry3d T = invert_pose ? f->getTransform().inverse() : f->getTransform();
+                        const Eigen::Isometry3d T = mapPoseOf(f);
                         poses.insert(poses.end(), T.data(), T.data() + 16);
                     }
                     int nmap = 0;
@@ -148,9 +175,9 @@ public:
             cout << "points in global map: " << map->points.size() << endl;
             cout << "Mapping cost time: " << ms << "ms" << endl;
         }
-        if (carve) {                                    // the key-frames that came after the last update are views too: the clouds' final state does not depend on this thread's timing
+        if (align || carve) {                           // the key-frames that came after the last update are aligned and are views too: the final state does not depend on this thread's timing
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            carveUpTo(kfs);
+            alignCarveUpTo(kfs);
         }
         if (render) {                                   // every key-frame is a view of the clouds around it, in their final state
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
@@ -202,7 +229,7 @@ public:
     // arithmetic ssm_backproject applies on the device when it is given T, so both routes give identical bits; -ffp-contract=off in host/Makefile)
     PointCloud::Ptr generatePointCloud(const RGBDFrame::Ptr& frame) {
         hostCloud(frame);
-        const Eigen::Isometry3d T = invert_pose ? frame->getTransform().inverse() : frame->getTransform();
+        const Eigen::Isometry3d T = mapPoseOf(frame);
         const double* t = T.data();                                            // column-major
         PointCloud::Ptr tmp(new PointCloud(*frame->pointcloud));
         for (PointT& p : tmp->points) {
@@ -245,19 +272,19 @@ public:
     }
     // free-space carving: the key-frames kfs[carved ..] become views, one after the other, each of the clouds of the `carve_window` key-frames before it.  The
     // viewer thread calls this; once that has ended its owner may (the host route then: the device clouds went with the thread)
-    void carveUpTo(const vector<RGBDFrame::Ptr>& kfs) {
-        for (; carved < kfs.size(); carved++) {
+    void carveUpTo(const vector<RGBDFrame::Ptr>& kfs, size_t upto = (size_t)-1) {
+        for (; carved < min(kfs.size(), upto); carved++) {
             const size_t j = carved, first = j > (size_t)max(carve_window, 0) ? j - (size_t)max(carve_window, 0) : 0;
             if (first == j) continue;
             const RGBDFrame::Ptr& vf = kfs[j];
             const int w = vf->depth.cols, h = vf->depth.rows;
             ssm::Device& d = device(w, h);
             ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
-            const Eigen::Isometry3d Tv = invert_pose ? vf->getTransform().inverse() : vf->getTransform();
+            const Eigen::Isometry3d Tv = mapPoseOf(vf);
             const int m = (int)(j - first);
             vector<double> poses; vector<ssm_carve_info> infos((size_t)m);
             for (size_t i = first; i < j; i++) {
-                const Eigen::Isometry3d T = invert_pose ? kfs[i]->getTransform().inverse() : kfs[i]->getTransform();
+                const Eigen::Isometry3d T = mapPoseOf(kfs[i]);
                 poses.insert(poses.end(), T.data(), T.data() + 16);
             }
             if (device_map) {
@@ -292,6 +319,68 @@ public:
             carveViews++;
         }
     }
+    // dense alignment: the key-frames kfs[aligned ..] are aligned, one after the other, each as the view of the clouds of the `align_window` key-frames before it at
+    // their map poses.  The viewer thread calls this; once that has ended its owner may (the host route then: the device clouds went with the thread)
+    void alignUpTo(const vector<RGBDFrame::Ptr>& kfs, size_t upto = (size_t)-1) {
+        for (; aligned < min(kfs.size(), upto); aligned++) {
+            const size_t j = aligned, first = j > (size_t)max(align_window, 0) ? j - (size_t)max(align_window, 0) : 0;
+            const RGBDFrame::Ptr& vf = kfs[j];
+            const Eigen::Isometry3d Pj = invert_pose ? vf->getTransform().inverse() : vf->getTransform();
+            const Eigen::Isometry3d start = alignD * Pj;
+            AlignResult R; R.D = alignD; R.map_pose = start; memset(&R.info, 0, sizeof R.info); R.accepted = false;
+            if (first < j) {
+                const int w = vf->depth.cols, h = vf->depth.rows;
+                ssm::Device& d = device(w, h);
+                ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
+                const int m = (int)(j - first);
+                vector<double> poses;
+                for (size_t i = first; i < j; i++) { const Eigen::Isometry3d T = mapPoseOf(kfs[i]); poses.insert(poses.end(), T.data(), T.data() + 16); }
+                vector<ssm_cloud*> cl; vector<const ssm_point*> pts; vector<int32_t> n;
+                for (size_t i = first; i < j; i++) {
+                    if (device_map) cl.push_back(deviceCloud(kfs[i]));
+                    else { hostCloud(kfs[i]); pts.push_back(reinterpret_cast<const ssm_point*>(kfs[i]->pointcloud->points.data())); n.push_back((int32_t)kfs[i]->pointcloud->points.size()); }
+                }
+                ssm_align_view* view = nullptr;
+                d.check(ssm_align_view_create(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, &align_params, &view), "ssm_align_view_create");
+                double To[16];
+                const int rc = device_map ? ssm_align_clouds(d.ctx(), view, start.data(), cl.data(), poses.data(), m, &align_params, To, &R.info)
+                                          : ssm_align_points(d.ctx(), view, start.data(), pts.data(), n.data(), poses.data(), m, &align_params, To, &R.info);
+                ssm_align_view_free(d.ctx(), view);
+                d.check(rc, device_map ? "ssm_align_clouds" : "ssm_align_points");
+                R.accepted = R.info.status == SSM_ALIGN_CONVERGED || (R.info.status == SSM_ALIGN_MAX_ITER && R.info.inliers_last >= (int64_t)align_params.min_inliers);
+                if (R.accepted) {
+                    Eigen::Isometry3d out; for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) out(r, c) = To[c * 4 + r];
+                    R.map_pose = out; R.D = out * Pj.inverse(); alignD = R.D; alignAccepted++;
+                }
+            }
+            alignResult[vf.get()] = R;
+        }
+    }
+    // what the viewer does with the key-frames so far: with both switches on, key-frame by key-frame -- j is aligned against the clouds as the views before j left
+    // them, then j is a carving view -- so the result does not depend on how many key-frames arrive between two updates
+    void alignCarveUpTo(const vector<RGBDFrame::Ptr>& kfs) {
+        if (align && carve) { for (size_t k = min(aligned, carved) + 1; k <= kfs.size(); k++) { alignUpTo(kfs, k); carveUpTo(kfs, k); } }
+        else if (align) alignUpTo(kfs);
+        else if (carve) carveUpTo(kfs);
+    }
+    struct AlignResult { Eigen::Isometry3d D, map_pose; ssm_align_info info; bool accepted; };
+    bool aligns() const { return align; }
+    int alignedKeyframes() const { return (int)aligned; }                    // key-frames aligned so far (the first has no earlier cloud: it keeps its pose)
+    int acceptedAlignments() const { return alignAccepted; }
+    // a key-frame's alignment (not while the viewer thread runs); false: not aligned yet, or the switch is off.  D: its world-frame correction D_j
+    bool alignInfoOf(const RGBDFrame::Ptr& frame, ssm_align_info* info, Eigen::Isometry3d* D = nullptr, bool* accepted = nullptr) const {
+        auto it = alignResult.find(frame.get());
+        if (it == alignResult.end()) return false;
+        if (info) *info = it->second.info;
+        if (D) *D = it->second.D;
+        if (accepted) *accepted = it->second.accepted;
+        return true;
+    }
+    // the pose the Mapper uses for a key-frame: its map pose D_j . P_j once it has been aligned, else its pose as before (mapper_invert_pose applied)
+    Eigen::Isometry3d mapPoseOf(const RGBDFrame::Ptr& frame) const {
+        if (align) { auto it = alignResult.find(frame.get()); if (it != alignResult.end()) return it->second.map_pose; }
+        return invert_pose ? frame->getTransform().inverse() : frame->getTransform();
+    }
     // map rendering: every key-frame of kfs is a view once, of the clouds of the key-frames within `render_window` of it (itself left out), compared with its own
     // depth and semantic image.  The viewer thread calls this as it ends; once that has ended its owner may (the host route then: the device clouds went with the thread)
     struct RenderTarget {        // the device images, of the size of the current view; freed on every way out
@@ -307,7 +396,7 @@ public:
             const int w = vf->depth.cols, h = vf->depth.rows;
             ssm::Device& d = device(w, h);
             ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
-            const Eigen::Isometry3d Tv = invert_pose ? vf->getTransform().inverse() : vf->getTransform();
+            const Eigen::Isometry3d Tv = mapPoseOf(vf);
             if (!target.t || target.w != w || target.h != h) {
                 if (target.t) { ssm_render_target_free(target.ctx, target.t); target.t = nullptr; }
                 target.ctx = d.ctx(); target.w = w; target.h = h;
@@ -317,7 +406,7 @@ public:
             for (size_t i = j > win ? j - win : 0; i < kfs.size() && i <= j + win; i++) if (i != j) around.push_back(i);
             vector<double> poses;
             for (size_t i : around) {
-                const Eigen::Isometry3d T = invert_pose ? kfs[i]->getTransform().inverse() : kfs[i]->getTransform();
+                const Eigen::Isometry3d T = mapPoseOf(kfs[i]);
                 poses.insert(poses.end(), T.data(), T.data() + 16);
             }
             ssm_render_info R{};
@@ -443,6 +532,9 @@ protected:
     bool carve = false; int carve_window = 5; ssm_carve_params carve_params{}; size_t carved = 0; int carveViews = 0;
     std::unordered_map<const RGBDFrame*, vector<uint8_t>> carveRun;      // host route: the run counters beside frame->pointcloud
     std::unordered_map<const RGBDFrame*, ssm_carve_info> carveInfo;      // key-frame -> what the views did to its cloud (viewer thread, or its owner once that has ended)
+    bool align = false; int align_window = 5, alignAccepted = 0; ssm_align_params align_params{}; size_t aligned = 0;
+    Eigen::Isometry3d alignD = Eigen::Isometry3d::Identity();            // D_prev: the last accepted world-frame correction
+    std::unordered_map<const RGBDFrame*, AlignResult> alignResult;       // key-frame -> its alignment and map pose (viewer thread, or its owner once that has ended)
     bool render = false; int render_window = 5, renderViews = 0; string render_dir; ssm_render_params render_params{};
     std::unordered_map<const RGBDFrame*, ssm_render_compare_info> renderInfo;      // key-frame -> its view's comparison (viewer thread, or its owner once that has ended)
     std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)

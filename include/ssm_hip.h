@@ -580,6 +580,58 @@ void ssm_render_label_colours(const uint8_t* label, int64_t n, uint8_t* bgr_out)
 /* the raw z-buffer after the target's last rendering (w h entries), for the tests */
 int  ssm_debug_render_keys(ssm_ctx* ctx, const ssm_render_target* target, uint64_t* keys);
 
+/* ---- dense alignment: projective point-to-plane ICP of the points of m posed clouds against a key-frame's depth image (the view).  The reference has no such
+ * step; DESIGN.md s.18 is the contract, include/ssm/align_core.h the arithmetic shared by the device path and the host function.  The view gets a normal per
+ * pixel (invalid at depth 0, at the border and across a depth edge: a neighbour farther than carving's tolerance).  Per iteration every point is carried into the
+ * view's frame by E . inverse(T_view) . T_cloud (E: the increment, the identity at first), projected to the nearest pixel, and contributes its point-to-plane
+ * residual r = n . (q - V) when the pixel is valid and |r| <= dist_max, Huber-weighted.  The sums are exact 64-bit integer sums of fixed-point terms, so the
+ * result does not depend on the order of the points or clouds.  The 6 x 6 solve (damped: lambda = damping inliers) runs on the host.
+ * status: 0 max_iterations reached, 1 converged (|omega| < eps_rot and |upsilon| < eps_trans), 2 fewer than min_inliers inliers, 3 a non-positive pivot,
+ * 4 the accumulated increment left max_shift / max_angle.  With 2, 3 and 4 T_view_out = T_view and E = the identity; else T_view_out = T_view . inverse(E).
+ * SSM_E_INVAL: max_iterations outside 1..64, stride outside 1..2^20, a negative or non-finite parameter, z_max < z_min, max_angle above pi, tolerance and camera
+ * limits as carving's, w or h < 3 or w h > 2^26, a non-finite pose, m < 0, a negative count, the same cloud twice, or a point count whose sums could reach 2^62
+ * (align_core.h term_bound_units, from z_max, dist_max and the camera's field of view). */
+enum { SSM_ALIGN_MAX_ITER = 0, SSM_ALIGN_CONVERGED = 1, SSM_ALIGN_TOO_FEW = 2, SSM_ALIGN_DEGENERATE = 3, SSM_ALIGN_DIVERGED = 4, SSM_ALIGN_NSUM = 30 };
+typedef struct {
+    int32_t max_iterations, stride;          /* stride: every k-th point of each cloud is used */
+    double z_min, z_max, dist_max, delta, damping, eps_rot, eps_trans;
+    int32_t min_inliers, pad;
+    double max_shift, max_angle;             /* bounds of the accumulated increment: metres, radians */
+    double tol_abs; int32_t tol_rel_ppm, pad2;      /* the depth-edge gate of the view (read by ssm_align_view_create / ssm_align_host) */
+} ssm_align_params;
+typedef struct {
+    int32_t status, iterations;              /* iterations: accumulations run */
+    int64_t n_in;                            /* points used (after stride) */
+    int64_t tested_first, inliers_first, tested_last, inliers_last;       /* tested: reached a valid pixel */
+    double chi2_first, chi2_last;            /* the robustified sum of squared residuals, m^2 */
+    double E[16];                            /* the increment, column-major 4 x 4 */
+} ssm_align_info;
+/* one iteration: 21 lower-triangle entries of H and 6 of b in units of 2^-20, chi2 in units of 2^-30, tested, inliers; E: the 3 x 4 row-major increment it used */
+typedef struct { int64_t sums[SSM_ALIGN_NSUM]; double E[12]; } ssm_align_iter;
+typedef struct ssm_align_view ssm_align_view;
+/* 10, 1, 0.1 m, 80 m, 0.25 m, 0.05 m, 1e-6, 1e-4 rad, 1e-4 m, 1000, 1 m, 0.2 rad, 0.05 m, 20000 ppm */
+void ssm_align_params_default(ssm_align_params* p);
+/* a view: the depth image goes to device memory once, the normal map is built there, and both stay until ssm_align_view_free.  params: the edge gate (NULL: defaults) */
+int  ssm_align_view_create(ssm_ctx* ctx, const uint16_t* depth_host, int w, int h, const ssm_camera* cam, const ssm_align_params* params, ssm_align_view** view_out);
+void ssm_align_view_free(ssm_ctx* ctx, ssm_align_view* view);
+/* device-resident clouds: nothing is uploaded but the poses and each iteration's E, nothing downloaded but the sums.  Clouds are not modified; size 0 is legal */
+int  ssm_align_clouds(ssm_ctx* ctx, const ssm_align_view* view, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
+                      const ssm_align_params* params, double* T_view_out, ssm_align_info* info);
+/* host arrays through the device: pts[k] holds n[k] points of cloud k */
+int  ssm_align_points(ssm_ctx* ctx, const ssm_align_view* view, const double* T_view, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m,
+                      const ssm_align_params* params, double* T_view_out, ssm_align_info* info);
+/* the same on the CPU, the same bits; needs no GPU.  valid (w h bytes), normals (w h x 4 floats: x y z 0), record (record_cap entries, *n_record of them
+ * written: one per iteration) may be NULL */
+int  ssm_align_host(const uint16_t* depth, int w, int h, const ssm_camera* cam, const double* T_view, const ssm_point* const* pts, const int32_t* n,
+                    const double* T_clouds, int m, const ssm_align_params* params, double* T_view_out, ssm_align_info* info, uint8_t* valid, float* normals,
+                    ssm_align_iter* record, int record_cap, int* n_record);
+/* the view's valid mask and normals as ssm_align_host gives them; each may be NULL */
+int  ssm_debug_align_normals(ssm_ctx* ctx, const ssm_align_view* view, uint8_t* valid, float* normals);
+/* the iterations of the context's last device alignment: *n_record of them (more than cap: SSM_E_CAPACITY) */
+int  ssm_debug_align_record(ssm_ctx* ctx, ssm_align_iter* record, int cap, int* n_record);
+/* points one pass of the accumulation's persistent grid covers (a larger call loops), for the tests */
+int64_t ssm_debug_align_pass_points(void);
+
 /* ---- PoseGraph's optimiser (reference src/pose_graph.cpp:82-305, include/pose_graph.h:53-62): a graph of SE3 vertices and SE3 edges with Huber kernels,
  * Levenberg (g2o's OptimizationAlgorithmLevenberg) over a direct block-envelope L D L^T.  DESIGN.md s.12 is the contract; include/ssm/pgo_core.h holds the
  * arithmetic, ONE function template that the host function runs with one thread and the device path with one 1024-thread block per graph, so device ==

@@ -109,6 +109,17 @@ class RenderCompareInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("unrendered", "no_depth", "in_front", "behind", "agree", "label_agree", "label_disagree", "label_unknown", "n_pixels")]
 
 
+class AlignParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("stride", C.c_int32)] + [(n, C.c_double) for n in ("z_min", "z_max", "dist_max", "delta", "damping", "eps_rot", "eps_trans")] + \
+               [("min_inliers", C.c_int32), ("pad", C.c_int32), ("max_shift", C.c_double), ("max_angle", C.c_double), ("tol_abs", C.c_double), ("tol_rel_ppm", C.c_int32),
+                ("pad2", C.c_int32)]
+
+
+class AlignInfo(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32)] + [(n, C.c_int64) for n in ("n_in", "tested_first", "inliers_first", "tested_last", "inliers_last")] + \
+               [("chi2_first", C.c_double), ("chi2_last", C.c_double), ("E", C.c_double * 16)]
+
+
 class VocabTrainParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("L", C.c_int32), ("max_iters", C.c_int32)]
 
@@ -251,6 +262,15 @@ SYMBOLS = {
     "ssm_render_compare_host": (_I, [_P, _P, _I, _I, _P, _P, C.c_double, C.POINTER(RenderParams), C.POINTER(RenderCompareInfo), _P]),
     "ssm_render_label_colours": (None, [_P, C.c_int64, _P]),
     "ssm_debug_render_keys": (_I, [_P, _P, _P]),
+    "ssm_align_params_default": (None, [C.POINTER(AlignParams)]),
+    "ssm_align_view_create": (_I, [_P, _P, _I, _I, C.POINTER(Camera), C.POINTER(AlignParams), C.POINTER(_P)]),
+    "ssm_align_view_free": (None, [_P, _P]),
+    "ssm_align_clouds": (_I, [_P, _P, _P, _P, _P, _I, C.POINTER(AlignParams), _P, C.POINTER(AlignInfo)]),
+    "ssm_align_points": (_I, [_P, _P, _P, _P, _P, _P, _I, C.POINTER(AlignParams), _P, C.POINTER(AlignInfo)]),
+    "ssm_align_host": (_I, [_P, _I, _I, C.POINTER(Camera), _P, _P, _P, _P, _I, C.POINTER(AlignParams), _P, C.POINTER(AlignInfo), _P, _P, _P, _I, C.POINTER(_I)]),
+    "ssm_debug_align_normals": (_I, [_P, _P, _P, _P]),
+    "ssm_debug_align_record": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "ssm_debug_align_pass_points": (C.c_int64, []),
     "ssm_pgo_create": (_I, [_P, C.POINTER(_P)]),
     "ssm_pgo_destroy": (None, [_P]),
     "ssm_pgo_clear": (_I, [_P]),

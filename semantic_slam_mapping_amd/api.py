@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -279,6 +279,52 @@ def label_colours(label):
     out = np.zeros(label.shape + (3,), np.uint8)
     _lib.load().ssm_render_label_colours(_ptr(label), label.size, _ptr(out))
     return out
+
+
+ALIGN_STATUS = ("max_iterations", "converged", "too_few", "degenerate", "diverged")
+ALIGN_INFO_FIELDS = ("status", "iterations", "n_in", "tested_first", "inliers_first", "tested_last", "inliers_last", "chi2_first", "chi2_last")
+ALIGN_DEFAULTS = dict(max_iterations=10, stride=1, z_min=0.1, z_max=80.0, dist_max=0.25, delta=0.05, damping=1.0e-6, eps_rot=1.0e-4, eps_trans=1.0e-4, min_inliers=1000,
+                      max_shift=1.0, max_angle=0.2, tol_abs=0.05, tol_rel_ppm=20000)
+ALIGN_NSUM = 30
+ALIGN_ITER_DTYPE = np.dtype([("sums", np.int64, (ALIGN_NSUM,)), ("E", np.float64, (12,))])
+ALIGN_MAX_ITERATIONS = 64
+
+
+def align_params(**kw):
+    """the parameters of dense alignment as the ABI's struct: ALIGN_DEFAULTS with kw on top"""
+    bad = set(kw) - set(ALIGN_DEFAULTS)
+    if bad:
+        raise TypeError("unknown alignment parameters: " + ", ".join(sorted(bad)))
+    p = dict(ALIGN_DEFAULTS, **kw)
+    return AlignParams(int(p["max_iterations"]), int(p["stride"]), float(p["z_min"]), float(p["z_max"]), float(p["dist_max"]), float(p["delta"]), float(p["damping"]),
+                       float(p["eps_rot"]), float(p["eps_trans"]), int(p["min_inliers"]), 0, float(p["max_shift"]), float(p["max_angle"]), float(p["tol_abs"]),
+                       int(p["tol_rel_ppm"]), 0)
+
+
+def _align_info(I):
+    out = {k: getattr(I, k) for k in ALIGN_INFO_FIELDS}
+    out["E"] = np.array(I.E, np.float64).reshape(4, 4).T.copy()
+    return out
+
+
+def align_host(depth, camera, T_view, clouds, T_clouds, **params):
+    """dense alignment on the CPU (ssm_align_host, no GPU): the points of `clouds` (host arrays of POINT_DTYPE at the poses T_clouds) against the view `depth`
+    (uint16, camera = (cx, cy, fx, fy, scale)) from the pose T_view -> {T_view, info, valid, normals (h x w x 4 floats), record (one ALIGN_ITER_DTYPE entry per
+    iteration)}"""
+    depth = np.ascontiguousarray(depth, np.uint16)
+    if depth.ndim != 2:
+        raise ValueError("a depth image is h x w")
+    h, w = depth.shape
+    keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+    P = align_params(**params); I = AlignInfo(); cam = Camera(*camera)
+    valid = np.zeros((h, w), np.uint8); normals = np.zeros((h, w, 4), np.float32); rec = np.zeros(ALIGN_MAX_ITERATIONS, ALIGN_ITER_DTYPE); nrec = C.c_int(0)
+    T_out = np.zeros(16)
+    lib = _lib.load()
+    rc = lib.ssm_align_host(_ptr(depth), w, h, C.byref(cam), _ptr(_cm16(T_view)), ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), _ptr(T_out), C.byref(I), _ptr(valid), _ptr(normals),
+                            _ptr(rec), len(rec), C.byref(nrec))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return {"T_view": T_out.reshape(4, 4).T.copy(), "info": _align_info(I), "valid": valid, "normals": normals, "record": rec[:nrec.value].copy()}
 
 
 def _carve_run(run, n):
@@ -1151,6 +1197,53 @@ class Context:
         self._chk(self.lib.ssm_render_compare(self.h, target, _ptr(depth), _ptr(sem), float(self.cfg.camera.scale if scale is None else scale), C.byref(P), C.byref(I), _ptr(cls)))
         info = {k: getattr(I, k) for k in RENDER_COMPARE_FIELDS}
         return (info, cls) if class_image else info
+
+    def align_view(self, depth, camera=None, **params):
+        """a view of dense alignment: the depth image goes to the device and its normal map is built there (ssm_align_view_create; params: the edge gate) -> an
+        opaque handle (align_view_free it)"""
+        depth = np.ascontiguousarray(depth, np.uint16)
+        h, w = depth.shape
+        cam = Camera(*camera) if camera is not None else self.cfg.camera
+        P = align_params(**params); v = C.c_void_p()
+        self._chk(self.lib.ssm_align_view_create(self.h, _ptr(depth), w, h, C.byref(cam), C.byref(P), C.byref(v)))
+        self._align_sizes = getattr(self, "_align_sizes", {})
+        self._align_sizes[v.value] = (w, h)
+        return v.value
+
+    def align_view_free(self, view):
+        self._align_sizes.pop(view, None)
+        self.lib.ssm_align_view_free(self.h, view)
+
+    def align_normals(self, view):
+        """the view's valid mask and normals as align_host gives them (ssm_debug_align_normals) -> (valid, normals)"""
+        w, h = self._align_sizes[view]
+        valid = np.zeros((h, w), np.uint8); normals = np.zeros((h, w, 4), np.float32)
+        self._chk(self.lib.ssm_debug_align_normals(self.h, view, _ptr(valid), _ptr(normals)))
+        return valid, normals
+
+    def align_record(self):
+        """the iterations of the context's last device alignment (ssm_debug_align_record): ALIGN_ITER_DTYPE entries"""
+        rec = np.zeros(ALIGN_MAX_ITERATIONS, ALIGN_ITER_DTYPE); n = C.c_int(0)
+        self._chk(self.lib.ssm_debug_align_record(self.h, _ptr(rec), len(rec), C.byref(n)))
+        return rec[:n.value].copy()
+
+    def align_points(self, view, T_view, clouds, T_clouds, **params):
+        """align_host's call through the device (ssm_align_points) -> {T_view, info}"""
+        keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+        P = align_params(**params); I = AlignInfo(); T_out = np.zeros(16)
+        self._chk(self.lib.ssm_align_points(self.h, view, _ptr(_cm16(T_view)), ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), _ptr(T_out), C.byref(I)))
+        return {"T_view": T_out.reshape(4, 4).T.copy(), "info": _align_info(I)}
+
+    def align_clouds(self, view, T_view, clouds, T_clouds, **params):
+        """device-resident clouds (backproject_dev's handles) at the poses T_clouds against the view (ssm_align_clouds); the clouds are not modified"""
+        m = len(clouds)
+        if len(T_clouds) != m:
+            raise ValueError("one pose per cloud")
+        arr = (C.c_void_p * max(m, 1))(*clouds)
+        Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+        P = align_params(**params); I = AlignInfo(); T_out = np.zeros(16)
+        self._chk(self.lib.ssm_align_clouds(self.h, view, _ptr(_cm16(T_view)), arr, _ptr(Tc), m, C.byref(P), _ptr(T_out), C.byref(I)))
+        return {"T_view": T_out.reshape(4, 4).T.copy(), "info": _align_info(I)}
 
     def backproject_fused(self, depth, rgb, sem, motion=None, T=None, camera=None, max_distance=None, area_thres=1000, overlay_thres=0.143, device=False):
         """generate_point_cloud with the fused mask (ssm_backproject_fused); device=True: backproject_dev's form, -> an opaque cloud handle (cloud_free it)"""

@@ -201,6 +201,17 @@ struct RenderWork {
     DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<unsigned long long> counts; PinBuf<unsigned long long> h_counts;
     DevBuf<ssm_point> in;
 };
+// a view of dense alignment (ssm_align.hip): a key-frame's depth image and its normal map (16 bytes per pixel) in device memory, its camera and edge gate
+struct ssm_align_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> normals; int w = 0, h = 0, device = 0; ssm_camera cam{}; double tol_abs = 0; int32_t tol_rel_ppm = 0; };
+// workspace of dense alignment for cap_m clouds and cap_b chunks of points: the table (AlignSeg[m], then the chunks' first clouds), one slot of sums per
+// iteration, the host-array call's staging, and the last device call's iterations (ssm_debug_align_record)
+struct AlignWork {
+    size_t cap_m = 0, cap_b = 0, in_cap = 0;
+    DevBuf<uint8_t> table; PinBuf<uint8_t> h_table;
+    DevBuf<unsigned long long> sums; PinBuf<unsigned long long> h_sums;
+    DevBuf<ssm_point> in;
+    std::vector<ssm_align_iter> record;
+};
 // workspace of free-space carving (ssm_carve.hip) for cap points in cap_m clouds; off: the last call's clouds as numbers of their first points (m + 1 entries), for
 // ssm_debug_carve_record
 struct CarveWork {
@@ -283,6 +294,7 @@ struct ssm_ctx {
     SorWork sor;                                             // statistical outlier removal: allocated by its first call, grown by the largest
     CarveWork carve;                                         // free-space carving: likewise
     RenderWork render;                                       // map rendering: likewise
+    AlignWork align;                                         // dense alignment: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;

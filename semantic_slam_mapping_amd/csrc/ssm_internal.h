@@ -262,6 +262,17 @@ hipError_t k_render(const ssm_renderc::Setup& S, const RenderSeg* seg, const int
 hipError_t k_render_compare(const uint16_t* rdepth, const uint8_t* rlabel, const uint16_t* depth, const uint8_t* sem, int64_t np, int64_t tol_abs, int64_t ppm,
                             uint8_t* cls, unsigned long long* counts, hipStream_t s);
 
+// dense alignment (kernels_align.hip; the arithmetic is include/ssm/align_core.h).  AlignSeg: one per cloud -- its points in device memory, the number of its
+// first USED point in the concatenation, how many of its points are used (every stride-th) and the 12 doubles of its relative pose.  blk: the cloud of each
+// chunk's first point (one per k_align_block() points).  k_align_normals fills a view's normal map (16 bytes per pixel); k_align_accumulate adds one iteration's
+// NSUM 64-bit sums under the increment E (12 doubles, host memory) to sums, which the caller has zeroed.  Both queue on s and wait for nothing.
+namespace ssm_alignc { struct Setup; }
+struct AlignSeg { const ssm_point* pts; int64_t off; int32_t n, stride; double M[12]; };
+int k_align_block();
+hipError_t k_align_normals(const uint16_t* depth, const ssm_alignc::Setup& S, void* normals, hipStream_t s);
+hipError_t k_align_accumulate(const ssm_alignc::Setup& S, const double* E, const AlignSeg* seg, const int32_t* blk, int64_t total, const uint16_t* depth,
+                              const void* normals, unsigned long long* sums, hipStream_t s);
+
 // pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);
 // op 1: linearise + assemble; op 2: factor and solve the view's envelope with `lambda`
 namespace ssm_pgc { struct View; }

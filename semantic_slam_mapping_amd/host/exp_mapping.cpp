@@ -34,6 +34,10 @@
 // rendered images are written there as PNG.  The summary line then carries `render_views V render_agree A render_in_front F render_behind B render_label_agree L
 // render_label_disagree D render_fnv H`: the views, the sums of those counts over them, and FNV-1a over every view's nine counts in key-frame order (the same in both
 // modes: it runs once, at the end).  Without the flag nothing of this runs and the line is as before.
+// `exp_mapping <parameters> --align` (or mapper_align=1): Mapper aligns every key-frame's depth image to the clouds of the mapper_align_window key-frames before it and
+// uses the corrected map pose from there on (dense alignment: include/ssm/mapper.h).  The summary line then carries `align_keyframes N align_accepted A
+// align_fnv H`: the key-frames aligned, the alignments accepted, and FNV-1a over every key-frame's status, iteration count, counts and the bytes of its correction D_j,
+// in key-frame order (the same in both modes: every key-frame is aligned exactly once).  Without the flag nothing of this runs and the line is as before.
 // `exp_mapping <parameters> --fuse-motion` (or motion_semantic_fuse=1; implies --moving, so it needs tracker_mode=stereo too): Mapper gates every key-frame's cloud with
 // the semantic-motion fusion of the frame's semantic image and its moving_mask (include/ssm/mapper.h) instead of the class mask alone.  The summary line
 // then carries `fused_keyframes K fused_confirmed C fused_added N fused_fnv H`: over the key-frames in order, the blobs confirmed as moving, the mask pixels they add to
@@ -140,6 +144,9 @@ int main(int argc, char** argv)
     bool carve = parameterReader.getData<int>("mapper_carve", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--carve") carve = true;
     if (carve) parameterReader.set("mapper_carve", "1");
+    bool align = parameterReader.getData<int>("mapper_align", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--align") align = true;
+    if (align) parameterReader.set("mapper_align", "1");
     bool render = parameterReader.getData<int>("mapper_render", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--render") {
         render = true;
@@ -398,6 +405,20 @@ int main(int argc, char** argv)
                 for (size_t k = 0; k < sizeof v; k++) { h ^= b[k]; h *= 0x100000001B3ull; }
             }
             cout << " carve_keyframes " << mapper.carvedViews() << " carve_tested " << tested << " carve_removed " << removed << " carve_fnv " << hex << h << dec;
+        }
+        if (align) {            // (the viewer thread aligned every key-frame before it ended)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before every key-frame was aligned" << endl; return 3; }
+            uint64_t h = 0xCBF29CE484222325ull;
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) {
+                ssm_align_info I{}; Eigen::Isometry3d D;
+                if (!mapper.alignInfoOf(kf, &I, &D)) { cerr << "exp_mapping: a key-frame was not aligned" << endl; return 3; }
+                const int64_t v[7] = {I.status, I.iterations, I.n_in, I.tested_first, I.inliers_first, I.tested_last, I.inliers_last};
+                const unsigned char* b = (const unsigned char*)v;
+                for (size_t k = 0; k < sizeof v; k++) { h ^= b[k]; h *= 0x100000001B3ull; }
+                b = (const unsigned char*)D.data();
+                for (size_t k = 0; k < 16 * sizeof(double); k++) { h ^= b[k]; h *= 0x100000001B3ull; }
+            }
+            cout << " align_keyframes " << mapper.alignedKeyframes() << " align_accepted " << mapper.acceptedAlignments() << " align_fnv " << hex << h << dec;
         }
         if (render) {           // (the viewer thread rendered every key-frame's view as it ended)
             if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before every view was rendered" << endl; return 3; }

@@ -152,6 +152,30 @@ int ssm_render_fetch(ssm_ctx*, const ssm_render_target* t, uint16_t* depth, uint
 }
 int ssm_render_compare(ssm_ctx*, ssm_render_target* t, const uint16_t* depth, const uint8_t* sem, double scale, const ssm_render_params* params, ssm_render_compare_info* info, uint8_t* cls)
 { return ssm_render_compare_host(t->depth.data(), t->label.data(), t->w, t->h, depth, sem, scale, params, info, cls); }
+// dense alignment (Mapper with mapper_align=1): a "view" is a host copy of the depth image, the linked host function in the device entry points' place
+struct ssm_align_view { std::vector<uint16_t> depth; int w, h; ssm_camera cam; double tol_abs; int32_t tol_rel_ppm; };
+int ssm_align_view_create(ssm_ctx*, const uint16_t* depth, int w, int h, const ssm_camera* cam, const ssm_align_params* params, ssm_align_view** out)
+{
+    if (w < 3 || h < 3) return SSM_E_INVAL;
+    ssm_align_params P; ssm_align_params_default(&P); if (params) P = *params;
+    ssm_align_view* v = new ssm_align_view(); v->depth.assign(depth, depth + (size_t)w * h); v->w = w; v->h = h; v->cam = *cam; v->tol_abs = P.tol_abs; v->tol_rel_ppm = P.tol_rel_ppm;
+    *out = v; return SSM_OK;
+}
+void ssm_align_view_free(ssm_ctx*, ssm_align_view* v) { delete v; }
+int ssm_align_points(ssm_ctx*, const ssm_align_view* v, const double* Tv, const ssm_point* const* pts, const int32_t* n, const double* Tc, int m, const ssm_align_params* params,
+                     double* T_out, ssm_align_info* info)
+{
+    ssm_align_params P; ssm_align_params_default(&P); if (params) P = *params;
+    P.tol_abs = v->tol_abs; P.tol_rel_ppm = v->tol_rel_ppm;
+    return ssm_align_host(v->depth.data(), v->w, v->h, &v->cam, Tv, pts, n, Tc, m, &P, T_out, info, nullptr, nullptr, nullptr, 0, nullptr);
+}
+int ssm_align_clouds(ssm_ctx* c, const ssm_align_view* v, const double* Tv, ssm_cloud* const* clouds, const double* Tc, int m, const ssm_align_params* params, double* T_out,
+                     ssm_align_info* info)
+{
+    std::vector<const ssm_point*> pts; std::vector<int32_t> n;
+    for (int k = 0; k < m; k++) { pts.push_back(clouds[k]->p.data()); n.push_back((int32_t)clouds[k]->p.size()); }
+    return ssm_align_points(c, v, Tv, pts.data(), n.data(), Tc, m, params, T_out, info);
+}
 int ssm_cloud_size(const ssm_cloud* cl) { return cl ? (int)cl->p.size() : 0; }
 void ssm_cloud_free(ssm_ctx*, ssm_cloud* cl) { delete cl; }
 int ssm_cloud_fetch(ssm_ctx*, const ssm_cloud* cl, const double*, ssm_point* out, int cap, int* n_out)
