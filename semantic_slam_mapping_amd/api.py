@@ -214,14 +214,15 @@ def _render_params(kw):
     return RenderParams(float(p["point_size"]), int(p["max_radius"]), 0, float(p["z_min"]), float(p["z_max"]), float(p["tol_abs"]), int(p["tol_rel_ppm"]), 0)
 
 
-def _render_clouds_args(clouds, T_clouds):
-    """host clouds -> (the arrays kept alive, pointer array, sizes, poses, m)"""
-    clouds = [_sor_points(c) for c in clouds]
+def _pack_clouds(clouds, T_clouds, host):
+    """a list of clouds and their poses as the ABI takes them: host arrays (host=True) -> (the arrays kept alive, pointer array, sizes, poses, m); device
+    handles -> (the handles, pointer array, None, poses, m).  The poses are m x 16 column-major doubles"""
+    clouds = [_sor_points(c) for c in clouds] if host else list(clouds)
     m = len(clouds)
     if len(T_clouds) != m:
         raise ValueError("one pose per cloud")
-    ptrs = (C.c_void_p * max(m, 1))(*[c.ctypes.data for c in clouds])
-    n = np.ascontiguousarray([len(c) for c in clouds] + ([] if m else [0]), np.int32)
+    ptrs = (C.c_void_p * max(m, 1))(*([c.ctypes.data for c in clouds] if host else clouds))
+    n = np.ascontiguousarray([len(c) for c in clouds] + ([] if m else [0]), np.int32) if host else None
     Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
     return clouds, ptrs, n, Tc, m
 
@@ -236,7 +237,7 @@ def _render_images(w, h, keys):
 def render_host(w, h, camera, T_view, clouds, T_clouds, keys=False, **params):
     """map rendering on the CPU (ssm_render_host, no GPU): the points of `clouds` (host arrays of POINT_DTYPE at the poses T_clouds) into the w x h view (camera =
     (cx, cy, fx, fy, scale), T_view) -> {depth, bgr, label, index, info}, with keys=True also the raw z-buffer"""
-    keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+    keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
     P = _render_params(params); I = RenderInfo(); cam = Camera(*camera)
     out = _render_images(int(w), int(h), keys) if w >= 1 and h >= 1 and w * h <= 1 << 26 else _render_images(1, 1, keys)
     lib = _lib.load()
@@ -315,7 +316,7 @@ def align_host(depth, camera, T_view, clouds, T_clouds, **params):
     if depth.ndim != 2:
         raise ValueError("a depth image is h x w")
     h, w = depth.shape
-    keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+    keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
     P = align_params(**params); I = AlignInfo(); cam = Camera(*camera)
     valid = np.zeros((h, w), np.uint8); normals = np.zeros((h, w, 4), np.float32); rec = np.zeros(ALIGN_MAX_ITERATIONS, ALIGN_ITER_DTYPE); nrec = C.c_int(0)
     T_out = np.zeros(16)
@@ -1113,10 +1114,8 @@ class Context:
 
     def carve(self, view, T_view, clouds, T_clouds, record=False, **params):
         """one view against device-resident clouds (backproject_dev's handles), which shrink in place (ssm_carve) -> the infos, or with record (infos, [{verdict, run}])"""
-        m = len(clouds)
         sizes = [self.cloud_size(cl) for cl in clouds]
-        arr = (C.c_void_p * max(m, 1))(*clouds)
-        Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+        _, arr, _, Tc, m = _pack_clouds(clouds, T_clouds, False)
         P = _carve_params(params); infos = (CarveInfo * max(m, 1))()
         self._chk(self.lib.ssm_carve(self.h, view, _ptr(_cm16(T_view)), arr, _ptr(Tc), m, C.byref(P), infos))
         out = [_carve_info(infos[k]) for k in range(m)]
@@ -1165,18 +1164,14 @@ class Context:
 
     def render_points(self, target, camera, T_view, clouds, T_clouds, keys=False, **params):
         """render_host's call through the device (ssm_render_points) -> {depth, bgr, label, index, info}, with keys=True also the raw z-buffer"""
-        keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+        keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
         P = _render_params(params); I = RenderInfo(); cam = Camera(*camera) if camera is not None else self.cfg.camera
         self._chk(self.lib.ssm_render_points(self.h, target, C.byref(cam), _ptr(_cm16(T_view)), ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), C.byref(I)))
         return self._render_result(target, I, keys)
 
     def render_clouds(self, target, camera, T_view, clouds, T_clouds, keys=False, **params):
         """device-resident clouds (backproject_dev's handles) at the poses T_clouds into the view (ssm_render_clouds); nothing is uploaded but the poses"""
-        m = len(clouds)
-        if len(T_clouds) != m:
-            raise ValueError("one pose per cloud")
-        arr = (C.c_void_p * max(m, 1))(*clouds)
-        Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+        _, arr, _, Tc, m = _pack_clouds(clouds, T_clouds, False)
         P = _render_params(params); I = RenderInfo(); cam = Camera(*camera) if camera is not None else self.cfg.camera
         self._chk(self.lib.ssm_render_clouds(self.h, target, C.byref(cam), _ptr(_cm16(T_view)), arr, _ptr(Tc), m, C.byref(P), C.byref(I)))
         return self._render_result(target, I, keys)
@@ -1229,18 +1224,14 @@ class Context:
 
     def align_points(self, view, T_view, clouds, T_clouds, **params):
         """align_host's call through the device (ssm_align_points) -> {T_view, info}"""
-        keep, ptrs, n, Tc, m = _render_clouds_args(clouds, T_clouds)
+        keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
         P = align_params(**params); I = AlignInfo(); T_out = np.zeros(16)
         self._chk(self.lib.ssm_align_points(self.h, view, _ptr(_cm16(T_view)), ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), _ptr(T_out), C.byref(I)))
         return {"T_view": T_out.reshape(4, 4).T.copy(), "info": _align_info(I)}
 
     def align_clouds(self, view, T_view, clouds, T_clouds, **params):
         """device-resident clouds (backproject_dev's handles) at the poses T_clouds against the view (ssm_align_clouds); the clouds are not modified"""
-        m = len(clouds)
-        if len(T_clouds) != m:
-            raise ValueError("one pose per cloud")
-        arr = (C.c_void_p * max(m, 1))(*clouds)
-        Tc = np.ascontiguousarray(np.stack([_cm16(T) for T in T_clouds]) if m else np.zeros((1, 16)))
+        _, arr, _, Tc, m = _pack_clouds(clouds, T_clouds, False)
         P = align_params(**params); I = AlignInfo(); T_out = np.zeros(16)
         self._chk(self.lib.ssm_align_clouds(self.h, view, _ptr(_cm16(T_view)), arr, _ptr(Tc), m, C.byref(P), _ptr(T_out), C.byref(I)))
         return {"T_view": T_out.reshape(4, 4).T.copy(), "info": _align_info(I)}

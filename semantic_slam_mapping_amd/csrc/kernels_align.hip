@@ -2,10 +2,8 @@
 // arithmetic is include/ssm/align_core.h, which the host function of ssm_align_host.cpp calls too.
 //
 // Normals: one thread per pixel, a block per 256 pixels of a row (the per-pixel kernels' row tiles), the four neighbours as plain loads.
-// Accumulate: one thread per point over the concatenation of the m (strided) clouds, with the segment table of kernels_carve.hip / kernels_render.hip: a table
-// gives each chunk of 256 points the cloud of its first point; when the whole chunk lies in that cloud (all but at most m - 1 chunks) the cloud's index, and with
-// it the 12 doubles of its relative pose, is uniform and comes through scalar loads; a chunk that a cloud boundary crosses takes the same code with a per-lane
-// cloud index.  The grid is persistent: at most ALIGN_MAX_BLOCKS blocks, each walking chunks blockIdx.x, + gridDim.x, ...  A lane keeps its 30 sums as 64-bit
+// Accumulate: one thread per point over the concatenation of the m (strided) clouds, found through the cloud-segment table (cloud_table.h) with chunks of 256
+// points as its blocks.  The grid is persistent: at most ALIGN_MAX_BLOCKS blocks, each walking chunks blockIdx.x, + gridDim.x, ...  A lane keeps its 30 sums as 64-bit
 // integers in registers over the whole walk; then the wave adds them by xor butterfly, the block through LDS, and 30 threads issue one 64-bit integer atomic
 // each.  The terms are integers (align_core.h to_units), so every order of addition gives the same bits: no floating-point atomic, no grid barrier, no block
 // waits for another.  Depth and normals are gathered with plain loads; E comes as a kernel argument.
@@ -32,7 +30,7 @@ align_normals_kernel(const uint16_t* __restrict__ depth, const Setup S, Normal* 
 }
 
 __global__ void __launch_bounds__(ALIGN_T)
-align_accumulate_kernel(const Setup S, const AlignE E, const AlignSeg* __restrict__ seg, const int32_t* __restrict__ blk, int64_t total, int64_t chunks,
+align_accumulate_kernel(const Setup S, const AlignE E, const CloudSeg* __restrict__ seg, const int32_t* __restrict__ blk, int64_t total, int64_t chunks,
                         const uint16_t* __restrict__ depth, const Normal* __restrict__ normals, unsigned long long* __restrict__ sums)
 {
     __shared__ int64_t part[ALIGN_W][NSUM];
@@ -46,8 +44,7 @@ align_accumulate_kernel(const Setup S, const AlignE E, const AlignSeg* __restric
         const int64_t last = min(total, (ch + 1) * ALIGN_T) - 1;
         const bool uniform = last < seg[k0].off + seg[k0].n;
         if (g < total) {
-            int k = k0;
-            if (!uniform) while (g >= seg[k].off + seg[k].n) k++;          // (ends: g < total = the last cloud's off + n; empty clouds are stepped over)
+            const int k = cloud_of<int64_t>(seg, k0, uniform, g);
             const ssm_point* p = seg[k].pts + (g - seg[k].off) * seg[k].stride;
             point_terms(p->x, p->y, p->z, seg[k].M, E.e, depth, normals, S, acc);
         }
@@ -76,7 +73,7 @@ hipError_t k_align_normals(const uint16_t* depth, const Setup& S, void* normals,
     return hipGetLastError();
 }
 // sums: NSUM 64-bit integers that the caller has zeroed
-hipError_t k_align_accumulate(const Setup& S, const double* E, const AlignSeg* seg, const int32_t* blk, int64_t total, const uint16_t* depth, const void* normals,
+hipError_t k_align_accumulate(const Setup& S, const double* E, const CloudSeg* seg, const int32_t* blk, int64_t total, const uint16_t* depth, const void* normals,
                               unsigned long long* sums, hipStream_t s)
 {
     if (total <= 0) return hipSuccess;

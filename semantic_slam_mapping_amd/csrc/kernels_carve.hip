@@ -1,12 +1,11 @@
 // kernels_carve.hip -- free-space carving of m clouds in device memory under one view: the verdicts, the run counters and the stable compaction
 // of points AND counters, per cloud.  The arithmetic is include/ssm/carve_core.h, which the host function of ssm_carve_host.cpp calls too.
 //
-// One thread per point over the concatenation of the m clouds.  A table gives each block the cloud of its first point; when the whole block lies in that cloud
-// (all but at most m - 1 blocks) the cloud's index, and with it the 12 doubles of its relative pose, is uniform and comes through scalar loads; a block that a
-// cloud boundary crosses takes the same code with a per-lane cloud index.  The view's depth image (0.6 - 0.9 MB) is read through plain uint16 loads and stays in
-// L2.  Verdict, counter and keep flag are made in registers; the kept are counted per block, one scan over the blocks of the whole concatenation gives every
-// block its offset, and the kept points and counters go to a scratch copy in that order -- a block's compacted output would land where EARLIER blocks still read
-// their input, so nothing is compacted in place -- from where the last kernel puts cloud k's share, which starts at base[k], back at the front of cloud k.
+// One thread per point over the concatenation of the m clouds, found through the cloud-segment table (cloud_table.h), here with 32-bit point numbers: a call
+// has 2^30 points at most.  The view's depth image (0.6 - 0.9 MB) is read through plain uint16 loads and stays in L2.  Verdict, counter and keep flag are
+// made in registers; the kept are counted per block, one scan over the blocks of the whole concatenation gives every block its offset, and the kept points and
+// counters go to a scratch copy in that order -- a block's compacted output would land where EARLIER blocks still read their input, so nothing is compacted in
+// place -- from where the last kernel puts cloud k's share, which starts at base[k], back at the front of cloud k.
 // Integer atomics only, and only for the info counters; no grid barrier, no block waits for another.
 #include "ssm_internal.h"
 #include "../../include/ssm/carve_core.h"
@@ -18,18 +17,7 @@ using namespace ssm_carvec;
 #define CARVE_W (CARVE_T / 64)
 int k_carve_block() { return CARVE_T; }
 
-// the cloud of point g of the concatenation (g < total).  k0: the cloud of the block's first point; uniform: the block's last point is in it too
-__device__ inline int carve_cloud_of(const CarveSeg* __restrict__ seg, int k0, bool uniform, int g)
-{
-    int k = k0;
-    if (!uniform) while (g >= seg[k].off + seg[k].n) k++;          // (ends: g < total = the last cloud's off + n; empty clouds are stepped over)
-    return k;
-}
-__device__ inline bool carve_block_uniform(const CarveSeg* __restrict__ seg, int k0, int total)
-{
-    const int last = min(total, (int)(blockIdx.x + 1) * CARVE_T) - 1;
-    return last < seg[k0].off + seg[k0].n;
-}
+__device__ inline bool carve_block_uniform(const CloudSeg* __restrict__ seg, int k0, int total) { return cloud_block_uniform<int>(seg, k0, (int)blockIdx.x * CARVE_T, CARVE_T, total); }
 
 __global__ void carve_init_kernel(int32_t* __restrict__ info, int m, uint32_t* __restrict__ block_cnt, int nb)
 {
@@ -38,7 +26,7 @@ __global__ void carve_init_kernel(int32_t* __restrict__ info, int m, uint32_t* _
     if (i == 0) block_cnt[nb] = 0;                                // the scan's last entry becomes the total
 }
 __global__ void __launch_bounds__(CARVE_T)
-carve_verdict_kernel(const uint16_t* __restrict__ depth, const Setup S, int min_votes, const CarveSeg* __restrict__ seg, const int32_t* __restrict__ blk, int total,
+carve_verdict_kernel(const uint16_t* __restrict__ depth, const Setup S, int min_votes, const CloudSeg* __restrict__ seg, const int32_t* __restrict__ blk, int total,
                      uint8_t* __restrict__ verdict, uint8_t* __restrict__ run_new, uint8_t* __restrict__ keep, uint32_t* __restrict__ block_cnt, int32_t* __restrict__ info)
 {
     __shared__ int cnt_s[CARVE_W];
@@ -48,8 +36,8 @@ carve_verdict_kernel(const uint16_t* __restrict__ depth, const Setup S, int min_
     const bool live = g < total;
     int k = k0, v = UNKNOWN; bool kp = false;
     if (live) {
-        k = carve_cloud_of(seg, k0, uniform, g);
-        const int local = g - seg[k].off;
+        k = cloud_of<int>(seg, k0, uniform, g);
+        const int local = g - (int)seg[k].off;
         const ssm_point* p = seg[k].pts + local;
         v = verdict_of(p->x, p->y, p->z, seg[k].M, depth, S);
         const uint8_t rn = run_after(seg[k].run[local], v);
@@ -78,7 +66,7 @@ carve_verdict_kernel(const uint16_t* __restrict__ depth, const Setup S, int min_
     if (threadIdx.x == 0) { int t = 0; for (int w = 0; w < CARVE_W; w++) t += cnt_s[w]; block_cnt[blockIdx.x] = (uint32_t)t; }
 }
 // per cloud: where its kept points start in the scratch copy, and the info fields that follow from the counts
-__global__ void carve_base_kernel(const CarveSeg* __restrict__ seg, int m, int32_t* __restrict__ info, uint32_t* __restrict__ base)
+__global__ void carve_base_kernel(const CloudSeg* __restrict__ seg, int m, int32_t* __restrict__ info, uint32_t* __restrict__ base)
 {
     if (blockIdx.x || threadIdx.x) return;
     uint32_t at = 0;
@@ -90,7 +78,7 @@ __global__ void carve_base_kernel(const CarveSeg* __restrict__ seg, int m, int32
 }
 // the stable move into the scratch copy: a kept point goes to its block's offset plus its rank inside the block, all 32 bytes, and its counter beside it
 __global__ void __launch_bounds__(CARVE_T)
-carve_compact_kernel(const CarveSeg* __restrict__ seg, const int32_t* __restrict__ blk, int total, const uint8_t* __restrict__ keep, const uint8_t* __restrict__ run_new,
+carve_compact_kernel(const CloudSeg* __restrict__ seg, const int32_t* __restrict__ blk, int total, const uint8_t* __restrict__ keep, const uint8_t* __restrict__ run_new,
                      const uint32_t* __restrict__ block_off, ssm_point* __restrict__ tmp_pts, uint8_t* __restrict__ tmp_run)
 {
     __shared__ int cnt_s[CARVE_W];
@@ -101,24 +89,24 @@ carve_compact_kernel(const CarveSeg* __restrict__ seg, const int32_t* __restrict
     __syncthreads();
     if (!kp) return;
     const int k0 = blk[blockIdx.x];
-    const int k = carve_cloud_of(seg, k0, carve_block_uniform(seg, k0, total), g);
+    const int k = cloud_of<int>(seg, k0, carve_block_uniform(seg, k0, total), g);
     uint32_t at = block_off[blockIdx.x] + (uint32_t)__popcll(b & (((unsigned long long)1 << lane) - 1));
     for (int w = 0; w < wave; w++) at += (uint32_t)cnt_s[w];
-    const uint4* src = reinterpret_cast<const uint4*>(seg[k].pts + (g - seg[k].off));
+    const uint4* src = reinterpret_cast<const uint4*>(seg[k].pts + (g - (int)seg[k].off));
     uint4* dst = reinterpret_cast<uint4*>(tmp_pts + at);
     dst[0] = src[0]; dst[1] = src[1];
     tmp_run[at] = run_new[g];
 }
 // back into the clouds: entry `local` of cloud k is entry base[k] + local of the scratch copy, for local below the cloud's kept count
 __global__ void __launch_bounds__(CARVE_T)
-carve_store_kernel(const CarveSeg* __restrict__ seg, const int32_t* __restrict__ blk, int total, const uint32_t* __restrict__ base,
+carve_store_kernel(const CloudSeg* __restrict__ seg, const int32_t* __restrict__ blk, int total, const uint32_t* __restrict__ base,
                    const ssm_point* __restrict__ tmp_pts, const uint8_t* __restrict__ tmp_run)
 {
     const int g = blockIdx.x * CARVE_T + threadIdx.x;
     if (g >= total) return;
     const int k0 = blk[blockIdx.x];
-    const int k = carve_cloud_of(seg, k0, carve_block_uniform(seg, k0, total), g);
-    const uint32_t local = (uint32_t)(g - seg[k].off), first = base[k];
+    const int k = cloud_of<int>(seg, k0, carve_block_uniform(seg, k0, total), g);
+    const uint32_t local = (uint32_t)(g - (int)seg[k].off), first = base[k];
     if (local >= base[k + 1] - first) return;
     const uint4* src = reinterpret_cast<const uint4*>(tmp_pts + first + local);
     uint4* dst = reinterpret_cast<uint4*>(seg[k].pts + local);

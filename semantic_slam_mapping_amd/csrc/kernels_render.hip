@@ -1,11 +1,9 @@
 // kernels_render.hip -- map rendering of m clouds in device memory into one pinhole view: the clear of the z-buffer, the splat, the resolve into
 // the four images, and the comparison with a frame.  The arithmetic is include/ssm/render_core.h, which the host functions of ssm_render_host.cpp call too.
 //
-// Splat: one thread per point over the concatenation of the m clouds, with the segment table of kernels_carve.hip: a table gives each block the cloud of its
-// first point; when the whole block lies in that cloud (all but at most m - 1 blocks) the cloud's index, and with it the 12 doubles of its relative pose, is
-// uniform and comes through scalar loads; a block that a cloud boundary crosses takes the same code with a per-lane cloud index.  A point offers its key
-// (quantised depth << 32 | index) to every pixel of its clipped footprint with a 64-bit integer atomicMin; the pixel keeps the minimum, so the result does not
-// depend on the order the points arrive in.  Resolve: one thread per pixel finds the winner's cloud by bisection of the table and gathers its colour and label.
+// Splat: one thread per point over the concatenation of the m clouds, found through the cloud-segment table (cloud_table.h).  A point offers its key (quantised
+// depth << 32 | index) to every pixel of its clipped footprint with a 64-bit integer atomicMin; the pixel keeps the minimum, so the result does not depend on the
+// order the points arrive in.  Resolve: one thread per pixel finds the winner's cloud by bisection of the table and gathers its colour and label.
 // Compare: one thread per pixel, the counts summed per wave by ballot, per block through LDS, then one 64-bit integer atomic per count and block.
 // Integer atomics only; no grid barrier, no block waits for another.
 #include "ssm_internal.h"
@@ -31,18 +29,16 @@ render_clear_kernel(unsigned long long* __restrict__ keys, int64_t np, int32_t* 
     if (i == 0) { info[0] = n_in; info[1] = 0; info[2] = 0; info[3] = 0; }
 }
 __global__ void __launch_bounds__(RENDER_T)
-render_splat_kernel(const Setup S, const RenderSeg* __restrict__ seg, const int32_t* __restrict__ blk, int64_t total, unsigned long long* __restrict__ keys,
+render_splat_kernel(const Setup S, const CloudSeg* __restrict__ seg, const int32_t* __restrict__ blk, int64_t total, unsigned long long* __restrict__ keys,
                     int32_t* __restrict__ info)
 {
     const int64_t g = (int64_t)blockIdx.x * RENDER_T + threadIdx.x;
     const int lane = threadIdx.x & 63;
     const int k0 = blk[blockIdx.x];
-    const int64_t last = min(total, ((int64_t)blockIdx.x + 1) * RENDER_T) - 1;
-    const bool uniform = last < seg[k0].off + seg[k0].n;
+    const bool uniform = cloud_block_uniform<int64_t>(seg, k0, (int64_t)blockIdx.x * RENDER_T, RENDER_T, total);
     bool vis = false;
     if (g < total) {
-        int k = k0;
-        if (!uniform) while (g >= seg[k].off + seg[k].n) k++;          // (ends: g < total = the last cloud's off + n; empty clouds are stepped over)
+        const int k = cloud_of<int64_t>(seg, k0, uniform, g);
         const ssm_point* p = seg[k].pts + (g - seg[k].off);
         Splat sp;
         vis = splat_of(p->x, p->y, p->z, seg[k].M, S, &sp);
@@ -63,7 +59,7 @@ render_splat_kernel(const Setup S, const RenderSeg* __restrict__ seg, const int3
     if (lane == 0 && c) atomicAdd(info + 1, c);
 }
 __global__ void __launch_bounds__(RENDER_T)
-render_resolve_kernel(const unsigned long long* __restrict__ keys, int64_t np, const RenderSeg* __restrict__ seg, int m, uint16_t* __restrict__ depth,
+render_resolve_kernel(const unsigned long long* __restrict__ keys, int64_t np, const CloudSeg* __restrict__ seg, int m, uint16_t* __restrict__ depth,
                       uint8_t* __restrict__ bgr, uint8_t* __restrict__ label, int32_t* __restrict__ index, int32_t* __restrict__ info)
 {
     const int64_t i = (int64_t)blockIdx.x * RENDER_T + threadIdx.x;
@@ -120,7 +116,7 @@ __global__ void render_counts_clear_kernel(unsigned long long* __restrict__ coun
 
 // ------------------------------------------------------------------ launchers
 static inline unsigned render_blocks(int64_t n) { return (unsigned)((n + RENDER_T - 1) / RENDER_T); }
-hipError_t k_render(const Setup& S, const RenderSeg* seg, const int32_t* blk, int m, int64_t total, const RenderImgs& T, int32_t* info, hipStream_t s)
+hipError_t k_render(const Setup& S, const CloudSeg* seg, const int32_t* blk, int m, int64_t total, const RenderImgs& T, int32_t* info, hipStream_t s)
 {
     const int64_t np = (int64_t)S.w * S.h;
     render_clear_kernel<<<render_blocks(np), RENDER_T, 0, s>>>(T.keys, np, info, (int32_t)(uint32_t)total);

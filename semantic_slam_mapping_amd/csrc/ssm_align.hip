@@ -1,28 +1,15 @@
 // ssm_align.hip -- the device path of dense alignment behind the C ABI.  DESIGN.md s.18 is the contract.  A view is one upload of the depth image and one launch
-// for its normal map.  An alignment is one upload of a small table (the clouds' pointers, sizes, strides and relative poses -- worked out on the host by
-// carve_core.h's rel_pose, the same 12 doubles the host function uses -- and each chunk's first cloud) and one clear of the sums' slots; then every iteration is
-// ONE launch of kernels_align.hip on the main stream (E travels as a kernel argument), one download of its slot of 30 integers and one wait.  The solve and the
-// stopping rules are align_drive of ssm_align_host.cpp, the same function the host path runs.  The table, the slots and the staging of the host-array call
-// belong to the context (AlignWork) and grow with the largest call.
+// for its normal map.  An alignment is one upload of the cloud table (cloud_table.h; the relative poses are worked out on the host by carve_core.h's rel_pose,
+// the same 12 doubles the host function uses) and one clear of the sums' slots; then every iteration is ONE launch of kernels_align.hip on the main stream (E
+// travels as a kernel argument), one download of its slot of 30 integers and one wait.  The solve and the stopping rules are align_drive of ssm_align_host.cpp,
+// the same function the host path runs.  The slots belong to the context (AlignWork), and so do the table and the staging of the host-array call
+// (CloudTableWork), which grow with the largest call.
 #include "ssm_ctx.h"
 #include "ssm_host.h"
 using namespace ssm_alignc;
 
 enum { SLOT = 32 };          // 64-bit words per iteration's slot (NSUM of them used)
 
-static int align_reserve(ssm_ctx* c, size_t m, size_t nb)
-{
-    AlignWork& W = c->align;
-    if (m <= W.cap_m && nb <= W.cap_b && W.sums) return SSM_OK;
-    HIPCHK(c, hipStreamSynchronize(c->main.stream));
-    const size_t mm = std::max(std::max(m, W.cap_m), (size_t)8), bb = std::max(std::max(nb, W.cap_b), (size_t)1024);
-    W.cap_m = 0; W.cap_b = 0;
-    const size_t bytes = mm * sizeof(AlignSeg) + bb * 4;
-    DALLOC(c, W.table, bytes); DALLOC(c, W.h_table, bytes);
-    DALLOC(c, W.sums, (size_t)MAX_ITERATIONS * SLOT); DALLOC(c, W.h_sums, (size_t)MAX_ITERATIONS * SLOT);
-    W.cap_m = mm; W.cap_b = bb;
-    return SSM_OK;
-}
 // what every alignment call checks first
 static int align_begin(ssm_ctx* c, const ssm_align_view* v, const double* T_view, const ssm_align_params* params, ssm_align_params* P, Setup* S)
 {
@@ -34,30 +21,22 @@ static int align_begin(ssm_ctx* c, const ssm_align_view* v, const double* T_view
     return r;
 }
 // segs: pts, n (points used), stride and M filled by the caller; everything from the table's upload to the last iteration's wait
-static int align_run(ssm_ctx* c, const ssm_align_view* v, const Setup& S, const ssm_align_params& P, const double* T_view, std::vector<AlignSeg>& segs, int64_t total,
+static int align_run(ssm_ctx* c, const ssm_align_view* v, const Setup& S, const ssm_align_params& P, const double* T_view, std::vector<CloudSeg>& segs,
                      double* T_view_out, ssm_align_info* info)
 {
     AlignWork& W = c->align; hipStream_t s = c->main.stream;
-    const int m = (int)segs.size();
-    const int64_t T = k_align_block(), nb = (total + T - 1) / T;
     W.record.clear();
-    { const int r = align_reserve(c, (size_t)m, (size_t)nb); if (r) return r; }
-    AlignSeg* hs = reinterpret_cast<AlignSeg*>((uint8_t*)W.h_table);
-    int32_t* hb = reinterpret_cast<int32_t*>((uint8_t*)W.h_table + (size_t)m * sizeof(AlignSeg));
-    int64_t at = 0;
-    for (int k = 0; k < m; k++) { segs[k].off = at; hs[k] = segs[k]; at += segs[k].n; }
-    for (int64_t b = 0, k = 0; b < nb; b++) { while (b * T >= segs[k].off + segs[k].n) k++; hb[b] = (int32_t)k; }
-    const size_t bytes = (size_t)m * sizeof(AlignSeg) + (size_t)nb * 4;
-    if (bytes) HIPCHK(c, hipMemcpyAsync(W.table, W.h_table, bytes, hipMemcpyHostToDevice, s));
+    if (!W.sums) { DALLOC(c, W.h_sums, (size_t)MAX_ITERATIONS * SLOT); DALLOC(c, W.sums, (size_t)MAX_ITERATIONS * SLOT); }
+    CloudTable t;
+    { const int r = cloud_table_upload(c, segs, k_align_block(), &t); if (r) return r; }
     HIPCHK(c, hipMemsetAsync(W.sums, 0, (size_t)P.max_iterations * SLOT * 8, s));
-    const AlignSeg* d_seg = W.table.as<AlignSeg>();
-    const int32_t* d_blk = reinterpret_cast<const int32_t*>((uint8_t*)W.table + (size_t)m * sizeof(AlignSeg));
     int it = 0, hip_rc = SSM_OK;
-    const int r = align_drive(P, total, T_view, [&](const double* E, int64_t* sums) -> int {
+    // (every iteration ends with a wait, and there is at least one: a return of align_drive without an error leaves nothing in flight)
+    const int r = align_drive(P, t.total, T_view, [&](const double* E, int64_t* sums) -> int {
         unsigned long long* slot = W.sums + (size_t)it * SLOT; unsigned long long* h_slot = W.h_sums + (size_t)it * SLOT;
         it++;
         prof_begin(c, s, "align_accumulate");
-        hipError_t e = k_align_accumulate(S, E, d_seg, d_blk, total, v->depth, v->normals, slot, s);
+        hipError_t e = k_align_accumulate(S, E, t.seg, t.blk, t.total, v->depth, v->normals, slot, s);
         prof_end(c, s);
         if (e == hipSuccess) e = hipMemcpyAsync(h_slot, slot, NSUM * 8, hipMemcpyDeviceToHost, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -65,6 +44,7 @@ static int align_run(ssm_ctx* c, const ssm_align_view* v, const Setup& S, const 
         memcpy(sums, h_slot, NSUM * 8);
         return SSM_OK;
     }, T_view_out, info, &W.record);
+    if (r == SSM_OK) t.in_flight = nullptr;
     return r ? (hip_rc ? hip_rc : r) : SSM_OK;
 }
 
@@ -104,25 +84,11 @@ extern "C" int ssm_align_points(ssm_ctx* c, const ssm_align_view* v, const doubl
     ssm_align_params P; Setup S;
     { const int r = align_begin(c, v, T_view, params, &P, &S); if (r) return r; }
     if (m < 0 || (m && (!pts || !n || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    int64_t total = 0, raw = 0;
+    int64_t total = 0;
     { const int r = align_total_check(c, S, n, m, P.stride, &total); if (r) return r; }
-    std::vector<AlignSeg> segs((size_t)m);
-    for (int k = 0; k < m; k++) {
-        if (n[k] && !pts[k]) FAIL(c, SSM_E_INVAL, "null argument");
-        for (int j = 0; j < k; j++) if (n[k] && n[j] && pts[j] == pts[k]) FAIL(c, SSM_E_INVAL, "align: the same cloud twice");
-        { const int r = carve_pose_check(c, T_clouds + 16 * k); if (r) return r; }
-        ssm_carvec::rel_pose(T_view, T_clouds + 16 * k, segs[k].M);
-        raw += n[k];
-    }
-    AlignWork& W = c->align; hipStream_t s = c->main.stream;
-    const size_t nn = (size_t)std::max<int64_t>(raw, 1);
-    if (nn > W.in_cap) { HIPCHK(c, hipStreamSynchronize(s)); W.in_cap = 0; DALLOC(c, W.in, nn); W.in_cap = nn; }
-    size_t at = 0;
-    for (int k = 0; k < m; k++) {
-        if (n[k]) HIPCHK(c, hipMemcpyAsync(W.in + at, pts[k], (size_t)n[k] * sizeof(ssm_point), hipMemcpyHostToDevice, s));
-        segs[k].pts = W.in + at; segs[k].n = (int32_t)(((int64_t)n[k] + P.stride - 1) / P.stride); segs[k].stride = P.stride; at += (size_t)n[k];
-    }
-    return align_run(c, v, S, P, T_view, segs, total, T_view_out, info);
+    std::vector<CloudSeg> segs;
+    { const int r = cloud_list(c, "align: the same cloud twice", T_view, nullptr, pts, n, T_clouds, m, P.stride, segs); if (r) return r; }
+    return align_run(c, v, S, P, T_view, segs, T_view_out, info);
 }
 extern "C" int ssm_align_clouds(ssm_ctx* c, const ssm_align_view* v, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
                                 const ssm_align_params* params, double* T_view_out, ssm_align_info* info)
@@ -132,21 +98,12 @@ extern "C" int ssm_align_clouds(ssm_ctx* c, const ssm_align_view* v, const doubl
     ssm_align_params P; Setup S;
     { const int r = align_begin(c, v, T_view, params, &P, &S); if (r) return r; }
     if (m < 0 || (m && (!clouds || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    std::vector<AlignSeg> segs((size_t)m);
-    std::vector<int32_t> n((size_t)m);
-    for (int k = 0; k < m; k++) {
-        const ssm_cloud* cl = clouds[k];
-        if (!cl) FAIL(c, SSM_E_INVAL, "null argument");
-        if (cl->device != c->device) FAIL(c, SSM_E_INVAL, "cloud of another device");
-        for (int j = 0; j < k; j++) if (clouds[j] == cl) FAIL(c, SSM_E_INVAL, "align: the same cloud twice");
-        { const int r = carve_pose_check(c, T_clouds + 16 * k); if (r) return r; }
-        ssm_carvec::rel_pose(T_view, T_clouds + 16 * k, segs[k].M);
-        n[k] = cl->n;
-        segs[k].pts = cl->d; segs[k].n = (int32_t)(((int64_t)cl->n + P.stride - 1) / P.stride); segs[k].stride = P.stride;
-    }
+    std::vector<CloudSeg> segs;
+    { const int r = cloud_list(c, "align: the same cloud twice", T_view, clouds, nullptr, nullptr, T_clouds, m, P.stride, segs); if (r) return r; }
+    std::vector<int32_t> n; for (int k = 0; k < m; k++) n.push_back(clouds[k]->n);
     int64_t total = 0;
     { const int r = align_total_check(c, S, n.data(), m, P.stride, &total); if (r) return r; }
-    return align_run(c, v, S, P, T_view, segs, total, T_view_out, info);
+    return align_run(c, v, S, P, T_view, segs, T_view_out, info);
 }
 extern "C" int ssm_debug_align_normals(ssm_ctx* c, const ssm_align_view* v, uint8_t* valid, float* normals)
 {

@@ -34,10 +34,8 @@ int align_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_align
 }
 int align_total_check(ssm_ctx* c, const Setup& S, const int32_t* n, int m, int stride, int64_t* total)
 {
-    int64_t t = 0;
-    for (int k = 0; k < m; k++) { if (n[k] < 0) return host_fail(c, SSM_E_INVAL, "align: a negative point count"); t += ((int64_t)n[k] + stride - 1) / stride; }
-    if (!sums_fit(S, t)) return host_fail(c, SSM_E_INVAL, "align: the sums of this many points at this z_max, dist_max and field of view could reach 2^62");
-    *total = t;
+    if (!cloud_count(n, m, stride, total)) return host_fail(c, SSM_E_INVAL, "align: a negative point count");
+    if (!sums_fit(S, *total)) return host_fail(c, SSM_E_INVAL, "align: the sums of this many points at this z_max, dist_max and field of view could reach 2^62");
     return SSM_OK;
 }
 

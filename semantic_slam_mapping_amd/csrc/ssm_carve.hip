@@ -1,20 +1,19 @@
-// ssm_carve.hip -- the device path of free-space carving behind the C ABI.  DESIGN.md s.16 is the contract.  A call is one upload of a small table (the clouds'
-// pointers, sizes and relative poses -- worked out on the host by carve_core.h's rel_pose, the same 12 doubles the host function uses -- and each block's first
-// cloud), the launches of kernels_carve.hip on the main stream, one download of the m infos and ONE wait.  The workspaces belong to the context (CarveWork) and
-// grow with the largest call; a cloud's run counters belong to the cloud.  The host function, the defaults and the argument check are ssm_carve_host.cpp.
+// ssm_carve.hip -- the device path of free-space carving behind the C ABI.  DESIGN.md s.16 is the contract.  A call is one upload of the cloud table (cloud_table.h;
+// the relative poses are worked out on the host by carve_core.h's rel_pose, the same 12 doubles the host function uses), the launches of kernels_carve.hip on the
+// main stream, one download of the m infos and ONE wait.  The workspaces belong to the context (CarveWork; the table: CloudTableWork) and grow with the largest
+// call; a cloud's run counters belong to the cloud.  The host function, the defaults and the argument check are ssm_carve_host.cpp.
 #include "ssm_ctx.h"
 #include "ssm_host.h"
 using namespace ssm_carvec;
 
-static int carve_reserve(ssm_ctx* c, int total, int m)
+// the verdict / keep / scan scratch for `total` points in m clouds (the cloud table is the context's: ssm_cloud_list.hip)
+static int carve_scratch(ssm_ctx* c, int total, int m)
 {
     CarveWork& W = c->carve;
     if (total <= W.cap && m <= W.cap_m) return SSM_OK;
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
     const size_t n = (size_t)std::max(std::max(total, W.cap), 1024), mm = (size_t)std::max(std::max(m, W.cap_m), 8), nb = (n + k_carve_block() - 1) / k_carve_block() + 1;
     W.cap = 0; W.cap_m = 0;
-    W.table_bytes = mm * sizeof(CarveSeg) + nb * 4;
-    DALLOC(c, W.table, W.table_bytes); DALLOC(c, W.h_table, W.table_bytes);
     DALLOC(c, W.info, mm * 8); DALLOC(c, W.h_info, mm * 8); DALLOC(c, W.base, mm + 1);
     DALLOC(c, W.block_cnt, nb); DALLOC(c, W.block_off, nb);
     DALLOC(c, W.verdict, n); DALLOC(c, W.run_new, n); DALLOC(c, W.keep, n); DALLOC(c, W.tmp_run, n); DALLOC(c, W.tmp_pts, n);
@@ -23,31 +22,26 @@ static int carve_reserve(ssm_ctx* c, int total, int m)
     return SSM_OK;
 }
 // segs: pts, run, n and M filled by the caller; everything from the table's upload to the call's wait
-static int carve_run(ssm_ctx* c, const uint16_t* d_depth, const Setup& S, int min_votes, std::vector<CarveSeg>& segs, ssm_carve_info* infos)
+static int carve_run(ssm_ctx* c, const uint16_t* d_depth, const Setup& S, int min_votes, std::vector<CloudSeg>& segs, ssm_carve_info* infos)
 {
     CarveWork& W = c->carve; hipStream_t s = c->main.stream;
     const int m = (int)segs.size();
     int64_t total64 = 0;
-    for (const CarveSeg& g : segs) total64 += g.n;
+    for (const CloudSeg& g : segs) total64 += g.n;
     if (total64 > ((int64_t)1 << 30)) FAIL(c, SSM_E_CAPACITY, "carve: more than 2^30 points in one call");
     const int total = (int)total64;
     W.off.assign(1, 0);
-    { const int r = carve_reserve(c, total, m); if (r) return r; }
-    CarveSeg* hs = reinterpret_cast<CarveSeg*>((uint8_t*)W.h_table);
-    int32_t* hb = reinterpret_cast<int32_t*>((uint8_t*)W.h_table + (size_t)m * sizeof(CarveSeg));
-    const int T = k_carve_block(), nb = (total + T - 1) / T;
-    int at = 0;
-    for (int k = 0; k < m; k++) { segs[k].off = at; hs[k] = segs[k]; at += segs[k].n; W.off.push_back(at); }
-    for (int b = 0, k = 0; b < nb; b++) { while (b * T >= segs[k].off + segs[k].n) k++; hb[b] = k; }
-    const size_t bytes = (size_t)m * sizeof(CarveSeg) + (size_t)nb * 4;
-    HIPCHK(c, hipMemcpyAsync(W.table, W.h_table, bytes, hipMemcpyHostToDevice, s));
-    const CarveBufs B{W.table.as<CarveSeg>(), reinterpret_cast<const int32_t*>((uint8_t*)W.table + (size_t)m * sizeof(CarveSeg)), W.info, W.base, W.verdict, W.run_new, W.keep,
-                      W.tmp_run, W.block_cnt, W.block_off, W.tmp_pts, W.tmp, W.tmp_bytes};
+    { const int r = carve_scratch(c, total, m); if (r) return r; }
+    CloudTable t;
+    { const int r = cloud_table_upload(c, segs, k_carve_block(), &t); if (r) return r; }
+    for (const CloudSeg& g : segs) W.off.push_back((int)(g.off + g.n));
+    const CarveBufs B{t.seg, t.blk, W.info, W.base, W.verdict, W.run_new, W.keep, W.tmp_run, W.block_cnt, W.block_off, W.tmp_pts, W.tmp, W.tmp_bytes};
     prof_begin(c, s, "carve");
     HIPCHK(c, k_carve(d_depth, S, min_votes, m, total, B, s));
     prof_end(c, s);
     HIPCHK(c, hipMemcpyAsync(W.h_info, W.info, (size_t)m * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
+    t.in_flight = nullptr;
     static_assert(sizeof(ssm_carve_info) == 32, "info is eight ints");
     memcpy(infos, (const int32_t*)W.h_info, (size_t)m * 32);
     return SSM_OK;
@@ -84,15 +78,8 @@ extern "C" int ssm_carve(ssm_ctx* c, const ssm_carve_view* v, const double* T_vi
     ssm_carve_params P; ssm_carve_params_default(&P); if (params) P = *params;
     Setup S;
     { int r = carve_check(c, v->w, v->h, &v->cam, P, &S); if (!r) r = carve_pose_check(c, T_view); if (r) return r; }
-    std::vector<CarveSeg> segs((size_t)m);
-    for (int k = 0; k < m; k++) {
-        ssm_cloud* cl = clouds[k];
-        if (!cl) FAIL(c, SSM_E_INVAL, "null argument");
-        if (cl->device != c->device) FAIL(c, SSM_E_INVAL, "cloud of another device");
-        for (int j = 0; j < k; j++) if (clouds[j] == cl) FAIL(c, SSM_E_INVAL, "carve: the same cloud twice in one call");
-        { const int r = carve_pose_check(c, T_clouds + 16 * k); if (r) return r; }
-        rel_pose(T_view, T_clouds + 16 * k, segs[k].M);
-    }
+    std::vector<CloudSeg> segs;
+    { const int r = cloud_list(c, "carve: the same cloud twice in one call", T_view, clouds, nullptr, nullptr, T_clouds, m, 1, segs); if (r) return r; }
     c->carve.off.assign(1, 0);
     if (m == 0) return SSM_OK;
     // a cloud's counters are made by its first view, zero; they become the cloud's only when the whole call has succeeded (a cloud that has counters is refused by
@@ -104,7 +91,7 @@ extern "C" int ssm_carve(ssm_ctx* c, const ssm_carve_view* v, const double* T_vi
             DALLOC(c, fresh[k], std::max(cl->n, 1));
             HIPCHK(c, hipMemsetAsync(fresh[k], 0, (size_t)std::max(cl->n, 1), c->main.stream));
         }
-        segs[k].pts = cl->d; segs[k].run = cl->run ? (uint8_t*)cl->run : (uint8_t*)fresh[k]; segs[k].n = cl->n; segs[k].off = 0;
+        segs[k].run = cl->run ? (uint8_t*)cl->run : (uint8_t*)fresh[k];
     }
     std::vector<ssm_carve_info> I((size_t)m);
     {
@@ -128,16 +115,15 @@ extern "C" int ssm_carve_points(ssm_ctx* c, const uint16_t* depth, int w, int h,
     *n_out = 0;
     CarveWork& W = c->carve; hipStream_t s = c->main.stream;
     const size_t np = (size_t)w * h, nn = (size_t)std::max(n, 1);
-    if (np > W.depth_cap || nn > W.in_cap) HIPCHK(c, hipStreamSynchronize(s));
+    if (np > W.depth_cap || nn > W.run_cap) HIPCHK(c, hipStreamSynchronize(s));
     if (np > W.depth_cap) { W.depth_cap = 0; DALLOC(c, W.depth, np); W.depth_cap = np; }
-    if (nn > W.in_cap) { W.in_cap = 0; DALLOC(c, W.in, nn); DALLOC(c, W.run_in, nn); W.in_cap = nn; }
+    if (nn > W.run_cap) { W.run_cap = 0; DALLOC(c, W.run_in, nn); W.run_cap = nn; }
     HIPCHK(c, hipMemcpyAsync(W.depth, depth, np * 2, hipMemcpyHostToDevice, s));
-    if (n) HIPCHK(c, hipMemcpyAsync(W.in, pts, (size_t)n * sizeof(ssm_point), hipMemcpyHostToDevice, s));
     if (n && run_inout) HIPCHK(c, hipMemcpyAsync(W.run_in, run_inout, (size_t)n, hipMemcpyHostToDevice, s));
     else HIPCHK(c, hipMemsetAsync(W.run_in, 0, nn, s));
-    std::vector<CarveSeg> segs(1);
-    segs[0].pts = W.in; segs[0].run = W.run_in; segs[0].n = n; segs[0].off = 0;
-    rel_pose(T_view, T_cloud, segs[0].M);
+    std::vector<CloudSeg> segs;          // the one cloud, staged like any list of host arrays
+    { const int r = cloud_list(c, nullptr, T_view, nullptr, &pts, &n, T_cloud, 1, 1, segs); if (r) return r; }
+    segs[0].run = W.run_in;
     ssm_carve_info I{};
     { const int r = carve_run(c, W.depth, S, P.min_votes, segs, &I); if (r) return r; }
     *n_out = I.n_kept;
@@ -145,7 +131,7 @@ extern "C" int ssm_carve_points(ssm_ctx* c, const uint16_t* depth, int w, int h,
     if (I.n_kept > cap) FAIL(c, SSM_E_CAPACITY, "point buffer too small (need " + std::to_string(I.n_kept) + ")");
     if (I.n_kept == 0) return SSM_OK;
     if (!out) FAIL(c, SSM_E_INVAL, "null argument");
-    HIPCHK(c, hipMemcpyAsync(out, W.in, (size_t)I.n_kept * sizeof(ssm_point), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(out, c->clouds.in, (size_t)I.n_kept * sizeof(ssm_point), hipMemcpyDeviceToHost, s));
     if (run_inout) HIPCHK(c, hipMemcpyAsync(run_inout, W.run_in, (size_t)I.n_kept, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     return SSM_OK;

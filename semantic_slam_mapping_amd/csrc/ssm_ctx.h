@@ -193,34 +193,26 @@ struct ssm_render_target {
     DevBuf<unsigned long long> keys; DevBuf<uint16_t> depth; DevBuf<uint8_t> bgr, label; DevBuf<int32_t> index;
     DevBuf<uint16_t> f_depth; DevBuf<uint8_t> f_sem, cls;
 };
-// workspace of map rendering for cap_m clouds and cap_b blocks of points: the table (RenderSeg[m], then the blocks' first clouds), the info, the comparison's
-// counts and the host-array call's staging
-struct RenderWork {
-    size_t cap_m = 0, cap_b = 0, in_cap = 0;
-    DevBuf<uint8_t> table; PinBuf<uint8_t> h_table;
-    DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<unsigned long long> counts; PinBuf<unsigned long long> h_counts;
-    DevBuf<ssm_point> in;
-};
+// workspace of map rendering: the info and the comparison's counts
+struct RenderWork { DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<unsigned long long> counts; PinBuf<unsigned long long> h_counts; };
 // a view of dense alignment (ssm_align.hip): a key-frame's depth image and its normal map (16 bytes per pixel) in device memory, its camera and edge gate
 struct ssm_align_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> normals; int w = 0, h = 0, device = 0; ssm_camera cam{}; double tol_abs = 0; int32_t tol_rel_ppm = 0; };
-// workspace of dense alignment for cap_m clouds and cap_b chunks of points: the table (AlignSeg[m], then the chunks' first clouds), one slot of sums per
-// iteration, the host-array call's staging, and the last device call's iterations (ssm_debug_align_record)
-struct AlignWork {
-    size_t cap_m = 0, cap_b = 0, in_cap = 0;
-    DevBuf<uint8_t> table; PinBuf<uint8_t> h_table;
-    DevBuf<unsigned long long> sums; PinBuf<unsigned long long> h_sums;
-    DevBuf<ssm_point> in;
-    std::vector<ssm_align_iter> record;
-};
+// workspace of dense alignment: one slot of sums per iteration, and the last device call's iterations (ssm_debug_align_record)
+struct AlignWork { DevBuf<unsigned long long> sums; PinBuf<unsigned long long> h_sums; std::vector<ssm_align_iter> record; };
 // workspace of free-space carving (ssm_carve.hip) for cap points in cap_m clouds; off: the last call's clouds as numbers of their first points (m + 1 entries), for
 // ssm_debug_carve_record
 struct CarveWork {
     int cap = 0, cap_m = 0; std::vector<int> off;
-    DevBuf<uint8_t> table; PinBuf<uint8_t> h_table; size_t table_bytes = 0;      // CarveSeg[m], then the blocks' first clouds
     DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<uint32_t> base, block_cnt, block_off; DevBuf<uint8_t> verdict, run_new, keep, tmp_run, tmp; size_t tmp_bytes = 0;
     DevBuf<ssm_point> tmp_pts;
-    DevBuf<ssm_point> in; DevBuf<uint8_t> run_in; DevBuf<uint16_t> depth; size_t in_cap = 0, depth_cap = 0;      // the host-array call's staging
+    DevBuf<uint8_t> run_in; DevBuf<uint16_t> depth; size_t run_cap = 0, depth_cap = 0;      // the host-array call's staging beside CloudTableWork::in
 };
+// The cloud-segment table (cloud_table.h) of the context, for carving, rendering and alignment alike: CloudSeg[m], then the blocks' first clouds, in device memory
+// and its pinned mirror, cap bytes each; in: the staging of the points of a host-array call (in_cap points).  Grown by the largest call (ssm_cloud_list.hip).
+struct CloudTableWork { size_t cap = 0, in_cap = 0; DevBuf<uint8_t> table; PinBuf<uint8_t> h_table; DevBuf<ssm_point> in; };
+// A call's table on the device, as the launchers take it.  in_flight: the stream its upload was queued on, until the call has waited there and says so (null) --
+// a return on an error path in between waits here, so the pinned mirror is never rewritten under a copy in flight
+struct CloudTable { const CloudSeg* seg; const int32_t* blk; int64_t total, blocks; hipStream_t in_flight = nullptr; ~CloudTable() { if (in_flight) (void)hipStreamSynchronize(in_flight); } };
 // workspace of the statistical outlier removal (ssm_sor.hip) for cap points; n: the last call, for ssm_debug_sor_record
 struct SorWork {
     int cap = 0, n = 0;
@@ -295,6 +287,7 @@ struct ssm_ctx {
     CarveWork carve;                                         // free-space carving: likewise
     RenderWork render;                                       // map rendering: likewise
     AlignWork align;                                         // dense alignment: likewise
+    CloudTableWork clouds;                                   // the cloud table and host-array staging of the three: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling
     bool profiling = false;
@@ -323,6 +316,12 @@ template <class T, bool Pinned> int DevBuf<T, Pinned>::alloc_bytes(ssm_ctx* c, s
     DevBufLive::buffers++; (Pinned ? DevBufLive::pinned_bytes : DevBufLive::device_bytes) += bytes;
     return SSM_OK;
 }
+// ssm_cloud_list.hip.  cloud_list: a call's device clouds or, with clouds null, host arrays (pts, n: counts the caller has checked; queued into the context's
+// staging) -> segs with pts, n (the points used: every stride-th), stride and M filled.  Per cloud, in this order: null, a cloud of another device, the same cloud
+// twice (twice_msg; null: allowed), its pose.  cloud_table_upload: numbers segs, builds the table for blocks of T points and queues its upload -> *t
+SSM_HIDDEN int cloud_list(ssm_ctx* c, const char* twice_msg, const double* T_view, ssm_cloud* const* clouds, const ssm_point* const* pts, const int32_t* n,
+                          const double* T_clouds, int m, int stride, std::vector<CloudSeg>& segs);
+SSM_HIDDEN int cloud_table_upload(ssm_ctx* c, std::vector<CloudSeg>& segs, int T, CloudTable* t);
 // ssm_abi.hip
 extern SSM_HIDDEN thread_local std::string g_create_err;
 SSM_HIDDEN int ensure_scratch(ssm_ctx* c, size_t bytes, DevBuf<uint8_t>* buf = nullptr);     // buf: c->d_scratch (the default) or c->d_scratch2

@@ -1,4 +1,4 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_track_host.cpp:
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_cloud_table.cpp, ssm_track_host.cpp:
 // plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units; ssm_orb_plan.cpp and ssm_map_plan.cpp are host-only sources with headers of their own.  Those sources are compiled once and LINKED into libssm_hip.so, into the
 // CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
 // defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
@@ -14,6 +14,7 @@
 #include "../../include/ssm/align_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
+#include "cloud_table.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -94,6 +95,12 @@ SSM_HIDDEN int mf_check(ssm_ctx* c, int n, int w, int h, size_t stride);        
 // ---------------------------------------------------------------- statistical outlier removal (ssm_sor_host.cpp)
 SSM_HIDDEN int sor_check(ssm_ctx* c, int n, const ssm_sor_params& P);          // the arguments a call may have (host function and device entry points alike)
 SSM_HIDDEN int sor_off_grid(ssm_ctx* c);                                       // SSM_E_INVAL with the message of a mean distance off the statistics grid
+
+// ---------------------------------------------------------------- the cloud-segment table (ssm_cloud_table.cpp; cloud_table.h)
+// seg: m records with n (the points used) filled -> every off; blk (null: not wanted): the cloud of each block of T points' first point; -> the points, *blocks
+SSM_HIDDEN int64_t cloud_table_build(CloudSeg* seg, int m, int T, int32_t* blk, int64_t* blocks);
+// the points a host-array call uses: the sum of ceil(n[k] / stride) -> *total; false: a negative count.  The bound on the sum and the messages are the stage's
+SSM_HIDDEN bool cloud_count(const int32_t* n, int m, int stride, int64_t* total);
 
 // ---------------------------------------------------------------- free-space carving (ssm_carve_host.cpp)
 // the arguments a call may have (host function and device entry points alike); S: what the view's size and camera and the parameters become for carve_core.h

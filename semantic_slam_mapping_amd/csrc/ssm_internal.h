@@ -5,6 +5,7 @@
 #include <vector>
 #include "../../include/ssm_hip.h"
 #include "ssm_orb_plan.h"      // the ORB geometry, the fused pyramid's plan types and the planner: HIP-free
+#include "cloud_table.h"       // CloudSeg and the device look-ups of carving, rendering and alignment
 
 #define SSM_VOX_EMPTY ((int64_t)-1)
 // Layout of one buffer that several regions share.  take<T>(count) starts a region of count T at the next multiple of `align` and returns its byte offset;
@@ -234,16 +235,14 @@ hipError_t k_sor_level(const ssm_point* pts, int n, int nf, const float lo[3], d
 hipError_t k_sor_stats(const ssm_point* pts, int n, const SorBufs& B, hipStream_t s);
 hipError_t k_sor_compact(const ssm_point* pts, int n, double threshold, int too_few, const SorBufs& B, ssm_point* out, hipStream_t s);
 
-// free-space carving (kernels_carve.hip; the arithmetic is include/ssm/carve_core.h): one view against m clouds whose points are numbered through, `total` in all.
-// CarveSeg: one per cloud -- its points and run counters in device memory, the number of its first point, its size and the 12 doubles of its relative pose.
-// CarveBufs: seg (m), blk (the cloud of each block's first point: one per k_carve_block() points), info (m ssm_carve_info, as 8 ints), base (m + 1: where a
-// cloud's kept points start in the scratch copy), verdict / run_new / keep / tmp_run (total bytes each), block_cnt / block_off (blocks + 1), tmp_pts (total),
-// tmp: k_carve_tmp_bytes(total) for rocPRIM.  k_carve queues everything on s and waits for nothing; afterwards the clouds hold their kept points and counters
-// at the front, info[k] is complete, and verdict / run_new are every point's verdict and counter before the compaction.
+// free-space carving (kernels_carve.hip; the arithmetic is include/ssm/carve_core.h): one view against m clouds whose points are numbered through, `total` in all
+// (2^30 at most).  CarveBufs: seg (m) and blk, the cloud table (cloud_table.h) with blocks of k_carve_block() points, info (m ssm_carve_info, as 8 ints), base
+// (m + 1: where a cloud's kept points start in the scratch copy), verdict / run_new / keep / tmp_run (total bytes each), block_cnt / block_off (blocks + 1),
+// tmp_pts (total), tmp: k_carve_tmp_bytes(total) for rocPRIM.  k_carve queues everything on s and waits for nothing; afterwards the clouds hold their kept
+// points and counters at the front, info[k] is complete, and verdict / run_new are every point's verdict and counter before the compaction.
 namespace ssm_carvec { struct Setup; }
-struct CarveSeg { ssm_point* pts; uint8_t* run; int32_t off, n; double M[12]; };
 struct CarveBufs {
-    const CarveSeg* seg; const int32_t* blk; int32_t* info; uint32_t* base; uint8_t *verdict, *run_new, *keep, *tmp_run; uint32_t *block_cnt, *block_off; ssm_point* tmp_pts;
+    const CloudSeg* seg; const int32_t* blk; int32_t* info; uint32_t* base; uint8_t *verdict, *run_new, *keep, *tmp_run; uint32_t *block_cnt, *block_off; ssm_point* tmp_pts;
     void* tmp; size_t tmp_bytes;
 };
 int k_carve_block();
@@ -251,26 +250,23 @@ size_t k_carve_tmp_bytes(int total);
 hipError_t k_carve(const uint16_t* depth, const ssm_carvec::Setup& S, int min_votes, int m, int total, const CarveBufs& B, hipStream_t s);
 
 // map rendering (kernels_render.hip; the arithmetic is include/ssm/render_core.h): m clouds whose points are numbered through, `total` in all (below 2^32), into a
-// w x h z-buffer of 64-bit keys.  RenderSeg: one per cloud -- its points in device memory, the number of its first point, its size and the 12 doubles of its
-// relative pose.  blk: the cloud of each block's first point (one per k_render_block() points).  info: 4 ints (ssm_render_info).  k_render queues the clear, the
-// splat and the resolve on s and waits for nothing; k_render_compare the comparison (counts: 9 x int64 as ssm_render_compare_info, cleared by the call).
+// w x h z-buffer of 64-bit keys.  seg, blk: the cloud table (cloud_table.h) with blocks of k_render_block() points.  info: 4 ints (ssm_render_info).  k_render
+// queues the clear, the splat and the resolve on s and waits for nothing; k_render_compare the comparison (counts: 9 x int64 as ssm_render_compare_info, cleared
+// by the call).
 namespace ssm_renderc { struct Setup; }
-struct RenderSeg { const ssm_point* pts; int64_t off; int32_t n, pad; double M[12]; };
 struct RenderImgs { unsigned long long* keys; uint16_t* depth; uint8_t* bgr; uint8_t* label; int32_t* index; };
 int k_render_block();
-hipError_t k_render(const ssm_renderc::Setup& S, const RenderSeg* seg, const int32_t* blk, int m, int64_t total, const RenderImgs& T, int32_t* info, hipStream_t s);
+hipError_t k_render(const ssm_renderc::Setup& S, const CloudSeg* seg, const int32_t* blk, int m, int64_t total, const RenderImgs& T, int32_t* info, hipStream_t s);
 hipError_t k_render_compare(const uint16_t* rdepth, const uint8_t* rlabel, const uint16_t* depth, const uint8_t* sem, int64_t np, int64_t tol_abs, int64_t ppm,
                             uint8_t* cls, unsigned long long* counts, hipStream_t s);
 
-// dense alignment (kernels_align.hip; the arithmetic is include/ssm/align_core.h).  AlignSeg: one per cloud -- its points in device memory, the number of its
-// first USED point in the concatenation, how many of its points are used (every stride-th) and the 12 doubles of its relative pose.  blk: the cloud of each
-// chunk's first point (one per k_align_block() points).  k_align_normals fills a view's normal map (16 bytes per pixel); k_align_accumulate adds one iteration's
-// NSUM 64-bit sums under the increment E (12 doubles, host memory) to sums, which the caller has zeroed.  Both queue on s and wait for nothing.
+// dense alignment (kernels_align.hip; the arithmetic is include/ssm/align_core.h).  seg, blk: the cloud table (cloud_table.h) of the points USED (every stride-th
+// of a cloud), with chunks of k_align_block() points as its blocks.  k_align_normals fills a view's normal map (16 bytes per pixel); k_align_accumulate adds one
+// iteration's NSUM 64-bit sums under the increment E (12 doubles, host memory) to sums, which the caller has zeroed.  Both queue on s and wait for nothing.
 namespace ssm_alignc { struct Setup; }
-struct AlignSeg { const ssm_point* pts; int64_t off; int32_t n, stride; double M[12]; };
 int k_align_block();
 hipError_t k_align_normals(const uint16_t* depth, const ssm_alignc::Setup& S, void* normals, hipStream_t s);
-hipError_t k_align_accumulate(const ssm_alignc::Setup& S, const double* E, const AlignSeg* seg, const int32_t* blk, int64_t total, const uint16_t* depth,
+hipError_t k_align_accumulate(const ssm_alignc::Setup& S, const double* E, const CloudSeg* seg, const int32_t* blk, int64_t total, const uint16_t* depth,
                               const void* normals, unsigned long long* sums, hipStream_t s);
 
 // pose-graph optimiser (kernels_pgo.hip; the arithmetic is include/ssm/pgo_core.h): n views in device memory, one 1024-thread block each.  op 0: optimize(iterations);

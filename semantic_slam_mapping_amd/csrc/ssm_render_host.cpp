@@ -46,10 +46,8 @@ int render_compare_check(ssm_ctx* c, const ssm_render_params& P, double scale, i
 }
 int render_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total)
 {
-    int64_t t = 0;
-    for (int k = 0; k < m; k++) { if (n[k] < 0) return host_fail(c, SSM_E_INVAL, "render: a negative point count"); t += n[k]; }
-    if (t >= ((int64_t)1 << 32)) return host_fail(c, SSM_E_INVAL, "render: 2^32 points or more in one call");
-    *total = t;
+    if (!cloud_count(n, m, 1, total)) return host_fail(c, SSM_E_INVAL, "render: a negative point count");
+    if (*total >= ((int64_t)1 << 32)) return host_fail(c, SSM_E_INVAL, "render: 2^32 points or more in one call");
     return SSM_OK;
 }
 
