@@ -1,6 +1,6 @@
 // match_bench -- the MFMA matcher (kernels_match.hip) alone on random descriptors: time per 250-frame launch, with the ablation switches of
 // MM_ABLATE compiled in (-DMM_ABLATE=n: 1 no key tracking, 2 no LDS staging / barrier, 4 no train prefetch, 8 no MFMA) to see where the time goes.
-// Build (repo root): hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off -fno-honor-nans -Iinclude -Isemantic_slam_mapping_amd/csrc [-DMM_ABLATE=n] scripts/ubench/match_bench.hip -o scripts/ubench/bin/match_bench_n
+// Build (repo root): hipcc -O3 --offload-arch=gfx950 -std=c++17 -ffp-contract=off -fno-honor-nans -Iinclude -Isemantic_slam_mapping_amd/csrc [-DMM_ABLATE=n] [-DMM_VPM=v: VALU asked for behind each MFMA] scripts/ubench/match_bench.hip -o scripts/ubench/bin/match_bench_n
 #include "kernels_match.hip"
 #include <cstdio>
 #include <vector>
@@ -22,11 +22,11 @@ int main(int argc, char** argv)
     float best = 1e9f, sum = 0;
     for (int it = 0; it < 12; it++) {
         hipEventRecord(e0, 0);
-        match_mfma_kernel<<<8 * fpx * R * qblocks, 256, 0, 0>>>(eq, et, dn, 0, n, R, R, capT, qblocks, fpx, knn);
+        match_mfma_kernel<<<8 * fpx * R * qblocks, 256, 0, 0>>>(eq, et, dn, 0, n, R, R, capT, qblocks, fpx, match_key_exp(capT), knn);
         hipEventRecord(e1, 0); CK(hipEventSynchronize(e1));
         float ms; hipEventElapsedTime(&ms, e0, e1); if (it >= 2) { best = ms < best ? ms : best; sum += ms; }
     }
     const double mf = (double)n * R * 4 * 4 * 32 * 2 * MM_KS;      // MFMAs per launch
-    printf("MM_ABLATE=%d  best %.1f us  mean %.1f us  (%.3f us/frame)   MFMA issue at 32 cycles, 2.4 GHz: %.1f us\n", MM_ABLATE, best * 1e3, sum / 10 * 1e3, best * 1e3 / n, mf * 32 / 1024 / 2.4e9 * 1e6);
+    printf("MM_ABLATE=%d MM_VPM=%d  best %.1f us  mean %.1f us  (%.3f us/frame)   MFMA issue at 32 cycles, 2.4 GHz: %.1f us\n", MM_ABLATE, MM_VPM, best * 1e3, sum / 10 * 1e3, best * 1e3 / n, mf * 32 / 1024 / 2.4e9 * 1e6);
     return 0;
 }

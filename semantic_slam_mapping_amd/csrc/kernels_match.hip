@@ -7,6 +7,7 @@
 //     descriptors staged in LDS (32 B each, read back as wave-wide broadcasts), every lane owns query descriptors in VGPRs, distance = 8 x (v_xor + v_bcnt
 //     accumulate), matches compacted in ascending queryIdx with wave ballots.
 #include "ssm_internal.h"
+#include "match_keys.h"
 
 #define MT 512           // threads per block; each lane owns 2 queries -> 1024 queries per pass
 #define TCH 1024         // train descriptors staged per chunk (32 KiB)
@@ -173,15 +174,25 @@ hipError_t k_match_seq(const uint8_t* desc, const int32_t* nkp, int f0, int n, i
 
 // ------------------------------------------------------------------ the matcher on the matrix cores (sequence path)
 // The Hamming distance matrix of two descriptor sets IS a matrix product: with the query bits expanded to q = -1 / +1 (bit set / clear) and the
-// train bits to t = +16 / -16, sum_k q_k t_k = 16 (H - (256 - H)) = 32 H - 4096.  The elements are FP4 (E2M1: +-1.0 are the nibbles 0x2 / 0xA; the
-// train side's 16 is its block scale 2^4) and the product runs on v_mfma_scale_f32_32x32x64_f8f6f4: 4 K-steps per 256-bit descriptor at the cycles
-// of a bf16 32x32x16, half the matrix time and half the operand bytes of the i8 form (v_mfma_i32_32x32x32_i8, 8 K-steps) this kernel started with;
-// every partial sum is an integer of magnitude <= 4096 + 31, exact in the f32 accumulator whatever the summation order.  The accumulator is not
-// started at zero but at C[row][col] = 4096 + row, so that a finished 32 x 32 tile holds 32 H + (train index inside the tile): a key whose order is
-// "smaller distance first, equal distances by the lower trainIdx", i.e. the strict '<' scan of oracle/match.c, with no VALU work to build it -- and
-// as the keys are non-negative floats, their BIT PATTERNS order like the values: the VALU keeps the two smallest with unsigned integer min / max on
-// the raw registers, and only a tile's two winners are converted (v_cvt_u32_f32), widened to (H << 16 | trainIdx) and merged into the running
-// pair.  Bit-exact with the VALU matcher above.
+// train bits to t = +2^e / -2^e, sum_k q_k t_k = 2^e (H - (256 - H)) = 2^(e+1) H - 2^(e+8).  The elements are FP4 (E2M1: +-1.0 are the nibbles
+// 0x2 / 0xA; the train side's 2^e is its block scale, E8M0 127 + e) and the product runs on v_mfma_scale_f32_32x32x64_f8f6f4: 4 K-steps per 256-bit
+// descriptor at the cycles of a bf16 32x32x16, half the matrix time and half the operand bytes of the i8 form (v_mfma_i32_32x32x32_i8, 8 K-steps)
+// this kernel started with.  The launcher chooses e from the row length (match_keys.h): the smallest with 2^(e+1) >= capT, 9 for rows of 1024.
+// The accumulator is not started at zero but at C[row][col] = 2^(e+8) + row, so that a finished 32 x 32 tile T holds
+//     2^(e+1) H + (train index inside the tile) = key - 32 T,      key = 2^(e+1) H + trainIdx  (the GLOBAL train index: it fits below 2^(e+1)),
+// a key whose order is "smaller distance first, equal distances by the lower trainIdx", i.e. the strict '<' scan of oracle/match.c, with no VALU
+// work to build it.  Every partial sum is an integer of magnitude <= 512 * 2^e + 31, exact in the f32 accumulator whatever the summation order for
+// e <= 14, i.e. capT <= 32768 (longer rows: the callers take the VALU matcher).
+// ONE running pair l0 <= l1 of floats per accumulator lives through the whole tile loop, in the frame of the tile being tracked: before tile T is
+// looked at, 32 is subtracted from both (2 instructions), so the pair always holds key - 32 T and the tile's values compare with it as they are.
+// Nothing is converted or widened per tile.  The shifted values are integers below 2^24 in magnitude and MAY BE NEGATIVE (H = 0 in tile 0, seen
+// from tile 31, is row - 992): the compares are signed float min / med3, never integer compares of the bit patterns.  Two new values x, y per update:
+//     l1' = min(med3(x, y, l0), l1),   l0' = min3(x, y, l0)       (3 instructions per two values)
+// -- the second smallest of {x, y, l0, l1} is min(second smallest of {x, y, l0}, l1), because l1 >= l0 >= min3(x, y, l0), and the second smallest of
+// three is their median.  Equal keys do not occur for one query (the trainIdx differs).  The pair starts at, and the last tile's padded rows are
+// masked with, SSM_MATCH_KEY_BIG: finite, above every key, unchanged by the shift.  The epilogue merges the two lane halves in floats, adds
+// 32 (ntile - 1) back, converts the two winners (v_cvt_u32_f32, once per query) and splits them at bit e + 1 into the record (H << 16 | trainIdx).
+// Bit-exact with the VALU matcher above.
 //
 // Layout of an expanded descriptor row (one frame): capT = cap rounded up to 32 descriptors, 128 B each, stored per tile of 32 descriptors in MFMA
 // fragment order [K-step s: 4][lane half h: 2][descriptor r: 32][16 B] -- lane (h, r) of a wave takes the 32 nibbles k = 64 s + 32 h .. + 31 of
@@ -198,6 +209,9 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 #define MM_TILE (32 * MM_DB)            // bytes of one expanded 32-descriptor tile
 #ifndef MM_ABLATE
 #define MM_ABLATE 0                     // scripts/ubench/match_bench.hip only (wrong results): 1 no key tracking, 2 no LDS staging / barrier, 4 no train prefetch, 8 no MFMA
+#endif
+#ifndef MM_VPM
+#define MM_VPM 7                        // VALU instructions the scheduler is asked to put behind each MFMA: a tile's tracking compiles to 44 for 8 MFMAs (5 .. 8 measure the same)
 #endif
 
 __global__ void __launch_bounds__(256)
@@ -225,25 +239,24 @@ match_expand_kernel(const uint8_t* __restrict__ desc, const int32_t* __restrict_
     *reinterpret_cast<uint4*>(et + o) = make_uint4(t[0], t[1], t[2], t[3]);
 }
 
-// the two smallest of a finished tile (keys 32 H + row), widened and merged into the running pair g0 <= g1 of keys (H << 16 | trainIdx).
-// Compiler-visible instructions only (v_min_f32 / v_med3_f32; the Makefile builds this file with -fno-honor-nans, otherwise every operand is
-// canonicalised by an extra v_max first): the compiler then places the wait states an MFMA result needs before its first VALU read, and the
-// scheduler can interleave these instructions with the next tile's MFMAs.
-__device__ __forceinline__ void mm_merge2(uint32_t& a0, uint32_t& a1, uint32_t b0, uint32_t b1)     // (a0 <= a1), (b0 <= b1) -> the two smallest of the four
+// A finished tile's 16 values of a lane (keys - 32 T) folded into the running pair l0 <= l1 (see above): the pair moves into the tile's frame, then takes the
+// values two at a time -- 2 + 8 x 3 instructions.  Compiler-visible instructions only (v_min3_f32 / v_med3_f32 / v_min_f32; the Makefile builds this file
+// with -fno-honor-nans, otherwise every operand is canonicalised by an extra v_max first and no min3 is formed): the compiler then places the wait states
+// an MFMA result needs before its first VALU read, and the scheduler can interleave these instructions with the next tile's MFMAs.
+__device__ __forceinline__ void mm_merge2(float& a0, float& a1, float b0, float b1)     // (a0 <= a1), (b0 <= b1) -> the two smallest of the four
 {
-    const uint32_t m = max(a0, b0);
-    a0 = min(a0, b0);
-    a1 = min(min(m, a1), b1);
+    const float m = __builtin_fmaxf(a0, b0);
+    a0 = __builtin_fminf(a0, b0);
+    a1 = __builtin_fminf(__builtin_fminf(m, a1), b1);
 }
-__device__ __forceinline__ void mm_track(const v16f& acc, uint32_t t32, uint32_t& g0, uint32_t& g1)
+__device__ __forceinline__ void mm_track(const v16f& acc, float& l0, float& l1)
 {
-    // the two smallest of 16 non-negative floats by the sequential form: (l0, l1) <- (min(x, l0), med3(x, l0, l1)), 2 instructions per value
-    float l0 = __builtin_fminf(acc[0], acc[1]), l1 = __builtin_fmaxf(acc[0], acc[1]);
+    l0 -= 32.0f; l1 -= 32.0f;
 #pragma unroll
-    for (int i = 2; i < 16; i++) { l1 = __builtin_amdgcn_fmed3f(acc[i], l0, l1); l0 = __builtin_fminf(acc[i], l0); }
-    const uint32_t k0 = (uint32_t)l0, k1 = (uint32_t)l1;               // v_cvt_u32_f32 (a masked row's 2^20 widens to distance 0x8000)
-    const uint32_t G0 = ((k0 >> 5) << 16) | ((k0 & 31u) | t32), G1 = ((k1 >> 5) << 16) | ((k1 & 31u) | t32);
-    mm_merge2(g0, g1, G0, G1);
+    for (int i = 0; i < 16; i += 2) {
+        l1 = __builtin_fminf(__builtin_amdgcn_fmed3f(acc[i], acc[i + 1], l0), l1);
+        l0 = __builtin_fminf(__builtin_fminf(acc[i], acc[i + 1]), l0);
+    }
 }
 
 // Block (frame, ref r, query block qb): queries [256 qb, +256) of reference frame `ref` against every descriptor of the current frame.
@@ -253,7 +266,7 @@ __device__ __forceinline__ void mm_track(const v16f& acc, uint32_t t32, uint32_t
 // (with the frame as the fast grid index the kernel moved 1.6 GB per 250 frames and was memory bound at half the matrix rate).
 __global__ void __launch_bounds__(256, 2)
 match_mfma_kernel(const uint8_t* __restrict__ eq, const uint8_t* __restrict__ et, const int32_t* __restrict__ nkp,
-                  int f0, int n, int R, int hist, int capT, int qblocks, int frames_per_xcd, uint2* __restrict__ knn)
+                  int f0, int n, int R, int hist, int capT, int qblocks, int frames_per_xcd, int e, uint2* __restrict__ knn)
 {
     __shared__ __attribute__((aligned(16))) uint4 ring0[MM_TILE / 16];       // the ring as four objects: the compiler then knows that a DMA into one
     __shared__ __attribute__((aligned(16))) uint4 ring1[MM_TILE / 16];       // slot does not alias the fragment reads of another
@@ -281,11 +294,12 @@ match_mfma_kernel(const uint8_t* __restrict__ eq, const uint8_t* __restrict__ et
                 b[u][s] = v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w};
             }
     }
-    v16f cc;                                                            // C of every tile: 4096 + the train row inside the tile
+    v16f cc;                                                            // C of every tile: 2^(e+8) + the train row inside the tile
 #pragma unroll
-    for (int i = 0; i < 16; i++) cc[i] = (float)(4096 + (i & 3) + 8 * (i >> 2) + 4 * h);
+    for (int i = 0; i < 16; i++) cc[i] = (float)(match_key_c0(e) + (i & 3) + 8 * (i >> 2) + 4 * h);
+    const int scale_t = (127 + e) * 0x01010101;                         // the train block scale 2^e as E8M0
     const int ntile = (nt + 31) >> 5;
-    uint32_t g0[2] = {0xFFFFFFFFu, 0xFFFFFFFFu}, g1[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+    float l0[2] = {SSM_MATCH_KEY_BIG, SSM_MATCH_KEY_BIG}, l1[2] = {SSM_MATCH_KEY_BIG, SSM_MATCH_KEY_BIG};      // the running pair of each accumulator
     // Train tiles go global -> LDS by LDS-DMA (no staging registers, no ds_write) through a ring of four 4 KB slots, up to four tiles ahead of the MFMAs:
     // with a register-staged double buffer the L2 latency of the next tile was exposed at every barrier and the kernel ran at half the matrix
     // rate.  Every thread issues exactly one DMA instruction per tile (clamped to the last tile past the end: same bytes, a slot nobody reads),
@@ -302,10 +316,10 @@ match_mfma_kernel(const uint8_t* __restrict__ eq, const uint8_t* __restrict__ et
 #pragma unroll
         for (int s = 0; s < MM_KS; s++) { const uint4 v = buf[s * 64 + lane]; a[s] = v4i{(int)v.x, (int)v.y, (int)v.z, (int)v.w}; }
     };
-    // the 8 MFMAs of a tile whose fragments are in registers, into (x0, x1): A = train nibbles with block scale 2^4 (E8M0 131), B = query nibbles, scale 1 (127)
-    auto mfma4 = [](const v4i& a, const v4i& bq, const v16f& c) {
+    // the 8 MFMAs of a tile whose fragments are in registers, into (x0, x1): A = train nibbles with block scale 2^e, B = query nibbles, scale 1 (127)
+    auto mfma4 = [scale_t](const v4i& a, const v4i& bq, const v16f& c) {
         const v8i a8 = {a[0], a[1], a[2], a[3], 0, 0, 0, 0}, b8 = {bq[0], bq[1], bq[2], bq[3], 0, 0, 0, 0};          // FP4 operands are the low four registers
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, 0x83838383, 0, 0x7F7F7F7F);
+        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a8, b8, c, 4, 4, 0, scale_t, 0, 0x7F7F7F7F);
     };
     auto issue = [&](const v4i (&a)[MM_KS], v16f& x0, v16f& x1) {
         if (MM_ABLATE & 8) { x0 = cc; x1 = cc; for (int s = 0; s < MM_KS; s++) { x0[s] += (float)a[s][0]; x1[s] += (float)a[s][1]; } return; }
@@ -320,16 +334,16 @@ match_mfma_kernel(const uint8_t* __restrict__ eq, const uint8_t* __restrict__ et
     // the MFMAs of a tile are issued first and the key tracking of the tile before it (VALU only, other registers) runs under them
     auto interleave = [&]() {
 #pragma unroll
-        for (int i = 0; i < 2 * MM_KS; i++) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 12, 0); }
+        for (int i = 0; i < 2 * MM_KS; i++) { __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, MM_VPM, 0); }
     };
     auto track = [&](const v16f& x0, const v16f& x1, int T) {
-        if (MM_ABLATE & 1) { g0[0] = min(g0[0], __float_as_uint(x0[0])); g0[1] = min(g0[1], __float_as_uint(x1[0])); return; }
-        mm_track(x0, (uint32_t)T << 5, g0[0], g1[0]); mm_track(x1, (uint32_t)T << 5, g0[1], g1[1]);
+        if (MM_ABLATE & 1) { l0[0] = __builtin_fminf(l0[0], x0[0]); l0[1] = __builtin_fminf(l0[1], x1[0]); return; }
+        mm_track(x0, l0[0], l1[0]); mm_track(x1, l0[1], l1[1]);
     };
     auto track_last = [&](v16f x0, v16f x1, int T) {                    // the last tile: its padded train rows (>= nt) never win
         const int valid = nt - T * 32;
 #pragma unroll
-        for (int i = 0; i < 16; i++) if ((i & 3) + 8 * (i >> 2) + 4 * h >= valid) { x0[i] = 1048576.0f; x1[i] = 1048576.0f; }       // a key no descriptor reaches (and finite: this file is built with -fno-honor-nans)
+        for (int i = 0; i < 16; i++) if ((i & 3) + 8 * (i >> 2) + 4 * h >= valid) { x0[i] = SSM_MATCH_KEY_BIG; x1[i] = SSM_MATCH_KEY_BIG; }       // a key no descriptor reaches (and finite: this file is built with -fno-honor-nans)
         track(x0, x1, T);
     };
     // Step T: tile T + 1 has landed (vmcnt(2): the DMAs of T + 2 and T + 3 stay in flight) and this wave holds the fragments of tile T
@@ -365,15 +379,14 @@ match_mfma_kernel(const uint8_t* __restrict__ eq, const uint8_t* __restrict__ et
     if ((ntile - 1) & 1) track_last(B0, B1, ntile - 1); else track_last(A0, A1, ntile - 1);
     __builtin_amdgcn_s_waitcnt(0x0070);                                 // the surplus DMA and fragment reads of the tail are done before the block's LDS is released
     // the lane halves hold different train rows of the same query: merge lane l with lane l ^ 32, then lanes 0..31 write accumulator 0's
-    // queries and lanes 32..63 accumulator 1's
+    // queries and lanes 32..63 accumulator 1's.  The pair is in the last tile's frame: back to keys, one conversion per winner (nt >= 2: both are
+    // real descriptors), split at bit e + 1 into (H << 16 | trainIdx)
 #pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const uint32_t o0 = __shfl_xor(g0[u], 32), o1 = __shfl_xor(g1[u], 32);
-        const uint32_t m = max(g0[u], o0);
-        g0[u] = min(g0[u], o0);
-        g1[u] = min(min(m, g1[u]), o1);
-    }
-    const uint32_t k0 = h ? g0[1] : g0[0], k1 = h ? g1[1] : g1[0];
+    for (int u = 0; u < 2; u++) mm_merge2(l0[u], l1[u], __shfl_xor(l0[u], 32), __shfl_xor(l1[u], 32));
+    const float back = (float)(32 * (ntile - 1));
+    const uint32_t c0 = (uint32_t)((h ? l0[1] : l0[0]) + back), c1 = (uint32_t)((h ? l1[1] : l1[0]) + back);
+    const uint32_t imask = (2u << e) - 1u;
+    const uint32_t k0 = ((c0 >> (e + 1)) << 16) | (c0 & imask), k1 = ((c1 >> (e + 1)) << 16) | (c1 & imask);
     const int qi = q0 + lane;                                            // lane 32 + j: column j of accumulator 1 = query q0 + 32 + j
     const int slot = f * R + r;
     if (qi < nq) knn[(size_t)slot * capT + qi] = make_uint2(k0, k1);
@@ -420,11 +433,12 @@ hipError_t k_match_expand(const uint8_t* desc, const int32_t* nkp, int row0, int
     return hipGetLastError();
 }
 hipError_t k_match_seq_mfma(const uint8_t* eq, const uint8_t* et, const int32_t* nkp, int f0, int n, int R, int hist, double ratio, int cap, int capT,
-                            void* knn, ssm_dmatch* out, int32_t* nout, hipStream_t s)
+                            int e, void* knn, ssm_dmatch* out, int32_t* nout, hipStream_t s)
 {
+    if (e < 0 || e != match_key_exp(capT)) return hipErrorInvalidValue;     // (no exponent: rows too long for an exact key, the caller's to route)
     const int qblocks = (capT + MM_QB - 1) / MM_QB;
     const int fpx = (n + 7) >> 3;
-    match_mfma_kernel<<<8 * fpx * R * qblocks, 256, 0, s>>>(eq, et, nkp, f0, n, R, hist, capT, qblocks, fpx, reinterpret_cast<uint2*>(knn));
+    match_mfma_kernel<<<8 * fpx * R * qblocks, 256, 0, s>>>(eq, et, nkp, f0, n, R, hist, capT, qblocks, fpx, e, reinterpret_cast<uint2*>(knn));
     match_compact_kernel<<<n * R, 256, 0, s>>>(reinterpret_cast<const uint2*>(knn), nkp, f0, R, hist, capT, ratio, cap, out, nout);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 // HIP is unusable ssm_create fails with SSM_E_NODEVICE / SSM_E_HIP.
 #include "ssm_ctx.h"
 #include "ssm_host.h"
+#include "match_keys.h"
 #include <set>
 
 static const int8_t k_default_pattern[1024] = {
@@ -396,6 +397,7 @@ struct OrbBlock {
 };
 // the matrix-core matcher's rows (kernels_match.hip): capT = descriptors per row rounded up to the 32-row tile; expanded rows (each of eq, et); key rows, one per pair
 static int match_capT(int cap) { return (cap + 31) & ~31; }
+static bool match_mfma_fits(int cap) { return match_key_fits(match_capT(cap)); }      // rows short enough for an exact accumulator key (match_keys.h); longer ones take the VALU matcher
 static size_t match_exp_bytes(size_t rows, int capT) { return rows * capT * SSM_MATCH_DESC_BYTES; }
 static size_t match_knn_bytes(size_t pairs, int capT) { return pairs * capT * 8; }
 // One matrix-core matcher call on rows <= 17 descriptor sets of up to capm descriptors: the query sets first, the train set last, nref = rows - 1 pairs.
@@ -510,7 +512,7 @@ static int match_mfma_enqueue(ssm_ctx* c, const uint8_t* const* qs, const int* n
     uint8_t* h_res = hp + L.h_res;
     HIPCHK(c, hipMemcpyAsync(dp, hp, L.inb, hipMemcpyHostToDevice, c->main.stream));
     HIPCHK(c, k_match_expand(dp, dnk, 0, L.rows, capm, L.capT, dp + L.d_eq, dp + L.d_et, c->main.stream));
-    HIPCHK(c, k_match_seq_mfma(dp + L.d_eq, dp + L.d_et, dnk, 0, 1, nref, nref, ratio, capm, L.capT, dp + L.d_knn,
+    HIPCHK(c, k_match_seq_mfma(dp + L.d_eq, dp + L.d_et, dnk, 0, 1, nref, nref, ratio, capm, L.capT, match_key_exp(L.capT), dp + L.d_knn,
                                reinterpret_cast<ssm_dmatch*>(dp + L.d_res + L.list(0)), reinterpret_cast<int32_t*>(dp + L.d_res), c->main.stream));
     if (idx) {
         const int nq = nqs[0];
@@ -538,7 +540,7 @@ static int match_mfma_enqueue(ssm_ctx* c, const uint8_t* const* qs, const int* n
     });
     return SSM_OK;
 }
-// the VALU variant (SSM_MATCH_VARIANT=0): one pair through d_scratch, complete when the call returns
+// the VALU variant (SSM_MATCH_VARIANT=0, and every pair with more than 32768 descriptors on a side): one pair through d_scratch, complete when the call returns
 static int match_valu(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, double ratio, int32_t* idx, int32_t* dist, ssm_dmatch* out, int cap, int* n_out)
 {
     const bool want_knn = idx != nullptr;
@@ -573,7 +575,7 @@ static int match_host(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, in
     if (nt < 2) FAIL(c, SSM_E_TOO_FEW_TRAIN, "knnMatch(k=2) needs at least 2 train descriptors");
     if (nt > 65535) FAIL(c, SSM_E_INVAL, "at most 65535 train descriptors per call");
     if (nq == 0) { if (n_out) *n_out = 0; return SSM_OK; }
-    if (!c->match_mfma) return match_valu(c, q, nq, t, nt, ratio, idx, dist, out, cap, n_out);
+    if (!c->match_mfma || !match_mfma_fits(nq > nt ? nq : nt)) return match_valu(c, q, nq, t, nt, ratio, idx, dist, out, cap, n_out);
     return match_mfma_enqueue(c, &q, &nq, 1, t, nt, nq > nt ? nq : nt, ratio, &out, &cap, n_out, idx, dist);
 }
 extern "C" int ssm_hamming_knn2(ssm_ctx* c, const uint8_t* q, int nq, const uint8_t* t, int nt, int32_t* idx, int32_t* dist)
@@ -609,8 +611,8 @@ static int match_refs_enqueue(ssm_ctx* c, const uint8_t* const* refs, const int*
     if (ncur > 65535) FAIL(c, SSM_E_INVAL, "at most 65535 train descriptors per call");
     int capm = ncur;
     for (int i = 0; i < nref; i++) { if (nrefs[i] < 0 || (nrefs[i] && !refs[i]) || (caps[i] > 0 && !outs[i])) FAIL(c, SSM_E_INVAL, "bad reference set"); if (nrefs[i] > capm) capm = nrefs[i]; }
-    if (c->match_mfma && nref <= 16) return match_mfma_enqueue(c, refs, nrefs, nref, cur, ncur, capm, ratio, outs, caps, n_outs);
-    for (int i = 0; i < nref; i++) {                                           // the VALU variant, or more pairs than one block holds: pair by pair
+    if (c->match_mfma && nref <= 16 && match_mfma_fits(capm)) return match_mfma_enqueue(c, refs, nrefs, nref, cur, ncur, capm, ratio, outs, caps, n_outs);
+    for (int i = 0; i < nref; i++) {                                           // the VALU variant, more pairs than one block holds, or rows too long for the accumulator key: pair by pair
         if (nrefs[i] == 0) { n_outs[i] = 0; continue; }
         int r = match_host(c, refs[i], nrefs[i], cur, ncur, ratio, nullptr, nullptr, outs[i], caps[i], &n_outs[i]); if (r) return r;
     }
@@ -733,7 +735,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
         HIPCHK(c, hipMemsetAsync(c->d_nkp_all, 0xFF, (size_t)R * 4, s));     // -1: no such reference frame
     }
     uint8_t* desc = c->d_desc_all + (size_t)R * row; int32_t* nkp = c->d_nkp_all + R;
-    const bool mfma = c->match_mfma && (stages & SSM_STAGE_MATCH);
+    const bool mfma = c->match_mfma && (stages & SSM_STAGE_MATCH) && match_key_fits(c->capT);
     if (mfma) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, 0, R, g.cap, c->capT, c->d_exp_q, c->d_exp_t, s));      // the history rows
     // Two streams: the ORB -> match chain of a sub-batch and its (SegNet ->) map stage share no data, only the inputs, so the
     // map side runs on side[0].  The chain's latency-bound kernels (pyramid, octree, describe) then overlap VALU/MFMA-bound
@@ -774,7 +776,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
                 prof_begin(c, cs, "match");
                 if (mfma) {
                     if (!(stages & SSM_STAGE_ORB)) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs));
-                    HIPCHK(c, k_match_seq_mfma(c->d_exp_q, c->d_exp_t, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->capT, c->d_knn, c->d_matches, c->d_nmatch, cs));
+                    HIPCHK(c, k_match_seq_mfma(c->d_exp_q, c->d_exp_t, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->capT, match_key_exp(c->capT), c->d_knn, c->d_matches, c->d_nmatch, cs));
                 } else
                     HIPCHK(c, k_match_seq(c->d_desc_all, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->d_matches, c->d_nmatch, c->d_match_pend + (size_t)f0 * R, cs));
                 prof_end(c, cs);

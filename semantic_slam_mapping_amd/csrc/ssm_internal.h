@@ -56,10 +56,11 @@ hipError_t k_match_seq(const uint8_t* desc, const int32_t* nkp, int f0, int n, i
 
 // the matcher on the matrix cores: descriptors expanded to FP4 rows (capT = cap rounded up to 32 descriptors, SSM_MATCH_DESC_BYTES each, tile-fragment
 // order), then v_mfma_scale_f32_32x32x64_f8f6f4 distance tiles -> knn keys -> ratio test + ordered compaction.  Same results as k_match_seq.
+// e = match_key_exp(capT) (match_keys.h): the train scale's exponent; rows with no exact key (e < 0, capT > 32768) go to the VALU matcher instead.
 #define SSM_MATCH_DESC_BYTES 128
 hipError_t k_match_expand(const uint8_t* desc, const int32_t* nkp, int row0, int nrows, int cap, int capT, uint8_t* eq, uint8_t* et, hipStream_t s);
 hipError_t k_match_seq_mfma(const uint8_t* eq, const uint8_t* et, const int32_t* nkp, int f0, int n, int R, int hist, double ratio, int cap, int capT,
-                            void* knn /* n * R * capT * 8 B */, ssm_dmatch* out, int32_t* nout, hipStream_t s);
+                            int e, void* knn /* n * R * capT * 8 B */, ssm_dmatch* out, int32_t* nout, hipStream_t s);
 
 // mapper front half
 hipError_t k_moving_mask(const uint8_t* sem, int n, int w, int h, uint8_t* mask, hipStream_t s);
