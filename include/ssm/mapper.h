@@ -48,9 +48,18 @@
 // the map update, carveUpTo and the rendering.  RGBDFrame::T_f_w, the tracker and the pose graph are not written, and the map pose is FIXED when the key-frame is
 // aligned: a pose-graph correction that arrives later does not recompute it (a limit).  Both routes give the same bytes: deviceCloud /
 // ssm_align_clouds and frame->pointcloud / ssm_align_points.
+// mapper_grid=1 (default 0: nothing of this runs, every cloud, map and figure exactly as before): the ground grid (the reference has no such step).
+// When the viewer ends -- after the rendering, before the device clouds are freed -- ONE grid is built from EVERY key-frame's cloud, in its final state (filtered
+// and carved as the other switches left it; made on demand) and at its map pose (mapPoseOf).  The extent is not a parameter: the bounding box, in the grid frame,
+// of the key-frames' map positions, widened by mapper_max_distance, x0 and y0 snapped down and the far edge up to whole cells; beyond 2^24 cells the build is
+// skipped with a notice (gridInfo().skipped).  mapper_grid_cell, _step, _ground_radius, _min_obstacle_points, _h_min, _h_max set the spec, mapper_grid_up and
+// mapper_grid_forward (three numbers each, default `0 -1 0` and `0 0 1`) the grid frame.  Both routes give the same bytes: deviceCloud / ssm_grid_clouds and
+// frame->pointcloud / ssm_grid_points.  With mapper_grid_dir set the build writes grid_colour.png, grid_height.png (16 bit) and grid.txt (x0, y0, cell, nx, ny,
+// h_min, G: what georeferences the images) there.
 #pragma once
 #include "common_headers.h"
 #include <atomic>
+#include <iomanip>
 #include <unordered_map>
 #include "device.h"
 #include "pose_graph.h"
@@ -104,6 +113,26 @@ public:
         align_params.max_angle = para.getData<double>("mapper_align_max_angle", align_params.max_angle);
         align_params.tol_abs = para.getData<double>("mapper_align_tol_abs", align_params.tol_abs);
         align_params.tol_rel_ppm = para.getData<int>("mapper_align_tol_rel_ppm", align_params.tol_rel_ppm);
+        grid = para.getData<int>("mapper_grid", 0) != 0;
+        grid_dir = para.getData<string>("mapper_grid_dir", string(""));
+        ssm_grid_params_default(&grid_params);
+        grid_params.cell = para.getData<double>("mapper_grid_cell", grid_params.cell);
+        grid_params.step = para.getData<double>("mapper_grid_step", grid_params.step);
+        grid_params.ground_radius = para.getData<int>("mapper_grid_ground_radius", grid_params.ground_radius);
+        grid_params.min_obstacle_points = para.getData<int>("mapper_grid_min_obstacle_points", grid_params.min_obstacle_points);
+        grid_params.h_min = para.getData<double>("mapper_grid_h_min", grid_params.h_min);
+        grid_params.h_max = para.getData<double>("mapper_grid_h_max", grid_params.h_max);
+        if (grid) {
+            double up[3] = {0, -1, 0}, fw[3] = {0, 0, 1};
+            auto three = [&](const char* key, double* v) {
+                auto it = para.data.find(key);
+                if (it == para.data.end()) return;
+                istringstream ss(it->second);
+                if (!(ss >> v[0] >> v[1] >> v[2])) throw std::runtime_error(string("Mapper: ") + key + " takes three numbers");
+            };
+            three("mapper_grid_up", up); three("mapper_grid_forward", fw);
+            if (ssm_grid_frame_from_up(up, fw, grid_params.G) != SSM_OK) throw std::runtime_error("Mapper: mapper_grid_up and mapper_grid_forward do not span a frame");
+        }
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
     }
@@ -182,6 +211,10 @@ public:
         if (render) {                                   // every key-frame is a view of the clouds around it, in their final state
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
             renderAll(kfs);
+        }
+        if (grid) {                                     // one ground grid of every key-frame's cloud, in its final state
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            buildGrid(kfs);
         }
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
@@ -460,6 +493,89 @@ public:
         if (info) *info = it->second;
         return true;
     }
+    // the ground grid: ONE grid of the clouds of every key-frame of kfs at their map poses.  The viewer thread calls this as it ends; once that has ended its owner
+    // may (the host route then: the device clouds went with the thread)
+    struct GridInfo { bool built = false, skipped = false; ssm_grid_info counts{}; };          // skipped: the extent exceeded 2^24 cells (or there was no key-frame)
+    struct GridTarget {          // the device accumulators and outputs; freed on every way out
+        ssm_ctx* ctx = nullptr; ssm_grid_target* t = nullptr;
+        GridTarget() = default; GridTarget(const GridTarget&) = delete; GridTarget& operator=(const GridTarget&) = delete;
+        ~GridTarget() { if (t) ssm_grid_target_free(ctx, t); }
+    };
+    void buildGrid(const vector<RGBDFrame::Ptr>& kfs) {
+        gridState = GridInfo(); gridSpec = grid_params; gridSpec.nx = gridSpec.ny = 0;
+        gridCls.clear(); gridGroundLabel.clear(); gridObstacleLabel.clear(); gridGroundQ.clear(); gridTopQ.clear(); gridN.clear(); gridNHigh.clear();
+        if (kfs.empty()) { gridState.skipped = true; return; }
+        // the extent: the key-frames' map positions in the grid frame, widened by max_distance, in whole cells
+        ssm_grid_params P = grid_params;
+        double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
+        vector<double> poses;
+        for (const RGBDFrame::Ptr& f : kfs) {
+            const Eigen::Isometry3d T = mapPoseOf(f);
+            poses.insert(poses.end(), T.data(), T.data() + 16);
+            for (int i = 0; i < 2; i++) {
+                const double g = ((P.G[i * 4] * T(0, 3) + P.G[i * 4 + 1] * T(1, 3)) + P.G[i * 4 + 2] * T(2, 3)) + P.G[i * 4 + 3];
+                lo[i] = min(lo[i], g); hi[i] = max(hi[i], g);
+            }
+        }
+        const double cx0 = floor((lo[0] - max_distance) / P.cell), cx1 = ceil((hi[0] + max_distance) / P.cell), cy0 = floor((lo[1] - max_distance) / P.cell),
+                     cy1 = ceil((hi[1] + max_distance) / P.cell);
+        const double nxd = max(cx1 - cx0, 1.0), nyd = max(cy1 - cy0, 1.0);
+        if (!(nxd * nyd <= 16777216.0) || !std::isfinite(cx0) || !std::isfinite(cy0)) {          // (false for NaN too)
+            cerr << "Mapper: the ground grid would have " << nxd << " x " << nyd << " cells, more than 2^24: not built" << endl;
+            gridState.skipped = true; return;
+        }
+        P.x0 = cx0 * P.cell; P.y0 = cy0 * P.cell; P.nx = (int)nxd; P.ny = (int)nyd;
+        const int w = kfs[0]->depth.cols, h = kfs[0]->depth.rows;
+        ssm::Device& d = device(w, h);
+        GridTarget target; target.ctx = d.ctx();
+        d.check(ssm_grid_target_create(d.ctx(), P.nx, P.ny, &target.t), "ssm_grid_target_create");
+        ssm_grid_info I{};
+        if (device_map) {
+            vector<ssm_cloud*> cl;
+            for (const RGBDFrame::Ptr& f : kfs) cl.push_back(deviceCloud(f));
+            d.check(ssm_grid_clouds(d.ctx(), target.t, cl.data(), poses.data(), (int)cl.size(), &P, &I), "ssm_grid_clouds");
+        } else {
+            vector<const ssm_point*> pts; vector<int32_t> n;
+            for (const RGBDFrame::Ptr& f : kfs) {
+                hostCloud(f);
+                pts.push_back(reinterpret_cast<const ssm_point*>(f->pointcloud->points.data())); n.push_back((int32_t)f->pointcloud->points.size());
+            }
+            d.check(ssm_grid_points(d.ctx(), target.t, pts.data(), n.data(), poses.data(), (int)pts.size(), &P, &I), "ssm_grid_points");
+        }
+        const size_t nc = (size_t)P.nx * P.ny;
+        gridCls.resize(nc); gridGroundLabel.resize(nc); gridObstacleLabel.resize(nc); gridGroundQ.resize(nc); gridTopQ.resize(nc); gridN.resize(nc); gridNHigh.resize(nc);
+        d.check(ssm_grid_fetch(d.ctx(), target.t, gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), gridTopQ.data(), gridN.data(), gridNHigh.data()),
+                "ssm_grid_fetch");
+        gridSpec = P; gridState.counts = I; gridState.built = true;
+        if (!grid_dir.empty()) {
+            cv::Mat col, hgt; col.create(P.ny, P.nx, CV_8UC3); hgt.create(P.ny, P.nx, CV_16UC1);
+            ssm_grid_colours(gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), P.nx, P.ny, P.h_min, col.data, hgt.ptr<uint16_t>());
+            ofstream txt(grid_dir + "/grid.txt");
+            txt << setprecision(17) << "x0 " << P.x0 << "\ny0 " << P.y0 << "\ncell " << P.cell << "\nnx " << P.nx << "\nny " << P.ny << "\nh_min " << P.h_min << "\nG";
+            for (int i = 0; i < 12; i++) txt << " " << P.G[i];
+            txt << "\n";
+            txt.close();
+            if (!(txt && ssm::imwritePNG(grid_dir + "/grid_colour.png", col) && ssm::imwritePNG(grid_dir + "/grid_height.png", hgt)))
+                throw std::runtime_error("Mapper: cannot write the ground grid to " + grid_dir);
+        }
+    }
+    bool buildsGrid() const { return grid; }
+    // the last buildGrid (not while the viewer thread runs): what happened and the counts; the spec actually used (nx = ny = 0 when nothing was built); the arrays,
+    // nx ny entries each, cell (cx, cy) at cy nx + cx -- each pointer may be null; false: nothing was built
+    const GridInfo& gridInfo() const { return gridState; }
+    const ssm_grid_params& gridParams() const { return gridSpec; }
+    bool gridFetch(vector<uint8_t>* cls, vector<uint8_t>* ground_label, vector<uint8_t>* obstacle_label, vector<int32_t>* ground_q, vector<int32_t>* top_q, vector<uint32_t>* n,
+                   vector<uint32_t>* n_high) const {
+        if (!gridState.built) return false;
+        if (cls) *cls = gridCls;
+        if (ground_label) *ground_label = gridGroundLabel;
+        if (obstacle_label) *obstacle_label = gridObstacleLabel;
+        if (ground_q) *ground_q = gridGroundQ;
+        if (top_q) *top_q = gridTopQ;
+        if (n) *n = gridN;
+        if (n_high) *n_high = gridNHigh;
+        return true;
+    }
     bool carves() const { return carve; }
     int carvedViews() const { return carveViews; }                            // views applied so far (a first key-frame has no earlier cloud and is none)
     // what carving did to a key-frame's cloud over all the views applied to it: n_in its size before the first, n_kept its size now, the verdicts and `removed` summed
@@ -537,6 +653,8 @@ protected:
     std::unordered_map<const RGBDFrame*, AlignResult> alignResult;       // key-frame -> its alignment and map pose (viewer thread, or its owner once that has ended)
     bool render = false; int render_window = 5, renderViews = 0; string render_dir; ssm_render_params render_params{};
     std::unordered_map<const RGBDFrame*, ssm_render_compare_info> renderInfo;      // key-frame -> its view's comparison (viewer thread, or its owner once that has ended)
+    bool grid = false; string grid_dir; ssm_grid_params grid_params{}, gridSpec{}; GridInfo gridState;
+    vector<uint8_t> gridCls, gridGroundLabel, gridObstacleLabel; vector<int32_t> gridGroundQ, gridTopQ; vector<uint32_t> gridN, gridNHigh;      // the last build's arrays
     std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)
     string map_output;
 };

@@ -580,6 +580,54 @@ void ssm_render_label_colours(const uint8_t* label, int64_t n, uint8_t* bgr_out)
 /* the raw z-buffer after the target's last rendering (w h entries), for the tests */
 int  ssm_debug_render_keys(ssm_ctx* ctx, const ssm_render_target* target, uint64_t* keys);
 
+/* ---- ground grid: the points of m posed clouds are dropped into a horizontal grid of nx x ny square cells (a bird's-eye semantic elevation map).  The reference
+ * has no such step; DESIGN.md s.19 is the contract, include/ssm/grid_core.h the arithmetic shared by the device path and the host function (device == host byte
+ * for byte, every raw accumulator included; integer accumulators only, so the order of points and clouds does not matter).  G: row-major 3 x 4, world -> grid
+ * frame (grid x, y span the plane, grid z is height).  A point is used when it is finite, its height lies in [h_min, h_max] and its cell is inside.  Pass A: per
+ * cell n, hmin, hmax (heights in units of 2^-10 m).  Ground: base = the smallest hmin of the non-empty cells of the (2 ground_radius + 1)^2 window.  Pass B: a
+ * point at most step above base is LOW (n_low, sum_low, hist_low[label]), otherwise HIGH (n_high, hist_high[label]); a label above 11 enters no bin.  Resolve:
+ * class 0 unobserved (heights INT32_MIN, labels 255), 4 obstacle (n_high >= min_obstacle_points), else by the ground label 1 drivable (Road 4, Road_marking 3),
+ * 2 walkable (Pavement 5), 3 other ground; ground_q = floor(sum_low / n_low) (base when n_low == 0), top_q = hmax; the labels are the fullest bins, the lowest id
+ * on a tie, 255 when empty (obstacle_label: 255 unless the cell is an obstacle).
+ * SSM_E_INVAL: a non-finite entry of G or parameter; cell <= 0; nx or ny < 1, nx ny > 2^24 or above the target's cells; h_max < h_min, |h_min| or |h_max| above
+ * 2^20; step < 0; ground_radius outside 0..4; min_obstacle_points < 1; a non-finite pose; m < 0, a negative count, the same cloud twice; 2^31 points or more. */
+typedef struct { double G[12]; double x0, y0, cell; int32_t nx, ny; double h_min, h_max, step; int32_t ground_radius, min_obstacle_points; } ssm_grid_params;
+typedef struct { int64_t n_in, n_finite, out_of_band, outside, n_used, unobserved, drivable, walkable, other_ground, obstacle; } ssm_grid_info;   /* points, then cells by class */
+/* a cell's raw accumulators (128 bytes).  A cell no point fell into: hmin and base INT32_MAX, hmax INT32_MIN, everything else 0 */
+typedef struct { uint32_t n; int32_t hmin, hmax, base; uint32_t n_low, n_high; int64_t sum_low; uint32_t hist_low[12], hist_high[12]; } ssm_grid_cell;
+typedef struct ssm_grid_target ssm_grid_target;
+/* G for a y-down, z-forward world (g.x = x, g.y = z, g.z = -y), 0.2 m cells, 512 x 512 of them centred in x and starting 10 m behind the origin, heights -3 .. +3 m,
+ * step 0.3 m, ground_radius 1, min_obstacle_points 3 */
+void ssm_grid_params_default(ssm_grid_params* p);
+/* G (translation 0) for a world whose up and forward directions are given; SSM_E_INVAL: a non-finite entry, an up of length 0, a forward along up */
+int  ssm_grid_frame_from_up(const double up[3], const double forward[3], double G[12]);
+/* device accumulators and outputs for grids of up to nx ny cells, reused across builds (every build clears them) */
+int  ssm_grid_target_create(ssm_ctx* ctx, int nx, int ny, ssm_grid_target** target_out);
+void ssm_grid_target_free(ssm_ctx* ctx, ssm_grid_target* target);
+/* m device-resident clouds at the poses T_clouds (m x 16 doubles, column-major); nothing is uploaded but the poses.  params NULL: the defaults; info may be NULL */
+int  ssm_grid_clouds(ssm_ctx* ctx, ssm_grid_target* target, ssm_cloud* const* clouds, const double* T_clouds, int m, const ssm_grid_params* params, ssm_grid_info* info);
+/* the same from host arrays, through the device */
+int  ssm_grid_points(ssm_ctx* ctx, ssm_grid_target* target, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m, const ssm_grid_params* params,
+                     ssm_grid_info* info);
+/* the map the last ssm_viewer_map_update left on the device, at the identity pose; SSM_E_INVAL when there is none */
+int  ssm_grid_viewer_map(ssm_ctx* ctx, ssm_grid_target* target, const ssm_grid_params* params, ssm_grid_info* info);
+/* the arrays of the target's last build, nx ny entries each, cell (cx, cy) at cy nx + cx; each may be NULL */
+int  ssm_grid_fetch(ssm_ctx* ctx, const ssm_grid_target* target, uint8_t* cls, uint8_t* ground_label, uint8_t* obstacle_label, int32_t* ground_q, int32_t* top_q,
+                    uint32_t* n, uint32_t* n_high);
+/* the same on the CPU, no GPU, the same bits; cells (may be NULL): the raw accumulators */
+int  ssm_grid_host(const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m, const ssm_grid_params* params, uint8_t* cls, uint8_t* ground_label,
+                   uint8_t* obstacle_label, int32_t* ground_q, int32_t* top_q, uint32_t* n_out, uint32_t* n_high, ssm_grid_cell* cells, ssm_grid_info* info);
+/* the raw cells after the target's last build (nx ny entries), for the tests */
+int  ssm_debug_grid_cells(ssm_ctx* ctx, const ssm_grid_target* target, ssm_grid_cell* cells);
+/* how the context's later builds accumulate, for the tests and the measurement: 0 one atomic per point and address, 1 one per run of adjacent lanes with the same
+ * destination, -1 the default (1); the same bits either way */
+int  ssm_debug_grid_form(ssm_ctx* ctx, int form);
+/* the cell arrays as images whose row r is cell row ny - 1 - r (forward is up).  bgr (3 bytes per cell, may be NULL): an obstacle takes the palette colour of its
+ * label, white when unknown; ground that of its label, (64, 64, 64) when unknown; unobserved is black.  height (16 bits per cell, may be NULL):
+ * clamp(ground_q - llrint(1024 h_min), 0, 65534) + 1, 0 for unobserved */
+void ssm_grid_colours(const uint8_t* cls, const uint8_t* ground_label, const uint8_t* obstacle_label, const int32_t* ground_q, int nx, int ny, double h_min,
+                      uint8_t* bgr_out, uint16_t* height_out);
+
 /* ---- dense alignment: projective point-to-plane ICP of the points of m posed clouds against a key-frame's depth image (the view).  The reference has no such
  * step; DESIGN.md s.18 is the contract, include/ssm/align_core.h the arithmetic shared by the device path and the host function.  The view gets a normal per
  * pixel (invalid at depth 0, at the border and across a depth edge: a neighbour farther than carving's tolerance).  Per iteration every point is carried into the

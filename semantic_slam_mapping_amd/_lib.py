@@ -109,6 +109,15 @@ class RenderCompareInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("unrendered", "no_depth", "in_front", "behind", "agree", "label_agree", "label_disagree", "label_unknown", "n_pixels")]
 
 
+class GridParams(C.Structure):
+    _fields_ = [("G", C.c_double * 12), ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32), ("h_min", C.c_double),
+                ("h_max", C.c_double), ("step", C.c_double), ("ground_radius", C.c_int32), ("min_obstacle_points", C.c_int32)]
+
+
+class GridInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_in", "n_finite", "out_of_band", "outside", "n_used", "unobserved", "drivable", "walkable", "other_ground", "obstacle")]
+
+
 class AlignParams(C.Structure):
     _fields_ = [("max_iterations", C.c_int32), ("stride", C.c_int32)] + [(n, C.c_double) for n in ("z_min", "z_max", "dist_max", "delta", "damping", "eps_rot", "eps_trans")] + \
                [("min_inliers", C.c_int32), ("pad", C.c_int32), ("max_shift", C.c_double), ("max_angle", C.c_double), ("tol_abs", C.c_double), ("tol_rel_ppm", C.c_int32),
@@ -262,6 +271,18 @@ SYMBOLS = {
     "ssm_render_compare_host": (_I, [_P, _P, _I, _I, _P, _P, C.c_double, C.POINTER(RenderParams), C.POINTER(RenderCompareInfo), _P]),
     "ssm_render_label_colours": (None, [_P, C.c_int64, _P]),
     "ssm_debug_render_keys": (_I, [_P, _P, _P]),
+    "ssm_grid_params_default": (None, [C.POINTER(GridParams)]),
+    "ssm_grid_frame_from_up": (_I, [_P, _P, _P]),
+    "ssm_grid_target_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "ssm_grid_target_free": (None, [_P, _P]),
+    "ssm_grid_clouds": (_I, [_P, _P, _P, _P, _I, C.POINTER(GridParams), C.POINTER(GridInfo)]),
+    "ssm_grid_points": (_I, [_P, _P, _P, _P, _P, _I, C.POINTER(GridParams), C.POINTER(GridInfo)]),
+    "ssm_grid_viewer_map": (_I, [_P, _P, C.POINTER(GridParams), C.POINTER(GridInfo)]),
+    "ssm_grid_fetch": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ssm_grid_host": (_I, [_P, _P, _P, _I, C.POINTER(GridParams), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(GridInfo)]),
+    "ssm_debug_grid_cells": (_I, [_P, _P, _P]),
+    "ssm_debug_grid_form": (_I, [_P, _I]),
+    "ssm_grid_colours": (None, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P]),
     "ssm_align_params_default": (None, [C.POINTER(AlignParams)]),
     "ssm_align_view_create": (_I, [_P, _P, _I, _I, C.POINTER(Camera), C.POINTER(AlignParams), C.POINTER(_P)]),
     "ssm_align_view_free": (None, [_P, _P]),

@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -280,6 +280,79 @@ def label_colours(label):
     out = np.zeros(label.shape + (3,), np.uint8)
     _lib.load().ssm_render_label_colours(_ptr(label), label.size, _ptr(out))
     return out
+
+
+GRID_INFO_FIELDS = ("n_in", "n_finite", "out_of_band", "outside", "n_used", "unobserved", "drivable", "walkable", "other_ground", "obstacle")
+GRID_ARRAYS = (("cls", np.uint8), ("ground_label", np.uint8), ("obstacle_label", np.uint8), ("ground_q", np.int32), ("top_q", np.int32), ("n", np.uint32), ("n_high", np.uint32))
+GRID_CELL_DTYPE = np.dtype([("n", "u4"), ("hmin", "i4"), ("hmax", "i4"), ("base", "i4"), ("n_low", "u4"), ("n_high", "u4"), ("sum_low", "i8"),
+                            ("hist_low", "u4", (12,)), ("hist_high", "u4", (12,))])
+GRID_FIELDS = ("G", "x0", "y0", "cell", "nx", "ny", "h_min", "h_max", "step", "ground_radius", "min_obstacle_points")
+
+
+def grid_params(**kw):
+    """the ground grid's parameters (ssm_grid_params): the library's defaults (ssm_grid_params_default) with the given fields replaced; G: 3 x 4, world -> grid"""
+    bad = set(kw) - set(GRID_FIELDS)
+    if bad:
+        raise TypeError("unknown grid parameters: " + ", ".join(sorted(bad)))
+    P = GridParams()
+    _lib.load().ssm_grid_params_default(C.byref(P))
+    for k, v in kw.items():
+        if k == "G":
+            G = np.ascontiguousarray(v, np.float64)
+            if G.size != 12:
+                raise ValueError("G is a 3 x 4 matrix")
+            P.G = (C.c_double * 12)(*G.reshape(12))
+        else:
+            setattr(P, k, int(v) if k in ("nx", "ny", "ground_radius", "min_obstacle_points") else float(v))
+    return P
+
+
+def grid_frame_from_up(up, forward):
+    """G (3 x 4, translation 0) for a world whose up and forward directions are given (ssm_grid_frame_from_up)"""
+    up = np.ascontiguousarray(up, np.float64); fw = np.ascontiguousarray(forward, np.float64)
+    if up.shape != (3,) or fw.shape != (3,):
+        raise ValueError("up and forward are three numbers each")
+    G = np.zeros((3, 4))
+    lib = _lib.load()
+    rc = lib.ssm_grid_frame_from_up(_ptr(up), _ptr(fw), _ptr(G))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return G
+
+
+def _grid_arrays(nx, ny, cells):
+    ok = nx >= 1 and ny >= 1 and nx * ny <= 1 << 24
+    shape = (ny, nx) if ok else (1, 1)
+    out = {k: np.zeros(shape, t) for k, t in GRID_ARRAYS}
+    if cells:
+        out["cells"] = np.zeros(shape, GRID_CELL_DTYPE)
+    return out
+
+
+def grid_host(clouds, T_clouds, cells=False, **params):
+    """the ground grid on the CPU (ssm_grid_host, no GPU): the points of `clouds` (host arrays of POINT_DTYPE at the poses T_clouds) -> {cls, ground_label,
+    obstacle_label, ground_q, top_q, n, n_high: ny x nx arrays, info}, with cells=True also the raw accumulators (GRID_CELL_DTYPE)"""
+    keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
+    P = grid_params(**params); I = GridInfo()
+    out = _grid_arrays(P.nx, P.ny, cells)
+    lib = _lib.load()
+    rc = lib.ssm_grid_host(ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), *[_ptr(out[k]) for k, _ in GRID_ARRAYS], _ptr(out.get("cells")), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    out["info"] = {k: getattr(I, k) for k in GRID_INFO_FIELDS}
+    return out
+
+
+def grid_colours(cls, ground_label, obstacle_label, ground_q, h_min=-3.0):
+    """the cell arrays (ny x nx) -> (the BGR image, the 16-bit height image), forward up (ssm_grid_colours)"""
+    cls = np.ascontiguousarray(cls, np.uint8); gl = np.ascontiguousarray(ground_label, np.uint8); ol = np.ascontiguousarray(obstacle_label, np.uint8)
+    gq = np.ascontiguousarray(ground_q, np.int32)
+    if cls.ndim != 2 or gl.shape != cls.shape or ol.shape != cls.shape or gq.shape != cls.shape:
+        raise ValueError("four ny x nx arrays of one grid")
+    ny, nx = cls.shape
+    bgr = np.zeros((ny, nx, 3), np.uint8); height = np.zeros((ny, nx), np.uint16)
+    _lib.load().ssm_grid_colours(_ptr(cls), _ptr(gl), _ptr(ol), _ptr(gq), nx, ny, float(h_min), _ptr(bgr), _ptr(height))
+    return bgr, height
 
 
 ALIGN_STATUS = ("max_iterations", "converged", "too_few", "degenerate", "diverged")
@@ -1192,6 +1265,65 @@ class Context:
         self._chk(self.lib.ssm_render_compare(self.h, target, _ptr(depth), _ptr(sem), float(self.cfg.camera.scale if scale is None else scale), C.byref(P), C.byref(I), _ptr(cls)))
         info = {k: getattr(I, k) for k in RENDER_COMPARE_FIELDS}
         return (info, cls) if class_image else info
+
+    def grid_target(self, nx, ny):
+        """the device accumulators and outputs for ground grids of up to nx * ny cells, reused across builds (ssm_grid_target_create) -> an opaque handle
+        (grid_target_free it)"""
+        t = C.c_void_p()
+        self._chk(self.lib.ssm_grid_target_create(self.h, int(nx), int(ny), C.byref(t)))
+        self._grid_sizes = getattr(self, "_grid_sizes", {})
+        self._grid_sizes[t.value] = None
+        return t.value
+
+    def grid_target_free(self, target):
+        self._grid_sizes.pop(target, None)
+        self.lib.ssm_grid_target_free(self.h, target)
+
+    def grid_form(self, form):
+        """how later builds accumulate (ssm_debug_grid_form): 0 one atomic per point, 1 one per run of adjacent lanes with the same destination, -1 the default"""
+        self._chk(self.lib.ssm_debug_grid_form(self.h, int(form)))
+
+    def grid_fetch(self, target):
+        """the arrays of the target's last build (ssm_grid_fetch) -> {cls, ground_label, obstacle_label, ground_q, top_q, n, n_high}, ny x nx each"""
+        nx, ny = self._grid_sizes[target] or (1, 1)
+        out = _grid_arrays(nx, ny, False)
+        self._chk(self.lib.ssm_grid_fetch(self.h, target, *[_ptr(out[k]) for k, _ in GRID_ARRAYS]))
+        return out
+
+    def grid_cells(self, target):
+        """the raw per-cell accumulators and base of the target's last build (ssm_debug_grid_cells), ny x nx of GRID_CELL_DTYPE"""
+        nx, ny = self._grid_sizes[target] or (1, 1)
+        cells = np.zeros((ny, nx), GRID_CELL_DTYPE)
+        self._chk(self.lib.ssm_debug_grid_cells(self.h, target, _ptr(cells)))
+        return cells
+
+    def _grid_result(self, target, P, I, cells):
+        self._grid_sizes[target] = (P.nx, P.ny)
+        out = self.grid_fetch(target)
+        if cells:
+            out["cells"] = self.grid_cells(target)
+        out["info"] = {k: getattr(I, k) for k in GRID_INFO_FIELDS}
+        return out
+
+    def grid_points(self, target, clouds, T_clouds, cells=False, **params):
+        """grid_host's call through the device (ssm_grid_points) -> the same dictionary"""
+        keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
+        P = grid_params(**params); I = GridInfo()
+        self._chk(self.lib.ssm_grid_points(self.h, target, ptrs, _ptr(n), _ptr(Tc), m, C.byref(P), C.byref(I)))
+        return self._grid_result(target, P, I, cells)
+
+    def grid_clouds(self, target, clouds, T_clouds, cells=False, **params):
+        """device-resident clouds (backproject_dev's handles) at the poses T_clouds into the grid (ssm_grid_clouds); nothing is uploaded but the poses"""
+        _, arr, _, Tc, m = _pack_clouds(clouds, T_clouds, False)
+        P = grid_params(**params); I = GridInfo()
+        self._chk(self.lib.ssm_grid_clouds(self.h, target, arr, _ptr(Tc), m, C.byref(P), C.byref(I)))
+        return self._grid_result(target, P, I, cells)
+
+    def grid_viewer_map(self, target, cells=False, **params):
+        """the map the last viewer_map_update left on the device, at the identity pose (ssm_grid_viewer_map)"""
+        P = grid_params(**params); I = GridInfo()
+        self._chk(self.lib.ssm_grid_viewer_map(self.h, target, C.byref(P), C.byref(I)))
+        return self._grid_result(target, P, I, cells)
 
     def align_view(self, depth, camera=None, **params):
         """a view of dense alignment: the depth image goes to the device and its normal map is built there (ssm_align_view_create; params: the edge gate) -> an

@@ -195,6 +195,13 @@ struct ssm_render_target {
 };
 // workspace of map rendering: the info and the comparison's counts
 struct RenderWork { DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<unsigned long long> counts; PinBuf<unsigned long long> h_counts; };
+// a grid target (ssm_grid.hip): the raw cells and the seven output arrays for up to cap cells; nx, ny, h_min: the last build's (built: there is one)
+struct ssm_grid_target {
+    int64_t cap = 0; int nx = 0, ny = 0, device = 0; bool built = false;
+    DevBuf<ssm_grid_cell> cells; DevBuf<uint8_t> cls, ground_label, obstacle_label; DevBuf<int32_t> ground_q, top_q; DevBuf<uint32_t> n, n_high;
+};
+// workspace of the ground grid: the info
+struct GridWork { DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; int form = GRID_FORM_DEFAULT; };          // form: ssm_debug_grid_form
 // a view of dense alignment (ssm_align.hip): a key-frame's depth image and its normal map (16 bytes per pixel) in device memory, its camera and edge gate
 struct ssm_align_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> normals; int w = 0, h = 0, device = 0; ssm_camera cam{}; double tol_abs = 0; int32_t tol_rel_ppm = 0; };
 // workspace of dense alignment: one slot of sums per iteration, and the last device call's iterations (ssm_debug_align_record)
@@ -287,6 +294,7 @@ struct ssm_ctx {
     CarveWork carve;                                         // free-space carving: likewise
     RenderWork render;                                       // map rendering: likewise
     AlignWork align;                                         // dense alignment: likewise
+    GridWork grid;                                           // ground grid: likewise
     CloudTableWork clouds;                                   // the cloud table and host-array staging of the three: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling

@@ -261,6 +261,16 @@ hipError_t k_render(const ssm_renderc::Setup& S, const CloudSeg* seg, const int3
 hipError_t k_render_compare(const uint16_t* rdepth, const uint8_t* rlabel, const uint16_t* depth, const uint8_t* sem, int64_t np, int64_t tol_abs, int64_t ppm,
                             uint8_t* cls, unsigned long long* counts, hipStream_t s);
 
+// ground grid (kernels_grid.hip; the arithmetic is include/ssm/grid_core.h): m clouds whose points are numbered through, `total` in all (below 2^31), into
+// S.nx x S.ny cells.  seg, blk: the cloud table (cloud_table.h) with blocks of k_grid_block() points.  info: 10 x int64 as ssm_grid_info.  k_grid queues the
+// clear, pass A, the ground kernel, pass B and the resolve on s and waits for nothing.  form: how passes A and B accumulate -- one atomic per point and address
+// (GRID_FORM_POINTS, the baseline), or one per run of adjacent lanes with the same destination (GRID_FORM_RUNS); the same bits.
+namespace ssm_gridc { struct Setup; }
+enum { GRID_FORM_POINTS = 0, GRID_FORM_RUNS = 1, GRID_FORM_DEFAULT = GRID_FORM_RUNS };
+struct GridBufs { ssm_grid_cell* cells; uint8_t *cls, *ground_label, *obstacle_label; int32_t *ground_q, *top_q; uint32_t *n, *n_high; };
+int k_grid_block();
+hipError_t k_grid(const ssm_gridc::Setup& S, const CloudSeg* seg, const int32_t* blk, int64_t total, const GridBufs& T, unsigned long long* info, int form, hipStream_t s);
+
 // dense alignment (kernels_align.hip; the arithmetic is include/ssm/align_core.h).  seg, blk: the cloud table (cloud_table.h) of the points USED (every stride-th
 // of a cloud), with chunks of k_align_block() points as its blocks.  k_align_normals fills a view's normal map (16 bytes per pixel); k_align_accumulate adds one
 // iteration's NSUM 64-bit sums under the increment E (12 doubles, host memory) to sums, which the caller has zeroed.  Both queue on s and wait for nothing.

@@ -34,6 +34,10 @@
 // rendered images are written there as PNG.  The summary line then carries `render_views V render_agree A render_in_front F render_behind B render_label_agree L
 // render_label_disagree D render_fnv H`: the views, the sums of those counts over them, and FNV-1a over every view's nine counts in key-frame order (the same in both
 // modes: it runs once, at the end).  Without the flag nothing of this runs and the line is as before.
+// `exp_mapping <parameters> --grid [DIR]` (or mapper_grid=1, mapper_grid_dir=DIR): when the viewer ends, Mapper builds ONE ground grid from every key-frame's cloud at
+// its map pose (include/ssm/mapper.h); with DIR grid_colour.png, grid_height.png and grid.txt are written there.  The summary line then carries
+// `grid_cells C grid_drivable D grid_walkable W grid_obstacle O grid_fnv H`: the cells of the grid, three of its class counts, and FNV-1a over nx, ny and the fetched
+// arrays in the order cls, ground_label, obstacle_label, ground_q, top_q, n, n_high (the same in both modes).  Without the flag nothing of this runs.
 // `exp_mapping <parameters> --align` (or mapper_align=1): Mapper aligns every key-frame's depth image to the clouds of the mapper_align_window key-frames before it and
 // uses the corrected map pose from there on (dense alignment: include/ssm/mapper.h).  The summary line then carries `align_keyframes N align_accepted A
 // align_fnv H`: the key-frames aligned, the alignments accepted, and FNV-1a over every key-frame's status, iteration count, counts and the bytes of its correction D_j,
@@ -153,6 +157,12 @@ int main(int argc, char** argv)
         if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_render_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
     }
     if (render) parameterReader.set("mapper_render", "1");
+    bool grid = parameterReader.getData<int>("mapper_grid", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--grid") {
+        grid = true;
+        if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_grid_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
+    }
+    if (grid) parameterReader.set("mapper_grid", "1");
     MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
@@ -432,6 +442,20 @@ int main(int argc, char** argv)
             }
             cout << " render_views " << mapper.renderedViews() << " render_agree " << agree << " render_in_front " << in_front << " render_behind " << behind
                  << " render_label_agree " << lab_agree << " render_label_disagree " << lab_dis << " render_fnv " << hex << h << dec;
+        }
+        if (grid) {             // (the viewer thread built the grid of every key-frame's cloud as it ended)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before the ground grid was built" << endl; return 3; }
+            const Mapper::GridInfo& G = mapper.gridInfo();
+            vector<uint8_t> cls, gl, ol; vector<int32_t> gq, tq; vector<uint32_t> gn, gh;
+            mapper.gridFetch(&cls, &gl, &ol, &gq, &tq, &gn, &gh);
+            uint64_t h = 0xCBF29CE484222325ull;           // FNV-1a over nx, ny and the arrays: cls, ground_label, obstacle_label, ground_q, top_q, n, n_high
+            auto eat = [&h](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; for (size_t k = 0; k < bytes; k++) { h ^= b[k]; h *= 0x100000001B3ull; } };
+            const int32_t shape[2] = {mapper.gridParams().nx, mapper.gridParams().ny};
+            eat(shape, sizeof shape);
+            eat(cls.data(), cls.size()); eat(gl.data(), gl.size()); eat(ol.data(), ol.size()); eat(gq.data(), gq.size() * 4); eat(tq.data(), tq.size() * 4); eat(gn.data(), gn.size() * 4);
+            eat(gh.data(), gh.size() * 4);
+            cout << " grid_cells " << cls.size() << " grid_drivable " << G.counts.drivable << " grid_walkable " << G.counts.walkable << " grid_obstacle " << G.counts.obstacle
+                 << " grid_fnv " << hex << h << dec;
         }
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;

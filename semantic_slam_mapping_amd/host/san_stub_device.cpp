@@ -2,7 +2,7 @@
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
 // which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_cloud_table.cpp,
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_cloud_table.cpp,
 // ssm_track_host.cpp, ssm_map_plan.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
 // "no device" form of csrc/ssm_host.h's hooks here (the bulk tracker's among them: no tracker is ever created on the stub; its state machine runs under the sanitizers
 // in host/test_track.cpp, over hooks of that program's own).  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
@@ -153,6 +153,41 @@ int ssm_render_fetch(ssm_ctx*, const ssm_render_target* t, uint16_t* depth, uint
 }
 int ssm_render_compare(ssm_ctx*, ssm_render_target* t, const uint16_t* depth, const uint8_t* sem, double scale, const ssm_render_params* params, ssm_render_compare_info* info, uint8_t* cls)
 { return ssm_render_compare_host(t->depth.data(), t->label.data(), t->w, t->h, depth, sem, scale, params, info, cls); }
+// the ground grid (Mapper with mapper_grid=1): a "target" is the host arrays, the linked host function in the device entry points' place
+struct ssm_grid_target { int64_t cap; int nx, ny; std::vector<uint8_t> cls, gl, ol; std::vector<int32_t> gq, tq; std::vector<uint32_t> n, nh; };
+int ssm_grid_target_create(ssm_ctx*, int nx, int ny, ssm_grid_target** out)
+{
+    if (nx < 1 || ny < 1 || (int64_t)nx * ny > ((int64_t)1 << 24)) return SSM_E_INVAL;
+    ssm_grid_target* t = new ssm_grid_target(); const size_t nc = (size_t)nx * ny;
+    t->cap = (int64_t)nc; t->nx = t->ny = 0; t->cls.resize(nc); t->gl.resize(nc); t->ol.resize(nc); t->gq.resize(nc); t->tq.resize(nc); t->n.resize(nc); t->nh.resize(nc); *out = t; return SSM_OK;
+}
+void ssm_grid_target_free(ssm_ctx*, ssm_grid_target* t) { delete t; }
+int ssm_grid_points(ssm_ctx*, ssm_grid_target* t, const ssm_point* const* pts, const int32_t* n, const double* Tc, int m, const ssm_grid_params* params, ssm_grid_info* info)
+{
+    ssm_grid_params P; ssm_grid_params_default(&P); if (params) P = *params;
+    if (P.nx >= 1 && P.ny >= 1 && (int64_t)P.nx * P.ny > t->cap) return SSM_E_INVAL;
+    const int rc = ssm_grid_host(pts, n, Tc, m, &P, t->cls.data(), t->gl.data(), t->ol.data(), t->gq.data(), t->tq.data(), t->n.data(), t->nh.data(), nullptr, info);
+    if (rc == SSM_OK) { t->nx = P.nx; t->ny = P.ny; }
+    return rc;
+}
+int ssm_grid_clouds(ssm_ctx* c, ssm_grid_target* t, ssm_cloud* const* clouds, const double* Tc, int m, const ssm_grid_params* params, ssm_grid_info* info)
+{
+    std::vector<const ssm_point*> pts; std::vector<int32_t> n;
+    for (int k = 0; k < m; k++) { pts.push_back(clouds[k]->p.data()); n.push_back((int32_t)clouds[k]->p.size()); }
+    return ssm_grid_points(c, t, pts.data(), n.data(), Tc, m, params, info);
+}
+int ssm_grid_fetch(ssm_ctx*, const ssm_grid_target* t, uint8_t* cls, uint8_t* gl, uint8_t* ol, int32_t* gq, int32_t* tq, uint32_t* n, uint32_t* nh)
+{
+    const size_t nc = (size_t)t->nx * t->ny;
+    if (cls) memcpy(cls, t->cls.data(), nc);
+    if (gl) memcpy(gl, t->gl.data(), nc);
+    if (ol) memcpy(ol, t->ol.data(), nc);
+    if (gq) memcpy(gq, t->gq.data(), nc * 4);
+    if (tq) memcpy(tq, t->tq.data(), nc * 4);
+    if (n) memcpy(n, t->n.data(), nc * 4);
+    if (nh) memcpy(nh, t->nh.data(), nc * 4);
+    return SSM_OK;
+}
 // dense alignment (Mapper with mapper_align=1): a "view" is a host copy of the depth image, the linked host function in the device entry points' place
 struct ssm_align_view { std::vector<uint16_t> depth; int w, h; ssm_camera cam; double tol_abs; int32_t tol_rel_ppm; };
 int ssm_align_view_create(ssm_ctx*, const uint16_t* depth, int w, int h, const ssm_camera* cam, const ssm_align_params* params, ssm_align_view** out)
