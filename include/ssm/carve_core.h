@@ -42,8 +42,10 @@ inline void rel_pose(const double Tv[16], const double Tc[16], double M[12])
     }
 }
 
-// the verdict of the point (x, y, z) of a cloud whose relative pose is M, under the view `depth` (w x h, row-major, device or host memory alike)
-CARVE_HD int verdict_of(float xf, float yf, float zf, const double* M, const uint16_t* depth, const Setup& S)
+// the verdict of the point (x, y, z) of a cloud whose relative pose is M, under the view `depth` (w x h, row-major, device or host memory alike), and the pixel
+// it was decided at: (*px_out, *py_out) is written for every verdict but UNKNOWN-before-the-window (then both stay as they were).  Label fusion
+// (relabel_core.h) reads the view's label there; verdict_of below is this function with the pixel dropped
+CARVE_HD int verdict_at(float xf, float yf, float zf, const double* M, const uint16_t* depth, const Setup& S, int* px_out, int* py_out)
 {
     const double x = (double)xf, y = (double)yf, z = (double)zf;
     if (!(finite_d(x) && finite_d(y) && finite_d(z))) return UNKNOWN;
@@ -57,6 +59,7 @@ CARVE_HD int verdict_of(float xf, float yf, float zf, const double* M, const uin
     // (the comparisons are false for NaN; only a value inside the image ever becomes an int)
     if (!(pxd >= r && pxd <= (double)(S.w - 1) - r && pyd >= r && pyd <= (double)(S.h - 1) - r)) return UNKNOWN;
     const int px = (int)pxd, py = (int)pyd;
+    *px_out = px; *py_out = py;
     int32_t dmin = 65536;
     for (int dy = -S.r; dy <= S.r; dy++) {
         const uint16_t* row = depth + (size_t)(py + dy) * (size_t)S.w + (size_t)(px - S.r);
@@ -70,6 +73,11 @@ CARVE_HD int verdict_of(float xf, float yf, float zf, const double* M, const uin
     if (zq + tol < (int64_t)dmin) return SEEN_THROUGH;
     const int64_t diff = zq > d ? zq - d : d - zq;
     return diff <= tol ? SUPPORTED : OCCLUDED;
+}
+CARVE_HD int verdict_of(float xf, float yf, float zf, const double* M, const uint16_t* depth, const Setup& S)
+{
+    int px = 0, py = 0;
+    return verdict_at(xf, yf, zf, M, depth, S, &px, &py);
 }
 CARVE_HD uint8_t run_after(uint8_t run, int verdict)
 {

@@ -56,10 +56,19 @@
 // mapper_grid_forward (three numbers each, default `0 -1 0` and `0 0 1`) the grid frame.  Both routes give the same bytes: deviceCloud / ssm_grid_clouds and
 // frame->pointcloud / ssm_grid_points.  With mapper_grid_dir set the build writes grid_colour.png, grid_height.png (16 bit) and grid.txt (x0, y0, cell, nx, ny,
 // h_min, G: what georeferences the images) there.
+// mapper_relabel=1 (default 0: nothing of this runs, every cloud, map and figure exactly as before): label fusion (the reference has no such step).
+// When the viewer ends -- after the last alignCarveUpTo, before the rendering and the ground grid, which then see the fused labels -- relabelAll lets the key-frames
+// j != i with |i - j| <= mapper_relabel_window (5; at most 8: a call takes 16 views) vote on the labels of key-frame i's cloud, at the map poses (mapPoseOf), every
+// cloud exactly once in ascending order.  The views are the key-frames' depth and semantic IMAGES, never other clouds, so the order does not matter.  View objects
+// are made when first needed and freed once no later cloud needs them: at most 2 window + 1 are alive.  mapper_relabel_radius, _edge_guard, _own_weight, _votes set
+// the rule; the tolerances are carving's parameters.  Both routes give the same bytes: deviceCloud / ssm_relabel and frame->pointcloud / ssm_relabel_points.  Then
+// ONE more map update with rebuild = true runs through the update code of the loop (updateMap), so the published and saved map carries fused labels whatever the
+// thread's timing was.  relabelInfoOf(frame), relabelledKeyframes(); with mapper_relabel_hash=1 also relabelLabelFnv() (the driver's relabel_fnv).
 #pragma once
 #include "common_headers.h"
 #include <atomic>
 #include <iomanip>
+#include <map>
 #include <unordered_map>
 #include "device.h"
 #include "pose_graph.h"
@@ -113,6 +122,16 @@ public:
         align_params.max_angle = para.getData<double>("mapper_align_max_angle", align_params.max_angle);
         align_params.tol_abs = para.getData<double>("mapper_align_tol_abs", align_params.tol_abs);
         align_params.tol_rel_ppm = para.getData<int>("mapper_align_tol_rel_ppm", align_params.tol_rel_ppm);
+        relabel = para.getData<int>("mapper_relabel", 0) != 0;
+        relabel_window = para.getData<int>("mapper_relabel_window", 5);
+        relabel_hash = para.getData<int>("mapper_relabel_hash", 0) != 0;          // relabelLabelFnv() is wanted: costs one fetch of every cloud on the device route
+        ssm_relabel_params_default(&relabel_params);
+        relabel_params.radius = para.getData<int>("mapper_relabel_radius", relabel_params.radius);
+        relabel_params.edge_guard = para.getData<int>("mapper_relabel_edge_guard", relabel_params.edge_guard);
+        relabel_params.own_weight = para.getData<int>("mapper_relabel_own_weight", relabel_params.own_weight);
+        relabel_params.min_votes = para.getData<int>("mapper_relabel_votes", relabel_params.min_votes);
+        relabel_params.tol_abs = carve_params.tol_abs; relabel_params.tol_rel_ppm = carve_params.tol_rel_ppm; relabel_params.z_min = carve_params.z_min;
+        if (relabel && (relabel_window < 0 || relabel_window > 8)) throw std::runtime_error("Mapper: mapper_relabel_window must be 0..8 (a call takes 16 views)");
         grid = para.getData<int>("mapper_grid", 0) != 0;
         grid_dir = para.getData<string>("mapper_grid_dir", string(""));
         ssm_grid_params_default(&grid_params);
@@ -151,8 +170,38 @@ public:
             vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
             auto t0 = chrono::steady_clock::now();
             alignCarveUpTo(kfs);
+            updateMap(kfs, cntGlobalUpdate % 15 == 0, map, t0);
+        }
+        if (align || carve) {                           // the key-frames that came after the last update are aligned and are views too: the final state does not depend on this thread's timing
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            alignCarveUpTo(kfs);
+        }
+        if (relabel) {                                  // every cloud takes the label its neighbouring views agree on; then one rebuild, so the map carries the fused labels
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            auto t0 = chrono::steady_clock::now();
+            relabelAll(kfs);
+            if (!kfs.empty()) updateMap(kfs, true, map, t0);          // (without a key-frame there is no map to rebuild)
+        }
+        if (render) {                                   // every key-frame is a view of the clouds around it, in their final state
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            renderAll(kfs);
+        }
+        if (grid) {                                     // one ground grid of every key-frame's cloud, in its final state
+            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            buildGrid(kfs);
+        }
+        } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
+            cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
+        }
+        if (poseGraph.shutDownFlag && !map_output.empty()) { writePCD(map_output, *map); cout << "Map saved!" << endl; }
+        for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second);      // the device clouds belong to this thread's context
+        devClouds.clear();
+    }
+    // one map update (the body of the viewer's loop, src/mapper.cpp:121-171): the key-frames it adds, the device or the host route, the published map and the two lines
+    void updateMap(const vector<RGBDFrame::Ptr>& kfs, const bool rebuild, PointCloud::Ptr& map, chrono::steady_clock::time_point t0) {
+        {
             // the key-frames this update adds (mapper.cpp:121-141)
-            vector<RGBDFrame::Ptr> sel; const bool rebuild = cntGlobalUpdate % 15 == 0;
+            vector<RGBDFrame::Ptr> sel;
             if (rebuild) { for (size_t i = 0; i < kfs.size(); i += 2) sel.push_back(kfs[i]); }
             else if (fix_incremental) { for (int i = (int)kfs.size() - 1; i >= 0 && i > (int)kfs.size() - 6; i--) sel.push_back(kfs[i]); }
             else { for (int i = (int)kfs.size() - 1; i >= 0 && (size_t)i > kfs.size() - 6; i--) sel.push_back(kfs[i]); }      // size_t wrap as in mapper.cpp:134
@@ -204,24 +253,6 @@ public:
             cout << "points in global map: " << map->points.size() << endl;
             cout << "Mapping cost time: " << ms << "ms" << endl;
         }
-        if (align || carve) {                           // the key-frames that came after the last update are aligned and are views too: the final state does not depend on this thread's timing
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            alignCarveUpTo(kfs);
-        }
-        if (render) {                                   // every key-frame is a view of the clouds around it, in their final state
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            renderAll(kfs);
-        }
-        if (grid) {                                     // one ground grid of every key-frame's cloud, in its final state
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            buildGrid(kfs);
-        }
-        } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
-            cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
-        }
-        if (poseGraph.shutDownFlag && !map_output.empty()) { writePCD(map_output, *map); cout << "Map saved!" << endl; }
-        for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second);      // the device clouds belong to this thread's context
-        devClouds.clear();
     }
     // the device form of frame->pointcloud: made once per key-frame, kept in HBM (viewer thread only)
     ssm_cloud* deviceCloud(const RGBDFrame::Ptr& frame) {
@@ -576,6 +607,75 @@ public:
         if (n_high) *n_high = gridNHigh;
         return true;
     }
+    // label fusion: every key-frame's cloud, once, in ascending order, under the key-frames around it (their images, at the map poses).  The viewer thread calls
+    // this as it ends; once that has ended its owner may (the host route then: the device clouds went with the thread)
+    void relabelAll(const vector<RGBDFrame::Ptr>& kfs) {
+        relabelInfo.clear(); relabelled = 0; relabelFnv = relabel_hash ? 0xCBF29CE484222325ull : 0;
+        if (kfs.empty()) return;
+        const size_t n = kfs.size(), win = (size_t)max(relabel_window, 0);
+        ssm::Device& d = device(kfs[0]->depth.cols, kfs[0]->depth.rows);
+        struct Views {          // the view objects alive, freed on every way out
+            ssm_ctx* ctx; std::map<size_t, ssm_relabel_view*> v;
+            ~Views() { for (auto& kv : v) ssm_relabel_view_free(ctx, kv.second); }
+        } views{d.ctx(), {}};
+        for (size_t i = 0; i < n; i++) {
+            const size_t first = i > win ? i - win : 0, last = min(n - 1, i + win);
+            for (auto it = views.v.begin(); it != views.v.end();) {          // a view below the window of cloud i is below that of every later cloud
+                if (it->first < first) { ssm_relabel_view_free(d.ctx(), it->second); it = views.v.erase(it); } else ++it;
+            }
+            vector<const ssm_relabel_view*> list; vector<double> poses;
+            for (size_t j = first; j <= last; j++) {
+                if (j == i) continue;
+                auto it = views.v.find(j);
+                if (it == views.v.end()) {
+                    const RGBDFrame::Ptr& f = kfs[j];
+                    ssm_camera cam; cam.cx = f->camera.cx; cam.cy = f->camera.cy; cam.fx = f->camera.fx; cam.fy = f->camera.fy; cam.scale = f->camera.scale;
+                    ssm_relabel_view* v = nullptr;
+                    d.check(ssm_relabel_view_create(d.ctx(), f->depth.ptr<uint16_t>(), f->semantic.data, f->depth.cols, f->depth.rows, &cam, &v), "ssm_relabel_view_create");
+                    it = views.v.emplace(j, v).first;
+                }
+                list.push_back(it->second);
+                const Eigen::Isometry3d T = mapPoseOf(kfs[j]);
+                poses.insert(poses.end(), T.data(), T.data() + 16);
+            }
+            relabelViewsAlive = max(relabelViewsAlive, (int)views.v.size());
+            const Eigen::Isometry3d Tc = mapPoseOf(kfs[i]);
+            ssm_relabel_info I{};
+            if (device_map) {
+                d.check(ssm_relabel(d.ctx(), list.data(), poses.data(), (int)list.size(), deviceCloud(kfs[i]), Tc.data(), &relabel_params, &I), "ssm_relabel");
+            } else {
+                hostCloud(kfs[i]);
+                PointCloud& pc = *kfs[i]->pointcloud;
+                const int np = (int)pc.points.size();
+                vector<uint32_t> lab((size_t)max(np, 1));
+                ssm_point* pts = reinterpret_cast<ssm_point*>(pc.points.data());
+                d.check(ssm_relabel_points(d.ctx(), list.data(), poses.data(), (int)list.size(), pts, np, Tc.data(), &relabel_params, lab.data(), &I), "ssm_relabel_points");
+                for (int k = 0; k < np; k++) pts[k].label = lab[(size_t)k];
+            }
+            if (relabel_hash) {          // the labels as they are now (the device route: one fetch of the cloud), only when somebody reads the hash
+                vector<ssm_point> now((size_t)max(I.n_in, 1)); int got = 0;
+                if (device_map) d.check(ssm_cloud_fetch(d.ctx(), deviceCloud(kfs[i]), nullptr, now.data(), (int)now.size(), &got), "ssm_cloud_fetch");
+                else { got = I.n_in; if (got) memcpy((void*)now.data(), kfs[i]->pointcloud->points.data(), (size_t)got * sizeof(ssm_point)); }
+                for (int k = 0; k < got; k++) {
+                    const unsigned char* b = (const unsigned char*)&now[(size_t)k].label;
+                    for (int q = 0; q < 4; q++) { relabelFnv ^= b[q]; relabelFnv *= 0x100000001B3ull; }
+                }
+            }
+            relabelInfo[kfs[i].get()] = I;
+            relabelled++;
+        }
+    }
+    bool relabels() const { return relabel; }
+    int relabelledKeyframes() const { return relabelled; }                    // clouds relabelled by the last relabelAll
+    uint64_t relabelLabelFnv() const { return relabelFnv; }                    // mapper_relabel_hash=1: FNV-1a over every key-frame's label bytes after the last relabelAll, in order; else 0
+    int relabelMaxViewsAlive() const { return relabelViewsAlive; }            // the most view objects alive at once so far (2 window + 1 at most)
+    // what label fusion did to a key-frame's cloud (not while the viewer thread runs); false: relabelAll has not reached it, or the switch is off
+    bool relabelInfoOf(const RGBDFrame::Ptr& frame, ssm_relabel_info* info) const {
+        auto it = relabelInfo.find(frame.get());
+        if (it == relabelInfo.end()) return false;
+        if (info) *info = it->second;
+        return true;
+    }
     bool carves() const { return carve; }
     int carvedViews() const { return carveViews; }                            // views applied so far (a first key-frame has no earlier cloud and is none)
     // what carving did to a key-frame's cloud over all the views applied to it: n_in its size before the first, n_kept its size now, the verdicts and `removed` summed
@@ -653,6 +753,8 @@ protected:
     std::unordered_map<const RGBDFrame*, AlignResult> alignResult;       // key-frame -> its alignment and map pose (viewer thread, or its owner once that has ended)
     bool render = false; int render_window = 5, renderViews = 0; string render_dir; ssm_render_params render_params{};
     std::unordered_map<const RGBDFrame*, ssm_render_compare_info> renderInfo;      // key-frame -> its view's comparison (viewer thread, or its owner once that has ended)
+    bool relabel = false; int relabel_window = 5, relabelled = 0, relabelViewsAlive = 0; ssm_relabel_params relabel_params{}; bool relabel_hash = false; uint64_t relabelFnv = 0;
+    std::unordered_map<const RGBDFrame*, ssm_relabel_info> relabelInfo;  // key-frame -> what the views did to its labels (viewer thread, or its owner once that has ended)
     bool grid = false; string grid_dir; ssm_grid_params grid_params{}, gridSpec{}; GridInfo gridState;
     vector<uint8_t> gridCls, gridGroundLabel, gridObstacleLabel; vector<int32_t> gridGroundQ, gridTopQ; vector<uint32_t> gridN, gridNHigh;      // the last build's arrays
     std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)

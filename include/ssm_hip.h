@@ -628,6 +628,44 @@ int  ssm_debug_grid_form(ssm_ctx* ctx, int form);
 void ssm_grid_colours(const uint8_t* cls, const uint8_t* ground_label, const uint8_t* obstacle_label, const int32_t* ground_q, int nx, int ny, double h_min,
                       uint8_t* bgr_out, uint16_t* height_out);
 
+/* ---- label fusion: the key-frames around a cloud (the views: depth image, label image, camera, world pose) vote on the label of each of its points, and a point
+ * takes the label its views agree on.  The reference has no such step; DESIGN.md s.20 is the contract, include/ssm/relabel_core.h the arithmetic shared by the
+ * device path and the host function (device == host bit for bit).  A view votes for a point with the label at the point's pixel when carving's verdict (s.16) is
+ * SUPPORTED, that label is one of the palette's twelve and -- with edge_guard -- the whole (2 radius + 1)^2 window carries it.  The point's own label (unknown
+ * above 11) counts own_weight.  The largest count wins, the own label on a tie, else the lowest id; the label changes when the winner differs and has at least
+ * min_votes.  Only the 4 label bytes of a point are ever written.  At most 16 views per call.
+ * SSM_E_INVAL: v outside 0..16, a null view or the same view twice, a view or cloud of another context, a non-finite pose or camera, a scale outside (0, 1e6],
+ * radius outside 0..3, edge_guard outside 0..1, own_weight outside 0..15, min_votes outside 1..31, the tolerances and z_min outside carving's ranges */
+typedef struct { int32_t radius, edge_guard, own_weight, min_votes; double tol_abs; int32_t tol_rel_ppm, pad; double z_min; } ssm_relabel_params;
+/* n_supported, n_voted: points with at least one SUPPORTED / voting view; n_filled: the changed points whose label was unknown; pairs: (point, view) pairs */
+typedef struct { int32_t n_in, n_supported, n_voted, n_changed, n_filled, pad; int64_t pairs_supported, pairs_voted; } ssm_relabel_info;
+/* a view of the host function: label is the w x h image of ssm_relabel_labels_host */
+typedef struct { const uint16_t* depth; const uint8_t* label; int32_t w, h; ssm_camera cam; } ssm_relabel_host_view;
+typedef struct ssm_relabel_view ssm_relabel_view;
+void ssm_relabel_params_default(ssm_relabel_params* p);                  /* 1, 1, 1, 2, 0.05 m, 20000 ppm, 0.1 m */
+/* a view: the depth image is uploaded, the label image made on the device from the semantic BGR image (3 bytes per pixel, rows packed); both stay there until
+ * ssm_relabel_view_free */
+int  ssm_relabel_view_create(ssm_ctx* ctx, const uint16_t* depth_host, const uint8_t* sem_bgr_host, int w, int h, const ssm_camera* cam, ssm_relabel_view** view_out);
+void ssm_relabel_view_free(ssm_ctx* ctx, ssm_relabel_view* view);
+/* v views (T_views: v x 16 doubles, column-major world poses) on one device-resident cloud, relabelled in place; info may be NULL */
+int  ssm_relabel(ssm_ctx* ctx, const ssm_relabel_view* const* views, const double* T_views, int v, ssm_cloud* cloud, const double* T_cloud,
+                 const ssm_relabel_params* params, ssm_relabel_info* info);
+/* the same on n host points through the device: label_out gets every point's label afterwards (n entries) */
+int  ssm_relabel_points(ssm_ctx* ctx, const ssm_relabel_view* const* views, const double* T_views, int v, const ssm_point* pts, int n, const double* T_cloud,
+                        const ssm_relabel_params* params, uint32_t* label_out, ssm_relabel_info* info);
+/* the same on the CPU, no GPU.  votes_out (may be NULL): every point's twelve counts, 5 bits each, class l at bits 5 l .. 5 l + 4 */
+int  ssm_relabel_host(const ssm_relabel_host_view* views, const double* T_views, int v, const ssm_point* pts, int n, const double* T_cloud,
+                      const ssm_relabel_params* params, uint32_t* label_out, uint64_t* votes_out, ssm_relabel_info* info);
+/* the label image of n semantic BGR pixels: the palette's class, 255 for any other colour */
+int  ssm_relabel_labels_host(const uint8_t* sem_bgr, int64_t n, uint8_t* label_out);
+/* the packed counts and the labels of the context's last device call over its n points; each may be NULL */
+int  ssm_debug_relabel_record(ssm_ctx* ctx, uint64_t* votes, uint32_t* new_label, int n);
+/* a view's label image (w h bytes) */
+int  ssm_debug_relabel_view(ssm_ctx* ctx, const ssm_relabel_view* view, uint8_t* label_out);
+/* how the context's later views are stored and read, for the tests and the measurement: 0 a depth and a label image, 1 one packed word per pixel (depth |
+ * label << 16) that the vote gathers alone, 2 the same with the windows of two views in flight, -1 the default; the same bits either way.  A view votes only under the form it was made under */
+int  ssm_debug_relabel_form(ssm_ctx* ctx, int form);
+
 /* ---- dense alignment: projective point-to-plane ICP of the points of m posed clouds against a key-frame's depth image (the view).  The reference has no such
  * step; DESIGN.md s.18 is the contract, include/ssm/align_core.h the arithmetic shared by the device path and the host function.  The view gets a normal per
  * pixel (invalid at depth 0, at the border and across a depth edge: a neighbour farther than carving's tolerance).  Per iteration every point is carried into the

@@ -109,6 +109,19 @@ class RenderCompareInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("unrendered", "no_depth", "in_front", "behind", "agree", "label_agree", "label_disagree", "label_unknown", "n_pixels")]
 
 
+class RelabelParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("edge_guard", C.c_int32), ("own_weight", C.c_int32), ("min_votes", C.c_int32), ("tol_abs", C.c_double), ("tol_rel_ppm", C.c_int32),
+                ("pad", C.c_int32), ("z_min", C.c_double)]
+
+
+class RelabelInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_in", "n_supported", "n_voted", "n_changed", "n_filled", "pad")] + [("pairs_supported", C.c_int64), ("pairs_voted", C.c_int64)]
+
+
+class RelabelHostView(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("label", C.c_void_p), ("w", C.c_int32), ("h", C.c_int32), ("cam", Camera)]
+
+
 class GridParams(C.Structure):
     _fields_ = [("G", C.c_double * 12), ("x0", C.c_double), ("y0", C.c_double), ("cell", C.c_double), ("nx", C.c_int32), ("ny", C.c_int32), ("h_min", C.c_double),
                 ("h_max", C.c_double), ("step", C.c_double), ("ground_radius", C.c_int32), ("min_obstacle_points", C.c_int32)]
@@ -283,6 +296,16 @@ SYMBOLS = {
     "ssm_debug_grid_cells": (_I, [_P, _P, _P]),
     "ssm_debug_grid_form": (_I, [_P, _I]),
     "ssm_grid_colours": (None, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P]),
+    "ssm_relabel_params_default": (None, [C.POINTER(RelabelParams)]),
+    "ssm_relabel_view_create": (_I, [_P, _P, _P, _I, _I, C.POINTER(Camera), C.POINTER(_P)]),
+    "ssm_relabel_view_free": (None, [_P, _P]),
+    "ssm_relabel": (_I, [_P, _P, _P, _I, _P, _P, C.POINTER(RelabelParams), C.POINTER(RelabelInfo)]),
+    "ssm_relabel_points": (_I, [_P, _P, _P, _I, _P, _I, _P, C.POINTER(RelabelParams), _P, C.POINTER(RelabelInfo)]),
+    "ssm_relabel_host": (_I, [_P, _P, _I, _P, _I, _P, C.POINTER(RelabelParams), _P, _P, C.POINTER(RelabelInfo)]),
+    "ssm_relabel_labels_host": (_I, [_P, C.c_int64, _P]),
+    "ssm_debug_relabel_record": (_I, [_P, _P, _P, _I]),
+    "ssm_debug_relabel_view": (_I, [_P, _P, _P]),
+    "ssm_debug_relabel_form": (_I, [_P, _I]),
     "ssm_align_params_default": (None, [C.POINTER(AlignParams)]),
     "ssm_align_view_create": (_I, [_P, _P, _I, _I, C.POINTER(Camera), C.POINTER(AlignParams), C.POINTER(_P)]),
     "ssm_align_view_free": (None, [_P, _P]),

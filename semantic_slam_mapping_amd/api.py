@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, RelabelParams, RelabelInfo, RelabelHostView
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -353,6 +353,68 @@ def grid_colours(cls, ground_label, obstacle_label, ground_q, h_min=-3.0):
     bgr = np.zeros((ny, nx, 3), np.uint8); height = np.zeros((ny, nx), np.uint16)
     _lib.load().ssm_grid_colours(_ptr(cls), _ptr(gl), _ptr(ol), _ptr(gq), nx, ny, float(h_min), _ptr(bgr), _ptr(height))
     return bgr, height
+
+
+RELABEL_INFO_FIELDS = ("n_in", "n_supported", "n_voted", "n_changed", "n_filled", "pairs_supported", "pairs_voted")
+RELABEL_FIELDS = ("radius", "edge_guard", "own_weight", "min_votes", "tol_abs", "tol_rel_ppm", "z_min")
+
+
+def relabel_params(**kw):
+    """label fusion's parameters (ssm_relabel_params): the library's defaults (ssm_relabel_params_default) with the given fields replaced"""
+    bad = set(kw) - set(RELABEL_FIELDS)
+    if bad:
+        raise TypeError("unknown label-fusion parameters: " + ", ".join(sorted(bad)))
+    P = RelabelParams()
+    _lib.load().ssm_relabel_params_default(C.byref(P))
+    for k, v in kw.items():
+        setattr(P, k, float(v) if k in ("tol_abs", "z_min") else int(v))
+    return P
+
+
+def relabel_labels_host(sem_bgr):
+    """the label image of a semantic BGR image (h x w x 3 uint8) on the CPU (ssm_relabel_labels_host): the palette's class, 255 for any other colour"""
+    sem = np.ascontiguousarray(sem_bgr, np.uint8)
+    if sem.ndim != 3 or sem.shape[2] != 3:
+        raise ValueError("sem_bgr: h x w x 3")
+    out = np.zeros(sem.shape[:2], np.uint8)
+    lib = _lib.load()
+    rc = lib.ssm_relabel_labels_host(_ptr(sem), sem.shape[0] * sem.shape[1], _ptr(out))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return out
+
+
+def _relabel_poses(T_views):
+    v = len(T_views)
+    return np.ascontiguousarray(np.stack([_cm16(T) for T in T_views]) if v else np.zeros((1, 16)))
+
+
+def _relabel_info(I):
+    return {k: getattr(I, k) for k in RELABEL_INFO_FIELDS}
+
+
+def relabel_host(views, T_views, points, T_cloud, **params):
+    """label fusion on the CPU (ssm_relabel_host, no GPU): views is a list of (depth h x w uint16, label h x w uint8, camera = (cx, cy, fx, fy, scale)) at the world
+    poses T_views; they vote on the labels of `points`, a cloud at T_cloud -> (labels, votes, info): every point's label afterwards and its packed counts"""
+    points = _sor_points(points)
+    n, v = len(points), len(views)
+    if len(T_views) != v:
+        raise ValueError("one pose per view")
+    keep = []; arr = (RelabelHostView * max(v, 1))()
+    for k, (depth, label, camera) in enumerate(views):
+        depth = np.ascontiguousarray(depth, np.uint16); label = np.ascontiguousarray(label, np.uint8)
+        if depth.ndim != 2 or label.shape != depth.shape:
+            raise ValueError("a view's depth and label images have one size")
+        keep.append((depth, label))
+        arr[k] = RelabelHostView(depth.ctypes.data, label.ctypes.data, depth.shape[1], depth.shape[0], Camera(*camera))
+    P = relabel_params(**params); I = RelabelInfo()
+    labels = np.zeros(n, np.uint32); votes = np.zeros(n, np.uint64)
+    lib = _lib.load()
+    Tv, Tc = _relabel_poses(T_views), _cm16(T_cloud)          # (named: a pointer does not keep its array alive)
+    rc = lib.ssm_relabel_host(arr, _ptr(Tv), v, _ptr(points), n, _ptr(Tc), C.byref(P), _ptr(labels), _ptr(votes), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return labels, votes, _relabel_info(I)
 
 
 ALIGN_STATUS = ("max_iterations", "converged", "too_few", "degenerate", "diverged")
@@ -1324,6 +1386,66 @@ class Context:
         P = grid_params(**params); I = GridInfo()
         self._chk(self.lib.ssm_grid_viewer_map(self.h, target, C.byref(P), C.byref(I)))
         return self._grid_result(target, P, I, cells)
+
+    def relabel_view(self, depth, sem_bgr, camera=None):
+        """a view of label fusion: the depth image goes to the device and the label image is made there from the semantic BGR image (ssm_relabel_view_create) -> an
+        opaque handle (relabel_view_free it)"""
+        depth = np.ascontiguousarray(depth, np.uint16); sem = np.ascontiguousarray(sem_bgr, np.uint8)
+        h, w = depth.shape
+        if sem.shape != (h, w, 3):
+            raise ValueError("sem_bgr: h x w x 3, the depth image's size")
+        cam = Camera(*camera) if camera is not None else self.cfg.camera
+        v = C.c_void_p()
+        self._chk(self.lib.ssm_relabel_view_create(self.h, _ptr(depth), _ptr(sem), w, h, C.byref(cam), C.byref(v)))
+        self._relabel_sizes = getattr(self, "_relabel_sizes", {})
+        self._relabel_sizes[v.value] = (w, h)
+        return v.value
+
+    def relabel_view_free(self, view):
+        getattr(self, "_relabel_sizes", {}).pop(view, None)
+        self.lib.ssm_relabel_view_free(self.h, view)
+
+    def relabel_view_labels(self, view):
+        """the view's label image as the device made it (ssm_debug_relabel_view)"""
+        w, h = self._relabel_sizes[view]
+        out = np.zeros((h, w), np.uint8)
+        self._chk(self.lib.ssm_debug_relabel_view(self.h, view, _ptr(out)))
+        return out
+
+    def relabel_form(self, form):
+        """how later views are stored and read (ssm_debug_relabel_form): 0 a depth and a label image, 1 one packed word per pixel, 2 packed with two views in flight, -1 the default"""
+        self._chk(self.lib.ssm_debug_relabel_form(self.h, int(form)))
+
+    def relabel_record(self, n):
+        """every point's packed counts and label after the context's last device call over n points (ssm_debug_relabel_record) -> (votes, labels)"""
+        votes = np.zeros(n, np.uint64); labels = np.zeros(n, np.uint32)
+        self._chk(self.lib.ssm_debug_relabel_record(self.h, _ptr(votes), _ptr(labels), n))
+        return votes, labels
+
+    def relabel(self, views, T_views, cloud, T_cloud, **params):
+        """the views (relabel_view's handles at the world poses T_views) vote on the labels of a device-resident cloud (backproject_dev's handle) at T_cloud, which
+        changes in place (ssm_relabel) -> info"""
+        v = len(views)
+        if len(T_views) != v:
+            raise ValueError("one pose per view")
+        arr = (C.c_void_p * max(v, 1))(*views)
+        P = relabel_params(**params); I = RelabelInfo()
+        Tv, Tc = _relabel_poses(T_views), _cm16(T_cloud)
+        self._chk(self.lib.ssm_relabel(self.h, arr, _ptr(Tv), v, cloud, _ptr(Tc), C.byref(P), C.byref(I)))
+        return _relabel_info(I)
+
+    def relabel_points(self, views, T_views, points, T_cloud, **params):
+        """relabel_host's call through the device (ssm_relabel_points), views as for relabel -> (labels, info)"""
+        points = _sor_points(points)
+        n, v = len(points), len(views)
+        if len(T_views) != v:
+            raise ValueError("one pose per view")
+        arr = (C.c_void_p * max(v, 1))(*views)
+        P = relabel_params(**params); I = RelabelInfo()
+        labels = np.zeros(n, np.uint32)
+        Tv, Tc = _relabel_poses(T_views), _cm16(T_cloud)
+        self._chk(self.lib.ssm_relabel_points(self.h, arr, _ptr(Tv), v, _ptr(points), n, _ptr(Tc), C.byref(P), _ptr(labels), C.byref(I)))
+        return labels, _relabel_info(I)
 
     def align_view(self, depth, camera=None, **params):
         """a view of dense alignment: the depth image goes to the device and its normal map is built there (ssm_align_view_create; params: the edge gate) -> an

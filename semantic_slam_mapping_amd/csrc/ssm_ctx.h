@@ -202,6 +202,15 @@ struct ssm_grid_target {
 };
 // workspace of the ground grid: the info
 struct GridWork { DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; int form = GRID_FORM_DEFAULT; };          // form: ssm_debug_grid_form
+// a view of label fusion (ssm_relabel.hip): a key-frame's depth and label images in device memory and its camera; packed: depth | label << 16 per pixel, what
+// the vote gathers under the packed form (the default; the depth image is then freed once the view is made), empty under the other (ssm_debug_relabel_form)
+struct ssm_relabel_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> label; DevBuf<uint32_t> packed; int w = 0, h = 0, device = 0; const ssm_ctx* owner = nullptr; ssm_camera cam{}; };
+// workspace of label fusion for cap points: every point's record of the last device call (n points, n < 0: none yet; ssm_debug_relabel_record), the info, and the
+// staging of the host-array call (in_cap points)
+struct RelabelWork {
+    int cap = 0, n = -1, form = RELABEL_FORM_DEFAULT; size_t in_cap = 0;
+    DevBuf<uint64_t> votes; DevBuf<uint32_t> new_label; DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; DevBuf<ssm_point> in;
+};
 // a view of dense alignment (ssm_align.hip): a key-frame's depth image and its normal map (16 bytes per pixel) in device memory, its camera and edge gate
 struct ssm_align_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> normals; int w = 0, h = 0, device = 0; ssm_camera cam{}; double tol_abs = 0; int32_t tol_rel_ppm = 0; };
 // workspace of dense alignment: one slot of sums per iteration, and the last device call's iterations (ssm_debug_align_record)
@@ -295,6 +304,7 @@ struct ssm_ctx {
     RenderWork render;                                       // map rendering: likewise
     AlignWork align;                                         // dense alignment: likewise
     GridWork grid;                                           // ground grid: likewise
+    RelabelWork relabel;                                     // label fusion: likewise
     CloudTableWork clouds;                                   // the cloud table and host-array staging of the three: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet
     // profiling

@@ -1,4 +1,4 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_cloud_table.cpp, ssm_track_host.cpp:
+// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_relabel_host.cpp, ssm_cloud_table.cpp, ssm_track_host.cpp:
 // plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units; ssm_orb_plan.cpp and ssm_map_plan.cpp are host-only sources with headers of their own.  Those sources are compiled once and LINKED into libssm_hip.so, into the
 // CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
 // defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
@@ -13,6 +13,7 @@
 #include "../../include/ssm/render_core.h"
 #include "../../include/ssm/align_core.h"
 #include "../../include/ssm/grid_core.h"
+#include "../../include/ssm/relabel_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
 #include "cloud_table.h"
@@ -120,6 +121,12 @@ SSM_HIDDEN int render_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* 
 SSM_HIDDEN int grid_check(ssm_ctx* c, const ssm_grid_params& P, ssm_gridc::Setup* S);
 SSM_HIDDEN int grid_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total);                                // SSM_E_INVAL for a negative count or 2^31 points and more
 SSM_HIDDEN const char* grid_twice_msg();
+
+// ---------------------------------------------------------------- label fusion (ssm_relabel_host.cpp)
+// the number of views and the parameters a call may have (host function and device entry points alike)
+SSM_HIDDEN int relabel_check(ssm_ctx* c, int v, const ssm_relabel_params& P);
+// one view's size, camera and pose checked -> V->S and V->M (T_cloud: checked by the caller); the image pointers are the caller's to fill
+SSM_HIDDEN int relabel_view_fill(ssm_ctx* c, int w, int h, const ssm_camera* cam, const double* T_view, const double* T_cloud, const ssm_relabel_params& P, ssm_relabelc::View* V);
 
 // ---------------------------------------------------------------- dense alignment (ssm_align_host.cpp)
 // the arguments a call may have (host function and device entry points alike); S: what the view's size and camera and the parameters become for align_core.h

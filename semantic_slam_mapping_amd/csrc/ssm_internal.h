@@ -271,6 +271,18 @@ struct GridBufs { ssm_grid_cell* cells; uint8_t *cls, *ground_label, *obstacle_l
 int k_grid_block();
 hipError_t k_grid(const ssm_gridc::Setup& S, const CloudSeg* seg, const int32_t* blk, int64_t total, const GridBufs& T, unsigned long long* info, int form, hipStream_t s);
 
+// label fusion (kernels_relabel.hip; the arithmetic is include/ssm/relabel_core.h): A.v views vote on the labels of the n points at pts, which change in place
+// (the 4 label bytes of a changed point).  votes, new_label: every point's record, n entries; info: 6 x uint64 (n_supported, n_voted, n_changed, n_filled,
+// pairs_supported, pairs_voted), cleared by the launcher.  form: RELABEL_FORM_IMAGES reads a view's depth and label images (View::depth, View::label),
+// RELABEL_FORM_PACKED one uint32 per pixel, depth | label << 16 (View::depth points at it), 1.4 - 1.5 times faster; RELABEL_FORM_PAIRS the packed image with the windows of two views in flight before either is
+// judged: the default, another 10 - 15 % (profiles/r22_relabel.md); the same bits.  k_relabel_labels makes a view's label image from its
+// semantic BGR image and, with packed not null, the packed image from that and the depth image.  Both queue on s and wait for nothing.
+#include "../../include/ssm/relabel_core.h"
+enum { RELABEL_FORM_IMAGES = 0, RELABEL_FORM_PACKED = 1, RELABEL_FORM_PAIRS = 2, RELABEL_FORM_DEFAULT = RELABEL_FORM_PAIRS };
+struct RelabelArgs { ssm_relabelc::View view[ssm_relabelc::MAX_VIEWS]; int32_t v, edge_guard, own_weight, min_votes; };
+hipError_t k_relabel_labels(const uint8_t* bgr, const uint16_t* depth, int64_t np, uint8_t* label, uint32_t* packed, hipStream_t s);
+hipError_t k_relabel(const RelabelArgs& A, int form, ssm_point* pts, int n, uint64_t* votes, uint32_t* new_label, unsigned long long* info, hipStream_t s);
+
 // dense alignment (kernels_align.hip; the arithmetic is include/ssm/align_core.h).  seg, blk: the cloud table (cloud_table.h) of the points USED (every stride-th
 // of a cloud), with chunks of k_align_block() points as its blocks.  k_align_normals fills a view's normal map (16 bytes per pixel); k_align_accumulate adds one
 // iteration's NSUM 64-bit sums under the increment E (12 doubles, host memory) to sums, which the caller has zeroed.  Both queue on s and wait for nothing.

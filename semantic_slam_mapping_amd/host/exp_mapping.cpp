@@ -34,6 +34,9 @@
 // rendered images are written there as PNG.  The summary line then carries `render_views V render_agree A render_in_front F render_behind B render_label_agree L
 // render_label_disagree D render_fnv H`: the views, the sums of those counts over them, and FNV-1a over every view's nine counts in key-frame order (the same in both
 // modes: it runs once, at the end).  Without the flag nothing of this runs and the line is as before.
+// `exp_mapping <parameters> --relabel` (or mapper_relabel=1): when the viewer ends, every key-frame's cloud takes the labels its neighbouring key-frames agree on (label
+// fusion: include/ssm/mapper.h), before the rendering and the grid, and one more map rebuild follows.  The summary line then carries `relabel_keyframes K
+// relabel_changed C relabel_filled F relabel_fnv H`: H is FNV-1a over every key-frame's label bytes, in order.  Without the flag nothing of this runs.
 // `exp_mapping <parameters> --grid [DIR]` (or mapper_grid=1, mapper_grid_dir=DIR): when the viewer ends, Mapper builds ONE ground grid from every key-frame's cloud at
 // its map pose (include/ssm/mapper.h); with DIR grid_colour.png, grid_height.png and grid.txt are written there.  The summary line then carries
 // `grid_cells C grid_drivable D grid_walkable W grid_obstacle O grid_fnv H`: the cells of the grid, three of its class counts, and FNV-1a over nx, ny and the fetched
@@ -163,6 +166,9 @@ int main(int argc, char** argv)
         if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_grid_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
     }
     if (grid) parameterReader.set("mapper_grid", "1");
+    bool relabel = parameterReader.getData<int>("mapper_relabel", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--relabel") relabel = true;
+    if (relabel) { parameterReader.set("mapper_relabel", "1"); parameterReader.set("mapper_relabel_hash", "1"); }
     MovingLog moving_log;
     for (int i = 2; i + 1 < argc; i++) {
         if (string(argv[i]) == "--ranks") nranks = atoi(argv[i + 1]);
@@ -442,6 +448,13 @@ int main(int argc, char** argv)
             }
             cout << " render_views " << mapper.renderedViews() << " render_agree " << agree << " render_in_front " << in_front << " render_behind " << behind
                  << " render_label_agree " << lab_agree << " render_label_disagree " << lab_dis << " render_fnv " << hex << h << dec;
+        }
+        if (relabel) {          // (the viewer thread relabelled every key-frame's cloud as it ended)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before the clouds were relabelled" << endl; return 3; }
+            long long changed = 0, filled = 0;
+            for (RGBDFrame::Ptr& kf : poseGraph.keyframes) { ssm_relabel_info I{}; mapper.relabelInfoOf(kf, &I); changed += I.n_changed; filled += I.n_filled; }
+            cout << " relabel_keyframes " << mapper.relabelledKeyframes() << " relabel_changed " << changed << " relabel_filled " << filled << " relabel_fnv " << hex
+                 << mapper.relabelLabelFnv() << dec;
         }
         if (grid) {             // (the viewer thread built the grid of every key-frame's cloud as it ended)
             if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before the ground grid was built" << endl; return 3; }

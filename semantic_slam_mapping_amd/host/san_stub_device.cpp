@@ -2,7 +2,7 @@
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
 // which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_cloud_table.cpp,
+// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_relabel_host.cpp, ssm_cloud_table.cpp,
 // ssm_track_host.cpp, ssm_map_plan.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
 // "no device" form of csrc/ssm_host.h's hooks here (the bulk tracker's among them: no tracker is ever created on the stub; its state machine runs under the sanitizers
 // in host/test_track.cpp, over hooks of that program's own).  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
@@ -187,6 +187,28 @@ int ssm_grid_fetch(ssm_ctx*, const ssm_grid_target* t, uint8_t* cls, uint8_t* gl
     if (n) memcpy(n, t->n.data(), nc * 4);
     if (nh) memcpy(nh, t->nh.data(), nc * 4);
     return SSM_OK;
+}
+// label fusion (Mapper with mapper_relabel=1): a "view" is a host copy of the depth image and the label image, the linked host function in the device entry points' place
+struct ssm_relabel_view { std::vector<uint16_t> depth; std::vector<uint8_t> label; int w, h; ssm_camera cam; };
+int ssm_relabel_view_create(ssm_ctx*, const uint16_t* depth, const uint8_t* sem, int w, int h, const ssm_camera* cam, ssm_relabel_view** out)
+{
+    ssm_relabel_view* v = new ssm_relabel_view(); v->depth.assign(depth, depth + (size_t)w * h); v->label.resize((size_t)w * h); v->w = w; v->h = h; v->cam = *cam;
+    ssm_relabel_labels_host(sem, (int64_t)w * h, v->label.data()); *out = v; return SSM_OK;
+}
+void ssm_relabel_view_free(ssm_ctx*, ssm_relabel_view* v) { delete v; }
+int ssm_relabel_points(ssm_ctx*, const ssm_relabel_view* const* views, const double* Tv, int v, const ssm_point* pts, int n, const double* Tc, const ssm_relabel_params* params,
+                       uint32_t* label_out, ssm_relabel_info* info)
+{
+    std::vector<ssm_relabel_host_view> hv;
+    for (int k = 0; k < v; k++) { if (!views[k]) return SSM_E_INVAL; ssm_relabel_host_view h; h.depth = views[k]->depth.data(); h.label = views[k]->label.data(); h.w = views[k]->w; h.h = views[k]->h; h.cam = views[k]->cam; hv.push_back(h); }
+    return ssm_relabel_host(hv.data(), Tv, v, pts, n, Tc, params, label_out, nullptr, info);
+}
+int ssm_relabel(ssm_ctx* c, const ssm_relabel_view* const* views, const double* Tv, int v, ssm_cloud* cl, const double* Tc, const ssm_relabel_params* params, ssm_relabel_info* info)
+{
+    std::vector<uint32_t> lab(cl->p.size() + 1);
+    const int rc = ssm_relabel_points(c, views, Tv, v, cl->p.data(), (int)cl->p.size(), Tc, params, lab.data(), info);
+    if (rc == SSM_OK) for (size_t i = 0; i < cl->p.size(); i++) cl->p[i].label = lab[i];
+    return rc;
 }
 // dense alignment (Mapper with mapper_align=1): a "view" is a host copy of the depth image, the linked host function in the device entry points' place
 struct ssm_align_view { std::vector<uint16_t> depth; int w, h; ssm_camera cam; double tol_abs; int32_t tol_rel_ppm; };
