@@ -66,7 +66,9 @@ typedef struct {
     int    max_batch;                /* frames per batched launch (device workspace is sized for this) */
     int    voxel_capacity_log2;      /* slots the context's voxel map STARTS with = 2^this (8..28).  The map grows by itself like the reference's globalMap
                                         (src/mapper.cpp:121-158): it is re-hashed into a larger table whenever it is a quarter full */
-    const int8_t* brief_pattern;     /* NULL = built-in 256x4 table; else 1024 int8 (x0,y0,x1,y1)*256 */
+    const int8_t* brief_pattern;     /* NULL = built-in 256x4 table; else 1024 int8 (x0,y0,x1,y1)*256.  Every point must have x^2 + y^2 <= SSM_BRIEF_MAX_R2 (342): turned by
+                                        the keypoint's angle it then rounds to at most 18 (sqrt(342) = 18.493), the reach of the patch the BRIEF kernel stages;
+                                        ssm_create refuses any other table with SSM_E_INVAL (before it looks for a device) */
     int    voxel_max_capacity_log2;  /* the map never grows beyond 2^this slots (default and maximum 28: 30 GB); a map that needs more fails with SSM_E_CAPACITY */
     /* the stereo path (configs[3]).  0 = the default of each */
     int    sgbm_form;                /* SGBM formulation: 2 (default) = two volumes, top-down sweep with strip hand-offs; 1 = four path volumes, no cross-block waits
@@ -74,6 +76,8 @@ typedef struct {
     int    sgbm_streams;             /* 1 | 2 | 3 streams (and workspaces) that alternate sub-batches of the batched stereo path; default 2 */
     int    stereo_batch;             /* frame pairs per launch of ssm_stereo_seq_process; default: max_batch, at most 128 */
 } ssm_config;
+
+#define SSM_BRIEF_MAX_R2 342             /* largest x^2 + y^2 of a brief_pattern point */
 
 typedef struct ssm_ctx ssm_ctx;
 
@@ -854,6 +858,28 @@ int ssm_segnet_debug_op(ssm_ctx* ctx, int op, int arg, const uint16_t* in, int H
  * calls run, > 0 = the fused kernel with that many bands (SSM_E_INVAL where the geometry has no fused form at that band count).  *bytes: one frame's
  * buffer (img and out both NULL: only that) */
 int ssm_debug_pyramid(ssm_ctx* ctx, const uint8_t* img, int channels, int n, int bands, uint8_t* out, int* bytes);
+/* the BLURRED pyramid of n frames (host, as for ssm_debug_pyramid; n <= max_batch), for exact tests of the blur kernels on every pixel: the pyramid is built the
+ * way the ORB calls build it, then blurred by the launch they make -- the variant the context was created with (SSM_BLUR_VARIANT=0 at ssm_create: the VALU
+ * kernel, else the matrix-core one).  out: n x ssm_debug_pyramid's buffer, in ITS layout -- level l at the same offset, rows of `stride` bytes -- so that
+ * byte i here is the 7x7 Gaussian (taps 18 34 49 55 49 34 18 / 256, BORDER_REFLECT_101, (v + 2^15) >> 16, saturated) at the pixel whose level image is byte i
+ * there.  The padding columns [w, stride) of every row are zero.  The device keeps the blurred pyramid in tiles of 8 rows x 16 columns; the un-tiling is a
+ * host loop over that layout, so a wrong tile offset shows as wrong pixels.  *bytes: one frame's buffer (img and out both NULL: only that) */
+int ssm_debug_orb_blur(ssm_ctx* ctx, const uint8_t* img, int channels, int n, uint8_t* out, int* bytes);
+/* the describe stage (slot bookkeeping, orientation moments, angle + sin / cos + keypoint record + position, steered BRIEF) on a PLANTED selection, for exact
+ * tests at chosen keypoints: pyramid and blurred pyramid of n frames as above, then the describe launches exactly as the ORB calls make them, with the
+ * selection uploaded in place of FAST's and the quad-tree's.
+ *   nsel     n x orb_levels counts; count of level l: 0 .. (features of the level + 3), the slots the level has
+ *   sel      the planted keypoints of all frames, frame by frame and level by level, sum(nsel) words x | y << 12 | score << 24 in level coordinates.
+ *            Every point must lie in [19, w_l - 19) x [19, h_l - 19): the window FAST reports in and the kernels rely on (their patch loads have no border case)
+ *   depth    NULL, or n depth images (w x h uint16, rows packed); moments: NULL, or (m10, m01) per planted keypoint, in sel's order: they replace the
+ *            orientation kernel's sums before the angle is taken from them, so any pair can be put through atan2 / sin / cos and the BRIEF that follows
+ *   outputs  nkp: n counts; kps, desc (32 bytes each), pos3d (3 floats each), moments_out (m10, m01) and sincos_out (sin, cos): n x ssm_orb_capacity
+ *            records each, frame f from f x capacity on, in output order = sel's order; all required.  Records from nkp[f] on are not written by the kernels
+ *            and come back as bytes 0xA5.  pos3d is project2dTo3d at the truncated level-0 position, zero without a depth image or at depth 0
+ * SSM_E_INVAL, on the host and before anything is launched: n outside 1 .. max_batch, a count outside its range, a point outside its window.  The context's
+ * later ORB calls are not affected (they overwrite the selection). */
+int ssm_debug_orb_describe(ssm_ctx* ctx, const uint8_t* img, int channels, int n, const uint16_t* depth, const int32_t* nsel, const uint32_t* sel,
+                           const int32_t* moments, int32_t* nkp, ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* moments_out, float* sincos_out);
 /* the FAST tile plan of a configuration, on the host only (no context, no device): for exact tests of the tiling.  Per tile, 16 ints:
  * level, interior x0, x1, y0, y1 (half-open), scored rectangle xs0, xs1, ys0, ys1 (interior + 1 on each side, clipped to the FAST window
  * [19, w - 19) x [19, h - 19)), 4-column groups, scored rows, cell columns and cell rows the scored rectangle touches, level w, h, stride.

@@ -149,6 +149,16 @@ class Oracle:
         finally:
             self.L.sso_orb_destroy(o)
 
+    def fast_atan2(self, y, x):
+        """sso_fast_atan2 (degrees, float32) of float32 y, x"""
+        return np.float32(self.L.sso_fast_atan2(C.c_float(float(np.float32(y))), C.c_float(float(np.float32(x)))))
+
+    def sincos(self, angle_rad):
+        """sso_sincos: the contract's (sin, cos) of a float32 angle in radians"""
+        s, c = C.c_float(), C.c_float()
+        self.L.sso_sincos(C.c_float(float(np.float32(angle_rad))), C.byref(s), C.byref(c))
+        return np.float32(s.value), np.float32(c.value)
+
     def project2dTo3d(self, depth, cam, u, v):
         depth = np.ascontiguousarray(depth, np.uint16); h, w = depth.shape
         out = np.zeros(3, np.float32); c = Cam(*cam)

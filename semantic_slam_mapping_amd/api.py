@@ -850,8 +850,12 @@ class Context:
 
     def __init__(self, device=0, cfg=None, **kw):
         self.lib = _lib.load()
+        pattern = kw.pop("brief_pattern", None)             # a 256 x 4 int8 table (x0, y0, x1, y1): copied by ssm_create, kept alive until then
         self.cfg = cfg if cfg is not None else default_config(**kw)
         self._pattern_keep = None
+        if pattern is not None:
+            self._pattern_keep = np.ascontiguousarray(pattern, np.int8).reshape(1024)
+            self.cfg.brief_pattern = self._pattern_keep.ctypes.data
         self._inflight = []                 # output buffers of asynchronous calls that have not been waited for
         h = C.c_void_p()
         rc = self.lib.ssm_create(device, C.byref(self.cfg), C.byref(h))
@@ -1065,6 +1069,54 @@ class Context:
         img = np.zeros((h.value, w.value), np.uint8); der = np.zeros((h.value, w.value, 2), np.int16)
         self._chk(self.lib.ssm_debug_quad_pyramid(self.h, side, level, _ptr(img), _ptr(der), C.byref(w), C.byref(h)))
         return img, der
+
+    def _debug_frames(self, img):
+        img = np.ascontiguousarray(img, np.uint8)
+        if img.ndim not in (3, 4) or img.shape[1:3] != (self.H, self.W) or (img.ndim == 4 and img.shape[3] != 3):
+            raise ValueError("frames must be (n, H, W) gray or (n, H, W, 3) BGR of the context's size")
+        return img, (1 if img.ndim == 3 else 3)
+
+    def debug_pyramid(self, img, bands=0):
+        """ssm_debug_pyramid: the pyramid buffers (n, bytes) of n frames, (n, H, W) gray or (n, H, W, 3) BGR"""
+        img, ch = self._debug_frames(img)
+        nbytes = C.c_int(0)
+        self._chk(self.lib.ssm_debug_pyramid(self.h, None, ch, len(img), bands, None, C.byref(nbytes)))
+        out = np.zeros((len(img), nbytes.value), np.uint8)
+        self._chk(self.lib.ssm_debug_pyramid(self.h, _ptr(img), ch, len(img), bands, _ptr(out), C.byref(nbytes)))
+        return out
+
+    def debug_orb_blur(self, img):
+        """ssm_debug_orb_blur: the blurred pyramids (n, bytes) of n frames, un-tiled into debug_pyramid's layout"""
+        img, ch = self._debug_frames(img)
+        nbytes = C.c_int(0)
+        self._chk(self.lib.ssm_debug_orb_blur(self.h, None, ch, len(img), None, C.byref(nbytes)))
+        out = np.zeros((len(img), nbytes.value), np.uint8)
+        self._chk(self.lib.ssm_debug_orb_blur(self.h, _ptr(img), ch, len(img), _ptr(out), C.byref(nbytes)))
+        return out
+
+    def debug_orb_describe(self, img, nsel, sel, depth=None, moments=None):
+        """ssm_debug_orb_describe: the describe stage on planted keypoints.  nsel (n, levels) counts; sel: the packed words x | y << 12 | score << 24 of all
+        frames, frame by frame and level by level; depth (n, H, W) uint16 or None; moments (len(sel), 2) planted (m10, m01) or None.  Returns a dict of
+        whole (n, capacity, ...) arrays: nkp, kps, desc, pos3d, moments (m10, m01), sincos (sin, cos); records from nkp[f] on hold the bytes 0xA5"""
+        img, ch = self._debug_frames(img)
+        n = len(img)
+        nsel = np.ascontiguousarray(nsel, np.int32); sel = np.ascontiguousarray(sel, np.uint32).reshape(-1)
+        if nsel.shape != (n, self.cfg.orb_levels) or (nsel >= 0).all() and int(nsel.sum()) != len(sel):
+            raise ValueError("nsel must be (n, levels) and sum to len(sel)")
+        if depth is not None:
+            depth = np.ascontiguousarray(depth, np.uint16)
+            if depth.shape != (n, self.H, self.W):
+                raise ValueError("depth must be (n, H, W)")
+        if moments is not None:
+            moments = np.ascontiguousarray(moments, np.int32)
+            if moments.shape != (len(sel), 2):
+                raise ValueError("moments must be (len(sel), 2)")
+        m = max(n, 1)
+        out = {"nkp": np.zeros(m, np.int32), "kps": np.zeros((m, self.cap), KEYPOINT_DTYPE), "desc": np.zeros((m, self.cap, 32), np.uint8),
+               "pos3d": np.zeros((m, self.cap, 3), np.float32), "moments": np.zeros((m, self.cap, 2), np.int32), "sincos": np.zeros((m, self.cap, 2), np.float32)}
+        self._chk(self.lib.ssm_debug_orb_describe(self.h, _ptr(img), ch, n, _ptr(depth), _ptr(nsel), _ptr(sel), _ptr(moments), _ptr(out["nkp"]), _ptr(out["kps"]),
+                                                  _ptr(out["desc"]), _ptr(out["pos3d"]), _ptr(out["moments"]), _ptr(out["sincos"])))
+        return out
 
     def window_match(self, kp1, d1, kp2, d2, sw, sh, thr):
         kp1 = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2); kp2 = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)

@@ -1645,7 +1645,8 @@ brief_kernel(OrbGeom g, const uint8_t* __restrict__ blur, const KpRec* __restric
     // steered BRIEF: lane -> 4 of the 256 comparisons.  The pattern arrives as floats (converted once on the host); the rotation runs on packed
     // pairs -- (x0, x1) and (y0, y1) of a comparison through v_pk_mul_f32 / v_pk_add_f32: the same IEEE multiplies and adds in the same order as the
     // scalar form (no contraction) -- and cvRound is the 1.5 * 2^23 trick: adding 12582912.0f rounds to nearest-even in the adder and leaves the
-    // integer in the low mantissa bits (|value| <= 18.4)
+    // integer in the low mantissa bits (|value| < 18.5, so the rounded coordinate stays inside the staged +-18: ssm_create admits only tables whose points have
+    // x^2 + y^2 <= SSM_BRIEF_MAX_R2)
     typedef float f2 __attribute__((ext_vector_type(2)));
     const float4* pf = reinterpret_cast<const float4*>(pattern_f) + lane * 4;
     const float4 pq[4] = {pf[0], pf[1], pf[2], pf[3]};
@@ -1726,7 +1727,7 @@ brief_kernel(OrbGeom g, const uint8_t* __restrict__ blur, const KpRec* __restric
 }
 hipError_t k_describe(int n, const OrbGeom& g, const uint8_t* pyr, const uint8_t* blur, const uint32_t* sel,
                       const int32_t* nsel, const float* pattern_f, const uint16_t* depth, ssm_camera cam, void* kpaux,
-                      ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp, hipStream_t s)
+                      ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp, hipStream_t s, const void* planted_aux)
 {
     unsigned long long um = 0;
     for (int v = 0; v <= SSM_HALF_PATCH; v++) um |= (unsigned long long)(g.umax[v] & 15) << (4 * v);
@@ -1734,6 +1735,10 @@ hipError_t k_describe(int n, const OrbGeom& g, const uint8_t* pyr, const uint8_t
     KpRec* recs = reinterpret_cast<KpRec*>(aux + (size_t)n * g.sel_total);       // second half of the buffer
     kp_prepare_kernel<<<dim3((g.sel_total + 255) / 256, n), 256, 0, s>>>(g, sel, nsel, recs, nkp);
     orient_kernel<<<dim3((n + 7) & ~7, (g.sel_total + 4 * OR_KPW - 1) / (4 * OR_KPW)), 256, 0, s>>>(g, um, pyr, recs, aux, n);
+    if (planted_aux) {                                                           // ssm_debug_orb_describe alone: planted moments take the place of orient_kernel's
+        const hipError_t e = hipMemcpyAsync(aux, planted_aux, (size_t)n * g.sel_total * sizeof(KpAux), hipMemcpyDeviceToDevice, s);
+        if (e != hipSuccess) return e;
+    }
     angle_kernel<<<dim3((g.sel_total + 255) / 256, n), 256, 0, s>>>(g, recs, depth, cam, aux, kps, pos3d);
     brief_kernel<<<dim3((n + 7) & ~7, (g.sel_total + 4 * BR_KPW * BR_NIT - 1) / (4 * BR_KPW * BR_NIT)), 256, 0, s>>>(g, blur, recs, pattern_f, aux, desc, n);
     return hipGetLastError();

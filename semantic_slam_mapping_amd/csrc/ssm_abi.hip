@@ -165,6 +165,16 @@ extern "C" int ssm_create(int device, const ssm_config* cfg, ssm_ctx** out)
 {
     if (!cfg || !out) { g_create_err = "null argument"; return SSM_E_INVAL; }
     *out = nullptr;
+    // brief_kernel stages the rows and columns -18 .. +18 around a keypoint: a pattern point (x, y) turned by any angle lands on a coordinate of at most
+    // sqrt(x^2 + y^2), which rounds to at most 18 while x^2 + y^2 <= 342 (sqrt(342) = 18.493).  Checked first: no device is needed to refuse a table
+    if (cfg->brief_pattern)
+        for (int i = 0; i < 512; i++) {
+            const int x = cfg->brief_pattern[2 * i], y = cfg->brief_pattern[2 * i + 1];
+            if (x * x + y * y > SSM_BRIEF_MAX_R2) {
+                g_create_err = "brief_pattern point " + std::to_string(i) + " (" + std::to_string(x) + ", " + std::to_string(y) + "): x^2 + y^2 must be <= " + std::to_string(SSM_BRIEF_MAX_R2);
+                return SSM_E_INVAL;
+            }
+        }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0) { g_create_err = std::string("no HIP device: ") + hipGetErrorString(e); return SSM_E_NODEVICE; }
@@ -285,6 +295,13 @@ static int make_pyramid(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_
     prof_begin(c, s, "pyramid");   HIPCHK(c, k_pyramid(nb, g, w.pyr, c->pyr_tabs.xofs, c->pyr_tabs.xa, c->pyr_tabs.yofs, c->pyr_tabs.ya, c->pyr_tabs.xgrp, s)); prof_end(c, s);
     return SSM_OK;
 }
+// the blurred pyramid of nb frames from w.pyr, by the variant the context was created with (orb_detect, and the two ssm_debug_orb_* hooks)
+static int orb_pyr_blur(ssm_ctx* c, hipStream_t s, OrbWork& w, int nb)
+{
+    const OrbGeom& g = c->g;
+    prof_begin(c, s, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(nb, g, w.pyr, w.blur, c->d_blur_tab, s) : k_blur(nb, g, w.pyr, w.blur, s)); prof_end(c, s);
+    return SSM_OK;
+}
 // run_orb in two halves, because the per-frame call (orb_extract_enqueue) has host work to do between them: everything in front of the one kernel that reads the depth image ...
 static int orb_detect(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_img, int channels, int nb)
 {
@@ -292,13 +309,13 @@ static int orb_detect(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_im
     { const int r = make_pyramid(c, s, w, d_img, channels, nb, nb > 1 ? c->pyr_bands : c->pyr_bands1); if (r) return r; }
     prof_begin(c, s, "fast");      HIPCHK(c, k_fast(nb, g, w.pyr, w.cand, w.ncand, w.cellmax, s)); prof_end(c, s);
     prof_begin(c, s, "octree");    HIPCHK(c, k_octree(nb, g, w.cand, w.ncand, w.cellmax, w.nodeof, w.sel, w.nsel, c->d_status, s)); prof_end(c, s);
-    prof_begin(c, s, "blur");      HIPCHK(c, c->blur_mfma ? k_blur_mfma(nb, g, w.pyr, w.blur, c->d_blur_tab, s) : k_blur(nb, g, w.pyr, w.blur, s)); prof_end(c, s);
-    return SSM_OK;
+    return orb_pyr_blur(c, s, w, nb);
 }
 // ... and that kernel
-static int orb_describe(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint16_t* d_depth, int nb, ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp)
+static int orb_describe(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint16_t* d_depth, int nb, ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp,
+                        const void* planted_aux = nullptr /* ssm_debug_orb_describe alone */)
 {
-    prof_begin(c, s, "describe");  HIPCHK(c, k_describe(nb, c->g, w.pyr, w.blur, w.sel, w.nsel, c->d_pattern_f, d_depth, c->cfg.camera, w.kpaux, kps, desc, pos3d, nkp, s)); prof_end(c, s);
+    prof_begin(c, s, "describe");  HIPCHK(c, k_describe(nb, c->g, w.pyr, w.blur, w.sel, w.nsel, c->d_pattern_f, d_depth, c->cfg.camera, w.kpaux, kps, desc, pos3d, nkp, s, planted_aux)); prof_end(c, s);
     return SSM_OK;
 }
 static int run_orb(ssm_ctx* c, hipStream_t s, OrbWork& w, const uint8_t* d_img, int channels, const uint16_t* d_depth, int nb,
@@ -347,6 +364,107 @@ extern "C" int ssm_debug_pyramid(ssm_ctx* c, const uint8_t* img, int channels, i
     if (r) return r;
     HIPCHK(c, hipMemcpyAsync(out, c->chain[0].work.pyr, (size_t)n * g.pyr_bytes, hipMemcpyDeviceToHost, c->main.stream));
     HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    return SSM_OK;
+}
+
+// The two hooks for exact tests of the blur and describe kernels (include/ssm_hip.h).  Both upload n host frames into d_scratch (at offset 0) and build the
+// pyramid and the blurred pyramid in the context's first workspace, by the calls orb_detect makes.
+static int debug_orb_pyr_blur(ssm_ctx* c, const uint8_t* img, int channels, int n, size_t scratch_bytes)
+{
+    const OrbGeom& g = c->g; OrbWork& w = c->chain[0].work; hipStream_t s = c->main.stream;
+    const size_t ib = (size_t)g.W * g.H * channels * n;
+    { const int r = ensure_scratch(c, scratch_bytes > ib ? scratch_bytes : ib); if (r) return r; }
+    HIPCHK(c, hipMemcpyAsync(c->d_scratch, img, ib, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(w.blur, 0xA5, (size_t)n * g.blur_bytes, s));                   // every byte that is read back must have been written
+    { const int r = make_pyramid(c, s, w, c->d_scratch, channels, n, n > 1 ? c->pyr_bands : c->pyr_bands1); if (r) return r; }
+    return orb_pyr_blur(c, s, w, n);
+}
+extern "C" int ssm_debug_orb_blur(ssm_ctx* c, const uint8_t* img, int channels, int n, uint8_t* out, int* bytes)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    const OrbGeom& g = c->g;
+    if (bytes) *bytes = g.pyr_bytes;
+    if (!img && !out) return SSM_OK;                                     // the size query
+    if (!img || !out || (channels != 1 && channels != 3) || n < 1 || n > c->B) FAIL(c, SSM_E_INVAL, "bad arguments");
+    { const int r = wait_pending(c); if (r) return r; }
+    { const int r = debug_orb_pyr_blur(c, img, channels, n, 0); if (r) return r; }
+    std::vector<uint8_t> tiled((size_t)n * g.blur_bytes);
+    HIPCHK(c, hipMemcpyAsync(tiled.data(), c->chain[0].work.blur, tiled.size(), hipMemcpyDeviceToHost, c->main.stream));
+    HIPCHK(c, hipStreamSynchronize(c->main.stream));
+    // the tiled layout (blur_off) back into rows of `stride` bytes at img_off, byte by byte on purpose: the layout is part of what the tests check
+    for (int f = 0; f < n; f++)
+        for (int l = 0; l < g.nlevels; l++) {
+            const LevelGeom& L = g.L[l];
+            const uint8_t* src = tiled.data() + (size_t)f * g.blur_bytes;
+            uint8_t* dst = out + (size_t)f * g.pyr_bytes + L.img_off;
+            for (int y = 0; y < L.h; y++)
+                for (int x = 0; x < L.stride; x++) dst[(size_t)y * L.stride + x] = src[blur_off(L.boff, L.stride, x, y)];
+        }
+    return SSM_OK;
+}
+extern "C" int ssm_debug_orb_describe(ssm_ctx* c, const uint8_t* img, int channels, int n, const uint16_t* depth, const int32_t* nsel, const uint32_t* sel,
+                                      const int32_t* moments, int32_t* nkp, ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* moments_out, float* sincos_out)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    const OrbGeom& g = c->g;
+    if (!img || !nsel || !nkp || !kps || !desc || !pos3d || !moments_out || !sincos_out || (channels != 1 && channels != 3)) FAIL(c, SSM_E_INVAL, "bad arguments");
+    if (n < 1 || n > c->B) FAIL(c, SSM_E_INVAL, "n must be 1..max_batch");
+    // the planted selection into the workspace's slot layout; everything is checked here, before the first launch: the kernels rely on it
+    struct Aux { int32_t m10, m01; float sn, cs; };                      // KpAux (kernels_orb.hip)
+    std::vector<uint32_t> h_sel((size_t)n * g.sel_total, 0u);
+    std::vector<Aux> h_aux(moments ? (size_t)n * g.sel_total : 0, Aux{0, 0, 0.f, 0.f});
+    size_t total = 0;
+    for (int f = 0; f < n; f++)
+        for (int l = 0; l < g.nlevels; l++) {
+            const LevelGeom& L = g.L[l]; const int k = nsel[f * g.nlevels + l];
+            if (k < 0 || k > L.sel_cap) FAIL(c, SSM_E_INVAL, "nsel of frame " + std::to_string(f) + " level " + std::to_string(l) + " outside 0.." + std::to_string(L.sel_cap));
+            if (k && !sel) FAIL(c, SSM_E_INVAL, "bad arguments");
+            for (int i = 0; i < k; i++, total++) {
+                const uint32_t pk = sel[total]; const int x = pk & 4095, y = (pk >> 12) & 4095;
+                if (x < SSM_EDGE || x >= L.w - SSM_EDGE || y < SSM_EDGE || y >= L.h - SSM_EDGE)
+                    FAIL(c, SSM_E_INVAL, "planted keypoint (" + std::to_string(x) + ", " + std::to_string(y) + ") of frame " + std::to_string(f) + " level " + std::to_string(l) +
+                                         " outside [19, w - 19) x [19, h - 19)");
+                const size_t slot = (size_t)f * g.sel_total + L.sel_off + i;
+                h_sel[slot] = pk;
+                if (moments) { h_aux[slot].m10 = moments[2 * total]; h_aux[slot].m01 = moments[2 * total + 1]; }
+            }
+        }
+    { const int r = wait_pending(c); if (r) return r; }
+    // d_scratch: [frames][depth][planted aux][nkp][keypoints][descriptors][positions]
+    Carve cv;
+    const size_t o_img = cv.take<uint8_t>((size_t)g.W * g.H * channels * n), o_dep = cv.take<uint16_t>(depth ? (size_t)g.W * g.H * n : 0), o_aux = cv.take<Aux>(h_aux.size());
+    const size_t o_out = cv.take<int32_t>(n), o_kps = cv.take<ssm_keypoint>((size_t)n * g.cap), o_desc = cv.take<uint8_t>((size_t)n * g.cap * 32), o_pos = cv.take<float>((size_t)n * g.cap * 3);
+    const size_t bytes = cv.end();
+    (void)o_img;                                                         // (offset 0: debug_orb_pyr_blur puts the frames there)
+    { const int r = debug_orb_pyr_blur(c, img, channels, n, bytes); if (r) return r; }
+    OrbWork& w = c->chain[0].work; hipStream_t s = c->main.stream; uint8_t* d = c->d_scratch;
+    if (depth) HIPCHK(c, hipMemcpyAsync(d + o_dep, depth, (size_t)g.W * g.H * n * 2, hipMemcpyHostToDevice, s));
+    if (moments) HIPCHK(c, hipMemcpyAsync(d + o_aux, h_aux.data(), h_aux.size() * sizeof(Aux), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(w.sel, h_sel.data(), h_sel.size() * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(w.nsel, nsel, (size_t)n * g.nlevels * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(d + o_out, 0xA5, bytes - o_out, s));        // what the kernels do not write comes back as this byte
+    HIPCHK(c, hipMemsetAsync(w.kpaux, 0xA5, (size_t)n * g.sel_total * 32, s));
+    { const int r = orb_describe(c, s, w, depth ? reinterpret_cast<const uint16_t*>(d + o_dep) : nullptr, n, reinterpret_cast<ssm_keypoint*>(d + o_kps), d + o_desc,
+                                 reinterpret_cast<float*>(d + o_pos), reinterpret_cast<int32_t*>(d + o_out), moments ? d + o_aux : nullptr); if (r) return r; }
+    std::vector<Aux> aux((size_t)n * g.sel_total);
+    HIPCHK(c, hipMemcpyAsync(nkp, d + o_out, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(kps, d + o_kps, (size_t)n * g.cap * sizeof(ssm_keypoint), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(desc, d + o_desc, (size_t)n * g.cap * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(pos3d, d + o_pos, (size_t)n * g.cap * 12, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(aux.data(), w.kpaux, aux.size() * sizeof(Aux), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    // KpAux is kept per slot: into output order (level by level, the order of `sel`)
+    memset(moments_out, 0xA5, (size_t)n * g.cap * 8); memset(sincos_out, 0xA5, (size_t)n * g.cap * 8);
+    for (int f = 0; f < n; f++) {
+        size_t o = (size_t)f * g.cap;
+        for (int l = 0; l < g.nlevels; l++)
+            for (int i = 0; i < nsel[f * g.nlevels + l]; i++, o++) {
+                const Aux& a = aux[(size_t)f * g.sel_total + g.L[l].sel_off + i];
+                moments_out[2 * o] = a.m10; moments_out[2 * o + 1] = a.m01; sincos_out[2 * o] = a.sn; sincos_out[2 * o + 1] = a.cs;
+            }
+    }
     return SSM_OK;
 }
 

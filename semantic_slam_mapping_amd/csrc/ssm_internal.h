@@ -44,7 +44,8 @@ hipError_t k_octree(int n, const OrbGeom& g, const cand_t* cand, const int32_t* 
                     uint32_t* sel, int32_t* nsel, int32_t* status, hipStream_t s);
 hipError_t k_describe(int n, const OrbGeom& g, const uint8_t* pyr, const uint8_t* blur, const uint32_t* sel,
                       const int32_t* nsel, const float* pattern_f /* the 256 x 4 BRIEF table as floats */, const uint16_t* depth, ssm_camera cam, void* kpaux /* n * sel_total * 32 B */,
-                      ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp, hipStream_t s);
+                      ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp, hipStream_t s,
+                      const void* planted_aux = nullptr /* ssm_debug_orb_describe: n * sel_total (m10, m01, 0.f, 0.f) records that replace orient_kernel's before angle_kernel reads them */);
 
 // matcher.  pair p: query = desc + qoff[p]*32 (nq[p] rows), train = desc + toff[p]*32 (nt[p] rows)
 struct MatchPair { int32_t qoff, nq, toff, nt, out_slot; };
