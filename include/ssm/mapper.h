@@ -165,31 +165,23 @@ public:
         PointCloud::Ptr map(new PointCloud);
         try {
         while (!shutdownFlag) {
-            size_t nkf; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); nkf = poseGraph.keyframes.size(); }
-            if (nkf <= (size_t)keyframe_size) { this_thread::sleep_for(chrono::milliseconds(1)); continue; }
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            const vector<RGBDFrame::Ptr> kfs = keyframesNow();
+            if (kfs.size() <= (size_t)keyframe_size) { this_thread::sleep_for(chrono::milliseconds(1)); continue; }
             auto t0 = chrono::steady_clock::now();
             alignCarveUpTo(kfs);
             updateMap(kfs, cntGlobalUpdate % 15 == 0, map, t0);
         }
         if (align || carve) {                           // the key-frames that came after the last update are aligned and are views too: the final state does not depend on this thread's timing
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            alignCarveUpTo(kfs);
+            alignCarveUpTo(keyframesNow());
         }
         if (relabel) {                                  // every cloud takes the label its neighbouring views agree on; then one rebuild, so the map carries the fused labels
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
+            const vector<RGBDFrame::Ptr> kfs = keyframesNow();
             auto t0 = chrono::steady_clock::now();
             relabelAll(kfs);
             if (!kfs.empty()) updateMap(kfs, true, map, t0);          // (without a key-frame there is no map to rebuild)
         }
-        if (render) {                                   // every key-frame is a view of the clouds around it, in their final state
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            renderAll(kfs);
-        }
-        if (grid) {                                     // one ground grid of every key-frame's cloud, in its final state
-            vector<RGBDFrame::Ptr> kfs; { unique_lock<mutex> lck(poseGraph.keyframes_mutex); kfs = poseGraph.keyframes; }
-            buildGrid(kfs);
-        }
+        if (render) renderAll(keyframesNow());          // every key-frame is a view of the clouds around it, in their final state
+        if (grid) buildGrid(keyframesNow());            // one ground grid of every key-frame's cloud, in its final state
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
         }
@@ -213,15 +205,10 @@ public:
                 // which is byte for byte what the host schedule would hold at this point, so the switch changes no bits
                 try {
                     ssm::Device& d = device(sel.empty() ? 0 : sel[0]->depth.cols, sel.empty() ? 0 : sel[0]->depth.rows);
-                    vector<ssm_cloud*> cl; vector<double> poses;
-                    for (const RGBDFrame::Ptr& f : sel) {
-                        cl.push_back(deviceCloud(f));
-                        const Eigen::Isometry3d T = mapPoseOf(f);
-                        poses.insert(poses.end(), T.data(), T.data() + 16);
-                    }
+                    CloudList L = cloudsOf(sel);
                     int nmap = 0;
                     if (test_fail_update >= 0 && cntGlobalUpdate == test_fail_update) d.check(ssm_viewer_map_release(d.ctx(), 1), "ssm_viewer_map_release");
-                    d.check(ssm_viewer_map_update(d.ctx(), rebuild ? 1 : 0, cl.data(), poses.data(), (int)cl.size(), (float)resolution, &nmap), "ssm_viewer_map_update");
+                    d.check(ssm_viewer_map_update(d.ctx(), rebuild ? 1 : 0, L.cl.data(), L.poses.data(), L.m, (float)resolution, &nmap), "ssm_viewer_map_update");
                     PointCloud::Ptr fetched(new PointCloud);
                     fetched->points.resize((size_t)nmap);
                     int got = 0;
@@ -260,7 +247,7 @@ public:
         if (it != devClouds.end()) return it->second;
         ssm::Device& d = device(frame->depth.cols, frame->depth.rows);
         const int w = frame->depth.cols, h = frame->depth.rows;
-        ssm_camera cam; cam.cx = frame->camera.cx; cam.cy = frame->camera.cy; cam.fx = frame->camera.fx; cam.fy = frame->camera.fy; cam.scale = frame->camera.scale;
+        const ssm_camera cam = cameraOf(frame);
         ssm_cloud* cl = nullptr;
         if (fuse_motion) {
             const ssm_motion_fuse_params P = fuseParams();
@@ -277,6 +264,10 @@ public:
         devClouds[frame.get()] = cl;
         cloudsComputed++;
         return cl;
+    }
+    static ssm_camera cameraOf(const RGBDFrame::Ptr& f) {                      // a frame's camera as the library takes it
+        ssm_camera cam; cam.cx = f->camera.cx; cam.cy = f->camera.cy; cam.fx = f->camera.fx; cam.fy = f->camera.fy; cam.scale = f->camera.scale;
+        return cam;
     }
     // binary PCD, FIELDS x y z rgba (what pcl::PCDWriter::write emits for PointXYZRGBA)
     static bool writePCD(const string& path, const PointCloud& c) {
@@ -310,7 +301,7 @@ public:
         if (frame->pointcloud == nullptr) {
             ssm::Device& d = device(frame->depth.cols, frame->depth.rows);
             const int w = frame->depth.cols, h = frame->depth.rows;
-            ssm_camera cam; cam.cx = frame->camera.cx; cam.cy = frame->camera.cy; cam.fx = frame->camera.fx; cam.fy = frame->camera.fy; cam.scale = frame->camera.scale;
+            const ssm_camera cam = cameraOf(frame);
             PointCloud::Ptr pc(new PointCloud());
             pc->points.resize((size_t)w * h);
             int n = 0;
@@ -343,22 +334,17 @@ public:
             const RGBDFrame::Ptr& vf = kfs[j];
             const int w = vf->depth.cols, h = vf->depth.rows;
             ssm::Device& d = device(w, h);
-            ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
+            const ssm_camera cam = cameraOf(vf);
             const Eigen::Isometry3d Tv = mapPoseOf(vf);
+            const vector<RGBDFrame::Ptr> before(kfs.begin() + first, kfs.begin() + j);
             const int m = (int)(j - first);
-            vector<double> poses; vector<ssm_carve_info> infos((size_t)m);
-            for (size_t i = first; i < j; i++) {
-                const Eigen::Isometry3d T = mapPoseOf(kfs[i]);
-                poses.insert(poses.end(), T.data(), T.data() + 16);
-            }
+            vector<ssm_carve_info> infos((size_t)m);
+            vector<double> poses = posesOf(before);
             if (device_map) {
-                vector<ssm_cloud*> cl;
-                for (size_t i = first; i < j; i++) cl.push_back(deviceCloud(kfs[i]));
-                ssm_carve_view* view = nullptr;
-                d.check(ssm_carve_view_create(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, &view), "ssm_carve_view_create");
-                const int rc = ssm_carve(d.ctx(), view, Tv.data(), cl.data(), poses.data(), m, &carve_params, infos.data());
-                ssm_carve_view_free(d.ctx(), view);
-                d.check(rc, "ssm_carve");
+                CloudList L = cloudsOf(before);
+                Owned<ssm_carve_view, ssm_carve_view_free> view(d.ctx());
+                d.check(ssm_carve_view_create(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, &view.t), "ssm_carve_view_create");
+                d.check(ssm_carve(d.ctx(), view.t, Tv.data(), L.cl.data(), poses.data(), m, &carve_params, infos.data()), "ssm_carve");
             } else {
                 for (size_t i = first; i < j; i++) {
                     hostCloud(kfs[i]);
@@ -395,22 +381,13 @@ public:
             if (first < j) {
                 const int w = vf->depth.cols, h = vf->depth.rows;
                 ssm::Device& d = device(w, h);
-                ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
-                const int m = (int)(j - first);
-                vector<double> poses;
-                for (size_t i = first; i < j; i++) { const Eigen::Isometry3d T = mapPoseOf(kfs[i]); poses.insert(poses.end(), T.data(), T.data() + 16); }
-                vector<ssm_cloud*> cl; vector<const ssm_point*> pts; vector<int32_t> n;
-                for (size_t i = first; i < j; i++) {
-                    if (device_map) cl.push_back(deviceCloud(kfs[i]));
-                    else { hostCloud(kfs[i]); pts.push_back(reinterpret_cast<const ssm_point*>(kfs[i]->pointcloud->points.data())); n.push_back((int32_t)kfs[i]->pointcloud->points.size()); }
-                }
-                ssm_align_view* view = nullptr;
-                d.check(ssm_align_view_create(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, &align_params, &view), "ssm_align_view_create");
+                const ssm_camera cam = cameraOf(vf);
+                CloudList L = cloudsOf(vector<RGBDFrame::Ptr>(kfs.begin() + first, kfs.begin() + j));
+                Owned<ssm_align_view, ssm_align_view_free> view(d.ctx());
+                d.check(ssm_align_view_create(d.ctx(), vf->depth.ptr<uint16_t>(), w, h, &cam, &align_params, &view.t), "ssm_align_view_create");
                 double To[16];
-                const int rc = device_map ? ssm_align_clouds(d.ctx(), view, start.data(), cl.data(), poses.data(), m, &align_params, To, &R.info)
-                                          : ssm_align_points(d.ctx(), view, start.data(), pts.data(), n.data(), poses.data(), m, &align_params, To, &R.info);
-                ssm_align_view_free(d.ctx(), view);
-                d.check(rc, device_map ? "ssm_align_clouds" : "ssm_align_points");
+                if (device_map) d.check(ssm_align_clouds(d.ctx(), view.t, start.data(), L.cl.data(), L.poses.data(), L.m, &align_params, To, &R.info), "ssm_align_clouds");
+                else d.check(ssm_align_points(d.ctx(), view.t, start.data(), L.pts.data(), L.n.data(), L.poses.data(), L.m, &align_params, To, &R.info), "ssm_align_points");
                 R.accepted = R.info.status == SSM_ALIGN_CONVERGED || (R.info.status == SSM_ALIGN_MAX_ITER && R.info.inliers_last >= (int64_t)align_params.min_inliers);
                 if (R.accepted) {
                     Eigen::Isometry3d out; for (int c = 0; c < 4; c++) for (int r = 0; r < 4; r++) out(r, c) = To[c * 4 + r];
@@ -433,11 +410,11 @@ public:
     int acceptedAlignments() const { return alignAccepted; }
     // a key-frame's alignment (not while the viewer thread runs); false: not aligned yet, or the switch is off.  D: its world-frame correction D_j
     bool alignInfoOf(const RGBDFrame::Ptr& frame, ssm_align_info* info, Eigen::Isometry3d* D = nullptr, bool* accepted = nullptr) const {
-        auto it = alignResult.find(frame.get());
-        if (it == alignResult.end()) return false;
-        if (info) *info = it->second.info;
-        if (D) *D = it->second.D;
-        if (accepted) *accepted = it->second.accepted;
+        AlignResult R;
+        if (!infoOf(alignResult, frame, &R)) return false;
+        if (info) *info = R.info;
+        if (D) *D = R.D;
+        if (accepted) *accepted = R.accepted;
         return true;
     }
     // the pose the Mapper uses for a key-frame: its map pose D_j . P_j once it has been aligned, else its pose as before (mapper_invert_pose applied)
@@ -447,11 +424,17 @@ public:
     }
     // map rendering: every key-frame of kfs is a view once, of the clouds of the key-frames within `render_window` of it (itself left out), compared with its own
     // depth and semantic image.  The viewer thread calls this as it ends; once that has ended its owner may (the host route then: the device clouds went with the thread)
-    struct RenderTarget {        // the device images, of the size of the current view; freed on every way out
-        ssm_ctx* ctx = nullptr; ssm_render_target* t = nullptr; int w = 0, h = 0;
-        RenderTarget() = default; RenderTarget(const RenderTarget&) = delete; RenderTarget& operator=(const RenderTarget&) = delete;
-        ~RenderTarget() { if (t) ssm_render_target_free(ctx, t); }
+protected:
+    // a device object of the library with the context it is freed in; freed on every way out
+    template <class T, void (*Free)(ssm_ctx*, T*)> struct Owned {
+        ssm_ctx* ctx = nullptr; T* t = nullptr;
+        explicit Owned(ssm_ctx* c = nullptr) : ctx(c) {}
+        Owned(const Owned&) = delete; Owned& operator=(const Owned&) = delete;
+        ~Owned() { reset(); }
+        void reset() { if (t) Free(ctx, t); t = nullptr; }
     };
+public:
+    struct RenderTarget : Owned<ssm_render_target, ssm_render_target_free> { int w = 0, h = 0; };        // the device images, of the size of the current view
     // the rendering of view j alone: the clouds around key-frame j into the target, which is made or remade when the view has another size
     void renderView(const vector<RGBDFrame::Ptr>& kfs, size_t j, RenderTarget& target, ssm_render_info* info = nullptr) {
         const size_t win = (size_t)max(render_window, 0);
@@ -459,33 +442,19 @@ public:
             const RGBDFrame::Ptr& vf = kfs[j];
             const int w = vf->depth.cols, h = vf->depth.rows;
             ssm::Device& d = device(w, h);
-            ssm_camera cam; cam.cx = vf->camera.cx; cam.cy = vf->camera.cy; cam.fx = vf->camera.fx; cam.fy = vf->camera.fy; cam.scale = vf->camera.scale;
+            const ssm_camera cam = cameraOf(vf);
             const Eigen::Isometry3d Tv = mapPoseOf(vf);
             if (!target.t || target.w != w || target.h != h) {
-                if (target.t) { ssm_render_target_free(target.ctx, target.t); target.t = nullptr; }
+                target.reset();
                 target.ctx = d.ctx(); target.w = w; target.h = h;
                 d.check(ssm_render_target_create(d.ctx(), w, h, &target.t), "ssm_render_target_create");
             }
-            vector<size_t> around;
-            for (size_t i = j > win ? j - win : 0; i < kfs.size() && i <= j + win; i++) if (i != j) around.push_back(i);
-            vector<double> poses;
-            for (size_t i : around) {
-                const Eigen::Isometry3d T = mapPoseOf(kfs[i]);
-                poses.insert(poses.end(), T.data(), T.data() + 16);
-            }
+            vector<RGBDFrame::Ptr> around;
+            for (size_t i = j > win ? j - win : 0; i < kfs.size() && i <= j + win; i++) if (i != j) around.push_back(kfs[i]);
+            CloudList L = cloudsOf(around);
             ssm_render_info R{};
-            if (device_map) {
-                vector<ssm_cloud*> cl;
-                for (size_t i : around) cl.push_back(deviceCloud(kfs[i]));
-                d.check(ssm_render_clouds(d.ctx(), target.t, &cam, Tv.data(), cl.data(), poses.data(), (int)cl.size(), &render_params, &R), "ssm_render_clouds");
-            } else {
-                vector<const ssm_point*> pts; vector<int32_t> n;
-                for (size_t i : around) {
-                    hostCloud(kfs[i]);
-                    pts.push_back(reinterpret_cast<const ssm_point*>(kfs[i]->pointcloud->points.data())); n.push_back((int32_t)kfs[i]->pointcloud->points.size());
-                }
-                d.check(ssm_render_points(d.ctx(), target.t, &cam, Tv.data(), pts.data(), n.data(), poses.data(), (int)pts.size(), &render_params, &R), "ssm_render_points");
-            }
+            if (device_map) d.check(ssm_render_clouds(d.ctx(), target.t, &cam, Tv.data(), L.cl.data(), L.poses.data(), L.m, &render_params, &R), "ssm_render_clouds");
+            else d.check(ssm_render_points(d.ctx(), target.t, &cam, Tv.data(), L.pts.data(), L.n.data(), L.poses.data(), L.m, &render_params, &R), "ssm_render_points");
             if (info) *info = R;
         }
     }
@@ -518,20 +487,11 @@ public:
     bool rendersViews() const { return render; }
     int renderedViews() const { return renderViews; }                        // views rendered by the last renderAll
     // the comparison of the rendering into a key-frame's view with the frame's own images (not while the viewer thread runs); false: not rendered, or the switch is off
-    bool renderInfoOf(const RGBDFrame::Ptr& frame, ssm_render_compare_info* info) const {
-        auto it = renderInfo.find(frame.get());
-        if (it == renderInfo.end()) return false;
-        if (info) *info = it->second;
-        return true;
-    }
+    bool renderInfoOf(const RGBDFrame::Ptr& frame, ssm_render_compare_info* info) const { return infoOf(renderInfo, frame, info); }
     // the ground grid: ONE grid of the clouds of every key-frame of kfs at their map poses.  The viewer thread calls this as it ends; once that has ended its owner
     // may (the host route then: the device clouds went with the thread)
     struct GridInfo { bool built = false, skipped = false; ssm_grid_info counts{}; };          // skipped: the extent exceeded 2^24 cells (or there was no key-frame)
-    struct GridTarget {          // the device accumulators and outputs; freed on every way out
-        ssm_ctx* ctx = nullptr; ssm_grid_target* t = nullptr;
-        GridTarget() = default; GridTarget(const GridTarget&) = delete; GridTarget& operator=(const GridTarget&) = delete;
-        ~GridTarget() { if (t) ssm_grid_target_free(ctx, t); }
-    };
+    typedef Owned<ssm_grid_target, ssm_grid_target_free> GridTarget;          // the device accumulators and outputs
     void buildGrid(const vector<RGBDFrame::Ptr>& kfs) {
         gridState = GridInfo(); gridSpec = grid_params; gridSpec.nx = gridSpec.ny = 0;
         gridCls.clear(); gridGroundLabel.clear(); gridObstacleLabel.clear(); gridGroundQ.clear(); gridTopQ.clear(); gridN.clear(); gridNHigh.clear();
@@ -539,10 +499,8 @@ public:
         // the extent: the key-frames' map positions in the grid frame, widened by max_distance, in whole cells
         ssm_grid_params P = grid_params;
         double lo[2] = {HUGE_VAL, HUGE_VAL}, hi[2] = {-HUGE_VAL, -HUGE_VAL};
-        vector<double> poses;
         for (const RGBDFrame::Ptr& f : kfs) {
             const Eigen::Isometry3d T = mapPoseOf(f);
-            poses.insert(poses.end(), T.data(), T.data() + 16);
             for (int i = 0; i < 2; i++) {
                 const double g = ((P.G[i * 4] * T(0, 3) + P.G[i * 4 + 1] * T(1, 3)) + P.G[i * 4 + 2] * T(2, 3)) + P.G[i * 4 + 3];
                 lo[i] = min(lo[i], g); hi[i] = max(hi[i], g);
@@ -558,21 +516,12 @@ public:
         P.x0 = cx0 * P.cell; P.y0 = cy0 * P.cell; P.nx = (int)nxd; P.ny = (int)nyd;
         const int w = kfs[0]->depth.cols, h = kfs[0]->depth.rows;
         ssm::Device& d = device(w, h);
-        GridTarget target; target.ctx = d.ctx();
+        GridTarget target(d.ctx());
         d.check(ssm_grid_target_create(d.ctx(), P.nx, P.ny, &target.t), "ssm_grid_target_create");
         ssm_grid_info I{};
-        if (device_map) {
-            vector<ssm_cloud*> cl;
-            for (const RGBDFrame::Ptr& f : kfs) cl.push_back(deviceCloud(f));
-            d.check(ssm_grid_clouds(d.ctx(), target.t, cl.data(), poses.data(), (int)cl.size(), &P, &I), "ssm_grid_clouds");
-        } else {
-            vector<const ssm_point*> pts; vector<int32_t> n;
-            for (const RGBDFrame::Ptr& f : kfs) {
-                hostCloud(f);
-                pts.push_back(reinterpret_cast<const ssm_point*>(f->pointcloud->points.data())); n.push_back((int32_t)f->pointcloud->points.size());
-            }
-            d.check(ssm_grid_points(d.ctx(), target.t, pts.data(), n.data(), poses.data(), (int)pts.size(), &P, &I), "ssm_grid_points");
-        }
+        CloudList L = cloudsOf(kfs);          // (the poses are those the extent was made from: nothing moved them in between)
+        if (device_map) d.check(ssm_grid_clouds(d.ctx(), target.t, L.cl.data(), L.poses.data(), L.m, &P, &I), "ssm_grid_clouds");
+        else d.check(ssm_grid_points(d.ctx(), target.t, L.pts.data(), L.n.data(), L.poses.data(), L.m, &P, &I), "ssm_grid_points");
         const size_t nc = (size_t)P.nx * P.ny;
         gridCls.resize(nc); gridGroundLabel.resize(nc); gridObstacleLabel.resize(nc); gridGroundQ.resize(nc); gridTopQ.resize(nc); gridN.resize(nc); gridNHigh.resize(nc);
         d.check(ssm_grid_fetch(d.ctx(), target.t, gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), gridTopQ.data(), gridN.data(), gridNHigh.data()),
@@ -614,31 +563,25 @@ public:
         if (kfs.empty()) return;
         const size_t n = kfs.size(), win = (size_t)max(relabel_window, 0);
         ssm::Device& d = device(kfs[0]->depth.cols, kfs[0]->depth.rows);
-        struct Views {          // the view objects alive, freed on every way out
-            ssm_ctx* ctx; std::map<size_t, ssm_relabel_view*> v;
-            ~Views() { for (auto& kv : v) ssm_relabel_view_free(ctx, kv.second); }
-        } views{d.ctx(), {}};
+        std::map<size_t, Owned<ssm_relabel_view, ssm_relabel_view_free>> views;          // the view objects alive
         for (size_t i = 0; i < n; i++) {
             const size_t first = i > win ? i - win : 0, last = min(n - 1, i + win);
-            for (auto it = views.v.begin(); it != views.v.end();) {          // a view below the window of cloud i is below that of every later cloud
-                if (it->first < first) { ssm_relabel_view_free(d.ctx(), it->second); it = views.v.erase(it); } else ++it;
-            }
+            views.erase(views.begin(), views.lower_bound(first));          // a view below the window of cloud i is below that of every later cloud
             vector<const ssm_relabel_view*> list; vector<double> poses;
             for (size_t j = first; j <= last; j++) {
                 if (j == i) continue;
-                auto it = views.v.find(j);
-                if (it == views.v.end()) {
+                auto& view = views[j];
+                if (!view.t) {
                     const RGBDFrame::Ptr& f = kfs[j];
-                    ssm_camera cam; cam.cx = f->camera.cx; cam.cy = f->camera.cy; cam.fx = f->camera.fx; cam.fy = f->camera.fy; cam.scale = f->camera.scale;
-                    ssm_relabel_view* v = nullptr;
-                    d.check(ssm_relabel_view_create(d.ctx(), f->depth.ptr<uint16_t>(), f->semantic.data, f->depth.cols, f->depth.rows, &cam, &v), "ssm_relabel_view_create");
-                    it = views.v.emplace(j, v).first;
+                    const ssm_camera cam = cameraOf(f);
+                    view.ctx = d.ctx();
+                    d.check(ssm_relabel_view_create(d.ctx(), f->depth.ptr<uint16_t>(), f->semantic.data, f->depth.cols, f->depth.rows, &cam, &view.t), "ssm_relabel_view_create");
                 }
-                list.push_back(it->second);
+                list.push_back(view.t);
                 const Eigen::Isometry3d T = mapPoseOf(kfs[j]);
                 poses.insert(poses.end(), T.data(), T.data() + 16);
             }
-            relabelViewsAlive = max(relabelViewsAlive, (int)views.v.size());
+            relabelViewsAlive = max(relabelViewsAlive, (int)views.size());
             const Eigen::Isometry3d Tc = mapPoseOf(kfs[i]);
             ssm_relabel_info I{};
             if (device_map) {
@@ -670,22 +613,12 @@ public:
     uint64_t relabelLabelFnv() const { return relabelFnv; }                    // mapper_relabel_hash=1: FNV-1a over every key-frame's label bytes after the last relabelAll, in order; else 0
     int relabelMaxViewsAlive() const { return relabelViewsAlive; }            // the most view objects alive at once so far (2 window + 1 at most)
     // what label fusion did to a key-frame's cloud (not while the viewer thread runs); false: relabelAll has not reached it, or the switch is off
-    bool relabelInfoOf(const RGBDFrame::Ptr& frame, ssm_relabel_info* info) const {
-        auto it = relabelInfo.find(frame.get());
-        if (it == relabelInfo.end()) return false;
-        if (info) *info = it->second;
-        return true;
-    }
+    bool relabelInfoOf(const RGBDFrame::Ptr& frame, ssm_relabel_info* info) const { return infoOf(relabelInfo, frame, info); }
     bool carves() const { return carve; }
     int carvedViews() const { return carveViews; }                            // views applied so far (a first key-frame has no earlier cloud and is none)
     // what carving did to a key-frame's cloud over all the views applied to it: n_in its size before the first, n_kept its size now, the verdicts and `removed` summed
     // (not while the viewer thread runs); false: no view has been applied to it, or the switch is off
-    bool carveInfoOf(const RGBDFrame::Ptr& frame, ssm_carve_info* info) const {
-        auto it = carveInfo.find(frame.get());
-        if (it == carveInfo.end()) return false;
-        if (info) *info = it->second;
-        return true;
-    }
+    bool carveInfoOf(const RGBDFrame::Ptr& frame, ssm_carve_info* info) const { return infoOf(carveInfo, frame, info); }
     // src/mapper.cpp:189-271 under its own name: the mask that gates the frame's cloud.  motion_semantic_fuse=0: the always-moving classes, dilated (what
     // ssm_moving_mask gives); 1: fused with frame->moving_mask.  info: the fusion's counters.  Uses the Mapper's device: not while the viewer thread runs
     cv::Mat semantic_motion_fuse(const RGBDFrame::Ptr& frame, ssm_motion_fuse_info* info = nullptr) {
@@ -699,12 +632,7 @@ public:
     bool fusesMotion() const { return fuse_motion; }
     bool removesOutliers() const { return outlier_removal; }
     // the filter's figures for a key-frame whose cloud has been made (either route; not while the viewer thread runs); false: no cloud yet, or the switch is off
-    bool sorInfoOf(const RGBDFrame::Ptr& frame, ssm_sor_info* info) const {
-        auto it = sorInfo.find(frame.get());
-        if (it == sorInfo.end()) return false;
-        if (info) *info = it->second;
-        return true;
-    }
+    bool sorInfoOf(const RGBDFrame::Ptr& frame, ssm_sor_info* info) const { return infoOf(sorInfo, frame, info); }
     std::atomic<bool> viewerFailed{false};
     std::atomic<bool> deviceMapFellBack{false};                              // the device-resident map update failed once: host path since (same bits)
     int cloudsComputed = 0;                                                    // device back-projections so far (each frame costs one)
@@ -722,6 +650,29 @@ public:
         return out;
     }
 protected:
+    vector<RGBDFrame::Ptr> keyframesNow() { unique_lock<mutex> lck(poseGraph.keyframes_mutex); return poseGraph.keyframes; }
+    template <class Map, class Info> static bool infoOf(const Map& m, const RGBDFrame::Ptr& frame, Info* info) {
+        auto it = m.find(frame.get());
+        if (it == m.end()) return false;
+        if (info) *info = it->second;
+        return true;
+    }
+    // the clouds of some key-frames as a library call takes them: handles (the device route) or arrays and counts (the host route), and the m map poses
+    struct CloudList { vector<ssm_cloud*> cl; vector<const ssm_point*> pts; vector<int32_t> n; vector<double> poses; int m = 0; };
+    vector<double> posesOf(const vector<RGBDFrame::Ptr>& fs) const {           // the map poses of these key-frames as 16 m doubles, read now
+        vector<double> poses;
+        for (const RGBDFrame::Ptr& f : fs) { const Eigen::Isometry3d T = mapPoseOf(f); poses.insert(poses.end(), T.data(), T.data() + 16); }
+        return poses;
+    }
+    // by the Mapper's current route: the poses read first, then the clouds made on demand, in the order given
+    CloudList cloudsOf(const vector<RGBDFrame::Ptr>& fs) {
+        CloudList L; L.poses = posesOf(fs); L.m = (int)fs.size();
+        for (const RGBDFrame::Ptr& f : fs) {
+            if (device_map) L.cl.push_back(deviceCloud(f));
+            else { hostCloud(f); L.pts.push_back(reinterpret_cast<const ssm_point*>(f->pointcloud->points.data())); L.n.push_back((int32_t)f->pointcloud->points.size()); }
+        }
+        return L;
+    }
     ssm_sor_params sorParams() const { ssm_sor_params P; ssm_sor_params_default(&P); P.mean_k = sor_mean_k; P.stddev_mul = sor_stddev; return P; }
     ssm_motion_fuse_params fuseParams() const { ssm_motion_fuse_params P; ssm_motion_fuse_params_default(&P); P.area_thres = area_thres; P.overlay_thres = overlay_portion_thres; return P; }
     // the frame's motion mask when UVDisparity left one of the semantic image's size (packed rows), else none

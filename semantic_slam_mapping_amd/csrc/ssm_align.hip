@@ -71,11 +71,7 @@ extern "C" int ssm_align_view_create(ssm_ctx* c, const uint16_t* depth, int w, i
     return SSM_OK;
 }
 extern "C" void ssm_align_view_free(ssm_ctx* c, ssm_align_view* v)
-{
-    if (!v) return;
-    if (c) { std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device); hipStreamSynchronize(c->main.stream); }
-    delete v;
-}
+{ free_after_wait(c, v); }
 extern "C" int ssm_align_points(ssm_ctx* c, const ssm_align_view* v, const double* T_view, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m,
                                 const ssm_align_params* params, double* T_view_out, ssm_align_info* info)
 {
@@ -83,11 +79,8 @@ extern "C" int ssm_align_points(ssm_ctx* c, const ssm_align_view* v, const doubl
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     ssm_align_params P; Setup S;
     { const int r = align_begin(c, v, T_view, params, &P, &S); if (r) return r; }
-    if (m < 0 || (m && (!pts || !n || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    int64_t total = 0;
-    { const int r = align_total_check(c, S, n, m, P.stride, &total); if (r) return r; }
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, "align: the same cloud twice", T_view, nullptr, pts, n, T_clouds, m, P.stride, segs); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_arrays(pts, n, T_clouds, m), align_cloud_rule(S, P.stride), T_view, segs, &total); if (r) return r; }
     return align_run(c, v, S, P, T_view, segs, T_view_out, info);
 }
 extern "C" int ssm_align_clouds(ssm_ctx* c, const ssm_align_view* v, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
@@ -97,12 +90,8 @@ extern "C" int ssm_align_clouds(ssm_ctx* c, const ssm_align_view* v, const doubl
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     ssm_align_params P; Setup S;
     { const int r = align_begin(c, v, T_view, params, &P, &S); if (r) return r; }
-    if (m < 0 || (m && (!clouds || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, "align: the same cloud twice", T_view, clouds, nullptr, nullptr, T_clouds, m, P.stride, segs); if (r) return r; }
-    std::vector<int32_t> n; for (int k = 0; k < m; k++) n.push_back(clouds[k]->n);
-    int64_t total = 0;
-    { const int r = align_total_check(c, S, n.data(), m, P.stride, &total); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_handles(clouds, T_clouds, m), align_cloud_rule(S, P.stride), T_view, segs, &total); if (r) return r; }
     return align_run(c, v, S, P, T_view, segs, T_view_out, info);
 }
 extern "C" int ssm_debug_align_normals(ssm_ctx* c, const ssm_align_view* v, uint8_t* valid, float* normals)

@@ -32,11 +32,10 @@ int align_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_align
     S->delta = P.delta; S->w = w; S->h = h; S->tol_abs = tol_abs_units(P.tol_abs, cam->scale); S->ppm = P.tol_rel_ppm;
     return SSM_OK;
 }
-int align_total_check(ssm_ctx* c, const Setup& S, const int32_t* n, int m, int stride, int64_t* total)
+CloudRule align_cloud_rule(const Setup& S, int stride)
 {
-    if (!cloud_count(n, m, stride, total)) return host_fail(c, SSM_E_INVAL, "align: a negative point count");
-    if (!sums_fit(S, *total)) return host_fail(c, SSM_E_INVAL, "align: the sums of this many points at this z_max, dist_max and field of view could reach 2^62");
-    return SSM_OK;
+    return {"align: the same cloud twice", stride, 0, &S, "align: a negative point count",
+            "align: the sums of this many points at this z_max, dist_max and field of view could reach 2^62"};
 }
 
 int align_drive(const ssm_align_params& P, int64_t n_in, const double* T_view, const std::function<int(const double*, int64_t*)>& accumulate, double* T_view_out,
@@ -90,14 +89,10 @@ extern "C" int ssm_align_host(const uint16_t* depth, int w, int h, const ssm_cam
     { int r = align_check(nullptr, w, h, cam, P, &S); if (!r) r = carve_pose_check(nullptr, T_view); if (r) return r; }
     if (!depth || m < 0 || (m && (!pts || !n || !T_clouds)) || record_cap < 0) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     int64_t total = 0;
-    { const int r = align_total_check(nullptr, S, n, m, P.stride, &total); if (r) return r; }
+    const CloudRule R = align_cloud_rule(S, P.stride);
+    { int r = cloud_total_check(nullptr, R, n, m, &total); if (!r) r = cloud_arrays_check(nullptr, R.twice_msg, pts, n, T_clouds, m); if (r) return r; }
     std::vector<double> M((size_t)m * 12);
-    for (int k = 0; k < m; k++) {
-        if (n[k] && !pts[k]) return host_fail(nullptr, SSM_E_INVAL, "null argument");
-        for (int j = 0; j < k; j++) if (n[k] && n[j] && pts[j] == pts[k]) return host_fail(nullptr, SSM_E_INVAL, "align: the same cloud twice");
-        const int r = carve_pose_check(nullptr, T_clouds + 16 * k); if (r) return r;
-        ssm_carvec::rel_pose(T_view, T_clouds + 16 * k, M.data() + 12 * (size_t)k);
-    }
+    for (int k = 0; k < m; k++) ssm_carvec::rel_pose(T_view, T_clouds + 16 * k, M.data() + 12 * (size_t)k);
     std::vector<Normal> nm((size_t)w * h);
     for (int y = 0; y < h; y++) for (int x = 0; x < w; x++) {
         const size_t at = (size_t)y * w + x;

@@ -21,6 +21,8 @@ static int carve_scratch(ssm_ctx* c, int total, int m)
     W.cap = (int)n; W.cap_m = (int)mm;
     return SSM_OK;
 }
+// the clouds of a carving call: no bound here (carve_run has the call's 2^30 with SSM_E_CAPACITY)
+static CloudRule carve_cloud_rule(const char* twice_msg) { return {twice_msg, 1, INT64_MAX, nullptr, "null argument", nullptr}; }
 // segs: pts, run, n and M filled by the caller; everything from the table's upload to the call's wait
 static int carve_run(ssm_ctx* c, const uint16_t* d_depth, const Setup& S, int min_votes, std::vector<CloudSeg>& segs, ssm_carve_info* infos)
 {
@@ -63,11 +65,7 @@ extern "C" int ssm_carve_view_create(ssm_ctx* c, const uint16_t* depth, int w, i
     return SSM_OK;
 }
 extern "C" void ssm_carve_view_free(ssm_ctx* c, ssm_carve_view* v)
-{
-    if (!v) return;
-    if (c) { std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device); hipStreamSynchronize(c->main.stream); }
-    delete v;
-}
+{ free_after_wait(c, v); }
 extern "C" int ssm_carve(ssm_ctx* c, const ssm_carve_view* v, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
                          const ssm_carve_params* params, ssm_carve_info* infos)
 {
@@ -78,8 +76,8 @@ extern "C" int ssm_carve(ssm_ctx* c, const ssm_carve_view* v, const double* T_vi
     ssm_carve_params P; ssm_carve_params_default(&P); if (params) P = *params;
     Setup S;
     { int r = carve_check(c, v->w, v->h, &v->cam, P, &S); if (!r) r = carve_pose_check(c, T_view); if (r) return r; }
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, "carve: the same cloud twice in one call", T_view, clouds, nullptr, nullptr, T_clouds, m, 1, segs); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_handles(clouds, T_clouds, m), carve_cloud_rule("carve: the same cloud twice in one call"), T_view, segs, &total); if (r) return r; }
     c->carve.off.assign(1, 0);
     if (m == 0) return SSM_OK;
     // a cloud's counters are made by its first view, zero; they become the cloud's only when the whole call has succeeded (a cloud that has counters is refused by
@@ -121,8 +119,8 @@ extern "C" int ssm_carve_points(ssm_ctx* c, const uint16_t* depth, int w, int h,
     HIPCHK(c, hipMemcpyAsync(W.depth, depth, np * 2, hipMemcpyHostToDevice, s));
     if (n && run_inout) HIPCHK(c, hipMemcpyAsync(W.run_in, run_inout, (size_t)n, hipMemcpyHostToDevice, s));
     else HIPCHK(c, hipMemsetAsync(W.run_in, 0, nn, s));
-    std::vector<CloudSeg> segs;          // the one cloud, staged like any list of host arrays
-    { const int r = cloud_list(c, nullptr, T_view, nullptr, &pts, &n, T_cloud, 1, 1, segs); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;          // the one cloud, staged like any list of host arrays
+    { const int r = cloud_call(c, cloud_arrays(&pts, &n, T_cloud, 1), carve_cloud_rule(nullptr), T_view, segs, &total); if (r) return r; }
     segs[0].run = W.run_in;
     ssm_carve_info I{};
     { const int r = carve_run(c, W.depth, S, P.min_votes, segs, &I); if (r) return r; }

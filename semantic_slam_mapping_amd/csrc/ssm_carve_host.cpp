@@ -28,6 +28,15 @@ int carve_pose_check(ssm_ctx* c, const double* T)
     for (int i = 0; i < 16; i++) if (!finite_d(T[i])) return host_fail(c, SSM_E_INVAL, "carve: a pose is not finite");
     return SSM_OK;
 }
+int cloud_arrays_check(ssm_ctx* c, const char* twice_msg, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m)
+{
+    for (int k = 0; k < m; k++) {
+        if (n[k] && !pts[k]) return host_fail(c, SSM_E_INVAL, "null argument");
+        if (twice_msg) for (int j = 0; j < k; j++) if (n[k] && n[j] && pts[j] == pts[k]) return host_fail(c, SSM_E_INVAL, twice_msg);
+        const int r = carve_pose_check(c, T_clouds + 16 * k); if (r) return r;
+    }
+    return SSM_OK;
+}
 
 extern "C" int ssm_carve_host(const uint16_t* depth, int w, int h, const ssm_camera* cam, const double* T_view, const ssm_point* pts, int n, const double* T_cloud,
                               uint8_t* run_inout, const ssm_carve_params* params, ssm_point* out, int cap, int* n_out, ssm_carve_info* info, uint8_t* verdict, uint8_t* run)

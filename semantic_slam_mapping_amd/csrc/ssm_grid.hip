@@ -6,8 +6,6 @@
 #include "ssm_host.h"
 using namespace ssm_gridc;
 
-static const double GRID_EYE[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-
 // what every build checks first
 static int grid_begin(ssm_ctx* c, ssm_grid_target* t, const ssm_grid_params* params, ssm_grid_params* P, Setup* S)
 {
@@ -58,11 +56,7 @@ extern "C" int ssm_grid_target_create(ssm_ctx* c, int nx, int ny, ssm_grid_targe
     return SSM_OK;
 }
 extern "C" void ssm_grid_target_free(ssm_ctx* c, ssm_grid_target* t)
-{
-    if (!t) return;
-    if (c) { std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device); hipStreamSynchronize(c->main.stream); }
-    delete t;
-}
+{ free_after_wait(c, t); }
 extern "C" int ssm_grid_points(ssm_ctx* c, ssm_grid_target* t, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m, const ssm_grid_params* params,
                                ssm_grid_info* info)
 {
@@ -70,11 +64,8 @@ extern "C" int ssm_grid_points(ssm_ctx* c, ssm_grid_target* t, const ssm_point* 
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     ssm_grid_params P; Setup S;
     { const int r = grid_begin(c, t, params, &P, &S); if (r) return r; }
-    if (m < 0 || (m && (!pts || !n || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    int64_t total = 0;
-    { const int r = grid_total_check(c, n, m, &total); if (r) return r; }
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, grid_twice_msg(), GRID_EYE, nullptr, pts, n, T_clouds, m, 1, segs); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_arrays(pts, n, T_clouds, m), grid_cloud_rule(), CLOUD_EYE, segs, &total); if (r) return r; }
     return grid_run(c, t, P, S, segs, T_clouds, info);
 }
 extern "C" int ssm_grid_clouds(ssm_ctx* c, ssm_grid_target* t, ssm_cloud* const* clouds, const double* T_clouds, int m, const ssm_grid_params* params, ssm_grid_info* info)
@@ -83,12 +74,8 @@ extern "C" int ssm_grid_clouds(ssm_ctx* c, ssm_grid_target* t, ssm_cloud* const*
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     ssm_grid_params P; Setup S;
     { const int r = grid_begin(c, t, params, &P, &S); if (r) return r; }
-    if (m < 0 || (m && (!clouds || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, grid_twice_msg(), GRID_EYE, clouds, nullptr, nullptr, T_clouds, m, 1, segs); if (r) return r; }
-    std::vector<int32_t> n; for (int k = 0; k < m; k++) n.push_back(clouds[k]->n);
-    int64_t total = 0;
-    { const int r = grid_total_check(c, n.data(), m, &total); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_handles(clouds, T_clouds, m), grid_cloud_rule(), CLOUD_EYE, segs, &total); if (r) return r; }
     return grid_run(c, t, P, S, segs, T_clouds, info);
 }
 extern "C" int ssm_grid_viewer_map(ssm_ctx* c, ssm_grid_target* t, const ssm_grid_params* params, ssm_grid_info* info)
@@ -97,12 +84,9 @@ extern "C" int ssm_grid_viewer_map(ssm_ctx* c, ssm_grid_target* t, const ssm_gri
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     ssm_grid_params P; Setup S;
     { const int r = grid_begin(c, t, params, &P, &S); if (r) return r; }
-    if (!c->d_vmap || c->vmap_n <= 0) FAIL(c, SSM_E_INVAL, "grid: the context holds no viewer map");
-    ssm_cloud vm; vm.d = c->d_vmap; vm.n = c->vmap_n; vm.device = c->device;             // the map as a list of one cloud: borrowed, nothing of it is owned here
-    ssm_cloud* const list[1] = {&vm};
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, nullptr, GRID_EYE, list, nullptr, nullptr, GRID_EYE, 1, 1, segs); if (r) return r; }
-    return grid_run(c, t, P, S, segs, GRID_EYE, info);
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_viewer_map("grid: the context holds no viewer map"), grid_cloud_rule(), CLOUD_EYE, segs, &total); if (r) return r; }
+    return grid_run(c, t, P, S, segs, CLOUD_EYE, info);
 }
 static int grid_target_ready(ssm_ctx* c, const ssm_grid_target* t)
 {

@@ -33,13 +33,7 @@ int grid_check(ssm_ctx* c, const ssm_grid_params& P, Setup* S)
     S->nx = P.nx; S->ny = P.ny; S->ground_radius = P.ground_radius; S->min_obstacle_points = P.min_obstacle_points;
     return SSM_OK;
 }
-int grid_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total)
-{
-    if (!cloud_count(n, m, 1, total)) return host_fail(c, SSM_E_INVAL, "grid: a negative point count");
-    if (*total >= MAX_POINTS) return host_fail(c, SSM_E_INVAL, "grid: 2^31 points or more in one call");
-    return SSM_OK;
-}
-const char* grid_twice_msg() { return "grid: the same cloud twice"; }
+CloudRule grid_cloud_rule() { return {"grid: the same cloud twice", 1, MAX_POINTS, nullptr, "grid: a negative point count", "grid: 2^31 points or more in one call"}; }
 
 // the base of cell (cx, cy) with n > 0: the smallest hmin over the non-empty cells of its window, clipped at the grid's edge
 static int32_t base_of(const ssm_grid_cell* cells, const Setup& S, int cx, int cy)
@@ -61,12 +55,8 @@ extern "C" int ssm_grid_host(const ssm_point* const* pts, const int32_t* n, cons
     { const int r = grid_check(nullptr, P, &S); if (r) return r; }
     if (m < 0 || (m && (!pts || !n || !T_clouds))) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     int64_t total = 0;
-    { const int r = grid_total_check(nullptr, n, m, &total); if (r) return r; }
-    for (int k = 0; k < m; k++) {
-        if (n[k] && !pts[k]) return host_fail(nullptr, SSM_E_INVAL, "null argument");
-        for (int j = 0; j < k; j++) if (n[k] && n[j] && pts[j] == pts[k]) return host_fail(nullptr, SSM_E_INVAL, grid_twice_msg());
-        const int r = carve_pose_check(nullptr, T_clouds + 16 * k); if (r) return r;
-    }
+    const CloudRule R = grid_cloud_rule();
+    { int r = cloud_total_check(nullptr, R, n, m, &total); if (!r) r = cloud_arrays_check(nullptr, R.twice_msg, pts, n, T_clouds, m); if (r) return r; }
     const size_t nc = (size_t)S.nx * S.ny;
     ssm_grid_cell empty; memset(&empty, 0, sizeof(empty)); empty.hmin = HMIN_EMPTY; empty.hmax = HMAX_EMPTY; empty.base = BASE_EMPTY;
     std::vector<ssm_grid_cell> cells(nc, empty);

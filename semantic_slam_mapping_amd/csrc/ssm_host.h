@@ -1,7 +1,7 @@
-// ssm_host.h -- what the library's host-only sources (ssm_vocab.cpp, ssm_vocab_train_host.cpp, ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_relabel_host.cpp, ssm_cloud_table.cpp, ssm_track_host.cpp:
-// plain C++ without a HIP header and without ssm_ctx.h) share with the device translation units; ssm_orb_plan.cpp and ssm_map_plan.cpp are host-only sources with headers of their own.  Those sources are compiled once and LINKED into libssm_hip.so, into the
+// ssm_host.h -- what the library's host-only sources (csrc/host_sources.mk lists them: plain C++ without a HIP header and without ssm_ctx.h) share with the device
+// translation units; ssm_orb_plan.cpp and ssm_map_plan.cpp are host-only sources with headers of their own.  Those sources are compiled once and LINKED into libssm_hip.so, into the
 // CPU sanitizer binaries of the host layer and into host/test_vocab_train / host/test_track.  What they need from the side that owns the context and the device are the hooks:
-// defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
+// defined in ssm_abi.hip / ssm_uvd.hip / ssm_pgo.hip / ssm_track.hip / ssm_cloud_list.hip, and as "no device" by a build without one (host/san_stub_device.cpp).  Not installed.
 #pragma once
 #include "../../include/ssm_hip.h"
 #include "../../include/ssm/vocab_train_core.h"
@@ -101,8 +101,31 @@ SSM_HIDDEN int sor_off_grid(ssm_ctx* c);                                       /
 // ---------------------------------------------------------------- the cloud-segment table (ssm_cloud_table.cpp; cloud_table.h)
 // seg: m records with n (the points used) filled -> every off; blk (null: not wanted): the cloud of each block of T points' first point; -> the points, *blocks
 SSM_HIDDEN int64_t cloud_table_build(CloudSeg* seg, int m, int T, int32_t* blk, int64_t* blocks);
-// the points a host-array call uses: the sum of ceil(n[k] / stride) -> *total; false: a negative count.  The bound on the sum and the messages are the stage's
+// the points a host-array call uses: the sum of ceil(n[k] / stride) -> *total; false: a negative count
 SSM_HIDDEN bool cloud_count(const int32_t* n, int m, int stride, int64_t* total);
+// A stage's rule for the clouds of one call.  twice_msg: the refusal of a cloud listed twice (null: allowed, it is only read); stride: every stride-th point is used;
+// the bound on the points used: fewer than limit, or with sums (alignment) what align_core.h's sums_fit allows; the stage's messages for a negative count and the bound
+struct CloudRule { const char* twice_msg; int stride; int64_t limit; const ssm_alignc::Setup* sums; const char* negative_msg; const char* bound_msg; };
+SSM_HIDDEN int cloud_bound_check(ssm_ctx* c, const CloudRule& R, int64_t total);                              // SSM_E_INVAL with R.bound_msg
+SSM_HIDDEN int cloud_total_check(ssm_ctx* c, const CloudRule& R, const int32_t* n, int m, int64_t* total);    // cloud_count (SSM_E_INVAL with R.negative_msg), then the bound
+// the clouds of a host-array call, per cloud in this order: a null array with a count, the same array twice (both used), the pose (ssm_carve_host.cpp)
+SSM_HIDDEN int cloud_arrays_check(ssm_ctx* c, const char* twice_msg, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m);
+// Where a call's clouds come from: device handles, host arrays with counts, or the context's viewer map as one borrowed cloud at the identity pose (no_map_msg: the
+// stage's refusal of a context without one)
+struct CloudSource {
+    enum Kind { HANDLES, ARRAYS, VIEWER_MAP } kind;
+    ssm_cloud* const* clouds; const ssm_point* const* pts; const int32_t* n; const double* T_clouds; int m; const char* no_map_msg;
+};
+extern SSM_HIDDEN const double CLOUD_EYE[16];
+inline CloudSource cloud_handles(ssm_cloud* const* clouds, const double* T_clouds, int m) { return {CloudSource::HANDLES, clouds, nullptr, nullptr, T_clouds, m, nullptr}; }
+inline CloudSource cloud_arrays(const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m) { return {CloudSource::ARRAYS, nullptr, pts, n, T_clouds, m, nullptr}; }
+inline CloudSource cloud_viewer_map(const char* no_map_msg) { return {CloudSource::VIEWER_MAP, nullptr, nullptr, nullptr, CLOUD_EYE, 1, no_map_msg}; }
+// hooks (ssm_cloud_list.hip).  cloud_call: what every entry point does with its list after its own *_begin -- the null test of the list, then for host arrays the
+// counts and the bound before the arrays (cloud_list), for handles the handles and poses (cloud_list) before the bound -> segs (pts, n, stride, M) and *total
+SSM_HIDDEN int cloud_call(ssm_ctx* c, const CloudSource& src, const CloudRule& R, const double* T_view, std::vector<CloudSeg>& segs, int64_t* total);
+SSM_HIDDEN void host_wait(ssm_ctx* c);          // the context's lock taken, its device made current, its main stream waited for; nothing without a context
+// every ssm_*_view_free / ssm_*_target_free: nothing queued may still read the object
+template <class T> void free_after_wait(ssm_ctx* c, T* t) { if (!t) return; host_wait(c); delete t; }
 
 // ---------------------------------------------------------------- free-space carving (ssm_carve_host.cpp)
 // the arguments a call may have (host function and device entry points alike); S: what the view's size and camera and the parameters become for carve_core.h
@@ -114,13 +137,12 @@ SSM_HIDDEN int carve_pose_check(ssm_ctx* c, const double* T);                  /
 SSM_HIDDEN int render_size_check(ssm_ctx* c, int w, int h);
 SSM_HIDDEN int render_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_render_params& P, ssm_renderc::Setup* S);
 SSM_HIDDEN int render_compare_check(ssm_ctx* c, const ssm_render_params& P, double scale, int64_t* tol_abs);      // tol_abs: in depth units
-SSM_HIDDEN int render_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total);                              // SSM_E_INVAL for a negative count or 2^32 points and more
+SSM_HIDDEN CloudRule render_cloud_rule();          // a cloud may be listed twice; fewer than 2^32 points
 
 // ---------------------------------------------------------------- ground grid (ssm_grid_host.cpp)
 // the arguments a call may have (host function and device entry points alike); S: what the parameters become for grid_core.h
 SSM_HIDDEN int grid_check(ssm_ctx* c, const ssm_grid_params& P, ssm_gridc::Setup* S);
-SSM_HIDDEN int grid_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total);                                // SSM_E_INVAL for a negative count or 2^31 points and more
-SSM_HIDDEN const char* grid_twice_msg();
+SSM_HIDDEN CloudRule grid_cloud_rule();            // no cloud twice; fewer than 2^31 points
 
 // ---------------------------------------------------------------- label fusion (ssm_relabel_host.cpp)
 // the number of views and the parameters a call may have (host function and device entry points alike)
@@ -131,8 +153,8 @@ SSM_HIDDEN int relabel_view_fill(ssm_ctx* c, int w, int h, const ssm_camera* cam
 // ---------------------------------------------------------------- dense alignment (ssm_align_host.cpp)
 // the arguments a call may have (host function and device entry points alike); S: what the view's size and camera and the parameters become for align_core.h
 SSM_HIDDEN int align_check(ssm_ctx* c, int w, int h, const ssm_camera* cam, const ssm_align_params& P, ssm_alignc::Setup* S);
-// total: the points used after the stride; SSM_E_INVAL for a negative count or sums that could reach 2^62
-SSM_HIDDEN int align_total_check(ssm_ctx* c, const ssm_alignc::Setup& S, const int32_t* n, int m, int stride, int64_t* total);
+// no cloud twice; the points used after the stride must keep the sums below 2^62 (S must outlive the rule)
+SSM_HIDDEN CloudRule align_cloud_rule(const ssm_alignc::Setup& S, int stride);
 // the iteration loop of both paths: accumulate(E as 3 x 4 row-major, sums[NSUM]) adds up one iteration (a status other than SSM_OK ends the call with it);
 // the solve, the stopping rules, T_view_out and the info are here.  record (may be null) gets one entry per iteration
 SSM_HIDDEN int align_drive(const ssm_align_params& P, int64_t n_in, const double* T_view, const std::function<int(const double*, int64_t*)>& accumulate,

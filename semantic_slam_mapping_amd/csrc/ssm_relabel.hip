@@ -93,11 +93,7 @@ extern "C" int ssm_relabel_view_create(ssm_ctx* c, const uint16_t* depth, const 
     return SSM_OK;
 }
 extern "C" void ssm_relabel_view_free(ssm_ctx* c, ssm_relabel_view* v)
-{
-    if (!v) return;
-    if (c) { std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device); hipStreamSynchronize(c->main.stream); }
-    delete v;
-}
+{ free_after_wait(c, v); }
 extern "C" int ssm_relabel(ssm_ctx* c, const ssm_relabel_view* const* views, const double* T_views, int v, ssm_cloud* cloud, const double* T_cloud,
                            const ssm_relabel_params* params, ssm_relabel_info* info)
 {

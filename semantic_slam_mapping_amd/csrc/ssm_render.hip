@@ -14,7 +14,7 @@ static int render_work(ssm_ctx* c)
     if (!W.info) { DALLOC(c, W.h_info, 4); DALLOC(c, W.counts, 9); DALLOC(c, W.h_counts, 9); DALLOC(c, W.info, 4); }
     return SSM_OK;
 }
-// segs: pts, n and M filled by the caller; everything from the table's upload to the call's wait
+// segs: pts, n and M filled by cloud_call; everything from the table's upload to the call's wait
 static int render_run(ssm_ctx* c, ssm_render_target* t, const Setup& S, std::vector<CloudSeg>& segs, ssm_render_info* info)
 {
     RenderWork& W = c->render; hipStream_t s = c->main.stream;
@@ -60,11 +60,7 @@ extern "C" int ssm_render_target_create(ssm_ctx* c, int w, int h, ssm_render_tar
     return SSM_OK;
 }
 extern "C" void ssm_render_target_free(ssm_ctx* c, ssm_render_target* t)
-{
-    if (!t) return;
-    if (c) { std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device); hipStreamSynchronize(c->main.stream); }
-    delete t;
-}
+{ free_after_wait(c, t); }
 extern "C" int ssm_render_points(ssm_ctx* c, ssm_render_target* t, const ssm_camera* cam, const double* T_view, const ssm_point* const* pts, const int32_t* n,
                                  const double* T_clouds, int m, const ssm_render_params* params, ssm_render_info* info)
 {
@@ -72,11 +68,8 @@ extern "C" int ssm_render_points(ssm_ctx* c, ssm_render_target* t, const ssm_cam
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     Setup S;
     { const int r = render_begin(c, t, cam, T_view, params, &S); if (r) return r; }
-    if (m < 0 || (m && (!pts || !n || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    int64_t total = 0;
-    { const int r = render_total_check(c, n, m, &total); if (r) return r; }
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, nullptr, T_view, nullptr, pts, n, T_clouds, m, 1, segs); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_arrays(pts, n, T_clouds, m), render_cloud_rule(), T_view, segs, &total); if (r) return r; }
     return render_run(c, t, S, segs, info);
 }
 extern "C" int ssm_render_clouds(ssm_ctx* c, ssm_render_target* t, const ssm_camera* cam, const double* T_view, ssm_cloud* const* clouds, const double* T_clouds, int m,
@@ -86,12 +79,8 @@ extern "C" int ssm_render_clouds(ssm_ctx* c, ssm_render_target* t, const ssm_cam
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     Setup S;
     { const int r = render_begin(c, t, cam, T_view, params, &S); if (r) return r; }
-    if (m < 0 || (m && (!clouds || !T_clouds))) FAIL(c, SSM_E_INVAL, "null argument");
-    std::vector<CloudSeg> segs;          // (a cloud may be listed twice: it is only read)
-    { const int r = cloud_list(c, nullptr, T_view, clouds, nullptr, nullptr, T_clouds, m, 1, segs); if (r) return r; }
-    std::vector<int32_t> n; for (int k = 0; k < m; k++) n.push_back(clouds[k]->n);
-    int64_t total = 0;
-    { const int r = render_total_check(c, n.data(), m, &total); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_handles(clouds, T_clouds, m), render_cloud_rule(), T_view, segs, &total); if (r) return r; }
     return render_run(c, t, S, segs, info);
 }
 extern "C" int ssm_render_viewer_map(ssm_ctx* c, ssm_render_target* t, const ssm_camera* cam, const double* T_view, const ssm_render_params* params, ssm_render_info* info)
@@ -100,12 +89,8 @@ extern "C" int ssm_render_viewer_map(ssm_ctx* c, ssm_render_target* t, const ssm
     std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
     Setup S;
     { const int r = render_begin(c, t, cam, T_view, params, &S); if (r) return r; }
-    if (!c->d_vmap || c->vmap_n <= 0) FAIL(c, SSM_E_INVAL, "render: the context holds no viewer map");
-    static const double EYE[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    ssm_cloud vm; vm.d = c->d_vmap; vm.n = c->vmap_n; vm.device = c->device;             // the map as a list of one cloud: borrowed, nothing of it is owned here
-    ssm_cloud* const list[1] = {&vm};
-    std::vector<CloudSeg> segs;
-    { const int r = cloud_list(c, nullptr, T_view, list, nullptr, nullptr, EYE, 1, 1, segs); if (r) return r; }
+    std::vector<CloudSeg> segs; int64_t total = 0;
+    { const int r = cloud_call(c, cloud_viewer_map("render: the context holds no viewer map"), render_cloud_rule(), T_view, segs, &total); if (r) return r; }
     return render_run(c, t, S, segs, info);
 }
 static int render_target_ready(ssm_ctx* c, const ssm_render_target* t)

@@ -44,12 +44,7 @@ int render_compare_check(ssm_ctx* c, const ssm_render_params& P, double scale, i
     *tol_abs = ssm_carvec::tol_abs_units(P.tol_abs, scale);
     return SSM_OK;
 }
-int render_total_check(ssm_ctx* c, const int32_t* n, int m, int64_t* total)
-{
-    if (!cloud_count(n, m, 1, total)) return host_fail(c, SSM_E_INVAL, "render: a negative point count");
-    if (*total >= ((int64_t)1 << 32)) return host_fail(c, SSM_E_INVAL, "render: 2^32 points or more in one call");
-    return SSM_OK;
-}
+CloudRule render_cloud_rule() { return {nullptr, 1, (int64_t)1 << 32, nullptr, "render: a negative point count", "render: 2^32 points or more in one call"}; }
 
 extern "C" int ssm_render_host(int w, int h, const ssm_camera* cam, const double* T_view, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m,
                                const ssm_render_params* params, uint16_t* depth, uint8_t* bgr, uint8_t* label, int32_t* index, uint64_t* keys, ssm_render_info* info)
@@ -59,11 +54,8 @@ extern "C" int ssm_render_host(int w, int h, const ssm_camera* cam, const double
     { int r = render_check(nullptr, w, h, cam, P, &S); if (!r) r = carve_pose_check(nullptr, T_view); if (r) return r; }
     if (m < 0 || (m && (!pts || !n || !T_clouds))) return host_fail(nullptr, SSM_E_INVAL, "null argument");
     int64_t total = 0;
-    { const int r = render_total_check(nullptr, n, m, &total); if (r) return r; }
-    for (int k = 0; k < m; k++) {
-        if (n[k] && !pts[k]) return host_fail(nullptr, SSM_E_INVAL, "null argument");
-        const int r = carve_pose_check(nullptr, T_clouds + 16 * k); if (r) return r;
-    }
+    const CloudRule R = render_cloud_rule();
+    { int r = cloud_total_check(nullptr, R, n, m, &total); if (!r) r = cloud_arrays_check(nullptr, R.twice_msg, pts, n, T_clouds, m); if (r) return r; }
     const size_t np = (size_t)w * h;
     std::vector<uint64_t> zb(np, KEY_EMPTY);
     std::vector<int64_t> first((size_t)m + 1, 0);

@@ -1,9 +1,8 @@
 // san_stub_device.cpp -- TEST INFRASTRUCTURE for the CPU sanitizer builds of the host layer (make SAN=asan|ubsan|tsan): a stand-in for the side of libssm_hip.so
 // that owns the context and the device, so that the THREADING of the host classes (Mapper::viewer on its own thread against the main thread's
 // tryInsertKeyFrame: the place of the reference's unlocked reads, /root/reference/src/mapper.cpp:114-136) can run under ThreadSanitizer in the build container,
-// which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
-// ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp, ssm_sor_host.cpp, ssm_carve_host.cpp, ssm_render_host.cpp, ssm_align_host.cpp, ssm_grid_host.cpp, ssm_relabel_host.cpp, ssm_cloud_table.cpp,
-// ssm_track_host.cpp, ssm_map_plan.cpp) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
+// which has no GPU and where sanitizer runtimes and the HIP runtime do not mix.  The library's host-only sources (the list of csrc/host_sources.mk without
+// the ORB planner) are compiled beside it as they are -- the sanitizers see the shipped code -- and get the
 // "no device" form of csrc/ssm_host.h's hooks here (the bulk tracker's among them: no tracker is ever created on the stub; its state machine runs under the sanitizers
 // in host/test_track.cpp, over hooks of that program's own).  The device entry points compute nothing of the product: placeholders.  Linked into the programs of a SAN build ONLY.
 #include "ssm_hip.h"

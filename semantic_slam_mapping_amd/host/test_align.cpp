@@ -8,47 +8,8 @@
 // closer to the truth than the planted pose in height, pitch and roll; over all views the rendering yardstick (ssm_render_compare through mapper_render=1) agrees
 // on strictly more pixels and has strictly fewer in front of or behind the measured surface than without the switch; mapper_carve=1 on top runs and both routes
 // agree; and a Mapper whose viewer thread runs aligns every key-frame exactly once.  Prints one "PASS name" / "FAIL name" line per check; exit code = failures.
-#include "ssm/rgbdframe.h"
-#include "ssm/track.h"
-#include "ssm/pose_graph.h"
-#include "ssm/mapper.h"
-#include "ssm/vo_stereo.hpp"
-using namespace std;
-using namespace rgbd_tutor;
-static int fails = 0;
-#define CHECK(name, cond) do { if (cond) cout << "PASS " << name << endl; else { cout << "FAIL " << name << endl; fails++; } } while (0)
+#include "test_lane_scene.h"
 
-// a Mapper whose viewer thread has ended, so that its device and its two routes can be driven from here
-struct QuietMapper : Mapper {
-    QuietMapper(const ParameterReader& p, PoseGraph& g) : Mapper(p, g) { shutdown(); }
-    ~QuietMapper() { for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second); devClouds.clear(); }
-    vector<ssm_point> cloudNow(const RGBDFrame::Ptr& f) {          // the camera-frame cloud as it is now, by the mapper's own route
-        vector<ssm_point> out;
-        if (device_map) {
-            ssm_cloud* cl = deviceCloud(f);
-            ssm::Device& d = device(f->depth.cols, f->depth.rows);
-            out.resize((size_t)max(ssm_cloud_size(cl), 1)); int n = 0;
-            d.check(ssm_cloud_fetch(d.ctx(), cl, nullptr, out.data(), (int)out.size(), &n), "ssm_cloud_fetch");
-            out.resize((size_t)n);
-        } else {
-            hostCloud(f);
-            out.resize(f->pointcloud->points.size());
-            if (!out.empty()) memcpy((void*)out.data(), f->pointcloud->points.data(), out.size() * sizeof(ssm_point));
-        }
-        return out;
-    }
-    ssm::Device& dev_(int w, int h) { return device(w, h); }
-};
-static bool same(const vector<ssm_point>& a, const vector<ssm_point>& b)
-{
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++) if (memcmp(&a[i], &b[i], 16) != 0 || a[i].b != b[i].b || a[i].g != b[i].g || a[i].r != b[i].r || a[i].label != b[i].label) return false;
-    return true;
-}
-static bool same_pose(const Eigen::Isometry3d& a, const Eigen::Isometry3d& b) { return memcmp(a.data(), b.data(), 16 * sizeof(double)) == 0; }
-
-static const int W = 400, H = 120, N = 8;
-static const double STEP = 0.5, GROUND = 1.6, BOX_LO[3] = {1.5, 0.4, 9.0}, BOX_HI[3] = {3.0, 1.6, 12.0};
 static const double PLANT_TY = 0.03, PLANT_RX = 0.004, PLANT_RZ = 0.003;          // per key-frame, cumulative
 // Rz(rz) Rx(rx) and a translation
 static Eigen::Isometry3d se3(double rx, double rz, double tx, double ty, double tz)
@@ -59,27 +20,6 @@ static Eigen::Isometry3d se3(double rx, double rz, double tx, double ty, double 
     for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) { double s = 0; for (int k = 0; k < 3; k++) s += Rz[r][k] * Rx[k][c]; T(r, c) = s; }
     T(0, 3) = tx; T(1, 3) = ty; T(2, 3) = tz;
     return T;
-}
-// the depth image from a camera at (0, 0, z0) looking along +z: the ground y = GROUND and the box; beyond 65 m: no depth
-static void cast(double z0, const CAMERA_INTRINSIC_PARAMETERS& cam, cv::Mat& depth)
-{
-    depth.create(H, W, CV_16UC1);
-    const double o[3] = {0.0, 0.0, z0};
-    for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) {
-        const double dir[3] = {(x - cam.cx) / cam.fx, (y - cam.cy) / cam.fy, 1.0};
-        double best = 1e30;
-        if (dir[1] > 0) best = (GROUND - o[1]) / dir[1];
-        double near = -1e30, far = 1e30;
-        for (int a = 0; a < 3; a++) {
-            if (dir[a] == 0.0) { if (o[a] < BOX_LO[a] || o[a] > BOX_HI[a]) { near = 1e30; } continue; }
-            double t0 = (BOX_LO[a] - o[a]) / dir[a], t1 = (BOX_HI[a] - o[a]) / dir[a];
-            if (t0 > t1) swap(t0, t1);
-            near = max(near, t0); far = min(far, t1);
-        }
-        if (near <= far && near > 1e-6 && near < best) best = near;
-        const double units = best * cam.scale;
-        depth.ptr<uint16_t>(y)[x] = (units >= 1.0 && units <= 65535.0) ? (uint16_t)llrint(units) : (uint16_t)0;
-    }
 }
 
 int main(int argc, char** argv)

@@ -6,46 +6,9 @@
 // points are decided per point from the scene's rectangle, its disparity and the shift of 2 (j - i) pixels: every point that two later views show in front of valid,
 // farther ground is gone, whole copies with them; with a window of 1 no view can vote twice and every point deep inside the box stays.  A Mapper whose viewer runs
 // through a rebuild publishes a map without a voxel in the trail.  Prints one "PASS name" / "FAIL name" line per check; exit code = failures.
-#include "ssm/rgbdframe.h"
-#include "ssm/track.h"
-#include "ssm/pose_graph.h"
-#include "ssm/mapper.h"
-#include "ssm/vo_stereo.hpp"
+#include "test_mapper_common.h"
 #include <set>
 #include <array>
-using namespace std;
-using namespace rgbd_tutor;
-static int fails = 0;
-#define CHECK(name, cond) do { if (cond) cout << "PASS " << name << endl; else { cout << "FAIL " << name << endl; fails++; } } while (0)
-
-// a Mapper whose viewer thread has ended, so that its device and its two routes can be driven from here
-struct QuietMapper : Mapper {
-    QuietMapper(const ParameterReader& p, PoseGraph& g) : Mapper(p, g) { shutdown(); }
-    ~QuietMapper() { for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second); devClouds.clear(); }
-    vector<ssm_point> deviceRoute(const RGBDFrame::Ptr& f) {          // the camera-frame cloud as it is now
-        ssm_cloud* cl = deviceCloud(f);
-        ssm::Device& d = device(f->depth.cols, f->depth.rows);
-        vector<ssm_point> out((size_t)max(ssm_cloud_size(cl), 1)); int n = 0;
-        d.check(ssm_cloud_fetch(d.ctx(), cl, nullptr, out.data(), (int)out.size(), &n), "ssm_cloud_fetch");
-        out.resize((size_t)n);
-        return out;
-    }
-    vector<ssm_point> hostRoute(const RGBDFrame::Ptr& f) {
-        hostCloud(f);
-        vector<ssm_point> out(f->pointcloud->points.size());
-        if (!out.empty()) memcpy((void*)out.data(), f->pointcloud->points.data(), out.size() * sizeof(ssm_point));
-        return out;
-    }
-    const vector<uint8_t>* runOf(const RGBDFrame::Ptr& f) const { auto it = carveRun.find(f.get()); return it == carveRun.end() ? nullptr : &it->second; }
-    ssm::Device& dev_(int w, int h) { return device(w, h); }
-};
-static bool same(const vector<ssm_point>& a, const vector<ssm_point>& b)
-{
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++) if (memcmp(&a[i], &b[i], 16) != 0 || a[i].b != b[i].b || a[i].g != b[i].g || a[i].r != b[i].r || a[i].label != b[i].label) return false;
-    return true;
-}
-static ssm_camera cam_of(const RGBDFrame::Ptr& f) { ssm_camera c; c.cx = f->camera.cx; c.cy = f->camera.cy; c.fx = f->camera.fx; c.fy = f->camera.fy; c.scale = f->camera.scale; return c; }
 // the scene of tests/test_gpu_uvd_host.py: the box covers rows 30..95, columns 150..229 at disparity 40 in every image
 static const int BOX_R0 = 30, BOX_R1 = 96, BOX_C0 = 150, BOX_C1 = 230; static const double BOX_DISP = 40.0, BASELINE = 0.532331858;
 static bool in_box(const ssm_point& p, const ssm_camera& c)
@@ -112,7 +75,7 @@ int main(int argc, char** argv)
         }
         CHECK("tracking_is_repeatable", poses);
         const int w = k0[0]->depth.cols, h = k0[0]->depth.rows; const double md = para.getData<double>("mapper_max_distance", 40.0);
-        const ssm_camera cam = cam_of(k0[0]);
+        const ssm_camera cam = Mapper::cameraOf(k0[0]);
         ssm::Device& d = off_m.dev_(w, h);
 
         // what the calls that exist give: the uncarved camera-frame clouds

@@ -45,7 +45,7 @@ static string name_of(const char* what, const vector<int32_t>& n, int T)
 }
 static void table_case(const char* what, const vector<int32_t>& n, int T = 256) { check(table_ok(n, T), name_of(what, n, T)); }
 
-// the two loops cloud_count replaced, as they stood in ssm_render_host.cpp and ssm_align_host.cpp: -1 a negative count, -2 beyond the stage's bound, else the total
+// the two loops cloud_count and cloud_total_check replaced, as they stood in ssm_render_host.cpp and ssm_align_host.cpp: -1 a negative count, -2 beyond the stage's bound, else the total
 static int64_t render_total_before(const vector<int32_t>& n)
 {
     int64_t t = 0;
@@ -58,18 +58,17 @@ static int64_t align_total_before(const ssm_alignc::Setup& S, const vector<int32
     for (size_t k = 0; k < n.size(); k++) { if (n[k] < 0) return -1; t += ((int64_t)n[k] + stride - 1) / stride; }
     return ssm_alignc::sums_fit(S, t) ? t : -2;
 }
-static int64_t render_total_now(const vector<int32_t>& n)
+// cloud_total_check under a stage's rule (the bounds of ssm_render_host.cpp and ssm_align_host.cpp), told apart by the message it hands to host_fail
+static string g_err;
+int host_fail(ssm_ctx*, int code, const std::string& msg) { g_err = msg; return code; }
+static int64_t total_now(const CloudRule& R, const vector<int32_t>& n)
 {
     int64_t t = -9;
-    if (!cloud_count(n.data(), (int)n.size(), 1, &t)) return -1;
-    return t >= ((int64_t)1 << 32) ? -2 : t;
+    if (cloud_total_check(nullptr, R, n.data(), (int)n.size(), &t) == SSM_OK) return t;
+    return g_err == R.negative_msg ? -1 : -2;
 }
-static int64_t align_total_now(const ssm_alignc::Setup& S, const vector<int32_t>& n, int stride)
-{
-    int64_t t = -9;
-    if (!cloud_count(n.data(), (int)n.size(), stride, &t)) return -1;
-    return ssm_alignc::sums_fit(S, t) ? t : -2;
-}
+static int64_t render_total_now(const vector<int32_t>& n) { return total_now({nullptr, 1, (int64_t)1 << 32, nullptr, "negative", "bound"}, n); }
+static int64_t align_total_now(const ssm_alignc::Setup& S, const vector<int32_t>& n, int stride) { return total_now({nullptr, stride, 0, &S, "negative", "bound"}, n); }
 
 int main()
 {

@@ -9,43 +9,7 @@
 // whose viewer thread runs builds the same grid as it ends.  The grid uses 0.5 m cells and ground_radius 3: the window (3.5 m) is wider than the box (1.5 m),
 // which the neighbourhood minimum needs to find the ground beside an obstacle whose top is seen from above (limits).
 // Prints one "PASS name" / "FAIL name" line per check; exit code = failures.
-#include "ssm/rgbdframe.h"
-#include "ssm/track.h"
-#include "ssm/pose_graph.h"
-#include "ssm/mapper.h"
-#include "ssm/vo_stereo.hpp"
-using namespace std;
-using namespace rgbd_tutor;
-static int fails = 0;
-#define CHECK(name, cond) do { if (cond) cout << "PASS " << name << endl; else { cout << "FAIL " << name << endl; fails++; } } while (0)
-
-// a Mapper whose viewer thread has ended, so that its device and its two routes can be driven from here
-struct QuietMapper : Mapper {
-    QuietMapper(const ParameterReader& p, PoseGraph& g) : Mapper(p, g) { shutdown(); }
-    ~QuietMapper() { for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second); devClouds.clear(); }
-    vector<ssm_point> cloudNow(const RGBDFrame::Ptr& f) {          // the camera-frame cloud as it is now, by the mapper's own route
-        vector<ssm_point> out;
-        if (device_map) {
-            ssm_cloud* cl = deviceCloud(f);
-            ssm::Device& d = device(f->depth.cols, f->depth.rows);
-            out.resize((size_t)max(ssm_cloud_size(cl), 1)); int n = 0;
-            d.check(ssm_cloud_fetch(d.ctx(), cl, nullptr, out.data(), (int)out.size(), &n), "ssm_cloud_fetch");
-            out.resize((size_t)n);
-        } else {
-            hostCloud(f);
-            out.resize(f->pointcloud->points.size());
-            if (!out.empty()) memcpy((void*)out.data(), f->pointcloud->points.data(), out.size() * sizeof(ssm_point));
-        }
-        return out;
-    }
-    ssm::Device& dev_(int w, int h) { return device(w, h); }
-};
-static bool same(const vector<ssm_point>& a, const vector<ssm_point>& b)
-{
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++) if (memcmp(&a[i], &b[i], 16) != 0 || a[i].b != b[i].b || a[i].g != b[i].g || a[i].r != b[i].r || a[i].label != b[i].label) return false;
-    return true;
-}
+#include "test_lane_scene.h"
 struct Grid { ssm_grid_params P{}; Mapper::GridInfo info; vector<uint8_t> cls, gl, ol; vector<int32_t> gq, tq; vector<uint32_t> n, nh; };
 static Grid grid_of(const Mapper& m) { Grid g; g.P = m.gridParams(); g.info = m.gridInfo(); m.gridFetch(&g.cls, &g.gl, &g.ol, &g.gq, &g.tq, &g.n, &g.nh); return g; }
 static bool same_grid(const Grid& a, const Grid& b)
@@ -54,32 +18,6 @@ static bool same_grid(const Grid& a, const Grid& b)
            a.ol == b.ol && a.gq == b.gq && a.tq == b.tq && a.n == b.n && a.nh == b.nh;
 }
 
-static const int W = 400, H = 120, N = 8;
-static const double STEP = 0.5, GROUND = 1.6, BOX_LO[3] = {1.5, 0.4, 9.0}, BOX_HI[3] = {3.0, 1.6, 12.0}, LANE = 1.0;
-enum { HIT_NONE = 0, HIT_ROAD = 1, HIT_PAVEMENT = 2, HIT_BOX = 3 };
-// the depth image from a camera at (0, 0, z0) looking along +z: the ground y = GROUND and the box; beyond 65 m: no depth.  hit: what every pixel's ray met
-static void cast(double z0, const CAMERA_INTRINSIC_PARAMETERS& cam, cv::Mat& depth, vector<uint8_t>& hit)
-{
-    depth.create(H, W, CV_16UC1); hit.assign((size_t)W * H, HIT_NONE);
-    const double o[3] = {0.0, 0.0, z0};
-    for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) {
-        const double dir[3] = {(x - cam.cx) / cam.fx, (y - cam.cy) / cam.fy, 1.0};
-        double best = 1e30; int what = HIT_NONE;
-        if (dir[1] > 0) { best = (GROUND - o[1]) / dir[1]; what = fabs(o[0] + best * dir[0]) < LANE ? HIT_ROAD : HIT_PAVEMENT; }
-        double near = -1e30, far = 1e30;
-        for (int a = 0; a < 3; a++) {
-            if (dir[a] == 0.0) { if (o[a] < BOX_LO[a] || o[a] > BOX_HI[a]) { near = 1e30; } continue; }
-            double t0 = (BOX_LO[a] - o[a]) / dir[a], t1 = (BOX_HI[a] - o[a]) / dir[a];
-            if (t0 > t1) swap(t0, t1);
-            near = max(near, t0); far = min(far, t1);
-        }
-        if (near <= far && near > 1e-6 && near < best) { best = near; what = HIT_BOX; }
-        const double units = best * cam.scale;
-        const bool ok = units >= 1.0 && units <= 65535.0;
-        depth.ptr<uint16_t>(y)[x] = ok ? (uint16_t)llrint(units) : (uint16_t)0;
-        hit[(size_t)y * W + x] = ok ? (uint8_t)what : (uint8_t)HIT_NONE;
-    }
-}
 
 int main(int argc, char** argv)
 {
@@ -98,7 +36,7 @@ int main(int argc, char** argv)
                 RGBDFrame::Ptr f(new RGBDFrame);
                 f->id = j; f->camera = camera;
                 vector<uint8_t> hit;
-                cast(STEP * j, camera, f->depth, hit);
+                cast(STEP * j, camera, f->depth, &hit);
                 f->rgb.create(H, W, CV_8UC3); f->semantic.create(H, W, CV_8UC3);
                 for (int y = 0; y < H; y++) for (int x = 0; x < W; x++) {
                     uint8_t* c = f->rgb.ptr<uint8_t>(y) + 3 * x; c[0] = (uint8_t)(x + j); c[1] = (uint8_t)(y * 2); c[2] = (uint8_t)(x ^ y);

@@ -5,58 +5,7 @@
 // ssm_render_host + ssm_render_compare_host on the same clouds, view after view; the PNG files read back as the arrays ssm_render_fetch gives; and with
 // mapper_carve=1 the views after the box left see strictly fewer map points in front of the measured surface inside the box's rectangle than without: carved points
 // are the ones later views see through, which is what `in_front` counts.  Prints one "PASS name" / "FAIL name" line per check; exit code = failures.
-#include "ssm/rgbdframe.h"
-#include "ssm/track.h"
-#include "ssm/pose_graph.h"
-#include "ssm/mapper.h"
-#include "ssm/vo_stereo.hpp"
-using namespace std;
-using namespace rgbd_tutor;
-static int fails = 0;
-#define CHECK(name, cond) do { if (cond) cout << "PASS " << name << endl; else { cout << "FAIL " << name << endl; fails++; } } while (0)
-
-// a Mapper whose viewer thread has ended, so that its device and its two routes can be driven from here
-struct QuietMapper : Mapper {
-    QuietMapper(const ParameterReader& p, PoseGraph& g) : Mapper(p, g) { shutdown(); }
-    ~QuietMapper() { for (auto& kv : devClouds) ssm_cloud_free(dev ? dev->ctx() : nullptr, kv.second); devClouds.clear(); }
-    vector<ssm_point> cloudNow(const RGBDFrame::Ptr& f) {          // the camera-frame cloud as it is now, by the mapper's own route
-        vector<ssm_point> out;
-        if (device_map) {
-            ssm_cloud* cl = deviceCloud(f);
-            ssm::Device& d = device(f->depth.cols, f->depth.rows);
-            out.resize((size_t)max(ssm_cloud_size(cl), 1)); int n = 0;
-            d.check(ssm_cloud_fetch(d.ctx(), cl, nullptr, out.data(), (int)out.size(), &n), "ssm_cloud_fetch");
-            out.resize((size_t)n);
-        } else {
-            hostCloud(f);
-            out.resize(f->pointcloud->points.size());
-            if (!out.empty()) memcpy((void*)out.data(), f->pointcloud->points.data(), out.size() * sizeof(ssm_point));
-        }
-        return out;
-    }
-    // view j once more, and what ssm_render_fetch gives for it
-    void fetchView(const vector<RGBDFrame::Ptr>& kfs, size_t j, cv::Mat& dep, cv::Mat& bgr, cv::Mat& lab) {
-        RenderTarget t;
-        renderView(kfs, j, t);
-        dep.create(t.h, t.w, CV_16UC1); bgr.create(t.h, t.w, CV_8UC3); lab.create(t.h, t.w, CV_8UC1);
-        ssm::Device& d = device(t.w, t.h);
-        d.check(ssm_render_fetch(d.ctx(), t.t, dep.ptr<uint16_t>(), bgr.data, lab.data, nullptr), "ssm_render_fetch");
-    }
-    ssm::Device& dev_(int w, int h) { return device(w, h); }
-};
-static bool same(const vector<ssm_point>& a, const vector<ssm_point>& b)
-{
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++) if (memcmp(&a[i], &b[i], 16) != 0 || a[i].b != b[i].b || a[i].g != b[i].g || a[i].r != b[i].r || a[i].label != b[i].label) return false;
-    return true;
-}
-static bool same_mat(const cv::Mat& a, const cv::Mat& b)
-{
-    if (a.empty() || a.rows != b.rows || a.cols != b.cols || a.type() != b.type()) return false;
-    for (int y = 0; y < a.rows; y++) if (memcmp(a.ptr<uint8_t>(y), b.ptr<uint8_t>(y), (size_t)a.cols * a.elemSize())) return false;
-    return true;
-}
-static ssm_camera cam_of(const RGBDFrame::Ptr& f) { ssm_camera c; c.cx = f->camera.cx; c.cy = f->camera.cy; c.fx = f->camera.fx; c.fy = f->camera.fy; c.scale = f->camera.scale; return c; }
+#include "test_mapper_common.h"
 // the scene of tests/test_gpu_uvd_host.py: the box covers rows 30..95, columns 150..229 in every image that has it
 static const int BOX_R0 = 30, BOX_R1 = 96, BOX_C0 = 150, BOX_C1 = 230; static const double BASELINE = 0.532331858;
 static string png(const string& dir, size_t j, const char* what) { char b[64]; snprintf(b, sizeof b, "/render_%06d_%s.png", (int)j, what); return dir + b; }
@@ -94,7 +43,7 @@ int main(int argc, char** argv)
         CHECK("sequence_has_frames", n >= 6 && kd.size() == n && kh.size() == n && kcd.size() == n && kch.size() == n && U >= 2 && U + 1 < n);
         if (n < 3) { cout << "FAILED" << endl; return fails ? fails : 1; }
         const int w = k0[0]->depth.cols, h = k0[0]->depth.rows; const double md = para.getData<double>("mapper_max_distance", 40.0);
-        const ssm_camera cam = cam_of(k0[0]);
+        const ssm_camera cam = Mapper::cameraOf(k0[0]);
         ssm::Device& d = off_m.dev_(w, h);
 
         // switch off: the clouds are what the calls that exist give, and nothing is recorded

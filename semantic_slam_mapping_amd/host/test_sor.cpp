@@ -2,43 +2,7 @@
 // clouds as they were; with 1 the device-map route (deviceCloud + ssm_cloud_fetch) and the host route (generatePointCloud) give the same bytes, which are those of
 // ssm_sor_filter on the unfiltered camera-frame cloud, transformed afterwards -- with and without motion_semantic_fuse -- and the depth speckles planted in the
 // scene are gone.  Prints one "PASS name" / "FAIL name" line per check; exit code = number of failures.
-#include "ssm/rgbdframe.h"
-#include "ssm/track.h"
-#include "ssm/pose_graph.h"
-#include "ssm/mapper.h"
-#include "ssm/vo_stereo.hpp"
-using namespace std;
-using namespace rgbd_tutor;
-static int fails = 0;
-#define CHECK(name, cond) do { if (cond) cout << "PASS " << name << endl; else { cout << "FAIL " << name << endl; fails++; } } while (0)
-
-// a Mapper whose viewer thread has ended, so that its device and its two routes to a cloud can be driven from here
-struct QuietMapper : Mapper {
-    QuietMapper(const ParameterReader& p, PoseGraph& g) : Mapper(p, g) { shutdown(); }
-    vector<ssm_point> viaDevice(const RGBDFrame::Ptr& f) {
-        ssm_cloud* cl = deviceCloud(f);
-        ssm::Device& d = device(f->depth.cols, f->depth.rows);
-        vector<ssm_point> out((size_t)max(ssm_cloud_size(cl), 1)); int n = 0;
-        const Eigen::Isometry3d T = f->getTransform();
-        d.check(ssm_cloud_fetch(d.ctx(), cl, T.data(), out.data(), (int)out.size(), &n), "ssm_cloud_fetch");
-        out.resize((size_t)n);
-        ssm_cloud_free(d.ctx(), cl); devClouds.erase(f.get());
-        return out;
-    }
-    vector<ssm_point> viaHost(const RGBDFrame::Ptr& f) {
-        PointCloud::Ptr c = generatePointCloud(f);
-        vector<ssm_point> out(c->points.size());
-        if (!out.empty()) memcpy((void*)out.data(), c->points.data(), out.size() * sizeof(ssm_point));
-        return out;
-    }
-    ssm::Device& dev_(int w, int h) { return device(w, h); }
-};
-static bool same(const vector<ssm_point>& a, const vector<ssm_point>& b)
-{
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++) if (memcmp(&a[i], &b[i], 16) != 0 || a[i].b != b[i].b || a[i].g != b[i].g || a[i].r != b[i].r || a[i].label != b[i].label) return false;
-    return true;
-}
+#include "test_mapper_common.h"
 static void box(cv::Mat& img, int x0, int y0, int x1, int y1, int b, int g, int r)
 {
     for (int y = y0; y < y1; y++) for (int x = x0; x < x1; x++) { unsigned char* p = img.ptr<unsigned char>(y) + 3 * x; p[0] = (unsigned char)b; p[1] = (unsigned char)g; p[2] = (unsigned char)r; }
