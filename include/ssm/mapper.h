@@ -56,6 +56,13 @@
 // mapper_grid_forward (three numbers each, default `0 -1 0` and `0 0 1`) the grid frame.  Both routes give the same bytes: deviceCloud / ssm_grid_clouds and
 // frame->pointcloud / ssm_grid_points.  With mapper_grid_dir set the build writes grid_colour.png, grid_height.png (16 bit) and grid.txt (x0, y0, cell, nx, ny,
 // h_min, G: what georeferences the images) there.
+// mapper_objects=1 (default 0: nothing of this runs, every cloud, map, grid and figure exactly as before): object extraction (the reference has
+// no such step).  Right after buildGrid, on the same grid target and cloud list, extractObjects labels the grid's obstacle cells of the wanted classes into
+// components (ssm_objects_grid) and assigns the clouds' HIGH points to the kept ones (ssm_objects_clouds / ssm_objects_points: both routes give the same bytes).
+// The grid is built for it even with mapper_grid=0; then no grid files are written.  mapper_objects_labels (a list of label ids, default `9 10 11`: Vehicle,
+// Pedestrian, Bike), _connectivity, _min_cells, _min_points, _min_height set the rule.  objectsInfo(), objectsFetch(records, object_id); with mapper_objects_dir
+// set the call writes objects.txt (one line per object: id, label name, cells, points, the box and the centroid in metres of the grid frame, ground and top
+// height) and objects_id.png (16 bit, id + 1, 0 where there is no object; row r is cell row ny - 1 - r as in the grid's images).
 // mapper_relabel=1 (default 0: nothing of this runs, every cloud, map and figure exactly as before): label fusion (the reference has no such step).
 // When the viewer ends -- after the last alignCarveUpTo, before the rendering and the ground grid, which then see the fused labels -- relabelAll lets the key-frames
 // j != i with |i - j| <= mapper_relabel_window (5; at most 8: a call takes 16 views) vote on the labels of key-frame i's cloud, at the map poses (mapPoseOf), every
@@ -141,7 +148,8 @@ public:
         grid_params.min_obstacle_points = para.getData<int>("mapper_grid_min_obstacle_points", grid_params.min_obstacle_points);
         grid_params.h_min = para.getData<double>("mapper_grid_h_min", grid_params.h_min);
         grid_params.h_max = para.getData<double>("mapper_grid_h_max", grid_params.h_max);
-        if (grid) {
+        objects = para.getData<int>("mapper_objects", 0) != 0;
+        if (grid || objects) {          // (the objects stand on a grid of the same frame, whether or not the grid itself is wanted)
             double up[3] = {0, -1, 0}, fw[3] = {0, 0, 1};
             auto three = [&](const char* key, double* v) {
                 auto it = para.data.find(key);
@@ -151,6 +159,19 @@ public:
             };
             three("mapper_grid_up", up); three("mapper_grid_forward", fw);
             if (ssm_grid_frame_from_up(up, fw, grid_params.G) != SSM_OK) throw std::runtime_error("Mapper: mapper_grid_up and mapper_grid_forward do not span a frame");
+        }
+        objects_dir = para.getData<string>("mapper_objects_dir", string(""));
+        ssm_objects_params_default(&objects_params);
+        objects_params.connectivity = para.getData<int>("mapper_objects_connectivity", objects_params.connectivity);
+        objects_params.min_cells = para.getData<int>("mapper_objects_min_cells", objects_params.min_cells);
+        objects_params.min_points = para.getData<int>("mapper_objects_min_points", objects_params.min_points);
+        objects_params.min_height = para.getData<double>("mapper_objects_min_height", objects_params.min_height);
+        {
+            auto it = para.data.find("mapper_objects_labels");
+            if (it != para.data.end()) {
+                istringstream ss(it->second); int l; objects_params.label_mask = 0;
+                while (ss >> l) { if (l < 0 || l > 11) throw std::runtime_error("Mapper: mapper_objects_labels takes label ids 0..11"); objects_params.label_mask |= 1u << l; }
+            }
         }
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
@@ -181,7 +202,7 @@ public:
             if (!kfs.empty()) updateMap(kfs, true, map, t0);          // (without a key-frame there is no map to rebuild)
         }
         if (render) renderAll(keyframesNow());          // every key-frame is a view of the clouds around it, in their final state
-        if (grid) buildGrid(keyframesNow());            // one ground grid of every key-frame's cloud, in its final state
+        if (grid || objects) buildGrid(keyframesNow()); // one ground grid of every key-frame's cloud, in its final state; and the objects that stand on it
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
         }
@@ -493,6 +514,7 @@ public:
     struct GridInfo { bool built = false, skipped = false; ssm_grid_info counts{}; };          // skipped: the extent exceeded 2^24 cells (or there was no key-frame)
     typedef Owned<ssm_grid_target, ssm_grid_target_free> GridTarget;          // the device accumulators and outputs
     void buildGrid(const vector<RGBDFrame::Ptr>& kfs) {
+        objectsState = ObjectsInfo(); objectRecords.clear(); objectIds.clear();
         gridState = GridInfo(); gridSpec = grid_params; gridSpec.nx = gridSpec.ny = 0;
         gridCls.clear(); gridGroundLabel.clear(); gridObstacleLabel.clear(); gridGroundQ.clear(); gridTopQ.clear(); gridN.clear(); gridNHigh.clear();
         if (kfs.empty()) { gridState.skipped = true; return; }
@@ -527,7 +549,8 @@ public:
         d.check(ssm_grid_fetch(d.ctx(), target.t, gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), gridTopQ.data(), gridN.data(), gridNHigh.data()),
                 "ssm_grid_fetch");
         gridSpec = P; gridState.counts = I; gridState.built = true;
-        if (!grid_dir.empty()) {
+        if (objects) extractObjects(d, target.t, L, P);
+        if ((grid || !objects) && !grid_dir.empty()) {          // (a grid built only for the objects writes no grid files)
             cv::Mat col, hgt; col.create(P.ny, P.nx, CV_8UC3); hgt.create(P.ny, P.nx, CV_16UC1);
             ssm_grid_colours(gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), P.nx, P.ny, P.h_min, col.data, hgt.ptr<uint16_t>());
             ofstream txt(grid_dir + "/grid.txt");
@@ -540,6 +563,53 @@ public:
         }
     }
     bool buildsGrid() const { return grid; }
+    // object extraction: both stages on the grid target buildGrid has just built and the cloud list it was built from (the same clouds at the same poses)
+    struct ObjectsInfo { bool built = false; ssm_objects_info counts{}; };
+    typedef Owned<ssm_objects_target, ssm_objects_target_free> ObjectsTarget;
+    static const char* labelName(int l) {
+        static const char* names[12] = {"Sky", "Building", "Pole", "Road_Marking", "Road", "Pavement", "Tree", "Sign_Symbol", "Fence", "Vehicle", "Pedestrian", "Bike"};
+        return l >= 0 && l < 12 ? names[l] : "Unknown";
+    }
+    template <class List /* CloudList, declared below */> void extractObjects(ssm::Device& d, ssm_grid_target* grid_target, const List& L, const ssm_grid_params& P) {
+        ObjectsTarget target(d.ctx());
+        d.check(ssm_objects_target_create(d.ctx(), P.nx, P.ny, &target.t), "ssm_objects_target_create");
+        ssm_objects_info I{};
+        d.check(ssm_objects_grid(d.ctx(), grid_target, &objects_params, target.t, &I), "ssm_objects_grid");
+        if (device_map) d.check(ssm_objects_clouds(d.ctx(), grid_target, target.t, L.cl.data(), L.poses.data(), L.m, &I), "ssm_objects_clouds");
+        else d.check(ssm_objects_points(d.ctx(), grid_target, target.t, L.pts.data(), L.n.data(), L.poses.data(), L.m, nullptr, &I), "ssm_objects_points");
+        int K = 0;
+        d.check(ssm_objects_fetch(d.ctx(), target.t, nullptr, 0, &K, nullptr), "ssm_objects_fetch");
+        objectRecords.resize((size_t)K); objectIds.resize((size_t)P.nx * P.ny);
+        d.check(ssm_objects_fetch(d.ctx(), target.t, objectRecords.data(), K, &K, objectIds.data()), "ssm_objects_fetch");
+        objectsState.counts = I; objectsState.built = true;
+        if (!objects_dir.empty()) {
+            ofstream txt(objects_dir + "/objects.txt");
+            txt << setprecision(17);
+            for (int k = 0; k < K; k++) {
+                const ssm_object& o = objectRecords[(size_t)k];
+                const double n = o.n_points ? (double)o.n_points : 1.0;
+                txt << k << " " << labelName(o.label) << " " << o.cells << " " << o.n_points << " " << o.x_min_q / 1024.0 << " " << o.x_max_q / 1024.0 << " " << o.y_min_q / 1024.0 << " "
+                    << o.y_max_q / 1024.0 << " " << o.z_min_q / 1024.0 << " " << o.z_max_q / 1024.0 << " " << (double)o.sum_x / n / 1024.0 << " " << (double)o.sum_y / n / 1024.0 << " "
+                    << (double)o.sum_z / n / 1024.0 << " " << o.ground_q / 1024.0 << " " << o.top_q / 1024.0 << "\n";
+            }
+            txt.close();
+            cv::Mat img; img.create(P.ny, P.nx, CV_16UC1);
+            for (int r = 0; r < P.ny; r++) for (int x = 0; x < P.nx; x++) {
+                const int32_t id = objectIds[(size_t)(P.ny - 1 - r) * P.nx + x];
+                img.ptr<uint16_t>(r)[x] = (uint16_t)(id < 0 ? 0 : min(id + 1, 65535));
+            }
+            if (!(txt && ssm::imwritePNG(objects_dir + "/objects_id.png", img))) throw std::runtime_error("Mapper: cannot write the objects to " + objects_dir);
+        }
+    }
+    bool extractsObjects() const { return objects; }
+    // the last extractObjects (not while the viewer thread runs): what happened and the counts; the records and the object_id image of the grid gridParams() describes
+    const ObjectsInfo& objectsInfo() const { return objectsState; }
+    bool objectsFetch(vector<ssm_object>* records, vector<int32_t>* object_id) const {
+        if (!objectsState.built) return false;
+        if (records) *records = objectRecords;
+        if (object_id) *object_id = objectIds;
+        return true;
+    }
     // the last buildGrid (not while the viewer thread runs): what happened and the counts; the spec actually used (nx = ny = 0 when nothing was built); the arrays,
     // nx ny entries each, cell (cx, cy) at cy nx + cx -- each pointer may be null; false: nothing was built
     const GridInfo& gridInfo() const { return gridState; }
@@ -706,6 +776,7 @@ protected:
     std::unordered_map<const RGBDFrame*, ssm_render_compare_info> renderInfo;      // key-frame -> its view's comparison (viewer thread, or its owner once that has ended)
     bool relabel = false; int relabel_window = 5, relabelled = 0, relabelViewsAlive = 0; ssm_relabel_params relabel_params{}; bool relabel_hash = false; uint64_t relabelFnv = 0;
     std::unordered_map<const RGBDFrame*, ssm_relabel_info> relabelInfo;  // key-frame -> what the views did to its labels (viewer thread, or its owner once that has ended)
+    bool objects = false; string objects_dir; ssm_objects_params objects_params{}; ObjectsInfo objectsState; vector<ssm_object> objectRecords; vector<int32_t> objectIds;
     bool grid = false; string grid_dir; ssm_grid_params grid_params{}, gridSpec{}; GridInfo gridState;
     vector<uint8_t> gridCls, gridGroundLabel, gridObstacleLabel; vector<int32_t> gridGroundQ, gridTopQ; vector<uint32_t> gridN, gridNHigh;      // the last build's arrays
     std::unordered_map<const RGBDFrame*, ssm_sor_info> sorInfo;          // key-frame -> what the filter did to its cloud (viewer thread, or its owner once that has ended)

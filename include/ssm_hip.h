@@ -632,6 +632,62 @@ int  ssm_debug_grid_form(ssm_ctx* ctx, int form);
 void ssm_grid_colours(const uint8_t* cls, const uint8_t* ground_label, const uint8_t* obstacle_label, const int32_t* ground_q, int nx, int ny, double h_min,
                       uint8_t* bgr_out, uint16_t* height_out);
 
+/* ---- object extraction: labelled obstacle instances from a built ground grid.  The reference has no such step; DESIGN.md s.21 is the contract,
+ * include/ssm/objects_core.h the arithmetic shared by the device path and the host functions (device == host byte for byte; integers only).
+ * Stage 1, cells: a cell is a MEMBER when its class is obstacle (4), its obstacle_label is below 12 and bit obstacle_label of label_mask is set.  Two members are
+ * joined when they are adjacent under `connectivity` (4 or 8) and have the same obstacle_label; a COMPONENT is a class of the closure, its root its smallest cell
+ * index cy nx + cx.  A component is KEPT when cells >= min_cells, cell_points (the sum of its cells' n_high) >= min_points and top_q - ground_q (the largest top_q
+ * and the smallest ground_q of its cells) >= llrint(1024 min_height); the info counts the first rule that fails, in that order.  The kept components are the
+ * objects 0 .. K - 1 in ascending root order; object_id (int32 per cell) is the object of a kept component's cells and -1 everywhere else.
+ * Stage 2, points: a point of the grid's clouds is a point of object k when the grid used it, it is HIGH in its cell and its cell's object_id is k.  Per object
+ * the count, those whose own label is the object's (n_label), the box and the sums of the quantised grid coordinates (units of 2^-10 m).  Before stage 2 the
+ * minima are INT32_MAX, the maxima INT32_MIN, counts and sums 0.
+ * SSM_E_INVAL: a null argument; a target of another context; a grid target never built or an object target smaller than the grid; connectivity other than 4 or 8;
+ * negative min_cells or min_points; a negative or non-finite min_height; a grid whose extent leaves +-2^20 m; stage 2 before stage 1, after the grid target was
+ * built again, or with a total point count other than that build's; the same cloud twice; 2^31 points or more. */
+typedef struct { uint32_t label_mask; int32_t connectivity, min_cells, min_points; double min_height; } ssm_objects_params;
+typedef struct { int64_t member_cells, components, kept, rejected_cells, rejected_points, rejected_height, n_in, object_points; } ssm_objects_info;   /* the last two: stage 2 */
+typedef struct {
+    int32_t root, label; uint32_t cells, n_points; uint64_t cell_points; int32_t cx_min, cx_max, cy_min, cy_max; int32_t ground_q, top_q;
+    int32_t x_min_q, x_max_q, y_min_q, y_max_q, z_min_q, z_max_q; uint32_t n_label, pad; int64_t sum_x, sum_y, sum_z;
+} ssm_object;                                                               /* 104 bytes */
+typedef struct ssm_objects_target ssm_objects_target;
+/* label_mask: Vehicle, Pedestrian, Bike (bits 9, 10, 11); connectivity 8; min_cells 2; min_points 20; min_height 0.3 m */
+void ssm_objects_params_default(ssm_objects_params* p);
+/* device labels, records and the object_id image for grids of up to nx ny cells, reused across calls */
+int  ssm_objects_target_create(ssm_ctx* ctx, int nx, int ny, ssm_objects_target** target_out);
+void ssm_objects_target_free(ssm_ctx* ctx, ssm_objects_target* target);
+/* stage 1 on the grid target's last build; nothing is uploaded.  params NULL: the defaults; info may be NULL */
+int  ssm_objects_grid(ssm_ctx* ctx, const ssm_grid_target* grid, const ssm_objects_params* params, ssm_objects_target* target, ssm_objects_info* info);
+/* stage 2 on the device clouds the grid was built from, at the same poses, under the grid build's parameters */
+int  ssm_objects_clouds(ssm_ctx* ctx, const ssm_grid_target* grid, ssm_objects_target* target, ssm_cloud* const* clouds, const double* T_clouds, int m, ssm_objects_info* info);
+/* the same from host arrays, through the device; ids_out (may be NULL): one int32 per point of the concatenation, its object or -1 */
+int  ssm_objects_points(ssm_ctx* ctx, const ssm_grid_target* grid, ssm_objects_target* target, const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m,
+                        int32_t* ids_out, ssm_objects_info* info);
+/* the same on the map the last ssm_viewer_map_update left on the device, at the identity pose */
+int  ssm_objects_viewer_map(ssm_ctx* ctx, const ssm_grid_target* grid, ssm_objects_target* target, ssm_objects_info* info);
+/* the K records of the target's last stage 1 (with the point figures of its last stage 2) and the object_id image (nx ny entries); either may be NULL.  cap < K:
+ * SSM_E_CAPACITY, *n_out = K and nothing else written */
+int  ssm_objects_fetch(ssm_ctx* ctx, const ssm_objects_target* target, ssm_object* out, int cap, int* n_out, int32_t* object_id);
+/* stage 1 on the CPU, no GPU, the same bits, from the arrays ssm_grid_fetch / ssm_grid_host give */
+int  ssm_objects_cells_host(const uint8_t* cls, const uint8_t* obstacle_label, const int32_t* ground_q, const int32_t* top_q, const uint32_t* n_high, int nx, int ny,
+                            const ssm_objects_params* params, ssm_object* out, int cap, int* n_out, int32_t* object_id, ssm_objects_info* info);
+/* ssm_grid_host, then both stages, on the CPU: the same bits as the device chain.  object_id (nx ny entries) and ids_out (one per point) may be NULL */
+int  ssm_objects_host(const ssm_point* const* pts, const int32_t* n, const double* T_clouds, int m, const ssm_grid_params* grid_params, const ssm_objects_params* params,
+                      ssm_object* out, int cap, int* n_out, int32_t* object_id, int32_t* ids_out, ssm_objects_info* info);
+/* for the tests: hand-made cell arrays (nx ny entries each) uploaded and stage 1 run on them, so that the labelling can be tested at any shape without clouds
+ * (stage 2 is refused after it).  SSM_E_INVAL also when the n_high sum to 2^31 or more: no built grid does */
+int  ssm_debug_objects_cells(ssm_ctx* ctx, ssm_objects_target* target, const uint8_t* cls, const uint8_t* obstacle_label, const int32_t* ground_q, const int32_t* top_q,
+                             const uint32_t* n_high, int nx, int ny, const ssm_objects_params* params, ssm_objects_info* info);
+/* how the context's later stage-2 calls accumulate: 0 one atomic per point and figure, 1 one per run of adjacent lanes with the same object, -1 the default; the
+ * same bits either way */
+int  ssm_debug_objects_form(ssm_ctx* ctx, int form);
+/* the per-point object ids of the context's last stage-2 call (n: that call's point count) */
+int  ssm_debug_objects_point_ids(ssm_ctx* ctx, int32_t* out, int64_t n);
+/* the labelling's tile, for the tests */
+int  ssm_debug_objects_tile_w(void);
+int  ssm_debug_objects_tile_h(void);
+
 /* ---- label fusion: the key-frames around a cloud (the views: depth image, label image, camera, world pose) vote on the label of each of its points, and a point
  * takes the label its views agree on.  The reference has no such step; DESIGN.md s.20 is the contract, include/ssm/relabel_core.h the arithmetic shared by the
  * device path and the host function (device == host bit for bit).  A view votes for a point with the label at the point's pixel when carving's verdict (s.16) is

@@ -127,6 +127,14 @@ class GridParams(C.Structure):
                 ("h_max", C.c_double), ("step", C.c_double), ("ground_radius", C.c_int32), ("min_obstacle_points", C.c_int32)]
 
 
+class ObjectsParams(C.Structure):
+    _fields_ = [("label_mask", C.c_uint32), ("connectivity", C.c_int32), ("min_cells", C.c_int32), ("min_points", C.c_int32), ("min_height", C.c_double)]
+
+
+class ObjectsInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("member_cells", "components", "kept", "rejected_cells", "rejected_points", "rejected_height", "n_in", "object_points")]
+
+
 class GridInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_in", "n_finite", "out_of_band", "outside", "n_used", "unobserved", "drivable", "walkable", "other_ground", "obstacle")]
 
@@ -296,6 +304,21 @@ SYMBOLS = {
     "ssm_debug_grid_cells": (_I, [_P, _P, _P]),
     "ssm_debug_grid_form": (_I, [_P, _I]),
     "ssm_grid_colours": (None, [_P, _P, _P, _P, _I, _I, C.c_double, _P, _P]),
+    "ssm_objects_params_default": (None, [C.POINTER(ObjectsParams)]),
+    "ssm_objects_target_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "ssm_objects_target_free": (None, [_P, _P]),
+    "ssm_objects_grid": (_I, [_P, _P, C.POINTER(ObjectsParams), _P, C.POINTER(ObjectsInfo)]),
+    "ssm_objects_clouds": (_I, [_P, _P, _P, _P, _P, _I, C.POINTER(ObjectsInfo)]),
+    "ssm_objects_points": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, C.POINTER(ObjectsInfo)]),
+    "ssm_objects_viewer_map": (_I, [_P, _P, _P, C.POINTER(ObjectsInfo)]),
+    "ssm_objects_fetch": (_I, [_P, _P, _P, _I, C.POINTER(_I), _P]),
+    "ssm_objects_cells_host": (_I, [_P, _P, _P, _P, _P, _I, _I, C.POINTER(ObjectsParams), _P, _I, C.POINTER(_I), _P, C.POINTER(ObjectsInfo)]),
+    "ssm_objects_host": (_I, [_P, _P, _P, _I, C.POINTER(GridParams), C.POINTER(ObjectsParams), _P, _I, C.POINTER(_I), _P, _P, C.POINTER(ObjectsInfo)]),
+    "ssm_debug_objects_cells": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, C.POINTER(ObjectsParams), C.POINTER(ObjectsInfo)]),
+    "ssm_debug_objects_form": (_I, [_P, _I]),
+    "ssm_debug_objects_point_ids": (_I, [_P, _P, C.c_int64]),
+    "ssm_debug_objects_tile_w": (_I, []),
+    "ssm_debug_objects_tile_h": (_I, []),
     "ssm_relabel_params_default": (None, [C.POINTER(RelabelParams)]),
     "ssm_relabel_view_create": (_I, [_P, _P, _P, _I, _I, C.POINTER(Camera), C.POINTER(_P)]),
     "ssm_relabel_view_free": (None, [_P, _P]),

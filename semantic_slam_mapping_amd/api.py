@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, RelabelParams, RelabelInfo, RelabelHostView
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, ObjectsParams, ObjectsInfo, RelabelParams, RelabelInfo, RelabelHostView
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -353,6 +353,68 @@ def grid_colours(cls, ground_label, obstacle_label, ground_q, h_min=-3.0):
     bgr = np.zeros((ny, nx, 3), np.uint8); height = np.zeros((ny, nx), np.uint16)
     _lib.load().ssm_grid_colours(_ptr(cls), _ptr(gl), _ptr(ol), _ptr(gq), nx, ny, float(h_min), _ptr(bgr), _ptr(height))
     return bgr, height
+
+
+OBJECTS_INFO_FIELDS = ("member_cells", "components", "kept", "rejected_cells", "rejected_points", "rejected_height", "n_in", "object_points")
+OBJECTS_FIELDS = ("label_mask", "connectivity", "min_cells", "min_points", "min_height")
+OBJECT_DTYPE = np.dtype([("root", "i4"), ("label", "i4"), ("cells", "u4"), ("n_points", "u4"), ("cell_points", "u8"), ("cx_min", "i4"), ("cx_max", "i4"), ("cy_min", "i4"),
+                         ("cy_max", "i4"), ("ground_q", "i4"), ("top_q", "i4"), ("x_min_q", "i4"), ("x_max_q", "i4"), ("y_min_q", "i4"), ("y_max_q", "i4"), ("z_min_q", "i4"),
+                         ("z_max_q", "i4"), ("n_label", "u4"), ("pad", "u4"), ("sum_x", "i8"), ("sum_y", "i8"), ("sum_z", "i8")])
+
+
+def objects_params(**kw):
+    """object extraction's parameters (ssm_objects_params): the library's defaults (ssm_objects_params_default) with the given fields replaced; labels=[ids] sets
+    label_mask from a list of label ids"""
+    bad = set(kw) - set(OBJECTS_FIELDS) - {"labels"}
+    if bad:
+        raise TypeError("unknown object parameters: " + ", ".join(sorted(bad)))
+    P = ObjectsParams()
+    _lib.load().ssm_objects_params_default(C.byref(P))
+    for k, v in kw.items():
+        if k == "labels":
+            P.label_mask = sum({1 << int(l) for l in v if 0 <= int(l) < 32})
+        elif k == "min_height":
+            P.min_height = float(v)
+        else:
+            setattr(P, k, int(v))
+    return P
+
+
+def _objects_info(I):
+    return {k: getattr(I, k) for k in OBJECTS_INFO_FIELDS}
+
+
+def objects_cells_host(cls, obstacle_label, ground_q, top_q, n_high, cap=None, **params):
+    """stage 1 of object extraction on the CPU (ssm_objects_cells_host, no GPU) from the ny x nx cell arrays of a grid -> (records of OBJECT_DTYPE, the object_id
+    image, info); cap: the record buffer's size (default: enough)"""
+    arr = [np.ascontiguousarray(a, t) for a, t in ((cls, np.uint8), (obstacle_label, np.uint8), (ground_q, np.int32), (top_q, np.int32), (n_high, np.uint32))]
+    if arr[0].ndim != 2 or any(a.shape != arr[0].shape for a in arr):
+        raise ValueError("five ny x nx arrays of one grid")
+    ny, nx = arr[0].shape
+    P = objects_params(**params); I = ObjectsInfo(); n = C.c_int(0)
+    cap = nx * ny if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), OBJECT_DTYPE); ids = np.full((ny, nx), -2, np.int32)
+    lib = _lib.load()
+    rc = lib.ssm_objects_cells_host(*[_ptr(a) for a in arr], nx, ny, C.byref(P), _ptr(out), cap, C.byref(n), _ptr(ids), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return out[:n.value].copy(), ids, _objects_info(I)
+
+
+def objects_host(clouds, T_clouds, grid=None, cap=None, **params):
+    """the ground grid, then both stages of object extraction, on the CPU (ssm_objects_host, no GPU): `clouds` (host arrays of POINT_DTYPE at the poses T_clouds),
+    grid: the grid's parameters as a dictionary -> (records, the object_id image, the per-point object ids of the concatenation, info)"""
+    keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
+    G = grid_params(**(grid or {})); P = objects_params(**params); I = ObjectsInfo(); k = C.c_int(0)
+    ok = G.nx >= 1 and G.ny >= 1 and G.nx * G.ny <= 1 << 24
+    shape = (G.ny, G.nx) if ok else (1, 1)
+    cap = min(shape[0] * shape[1], 1 << 20) if cap is None else int(cap)
+    out = np.zeros(max(cap, 1), OBJECT_DTYPE); oid = np.full(shape, -2, np.int32); ids = np.full(max(int(n[:m].sum()), 1), -2, np.int32)
+    lib = _lib.load()
+    rc = lib.ssm_objects_host(ptrs, _ptr(n), _ptr(Tc), m, C.byref(G), C.byref(P), _ptr(out), cap, C.byref(k), _ptr(oid), _ptr(ids), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return out[:k.value].copy(), oid, ids[:int(n[:m].sum())].copy(), _objects_info(I)
 
 
 RELABEL_INFO_FIELDS = ("n_in", "n_supported", "n_voted", "n_changed", "n_filled", "pairs_supported", "pairs_voted")
@@ -1438,6 +1500,81 @@ class Context:
         P = grid_params(**params); I = GridInfo()
         self._chk(self.lib.ssm_grid_viewer_map(self.h, target, C.byref(P), C.byref(I)))
         return self._grid_result(target, P, I, cells)
+
+    def objects_target(self, nx, ny):
+        """the device labels, records and object_id image of object extraction for grids of up to nx * ny cells (ssm_objects_target_create) -> an opaque handle
+        (objects_target_free it)"""
+        t = C.c_void_p()
+        self._chk(self.lib.ssm_objects_target_create(self.h, int(nx), int(ny), C.byref(t)))
+        self._objects_sizes = getattr(self, "_objects_sizes", {})
+        self._objects_sizes[t.value] = None
+        return t.value
+
+    def objects_target_free(self, target):
+        self._objects_sizes.pop(target, None)
+        self.lib.ssm_objects_target_free(self.h, target)
+
+    def objects_form(self, form):
+        """how later stage-2 calls accumulate (ssm_debug_objects_form): 0 one atomic per point and figure, 1 one per run of adjacent lanes with the same object,
+        -1 the default"""
+        self._chk(self.lib.ssm_debug_objects_form(self.h, int(form)))
+
+    def objects_grid(self, grid_target, target, **params):
+        """stage 1 on the grid target's last build (ssm_objects_grid) -> info"""
+        P = objects_params(**params); I = ObjectsInfo()
+        self._chk(self.lib.ssm_objects_grid(self.h, grid_target, C.byref(P), target, C.byref(I)))
+        self._objects_sizes[target] = self._grid_sizes[grid_target]
+        return _objects_info(I)
+
+    def objects_cells(self, target, cls, obstacle_label, ground_q, top_q, n_high, **params):
+        """hand-made ny x nx cell arrays uploaded and stage 1 run on them (ssm_debug_objects_cells) -> info"""
+        arr = [np.ascontiguousarray(a, t) for a, t in ((cls, np.uint8), (obstacle_label, np.uint8), (ground_q, np.int32), (top_q, np.int32), (n_high, np.uint32))]
+        if arr[0].ndim != 2 or any(a.shape != arr[0].shape for a in arr):
+            raise ValueError("five ny x nx arrays of one grid")
+        ny, nx = arr[0].shape
+        P = objects_params(**params); I = ObjectsInfo()
+        self._chk(self.lib.ssm_debug_objects_cells(self.h, target, *[_ptr(a) for a in arr], nx, ny, C.byref(P), C.byref(I)))
+        self._objects_sizes[target] = (nx, ny)
+        return _objects_info(I)
+
+    def objects_clouds(self, grid_target, target, clouds, T_clouds):
+        """stage 2 on the device clouds the grid was built from, at the same poses (ssm_objects_clouds) -> info"""
+        _, arr, _, Tc, m = _pack_clouds(clouds, T_clouds, False)
+        I = ObjectsInfo()
+        self._chk(self.lib.ssm_objects_clouds(self.h, grid_target, target, arr, _ptr(Tc), m, C.byref(I)))
+        return _objects_info(I)
+
+    def objects_points(self, grid_target, target, clouds, T_clouds):
+        """stage 2 on host arrays, through the device (ssm_objects_points) -> (the per-point object ids of the concatenation, info)"""
+        keep, ptrs, n, Tc, m = _pack_clouds(clouds, T_clouds, True)
+        total = int(n[:m].sum())
+        ids = np.full(max(total, 1), -2, np.int32); I = ObjectsInfo()
+        self._chk(self.lib.ssm_objects_points(self.h, grid_target, target, ptrs, _ptr(n), _ptr(Tc), m, _ptr(ids), C.byref(I)))
+        return ids[:total].copy(), _objects_info(I)
+
+    def objects_viewer_map(self, grid_target, target):
+        """stage 2 on the map the last viewer_map_update left on the device (ssm_objects_viewer_map) -> info"""
+        I = ObjectsInfo()
+        self._chk(self.lib.ssm_objects_viewer_map(self.h, grid_target, target, C.byref(I)))
+        return _objects_info(I)
+
+    def objects_fetch(self, target, cap=None):
+        """the records of the target's last stage 1 with the point figures of its last stage 2, and the object_id image (ssm_objects_fetch) -> (records of
+        OBJECT_DTYPE, ny x nx int32); cap: the record buffer's size (default: enough)"""
+        size = self._objects_sizes[target]          # None: nothing was labelled into the target through this binding -- the image's size is not known, so it is not fetched
+        n = C.c_int(0)
+        if cap is None:
+            self._chk(self.lib.ssm_objects_fetch(self.h, target, None, 0, C.byref(n), None))
+            cap = n.value
+        out = np.zeros(max(int(cap), 1), OBJECT_DTYPE); oid = np.full((size[1], size[0]), -2, np.int32) if size else None
+        self._chk(self.lib.ssm_objects_fetch(self.h, target, _ptr(out), int(cap), C.byref(n), _ptr(oid)))
+        return out[:n.value].copy(), oid
+
+    def objects_point_ids(self, n):
+        """the per-point object ids of the context's last stage-2 call (ssm_debug_objects_point_ids)"""
+        ids = np.full(max(int(n), 1), -2, np.int32)
+        self._chk(self.lib.ssm_debug_objects_point_ids(self.h, _ptr(ids), int(n)))
+        return ids[:int(n)].copy()
 
     def relabel_view(self, depth, sem_bgr, camera=None):
         """a view of label fusion: the depth image goes to the device and the label image is made there from the semantic BGR image (ssm_relabel_view_create) -> an

@@ -198,10 +198,25 @@ struct RenderWork { DevBuf<int32_t> info; PinBuf<int32_t> h_info; DevBuf<unsigne
 // a grid target (ssm_grid.hip): the raw cells and the seven output arrays for up to cap cells; nx, ny, h_min: the last build's (built: there is one)
 struct ssm_grid_target {
     int64_t cap = 0; int nx = 0, ny = 0, device = 0; bool built = false;
+    const ssm_ctx* owner = nullptr; ssm_grid_params params{}; int64_t builds = 0, n_in = 0;      // the context that made it; the last build's parameters, number and point count (ssm_objects.hip)
     DevBuf<ssm_grid_cell> cells; DevBuf<uint8_t> cls, ground_label, obstacle_label; DevBuf<int32_t> ground_q, top_q; DevBuf<uint32_t> n, n_high;
 };
 // workspace of the ground grid: the info
 struct GridWork { DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; int form = GRID_FORM_DEFAULT; };          // form: ssm_debug_grid_form
+// an object target (ssm_objects.hip): the labelling's arrays for up to cap cells, the component and object records (grown by the call that needs more), the
+// object_id image.  staged: stage 1 has run (nx, ny, K: its grid and objects); grid, grid_build: the grid target and build it ran on (null: hand-made cells)
+struct ssm_objects_target {
+    int64_t cap = 0; int nx = 0, ny = 0, device = 0, K = 0; const ssm_ctx* owner = nullptr; bool staged = false;
+    const ssm_grid_target* grid = nullptr; int64_t grid_build = 0;
+    DevBuf<int32_t> labels, isroot, rank, object_id, keep, kid; DevBuf<uint16_t> loc; DevBuf<uint8_t> tmp; size_t tmp_bytes = 0;
+    DevBuf<ssm_object> comp, objs; int32_t comp_cap = 0;
+};
+// workspace of object extraction: the info, the last stage-2 call's per-point ids (n_ids of them, < 0: none yet), the staging of ssm_debug_objects_cells
+struct ObjectsWork {
+    DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; PinBuf<int32_t> h_count; int form = OBJECTS_FORM_DEFAULT;
+    DevBuf<int32_t> ids; int64_t ids_cap = 0, n_ids = -1;
+    DevBuf<uint8_t> in_cls, in_label; DevBuf<int32_t> in_ground, in_top; DevBuf<uint32_t> in_high; int64_t in_cap = 0;
+};
 // a view of label fusion (ssm_relabel.hip): a key-frame's depth and label images in device memory and its camera; packed: depth | label << 16 per pixel, what
 // the vote gathers under the packed form (the default; the depth image is then freed once the view is made), empty under the other (ssm_debug_relabel_form)
 struct ssm_relabel_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> label; DevBuf<uint32_t> packed; int w = 0, h = 0, device = 0; const ssm_ctx* owner = nullptr; ssm_camera cam{}; };
@@ -304,6 +319,7 @@ struct ssm_ctx {
     RenderWork render;                                       // map rendering: likewise
     AlignWork align;                                         // dense alignment: likewise
     GridWork grid;                                           // ground grid: likewise
+    ObjectsWork objects;                                     // object extraction: likewise
     RelabelWork relabel;                                     // label fusion: likewise
     CloudTableWork clouds;                                   // the cloud table and host-array staging of the three: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet

@@ -6,6 +6,7 @@
 #include "ssm_host.h"
 using namespace ssm_gridc;
 
+static std::atomic<int64_t> g_grid_builds{0};          // every build of every target has a number of its own: what ssm_objects.hip remembers of the build it labelled
 // what every build checks first
 static int grid_begin(ssm_ctx* c, ssm_grid_target* t, const ssm_grid_params* params, ssm_grid_params* P, Setup* S)
 {
@@ -33,7 +34,7 @@ static int grid_run(ssm_ctx* c, ssm_grid_target* t, const ssm_grid_params& P, co
     HIPCHK(c, hipMemcpyAsync(W.h_info, W.info, 80, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
     tab.in_flight = nullptr;
-    t->built = true; t->nx = S.nx; t->ny = S.ny;
+    t->built = true; t->nx = S.nx; t->ny = S.ny; t->params = P; t->builds = ++g_grid_builds; t->n_in = tab.total;
     unsigned long long* hi = W.h_info;
     hi[1] = hi[0] - hi[1];                       // the kernels count the rejected points: n_finite = n_in - rejected
     if (info) memcpy(info, hi, 80);
@@ -49,7 +50,7 @@ extern "C" int ssm_grid_target_create(ssm_ctx* c, int nx, int ny, ssm_grid_targe
     if (nx < 1 || ny < 1 || (int64_t)nx * ny > MAX_CELLS) FAIL(c, SSM_E_INVAL, "grid: at least 1 x 1 and at most 2^24 cells");
     std::unique_ptr<ssm_grid_target> t(new ssm_grid_target());
     const size_t nc = (size_t)nx * ny;
-    t->cap = (int64_t)nc; t->device = c->device;
+    t->cap = (int64_t)nc; t->device = c->device; t->owner = c;
     DALLOC(c, t->cells, nc); DALLOC(c, t->cls, nc); DALLOC(c, t->ground_label, nc); DALLOC(c, t->obstacle_label, nc); DALLOC(c, t->ground_q, nc); DALLOC(c, t->top_q, nc);
     DALLOC(c, t->n, nc); DALLOC(c, t->n_high, nc);
     *out = t.release();

@@ -13,6 +13,7 @@
 #include "../../include/ssm/render_core.h"
 #include "../../include/ssm/align_core.h"
 #include "../../include/ssm/grid_core.h"
+#include "../../include/ssm/objects_core.h"
 #include "../../include/ssm/relabel_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
@@ -143,6 +144,12 @@ SSM_HIDDEN CloudRule render_cloud_rule();          // a cloud may be listed twic
 // the arguments a call may have (host function and device entry points alike); S: what the parameters become for grid_core.h
 SSM_HIDDEN int grid_check(ssm_ctx* c, const ssm_grid_params& P, ssm_gridc::Setup* S);
 SSM_HIDDEN CloudRule grid_cloud_rule();            // no cloud twice; fewer than 2^31 points
+
+// ---------------------------------------------------------------- object extraction (ssm_objects_host.cpp)
+// the parameters a call may have (host functions and device entry points alike); S: what they become for objects_core.h
+SSM_HIDDEN int objects_check(ssm_ctx* c, const ssm_objects_params& P, ssm_objc::Setup* S);
+SSM_HIDDEN int objects_extent_check(ssm_ctx* c, double x0, double y0, double cell, int nx, int ny);      // SSM_E_INVAL for a grid whose extent leaves +-2^20 m
+SSM_HIDDEN CloudRule objects_cloud_rule();         // no cloud twice; fewer than 2^31 points (the grid's bound)
 
 // ---------------------------------------------------------------- label fusion (ssm_relabel_host.cpp)
 // the number of views and the parameters a call may have (host function and device entry points alike)

@@ -272,6 +272,25 @@ struct GridBufs { ssm_grid_cell* cells; uint8_t *cls, *ground_label, *obstacle_l
 int k_grid_block();
 hipError_t k_grid(const ssm_gridc::Setup& S, const CloudSeg* seg, const int32_t* blk, int64_t total, const GridBufs& T, unsigned long long* info, int form, hipStream_t s);
 
+// object extraction (kernels_objects.hip; the arithmetic is include/ssm/objects_core.h).  Stage 1 on nx x ny cells: k_objects_label queues the tile forests, the rim
+// unions, the flatten pass and the scan of the roots; labels[i]: the root of cell i's component (-1: no member), rank[i]: the roots below cell i, rank[nc] their
+// number, which the host reads before k_objects_records (comp: that many records), which queues the figures, the keep decision, the scan of the kept (kid[C]: their
+// number), the compaction into objs and the paint of object_id.  info: 8 x int64 as ssm_objects_info (k_objects_label sets it).  Stage 2: k_objects_points over the
+// cloud table with blocks of k_objects_block() points; form as ssm_debug_objects_form.  Everything is queued on s, nothing waits.
+namespace ssm_objc { struct Setup; }
+enum { OBJECTS_FORM_POINTS = 0, OBJECTS_FORM_RUNS = 1, OBJECTS_FORM_DEFAULT = OBJECTS_FORM_RUNS };
+struct ObjectsCells { const uint8_t *cls, *obstacle_label; const int32_t *ground_q, *top_q; const uint32_t* n_high; int nx, ny; };
+struct ObjectsBufs { int32_t *labels, *isroot, *rank, *object_id; uint16_t* loc; void* tmp; size_t tmp_bytes; };
+int k_objects_tile_w();
+int k_objects_tile_h();
+int k_objects_block();
+size_t k_objects_tmp_bytes(int64_t nc);
+hipError_t k_objects_label(const ObjectsCells& G, const ssm_objc::Setup& S, const ObjectsBufs& B, unsigned long long* info, hipStream_t s);
+hipError_t k_objects_records(const ObjectsCells& G, const ssm_objc::Setup& S, const ObjectsBufs& B, int32_t C, ssm_object* comp, int32_t* keep, int32_t* kid, ssm_object* objs,
+                             unsigned long long* info, hipStream_t s);
+hipError_t k_objects_points(const ssm_gridc::Setup& G, const CloudSeg* seg, const int32_t* blk, int64_t total, const ssm_grid_cell* cells, const int32_t* object_id,
+                            ssm_object* objs, int32_t K, int32_t* point_ids, unsigned long long* info, int form, hipStream_t s);
+
 // label fusion (kernels_relabel.hip; the arithmetic is include/ssm/relabel_core.h): A.v views vote on the labels of the n points at pts, which change in place
 // (the 4 label bytes of a changed point).  votes, new_label: every point's record, n entries; info: 6 x uint64 (n_supported, n_voted, n_changed, n_filled,
 // pairs_supported, pairs_voted), cleared by the launcher.  form: RELABEL_FORM_IMAGES reads a view's depth and label images (View::depth, View::label),

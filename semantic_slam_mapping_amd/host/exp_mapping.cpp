@@ -37,6 +37,9 @@
 // `exp_mapping <parameters> --relabel` (or mapper_relabel=1): when the viewer ends, every key-frame's cloud takes the labels its neighbouring key-frames agree on (label
 // fusion: include/ssm/mapper.h), before the rendering and the grid, and one more map rebuild follows.  The summary line then carries `relabel_keyframes K
 // relabel_changed C relabel_filled F relabel_fnv H`: H is FNV-1a over every key-frame's label bytes, in order.  Without the flag nothing of this runs.
+// `exp_mapping <parameters> --objects [DIR]` (or mapper_objects=1, mapper_objects_dir=DIR): right after the ground grid, Mapper extracts the labelled obstacle instances
+// that stand on it (include/ssm/mapper.h); with DIR objects.txt and objects_id.png are written there.  The summary line then carries
+// `objects_found K objects_cells C objects_points P objects_fnv H`: the objects, their cells, their points, and FNV-1a over nx, ny, the records and the object_id image.
 // `exp_mapping <parameters> --grid [DIR]` (or mapper_grid=1, mapper_grid_dir=DIR): when the viewer ends, Mapper builds ONE ground grid from every key-frame's cloud at
 // its map pose (include/ssm/mapper.h); with DIR grid_colour.png, grid_height.png and grid.txt are written there.  The summary line then carries
 // `grid_cells C grid_drivable D grid_walkable W grid_obstacle O grid_fnv H`: the cells of the grid, three of its class counts, and FNV-1a over nx, ny and the fetched
@@ -166,6 +169,12 @@ int main(int argc, char** argv)
         if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_grid_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
     }
     if (grid) parameterReader.set("mapper_grid", "1");
+    bool objects = parameterReader.getData<int>("mapper_objects", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--objects") {
+        objects = true;
+        if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_objects_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
+    }
+    if (objects) parameterReader.set("mapper_objects", "1");
     bool relabel = parameterReader.getData<int>("mapper_relabel", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--relabel") relabel = true;
     if (relabel) { parameterReader.set("mapper_relabel", "1"); parameterReader.set("mapper_relabel_hash", "1"); }
@@ -469,6 +478,18 @@ int main(int argc, char** argv)
             eat(gh.data(), gh.size() * 4);
             cout << " grid_cells " << cls.size() << " grid_drivable " << G.counts.drivable << " grid_walkable " << G.counts.walkable << " grid_obstacle " << G.counts.obstacle
                  << " grid_fnv " << hex << h << dec;
+        }
+        if (objects) {          // (the viewer thread extracted the objects right after the grid as it ended)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before the objects were extracted" << endl; return 3; }
+            const Mapper::ObjectsInfo& O = mapper.objectsInfo();
+            vector<ssm_object> rec; vector<int32_t> oid;
+            mapper.objectsFetch(&rec, &oid);
+            uint64_t h = 0xCBF29CE484222325ull;           // FNV-1a over nx, ny, the records and the object_id image
+            auto eat = [&h](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; for (size_t k = 0; k < bytes; k++) { h ^= b[k]; h *= 0x100000001B3ull; } };
+            const int32_t shape[2] = {mapper.gridParams().nx, mapper.gridParams().ny};
+            eat(shape, sizeof shape); eat(rec.data(), rec.size() * sizeof(ssm_object)); eat(oid.data(), oid.size() * 4);
+            uint64_t cells = 0; for (const ssm_object& o : rec) cells += o.cells;
+            cout << " objects_found " << rec.size() << " objects_cells " << cells << " objects_points " << O.counts.object_points << " objects_fnv " << hex << h << dec;
         }
         if (timed > 0) {
             const Tracker::Timing& tt = tracker->timing; const double fr = tt.frames > 0 ? (double)tt.frames : 1.0;

@@ -153,7 +153,7 @@ int ssm_render_fetch(ssm_ctx*, const ssm_render_target* t, uint16_t* depth, uint
 int ssm_render_compare(ssm_ctx*, ssm_render_target* t, const uint16_t* depth, const uint8_t* sem, double scale, const ssm_render_params* params, ssm_render_compare_info* info, uint8_t* cls)
 { return ssm_render_compare_host(t->depth.data(), t->label.data(), t->w, t->h, depth, sem, scale, params, info, cls); }
 // the ground grid (Mapper with mapper_grid=1): a "target" is the host arrays, the linked host function in the device entry points' place
-struct ssm_grid_target { int64_t cap; int nx, ny; std::vector<uint8_t> cls, gl, ol; std::vector<int32_t> gq, tq; std::vector<uint32_t> n, nh; };
+struct ssm_grid_target { int64_t cap; int nx, ny; ssm_grid_params P; std::vector<uint8_t> cls, gl, ol; std::vector<int32_t> gq, tq; std::vector<uint32_t> n, nh; };
 int ssm_grid_target_create(ssm_ctx*, int nx, int ny, ssm_grid_target** out)
 {
     if (nx < 1 || ny < 1 || (int64_t)nx * ny > ((int64_t)1 << 24)) return SSM_E_INVAL;
@@ -166,7 +166,7 @@ int ssm_grid_points(ssm_ctx*, ssm_grid_target* t, const ssm_point* const* pts, c
     ssm_grid_params P; ssm_grid_params_default(&P); if (params) P = *params;
     if (P.nx >= 1 && P.ny >= 1 && (int64_t)P.nx * P.ny > t->cap) return SSM_E_INVAL;
     const int rc = ssm_grid_host(pts, n, Tc, m, &P, t->cls.data(), t->gl.data(), t->ol.data(), t->gq.data(), t->tq.data(), t->n.data(), t->nh.data(), nullptr, info);
-    if (rc == SSM_OK) { t->nx = P.nx; t->ny = P.ny; }
+    if (rc == SSM_OK) { t->nx = P.nx; t->ny = P.ny; t->P = P; }
     return rc;
 }
 int ssm_grid_clouds(ssm_ctx* c, ssm_grid_target* t, ssm_cloud* const* clouds, const double* Tc, int m, const ssm_grid_params* params, ssm_grid_info* info)
@@ -185,6 +185,48 @@ int ssm_grid_fetch(ssm_ctx*, const ssm_grid_target* t, uint8_t* cls, uint8_t* gl
     if (tq) memcpy(tq, t->tq.data(), nc * 4);
     if (n) memcpy(n, t->n.data(), nc * 4);
     if (nh) memcpy(nh, t->nh.data(), nc * 4);
+    return SSM_OK;
+}
+// object extraction (Mapper with mapper_objects=1): a "target" is the host records and image; stage 1 only remembers its parameters, stage 2 runs the linked host
+// function (the grid again, then both stages) in the device entry points' place
+struct ssm_objects_target { int64_t cap; ssm_objects_params P; std::vector<ssm_object> rec; std::vector<int32_t> oid; };
+int ssm_objects_target_create(ssm_ctx*, int nx, int ny, ssm_objects_target** out)
+{
+    if (nx < 1 || ny < 1 || (int64_t)nx * ny > ((int64_t)1 << 24)) return SSM_E_INVAL;
+    ssm_objects_target* t = new ssm_objects_target(); t->cap = (int64_t)nx * ny; ssm_objects_params_default(&t->P); *out = t; return SSM_OK;
+}
+void ssm_objects_target_free(ssm_ctx*, ssm_objects_target* t) { delete t; }
+int ssm_objects_grid(ssm_ctx*, const ssm_grid_target* g, const ssm_objects_params* params, ssm_objects_target* t, ssm_objects_info* info)
+{
+    if (!g || !t || (int64_t)g->nx * g->ny > t->cap || g->nx < 1) return SSM_E_INVAL;
+    ssm_objects_params_default(&t->P); if (params) t->P = *params;
+    t->rec.clear(); t->oid.resize((size_t)g->nx * g->ny); int n = 0;          // (a first call with cap 0 gives the count: records per object, never per cell)
+    int rc = ssm_objects_cells_host(g->cls.data(), g->ol.data(), g->gq.data(), g->tq.data(), g->nh.data(), g->nx, g->ny, &t->P, nullptr, 0, &n, nullptr, nullptr);
+    if (rc != SSM_OK && rc != SSM_E_CAPACITY) return rc;
+    t->rec.resize((size_t)n);
+    return ssm_objects_cells_host(g->cls.data(), g->ol.data(), g->gq.data(), g->tq.data(), g->nh.data(), g->nx, g->ny, &t->P, t->rec.data(), n, &n, t->oid.data(), info);
+}
+int ssm_objects_points(ssm_ctx*, const ssm_grid_target* g, ssm_objects_target* t, const ssm_point* const* pts, const int32_t* n, const double* Tc, int m, int32_t* ids, ssm_objects_info* info)
+{
+    if (!g || !t) return SSM_E_INVAL;
+    t->rec.clear(); t->oid.resize((size_t)g->nx * g->ny); int k = 0;
+    int rc = ssm_objects_host(pts, n, Tc, m, &g->P, &t->P, nullptr, 0, &k, nullptr, nullptr, nullptr);
+    if (rc != SSM_OK && rc != SSM_E_CAPACITY) return rc;
+    t->rec.resize((size_t)k);
+    return ssm_objects_host(pts, n, Tc, m, &g->P, &t->P, t->rec.data(), k, &k, t->oid.data(), ids, info);
+}
+int ssm_objects_clouds(ssm_ctx* c, const ssm_grid_target* g, ssm_objects_target* t, ssm_cloud* const* clouds, const double* Tc, int m, ssm_objects_info* info)
+{
+    std::vector<const ssm_point*> pts; std::vector<int32_t> n;
+    for (int k = 0; k < m; k++) { pts.push_back(clouds[k]->p.data()); n.push_back((int32_t)clouds[k]->p.size()); }
+    return ssm_objects_points(c, g, t, pts.data(), n.data(), Tc, m, nullptr, info);
+}
+int ssm_objects_fetch(ssm_ctx*, const ssm_objects_target* t, ssm_object* out, int cap, int* n_out, int32_t* object_id)
+{
+    if (n_out) *n_out = (int)t->rec.size();
+    if (out && (int)t->rec.size() > cap) return SSM_E_CAPACITY;
+    if (out && !t->rec.empty()) memcpy(out, t->rec.data(), t->rec.size() * sizeof(ssm_object));
+    if (object_id && !t->oid.empty()) memcpy(object_id, t->oid.data(), t->oid.size() * 4);
     return SSM_OK;
 }
 // label fusion (Mapper with mapper_relabel=1): a "view" is a host copy of the depth image and the label image, the linked host function in the device entry points' place
