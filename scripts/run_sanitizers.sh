@@ -4,7 +4,7 @@
 # committed golden case files), test_threads (PoseGraph + Mapper::viewer + a polling thread; device calls -> san_stub_device.cpp), test_looper (rgbd_tutor::Looper on
 # its host path), test_uvd (UVDisparity on its host path), test_posegraph --graph-only (PoseGraph's graph bookkeeping + the pose-graph optimiser's host function).
 # test_orb_plan is the ORB planner (csrc/ssm_orb_plan.cpp) alone, swept over the configurations of the plan tests; test_track the bulk tracker's state machine
-# (csrc/ssm_track_host.cpp) alone, over hooks of the program's own; test_map_plan the voxel map's protocol (csrc/ssm_map_plan.cpp) alone.  The stages' host code is the library's own: csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
+# (csrc/ssm_track_host.cpp) alone, over hooks of the program's own; test_map_plan the voxel map's protocol (csrc/ssm_map_plan.cpp) alone, test_seq_plan the sequence calls' schedule (csrc/ssm_seq_plan.cpp) alone.  The stages' host code is the library's own: csrc/ssm_vocab.cpp, ssm_vocab_train_host.cpp,
 # ssm_uvd_host.cpp, ssm_pgo_host.cpp, ssm_motion_fuse_host.cpp and ssm_track_host.cpp are compiled with the sanitizer and linked beside the stub.
 # Every step's OWN exit status decides (no status of a `tail` / `grep` behind a pipe): a failed build, a missing binary, a non-zero exit or a sanitizer
 # report anywhere in the full, un-tailed output makes the run fail; the log keeps the complete output of failing steps and the tail of passing ones.
@@ -53,7 +53,7 @@ step() {
     step "oracle build + run ($s)" make -s -C "$ROOT/oracle" SAN=$s san
     echo "## host SAN=$s"
     step "host build ($s)" make -s -C "$HOST" SAN=$s san
-    for b in test_png_$s test_pnp_$s test_threads_$s test_looper_$s test_uvd_$s test_posegraph_$s test_orb_plan_$s test_map_plan_$s test_track_$s; do [ -x "$HOST/$b" ] || { echo "### $b: MISSING BINARY"; fail=1; }; done
+    for b in test_png_$s test_pnp_$s test_threads_$s test_looper_$s test_uvd_$s test_posegraph_$s test_orb_plan_$s test_map_plan_$s test_seq_plan_$s test_track_$s; do [ -x "$HOST/$b" ] || { echo "### $b: MISSING BINARY"; fail=1; }; done
     [ -x "$HOST/test_png_$s" ] && step "test_png_$s" "$HOST/test_png_$s" "$TMP/png"
     for c in outliers nodepth lanes; do
       [ -x "$HOST/test_pnp_$s" ] && step "test_pnp_$s $c" "$HOST/test_pnp_$s" "$HOST/parameters_test.txt" "$TMP/$c.bin" "$TMP/$c.out"
@@ -63,6 +63,7 @@ step() {
     [ -x "$HOST/test_posegraph_$s" ] && step "test_posegraph_$s" "$HOST/test_posegraph_$s" --graph-only "$HOST/parameters_test.txt"
     [ -x "$HOST/test_orb_plan_$s" ] && step "test_orb_plan_$s" "$HOST/test_orb_plan_$s"
     [ -x "$HOST/test_map_plan_$s" ] && step "test_map_plan_$s" "$HOST/test_map_plan_$s"
+    [ -x "$HOST/test_seq_plan_$s" ] && step "test_seq_plan_$s" "$HOST/test_seq_plan_$s"
     [ -x "$HOST/test_track_$s" ] && step "test_track_$s" "$HOST/test_track_$s"
     [ -x "$HOST/test_threads_$s" ] && step "test_threads_$s" "$HOST/test_threads_$s" "$HOST/parameters_test.txt"
   done

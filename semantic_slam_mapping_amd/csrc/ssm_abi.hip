@@ -266,15 +266,16 @@ int ensure_side_streams(ssm_ctx* c)
     c->side_ready = true;
     return SSM_OK;
 }
-int lanes_fork(ssm_ctx* c, std::initializer_list<Lane*> lanes)
+int lanes_fork(ssm_ctx* c, const LaneList& lanes)
 {
+    if (!lanes.n) return SSM_OK;
     HIPCHK(c, hipEventRecord(c->forked, c->main.stream));
-    for (Lane* l : lanes) if (l) HIPCHK(c, hipStreamWaitEvent(l->stream, c->forked, 0));
+    for (int i = 0; i < lanes.n; i++) HIPCHK(c, hipStreamWaitEvent(lane(c, lanes.lane[i]).stream, c->forked, 0));
     return SSM_OK;
 }
-int lanes_join(ssm_ctx* c, std::initializer_list<Lane*> lanes)
+int lanes_join(ssm_ctx* c, const LaneList& lanes)
 {
-    for (Lane* l : lanes) if (l) { HIPCHK(c, hipEventRecord(l->joined, l->stream)); HIPCHK(c, hipStreamWaitEvent(c->main.stream, l->joined, 0)); }
+    for (int i = 0; i < lanes.n; i++) { Lane& l = lane(c, lanes.lane[i]); HIPCHK(c, hipEventRecord(l.joined, l.stream)); HIPCHK(c, hipStreamWaitEvent(c->main.stream, l.joined, 0)); }
     return SSM_OK;
 }
 static int ensure_alt(ssm_ctx* c)          // the workspaces of chains 1, 2 of ssm_seq_process
@@ -826,6 +827,75 @@ static int ensure_seq(ssm_ctx* c, int n)
     c->d_desc_all = std::move(nd); c->d_nkp_all = std::move(nn); c->seq_cap = n;
     return SSM_OK;
 }
+// ORB -> expand -> (record, waits) -> match of one sub-batch on its chain's lane
+static int seq_front(ssm_ctx* c, const ssm_frames_dev* in, int stages, bool mfma, const SeqStep& st)
+{
+    const OrbGeom& g = c->g; const int R = c->R, f0 = st.f0, nb = st.nb;
+    const size_t npix = (size_t)g.W * g.H, row = (size_t)g.cap * 32;
+    uint8_t* desc = c->d_desc_all + (size_t)R * row; int32_t* nkp = c->d_nkp_all + R;
+    OrbChain& ch = c->chain[st.chain]; const hipStream_t cs = lane(c, st.lane).stream;
+    if (stages & SSM_STAGE_ORB) {
+        int r = run_orb(c, cs, ch.work, in->bgr + (size_t)f0 * npix * 3, 3, in->depth ? in->depth + (size_t)f0 * npix : nullptr, nb,
+                        c->d_kps + (size_t)f0 * g.cap, desc + (size_t)f0 * row, c->d_pos3d + (size_t)f0 * g.cap * 3, nkp + f0);
+        if (r) return r;
+        if (mfma) { prof_begin(c, cs, "match"); HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs)); prof_end(c, cs); }
+        if (st.record_orb_done) {
+            HIPCHK(c, hipEventRecord(ch.orb_done, cs));
+            for (int k = 0; k < st.nwait; k++) HIPCHK(c, hipStreamWaitEvent(cs, c->chain[st.wait_chain[k]].orb_done, 0));
+        }
+    }
+    if (stages & SSM_STAGE_MATCH) {
+        prof_begin(c, cs, "match");
+        if (mfma) {
+            if (!(stages & SSM_STAGE_ORB)) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs));
+            HIPCHK(c, k_match_seq_mfma(c->d_exp_q, c->d_exp_t, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->capT, match_key_exp(c->capT), c->d_knn, c->d_matches, c->d_nmatch, cs));
+        } else
+            HIPCHK(c, k_match_seq(c->d_desc_all, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->d_matches, c->d_nmatch, c->d_match_pend + (size_t)f0 * R, cs));
+        prof_end(c, cs);
+    }
+    return SSM_OK;
+}
+// (SegNet ->) map of one sub-batch on its map lane
+static int seq_back(ssm_ctx* c, const ssm_frames_dev* in, int stages, const SeqStep& st)
+{
+    if (st.map_lane == LANE_NONE) return SSM_OK;
+    const OrbGeom& g = c->g; const int W = g.W, H = g.H, f0 = st.f0, nb = st.nb; const size_t npix = (size_t)W * H;
+    Lane& ml = lane(c, st.map_lane); const hipStream_t s = ml.stream; int r;
+    const uint8_t* sem_src = in->sem_bgr ? in->sem_bgr + (size_t)f0 * npix * 3 : nullptr;
+    if (stages & SSM_STAGE_SEGNET) {          // Classifier in the loop (the variant commented out at src/rgbdframe.cpp:119-136)
+        r = seg_init(c); if (r) return r;
+        prof_begin(c, s, "segnet");
+        r = seg_forward_dev(c, ml, in->bgr + (size_t)f0 * npix * 3, nb, nullptr, c->seg->d_sem_gen, 0); if (r) return r;
+        prof_end(c, s);
+        sem_src = c->seg->d_sem_gen;
+    }
+    // The map of a context grows (map_settle): a launch covers all nb frames when the table is large, fewer while it is small, and the table's counters
+    // are looked at between launches (map_before_launch).  Exact integer sums: how the frames are cut into launches does not change the map.
+    for (int q0 = 0, nq; (stages & SSM_STAGE_MAP) && q0 < nb; q0 += nq) {
+        r = map_before_launch(c, s, nb - q0, &nq); if (r) return r;
+        const int g0 = f0 + q0;
+        const uint8_t* sem_q = sem_src + (size_t)q0 * npix * 3;
+        if ((W & 15) == 0) {         // streaming fused kernels (16 pixels per thread, 16-byte loads)
+            prof_begin(c, s, "map_fuse");
+            { MapLaunch L; L.depth = in->depth + (size_t)g0 * npix; L.rgb = in->bgr + (size_t)g0 * npix * 3; L.sem = sem_q; L.pose = in->pose ? in->pose + (size_t)g0 * 16 : nullptr;
+              L.n = nq; L.w = W; L.h = H; L.npoints = c->d_npoints + g0;
+              r = map_fuse_launch(c, s, L); if (r) return r; }
+            prof_end(c, s);
+        } else {                     // odd widths: mask -> ordered back-projection -> insert
+            prof_begin(c, s, "mask");
+            HIPCHK(c, k_moving_mask(sem_q, nq, W, H, c->d_mask, s)); prof_end(c, s);
+            prof_begin(c, s, "backproject");
+            HIPCHK(c, k_backproject(in->depth + (size_t)g0 * npix, in->bgr + (size_t)g0 * npix * 3, sem_q, c->d_mask,
+                                    in->pose ? in->pose + (size_t)g0 * 16 : nullptr, nq, W, H, c->cfg.camera, c->cfg.mapper_max_distance,
+                                    c->d_chunk_cnt, c->d_chunk_off, c->d_npoints + g0, c->d_total, c->d_points, s)); prof_end(c, s);
+            prof_begin(c, s, "voxel_insert");
+            HIPCHK(c, k_voxel_insert(c->d_points, c->d_total, (int64_t)nq * (int64_t)npix, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, s));
+            prof_end(c, s);
+        }
+        r = map_after_launch(c, s, nq, (stages & SSM_STAGE_SEGNET) != 0 && (W & 15) == 0); if (r) return r;
+    }
+    return SSM_OK;
+}
 extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out_dev* out)
 {
     if (!c) return SSM_E_INVAL;
@@ -834,8 +904,7 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     const int stages = in->stages ? in->stages : (SSM_STAGE_ORB | SSM_STAGE_MATCH | SSM_STAGE_MAP);
     if ((stages & (SSM_STAGE_ORB | SSM_STAGE_MATCH)) && !in->bgr) FAIL(c, SSM_E_INVAL, "bgr is required");
     if ((stages & SSM_STAGE_MAP) && (!in->depth || !in->bgr || (!in->sem_bgr && !(stages & SSM_STAGE_SEGNET)))) FAIL(c, SSM_E_INVAL, "bgr, depth and sem_bgr (or SSM_STAGE_SEGNET) are required for the map stage");
-    const OrbGeom& g = c->g; const int R = c->R, n = in->n, W = g.W, H = g.H; const hipStream_t s = c->main.stream;
-    const size_t npix = (size_t)W * H;
+    const OrbGeom& g = c->g; const int R = c->R, n = in->n; const hipStream_t s = c->main.stream;
     // fused map launches of an earlier call that nobody has looked at since (no ssm_sync / map read in between): their skipped blocks -- if any -- are run again NOW,
     // while the launch descriptors still point at that call's outputs (ensure_seq below may re-allocate the per-frame point counts)
     if (c->gov.unexamined) { const int r0 = map_settle(c, c->mapdev.tail ? c->mapdev.tail : c->main.stream, 0); if (r0) return r0; }
@@ -852,108 +921,23 @@ extern "C" int ssm_seq_process(ssm_ctx* c, const ssm_frames_dev* in, ssm_seq_out
     } else {
         HIPCHK(c, hipMemsetAsync(c->d_nkp_all, 0xFF, (size_t)R * 4, s));     // -1: no such reference frame
     }
-    uint8_t* desc = c->d_desc_all + (size_t)R * row; int32_t* nkp = c->d_nkp_all + R;
     const bool mfma = c->match_mfma && (stages & SSM_STAGE_MATCH) && match_key_fits(c->capT);
     if (mfma) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, 0, R, g.cap, c->capT, c->d_exp_q, c->d_exp_t, s));      // the history rows
-    // Two streams: the ORB -> match chain of a sub-batch and its (SegNet ->) map stage share no data, only the inputs, so the
-    // map side runs on side[0].  The chain's latency-bound kernels (pyramid, octree, describe) then overlap VALU/MFMA-bound
-    // map / SegNet work.  side[0] starts behind everything already queued on the context stream and is joined at the end.
-    const bool side_work = (stages & (SSM_STAGE_MAP | SSM_STAGE_SEGNET)) != 0;
-    // Two chains: without the SegNet stage (one activation workspace) and with two or more sub-batches, alternate sub-batches run
-    // their whole ORB -> match -> map chain on the context stream and on side[0] (and side[2], from three sub-batches on) with an OrbWork each, so that one chain's
-    // latency-bound kernels (quad-tree, pyramid launches, block tails) overlap the other chain's VALU-bound ones.  The only
-    // dependence between neighbours is the matcher's: the reference descriptors of sub-batch b - 1 (an event per chain).
-    const bool two_chains = !c->serialize && !(stages & SSM_STAGE_SEGNET) && n > c->B && (stages & SSM_STAGE_ORB) && (W & 15) == 0;
-    const bool side = side_work && !c->serialize && !two_chains;
-    if (side || two_chains) { r = ensure_side_streams(c); if (r) return r; }
-    if (two_chains) { r = ensure_alt(c); if (r) return r; }
-    const int nch = two_chains ? (n > 2 * c->B ? 3 : 2) : 1;
-    const bool map3 = two_chains && c->mapdev.own_stream == 1;
-    Lane* const used[3] = {&c->side[0], nch == 3 ? &c->side[2] : nullptr, map3 ? &c->side[1] : nullptr};      // the side lanes of this call, in fork / join order
-    if (side || two_chains) { r = lanes_fork(c, {used[0], used[1], used[2]}); if (r) return r; }
-    int bi = 0;
-    for (int f0 = 0; f0 < n; f0 += c->B, bi++) {
-        const int nb = (n - f0 < c->B) ? n - f0 : c->B;
-        const int chain = bi % nch;
-        OrbChain& ch = c->chain[chain]; const hipStream_t cs = ch.lane->stream; OrbWork& work = ch.work;      // this chain's stream and ORB workspace
-        auto front = [&]() -> int {                                       // ORB -> match of this sub-batch
-            if (stages & SSM_STAGE_ORB) {
-                r = run_orb(c, cs, work, in->bgr + (size_t)f0 * npix * 3, 3, in->depth ? in->depth + (size_t)f0 * npix : nullptr, nb,
-                            c->d_kps + (size_t)f0 * g.cap, desc + (size_t)f0 * row, c->d_pos3d + (size_t)f0 * g.cap * 3, nkp + f0);
-                if (r) return r;
-                if (mfma) { prof_begin(c, cs, "match"); HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs)); prof_end(c, cs); }
-                if (two_chains) {
-                    // The matcher of sub-batch bi reads the descriptor rows of the R preceding FRAMES, i.e. (max_batch < tracker_ref_frames) of several
-                    // preceding sub-batches.  Every other chain's newest event is the ORB + expand of one of bi-1 .. bi-(nch-1); an older sub-batch sits on
-                    // one of those streams (or on this one) in front of that record, so waiting on all of them orders the matcher behind every row it reads.
-                    HIPCHK(c, hipEventRecord(ch.orb_done, cs));
-                    for (int k = 1; k < nch && k <= bi; k++) HIPCHK(c, hipStreamWaitEvent(cs, c->chain[(bi - k) % nch].orb_done, 0));
-                }
-            }
-            if (stages & SSM_STAGE_MATCH) {
-                prof_begin(c, cs, "match");
-                if (mfma) {
-                    if (!(stages & SSM_STAGE_ORB)) HIPCHK(c, k_match_expand(c->d_desc_all, c->d_nkp_all, R + f0, nb, g.cap, c->capT, c->d_exp_q, c->d_exp_t, cs));
-                    HIPCHK(c, k_match_seq_mfma(c->d_exp_q, c->d_exp_t, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->capT, match_key_exp(c->capT), c->d_knn, c->d_matches, c->d_nmatch, cs));
-                } else
-                    HIPCHK(c, k_match_seq(c->d_desc_all, c->d_nkp_all, f0, nb, R, R, c->cfg.knn_match_ratio, g.cap, c->d_matches, c->d_nmatch, c->d_match_pend + (size_t)f0 * R, cs));
-                prof_end(c, cs);
-            }
-            return SSM_OK;
-        };
-        auto back = [&]() -> int {                                        // (SegNet ->) map of this sub-batch
-            if (!side_work) return SSM_OK;
-            Lane& ml = map3 ? c->side[1] : side ? c->side[0] : *ch.lane;      // the map lane, side[0] beside a single chain, or the chain's own lane
-            const hipStream_t s = ml.stream;
-            const uint8_t* sem_src = in->sem_bgr ? in->sem_bgr + (size_t)f0 * npix * 3 : nullptr;
-            if (stages & SSM_STAGE_SEGNET) {          // Classifier in the loop (the variant commented out at src/rgbdframe.cpp:119-136)
-                r = seg_init(c); if (r) return r;
-                prof_begin(c, s, "segnet");
-                r = seg_forward_dev(c, ml, in->bgr + (size_t)f0 * npix * 3, nb, nullptr, c->seg->d_sem_gen, 0); if (r) return r;
-                prof_end(c, s);
-                sem_src = c->seg->d_sem_gen;
-            }
-            // The map of a context grows (map_settle): a launch covers all nb frames when the table is large, fewer while it is small, and the table's counters
-            // are looked at between launches (map_before_launch).  Exact integer sums: how the frames are cut into launches does not change the map.
-            for (int q0 = 0, nq; (stages & SSM_STAGE_MAP) && q0 < nb; q0 += nq) {
-                r = map_before_launch(c, s, nb - q0, &nq); if (r) return r;
-                const int g0 = f0 + q0;
-                const uint8_t* sem_q = sem_src + (size_t)q0 * npix * 3;
-                if ((W & 15) == 0) {         // streaming fused kernels (16 pixels per thread, 16-byte loads)
-                    prof_begin(c, s, "map_fuse");
-                    { MapLaunch L; L.depth = in->depth + (size_t)g0 * npix; L.rgb = in->bgr + (size_t)g0 * npix * 3; L.sem = sem_q; L.pose = in->pose ? in->pose + (size_t)g0 * 16 : nullptr;
-                      L.n = nq; L.w = W; L.h = H; L.npoints = c->d_npoints + g0;
-                      r = map_fuse_launch(c, s, L); if (r) return r; }
-                    prof_end(c, s);
-                } else {                     // odd widths: mask -> ordered back-projection -> insert
-                    prof_begin(c, s, "mask");
-                    HIPCHK(c, k_moving_mask(sem_q, nq, W, H, c->d_mask, s)); prof_end(c, s);
-                    prof_begin(c, s, "backproject");
-                    HIPCHK(c, k_backproject(in->depth + (size_t)g0 * npix, in->bgr + (size_t)g0 * npix * 3, sem_q, c->d_mask,
-                                            in->pose ? in->pose + (size_t)g0 * 16 : nullptr, nq, W, H, c->cfg.camera, c->cfg.mapper_max_distance,
-                                            c->d_chunk_cnt, c->d_chunk_off, c->d_npoints + g0, c->d_total, c->d_points, s)); prof_end(c, s);
-                    prof_begin(c, s, "voxel_insert");
-                    HIPCHK(c, k_voxel_insert(c->d_points, c->d_total, (int64_t)nq * (int64_t)npix, (float)c->cfg.mapper_resolution, c->map.tab, c->map.cap_log2, c->map.counters, s));
-                    prof_end(c, s);
-                }
-                r = map_after_launch(c, s, nq, (stages & SSM_STAGE_SEGNET) != 0 && (W & 15) == 0); if (r) return r;
-            }
-            return SSM_OK;
-        };
-        // The map stage shares no data with the ORB -> match chain: in two-chain mode it runs on a third stream (all sub-batches in order, one workspace),
-        // so that the chains' latency-bound kernels (pyramid, quad-tree, orientation / BRIEF gathers) always have VALU-bound map work beside them
-        // (+4 % over map-after-match on the chain's own stream).  Chain 1 enqueues its map stage FIRST: with SSM_MAP_STREAM=0 (the map stage on the chain's
-        // own stream) that puts the two chains half a sub-batch out of step (+2.4 %)
-        const bool map_first = two_chains && chain == 1;
-        if (map_first) { r = back(); if (r) return r; r = front(); if (r) return r; }
-        else           { r = front(); if (r) return r; r = back(); if (r) return r; }
+    // who runs on which lane, in which order, behind which events: ssm_seq_plan.cpp.  The side lanes start behind everything already queued on the main lane
+    // and are joined into it at the end.
+    const SeqPlan plan = seq_plan({n, c->B, stages, c->serialize, (g.W & 15) == 0, c->mapdev.own_stream});
+    if (plan.needs_side_streams) { r = ensure_side_streams(c); if (r) return r; }
+    if (plan.needs_alt_work) { r = ensure_alt(c); if (r) return r; }
+    r = lanes_fork(c, plan.forked); if (r) return r;
+    for (const SeqStep& st : plan.steps) {
+        if (st.map_first) { r = seq_back(c, in, stages, st); if (r) return r; r = seq_front(c, in, stages, mfma, st); if (r) return r; }
+        else              { r = seq_front(c, in, stages, mfma, st); if (r) return r; r = seq_back(c, in, stages, st); if (r) return r; }
     }
-    if (side || two_chains) { r = lanes_join(c, {used[0], used[1], used[2]}); if (r) return r; }
-    // where the map's newest work sits (MapDev::tail): one side stream, or the context stream (serialised, no map stage, or the chains' own streams in turn)
-    if (stages & SSM_STAGE_MAP) c->mapdev.tail = map3 ? (hipStream_t)c->side[1].stream : side ? (hipStream_t)c->side[0].stream : nullptr;
+    r = lanes_join(c, plan.forked); if (r) return r;
+    if (stages & SSM_STAGE_MAP) c->mapdev.tail = plan.map_tail == LANE_MAIN ? nullptr : (hipStream_t)lane(c, plan.map_tail).stream;      // MapDev::tail
     c->prev_n = n;
     if (out) {
-        out->kps = c->d_kps; out->desc = desc; out->pos3d = c->d_pos3d; out->nkp = nkp; out->matches = c->d_matches; out->nmatch = c->d_nmatch;
+        out->kps = c->d_kps; out->desc = c->d_desc_all + (size_t)R * row; out->pos3d = c->d_pos3d; out->nkp = c->d_nkp_all + R; out->matches = c->d_matches; out->nmatch = c->d_nmatch;
         out->npoints = c->d_npoints; out->cap = g.cap; out->R = R;
     }
     return SSM_OK;

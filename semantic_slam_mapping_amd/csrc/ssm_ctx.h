@@ -4,6 +4,7 @@
 #include "ssm_internal.h"
 #include "pnp_chain.h"
 #include "ssm_map_plan.h"
+#include "ssm_seq_plan.h"
 #include <rccl/rccl.h>
 #include <cmath>
 #include <cfloat>
@@ -252,18 +253,16 @@ struct SorWork {
     DevBuf<uint32_t> idx_a, idx_b, query, block_cnt, block_off; DevBuf<float4> sorted; DevBuf<uint8_t> tmp; size_t tmp_bytes = 0;
     DevBuf<ssm_point> in, out;      // the host-array call's staging; out also holds ssm_cloud_sor's kept points before they go back into the cloud
 };
-// one ORB -> match chain of ssm_seq_process: the lane it runs on, its workspace, and the event behind its newest ORB + expand (what the next sub-batch's matcher waits for)
-struct OrbChain { Lane* lane; OrbWork work; Event orb_done; };
+// one ORB -> match chain of ssm_seq_process: its workspace, and the event behind its newest ORB + expand (what later sub-batches' matchers wait for)
+struct OrbChain { OrbWork work; Event orb_done; };
 
 struct ssm_ctx {
     std::mutex mu;
     int device = 0;
     DeviceInfo dev;                     // CU count and LDS limit of `device`, asked once (ctx_init): what the launchers size grids and dynamic LDS from
-    // main: the context's stream, created in ctx_init and never re-pointed; every per-call entry point runs here, and chain 0 of ssm_seq_process.
-    // side[]: created at first use (ensure_side_streams), forked from and joined into main by every call that uses them (lanes_fork / lanes_join):
-    //   side[0]  ssm_seq_process: chain 1; with a single chain, the SegNet + map stage of a sub-batch runs here beside it.  Stereo: SGBM (first workspace)
-    //   side[1]  two-chain mode: the map stage on a stream of its own (SSM_MAP_STREAM=0: on the chain's stream).  Stereo: SGBM, second workspace
-    //   side[2]  the third chain, used when a call has more than two sub-batches.  Stereo: SGBM, third workspace
+    // main: the context's stream, created in ctx_init and never re-pointed; every per-call entry point runs here.
+    // side[]: created at first use (ensure_side_streams), forked from and joined into main by every call that uses them (lanes_fork / lanes_join).  Who runs
+    // on which: ssm_seq_plan.h SeqLane.
     Lane main, side[3]; Event forked; bool side_ready = false /* ensure_side_streams completed */;
     ssm_config cfg{};
     OrbPlan plan;                       // what cfg fixes of the ORB front end (ssm_orb_plan.h), built by ssm_create; ctx_init uploads its tables
@@ -281,8 +280,8 @@ struct ssm_ctx {
     PyrBandPlan pyr_bands, pyr_bands1;       // resize4_kernel_bands for batches / for the per-frame call (bands == 0: gray_kernel + k_pyramid)
     DevBuf<int32_t> d_band_tab, d_band_tab1; // their band tables (PyrBandPlan::d_tab points here)
     // the ORB -> match chains (a workspace of B frames each): chain[0] serves every entry point that runs on the main lane; ssm_seq_process runs successive
-    // sub-batches on up to three chains, each on its own lane; the workspaces of chains 1, 2 are allocated at first use
-    OrbChain chain[3] = {{&main}, {&side[0]}, {&side[2]}};
+    // sub-batches on up to three chains, each on its own lane (ssm_seq_plan.h); the workspaces of chains 1, 2 are allocated at first use
+    OrbChain chain[3];
     DevBuf<int32_t> d_status;           // the ORB scratch-overflow word: one, shared by all chains
     DevBuf<uint8_t> d_mask; DevBuf<int32_t> d_chunk_cnt; DevBuf<int64_t> d_chunk_off, d_total;
     DevBuf<ssm_point> d_points;
@@ -335,6 +334,8 @@ struct ssm_ctx {
     std::vector<std::string> stage_names; std::vector<float> stage_ms; std::vector<int> stage_launches;
 };
 
+inline Lane& lane(ssm_ctx* c, SeqLane l) { return l == LANE_MAIN ? c->main : c->side[l - LANE_SIDE0]; }
+
 #define FAIL(ctx, code, msg) do { (ctx)->err = (msg); return (code); } while (0)
 #define HIPCHK(ctx, expr) do { hipError_t e__ = (expr); if (e__ != hipSuccess) { (ctx)->err = std::string(#expr) + ": " + hipGetErrorString(e__); return SSM_E_HIP; } } while (0)
 
@@ -367,9 +368,9 @@ SSM_HIDDEN int check_device_flags(ssm_ctx* c, bool with_map);
 SSM_HIDDEN int wait_pending(ssm_ctx* c);
 SSM_HIDDEN bool host_is_pinned(const void* p);             // page-locked host memory (ssm_host_alloc, hipHostRegister)?
 SSM_HIDDEN int ensure_side_streams(ssm_ctx* c);
-// fork: the listed side lanes wait for everything queued on the main stream so far; join: the main stream waits for everything queued on them.  Null entries are skipped.
-SSM_HIDDEN int lanes_fork(ssm_ctx* c, std::initializer_list<Lane*> lanes);
-SSM_HIDDEN int lanes_join(ssm_ctx* c, std::initializer_list<Lane*> lanes);
+// fork: the listed side lanes wait for everything queued on the main stream so far; join: the main stream waits for everything queued on them
+SSM_HIDDEN int lanes_fork(ssm_ctx* c, const LaneList& lanes);
+SSM_HIDDEN int lanes_join(ssm_ctx* c, const LaneList& lanes);
 // ssm_map.hip
 SSM_HIDDEN int table_alloc(ssm_ctx* c, hipStream_t s, VoxTable& t, int cap_log2, const VoxTable* lists = nullptr);      // lists: the table whose overflow list the counter block names (default: t's own)
 SSM_HIDDEN int map_settle(ssm_ctx* c, hipStream_t s, int64_t reserve, int32_t* counters_out = nullptr);

@@ -104,17 +104,12 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
     const size_t np = (size_t)w * h;
     const QuadBatch& qb = q->qb;
     const hipStream_t sq = c->main.stream;
-    // the quad matcher + VO chain (many small latency-bound kernels) and SGBM (volume kernels) of a sub-batch share nothing but the input images:
-    // SGBM runs on the first side lane beside the chain; sub-batches follow each other on both streams without a join in between
-    const bool two = (stages & SSM_STEREO_DEPTH) && (stages & SSM_STEREO_QUAD) && !c->serialize;
-    if (two) { r = ensure_side_streams(c); if (r) return r; }
-    // ... and with more than one sub-batch SGBM alternates between TWO (sgbm_streams: up to three) lanes with a workspace each: the cost kernel and the small
-    // kernels of one sub-batch (LDS / latency-bound) run beside the scan-direction and winner-takes-all kernels of the other (HBM-bound)
-    const int nsub = (n + B - 1) / B;
-    const int nsg = two ? (c->stereo_sgbm_streams < nsub ? c->stereo_sgbm_streams : nsub) : 1;
-    Lane* const sgl[3] = {two ? &c->side[0] : &c->main, nsg > 1 ? &c->side[1] : nullptr, nsg > 2 ? &c->side[2] : nullptr};      // SGBM's lanes
+    // SGBM beside the quad matcher + VO chain, alternating between lanes with a workspace each: ssm_seq_plan.cpp
+    const StereoPlan plan = stereo_plan(n, B, stages, c->serialize, c->stereo_sgbm_streams);
+    const int nsg = plan.nsg;
+    if (plan.two) { r = ensure_side_streams(c); if (r) return r; }
     for (int k = 1; k < nsg; k++) { r = stereo_ensure_sgbm(c, in->sgbm, B, k); if (r) return r; }
-    if (two) { r = lanes_fork(c, {sgl[0], sgl[1], sgl[2]}); if (r) return r; }
+    r = lanes_fork(c, plan.forked); if (r) return r;
     prof_reset(c);
     const bool prev0 = in->continue_sequence && q->have_prev;
     if (stages & SSM_STEREO_VO) HIPCHK(c, hipMemsetAsync(q->consumed, 0, 4, sq));
@@ -148,8 +143,8 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
             prof_end(c, sq);
         }
         if (stages & SSM_STEREO_DEPTH) {
-            const int alt = (f0 / B) % nsg;
-            Lane& sl = *sgl[alt]; const hipStream_t sg = sl.stream;
+            const int alt = plan.work(f0 / B);
+            Lane& sl = lane(c, plan.lane(f0 / B)); const hipStream_t sg = sl.stream;
             prof_begin(c, sg, "sgbm");                                  // (the stage events on SGBM's stream)
             HIPCHK(c, k_sgbm(in->left + (size_t)f0 * np, in->right + (size_t)f0 * np, w, h, nb, in->sgbm, q->sg_wsN[alt], q->sg_wsN[alt].bytes(), q->disp + (size_t)f0 * np, 0, c->dev, sl.sg, sg,
                              q->sg_fail + (f0 / B) % SG_FAIL_WORDS, c->sgbm_form_cfg, nsg));
@@ -157,7 +152,7 @@ static int stereo_seq_run(ssm_ctx* c, const ssm_stereo_frames_dev* in, ssm_stere
             prof_end(c, sg);
         }
     }
-    if (two) { r = lanes_join(c, {sgl[0], sgl[1], sgl[2]}); if (r) return r; }
+    r = lanes_join(c, plan.forked); if (r) return r;
     if (n > 0) q->have_prev = (stages & SSM_STEREO_QUAD) != 0;
     q->sg_pending.valid = (stages & SSM_STEREO_DEPTH) && n > 0;
     if (q->sg_pending.valid) { q->sg_pending.in = *in; q->sg_pending.B = B; }
