@@ -63,6 +63,15 @@
 // Pedestrian, Bike), _connectivity, _min_cells, _min_points, _min_height set the rule.  objectsInfo(), objectsFetch(records, object_id); with mapper_objects_dir
 // set the call writes objects.txt (one line per object: id, label name, cells, points, the box and the centroid in metres of the grid frame, ground and top
 // height) and objects_id.png (16 bit, id + 1, 0 where there is no object; row r is cell row ny - 1 - r as in the grid's images).
+// mapper_clearance=1 (default 0: nothing of this runs, every cloud, map, grid, object and figure exactly as before): the clearance map (the
+// reference has no such step).  In buildGrid, after the grid (and after the objects when both are on), on the same grid target, mapClearance gives every cell the
+// squared distance to the nearest blocked cell and marks the free cells a vehicle of mapper_clearance_radius (1.0 m) can occupy and those of them connected to
+// the seed (ssm_clearance_grid).  The grid is built for it even with mapper_grid=0; then no grid files are written.  mapper_clearance_blocked and
+// mapper_clearance_free (lists of cell classes, default `4` and `1`), _connectivity (4), _seed_snap (10 cells) set the rule.  The seed is the cell of the last
+// key-frame's camera centre at its map pose, through the grid's G and ssm_clrc::cell_of; a centre outside the grid means no seed.  clearanceInfo(),
+// clearanceFetch(dist2, nearest, reach); with mapper_clearance_dir set the call writes clearance.png (16 bit: min(65535, floor(sqrt(dist2) cell 100)) centimetres,
+// 65535 where nothing is blocked), reach.png (8 bit: 0 / 128 / 255) and clearance.txt (the info, one `name value` per line); image row r is cell row ny - 1 - r as
+// in the grid's images.
 // mapper_relabel=1 (default 0: nothing of this runs, every cloud, map and figure exactly as before): label fusion (the reference has no such step).
 // When the viewer ends -- after the last alignCarveUpTo, before the rendering and the ground grid, which then see the fused labels -- relabelAll lets the key-frames
 // j != i with |i - j| <= mapper_relabel_window (5; at most 8: a call takes 16 views) vote on the labels of key-frame i's cloud, at the map poses (mapPoseOf), every
@@ -81,6 +90,7 @@
 #include "pose_graph.h"
 #include "rgbdframe.h"
 #include "png_io.h"
+#include "clearance_core.h"
 namespace rgbd_tutor {
 class Mapper {
 public:
@@ -149,7 +159,8 @@ public:
         grid_params.h_min = para.getData<double>("mapper_grid_h_min", grid_params.h_min);
         grid_params.h_max = para.getData<double>("mapper_grid_h_max", grid_params.h_max);
         objects = para.getData<int>("mapper_objects", 0) != 0;
-        if (grid || objects) {          // (the objects stand on a grid of the same frame, whether or not the grid itself is wanted)
+        clearance = para.getData<int>("mapper_clearance", 0) != 0;
+        if (grid || objects || clearance) {          // (the objects and the clearance map stand on a grid of the same frame, whether or not the grid itself is wanted)
             double up[3] = {0, -1, 0}, fw[3] = {0, 0, 1};
             auto three = [&](const char* key, double* v) {
                 auto it = para.data.find(key);
@@ -172,6 +183,18 @@ public:
                 istringstream ss(it->second); int l; objects_params.label_mask = 0;
                 while (ss >> l) { if (l < 0 || l > 11) throw std::runtime_error("Mapper: mapper_objects_labels takes label ids 0..11"); objects_params.label_mask |= 1u << l; }
             }
+        }
+        clearance_dir = para.getData<string>("mapper_clearance_dir", string(""));
+        ssm_clearance_params_default(&clearance_params);
+        clearance_params.radius = para.getData<double>("mapper_clearance_radius", clearance_params.radius);
+        clearance_params.connectivity = para.getData<int>("mapper_clearance_connectivity", clearance_params.connectivity);
+        clearance_params.seed_snap = para.getData<int>("mapper_clearance_seed_snap", clearance_params.seed_snap);
+        for (int which = 0; which < 2; which++) {
+            auto it = para.data.find(which ? "mapper_clearance_free" : "mapper_clearance_blocked");
+            if (it == para.data.end()) continue;
+            istringstream ss(it->second); int l; uint32_t mask = 0;
+            while (ss >> l) { if (l < 0 || l > 4) throw std::runtime_error("Mapper: mapper_clearance_blocked and mapper_clearance_free take cell classes 0..4"); mask |= 1u << l; }
+            (which ? clearance_params.free_mask : clearance_params.blocked_mask) = mask;
         }
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
@@ -202,7 +225,7 @@ public:
             if (!kfs.empty()) updateMap(kfs, true, map, t0);          // (without a key-frame there is no map to rebuild)
         }
         if (render) renderAll(keyframesNow());          // every key-frame is a view of the clouds around it, in their final state
-        if (grid || objects) buildGrid(keyframesNow()); // one ground grid of every key-frame's cloud, in its final state; and the objects that stand on it
+        if (grid || objects || clearance) buildGrid(keyframesNow()); // one ground grid of every key-frame's cloud, in its final state; the objects that stand on it; its clearance map
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
         }
@@ -515,6 +538,7 @@ public:
     typedef Owned<ssm_grid_target, ssm_grid_target_free> GridTarget;          // the device accumulators and outputs
     void buildGrid(const vector<RGBDFrame::Ptr>& kfs) {
         objectsState = ObjectsInfo(); objectRecords.clear(); objectIds.clear();
+        clearanceState = ClearanceInfo(); clearanceD2.clear(); clearanceNearest.clear(); clearanceReach.clear();
         gridState = GridInfo(); gridSpec = grid_params; gridSpec.nx = gridSpec.ny = 0;
         gridCls.clear(); gridGroundLabel.clear(); gridObstacleLabel.clear(); gridGroundQ.clear(); gridTopQ.clear(); gridN.clear(); gridNHigh.clear();
         if (kfs.empty()) { gridState.skipped = true; return; }
@@ -550,7 +574,8 @@ public:
                 "ssm_grid_fetch");
         gridSpec = P; gridState.counts = I; gridState.built = true;
         if (objects) extractObjects(d, target.t, L, P);
-        if ((grid || !objects) && !grid_dir.empty()) {          // (a grid built only for the objects writes no grid files)
+        if (clearance) mapClearance(d, target.t, P, mapPoseOf(kfs.back()));
+        if ((grid || !(objects || clearance)) && !grid_dir.empty()) {          // (a grid built only for the objects or the clearance map writes no grid files)
             cv::Mat col, hgt; col.create(P.ny, P.nx, CV_8UC3); hgt.create(P.ny, P.nx, CV_16UC1);
             ssm_grid_colours(gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), P.nx, P.ny, P.h_min, col.data, hgt.ptr<uint16_t>());
             ofstream txt(grid_dir + "/grid.txt");
@@ -602,6 +627,49 @@ public:
         }
     }
     bool extractsObjects() const { return objects; }
+    // the clearance map of the grid buildGrid has just built, on the same grid target; camera: the map pose of the last key-frame, whose centre is the seed
+    struct ClearanceInfo { bool built = false; int32_t seed_cx = -1, seed_cy = -1; ssm_clearance_info counts{}; };          // seed_cx, seed_cy: the camera's cell (-1, -1: outside the grid)
+    typedef Owned<ssm_clearance_target, ssm_clearance_target_free> ClearanceTarget;
+    void mapClearance(ssm::Device& d, ssm_grid_target* grid_target, const ssm_grid_params& P, const Eigen::Isometry3d& camera) {
+        ssm_clearance_params C = clearance_params;
+        double g[2];
+        for (int i = 0; i < 2; i++) g[i] = ((P.G[i * 4] * camera(0, 3) + P.G[i * 4 + 1] * camera(1, 3)) + P.G[i * 4 + 2] * camera(2, 3)) + P.G[i * 4 + 3];
+        if (!ssm_clrc::cell_of(P, g[0], g[1], &C.seed_cx, &C.seed_cy)) C.seed_cx = C.seed_cy = -1;
+        ClearanceTarget target(d.ctx());
+        d.check(ssm_clearance_target_create(d.ctx(), P.nx, P.ny, &target.t), "ssm_clearance_target_create");
+        ssm_clearance_info I{};
+        d.check(ssm_clearance_grid(d.ctx(), grid_target, &C, target.t, &I), "ssm_clearance_grid");
+        const size_t nc = (size_t)P.nx * P.ny;
+        clearanceD2.resize(nc); clearanceNearest.resize(nc); clearanceReach.resize(nc);
+        d.check(ssm_clearance_fetch(d.ctx(), target.t, clearanceD2.data(), clearanceNearest.data(), clearanceReach.data()), "ssm_clearance_fetch");
+        clearanceState.counts = I; clearanceState.seed_cx = C.seed_cx; clearanceState.seed_cy = C.seed_cy; clearanceState.built = true;
+        if (!clearance_dir.empty()) {
+            cv::Mat cm, rm; cm.create(P.ny, P.nx, CV_16UC1); rm.create(P.ny, P.nx, CV_8UC1);
+            for (int r = 0; r < P.ny; r++) for (int x = 0; x < P.nx; x++) {
+                const size_t i = (size_t)(P.ny - 1 - r) * P.nx + x;
+                const uint32_t d2 = clearanceD2[i];
+                const double v = d2 == UINT32_MAX ? 65535.0 : floor(sqrt((double)d2) * P.cell * 100.0);
+                cm.ptr<uint16_t>(r)[x] = (uint16_t)(v < 65535.0 ? v : 65535.0);
+                rm.ptr<uint8_t>(r)[x] = (uint8_t)(clearanceReach[i] == 2 ? 255 : clearanceReach[i] == 1 ? 128 : 0);
+            }
+            ofstream txt(clearance_dir + "/clearance.txt");
+            txt << "blocked " << I.blocked << "\nfree_cells " << I.free_cells << "\ntraversable " << I.traversable << "\ncomponents " << I.components << "\nreachable " << I.reachable
+                << "\nseed_cell " << I.seed_cell << "\nmax_d2_reachable " << I.max_d2_reachable << "\nr2 " << I.r2 << "\n";
+            txt.close();
+            if (!(txt && ssm::imwritePNG(clearance_dir + "/clearance.png", cm) && ssm::imwritePNG(clearance_dir + "/reach.png", rm)))
+                throw std::runtime_error("Mapper: cannot write the clearance map to " + clearance_dir);
+        }
+    }
+    bool mapsClearance() const { return clearance; }
+    // the last mapClearance (not while the viewer thread runs): what happened, the seed and the counts; the images of the grid gridParams() describes
+    const ClearanceInfo& clearanceInfo() const { return clearanceState; }
+    bool clearanceFetch(vector<uint32_t>* dist2, vector<int32_t>* nearest, vector<uint8_t>* reach) const {
+        if (!clearanceState.built) return false;
+        if (dist2) *dist2 = clearanceD2;
+        if (nearest) *nearest = clearanceNearest;
+        if (reach) *reach = clearanceReach;
+        return true;
+    }
     // the last extractObjects (not while the viewer thread runs): what happened and the counts; the records and the object_id image of the grid gridParams() describes
     const ObjectsInfo& objectsInfo() const { return objectsState; }
     bool objectsFetch(vector<ssm_object>* records, vector<int32_t>* object_id) const {
@@ -776,6 +844,8 @@ protected:
     std::unordered_map<const RGBDFrame*, ssm_render_compare_info> renderInfo;      // key-frame -> its view's comparison (viewer thread, or its owner once that has ended)
     bool relabel = false; int relabel_window = 5, relabelled = 0, relabelViewsAlive = 0; ssm_relabel_params relabel_params{}; bool relabel_hash = false; uint64_t relabelFnv = 0;
     std::unordered_map<const RGBDFrame*, ssm_relabel_info> relabelInfo;  // key-frame -> what the views did to its labels (viewer thread, or its owner once that has ended)
+    bool clearance = false; string clearance_dir; ssm_clearance_params clearance_params{}; ClearanceInfo clearanceState;
+    vector<uint32_t> clearanceD2; vector<int32_t> clearanceNearest; vector<uint8_t> clearanceReach;      // the last mapClearance's images
     bool objects = false; string objects_dir; ssm_objects_params objects_params{}; ObjectsInfo objectsState; vector<ssm_object> objectRecords; vector<int32_t> objectIds;
     bool grid = false; string grid_dir; ssm_grid_params grid_params{}, gridSpec{}; GridInfo gridState;
     vector<uint8_t> gridCls, gridGroundLabel, gridObstacleLabel; vector<int32_t> gridGroundQ, gridTopQ; vector<uint32_t> gridN, gridNHigh;      // the last build's arrays

@@ -688,6 +688,44 @@ int  ssm_debug_objects_point_ids(ssm_ctx* ctx, int32_t* out, int64_t n);
 int  ssm_debug_objects_tile_w(void);
 int  ssm_debug_objects_tile_h(void);
 
+/* ---- clearance map: obstacle distance and reachable free space of a built ground grid.  The reference has no such step; DESIGN.md s.22 is the contract,
+ * include/ssm/clearance_core.h the arithmetic shared by the device path and the host function (device == host byte for byte; integers only).
+ * Input: the class image cls of a grid (nx x ny, cell (cx, cy) at cy nx + cx; nx, ny <= 32768).  A cell is BLOCKED when bit cls of blocked_mask is set.
+ * dist2 (uint32) and nearest (int32) are the minimum over ALL blocked cells b of the key (d2(c, b) << 24) | index(b): dist2 the exact squared Euclidean distance
+ * in cells (0 on a blocked cell), nearest the index of the blocked cell that attains it, the lowest index among equals; no blocked cell at all: UINT32_MAX and -1.
+ * A cell is TRAVERSABLE when bit cls of free_mask is set and dist2 > r2 = floor((radius / cell)^2) (saturated at 2^31).  The SEED is the traversable cell with the
+ * smallest key (d2 to (seed_cx, seed_cy) << 24) | index among those with d2 <= seed_snap^2, or none.  reach (uint8): 2 in the seed's connected component of
+ * traversable cells (under `connectivity`), 1 on every other traversable cell, 0 elsewhere; without a seed every traversable cell is 1.
+ * SSM_E_INVAL: a null argument; mask bits above class 4; masks that overlap; connectivity other than 4 or 8; a negative or non-finite radius; a cell size that
+ * is not positive and finite; seed_snap outside 0 .. 1024; a seed outside the grid other than (-1, -1); a side above 32768 or more than 2^24 cells; a target
+ * smaller than the grid or of another context; a grid target never built. */
+typedef struct {
+    uint32_t blocked_mask, free_mask;        /* bits over the cell classes 0 .. 4 */
+    int32_t connectivity, seed_cx, seed_cy, seed_snap;
+    double radius;                           /* metres */
+    double cell;                             /* metres per cell of a hand-made class image (ssm_clearance_cells_host, ssm_debug_clearance_cells); ssm_clearance_grid takes the grid's */
+} ssm_clearance_params;
+typedef struct { int64_t blocked, free_cells, traversable, components, reachable, seed_cell, max_d2_reachable, r2; } ssm_clearance_info;
+typedef struct ssm_clearance_target ssm_clearance_target;
+/* blocked_mask: OBSTACLE (bit 4); free_mask: DRIVABLE (bit 1); radius 1.0 m; connectivity 4; no seed (-1, -1); seed_snap 10; cell 1.0 */
+void ssm_clearance_params_default(ssm_clearance_params* p);
+/* device arrays for grids of up to nx ny cells, reused across calls */
+int  ssm_clearance_target_create(ssm_ctx* ctx, int nx, int ny, ssm_clearance_target** target_out);
+void ssm_clearance_target_free(ssm_ctx* ctx, ssm_clearance_target* target);
+/* the stage on the grid target's last build; nothing is uploaded, one download (the info).  params NULL: the defaults; info may be NULL */
+int  ssm_clearance_grid(ssm_ctx* ctx, const ssm_grid_target* grid, const ssm_clearance_params* params, ssm_clearance_target* target, ssm_clearance_info* info);
+/* the images of the target's last call (nx ny entries each); each pointer may be NULL */
+int  ssm_clearance_fetch(ssm_ctx* ctx, const ssm_clearance_target* target, uint32_t* dist2, int32_t* nearest, uint8_t* reach);
+/* the stage on the CPU, no GPU, the same bits: a column pass, then the lower envelope of every row's parabolas, then a flood fill.  Each output may be NULL */
+int  ssm_clearance_cells_host(const uint8_t* cls, int nx, int ny, const ssm_clearance_params* params, uint32_t* dist2, int32_t* nearest, uint8_t* reach, ssm_clearance_info* info);
+/* for the tests: a hand-made class image uploaded and the stage run on it */
+int  ssm_debug_clearance_cells(ssm_ctx* ctx, ssm_clearance_target* target, const uint8_t* cls, int nx, int ny, const ssm_clearance_params* params, ssm_clearance_info* info);
+/* the row pass of the context's later calls: 0 the whole row staged through LDS in chunks, 1 an outward scan that stops at the best distance, -1 the default; the
+ * same bits either way */
+int  ssm_debug_clearance_form(ssm_ctx* ctx, int form);
+/* the staging width of row-pass form 0, for the tests */
+int  ssm_debug_clearance_chunk(void);
+
 /* ---- label fusion: the key-frames around a cloud (the views: depth image, label image, camera, world pose) vote on the label of each of its points, and a point
  * takes the label its views agree on.  The reference has no such step; DESIGN.md s.20 is the contract, include/ssm/relabel_core.h the arithmetic shared by the
  * device path and the host function (device == host bit for bit).  A view votes for a point with the label at the point's pixel when carving's verdict (s.16) is

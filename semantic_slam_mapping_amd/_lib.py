@@ -135,6 +135,15 @@ class ObjectsInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("member_cells", "components", "kept", "rejected_cells", "rejected_points", "rejected_height", "n_in", "object_points")]
 
 
+class ClearanceParams(C.Structure):
+    _fields_ = [("blocked_mask", C.c_uint32), ("free_mask", C.c_uint32), ("connectivity", C.c_int32), ("seed_cx", C.c_int32), ("seed_cy", C.c_int32), ("seed_snap", C.c_int32),
+                ("radius", C.c_double), ("cell", C.c_double)]
+
+
+class ClearanceInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("blocked", "free_cells", "traversable", "components", "reachable", "seed_cell", "max_d2_reachable", "r2")]
+
+
 class GridInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_in", "n_finite", "out_of_band", "outside", "n_used", "unobserved", "drivable", "walkable", "other_ground", "obstacle")]
 
@@ -319,6 +328,15 @@ SYMBOLS = {
     "ssm_debug_objects_point_ids": (_I, [_P, _P, C.c_int64]),
     "ssm_debug_objects_tile_w": (_I, []),
     "ssm_debug_objects_tile_h": (_I, []),
+    "ssm_clearance_params_default": (None, [C.POINTER(ClearanceParams)]),
+    "ssm_clearance_target_create": (_I, [_P, _I, _I, C.POINTER(_P)]),
+    "ssm_clearance_target_free": (None, [_P, _P]),
+    "ssm_clearance_grid": (_I, [_P, _P, C.POINTER(ClearanceParams), _P, C.POINTER(ClearanceInfo)]),
+    "ssm_clearance_fetch": (_I, [_P, _P, _P, _P, _P]),
+    "ssm_clearance_cells_host": (_I, [_P, _I, _I, C.POINTER(ClearanceParams), _P, _P, _P, C.POINTER(ClearanceInfo)]),
+    "ssm_debug_clearance_cells": (_I, [_P, _P, _P, _I, _I, C.POINTER(ClearanceParams), C.POINTER(ClearanceInfo)]),
+    "ssm_debug_clearance_form": (_I, [_P, _I]),
+    "ssm_debug_clearance_chunk": (_I, []),
     "ssm_relabel_params_default": (None, [C.POINTER(RelabelParams)]),
     "ssm_relabel_view_create": (_I, [_P, _P, _P, _I, _I, C.POINTER(Camera), C.POINTER(_P)]),
     "ssm_relabel_view_free": (None, [_P, _P]),

@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, ObjectsParams, ObjectsInfo, RelabelParams, RelabelInfo, RelabelHostView
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, ObjectsParams, ObjectsInfo, ClearanceParams, ClearanceInfo, RelabelParams, RelabelInfo, RelabelHostView
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -415,6 +415,54 @@ def objects_host(clouds, T_clouds, grid=None, cap=None, **params):
     if rc != 0:
         raise SsmError(rc, lib.ssm_last_error(None).decode())
     return out[:k.value].copy(), oid, ids[:int(n[:m].sum())].copy(), _objects_info(I)
+
+
+CLEARANCE_INFO_FIELDS = ("blocked", "free_cells", "traversable", "components", "reachable", "seed_cell", "max_d2_reachable", "r2")
+CLEARANCE_FIELDS = ("blocked_mask", "free_mask", "connectivity", "seed_cx", "seed_cy", "seed_snap", "radius", "cell")
+
+
+def clearance_params(**kw):
+    """the clearance map's parameters (ssm_clearance_params): the library's defaults (ssm_clearance_params_default) with the given fields replaced; blocked=[ids] and
+    free=[ids] set the masks from lists of cell classes, seed=(cx, cy) the seed cell"""
+    bad = set(kw) - set(CLEARANCE_FIELDS) - {"blocked", "free", "seed"}
+    if bad:
+        raise TypeError("unknown clearance parameters: " + ", ".join(sorted(bad)))
+    P = ClearanceParams()
+    _lib.load().ssm_clearance_params_default(C.byref(P))
+    for k, v in kw.items():
+        if k in ("blocked", "free"):
+            setattr(P, k + "_mask", sum({1 << int(c) for c in v if 0 <= int(c) < 32}))
+        elif k == "seed":
+            P.seed_cx, P.seed_cy = (-1, -1) if v is None else (int(v[0]), int(v[1]))
+        elif k in ("radius", "cell"):
+            setattr(P, k, float(v))
+        else:
+            setattr(P, k, int(v))
+    return P
+
+
+def _clearance_info(I):
+    return {k: getattr(I, k) for k in CLEARANCE_INFO_FIELDS}
+
+
+def _clearance_cls(cls):
+    a = np.ascontiguousarray(cls, np.uint8)
+    if a.ndim != 2:
+        raise ValueError("a ny x nx array of cell classes")
+    return a
+
+
+def clearance_cells_host(cls, **params):
+    """the clearance map on the CPU (ssm_clearance_cells_host, no GPU) from the ny x nx class image of a grid -> (dist2 uint32, nearest int32, reach uint8, info)"""
+    a = _clearance_cls(cls)
+    ny, nx = a.shape
+    P = clearance_params(**params); I = ClearanceInfo()
+    d2 = np.zeros((ny, nx), np.uint32); near = np.full((ny, nx), -2, np.int32); reach = np.full((ny, nx), 255, np.uint8)
+    lib = _lib.load()
+    rc = lib.ssm_clearance_cells_host(_ptr(a), nx, ny, C.byref(P), _ptr(d2), _ptr(near), _ptr(reach), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return d2, near, reach, _clearance_info(I)
 
 
 RELABEL_INFO_FIELDS = ("n_in", "n_supported", "n_voted", "n_changed", "n_filled", "pairs_supported", "pairs_voted")
@@ -1575,6 +1623,46 @@ class Context:
         ids = np.full(max(int(n), 1), -2, np.int32)
         self._chk(self.lib.ssm_debug_objects_point_ids(self.h, _ptr(ids), int(n)))
         return ids[:int(n)].copy()
+
+    def clearance_target(self, nx, ny):
+        """the device images and labels of the clearance map for grids of up to nx * ny cells (ssm_clearance_target_create) -> an opaque handle (clearance_target_free
+        it)"""
+        t = C.c_void_p()
+        self._chk(self.lib.ssm_clearance_target_create(self.h, int(nx), int(ny), C.byref(t)))
+        self._clearance_sizes = getattr(self, "_clearance_sizes", {})
+        self._clearance_sizes[t.value] = None
+        return t.value
+
+    def clearance_target_free(self, target):
+        self._clearance_sizes.pop(target, None)
+        self.lib.ssm_clearance_target_free(self.h, target)
+
+    def clearance_form(self, form):
+        """the row pass of later calls (ssm_debug_clearance_form): 0 the whole row staged through LDS, 1 an outward scan, -1 the default"""
+        self._chk(self.lib.ssm_debug_clearance_form(self.h, int(form)))
+
+    def clearance_grid(self, grid_target, target, **params):
+        """the clearance map of the grid target's last build (ssm_clearance_grid) -> info"""
+        P = clearance_params(**params); I = ClearanceInfo()
+        self._chk(self.lib.ssm_clearance_grid(self.h, grid_target, C.byref(P), target, C.byref(I)))
+        self._clearance_sizes[target] = self._grid_sizes[grid_target]
+        return _clearance_info(I)
+
+    def clearance_cells(self, target, cls, **params):
+        """a hand-made ny x nx class image uploaded and the stage run on it (ssm_debug_clearance_cells) -> info"""
+        a = _clearance_cls(cls)
+        ny, nx = a.shape
+        P = clearance_params(**params); I = ClearanceInfo()
+        self._chk(self.lib.ssm_debug_clearance_cells(self.h, target, _ptr(a), nx, ny, C.byref(P), C.byref(I)))
+        self._clearance_sizes[target] = (nx, ny)
+        return _clearance_info(I)
+
+    def clearance_fetch(self, target):
+        """the images of the target's last call (ssm_clearance_fetch) -> (dist2 uint32, nearest int32, reach uint8), ny x nx each"""
+        nx, ny = self._clearance_sizes[target]
+        d2 = np.zeros((ny, nx), np.uint32); near = np.full((ny, nx), -2, np.int32); reach = np.full((ny, nx), 255, np.uint8)
+        self._chk(self.lib.ssm_clearance_fetch(self.h, target, _ptr(d2), _ptr(near), _ptr(reach)))
+        return d2, near, reach
 
     def relabel_view(self, depth, sem_bgr, camera=None):
         """a view of label fusion: the depth image goes to the device and the label image is made there from the semantic BGR image (ssm_relabel_view_create) -> an

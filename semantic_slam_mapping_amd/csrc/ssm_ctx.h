@@ -218,6 +218,13 @@ struct ObjectsWork {
     DevBuf<int32_t> ids; int64_t ids_cap = 0, n_ids = -1;
     DevBuf<uint8_t> in_cls, in_label; DevBuf<int32_t> in_ground, in_top; DevBuf<uint32_t> in_high; int64_t in_cap = 0;
 };
+// a clearance target (ssm_clearance.hip): the column pass's masks and rows, the images and the labels for up to cap cells; staged: a call has run (nx, ny: its grid)
+struct ssm_clearance_target {
+    int64_t cap = 0; int nx = 0, ny = 0, device = 0; const ssm_ctx* owner = nullptr; bool staged = false;
+    DevBuf<uint32_t> mask, dist2; DevBuf<int32_t> row, nearest, labels; DevBuf<uint8_t> reach;
+};
+// workspace of the clearance map: the info (and the seed's key behind it), the staging of ssm_debug_clearance_cells
+struct ClearanceWork { DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; int form = CLEARANCE_FORM_DEFAULT; DevBuf<uint8_t> in_cls; int64_t in_cap = 0; };
 // a view of label fusion (ssm_relabel.hip): a key-frame's depth and label images in device memory and its camera; packed: depth | label << 16 per pixel, what
 // the vote gathers under the packed form (the default; the depth image is then freed once the view is made), empty under the other (ssm_debug_relabel_form)
 struct ssm_relabel_view { DevBuf<uint16_t> depth; DevBuf<uint8_t> label; DevBuf<uint32_t> packed; int w = 0, h = 0, device = 0; const ssm_ctx* owner = nullptr; ssm_camera cam{}; };
@@ -319,6 +326,7 @@ struct ssm_ctx {
     AlignWork align;                                         // dense alignment: likewise
     GridWork grid;                                           // ground grid: likewise
     ObjectsWork objects;                                     // object extraction: likewise
+    ClearanceWork clearance;                                 // clearance map: likewise
     RelabelWork relabel;                                     // label fusion: likewise
     CloudTableWork clouds;                                   // the cloud table and host-array staging of the three: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet

@@ -14,6 +14,7 @@
 #include "../../include/ssm/align_core.h"
 #include "../../include/ssm/grid_core.h"
 #include "../../include/ssm/objects_core.h"
+#include "../../include/ssm/clearance_core.h"
 #include "../../include/ssm/relabel_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
@@ -150,6 +151,10 @@ SSM_HIDDEN CloudRule grid_cloud_rule();            // no cloud twice; fewer than
 SSM_HIDDEN int objects_check(ssm_ctx* c, const ssm_objects_params& P, ssm_objc::Setup* S);
 SSM_HIDDEN int objects_extent_check(ssm_ctx* c, double x0, double y0, double cell, int nx, int ny);      // SSM_E_INVAL for a grid whose extent leaves +-2^20 m
 SSM_HIDDEN CloudRule objects_cloud_rule();         // no cloud twice; fewer than 2^31 points (the grid's bound)
+
+// ---------------------------------------------------------------- clearance map (ssm_clearance_host.cpp)
+// the grid's size and the parameters a call may have (host function and device entry points alike); cell: the grid's cell size; S: what they become for clearance_core.h
+SSM_HIDDEN int clearance_check(ssm_ctx* c, const ssm_clearance_params& P, int nx, int ny, double cell, ssm_clrc::Setup* S);
 
 // ---------------------------------------------------------------- label fusion (ssm_relabel_host.cpp)
 // the number of views and the parameters a call may have (host function and device entry points alike)

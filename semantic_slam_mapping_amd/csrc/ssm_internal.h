@@ -291,6 +291,17 @@ hipError_t k_objects_records(const ObjectsCells& G, const ssm_objc::Setup& S, co
 hipError_t k_objects_points(const ssm_gridc::Setup& G, const CloudSeg* seg, const int32_t* blk, int64_t total, const ssm_grid_cell* cells, const int32_t* object_id,
                             ssm_object* objs, int32_t K, int32_t* point_ids, unsigned long long* info, int form, hipStream_t s);
 
+// clearance map (kernels_clearance.hip; the arithmetic is include/ssm/clearance_core.h): k_clearance queues the whole stage on the class image cls of nx x ny cells --
+// the column pass (mask: k_clearance_mask_words(nx, ny) words; row: every cell's nearest blocked row of its column), the row pass in the given form (dist2, nearest),
+// the seed's snap, the labelling of the traversable cells (labels) and the finish (reach, the counts).  info: 9 x uint64, the eight counts of ssm_clearance_info and
+// the seed's key (k_clearance sets them).  Everything is queued on s, nothing waits.
+namespace ssm_clrc { struct Setup; }
+enum { CLEARANCE_FORM_LDS = 0, CLEARANCE_FORM_SCAN = 1, CLEARANCE_FORM_DEFAULT = CLEARANCE_FORM_LDS };
+struct ClearanceBufs { uint32_t* mask; int32_t* row; uint32_t* dist2; int32_t *nearest, *labels; uint8_t* reach; };
+int k_clearance_chunk();
+size_t k_clearance_mask_words(int nx, int ny);
+hipError_t k_clearance(const uint8_t* cls, int nx, int ny, const ssm_clrc::Setup& S, const ClearanceBufs& B, unsigned long long* info, int form, hipStream_t s);
+
 // label fusion (kernels_relabel.hip; the arithmetic is include/ssm/relabel_core.h): A.v views vote on the labels of the n points at pts, which change in place
 // (the 4 label bytes of a changed point).  votes, new_label: every point's record, n entries; info: 6 x uint64 (n_supported, n_voted, n_changed, n_filled,
 // pairs_supported, pairs_voted), cleared by the launcher.  form: RELABEL_FORM_IMAGES reads a view's depth and label images (View::depth, View::label),

@@ -40,6 +40,9 @@
 // `exp_mapping <parameters> --objects [DIR]` (or mapper_objects=1, mapper_objects_dir=DIR): right after the ground grid, Mapper extracts the labelled obstacle instances
 // that stand on it (include/ssm/mapper.h); with DIR objects.txt and objects_id.png are written there.  The summary line then carries
 // `objects_found K objects_cells C objects_points P objects_fnv H`: the objects, their cells, their points, and FNV-1a over nx, ny, the records and the object_id image.
+// `exp_mapping <parameters> --clearance [DIR]` (or mapper_clearance=1, mapper_clearance_dir=DIR): after the ground grid (and the objects), Mapper computes the grid's
+// clearance map (include/ssm/mapper.h); with DIR clearance.png, reach.png and clearance.txt are written there.  The summary line then carries, after
+// every other field, `clearance_blocked B clearance_traversable T clearance_reachable R clearance_max_d2 M clearance_fnv H`: H is FNV-1a over dist2, nearest and reach.
 // `exp_mapping <parameters> --grid [DIR]` (or mapper_grid=1, mapper_grid_dir=DIR): when the viewer ends, Mapper builds ONE ground grid from every key-frame's cloud at
 // its map pose (include/ssm/mapper.h); with DIR grid_colour.png, grid_height.png and grid.txt are written there.  The summary line then carries
 // `grid_cells C grid_drivable D grid_walkable W grid_obstacle O grid_fnv H`: the cells of the grid, three of its class counts, and FNV-1a over nx, ny and the fetched
@@ -175,6 +178,12 @@ int main(int argc, char** argv)
         if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_objects_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
     }
     if (objects) parameterReader.set("mapper_objects", "1");
+    bool clearance = parameterReader.getData<int>("mapper_clearance", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--clearance") {
+        clearance = true;
+        if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_clearance_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
+    }
+    if (clearance) parameterReader.set("mapper_clearance", "1");
     bool relabel = parameterReader.getData<int>("mapper_relabel", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--relabel") relabel = true;
     if (relabel) { parameterReader.set("mapper_relabel", "1"); parameterReader.set("mapper_relabel_hash", "1"); }
@@ -524,6 +533,17 @@ int main(int argc, char** argv)
             const string mo = parameterReader.getData<string>("map_output", string(""));
             const size_t slash = mo.find_last_of('/');
             poseGraph.save((slash == string::npos ? string("") : mo.substr(0, slash + 1)) + "traj.g2o");
+        }
+        if (clearance) {          // (the viewer thread mapped the clearance right after the grid as it ended; these fields come after every other)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before the clearance map was made" << endl; return 3; }
+            const Mapper::ClearanceInfo& K = mapper.clearanceInfo();
+            vector<uint32_t> d2; vector<int32_t> nearest; vector<uint8_t> reach;
+            mapper.clearanceFetch(&d2, &nearest, &reach);
+            uint64_t h = 0xCBF29CE484222325ull;           // FNV-1a over dist2, nearest and reach
+            auto eat = [&h](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; for (size_t k = 0; k < bytes; k++) { h ^= b[k]; h *= 0x100000001B3ull; } };
+            eat(d2.data(), d2.size() * 4); eat(nearest.data(), nearest.size() * 4); eat(reach.data(), reach.size());
+            cout << " clearance_blocked " << K.counts.blocked << " clearance_traversable " << K.counts.traversable << " clearance_reachable " << K.counts.reachable << " clearance_max_d2 "
+                 << K.counts.max_d2_reachable << " clearance_fnv " << hex << h << dec;
         }
         cout << endl;
     } catch (const exception& e) { cerr << RED << "exp_mapping: " << e.what() << RESET << endl; return 2; }

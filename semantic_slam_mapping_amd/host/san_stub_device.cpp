@@ -229,6 +229,35 @@ int ssm_objects_fetch(ssm_ctx*, const ssm_objects_target* t, ssm_object* out, in
     if (object_id && !t->oid.empty()) memcpy(object_id, t->oid.data(), t->oid.size() * 4);
     return SSM_OK;
 }
+// the clearance map (Mapper with mapper_clearance=1): a "target" is the host images, the linked host function in the device entry point's place (the cell size the
+// grid build's, as on the device)
+struct ssm_clearance_target { int64_t cap; int nx, ny; std::vector<uint32_t> d2; std::vector<int32_t> near; std::vector<uint8_t> reach; };
+int ssm_clearance_target_create(ssm_ctx*, int nx, int ny, ssm_clearance_target** out)
+{
+    if (!out || nx < 1 || ny < 1 || (int64_t)nx * ny > ((int64_t)1 << 24)) return SSM_E_INVAL;
+    ssm_clearance_target* t = new ssm_clearance_target(); t->cap = (int64_t)nx * ny; t->nx = t->ny = 0; *out = t; return SSM_OK;
+}
+void ssm_clearance_target_free(ssm_ctx*, ssm_clearance_target* t) { delete t; }
+int ssm_clearance_grid(ssm_ctx*, const ssm_grid_target* g, const ssm_clearance_params* params, ssm_clearance_target* t, ssm_clearance_info* info)
+{
+    if (!g || !t || g->nx < 1 || (int64_t)g->nx * g->ny > t->cap) return SSM_E_INVAL;
+    ssm_clearance_params P; ssm_clearance_params_default(&P); if (params) P = *params;
+    P.cell = g->P.cell;
+    const size_t nc = (size_t)g->nx * g->ny;
+    std::vector<uint32_t> d2(nc); std::vector<int32_t> near(nc); std::vector<uint8_t> reach(nc);
+    const int rc = ssm_clearance_cells_host(g->cls.data(), g->nx, g->ny, &P, d2.data(), near.data(), reach.data(), info);
+    if (rc == SSM_OK) { t->nx = g->nx; t->ny = g->ny; t->d2.swap(d2); t->near.swap(near); t->reach.swap(reach); }
+    return rc;
+}
+int ssm_clearance_fetch(ssm_ctx*, const ssm_clearance_target* t, uint32_t* dist2, int32_t* nearest, uint8_t* reach)
+{
+    if (!t || t->nx < 1) return SSM_E_INVAL;
+    const size_t nc = (size_t)t->nx * t->ny;
+    if (dist2) memcpy(dist2, t->d2.data(), nc * 4);
+    if (nearest) memcpy(nearest, t->near.data(), nc * 4);
+    if (reach) memcpy(reach, t->reach.data(), nc);
+    return SSM_OK;
+}
 // label fusion (Mapper with mapper_relabel=1): a "view" is a host copy of the depth image and the label image, the linked host function in the device entry points' place
 struct ssm_relabel_view { std::vector<uint16_t> depth; std::vector<uint8_t> label; int w, h; ssm_camera cam; };
 int ssm_relabel_view_create(ssm_ctx*, const uint16_t* depth, const uint8_t* sem, int w, int h, const ssm_camera* cam, ssm_relabel_view** out)
