@@ -974,6 +974,28 @@ int ssm_debug_orb_blur(ssm_ctx* ctx, const uint8_t* img, int channels, int n, ui
  * later ORB calls are not affected (they overwrite the selection). */
 int ssm_debug_orb_describe(ssm_ctx* ctx, const uint8_t* img, int channels, int n, const uint16_t* depth, const int32_t* nsel, const uint32_t* sel,
                            const int32_t* moments, int32_t* nkp, ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* moments_out, float* sincos_out);
+/* the quad-tree selection (ORBextractor::DistributeOctTree, one block per (frame, level)) ALONE on PLANTED candidate lists, for exact tests of its list order,
+ * its two split phases and its drop rule: the lists and the cell maxima of n frames are uploaded in place of FAST's, then the one launch the ORB calls make.
+ *   geom     may be NULL; else orb_levels x SSM_OCTREE_GEOM_LEVEL_INTS ints -- per level w, h, minBorder, nCols, nRows, wCell, hCell, features, root nodes, candidate
+ *            capacity, selection slots -- then cells_total, cand_total, sel_total (per frame) and the node capacity (256 / 512 / 1024) of the kernel instance that
+ *            runs.  With ncand, cand and cellmax all NULL only this is filled, and nothing is launched
+ *   ncand    n x orb_levels counts, each 0 .. the level's candidate capacity
+ *   cand     the candidates of all (frame, level) pairs, frame by frame and level by level, in the order they shall lie in the buffer: sum(ncand) pairs of words
+ *            x | y << 12 | score << 24 (x, y relative to minBorder, score = the FAST response) and cell << 14 | yInCell << 7 | xInCell (the rank word: detection
+ *            order).  With W = w - 2 * minBorder, H = h - 2 * minBorder: 3 <= x < W - 3, 3 <= y < H - 3; cell = ((y - 3) / hCell) * nCols + (x - 3) / wCell,
+ *            xInCell = x - ((x - 3) / wCell) * wCell, yInCell likewise: what the FAST kernel writes
+ *   cellmax  n x cells_total: per FAST cell the largest S = score + 1 among its kept maxima, 0 .. 255 (a candidate survives iff S > (cellmax > ini ? ini : min))
+ *   outputs  nsel: n x orb_levels; sel: n x sel_total words x | y << 12 | score << 24 in level coordinates, level l of frame f from f * sel_total + the sum of the
+ *            lower levels' slots on, in output order (slots the kernel did not write hold the bytes 0xA5); status: the ORB scratch-overflow word of this launch;
+ *            nodeof (may be NULL): n x cand_total, the kernel's global node-id scratch after the launch, laid out like the candidate buffer -- a level with more
+ *            than 2048 candidates keeps the node id of every candidate there (its final node, or 0xFFFF where the drop rule removed it), every other entry
+ *            still holds the bytes 0xA5
+ * SSM_E_INVAL, on the host and before anything is launched: n outside 1 .. max_batch, a count outside its range, a position outside its window, a cell id outside
+ * the level, a rank word that does not match its position, a cell maximum outside 0 .. 255.  The status word is zero again when the call returns, and the
+ * context's later ORB calls are not affected (they overwrite every buffer). */
+#define SSM_OCTREE_GEOM_LEVEL_INTS 11
+int ssm_debug_orb_octree(ssm_ctx* ctx, int n, const int32_t* ncand, const uint32_t* cand, const int32_t* cellmax, int32_t* geom, int32_t* nsel, uint32_t* sel,
+                         int32_t* status, uint16_t* nodeof);
 /* the FAST tile plan of a configuration, on the host only (no context, no device): for exact tests of the tiling.  Per tile, 16 ints:
  * level, interior x0, x1, y0, y1 (half-open), scored rectangle xs0, xs1, ys0, ys1 (interior + 1 on each side, clipped to the FAST window
  * [19, w - 19) x [19, h - 19)), 4-column groups, scored rows, cell columns and cell rows the scored rectangle touches, level w, h, stride.

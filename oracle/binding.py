@@ -50,6 +50,7 @@ class Oracle:
         L.sso_orb_level_image.argtypes = [P, I, I]
         L.sso_orb_level_candidates.argtypes = [P, I, P, I]
         L.sso_orb_features_per_level.argtypes = [P, I]
+        L.sso_distribute_octtree.argtypes = [P, I, I, I, I, I, I, P]
         L.sso_bgr2gray.argtypes = [P, I, I, I, P]
         L.sso_resize_linear_u8.argtypes = [P, I, I, P, I, I]
         L.sso_gaussian7.argtypes = [P, I, I, P]
@@ -148,6 +149,14 @@ class Oracle:
             return kps[:n].copy(), desc[:n].copy(), stages
         finally:
             self.L.sso_orb_destroy(o)
+
+    def distribute_octtree(self, cands, minX, maxX, minY, maxY, N):
+        """sso_distribute_octtree: the literal list code on (x, y, score) triples relative to (minX, minY), in detection order -> the indices of the selected
+        candidates, in output order"""
+        c = np.ascontiguousarray(cands, np.int32).reshape(-1, 3)
+        sel = np.zeros(max(len(c), 1), np.int32)
+        n = self.L.sso_distribute_octtree(c.ctypes.data, len(c), int(minX), int(maxX), int(minY), int(maxY), int(N), sel.ctypes.data)
+        return sel[:n].copy()
 
     def fast_atan2(self, y, x):
         """sso_fast_atan2 (degrees, float32) of float32 y, x"""

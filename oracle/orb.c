@@ -442,6 +442,20 @@ static int distribute_octtree(const cand_t* c, int nc, int minX, int maxX, int m
     return ns;
 }
 
+/* the list code above on a caller's candidates, for tests of the selection alone: xys = nc (x, y, score) triples relative to (minX, minY), in detection order;
+ * sel_out (room for nc) = the indices of the selected candidates in lNodes order.  Returns their number */
+int sso_distribute_octtree(const int32_t* xys, int nc, int minX, int maxX, int minY, int maxY, int N, int32_t* sel_out)
+{
+    if (nc <= 0) return 0;
+    cand_t* c = (cand_t*)malloc(sizeof(cand_t) * nc);
+    for (int i = 0; i < nc; i++) { c[i].x = (int16_t)xys[3*i]; c[i].y = (int16_t)xys[3*i+1]; c[i].score = xys[3*i+2]; c[i].rank = i; }
+    int* s = (int*)malloc(sizeof(int) * ((size_t)nc + 4));
+    const int ns = distribute_octtree(c, nc, minX, maxX, minY, maxY, N, s);
+    for (int i = 0; i < ns; i++) sel_out[i] = s[i];
+    free(s); free(c);
+    return ns;
+}
+
 /* ---------------- K5: IC_Angle + steered BRIEF ---------------- */
 static float ic_angle(const sso_orb* o, const uint8_t* im, int step, int x, int y)
 {

@@ -60,6 +60,9 @@ int      sso_orb_extract(sso_orb*, const uint8_t* gray, int w, int h, int stride
  * FAST candidates of a level before the quad-tree (x,y level coords rel. to image, score) */
 const uint8_t* sso_orb_level_image(const sso_orb*, int level, int blurred);
 int      sso_orb_level_candidates(const sso_orb*, int level, int32_t* xys /*3 per cand*/, int cap);
+/* ORBextractor::DistributeOctTree alone on nc (x, y, score) triples relative to (minX, minY), in detection order; sel_out (room for nc): the indices of
+ * the selected candidates in lNodes order.  returns their number */
+int      sso_distribute_octtree(const int32_t* xys, int nc, int minX, int maxX, int minY, int maxY, int N, int32_t* sel_out);
 /* the scalar pieces, exposed for KATs */
 int      sso_fast_score(const uint8_t* p, int stride);   /* max(bright,dark arc-min) at p; corner iff > t; cv score = this-1 */
 float    sso_fast_atan2(float y, float x);               /* cv::fastAtan2 (2.4), degrees */

@@ -389,6 +389,7 @@ SYMBOLS = {
     "ssm_debug_pyramid": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(_I)]),
     "ssm_debug_orb_blur": (_I, [_P, _P, _I, _I, _P, C.POINTER(_I)]),
     "ssm_debug_orb_describe": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ssm_debug_orb_octree": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "ssm_debug_fast_plan": (_I, [C.POINTER(Config), _P, _I, C.POINTER(_I), _P]),
     "ssm_debug_fast_quick": (_I, [_P, _I, _I, _I, _P]),
     "ssm_debug_pyramid_plan": (_I, [C.POINTER(Config), _I, _P, _I, C.POINTER(_I), _P, _P]),

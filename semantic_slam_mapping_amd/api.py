@@ -1228,6 +1228,33 @@ class Context:
                                                   _ptr(out["desc"]), _ptr(out["pos3d"]), _ptr(out["moments"]), _ptr(out["sincos"])))
         return out
 
+    OCTREE_GEOM_FIELDS = ("w", "h", "minB", "nCols", "nRows", "wCell", "hCell", "nfeat", "nIni", "cand_cap", "sel_cap")
+
+    def debug_orb_octree_geometry(self):
+        """ssm_debug_orb_octree's geometry query: {"levels": [per level a dict of OCTREE_GEOM_FIELDS], "cells_total", "cand_total", "sel_total", "nodes"}"""
+        nl, k = self.cfg.orb_levels, len(self.OCTREE_GEOM_FIELDS)
+        g = np.zeros(nl * k + 4, np.int32)
+        self._chk(self.lib.ssm_debug_orb_octree(self.h, 0, None, None, None, _ptr(g), None, None, None, None))
+        out = {"levels": [dict(zip(self.OCTREE_GEOM_FIELDS, (int(v) for v in g[l * k:(l + 1) * k]))) for l in range(nl)]}
+        out.update(zip(("cells_total", "cand_total", "sel_total", "nodes"), (int(v) for v in g[nl * k:])))
+        return out
+
+    def debug_orb_octree(self, ncand, cand, cellmax, want_nodeof=False):
+        """ssm_debug_orb_octree: the quad-tree selection alone on planted candidates.  ncand (n, levels) counts; cand (sum(ncand), 2) uint32 words
+        (x | y << 12 | score << 24, cell << 14 | yInCell << 7 | xInCell) of all frames, frame by frame and level by level, in buffer order; cellmax
+        (n, cells_total).  Returns (nsel (n, levels), sel (n, sel_total) -- slots that were not written hold 0xA5A5A5A5 --, status), and with want_nodeof
+        a fourth element: the global node-id scratch (n, cand_total) uint16 after the launch, 0xA5A5 where the kernel did not write"""
+        geo = self.debug_orb_octree_geometry()
+        ncand = np.ascontiguousarray(ncand, np.int32); cand = np.ascontiguousarray(cand, np.uint32).reshape(-1, 2); cellmax = np.ascontiguousarray(cellmax, np.int32)
+        n = len(ncand)
+        if ncand.ndim != 2 or ncand.shape[1] != self.cfg.orb_levels or cellmax.shape != (n, geo["cells_total"]) or (ncand >= 0).all() and int(ncand.sum()) != len(cand):
+            raise ValueError("ncand must be (n, levels) and sum to len(cand); cellmax (n, cells_total)")
+        m = max(n, 1)
+        nsel = np.zeros((m, self.cfg.orb_levels), np.int32); sel = np.zeros((m, geo["sel_total"]), np.uint32); status = np.zeros(1, np.int32)
+        nodeof = np.zeros((m, geo["cand_total"]), np.uint16) if want_nodeof else None
+        self._chk(self.lib.ssm_debug_orb_octree(self.h, n, _ptr(ncand), _ptr(cand), _ptr(cellmax), None, _ptr(nsel), _ptr(sel), _ptr(status), _ptr(nodeof)))
+        return (nsel, sel, int(status[0]), nodeof) if want_nodeof else (nsel, sel, int(status[0]))
+
     def window_match(self, kp1, d1, kp2, d2, sw, sh, thr):
         kp1 = np.ascontiguousarray(kp1, np.float32).reshape(-1, 2); kp2 = np.ascontiguousarray(kp2, np.float32).reshape(-1, 2)
         d1 = np.ascontiguousarray(d1, np.uint8).reshape(-1, 32); d2 = np.ascontiguousarray(d2, np.uint8).reshape(-1, 32)

@@ -1430,15 +1430,20 @@ extern "C" void ssm_debug_octree_prof(void)
     (void)hipMemcpyToSymbol(HIP_SYMBOL(ot_prof), h, sizeof(h));
 }
 #endif
-hipError_t k_octree(int n, const OrbGeom& g, const cand_t* cand, const int32_t* ncand, const int32_t* cellmax, uint16_t* node_of,
-                    uint32_t* sel, int32_t* nsel, int32_t* status, hipStream_t s)
+int k_octree_nodes(const OrbGeom& g)
 {
     int need = 0;
     for (int l = 0; l < g.nlevels; l++) need = need > g.L[l].nfeat + 3 ? need : g.L[l].nfeat + 3;
     for (int l = 0; l < g.nlevels; l++) need = need > 4 * g.L[l].nIni + 8 ? need : 4 * g.L[l].nIni + 8;
-    if (need <= 256 - 8) octree_kernel<256><<<dim3(n, g.nlevels), OT_T, 0, s>>>(g, cand, ncand, cellmax, node_of, sel, nsel, status);
-    else if (need <= 512 - 8) octree_kernel<512><<<dim3(n, g.nlevels), OT_T, 0, s>>>(g, cand, ncand, cellmax, node_of, sel, nsel, status);
-    else                 octree_kernel<1024><<<dim3(n, g.nlevels), OT_T, 0, s>>>(g, cand, ncand, cellmax, node_of, sel, nsel, status);
+    return need <= 256 - 8 ? 256 : need <= 512 - 8 ? 512 : 1024;
+}
+hipError_t k_octree(int n, const OrbGeom& g, const cand_t* cand, const int32_t* ncand, const int32_t* cellmax, uint16_t* node_of,
+                    uint32_t* sel, int32_t* nsel, int32_t* status, hipStream_t s)
+{
+    const int nodes = k_octree_nodes(g);
+    if (nodes == 256)      octree_kernel<256><<<dim3(n, g.nlevels), OT_T, 0, s>>>(g, cand, ncand, cellmax, node_of, sel, nsel, status);
+    else if (nodes == 512) octree_kernel<512><<<dim3(n, g.nlevels), OT_T, 0, s>>>(g, cand, ncand, cellmax, node_of, sel, nsel, status);
+    else                   octree_kernel<1024><<<dim3(n, g.nlevels), OT_T, 0, s>>>(g, cand, ncand, cellmax, node_of, sel, nsel, status);
     return hipGetLastError();
 }
 

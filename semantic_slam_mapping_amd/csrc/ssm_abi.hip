@@ -468,6 +468,67 @@ extern "C" int ssm_debug_orb_describe(ssm_ctx* c, const uint8_t* img, int channe
     }
     return SSM_OK;
 }
+// The hook for exact tests of the quad-tree selection: k_octree alone, as orb_detect launches it, on PLANTED candidate lists and cell maxima in the context's
+// first workspace (include/ssm_hip.h).  Everything the kernel relies on is checked here, on the host, before the first launch.
+extern "C" int ssm_debug_orb_octree(ssm_ctx* c, int n, const int32_t* ncand, const uint32_t* cand, const int32_t* cellmax, int32_t* geom, int32_t* nsel, uint32_t* sel, int32_t* status,
+                                    uint16_t* nodeof)
+{
+    if (!c) return SSM_E_INVAL;
+    std::lock_guard<std::mutex> lk(c->mu); hipSetDevice(c->device);
+    const OrbGeom& g = c->g;
+    if (geom) {
+        for (int l = 0; l < g.nlevels; l++) {
+            const LevelGeom& L = g.L[l];
+            const int32_t v[SSM_OCTREE_GEOM_LEVEL_INTS] = {L.w, L.h, L.minBX, L.nCols, L.nRows, L.wCell, L.hCell, L.nfeat, L.nIni, L.cand_cap, L.sel_cap};
+            memcpy(geom + l * SSM_OCTREE_GEOM_LEVEL_INTS, v, sizeof(v));
+        }
+        int32_t* t = geom + g.nlevels * SSM_OCTREE_GEOM_LEVEL_INTS;
+        t[0] = g.cells_total; t[1] = g.cand_total; t[2] = g.sel_total; t[3] = k_octree_nodes(g);
+    }
+    if (!ncand && !cand && !cellmax) { if (!geom) FAIL(c, SSM_E_INVAL, "bad arguments"); return SSM_OK; }      // the geometry query
+    if (!ncand || !cellmax || !nsel || !sel || !status) FAIL(c, SSM_E_INVAL, "bad arguments");
+    if (n < 1 || n > c->B) FAIL(c, SSM_E_INVAL, "n must be 1..max_batch");
+    std::vector<cand_t> h_cand((size_t)n * g.cand_total, make_uint2(0u, 0u));
+    size_t total = 0;
+    for (int f = 0; f < n; f++)
+        for (int l = 0; l < g.nlevels; l++) {
+            const LevelGeom& L = g.L[l]; const int k = ncand[f * g.nlevels + l];
+            const std::string at = " of frame " + std::to_string(f) + " level " + std::to_string(l);
+            if (k < 0 || k > L.cand_cap) FAIL(c, SSM_E_INVAL, "ncand" + at + " outside 0.." + std::to_string(L.cand_cap));
+            if (k && !cand) FAIL(c, SSM_E_INVAL, "bad arguments");
+            const int W = L.maxBX - L.minBX, H = L.maxBY - L.minBY;
+            for (int i = 0; i < k; i++, total++) {
+                const uint32_t lo = cand[2 * total], hi = cand[2 * total + 1];
+                const int x = lo & 4095, y = (lo >> 12) & 4095, cell = (int)(hi >> 14), yin = (hi >> 7) & 127, xin = hi & 127;
+                if (x < 3 || x >= W - 3 || y < 3 || y >= H - 3)
+                    FAIL(c, SSM_E_INVAL, "planted candidate (" + std::to_string(x) + ", " + std::to_string(y) + ")" + at + " outside the detection window [3, W - 3) x [3, H - 3)");
+                if (cell >= L.nCols * L.nRows) FAIL(c, SSM_E_INVAL, "cell " + std::to_string(cell) + at + " outside the level's " + std::to_string(L.nCols * L.nRows) + " cells");
+                const int cj = (x - 3) / L.wCell, ci = (y - 3) / L.hCell;                       // fast_tile's cellx / celly
+                if (cell != ci * L.nCols + cj || xin != x - cj * L.wCell || yin != y - ci * L.hCell)
+                    FAIL(c, SSM_E_INVAL, "rank word of candidate (" + std::to_string(x) + ", " + std::to_string(y) + ")" + at + " does not match its position");
+                h_cand[(size_t)f * g.cand_total + L.cand_off + i] = make_uint2(lo, hi);
+            }
+        }
+    for (size_t i = 0; i < (size_t)n * g.cells_total; i++)
+        if (cellmax[i] < 0 || cellmax[i] > 255) FAIL(c, SSM_E_INVAL, "cellmax entry " + std::to_string(i) + " outside 0..255");
+    { const int r = wait_pending(c); if (r) return r; }
+    OrbWork& w = c->chain[0].work; hipStream_t s = c->main.stream;
+    HIPCHK(c, hipMemcpyAsync(w.cand, h_cand.data(), h_cand.size() * sizeof(cand_t), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(w.ncand, ncand, (size_t)n * g.nlevels * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(w.cellmax, cellmax, (size_t)n * g.cells_total * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(w.sel, 0xA5, (size_t)n * g.sel_total * 4, s));                  // what the kernel does not write comes back as this byte
+    HIPCHK(c, hipMemsetAsync(w.nsel, 0xA5, (size_t)n * g.nlevels * 4, s));
+    HIPCHK(c, hipMemsetAsync(w.nodeof, 0xA5, (size_t)n * g.cand_total * 2, s));
+    HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4, s));
+    HIPCHK(c, k_octree(n, g, w.cand, w.ncand, w.cellmax, w.nodeof, w.sel, w.nsel, c->d_status, s));
+    HIPCHK(c, hipMemcpyAsync(nsel, w.nsel, (size_t)n * g.nlevels * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(sel, w.sel, (size_t)n * g.sel_total * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemcpyAsync(status, c->d_status, 4, hipMemcpyDeviceToHost, s));
+    if (nodeof) HIPCHK(c, hipMemcpyAsync(nodeof, w.nodeof, (size_t)n * g.cand_total * 2, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipMemsetAsync(c->d_status, 0, 4, s));                                         // nothing planted leaks into the next call
+    HIPCHK(c, hipStreamSynchronize(s));
+    return SSM_OK;
+}
 
 // ---- the per-frame calls of the reference's unchanged loop (Tracker::trackRefFrame: detectFeatures, then match against every reference frame,
 // src/track.cpp:140-163 there).  Each call takes ONE block of the pinned ring (inputs staged, results landed) and ONE block of the device ring.  A small struct

@@ -42,6 +42,7 @@ size_t k_fast_ncand_pad(int nframes, const OrbGeom& g);         // ints reserved
 size_t k_fast_cellmax_ints(int nframes, const OrbGeom& g);      // per-cell maxima of nframes frames + the retry work list of k_fast behind them
 hipError_t k_octree(int n, const OrbGeom& g, const cand_t* cand, const int32_t* ncand, const int32_t* cellmax, uint16_t* node_of,
                     uint32_t* sel, int32_t* nsel, int32_t* status, hipStream_t s);
+int k_octree_nodes(const OrbGeom& g);       // the LDS node capacity (256 / 512 / 1024) of the instance k_octree launches for this geometry
 hipError_t k_describe(int n, const OrbGeom& g, const uint8_t* pyr, const uint8_t* blur, const uint32_t* sel,
                       const int32_t* nsel, const float* pattern_f /* the 256 x 4 BRIEF table as floats */, const uint16_t* depth, ssm_camera cam, void* kpaux /* n * sel_total * 32 B */,
                       ssm_keypoint* kps, uint8_t* desc, float* pos3d, int32_t* nkp, hipStream_t s,

@@ -37,6 +37,7 @@ int ssm_uvd_process_dev(ssm_uvd*, const uint8_t*, const int16_t*, int, int, int,
 // PoseGraph::step reaches the extractor and the matcher through solvePnPLazy; test_posegraph --graph-only never gets there (no neighbours, no looper): they only have to link
 int ssm_orb_extract(ssm_ctx*, const uint8_t*, int, int, int, int, const uint16_t*, ssm_keypoint*, uint8_t*, float*, int, int*) { return SSM_E_NODEVICE; }
 int ssm_match(ssm_ctx*, const uint8_t*, int, const uint8_t*, int, double, ssm_dmatch*, int, int*) { return SSM_E_NODEVICE; }
+int ssm_debug_orb_octree(ssm_ctx*, int, const int32_t*, const uint32_t*, const int32_t*, int32_t*, int32_t*, uint32_t*, int32_t*, uint16_t*) { return SSM_E_NODEVICE; }      // (a test hook of the device library: no device here)
 int ssm_looper_create(ssm_ctx*, const ssm_vocab*, ssm_looper**) { return SSM_E_NODEVICE; }
 void ssm_looper_destroy(ssm_looper*) {}
 int ssm_looper_size(const ssm_looper*) { return 0; }

@@ -1,6 +1,7 @@
 """Independent numpy / pure-Python restatement of the path's contracts, written from the same published
 algorithms as oracle/*.c but sharing no code with it.  Used by make_golden.py to mint the committed fixtures and by
 tests/test_oracle_golden.py to pin the C oracle.  Small inputs only (pure-Python loops)."""
+import functools
 import math
 import numpy as np
 
@@ -291,8 +292,13 @@ class _Node:
     __slots__ = ("UL", "UR", "BL", "BR", "keys", "no_more", "seq")
 
 
-def distribute_octtree(cands, minX, maxX, minY, maxY, N):
-    """literal port of ORBextractor::DistributeOctTree with Python lists standing in for std::list"""
+def distribute_octtree(cands, minX, maxX, minY, maxY, N, trace=None):
+    """literal port of ORBextractor::DistributeOctTree with Python lists standing in for std::list.  trace: a dict that receives which paths the call took --
+    passes1 / passes2 (split passes of the first / second phase), broke (second-phase passes that stopped at N with nodes still waiting), finish1 (">= N",
+    "no growth", or "second phase" where the mode switch ended the first phase) and finish2 (">= N", "no growth", or None), seq_decided (comparisons of the
+    second phase's sort that equal sizes left to the creation sequence), tied_best (final nodes whose best response more than one key holds), final (nodes)"""
+    if trace is not None:
+        trace.update(passes1=0, passes2=0, broke=0, finish1=None, finish2=None, seq_decided=0, tied_best=0, final=0)
     if not cands:
         return []
     seq = [0]
@@ -333,9 +339,17 @@ def distribute_octtree(cands, minX, maxX, minY, maxY, N):
                 n.no_more = True
         return n1, n2, n3, n4
 
+    def by_size_then_seq(a, b):                                     # the order of sorted(key=(len(keys), seq)), counting what seq alone decides
+        if len(a.keys) != len(b.keys):
+            return -1 if len(a.keys) < len(b.keys) else 1
+        trace["seq_decided"] += 1
+        return -1 if a.seq < b.seq else (1 if a.seq > b.seq else 0)
+
     finish = False
     while not finish:
         prev = len(L); to_expand = 0; vs = []
+        if trace is not None:
+            trace["passes1"] += 1
         for p in [n for n in L]:                                   # iteration over the list as it was at the start
             if p.no_more:
                 continue
@@ -347,11 +361,19 @@ def distribute_octtree(cands, minX, maxX, minY, maxY, N):
             L.remove(p)
         if len(L) >= N or len(L) == prev:
             finish = True
+            if trace is not None:
+                trace["finish1"] = ">= N" if len(L) >= N else "no growth"
         elif len(L) + to_expand * 3 > N:
+            if trace is not None:
+                trace["finish1"] = "second phase"
             while not finish:
                 prev = len(L)
-                vp = sorted(vs, key=lambda n: (len(n.keys), n.seq)); vs = []
-                for p in reversed(vp):
+                if trace is not None:
+                    trace["passes2"] += 1
+                    vp = sorted(vs, key=functools.cmp_to_key(by_size_then_seq)); vs = []
+                else:
+                    vp = sorted(vs, key=lambda n: (len(n.keys), n.seq)); vs = []
+                for done, p in enumerate(reversed(vp)):
                     for c in divide(p):
                         if c.keys:
                             L.insert(0, c)
@@ -359,9 +381,13 @@ def distribute_octtree(cands, minX, maxX, minY, maxY, N):
                                 vs.append(c)
                     L.remove(p)
                     if len(L) >= N:
+                        if trace is not None and done + 1 < len(vp):
+                            trace["broke"] += 1
                         break
                 if len(L) >= N or len(L) == prev:
                     finish = True
+                    if trace is not None:
+                        trace["finish2"] = ">= N" if len(L) >= N else "no growth"
     res = []
     for n in L:
         best = n.keys[0]
@@ -369,6 +395,10 @@ def distribute_octtree(cands, minX, maxX, minY, maxY, N):
             if k[2] > best[2]:
                 best = k
         res.append(best)
+        if trace is not None and sum(1 for k in n.keys if k[2] == best[2]) > 1:
+            trace["tied_best"] += 1
+    if trace is not None:
+        trace["final"] = len(L)
     return res
 
 
