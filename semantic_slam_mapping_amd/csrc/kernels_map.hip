@@ -373,7 +373,9 @@ hipError_t k_voxel_insert(const ssm_point* pts, const int64_t* n_dev, int64_t n_
 // ------------------------------------------------------------------ K10+K11+K12, streaming form (w % 16 == 0): map_stream2_kernel below.
 // One thread = 16 consecutive pixels of a row; consecutive pixels with the same (voxel, label) are summed in registers, the run tails update a block-local LDS hash
 // (256 slots for the 3 x 4096 pixels of a block) and the block flushes it with one global atomic group per voxel.  The point list of generatePointCloud is never
-// written: exact integer sums make the map independent of order, so the result is bit-identical to mask -> backproject -> insert (tests/test_gpu_parity.py).
+// written: exact integer sums make the map independent of order, so the result is bit-identical to mask -> backproject -> insert (tests/test_gpu_parity.py on
+// the synthetic stream; tests/test_gpu_map_planted.py on planted frames -- kept pixels per wave, runs inside a lane's share, widths, gate and dilate edges --
+// against the oracle's voxel TABLE, every sum and every label vote).
 // (Rounds 1-5 also carried the first form of this fusion -- class_bits_kernel + vdilate_bits_kernel + map_stream_kernel, every pixel through the full arithmetic,
 // two wave-wide segmented scans per chunk: 12 % slower, profiles/r03_*; removed in round 6, the compacting kernel covers every width the path accepts.)
 template <int CTRL, int ROW_MASK>
@@ -775,14 +777,16 @@ int k_map_fuse_blocks_per_frame(int w, int h) { const int words = (w >> 4) * h; 
 int k_map_fuse_block_records(void) { return MS_CH * 4096; }            // overflow records one block can append at most: one per pixel
 int k_map_fuse_resident_blocks(void) { return 256 * MS2_MINB; }
 int k_map_fuse_skip_cap(void) { return MS2_SKIP_CAP; }
-// n frames of w x h (w % 16 == 0, w <= 4096).  skip / hw / tag: see map_stream2_kernel (skip = the context's skip list, MS2_SKIP_CAP entries; counters[6] counts them).
+// n frames of w x h (w % 16 == 0, 32 <= w <= 4096).  skip / hw / tag: see map_stream2_kernel (skip = the context's skip list, MS2_SKIP_CAP entries; counters[6] counts them).
 // nredo > 0: run exactly the blocks redo_ids[0 .. nredo) (device) of an earlier launch with these arguments again (its per-frame point counts go on counting).
 hipError_t k_map_fuse(const uint16_t* depth, const uint8_t* rgb, const uint8_t* sem, const double* pose, int n, int w, int h,
                       ssm_camera cam, const MapDiv& md, bool fast, double max_distance, float leaf,
                       ssm_voxel* tab, int cap_log2, int32_t* counters, int32_t* npoints, hipStream_t s, int32_t* skip, int hw, int tag, const int32_t* redo_ids, int nredo)
 {
     const int wpr = w >> 4, words = wpr * h;
-    if (!((long long)words * wpr < (1ll << 32) && wpr <= 256)) return hipErrorInvalidValue;      // frames wider than 4096 pixels: not supported by the fused map stage
+    // frames wider than 4096 pixels (the kernel's bit image) or narrower than 32 (mul_wpr below: ceil(2^32 / 1) does not fit 32 bits, and wpr = 0 would divide by
+    // zero): not supported by the fused map stage.  (ssm_create refuses both long before: frames of 64 .. 4000 pixels.)
+    if (!((long long)words * wpr < (1ll << 32) && wpr >= 2 && wpr <= 256)) return hipErrorInvalidValue;
     if (nredo <= 0) { const hipError_t e = hipMemsetAsync(npoints, 0, sizeof(int32_t) * n, s); if (e != hipSuccess) return e; }
     const int gx = (words + 256 * MS_CH - 1) / (256 * MS_CH);
     const dim3 grid(gx, n);
