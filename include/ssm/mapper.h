@@ -160,7 +160,8 @@ public:
         grid_params.h_max = para.getData<double>("mapper_grid_h_max", grid_params.h_max);
         objects = para.getData<int>("mapper_objects", 0) != 0;
         clearance = para.getData<int>("mapper_clearance", 0) != 0;
-        if (grid || objects || clearance) {          // (the objects and the clearance map stand on a grid of the same frame, whether or not the grid itself is wanted)
+        route = para.getData<int>("mapper_route", 0) != 0;
+        if (grid || objects || clearance || route) {          // (the objects, the clearance map and the route field stand on a grid of the same frame, whether or not the grid itself is wanted)
             double up[3] = {0, -1, 0}, fw[3] = {0, 0, 1};
             auto three = [&](const char* key, double* v) {
                 auto it = para.data.find(key);
@@ -196,6 +197,15 @@ public:
             while (ss >> l) { if (l < 0 || l > 4) throw std::runtime_error("Mapper: mapper_clearance_blocked and mapper_clearance_free take cell classes 0..4"); mask |= 1u << l; }
             (which ? clearance_params.free_mask : clearance_params.blocked_mask) = mask;
         }
+        route_dir = para.getData<string>("mapper_route_dir", string(""));
+        ssm_route_params_default(&route_params);
+        route_params.moves = para.getData<int>("mapper_route_moves", route_params.moves);
+        route_params.near_weight = para.getData<int>("mapper_route_near_weight", route_params.near_weight);
+        route_params.comfort = para.getData<double>("mapper_route_comfort", route_params.comfort);
+        route_goal_snap = para.getData<int>("mapper_route_goal_snap", 10);
+        route_max_path = para.getData<int>("mapper_route_max_path", 0);          // 0: 4 (nx + ny) of the grid that is built
+        route_has_goal = para.data.find("mapper_route_goal_x") != para.data.end() && para.data.find("mapper_route_goal_y") != para.data.end();
+        route_goal_x = para.getData<double>("mapper_route_goal_x", 0.0); route_goal_y = para.getData<double>("mapper_route_goal_y", 0.0);
         test_fail_update = para.getData<int>("mapper_test_fail_update", -1);        // tests: the device-resident update with this number fails (-> the host path from there on)
         viewerThread = make_shared<thread>(bind(&Mapper::viewer, this));
     }
@@ -225,7 +235,7 @@ public:
             if (!kfs.empty()) updateMap(kfs, true, map, t0);          // (without a key-frame there is no map to rebuild)
         }
         if (render) renderAll(keyframesNow());          // every key-frame is a view of the clouds around it, in their final state
-        if (grid || objects || clearance) buildGrid(keyframesNow()); // one ground grid of every key-frame's cloud, in its final state; the objects that stand on it; its clearance map
+        if (grid || objects || clearance || route) buildGrid(keyframesNow()); // one ground grid of every key-frame's cloud, in its final state; the objects that stand on it; its clearance map
         } catch (const std::exception& e) {             // a device error on this thread must not std::terminate the process: report it and stop mapping
             cerr << "Mapper::viewer stopped: " << e.what() << endl; viewerFailed = true;
         }
@@ -539,6 +549,7 @@ public:
     void buildGrid(const vector<RGBDFrame::Ptr>& kfs) {
         objectsState = ObjectsInfo(); objectRecords.clear(); objectIds.clear();
         clearanceState = ClearanceInfo(); clearanceD2.clear(); clearanceNearest.clear(); clearanceReach.clear();
+        routeState = RouteInfo(); routeCost.clear(); routeParent.clear(); routeCells.clear();
         gridState = GridInfo(); gridSpec = grid_params; gridSpec.nx = gridSpec.ny = 0;
         gridCls.clear(); gridGroundLabel.clear(); gridObstacleLabel.clear(); gridGroundQ.clear(); gridTopQ.clear(); gridN.clear(); gridNHigh.clear();
         if (kfs.empty()) { gridState.skipped = true; return; }
@@ -574,8 +585,8 @@ public:
                 "ssm_grid_fetch");
         gridSpec = P; gridState.counts = I; gridState.built = true;
         if (objects) extractObjects(d, target.t, L, P);
-        if (clearance) mapClearance(d, target.t, P, mapPoseOf(kfs.back()));
-        if ((grid || !(objects || clearance)) && !grid_dir.empty()) {          // (a grid built only for the objects or the clearance map writes no grid files)
+        if (clearance || route) mapClearance(d, target.t, P, mapPoseOf(kfs.back()));          // (the route field has the clearance map built for it, which then writes no file)
+        if ((grid || !(objects || clearance || route)) && !grid_dir.empty()) {          // (a grid built only for the objects, the clearance map or the route field writes no grid files)
             cv::Mat col, hgt; col.create(P.ny, P.nx, CV_8UC3); hgt.create(P.ny, P.nx, CV_16UC1);
             ssm_grid_colours(gridCls.data(), gridGroundLabel.data(), gridObstacleLabel.data(), gridGroundQ.data(), P.nx, P.ny, P.h_min, col.data, hgt.ptr<uint16_t>());
             ofstream txt(grid_dir + "/grid.txt");
@@ -643,7 +654,8 @@ public:
         clearanceD2.resize(nc); clearanceNearest.resize(nc); clearanceReach.resize(nc);
         d.check(ssm_clearance_fetch(d.ctx(), target.t, clearanceD2.data(), clearanceNearest.data(), clearanceReach.data()), "ssm_clearance_fetch");
         clearanceState.counts = I; clearanceState.seed_cx = C.seed_cx; clearanceState.seed_cy = C.seed_cy; clearanceState.built = true;
-        if (!clearance_dir.empty()) {
+        if (route) mapRoute(d, target.t, P);          // (while the clearance target lives: the field reads it on the device)
+        if (clearance && !clearance_dir.empty()) {
             cv::Mat cm, rm; cm.create(P.ny, P.nx, CV_16UC1); rm.create(P.ny, P.nx, CV_8UC1);
             for (int r = 0; r < P.ny; r++) for (int x = 0; x < P.nx; x++) {
                 const size_t i = (size_t)(P.ny - 1 - r) * P.nx + x;
@@ -660,6 +672,64 @@ public:
                 throw std::runtime_error("Mapper: cannot write the clearance map to " + clearance_dir);
         }
     }
+    // mapper_route=1 (default 0: nothing of this runs, every cloud, map, grid, object, clearance result, file and figure exactly as before): the route field
+    // (the reference has no such step) over the clearance map mapClearance has just made, on the device (ssm_route_field), then ONE path: to the cell
+    // of (mapper_route_goal_x, _goal_y), metres in the grid frame, through ssm_clrc::cell_of -- a goal outside the grid is refused -- or, without a goal, to
+    // far_cell, the farthest place the vehicle can drive to.  mapper_route_moves (8), _near_weight (2), _comfort (2.0 m), _goal_snap (10 cells), _max_path
+    // (4 (nx + ny)).  routeInfo(), routePathInfo(), routeFetch(cost, parent), routePath(); with mapper_route_dir set the call writes route.png (8 bit: reach.png's
+    // values with the path's cells at 64), route_cost.png (16 bit: min(65534, cost), 65535 for no cost) and route.txt (both infos as `name value` lines, then one
+    // `cx cy` per path cell); image row r is cell row ny - 1 - r as in the grid's images
+    struct RouteInfo { bool built = false; int32_t goal_cx = -1, goal_cy = -1; ssm_route_info counts{}; ssm_route_path_info path{}; };          // goal_cx, goal_cy: the goal asked for (-1, -1: nothing routed)
+    typedef Owned<ssm_route_target, ssm_route_target_free> RouteTarget;
+    void mapRoute(ssm::Device& d, ssm_clearance_target* clearance_target, const ssm_grid_params& P) {
+        const int max_path = route_max_path > 0 ? route_max_path : 4 * (P.nx + P.ny);
+        RouteTarget target(d.ctx());
+        d.check(ssm_route_target_create(d.ctx(), P.nx, P.ny, max_path, &target.t), "ssm_route_target_create");
+        ssm_route_info I{};
+        d.check(ssm_route_field(d.ctx(), clearance_target, &route_params, target.t, &I), "ssm_route_field");
+        const size_t nc = (size_t)P.nx * P.ny;
+        routeCost.resize(nc); routeParent.resize(nc);
+        d.check(ssm_route_fetch(d.ctx(), target.t, routeCost.data(), routeParent.data()), "ssm_route_fetch");
+        int32_t gx = -1, gy = -1, snap = route_goal_snap;
+        if (route_has_goal) { if (!ssm_clrc::cell_of(P, route_goal_x, route_goal_y, &gx, &gy)) throw std::runtime_error("Mapper: mapper_route_goal_x, _goal_y lie outside the grid"); }
+        else if (I.far_cell >= 0) { gx = (int32_t)(I.far_cell % P.nx); gy = (int32_t)(I.far_cell / P.nx); snap = 0; }
+        ssm_route_path_info PI{}; PI.goal_cell = -1; PI.cost = -1; PI.min_d2 = -1;
+        routeCells.assign((size_t)min<int64_t>(max_path, (int64_t)nc), -1);
+        if (gx >= 0) {
+            d.check(ssm_route_path(d.ctx(), target.t, gx, gy, snap, routeCells.data(), &PI), "ssm_route_path");
+            routeCells.resize((size_t)PI.len);
+        } else routeCells.clear();
+        routeState.counts = I; routeState.path = PI; routeState.goal_cx = gx; routeState.goal_cy = gy; routeState.built = true;
+        if (!route_dir.empty()) {
+            cv::Mat rm, cm; rm.create(P.ny, P.nx, CV_8UC1); cm.create(P.ny, P.nx, CV_16UC1);
+            vector<uint8_t> on(nc, 0);
+            for (int32_t c : routeCells) on[(size_t)c] = 1;
+            for (int r = 0; r < P.ny; r++) for (int x = 0; x < P.nx; x++) {
+                const size_t i = (size_t)(P.ny - 1 - r) * P.nx + x;
+                rm.ptr<uint8_t>(r)[x] = (uint8_t)(on[i] ? 64 : clearanceReach[i] == 2 ? 255 : clearanceReach[i] == 1 ? 128 : 0);
+                cm.ptr<uint16_t>(r)[x] = (uint16_t)(routeCost[i] == UINT32_MAX ? 65535u : min<uint32_t>(65534u, routeCost[i]));
+            }
+            ofstream txt(route_dir + "/route.txt");
+            txt << "routed " << I.routed << "\nunrouted " << I.unrouted << "\nnear_cells " << I.near_cells << "\nmax_cost " << I.max_cost << "\nfar_cell " << I.far_cell << "\nsource_cell "
+                << I.source_cell << "\ncomfort2 " << I.comfort2 << "\nmoves " << I.moves << "\nlen " << PI.len << "\ngoal_cell " << PI.goal_cell << "\ncost " << PI.cost << "\nn_axial "
+                << PI.n_axial << "\nn_diag " << PI.n_diag << "\nnear_steps " << PI.near_steps << "\nmin_d2 " << PI.min_d2 << "\n";
+            for (int32_t c : routeCells) txt << c % P.nx << " " << c / P.nx << "\n";
+            txt.close();
+            if (!(txt && ssm::imwritePNG(route_dir + "/route.png", rm) && ssm::imwritePNG(route_dir + "/route_cost.png", cm)))
+                throw std::runtime_error("Mapper: cannot write the route field to " + route_dir);
+        }
+    }
+    bool mapsRoute() const { return route; }
+    // the last mapRoute (not while the viewer thread runs): the goal, both infos; the field of the grid gridParams() describes; the path's cells, source first
+    const RouteInfo& routeInfo() const { return routeState; }
+    const ssm_route_path_info& routePathInfo() const { return routeState.path; }
+    bool routeFetch(vector<uint32_t>* cost, vector<int32_t>* parent) const {
+        if (!routeState.built) return false;
+        if (cost) *cost = routeCost;
+        if (parent) *parent = routeParent;
+        return true;
+    }
+    const vector<int32_t>& routePath() const { return routeCells; }
     bool mapsClearance() const { return clearance; }
     // the last mapClearance (not while the viewer thread runs): what happened, the seed and the counts; the images of the grid gridParams() describes
     const ClearanceInfo& clearanceInfo() const { return clearanceState; }
@@ -845,6 +915,8 @@ protected:
     bool relabel = false; int relabel_window = 5, relabelled = 0, relabelViewsAlive = 0; ssm_relabel_params relabel_params{}; bool relabel_hash = false; uint64_t relabelFnv = 0;
     std::unordered_map<const RGBDFrame*, ssm_relabel_info> relabelInfo;  // key-frame -> what the views did to its labels (viewer thread, or its owner once that has ended)
     bool clearance = false; string clearance_dir; ssm_clearance_params clearance_params{}; ClearanceInfo clearanceState;
+    bool route = false, route_has_goal = false; string route_dir; ssm_route_params route_params{}; int route_goal_snap = 10, route_max_path = 0; double route_goal_x = 0, route_goal_y = 0;
+    RouteInfo routeState; vector<uint32_t> routeCost; vector<int32_t> routeParent, routeCells;      // the last mapRoute's field and path
     vector<uint32_t> clearanceD2; vector<int32_t> clearanceNearest; vector<uint8_t> clearanceReach;      // the last mapClearance's images
     bool objects = false; string objects_dir; ssm_objects_params objects_params{}; ObjectsInfo objectsState; vector<ssm_object> objectRecords; vector<int32_t> objectIds;
     bool grid = false; string grid_dir; ssm_grid_params grid_params{}, gridSpec{}; GridInfo gridState;

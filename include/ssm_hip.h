@@ -726,6 +726,61 @@ int  ssm_debug_clearance_form(ssm_ctx* ctx, int form);
 /* the staging width of row-pass form 0, for the tests */
 int  ssm_debug_clearance_chunk(void);
 
+/* ---- route field: the cheapest paths over a clearance map.  The reference has no such step; DESIGN.md s.23 is the contract, include/ssm/route_core.h the
+ * arithmetic shared by the device path and the host functions (device == host byte for byte; integers only).
+ * Input: the last result of a clearance target -- reach, dist2 and the seed cell.  Only cells with reach == 2 take part; the SOURCE is the seed cell.  A cell
+ * weighs 1 + near_weight when dist2 <= comfort2 = floor((comfort / cell)^2) (saturated at 2^31), else 1.  The axial moves have step 5, with moves == 8 the diagonal
+ * ones step 7, and a diagonal move exists only when both cells that share an edge with its two ends take part as well (no corner is cut).  An edge costs
+ * step (w(a) + w(b)).  cost (uint32): the minimum over all paths from the source of the sum of the edges, 0 at the source, UINT32_MAX where no path leads.
+ * parent (int32): for a routed cell other than the source the neighbour p with the smallest key ((cost(p) + edge(p, c)) << 24) | index(p), -1 at the source and
+ * on unrouted cells.  Without a seed the call succeeds and routes nothing.
+ * A path query snaps the goal to the routed cell with the smallest key (d2 << 24) | index within goal_snap cells (the clearance seed's rule) and writes the cells
+ * from the source to that cell.  No such cell: len 0, goal_cell -1, cost -1, min_d2 -1.  A path longer than the target's max_path: SSM_E_CAPACITY, the path info
+ * filled (len: the length needed), no cell written.
+ * SSM_E_INVAL: a null argument; moves other than 4 or 8; near_weight outside 0 .. 8; a negative or non-finite comfort; a cell size that is not positive and
+ * finite; goal_snap outside 0 .. 1024; a goal outside the grid; a side above 32768 or more than 2^24 cells; a source that is neither -1 nor a cell with
+ * reach == 2; a target smaller than the grid or of another context; max_path < 1; a clearance target never run; a path query before a field. */
+typedef struct {
+    int32_t moves, near_weight;
+    double comfort;                          /* metres */
+    double cell;                             /* metres per cell of hand-made inputs (the host functions, ssm_debug_route_cells); ssm_route_field takes the clearance call's */
+} ssm_route_params;
+/* near_cells: routed cells with dist2 <= comfort2 (whatever near_weight); far_cell: the routed cell of largest cost, the lowest index among equals */
+typedef struct { int64_t routed, unrouted, near_cells, max_cost, far_cell, source_cell, comfort2, moves; } ssm_route_info;
+/* near_steps: cells of the path with dist2 <= comfort2; min_d2: the smallest dist2 on the path */
+typedef struct { int64_t len, goal_cell, cost, n_axial, n_diag, near_steps, min_d2; } ssm_route_path_info;
+typedef struct ssm_route_target ssm_route_target;
+/* moves 8; near_weight 2; comfort 2.0 m; cell 1.0 */
+void ssm_route_params_default(ssm_route_params* p);
+/* device arrays for grids of up to nx ny cells and paths of up to max_path cells, reused across calls */
+int  ssm_route_target_create(ssm_ctx* ctx, int nx, int ny, int max_path, ssm_route_target** target_out);
+void ssm_route_target_free(ssm_ctx* ctx, ssm_route_target* target);
+/* the field over the clearance target's last result; nothing is uploaded.  The route target keeps what a path query needs: the clearance target may be run again
+ * or freed afterwards.  params NULL: the defaults; info may be NULL */
+int  ssm_route_field(ssm_ctx* ctx, const ssm_clearance_target* clearance, const ssm_route_params* params, ssm_route_target* target, ssm_route_info* info);
+/* a path of the target's field: cells_out has room for the target's max_path indices (cy nx + cx), source first */
+int  ssm_route_path(ssm_ctx* ctx, ssm_route_target* target, int goal_cx, int goal_cy, int goal_snap, int32_t* cells_out, ssm_route_path_info* path_info);
+/* the images of the target's field (nx ny entries each); each pointer may be NULL */
+int  ssm_route_fetch(ssm_ctx* ctx, const ssm_route_target* target, uint32_t* cost, int32_t* parent);
+/* the field on the CPU, no GPU, the same bits: Dijkstra with a circular bucket queue.  source_cell: an index or -1; each output may be NULL */
+int  ssm_route_cells_host(const uint8_t* reach, const uint32_t* dist2, int nx, int ny, int source_cell, const ssm_route_params* params, uint32_t* cost, int32_t* parent,
+                          ssm_route_info* info);
+/* a path on the CPU from the arrays of a field (cost, parent) and the clearance map's dist2; cells_out (room for max_path indices) may be NULL: only the info */
+int  ssm_route_path_host(const uint32_t* cost, const int32_t* parent, const uint32_t* dist2, int nx, int ny, const ssm_route_params* params, int goal_cx, int goal_cy, int goal_snap,
+                         int max_path, int32_t* cells_out, ssm_route_path_info* path_info);
+/* for the tests: hand-made reach and dist2 images uploaded and the stage run on them */
+int  ssm_debug_route_cells(ssm_ctx* ctx, ssm_route_target* target, const uint8_t* reach, const uint32_t* dist2, int nx, int ny, int source_cell, const ssm_route_params* params,
+                           ssm_route_info* info);
+/* how the context's later fields relax: 0 sweeps of one thread per cell in batches, 1 tiles relaxed to their own fixed point from an active list, -1 the default;
+ * the same bits either way */
+int  ssm_debug_route_form(ssm_ctx* ctx, int form);
+/* how many times the context's last field asked the device whether it was done (form 0: batches of sweeps, form 1: rounds of active tiles); a measurement, not
+ * part of the contract */
+int  ssm_debug_route_rounds(ssm_ctx* ctx);
+/* the tile of form 1 and the sweeps per batch of form 0, for the tests */
+int  ssm_debug_route_tile(void);
+int  ssm_debug_route_batch(void);
+
 /* ---- label fusion: the key-frames around a cloud (the views: depth image, label image, camera, world pose) vote on the label of each of its points, and a point
  * takes the label its views agree on.  The reference has no such step; DESIGN.md s.20 is the contract, include/ssm/relabel_core.h the arithmetic shared by the
  * device path and the host function (device == host bit for bit).  A view votes for a point with the label at the point's pixel when carving's verdict (s.16) is

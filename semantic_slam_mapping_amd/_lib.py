@@ -144,6 +144,18 @@ class ClearanceInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("blocked", "free_cells", "traversable", "components", "reachable", "seed_cell", "max_d2_reachable", "r2")]
 
 
+class RouteParams(C.Structure):
+    _fields_ = [("moves", C.c_int32), ("near_weight", C.c_int32), ("comfort", C.c_double), ("cell", C.c_double)]
+
+
+class RouteInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("routed", "unrouted", "near_cells", "max_cost", "far_cell", "source_cell", "comfort2", "moves")]
+
+
+class RoutePathInfo(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("len", "goal_cell", "cost", "n_axial", "n_diag", "near_steps", "min_d2")]
+
+
 class GridInfo(C.Structure):
     _fields_ = [(n, C.c_int64) for n in ("n_in", "n_finite", "out_of_band", "outside", "n_used", "unobserved", "drivable", "walkable", "other_ground", "obstacle")]
 
@@ -337,6 +349,19 @@ SYMBOLS = {
     "ssm_debug_clearance_cells": (_I, [_P, _P, _P, _I, _I, C.POINTER(ClearanceParams), C.POINTER(ClearanceInfo)]),
     "ssm_debug_clearance_form": (_I, [_P, _I]),
     "ssm_debug_clearance_chunk": (_I, []),
+    "ssm_route_params_default": (None, [C.POINTER(RouteParams)]),
+    "ssm_route_target_create": (_I, [_P, _I, _I, _I, C.POINTER(_P)]),
+    "ssm_route_target_free": (None, [_P, _P]),
+    "ssm_route_field": (_I, [_P, _P, C.POINTER(RouteParams), _P, C.POINTER(RouteInfo)]),
+    "ssm_route_path": (_I, [_P, _P, _I, _I, _I, _P, C.POINTER(RoutePathInfo)]),
+    "ssm_route_fetch": (_I, [_P, _P, _P, _P]),
+    "ssm_route_cells_host": (_I, [_P, _P, _I, _I, _I, C.POINTER(RouteParams), _P, _P, C.POINTER(RouteInfo)]),
+    "ssm_route_path_host": (_I, [_P, _P, _P, _I, _I, C.POINTER(RouteParams), _I, _I, _I, _I, _P, C.POINTER(RoutePathInfo)]),
+    "ssm_debug_route_cells": (_I, [_P, _P, _P, _P, _I, _I, _I, C.POINTER(RouteParams), C.POINTER(RouteInfo)]),
+    "ssm_debug_route_form": (_I, [_P, _I]),
+    "ssm_debug_route_rounds": (_I, [_P]),
+    "ssm_debug_route_tile": (_I, []),
+    "ssm_debug_route_batch": (_I, []),
     "ssm_relabel_params_default": (None, [C.POINTER(RelabelParams)]),
     "ssm_relabel_view_create": (_I, [_P, _P, _P, _I, _I, C.POINTER(Camera), C.POINTER(_P)]),
     "ssm_relabel_view_free": (None, [_P, _P]),

@@ -8,7 +8,7 @@ used in Mapper::viewer (src/mapper.cpp:154-155).
 import ctypes as C
 import numpy as np
 from . import _lib
-from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, ObjectsParams, ObjectsInfo, ClearanceParams, ClearanceInfo, RelabelParams, RelabelInfo, RelabelHostView
+from ._lib import Camera, Config, FramesDev, SeqOutDev, SgbmParams, VoParams, StereoFramesDev, StereoOutDev, TrackerParams, UvdParams, UvdInfo, VocabTrainParams, VocabTrainReport, MotionFuseParams, MotionFuseInfo, SorParams, SorInfo, CarveParams, CarveInfo, RenderParams, RenderInfo, RenderCompareInfo, AlignParams, AlignInfo, GridParams, GridInfo, ObjectsParams, ObjectsInfo, ClearanceParams, ClearanceInfo, RouteParams, RouteInfo, RoutePathInfo, RelabelParams, RelabelInfo, RelabelHostView
 
 KEYPOINT_DTYPE = np.dtype([("x", "f4"), ("y", "f4"), ("size", "f4"), ("angle", "f4"), ("response", "f4"),
                            ("octave", "i4"), ("class_id", "i4")])
@@ -463,6 +463,77 @@ def clearance_cells_host(cls, **params):
     if rc != 0:
         raise SsmError(rc, lib.ssm_last_error(None).decode())
     return d2, near, reach, _clearance_info(I)
+
+
+ROUTE_INFO_FIELDS = ("routed", "unrouted", "near_cells", "max_cost", "far_cell", "source_cell", "comfort2", "moves")
+ROUTE_PATH_INFO_FIELDS = ("len", "goal_cell", "cost", "n_axial", "n_diag", "near_steps", "min_d2")
+ROUTE_FIELDS = ("moves", "near_weight", "comfort", "cell")
+COST_NONE = 0xFFFFFFFF
+
+
+def route_params(**kw):
+    """the route field's parameters (ssm_route_params): the library's defaults (ssm_route_params_default) with the given fields replaced"""
+    bad = set(kw) - set(ROUTE_FIELDS)
+    if bad:
+        raise TypeError("unknown route parameters: " + ", ".join(sorted(bad)))
+    P = RouteParams()
+    _lib.load().ssm_route_params_default(C.byref(P))
+    for k, v in kw.items():
+        setattr(P, k, float(v) if k in ("comfort", "cell") else int(v))
+    return P
+
+
+def _route_info(I):
+    return {k: getattr(I, k) for k in ROUTE_INFO_FIELDS}
+
+
+def _route_path_info(I):
+    return {k: getattr(I, k) for k in ROUTE_PATH_INFO_FIELDS}
+
+
+def _route_inputs(reach, dist2, source):
+    """-> (reach uint8, dist2 uint32, the source as a cell index or -1); source: None, an index or (cx, cy)"""
+    r = np.ascontiguousarray(reach, np.uint8); d = np.ascontiguousarray(dist2, np.uint32)
+    if r.ndim != 2 or d.shape != r.shape:
+        raise ValueError("two ny x nx arrays of one grid")
+    if source is None:
+        return r, d, -1
+    if isinstance(source, (tuple, list)):
+        return r, d, int(source[1]) * r.shape[1] + int(source[0])
+    return r, d, int(source)
+
+
+def route_cells_host(reach, dist2, source=None, **params):
+    """the route field on the CPU (ssm_route_cells_host, no GPU) from the ny x nx reach and dist2 images of a clearance map and the source cell (None, an index or
+    (cx, cy)) -> (cost uint32, parent int32, info)"""
+    r, d, src = _route_inputs(reach, dist2, source)
+    ny, nx = r.shape
+    P = route_params(**params); I = RouteInfo()
+    cost = np.zeros((ny, nx), np.uint32); parent = np.full((ny, nx), -2, np.int32)
+    lib = _lib.load()
+    rc = lib.ssm_route_cells_host(_ptr(r), _ptr(d), nx, ny, src, C.byref(P), _ptr(cost), _ptr(parent), C.byref(I))
+    if rc != 0:
+        raise SsmError(rc, lib.ssm_last_error(None).decode())
+    return cost, parent, _route_info(I)
+
+
+def route_path_host(cost, parent, dist2, goal, goal_snap=0, max_path=None, **params):
+    """a path on the CPU (ssm_route_path_host) from a field's ny x nx cost and parent images and the clearance map's dist2 to the goal (cx, cy) -> (the path's cell
+    indices int32, source first, path info).  A path longer than max_path (default: the cells of the grid) raises SsmError with code SSM_E_CAPACITY; its `info`
+    attribute holds the path info"""
+    c = np.ascontiguousarray(cost, np.uint32); p = np.ascontiguousarray(parent, np.int32); d = np.ascontiguousarray(dist2, np.uint32)
+    if c.ndim != 2 or p.shape != c.shape or d.shape != c.shape:
+        raise ValueError("three ny x nx arrays of one grid")
+    ny, nx = c.shape
+    max_path = nx * ny if max_path is None else int(max_path)
+    P = route_params(**params); I = RoutePathInfo()
+    cells = np.full(max(max_path, 1), -2, np.int32)
+    lib = _lib.load()
+    rc = lib.ssm_route_path_host(_ptr(c), _ptr(p), _ptr(d), nx, ny, C.byref(P), int(goal[0]), int(goal[1]), int(goal_snap), max_path, _ptr(cells), C.byref(I))
+    if rc != 0:
+        e = SsmError(rc, lib.ssm_last_error(None).decode()); e.info = _route_path_info(I)
+        raise e
+    return cells[:I.len].copy(), _route_path_info(I)
 
 
 RELABEL_INFO_FIELDS = ("n_in", "n_supported", "n_voted", "n_changed", "n_filled", "pairs_supported", "pairs_voted")
@@ -1690,6 +1761,67 @@ class Context:
         d2 = np.zeros((ny, nx), np.uint32); near = np.full((ny, nx), -2, np.int32); reach = np.full((ny, nx), 255, np.uint8)
         self._chk(self.lib.ssm_clearance_fetch(self.h, target, _ptr(d2), _ptr(near), _ptr(reach)))
         return d2, near, reach
+
+    def route_target(self, nx, ny, max_path=None):
+        """the device field and path arrays of the route field for grids of up to nx * ny cells and paths of up to max_path cells (default 4 (nx + ny))
+        (ssm_route_target_create) -> an opaque handle (route_target_free it)"""
+        max_path = 4 * (int(nx) + int(ny)) if max_path is None else int(max_path)
+        t = C.c_void_p()
+        self._chk(self.lib.ssm_route_target_create(self.h, int(nx), int(ny), max_path, C.byref(t)))
+        self._route_sizes = getattr(self, "_route_sizes", {})
+        self._route_sizes[t.value] = (None, max_path)
+        return t.value
+
+    def route_target_free(self, target):
+        self._route_sizes.pop(target, None)
+        self.lib.ssm_route_target_free(self.h, target)
+
+    def route_form(self, form):
+        """how later fields relax (ssm_debug_route_form): 0 sweeps of one thread per cell in batches, 1 active tiles relaxed to their fixed points, -1 the default"""
+        self._chk(self.lib.ssm_debug_route_form(self.h, int(form)))
+
+    def route_rounds(self):
+        """how many times the last field asked the device whether it was done (ssm_debug_route_rounds)"""
+        return self.lib.ssm_debug_route_rounds(self.h)
+
+    def route_field(self, clearance_target, target, **params):
+        """the route field over the clearance target's last result (ssm_route_field) -> info"""
+        P = route_params(**params); I = RouteInfo()
+        self._chk(self.lib.ssm_route_field(self.h, clearance_target, C.byref(P), target, C.byref(I)))
+        self._route_sizes[target] = (self._clearance_sizes[clearance_target], self._route_sizes[target][1])
+        return _route_info(I)
+
+    def route_cells(self, target, reach, dist2, source=None, **params):
+        """hand-made ny x nx reach and dist2 images uploaded and the stage run on them (ssm_debug_route_cells); source: None, a cell index or (cx, cy) -> info"""
+        r, d, src = _route_inputs(reach, dist2, source)
+        ny, nx = r.shape
+        P = route_params(**params); I = RouteInfo()
+        self._chk(self.lib.ssm_debug_route_cells(self.h, target, _ptr(r), _ptr(d), nx, ny, src, C.byref(P), C.byref(I)))
+        self._route_sizes[target] = ((nx, ny), self._route_sizes[target][1])
+        return _route_info(I)
+
+    def route_path(self, target, goal, goal_snap=0):
+        """a path of the target's field to the goal (cx, cy) (ssm_route_path) -> (the path's cell indices int32, source first, path info).  A path longer than the
+        target's max_path raises SsmError with code SSM_E_CAPACITY; its `info` attribute holds the path info"""
+        I = RoutePathInfo()
+        cells = np.full(max(getattr(self, "_route_sizes", {}).get(target, (None, 1))[1], 1), -2, np.int32)          # (a handle this binding does not know: the library refuses it)
+        rc = self.lib.ssm_route_path(self.h, target, int(goal[0]), int(goal[1]), int(goal_snap), _ptr(cells), C.byref(I))
+        if rc != 0:
+            e = SsmError(rc, (self.lib.ssm_last_error(self.h) or b"").decode()); e.info = _route_path_info(I)
+            raise e
+        return cells[:I.len].copy(), _route_path_info(I)
+
+    def route_fetch(self, target, shape=None):
+        """the images of the target's field (ssm_route_fetch) -> (cost uint32, parent int32), ny x nx each.  shape: (nx, ny) of a field that was not made through this
+        binding (a call on the library itself); otherwise the binding remembers it"""
+        known = getattr(self, "_route_sizes", {}).get(target, (None, 1))[0]
+        if shape is None and known is None:
+            self._chk(self.lib.ssm_route_fetch(self.h, target, None, None))          # (no field, or a handle of another context: the library refuses with its own message)
+            raise ValueError("route_fetch: the field was not made through this binding; pass shape=(nx, ny)")
+        nx, ny = known if shape is None else (int(shape[0]), int(shape[1]))
+        cost = np.zeros((ny, nx), np.uint32); parent = np.full((ny, nx), -2, np.int32)
+        self._chk(self.lib.ssm_route_fetch(self.h, target, _ptr(cost), _ptr(parent)))
+        return cost, parent
 
     def relabel_view(self, depth, sem_bgr, camera=None):
         """a view of label fusion: the depth image goes to the device and the label image is made there from the semantic BGR image (ssm_relabel_view_create) -> an

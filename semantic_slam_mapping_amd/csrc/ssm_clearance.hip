@@ -13,7 +13,7 @@ static int clearance_target_ok(ssm_ctx* c, const ssm_clearance_target* t)
     return SSM_OK;
 }
 // the stage on a class image in device memory, from the first launch to the call's wait
-static int clearance_run(ssm_ctx* c, ssm_clearance_target* t, const uint8_t* cls, int nx, int ny, const Setup& S, ssm_clearance_info* info)
+static int clearance_run(ssm_ctx* c, ssm_clearance_target* t, const uint8_t* cls, int nx, int ny, double cell, const Setup& S, ssm_clearance_info* info)
 {
     ClearanceWork& W = c->clearance; hipStream_t s = c->main.stream;
     if (!W.info) { DALLOC(c, W.h_info, 8); DALLOC(c, W.info, 9); }
@@ -25,7 +25,7 @@ static int clearance_run(ssm_ctx* c, ssm_clearance_target* t, const uint8_t* cls
     static_assert(sizeof(ssm_clearance_info) == 64, "info is eight 64-bit counts");
     HIPCHK(c, hipMemcpyAsync(W.h_info, W.info, 64, hipMemcpyDeviceToHost, s));
     HIPCHK(c, hipStreamSynchronize(s));
-    t->staged = true; t->nx = nx; t->ny = ny;
+    t->staged = true; t->nx = nx; t->ny = ny; t->seed_cell = (int64_t)W.h_info[5]; t->cell = cell;          // (the seed and the cell size: what a route field starts from)
     if (info) memcpy(info, W.h_info, 64);
     return SSM_OK;
 }
@@ -60,7 +60,7 @@ extern "C" int ssm_clearance_grid(ssm_ctx* c, const ssm_grid_target* g, const ss
     Setup S;
     { const int r = clearance_check(c, P, g->nx, g->ny, g->params.cell, &S); if (r) return r; }
     if ((int64_t)g->nx * g->ny > t->cap) FAIL(c, SSM_E_INVAL, "clearance: the grid has more cells than the target");
-    return clearance_run(c, t, g->cls, g->nx, g->ny, S, info);
+    return clearance_run(c, t, g->cls, g->nx, g->ny, g->params.cell, S, info);
 }
 extern "C" int ssm_debug_clearance_cells(ssm_ctx* c, ssm_clearance_target* t, const uint8_t* cls, int nx, int ny, const ssm_clearance_params* params, ssm_clearance_info* info)
 {
@@ -76,7 +76,7 @@ extern "C" int ssm_debug_clearance_cells(ssm_ctx* c, ssm_clearance_target* t, co
     const size_t nc = (size_t)nx * ny;
     if ((int64_t)nc > W.in_cap) { HIPCHK(c, hipStreamSynchronize(s)); W.in_cap = 0; DALLOC(c, W.in_cls, nc); W.in_cap = (int64_t)nc; }
     HIPCHK(c, hipMemcpyAsync(W.in_cls, cls, nc, hipMemcpyHostToDevice, s));
-    return clearance_run(c, t, W.in_cls, nx, ny, S, info);
+    return clearance_run(c, t, W.in_cls, nx, ny, P.cell, S, info);
 }
 extern "C" int ssm_clearance_fetch(ssm_ctx* c, const ssm_clearance_target* t, uint32_t* dist2, int32_t* nearest, uint8_t* reach)
 {

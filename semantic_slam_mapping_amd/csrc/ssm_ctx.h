@@ -219,9 +219,24 @@ struct ObjectsWork {
     DevBuf<uint8_t> in_cls, in_label; DevBuf<int32_t> in_ground, in_top; DevBuf<uint32_t> in_high; int64_t in_cap = 0;
 };
 // a clearance target (ssm_clearance.hip): the column pass's masks and rows, the images and the labels for up to cap cells; staged: a call has run (nx, ny: its grid)
+// seed_cell, cell: that call's seed (-1: none) and cell size, what a route field over it starts from (ssm_route.hip)
 struct ssm_clearance_target {
     int64_t cap = 0; int nx = 0, ny = 0, device = 0; const ssm_ctx* owner = nullptr; bool staged = false;
+    int64_t seed_cell = -1; double cell = 1.0;
     DevBuf<uint32_t> mask, dist2; DevBuf<int32_t> row, nearest, labels; DevBuf<uint8_t> reach;
+};
+// a route target (ssm_route.hip): the cells' bytes, the dist2 copy, the field and a path's cells for up to cap cells and max_path cells; flag, list: form 1's tile
+// marks and active list for tile_cap tiles (grown by the call that needs more).  fielded: a field has run (nx, ny, S, source: its grid, setup and source)
+struct ssm_route_target {
+    int64_t cap = 0, tile_cap = 0; int nx = 0, ny = 0, device = 0, max_path = 0; const ssm_ctx* owner = nullptr; bool fielded = false;
+    ssm_rtc::Setup S{}; int32_t source = -1;
+    DevBuf<uint8_t> in; DevBuf<uint32_t> dist2, cost; DevBuf<int32_t> parent, path, rev, flag, list;
+};
+// workspace of the route field: the info (and the far key behind it), the path info (and the goal's key behind it), the ring of active counts and form 0's changed
+// word (ctl[2]), the last field's rounds, the staging of ssm_debug_route_cells
+struct RouteWork {
+    DevBuf<unsigned long long> info, pinfo; PinBuf<unsigned long long> h_info, h_pinfo; DevBuf<int32_t> ctl; PinBuf<int32_t> h_ctl; int form = ROUTE_FORM_DEFAULT, rounds = 0;
+    DevBuf<uint8_t> in_reach; DevBuf<uint32_t> in_dist2; int64_t in_cap = 0;
 };
 // workspace of the clearance map: the info (and the seed's key behind it), the staging of ssm_debug_clearance_cells
 struct ClearanceWork { DevBuf<unsigned long long> info; PinBuf<unsigned long long> h_info; int form = CLEARANCE_FORM_DEFAULT; DevBuf<uint8_t> in_cls; int64_t in_cap = 0; };
@@ -327,6 +342,7 @@ struct ssm_ctx {
     GridWork grid;                                           // ground grid: likewise
     ObjectsWork objects;                                     // object extraction: likewise
     ClearanceWork clearance;                                 // clearance map: likewise
+    RouteWork route;                                         // route field: likewise
     RelabelWork relabel;                                     // label fusion: likewise
     CloudTableWork clouds;                                   // the cloud table and host-array staging of the three: likewise
     double vt_level_ms[10] = {0}, vt_total_ms = -1.0;     // wall time of the last ssm_vocab_train per level and in all (ssm_debug_vocab_train_times); < 0: none yet

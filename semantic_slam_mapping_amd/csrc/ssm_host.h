@@ -15,6 +15,7 @@
 #include "../../include/ssm/grid_core.h"
 #include "../../include/ssm/objects_core.h"
 #include "../../include/ssm/clearance_core.h"
+#include "../../include/ssm/route_core.h"
 #include "../../include/ssm/relabel_core.h"
 #include "../../include/ssm/pnp_core.h"
 #include "pnp_state.h"
@@ -155,6 +156,14 @@ SSM_HIDDEN CloudRule objects_cloud_rule();         // no cloud twice; fewer than
 // ---------------------------------------------------------------- clearance map (ssm_clearance_host.cpp)
 // the grid's size and the parameters a call may have (host function and device entry points alike); cell: the grid's cell size; S: what they become for clearance_core.h
 SSM_HIDDEN int clearance_check(ssm_ctx* c, const ssm_clearance_params& P, int nx, int ny, double cell, ssm_clrc::Setup* S);
+
+// ---------------------------------------------------------------- route field (ssm_route_host.cpp)
+// the grid's size and the parameters a call may have (host functions and device entry points alike); cell: the clearance map's cell size; S: what they become for
+// route_core.h.  The goal of a path query; the source of hand-made inputs (reach on the host); the path info of "no goal cell"
+SSM_HIDDEN int route_check(ssm_ctx* c, const ssm_route_params& P, int nx, int ny, double cell, ssm_rtc::Setup* S);
+SSM_HIDDEN int route_goal_check(ssm_ctx* c, int nx, int ny, int goal_cx, int goal_cy, int goal_snap);
+SSM_HIDDEN int route_source_check(ssm_ctx* c, const uint8_t* reach, int nx, int ny, int source_cell);
+SSM_HIDDEN void route_path_none(ssm_route_path_info* I);
 
 // ---------------------------------------------------------------- label fusion (ssm_relabel_host.cpp)
 // the number of views and the parameters a call may have (host function and device entry points alike)

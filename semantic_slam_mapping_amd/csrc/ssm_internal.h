@@ -303,6 +303,27 @@ int k_clearance_chunk();
 size_t k_clearance_mask_words(int nx, int ny);
 hipError_t k_clearance(const uint8_t* cls, int nx, int ny, const ssm_clrc::Setup& S, const ClearanceBufs& B, unsigned long long* info, int form, hipStream_t s);
 
+// route field (kernels_route.hip; the arithmetic is include/ssm/route_core.h) on nx x ny cells.  k_route_begin: every cell's byte (in), its dist2 copied (d2), cost
+// COST_NONE but 0 at the source (source < 0: none), the tile flags cleared, the active list the *n_first tiles of form 1's first round (the source's and its neighbours), info (9 x uint64: routed, unrouted,
+// near_cells, ..., [8] the far key) and ctl (2 x int32, the ring of active counts) zeroed.  k_route_sweeps: form 0, one batch of k_route_batch() sweeps; *changed is
+// cleared first and non-zero afterwards when a cost fell.  k_route_round: form 1, the n_active tiles of list relaxed to their fixed points, then the tiles their
+// rims woke compacted into list and counted in ctl[round & 1].  k_route_finish: parent, the counts and the far key.  k_route_path: the goal's snap and the walk --
+// pinfo: 8 x uint64, the seven counts of ssm_route_path_info and the goal's key; rev: the walk's cells, goal first; path: the same, source first (both max_path
+// entries).  Everything is queued on s, nothing waits.
+#include "../../include/ssm/route_core.h"
+enum { ROUTE_FORM_SWEEPS = 0, ROUTE_FORM_TILES = 1, ROUTE_FORM_DEFAULT = ROUTE_FORM_TILES };
+struct RouteBufs { uint8_t* in; uint32_t *d2, *cost; int32_t *parent, *flag, *list; };
+int k_route_tile();
+int k_route_batch();
+int64_t k_route_tiles(int nx, int ny);
+hipError_t k_route_begin(const uint8_t* reach, const uint32_t* dist2, int nx, int ny, int32_t source, const ssm_rtc::Setup& S, const RouteBufs& B, unsigned long long* info, int32_t* ctl,
+                         int* n_first, hipStream_t s);
+hipError_t k_route_sweeps(int nx, int ny, const ssm_rtc::Setup& S, const RouteBufs& B, int32_t* changed, hipStream_t s);
+hipError_t k_route_round(int nx, int ny, const ssm_rtc::Setup& S, const RouteBufs& B, int n_active, int round, int32_t* ctl, hipStream_t s);
+hipError_t k_route_finish(int nx, int ny, int32_t source, const ssm_rtc::Setup& S, const RouteBufs& B, unsigned long long* info, hipStream_t s);
+hipError_t k_route_path(int nx, int ny, const ssm_rtc::Setup& S, const RouteBufs& B, int goal_cx, int goal_cy, int goal_snap, int max_path, int32_t* rev, int32_t* path,
+                        unsigned long long* pinfo, hipStream_t s);
+
 // label fusion (kernels_relabel.hip; the arithmetic is include/ssm/relabel_core.h): A.v views vote on the labels of the n points at pts, which change in place
 // (the 4 label bytes of a changed point).  votes, new_label: every point's record, n entries; info: 6 x uint64 (n_supported, n_voted, n_changed, n_filled,
 // pairs_supported, pairs_voted), cleared by the launcher.  form: RELABEL_FORM_IMAGES reads a view's depth and label images (View::depth, View::label),

@@ -43,6 +43,9 @@
 // `exp_mapping <parameters> --clearance [DIR]` (or mapper_clearance=1, mapper_clearance_dir=DIR): after the ground grid (and the objects), Mapper computes the grid's
 // clearance map (include/ssm/mapper.h); with DIR clearance.png, reach.png and clearance.txt are written there.  The summary line then carries, after
 // every other field, `clearance_blocked B clearance_traversable T clearance_reachable R clearance_max_d2 M clearance_fnv H`: H is FNV-1a over dist2, nearest and reach.
+// `exp_mapping <parameters> --route [DIR]` (or mapper_route=1, mapper_route_dir=DIR): after the clearance map Mapper computes the route field over it and one path
+// (include/ssm/mapper.h); with DIR route.png, route_cost.png and route.txt are written there.  The summary line then carries, after every other field,
+// `route_routed N route_max_cost C route_path_len L route_path_cost P route_fnv H`: H is FNV-1a over cost, parent and the path's cells.
 // `exp_mapping <parameters> --grid [DIR]` (or mapper_grid=1, mapper_grid_dir=DIR): when the viewer ends, Mapper builds ONE ground grid from every key-frame's cloud at
 // its map pose (include/ssm/mapper.h); with DIR grid_colour.png, grid_height.png and grid.txt are written there.  The summary line then carries
 // `grid_cells C grid_drivable D grid_walkable W grid_obstacle O grid_fnv H`: the cells of the grid, three of its class counts, and FNV-1a over nx, ny and the fetched
@@ -184,6 +187,12 @@ int main(int argc, char** argv)
         if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_clearance_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
     }
     if (clearance) parameterReader.set("mapper_clearance", "1");
+    bool route = parameterReader.getData<int>("mapper_route", 0) != 0;
+    for (int i = 2; i < argc; i++) if (string(argv[i]) == "--route") {
+        route = true;
+        if (i + 1 < argc && argv[i + 1][0] != '-') parameterReader.set("mapper_route_dir", argv[i + 1]);          // (the directory is optional: without it no file is written)
+    }
+    if (route) parameterReader.set("mapper_route", "1");
     bool relabel = parameterReader.getData<int>("mapper_relabel", 0) != 0;
     for (int i = 2; i < argc; i++) if (string(argv[i]) == "--relabel") relabel = true;
     if (relabel) { parameterReader.set("mapper_relabel", "1"); parameterReader.set("mapper_relabel_hash", "1"); }
@@ -544,6 +553,18 @@ int main(int argc, char** argv)
             eat(d2.data(), d2.size() * 4); eat(nearest.data(), nearest.size() * 4); eat(reach.data(), reach.size());
             cout << " clearance_blocked " << K.counts.blocked << " clearance_traversable " << K.counts.traversable << " clearance_reachable " << K.counts.reachable << " clearance_max_d2 "
                  << K.counts.max_d2_reachable << " clearance_fnv " << hex << h << dec;
+        }
+        if (route) {          // (the viewer thread routed right after the clearance map as it ended; these fields come after every other, the clearance map's included)
+            if (mapper.viewerFailed) { cerr << "exp_mapping: the viewer stopped before the route field was made" << endl; return 3; }
+            const Mapper::RouteInfo& R = mapper.routeInfo();
+            vector<uint32_t> cost; vector<int32_t> parent;
+            mapper.routeFetch(&cost, &parent);
+            const vector<int32_t>& path = mapper.routePath();
+            uint64_t h = 0xCBF29CE484222325ull;           // FNV-1a over cost, parent and the path
+            auto eat = [&h](const void* p, size_t bytes) { const unsigned char* b = (const unsigned char*)p; for (size_t k = 0; k < bytes; k++) { h ^= b[k]; h *= 0x100000001B3ull; } };
+            eat(cost.data(), cost.size() * 4); eat(parent.data(), parent.size() * 4); eat(path.data(), path.size() * 4);
+            cout << " route_routed " << R.counts.routed << " route_max_cost " << R.counts.max_cost << " route_path_len " << R.path.len << " route_path_cost " << R.path.cost << " route_fnv "
+                 << hex << h << dec;
         }
         cout << endl;
     } catch (const exception& e) { cerr << RED << "exp_mapping: " << e.what() << RESET << endl; return 2; }

@@ -232,7 +232,7 @@ int ssm_objects_fetch(ssm_ctx*, const ssm_objects_target* t, ssm_object* out, in
 }
 // the clearance map (Mapper with mapper_clearance=1): a "target" is the host images, the linked host function in the device entry point's place (the cell size the
 // grid build's, as on the device)
-struct ssm_clearance_target { int64_t cap; int nx, ny; std::vector<uint32_t> d2; std::vector<int32_t> near; std::vector<uint8_t> reach; };
+struct ssm_clearance_target { int64_t cap; int nx, ny; std::vector<uint32_t> d2; std::vector<int32_t> near; std::vector<uint8_t> reach; int64_t seed_cell = -1; double cell = 1.0; };
 int ssm_clearance_target_create(ssm_ctx*, int nx, int ny, ssm_clearance_target** out)
 {
     if (!out || nx < 1 || ny < 1 || (int64_t)nx * ny > ((int64_t)1 << 24)) return SSM_E_INVAL;
@@ -246,8 +246,9 @@ int ssm_clearance_grid(ssm_ctx*, const ssm_grid_target* g, const ssm_clearance_p
     P.cell = g->P.cell;
     const size_t nc = (size_t)g->nx * g->ny;
     std::vector<uint32_t> d2(nc); std::vector<int32_t> near(nc); std::vector<uint8_t> reach(nc);
-    const int rc = ssm_clearance_cells_host(g->cls.data(), g->nx, g->ny, &P, d2.data(), near.data(), reach.data(), info);
-    if (rc == SSM_OK) { t->nx = g->nx; t->ny = g->ny; t->d2.swap(d2); t->near.swap(near); t->reach.swap(reach); }
+    ssm_clearance_info I;
+    const int rc = ssm_clearance_cells_host(g->cls.data(), g->nx, g->ny, &P, d2.data(), near.data(), reach.data(), &I);
+    if (rc == SSM_OK) { t->nx = g->nx; t->ny = g->ny; t->d2.swap(d2); t->near.swap(near); t->reach.swap(reach); t->seed_cell = I.seed_cell; t->cell = P.cell; if (info) *info = I; }
     return rc;
 }
 int ssm_clearance_fetch(ssm_ctx*, const ssm_clearance_target* t, uint32_t* dist2, int32_t* nearest, uint8_t* reach)
@@ -257,6 +258,39 @@ int ssm_clearance_fetch(ssm_ctx*, const ssm_clearance_target* t, uint32_t* dist2
     if (dist2) memcpy(dist2, t->d2.data(), nc * 4);
     if (nearest) memcpy(nearest, t->near.data(), nc * 4);
     if (reach) memcpy(reach, t->reach.data(), nc);
+    return SSM_OK;
+}
+// the route field (Mapper with mapper_route=1): a "target" is the host field with the copy of dist2 a path query needs, the linked host functions in the device
+// entry points' place (the cell size and the source the clearance call's, as on the device)
+struct ssm_route_target { int64_t cap; int nx, ny, max_path; ssm_route_params P; std::vector<uint32_t> cost, d2; std::vector<int32_t> parent; };
+int ssm_route_target_create(ssm_ctx*, int nx, int ny, int max_path, ssm_route_target** out)
+{
+    if (!out || nx < 1 || ny < 1 || (int64_t)nx * ny > ((int64_t)1 << 24) || max_path < 1) return SSM_E_INVAL;
+    ssm_route_target* t = new ssm_route_target(); t->cap = (int64_t)nx * ny; t->nx = t->ny = 0; t->max_path = max_path; ssm_route_params_default(&t->P); *out = t; return SSM_OK;
+}
+void ssm_route_target_free(ssm_ctx*, ssm_route_target* t) { delete t; }
+int ssm_route_field(ssm_ctx*, const ssm_clearance_target* ct, const ssm_route_params* params, ssm_route_target* t, ssm_route_info* info)
+{
+    if (!ct || !t || ct->nx < 1 || (int64_t)ct->nx * ct->ny > t->cap) return SSM_E_INVAL;
+    ssm_route_params P; ssm_route_params_default(&P); if (params) P = *params;
+    P.cell = ct->cell;
+    const size_t nc = (size_t)ct->nx * ct->ny;
+    std::vector<uint32_t> cost(nc); std::vector<int32_t> parent(nc);
+    const int rc = ssm_route_cells_host(ct->reach.data(), ct->d2.data(), ct->nx, ct->ny, (int)ct->seed_cell, &P, cost.data(), parent.data(), info);
+    if (rc == SSM_OK) { t->nx = ct->nx; t->ny = ct->ny; t->P = P; t->cost.swap(cost); t->parent.swap(parent); t->d2 = ct->d2; }
+    return rc;
+}
+int ssm_route_path(ssm_ctx*, ssm_route_target* t, int goal_cx, int goal_cy, int goal_snap, int32_t* cells_out, ssm_route_path_info* path_info)
+{
+    if (!t || t->nx < 1 || !cells_out || !path_info) return SSM_E_INVAL;
+    return ssm_route_path_host(t->cost.data(), t->parent.data(), t->d2.data(), t->nx, t->ny, &t->P, goal_cx, goal_cy, goal_snap, t->max_path, cells_out, path_info);
+}
+int ssm_route_fetch(ssm_ctx*, const ssm_route_target* t, uint32_t* cost, int32_t* parent)
+{
+    if (!t || t->nx < 1) return SSM_E_INVAL;
+    const size_t nc = (size_t)t->nx * t->ny;
+    if (cost) memcpy(cost, t->cost.data(), nc * 4);
+    if (parent) memcpy(parent, t->parent.data(), nc * 4);
     return SSM_OK;
 }
 // label fusion (Mapper with mapper_relabel=1): a "view" is a host copy of the depth image and the label image, the linked host function in the device entry points' place
